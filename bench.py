@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BN256 G1 MSM throughput on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,7 +9,11 @@ A "step" is one best_multiexp over the global array: every rank runs the MSM of 
 shard (2^24 points per GPU, inputs resident in HBM before the timed region), the 96-byte partial
 results are all-gathered over RCCL and folded on every rank.  Weak scaling: N=1 is the north
 star's 2^24 headline, N=4 is BASELINE config 5's 2^26.  Rank 0 prints ONE JSON line.
-Beside the weak-scaling `value` the line carries, at every N:
+A plain run does only what the headline needs: inputs, registration, W warm-up steps, the K timed
+steps, the known-answer check of their result, the line.  --dump-outputs DIR then writes the last
+timed step's result as DIR/msm_result.npy (dump_outputs()).  Every side measurement below runs
+with --full only; the --no-* switches and --replay select among them there.
+With --full, beside the weak-scaling `value` the line carries, at every N:
   strong_scaling   BASELINE configs[4] as written -- ONE global 2^26-point MSM (and one global 2^24) split by index
                    range over the N ranks: ms per MSM (max over ranks), points/s, known answer of the folded result
   one_process      (N > 1) the form the reference's prover would use -- ONE process for the node
@@ -28,8 +32,8 @@ Objects of the full record:
                 32 B scalar + 64 B affine base, each read once) x points per launch / the
                 launch's duration from HIP events on its own stream (hm_get_msm_stats).
                 traffic / valu_issue: PMC counters measured IN THE RUN by three child processes of
-                this script under `rocprofv3 --pmc` (N = 1; --no-live-pmc or no rocprofv3: the
-                committed profiles/<tag>_baked_counters.json, flagged stale when the kernels changed).
+                this script under `rocprofv3 --pmc` (N = 1 with --full; a plain run, --no-live-pmc or no
+                rocprofv3: the committed profiles/<tag>_baked_counters.json, flagged stale when the kernels changed).
   ntt           2^24 Fr NTT on one GPU (64 B/element algorithmic), same treatment.
   cpu_baseline  oracle/cpu_ref.c (C restatement of halo2_proofs v2023_02_02's best_multiexp) timed
                 on this box's host cores on a bounded sample of the same workload (rank 0, N=1).
@@ -268,6 +272,16 @@ def emit(full: dict, extras_out: str):
     else:
         sys.stdout.flush()
         os.write(_REAL_STDOUT_FD, (text + "\n").encode())
+
+
+def dump_outputs(out_dir: str, **arrays):
+    """--dump-outputs: what the timed path returned in its last step, one DIR/<name>.npy per array.  The arrays are uint64
+    words (a G1 point: x, y, z as 4 Montgomery limbs each); every word is stored as its (low, high) 32-bit halves in float64,
+    which holds them exactly: shape (..., 2), word = low + high * 2^32."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        w = np.ascontiguousarray(a, dtype=np.uint64)
+        np.save(os.path.join(out_dir, name + ".npy"), np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=-1).astype(np.float64))
 
 
 def rand_fr(n, seed, device):
@@ -519,7 +533,7 @@ def live_pmc(log_points, log_ntt, with_ntt):
     out = {}
     tmp = tempfile.mkdtemp(prefix="hm_pmc_", dir="/tmp")
     try:
-        child = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--log-points", str(log_points), "--log-ntt",
+        child = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "2", "--warmup", "1", "--log-points", str(log_points), "--log-ntt",
                  str(log_ntt), "--no-cpu-baseline", "--replay", "none", "--no-extras", "--no-strong", "--no-live-pmc", "--no-collective", "--extras-out", "none"] + ([] if with_ntt else ["--no-ntt"])
         env = dict(os.environ, TMPDIR="/tmp")
         for group in (["FETCH_SIZE"], ["WRITE_SIZE"], ["SQ_INSTS_VALU", "GRBM_GUI_ACTIVE"]):
@@ -858,6 +872,8 @@ def main_one_process(args):
         ok = bool(np.array_equal(result, expected))
         if not ok:
             raise SystemExit("bench.py --one-process: the MSM result does not match the known answer [sum s_i (a + i b)]G")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, msm_result=result)
         h.release_bases(handle)
         del scalars
         torch.cuda.empty_cache()
@@ -888,7 +904,10 @@ def main_one_process(args):
     emit(line, args.extras_out)
 
 
-def main():
+SIDE_LEG_SWITCHES = ("no_cpu_baseline", "no_ntt", "no_extras", "no_2_26", "no_live_pmc", "no_shares", "no_strong", "no_one_process")
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -899,7 +918,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ntt", action="store_true")
     ap.add_argument("--replay", default="merkle_sum_tree_k9,poseidon_k11,merkle_v3_k17,merkle_sum_tree_k18",
-                    help="comma-separated create_proof MSM/NTT traces to replay after the timed MSM steps ('none' to skip)")
+                    help="--full: comma-separated create_proof MSM/NTT traces to replay after the timed MSM steps ('none' to skip)")
     ap.add_argument("--no-extras", action="store_true", help="skip the prover-like and host-pointer MSM side measurements")
     ap.add_argument("--no-2-26", action="store_true", help="skip the global 2^26-point strong-scaling measurement")
     ap.add_argument("--no-live-pmc", action="store_true",
@@ -917,7 +936,23 @@ def main():
     ap.add_argument("--one-process", action="store_true",
                     help="ONE process drives --gpus devices through hm_set_msm_devices (launch WITHOUT torchrun): the whole benchmark in the "
                          "form the reference's single-process prover would use")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the side measurements as well (replays, NTT, CPU baselines, strong scaling, live PMC, "
+                         "one-process form; the --no-* switches and --replay select among them); without it only the headline runs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the result of the last timed step to DIR/msm_result.npy (float64, see dump_outputs())")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:                # a plain run: set-up, warm-up, the timed steps, the line -- no side leg
+        args.replay = "none"
+        for name in SIDE_LEG_SWITCHES:
+            setattr(args, name, True)
+    return args
+
+
+def main():
+    args = parse_args()
     guard_stdout()
     if args.one_process:
         return main_one_process(args)
@@ -1003,6 +1038,8 @@ def main():
     answer_ok = answer_ok and bool(np.array_equal(result, expected_global))     # the timed steps' own result
     if not answer_ok:
         raise SystemExit("bench.py: the MSM result does not match the known answer [sum s_i (a + i b)]G")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, msm_result=result)
 
     # ---- the create_proof replays (configs[1..3] and the reference's own k = 9), FIRST among the side legs: with the headline's base
     # set and scalars still resident (12.5 GiB of 288: nothing is freed here).  Why first: freeing GiBs of device memory -- what the

@@ -152,3 +152,26 @@ def test_a_box_without_a_working_one_rank_communicator_keeps_its_headline():
         bench.COLLECTIVE.update(saved)
         if dist.is_initialized():
             dist.destroy_process_group()
+
+
+def test_a_plain_run_has_no_side_leg_and_full_keeps_every_switch():
+    """Without --full every side leg is off whatever else the command line says; with it the --no-* switches and --replay hold."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2", "--replay", "poseidon_k11"])
+    assert plain.steps == 5 and plain.warmup == 2 and not plain.full and plain.dump_outputs is None
+    assert plain.replay == "none" and all(getattr(plain, name) is True for name in bench.SIDE_LEG_SWITCHES)
+    full = bench.parse_args(["--full", "--no-ntt", "--replay", "poseidon_k11", "--dump-outputs", "out"])
+    assert full.replay == "poseidon_k11" and full.no_ntt and full.dump_outputs == "out"
+    assert not any(getattr(full, name) for name in bench.SIDE_LEG_SWITCHES if name != "no_ntt")
+    import pytest
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dumped_words_come_back_exactly(tmp_path):
+    import numpy as np
+    words = np.array([0, 1, 0xFFFFFFFF, 1 << 32, (1 << 64) - 1, 0x30644E72E131A029] * 2, dtype=np.uint64)
+    bench.dump_outputs(str(tmp_path / "d"), msm_result=words)
+    out = np.load(tmp_path / "d" / "msm_result.npy")
+    assert out.dtype == np.float64 and out.shape == (12, 2) and out.max() < 2 ** 32
+    assert np.array_equal(out[:, 0].astype(np.uint64) + (out[:, 1].astype(np.uint64) << np.uint64(32)), words)

@@ -31,7 +31,7 @@ def _bench(world, log_points, replay="none", extra=(), extras=False):
     import tempfile
     fd, extras_out = tempfile.mkstemp(prefix="hm_bench_extras_", suffix=".json", dir="/tmp")
     os.close(fd)
-    args = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--log-points", str(log_points), "--no-cpu-baseline", "--no-ntt",
+    args = ["--full", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--log-points", str(log_points), "--no-cpu-baseline", "--no-ntt",
             "--replay", replay, "--no-2-26", "--extras-out", extras_out] + ([] if extras else ["--no-extras"]) + list(extra)
     if "--live-pmc" in args:
         args.remove("--live-pmc")
@@ -160,3 +160,36 @@ def test_pmc_counters_are_measured_in_the_run():
     assert rf["traffic"] > 96 * (1 << 20)                       # at least the algorithmic bytes of 2^20 points
     assert rf["valu_issue"]["stale"] is False and rf["valu_issue"]["sq_insts_valu_per_launch"] > 0
     assert 1000 < rf["valu_issue"]["wave_instr_per_64_units"] < 4000        # ~2 200 wave-instructions per 64 mixed additions
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_headline_only_and_dumps_its_result(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the K timed steps and the line, no side leg; --dump-outputs writes the
+    last step's result, which is the known answer [sum s_i (a + i b)]G of the seeded inputs, word for word."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from halo2_experiments_amd.sharding import g1_sum
+    extras, dump = tmp_path / "extras.json", tmp_path / "dump"
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("HALO2_BENCH_BACKEND", "MASTER_PORT", "RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-points", "18",
+                        "--extras-out", str(extras), "--dump-outputs", str(dump)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
+    assert r.returncode == 0, r.stderr[-3000:]
+    (text,) = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    line = json.loads(text)
+    full = json.loads(extras.read_text())
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["known_answer_ok"] is True and line["ranks_in_collective"] == 1
+    assert abs(line["value"] - (1 << 18) / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    for leg in ("create_proof_replay", "ntt", "strong_scaling", "cpu_baseline", "one_process", "msm_prover_like", "msm_plain_bases",
+                "msm_pipelined_3_in_flight", "msm_host_pointer"):
+        assert leg not in full, leg
+    assert full["time_budget"]["legs_wall_s"] == {} and full["time_budget"]["dropped"] == []
+    out = np.load(dump / "msm_result.npy")
+    assert out.dtype == np.float64 and out.shape == (12, 2) and os.listdir(dump) == ["msm_result.npy"]
+    words = out[:, 0].astype(np.uint64) + (out[:, 1].astype(np.uint64) << np.uint64(32))
+    dev = torch.device("cuda", 0)
+    s, _, t = bench.bench_inputs(1 << 18, 0, bench.BENCH_SEED, dev)
+    assert words[8:].any() and np.array_equal(words, g1_sum(bench.known_answer(s, t, dev).reshape(1, 12)))

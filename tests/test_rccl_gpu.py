@@ -164,7 +164,7 @@ def test_bench_at_one_gpu_counts_its_ranks_with_an_rccl_all_reduce(tmp_path):
     assert line["config"]["collective"].startswith("rccl all-gather") and line["known_answer_ok"] is True
     assert full["time_budget"]["dropped"] == [] and full["time_budget"]["budget_s"] == 300.0
     # a budget that is already spent drops every side leg and keeps the headline
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--log-points", "18",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--log-points", "18",
                         "--no-cpu-baseline", "--no-live-pmc", "--replay", "poseidon_k11", "--time-budget", "0.001",
                         "--extras-out", str(extras)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-3000:]
