@@ -5,7 +5,7 @@ There is no Rust toolchain in this image, so the device-resident half of the Rus
 module is its twin, method for method: every method below makes the C-ABI call its Rust namesake makes -- the same entry point,
 the same argument order, NULL stream, host arrays where the Rust passes slices -- through ``sys``, a recorder over the
 library that counts calls by name.  No torch, no HIP binding: device memory comes from ``hm_device_malloc`` exactly as a Rust
-prover's would.  tests/test_rust_glue_gpu.py extracts the ``sys::hm_*`` names from the .rs file and holds this module (and a whole
+prover's would.  tests/test_rust_glue.py extracts the ``sys::hm_*`` names from the .rs file and holds this module (and a whole
 k = 18 proof driven through it, ``run_proof``) to that list: what ``run_proof`` measures is what a prover adopting that file gets.
 
 Reference boundary: /root/reference/src/circuits/utils.rs:40-48 (create_proof) over halo2_proofs v2023_02_02.

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Apply the halo2_proofs edits of this directory to a checkout of privacy-scaling-explorations/halo2 at tag v2023_02_02
-(what /root/reference/Cargo.toml:10 pins) -- the same edits as halo2_proofs.patch, from the same table (edits.json,
-generated by tools/gen_rust_shim.py), but found as literal LINES instead of line numbers:
+(what /root/reference/Cargo.toml:10 pins) -- the same edits as halo2_proofs.patch, from the same table (edits.json, the
+table's source, maintained by hand; tools/gen_rust_shim.py builds the patch from it), but found as literal LINES instead of
+line numbers:
 
     python3 apply_edits.py <halo2 checkout>/halo2_proofs          # edit in place
     python3 apply_edits.py --dry-run <...>/halo2_proofs           # say what would change

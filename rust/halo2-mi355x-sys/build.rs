@@ -1,4 +1,4 @@
-// GENERATED by tools/gen_rust_shim.py
+// Maintained by hand (tools/gen_rust_shim.py generates only src/lib.rs of this crate)
 // HALO2_MI355X_LIB_DIR = <this repository>/halo2-experiments_amd/csrc (where `make` leaves libhalo2_mi355x.so)
 fn main() {
     let dir = std::env::var("HALO2_MI355X_LIB_DIR")

@@ -1,5 +1,5 @@
 //! mi355x.rs -- glue between halo2_proofs::arithmetic and libhalo2_mi355x.so (added by rust/halo2_proofs.patch).
-//! GENERATED by tools/gen_rust_shim.py (a fixed template: the C entry points it calls are checked against the header
+//! Maintained by hand (not generated: the sys:: items it uses are checked against the header
 //! by the repository's tests).  The two functions return None / false whenever the GPU path does not apply or fails
 //! WITHOUT having touched the caller's arrays, and the caller falls through to the untouched upstream body: other
 //! curves / fields, tiny inputs, no device, any error code but HM_ERR_PARTIAL_OUTPUT (which panics: see try_best_fft).
@@ -21,6 +21,10 @@ use crate::arithmetic::Group;
 
 /// Below these sizes the host-pointer round trip (launch + PCIe latency) is no faster than the CPU body: measured
 /// crossover against a 16-core host, stay on the CPU.
+// MEASURED (tools/crossover.py on the MI355X box against oracle/cpu_ref.c on its 16 granted cores; table in DESIGN.md
+// section 8 and profiles/r04_crossover.json).  MSM: 0.30 ms against 1.4 ms (16 threads) / 5.4 ms (1 thread) at 2^8, the
+// smallest size measured.  NTT: 0.057 ms against 0.111 ms on one thread at 2^10; 2^9 is a tie, 2^8 loses.
+// bench.py reads both values from the two lines below: keep their spelling.
 pub const GPU_MIN_LOG_N_MSM: u32 = 8;
 pub const GPU_MIN_LOG_N_NTT: u32 = 10;
 

@@ -1,5 +1,5 @@
 //! mi355x_dev.rs -- polynomials that STAY in HBM between the steps of create_proof (added by rust/apply_edits.py next to mi355x.rs,
-//! declared in arithmetic.rs).  GENERATED by tools/gen_rust_shim.py.
+//! declared in arithmetic.rs).  Maintained by hand.
 //!
 //! The drop-in edits (mi355x.rs, mi355x_kzg.rs) leave every polynomial in a host Vec, so each best_fft / coeff_to_extended moves its
 //! array over PCIe twice: 122-292 ms of the k = 18 proof against 34 ms of device time.  This module is the

@@ -1,5 +1,5 @@
 //! mi355x_kzg.rs -- ParamsKZG's side of the binding (added by rust/halo2_proofs.patch / rust/apply_edits.py next to
-//! mi355x.rs, declared in arithmetic.rs).  GENERATED by tools/gen_rust_shim.py.
+//! mi355x.rs, declared in arithmetic.rs).  Maintained by hand.
 //!
 //! create_proof commits ~56 times per MerkleSumTree proof (/root/reference/src/circuits/utils.rs:40-48), always against
 //! the same two arrays, params.g and params.g_lagrange.  The free-function drop-in (mi355x.rs) re-reads the whole base

@@ -208,9 +208,14 @@ def test_rust_bindings_agree_with_the_header_in_arity_and_types():
 
 
 def test_generated_rust_files_are_up_to_date():
-    """rust/ and the extern block of INTEGRATION.md are outputs of tools/gen_rust_shim.py: regenerate and compare."""
+    """rust/halo2-mi355x-sys/src/lib.rs and the extern block of INTEGRATION.md (from the header) and rust/halo2_proofs.patch
+    (from the glue modules and rust/edits.json) are outputs of tools/gen_rust_shim.py: regenerate and compare.  The glue
+    modules themselves are maintained by hand; every sys:: item they use must be declared by the header."""
     gen = _gen()
-    for path, text in gen.generate().items():
+    generated = gen.generate()
+    assert {os.path.relpath(p, gen.ROOT) for p in generated} == {"rust/halo2-mi355x-sys/src/lib.rs", "rust/halo2_proofs.patch",
+                                                                 "INTEGRATION.md"}
+    for path, text in generated.items():
         assert os.path.exists(path), f"{path} missing: run tools/gen_rust_shim.py"
         assert open(path).read() == text, f"{os.path.relpath(path)} is stale: run tools/gen_rust_shim.py"
     patch = open(os.path.join(gen.RUST_DIR, "halo2_proofs.patch")).read()
@@ -218,6 +223,12 @@ def test_generated_rust_files_are_up_to_date():
     glue = open(os.path.join(gen.RUST_DIR, "halo2_proofs-patch", "src", "mi355x.rs")).read()
     for fn in re.findall(r"sys::(hm_\w+)", glue):         # the glue only calls entry points the header declares
         assert fn in declared_symbols(), fn
+    _, _, defines = gen.parse_header(open(_lib.HEADER_PATH).read())
+    declared = set(declared_symbols()) | {n for n, _ in defines} | {"last_error"}     # lib.rs adds last_error()
+    for name in ("mi355x.rs", "mi355x_kzg.rs", "mi355x_dev.rs"):
+        text = open(os.path.join(gen.RUST_DIR, "halo2_proofs-patch", "src", name)).read()
+        used = set(re.findall(r"sys::(\w+)", text))
+        assert used and used <= declared, f"{name} uses sys:: items the header does not declare: {sorted(used - declared)}"
 
 
 def test_header_is_plain_c(tmp_path):

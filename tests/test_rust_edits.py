@@ -160,7 +160,7 @@ def test_glue_is_free_of_the_risks_the_review_named():
 
 def test_the_device_glue_cannot_cost_the_drop_in_its_build():
     """mi355x_dev.rs (264 lines that have never met rustc) was compiled for every user of the drop-in patch.  Now behind a
-    cargo feature; every generated module carries its own lint allowance (the crate denies missing_docs / missing_debug_implementations
+    cargo feature; every glue module carries its own lint allowance (the crate denies missing_docs / missing_debug_implementations
     / unsafe_code as recalled); none depends on the ff version's `one()`."""
     table = json.load(open(os.path.join(RUST, "edits.json")))
     arith = next(e for e in table if e["file"] == "src/arithmetic.rs" and "best_multiexp" in e["anchor"])
