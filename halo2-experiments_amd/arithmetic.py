@@ -456,6 +456,54 @@ def g1_fixed_base_mul(scalars, base_xy: np.ndarray):
     return out
 
 
+def _fr_one(value, name: str) -> np.ndarray:
+    w = _np(value, 4, name)
+    if w.shape[0] != 1:
+        raise ValueError(f"{name} must be one field element")
+    return w
+
+
+def g1_fft(points, omega, log_n: int, scale=None) -> None:
+    """``best_fft::<G1>`` on a GPU tensor of (n, 8) affine Montgomery words ((0, 0) = identity), in place:
+    a[i] <- sum_j [omega^(ij)] a[j], then a[i] <- [scale] a[i] when ``scale`` is given.  n = 2^log_n <= 2^24."""
+    w = _fr_one(omega, "omega")
+    sc = None if scale is None else _fr_one(scale, "scale")
+    if not _is_tensor(points):
+        raise TypeError("g1_fft: a GPU tensor of (n, 8) words is expected (g1_fft_host takes numpy Jacobian arrays)")
+    if _tensor_rows(points, 8, "points") != 1 << log_n:
+        raise ValueError("g1_fft: points.len() != 1 << log_n")
+    _lib.check(_lib.load().hm_g1_fft_bn256_dev(ctypes.c_void_p(points.data_ptr()), _ptr(w), log_n, None if sc is None else _ptr(sc),
+                                               ctypes.c_void_p(_stream_ptr(points))))
+
+
+def g1_fft_host(xyz: np.ndarray, omega, log_n: int, scale=None) -> None:
+    """The drop-in's form (``hm_g1_fft_bn256``): a numpy (n, 12) Jacobian array as bn256::G1 lays it out (z = 0: identity), in
+    place; outputs come back as (x, y, 1) / all zero."""
+    w = _fr_one(omega, "omega")
+    sc = None if scale is None else _fr_one(scale, "scale")
+    if not isinstance(xyz, np.ndarray):
+        raise TypeError("g1_fft_host transforms in place: pass a numpy array")
+    arr = _np(xyz, 12, "xyz", writable=True)
+    if arr.shape[0] != 1 << log_n:
+        raise ValueError("g1_fft_host: xyz.len() != 1 << log_n")
+    _lib.check(_lib.load().hm_g1_fft_bn256(_ptr(arr), _ptr(w), log_n, None if sc is None else _ptr(sc)))
+
+
+def g_to_lagrange(g, k: int):
+    """``halo2_proofs::arithmetic::g_to_lagrange``: the Lagrange basis [L_i(s)]G1 from the monomial points g[i] = [s^i]G1 (a (2^k, 8)
+    GPU tensor), as a new tensor.  omega^-1 = ROOT_OF_UNITY_INV squared S - k times, n^-1 = TWO_INV^k, as upstream computes them."""
+    from .domain import FR_MODULUS, FR_ROOT_OF_UNITY, FR_S, fr_words
+
+    r = FR_MODULUS
+    omega_inv = pow(FR_ROOT_OF_UNITY, -1, r)
+    for _ in range(k, FR_S):
+        omega_inv = omega_inv * omega_inv % r
+    n_inv = pow(pow(2, -1, r), k, r)
+    out = g.clone()
+    g1_fft(out, fr_words(omega_inv), k, fr_words(n_inv))
+    return out
+
+
 def random_fr(n: int, seed: int, device=None, shape=None):
     """``n`` field elements uniform over the WHOLE of [0, r) (``Fr::random``) as an (n, 4) int64 device tensor -- ``shape`` reshapes,
     e.g. (columns, rows, 4).  hm_fr_random_dev: one xoshiro256** stream per element seeded from (seed, index), 254-bit candidates

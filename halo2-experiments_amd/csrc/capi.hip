@@ -2064,6 +2064,40 @@ int hm_g1_fixed_base_mul_dev(const void* d_scalars, size_t n, const uint64_t bas
   return g1_fixed_base_mul_run(*ctx, (const uint32_t*)d_scalars, n, base_xy, (uint32_t*)d_out_xy, (hipStream_t)stream);
 } HM_API_CATCH("hm_g1_fixed_base_mul_dev")
 
+int hm_g1_fft_bn256_dev(void* d_points_xy, const uint64_t omega[4], uint32_t log_n, const uint64_t* scale, void* stream) try {
+  if (!d_points_xy || !omega) return hm_fail(HM_ERR_BAD_ARG, "hm_g1_fft_bn256_dev: null argument");
+  if (log_n > 24) return hm_fail(HM_ERR_BAD_ARG, "hm_g1_fft_bn256_dev: log_n > 24");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return g1_fft_run(*ctx, (uint32_t*)d_points_xy, 16, omega, log_n, scale, (hipStream_t)stream);
+} HM_API_CATCH("hm_g1_fft_bn256_dev")
+
+int hm_g1_fft_bn256(uint64_t* points_xyz, const uint64_t omega[4], uint32_t log_n, const uint64_t* scale) try {
+  if (!points_xyz || !omega) return hm_fail(HM_ERR_BAD_ARG, "hm_g1_fft_bn256: null argument");
+  if (log_n > 24) return hm_fail(HM_ERR_BAD_ARG, "hm_g1_fft_bn256: log_n > 24");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  hm_fault_point("g1_fft_upload");
+  const size_t bytes = ((size_t)96) << log_n;
+  void* d_p = ctx->io.ensure(bytes);
+  if (!d_p) return hm_fail(HM_ERR_HIP, "hm_g1_fft_bn256: staging allocation failed");
+  int rc = xfer_h2d(*ctx, d_p, points_xyz, bytes, "hm_g1_fft_bn256: upload");
+  if (rc != HM_OK) return rc;
+  rc = g1_fft_run(*ctx, (uint32_t*)d_p, 24, omega, log_n, scale, nullptr);
+  if (rc != HM_OK) return rc;
+  HM_HIP_CHECK(hipStreamSynchronize(nullptr));
+  hm_fault_point("g1_fft_download");
+  // from here on `points_xyz` is being overwritten: a failure is NOT one a caller may answer by running its CPU body on it
+  if (xfer_d2h(*ctx, points_xyz, d_p, bytes, "hm_g1_fft_bn256") != HM_OK)
+    return hm_fail(HM_ERR_PARTIAL_OUTPUT, "hm_g1_fft_bn256: copying the result back failed, the array is partly overwritten: " +
+                                              hm_last_error_string());
+  ctx->calls.h2d_bytes += bytes;
+  ctx->calls.d2h_bytes += bytes;
+  return HM_OK;
+} HM_API_CATCH("hm_g1_fft_bn256")
+
 #ifdef HM_FAULT_INJECTION
 // test build only (libhalo2_mi355x_fi.so; not declared in the public header): the (after + 1)-th passage through the
 // named fault point throws std::runtime_error; point == NULL disarms

@@ -428,5 +428,9 @@ int msm_precompute(uint32_t* d_table, const uint8_t* d_inf, size_t n, uint32_t c
 void host_sum_points(const uint64_t* pts, size_t count, uint64_t out_jac_ext[12], int* out_is_identity);
 int g1_fixed_base_mul_run(DeviceCtx& ctx, const uint32_t* d_scalars_ext, size_t n, const uint64_t base_affine_ext[8],
                           uint32_t* d_out_affine_ext, hipStream_t stream);
+// best_fft over G1 in place on n = 2^log_n <= 2^24 points of `words` u32 each: 16 affine external ((0, 0) = identity) or 24
+// Jacobian external (z = 0 = identity; outputs (x, y, 1) / zeros).  scale_ext: optional Fr Montgomery words multiplied into every output.
+int g1_fft_run(DeviceCtx& ctx, uint32_t* d_points, uint32_t words, const uint64_t omega_ext[4], uint32_t log_n,
+               const uint64_t* scale_ext, hipStream_t stream);
 
 }  // namespace hm

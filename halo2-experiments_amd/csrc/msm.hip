@@ -26,6 +26,7 @@
 
 #include "hm_internal.h"
 #include "host_fq.h"
+#include "host_fr.h"
 #include "msm_dev.h"
 
 namespace hm {
@@ -1672,6 +1673,8 @@ __global__ __launch_bounds__(ACC_THREADS) void g1_fixed_base_mul_kernel(const ui
   o[3] = make_uint4(oy[4], oy[5], oy[6], oy[7]);
 }
 
+#include "g1_fft.inc"   // best_fft over G1: g1_fft_run below
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -2454,6 +2457,56 @@ int g1_fixed_base_mul_run(DeviceCtx& ctx, const uint32_t* d_scalars_ext, size_t 
                      stream, d_scalars_ext, (const uint32_t*)d_table, d_out_affine_ext, n);
   HM_HIP_CHECK(hipGetLastError());
   return aux_release(ctx, slot, stream);
+}
+
+// best_fft over G1 (g1_fft.inc), in place on `d_points`: WORDS = 16 u32 per point (affine external, (0, 0) = identity) or 24
+// (Jacobian external, z = 0 = identity; written back as (x, y, 1) / zeros).  The working buffer (n Jacobian records) and the
+// twiddle table (n / 2 canonical omega^j) are allocated per call, stream-ordered on `stream`, and freed behind the last kernel.
+int g1_fft_run(DeviceCtx& ctx, uint32_t* d_points, uint32_t words, const uint64_t omega_ext[4], uint32_t log_n,
+               const uint64_t* scale_ext, hipStream_t stream) {
+  (void)ctx;
+  if (log_n > G1_FFT_LOG_MAX) return hm_fail(HM_ERR_BAD_ARG, "g1_fft: log_n > 24");
+  if (words != 16 && words != 24) return hm_fail(HM_ERR_BAD_ARG, "g1_fft: point layout must be 16 or 24 words");
+  const size_t n = (size_t)1 << log_n, half = n / 2;
+  G1FftScale scale{};
+  if (scale_ext) {
+    const host::Fr4 one_int = {{1, 0, 0, 0}};
+    const host::Fr4 v = host::fr_mul(host::fr_load(scale_ext), one_int);    // Montgomery words -> canonical integer
+    std::memcpy(scale.w, v.l, 32);
+    scale.on = 1;
+  }
+  const size_t work_bytes = n * PT_WORDS * 4, tw_bytes = half * 32;
+  void* mem = nullptr;
+  HM_HIP_CHECK(hipMallocAsync(&mem, work_bytes + tw_bytes, stream));
+  uint32_t* work = (uint32_t*)mem;
+  uint32_t* tw = work + n * PT_WORDS;
+  const dim3 all((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS)), pairs((uint32_t)((half + ACC_THREADS - 1) / ACC_THREADS));
+  int rc = HM_OK;
+  if (half) {
+    rc = fr_powers_run(tw, half, omega_ext, stream);
+    if (rc == HM_OK) {
+      hipLaunchKernelGGL(g1_fft_twiddle_kernel, dim3((uint32_t)((half + 255) / 256)), dim3(256), 0, stream, tw, half);
+      if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: twiddle kernel launch failed");
+    }
+  }
+  if (rc == HM_OK) {
+    if (words == 16) hipLaunchKernelGGL(g1_fft_load_kernel<16>, all, dim3(ACC_THREADS), 0, stream, d_points, work, log_n);
+    else hipLaunchKernelGGL(g1_fft_load_kernel<24>, all, dim3(ACC_THREADS), 0, stream, d_points, work, log_n);
+    if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: load kernel launch failed");
+  }
+  for (uint32_t s = 0; rc == HM_OK && s < log_n; ++s) {
+    if (log_n - 1 - s >= 6) hipLaunchKernelGGL(g1_fft_stage_kernel<true>, pairs, dim3(ACC_THREADS), 0, stream, work, tw, log_n, s);
+    else hipLaunchKernelGGL(g1_fft_stage_kernel<false>, pairs, dim3(ACC_THREADS), 0, stream, work, tw, log_n, s);
+    if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: stage kernel launch failed");
+  }
+  if (rc == HM_OK) {
+    if (words == 16) hipLaunchKernelGGL(g1_fft_store_kernel<16>, all, dim3(ACC_THREADS), 0, stream, work, d_points, log_n, scale);
+    else hipLaunchKernelGGL(g1_fft_store_kernel<24>, all, dim3(ACC_THREADS), 0, stream, work, d_points, log_n, scale);
+    if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: store kernel launch failed");
+  }
+  const hipError_t fe = hipFreeAsync(mem, stream);
+  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("g1_fft: hipFreeAsync: ") + hipGetErrorString(fe));
+  return rc;
 }
 
 }  // namespace hm

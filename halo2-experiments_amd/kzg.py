@@ -6,6 +6,8 @@ calls ``ParamsKZG::<Bn256>::setup(k, OsRng)`` at /root/reference/src/circuits/ut
     commit(poly)           best_multiexp(poly, g[..len])           (coefficient form)
     commit_lagrange(poly)  best_multiexp(poly, g_lagrange[..len])  (evaluation form)
     write(f) / read(f)     the SRS on disk, so that it is loaded instead of regenerated every run
+    from_monomial(k, g)    g alone (a powers-of-tau SRS): g_lagrange = g_to_lagrange(g, k), an inverse FFT over G1
+    downsize(k)            truncate g, recompute g_lagrange, re-register both sets
 
 All G1 work runs on the GPU through the C ABI: the scalar ladder (``hm_fr_powers_dev``), the Lagrange scalars
 (one scaled inverse NTT of the ladder: L_i(s) = n^-1 sum_j s^j omega^(-ij)), the 2 n fixed-base multiplications
@@ -27,8 +29,8 @@ from typing import BinaryIO, Optional
 import numpy as np
 
 from . import _lib
-from .arithmetic import (FQ_MODULUS, G1_GENERATOR, BasesHandle, _ptr, _stream_ptr, best_multiexp, best_multiexp_submit,
-                         best_multiexp_wait, g1_fixed_base_mul, register_bases, release_bases)
+from .arithmetic import (FQ_MODULUS, G1_GENERATOR, BasesHandle, _is_tensor, _ptr, _stream_ptr, best_multiexp, best_multiexp_submit,
+                         best_multiexp_wait, g1_fixed_base_mul, g_to_lagrange, register_bases, release_bases)
 from .domain import FR_MODULUS, EvaluationDomain, fr_words
 
 _P = FQ_MODULUS
@@ -96,6 +98,7 @@ class ParamsKZG:
         """``g`` / ``g_lagrange``: (n, 8) GPU tensors or numpy arrays of affine Montgomery words."""
         self.k, self.n = k, 1 << k
         self.g2, self.s_g2 = g2, s_g2
+        self._precompute = precompute
         self._g_h = register_bases(g, precompute=precompute)
         self._gl_h = register_bases(g_lagrange, precompute=precompute)
         if len(self._g_h) != self.n or len(self._gl_h) != self.n:
@@ -120,6 +123,45 @@ class ParamsKZG:
         if keep_points:
             params.g_points, params.g_lagrange_points = g, g_lagrange
         return params
+
+    # -- from a universal SRS / ParamsKZG::downsize -------------------------------------------------------
+    @staticmethod
+    def _device_points(points, device=None):
+        import torch
+
+        if _is_tensor(points):
+            return points.contiguous()
+        device = device or torch.device("cuda", torch.cuda.current_device())
+        arr = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+        return torch.from_numpy(arr.view(np.int64)).to(device)
+
+    @classmethod
+    def from_monomial(cls, k: int, g, g2: bytes, s_g2: bytes, precompute: bool = False) -> "ParamsKZG":
+        """Parameters from the monomial points g[i] = [s^i]G1 alone (a powers-of-tau SRS, s unknown): g_lagrange is derived on the
+        GPU by ``g_to_lagrange`` (one inverse FFT over G1), and both sets are registered as the constructor does."""
+        g = cls._device_points(g)
+        if g.shape[0] != 1 << k:
+            raise ValueError("ParamsKZG.from_monomial: g must hold 2^k points")
+        g_lagrange = g_to_lagrange(g, k)
+        params = cls(k, g, g_lagrange, g2, s_g2, precompute=precompute)
+        params.g_points, params.g_lagrange_points = g, g_lagrange
+        return params
+
+    def downsize(self, k: int) -> None:
+        """``ParamsKZG::downsize``: keep the first 2^k monomial points, recompute g_lagrange from them, and replace both registered
+        sets.  Needs the affine points (setup(..., keep_points=True), read() or from_monomial())."""
+        if k > self.k:
+            raise ValueError("ParamsKZG.downsize: k exceeds the current size")
+        if not hasattr(self, "g_points"):
+            raise ValueError("ParamsKZG.downsize: the affine points were not kept (setup(..., keep_points=True))")
+        n = 1 << k
+        g = self._device_points(self.g_points)[:n].contiguous()
+        g_lagrange = g_to_lagrange(g, k)
+        g_h, gl_h = register_bases(g, precompute=self._precompute), register_bases(g_lagrange, precompute=self._precompute)
+        self.release()
+        self._g_h, self._gl_h = g_h, gl_h
+        self.k, self.n = k, n
+        self.g_points, self.g_lagrange_points = g, g_lagrange
 
     def release(self) -> None:
         for name in ("_g_h", "_gl_h"):

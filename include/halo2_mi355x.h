@@ -470,6 +470,19 @@ int hm_fr_distribute_powers_dev(void* d_a, size_t n, const uint64_t c3[12], void
  * scalars: n x 4 u64 device; out: n x 8 u64 device. */
 int hm_g1_fixed_base_mul_dev(const void* d_scalars, size_t n, const uint64_t base_xy[8], void* d_out_xy, void* stream);
 
+/* ---- best_fft over G1: stands in for halo2_proofs::arithmetic::best_fft::<bn256::G1> (g_to_lagrange, ParamsKZG::downsize) */
+
+/* Device form: n = 2^log_n affine points (n x 8 u64 Montgomery, (0,0) = identity -- the layout hm_register_bases reads and
+ * hm_g1_fixed_base_mul_dev writes), a[i] <- sum_j [omega^(ij)] a[j] in place, asynchronous on `stream`; then, when `scale`
+ * is not NULL, every output is multiplied by it.  omega, scale: Fr Montgomery words as for hm_ntt_bn256_fr_dev; omega a
+ * 2^log_n-th root of unity; log_n <= 24.  Working memory is allocated per call, stream-ordered on `stream`. */
+int hm_g1_fft_bn256_dev(void* d_points_xy, const uint64_t omega[4], uint32_t log_n, const uint64_t* scale, void* stream);
+
+/* Host form: n x 12 u64 Jacobian (x, y, z) as bn256::G1 lays them out, any z (z == 0: identity), in place; outputs
+ * normalised to (x, y, 1) / (0, 0, 0) like hm_msm_bn256_g1_jacobian.  `points_xyz` is written only by the final copy from
+ * the device: every error code but HM_ERR_PARTIAL_OUTPUT (that copy itself failed) leaves it exactly as it was. */
+int hm_g1_fft_bn256(uint64_t* points_xyz, const uint64_t omega[4], uint32_t log_n, const uint64_t* scale);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 
 typedef struct hm_msm_stats {

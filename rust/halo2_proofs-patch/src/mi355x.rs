@@ -27,6 +27,10 @@ use crate::arithmetic::Group;
 // bench.py reads both values from the two lines below: keep their spelling.
 pub const GPU_MIN_LOG_N_MSM: u32 = 8;
 pub const GPU_MIN_LOG_N_NTT: u32 = 10;
+/// best_fft over G1 (g_to_lagrange, ParamsKZG::downsize): every butterfly is a 254-bit scalar multiplication, so the GPU wins
+/// far earlier than for Fr.  ESTIMATE, not a measurement: no Rust toolchain has timed the CPU body against hm_g1_fft_bn256
+/// yet; re-measure the crossover when one does.
+pub const GPU_MIN_LOG_N_G1_FFT: u32 = 6;
 
 fn layout_check() -> bool {
     if std::mem::size_of::<Fr>() != 32 || std::mem::size_of::<G1Affine>() != 64 || std::mem::size_of::<G1>() != 96 {
@@ -72,6 +76,9 @@ pub fn try_best_multiexp<C: CurveAffine>(coeffs: &[C::Scalar], bases: &[C]) -> O
 }
 
 pub fn try_best_fft<G: Group>(a: &mut [G], omega: &G::Scalar, log_n: u32) -> bool {
+    if TypeId::of::<G>() == TypeId::of::<G1>() {
+        return try_best_fft_g1(a, omega, log_n);
+    }
     if TypeId::of::<G>() != TypeId::of::<Fr>() || log_n < GPU_MIN_LOG_N_NTT || log_n > 28 || !layout_ok() {
         return false;
     }
@@ -82,6 +89,29 @@ pub fn try_best_fft<G: Group>(a: &mut [G], omega: &G::Scalar, log_n: u32) -> boo
         panic!("hm_ntt_bn256_fr: {}", sys::last_error());
     }
     rc == sys::HM_OK // every other error code leaves `a` exactly as it was: the caller runs the CPU body
+}
+
+/// best_fft::<G1> (upstream's g_to_lagrange calls it with omega^-1 and scales afterwards): hm_g1_fft_bn256 on the Jacobian array
+/// in place, outputs normalised to (x, y, 1) with the identity mapped through g1_from_words to G1::identity().
+fn try_best_fft_g1<G: Group>(a: &mut [G], omega: &G::Scalar, log_n: u32) -> bool {
+    if TypeId::of::<G::Scalar>() != TypeId::of::<Fr>() || log_n < GPU_MIN_LOG_N_G1_FFT || log_n > 24 || !layout_ok() {
+        return false;
+    }
+    let rc = unsafe { sys::hm_g1_fft_bn256(a.as_mut_ptr() as *mut u64, omega as *const _ as *const u64, log_n, std::ptr::null()) };
+    if rc == sys::HM_ERR_PARTIAL_OUTPUT {
+        // as in the Fr branch: `a` is neither the input nor the output any more, the CPU body must not run on it
+        panic!("hm_g1_fft_bn256: {}", sys::last_error());
+    }
+    if rc != sys::HM_OK {
+        return false; // `a` untouched: the caller runs the CPU body
+    }
+    for p in a.iter_mut() {
+        // G == G1 here (TypeId-checked above; 96 bytes by layout_ok): identities come back as all-zero words
+        let xyz = unsafe { std::mem::transmute_copy::<G, [u64; 12]>(p) };
+        let q = g1_from_words(xyz);
+        *p = unsafe { std::mem::transmute_copy::<G1, G>(&q) };
+    }
+    true
 }
 
 /// R mod r: bn256::Fr::one() as the four Montgomery words the library reads (spelled out: no dependence on the ff version's `one()` / `ONE`).
