@@ -151,6 +151,12 @@ _SIGNATURES = {
     "hm_g1_fixed_base_mul_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, _vp, _vp]),
     "hm_g1_fft_bn256_dev": (ctypes.c_int, [_vp, _u64p, ctypes.c_uint32, _u64p, _vp]),
     "hm_g1_fft_bn256": (ctypes.c_int, [_u64p, _u64p, ctypes.c_uint32, _u64p]),
+    "hm_g1_compress_bn256_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp]),
+    "hm_g1_decompress_bn256_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _u64p, _vp]),
+    "hm_g1_check_bn256_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, _vp]),
+    "hm_g1_compress_bn256": (ctypes.c_int, [_u64p, ctypes.c_size_t, _vp]),
+    "hm_g1_decompress_bn256": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, _u64p]),
+    "hm_g1_check_bn256": (ctypes.c_int, [_u64p, ctypes.c_size_t, _u64p]),
     "hm_extended_to_coeff_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p, _u64p, _vp]),
     "hm_eval_polynomial_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32), _u64p, ctypes.c_size_t,
                                                        _u64p, _vp]),

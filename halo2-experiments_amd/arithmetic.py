@@ -504,6 +504,113 @@ def g_to_lagrange(g, k: int):
     return out
 
 
+# ---- SRS point encodings (ParamsKZG.read / write) ----------------------------------------------------------
+HM_ERR_INVALID_DATA = -7
+
+
+class InvalidPointError(ValueError):
+    """An encoding or point that does not decode to a curve point; ``index`` is the smallest such entry."""
+
+    def __init__(self, message: str, index: int):
+        super().__init__(message)
+        self.index = index
+
+
+def _codec_rc(rc: int, bad: ctypes.c_uint64, who: str) -> None:
+    if rc == HM_ERR_INVALID_DATA:
+        raise InvalidPointError(f"{who}: invalid point at index {bad.value}", bad.value)
+    _lib.check(rc)
+
+
+def _bytes_rows(t, name: str) -> int:
+    if not t.is_cuda:
+        raise ValueError(f"{name}: torch tensors must live on the GPU (the *_host forms take numpy arrays)")
+    if t.element_size() != 1 or not t.is_contiguous() or t.numel() % 32:
+        raise ValueError(f"{name}: need a contiguous uint8 tensor of 32-byte encodings")
+    return t.numel() // 32
+
+
+def g1_compress(points):
+    """Compressed G1 encodings (32 bytes: canonical x little-endian, bit 7 of byte 31 = parity of y; zeros = identity) of a GPU
+    tensor of (n, 8) affine Montgomery words ((0, 0) = identity), as a new (n, 32) uint8 tensor.  The points are not validated."""
+    import torch
+
+    if not _is_tensor(points):
+        raise TypeError("g1_compress: a GPU tensor of (n, 8) words is expected (g1_compress_host takes numpy arrays)")
+    n = _tensor_rows(points, 8, "points")
+    out = torch.empty((n, 32), dtype=torch.uint8, device=points.device)
+    _lib.check(_lib.load().hm_g1_compress_bn256_dev(ctypes.c_void_p(points.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
+                                                    ctypes.c_void_p(_stream_ptr(points))))
+    return out
+
+
+def g1_decompress(data):
+    """The inverse of ``g1_compress`` on a GPU uint8 tensor of n x 32 bytes: a new (n, 8) int64 tensor of affine Montgomery words.
+    Raises ValueError naming the smallest index whose x is not canonical or not the x of a curve point."""
+    import torch
+
+    if not _is_tensor(data):
+        raise TypeError("g1_decompress: a GPU uint8 tensor is expected (g1_decompress_host takes numpy arrays)")
+    n = _bytes_rows(data, "data")
+    out = torch.empty((n, 8), dtype=torch.int64, device=data.device)
+    bad = ctypes.c_uint64(0)
+    rc = _lib.load().hm_g1_decompress_bn256_dev(ctypes.c_void_p(data.data_ptr()), n, ctypes.c_void_p(out.data_ptr()), ctypes.byref(bad),
+                                                ctypes.c_void_p(_stream_ptr(data)))
+    _codec_rc(rc, bad, "g1_decompress")
+    return out
+
+
+def g1_check(points) -> None:
+    """``SerdeFormat::RawBytes``' validation of a GPU tensor of (n, 8) affine Montgomery words: every word < p and every point on
+    y^2 = x^3 + 3 or (0, 0).  Raises ValueError naming the smallest bad index."""
+    if not _is_tensor(points):
+        raise TypeError("g1_check: a GPU tensor of (n, 8) words is expected (g1_check_host takes numpy arrays)")
+    n = _tensor_rows(points, 8, "points")
+    bad = ctypes.c_uint64(0)
+    rc = _lib.load().hm_g1_check_bn256_dev(ctypes.c_void_p(points.data_ptr()), n, ctypes.byref(bad), ctypes.c_void_p(_stream_ptr(points)))
+    _codec_rc(rc, bad, "g1_check")
+
+
+def _u8_rows(data, name: str) -> np.ndarray:
+    arr = np.asarray(data)
+    if arr.dtype != np.uint8:
+        raise TypeError(f"{name} must be uint8 bytes, got {arr.dtype}")
+    if arr.size % 32:
+        raise ValueError(f"{name}: size is not a multiple of 32 bytes")
+    return np.ascontiguousarray(arr).reshape(-1, 32)
+
+
+def g1_compress_host(points: np.ndarray) -> np.ndarray:
+    """``g1_compress`` on a numpy (n, 8) uint64 array through the host-pointer form: a new (n, 32) uint8 array."""
+    if _is_tensor(points):
+        raise TypeError("g1_compress_host takes numpy arrays (g1_compress takes GPU tensors)")
+    p = _np(points, 8, "points")
+    out = np.zeros((p.shape[0], 32), dtype=np.uint8)
+    _lib.check(_lib.load().hm_g1_compress_bn256(_ptr(p), p.shape[0], out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def g1_decompress_host(data: np.ndarray) -> np.ndarray:
+    """``g1_decompress`` on numpy bytes (n x 32 uint8): a new (n, 8) uint64 array."""
+    if _is_tensor(data):
+        raise TypeError("g1_decompress_host takes numpy arrays (g1_decompress takes GPU tensors)")
+    d = _u8_rows(data, "data")
+    out = np.zeros((d.shape[0], 8), dtype=np.uint64)
+    bad = ctypes.c_uint64(0)
+    rc = _lib.load().hm_g1_decompress_bn256(d.ctypes.data_as(ctypes.c_void_p), d.shape[0], _ptr(out), ctypes.byref(bad))
+    _codec_rc(rc, bad, "g1_decompress")
+    return out
+
+
+def g1_check_host(points: np.ndarray) -> None:
+    """``g1_check`` on a numpy (n, 8) uint64 array."""
+    if _is_tensor(points):
+        raise TypeError("g1_check_host takes numpy arrays (g1_check takes GPU tensors)")
+    p = _np(points, 8, "points")
+    bad = ctypes.c_uint64(0)
+    _codec_rc(_lib.load().hm_g1_check_bn256(_ptr(p), p.shape[0], ctypes.byref(bad)), bad, "g1_check")
+
+
 def random_fr(n: int, seed: int, device=None, shape=None):
     """``n`` field elements uniform over the WHOLE of [0, r) (``Fr::random``) as an (n, 4) int64 device tensor -- ``shape`` reshapes,
     e.g. (columns, rows, 4).  hm_fr_random_dev: one xoshiro256** stream per element seeded from (seed, index), 254-bit candidates

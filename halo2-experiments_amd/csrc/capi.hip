@@ -2098,6 +2098,103 @@ int hm_g1_fft_bn256(uint64_t* points_xyz, const uint64_t omega[4], uint32_t log_
   return HM_OK;
 } HM_API_CATCH("hm_g1_fft_bn256")
 
+// ---- SRS point encodings (g1_codec.inc) --------------------------------------------------------------------------------------
+static constexpr size_t G1_CODEC_MAX_N = (size_t)1 << 30;
+
+static int g1_codec_args(const char* who, size_t n, const void* in, const void* out, bool has_out, const uint64_t* first_invalid,
+                         bool has_flag) {
+  if ((n && (!in || (has_out && !out))) || (has_flag && !first_invalid)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (n > G1_CODEC_MAX_N) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": n > 2^30");
+  return HM_OK;
+}
+
+int hm_g1_compress_bn256_dev(const void* d_points_xy, size_t n, void* d_out32, void* stream) try {
+  if (int rc = g1_codec_args("hm_g1_compress_bn256_dev", n, d_points_xy, d_out32, true, nullptr, false)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return g1_compress_run((const uint32_t*)d_points_xy, n, (uint32_t*)d_out32, (hipStream_t)stream);
+} HM_API_CATCH("hm_g1_compress_bn256_dev")
+
+int hm_g1_decompress_bn256_dev(const void* d_in32, size_t n, void* d_points_xy, uint64_t* out_first_invalid, void* stream) try {
+  if (int rc = g1_codec_args("hm_g1_decompress_bn256_dev", n, d_in32, d_points_xy, true, out_first_invalid, true)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return g1_decompress_run((const uint32_t*)d_in32, n, (uint32_t*)d_points_xy, out_first_invalid, (hipStream_t)stream);
+} HM_API_CATCH("hm_g1_decompress_bn256_dev")
+
+int hm_g1_check_bn256_dev(const void* d_points_xy, size_t n, uint64_t* out_first_invalid, void* stream) try {
+  if (int rc = g1_codec_args("hm_g1_check_bn256_dev", n, d_points_xy, nullptr, false, out_first_invalid, true)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return g1_check_run((const uint32_t*)d_points_xy, n, out_first_invalid, (hipStream_t)stream);
+} HM_API_CATCH("hm_g1_check_bn256_dev")
+
+// Host forms: input and output share one staging buffer (input first); the caller's output is written only by the last copy.
+int hm_g1_compress_bn256(const uint64_t* points_xy, size_t n, uint8_t* out32) try {
+  if (int rc = g1_codec_args("hm_g1_compress_bn256", n, points_xy, out32, true, nullptr, false)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  if (n == 0) return HM_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  hm_fault_point("g1_codec_upload");
+  const size_t in_bytes = n * 64, out_bytes = n * 32;
+  uint8_t* d_p = (uint8_t*)ctx->io.ensure(in_bytes + out_bytes);
+  if (!d_p) return hm_fail(HM_ERR_HIP, "hm_g1_compress_bn256: staging allocation failed");
+  int rc = xfer_h2d(*ctx, d_p, points_xy, in_bytes, "hm_g1_compress_bn256: upload");
+  if (rc != HM_OK) return rc;
+  rc = g1_compress_run((const uint32_t*)d_p, n, (uint32_t*)(d_p + in_bytes), nullptr);
+  if (rc != HM_OK) return rc;
+  HM_HIP_CHECK(hipStreamSynchronize(nullptr));
+  hm_fault_point("g1_codec_download");
+  if (xfer_d2h(*ctx, out32, d_p + in_bytes, out_bytes, "hm_g1_compress_bn256") != HM_OK)
+    return hm_fail(HM_ERR_PARTIAL_OUTPUT, "hm_g1_compress_bn256: copying the result back failed, the output is partly written: " +
+                                              hm_last_error_string());
+  ctx->calls.h2d_bytes += in_bytes;
+  ctx->calls.d2h_bytes += out_bytes;
+  return HM_OK;
+} HM_API_CATCH("hm_g1_compress_bn256")
+
+int hm_g1_decompress_bn256(const uint8_t* in32, size_t n, uint64_t* points_xy, uint64_t* out_first_invalid) try {
+  if (int rc = g1_codec_args("hm_g1_decompress_bn256", n, in32, points_xy, true, out_first_invalid, true)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  *out_first_invalid = n;
+  if (n == 0) return HM_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  hm_fault_point("g1_codec_upload");
+  const size_t in_bytes = n * 32, out_bytes = n * 64;
+  uint8_t* d_p = (uint8_t*)ctx->io.ensure(in_bytes + out_bytes);
+  if (!d_p) return hm_fail(HM_ERR_HIP, "hm_g1_decompress_bn256: staging allocation failed");
+  int rc = xfer_h2d(*ctx, d_p, in32, in_bytes, "hm_g1_decompress_bn256: upload");
+  if (rc != HM_OK) return rc;
+  rc = g1_decompress_run((const uint32_t*)d_p, n, (uint32_t*)(d_p + in_bytes), out_first_invalid, nullptr);
+  if (rc != HM_OK) return rc;                     // HM_ERR_INVALID_DATA included: the caller's array is untouched
+  hm_fault_point("g1_codec_download");
+  if (xfer_d2h(*ctx, points_xy, d_p + in_bytes, out_bytes, "hm_g1_decompress_bn256") != HM_OK)
+    return hm_fail(HM_ERR_PARTIAL_OUTPUT, "hm_g1_decompress_bn256: copying the result back failed, the array is partly written: " +
+                                              hm_last_error_string());
+  ctx->calls.h2d_bytes += in_bytes;
+  ctx->calls.d2h_bytes += out_bytes;
+  return HM_OK;
+} HM_API_CATCH("hm_g1_decompress_bn256")
+
+int hm_g1_check_bn256(const uint64_t* points_xy, size_t n, uint64_t* out_first_invalid) try {
+  if (int rc = g1_codec_args("hm_g1_check_bn256", n, points_xy, nullptr, false, out_first_invalid, true)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  *out_first_invalid = n;
+  if (n == 0) return HM_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  hm_fault_point("g1_codec_upload");
+  const size_t bytes = n * 64;
+  void* d_p = ctx->io.ensure(bytes);
+  if (!d_p) return hm_fail(HM_ERR_HIP, "hm_g1_check_bn256: staging allocation failed");
+  int rc = xfer_h2d(*ctx, d_p, points_xy, bytes, "hm_g1_check_bn256: upload");
+  if (rc != HM_OK) return rc;
+  ctx->calls.h2d_bytes += bytes;
+  return g1_check_run((const uint32_t*)d_p, n, out_first_invalid, nullptr);
+} HM_API_CATCH("hm_g1_check_bn256")
+
 #ifdef HM_FAULT_INJECTION
 // test build only (libhalo2_mi355x_fi.so; not declared in the public header): the (after + 1)-th passage through the
 // named fault point throws std::runtime_error; point == NULL disarms

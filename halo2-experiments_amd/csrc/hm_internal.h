@@ -432,5 +432,10 @@ int g1_fixed_base_mul_run(DeviceCtx& ctx, const uint32_t* d_scalars_ext, size_t 
 // Jacobian external (z = 0 = identity; outputs (x, y, 1) / zeros).  scale_ext: optional Fr Montgomery words multiplied into every output.
 int g1_fft_run(DeviceCtx& ctx, uint32_t* d_points, uint32_t words, const uint64_t omega_ext[4], uint32_t log_n,
                const uint64_t* scale_ext, hipStream_t stream);
+// SRS point encodings (g1_codec.inc): 16-word affine external points <-> 8-word compressed encodings.  compress is asynchronous;
+// decompress / check wait for `stream` and answer HM_ERR_INVALID_DATA with the smallest invalid index in *first_invalid (n if none).
+int g1_compress_run(const uint32_t* d_xy, size_t n, uint32_t* d_out32, hipStream_t stream);
+int g1_decompress_run(const uint32_t* d_in32, size_t n, uint32_t* d_xy, uint64_t* first_invalid, hipStream_t stream);
+int g1_check_run(const uint32_t* d_xy, size_t n, uint64_t* first_invalid, hipStream_t stream);
 
 }  // namespace hm

@@ -9,6 +9,10 @@
 
 #include "g1.h"
 
+namespace hm {
+#include "g1_codec.inc"   // the per-point SRS codec formulas (its kernels are HIP-only)
+}
+
 using namespace hm;
 
 namespace {
@@ -309,6 +313,31 @@ int hc_fr_vector_bounds_closure(const uint64_t* a_ext, const uint64_t* b_ext, do
   (void)fe_canonical(fe_reduce_small(o0));
   (void)fe_canonical(fe_mul(o1, z));
   return ok;
+}
+
+// The SRS codec (g1_codec.inc) on n entries, the exact per-point code of its kernels.  op 0: compress (16 words in, 8 out);
+// 1: decompress (8 words in, 16 out); 2: check (16 words in).  valid[i] = 1 / 0.  The tracked bounds are data-independent (every
+// input enters through fe_unpack / fe_from_ext at the 2^256 class), so one valid point of each y parity proves them for all inputs.
+void hc_g1_codec(int op, const uint32_t* in, uint32_t* out, int* valid, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    uint32_t a[8], b[8], o1[8], o2[8];
+    if (op == 1) {
+      std::memcpy(a, in + 8 * i, 32);
+      valid[i] = g1_decompress_one(a, o1, o2) ? 1 : 0;
+      std::memcpy(out + 16 * i, o1, 32);
+      std::memcpy(out + 16 * i + 8, o2, 32);
+      continue;
+    }
+    std::memcpy(a, in + 16 * i, 32);
+    std::memcpy(b, in + 16 * i + 8, 32);
+    if (op == 0) {
+      g1_compress_one(a, b, o1);
+      std::memcpy(out + 8 * i, o1, 32);
+      valid[i] = 1;
+    } else {
+      valid[i] = g1_check_one(a, b) ? 1 : 0;
+    }
+  }
 }
 
 }  // extern "C"

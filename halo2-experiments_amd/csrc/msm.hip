@@ -1674,6 +1674,7 @@ __global__ __launch_bounds__(ACC_THREADS) void g1_fixed_base_mul_kernel(const ui
 }
 
 #include "g1_fft.inc"   // best_fft over G1: g1_fft_run below
+#include "g1_codec.inc" // SRS point encodings: g1_compress_run / g1_decompress_run / g1_check_run below
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -2507,6 +2508,59 @@ int g1_fft_run(DeviceCtx& ctx, uint32_t* d_points, uint32_t words, const uint64_
   const hipError_t fe = hipFreeAsync(mem, stream);
   if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("g1_fft: hipFreeAsync: ") + hipGetErrorString(fe));
   return rc;
+}
+
+// SRS point encodings (g1_codec.inc).  Compression is asynchronous on `stream`.
+int g1_compress_run(const uint32_t* d_xy, size_t n, uint32_t* d_out32, hipStream_t stream) {
+  if (n == 0) return HM_OK;
+  hipLaunchKernelGGL(g1_compress_kernel, dim3((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS)), dim3(ACC_THREADS), 0, stream, d_xy,
+                     d_out32, n);
+  HM_HIP_CHECK(hipGetLastError());
+  return HM_OK;
+}
+
+// The validating kernels lower one device word (allocated per call, stream-ordered, all ones) to the smallest invalid index; this waits for
+// `stream`, reads it back and answers HM_ERR_INVALID_DATA with *first_invalid set, or HM_OK with *first_invalid = n.
+template <class Launch>
+static int g1_codec_validating_run(const char* who, size_t n, uint64_t* first_invalid, hipStream_t stream, Launch launch) {
+  *first_invalid = n;
+  if (n == 0) return HM_OK;
+  void* mem = nullptr;
+  HM_HIP_CHECK(hipMallocAsync(&mem, sizeof(unsigned long long), stream));
+  unsigned long long* flag = (unsigned long long*)mem;
+  unsigned long long bad = ~0ull;
+  int rc = HM_OK;
+  const hipError_t me = hipMemsetAsync(flag, 0xff, sizeof(bad), stream);
+  if (me != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": hipMemsetAsync: " + hipGetErrorString(me));
+  if (rc == HM_OK) {
+    launch(dim3((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS)), flag);
+    if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": kernel launch failed");
+  }
+  if (rc == HM_OK) {
+    const hipError_t ce = hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, stream);
+    if (ce != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": reading the flag: " + hipGetErrorString(ce));
+  }
+  const hipError_t fe = hipFreeAsync(mem, stream);
+  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": hipFreeAsync: " + hipGetErrorString(fe));
+  const hipError_t se = hipStreamSynchronize(stream);
+  if (rc == HM_OK && se != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": " + hipGetErrorString(se));
+  if (rc == HM_OK && bad < n) {
+    *first_invalid = bad;
+    rc = hm_fail(HM_ERR_INVALID_DATA, std::string(who) + ": invalid point at index " + std::to_string(bad));
+  }
+  return rc;
+}
+
+int g1_decompress_run(const uint32_t* d_in32, size_t n, uint32_t* d_xy, uint64_t* first_invalid, hipStream_t stream) {
+  return g1_codec_validating_run("g1_decompress", n, first_invalid, stream, [&](dim3 grid, unsigned long long* flag) {
+    hipLaunchKernelGGL(g1_decompress_kernel, grid, dim3(ACC_THREADS), 0, stream, d_in32, d_xy, n, flag);
+  });
+}
+
+int g1_check_run(const uint32_t* d_xy, size_t n, uint64_t* first_invalid, hipStream_t stream) {
+  return g1_codec_validating_run("g1_check", n, first_invalid, stream, [&](dim3 grid, unsigned long long* flag) {
+    hipLaunchKernelGGL(g1_check_kernel, grid, dim3(ACC_THREADS), 0, stream, d_xy, n, flag);
+  });
 }
 
 }  // namespace hm

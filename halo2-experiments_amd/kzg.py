@@ -14,11 +14,15 @@ All G1 work runs on the GPU through the C ABI: the scalar ladder (``hm_fr_powers
 (``hm_g1_fixed_base_mul_dev``), and the two base sets stay registered on the device.  The single G2 scalar
 multiplication of ``s_g2`` is host integer arithmetic (one point, a few milliseconds).
 
-On-disk layout (little-endian, exactly the bytes the Rust types hold -- Montgomery limbs):
-    u32 k | n x 64 B g | n x 64 B g_lagrange | 128 B g2 | 128 B s_g2          (G2Affine = x.c0, x.c1, y.c0, y.c1)
-which is the field order of upstream's ``ParamsKZG::write`` with raw (uncompressed Montgomery) points
-[UPSTREAM-RECALLED: later PSE releases call it ``SerdeFormat::RawBytesUnchecked``; the pinned tag's own
-``write`` compresses points -- a Rust-side loader converts once].
+On-disk layouts (little-endian; the field order of upstream's ``ParamsKZG::write``), ``format=`` of read / write:
+    "raw_unchecked" (default)  u32 k | n x 64 B g | n x 64 B g_lagrange | 128 B g2 | 128 B s_g2
+                               exactly the bytes the Rust types hold: Montgomery limbs, G2Affine = x.c0, x.c1, y.c0, y.c1
+    "raw"                      the same bytes; read() rejects a coordinate >= p or a point off the curve
+    "processed"                u32 k | n x 32 B g | n x 32 B g_lagrange | 64 B g2 | 64 B s_g2   (compressed points)
+[UPSTREAM-RECALLED: later PSE releases name them ``SerdeFormat::RawBytesUnchecked`` / ``RawBytes`` / ``Processed``; the pinned
+tag's own ``write`` / ``read`` use the compressed form.]  Compressed G1: canonical x little-endian, bit 7 of byte 31 = parity of
+canonical y, the identity 32 zero bytes; G2 likewise over x.c0 | x.c1 with the parity of y.c0 in bit 7 of byte 63.  G1 points
+are compressed and decompressed on the GPU (``g1_compress`` / ``g1_decompress``); G2 (two points) in host integers.
 """
 from __future__ import annotations
 
@@ -29,8 +33,9 @@ from typing import BinaryIO, Optional
 import numpy as np
 
 from . import _lib
-from .arithmetic import (FQ_MODULUS, G1_GENERATOR, BasesHandle, _is_tensor, _ptr, _stream_ptr, best_multiexp, best_multiexp_submit,
-                         best_multiexp_wait, g1_fixed_base_mul, g_to_lagrange, register_bases, release_bases)
+from .arithmetic import (FQ_MODULUS, G1_GENERATOR, BasesHandle, InvalidPointError, _is_tensor, _ptr, _stream_ptr, best_multiexp,
+                         best_multiexp_submit, best_multiexp_wait, g1_check_host, g1_compress, g1_compress_host, g1_decompress,
+                         g1_fixed_base_mul, g_to_lagrange, register_bases, release_bases)
 from .domain import FR_MODULUS, EvaluationDomain, fr_words
 
 _P = FQ_MODULUS
@@ -91,6 +96,101 @@ def g2_bytes(p) -> bytes:
     if p is None:
         return bytes(128)
     return b"".join(_fq_mont_bytes(c) for c in (p[0][0], p[0][1], p[1][0], p[1][1]))
+
+
+# ---- G2 encodings (two points per SRS: host integers) -----------------------------------------------------------------------------
+_B2 = _fq2_mul((3, 0), _fq2_inv((9, 1)))           # the twist's b = 3 / (9 + u)
+
+
+def _g2_rhs(x):
+    x3 = _fq2_mul(_fq2_mul(x, x), x)
+    return ((x3[0] + _B2[0]) % _P, (x3[1] + _B2[1]) % _P)
+
+
+def g2_on_curve(p) -> bool:
+    return p is None or _fq2_mul(p[1], p[1]) == _g2_rhs(p[0])
+
+
+def _fq_sqrt(a: int):
+    r = pow(a, (_P + 1) // 4, _P)                  # p = 3 mod 4
+    return r if r * r % _P == a % _P else None
+
+
+def _fq2_sqrt(a):
+    """A square root in Fq2 = Fq[u] / (u^2 + 1) by the complex method, or None for a non-residue."""
+    a0, a1 = a[0] % _P, a[1] % _P
+    if a1 == 0:
+        r = _fq_sqrt(a0)
+        if r is not None:
+            return (r, 0)
+        r = _fq_sqrt(-a0 % _P)
+        return None if r is None else (0, r)
+    alpha = _fq_sqrt((a0 * a0 + a1 * a1) % _P)     # the norm's root
+    if alpha is None:
+        return None
+    half = (_P + 1) // 2
+    x0 = _fq_sqrt((a0 + alpha) * half % _P)
+    if x0 is None:
+        x0 = _fq_sqrt((a0 - alpha) * half % _P)
+        if x0 is None:
+            return None
+    return (x0, a1 * pow(2 * x0, -1, _P) % _P)
+
+
+def g2_compress(p) -> bytes:
+    """64 bytes: x.c0 | x.c1 canonical little-endian, bit 7 of byte 63 = parity of canonical y.c0; the identity (None) is zeros."""
+    if p is None:
+        return bytes(64)
+    out = bytearray(p[0][0].to_bytes(32, "little") + p[0][1].to_bytes(32, "little"))
+    out[63] |= (p[1][0] & 1) << 7
+    return bytes(out)
+
+
+def g2_decompress(data: bytes):
+    """The inverse of ``g2_compress``: the affine point, or None for the identity.  Raises ValueError for a coordinate >= p or an x
+    that is not on the curve."""
+    if len(data) != 64:
+        raise ValueError("g2_decompress: 64 bytes expected")
+    sign = data[63] >> 7
+    b = bytearray(data)
+    b[63] &= 0x7F
+    x = (int.from_bytes(b[:32], "little"), int.from_bytes(b[32:], "little"))
+    if x[0] >= _P or x[1] >= _P:
+        raise ValueError("g2_decompress: coordinate >= p")
+    if x == (0, 0) and not sign:
+        return None
+    rhs = _g2_rhs(x)
+    y = _fq2_sqrt(rhs)
+    if y is None or _fq2_mul(y, y) != rhs:
+        raise ValueError("g2_decompress: not on the curve")
+    if (y[0] & 1) != sign:
+        y = (-y[0] % _P, -y[1] % _P)
+    return (x, y)
+
+
+def g2_from_bytes(data: bytes, check: bool = False):
+    """The inverse of ``g2_bytes`` (Montgomery limbs); ``check``: reject a coordinate word >= p or a point off the curve."""
+    if len(data) != 128:
+        raise ValueError("g2_from_bytes: 128 bytes expected")
+    words = [int.from_bytes(data[32 * i: 32 * i + 32], "little") for i in range(4)]
+    if check and any(w >= _P for w in words):
+        raise ValueError("g2_from_bytes: coordinate >= p")
+    if not any(words):
+        return None
+    rinv = pow(1 << 256, -1, _P)
+    c = [w * rinv % _P for w in words]
+    p = ((c[0], c[1]), (c[2], c[3]))
+    if check and not g2_on_curve(p):
+        raise ValueError("g2_from_bytes: not on the curve")
+    return p
+
+
+FORMATS = ("raw_unchecked", "raw", "processed")
+
+
+def _check_format(fmt: str, who: str) -> None:
+    if fmt not in FORMATS:
+        raise ValueError(f"{who}: unknown format {fmt!r} (one of {', '.join(FORMATS)})")
 
 
 class ParamsKZG:
@@ -195,8 +295,22 @@ class ParamsKZG:
 
     # -- write / read --------------------------------------------------------------------------------
     @staticmethod
-    def write_points(f: BinaryIO, k: int, g: np.ndarray, g_lagrange: np.ndarray, g2: bytes, s_g2: bytes) -> None:
+    def write_points(f: BinaryIO, k: int, g, g_lagrange, g2: bytes, s_g2: bytes, format: str = "raw_unchecked") -> None:
+        """``g`` / ``g_lagrange``: (n, 8) numpy arrays, or GPU tensors for ``format="processed"`` (compressed on the device)."""
+        _check_format(format, "ParamsKZG.write")
         n = 1 << k
+        if format == "processed":
+            f.write(struct.pack("<I", k))
+            for pts in (g, g_lagrange):
+                if _is_tensor(pts):
+                    if pts.shape[0] != n:
+                        raise ValueError("ParamsKZG.write: g and g_lagrange must hold 2^k points")
+                    f.write(g1_compress(pts.contiguous()).cpu().numpy().tobytes())
+                else:
+                    f.write(g1_compress_host(np.ascontiguousarray(pts, dtype=np.uint64).reshape(n, 8)).tobytes())
+            f.write(g2_compress(g2_from_bytes(g2)))
+            f.write(g2_compress(g2_from_bytes(s_g2)))
+            return
         g = np.ascontiguousarray(g, dtype=np.uint64).reshape(n, 8)
         gl = np.ascontiguousarray(g_lagrange, dtype=np.uint64).reshape(n, 8)
         f.write(struct.pack("<I", k))
@@ -205,15 +319,22 @@ class ParamsKZG:
         f.write(g2)
         f.write(s_g2)
 
-    def write(self, f: BinaryIO) -> None:
-        """Needs the affine points (setup(..., keep_points=True) or read())."""
+    def write(self, f: BinaryIO, format: str = "raw_unchecked") -> None:
+        """Needs the affine points (setup(..., keep_points=True), read() or from_monomial())."""
+        _check_format(format, "ParamsKZG.write")
         if not hasattr(self, "g_points"):
             raise ValueError("ParamsKZG.write: the affine points were not kept (setup(..., keep_points=True))")
+        if format == "processed":
+            self.write_points(f, self.k, self.g_points, self.g_lagrange_points, self.g2, self.s_g2, format=format)
+            return
         to_np = lambda t: t.cpu().numpy().view(np.uint64) if hasattr(t, "cpu") else np.asarray(t)
-        self.write_points(f, self.k, to_np(self.g_points), to_np(self.g_lagrange_points), self.g2, self.s_g2)
+        self.write_points(f, self.k, to_np(self.g_points), to_np(self.g_lagrange_points), self.g2, self.s_g2, format=format)
 
     @classmethod
-    def read(cls, f: BinaryIO, precompute: bool = False) -> "ParamsKZG":
+    def read(cls, f: BinaryIO, precompute: bool = False, format: str = "raw_unchecked") -> "ParamsKZG":
+        """``format="raw"`` rejects a coordinate >= p or a point off the curve; ``"processed"`` decodes the compressed points on the
+        GPU and registers the device tensors.  An invalid point raises ValueError naming its set (g / g_lagrange / g2 / s_g2) and index."""
+        _check_format(format, "ParamsKZG.read")
         head = f.read(4)
         if len(head) != 4:
             raise ValueError("ParamsKZG.read: truncated header")
@@ -221,10 +342,53 @@ class ParamsKZG:
         if k > 28:
             raise ValueError("ParamsKZG.read: k out of range")
         n = 1 << k
+        if format == "processed":
+            return cls._read_processed(f, k, precompute)
         raw = f.read(n * 128 + 256)
         if len(raw) != n * 128 + 256:
             raise ValueError("ParamsKZG.read: truncated file")
         pts = np.frombuffer(raw, dtype=np.uint64, count=n * 16).reshape(2, n, 8)
-        params = cls(k, pts[0], pts[1], raw[n * 128: n * 128 + 128], raw[n * 128 + 128:], precompute=precompute)
+        g2, s_g2 = raw[n * 128: n * 128 + 128], raw[n * 128 + 128:]
+        if format == "raw":
+            for name, set_ in (("g", pts[0]), ("g_lagrange", pts[1])):
+                try:
+                    g1_check_host(set_)
+                except InvalidPointError as e:
+                    raise InvalidPointError(f"ParamsKZG.read: invalid point in {name} at index {e.index}", e.index) from None
+            for name, b in (("g2", g2), ("s_g2", s_g2)):
+                try:
+                    g2_from_bytes(b, check=True)
+                except ValueError as e:
+                    raise ValueError(f"ParamsKZG.read: invalid {name}: {e}") from None
+        params = cls(k, pts[0], pts[1], g2, s_g2, precompute=precompute)
         params.g_points, params.g_lagrange_points = pts[0], pts[1]
+        return params
+
+    @classmethod
+    def _read_processed(cls, f: BinaryIO, k: int, precompute: bool) -> "ParamsKZG":
+        import torch
+
+        n = 1 << k
+        body = np.empty(n * 64, dtype=np.uint8)
+        if f.readinto(memoryview(body)) != body.size:
+            raise ValueError("ParamsKZG.read: truncated file")
+        tail = f.read(128)
+        if len(tail) != 128:
+            raise ValueError("ParamsKZG.read: truncated file")
+        dev = torch.from_numpy(body).to(torch.device("cuda", torch.cuda.current_device()))
+        sets = []
+        for i, name in enumerate(("g", "g_lagrange")):
+            try:
+                sets.append(g1_decompress(dev[i * n * 32: (i + 1) * n * 32]))
+            except InvalidPointError as e:
+                raise InvalidPointError(f"ParamsKZG.read: invalid point in {name} at index {e.index}", e.index) from None
+        del dev
+        g2s = []
+        for name, b in (("g2", tail[:64]), ("s_g2", tail[64:])):
+            try:
+                g2s.append(g2_bytes(g2_decompress(b)))
+            except ValueError as e:
+                raise ValueError(f"ParamsKZG.read: invalid {name}: {e}") from None
+        params = cls(k, sets[0], sets[1], g2s[0], g2s[1], precompute=precompute)
+        params.g_points, params.g_lagrange_points = sets[0], sets[1]
         return params

@@ -44,6 +44,8 @@ extern "C" {
 /* an in-place host-pointer call failed AFTER it began writing its result: the array is undefined (every other error
  * leaves the caller's arrays untouched, so a caller may fall back to its CPU body on them -- not after this one) */
 #define HM_ERR_PARTIAL_OUTPUT (-6)
+/* the input holds an invalid encoding or point (hm_g1_decompress_bn256*, hm_g1_check_bn256*): the smallest bad index is reported */
+#define HM_ERR_INVALID_DATA (-7)
 
 /* ---- lifecycle ---------------------------------------------------------------------------- */
 
@@ -482,6 +484,26 @@ int hm_g1_fft_bn256_dev(void* d_points_xy, const uint64_t omega[4], uint32_t log
  * normalised to (x, y, 1) / (0, 0, 0) like hm_msm_bn256_g1_jacobian.  `points_xyz` is written only by the final copy from
  * the device: every error code but HM_ERR_PARTIAL_OUTPUT (that copy itself failed) leaves it exactly as it was. */
 int hm_g1_fft_bn256(uint64_t* points_xyz, const uint64_t omega[4], uint32_t log_n, const uint64_t* scale);
+
+/* ---- SRS point encodings: ParamsKZG::read / write (compressed G1 and the checked raw format) ---------------------------- */
+
+/* Compressed G1, 32 bytes: canonical x little-endian (Fq::to_bytes), bit 7 of byte 31 = parity of canonical y; the identity is 32
+ * zero bytes.  Points: n x 8 u64 affine Montgomery, (0,0) = identity (the hm_register_bases layout).  n <= 2^30 in every form.
+ *
+ * compress: points -> n x 32 bytes, asynchronous on `stream`.  The points are trusted (no validation).
+ * decompress: n x 32 bytes -> points; waits for `stream`.  An entry with x >= p or x^3 + 3 not a square is written as (0,0).
+ * check (the checked raw format): every coordinate word < p, and y^2 = x^3 + 3 or the point is (0,0); waits for `stream`.
+ * decompress and check return HM_ERR_INVALID_DATA with the smallest bad index in *out_first_invalid, or HM_OK with
+ * *out_first_invalid = n. */
+int hm_g1_compress_bn256_dev(const void* d_points_xy, size_t n, void* d_out32, void* stream);
+int hm_g1_decompress_bn256_dev(const void* d_in32, size_t n, void* d_points_xy, uint64_t* out_first_invalid, void* stream);
+int hm_g1_check_bn256_dev(const void* d_points_xy, size_t n, uint64_t* out_first_invalid, void* stream);
+
+/* Host forms of the same, through the library's staging.  The output array is written only by the final copy from the device:
+ * every error code but HM_ERR_PARTIAL_OUTPUT (that copy itself failed) leaves it exactly as it was, HM_ERR_INVALID_DATA included. */
+int hm_g1_compress_bn256(const uint64_t* points_xy, size_t n, uint8_t* out32);
+int hm_g1_decompress_bn256(const uint8_t* in32, size_t n, uint64_t* points_xy, uint64_t* out_first_invalid);
+int hm_g1_check_bn256(const uint64_t* points_xy, size_t n, uint64_t* out_first_invalid);
 
 /* ---- introspection --------------------------------------------------------------------------- */
 
