@@ -157,6 +157,14 @@ _SIGNATURES = {
     "hm_g1_compress_bn256": (ctypes.c_int, [_u64p, ctypes.c_size_t, _vp]),
     "hm_g1_decompress_bn256": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, _u64p]),
     "hm_g1_check_bn256": (ctypes.c_int, [_u64p, ctypes.c_size_t, _u64p]),
+    "hm_poseidon_create": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u64p, _u64p, _u64p]),
+    "hm_poseidon_destroy": (ctypes.c_int, [ctypes.c_uint64]),
+    "hm_poseidon_hash_bn256_fr_dev": (ctypes.c_int, [ctypes.c_uint64, _vp, ctypes.c_size_t, _vp, _vp]),
+    "hm_poseidon_hash_bn256_fr": (ctypes.c_int, [ctypes.c_uint64, _u64p, ctypes.c_size_t, _u64p]),
+    "hm_merkle_sum_tree_build_dev": (ctypes.c_int, [ctypes.c_uint64, _vp, ctypes.c_uint32, _vp, _vp]),
+    "hm_merkle_sum_tree_build": (ctypes.c_int, [ctypes.c_uint64, _u64p, ctypes.c_uint32, _u64p, _u64p]),
+    "hm_merkle_tree_build_dev": (ctypes.c_int, [ctypes.c_uint64, _vp, ctypes.c_uint32, _vp, _vp]),
+    "hm_merkle_paths_dev": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64p, ctypes.c_size_t, _vp, _vp]),
     "hm_extended_to_coeff_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p, _u64p, _vp]),
     "hm_eval_polynomial_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32), _u64p, ctypes.c_size_t,
                                                        _u64p, _vp]),

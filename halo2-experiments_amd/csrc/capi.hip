@@ -316,6 +316,8 @@ int hm_shutdown(void) try {
   c.free_bases.clear();
   for (auto& g : c.graphs) graph_release(*g);
   c.graphs.clear();
+  for (auto& p : c.poseidon) poseidon_spec_release(*p);
+  c.poseidon.clear();
   if (c.batch_streams_ready) {
     for (auto& st : c.batch_streams) (void)hipStreamDestroy(st);
     (void)hipEventDestroy(c.batch_event);
@@ -2194,6 +2196,168 @@ int hm_g1_check_bn256(const uint64_t* points_xy, size_t n, uint64_t* out_first_i
   ctx->calls.h2d_bytes += bytes;
   return g1_check_run((const uint32_t*)d_p, n, out_first_invalid, nullptr);
 } HM_API_CATCH("hm_g1_check_bn256")
+
+// ---- Poseidon and Merkle trees (poseidon.inc, polyops.hip) --------------------------------------------------------------------
+static constexpr size_t POSEIDON_MAX_N = (size_t)1 << 31;
+static constexpr uint32_t MERKLE_MAX_DEPTH = 30;
+
+int hm_poseidon_create(uint32_t width, uint32_t rate, uint32_t r_f, uint32_t r_p, const uint64_t* round_constants, const uint64_t* mds,
+                       uint64_t* out_handle) try {
+  if (!round_constants || !mds || !out_handle) return hm_fail(HM_ERR_BAD_ARG, "hm_poseidon_create: null argument");
+  if (width != 3 && width != 5) return hm_fail(HM_ERR_BAD_ARG, "hm_poseidon_create: width must be 3 or 5");
+  if (rate != width - 1) return hm_fail(HM_ERR_BAD_ARG, "hm_poseidon_create: rate must be width - 1");
+  if ((r_f & 1) || r_f > 1024 || r_p > 1024 || r_f + r_p == 0 || r_f + r_p > 1024)
+    return hm_fail(HM_ERR_BAD_ARG, "hm_poseidon_create: r_f must be even and 0 < r_f + r_p <= 1024");
+  for (size_t i = 0, n_rc = (size_t)(r_f + r_p) * width, total = n_rc + (size_t)width * width; i < total; ++i) {
+    const uint64_t* w = i < n_rc ? round_constants + i * 4 : mds + (i - n_rc) * 4;
+    bool lt = false;
+    for (int k = 3; k >= 0; --k)
+      if (w[k] != host::FR_MOD[k]) {
+        lt = w[k] < host::FR_MOD[k];
+        break;
+      }
+    if (!lt) return hm_fail(HM_ERR_BAD_ARG, "hm_poseidon_create: a constant is not below the modulus");
+  }
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return poseidon_spec_create(*ctx, width, rate, r_f, r_p, round_constants, mds, out_handle);
+} HM_API_CATCH("hm_poseidon_create")
+
+int hm_poseidon_destroy(uint64_t handle) try {
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  for (size_t i = 0; i < ctx->poseidon.size(); ++i)
+    if (ctx->poseidon[i]->handle == handle) {
+      (void)hipDeviceSynchronize();          // a launch may still read the constants (rare call: once per spec)
+      poseidon_spec_release(*ctx->poseidon[i]);
+      ctx->poseidon.erase(ctx->poseidon.begin() + i);
+      return HM_OK;
+    }
+  return hm_fail(HM_ERR_NOT_FOUND, "hm_poseidon_destroy: unknown spec handle");
+} HM_API_CATCH("hm_poseidon_destroy")
+
+static PoseidonSpec* find_poseidon(DeviceCtx& ctx, uint64_t handle) {      // ctx.mu held
+  for (auto& p : ctx.poseidon)
+    if (p->handle == handle) return p.get();
+  return nullptr;
+}
+// the spec of a tree call: `width` 5 for the sum tree, 3 for the plain tree
+static int merkle_spec(const char* who, DeviceCtx& ctx, uint64_t handle, uint32_t width, PoseidonSpec** out) {
+  *out = find_poseidon(ctx, handle);
+  if (!*out) return hm_fail(HM_ERR_NOT_FOUND, std::string(who) + ": unknown spec handle");
+  if ((*out)->width != width)
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the spec has width " + std::to_string((*out)->width) + ", this tree needs width " +
+                                       std::to_string(width));
+  return HM_OK;
+}
+
+int hm_poseidon_hash_bn256_fr_dev(uint64_t handle, const void* d_msgs, size_t n, void* d_out, void* stream) try {
+  if (n && (!d_msgs || !d_out)) return hm_fail(HM_ERR_BAD_ARG, "hm_poseidon_hash_bn256_fr_dev: null argument");
+  if (n > POSEIDON_MAX_N) return hm_fail(HM_ERR_BAD_ARG, "hm_poseidon_hash_bn256_fr_dev: n > 2^31");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PoseidonSpec* s = find_poseidon(*ctx, handle);
+  if (!s) return hm_fail(HM_ERR_NOT_FOUND, "hm_poseidon_hash_bn256_fr_dev: unknown spec handle");
+  return poseidon_hash_run(*s, (const uint32_t*)d_msgs, (uint64_t)s->rate * 8, (uint32_t*)d_out, 8, n, (hipStream_t)stream);
+} HM_API_CATCH("hm_poseidon_hash_bn256_fr_dev")
+
+// Host forms: input and output share one staging buffer; the caller's outputs are written only by the last copies.
+int hm_poseidon_hash_bn256_fr(uint64_t handle, const uint64_t* msgs, size_t n, uint64_t* out) try {
+  if (n && (!msgs || !out)) return hm_fail(HM_ERR_BAD_ARG, "hm_poseidon_hash_bn256_fr: null argument");
+  if (n > POSEIDON_MAX_N) return hm_fail(HM_ERR_BAD_ARG, "hm_poseidon_hash_bn256_fr: n > 2^31");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PoseidonSpec* s = find_poseidon(*ctx, handle);
+  if (!s) return hm_fail(HM_ERR_NOT_FOUND, "hm_poseidon_hash_bn256_fr: unknown spec handle");
+  if (n == 0) return HM_OK;
+  hm_fault_point("poseidon_upload");
+  const size_t in_bytes = n * s->rate * 32, out_bytes = n * 32;
+  uint8_t* d_p = (uint8_t*)ctx->io.ensure(in_bytes + out_bytes);
+  if (!d_p) return hm_fail(HM_ERR_HIP, "hm_poseidon_hash_bn256_fr: staging allocation failed");
+  int rc = xfer_h2d(*ctx, d_p, msgs, in_bytes, "hm_poseidon_hash_bn256_fr: upload");
+  if (rc != HM_OK) return rc;
+  rc = poseidon_hash_run(*s, (const uint32_t*)d_p, (uint64_t)s->rate * 8, (uint32_t*)(d_p + in_bytes), 8, n, nullptr);
+  if (rc != HM_OK) return rc;
+  HM_HIP_CHECK(hipStreamSynchronize(nullptr));
+  hm_fault_point("poseidon_download");
+  if (xfer_d2h(*ctx, out, d_p + in_bytes, out_bytes, "hm_poseidon_hash_bn256_fr") != HM_OK)
+    return hm_fail(HM_ERR_PARTIAL_OUTPUT, "hm_poseidon_hash_bn256_fr: copying the result back failed, the output is partly written: " +
+                                              hm_last_error_string());
+  ctx->calls.h2d_bytes += in_bytes;
+  ctx->calls.d2h_bytes += out_bytes;
+  return HM_OK;
+} HM_API_CATCH("hm_poseidon_hash_bn256_fr")
+
+static int merkle_build_dev(const char* who, uint64_t handle, uint32_t width, const void* d_leaves, uint32_t depth, void* d_nodes,
+                            void* stream) {
+  if (!d_leaves || !d_nodes) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (depth > MERKLE_MAX_DEPTH) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": depth > 30");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PoseidonSpec* s = nullptr;
+  if (int rc = merkle_spec(who, *ctx, handle, width, &s)) return rc;
+  const size_t leaf_bytes = ((size_t)1 << depth) * (width == 5 ? 64 : 32);
+  if (d_leaves != d_nodes) {
+    if (ranges_overlap(d_leaves, leaf_bytes, d_nodes, 2 * leaf_bytes))
+      return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": d_leaves partially overlaps d_nodes");
+    HM_HIP_CHECK(hipMemcpyAsync(d_nodes, d_leaves, leaf_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  }
+  return merkle_build_run(*s, (uint32_t*)d_nodes, depth, (hipStream_t)stream);
+}
+
+int hm_merkle_sum_tree_build_dev(uint64_t handle, const void* d_leaves, uint32_t depth, void* d_nodes, void* stream) try {
+  return merkle_build_dev("hm_merkle_sum_tree_build_dev", handle, 5, d_leaves, depth, d_nodes, stream);
+} HM_API_CATCH("hm_merkle_sum_tree_build_dev")
+
+int hm_merkle_tree_build_dev(uint64_t handle, const void* d_leaves, uint32_t depth, void* d_nodes, void* stream) try {
+  return merkle_build_dev("hm_merkle_tree_build_dev", handle, 3, d_leaves, depth, d_nodes, stream);
+} HM_API_CATCH("hm_merkle_tree_build_dev")
+
+int hm_merkle_sum_tree_build(uint64_t handle, const uint64_t* leaves, uint32_t depth, uint64_t* root, uint64_t* nodes_or_null) try {
+  if (!leaves || !root) return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_sum_tree_build: null argument");
+  if (depth > MERKLE_MAX_DEPTH) return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_sum_tree_build: depth > 30");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PoseidonSpec* s = nullptr;
+  if (int rc = merkle_spec("hm_merkle_sum_tree_build", *ctx, handle, 5, &s)) return rc;
+  hm_fault_point("poseidon_upload");
+  const size_t leaf_bytes = ((size_t)1 << depth) * 64, node_bytes = 2 * leaf_bytes - 64;
+  uint8_t* d_p = (uint8_t*)ctx->io.ensure(node_bytes);
+  if (!d_p) return hm_fail(HM_ERR_HIP, "hm_merkle_sum_tree_build: staging allocation failed");
+  int rc = xfer_h2d(*ctx, d_p, leaves, leaf_bytes, "hm_merkle_sum_tree_build: upload");
+  if (rc != HM_OK) return rc;
+  rc = merkle_build_run(*s, (uint32_t*)d_p, depth, nullptr);
+  if (rc != HM_OK) return rc;
+  HM_HIP_CHECK(hipStreamSynchronize(nullptr));
+  hm_fault_point("poseidon_download");
+  uint64_t root_words[8];
+  rc = xfer_d2h(*ctx, root_words, d_p + node_bytes - 64, 64, "hm_merkle_sum_tree_build: root");
+  if (rc != HM_OK) return rc;                       // nothing of the caller's has been written yet
+  if (nodes_or_null && xfer_d2h(*ctx, nodes_or_null, d_p, node_bytes, "hm_merkle_sum_tree_build") != HM_OK)
+    return hm_fail(HM_ERR_PARTIAL_OUTPUT, "hm_merkle_sum_tree_build: copying the nodes back failed, the array is partly written: " +
+                                              hm_last_error_string());
+  std::memcpy(root, root_words, 64);
+  ctx->calls.h2d_bytes += leaf_bytes;
+  ctx->calls.d2h_bytes += 64 + (nodes_or_null ? node_bytes : 0);
+  return HM_OK;
+} HM_API_CATCH("hm_merkle_sum_tree_build")
+
+int hm_merkle_paths_dev(const void* d_nodes, uint32_t depth, uint32_t words_per_node, const uint64_t* d_indices, size_t m, void* d_out,
+                        void* stream) try {
+  if (m && depth && (!d_nodes || !d_indices || !d_out)) return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_paths_dev: null argument");
+  if (depth > MERKLE_MAX_DEPTH) return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_paths_dev: depth > 30");
+  if (words_per_node != 1 && words_per_node != 2) return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_paths_dev: words_per_node must be 1 or 2");
+  if (m > POSEIDON_MAX_N) return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_paths_dev: m > 2^31");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return merkle_paths_run((const uint32_t*)d_nodes, depth, words_per_node, d_indices, m, (uint32_t*)d_out, (hipStream_t)stream);
+} HM_API_CATCH("hm_merkle_paths_dev")
 
 #ifdef HM_FAULT_INJECTION
 // test build only (libhalo2_mi355x_fi.so; not declared in the public header): the (after + 1)-th passage through the

@@ -223,6 +223,12 @@ struct GraphProgram {       // a compiled evaluate_h program (graph.hip): the va
   GraphVariant variant[2];           // [0] external-form columns, [1] internal-form columns (HM_GRAPH_COLUMNS_INTERNAL)
 };
 
+struct PoseidonSpec {       // hm_poseidon_create: the constants of one spec on the device, internal form (poseidon.inc's layout)
+  uint64_t handle = 0;
+  uint32_t width = 0, rate = 0, r_f = 0, r_p = 0;
+  uint32_t* d_consts = nullptr;
+};
+
 struct FreeBases {          // buffers of a released base set, kept for the next registration of that size
   uint32_t* d_xy = nullptr;
   uint8_t* d_inf = nullptr;
@@ -260,6 +266,7 @@ struct DeviceCtx {
   std::vector<BasesEntry> zombie_bases;   // released while a ticket still reads them: freed by the last hm_msm_wait
   std::vector<FreeBases> free_bases;      // recycled buffers (no hipFree => no device-wide synchronisation)
   std::vector<std::unique_ptr<GraphProgram>> graphs;
+  std::vector<std::unique_ptr<PoseidonSpec>> poseidon;   // live specs: freed by hm_poseidon_destroy / hm_shutdown only, never by a give-back
   hipStream_t batch_streams[HM_MSM_SLOTS - 1] = {};   // hm_msm_batch_bn256_g1_dev: one per asynchronous slot
   hipEvent_t batch_event = nullptr;
   bool batch_streams_ready = false;
@@ -385,6 +392,18 @@ int fr_batch_invert_run(uint32_t* d_v, uint64_t n, hipStream_t stream);
 int fr_mul_periodic_run(uint32_t* d_a, uint64_t n, const uint64_t* pattern_ext, uint32_t period, hipStream_t stream);
 int fr_linear_combination_run(const void* const* d_polys, const uint64_t* coeffs_ext, size_t count, uint64_t n, uint32_t* d_out,
                               hipStream_t stream);
+// Poseidon and Merkle trees (poseidon.inc).  Everything is asynchronous on `stream`; pointers are device memory of u32 words.
+int poseidon_spec_create(DeviceCtx& ctx, uint32_t width, uint32_t rate, uint32_t r_f, uint32_t r_p, const uint64_t* rc_ext,
+                         const uint64_t* mds_ext, uint64_t* out_handle);
+void poseidon_spec_release(PoseidonSpec& s);
+// digest i of the rate consecutive elements at d_in + i * in_stride words -> d_out + i * out_stride words
+int poseidon_hash_run(const PoseidonSpec& s, const uint32_t* d_in, uint64_t in_stride, uint32_t* d_out, uint64_t out_stride, size_t n,
+                      hipStream_t stream);
+// levels 1 .. depth of a tree whose level 0 (2^depth nodes) is already at the start of d_nodes; width 5: (hash, balance) nodes
+// with the balances summed, width 3: one hash per node
+int merkle_build_run(const PoseidonSpec& s, uint32_t* d_nodes, uint32_t depth, hipStream_t stream);
+int merkle_paths_run(const uint32_t* d_nodes, uint32_t depth, uint32_t words_per_node, const uint64_t* d_indices, size_t m,
+                     uint32_t* d_out, hipStream_t stream);
 
 // lookup.hip
 int lookup_permute_run(DeviceCtx& ctx, const void* const* d_inputs, const void* const* d_tables, size_t pairs, uint64_t rows,

@@ -6,11 +6,13 @@
 //
 // Build: g++ -O2 -std=c++17 -DHM_BOUNDS -shared -fPIC -o libhm_hostcheck.so host_check.cpp
 #include <cstring>
+#include <utility>
 
 #include "g1.h"
 
 namespace hm {
 #include "g1_codec.inc"   // the per-point SRS codec formulas (its kernels are HIP-only)
+#include "poseidon.inc"   // the per-hash Poseidon / Merkle node functions (likewise)
 }
 
 using namespace hm;
@@ -338,6 +340,34 @@ void hc_g1_codec(int op, const uint32_t* in, uint32_t* out, int* valid, size_t n
       valid[i] = g1_check_one(a, b) ? 1 : 0;
     }
   }
+}
+
+// Poseidon (poseidon.inc) on n messages, the exact per-hash code of its kernels.  consts: the spec's block as the library lays it out
+// on the device (rc, mds, capacity word; 9 limbs each, canonical internal form).  op 0: n x (width - 1) elements -> n digests;
+// op 1 (width 5 only): n x 4 elements (hash, balance, hash, balance) -> n x 2 (hash, balance), a Merkle sum tree node.
+// The tracked bounds are data-independent: one message proves the 64-round chain for all inputs.
+int hc_poseidon(int op, uint32_t width, const uint32_t* consts, uint32_t r_f, uint32_t r_p, const uint32_t* in, uint32_t* out, size_t n) {
+  if ((width != 3 && width != 5) || (op == 1 && width != 5) || (op != 0 && op != 1)) return -1;
+  for (size_t i = 0; i < n; ++i) {
+    if (width == 3) {
+      uint32_t msg[2][8], d[8];
+      std::memcpy(msg, in + 16 * i, 64);
+      poseidon_hash_one<3>(msg, consts, r_f, r_p, d);
+      std::memcpy(out + 8 * i, d, 32);
+    } else {
+      uint32_t msg[4][8], d[8], b[8];
+      std::memcpy(msg, in + 32 * i, 128);
+      if (op == 0) {
+        poseidon_hash_one<5>(msg, consts, r_f, r_p, d);
+        std::memcpy(out + 8 * i, d, 32);
+      } else {
+        merkle_sum_node_one(msg, consts, r_f, r_p, d, b);
+        std::memcpy(out + 16 * i, d, 32);
+        std::memcpy(out + 16 * i + 8, b, 32);
+      }
+    }
+  }
+  return 0;
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 
 #include <cstring>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "g1.h"
@@ -645,6 +646,92 @@ int fr_mul_periodic_run(uint32_t* d_a, uint64_t n, const uint64_t* pattern_ext, 
   std::memset(&pat, 0, sizeof pat);
   for (uint32_t k = 0; k < period; ++k) po_internal(pattern_ext + (size_t)k * 4, pat.v[k]);
   hipLaunchKernelGGL(fr_mul_periodic_kernel, dim3((uint32_t)((n + PO_THREADS - 1) / PO_THREADS)), dim3(PO_THREADS), 0, stream, d_a, n, pat, period - 1);
+  HM_HIP_CHECK(hipGetLastError());
+  return HM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Poseidon over Fr and the Merkle (sum) trees built from it: kernels and per-hash functions in poseidon.inc
+// ---------------------------------------------------------------------------------------------
+#include "poseidon.inc"
+
+// the constants were validated by the caller (capi.hip: canonical, the shape of the spec)
+int poseidon_spec_create(DeviceCtx& ctx, uint32_t width, uint32_t rate, uint32_t r_f, uint32_t r_p, const uint64_t* rc_ext,
+                         const uint64_t* mds_ext, uint64_t* out_handle) {
+  const size_t n_rc = (size_t)(r_f + r_p) * width, n_mds = (size_t)width * width;
+  std::vector<uint32_t> h((n_rc + n_mds + 1) * 9);
+  for (size_t i = 0; i < n_rc + n_mds; ++i) {
+    const uint64_t* w = i < n_rc ? rc_ext + i * 4 : mds_ext + (i - n_rc) * 4;
+    host::fr_to_internal9(host::fr_load(w), &h[i * 9]);
+  }
+  // the capacity word of ConstantLength<L>, L = rate: the field element L * 2^64, as L additions of ONE and 64 doublings
+  // (a + b written as a - (0 - b): host_fr.h has no addition)
+  host::Fr4 cap = {{0, 0, 0, 0}};
+  const host::Fr4 zero = {{0, 0, 0, 0}};
+  for (uint32_t k = 0; k < rate; ++k) cap = host::fr_sub(cap, host::fr_sub(zero, host::FR_ONE));
+  for (int k = 0; k < 64; ++k) cap = host::fr_sub(cap, host::fr_sub(zero, cap));
+  host::fr_to_internal9(cap, &h[(n_rc + n_mds) * 9]);
+  auto s = std::make_unique<PoseidonSpec>();
+  s->width = width;
+  s->rate = rate;
+  s->r_f = r_f;
+  s->r_p = r_p;
+  HM_HIP_CHECK(hipMalloc((void**)&s->d_consts, h.size() * sizeof(uint32_t)));
+  if (hipError_t e = hipMemcpy(s->d_consts, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice); e != hipSuccess) {
+    poseidon_spec_release(*s);
+    return hm_fail(HM_ERR_HIP, std::string("hm_poseidon_create: ") + hipGetErrorString(e));
+  }
+  s->handle = ctx.next_handle++;
+  *out_handle = s->handle;
+  ctx.poseidon.push_back(std::move(s));
+  return HM_OK;
+}
+
+void poseidon_spec_release(PoseidonSpec& s) {
+  if (s.d_consts) (void)hipFree(s.d_consts);
+  s.d_consts = nullptr;
+}
+
+int poseidon_hash_run(const PoseidonSpec& s, const uint32_t* d_in, uint64_t in_stride, uint32_t* d_out, uint64_t out_stride, size_t n,
+                      hipStream_t stream) {
+  if (n == 0) return HM_OK;
+  const dim3 grid((unsigned)((n + PS_THREADS - 1) / PS_THREADS));
+  if (s.width == 3)
+    hipLaunchKernelGGL(poseidon_hash_kernel<3>, grid, dim3(PS_THREADS), 0, stream, d_in, in_stride, d_out, out_stride, (uint64_t)n,
+                       s.d_consts, s.r_f, s.r_p);
+  else
+    hipLaunchKernelGGL(poseidon_hash_kernel<5>, grid, dim3(PS_THREADS), 0, stream, d_in, in_stride, d_out, out_stride, (uint64_t)n,
+                       s.d_consts, s.r_f, s.r_p);
+  HM_HIP_CHECK(hipGetLastError());
+  return HM_OK;
+}
+
+// One launch per level: level l reads only level l - 1, so the chain is depth launches in stream order.  The levels that no longer
+// fill the chip each take one hash latency whatever the launch shape (a node needs both children finished), so a single small kernel
+// for the top would save only the launch gaps.
+int merkle_build_run(const PoseidonSpec& s, uint32_t* d_nodes, uint32_t depth, hipStream_t stream) {
+  const uint32_t words = s.width == 5 ? 16 : 8;
+  uint64_t below = 0;                                   // first node of level l - 1
+  for (uint32_t l = 1; l <= depth; ++l) {
+    const uint64_t n = 1ull << (depth - l), start = below + 2 * n;
+    if (s.width == 5) {
+      hipLaunchKernelGGL(merkle_sum_level_kernel, dim3((unsigned)((n + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, stream,
+                         d_nodes + below * words, d_nodes + start * words, n, s.d_consts, s.r_f, s.r_p);
+      HM_HIP_CHECK(hipGetLastError());
+    } else if (int rc = poseidon_hash_run(s, d_nodes + below * words, 16, d_nodes + start * words, 8, n, stream)) {
+      return rc;
+    }
+    below = start;
+  }
+  return HM_OK;
+}
+
+int merkle_paths_run(const uint32_t* d_nodes, uint32_t depth, uint32_t words_per_node, const uint64_t* d_indices, size_t m,
+                     uint32_t* d_out, hipStream_t stream) {
+  const uint64_t lanes = (uint64_t)m * depth * words_per_node;
+  if (lanes == 0) return HM_OK;
+  hipLaunchKernelGGL(merkle_path_kernel, dim3((unsigned)((lanes + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, stream, d_nodes,
+                     depth, words_per_node, d_indices, (uint64_t)m, d_out);
   HM_HIP_CHECK(hipGetLastError());
   return HM_OK;
 }

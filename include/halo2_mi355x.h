@@ -505,6 +505,35 @@ int hm_g1_compress_bn256(const uint64_t* points_xy, size_t n, uint8_t* out32);
 int hm_g1_decompress_bn256(const uint8_t* in32, size_t n, uint64_t* points_xy, uint64_t* out_first_invalid);
 int hm_g1_check_bn256(const uint64_t* points_xy, size_t n, uint64_t* out_first_invalid);
 
+/* ---- Poseidon over BN256 Fr and Merkle (sum) trees --------------------------------------------- */
+
+/* Poseidon as halo2_gadgets::poseidon::primitives::Hash<Fr, Spec, ConstantLength<L>, WIDTH, RATE> with L = RATE (one permutation
+ * per hash): state = [m_0 .. m_{RATE-1}, L * 2^64]; r_f / 2 full rounds, r_p partial rounds, r_f / 2 full rounds, each
+ * `state += rc[r]; x^5 on every word (full) or on word 0 (partial); state = MDS * state`; digest = state[0].
+ * The constants are DATA: hand over Spec::constants() verbatim (round_constants: (r_f + r_p) x width elements, mds: width x width
+ * row-major, each 4 x u64 Montgomery).  HM_ERR_BAD_ARG for width other than 3 or 5, rate != width - 1, an odd r_f, r_f + r_p = 0 or
+ * above 1024, or a constant >= r.  The handle owns a small device buffer until hm_poseidon_destroy / hm_shutdown. */
+int hm_poseidon_create(uint32_t width, uint32_t rate, uint32_t r_f, uint32_t r_p, const uint64_t* round_constants, const uint64_t* mds,
+                       uint64_t* out_handle);
+int hm_poseidon_destroy(uint64_t handle);
+/* n messages of `rate` elements each (n x rate x 4 u64) -> n digests (n x 4 u64).  _dev: asynchronous on `stream`; the host form
+ * goes through the library's staging and writes `out` only by its final copy. */
+int hm_poseidon_hash_bn256_fr_dev(uint64_t handle, const void* d_msgs, size_t n, void* d_out, void* stream);
+int hm_poseidon_hash_bn256_fr(uint64_t handle, const uint64_t* msgs, size_t n, uint64_t* out);
+/* Merkle sum tree (the reference's compute_merkle_sum_root): a node is (hash, balance), 2 elements; parent.hash =
+ * H(left.hash, left.balance, right.hash, right.balance) with a width-5 spec, parent.balance = left.balance + right.balance mod r.
+ * d_nodes receives all 2^(depth+1) - 1 nodes, level by level: the 2^depth leaves first (copied from d_leaves, which may be d_nodes
+ * itself), then 2^(depth-1) parents, ... the root last.  depth <= 30; a handle of another width is HM_ERR_BAD_ARG.
+ * Host form: root (2 elements) and, unless NULL, all nodes; both are written only after the tree is built. */
+int hm_merkle_sum_tree_build_dev(uint64_t handle, const void* d_leaves, uint32_t depth, void* d_nodes, void* stream);
+int hm_merkle_sum_tree_build(uint64_t handle, const uint64_t* leaves, uint32_t depth, uint64_t* root, uint64_t* nodes_or_null);
+/* The plain tree of a width-3 spec (merkle_v3): one element per node, parent = H(left, right); same node order. */
+int hm_merkle_tree_build_dev(uint64_t handle, const void* d_leaves, uint32_t depth, void* d_nodes, void* stream);
+/* Sibling nodes of m leaves, bottom up: d_out[(p * depth + l) * words_per_node ..] = node ((d_indices[p] >> l) ^ 1) of level l.
+ * words_per_node = elements per node (2 sum tree, 1 plain tree); d_indices is DEVICE memory; an index >= 2^depth yields zeros. */
+int hm_merkle_paths_dev(const void* d_nodes, uint32_t depth, uint32_t words_per_node, const uint64_t* d_indices, size_t m, void* d_out,
+                        void* stream);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 
 typedef struct hm_msm_stats {
