@@ -15,6 +15,7 @@ HOSTCHECK_PATH = os.path.join(CSRC, "libhm_hostcheck.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "halo2_mi355x.h")
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
+_u32p = ctypes.POINTER(ctypes.c_uint32)
 _vp = ctypes.c_void_p
 NO_CHAIN = ctypes.c_size_t(-1).value      # HM_NO_CHAIN of the header
 
@@ -165,6 +166,11 @@ _SIGNATURES = {
     "hm_merkle_sum_tree_build": (ctypes.c_int, [ctypes.c_uint64, _u64p, ctypes.c_uint32, _u64p, _u64p]),
     "hm_merkle_tree_build_dev": (ctypes.c_int, [ctypes.c_uint64, _vp, ctypes.c_uint32, _vp, _vp]),
     "hm_merkle_paths_dev": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64p, ctypes.c_size_t, _vp, _vp]),
+    "hm_merkle_sum_witness_layout": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p, _u32p]),
+    "hm_merkle_sum_witness_bn256_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, _vp, _vp, _u64p,
+                                                      _u64p, _vp, _vp, _vp, _vp]),
+    "hm_merkle_sum_witness_bn256": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, _u64p, _u64p, _u64p,
+                                                  _u64p, _u64p, _u64p]),
     "hm_extended_to_coeff_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p, _u64p, _vp]),
     "hm_eval_polynomial_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32), _u64p, ctypes.c_size_t,
                                                        _u64p, _vp]),

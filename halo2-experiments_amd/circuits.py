@@ -15,6 +15,8 @@ What is transcribed from files of the reference (read as text; cited per gate) a
 
 The MDS matrix, its inverse and the round constants of the Spec are generic field elements here (halo2_gadgets derives
 them with a Grain LFSR): the program's shape -- calculations, rotations, columns -- does not depend on their values.
+With a ``poseidon.Spec`` (``merkle_sum_tree(spec)`` ...) the MDS matrix and its inverse are the spec's: the system a witness
+can satisfy (synthesis.py fills the round-constant columns from the same spec).
 Selectors are fixed columns, one each (what keygen gives with selector compression off; compression only merges columns).
 """
 from __future__ import annotations
@@ -112,12 +114,20 @@ def _rand_constants(count: int, seed: int) -> List[int]:
 
 
 def pow5_gates(state: Sequence[int], partial_sbox: int, rc_a: Sequence[int], rc_b: Sequence[int], s_full: int, s_partial: int,
-               s_pad_and_add: int, rate: int) -> List[Tuple[str, List[Expression]]]:
+               s_pad_and_add: int, rate: int, constants=None) -> List[Tuple[str, List[Expression]]]:
     """halo2_gadgets Pow5Chip::configure (recalled): the three gates of the Poseidon permutation chip over `state` (WIDTH
-    advice columns), `partial_sbox`, the round-constant columns rc_a / rc_b and three selectors."""
+    advice columns), `partial_sbox`, the round-constant columns rc_a / rc_b and three selectors.
+    constants: a ``poseidon.Spec`` whose ``mds`` / ``mds_inv`` become m_reg / m_inv (what a witness can satisfy: synthesis.py);
+    None: generic elements, the shape-only form."""
     width = len(state)
-    m_reg = [_rand_constants(width, 1000 + i) for i in range(width)]
-    m_inv = [_rand_constants(width, 2000 + i) for i in range(width)]
+    if constants is None:
+        m_reg = [_rand_constants(width, 1000 + i) for i in range(width)]
+        m_inv = [_rand_constants(width, 2000 + i) for i in range(width)]
+    else:
+        if constants.width != width:
+            raise ValueError(f"pow5_gates: the spec has width {constants.width}, the chip has {width} state columns")
+        _, mds, mds_inv = constants.constants()
+        m_reg, m_inv = [list(row) for row in mds], [list(row) for row in mds_inv]
 
     def pow_5(v: Expression) -> Expression:
         v2 = v * v
@@ -156,7 +166,7 @@ def pow5_gates(state: Sequence[int], partial_sbox: int, rc_a: Sequence[int], rc_
     return [("full round", full), ("partial rounds", partial), ("pad-and-add", pad)]
 
 
-def _poseidon_chip(cols: _Columns, hash_inputs: Sequence[int], rate: int):
+def _poseidon_chip(cols: _Columns, hash_inputs: Sequence[int], rate: int, spec=None):
     """PoseidonChip::configure, /root/reference/src/chips/poseidon/hash.rs:45-72: partial_sbox, rc_a, rc_b, equality on the
     hash inputs, constants in rc_b[0]; then Pow5Chip::configure (which allocates its three selectors)."""
     width = len(hash_inputs)
@@ -167,7 +177,7 @@ def _poseidon_chip(cols: _Columns, hash_inputs: Sequence[int], rate: int):
         cols.enable_equality("advice", c)
     cols.enable_equality("fixed", rc_b[0])                 # meta.enable_constant(rc_b[0])
     s_full, s_partial, s_pad = cols.selector(), cols.selector(), cols.selector()
-    return pow5_gates(hash_inputs, partial_sbox, rc_a, rc_b, s_full, s_partial, s_pad, rate)
+    return pow5_gates(hash_inputs, partial_sbox, rc_a, rc_b, s_full, s_partial, s_pad, rate, constants=spec)
 
 
 def lt_chip(cols: _Columns, q_enable: Expression, lhs: Expression, rhs: Expression, n_bytes: int = 8):
@@ -186,8 +196,9 @@ def lt_chip(cols: _Columns, q_enable: Expression, lhs: Expression, rhs: Expressi
     return gates, lookups, lt
 
 
-def merkle_sum_tree() -> ConstraintSystem:
-    """MerkleSumTreeChip::configure, /root/reference/src/chips/merkle_sum_tree.rs:32-138 (WIDTH 5, RATE 4, LtChip over 8 bytes)."""
+def merkle_sum_tree(spec=None) -> ConstraintSystem:
+    """MerkleSumTreeChip::configure, /root/reference/src/chips/merkle_sum_tree.rs:32-138 (WIDTH 5, RATE 4, LtChip over 8 bytes).
+    spec: the width-5 ``poseidon.Spec`` whose MDS matrix the Pow5 gates take (see pow5_gates)."""
     cols = _Columns()
     a, b, c, d, e = (cols.advice() for _ in range(5))      # circuits/merkle_sum_tree.rs:27-31
     inst = cols.instance()
@@ -203,7 +214,7 @@ def merkle_sum_tree() -> ConstraintSystem:
         ("sum constraint", [Fixed(sum_s) * (A(b) + A(d) - A(e))]),                                                   # :95-101
     ]
     hash_inputs = [cols.advice() for _ in range(5)]                                                                  # :103
-    gates += _poseidon_chip(cols, hash_inputs, rate=4)                                                               # :105-106
+    gates += _poseidon_chip(cols, hash_inputs, rate=4, spec=spec)                                                    # :105-106
     lt_gates, lookups, lt = lt_chip(cols, Fixed(lt_s), A(a), A(b))                                                   # :109-114
     gates += lt_gates
     gates.append(("check == is_lt", [Fixed(lt_s) * (A(lt) - A(c))]))                                                 # :127-138
@@ -211,7 +222,7 @@ def merkle_sum_tree() -> ConstraintSystem:
                             cols.num_fixed, cols.num_advice, cols.num_instance, gates, lookups, cols.equality)
 
 
-def merkle_v3() -> ConstraintSystem:
+def merkle_v3(spec=None) -> ConstraintSystem:
     """MerkleTreeV3Chip::configure, /root/reference/src/chips/merkle_v3.rs:30-82 (WIDTH 3, RATE 2)."""
     cols = _Columns()
     a, b, c = (cols.advice() for _ in range(3))
@@ -226,19 +237,19 @@ def merkle_v3() -> ConstraintSystem:
         ("swap constraint", [Fixed(swap_s) * (A(c) * Constant(2) * (A(b) - A(a)) - (A(a, 1) - A(a)) - (A(b) - A(b, 1)))]),  # :57-68
     ]
     hash_inputs = [cols.advice() for _ in range(3)]                                                                  # :70
-    gates += _poseidon_chip(cols, hash_inputs, rate=2)                                                               # :72-73
+    gates += _poseidon_chip(cols, hash_inputs, rate=2, spec=spec)                                                    # :72-73
     return ConstraintSystem("MerkleTreeV3 depth 20 (config 3)", "chips/merkle_v3.rs:30-82 (+ Pow5Chip recalled)",
                             cols.num_fixed, cols.num_advice, cols.num_instance, gates, [], cols.equality)
 
 
-def poseidon() -> ConstraintSystem:
+def poseidon(spec=None) -> ConstraintSystem:
     """PoseidonCircuit::configure, /root/reference/src/circuits/poseidon.rs:36-41 with WIDTH 5, RATE 4 (:79-81): the hash
     inputs, an instance column for the digest, PoseidonChip (hash_with_instance.rs: the same allocations + equality on the
     instance column)."""
     cols = _Columns()
     inst = cols.instance()
     hash_inputs = [cols.advice() for _ in range(5)]
-    gates = _poseidon_chip(cols, hash_inputs, rate=4)
+    gates = _poseidon_chip(cols, hash_inputs, rate=4, spec=spec)
     cols.enable_equality("instance", inst)
     return ConstraintSystem("Poseidon (config 2)", "circuits/poseidon.rs:36-41, chips/poseidon/hash_with_instance.rs (+ Pow5Chip recalled)",
                             cols.num_fixed, cols.num_advice, cols.num_instance, gates, [], cols.equality)

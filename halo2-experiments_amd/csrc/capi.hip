@@ -2359,6 +2359,102 @@ int hm_merkle_paths_dev(const void* d_nodes, uint32_t depth, uint32_t words_per_
   return merkle_paths_run((const uint32_t*)d_nodes, depth, words_per_node, d_indices, m, (uint32_t*)d_out, (hipStream_t)stream);
 } HM_API_CATCH("hm_merkle_paths_dev")
 
+// ---- the MerkleSumTree witness (poseidon.inc: merkle_sum_witness_lane) ------------------------------------------------------------
+static constexpr uint32_t WITNESS_MAX_DEPTH = 32, WITNESS_MAX_LOG_N = 24;
+static constexpr size_t WITNESS_HOST_MAX_BYTES = (size_t)1 << 28;
+
+static int witness_layout(const char* who, uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, uint32_t (&out)[6]) {
+  if (depth == 0 || depth > WITNESS_MAX_DEPTH) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": depth must be 1 .. 32");
+  if ((r_f & 1) || (r_p & 1) || r_f + r_p == 0 || r_f > 1024 || r_p > 1024)
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the Pow5 chip needs even r_f and r_p");
+  if (log_n > WITNESS_MAX_LOG_N) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": log_n > 24");
+  merkle_sum_witness_rows(depth, r_f, r_p, out);
+  if (((uint64_t)1 << log_n) < (uint64_t)out[0] + 6)
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the circuit needs " + std::to_string(out[0]) + " rows, 2^log_n - 6 is fewer");
+  return HM_OK;
+}
+
+int hm_merkle_sum_witness_layout(uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, uint32_t* out_rows_used,
+                                 uint32_t* out_n_advice, uint32_t* out_regions) try {
+  if (!out_rows_used || !out_n_advice) return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_sum_witness_layout: null argument");
+  uint32_t t[6];
+  if (int rc = witness_layout("hm_merkle_sum_witness_layout", r_f, r_p, depth, log_n, t)) return rc;
+  *out_rows_used = t[0];
+  *out_n_advice = t[1];
+  if (out_regions) std::memcpy(out_regions, t + 2, 4 * sizeof(uint32_t));
+  return HM_OK;
+} HM_API_CATCH("hm_merkle_sum_witness_layout")
+
+// everything that can be refused is refused here, before the first launch; -> the spec and n_advice
+static int witness_args(const char* who, DeviceCtx& ctx, uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, bool with_nodes,
+                        PoseidonSpec** s, uint32_t* n_advice) {
+  if (int rc = merkle_spec(who, ctx, handle, 5, s)) return rc;
+  uint32_t t[6];
+  if (int rc = witness_layout(who, (*s)->r_f, (*s)->r_p, depth, log_n, t)) return rc;
+  if (with_nodes && depth > MERKLE_MAX_DEPTH) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a built tree has depth <= 30");
+  if ((uint64_t)m * depth > POSEIDON_MAX_N) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": m * depth > 2^31");
+  *n_advice = t[1];
+  return HM_OK;
+}
+
+int hm_merkle_sum_witness_bn256_dev(uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const void* d_leaves,
+                                    const void* d_siblings, const uint64_t* d_indices, const uint64_t* assets_sum,
+                                    const void* d_nodes_or_null, void* d_advice, void* d_instance, void* stream) try {
+  if (!d_leaves || !d_siblings || !d_indices || !assets_sum || !d_advice || !d_instance)
+    return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_sum_witness_bn256_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PoseidonSpec* s = nullptr;
+  uint32_t n_advice = 0;
+  if (int rc = witness_args("hm_merkle_sum_witness_bn256_dev", *ctx, handle, depth, log_n, m, d_nodes_or_null != nullptr, &s, &n_advice))
+    return rc;
+  return merkle_sum_witness_run(*s, depth, log_n, m, (const uint32_t*)d_leaves, (const uint32_t*)d_siblings, d_indices, assets_sum,
+                                (const uint32_t*)d_nodes_or_null, (uint32_t*)d_advice, (uint32_t*)d_instance, (hipStream_t)stream);
+} HM_API_CATCH("hm_merkle_sum_witness_bn256_dev")
+
+int hm_merkle_sum_witness_bn256(uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const uint64_t* leaves,
+                                const uint64_t* siblings, const uint64_t* indices, const uint64_t* assets_sum, uint64_t* advice,
+                                uint64_t* instance) try {
+  if (!leaves || !siblings || !indices || !assets_sum || !advice || !instance)
+    return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_sum_witness_bn256: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PoseidonSpec* s = nullptr;
+  uint32_t n_advice = 0;
+  if (int rc = witness_args("hm_merkle_sum_witness_bn256", *ctx, handle, depth, log_n, m, false, &s, &n_advice)) return rc;
+  if (m == 0) return HM_OK;
+  const size_t col_bytes = (size_t)32 << log_n;
+  if (m > WITNESS_HOST_MAX_BYTES / ((size_t)n_advice * col_bytes))
+    return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_sum_witness_bn256: the columns exceed 256 MiB; use the device form");
+  const size_t leaf_bytes = m * 64, sib_bytes = m * depth * 64, idx_bytes = (m * 8 + 63) / 64 * 64, adv_bytes = m * n_advice * col_bytes,
+               inst_bytes = m * 128;
+  hm_fault_point("witness_upload");
+  uint8_t* d_p = (uint8_t*)ctx->io.ensure(leaf_bytes + sib_bytes + idx_bytes + adv_bytes + inst_bytes);
+  if (!d_p) return hm_fail(HM_ERR_HIP, "hm_merkle_sum_witness_bn256: staging allocation failed");
+  uint8_t *d_sib = d_p + leaf_bytes, *d_idx = d_sib + sib_bytes, *d_adv = d_idx + idx_bytes, *d_inst = d_adv + adv_bytes;
+  int rc = xfer_h2d(*ctx, d_p, leaves, leaf_bytes, "hm_merkle_sum_witness_bn256: upload");
+  if (rc == HM_OK) rc = xfer_h2d(*ctx, d_sib, siblings, sib_bytes, "hm_merkle_sum_witness_bn256: upload");
+  if (rc == HM_OK) rc = xfer_h2d(*ctx, d_idx, indices, m * 8, "hm_merkle_sum_witness_bn256: upload");
+  if (rc != HM_OK) return rc;
+  rc = merkle_sum_witness_run(*s, depth, log_n, m, (const uint32_t*)d_p, (const uint32_t*)d_sib, (const uint64_t*)d_idx, assets_sum, nullptr,
+                              (uint32_t*)d_adv, (uint32_t*)d_inst, nullptr);
+  if (rc != HM_OK) return rc;
+  HM_HIP_CHECK(hipStreamSynchronize(nullptr));
+  hm_fault_point("witness_download");
+  std::vector<uint64_t> inst(m * 16);
+  rc = xfer_d2h(*ctx, inst.data(), d_inst, inst_bytes, "hm_merkle_sum_witness_bn256: instance");
+  if (rc != HM_OK) return rc;                       // nothing of the caller's has been written yet
+  if (xfer_d2h(*ctx, advice, d_adv, adv_bytes, "hm_merkle_sum_witness_bn256") != HM_OK)
+    return hm_fail(HM_ERR_PARTIAL_OUTPUT, "hm_merkle_sum_witness_bn256: copying the columns back failed, they are partly written: " +
+                                              hm_last_error_string());
+  std::memcpy(instance, inst.data(), inst_bytes);
+  ctx->calls.h2d_bytes += leaf_bytes + sib_bytes + m * 8;
+  ctx->calls.d2h_bytes += adv_bytes + inst_bytes;
+  return HM_OK;
+} HM_API_CATCH("hm_merkle_sum_witness_bn256")
+
 #ifdef HM_FAULT_INJECTION
 // test build only (libhalo2_mi355x_fi.so; not declared in the public header): the (after + 1)-th passage through the
 // named fault point throws std::runtime_error; point == NULL disarms

@@ -404,6 +404,11 @@ int poseidon_hash_run(const PoseidonSpec& s, const uint32_t* d_in, uint64_t in_s
 int merkle_build_run(const PoseidonSpec& s, uint32_t* d_nodes, uint32_t depth, hipStream_t stream);
 int merkle_paths_run(const uint32_t* d_nodes, uint32_t depth, uint32_t words_per_node, const uint64_t* d_indices, size_t m,
                      uint32_t* d_out, hipStream_t stream);
+// the MerkleSumTree witness (poseidon.inc): out = rows_used, n_advice, perm_rows, level_rows, lt_row, const_row
+void merkle_sum_witness_rows(uint32_t depth, uint32_t r_f, uint32_t r_p, uint32_t (&out)[6]);
+int merkle_sum_witness_run(const PoseidonSpec& s, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* d_leaves,
+                           const uint32_t* d_siblings, const uint64_t* d_indices, const uint64_t* assets_ext, const uint32_t* d_nodes,
+                           uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream);
 
 // lookup.hip
 int lookup_permute_run(DeviceCtx& ctx, const void* const* d_inputs, const void* const* d_tables, size_t pairs, uint64_t rows,

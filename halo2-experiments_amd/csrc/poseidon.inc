@@ -99,25 +99,45 @@ HM_HD void poseidon_mix(Fr (&s)[W], const uint32_t* mds, const Fr (&x)[W], std::
   ((s[I] = poseidon_dot<W>(mds + I * W * 9, x)), ...);
 }
 
+// What a caller may watch of a permutation -- the rows of the Pow5 chip's "permute state" region (witness.inc section below):
+// row(i, s) gets the state BEFORE every full round and before every first round of a pair of partial rounds, and the final state;
+// sbox0(i, x) the first S-box output of the pair that row i starts.  The hashing kernels pass PoseidonNoTrace: nothing is
+// computed for it and their code is what it was.
+struct PoseidonNoTrace {
+  template <int W>
+  HM_HD void row(uint32_t, const Fr (&)[W]) const {}
+  HM_HD void sbox0(uint32_t, const Fr&) const {}
+};
+
 // the permutation on WIDTH words in internal form (normalised, product outputs or constants); c = the spec's constant block
-template <int W>
-HM_HD void poseidon_permute(Fr (&s)[W], const uint32_t* c, uint32_t r_f, uint32_t r_p) {
+template <int W, class Sink>
+HM_HD void poseidon_permute(Fr (&s)[W], const uint32_t* c, uint32_t r_f, uint32_t r_p, const Sink& sink) {
   const uint32_t rounds = r_f + r_p, half = r_f >> 1;
   const uint32_t* mds = c + (size_t)rounds * W * 9;
+  uint32_t row = 0;
 #pragma unroll 1
   for (uint32_t r = 0; r < rounds; ++r) {
     const bool full = r < half || r >= half + r_p;     // the same in every lane
+    const bool first = full || !((r - half) & 1u);     // a row of the chip starts with this round
     const uint32_t* rc = c + (size_t)r * W * 9;
+    if (first) sink.row(row, s);
     Fr x[W];
 #pragma unroll
     for (int j = 0; j < W; ++j) x[j] = fe_add(s[j], ps_load9(rc + j * 9));
     x[0] = poseidon_sbox(x[0]);
+    if (first && !full) sink.sbox0(row, x[0]);
+    row += first ? 1u : 0u;
     if (full)
       poseidon_sbox_rest<W>(x, std::make_integer_sequence<int, W - 1>{});
     else
       poseidon_norm_rest<W>(x, std::make_integer_sequence<int, W - 1>{});
     poseidon_mix<W>(s, mds, x, std::make_integer_sequence<int, W>{});
   }
+  sink.row(row, s);
+}
+template <int W>
+HM_HD void poseidon_permute(Fr (&s)[W], const uint32_t* c, uint32_t r_f, uint32_t r_p) {
+  poseidon_permute<W>(s, c, r_f, r_p, PoseidonNoTrace{});
 }
 
 // Hash<_, Spec, ConstantLength<W - 1>, W, W - 1>::init().hash(msg): state = [msg, L * 2^64], one permutation, word 0.
@@ -143,6 +163,271 @@ HM_HD void merkle_sum_node_one(const uint32_t (&kids)[4][8], const uint32_t* c, 
                                uint32_t (&balance)[8]) {
   fr_add_ext(kids[1], kids[3], balance);
   poseidon_hash_one<5>(kids, c, r_f, r_p, hash);
+}
+
+// ---- the MerkleSumTree circuit's witness (DESIGN.md section 13) -----------------------------------------------------------------
+// The advice columns of circuits.merkle_sum_tree() for one inclusion path, filled as the reference's chip assigns them
+// (/root/reference/src/chips/merkle_sum_tree.rs:140-352; the Pow5 and Lt chips as recalled in synthesis.py).  One lane per
+// (user, level): it writes the level's "merkle prove layer" rows, the hash's initial-state and pad-and-add rows and, through the
+// sink of poseidon_permute, the trace of the permutation; the lane of level 0 adds the leaf rows, the lane of the last level the
+// less-than region and the root.  Cells the chip leaves unassigned are zero: the caller clears the columns first.
+//
+// Row placement (synthesis.MerkleSumTreeLayout restates it; tests compare the two for every depth):
+//     row 0 leaf hash, row 1 leaf balance; level l at 2 + l * level_rows: prove layer (2 rows), initial state (1), pad-and-add (3),
+//     permute state (perm_rows = r_f + r_p / 2 + 1); then the less-than row; then 5 constants per level in rc_b[0] (fixed only).
+constexpr uint32_t WITNESS_ADVICE = 20;      // a b c d e | state[5] | partial_sbox | lt | diff[8]
+constexpr uint32_t WITNESS_U8_ROWS = 256;    // the LtChip's range table occupies rows 0..255 of its own fixed column
+struct WitnessLayout {
+  uint32_t perm_rows, level_rows, lt_row, const_row, rows_used;
+};
+HM_HD WitnessLayout merkle_sum_witness_layout(uint32_t depth, uint32_t r_f, uint32_t r_p) {
+  WitnessLayout w;
+  w.perm_rows = r_f + r_p / 2 + 1;
+  w.level_rows = 2 + 1 + 3 + w.perm_rows;
+  w.lt_row = 2 + depth * w.level_rows;
+  w.const_row = w.lt_row + 1;
+  w.rows_used = w.const_row + 5 * depth;
+  if (w.rows_used < WITNESS_U8_ROWS) w.rows_used = WITNESS_U8_ROWS;
+  return w;
+}
+
+struct PsConst {
+  static constexpr uint32_t TO_CANON[9] = {32u, 0, 0, 0, 0, 0, 0, 0, 0};     // x * 32 * 2^-261 = x * 2^-256: Montgomery words -> the integer
+  // 2^517 mod r: v * 2^517 * 2^-261 = v * 2^256, a small integer -> its Montgomery words
+  static constexpr uint32_t SMALL2EXT[9] = {0x142db4dfu, 0x19d6990eu, 0x1472f48cu, 0x06dbe7e3u, 0x0b84d579u, 0x10f9faf7u, 0x121f4380u,
+                                            0x17a112deu, 0x001275c7u};
+};
+
+struct alignas(16) PsQuad {
+  uint32_t v[4];
+};
+HM_HD void ps_get_words(const uint32_t* p, uint32_t (&w)[8]) {
+  const PsQuad* q = reinterpret_cast<const PsQuad*>(p);
+  const PsQuad lo = q[0], hi = q[1];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    w[i] = lo.v[i];
+    w[4 + i] = hi.v[i];
+  }
+}
+HM_HD void ps_put_words(uint32_t* p, const uint32_t (&w)[8]) {
+  PsQuad* q = reinterpret_cast<PsQuad*>(p);
+  q[0] = PsQuad{{w[0], w[1], w[2], w[3]}};
+  q[1] = PsQuad{{w[4], w[5], w[6], w[7]}};
+}
+
+// internal form -> Montgomery words as a division by 32 (v * 2^261 -> v * 2^256): one reduction step on the low 5 bits and a shift,
+// 9 narrow multiplies instead of fe_to_ext's full product by a constant.  a: normalised limbs, value < 2^261.  Canonical output.
+HM_HD void fe_to_ext_shift(uint32_t (&w)[8], const Fr& a) {
+#ifdef HM_BOUNDS
+  HM_CHECK(a.lb <= MASK29 && a.tb < (1ull << 29), "fe_to_ext_shift needs normalised limbs");
+#endif
+  const uint32_t m = (a.l[0] * FrParams::INV29) & 31u;        // a + m * MOD = 0 mod 32
+  uint32_t t[9];
+  uint64_t carry = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint64_t v = (uint64_t)a.l[i] + (uint64_t)m * FrParams::MOD[i] + carry;
+    t[i] = (uint32_t)v & MASK29;
+    carry = v >> 29;
+  }
+  t[8] = (uint32_t)((uint64_t)a.l[8] + (uint64_t)m * FrParams::MOD[8] + carry);     // < 2^29 + 2^30
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) r.l[i] = (t[i] >> 5) | ((t[i + 1] & 31u) << 24);
+  r.l[8] = t[8] >> 5;
+#ifdef HM_BOUNDS
+  HM_CHECK((t[0] & 31u) == 0, "fe_to_ext_shift: the sum is not divisible by 32");
+  {
+    const double vb = (a.vb + 31.0) / 32.0;
+    set_bounds(r, vb, MASK29, top_bound_from_value<FrParams>(vb));
+    HM_CHECK(r.l[8] <= r.tb, "fe_to_ext_shift result exceeds its bound");
+  }
+#endif
+  fe_pack(w, fe_canonical(r));
+}
+
+// Montgomery words (any 256-bit value) -> the canonical integer as 8 little-endian words
+HM_HD void fr_ext_to_int(const uint32_t (&w)[8], uint32_t (&out)[8]) {
+  fe_pack(out, fe_canonical(fe_mul(fe_unpack<FrParams>(w), fe_const<FrParams>(PsConst::TO_CANON))));
+}
+// an integer below 2^29 -> its Montgomery words
+HM_HD void fr_small_to_ext(uint32_t v, uint32_t (&out)[8]) {
+  Fr x = fe_zero<FrParams>();
+  x.l[0] = v & MASK29;
+  HM_DECLARE(x, 1.0);
+  fe_pack(out, fe_canonical(fe_mul(x, fe_const<FrParams>(PsConst::SMALL2EXT))));
+}
+
+// LtChip::assign on the integers lhs, rhs (canonical, 8 words each): lt = lhs < rhs and the low 8 bytes of
+// (lhs - rhs + lt * 2^64) mod r.  r mod 2^64 = 0x43e1f593f0000001.
+HM_HD void lt_chip_values(const uint32_t (&lhs)[8], const uint32_t (&rhs)[8], uint32_t& lt, uint64_t& diff) {
+  bool less = false, decided = false;
+#pragma unroll
+  for (int i = 7; i >= 0; --i) {
+    less = (!decided && lhs[i] != rhs[i]) ? lhs[i] < rhs[i] : less;
+    decided = decided || lhs[i] != rhs[i];
+  }
+  uint32_t e[8];                       // |lhs - rhs|
+  uint32_t borrow = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t hi = less ? rhs[i] : lhs[i], lo = less ? lhs[i] : rhs[i];
+    const uint64_t t = (uint64_t)hi - lo - borrow;
+    e[i] = (uint32_t)t;
+    borrow = (uint32_t)(t >> 63);
+  }
+  const uint64_t e_lo = (uint64_t)e[0] | ((uint64_t)e[1] << 32);
+  const bool above = (e[3] | e[4] | e[5] | e[6] | e[7]) != 0 || e[2] > 1 || (e[2] == 1 && e_lo != 0);   // e > 2^64
+  lt = less ? 1u : 0u;
+  diff = !less ? e_lo : (above ? 0x43e1f593f0000001ull - e_lo : 0ull - e_lo);
+}
+
+struct WitnessArgs {
+  const uint32_t* leaves;        // m x 16 words: hash, balance
+  const uint32_t* siblings;      // m x depth x 16
+  const uint64_t* indices;       // m: bit l = the path's node is the right child at level l
+  const uint32_t* nodes;         // the built tree (2^(depth+1) - 1 nodes of 16 words), or null
+  const uint32_t* run;           // without a tree: m x (depth - 1) x 16, the path's node after levels 1 .. depth - 1 (merkle_sum_chain_lane)
+  uint32_t* advice;              // m x WITNESS_ADVICE x 2^log_n x 8, cleared
+  uint32_t* instance;            // m x 4 x 8: leaf hash, leaf balance, root, assets
+  const uint32_t* consts;
+  uint64_t m;
+  uint32_t depth, log_n, r_f, r_p;
+  uint32_t assets[8];
+};
+
+// the rows of "permute state" into the columns state[0..4] (advice 5..9) and partial_sbox (10) of one hash
+struct WitnessSink {
+  uint32_t* state0;              // word 0 of column state[0] at the region's first row
+  uint64_t col_words;            // words from one column to the next
+  template <int W>
+  HM_HD void row(uint32_t i, const Fr (&s)[W]) const {
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      uint32_t w[8];
+      fe_to_ext_shift(w, s[j]);
+      ps_put_words(state0 + j * col_words + (uint64_t)i * 8, w);
+    }
+  }
+  HM_HD void sbox0(uint32_t i, const Fr& x) const {
+    uint32_t w[8];
+    fe_to_ext_shift(w, x);
+    ps_put_words(state0 + 5 * col_words + (uint64_t)i * 8, w);
+  }
+};
+
+// the path's node after level l + 1, for l = 0 .. depth - 2, of user u: the chain that a built tree makes unnecessary
+HM_HD void merkle_sum_chain_lane(const WitnessArgs& a, uint64_t u, uint32_t* run) {
+  uint32_t node[2][8];
+  ps_get_words(a.leaves + u * 16, node[0]);
+  ps_get_words(a.leaves + u * 16 + 8, node[1]);
+  const uint64_t idx = a.indices[u];
+#pragma unroll 1
+  for (uint32_t l = 0; l + 1 < a.depth; ++l) {
+    uint32_t sib[2][8], kids[4][8];
+    ps_get_words(a.siblings + (u * a.depth + l) * 16, sib[0]);
+    ps_get_words(a.siblings + (u * a.depth + l) * 16 + 8, sib[1]);
+    const bool right = (idx >> l) & 1ull;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      kids[0][i] = right ? sib[0][i] : node[0][i];
+      kids[1][i] = right ? sib[1][i] : node[1][i];
+      kids[2][i] = right ? node[0][i] : sib[0][i];
+      kids[3][i] = right ? node[1][i] : sib[1][i];
+    }
+    merkle_sum_node_one(kids, a.consts, a.r_f, a.r_p, node[0], node[1]);
+    ps_put_words(run + (u * (a.depth - 1) + l) * 16, node[0]);
+    ps_put_words(run + (u * (a.depth - 1) + l) * 16 + 8, node[1]);
+  }
+}
+
+// everything level l of user u contributes to the witness (see the head of this section)
+HM_HD void merkle_sum_witness_lane(const WitnessArgs& a, uint64_t u, uint32_t l) {
+  const WitnessLayout lay = merkle_sum_witness_layout(a.depth, a.r_f, a.r_p);
+  const uint64_t col_words = (uint64_t)8 << a.log_n;
+  uint32_t* adv = a.advice + u * WITNESS_ADVICE * col_words;
+  const uint64_t base = 2 + (uint64_t)l * lay.level_rows;
+  const uint64_t idx = a.indices[u] & ((a.depth >= 64 ? 0 : (1ull << a.depth)) - 1);
+  const bool right = (idx >> l) & 1ull;
+
+  uint32_t kids[4][8], sum[8], w[8];
+  {
+    uint32_t prev[2][8], sib[2][8];
+    const uint32_t* p = l == 0 ? a.leaves + u * 16
+                        : a.nodes ? a.nodes + (((2ull << a.depth) - (2ull << (a.depth - l))) + (idx >> l)) * 16
+                                  : a.run + (u * (a.depth - 1) + (l - 1)) * 16;
+    ps_get_words(p, prev[0]);
+    ps_get_words(p + 8, prev[1]);
+    ps_get_words(a.siblings + (u * a.depth + l) * 16, sib[0]);
+    ps_get_words(a.siblings + (u * a.depth + l) * 16 + 8, sib[1]);
+    if (l == 0) {                                          // "assign leaf hash", "assign leaf balance"; instance rows 0, 1
+      ps_put_words(adv + 0 * col_words + 0 * 8, prev[0]);
+      ps_put_words(adv + 1 * col_words + 1 * 8, prev[1]);
+      ps_put_words(a.instance + u * 32, prev[0]);
+      ps_put_words(a.instance + u * 32 + 8, prev[1]);
+    }
+    // "merkle prove layer" row 0: previous node, sibling, index
+    ps_put_words(adv + 0 * col_words + base * 8, prev[0]);
+    ps_put_words(adv + 1 * col_words + base * 8, prev[1]);
+    ps_put_words(adv + 2 * col_words + base * 8, sib[0]);
+    ps_put_words(adv + 3 * col_words + base * 8, sib[1]);
+    fr_small_to_ext(right ? 1u : 0u, w);
+    ps_put_words(adv + 4 * col_words + base * 8, w);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      kids[0][i] = right ? sib[0][i] : prev[0][i];
+      kids[1][i] = right ? sib[1][i] : prev[1][i];
+      kids[2][i] = right ? prev[0][i] : sib[0][i];
+      kids[3][i] = right ? prev[1][i] : sib[1][i];
+    }
+  }
+  fr_add_ext(kids[1], kids[3], sum);
+  // row 1: left, right, their sum; the hash's input row and the pad-and-add output row repeat the four words
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    ps_put_words(adv + j * col_words + (base + 1) * 8, kids[j]);
+    ps_put_words(adv + (5 + j) * col_words + (base + 4) * 8, kids[j]);
+    ps_put_words(adv + (5 + j) * col_words + (base + 5) * 8, kids[j]);
+  }
+  ps_put_words(adv + 4 * col_words + (base + 1) * 8, sum);
+  // the capacity word: "initial state", pad-and-add rows 0 and 2 (the four rate words of the initial state are zero)
+  fe_to_ext_shift(w, ps_load9(a.consts + ((size_t)(a.r_f + a.r_p) * 5 + 25) * 9));
+  ps_put_words(adv + 9 * col_words + (base + 2) * 8, w);
+  ps_put_words(adv + 9 * col_words + (base + 3) * 8, w);
+  ps_put_words(adv + 9 * col_words + (base + 5) * 8, w);
+
+  if (l + 1 == a.depth) {          // "enforce sum to be less than total assets": a = the sum, b = the assets, c = check = 1, LtChip
+    const uint64_t row = lay.lt_row;
+    uint32_t si[8], ai[8], lt;
+    uint64_t diff;
+    ps_put_words(adv + 0 * col_words + row * 8, sum);
+    ps_put_words(adv + 1 * col_words + row * 8, a.assets);
+    ps_put_words(a.instance + u * 32 + 24, a.assets);
+    fr_ext_to_int(sum, si);
+    fr_ext_to_int(a.assets, ai);
+    lt_chip_values(si, ai, lt, diff);
+    fr_small_to_ext(1u, w);
+    ps_put_words(adv + 2 * col_words + row * 8, w);
+    fr_small_to_ext(lt, w);
+    ps_put_words(adv + 11 * col_words + row * 8, w);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      fr_small_to_ext((uint32_t)(diff >> (8 * i)) & 0xffu, w);
+      ps_put_words(adv + (12 + i) * col_words + row * 8, w);
+    }
+  }
+
+  Fr s[5];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) s[j] = fe_from_ext<FrParams>(kids[j]);
+  s[4] = ps_load9(a.consts + ((size_t)(a.r_f + a.r_p) * 5 + 25) * 9);
+  const WitnessSink sink{adv + 5 * col_words + (base + 6) * 8, col_words};
+  poseidon_permute<5>(s, a.consts, a.r_f, a.r_p, sink);
+  if (l + 1 == a.depth) {                                  // the root: instance row 2
+    fe_to_ext_shift(w, s[0]);
+    ps_put_words(a.instance + u * 32 + 16, w);
+  }
 }
 
 #if defined(__HIPCC__)
@@ -208,5 +493,18 @@ __global__ __launch_bounds__(PS_THREADS) void merkle_path_kernel(const uint32_t*
     ps_load_words(nodes + (node * words_per_node + e) * 8, w);
   }
   ps_store_words(out + t * 8, w);
+}
+// one lane per (user, level); the columns were cleared by the caller
+__global__ __launch_bounds__(PS_THREADS) void merkle_sum_witness_kernel(const WitnessArgs a) {
+  const uint64_t t = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
+  if (t >= a.m * a.depth) return;
+  merkle_sum_witness_lane(a, t / a.depth, (uint32_t)(t % a.depth));
+}
+
+// one lane per user: depth - 1 hashes in sequence (paths that come without a tree)
+__global__ __launch_bounds__(PS_THREADS) void merkle_sum_chain_kernel(const WitnessArgs a, uint32_t* __restrict__ run) {
+  const uint64_t u = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
+  if (u >= a.m) return;
+  merkle_sum_chain_lane(a, u, run);
 }
 #endif

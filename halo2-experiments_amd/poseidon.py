@@ -335,6 +335,25 @@ class MerkleSumTree(_Tree):
     def path(self, index: int) -> Tuple[List[int], List[int], List[int]]:
         return self.paths([index])[0]
 
+    def witness(self, indices, assets_sum: int, k: int, out=None):
+        """The MerkleSumTree circuit's witnesses of the inclusion paths of ``indices`` (``synthesis.merkle_sum_witness`` with the
+        path's nodes read from this tree; nothing leaves the device): -> (advice (m, 20, 2^k, 4), instance (m, 4, 4)) tensors."""
+        import torch
+
+        from .synthesis import merkle_sum_witness
+
+        idx = [int(i) for i in indices]
+        if not idx or any(not 0 <= i < (1 << self.depth) for i in idx):
+            raise IndexError(f"MerkleSumTree.witness: leaf indices must lie in [0, {1 << self.depth}) and there must be one at least")
+        d_idx = torch.tensor(idx, dtype=torch.int64, device=self.nodes.device)
+        sib = torch.empty((len(idx), self.depth, 2, 4), dtype=torch.int64, device=self.nodes.device)
+        with torch.cuda.device(self.nodes.device):
+            _lib.check(_lib.load().hm_merkle_paths_dev(ctypes.c_void_p(self.nodes.data_ptr()), self.depth, 2,
+                                                       ctypes.cast(ctypes.c_void_p(d_idx.data_ptr()), ctypes.POINTER(ctypes.c_uint64)),
+                                                       len(idx), ctypes.c_void_p(sib.data_ptr()), ctypes.c_void_p(_stream_ptr(self.nodes))))
+        leaves = self.nodes[d_idx].contiguous()
+        return merkle_sum_witness(self.spec, leaves, sib, d_idx, assets_sum, k, nodes=self.nodes, out=out)
+
     @staticmethod
     def verify_path(leaf: Tuple[int, int], path, spec: Optional[Spec] = None) -> Tuple[int, int]:
         """``compute_merkle_sum_root`` on host integers: fold (hash, balance) of a leaf up its path; -> (hash, balance) of the root."""

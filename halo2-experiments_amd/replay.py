@@ -126,7 +126,8 @@ def run_replay(shape_name: str, device=None, group=None, include_host_pointer_es
     ``min_cosets`` (with the coset route; default on): evaluate_h on the j - 1 cosets that DETERMINE the quotient instead of all
     E = 2^(extended_k - k) (EvaluationDomain.combine_cosets(cosets=...): h has fewer than n (j - 1) coefficients -- 5 of 8 cosets for
     the MerkleSumTree circuit); the cosets are then dealt from the last rank backwards, rank 0 gets one last.  The same h for a
-    satisfied circuit, word for word (tests/test_mini_prover_gpu.py); the replay's columns are synthetic and its h is not checked.
+    satisfied circuit, word for word (tests/test_mini_prover_gpu.py on a toy circuit, tests/test_witness_proof_gpu.py on the real
+    MerkleSumTree witness at k = 9 and k = 10); the replay's own columns are synthetic and its h is not checked.
     ``by_cosets``: the extended-domain steps (coset transforms, evaluate_h, the inverse transform of h) one coset of the
     n-th roots at a time (EvaluationDomain.coeff_to_coset).  Default: on with more than one rank from k = 14 -- the E = 2^(extended_k
     - k) cosets are dealt over the ranks, every rank transforms all columns onto ITS cosets from the coefficient arrays, runs

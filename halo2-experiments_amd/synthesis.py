@@ -1,0 +1,400 @@
+"""What ``MerkleSumTreeCircuit::synthesize`` decides, for ``circuits.merkle_sum_tree(spec)``: where every region lies, what the fixed
+columns hold, which cells are copy-constrained, and the advice columns themselves -- on Python integers here (``assign_ints``, the
+CPU twin) and on the GPU through the C ABI (``merkle_sum_witness``, csrc/poseidon.inc: one lane per (user, level), the Pow5 chip's
+trace of every Poseidon round written straight into the columns).  DESIGN.md section 13.
+
+TRANSCRIBED from the reference (read as text):
+    "assign leaf hash", "assign leaf balance"        /root/reference/src/chips/merkle_sum_tree.rs:140-171
+    "merkle prove layer" (two rows per level)        :182-286   bool + swap selectors on row 0, sum selector on row 1, swap by index :227-263
+    the hash of [left_hash, left_balance, right_hash, right_balance]   :289-300, src/chips/poseidon/hash.rs:75-89
+    "enforce sum to be less than total assets"       :317-352   a = the sum (copied), b = the assets (from instance row 3), c = check = 1
+    expose_public rows 0, 1, 2; instance row 3       src/circuits/merkle_sum_tree.rs:50-55,96, chips/merkle_sum_tree.rs:329-335
+RECALLED (the crates are git dependencies that are not at hand, as for the gates in circuits.py):
+    halo2_gadgets Pow5Chip -- "initial state": one row, the WIDTH state words assigned from constants (0 .. 0, RATE * 2^64), i.e.
+    copy-constrained to cells of rc_b[0], the ``enable_constant`` column; "pad-and-add": the initial state copied to row 0, the
+    message copied to row 1 (s_pad_and_add there), their sum on row 2; "permute state": the sum copied to row 0, then one row per
+    full round and one per PAIR of partial rounds (partial_sbox = the first S-box output of the pair; rc_a / rc_b = the round
+    constants of the first / second round), and the final state on the last row, whose word 0 is the digest.
+    LtChip::assign -- lt = lhs < rhs, diff = lhs - rhs + lt * 2^64 as 8 little-endian bytes; the u8 table in rows 0 .. 255.
+
+Row placement: the regions follow one another in ``synthesize`` order, each starting at the first row that no earlier region uses;
+the two regions that touch fixed columns only are placed by column: the u8 table in rows 0 .. 255 of its own column, the constants
+in rc_b[0] after the last region.  Upstream's ``SimpleFloorPlanner`` packs every region per column and may start some earlier; that
+cannot be pinned without the crate.  Every legal placement gives a valid circuit and the gates only use rotations inside a region,
+so this is A valid layout of the reference's circuit, not a row-for-row copy of upstream's.
+"""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+from .arithmetic import _ptr
+from .circuits import ConstraintSystem, merkle_sum_tree
+from .domain import FR_MODULUS, fr_words
+from .poseidon import Spec, default_spec, ints_to_words
+
+R = FR_MODULUS
+Cell = Tuple[str, int, int]            # (kind, column, row)
+
+# circuits.merkle_sum_tree()'s allocation order (asserted against the constraint system in MerkleSumTreeLayout.__init__)
+A, B, C, D, E = range(5)
+STATE = tuple(range(5, 10))
+PARTIAL_SBOX, LT = 10, 11
+DIFF = tuple(range(12, 20))
+N_ADVICE = 20
+BOOL_S, SWAP_S, SUM_S, LT_S = range(4)
+RC_A = tuple(range(4, 9))
+RC_B = tuple(range(9, 14))
+S_FULL, S_PARTIAL, S_PAD, U8 = 14, 15, 16, 17
+N_FIXED = 18
+BLINDING_ROWS = 6                       # blinding_factors + 1: the rows create_proof keeps for itself
+
+
+@dataclass
+class Region:
+    name: str
+    start: int
+    height: int
+    columns: Tuple[Tuple[str, int], ...]
+
+    @property
+    def rows(self) -> range:
+        return range(self.start, self.start + self.height)
+
+
+class MerkleSumTreeLayout:
+    """A pure function of (depth, k, spec); see the module docstring for what is transcribed and what is recalled."""
+
+    def __init__(self, depth: int, k: int, spec: Optional[Spec] = None):
+        spec = default_spec(5) if spec is None else spec
+        if spec.width != 5:
+            raise ValueError("MerkleSumTreeLayout: needs a width-5 spec")
+        if not 1 <= depth <= 32:
+            raise ValueError("MerkleSumTreeLayout: depth must be 1 .. 32")
+        if spec.r_f % 2 or spec.r_p % 2:
+            raise ValueError("MerkleSumTreeLayout: the Pow5 chip needs even r_f and r_p")
+        self.depth, self.k, self.n, self.spec = depth, k, 1 << k, spec
+        self.perm_rows = spec.r_f + spec.r_p // 2 + 1
+        adv = lambda *cols: tuple(("advice", c) for c in cols)
+        regions: List[Region] = [Region("load u8 range check table", 0, 256, (("fixed", U8),))]
+        row = 0
+
+        def place(name: str, height: int, columns) -> Region:
+            nonlocal row
+            regions.append(Region(name, row, height, tuple(columns)))
+            row += height
+            return regions[-1]
+
+        place("assign leaf hash", 1, adv(A))
+        place("assign leaf balance", 1, adv(B))
+        self.level_start: List[int] = []
+        for l in range(depth):
+            self.level_start.append(row)
+            place(f"merkle prove layer {l}", 2, adv(A, B, C, D, E) + (("fixed", BOOL_S), ("fixed", SWAP_S), ("fixed", SUM_S)))
+            place(f"initial state {l}", 1, adv(*STATE))
+            place(f"pad-and-add {l}", 3, adv(*STATE) + (("fixed", S_PAD),))
+            place(f"permute state {l}", self.perm_rows,
+                  adv(*STATE, PARTIAL_SBOX) + tuple(("fixed", c) for c in RC_A + RC_B + (S_FULL, S_PARTIAL)))
+        self.level_rows = 6 + self.perm_rows
+        self.lt_row = row
+        place("enforce sum to be less than total assets", 1, adv(A, B, C, LT, *DIFF) + (("fixed", LT_S),))
+        self.const_row = row
+        place("constants", 5 * depth, (("fixed", RC_B[0]),))
+        self.regions = regions
+        self.used_rows = max(row, 256)
+        if self.used_rows > self.n - BLINDING_ROWS:
+            raise ValueError(f"MerkleSumTreeLayout: depth {depth} needs {self.used_rows} rows, 2^{k} - {BLINDING_ROWS} is fewer "
+                             f"(min_k = {self.min_k(depth, spec)})")
+
+    @staticmethod
+    def rows_needed(depth: int, spec: Optional[Spec] = None) -> int:
+        spec = default_spec(5) if spec is None else spec
+        return max(2 + depth * (6 + spec.r_f + spec.r_p // 2 + 1) + 1 + 5 * depth, 256)
+
+    @classmethod
+    def min_k(cls, depth: int, spec: Optional[Spec] = None) -> int:
+        return (cls.rows_needed(depth, spec) + BLINDING_ROWS - 1).bit_length()
+
+    # rows of level l
+    def prove_row(self, l: int) -> int:
+        return self.level_start[l]
+
+    def init_row(self, l: int) -> int:
+        return self.level_start[l] + 2
+
+    def pad_row(self, l: int) -> int:
+        return self.level_start[l] + 3
+
+    def perm_row(self, l: int) -> int:
+        return self.level_start[l] + 6
+
+    def digest_cell(self, l: int) -> Cell:
+        return ("advice", STATE[0], self.perm_row(l) + self.perm_rows - 1)
+
+    def sum_cell(self, l: int) -> Cell:
+        return ("advice", E, self.prove_row(l) + 1)
+
+    def _round_of_row(self, i: int) -> int:
+        """the (first) round that row i of "permute state" holds"""
+        half, r_p = self.spec.r_f // 2, self.spec.r_p
+        if i < half:
+            return i
+        if i < half + r_p // 2:
+            return half + 2 * (i - half)
+        return half + r_p + (i - half - r_p // 2)
+
+    def check_constraint_system(self, cs: ConstraintSystem) -> None:
+        if (cs.num_advice, cs.num_fixed, cs.num_instance) != (N_ADVICE, N_FIXED, 1):
+            raise ValueError("MerkleSumTreeLayout: the constraint system is not circuits.merkle_sum_tree()")
+
+    def selector_rows(self) -> Dict[int, List[int]]:
+        """fixed column of a selector -> the rows where it is enabled"""
+        half, pairs = self.spec.r_f // 2, self.spec.r_p // 2
+        out: Dict[int, List[int]] = {c: [] for c in (BOOL_S, SWAP_S, SUM_S, LT_S, S_FULL, S_PARTIAL, S_PAD)}
+        for l in range(self.depth):
+            out[BOOL_S].append(self.prove_row(l))
+            out[SWAP_S].append(self.prove_row(l))
+            out[SUM_S].append(self.prove_row(l) + 1)
+            out[S_PAD].append(self.pad_row(l) + 1)
+            p = self.perm_row(l)
+            out[S_FULL] += [p + i for i in range(half)] + [p + half + pairs + i for i in range(half)]
+            out[S_PARTIAL] += [p + half + i for i in range(pairs)]
+        out[LT_S].append(self.lt_row)
+        return out
+
+    def fixed_columns(self) -> List[List[int]]:
+        """The N_FIXED fixed columns as integers: selectors, rc_a / rc_b per "permute state" row, the u8 table, the constants."""
+        rc, _, _ = self.spec.constants()
+        half, pairs = self.spec.r_f // 2, self.spec.r_p // 2
+        cols = [[0] * self.n for _ in range(N_FIXED)]
+        for c, rows in self.selector_rows().items():
+            for r in rows:
+                cols[c][r] = 1
+        for l in range(self.depth):
+            p = self.perm_row(l)
+            for i in range(self.perm_rows - 1):
+                rnd = self._round_of_row(i)
+                for j in range(5):
+                    cols[RC_A[j]][p + i] = rc[rnd][j]
+                    if half <= i < half + pairs:
+                        cols[RC_B[j]][p + i] = rc[rnd + 1][j]
+            for j in range(5):
+                cols[RC_B[0]][self.const_row + 5 * l + j] = (self.spec.rate << 64) if j == 4 else 0
+        for v in range(256):
+            cols[U8][v] = v
+        return cols
+
+    def copies(self) -> List[Tuple[Cell, Cell]]:
+        out: List[Tuple[Cell, Cell]] = [(("advice", A, 0), ("instance", 0, 0)), (("advice", B, 1), ("instance", 0, 1))]   # expose_public 0, 1
+        prev_hash, prev_balance = ("advice", A, 0), ("advice", B, 1)
+        for l in range(self.depth):
+            pr, ini, pad, perm = self.prove_row(l), self.init_row(l), self.pad_row(l), self.perm_row(l)
+            out += [(prev_hash, ("advice", A, pr)), (prev_balance, ("advice", B, pr))]
+            for j in range(5):
+                out.append((("fixed", RC_B[0], self.const_row + 5 * l + j), ("advice", STATE[j], ini)))     # assign_advice_from_constant
+                out.append((("advice", STATE[j], ini), ("advice", STATE[j], pad)))
+                out.append((("advice", STATE[j], pad + 2), ("advice", STATE[j], perm)))
+            for j in range(4):
+                out.append((("advice", j, pr + 1), ("advice", STATE[j], pad + 1)))
+            prev_hash, prev_balance = self.digest_cell(l), self.sum_cell(l)
+        out += [(prev_balance, ("advice", A, self.lt_row)), (("instance", 0, 3), ("advice", B, self.lt_row)),
+                (prev_hash, ("instance", 0, 2))]
+        return out
+
+    def instance(self, leaf: Tuple[int, int], root: int, assets: int) -> List[List[int]]:
+        col = [0] * self.n
+        col[0], col[1], col[2], col[3] = int(leaf[0]) % R, int(leaf[1]) % R, int(root) % R, int(assets) % R
+        return [col]
+
+    def assign_ints(self, leaf: Tuple[int, int], siblings: Sequence[Tuple[int, int]], indices: Sequence[int], assets_sum: int) -> List[List[int]]:
+        """The N_ADVICE advice columns as the chip assigns them.  Nothing is judged: an index of 2 or a sum above the assets
+        gives an unsatisfied witness, as in the reference's negative tests."""
+        if len(siblings) != self.depth or len(indices) != self.depth:
+            raise ValueError("assign_ints: the path must have `depth` siblings and indices")
+        rc, mds, _ = self.spec.constants()
+        half, r_p, rounds = self.spec.r_f // 2, self.spec.r_p, self.spec.r_f + self.spec.r_p
+        cap = self.spec.rate << 64
+        adv = [[0] * self.n for _ in range(N_ADVICE)]
+        h, b = int(leaf[0]) % R, int(leaf[1]) % R
+        adv[A][0], adv[B][1] = h, b
+        total = b
+        for l, ((eh, eb), index) in enumerate(zip(siblings, indices)):
+            eh, eb, index = int(eh) % R, int(eb) % R, int(index) % R
+            pr, ini, pad, perm = self.prove_row(l), self.init_row(l), self.pad_row(l), self.perm_row(l)
+            adv[A][pr], adv[B][pr], adv[C][pr], adv[D][pr], adv[E][pr] = h, b, eh, eb, index
+            msg = [h, b, eh, eb] if index == 0 else [eh, eb, h, b]                         # :227-234
+            for j in range(4):
+                adv[j][pr + 1] = msg[j]
+                adv[STATE[j]][pad + 1] = msg[j]
+                adv[STATE[j]][pad + 2] = msg[j]
+            adv[E][pr + 1] = (msg[1] + msg[3]) % R
+            adv[STATE[4]][ini] = adv[STATE[4]][pad] = adv[STATE[4]][pad + 2] = cap
+            s, row = msg + [cap], 0
+            for r in range(rounds):
+                full = r < half or r >= half + r_p
+                first = full or (r - half) % 2 == 0
+                if first:
+                    for j in range(5):
+                        adv[STATE[j]][perm + row] = s[j]
+                x = [(v + c) % R for v, c in zip(s, rc[r])]
+                x[0] = pow(x[0], 5, R)
+                if first and not full:
+                    adv[PARTIAL_SBOX][perm + row] = x[0]
+                row += first
+                if full:
+                    x[1:] = [pow(v, 5, R) for v in x[1:]]
+                s = [sum(m * v for m, v in zip(mrow, x)) % R for mrow in mds]
+            for j in range(5):
+                adv[STATE[j]][perm + row] = s[j]
+            h, b = s[0], adv[E][pr + 1]
+            total = (total + eb) % R
+        assets = int(assets_sum) % R
+        lt = int(total < assets)
+        diff = (total - assets + (lt << 64)) % R
+        adv[A][self.lt_row], adv[B][self.lt_row], adv[C][self.lt_row], adv[LT][self.lt_row] = b, assets, 1, lt
+        for i, byte in enumerate(diff.to_bytes(32, "little")[:8]):
+            adv[DIFF[i]][self.lt_row] = byte
+        return adv
+
+
+# ---- keygen's permutation columns -----------------------------------------------------------------------------------------------
+def permutation_cells(cs: ConstraintSystem, layout: MerkleSumTreeLayout) -> List[List[Tuple[int, int]]]:
+    """``permutation::keygen::Assembly``: sigma as cells -- out[j][i] = (j', i') for column j of ``cs.equality`` and row i; the
+    identity outside the copy cycles, every cycle rotated by one."""
+    index = {col: j for j, col in enumerate(cs.equality)}
+    n = layout.n
+    parent: Dict[Tuple[int, int], Tuple[int, int]] = {}
+
+    def find(c):
+        while parent.setdefault(c, c) != c:
+            parent[c] = parent[parent[c]]
+            c = parent[c]
+        return c
+
+    for (ka, ca, ra), (kb, cb, rb) in layout.copies():
+        if (ka, ca) not in index or (kb, cb) not in index:
+            raise ValueError(f"permutation_cells: a copy touches a column without equality: {(ka, ca)} / {(kb, cb)}")
+        a, b = find((index[(ka, ca)], ra)), find((index[(kb, cb)], rb))
+        if a != b:
+            parent[a] = b
+    cycles: Dict[Tuple[int, int], List[Tuple[int, int]]] = {}
+    for c in sorted(parent):
+        cycles.setdefault(find(c), []).append(c)
+    sigma = [[(j, i) for i in range(n)] for j in range(len(cs.equality))]
+    for members in cycles.values():
+        for c, nxt in zip(members, members[1:] + members[:1]):
+            sigma[c[0]][c[1]] = nxt
+    return sigma
+
+
+def permutation_columns_ints(cs: ConstraintSystem, layout: MerkleSumTreeLayout, omega: int, delta: int) -> List[List[int]]:
+    """The sigma columns as integers: cell (j, i) stands for delta^j * omega^i."""
+    n = layout.n
+    w = [1] * n
+    for i in range(1, n):
+        w[i] = w[i - 1] * omega % R
+    d = [pow(delta, j, R) for j in range(len(cs.equality))]
+    return [[d[j2] * w[i2] % R for (j2, i2) in col] for col in permutation_cells(cs, layout)]
+
+
+def permutation_columns(cs: ConstraintSystem, layout: MerkleSumTreeLayout, omega: int, delta: int, device="cuda"):
+    """The sigma columns as a (P, n, 4) int64 device tensor: the identity columns delta^j * omega^i from ``hm_fr_powers_dev`` /
+    ``hm_fr_scale_dev``, the cells of the copy cycles scattered in."""
+    import torch
+
+    from .arithmetic import _stream_ptr
+
+    lib, n, P = _lib.load(), layout.n, len(cs.equality)
+    out = torch.empty((P, n, 4), dtype=torch.int64, device=device)
+    with torch.cuda.device(out.device):
+        stream = ctypes.c_void_p(_stream_ptr(out))
+        for j in range(P):
+            _lib.check(lib.hm_fr_powers_dev(ctypes.c_void_p(out[j].data_ptr()), n, _ptr(fr_words(omega)), stream))
+            if j:
+                _lib.check(lib.hm_fr_scale_dev(ctypes.c_void_p(out[j].data_ptr()), n, _ptr(fr_words(pow(delta, j, R))), stream))
+    moved = [(j, i, c) for j, col in enumerate(permutation_cells(cs, layout)) for i, c in enumerate(col) if c != (j, i)]
+    if moved:
+        w = {}
+        vals = []
+        for _, _, (j2, i2) in moved:
+            if i2 not in w:
+                w[i2] = pow(omega, i2, R)
+            vals.append(pow(delta, j2, R) * w[i2] % R)
+        at = torch.tensor([j * n + i for j, i, _ in moved], dtype=torch.int64, device=out.device)
+        out.view(P * n, 4)[at] = torch.from_numpy(ints_to_words(vals).view(np.int64)).to(out.device)
+    return out
+
+
+# ---- the witness on the GPU -------------------------------------------------------------------------------------------------------
+def c_layout(depth: int, k: int, spec: Optional[Spec] = None) -> Dict[str, int]:
+    """``hm_merkle_sum_witness_layout``: the placement the kernel uses (no device needed)."""
+    spec = default_spec(5) if spec is None else spec
+    rows, n_adv, reg = ctypes.c_uint32(0), ctypes.c_uint32(0), (ctypes.c_uint32 * 4)()
+    _lib.check(_lib.load().hm_merkle_sum_witness_layout(spec.r_f, spec.r_p, depth, k, ctypes.byref(rows), ctypes.byref(n_adv), reg))
+    return {"used_rows": rows.value, "n_advice": n_adv.value, "perm_rows": reg[0], "level_rows": reg[1], "lt_row": reg[2],
+            "const_row": reg[3]}
+
+
+def merkle_sum_witness(spec: Optional[Spec], leaves, siblings, indices, assets_sum: int, k: int, nodes=None, out=None):
+    """The witnesses of m inclusion paths: ``leaves`` (m, 2, 4), ``siblings`` (m, depth, 2, 4) as ``hm_merkle_paths_dev`` writes
+    them and ``indices`` (m,) int64 (bit l = right child at level l) are GPU tensors of canonical Montgomery words; ``nodes`` is
+    the built tree's node tensor (the path's nodes are read from it) or None (they are hashed from the siblings).
+    -> (advice (m, N_ADVICE, 2^k, 4), instance (m, 4, 4)) int64 tensors, every word written; asynchronous on the current stream.
+    ``out``: an advice tensor to fill instead of a new one (it may be uninitialised)."""
+    import torch
+
+    from .arithmetic import _stream_ptr, _tensor_rows
+
+    spec = default_spec(5) if spec is None else spec
+    m = _tensor_rows(leaves, 8, "leaves")
+    if m == 0:
+        raise ValueError("merkle_sum_witness: no paths")
+    depth = _tensor_rows(siblings, 8 * m, "siblings")
+    if not (indices.is_cuda and indices.is_contiguous() and indices.element_size() == 8 and indices.numel() == m):
+        raise ValueError("merkle_sum_witness: indices must be m 64-bit integers on the GPU")
+    if nodes is not None and not (nodes.is_cuda and nodes.is_contiguous() and nodes.element_size() == 8
+                                  and nodes.numel() == ((2 << depth) - 1) * 8):
+        raise ValueError(f"merkle_sum_witness: nodes must be the contiguous (2^(depth+1) - 1, 2, 4) GPU tensor of a tree of depth {depth}")
+    for name, t in (("siblings", siblings), ("indices", indices), ("nodes", nodes), ("out", out)):
+        if t is not None and t.is_cuda and t.device != leaves.device:
+            raise ValueError(f"merkle_sum_witness: {name} is on {t.device}, leaves on {leaves.device}")
+    for name, t in (("leaves", leaves), ("siblings", siblings), ("nodes", nodes), ("out", out)):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"merkle_sum_witness: {name} must be 16-byte aligned")
+    n = 1 << k
+    if out is None:
+        out = torch.empty((m, N_ADVICE, n, 4), dtype=torch.int64, device=leaves.device)
+    elif not (out.is_cuda and out.is_contiguous() and out.element_size() == 8 and out.numel() == m * N_ADVICE * n * 4):
+        raise ValueError("merkle_sum_witness: out must be a contiguous (m, N_ADVICE, 2^k, 4) GPU tensor")
+    inst = torch.empty((m, 4, 4), dtype=torch.int64, device=leaves.device)
+    assets = np.ascontiguousarray(fr_words(int(assets_sum) % R))
+    with torch.cuda.device(leaves.device):
+        spec.call(_lib.load().hm_merkle_sum_witness_bn256_dev, depth, k, m, ctypes.c_void_p(leaves.data_ptr()),
+                  ctypes.c_void_p(siblings.data_ptr()), ctypes.cast(ctypes.c_void_p(indices.data_ptr()), ctypes.POINTER(ctypes.c_uint64)),
+                  _ptr(assets), ctypes.c_void_p(nodes.data_ptr()) if nodes is not None else None,
+                  ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(inst.data_ptr()), ctypes.c_void_p(_stream_ptr(leaves)))
+    return out, inst
+
+
+def merkle_sum_witness_host(spec: Optional[Spec], leaves: np.ndarray, siblings: np.ndarray, indices: np.ndarray, assets_sum: int, k: int):
+    """``merkle_sum_witness`` on numpy arrays through the host-pointer form (small m: the columns must stay below 256 MiB)."""
+    spec = default_spec(5) if spec is None else spec
+    lv = np.ascontiguousarray(np.asarray(leaves, dtype=np.uint64).reshape(-1, 2, 4))
+    m = lv.shape[0]
+    sb = np.ascontiguousarray(np.asarray(siblings, dtype=np.uint64).reshape(m, -1, 2, 4))
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(m))
+    adv = np.zeros((m, N_ADVICE, 1 << k, 4), dtype=np.uint64)
+    inst = np.zeros((m, 4, 4), dtype=np.uint64)
+    p = _ptr
+    spec.call(_lib.load().hm_merkle_sum_witness_bn256, sb.shape[1], k, m, p(lv), p(sb), p(idx), p(np.ascontiguousarray(fr_words(int(assets_sum) % R))),
+              p(adv), p(inst))
+    return adv, inst
+
+
+def columns_to_words(cols: Sequence[Sequence[int]]) -> np.ndarray:
+    """integer columns -> (len(cols), n, 4) uint64 Montgomery words (what the device tensors hold)"""
+    return np.stack([ints_to_words(c) for c in cols])

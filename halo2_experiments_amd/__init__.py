@@ -5,7 +5,7 @@ Host-side mirror of ``halo2_proofs::arithmetic`` (``best_multiexp``, ``best_fft`
 
 The sources live in ``halo2-experiments_amd/`` (the directory name the project layout prescribes; not a valid
 Python identifier): this package is the importable name, and its ``__path__`` points there, so every submodule
-(``_lib``, ``arithmetic``, ``domain``, ``kzg``, ``poseidon``, ``replay``, ``sharding``) is an ordinary module of this package
+(``_lib``, ``arithmetic``, ``domain``, ``kzg``, ``poseidon``, ``replay``, ``sharding``, ``synthesis``) is an ordinary module of this package
 with an ordinary ``__spec__`` / ``__file__``.
 """
 import os as _os
@@ -21,10 +21,12 @@ from .arithmetic import (bases_info, batch_invert, best_fft, best_multiexp, best
                          release_bases)
 from .domain import EvaluationDomain  # noqa: F401
 from .poseidon import MerkleSumTree, MerkleTree, Spec, poseidon_hash, poseidon_hash_host  # noqa: F401
+from .synthesis import MerkleSumTreeLayout, merkle_sum_witness, merkle_sum_witness_host, permutation_columns  # noqa: F401
 
 __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_multiexp_submit", "best_multiexp_wait", "best_fft",
            "register_bases", "release_bases", "bases_info", "g1_fixed_base_mul", "g1_fft", "g1_fft_host", "g1_compress", "g1_compress_host",
            "g1_decompress", "g1_decompress_host", "g1_check", "g1_check_host", "g_to_lagrange", "msm_stats", "kate_division", "kate_division_batch", "grand_product",
            "grand_product_batch", "batch_invert",
            "linear_combination", "random_fr", "permute_expression_pair", "permute_expression_pairs", "EvaluationDomain",
-           "Spec", "poseidon_hash", "poseidon_hash_host", "MerkleSumTree", "MerkleTree"]
+           "Spec", "poseidon_hash", "poseidon_hash_host", "MerkleSumTree", "MerkleTree", "MerkleSumTreeLayout", "merkle_sum_witness",
+           "merkle_sum_witness_host", "permutation_columns"]

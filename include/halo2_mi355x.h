@@ -533,6 +533,28 @@ int hm_merkle_tree_build_dev(uint64_t handle, const void* d_leaves, uint32_t dep
  * words_per_node = elements per node (2 sum tree, 1 plain tree); d_indices is DEVICE memory; an index >= 2^depth yields zeros. */
 int hm_merkle_paths_dev(const void* d_nodes, uint32_t depth, uint32_t words_per_node, const uint64_t* d_indices, size_t m, void* d_out,
                         void* stream);
+/* The witness of the reference's MerkleSumTree circuit (one inclusion path per user), filled on the GPU: the advice columns as
+ * MerkleSumTreeChip::synthesize assigns them, the Pow5 chip's trace of every Poseidon round among them.
+ * layout: the rows and columns the call below fills for a spec with r_f / r_p rounds (r_p even); needs no device.  out_regions, unless
+ * NULL, receives 4 numbers: rows of a "permute state" region, rows of one level, the row of the less-than region, the first row
+ * of the constants.  HM_ERR_BAD_ARG for depth 0 or above 32, an odd r_f or r_p, log_n above 24, or rows_used > 2^log_n - 6.
+ * witness: m users; d_leaves m x 2 elements (hash, balance), d_siblings m x depth x 2 elements as hm_merkle_paths_dev writes them,
+ * d_indices m u64 (bit l = the path's node is the RIGHT child at level l; higher bits are ignored), assets_sum one element in HOST
+ * memory; all elements canonical.  d_nodes_or_null: the tree hm_merkle_sum_tree_build_dev built (depth <= 30), from which the
+ * path's nodes are read; NULL: they are hashed from the siblings, one chain per user.  d_advice: m x n_advice x 2^log_n elements
+ * (column c of user u is contiguous), every word of which is written (unassigned cells and the last rows are zero: blinding is the
+ * prover's business); d_instance: m x 4 elements (leaf hash, leaf balance, root, assets).  Nothing is judged: a sum above the
+ * assets gives an unsatisfied witness.  Asynchronous on `stream`.  Arguments are checked before anything is launched.  Every device
+ * pointer must be 16-byte aligned (elements are moved as two 16-byte halves); d_nodes must hold all 2^(depth+1) - 1 nodes of `depth`.
+ * Host form: m * n_advice * 2^log_n * 32 bytes <= 256 MiB; outputs are written only by the final copies. */
+int hm_merkle_sum_witness_layout(uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, uint32_t* out_rows_used,
+                                 uint32_t* out_n_advice, uint32_t* out_regions);
+int hm_merkle_sum_witness_bn256_dev(uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const void* d_leaves,
+                                    const void* d_siblings, const uint64_t* d_indices, const uint64_t* assets_sum,
+                                    const void* d_nodes_or_null, void* d_advice, void* d_instance, void* stream);
+int hm_merkle_sum_witness_bn256(uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const uint64_t* leaves,
+                                const uint64_t* siblings, const uint64_t* indices, const uint64_t* assets_sum, uint64_t* advice,
+                                uint64_t* instance);
 
 /* ---- introspection --------------------------------------------------------------------------- */
 
