@@ -22,6 +22,7 @@
 #include <map>
 
 #include "g1.h"
+#include "graph_lower.h"
 #include "hm_internal.h"
 #include "host_fr.h"
 
@@ -29,33 +30,8 @@ namespace hm {
 
 constexpr int GE_THREADS = 256;
 
-enum GraphOp : uint32_t { GOP_ADD = 0, GOP_SUB = 1, GOP_MUL = 2, GOP_SQUARE = 3, GOP_DOUBLE = 4, GOP_NEGATE = 5, GOP_STORE = 6, GOP_MULADD = 7 };
-enum GraphSrc : uint32_t { GSRC_CONST = 0, GSRC_INTER = 1, GSRC_COLUMN = 2, GSRC_PREV = 3 };
-// a source is one word: kind (bits 30..31) | rotation index (bits 20..29) | index (bits 0..19); a column source uses
-// index bits 0..13 for the column and bits 14..19 for the column's log2 row count when it is SHORTER than the domain
-// (read at row mod 2^that; 0 = a full-size column): the period lives in the instruction, not in a per-call table.
-__host__ __device__ inline uint32_t gsrc_kind(uint32_t s) { return s >> 30; }
-__host__ __device__ inline uint32_t gsrc_rot(uint32_t s) { return (s >> 20) & 1023u; }
-__host__ __device__ inline uint32_t gsrc_index(uint32_t s) { return s & 0xfffffu; }
-__host__ __device__ inline uint32_t gsrc_column(uint32_t s) { return s & 0x3fffu; }
-__host__ __device__ inline uint32_t gsrc_log_rows(uint32_t s) { return (s >> 14) & 63u; }
-
-struct GraphCalc {      // device form: 5 words; op carries the forwarding flags in bits 8..11
-  uint32_t op, a, b, c, target;
-};
-// Expression trees are evaluated depth first, so the result of calculation k is very often an operand of k + 1 and of
-// nothing else (45 % of all intermediate reads and 55 % of all writes of the MerkleSumTree program): the lowering marks
-// those operands "take the previous result from registers" and those targets "never stored", which removes that share
-// of the [slot][word][lane] scratch traffic -- the interpreter is bound by it, not by the arithmetic.
-constexpr uint32_t GF_A_PREV = 1u << 8, GF_B_PREV = 1u << 9, GF_C_PREV = 1u << 10, GF_NO_STORE = 1u << 11;
-// Lazy reductions.  An intermediate is a normalised element (29-bit limbs) of value < GE_CAP * r, not < 3r: products
-// accept that (inputs < 18r give outputs < 3r; the column sums depend on the limbs only), so a sum or difference needs
-// its ~50-instruction modular reduction only when its STATIC bound -- propagated through the program at lowering time --
-// would pass GE_CAP.  GF_NO_REDUCE: carry propagation only.  GF_SUB_WIDE: the subtrahend may exceed 3r, so the
-// subtraction adds 20r instead of 4r (and is always reduced).  Bounds of every combination: hc_graph_bounds_closure
-// (host_check.cpp, HM_BOUNDS build), tests/test_ff29_host.py.
-constexpr uint32_t GF_NO_REDUCE = 1u << 12, GF_SUB_WIDE = 1u << 13;
-constexpr double GE_CAP = 16.0, GE_COLUMN_BOUND = 6.0;     // a packed 256-bit word is < 2^256 < 5.3 r whatever it holds
+// the instruction encoding (GraphOp, GraphSrc, GraphCalc, GF_*, GE_CAP ...), graph_validate and graph_lower_host: graph_lower.h,
+// shared with the host replay of host_check.cpp
 
 __device__ __forceinline__ Fr ge_reduce(const Fr& lazy) { return fe_reduce_small(fe_norm(lazy)); }   // any lazy sum < 2^261 -> < 3r
 
@@ -91,8 +67,6 @@ __device__ __forceinline__ Fr ge_from_internal(const uint32_t* __restrict__ p) {
 // shape), and tests/test_isa.py asserts on the built objects that no kernel of the library addresses a vector memory
 // instruction through its kernarg pointer.  tests/test_evaluation.py runs 256 columns, short-period columns and 16
 // per-call constants through it.
-constexpr uint32_t GE_MAX_COLUMNS = 256;
-constexpr uint32_t GE_MAX_DYN = 16;
 struct GraphColumns {
   const uint32_t* p[GE_MAX_COLUMNS];
   uint32_t dyn[GE_MAX_DYN * 9];   // challenges, beta, gamma, theta, y ... of THIS proof, internal form
@@ -160,6 +134,8 @@ __global__ __launch_bounds__(GE_THREADS) void graph_evaluate_kernel(const GraphC
       Fr out;
       const bool lazy = (cc.op & GF_NO_REDUCE) != 0, wide = (cc.op & GF_SUB_WIDE) != 0;      // wave-uniform
       auto settle = [&](const Fr& t) -> Fr { return lazy ? fe_norm(t) : ge_reduce(t); };
+      // hc_graph_replay (host_check.cpp) restates this switch for the HM_BOUNDS build; tests/test_graph_programs_gpu.py holds
+      // the two to the same words
       switch (op) {
         case GOP_ADD:
           out = settle(fe_add(a, src(cc.b, GF_B_PREV)));
@@ -213,154 +189,18 @@ __global__ __launch_bounds__(GE_THREADS) void graph_evaluate_kernel(const GraphC
 }
 
 // ---- host: program "compilation" (validation, Horner-free device form, liveness slot allocation) and launch ----
-static bool src_ok(uint32_t s, size_t n_const, size_t n_inter, size_t n_cols, size_t n_rot) {
-  switch (gsrc_kind(s)) {
-    case GSRC_CONST: return gsrc_index(s) < n_const;
-    case GSRC_INTER: return gsrc_index(s) < n_inter;
-    case GSRC_COLUMN: return gsrc_column(s) < n_cols && gsrc_rot(s) < n_rot && gsrc_log_rows(s) <= 30;
-    default: return true;
-  }
-}
-
-// Lower the validated program for one column format.  Steps: (1) copy propagation -- a Store of a constant, or of a
-// column when columns need no conversion, defines nothing new: its users read the source directly (upstream stores every
-// queried cell once so that the CPU loop converts it once; here a column read costs what a scratch read costs);
-// (2) forwarding flags and store elision (see GF_*); (3) linear-scan slot allocation by liveness for what is still stored.
+// Lower the validated program for one column format (graph_lower.h: copy propagation, forwarding and store elision, static
+// bounds, slot allocation) and upload the device form.
 static int graph_lower(const GraphProgram& g, bool internal_cols, GraphVariant& out) {
-  const size_t n_in = g.calcs5.size() / 5;
-  const uint32_t n_inter = g.n_intermediates;
-  auto nsrc_of = [](uint32_t op) { return op == GOP_MULADD ? 3 : (op <= GOP_MUL ? 2 : 1); };
-  // (1) copy propagation
-  std::vector<uint32_t> alias(n_inter, 0xffffffffu);          // intermediate -> the source word that replaces it
-  auto resolve = [&](uint32_t s) { return gsrc_kind(s) == GSRC_INTER && alias[gsrc_index(s)] != 0xffffffffu ? alias[gsrc_index(s)] : s; };
-  struct Ins { uint32_t op, src[3], target; };
-  std::vector<Ins> prog;
-  prog.reserve(n_in);
-  for (size_t k = 0; k < n_in; ++k) {
-    const uint32_t* c = &g.calcs5[5 * k];
-    Ins in{c[0], {resolve(c[1]), resolve(c[2]), resolve(c[3])}, c[4]};
-    if (in.op == GOP_STORE) {
-      const uint32_t kd = gsrc_kind(in.src[0]);
-      if (kd == GSRC_CONST || (kd == GSRC_COLUMN && internal_cols)) {
-        alias[in.target] = in.src[0];
-        continue;
-      }
-    }
-    prog.push_back(in);
-  }
-  uint32_t result_src = n_in ? resolve((GSRC_INTER << 30) | g.calcs5[5 * (n_in - 1) + 4]) : ((GSRC_INTER << 30) | 0u);
-  const size_t n = prog.size();
-  // (2) uses of every intermediate; forwarding and store elision
-  std::vector<std::vector<uint32_t>> uses(n_inter);
-  for (size_t k = 0; k < n; ++k)
-    for (int j = 0; j < nsrc_of(prog[k].op); ++j)
-      if (gsrc_kind(prog[k].src[j]) == GSRC_INTER) uses[gsrc_index(prog[k].src[j])].push_back((uint32_t)k);
-  const bool result_is_inter = n_in != 0 && gsrc_kind(result_src) == GSRC_INTER;
-  const bool result_prev = result_is_inter && n != 0 && prog[n - 1].target == gsrc_index(result_src);
-  std::vector<uint32_t> flags(n, 0);
-  std::vector<char> stored(n, 1);
-  for (size_t k = 0; k < n; ++k) {
-    if (k > 0)
-      for (int j = 0; j < nsrc_of(prog[k].op); ++j)
-        if (gsrc_kind(prog[k].src[j]) == GSRC_INTER && gsrc_index(prog[k].src[j]) == prog[k - 1].target)
-          flags[k] |= j == 0 ? GF_A_PREV : (j == 1 ? GF_B_PREV : GF_C_PREV);
-    bool only_next = true;
-    for (uint32_t u : uses[prog[k].target]) only_next = only_next && u == (uint32_t)k + 1;
-    const bool is_result = result_is_inter && prog[k].target == gsrc_index(result_src);
-    if (only_next && (!is_result || (result_prev && k == n - 1))) {     // read (if at all) by the next instruction only
-      stored[k] = 0;
-      flags[k] |= GF_NO_STORE;
-    }
-  }
-  // (2b) static value bounds (in units of r) -> which sums and differences keep their reduction
-  {
-    std::vector<double> vb(n_inter, 3.0);
-    auto bound_of = [&](uint32_t sw) -> double {
-      switch (gsrc_kind(sw)) {
-        case GSRC_CONST: return 1.0;                                  // canonical constants
-        case GSRC_INTER: return vb[gsrc_index(sw)];
-        case GSRC_COLUMN: return internal_cols ? GE_COLUMN_BOUND : 3.0;   // external words pass through a product
-        default: return 3.0;                                          // PreviousValue: a product output
-      }
-    };
-    for (size_t k = 0; k < n; ++k) {
-      const Ins& in = prog[k];
-      double r = 3.0;
-      uint32_t f = 0;
-      switch (in.op) {
-        case GOP_ADD: r = bound_of(in.src[0]) + bound_of(in.src[1]); break;
-        case GOP_DOUBLE: r = 2.0 * bound_of(in.src[0]); break;
-        case GOP_MULADD: r = 3.0 + bound_of(in.src[2]); break;
-        case GOP_SUB:
-        case GOP_NEGATE: {
-          const double minuend = in.op == GOP_SUB ? bound_of(in.src[0]) : 0.0;
-          const double subtrahend = bound_of(in.src[in.op == GOP_SUB ? 1 : 0]);
-          if (subtrahend <= 3.0) {
-            r = minuend + 4.0;
-          } else {
-            f |= GF_SUB_WIDE;                                         // reduced in the kernel whatever r is
-            r = 1e9;
-          }
-          break;
-        }
-        case GOP_STORE: r = bound_of(in.src[0]); f |= GF_NO_REDUCE; break;     // a copy
-        default: r = 3.0; f |= GF_NO_REDUCE; break;                   // Mul / Square: product outputs (the flag is not read)
-      }
-      if (!(f & (GF_NO_REDUCE | GF_SUB_WIDE))) {
-        if (r <= GE_CAP) f |= GF_NO_REDUCE;
-        else r = 3.0;                                                 // reduced
-      } else if (f & GF_SUB_WIDE) {
-        r = 3.0;
-      }
-      vb[in.target] = r;
-      flags[k] |= f;
-    }
-  }
-  // (3) slots for what is stored
-  std::vector<uint32_t> last_use(n_inter, 0), slot_of(n_inter, 0xffffffffu), free_slots;
-  for (size_t k = 0; k < n; ++k)
-    for (int j = 0; j < nsrc_of(prog[k].op); ++j)
-      if (gsrc_kind(prog[k].src[j]) == GSRC_INTER) last_use[gsrc_index(prog[k].src[j])] = (uint32_t)k;
-  if (result_is_inter && !result_prev) last_use[gsrc_index(result_src)] = (uint32_t)n;
-  std::multimap<uint32_t, uint32_t> expiring;                  // last use -> slot
-  std::vector<GraphCalc> dev(n);
-  uint32_t n_slots = 0;
-  auto remap = [&](uint32_t s) -> uint32_t {
-    if (gsrc_kind(s) != GSRC_INTER) return s;
-    const uint32_t sl = slot_of[gsrc_index(s)];
-    return (GSRC_INTER << 30) | (sl == 0xffffffffu ? 0u : sl);   // a never-stored operand is always taken from registers
-  };
-  for (size_t k = 0; k < n; ++k) {
-    const Ins& in = prog[k];
-    const int ns = nsrc_of(in.op);
-    GraphCalc d{in.op | flags[k], remap(in.src[0]), ns > 1 ? remap(in.src[1]) : 0u, ns > 2 ? remap(in.src[2]) : 0u, 0};
-    // slots whose value was read for the last time BEFORE this instruction are free (its own operands are read before
-    // its target is written, so a slot expiring AT k may be reused as k's target)
-    while (!expiring.empty() && expiring.begin()->first <= (uint32_t)k) {
-      free_slots.push_back(expiring.begin()->second);
-      expiring.erase(expiring.begin());
-    }
-    if (stored[k]) {
-      uint32_t slot;
-      if (!free_slots.empty()) {
-        slot = free_slots.back();
-        free_slots.pop_back();
-      } else {
-        slot = n_slots++;
-      }
-      slot_of[in.target] = slot;
-      // a value that is never read again still needs its slot for this one instruction
-      expiring.emplace(last_use[in.target] > (uint32_t)k ? last_use[in.target] : (uint32_t)k + 1, slot);
-      d.target = slot;
-    }
-    dev[k] = d;
-  }
+  GraphLowered low;
+  graph_lower_host(g.calcs5.data(), g.calcs5.size() / 5, g.n_intermediates, internal_cols, low);
+  const size_t n = low.calcs.size();
   out.n_calc = (uint32_t)n;
-  out.n_slots = n_slots ? n_slots : 1;
-  out.result_prev = result_prev ? 1u : 0u;
-  out.result_src = result_is_inter ? remap(result_src) : result_src;
+  out.n_slots = low.n_slots;
+  out.result_prev = low.result_prev;
+  out.result_src = low.result_src;
   HM_HIP_CHECK(hipMalloc(&out.d_calcs, std::max<size_t>(n, 1) * sizeof(GraphCalc)));
-  if (n) HM_HIP_CHECK(hipMemcpy(out.d_calcs, dev.data(), n * sizeof(GraphCalc), hipMemcpyHostToDevice));
+  if (n) HM_HIP_CHECK(hipMemcpy(out.d_calcs, low.calcs.data(), n * sizeof(GraphCalc), hipMemcpyHostToDevice));
   out.ready = true;
   return HM_OK;
 }
@@ -368,31 +208,13 @@ static int graph_lower(const GraphProgram& g, bool internal_cols, GraphVariant& 
 int graph_create(DeviceCtx& ctx, const uint32_t* calcs5, size_t n_calc, const uint64_t* constants_ext, size_t n_const_static,
                  size_t n_dynamic, const int32_t* rotations, size_t n_rot, size_t n_columns, uint32_t n_intermediates,
                  uint64_t* out_handle) {
-  if (n_dynamic > GE_MAX_DYN) return hm_fail(HM_ERR_BAD_ARG, "graph: more than 16 per-call constants");
-  const size_t n_const = n_const_static + n_dynamic;
-  if (n_calc > (1u << 24) || n_const >= (1u << 20) || n_rot > 1024 || n_columns > GE_MAX_COLUMNS || n_intermediates >= (1u << 20))
-    return hm_fail(HM_ERR_BAD_ARG, "graph: program too large for the instruction encoding");
+  if (const char* why = graph_validate(calcs5, n_calc, n_const_static, n_dynamic, n_rot, n_columns, n_intermediates))
+    return hm_fail(HM_ERR_BAD_ARG, why);
   auto g = std::make_unique<GraphProgram>();
   g->n_columns = n_columns;
   g->n_static = (uint32_t)n_const_static;
   g->n_dynamic = (uint32_t)n_dynamic;
   g->n_intermediates = n_intermediates;
-  // validate
-  std::vector<char> defined(n_intermediates, 0);
-  for (size_t k = 0; k < n_calc; ++k) {
-    const uint32_t* c = calcs5 + 5 * k;
-    if (c[0] > GOP_MULADD) return hm_fail(HM_ERR_BAD_ARG, "graph: unknown operation");
-    const int nsrc = c[0] == GOP_MULADD ? 3 : (c[0] <= GOP_MUL ? 2 : 1);
-    for (int j = 0; j < nsrc; ++j) {
-      const uint32_t s = c[1 + j];
-      if (!src_ok(s, n_const, n_intermediates, n_columns, n_rot)) return hm_fail(HM_ERR_BAD_ARG, "graph: source out of range");
-      if (gsrc_kind(s) == GSRC_INTER && !defined[gsrc_index(s)])
-        return hm_fail(HM_ERR_BAD_ARG, "graph: intermediate read before it is written");
-    }
-    if (c[4] >= n_intermediates) return hm_fail(HM_ERR_BAD_ARG, "graph: target out of range");
-    if (defined[c[4]]) return hm_fail(HM_ERR_BAD_ARG, "graph: intermediate written twice (every calculation owns its target)");
-    defined[c[4]] = 1;
-  }
   g->calcs5.assign(calcs5, calcs5 + 5 * n_calc);
   // constants -> internal form
   std::vector<uint32_t> c9(std::max<size_t>(n_const_static, 1) * 9, 0);

@@ -3,12 +3,16 @@
 // tests can (a) compare the exact code the kernels run with the oracle and (b) prove, by running
 // every formula once with its inputs declared at the class bounds, that no 64-bit column sum,
 // limb or lazy value can overflow for ANY input (the tracked bounds are data-independent).
+// It also holds the host replay of the GraphEvaluator (hc_graph_replay): graph.hip's lowering, shared through graph_lower.h,
+// and a restatement of its kernel's interpreter loop on these primitives.
 //
 // Build: g++ -O2 -std=c++17 -DHM_BOUNDS -shared -fPIC -o libhm_hostcheck.so host_check.cpp
 #include <cstring>
 #include <utility>
 
 #include "g1.h"
+#include "graph_lower.h"
+#include "host_fr.h"
 
 namespace hm {
 #include "g1_codec.inc"   // the per-point SRS codec formulas (its kernels are HIP-only)
@@ -89,6 +93,23 @@ void field_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t 
     store_ext(o + 4 * i, r);
   }
 }
+
+// ---- the GraphEvaluator on the host (graph.hip) ----
+typedef Fe<FrParams> GFr;
+GFr gr_reduce(const GFr& lazy) { return fe_reduce_small(fe_norm(lazy)); }                 // graph.hip: ge_reduce
+GFr gr_from_ext(const uint32_t* p) {                                                      // graph.hip: ge_from_ext
+  uint32_t w[8];
+  std::memcpy(w, p, 32);
+  return fe_mul(fe_unpack<FrParams>(w), fe_const<FrParams>(FrParams::EXT2INT));
+}
+GFr gr_from_internal(const uint32_t* p) {                                                 // graph.hip: ge_from_internal
+  uint32_t w[8];
+  std::memcpy(w, p, 32);
+  GFr r = fe_unpack<FrParams>(w);
+  HM_DECLARE(r, GE_COLUMN_BOUND);
+  return r;
+}
+const char* g_graph_error = "";
 
 }  // namespace
 
@@ -255,6 +276,138 @@ int hc_graph_bounds_closure(const uint64_t* a_ext, double* report) {
   (void)fe_canonical(fe_mul(fe_reduce_small(fe_norm(c16)), fe_const<FrParams>(FrParams::INT2EXT)));
   return ok;
 }
+
+// The GraphEvaluator without a GPU: validate and lower a program exactly as hm_graph_create / graph_evaluate do (graph_lower.h is the
+// code they run), then interpret the LOWERED program row by row as graph_evaluate_kernel does -- THIS LOOP RESTATES THAT KERNEL'S
+// switch (graph.hip), primitive for primitive and in its order; tests/test_graph_programs_gpu.py holds the two to the same words.
+// Column loads, constants and PreviousValue enter at the class maxima the kernel declares; a value in a slot keeps the bound the
+// tracker gave it (the kernel re-declares it at GE_CAP, which the caller checks against the static bound instead), and the slots keep
+// their contents from row to row, as a lane's slots do in the grid-stride loop.
+//   calcs5 ... n_intermediates: as hm_graph_create;  dyn_ext: the per-call constants;  columns[i]: column_rows[i] x 8 words;
+//   values: (segments << log_segment) x 8 words, PreviousValue in, the program's value out;  flags: HM_GRAPH_COLUMNS_INTERNAL = 1.
+//   lowered5 / static_bound / tracked_bound: room for n_calc calculations -- the lowered program, the lowering's static bound of each
+//   result and the largest bound the tracker saw for it;  info: {lowered calculations, slots, result_src, result_prev, Stores of
+//   constants removed, Stores of columns removed}.
+// -> 0; -1: the program is refused (hc_graph_last_error); -2: a column read past column_rows.  A violated precondition aborts.
+int hc_graph_replay(const uint32_t* calcs5, size_t n_calc, const uint64_t* constants_ext, size_t n_const_static, const uint64_t* dyn_ext,
+                    size_t n_dynamic, const int32_t* rotations, size_t n_rot, const uint32_t* const* columns, const uint64_t* column_rows,
+                    size_t n_columns, uint32_t n_intermediates, uint32_t log_segment, uint32_t segments, uint32_t flags, uint32_t* values,
+                    uint32_t* lowered5, double* static_bound, double* tracked_bound, uint32_t* info) {
+  g_graph_error = "";
+  if (const char* why = graph_validate(calcs5, n_calc, n_const_static, n_dynamic, n_rot, n_columns, n_intermediates)) {
+    g_graph_error = why;
+    return -1;
+  }
+  if (flags & ~1u) { g_graph_error = "graph: unknown flag"; return -1; }
+  if (log_segment > 30) { g_graph_error = "graph: log_size > 30"; return -1; }
+  if (segments == 0 || ((uint64_t)segments << log_segment) > (1ull << 32)) { g_graph_error = "graph: segments must be >= 1 and rows <= 2^32"; return -1; }
+  const bool internal_cols = (flags & 1u) != 0;
+  GraphLowered low;
+  graph_lower_host(calcs5, n_calc, n_intermediates, internal_cols, low);
+  const size_t n = low.calcs.size();
+  for (size_t k = 0; k < n; ++k) {
+    const GraphCalc& c = low.calcs[k];
+    const uint32_t w[5] = {c.op, c.a, c.b, c.c, c.target};
+    std::memcpy(lowered5 + 5 * k, w, 20);
+    static_bound[k] = low.bound[k];
+    tracked_bound[k] = 0.0;
+  }
+  info[0] = (uint32_t)n, info[1] = low.n_slots, info[2] = low.result_src, info[3] = low.result_prev;
+  info[4] = low.stores_of_constants_removed, info[5] = low.stores_of_columns_removed;
+  // constants -> internal form, as graph_create and graph_evaluate convert them
+  std::vector<uint32_t> consts((n_const_static + n_dynamic + 1) * 9, 0);
+  for (size_t i = 0; i < n_const_static; ++i) host::fr_to_internal9(host::fr_load(constants_ext + 4 * i), &consts[9 * i]);
+  for (size_t i = 0; i < n_dynamic; ++i) host::fr_to_internal9(host::fr_load(dyn_ext + 4 * i), &consts[9 * (n_const_static + i)]);
+  // a slot that was never written holds SOMETHING on the device: here a recognisable element inside the class
+  GFr stale;
+  for (int i = 0; i < 9; ++i) stale.l[i] = 0x5a5a5a5u;
+  stale.l[8] = 0x5a5u;
+  HM_DECLARE(stale, GE_CAP);
+  std::vector<GFr> slots(low.n_slots, stale);
+  const uint64_t size = (uint64_t)segments << log_segment, mask = (1ull << log_segment) - 1;
+  int rc = 0;
+  for (uint64_t idx = 0; idx < size && rc == 0; ++idx) {
+    uint32_t* vrow = values + idx * 8;
+    auto fetch = [&](uint32_t src) -> GFr {                     // graph.hip: ge_fetch
+      const uint32_t kind = gsrc_kind(src), index = gsrc_index(src);
+      GFr r;
+      if (kind == GSRC_INTER) {
+        r = slots[index];
+      } else if (kind == GSRC_CONST) {
+        for (int i = 0; i < 9; ++i) r.l[i] = consts[(size_t)index * 9 + i];
+        HM_DECLARE(r, 1.0);
+      } else if (kind == GSRC_COLUMN) {
+        uint64_t row = (idx & ~mask) | ((idx + (uint64_t)(int64_t)rotations[gsrc_rot(src)]) & mask);
+        const uint32_t lr = gsrc_log_rows(src);
+        if (lr != 0) row &= (1ull << lr) - 1ull;
+        if (row >= column_rows[gsrc_column(src)]) {
+          rc = -2;
+          return fe_zero<FrParams>();
+        }
+        const uint32_t* cell = columns[gsrc_column(src)] + row * 8;
+        r = internal_cols ? gr_from_internal(cell) : gr_from_ext(cell);
+      } else {
+        r = gr_from_ext(vrow);
+      }
+      return r;
+    };
+    GFr prev = fe_zero<FrParams>();
+    HM_DECLARE(prev, 3.0);
+    for (size_t k = 0; k < n; ++k) {
+      const GraphCalc cc = low.calcs[k];
+      const uint32_t op = cc.op & 0xffu;
+      auto src = [&](uint32_t word, uint32_t flag) -> GFr { return (cc.op & flag) ? prev : fetch(word); };
+      const GFr a = src(cc.a, GF_A_PREV);
+      GFr out;
+      const bool lazy = (cc.op & GF_NO_REDUCE) != 0, wide = (cc.op & GF_SUB_WIDE) != 0;
+      auto settle = [&](const GFr& t) -> GFr { return lazy ? fe_norm(t) : gr_reduce(t); };
+      switch (op) {
+        case GOP_ADD:
+          out = settle(fe_add(a, src(cc.b, GF_B_PREV)));
+          break;
+        case GOP_SUB: {
+          const GFr b = src(cc.b, GF_B_PREV);
+          out = wide ? gr_reduce(fe_sub<20, 29>(a, b)) : settle(fe_sub<4, 29>(a, b));
+          break;
+        }
+        case GOP_MUL:
+          out = fe_mul(a, src(cc.b, GF_B_PREV));
+          break;
+        case GOP_SQUARE:
+          out = fe_sqr(a);
+          break;
+        case GOP_DOUBLE:
+          out = settle(fe_dbl(a));
+          break;
+        case GOP_NEGATE:
+          out = wide ? gr_reduce(fe_sub<20, 29>(fe_zero<FrParams>(), a)) : settle(fe_sub<4, 29>(fe_zero<FrParams>(), a));
+          break;
+        case GOP_MULADD: {
+          const GFr b = src(cc.b, GF_B_PREV);
+          const GFr c = src(cc.c, GF_C_PREV);
+          out = settle(fe_add(fe_mul(a, b), c));
+          break;
+        }
+        default:
+          out = a;
+          break;
+      }
+      if (!(cc.op & GF_NO_STORE)) slots[cc.target] = out;
+      if (out.vb > tracked_bound[k]) tracked_bound[k] = out.vb;
+      prev = out;
+    }
+    GFr res = fe_zero<FrParams>();
+    if (low.result_prev)
+      res = prev;
+    else if (n != 0 || gsrc_kind(low.result_src) != GSRC_INTER)
+      res = fetch(low.result_src);
+    uint32_t w[8];
+    fe_to_ext(w, gr_reduce(res));
+    std::memcpy(vrow, w, 32);
+  }
+  return rc;
+}
+const char* hc_graph_last_error() { return g_graph_error; }
 
 int hc_fr_vector_bounds_closure(const uint64_t* a_ext, const uint64_t* b_ext, double* report) {
   typedef Fe<FrParams> F;

@@ -240,6 +240,13 @@ class GraphEvaluator:
         """Column table = fixed | advice | instance.  Per-call constants = challenges..., beta, gamma, theta, y.
         short_columns: {column table index: log2(rows)} for columns shorter than the domain, read periodically (the inverse
         vanishing-polynomial pattern)."""
+        return CompiledGraph(**self.lower(num_fixed, num_advice, num_instance, num_challenges, rot_scale, short_columns))
+
+    def lower(self, num_fixed: int, num_advice: int, num_instance: int, num_challenges: int = 0, rot_scale: int = 1,
+              short_columns: Dict[int, int] = None) -> Dict:
+        """``compile`` without the device: the arguments of ``hm_graph_create`` as ``CompiledGraph`` takes them (the host replay
+        of the HM_BOUNDS build consumes the same words).  The instruction encodes a short column's log2(rows) with 0 meaning
+        "full size", so a ONE-row column (log2 = 0) is encoded as a two-row one; ``CompiledGraph.evaluate`` passes its row twice."""
         short_columns = short_columns or {}
         n_static = len(self.constants)
         dyn_index = {("Challenge", i): n_static + i for i in range(num_challenges)}
@@ -260,7 +267,8 @@ class GraphEvaluator:
                 col = col_base[kind] + vs[1]
                 if not 0 <= vs[1] < {"Fixed": num_fixed, "Advice": num_advice, "Instance": num_instance}[kind]:
                     raise ValueError(f"{kind} column {vs[1]} out of range")
-                return (2 << 30) | (vs[2] << 20) | (short_columns.get(col, 0) << 14) | col
+                log_rows = max(short_columns[col], 1) if col in short_columns else 0
+                return (2 << 30) | (vs[2] << 20) | (log_rows << 14) | col
             if kind == "PreviousValue":
                 return 3 << 30
             if vs in dyn_index:
@@ -285,8 +293,9 @@ class GraphEvaluator:
                 words += [ops[name], src(calc[1]), src(calc[2]), 0, target]
             else:
                 words += [ops[name], src(calc[1]), 0, 0, target]
-        return CompiledGraph(np.array(words, dtype=np.uint32).reshape(-1, 5), list(self.constants), num_challenges + 4,
-                             [r * rot_scale for r in self.rotations], n_cols, next_inter[0], num_challenges, dict(short_columns))
+        return dict(calcs=np.array(words, dtype=np.uint32).reshape(-1, 5), constants=list(self.constants), n_dynamic=num_challenges + 4,
+                    rotations=[r * rot_scale for r in self.rotations], n_columns=n_cols, n_intermediates=next_inter[0],
+                    num_challenges=num_challenges, short_columns=dict(short_columns))
 
 
 class CompiledGraph:
@@ -323,10 +332,13 @@ class CompiledGraph:
             raise ValueError("evaluate: the (segment of the) domain must be a power of two")
         if len(columns) != self.n_columns or len(challenges) != self.num_challenges:
             raise ValueError("evaluate: column / challenge count differs from the compiled program's")
+        columns = list(columns)
         for i, c in enumerate(columns):
             want = (1 << self.short_columns[i]) if i in self.short_columns else size
             if _tensor_rows(c, 4, "column") != want:
                 raise ValueError(f"evaluate: column {i} must hold {want} rows")
+            if want == 1 and i in self.short_columns:          # encoded as two rows (GraphEvaluator.lower): the same row twice
+                columns[i] = c.reshape(1, 4).expand(2, 4).contiguous()
         ptrs = (ctypes.c_void_p * max(len(columns), 1))(*[c.data_ptr() for c in columns])
         dyn = np.stack([fr_words(v) for v in list(challenges) + [beta, gamma, theta, y]])
         _lib.check(_lib.load().hm_graph_evaluate_segments_dev(ctypes.c_uint64(self.handle), ptrs, len(columns), _ptr(dyn), dyn.shape[0],

@@ -1,5 +1,5 @@
 """tools/fuzz.py -- the differential fuzzer against the oracles (single MSMs on both layouts, whole phases through the batch call,
-batched scans / divisions, coset decompositions, lookup permutations) -- a short run of every mode under pytest: a seed a round,
+batched scans / divisions, coset decompositions, lookup permutations, raw evaluate_h programs) -- a short run of every mode under pytest: a seed a round,
 two cases a mode; `python tools/fuzz.py <mode> SEED CASES` runs it for as long as one likes."""
 import os
 import subprocess
@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("mode", ["single", "batch", "scans", "cosets", "lookup"])
+@pytest.mark.parametrize("mode", ["single", "batch", "scans", "cosets", "lookup", "graph"])
 def test_a_short_fuzz_run(mode):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz.py"), mode, "505", "2"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]

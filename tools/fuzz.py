@@ -7,6 +7,9 @@
                                              rows) and batched kate divisions == the single-column calls; one column per case == oracle/poly_ref.py
     python tools/fuzz.py cosets SEED CASES   random (k, max degree, batch): every coset of coeff_to_coset == the residue class of rows of
                                              coeff_to_extended; coset_to_partial + combine_cosets == extended_to_coeff
+    python tools/fuzz.py graph  SEED CASES   random raw evaluate_h programs (tests/graph_programs.py: 5 .. 120 calculations, Stores of anything, dead and
+                                             long-lived values, lazy-sum ladders) at 1 .. 2048 rows in 1 / 2 / 8 segments, external and internal columns,
+                                             two chained calls: device == oracle/graph_ref.py == the host replay of the lowered program
 """
 import sys
 mode = sys.argv.pop(1) if len(sys.argv) > 1 else "single"
@@ -156,6 +159,28 @@ elif mode == "cosets":
         if not bool((dom.combine_cosets(parts, pieces=e) == whole).all()):
             bad += 1
             print("MISMATCH recombination", case, k, j, flush=True)
+        if case % 10 == 9: print("case", case, "bad =", bad, f"{time.time()-t0:.0f}s", flush=True)
+    print("done, mismatches:", bad)
+elif mode == "graph":
+    import os, sys, random, time
+    sys.path.insert(0, os.getcwd())
+    sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
+    import graph_programs as gp
+    base = int(sys.argv[1]) if len(sys.argv) > 1 else 1
+    rng = random.Random(base)
+    hc = gp.hostcheck()
+    bad, t0 = 0, time.time()
+    for case in range(int(sys.argv[2]) if len(sys.argv) > 2 else 40):
+        seed = base * 100_000 + case
+        p = gp.random_program(seed)
+        sizes = [(s, c) for s in gp.SEGMENT_ROWS for c in gp.SEGMENT_COUNTS if s * c * len(p.lower()["calcs"]) <= 40_000]
+        seg, segments = rng.choice(sizes)
+        d = gp.make_data(random.Random(seed), seg, segments, uniform=rng.random() < 0.25)
+        failures = gp.device_against_oracle_and_replay(hc, p, d, random.Random(seed + 1))
+        if failures:
+            bad += 1
+            print("MISMATCH program seed", seed, "seg", seg, "segments", segments, flush=True)
+            for f in failures: print("   ", f, flush=True)
         if case % 10 == 9: print("case", case, "bad =", bad, f"{time.time()-t0:.0f}s", flush=True)
     print("done, mismatches:", bad)
 elif mode == "lookup":
