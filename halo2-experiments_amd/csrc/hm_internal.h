@@ -409,6 +409,14 @@ void merkle_sum_witness_rows(uint32_t depth, uint32_t r_f, uint32_t r_p, uint32_
 int merkle_sum_witness_run(const PoseidonSpec& s, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* d_leaves,
                            const uint32_t* d_siblings, const uint64_t* d_indices, const uint64_t* assets_ext, const uint32_t* d_nodes,
                            uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream);
+// the MerkleTreeV3 / Poseidon circuit witnesses (poseidon.inc): out = rows_used, n_advice, perm_rows, level_rows, const_row
+// (depth is ignored for the Poseidon circuit, whose level_rows counts every row before the constants)
+void merkle_witness_rows(uint32_t depth, uint32_t r_f, uint32_t r_p, uint32_t (&out)[5]);
+void poseidon_witness_rows(uint32_t r_f, uint32_t r_p, uint32_t (&out)[5]);
+int merkle_witness_run(const PoseidonSpec& s, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* d_leaves, const uint32_t* d_siblings,
+                       const uint64_t* d_indices, const uint32_t* d_nodes, uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream);
+int poseidon_witness_run(const PoseidonSpec& s, uint32_t log_n, size_t m, const uint32_t* d_msgs, uint32_t* d_advice, uint32_t* d_instance,
+                         hipStream_t stream);
 
 // lookup.hip
 int lookup_permute_run(DeviceCtx& ctx, const void* const* d_inputs, const void* const* d_tables, size_t pairs, uint64_t rows,

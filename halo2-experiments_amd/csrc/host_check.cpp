@@ -543,4 +543,33 @@ int hc_merkle_sum_witness(const uint32_t* consts, uint32_t r_f, uint32_t r_p, ui
   return 0;
 }
 
+// The MerkleTreeV3 witness of m users and the Poseidon circuit's witness of m messages on host memory, lane by lane like the above.
+// run: m x (depth - 1) x 8 words of scratch (used when nodes is null); advice must be cleared by the caller.
+int hc_merkle_witness(const uint32_t* consts, uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* leaves,
+                      const uint32_t* siblings, const uint64_t* indices, const uint32_t* nodes, uint32_t* run, uint32_t* advice,
+                      uint32_t* instance) {
+  if (depth == 0 || depth > 32 || (r_f & 1) || (r_p & 1)) return -1;
+  if (((uint64_t)1 << log_n) < (uint64_t)merkle_witness_layout(depth, r_f, r_p).rows_used + 6) return -1;
+  MerkleWitnessArgs a;
+  a.leaves = leaves, a.siblings = siblings, a.indices = indices, a.nodes = nodes, a.run = nodes ? nullptr : run;
+  a.advice = advice, a.instance = instance, a.consts = consts;
+  a.m = m, a.depth = depth, a.log_n = log_n, a.r_f = r_f, a.r_p = r_p;
+  for (size_t u = 0; u < m; ++u) {
+    if (!nodes) merkle_chain_lane(a, u, run);
+    for (uint32_t l = 0; l < depth; ++l) merkle_witness_lane(a, u, l);
+  }
+  return 0;
+}
+
+int hc_poseidon_witness(const uint32_t* consts, uint32_t r_f, uint32_t r_p, uint32_t log_n, size_t m, const uint32_t* msgs, uint32_t* advice,
+                        uint32_t* instance) {
+  if ((r_f & 1) || (r_p & 1)) return -1;
+  if (((uint64_t)1 << log_n) < (uint64_t)poseidon_witness_layout(r_f, r_p).rows_used + 6) return -1;
+  PoseidonWitnessArgs a;
+  a.msgs = msgs, a.advice = advice, a.instance = instance, a.consts = consts;
+  a.m = m, a.log_n = log_n, a.r_f = r_f, a.r_p = r_p;
+  for (size_t u = 0; u < m; ++u) poseidon_witness_lane(a, u);
+  return 0;
+}
+
 }  // extern "C"

@@ -106,6 +106,7 @@ HM_HD void poseidon_mix(Fr (&s)[W], const uint32_t* mds, const Fr (&x)[W], std::
 struct PoseidonNoTrace {
   template <int W>
   HM_HD void row(uint32_t, const Fr (&)[W]) const {}
+  template <int W>
   HM_HD void sbox0(uint32_t, const Fr&) const {}
 };
 
@@ -125,7 +126,7 @@ HM_HD void poseidon_permute(Fr (&s)[W], const uint32_t* c, uint32_t r_f, uint32_
 #pragma unroll
     for (int j = 0; j < W; ++j) x[j] = fe_add(s[j], ps_load9(rc + j * 9));
     x[0] = poseidon_sbox(x[0]);
-    if (first && !full) sink.sbox0(row, x[0]);
+    if (first && !full) sink.template sbox0<W>(row, x[0]);
     row += first ? 1u : 0u;
     if (full)
       poseidon_sbox_rest<W>(x, std::make_integer_sequence<int, W - 1>{});
@@ -297,7 +298,7 @@ struct WitnessArgs {
   uint32_t assets[8];
 };
 
-// the rows of "permute state" into the columns state[0..4] (advice 5..9) and partial_sbox (10) of one hash
+// the rows of "permute state" into the columns state[0..W-1] and partial_sbox (the column after them) of one hash
 struct WitnessSink {
   uint32_t* state0;              // word 0 of column state[0] at the region's first row
   uint64_t col_words;            // words from one column to the next
@@ -310,10 +311,11 @@ struct WitnessSink {
       ps_put_words(state0 + j * col_words + (uint64_t)i * 8, w);
     }
   }
+  template <int W>
   HM_HD void sbox0(uint32_t i, const Fr& x) const {
     uint32_t w[8];
     fe_to_ext_shift(w, x);
-    ps_put_words(state0 + 5 * col_words + (uint64_t)i * 8, w);
+    ps_put_words(state0 + W * col_words + (uint64_t)i * 8, w);
   }
 };
 
@@ -430,6 +432,163 @@ HM_HD void merkle_sum_witness_lane(const WitnessArgs& a, uint64_t u, uint32_t l)
   }
 }
 
+// ---- the MerkleTreeV3 and Poseidon circuits' witnesses (DESIGN.md section 14) -------------------------------------------------------
+// The advice columns of circuits.merkle_v3() for one inclusion path (/root/reference/src/chips/merkle_v3.rs:84-172) and of
+// circuits.poseidon() for one hash (src/chips/poseidon/hash_with_instance.rs:78-148), with the Pow5 regions of the section above.
+// Row placement (synthesis.MerkleTreeV3Layout / PoseidonCircuitLayout restate it; tests compare the two):
+//     merkle_v3: row 0 the leaf; level l at 1 + l * level_rows: prove layer (2 rows), initial state (1), pad-and-add (3), permute
+//                state (perm_rows); then 3 constants per level in rc_b[0] (fixed only).
+//     poseidon:  row 0 the private inputs, row 1 their copies, initial state (1), pad-and-add (3), permute state; then 5 constants.
+constexpr uint32_t MERKLE_WITNESS_ADVICE = 7;        // a b c | state[3] | partial_sbox
+constexpr uint32_t POSEIDON_WITNESS_ADVICE = 6;      // state[5] | partial_sbox
+struct Pow5Layout {
+  uint32_t perm_rows, level_rows, const_row, rows_used;
+};
+HM_HD Pow5Layout merkle_witness_layout(uint32_t depth, uint32_t r_f, uint32_t r_p) {
+  Pow5Layout w;
+  w.perm_rows = r_f + r_p / 2 + 1;
+  w.level_rows = 2 + 1 + 3 + w.perm_rows;
+  w.const_row = 1 + depth * w.level_rows;
+  w.rows_used = w.const_row + 3 * depth;
+  return w;
+}
+HM_HD Pow5Layout poseidon_witness_layout(uint32_t r_f, uint32_t r_p) {      // level_rows: everything before the constants
+  Pow5Layout w;
+  w.perm_rows = r_f + r_p / 2 + 1;
+  w.level_rows = 1 + 1 + 1 + 3 + w.perm_rows;
+  w.const_row = w.level_rows;
+  w.rows_used = w.const_row + 5;
+  return w;
+}
+
+struct MerkleWitnessArgs {
+  const uint32_t* leaves;        // m x 8 words
+  const uint32_t* siblings;      // m x depth x 8
+  const uint64_t* indices;       // m: bit l = the path's node is the right child at level l
+  const uint32_t* nodes;         // the built tree (2^(depth+1) - 1 nodes of 8 words), or null
+  const uint32_t* run;           // without a tree: m x (depth - 1) x 8, the path's node after levels 1 .. depth - 1 (merkle_chain_lane)
+  uint32_t* advice;              // m x MERKLE_WITNESS_ADVICE x 2^log_n x 8, cleared
+  uint32_t* instance;            // m x 2 x 8: leaf, root
+  const uint32_t* consts;
+  uint64_t m;
+  uint32_t depth, log_n, r_f, r_p;
+};
+
+// the path's node after level l + 1, for l = 0 .. depth - 2, of user u
+HM_HD void merkle_chain_lane(const MerkleWitnessArgs& a, uint64_t u, uint32_t* run) {
+  uint32_t node[8];
+  ps_get_words(a.leaves + u * 8, node);
+  const uint64_t idx = a.indices[u];
+#pragma unroll 1
+  for (uint32_t l = 0; l + 1 < a.depth; ++l) {
+    uint32_t sib[8], kids[2][8];
+    ps_get_words(a.siblings + (u * a.depth + l) * 8, sib);
+    const bool right = (idx >> l) & 1ull;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      kids[0][i] = right ? sib[i] : node[i];
+      kids[1][i] = right ? node[i] : sib[i];
+    }
+    poseidon_hash_one<3>(kids, a.consts, a.r_f, a.r_p, node);
+    ps_put_words(run + (u * (a.depth - 1) + l) * 8, node);
+  }
+}
+
+// everything level l of user u contributes to the MerkleTreeV3 witness
+HM_HD void merkle_witness_lane(const MerkleWitnessArgs& a, uint64_t u, uint32_t l) {
+  const Pow5Layout lay = merkle_witness_layout(a.depth, a.r_f, a.r_p);
+  const uint64_t col_words = (uint64_t)8 << a.log_n;
+  uint32_t* adv = a.advice + u * MERKLE_WITNESS_ADVICE * col_words;
+  const uint64_t base = 1 + (uint64_t)l * lay.level_rows;
+  const uint64_t idx = a.indices[u] & ((1ull << a.depth) - 1);          // depth <= 32
+  const bool right = (idx >> l) & 1ull;
+
+  uint32_t kids[2][8], w[8];
+  {
+    uint32_t prev[8], sib[8];
+    const uint32_t* p = l == 0 ? a.leaves + u * 8
+                        : a.nodes ? a.nodes + (((2ull << a.depth) - (2ull << (a.depth - l))) + (idx >> l)) * 8
+                                  : a.run + (u * (a.depth - 1) + (l - 1)) * 8;
+    ps_get_words(p, prev);
+    ps_get_words(a.siblings + (u * a.depth + l) * 8, sib);
+    if (l == 0) {                                          // "assign leaf"; instance row 0
+      ps_put_words(adv + 0 * col_words + 0 * 8, prev);
+      ps_put_words(a.instance + u * 16, prev);
+    }
+    // "merkle prove layer" row 0: previous node, path element, index
+    ps_put_words(adv + 0 * col_words + base * 8, prev);
+    ps_put_words(adv + 1 * col_words + base * 8, sib);
+    fr_small_to_ext(right ? 1u : 0u, w);
+    ps_put_words(adv + 2 * col_words + base * 8, w);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      kids[0][i] = right ? sib[i] : prev[i];
+      kids[1][i] = right ? prev[i] : sib[i];
+    }
+  }
+  // row 1: left, right; the hash's input row and the pad-and-add output row repeat the two words
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    ps_put_words(adv + j * col_words + (base + 1) * 8, kids[j]);
+    ps_put_words(adv + (3 + j) * col_words + (base + 4) * 8, kids[j]);
+    ps_put_words(adv + (3 + j) * col_words + (base + 5) * 8, kids[j]);
+  }
+  // the capacity word: "initial state", pad-and-add rows 0 and 2 (the two rate words of the initial state are zero)
+  const uint32_t* cap = a.consts + ((size_t)(a.r_f + a.r_p) * 3 + 9) * 9;
+  fe_to_ext_shift(w, ps_load9(cap));
+  ps_put_words(adv + 5 * col_words + (base + 2) * 8, w);
+  ps_put_words(adv + 5 * col_words + (base + 3) * 8, w);
+  ps_put_words(adv + 5 * col_words + (base + 5) * 8, w);
+
+  Fr s[3];
+  s[0] = fe_from_ext<FrParams>(kids[0]);
+  s[1] = fe_from_ext<FrParams>(kids[1]);
+  s[2] = ps_load9(cap);
+  const WitnessSink sink{adv + 3 * col_words + (base + 6) * 8, col_words};
+  poseidon_permute<3>(s, a.consts, a.r_f, a.r_p, sink);
+  if (l + 1 == a.depth) {                                  // the root: instance row 1
+    fe_to_ext_shift(w, s[0]);
+    ps_put_words(a.instance + u * 16 + 8, w);
+  }
+}
+
+struct PoseidonWitnessArgs {
+  const uint32_t* msgs;          // m x 4 x 8 words
+  uint32_t* advice;              // m x POSEIDON_WITNESS_ADVICE x 2^log_n x 8, cleared
+  uint32_t* instance;            // m x 8: the digest
+  const uint32_t* consts;
+  uint64_t m;
+  uint32_t log_n, r_f, r_p;
+};
+
+// the whole Poseidon circuit of message u
+HM_HD void poseidon_witness_lane(const PoseidonWitnessArgs& a, uint64_t u) {
+  const uint64_t col_words = (uint64_t)8 << a.log_n;
+  uint32_t* adv = a.advice + u * POSEIDON_WITNESS_ADVICE * col_words;
+  uint32_t msg[4][8], w[8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    ps_get_words(a.msgs + (u * 4 + j) * 8, msg[j]);
+    ps_put_words(adv + j * col_words + 0 * 8, msg[j]);     // "load private inputs"
+    ps_put_words(adv + j * col_words + 1 * 8, msg[j]);     // "copy input cells to hash input cells"
+    ps_put_words(adv + j * col_words + 4 * 8, msg[j]);     // pad-and-add: the message row and the output row
+    ps_put_words(adv + j * col_words + 5 * 8, msg[j]);
+  }
+  const uint32_t* cap = a.consts + ((size_t)(a.r_f + a.r_p) * 5 + 25) * 9;
+  fe_to_ext_shift(w, ps_load9(cap));
+  ps_put_words(adv + 4 * col_words + 2 * 8, w);            // "initial state", pad-and-add rows 0 and 2
+  ps_put_words(adv + 4 * col_words + 3 * 8, w);
+  ps_put_words(adv + 4 * col_words + 5 * 8, w);
+  Fr s[5];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) s[j] = fe_from_ext<FrParams>(msg[j]);
+  s[4] = ps_load9(cap);
+  const WitnessSink sink{adv + 6 * 8, col_words};
+  poseidon_permute<5>(s, a.consts, a.r_f, a.r_p, sink);
+  fe_to_ext_shift(w, s[0]);
+  ps_put_words(a.instance + u * 8, w);
+}
+
 #if defined(__HIPCC__)
 constexpr int PS_THREADS = 256;
 
@@ -506,5 +665,23 @@ __global__ __launch_bounds__(PS_THREADS) void merkle_sum_chain_kernel(const Witn
   const uint64_t u = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
   if (u >= a.m) return;
   merkle_sum_chain_lane(a, u, run);
+}
+
+// MerkleTreeV3: one lane per (user, level); the columns were cleared by the caller
+__global__ __launch_bounds__(PS_THREADS) void merkle_witness_kernel(const MerkleWitnessArgs a) {
+  const uint64_t t = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
+  if (t >= a.m * a.depth) return;
+  merkle_witness_lane(a, t / a.depth, (uint32_t)(t % a.depth));
+}
+__global__ __launch_bounds__(PS_THREADS) void merkle_chain_kernel(const MerkleWitnessArgs a, uint32_t* __restrict__ run) {
+  const uint64_t u = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
+  if (u >= a.m) return;
+  merkle_chain_lane(a, u, run);
+}
+// the Poseidon circuit: one lane per hash
+__global__ __launch_bounds__(PS_THREADS) void poseidon_witness_kernel(const PoseidonWitnessArgs a) {
+  const uint64_t u = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
+  if (u >= a.m) return;
+  poseidon_witness_lane(a, u);
 }
 #endif

@@ -388,6 +388,25 @@ class MerkleTree(_Tree):
     def path(self, index: int) -> Tuple[List[int], List[int]]:
         return self.paths([index])[0]
 
+    def witness(self, indices, k: int, out=None):
+        """The MerkleTreeV3 circuit's witnesses of the inclusion paths of ``indices`` (``synthesis.merkle_witness`` with the path's
+        nodes read from this tree; nothing leaves the device): -> (advice (m, 7, 2^k, 4), instance (m, 2, 4)) tensors."""
+        import torch
+
+        from .synthesis import merkle_witness
+
+        idx = [int(i) for i in indices]
+        if not idx or any(not 0 <= i < (1 << self.depth) for i in idx):
+            raise IndexError(f"MerkleTree.witness: leaf indices must lie in [0, {1 << self.depth}) and there must be one at least")
+        d_idx = torch.tensor(idx, dtype=torch.int64, device=self.nodes.device)
+        sib = torch.empty((len(idx), self.depth, 4), dtype=torch.int64, device=self.nodes.device)
+        with torch.cuda.device(self.nodes.device):
+            _lib.check(_lib.load().hm_merkle_paths_dev(ctypes.c_void_p(self.nodes.data_ptr()), self.depth, 1,
+                                                       ctypes.cast(ctypes.c_void_p(d_idx.data_ptr()), ctypes.POINTER(ctypes.c_uint64)),
+                                                       len(idx), ctypes.c_void_p(sib.data_ptr()), ctypes.c_void_p(_stream_ptr(self.nodes))))
+        leaves = self.nodes[d_idx].contiguous()
+        return merkle_witness(self.spec, leaves, sib, d_idx, k, nodes=self.nodes, out=out)
+
     @staticmethod
     def verify_path(leaf: int, path, spec: Optional[Spec] = None) -> int:
         spec = default_spec(3) if spec is None else spec

@@ -22,12 +22,23 @@ the two regions that touch fixed columns only are placed by column: the u8 table
 in rc_b[0] after the last region.  Upstream's ``SimpleFloorPlanner`` packs every region per column and may start some earlier; that
 cannot be pinned without the crate.  Every legal placement gives a valid circuit and the gates only use rotations inside a region,
 so this is A valid layout of the reference's circuit, not a row-for-row copy of upstream's.
+
+The two other circuits of the reference, with the same placement rule and the same Pow5 regions (``_Pow5Layout``):
+``MerkleTreeV3Layout`` for ``circuits.merkle_v3(spec)`` (``merkle_witness``, one lane per (user, level)) and ``PoseidonCircuitLayout``
+for ``circuits.poseidon(spec)`` (``poseidon_circuit_witness``, one lane per hash).  TRANSCRIBED (read as text):
+    "assign leaf" (column a, row 0)                  /root/reference/src/chips/merkle_v3.rs:84-95
+    "merkle prove layer" (two rows per level)        :97-148    bool + swap selectors on row 0; swapped whenever the index is not zero :126-130
+    the hash of [left, right]                        :150-161
+    expose_public rows 0 (leaf) and 1 (root)         :165-172, src/circuits/merkle_v3.rs:29-59
+    "load private inputs" (hash_inputs[0 .. L), row 0)            src/chips/poseidon/hash_with_instance.rs:78-101
+    "copy input cells to hash input cells" (copies of those)      :106-139
+    the digest exposed at instance row 0             :141-148, src/circuits/poseidon.rs:43-59
 """
 from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -261,8 +272,316 @@ class MerkleSumTreeLayout:
         return adv
 
 
+# ---- the two other circuits: MerkleTreeV3 and Poseidon ---------------------------------------------------------------------------
+class _Pow5Layout:
+    """What the two layouts below share: the Pow5 chip's regions of one hash ("initial state" 1 row, "pad-and-add" 3, "permute
+    state" perm_rows), their selectors, rc_a / rc_b rows, constants, copies and the assignment of the trace.  A subclass names its
+    columns (WIDTH, STATE, PARTIAL_SBOX, RC_A, RC_B, S_FULL, S_PARTIAL, S_PAD, N_ADVICE, N_FIXED) and lists ``hash_start``: the
+    "initial state" row of every hash; the constants of hash h lie in rc_b[0] at const_row + WIDTH * h."""
+    NAME = ""
+    WIDTH = 0
+    STATE: Tuple[int, ...] = ()
+    PARTIAL_SBOX = 0
+    RC_A: Tuple[int, ...] = ()
+    RC_B: Tuple[int, ...] = ()
+    S_FULL = S_PARTIAL = S_PAD = 0
+    N_ADVICE = N_FIXED = N_INSTANCE_ROWS = 0
+
+    def _init_pow5(self, k: int, spec: Optional[Spec]) -> Spec:
+        spec = default_spec(self.WIDTH) if spec is None else spec
+        if spec.width != self.WIDTH:
+            raise ValueError(f"{self.NAME}: needs a width-{self.WIDTH} spec")
+        if spec.r_f % 2 or spec.r_p % 2:
+            raise ValueError(f"{self.NAME}: the Pow5 chip needs even r_f and r_p")
+        self.k, self.n, self.spec = k, 1 << k, spec
+        self.perm_rows = spec.r_f + spec.r_p // 2 + 1
+        self.hash_start: List[int] = []
+        return spec
+
+    def _place_hash(self, place, tag: str) -> None:
+        adv = tuple(("advice", c) for c in self.STATE)
+        self.hash_start.append(place(f"initial state{tag}", 1, adv).start)
+        place(f"pad-and-add{tag}", 3, adv + (("fixed", self.S_PAD),))
+        place(f"permute state{tag}", self.perm_rows, adv + (("advice", self.PARTIAL_SBOX),) +
+              tuple(("fixed", c) for c in self.RC_A + self.RC_B + (self.S_FULL, self.S_PARTIAL)))
+
+    def _finish(self, row: int, place) -> None:
+        self.const_row = row
+        place("constants", self.WIDTH * len(self.hash_start), (("fixed", self.RC_B[0]),))
+        self.used_rows = self.const_row + self.WIDTH * len(self.hash_start)
+        if self.used_rows > self.n - BLINDING_ROWS:
+            raise ValueError(f"{self.NAME}: {self.used_rows} rows are needed, 2^{self.k} - {BLINDING_ROWS} is fewer")
+
+    # rows of hash h
+    def init_row(self, h: int = 0) -> int:
+        return self.hash_start[h]
+
+    def pad_row(self, h: int = 0) -> int:
+        return self.hash_start[h] + 1
+
+    def perm_row(self, h: int = 0) -> int:
+        return self.hash_start[h] + 4
+
+    def digest_cell(self, h: int = 0) -> Cell:
+        return ("advice", self.STATE[0], self.perm_row(h) + self.perm_rows - 1)
+
+    _round_of_row = MerkleSumTreeLayout._round_of_row
+
+    def check_constraint_system(self, cs: ConstraintSystem) -> None:
+        if (cs.num_advice, cs.num_fixed, cs.num_instance) != (self.N_ADVICE, self.N_FIXED, 1):
+            raise ValueError(f"{self.NAME}: the constraint system is not the circuit's")
+
+    def _pow5_selector_rows(self, out: Dict[int, List[int]]) -> Dict[int, List[int]]:
+        half, pairs = self.spec.r_f // 2, self.spec.r_p // 2
+        for c in (self.S_FULL, self.S_PARTIAL, self.S_PAD):
+            out[c] = []
+        for h in range(len(self.hash_start)):
+            out[self.S_PAD].append(self.pad_row(h) + 1)
+            p = self.perm_row(h)
+            out[self.S_FULL] += [p + i for i in range(half)] + [p + half + pairs + i for i in range(half)]
+            out[self.S_PARTIAL] += [p + half + i for i in range(pairs)]
+        return out
+
+    def selector_rows(self) -> Dict[int, List[int]]:
+        """fixed column of a selector -> the rows where it is enabled"""
+        return self._pow5_selector_rows({})
+
+    def fixed_columns(self) -> List[List[int]]:
+        """The N_FIXED fixed columns as integers: selectors, rc_a / rc_b per "permute state" row, the constants."""
+        rc, _, _ = self.spec.constants()
+        half, pairs, W = self.spec.r_f // 2, self.spec.r_p // 2, self.WIDTH
+        cols = [[0] * self.n for _ in range(self.N_FIXED)]
+        for c, rows in self.selector_rows().items():
+            for r in rows:
+                cols[c][r] = 1
+        for h in range(len(self.hash_start)):
+            p = self.perm_row(h)
+            for i in range(self.perm_rows - 1):
+                rnd = self._round_of_row(i)
+                for j in range(W):
+                    cols[self.RC_A[j]][p + i] = rc[rnd][j]
+                    if half <= i < half + pairs:
+                        cols[self.RC_B[j]][p + i] = rc[rnd + 1][j]
+            cols[self.RC_B[0]][self.const_row + W * h + W - 1] = self.spec.rate << 64
+        return cols
+
+    def _pow5_copies(self, h: int, message: Sequence[Cell]) -> List[Tuple[Cell, Cell]]:
+        """constants -> initial state -> pad-and-add row 0; the message cells -> row 1; row 2 -> the first permute row"""
+        ini, pad, perm, W = self.init_row(h), self.pad_row(h), self.perm_row(h), self.WIDTH
+        out: List[Tuple[Cell, Cell]] = []
+        for j in range(W):
+            out.append((("fixed", self.RC_B[0], self.const_row + W * h + j), ("advice", self.STATE[j], ini)))     # assign_advice_from_constant
+            out.append((("advice", self.STATE[j], ini), ("advice", self.STATE[j], pad)))
+            out.append((("advice", self.STATE[j], pad + 2), ("advice", self.STATE[j], perm)))
+        for j, cell in enumerate(message):
+            out.append((cell, ("advice", self.STATE[j], pad + 1)))
+        return out
+
+    def _pow5_assign(self, adv: List[List[int]], h: int, msg: Sequence[int]) -> int:
+        """the rows of hash h for the message ``msg`` (WIDTH - 1 integers) -> the digest"""
+        rc, mds, _ = self.spec.constants()
+        half, r_p, rounds, W = self.spec.r_f // 2, self.spec.r_p, self.spec.r_f + self.spec.r_p, self.WIDTH
+        ini, pad, perm, cap = self.init_row(h), self.pad_row(h), self.perm_row(h), self.spec.rate << 64
+        for j in range(W - 1):
+            adv[self.STATE[j]][pad + 1] = adv[self.STATE[j]][pad + 2] = msg[j]
+        adv[self.STATE[W - 1]][ini] = adv[self.STATE[W - 1]][pad] = adv[self.STATE[W - 1]][pad + 2] = cap
+        s, row = list(msg) + [cap], 0
+        for r in range(rounds):
+            full = r < half or r >= half + r_p
+            first = full or (r - half) % 2 == 0
+            if first:
+                for j in range(W):
+                    adv[self.STATE[j]][perm + row] = s[j]
+            x = [(v + c) % R for v, c in zip(s, rc[r])]
+            x[0] = pow(x[0], 5, R)
+            if first and not full:
+                adv[self.PARTIAL_SBOX][perm + row] = x[0]
+            row += first
+            if full:
+                x[1:] = [pow(v, 5, R) for v in x[1:]]
+            s = [sum(m * v for m, v in zip(mrow, x)) % R for mrow in mds]
+        for j in range(W):
+            adv[self.STATE[j]][perm + row] = s[j]
+        return s[0]
+
+
+class MerkleTreeV3Layout(_Pow5Layout):
+    """``MerkleTreeV3Circuit::synthesize`` for ``circuits.merkle_v3(spec)``: a pure function of (depth, k, spec).  Row 0 the leaf;
+    level l at 1 + l * level_rows: "merkle prove layer" (2 rows), then the hash's three regions; 3 constants per level at the end."""
+    NAME = "MerkleTreeV3Layout"
+    WIDTH = 3
+    A, B, C = range(3)                      # circuits.merkle_v3()'s allocation order (asserted in check_constraint_system)
+    STATE = (3, 4, 5)
+    PARTIAL_SBOX = 6
+    N_ADVICE = 7
+    BOOL_S, SWAP_S = 0, 1
+    RC_A = (2, 3, 4)
+    RC_B = (5, 6, 7)
+    S_FULL, S_PARTIAL, S_PAD = 8, 9, 10
+    N_FIXED = 11
+    N_INSTANCE_ROWS = 2
+
+    def __init__(self, depth: int, k: int, spec: Optional[Spec] = None):
+        if not 1 <= depth <= 32:
+            raise ValueError("MerkleTreeV3Layout: depth must be 1 .. 32")
+        spec = self._init_pow5(k, spec)
+        self.depth = depth
+        adv = lambda *cols: tuple(("advice", c) for c in cols)
+        regions: List[Region] = []
+        row = 0
+
+        def place(name: str, height: int, columns) -> Region:
+            nonlocal row
+            regions.append(Region(name, row, height, tuple(columns)))
+            row += height
+            return regions[-1]
+
+        place("assign leaf", 1, adv(self.A))
+        self.level_start: List[int] = []
+        for l in range(depth):
+            self.level_start.append(row)
+            place(f"merkle prove layer {l}", 2, adv(self.A, self.B, self.C) + (("fixed", self.BOOL_S), ("fixed", self.SWAP_S)))
+            self._place_hash(place, f" {l}")
+        self.level_rows = 6 + self.perm_rows
+        self.regions = regions
+        try:
+            self._finish(row, place)
+        except ValueError as e:
+            raise ValueError(f"{e} (depth {depth}: min_k = {self.min_k(depth, spec)})") from None
+
+    @staticmethod
+    def rows_needed(depth: int, spec: Optional[Spec] = None) -> int:
+        spec = default_spec(3) if spec is None else spec
+        return 1 + depth * (6 + spec.r_f + spec.r_p // 2 + 1) + 3 * depth
+
+    @classmethod
+    def min_k(cls, depth: int, spec: Optional[Spec] = None) -> int:
+        return (cls.rows_needed(depth, spec) + BLINDING_ROWS - 1).bit_length()
+
+    def prove_row(self, l: int) -> int:
+        return self.level_start[l]
+
+    def check_constraint_system(self, cs: ConstraintSystem) -> None:
+        super().check_constraint_system(cs)
+        want = [("advice", c) for c in (self.A, self.B, self.C)] + [("instance", 0)] + [("advice", c) for c in self.STATE] + [("fixed", self.RC_B[0])]
+        if list(cs.equality) != want:
+            raise ValueError("MerkleTreeV3Layout: the constraint system is not circuits.merkle_v3()")
+
+    def selector_rows(self) -> Dict[int, List[int]]:
+        out = {self.BOOL_S: [self.prove_row(l) for l in range(self.depth)], self.SWAP_S: [self.prove_row(l) for l in range(self.depth)]}
+        return self._pow5_selector_rows(out)
+
+    def copies(self) -> List[Tuple[Cell, Cell]]:
+        out: List[Tuple[Cell, Cell]] = [(("advice", self.A, 0), ("instance", 0, 0))]                    # expose_public 0
+        prev: Cell = ("advice", self.A, 0)
+        for l in range(self.depth):
+            pr = self.prove_row(l)
+            out.append((prev, ("advice", self.A, pr)))
+            out += self._pow5_copies(l, [("advice", self.A, pr + 1), ("advice", self.B, pr + 1)])
+            prev = self.digest_cell(l)
+        out.append((prev, ("instance", 0, 1)))                                                         # expose_public 1
+        return out
+
+    def instance(self, leaf: int, root: int) -> List[List[int]]:
+        col = [0] * self.n
+        col[0], col[1] = int(leaf) % R, int(root) % R
+        return [col]
+
+    def assign_ints(self, leaf: int, siblings: Sequence[int], indices: Sequence[int]) -> List[List[int]]:
+        """The N_ADVICE advice columns as the chip assigns them.  Nothing is judged: an index of 2 gives an unsatisfied witness
+        (the pair is swapped whenever the index is not zero, merkle_v3.rs:126-130)."""
+        if len(siblings) != self.depth or len(indices) != self.depth:
+            raise ValueError("assign_ints: the path must have `depth` siblings and indices")
+        adv = [[0] * self.n for _ in range(self.N_ADVICE)]
+        h = int(leaf) % R
+        adv[self.A][0] = h
+        for l, (e, index) in enumerate(zip(siblings, indices)):
+            e, index, pr = int(e) % R, int(index) % R, self.prove_row(l)
+            adv[self.A][pr], adv[self.B][pr], adv[self.C][pr] = h, e, index
+            msg = [h, e] if index == 0 else [e, h]
+            adv[self.A][pr + 1], adv[self.B][pr + 1] = msg
+            h = self._pow5_assign(adv, l, msg)
+        return adv
+
+
+class PoseidonCircuitLayout(_Pow5Layout):
+    """``PoseidonCircuit::synthesize`` for ``circuits.poseidon(spec)`` (WIDTH 5, L = 4): row 0 "load private inputs", row 1 "copy
+    input cells to hash input cells", then the hash's three regions and 5 constants; the digest is instance row 0."""
+    NAME = "PoseidonCircuitLayout"
+    WIDTH = 5
+    STATE = (0, 1, 2, 3, 4)                 # circuits.poseidon()'s allocation order (asserted in check_constraint_system)
+    PARTIAL_SBOX = 5
+    N_ADVICE = 6
+    RC_A = (0, 1, 2, 3, 4)
+    RC_B = (5, 6, 7, 8, 9)
+    S_FULL, S_PARTIAL, S_PAD = 10, 11, 12
+    N_FIXED = 13
+    N_INSTANCE_ROWS = 1
+    LOAD_ROW, COPY_ROW = 0, 1
+
+    def __init__(self, k: int, spec: Optional[Spec] = None):
+        spec = self._init_pow5(k, spec)
+        regions: List[Region] = []
+        row = 0
+
+        def place(name: str, height: int, columns) -> Region:
+            nonlocal row
+            regions.append(Region(name, row, height, tuple(columns)))
+            row += height
+            return regions[-1]
+
+        inputs = tuple(("advice", c) for c in self.STATE[:4])
+        place("load private inputs", 1, inputs)
+        place("copy input cells to hash input cells", 1, inputs)
+        self._place_hash(place, "")
+        self.level_rows = row
+        self.regions = regions
+        try:
+            self._finish(row, place)
+        except ValueError as e:
+            raise ValueError(f"{e} (min_k = {self.min_k(spec)})") from None
+
+    @staticmethod
+    def rows_needed(spec: Optional[Spec] = None) -> int:
+        spec = default_spec(5) if spec is None else spec
+        return 2 + 4 + spec.r_f + spec.r_p // 2 + 1 + 5
+
+    @classmethod
+    def min_k(cls, spec: Optional[Spec] = None) -> int:
+        return (cls.rows_needed(spec) + BLINDING_ROWS - 1).bit_length()
+
+    def check_constraint_system(self, cs: ConstraintSystem) -> None:
+        super().check_constraint_system(cs)
+        if list(cs.equality) != [("advice", c) for c in self.STATE] + [("fixed", self.RC_B[0]), ("instance", 0)]:
+            raise ValueError("PoseidonCircuitLayout: the constraint system is not circuits.poseidon()")
+
+    def copies(self) -> List[Tuple[Cell, Cell]]:
+        out: List[Tuple[Cell, Cell]] = [(("advice", c, self.LOAD_ROW), ("advice", c, self.COPY_ROW)) for c in self.STATE[:4]]
+        out += self._pow5_copies(0, [("advice", c, self.COPY_ROW) for c in self.STATE[:4]])
+        out.append((self.digest_cell(0), ("instance", 0, 0)))
+        return out
+
+    def instance(self, digest: int) -> List[List[int]]:
+        col = [0] * self.n
+        col[0] = int(digest) % R
+        return [col]
+
+    def assign_ints(self, message: Sequence[int]) -> List[List[int]]:
+        if len(message) != 4:
+            raise ValueError("assign_ints: the message must have 4 elements")
+        msg = [int(v) % R for v in message]
+        adv = [[0] * self.n for _ in range(self.N_ADVICE)]
+        for j in range(4):
+            adv[self.STATE[j]][self.LOAD_ROW] = adv[self.STATE[j]][self.COPY_ROW] = msg[j]
+        self._pow5_assign(adv, 0, msg)
+        return adv
+
+
 # ---- keygen's permutation columns -----------------------------------------------------------------------------------------------
-def permutation_cells(cs: ConstraintSystem, layout: MerkleSumTreeLayout) -> List[List[Tuple[int, int]]]:
+AnyLayout = Union[MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout]      # anything with ``n`` and ``copies()``
+
+
+def permutation_cells(cs: ConstraintSystem, layout: "AnyLayout") -> List[List[Tuple[int, int]]]:
     """``permutation::keygen::Assembly``: sigma as cells -- out[j][i] = (j', i') for column j of ``cs.equality`` and row i; the
     identity outside the copy cycles, every cycle rotated by one."""
     index = {col: j for j, col in enumerate(cs.equality)}
@@ -291,7 +610,7 @@ def permutation_cells(cs: ConstraintSystem, layout: MerkleSumTreeLayout) -> List
     return sigma
 
 
-def permutation_columns_ints(cs: ConstraintSystem, layout: MerkleSumTreeLayout, omega: int, delta: int) -> List[List[int]]:
+def permutation_columns_ints(cs: ConstraintSystem, layout: "AnyLayout", omega: int, delta: int) -> List[List[int]]:
     """The sigma columns as integers: cell (j, i) stands for delta^j * omega^i."""
     n = layout.n
     w = [1] * n
@@ -301,7 +620,7 @@ def permutation_columns_ints(cs: ConstraintSystem, layout: MerkleSumTreeLayout, 
     return [[d[j2] * w[i2] % R for (j2, i2) in col] for col in permutation_cells(cs, layout)]
 
 
-def permutation_columns(cs: ConstraintSystem, layout: MerkleSumTreeLayout, omega: int, delta: int, device="cuda"):
+def permutation_columns(cs: ConstraintSystem, layout: "AnyLayout", omega: int, delta: int, device="cuda"):
     """The sigma columns as a (P, n, 4) int64 device tensor: the identity columns delta^j * omega^i from ``hm_fr_powers_dev`` /
     ``hm_fr_scale_dev``, the cells of the copy cycles scattered in."""
     import torch
@@ -392,6 +711,121 @@ def merkle_sum_witness_host(spec: Optional[Spec], leaves: np.ndarray, siblings: 
     p = _ptr
     spec.call(_lib.load().hm_merkle_sum_witness_bn256, sb.shape[1], k, m, p(lv), p(sb), p(idx), p(np.ascontiguousarray(fr_words(int(assets_sum) % R))),
               p(adv), p(inst))
+    return adv, inst
+
+
+# ---- the MerkleTreeV3 and Poseidon circuit witnesses on the GPU ---------------------------------------------------------------------
+def merkle_c_layout(depth: int, k: int, spec: Optional[Spec] = None) -> Dict[str, int]:
+    """``hm_merkle_witness_layout``: the placement the MerkleTreeV3 kernel uses (no device needed)."""
+    spec = default_spec(3) if spec is None else spec
+    rows, n_adv, reg = ctypes.c_uint32(0), ctypes.c_uint32(0), (ctypes.c_uint32 * 3)()
+    _lib.check(_lib.load().hm_merkle_witness_layout(spec.r_f, spec.r_p, depth, k, ctypes.byref(rows), ctypes.byref(n_adv), reg))
+    return {"used_rows": rows.value, "n_advice": n_adv.value, "perm_rows": reg[0], "level_rows": reg[1], "const_row": reg[2]}
+
+
+def poseidon_c_layout(k: int, spec: Optional[Spec] = None) -> Dict[str, int]:
+    """``hm_poseidon_witness_layout``: the placement the Poseidon circuit's kernel uses (level_rows: the rows before the constants)."""
+    spec = default_spec(5) if spec is None else spec
+    rows, n_adv, reg = ctypes.c_uint32(0), ctypes.c_uint32(0), (ctypes.c_uint32 * 3)()
+    _lib.check(_lib.load().hm_poseidon_witness_layout(spec.r_f, spec.r_p, k, ctypes.byref(rows), ctypes.byref(n_adv), reg))
+    return {"used_rows": rows.value, "n_advice": n_adv.value, "perm_rows": reg[0], "level_rows": reg[1], "const_row": reg[2]}
+
+
+def _witness_out(who: str, out, m: int, n_advice: int, n: int, device):
+    import torch
+
+    if out is None:
+        return torch.empty((m, n_advice, n, 4), dtype=torch.int64, device=device)
+    if not (out.is_cuda and out.is_contiguous() and out.element_size() == 8 and out.numel() == m * n_advice * n * 4):
+        raise ValueError(f"{who}: out must be a contiguous (m, {n_advice}, 2^k, 4) GPU tensor")
+    return out
+
+
+def merkle_witness(spec: Optional[Spec], leaves, siblings, indices, k: int, nodes=None, out=None):
+    """The MerkleTreeV3 witnesses of m inclusion paths: ``leaves`` (m, 4), ``siblings`` (m, depth, 4) as ``hm_merkle_paths_dev``
+    writes them with one word per node and ``indices`` (m,) int64 (bit l = right child at level l) are GPU tensors of canonical
+    Montgomery words; ``nodes`` is the built tree's node tensor or None (the path's nodes are hashed from the siblings).
+    -> (advice (m, 7, 2^k, 4), instance (m, 2, 4)) int64 tensors, every word written; asynchronous on the current stream.
+    ``out``: an advice tensor to fill instead of a new one (it may be uninitialised)."""
+    import torch
+
+    from .arithmetic import _stream_ptr, _tensor_rows
+
+    spec = default_spec(3) if spec is None else spec
+    m = _tensor_rows(leaves, 4, "leaves")
+    if m == 0:
+        raise ValueError("merkle_witness: no paths")
+    depth = _tensor_rows(siblings, 4 * m, "siblings")
+    if not (indices.is_cuda and indices.is_contiguous() and indices.element_size() == 8 and indices.numel() == m):
+        raise ValueError("merkle_witness: indices must be m 64-bit integers on the GPU")
+    if nodes is not None and not (nodes.is_cuda and nodes.is_contiguous() and nodes.element_size() == 8
+                                  and nodes.numel() == ((2 << depth) - 1) * 4):
+        raise ValueError(f"merkle_witness: nodes must be the contiguous (2^(depth+1) - 1, 1, 4) GPU tensor of a tree of depth {depth}")
+    for name, t in (("siblings", siblings), ("indices", indices), ("nodes", nodes), ("out", out)):
+        if t is not None and t.is_cuda and t.device != leaves.device:
+            raise ValueError(f"merkle_witness: {name} is on {t.device}, leaves on {leaves.device}")
+    for name, t in (("leaves", leaves), ("siblings", siblings), ("nodes", nodes), ("out", out)):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"merkle_witness: {name} must be 16-byte aligned")
+    out = _witness_out("merkle_witness", out, m, MerkleTreeV3Layout.N_ADVICE, 1 << k, leaves.device)
+    inst = torch.empty((m, 2, 4), dtype=torch.int64, device=leaves.device)
+    with torch.cuda.device(leaves.device):
+        spec.call(_lib.load().hm_merkle_witness_bn256_dev, depth, k, m, ctypes.c_void_p(leaves.data_ptr()),
+                  ctypes.c_void_p(siblings.data_ptr()), ctypes.cast(ctypes.c_void_p(indices.data_ptr()), ctypes.POINTER(ctypes.c_uint64)),
+                  ctypes.c_void_p(nodes.data_ptr()) if nodes is not None else None,
+                  ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(inst.data_ptr()), ctypes.c_void_p(_stream_ptr(leaves)))
+    return out, inst
+
+
+def merkle_witness_host(spec: Optional[Spec], leaves: np.ndarray, siblings: np.ndarray, indices: np.ndarray, k: int):
+    """``merkle_witness`` on numpy arrays through the host-pointer form (small m: the columns must stay below 256 MiB)."""
+    spec = default_spec(3) if spec is None else spec
+    lv = np.ascontiguousarray(np.asarray(leaves, dtype=np.uint64).reshape(-1, 4))
+    m = lv.shape[0]
+    if m == 0:
+        raise ValueError("merkle_witness_host: no paths")
+    sb = np.ascontiguousarray(np.asarray(siblings, dtype=np.uint64).reshape(m, -1, 4))
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(m))
+    adv = np.zeros((m, MerkleTreeV3Layout.N_ADVICE, 1 << k, 4), dtype=np.uint64)
+    inst = np.zeros((m, 2, 4), dtype=np.uint64)
+    spec.call(_lib.load().hm_merkle_witness_bn256, sb.shape[1], k, m, _ptr(lv), _ptr(sb), _ptr(idx), _ptr(adv), _ptr(inst))
+    return adv, inst
+
+
+def poseidon_circuit_witness(spec: Optional[Spec], msgs, k: int, out=None):
+    """The Poseidon circuit's witnesses of m messages: ``msgs`` (m, 4, 4) GPU tensor of canonical Montgomery words
+    -> (advice (m, 6, 2^k, 4), instance (m, 1, 4)); every word written; asynchronous on the current stream."""
+    import torch
+
+    from .arithmetic import _stream_ptr, _tensor_rows
+
+    spec = default_spec(5) if spec is None else spec
+    m = _tensor_rows(msgs, 16, "msgs")
+    if m == 0:
+        raise ValueError("poseidon_circuit_witness: no messages")
+    if out is not None and out.is_cuda and out.device != msgs.device:
+        raise ValueError(f"poseidon_circuit_witness: out is on {out.device}, msgs on {msgs.device}")
+    for name, t in (("msgs", msgs), ("out", out)):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"poseidon_circuit_witness: {name} must be 16-byte aligned")
+    out = _witness_out("poseidon_circuit_witness", out, m, PoseidonCircuitLayout.N_ADVICE, 1 << k, msgs.device)
+    inst = torch.empty((m, 1, 4), dtype=torch.int64, device=msgs.device)
+    with torch.cuda.device(msgs.device):
+        spec.call(_lib.load().hm_poseidon_witness_bn256_dev, k, m, ctypes.c_void_p(msgs.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                  ctypes.c_void_p(inst.data_ptr()), ctypes.c_void_p(_stream_ptr(msgs)))
+    return out, inst
+
+
+def poseidon_circuit_witness_host(spec: Optional[Spec], msgs: np.ndarray, k: int):
+    """``poseidon_circuit_witness`` on a numpy (m, 4, 4) array through the host-pointer form (columns below 256 MiB)."""
+    spec = default_spec(5) if spec is None else spec
+    ms = np.ascontiguousarray(np.asarray(msgs, dtype=np.uint64).reshape(-1, 4, 4))
+    m = ms.shape[0]
+    if m == 0:
+        raise ValueError("poseidon_circuit_witness_host: no messages")
+    adv = np.zeros((m, PoseidonCircuitLayout.N_ADVICE, 1 << k, 4), dtype=np.uint64)
+    inst = np.zeros((m, 1, 4), dtype=np.uint64)
+    spec.call(_lib.load().hm_poseidon_witness_bn256, k, m, _ptr(ms), _ptr(adv), _ptr(inst))
     return adv, inst
 
 

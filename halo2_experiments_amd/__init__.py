@@ -21,7 +21,9 @@ from .arithmetic import (bases_info, batch_invert, best_fft, best_multiexp, best
                          release_bases)
 from .domain import EvaluationDomain  # noqa: F401
 from .poseidon import MerkleSumTree, MerkleTree, Spec, poseidon_hash, poseidon_hash_host  # noqa: F401
-from .synthesis import MerkleSumTreeLayout, merkle_sum_witness, merkle_sum_witness_host, permutation_columns  # noqa: F401
+from .synthesis import (MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, merkle_sum_witness,  # noqa: F401
+                        merkle_sum_witness_host, merkle_witness, merkle_witness_host, permutation_columns, poseidon_circuit_witness,
+                        poseidon_circuit_witness_host)
 
 __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_multiexp_submit", "best_multiexp_wait", "best_fft",
            "register_bases", "release_bases", "bases_info", "g1_fixed_base_mul", "g1_fft", "g1_fft_host", "g1_compress", "g1_compress_host",
@@ -29,4 +31,5 @@ __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_mult
            "grand_product_batch", "batch_invert",
            "linear_combination", "random_fr", "permute_expression_pair", "permute_expression_pairs", "EvaluationDomain",
            "Spec", "poseidon_hash", "poseidon_hash_host", "MerkleSumTree", "MerkleTree", "MerkleSumTreeLayout", "merkle_sum_witness",
-           "merkle_sum_witness_host", "permutation_columns"]
+           "merkle_sum_witness_host", "permutation_columns", "MerkleTreeV3Layout", "PoseidonCircuitLayout", "merkle_witness",
+           "merkle_witness_host", "poseidon_circuit_witness", "poseidon_circuit_witness_host"]

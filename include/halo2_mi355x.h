@@ -556,6 +556,28 @@ int hm_merkle_sum_witness_bn256(uint64_t handle, uint32_t depth, uint32_t log_n,
                                 const uint64_t* siblings, const uint64_t* indices, const uint64_t* assets_sum, uint64_t* advice,
                                 uint64_t* instance);
 
+/* The witnesses of the reference's two other circuits, with the same conventions as the sum tree's above.
+ * MerkleTreeV3 (width-3 spec): d_leaves m elements, d_siblings m x depth elements as hm_merkle_paths_dev writes them with one
+ * word per node, d_nodes_or_null the tree of hm_merkle_tree_build_dev; d_advice m x 7 x 2^log_n elements (a b c | state[3] |
+ * partial_sbox), d_instance m x 2 (leaf, root).  out_regions, unless NULL, receives 3 numbers: rows of a "permute state" region,
+ * rows of one level, the first row of the constants.
+ * Poseidon circuit (width-5 spec): d_msgs m x 4 elements; d_advice m x 6 x 2^log_n (state[5] | partial_sbox), d_instance m x 1
+ * (the digest).  out_regions: rows of "permute state", rows before the constants, the first row of the constants.
+ * HM_ERR_BAD_ARG: a handle of the wrong width, depth 0 or above 32, a tree pointer with depth above 30, an odd r_f or r_p, log_n
+ * above 24, rows_used > 2^log_n - 6, a device pointer that is not 16-byte aligned (d_indices: 8), m == 0, more than 2^31 hashes;
+ * the host forms: more than 256 MiB of columns.  Nothing is written or launched in those cases. */
+int hm_merkle_witness_layout(uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, uint32_t* out_rows_used, uint32_t* out_n_advice,
+                             uint32_t* out_regions);
+int hm_merkle_witness_bn256_dev(uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const void* d_leaves, const void* d_siblings,
+                                const uint64_t* d_indices, const void* d_nodes_or_null, void* d_advice, void* d_instance, void* stream);
+int hm_merkle_witness_bn256(uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const uint64_t* leaves, const uint64_t* siblings,
+                            const uint64_t* indices, uint64_t* advice, uint64_t* instance);
+int hm_poseidon_witness_layout(uint32_t r_f, uint32_t r_p, uint32_t log_n, uint32_t* out_rows_used, uint32_t* out_n_advice,
+                               uint32_t* out_regions);
+int hm_poseidon_witness_bn256_dev(uint64_t handle, uint32_t log_n, size_t m, const void* d_msgs, void* d_advice, void* d_instance,
+                                  void* stream);
+int hm_poseidon_witness_bn256(uint64_t handle, uint32_t log_n, size_t m, const uint64_t* msgs, uint64_t* advice, uint64_t* instance);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 
 typedef struct hm_msm_stats {

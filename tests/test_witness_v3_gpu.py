@@ -1,0 +1,390 @@
+"""The MerkleTreeV3 and Poseidon circuit witnesses on the GPU (csrc/poseidon.inc: merkle_witness_kernel / merkle_chain_kernel /
+poseidon_witness_kernel) against synthesis.assign_ints word for word, against the tests' MockProver, and against the gate
+polynomials of circuits.merkle_v3(spec) / circuits.poseidon(spec) run by the device GraphEvaluator over every user's columns.
+Outputs are prefilled with a sentinel, so a word the call does not write shows."""
+import ctypes
+import random
+
+import numpy as np
+import pytest
+import torch
+
+from halo2_experiments_amd import _lib, circuits, poseidon as ps, synthesis as sy
+from halo2_experiments_amd.domain import FR_MODULUS as R
+from halo2_experiments_amd.evaluation import GraphEvaluator
+
+import mock_prover
+
+pytestmark = pytest.mark.gpu
+HM_OK, HM_ERR_BAD_ARG, HM_ERR_NOT_FOUND, HM_ERR_INTERNAL = 0, -1, -4, -5
+FILL = 0x5A5A5A5A5A5A5A5A
+V3, PC = sy.MerkleTreeV3Layout, sy.PoseidonCircuitLayout
+LEAF, ELEMENTS, INDICES = 99, [1, 5, 6, 9, 9], [0, 0, 0, 0, 0]       # the reference's case, circuits/merkle_v3.rs:91-93
+
+
+def _gpu(words):
+    return torch.from_numpy(np.ascontiguousarray(words).view(np.int64)).cuda()
+
+
+def _ints(t):
+    return ps.words_to_ints(t.cpu().numpy().view(np.uint64))
+
+
+def _columns(t):
+    return [_ints(c) for c in t]
+
+
+def _u64(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+
+
+def _words(t):
+    return t.cpu().numpy().view(np.uint64)
+
+
+def _sentinel(*shape):
+    return torch.full(shape, FILL, dtype=torch.int64, device="cuda")
+
+
+def _path_tensors(paths):
+    """[(leaf, elements, index)] -> leaves (m, 4), siblings (m, depth, 4), indices (m,)"""
+    leaves = _gpu(ps.ints_to_words([p[0] for p in paths]))
+    sibs = _gpu(ps.ints_to_words([e for p in paths for e in p[1]]).reshape(len(paths), len(paths[0][1]), 4))
+    idx = torch.tensor([p[2] for p in paths], dtype=torch.int64, device="cuda")
+    return leaves, sibs, idx
+
+
+def _bits(index, depth):
+    return [(index >> l) & 1 for l in range(depth)]
+
+
+class GateCheck:
+    """Every gate of the constraint system as a program of its own on the device GraphEvaluator (rotations unscaled, 2^k rows,
+    no permutation argument): rows(...) -> {gate name: usable rows where it does not vanish}."""
+
+    def __init__(self, cs, lay):
+        self.cs, self.lay = cs, lay
+        self.fixed = [c.contiguous() for c in _gpu(sy.columns_to_words(lay.fixed_columns()))]
+        g = GraphEvaluator()
+        g.add_custom_gates(cs.polynomials())
+        self.all = g.compile(cs.num_fixed, cs.num_advice, cs.num_instance)
+        self.per_gate = {}
+        for name, polys in cs.gates:
+            g = GraphEvaluator()
+            g.add_custom_gates(polys)
+            self.per_gate[name] = g.compile(cs.num_fixed, cs.num_advice, cs.num_instance)
+        self.y = random.Random(99).randrange(R)
+
+    def _run(self, prog, adv, inst):
+        col = torch.zeros((self.lay.n, 4), dtype=torch.int64, device="cuda")
+        col[: inst.shape[0]] = inst
+        values = torch.zeros((self.lay.n, 4), dtype=torch.int64, device="cuda")
+        prog.evaluate(self.fixed + [adv[c] for c in range(self.lay.N_ADVICE)] + [col], values, y=self.y)
+        return values[: self.lay.n - sy.BLINDING_ROWS]
+
+    def satisfied(self, adv, inst) -> bool:
+        return not bool(self._run(self.all, adv, inst).any())
+
+    def rows(self, adv, inst):
+        out = {}
+        for name, prog in self.per_gate.items():
+            bad = self._run(prog, adv, inst).ne(0).any(dim=1).nonzero().flatten().tolist()
+            if bad:
+                out[name] = bad
+        return out
+
+
+@pytest.fixture(scope="module")
+def spec():
+    return ps.default_spec(3)
+
+
+def _expected(lay, paths):
+    return np.stack([sy.columns_to_words(lay.assign_ints(leaf, el, _bits(index, lay.depth))) for leaf, el, index in paths])
+
+
+def _expected_instance(spec, paths, depth):
+    return np.stack([ps.ints_to_words([leaf, ps.MerkleTree.verify_path(leaf, (el, _bits(index, depth)), spec)]) for leaf, el, index in paths])
+
+
+def test_reference_case_word_for_word_from_all_three_sources(spec):
+    lay = V3(5, 10, spec)
+    paths = [(LEAF, ELEMENTS, 0)]
+    exp, exp_inst = _expected(lay, paths), _expected_instance(spec, paths, 5)
+    leaves, sibs, idx = _path_tensors(paths)
+    # a depth-5 tree that contains the path: its nodes at position 0 of every level, the elements beside them; every other node
+    # holds the sentinel (nothing else is read)
+    nodes = _sentinel(63, 1, 4)
+    h, start = LEAF, 0
+    for l in range(5):
+        nodes[start, 0] = _gpu(ps.ints_to_words([h]))[0]
+        nodes[start + 1, 0] = _gpu(ps.ints_to_words([ELEMENTS[l]]))[0]
+        h = ps.hash_ints(spec, [h, ELEMENTS[l]])
+        start += 32 >> l
+    nodes[62, 0] = _gpu(ps.ints_to_words([h]))[0]
+    for source in (nodes, None):
+        out = _sentinel(1, V3.N_ADVICE, 1024, 4)
+        adv, inst = sy.merkle_witness(spec, leaves, sibs, idx, 10, nodes=source, out=out)
+        assert adv.data_ptr() == out.data_ptr()
+        assert np.array_equal(_words(adv), exp) and np.array_equal(_words(inst), exp_inst)
+    h_adv, h_inst = sy.merkle_witness_host(spec, _words(leaves), _words(sibs), _words(idx), 10)
+    assert np.array_equal(h_adv, exp) and np.array_equal(h_inst, exp_inst)
+    assert ps.words_to_ints(h_inst[0]) == [LEAF, h]
+    # and a path with right-hand positions from both device sources (the tree's path nodes are then not at position 0)
+    paths = [(LEAF, ELEMENTS, 0b01101)]
+    leaves, sibs, idx = _path_tensors(paths)
+    adv, inst = sy.merkle_witness(spec, leaves, sibs, idx, 10)
+    assert np.array_equal(_words(adv), _expected(lay, paths)) and np.array_equal(_words(inst), _expected_instance(spec, paths, 5))
+
+
+@pytest.fixture(scope="module")
+def batch(spec):
+    depth, m, k = 12, 1024, 10
+    rng = random.Random(2025)
+    n = 1 << depth
+    leaves = [rng.randrange(R) for _ in range(n)]
+    tree = ps.MerkleTree.build(_gpu(ps.ints_to_words(leaves)), spec)
+    idx = [0, n - 1] + [rng.randrange(n) for _ in range(m - 2)]
+    out = _sentinel(m, V3.N_ADVICE, 1 << k, 4)
+    adv, inst = tree.witness(idx, k, out=out)
+    torch.cuda.synchronize()
+    lay = V3(depth, k, spec)
+    cs = circuits.merkle_v3(spec)
+    return dict(depth=depth, m=m, k=k, rng=rng, leaves=leaves, tree=tree, idx=idx, adv=adv, inst=inst, lay=lay, cs=cs, check=GateCheck(cs, lay))
+
+
+def test_batch_every_user_satisfies_the_gates(batch):
+    chk = batch["check"]
+    assert not bool((batch["adv"] == FILL).all(dim=-1).any())          # no element is left as the sentinel
+    bad = [u for u in range(batch["m"]) if not chk.satisfied(batch["adv"][u], batch["inst"][u])]
+    assert bad == []
+    # the check is not blind: one changed state word of one user is seen
+    adv = batch["adv"][7].clone()
+    adv[V3.STATE[1], batch["lay"].perm_row(3) + 10, 0] ^= 1
+    assert not chk.satisfied(adv, batch["inst"][7])
+    assert set(chk.rows(adv, batch["inst"][7])) == {"partial rounds"}
+
+
+def test_batch_roots_and_leaves(batch):
+    lay, adv, inst, tree = batch["lay"], batch["adv"], batch["inst"], batch["tree"]
+    _, col, row = lay.digest_cell(lay.depth - 1)
+    assert set(_ints(adv[:, col, row])) == {tree.root} and set(_ints(inst[:, 1])) == {tree.root}
+    assert _ints(inst[:, 0]) == [batch["leaves"][i] for i in batch["idx"]] == _ints(adv[:, V3.A, 0])
+
+
+def test_batch_sixteen_users_word_for_word_and_mock_prover(batch):
+    lay, cs, tree = batch["lay"], batch["cs"], batch["tree"]
+    users = [0, 1] + batch["rng"].sample(range(2, batch["m"]), 14)
+    fixed = lay.fixed_columns()
+    paths = tree.paths([batch["idx"][u] for u in users])
+    rows = [r for reg in lay.regions if reg.name != "constants" for r in reg.rows] + [lay.used_rows, lay.n - 7]
+    for u, (elements, bits) in zip(users, paths):
+        exp = lay.assign_ints(batch["leaves"][batch["idx"][u]], elements, bits)
+        assert np.array_equal(_words(batch["adv"][u]), sy.columns_to_words(exp)), u
+        inst_col = [0] * lay.n
+        inst_col[:2] = _ints(batch["inst"][u])
+        assert mock_prover.verify(cs, fixed, _columns(batch["adv"][u]), [inst_col], lay.copies(), lay.n, lay.n - sy.BLINDING_ROWS, rows=rows) == [], u
+
+
+def test_batch_without_the_tree_gives_identical_bytes(batch, spec):
+    tree, idx = batch["tree"], batch["idx"]
+    d_idx = torch.tensor(idx, dtype=torch.int64, device="cuda")
+    sib = torch.empty((len(idx), tree.depth, 4), dtype=torch.int64, device="cuda")
+    _lib.check(_lib.load().hm_merkle_paths_dev(ctypes.c_void_p(tree.nodes.data_ptr()), tree.depth, 1,
+                                               ctypes.cast(ctypes.c_void_p(d_idx.data_ptr()), ctypes.POINTER(ctypes.c_uint64)), len(idx),
+                                               ctypes.c_void_p(sib.data_ptr()), None))
+    torch.cuda.synchronize()
+    out = _sentinel(len(idx), V3.N_ADVICE, 1 << batch["k"], 4)
+    adv, inst = sy.merkle_witness(spec, tree.nodes[d_idx].reshape(-1, 4).contiguous(), sib, d_idx, batch["k"], out=out)
+    assert torch.equal(adv, batch["adv"]) and torch.equal(inst, batch["inst"])
+
+
+@pytest.mark.parametrize("depth,m,k,with_tree", [(1, 1, 6, True), (1, 257, 6, True), (1, 257, 6, False), (2, 129, 7, True), (2, 129, 7, False),
+                                                 (32, 3, 11, False)])
+def test_smallest_shapes(spec, depth, m, k, with_tree):
+    """depth 1: level 0 is also the last level and the chain has nothing to do; m * depth = 257, 258 and 96 are no multiples of the
+    256 lanes of a workgroup; depth 32 is the deepest path (no tree that deep can be built); index bits above `depth` are ignored."""
+    assert k == V3.min_k(depth, spec)
+    lay = V3(depth, k, spec)
+    rng = random.Random(100 * depth + m)
+    if with_tree:
+        leaves = [rng.randrange(R) for _ in range(1 << depth)]
+        tree = ps.MerkleTree.build(_gpu(ps.ints_to_words(leaves)), spec)
+        index = [rng.randrange(1 << depth) for _ in range(m)]
+        paths = [(leaves[i], el, i) for i, (el, _) in zip(index, tree.paths(index))]
+        nodes = tree.nodes
+    else:
+        paths = [(rng.randrange(R), [rng.randrange(R) for _ in range(depth)], rng.randrange(1 << depth)) for _ in range(m)]
+        paths[0] = (paths[0][0], paths[0][1], (1 << depth) - 1)
+        nodes = None
+    exp, exp_inst = _expected(lay, paths), _expected_instance(spec, paths, depth)
+    leaves_t, sibs, idx = _path_tensors(paths)
+    out = _sentinel(m, V3.N_ADVICE, 1 << k, 4)
+    adv, inst = sy.merkle_witness(spec, leaves_t, sibs, idx, k, nodes=nodes, out=out)
+    assert np.array_equal(_words(adv), exp) and np.array_equal(_words(inst), exp_inst)
+    if with_tree:
+        assert set(_ints(inst[:, 1])) == {tree.root}
+    high = idx | (0x5A5A5 << 33) | (1 << depth if depth < 32 else 0)        # bits above `depth`: ignored
+    adv2, inst2 = sy.merkle_witness(spec, leaves_t, sibs, high, k, nodes=nodes, out=_sentinel(m, V3.N_ADVICE, 1 << k, 4))
+    assert torch.equal(adv2, adv) and torch.equal(inst2, inst)
+
+
+@pytest.mark.parametrize("k", [6, 7])
+def test_poseidon_circuit_thousand_messages(k):
+    spec = ps.default_spec(5)
+    lay = PC(k, spec)
+    cs = circuits.poseidon(spec)
+    m = 1000
+    rng = random.Random(k)
+    msgs = [[99] * 4, [0, 1, R - 1, R - 2]] + [[rng.randrange(R) for _ in range(4)] for _ in range(m - 2)]
+    d_msgs = _gpu(ps.ints_to_words([v for msg in msgs for v in msg]).reshape(m, 4, 4))
+    out = _sentinel(m, PC.N_ADVICE, 1 << k, 4)
+    adv, inst = sy.poseidon_circuit_witness(spec, d_msgs, k, out=out)
+    assert adv.data_ptr() == out.data_ptr() and inst.shape == (m, 1, 4)
+    digests = ps.poseidon_hash(spec, d_msgs)
+    _, col, row = lay.digest_cell()
+    assert torch.equal(adv[:, col, row], digests) and torch.equal(inst[:, 0], digests)
+    assert _ints(digests[:2]) == [ps.hash_ints(spec, msgs[0]), ps.hash_ints(spec, msgs[1])]
+    for u in [0, 1] + rng.sample(range(2, m), 14):
+        assert np.array_equal(_words(adv[u]), sy.columns_to_words(lay.assign_ints(msgs[u]))), u
+    chk = GateCheck(cs, lay)
+    assert [u for u in range(m) if not chk.satisfied(adv[u], inst[u])] == []
+    bad = adv[5].clone()
+    bad[PC.STATE[3], lay.perm_row() + 2, 0] ^= 1
+    assert set(chk.rows(bad, inst[5])) == {"full round"}
+    h_adv, h_inst = sy.poseidon_circuit_witness_host(spec, _words(d_msgs[:3]), k)
+    assert np.array_equal(h_adv, _words(adv[:3])) and np.array_equal(h_inst, _words(inst[:3]))
+    u = 17
+    inst_col = [0] * lay.n
+    inst_col[0] = _ints(inst[u])[0]
+    assert mock_prover.verify(cs, lay.fixed_columns(), _columns(adv[u]), [inst_col], lay.copies(), lay.n, lay.n - sy.BLINDING_ROWS) == []
+
+
+def test_rejected_arguments_leave_the_output_untouched(spec):
+    lib = _lib.load()
+    leaves, sibs, idx = _path_tensors([(LEAF, ELEMENTS, 0)])
+    adv, inst = _sentinel(1, V3.N_ADVICE, 1024, 4), _sentinel(1, 2, 4)
+    h3, h5 = spec.handle(), ps.default_spec(5).handle()
+    odd = ps.Spec(3, 2, 8, 55)                                     # the library takes an odd r_p as a spec; the Pow5 chip does not
+    P = lambda t: (ctypes.c_void_p(t) if isinstance(t, int) else ctypes.c_void_p(t.data_ptr())) if t is not None else None
+    I = lambda t: ctypes.cast(P(t), ctypes.POINTER(ctypes.c_uint64)) if t is not None else None
+
+    def call(handle=h3, depth=5, log_n=10, m=1, lv=leaves, sb=sibs, ix=idx, nodes=None, out=adv, ins=inst):
+        return lib.hm_merkle_witness_bn256_dev(handle, depth, log_n, m, P(lv), P(sb), I(ix), P(nodes), P(out), P(ins), None)
+
+    assert call(handle=h5) == HM_ERR_BAD_ARG                      # a width-5 spec
+    assert call(handle=987654321) == HM_ERR_NOT_FOUND
+    assert call(handle=odd.handle()) == HM_ERR_BAD_ARG and b"even" in lib.hm_last_error()
+    assert call(depth=0) == HM_ERR_BAD_ARG and call(depth=33, log_n=12) == HM_ERR_BAD_ARG
+    assert call(log_n=7) == HM_ERR_BAD_ARG and b"231" in lib.hm_last_error()      # 231 rows do not fit 2^7 - 6
+    assert call(log_n=25) == HM_ERR_BAD_ARG
+    assert call(depth=20, log_n=9) == HM_ERR_BAD_ARG and b"921" in lib.hm_last_error()
+    assert call(depth=31, log_n=11, nodes=adv) == HM_ERR_BAD_ARG  # a built tree has depth <= 30
+    assert call(m=0) == HM_ERR_BAD_ARG
+    for kw in ("lv", "sb", "ix", "out", "ins"):
+        assert call(**{kw: None}) == HM_ERR_BAD_ARG, kw
+    for kw, t in (("lv", leaves), ("sb", sibs), ("out", adv), ("ins", inst), ("nodes", adv)):
+        assert call(**{kw: t.data_ptr() + 8}) == HM_ERR_BAD_ARG and b"aligned" in lib.hm_last_error(), kw
+    assert call(m=((1 << 31) // 5) + 1) == HM_ERR_BAD_ARG and b"2^31" in lib.hm_last_error()
+    torch.cuda.synchronize()
+    assert bool((adv == FILL).all()) and bool((inst == FILL).all())
+    tree4 = ps.MerkleTree.build(_gpu(ps.ints_to_words(list(range(16)))), spec)      # depth 4: too small for a depth-5 path
+    with pytest.raises(ValueError, match="nodes"):
+        sy.merkle_witness(spec, leaves, sibs, idx, 10, nodes=tree4.nodes)
+    with pytest.raises(ValueError, match="aligned"):
+        sy.merkle_witness(spec, leaves, sibs, idx, 10, out=_sentinel(V3.N_ADVICE * 1024 * 4 + 1)[1:])
+    with pytest.raises(ValueError, match="out"):
+        sy.merkle_witness(spec, leaves, sibs, idx, 10, out=_sentinel(1, V3.N_ADVICE, 512, 4))
+    # the host form
+    h_adv, h_inst = np.full((1, V3.N_ADVICE, 1024, 4), FILL, dtype=np.uint64), np.full((1, 2, 4), FILL, dtype=np.uint64)
+    lv, sb, ix = (_words(t) for t in (leaves, sibs, idx))
+    host = lambda handle=h3, depth=5, log_n=10, m=1, lv=lv: lib.hm_merkle_witness_bn256(
+        handle, depth, log_n, m, _u64(lv) if lv is not None else None, _u64(sb), _u64(ix), _u64(h_adv), _u64(h_inst))
+    assert host(handle=h5) == HM_ERR_BAD_ARG and host(depth=0) == HM_ERR_BAD_ARG and host(log_n=7) == HM_ERR_BAD_ARG
+    assert host(lv=None) == HM_ERR_BAD_ARG and host(m=0) == HM_ERR_BAD_ARG
+    assert host(m=100000) == HM_ERR_BAD_ARG and b"256 MiB" in lib.hm_last_error()
+    assert (h_adv == FILL).all() and (h_inst == FILL).all()
+    rows, n_adv = ctypes.c_uint32(7), ctypes.c_uint32(7)
+    assert lib.hm_merkle_witness_layout(8, 56, 5, 10, None, ctypes.byref(n_adv), None) == HM_ERR_BAD_ARG
+    assert lib.hm_merkle_witness_layout(8, 55, 5, 10, ctypes.byref(rows), ctypes.byref(n_adv), None) == HM_ERR_BAD_ARG
+    assert lib.hm_merkle_witness_layout(7, 56, 5, 10, ctypes.byref(rows), ctypes.byref(n_adv), None) == HM_ERR_BAD_ARG
+    assert (rows.value, n_adv.value) == (7, 7)
+    assert call() == HM_OK                                        # and the same arguments, valid, work
+    torch.cuda.synchronize()
+    assert not bool((adv == FILL).all(dim=-1).any()) and not bool((inst == FILL).any())
+    odd.release()
+
+
+def test_rejected_arguments_of_the_poseidon_circuit():
+    lib = _lib.load()
+    spec = ps.default_spec(5)
+    msgs = _gpu(ps.ints_to_words([99] * 4).reshape(1, 4, 4))
+    adv, inst = _sentinel(1, PC.N_ADVICE, 64, 4), _sentinel(1, 1, 4)
+    h5, h3 = spec.handle(), ps.default_spec(3).handle()
+    odd = ps.Spec(5, 4, 8, 55)
+    P = lambda t: (ctypes.c_void_p(t) if isinstance(t, int) else ctypes.c_void_p(t.data_ptr())) if t is not None else None
+
+    def call(handle=h5, log_n=6, m=1, ms=msgs, out=adv, ins=inst):
+        return lib.hm_poseidon_witness_bn256_dev(handle, log_n, m, P(ms), P(out), P(ins), None)
+
+    assert call(handle=h3) == HM_ERR_BAD_ARG and call(handle=987654321) == HM_ERR_NOT_FOUND
+    assert call(handle=odd.handle()) == HM_ERR_BAD_ARG and b"even" in lib.hm_last_error()
+    assert call(log_n=5) == HM_ERR_BAD_ARG and b"48" in lib.hm_last_error()
+    assert call(log_n=25) == HM_ERR_BAD_ARG and call(m=0) == HM_ERR_BAD_ARG
+    assert call(m=(1 << 31) + 1) == HM_ERR_BAD_ARG and b"2^31" in lib.hm_last_error()
+    for kw, t in (("ms", msgs), ("out", adv), ("ins", inst)):
+        assert call(**{kw: None}) == HM_ERR_BAD_ARG, kw
+        assert call(**{kw: t.data_ptr() + 8}) == HM_ERR_BAD_ARG and b"aligned" in lib.hm_last_error(), kw
+    torch.cuda.synchronize()
+    assert bool((adv == FILL).all()) and bool((inst == FILL).all())
+    h_adv, h_inst = np.full((1, PC.N_ADVICE, 64, 4), FILL, dtype=np.uint64), np.full((1, 1, 4), FILL, dtype=np.uint64)
+    ms = _words(msgs)
+    host = lambda handle=h5, log_n=6, m=1, ms=ms: lib.hm_poseidon_witness_bn256(handle, log_n, m, _u64(ms) if ms is not None else None,
+                                                                                 _u64(h_adv), _u64(h_inst))
+    assert host(handle=h3) == HM_ERR_BAD_ARG and host(log_n=5) == HM_ERR_BAD_ARG and host(ms=None) == HM_ERR_BAD_ARG and host(m=0) == HM_ERR_BAD_ARG
+    assert host(m=100000) == HM_ERR_BAD_ARG and b"256 MiB" in lib.hm_last_error()
+    assert (h_adv == FILL).all() and (h_inst == FILL).all()
+    rows, n_adv = ctypes.c_uint32(7), ctypes.c_uint32(7)
+    assert lib.hm_poseidon_witness_layout(8, 56, 6, None, ctypes.byref(n_adv), None) == HM_ERR_BAD_ARG
+    assert lib.hm_poseidon_witness_layout(8, 55, 6, ctypes.byref(rows), ctypes.byref(n_adv), None) == HM_ERR_BAD_ARG
+    assert (rows.value, n_adv.value) == (7, 7)
+    with pytest.raises(ValueError, match="out"):
+        sy.poseidon_circuit_witness(spec, msgs, 6, out=_sentinel(1, PC.N_ADVICE, 128, 4))
+    assert call() == HM_OK
+    torch.cuda.synchronize()
+    assert not bool((adv == FILL).all(dim=-1).any()) and not bool((inst == FILL).any())
+    odd.release()
+
+
+def test_fault_points_of_the_host_forms(spec):
+    fi = _lib.load_fi()
+    try:
+        handles = {}
+        for width, sp in ((3, spec), (5, ps.default_spec(5))):
+            rc, mds, _ = sp.constants()
+            h = ctypes.c_uint64(0)
+            assert fi.hm_poseidon_create(width, width - 1, 8, 56, _u64(ps.ints_to_words([v for r in rc for v in r])),
+                                         _u64(ps.ints_to_words([v for r in mds for v in r])), ctypes.byref(h)) == HM_OK
+            handles[width] = h
+        lay, play = V3(5, 10, spec), PC(6)
+        exp = sy.columns_to_words(lay.assign_ints(LEAF, ELEMENTS, INDICES))
+        pexp = sy.columns_to_words(play.assign_ints([99] * 4))
+        lv, sb, ix = ps.ints_to_words([LEAF]), ps.ints_to_words(ELEMENTS), np.zeros(1, dtype=np.uint64)
+        ms = ps.ints_to_words([99] * 4)
+        for point in (b"witness_upload", b"witness_download"):
+            adv, inst = np.full((1, V3.N_ADVICE, 1024, 4), FILL, dtype=np.uint64), np.full((1, 2, 4), FILL, dtype=np.uint64)
+            merkle = lambda: fi.hm_merkle_witness_bn256(handles[3], 5, 10, 1, _u64(lv), _u64(sb), _u64(ix), _u64(adv), _u64(inst))
+            fi.hm_test_arm_fault(point, 0)
+            assert merkle() == HM_ERR_INTERNAL and b"injected fault at " + point in fi.hm_last_error()
+            assert (adv == FILL).all() and (inst == FILL).all()
+            assert merkle() == HM_OK and np.array_equal(adv[0], exp)
+            padv, pinst = np.full((1, PC.N_ADVICE, 64, 4), FILL, dtype=np.uint64), np.full((1, 1, 4), FILL, dtype=np.uint64)
+            poseidon = lambda: fi.hm_poseidon_witness_bn256(handles[5], 6, 1, _u64(ms), _u64(padv), _u64(pinst))
+            fi.hm_test_arm_fault(point, 0)
+            assert poseidon() == HM_ERR_INTERNAL and b"injected fault at " + point in fi.hm_last_error()
+            assert (padv == FILL).all() and (pinst == FILL).all()
+            assert poseidon() == HM_OK and np.array_equal(padv[0], pexp)
+        for h in handles.values():
+            assert fi.hm_poseidon_destroy(h) == HM_OK
+    finally:
+        fi.hm_test_arm_fault(None, 0)

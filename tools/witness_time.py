@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Times the MerkleSumTree witness call (hm_merkle_sum_witness_bn256_dev) against its two floors, in one process and one run:
+"""Times a circuit's witness call against its two floors, in one process and one run (--circuit: merkle_sum_tree, the default,
+hm_merkle_sum_witness_bn256_dev; merkle_v3, hm_merkle_witness_bn256_dev at k = 10 depth 20; poseidon, hm_poseidon_witness_bn256_dev at
+k = 6, one hash per user):
 
-    hash floor   hm_poseidon_hash_bn256_fr_dev on the same number of width-5 hashes (the arithmetic alone)
+    hash floor   hm_poseidon_hash_bn256_fr_dev on the same number of hashes of the circuit's width (the arithmetic alone)
     write floor  hipMemsetAsync of the same output size (every word of the columns is written)
 
 The yardstick is the SUM of the floors.  Shapes: k = 9 depth 5 and k = 10 depth 20, m x depth = 2^16, 2^18,
@@ -10,7 +12,7 @@ at k = 9 and 3 276 users (65 520 hashes) at k = 10: a few hundred blocks, so the
 not full; a larger --max-gib shows the filled rate.  Each figure is the median of --reps timed runs after a
 warm-up; times are hipEvent times around the whole chunk loop.  The chain kernel of tree-less paths is reported separately.
 
-    python tools/witness_time.py [--hashes 65536 262144 1048576] [--reps 5] [--max-gib 2] [--json out.json]
+    python tools/witness_time.py [--circuit merkle_sum_tree] [--hashes 65536 262144 1048576] [--reps 5] [--max-gib 2] [--json out.json]
 """
 import argparse
 import ctypes
@@ -24,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main() -> int:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--circuit", choices=["merkle_sum_tree", "merkle_v3", "poseidon"], default="merkle_sum_tree")
     ap.add_argument("--hashes", type=int, nargs="+", default=[1 << 16, 1 << 18, 1 << 20])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--max-gib", type=float, default=2.0)
@@ -33,7 +36,11 @@ def main() -> int:
     import torch
     from halo2_experiments_amd import poseidon as ps, random_fr, synthesis as sy
 
-    spec = ps.default_spec(5)
+    # per circuit: spec width, advice columns, elements per node, the (k, depth) shapes
+    width, n_advice, elems, shapes = {"merkle_sum_tree": (5, sy.N_ADVICE, 2, ((9, 5), (10, 20))),
+                                      "merkle_v3": (3, sy.MerkleTreeV3Layout.N_ADVICE, 1, ((10, 20),)),
+                                      "poseidon": (5, sy.PoseidonCircuitLayout.N_ADVICE, 0, ((6, 1),))}[args.circuit]
+    spec = ps.default_spec(width)
     results = []
     torch.cuda.init()
     with open("/proc/self/maps") as f:              # the HIP runtime this process already runs on (torch's), not a second copy
@@ -55,22 +62,29 @@ def main() -> int:
             ts.append(a.elapsed_time(b))
         return statistics.median(ts)
 
-    for k, depth in ((9, 5), (10, 20)):
-        user_bytes = sy.N_ADVICE * (32 << k)
+    for k, depth in shapes:
+        user_bytes = n_advice * (32 << k)
         for hashes in args.hashes:
             m = hashes // depth
             chunk = max(1, min(m, int(args.max_gib * (1 << 30)) // user_bytes))
-            leaves = random_fr(chunk * 2, 1, "cuda").view(chunk, 2, 4)
-            sib = random_fr(chunk * depth * 2, 2, "cuda").view(chunk, depth, 2, 4)
-            idx = torch.arange(chunk, dtype=torch.int64, device="cuda") * 2654435761 % (1 << depth)
-            nodes = random_fr(((2 << depth) - 1) * 2, 3, "cuda").view(-1, 2, 4)      # any node values: the time does not depend on them
-            out = torch.empty((chunk, sy.N_ADVICE, 1 << k, 4), dtype=torch.int64, device="cuda")
-            msgs = random_fr(chunk * depth * 4, 4, "cuda").view(chunk * depth, 4, 4)
+            out = torch.empty((chunk, n_advice, 1 << k, 4), dtype=torch.int64, device="cuda")
+            msgs = random_fr(chunk * depth * (width - 1), 4, "cuda").view(chunk * depth, width - 1, 4)
             chunks = [chunk] * (m // chunk) + ([m % chunk] if m % chunk else [])
+            leaves = sib = idx = nodes = None
+            if elems:
+                leaves = random_fr(chunk * elems, 1, "cuda").view(chunk, elems, 4)
+                sib = random_fr(chunk * depth * elems, 2, "cuda").view(chunk, depth, elems, 4)
+                idx = torch.arange(chunk, dtype=torch.int64, device="cuda") * 2654435761 % (1 << depth)
+                nodes = random_fr(((2 << depth) - 1) * elems, 3, "cuda").view(-1, elems, 4)      # any node values: the time does not depend on them
 
             def witness(nodes_arg):
                 for c in chunks:
-                    sy.merkle_sum_witness(spec, leaves[:c], sib[:c], idx[:c], 1 << 60, k, nodes=nodes_arg, out=out[:c])
+                    if args.circuit == "merkle_sum_tree":
+                        sy.merkle_sum_witness(spec, leaves[:c], sib[:c], idx[:c], 1 << 60, k, nodes=nodes_arg, out=out[:c])
+                    elif args.circuit == "merkle_v3":
+                        sy.merkle_witness(spec, leaves[:c], sib[:c], idx[:c], k, nodes=nodes_arg, out=out[:c])
+                    else:
+                        sy.poseidon_circuit_witness(spec, msgs[:c], k, out=out[:c])
 
             def hash_floor():
                 for c in chunks:
@@ -82,11 +96,12 @@ def main() -> int:
                     if hip.hipMemsetAsync(ctypes.c_void_p(out.data_ptr()), 0, ctypes.c_size_t(c * user_bytes), stream) != 0:
                         raise RuntimeError("hipMemsetAsync failed")
 
-            t_tree, t_chain = timed(lambda: witness(nodes)), timed(lambda: witness(None))
+            t_tree = timed(lambda: witness(nodes))
+            t_chain = timed(lambda: witness(None)) if elems else None          # the Poseidon circuit has no path and no chain
             t_hash, t_write = timed(hash_floor), timed(write_floor)
-            row = dict(k=k, depth=depth, hashes=m * depth, users=m, chunk=chunk, output_gib=round(m * user_bytes / (1 << 30), 3),
+            row = dict(circuit=args.circuit, k=k, depth=depth, hashes=m * depth, users=m, chunk=chunk, output_gib=round(m * user_bytes / (1 << 30), 3),
                        witness_ms=round(t_tree, 3), hash_floor_ms=round(t_hash, 3), write_floor_ms=round(t_write, 3),
-                       ratio=round(t_tree / (t_hash + t_write), 3), witness_without_tree_ms=round(t_chain, 3))
+                       ratio=round(t_tree / (t_hash + t_write), 3), witness_without_tree_ms=round(t_chain, 3) if elems else None)
             print(json.dumps(row), flush=True)
             results.append(row)
             del leaves, sib, idx, nodes, out, msgs
