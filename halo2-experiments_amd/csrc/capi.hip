@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <initializer_list>
 #include <string>
 #include <map>
 #include <random>
@@ -2359,192 +2360,128 @@ int hm_merkle_paths_dev(const void* d_nodes, uint32_t depth, uint32_t words_per_
   return merkle_paths_run((const uint32_t*)d_nodes, depth, words_per_node, d_indices, m, (uint32_t*)d_out, (hipStream_t)stream);
 } HM_API_CATCH("hm_merkle_paths_dev")
 
-// ---- the MerkleSumTree witness (poseidon.inc: merkle_sum_witness_lane) ------------------------------------------------------------
+// ---- the witnesses of the three circuits (poseidon.inc: merkle_witness_lane<E>, poseidon_witness_lane) -------------------------------
+// E, the elements per node, names the circuit: 2 MerkleSumTree (width 5), 1 MerkleTreeV3 (width 3), 0 the Poseidon circuit (width 5,
+// one hash, no levels: depth is ignored)
 static constexpr uint32_t WITNESS_MAX_DEPTH = 32, WITNESS_MAX_LOG_N = 24;
 static constexpr size_t WITNESS_HOST_MAX_BYTES = (size_t)1 << 28;
 
-static int witness_layout(const char* who, uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, uint32_t (&out)[6]) {
-  if (depth == 0 || depth > WITNESS_MAX_DEPTH) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": depth must be 1 .. 32");
+// out = rows_used, n_advice, perm_rows, level_rows, lt_row, const_row
+static int witness_layout(const char* who, uint32_t E, uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, uint32_t (&out)[6]) {
+  if (E && (depth == 0 || depth > WITNESS_MAX_DEPTH)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": depth must be 1 .. 32");
   if ((r_f & 1) || (r_p & 1) || r_f + r_p == 0 || r_f > 1024 || r_p > 1024)
     return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the Pow5 chip needs even r_f and r_p");
   if (log_n > WITNESS_MAX_LOG_N) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": log_n > 24");
-  merkle_sum_witness_rows(depth, r_f, r_p, out);
+  witness_rows(E, depth, r_f, r_p, out);
   if (((uint64_t)1 << log_n) < (uint64_t)out[0] + 6)
     return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the circuit needs " + std::to_string(out[0]) + " rows, 2^log_n - 6 is fewer");
+  return HM_OK;
+}
+
+// the hm_*_witness_layout entry points; out_regions: perm_rows, level_rows, (E = 2: lt_row,) const_row
+static int witness_layout_api(const char* who, uint32_t E, uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n,
+                              uint32_t* out_rows_used, uint32_t* out_n_advice, uint32_t* out_regions) {
+  if (!out_rows_used || !out_n_advice) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  uint32_t t[6];
+  if (int rc = witness_layout(who, E, r_f, r_p, depth, log_n, t)) return rc;
+  *out_rows_used = t[0];
+  *out_n_advice = t[1];
+  if (out_regions) {
+    *out_regions++ = t[2];
+    *out_regions++ = t[3];
+    if (E == 2) *out_regions++ = t[4];
+    *out_regions = t[5];
+  }
   return HM_OK;
 }
 
 int hm_merkle_sum_witness_layout(uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, uint32_t* out_rows_used,
                                  uint32_t* out_n_advice, uint32_t* out_regions) try {
-  if (!out_rows_used || !out_n_advice) return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_sum_witness_layout: null argument");
-  uint32_t t[6];
-  if (int rc = witness_layout("hm_merkle_sum_witness_layout", r_f, r_p, depth, log_n, t)) return rc;
-  *out_rows_used = t[0];
-  *out_n_advice = t[1];
-  if (out_regions) std::memcpy(out_regions, t + 2, 4 * sizeof(uint32_t));
-  return HM_OK;
+  return witness_layout_api("hm_merkle_sum_witness_layout", 2, r_f, r_p, depth, log_n, out_rows_used, out_n_advice, out_regions);
 } HM_API_CATCH("hm_merkle_sum_witness_layout")
 
-// everything that can be refused is refused here, before the first launch; -> the spec and n_advice
-static int witness_args(const char* who, DeviceCtx& ctx, uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, bool with_nodes,
-                        PoseidonSpec** s, uint32_t* n_advice) {
-  if (int rc = merkle_spec(who, ctx, handle, 5, s)) return rc;
+int hm_merkle_witness_layout(uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, uint32_t* out_rows_used, uint32_t* out_n_advice,
+                             uint32_t* out_regions) try {
+  return witness_layout_api("hm_merkle_witness_layout", 1, r_f, r_p, depth, log_n, out_rows_used, out_n_advice, out_regions);
+} HM_API_CATCH("hm_merkle_witness_layout")
+
+int hm_poseidon_witness_layout(uint32_t r_f, uint32_t r_p, uint32_t log_n, uint32_t* out_rows_used, uint32_t* out_n_advice,
+                               uint32_t* out_regions) try {
+  return witness_layout_api("hm_poseidon_witness_layout", 0, r_f, r_p, 0, log_n, out_rows_used, out_n_advice, out_regions);
+} HM_API_CATCH("hm_poseidon_witness_layout")
+
+// Everything that can be refused is refused here, before the first launch; -> the spec and n_advice.  The sum tree's forms accept
+// m == 0 (nothing is written), the two others refuse it.
+static int witness_args(const char* who, DeviceCtx& ctx, uint64_t handle, uint32_t E, uint32_t depth, uint32_t log_n, size_t m,
+                        bool with_nodes, PoseidonSpec** s, uint32_t* n_advice) {
+  if (m == 0 && E != 2) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": m must be at least 1");
+  if (int rc = merkle_spec(who, ctx, handle, E == 1 ? 3 : 5, s)) return rc;
   uint32_t t[6];
-  if (int rc = witness_layout(who, (*s)->r_f, (*s)->r_p, depth, log_n, t)) return rc;
+  if (int rc = witness_layout(who, E, (*s)->r_f, (*s)->r_p, depth, log_n, t)) return rc;
   if (with_nodes && depth > MERKLE_MAX_DEPTH) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a built tree has depth <= 30");
-  if ((uint64_t)m * depth > POSEIDON_MAX_N) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": m * depth > 2^31");
+  if ((uint64_t)m * (E ? depth : 1u) > POSEIDON_MAX_N) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": more than 2^31 hashes");
   *n_advice = t[1];
   return HM_OK;
+}
+
+// the lanes move elements as 16-byte vectors; p8: the indices (or null)
+static int witness_aligned(const char* who, std::initializer_list<const void*> p16, const void* p8) {
+  uintptr_t bits = (uintptr_t)p8 & 7u;
+  for (const void* p : p16) bits |= (uintptr_t)p & 15u;
+  if (bits) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a device pointer is not 16-byte aligned (d_indices: 8)");
+  return HM_OK;
+}
+
+// the device forms of the two path circuits
+static int merkle_witness_dev(const char* who, uint32_t E, uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const void* d_leaves,
+                              const void* d_siblings, const uint64_t* d_indices, const uint64_t* assets_sum, const void* d_nodes_or_null,
+                              void* d_advice, void* d_instance, void* stream) {
+  if (!d_leaves || !d_siblings || !d_indices || (E == 2 && !assets_sum) || !d_advice || !d_instance)
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (int rc = witness_aligned(who, {d_leaves, d_siblings, d_nodes_or_null, d_advice, d_instance}, d_indices)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PoseidonSpec* s = nullptr;
+  uint32_t n_advice = 0;
+  if (int rc = witness_args(who, *ctx, handle, E, depth, log_n, m, d_nodes_or_null != nullptr, &s, &n_advice)) return rc;
+  return merkle_witness_run(E, *s, depth, log_n, m, (const uint32_t*)d_leaves, (const uint32_t*)d_siblings, d_indices, assets_sum,
+                            (const uint32_t*)d_nodes_or_null, (uint32_t*)d_advice, (uint32_t*)d_instance, (hipStream_t)stream);
 }
 
 int hm_merkle_sum_witness_bn256_dev(uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const void* d_leaves,
                                     const void* d_siblings, const uint64_t* d_indices, const uint64_t* assets_sum,
                                     const void* d_nodes_or_null, void* d_advice, void* d_instance, void* stream) try {
-  if (!d_leaves || !d_siblings || !d_indices || !assets_sum || !d_advice || !d_instance)
-    return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_sum_witness_bn256_dev: null argument");
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PoseidonSpec* s = nullptr;
-  uint32_t n_advice = 0;
-  if (int rc = witness_args("hm_merkle_sum_witness_bn256_dev", *ctx, handle, depth, log_n, m, d_nodes_or_null != nullptr, &s, &n_advice))
-    return rc;
-  return merkle_sum_witness_run(*s, depth, log_n, m, (const uint32_t*)d_leaves, (const uint32_t*)d_siblings, d_indices, assets_sum,
-                                (const uint32_t*)d_nodes_or_null, (uint32_t*)d_advice, (uint32_t*)d_instance, (hipStream_t)stream);
+  return merkle_witness_dev("hm_merkle_sum_witness_bn256_dev", 2, handle, depth, log_n, m, d_leaves, d_siblings, d_indices, assets_sum,
+                            d_nodes_or_null, d_advice, d_instance, stream);
 } HM_API_CATCH("hm_merkle_sum_witness_bn256_dev")
-
-int hm_merkle_sum_witness_bn256(uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const uint64_t* leaves,
-                                const uint64_t* siblings, const uint64_t* indices, const uint64_t* assets_sum, uint64_t* advice,
-                                uint64_t* instance) try {
-  if (!leaves || !siblings || !indices || !assets_sum || !advice || !instance)
-    return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_sum_witness_bn256: null argument");
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PoseidonSpec* s = nullptr;
-  uint32_t n_advice = 0;
-  if (int rc = witness_args("hm_merkle_sum_witness_bn256", *ctx, handle, depth, log_n, m, false, &s, &n_advice)) return rc;
-  if (m == 0) return HM_OK;
-  const size_t col_bytes = (size_t)32 << log_n;
-  if (m > WITNESS_HOST_MAX_BYTES / ((size_t)n_advice * col_bytes))
-    return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_sum_witness_bn256: the columns exceed 256 MiB; use the device form");
-  const size_t leaf_bytes = m * 64, sib_bytes = m * depth * 64, idx_bytes = (m * 8 + 63) / 64 * 64, adv_bytes = m * n_advice * col_bytes,
-               inst_bytes = m * 128;
-  hm_fault_point("witness_upload");
-  uint8_t* d_p = (uint8_t*)ctx->io.ensure(leaf_bytes + sib_bytes + idx_bytes + adv_bytes + inst_bytes);
-  if (!d_p) return hm_fail(HM_ERR_HIP, "hm_merkle_sum_witness_bn256: staging allocation failed");
-  uint8_t *d_sib = d_p + leaf_bytes, *d_idx = d_sib + sib_bytes, *d_adv = d_idx + idx_bytes, *d_inst = d_adv + adv_bytes;
-  int rc = xfer_h2d(*ctx, d_p, leaves, leaf_bytes, "hm_merkle_sum_witness_bn256: upload");
-  if (rc == HM_OK) rc = xfer_h2d(*ctx, d_sib, siblings, sib_bytes, "hm_merkle_sum_witness_bn256: upload");
-  if (rc == HM_OK) rc = xfer_h2d(*ctx, d_idx, indices, m * 8, "hm_merkle_sum_witness_bn256: upload");
-  if (rc != HM_OK) return rc;
-  rc = merkle_sum_witness_run(*s, depth, log_n, m, (const uint32_t*)d_p, (const uint32_t*)d_sib, (const uint64_t*)d_idx, assets_sum, nullptr,
-                              (uint32_t*)d_adv, (uint32_t*)d_inst, nullptr);
-  if (rc != HM_OK) return rc;
-  HM_HIP_CHECK(hipStreamSynchronize(nullptr));
-  hm_fault_point("witness_download");
-  std::vector<uint64_t> inst(m * 16);
-  rc = xfer_d2h(*ctx, inst.data(), d_inst, inst_bytes, "hm_merkle_sum_witness_bn256: instance");
-  if (rc != HM_OK) return rc;                       // nothing of the caller's has been written yet
-  if (xfer_d2h(*ctx, advice, d_adv, adv_bytes, "hm_merkle_sum_witness_bn256") != HM_OK)
-    return hm_fail(HM_ERR_PARTIAL_OUTPUT, "hm_merkle_sum_witness_bn256: copying the columns back failed, they are partly written: " +
-                                              hm_last_error_string());
-  std::memcpy(instance, inst.data(), inst_bytes);
-  ctx->calls.h2d_bytes += leaf_bytes + sib_bytes + m * 8;
-  ctx->calls.d2h_bytes += adv_bytes + inst_bytes;
-  return HM_OK;
-} HM_API_CATCH("hm_merkle_sum_witness_bn256")
-
-// ---- the MerkleTreeV3 and Poseidon circuit witnesses (poseidon.inc: merkle_witness_lane, poseidon_witness_lane) ---------------------
-// depth == 0 selects the Poseidon circuit (one hash, no levels); out = rows_used, n_advice, perm_rows, level_rows, const_row
-static int pow5_witness_layout(const char* who, bool merkle, uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, uint32_t (&out)[5]) {
-  if (merkle && (depth == 0 || depth > WITNESS_MAX_DEPTH)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": depth must be 1 .. 32");
-  if ((r_f & 1) || (r_p & 1) || r_f + r_p == 0 || r_f > 1024 || r_p > 1024)
-    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the Pow5 chip needs even r_f and r_p");
-  if (log_n > WITNESS_MAX_LOG_N) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": log_n > 24");
-  if (merkle)
-    merkle_witness_rows(depth, r_f, r_p, out);
-  else
-    poseidon_witness_rows(r_f, r_p, out);
-  if (((uint64_t)1 << log_n) < (uint64_t)out[0] + 6)
-    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the circuit needs " + std::to_string(out[0]) + " rows, 2^log_n - 6 is fewer");
-  return HM_OK;
-}
-static int pow5_layout_out(const uint32_t (&t)[5], uint32_t* out_rows_used, uint32_t* out_n_advice, uint32_t* out_regions) {
-  *out_rows_used = t[0];
-  *out_n_advice = t[1];
-  if (out_regions) std::memcpy(out_regions, t + 2, 3 * sizeof(uint32_t));
-  return HM_OK;
-}
-static bool misaligned16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
-
-int hm_merkle_witness_layout(uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, uint32_t* out_rows_used, uint32_t* out_n_advice,
-                             uint32_t* out_regions) try {
-  if (!out_rows_used || !out_n_advice) return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_witness_layout: null argument");
-  uint32_t t[5];
-  if (int rc = pow5_witness_layout("hm_merkle_witness_layout", true, r_f, r_p, depth, log_n, t)) return rc;
-  return pow5_layout_out(t, out_rows_used, out_n_advice, out_regions);
-} HM_API_CATCH("hm_merkle_witness_layout")
-
-int hm_poseidon_witness_layout(uint32_t r_f, uint32_t r_p, uint32_t log_n, uint32_t* out_rows_used, uint32_t* out_n_advice,
-                               uint32_t* out_regions) try {
-  if (!out_rows_used || !out_n_advice) return hm_fail(HM_ERR_BAD_ARG, "hm_poseidon_witness_layout: null argument");
-  uint32_t t[5];
-  if (int rc = pow5_witness_layout("hm_poseidon_witness_layout", false, r_f, r_p, 0, log_n, t)) return rc;
-  return pow5_layout_out(t, out_rows_used, out_n_advice, out_regions);
-} HM_API_CATCH("hm_poseidon_witness_layout")
-
-// everything that can be refused is refused here, before the first launch; depth == 0: the Poseidon circuit (width 5)
-static int pow5_witness_args(const char* who, DeviceCtx& ctx, uint64_t handle, bool merkle, uint32_t depth, uint32_t log_n, size_t m,
-                             bool with_nodes, PoseidonSpec** s, uint32_t* n_advice) {
-  if (m == 0) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": m must be at least 1");
-  if (int rc = merkle_spec(who, ctx, handle, merkle ? 3 : 5, s)) return rc;
-  uint32_t t[5];
-  if (int rc = pow5_witness_layout(who, merkle, (*s)->r_f, (*s)->r_p, depth, log_n, t)) return rc;
-  if (with_nodes && depth > MERKLE_MAX_DEPTH) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a built tree has depth <= 30");
-  if ((uint64_t)m * (merkle ? depth : 1u) > POSEIDON_MAX_N) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": more than 2^31 hashes");
-  *n_advice = t[1];
-  return HM_OK;
-}
 
 int hm_merkle_witness_bn256_dev(uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const void* d_leaves, const void* d_siblings,
                                 const uint64_t* d_indices, const void* d_nodes_or_null, void* d_advice, void* d_instance, void* stream) try {
-  if (!d_leaves || !d_siblings || !d_indices || !d_advice || !d_instance)
-    return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_witness_bn256_dev: null argument");
-  if (misaligned16(d_leaves) || misaligned16(d_siblings) || misaligned16(d_nodes_or_null) || misaligned16(d_advice) ||
-      misaligned16(d_instance) || ((uintptr_t)d_indices & 7u))
-    return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_witness_bn256_dev: a device pointer is not 16-byte aligned (d_indices: 8)");
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PoseidonSpec* s = nullptr;
-  uint32_t n_advice = 0;
-  if (int rc = pow5_witness_args("hm_merkle_witness_bn256_dev", *ctx, handle, true, depth, log_n, m, d_nodes_or_null != nullptr, &s, &n_advice))
-    return rc;
-  return merkle_witness_run(*s, depth, log_n, m, (const uint32_t*)d_leaves, (const uint32_t*)d_siblings, d_indices,
-                            (const uint32_t*)d_nodes_or_null, (uint32_t*)d_advice, (uint32_t*)d_instance, (hipStream_t)stream);
+  return merkle_witness_dev("hm_merkle_witness_bn256_dev", 1, handle, depth, log_n, m, d_leaves, d_siblings, d_indices, nullptr,
+                            d_nodes_or_null, d_advice, d_instance, stream);
 } HM_API_CATCH("hm_merkle_witness_bn256_dev")
 
 int hm_poseidon_witness_bn256_dev(uint64_t handle, uint32_t log_n, size_t m, const void* d_msgs, void* d_advice, void* d_instance,
                                   void* stream) try {
-  if (!d_msgs || !d_advice || !d_instance) return hm_fail(HM_ERR_BAD_ARG, "hm_poseidon_witness_bn256_dev: null argument");
-  if (misaligned16(d_msgs) || misaligned16(d_advice) || misaligned16(d_instance))
-    return hm_fail(HM_ERR_BAD_ARG, "hm_poseidon_witness_bn256_dev: a device pointer is not 16-byte aligned");
+  const char* who = "hm_poseidon_witness_bn256_dev";
+  if (!d_msgs || !d_advice || !d_instance) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (int rc = witness_aligned(who, {d_msgs, d_advice, d_instance}, nullptr)) return rc;
   DeviceCtx* ctx = ctx_for_current_device();
   if (!ctx) return HM_ERR_NO_DEVICE;
   std::lock_guard<std::mutex> lk(ctx->mu);
   PoseidonSpec* s = nullptr;
   uint32_t n_advice = 0;
-  if (int rc = pow5_witness_args("hm_poseidon_witness_bn256_dev", *ctx, handle, false, 0, log_n, m, false, &s, &n_advice)) return rc;
+  if (int rc = witness_args(who, *ctx, handle, 0, 0, log_n, m, false, &s, &n_advice)) return rc;
   return poseidon_witness_run(*s, log_n, m, (const uint32_t*)d_msgs, (uint32_t*)d_advice, (uint32_t*)d_instance, (hipStream_t)stream);
 } HM_API_CATCH("hm_poseidon_witness_bn256_dev")
 
-// The two host forms: inputs (`in_count` arrays, each padded to 64 bytes in the staging buffer), columns and instance share one
+// The host forms: inputs (`in_count` arrays, each padded to 64 bytes in the staging buffer), columns and instance share one
 // staging buffer; `launch` gets the device addresses of the inputs, the columns and the instance.
-using Pow5Launch = std::function<int(const uint8_t* const*, uint32_t*, uint32_t*)>;
-static int pow5_witness_host(const char* who, DeviceCtx& ctx, uint32_t n_advice, uint32_t log_n, size_t m, const void* const* in,
-                             const size_t* in_bytes, size_t in_count, size_t inst_bytes, uint64_t* advice, uint64_t* instance,
-                             const Pow5Launch& launch) {
+using WitnessLaunch = std::function<int(const uint8_t* const*, uint32_t*, uint32_t*)>;
+static int witness_host(const char* who, DeviceCtx& ctx, uint32_t n_advice, uint32_t log_n, size_t m, const void* const* in,
+                        const size_t* in_bytes, size_t in_count, size_t inst_bytes, uint64_t* advice, uint64_t* instance,
+                        const WitnessLaunch& launch) {
   const std::string w(who);
   const size_t col_bytes = (size_t)32 << log_n;
   if (m > WITNESS_HOST_MAX_BYTES / ((size_t)n_advice * col_bytes))
@@ -2579,22 +2516,37 @@ static int pow5_witness_host(const char* who, DeviceCtx& ctx, uint32_t n_advice,
   return HM_OK;
 }
 
-int hm_merkle_witness_bn256(uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const uint64_t* leaves, const uint64_t* siblings,
-                            const uint64_t* indices, uint64_t* advice, uint64_t* instance) try {
-  if (!leaves || !siblings || !indices || !advice || !instance) return hm_fail(HM_ERR_BAD_ARG, "hm_merkle_witness_bn256: null argument");
+// the host forms of the two path circuits (never with a built tree)
+static int merkle_witness_host(const char* who, uint32_t E, uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const uint64_t* leaves,
+                               const uint64_t* siblings, const uint64_t* indices, const uint64_t* assets_sum, uint64_t* advice,
+                               uint64_t* instance) {
+  if (!leaves || !siblings || !indices || (E == 2 && !assets_sum) || !advice || !instance)
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
   DeviceCtx* ctx = ctx_for_current_device();
   if (!ctx) return HM_ERR_NO_DEVICE;
   std::lock_guard<std::mutex> lk(ctx->mu);
   PoseidonSpec* s = nullptr;
   uint32_t n_advice = 0;
-  if (int rc = pow5_witness_args("hm_merkle_witness_bn256", *ctx, handle, true, depth, log_n, m, false, &s, &n_advice)) return rc;
+  if (int rc = witness_args(who, *ctx, handle, E, depth, log_n, m, false, &s, &n_advice)) return rc;
+  if (m == 0) return HM_OK;
   const void* in[3] = {leaves, siblings, indices};
-  const size_t in_bytes[3] = {m * 32, m * depth * 32, m * 8};
-  return pow5_witness_host("hm_merkle_witness_bn256", *ctx, n_advice, log_n, m, in, in_bytes, 3, m * 64, advice, instance,
-                           [&](const uint8_t* const* d_in, uint32_t* d_adv, uint32_t* d_inst) {
-                             return merkle_witness_run(*s, depth, log_n, m, (const uint32_t*)d_in[0], (const uint32_t*)d_in[1],
-                                                       (const uint64_t*)d_in[2], nullptr, d_adv, d_inst, nullptr);
-                           });
+  const size_t in_bytes[3] = {m * E * 32, m * depth * E * 32, m * 8};
+  return witness_host(who, *ctx, n_advice, log_n, m, in, in_bytes, 3, m * (E == 2 ? 128 : 64), advice, instance,
+                      [&](const uint8_t* const* d_in, uint32_t* d_adv, uint32_t* d_inst) {
+                        return merkle_witness_run(E, *s, depth, log_n, m, (const uint32_t*)d_in[0], (const uint32_t*)d_in[1],
+                                                  (const uint64_t*)d_in[2], assets_sum, nullptr, d_adv, d_inst, nullptr);
+                      });
+}
+
+int hm_merkle_sum_witness_bn256(uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const uint64_t* leaves,
+                                const uint64_t* siblings, const uint64_t* indices, const uint64_t* assets_sum, uint64_t* advice,
+                                uint64_t* instance) try {
+  return merkle_witness_host("hm_merkle_sum_witness_bn256", 2, handle, depth, log_n, m, leaves, siblings, indices, assets_sum, advice, instance);
+} HM_API_CATCH("hm_merkle_sum_witness_bn256")
+
+int hm_merkle_witness_bn256(uint64_t handle, uint32_t depth, uint32_t log_n, size_t m, const uint64_t* leaves, const uint64_t* siblings,
+                            const uint64_t* indices, uint64_t* advice, uint64_t* instance) try {
+  return merkle_witness_host("hm_merkle_witness_bn256", 1, handle, depth, log_n, m, leaves, siblings, indices, nullptr, advice, instance);
 } HM_API_CATCH("hm_merkle_witness_bn256")
 
 int hm_poseidon_witness_bn256(uint64_t handle, uint32_t log_n, size_t m, const uint64_t* msgs, uint64_t* advice, uint64_t* instance) try {
@@ -2604,13 +2556,13 @@ int hm_poseidon_witness_bn256(uint64_t handle, uint32_t log_n, size_t m, const u
   std::lock_guard<std::mutex> lk(ctx->mu);
   PoseidonSpec* s = nullptr;
   uint32_t n_advice = 0;
-  if (int rc = pow5_witness_args("hm_poseidon_witness_bn256", *ctx, handle, false, 0, log_n, m, false, &s, &n_advice)) return rc;
+  if (int rc = witness_args("hm_poseidon_witness_bn256", *ctx, handle, 0, 0, log_n, m, false, &s, &n_advice)) return rc;
   const void* in[1] = {msgs};
   const size_t in_bytes[1] = {m * 128};
-  return pow5_witness_host("hm_poseidon_witness_bn256", *ctx, n_advice, log_n, m, in, in_bytes, 1, m * 32, advice, instance,
-                           [&](const uint8_t* const* d_in, uint32_t* d_adv, uint32_t* d_inst) {
-                             return poseidon_witness_run(*s, log_n, m, (const uint32_t*)d_in[0], d_adv, d_inst, nullptr);
-                           });
+  return witness_host("hm_poseidon_witness_bn256", *ctx, n_advice, log_n, m, in, in_bytes, 1, m * 32, advice, instance,
+                      [&](const uint8_t* const* d_in, uint32_t* d_adv, uint32_t* d_inst) {
+                        return poseidon_witness_run(*s, log_n, m, (const uint32_t*)d_in[0], d_adv, d_inst, nullptr);
+                      });
 } HM_API_CATCH("hm_poseidon_witness_bn256")
 
 #ifdef HM_FAULT_INJECTION

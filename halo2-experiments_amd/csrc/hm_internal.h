@@ -404,17 +404,14 @@ int poseidon_hash_run(const PoseidonSpec& s, const uint32_t* d_in, uint64_t in_s
 int merkle_build_run(const PoseidonSpec& s, uint32_t* d_nodes, uint32_t depth, hipStream_t stream);
 int merkle_paths_run(const uint32_t* d_nodes, uint32_t depth, uint32_t words_per_node, const uint64_t* d_indices, size_t m,
                      uint32_t* d_out, hipStream_t stream);
-// the MerkleSumTree witness (poseidon.inc): out = rows_used, n_advice, perm_rows, level_rows, lt_row, const_row
-void merkle_sum_witness_rows(uint32_t depth, uint32_t r_f, uint32_t r_p, uint32_t (&out)[6]);
-int merkle_sum_witness_run(const PoseidonSpec& s, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* d_leaves,
-                           const uint32_t* d_siblings, const uint64_t* d_indices, const uint64_t* assets_ext, const uint32_t* d_nodes,
-                           uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream);
-// the MerkleTreeV3 / Poseidon circuit witnesses (poseidon.inc): out = rows_used, n_advice, perm_rows, level_rows, const_row
-// (depth is ignored for the Poseidon circuit, whose level_rows counts every row before the constants)
-void merkle_witness_rows(uint32_t depth, uint32_t r_f, uint32_t r_p, uint32_t (&out)[5]);
-void poseidon_witness_rows(uint32_t r_f, uint32_t r_p, uint32_t (&out)[5]);
-int merkle_witness_run(const PoseidonSpec& s, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* d_leaves, const uint32_t* d_siblings,
-                       const uint64_t* d_indices, const uint32_t* d_nodes, uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream);
+// The witnesses of the three circuits (poseidon.inc).  E, the elements per node, selects the circuit: 2 MerkleSumTree, 1 MerkleTreeV3,
+// 0 the Poseidon circuit (depth is ignored; its level_rows counts every row before the constants).
+// out = rows_used, n_advice, perm_rows, level_rows, lt_row (E = 2 only), const_row
+void witness_rows(uint32_t E, uint32_t depth, uint32_t r_f, uint32_t r_p, uint32_t (&out)[6]);
+// E = 2 or 1; assets_ext is read for E = 2 only; d_nodes: the built tree, or null
+int merkle_witness_run(uint32_t E, const PoseidonSpec& s, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* d_leaves,
+                       const uint32_t* d_siblings, const uint64_t* d_indices, const uint64_t* assets_ext, const uint32_t* d_nodes,
+                       uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream);
 int poseidon_witness_run(const PoseidonSpec& s, uint32_t log_n, size_t m, const uint32_t* d_msgs, uint32_t* d_advice, uint32_t* d_instance,
                          hipStream_t stream);
 

@@ -523,51 +523,55 @@ int hc_poseidon(int op, uint32_t width, const uint32_t* consts, uint32_t r_f, ui
   return 0;
 }
 
-// The MerkleSumTree witness (poseidon.inc) of m users on host memory: the lane functions its two kernels run, lane by lane, so that
-// the limb bounds of the traced permutation and of the less-than arithmetic are proven on the code the GPU executes.
-// run: m x (depth - 1) x 16 words of scratch (used when nodes is null); advice must be cleared by the caller, as on the device.
+}  // extern "C"
+
+// The witnesses of the three circuits (poseidon.inc) of m users / messages on host memory: the lane functions their kernels run, lane
+// by lane, so that the limb bounds of the traced permutation and of the less-than arithmetic are proven on the code the GPU executes.
+// E = 2 MerkleSumTree, 1 MerkleTreeV3, 0 the Poseidon circuit.  advice must be cleared by the caller, as on the device.
+static int hc_witness_args(uint32_t E, const uint32_t* consts, uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, size_t m,
+                           const uint32_t* leaves, uint32_t* advice, uint32_t* instance, WitnessArgs& a) {
+  if ((E && (depth == 0 || depth > 32)) || (r_f & 1) || (r_p & 1)) return -1;
+  if (((uint64_t)1 << log_n) < (uint64_t)witness_layout(E, depth, r_f, r_p).rows_used + 6) return -1;
+  a = WitnessArgs{};
+  a.leaves = leaves, a.advice = advice, a.instance = instance, a.consts = consts;
+  a.m = m, a.depth = depth, a.log_n = log_n, a.r_f = r_f, a.r_p = r_p;
+  return 0;
+}
+template <int E>
+static void hc_merkle_lanes(WitnessArgs& a, const uint32_t* siblings, const uint64_t* indices, const uint32_t* nodes, uint32_t* run) {
+  a.siblings = siblings, a.indices = indices, a.nodes = nodes, a.run = nodes ? nullptr : run;
+  for (size_t u = 0; u < a.m; ++u) {
+    if (!nodes) merkle_chain_lane<E>(a, u, run);
+    for (uint32_t l = 0; l < a.depth; ++l) merkle_witness_lane<E>(a, u, l);
+  }
+}
+
+extern "C" {
+// run: m x (depth - 1) x 16 words of scratch (used when nodes is null)
 int hc_merkle_sum_witness(const uint32_t* consts, uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* leaves,
                           const uint32_t* siblings, const uint64_t* indices, const uint32_t* assets, const uint32_t* nodes, uint32_t* run,
                           uint32_t* advice, uint32_t* instance) {
-  if (depth == 0 || depth > 32 || (r_f & 1) || (r_p & 1)) return -1;
-  if (((uint64_t)1 << log_n) < (uint64_t)merkle_sum_witness_layout(depth, r_f, r_p).rows_used + 6) return -1;
   WitnessArgs a;
-  a.leaves = leaves, a.siblings = siblings, a.indices = indices, a.nodes = nodes, a.run = nodes ? nullptr : run;
-  a.advice = advice, a.instance = instance, a.consts = consts;
-  a.m = m, a.depth = depth, a.log_n = log_n, a.r_f = r_f, a.r_p = r_p;
+  if (int rc = hc_witness_args(2, consts, r_f, r_p, depth, log_n, m, leaves, advice, instance, a)) return rc;
   std::memcpy(a.assets, assets, 32);
-  for (size_t u = 0; u < m; ++u) {
-    if (!nodes) merkle_sum_chain_lane(a, u, run);
-    for (uint32_t l = 0; l < depth; ++l) merkle_sum_witness_lane(a, u, l);
-  }
+  hc_merkle_lanes<2>(a, siblings, indices, nodes, run);
   return 0;
 }
 
-// The MerkleTreeV3 witness of m users and the Poseidon circuit's witness of m messages on host memory, lane by lane like the above.
-// run: m x (depth - 1) x 8 words of scratch (used when nodes is null); advice must be cleared by the caller.
+// run: m x (depth - 1) x 8 words of scratch (used when nodes is null)
 int hc_merkle_witness(const uint32_t* consts, uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* leaves,
                       const uint32_t* siblings, const uint64_t* indices, const uint32_t* nodes, uint32_t* run, uint32_t* advice,
                       uint32_t* instance) {
-  if (depth == 0 || depth > 32 || (r_f & 1) || (r_p & 1)) return -1;
-  if (((uint64_t)1 << log_n) < (uint64_t)merkle_witness_layout(depth, r_f, r_p).rows_used + 6) return -1;
-  MerkleWitnessArgs a;
-  a.leaves = leaves, a.siblings = siblings, a.indices = indices, a.nodes = nodes, a.run = nodes ? nullptr : run;
-  a.advice = advice, a.instance = instance, a.consts = consts;
-  a.m = m, a.depth = depth, a.log_n = log_n, a.r_f = r_f, a.r_p = r_p;
-  for (size_t u = 0; u < m; ++u) {
-    if (!nodes) merkle_chain_lane(a, u, run);
-    for (uint32_t l = 0; l < depth; ++l) merkle_witness_lane(a, u, l);
-  }
+  WitnessArgs a;
+  if (int rc = hc_witness_args(1, consts, r_f, r_p, depth, log_n, m, leaves, advice, instance, a)) return rc;
+  hc_merkle_lanes<1>(a, siblings, indices, nodes, run);
   return 0;
 }
 
 int hc_poseidon_witness(const uint32_t* consts, uint32_t r_f, uint32_t r_p, uint32_t log_n, size_t m, const uint32_t* msgs, uint32_t* advice,
                         uint32_t* instance) {
-  if ((r_f & 1) || (r_p & 1)) return -1;
-  if (((uint64_t)1 << log_n) < (uint64_t)poseidon_witness_layout(r_f, r_p).rows_used + 6) return -1;
-  PoseidonWitnessArgs a;
-  a.msgs = msgs, a.advice = advice, a.instance = instance, a.consts = consts;
-  a.m = m, a.log_n = log_n, a.r_f = r_f, a.r_p = r_p;
+  WitnessArgs a;
+  if (int rc = hc_witness_args(0, consts, r_f, r_p, 0, log_n, m, msgs, advice, instance, a)) return rc;
   for (size_t u = 0; u < m; ++u) poseidon_witness_lane(a, u);
   return 0;
 }

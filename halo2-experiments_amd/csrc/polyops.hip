@@ -736,78 +736,49 @@ int merkle_paths_run(const uint32_t* d_nodes, uint32_t depth, uint32_t words_per
   return HM_OK;
 }
 
-void merkle_sum_witness_rows(uint32_t depth, uint32_t r_f, uint32_t r_p, uint32_t (&out)[6]) {
-  const WitnessLayout w = merkle_sum_witness_layout(depth, r_f, r_p);
-  out[0] = w.rows_used, out[1] = WITNESS_ADVICE, out[2] = w.perm_rows, out[3] = w.level_rows, out[4] = w.lt_row, out[5] = w.const_row;
+// out = rows_used, n_advice, perm_rows, level_rows, lt_row, const_row
+void witness_rows(uint32_t E, uint32_t depth, uint32_t r_f, uint32_t r_p, uint32_t (&out)[6]) {
+  const WitnessLayout w = witness_layout(E, depth, r_f, r_p);
+  out[0] = w.rows_used, out[1] = witness_advice(E), out[2] = w.perm_rows, out[3] = w.level_rows, out[4] = w.lt_row, out[5] = w.const_row;
+}
+
+static WitnessArgs witness_args(const PoseidonSpec& s, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* d_leaves,
+                                uint32_t* d_advice, uint32_t* d_instance) {
+  WitnessArgs a{};
+  a.leaves = d_leaves, a.advice = d_advice, a.instance = d_instance, a.consts = s.d_consts;
+  a.m = m, a.depth = depth, a.log_n = log_n, a.r_f = s.r_f, a.r_p = s.r_p;
+  return a;
 }
 
 // The columns are cleared, then every (user, level) lane writes its cells; without a tree a chain launch (one lane per user,
 // depth - 1 hashes in sequence) first leaves the path's running nodes in stream-ordered scratch.
-int merkle_sum_witness_run(const PoseidonSpec& s, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* d_leaves,
-                           const uint32_t* d_siblings, const uint64_t* d_indices, const uint64_t* assets_ext, const uint32_t* d_nodes,
-                           uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream) {
+int merkle_witness_run(uint32_t E, const PoseidonSpec& s, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* d_leaves,
+                       const uint32_t* d_siblings, const uint64_t* d_indices, const uint64_t* assets_ext, const uint32_t* d_nodes,
+                       uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream) {
   if (m == 0) return HM_OK;
-  WitnessArgs a;
-  a.leaves = d_leaves, a.siblings = d_siblings, a.indices = d_indices, a.nodes = d_nodes, a.run = nullptr;
-  a.advice = d_advice, a.instance = d_instance, a.consts = s.d_consts;
-  a.m = m, a.depth = depth, a.log_n = log_n, a.r_f = s.r_f, a.r_p = s.r_p;
-  std::memcpy(a.assets, assets_ext, 32);
-  HM_HIP_CHECK(hipMemsetAsync(d_advice, 0, (size_t)m * WITNESS_ADVICE * ((size_t)32 << log_n), stream));
+  const std::string who = E == 2 ? "merkle_sum_witness: " : "merkle_witness: ";
+  WitnessArgs a = witness_args(s, depth, log_n, m, d_leaves, d_advice, d_instance);
+  a.siblings = d_siblings, a.indices = d_indices, a.nodes = d_nodes;
+  if (E == 2) std::memcpy(a.assets, assets_ext, 32);
+  HM_HIP_CHECK(hipMemsetAsync(d_advice, 0, (size_t)m * witness_advice(E) * ((size_t)32 << log_n), stream));
   void* run = nullptr;
   int rc = HM_OK;
   if (!d_nodes && depth > 1) {
-    HM_HIP_CHECK(hipMallocAsync(&run, (size_t)m * (depth - 1) * 64, stream));
+    HM_HIP_CHECK(hipMallocAsync(&run, (size_t)m * (depth - 1) * E * 32, stream));
     a.run = (const uint32_t*)run;
-    hipLaunchKernelGGL(merkle_sum_chain_kernel, dim3((unsigned)((m + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, stream, a,
-                       (uint32_t*)run);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("merkle_sum_witness: ") + hipGetErrorString(e));
+    hipLaunchKernelGGL(E == 2 ? merkle_chain_kernel<2> : merkle_chain_kernel<1>, dim3((unsigned)((m + PS_THREADS - 1) / PS_THREADS)),
+                       dim3(PS_THREADS), 0, stream, a, (uint32_t*)run);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, who + hipGetErrorString(e));
   }
   if (rc == HM_OK) {
     const uint64_t lanes = (uint64_t)m * depth;
-    hipLaunchKernelGGL(merkle_sum_witness_kernel, dim3((unsigned)((lanes + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, stream, a);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("merkle_sum_witness: ") + hipGetErrorString(e));
+    hipLaunchKernelGGL(E == 2 ? merkle_witness_kernel<2> : merkle_witness_kernel<1>, dim3((unsigned)((lanes + PS_THREADS - 1) / PS_THREADS)),
+                       dim3(PS_THREADS), 0, stream, a);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, who + hipGetErrorString(e));
   }
   if (run) {
     const hipError_t fe = hipFreeAsync(run, stream);
-    if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("merkle_sum_witness: hipFreeAsync: ") + hipGetErrorString(fe));
-  }
-  return rc;
-}
-
-void merkle_witness_rows(uint32_t depth, uint32_t r_f, uint32_t r_p, uint32_t (&out)[5]) {
-  const Pow5Layout w = merkle_witness_layout(depth, r_f, r_p);
-  out[0] = w.rows_used, out[1] = MERKLE_WITNESS_ADVICE, out[2] = w.perm_rows, out[3] = w.level_rows, out[4] = w.const_row;
-}
-void poseidon_witness_rows(uint32_t r_f, uint32_t r_p, uint32_t (&out)[5]) {
-  const Pow5Layout w = poseidon_witness_layout(r_f, r_p);
-  out[0] = w.rows_used, out[1] = POSEIDON_WITNESS_ADVICE, out[2] = w.perm_rows, out[3] = w.level_rows, out[4] = w.const_row;
-}
-
-// merkle_sum_witness_run for the plain tree of merkle_v3: clear, (chain,) one lane per (user, level)
-int merkle_witness_run(const PoseidonSpec& s, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* d_leaves, const uint32_t* d_siblings,
-                       const uint64_t* d_indices, const uint32_t* d_nodes, uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream) {
-  if (m == 0) return HM_OK;
-  MerkleWitnessArgs a;
-  a.leaves = d_leaves, a.siblings = d_siblings, a.indices = d_indices, a.nodes = d_nodes, a.run = nullptr;
-  a.advice = d_advice, a.instance = d_instance, a.consts = s.d_consts;
-  a.m = m, a.depth = depth, a.log_n = log_n, a.r_f = s.r_f, a.r_p = s.r_p;
-  HM_HIP_CHECK(hipMemsetAsync(d_advice, 0, (size_t)m * MERKLE_WITNESS_ADVICE * ((size_t)32 << log_n), stream));
-  void* run = nullptr;
-  int rc = HM_OK;
-  if (!d_nodes && depth > 1) {
-    HM_HIP_CHECK(hipMallocAsync(&run, (size_t)m * (depth - 1) * 32, stream));
-    a.run = (const uint32_t*)run;
-    hipLaunchKernelGGL(merkle_chain_kernel, dim3((unsigned)((m + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, stream, a, (uint32_t*)run);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("merkle_witness: ") + hipGetErrorString(e));
-  }
-  if (rc == HM_OK) {
-    const uint64_t lanes = (uint64_t)m * depth;
-    hipLaunchKernelGGL(merkle_witness_kernel, dim3((unsigned)((lanes + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, stream, a);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("merkle_witness: ") + hipGetErrorString(e));
-  }
-  if (run) {
-    const hipError_t fe = hipFreeAsync(run, stream);
-    if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("merkle_witness: hipFreeAsync: ") + hipGetErrorString(fe));
+    if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, who + "hipFreeAsync: " + hipGetErrorString(fe));
   }
   return rc;
 }
@@ -815,10 +786,8 @@ int merkle_witness_run(const PoseidonSpec& s, uint32_t depth, uint32_t log_n, si
 int poseidon_witness_run(const PoseidonSpec& s, uint32_t log_n, size_t m, const uint32_t* d_msgs, uint32_t* d_advice, uint32_t* d_instance,
                          hipStream_t stream) {
   if (m == 0) return HM_OK;
-  PoseidonWitnessArgs a;
-  a.msgs = d_msgs, a.advice = d_advice, a.instance = d_instance, a.consts = s.d_consts;
-  a.m = m, a.log_n = log_n, a.r_f = s.r_f, a.r_p = s.r_p;
-  HM_HIP_CHECK(hipMemsetAsync(d_advice, 0, (size_t)m * POSEIDON_WITNESS_ADVICE * ((size_t)32 << log_n), stream));
+  const WitnessArgs a = witness_args(s, 0, log_n, m, d_msgs, d_advice, d_instance);
+  HM_HIP_CHECK(hipMemsetAsync(d_advice, 0, (size_t)m * witness_advice(0) * ((size_t)32 << log_n), stream));
   hipLaunchKernelGGL(poseidon_witness_kernel, dim3((unsigned)((m + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, stream, a);
   HM_HIP_CHECK(hipGetLastError());
   return HM_OK;

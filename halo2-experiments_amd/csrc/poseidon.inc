@@ -166,29 +166,35 @@ HM_HD void merkle_sum_node_one(const uint32_t (&kids)[4][8], const uint32_t* c, 
   poseidon_hash_one<5>(kids, c, r_f, r_p, hash);
 }
 
-// ---- the MerkleSumTree circuit's witness (DESIGN.md section 13) -----------------------------------------------------------------
-// The advice columns of circuits.merkle_sum_tree() for one inclusion path, filled as the reference's chip assigns them
-// (/root/reference/src/chips/merkle_sum_tree.rs:140-352; the Pow5 and Lt chips as recalled in synthesis.py).  One lane per
-// (user, level): it writes the level's "merkle prove layer" rows, the hash's initial-state and pad-and-add rows and, through the
-// sink of poseidon_permute, the trace of the permutation; the lane of level 0 adds the leaf rows, the lane of the last level the
-// less-than region and the root.  Cells the chip leaves unassigned are zero: the caller clears the columns first.
+// ---- the witnesses of the three circuits (DESIGN.md section 13) -----------------------------------------------------------------
+// The advice columns of circuits.merkle_sum_tree(), circuits.merkle_v3() and circuits.poseidon(), filled as the reference's chips
+// assign them (/root/reference/src/chips/merkle_sum_tree.rs:140-352, src/chips/merkle_v3.rs:84-172,
+// src/chips/poseidon/hash_with_instance.rs:78-148; the Pow5 and Lt chips as recalled in synthesis.py).  The rows of one hash are
+// written in ONE place, pow5_hash_rows; the two path circuits are one lane function over E, the elements per node (2: the sum tree's
+// (hash, balance), W = 5; 1: MerkleTreeV3, W = 3), one lane per (user, level); the Poseidon circuit is one lane per hash.
+// Cells the chips leave unassigned are zero: the caller clears the columns first.
 //
-// Row placement (synthesis.MerkleSumTreeLayout restates it; tests compare the two for every depth):
-//     row 0 leaf hash, row 1 leaf balance; level l at 2 + l * level_rows: prove layer (2 rows), initial state (1), pad-and-add (3),
-//     permute state (perm_rows = r_f + r_p / 2 + 1); then the less-than row; then 5 constants per level in rc_b[0] (fixed only).
-constexpr uint32_t WITNESS_ADVICE = 20;      // a b c d e | state[5] | partial_sbox | lt | diff[8]
+// Row placement (synthesis.py's layouts restate it; tests compare the two for every depth), with hash = initial state (1 row),
+// pad-and-add (3), permute state (perm_rows = r_f + r_p / 2 + 1):
+//     path circuits: leaf element e in column e, row e; level l at E + l * level_rows: prove layer (2 rows), hash; E = 2 only: the
+//                    less-than row; then W constants per level in rc_b[0] (fixed only).
+//     poseidon:      row 0 the private inputs, row 1 their copies, hash; then 5 constants.
+// Columns: a b c d e | state[5] | partial_sbox | lt | diff[8] (E = 2), a b c | state[3] | partial_sbox (E = 1), state[5] | partial_sbox
 constexpr uint32_t WITNESS_U8_ROWS = 256;    // the LtChip's range table occupies rows 0..255 of its own fixed column
+HM_HD constexpr uint32_t witness_advice(uint32_t E) { return E == 2 ? 20u : E == 1 ? 7u : 6u; }
 struct WitnessLayout {
-  uint32_t perm_rows, level_rows, lt_row, const_row, rows_used;
+  uint32_t perm_rows, level_rows, lt_row, const_row, rows_used;      // lt_row: E = 2 only
 };
-HM_HD WitnessLayout merkle_sum_witness_layout(uint32_t depth, uint32_t r_f, uint32_t r_p) {
+// E = 0: the Poseidon circuit (depth is ignored; level_rows counts every row before the constants)
+HM_HD WitnessLayout witness_layout(uint32_t E, uint32_t depth, uint32_t r_f, uint32_t r_p) {
+  const uint32_t levels = E ? depth : 1u, W = E ? 2 * E + 1 : 5u;
   WitnessLayout w;
   w.perm_rows = r_f + r_p / 2 + 1;
   w.level_rows = 2 + 1 + 3 + w.perm_rows;
-  w.lt_row = 2 + depth * w.level_rows;
-  w.const_row = w.lt_row + 1;
-  w.rows_used = w.const_row + 5 * depth;
-  if (w.rows_used < WITNESS_U8_ROWS) w.rows_used = WITNESS_U8_ROWS;
+  w.lt_row = E + levels * w.level_rows;
+  w.const_row = w.lt_row + (E == 2 ? 1u : 0u);
+  w.rows_used = w.const_row + W * levels;
+  if (E == 2 && w.rows_used < WITNESS_U8_ROWS) w.rows_used = WITNESS_U8_ROWS;
   return w;
 }
 
@@ -285,17 +291,17 @@ HM_HD void lt_chip_values(const uint32_t (&lhs)[8], const uint32_t (&rhs)[8], ui
 }
 
 struct WitnessArgs {
-  const uint32_t* leaves;        // m x 16 words: hash, balance
-  const uint32_t* siblings;      // m x depth x 16
+  const uint32_t* leaves;        // m x E x 8 words (E = 2: hash, balance); the Poseidon circuit: the messages, m x 4 x 8
+  const uint32_t* siblings;      // m x depth x E x 8
   const uint64_t* indices;       // m: bit l = the path's node is the right child at level l
-  const uint32_t* nodes;         // the built tree (2^(depth+1) - 1 nodes of 16 words), or null
-  const uint32_t* run;           // without a tree: m x (depth - 1) x 16, the path's node after levels 1 .. depth - 1 (merkle_sum_chain_lane)
-  uint32_t* advice;              // m x WITNESS_ADVICE x 2^log_n x 8, cleared
-  uint32_t* instance;            // m x 4 x 8: leaf hash, leaf balance, root, assets
+  const uint32_t* nodes;         // the built tree (2^(depth+1) - 1 nodes of E x 8 words), or null
+  const uint32_t* run;           // without a tree: m x (depth - 1) x E x 8, the path's node after levels 1 .. depth - 1 (merkle_chain_lane)
+  uint32_t* advice;              // m x witness_advice(E) x 2^log_n x 8, cleared
+  uint32_t* instance;            // m x rows x 8: E = 2 leaf hash, leaf balance, root, assets; E = 1 leaf, root; poseidon the digest
   const uint32_t* consts;
   uint64_t m;
   uint32_t depth, log_n, r_f, r_p;
-  uint32_t assets[8];
+  uint32_t assets[8];            // E = 2 only
 };
 
 // the rows of "permute state" into the columns state[0..W-1] and partial_sbox (the column after them) of one hash
@@ -319,272 +325,151 @@ struct WitnessSink {
   }
 };
 
+// The Pow5 chip's rows of one hash of `msg`; state0: word 0 of column state[0] at the "initial state" row.  The capacity word on
+// rows 0 ("initial state"), 1 and 3 (pad-and-add rows 0 and 2; the rate words of the initial state are zero), the message on rows
+// 2 and 3 (the message row and the output row), the trace of the permutation from row 4.  Leaves the final state in s.
+template <int W>
+HM_HD void pow5_hash_rows(uint32_t* state0, uint64_t col_words, const uint32_t (&msg)[W - 1][8], const uint32_t* consts, uint32_t r_f,
+                          uint32_t r_p, Fr (&s)[W]) {
+#pragma unroll
+  for (int j = 0; j < W - 1; ++j) {
+    ps_put_words(state0 + j * col_words + 2 * 8, msg[j]);
+    ps_put_words(state0 + j * col_words + 3 * 8, msg[j]);
+  }
+  const uint32_t* cap = consts + ((size_t)(r_f + r_p) * W + (size_t)W * W) * 9;
+  uint32_t w[8];
+  fe_to_ext_shift(w, ps_load9(cap));
+  ps_put_words(state0 + (W - 1) * col_words + 0 * 8, w);
+  ps_put_words(state0 + (W - 1) * col_words + 1 * 8, w);
+  ps_put_words(state0 + (W - 1) * col_words + 3 * 8, w);
+#pragma unroll
+  for (int j = 0; j < W - 1; ++j) s[j] = fe_from_ext<FrParams>(msg[j]);
+  s[W - 1] = ps_load9(cap);
+  poseidon_permute<W>(s, consts, r_f, r_p, WitnessSink{state0 + 4 * 8, col_words});
+}
+
 // the path's node after level l + 1, for l = 0 .. depth - 2, of user u: the chain that a built tree makes unnecessary
-HM_HD void merkle_sum_chain_lane(const WitnessArgs& a, uint64_t u, uint32_t* run) {
-  uint32_t node[2][8];
-  ps_get_words(a.leaves + u * 16, node[0]);
-  ps_get_words(a.leaves + u * 16 + 8, node[1]);
+template <int E>
+HM_HD void merkle_chain_lane(const WitnessArgs& a, uint64_t u, uint32_t* run) {
+  uint32_t node[E][8];
+#pragma unroll
+  for (int e = 0; e < E; ++e) ps_get_words(a.leaves + (u * E + e) * 8, node[e]);
   const uint64_t idx = a.indices[u];
 #pragma unroll 1
   for (uint32_t l = 0; l + 1 < a.depth; ++l) {
-    uint32_t sib[2][8], kids[4][8];
-    ps_get_words(a.siblings + (u * a.depth + l) * 16, sib[0]);
-    ps_get_words(a.siblings + (u * a.depth + l) * 16 + 8, sib[1]);
+    uint32_t sib[E][8], kids[2 * E][8];
     const bool right = (idx >> l) & 1ull;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      kids[0][i] = right ? sib[0][i] : node[0][i];
-      kids[1][i] = right ? sib[1][i] : node[1][i];
-      kids[2][i] = right ? node[0][i] : sib[0][i];
-      kids[3][i] = right ? node[1][i] : sib[1][i];
+    for (int e = 0; e < E; ++e) {
+      ps_get_words(a.siblings + ((u * a.depth + l) * E + e) * 8, sib[e]);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        kids[e][i] = right ? sib[e][i] : node[e][i];
+        kids[E + e][i] = right ? node[e][i] : sib[e][i];
+      }
     }
-    merkle_sum_node_one(kids, a.consts, a.r_f, a.r_p, node[0], node[1]);
-    ps_put_words(run + (u * (a.depth - 1) + l) * 16, node[0]);
-    ps_put_words(run + (u * (a.depth - 1) + l) * 16 + 8, node[1]);
+    if constexpr (E == 2)
+      merkle_sum_node_one(kids, a.consts, a.r_f, a.r_p, node[0], node[1]);
+    else
+      poseidon_hash_one<3>(kids, a.consts, a.r_f, a.r_p, node[0]);
+#pragma unroll
+    for (int e = 0; e < E; ++e) ps_put_words(run + ((u * (a.depth - 1) + l) * E + e) * 8, node[e]);
   }
 }
 
-// everything level l of user u contributes to the witness (see the head of this section)
-HM_HD void merkle_sum_witness_lane(const WitnessArgs& a, uint64_t u, uint32_t l) {
-  const WitnessLayout lay = merkle_sum_witness_layout(a.depth, a.r_f, a.r_p);
+// "enforce sum to be less than total assets" at row0 = word 0 of column a at the less-than row: a = the sum, b = the assets,
+// c = check = 1, LtChip (lt in column 11, the bytes of diff in 12 .. 19)
+HM_HD void merkle_sum_lt_row(uint32_t* row0, uint64_t col_words, const uint32_t (&sum)[8], const uint32_t (&assets)[8]) {
+  uint32_t si[8], ai[8], w[8], lt;
+  uint64_t diff;
+  ps_put_words(row0 + 0 * col_words, sum);
+  ps_put_words(row0 + 1 * col_words, assets);
+  fr_ext_to_int(sum, si);
+  fr_ext_to_int(assets, ai);
+  lt_chip_values(si, ai, lt, diff);
+  fr_small_to_ext(1u, w);
+  ps_put_words(row0 + 2 * col_words, w);
+  fr_small_to_ext(lt, w);
+  ps_put_words(row0 + 11 * col_words, w);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    fr_small_to_ext((uint32_t)(diff >> (8 * i)) & 0xffu, w);
+    ps_put_words(row0 + (12 + i) * col_words, w);
+  }
+}
+
+// everything level l of user u contributes to the witness of a path circuit: the level's "merkle prove layer" rows and its hash;
+// the lane of level 0 adds the leaf rows, the lane of the last level the root (and, E = 2, the less-than region and the assets)
+template <int E>
+HM_HD void merkle_witness_lane(const WitnessArgs& a, uint64_t u, uint32_t l) {
+  constexpr int W = 2 * E + 1;
+  const WitnessLayout lay = witness_layout(E, a.depth, a.r_f, a.r_p);
   const uint64_t col_words = (uint64_t)8 << a.log_n;
-  uint32_t* adv = a.advice + u * WITNESS_ADVICE * col_words;
-  const uint64_t base = 2 + (uint64_t)l * lay.level_rows;
-  const uint64_t idx = a.indices[u] & ((a.depth >= 64 ? 0 : (1ull << a.depth)) - 1);
-  const bool right = (idx >> l) & 1ull;
-
-  uint32_t kids[4][8], sum[8], w[8];
-  {
-    uint32_t prev[2][8], sib[2][8];
-    const uint32_t* p = l == 0 ? a.leaves + u * 16
-                        : a.nodes ? a.nodes + (((2ull << a.depth) - (2ull << (a.depth - l))) + (idx >> l)) * 16
-                                  : a.run + (u * (a.depth - 1) + (l - 1)) * 16;
-    ps_get_words(p, prev[0]);
-    ps_get_words(p + 8, prev[1]);
-    ps_get_words(a.siblings + (u * a.depth + l) * 16, sib[0]);
-    ps_get_words(a.siblings + (u * a.depth + l) * 16 + 8, sib[1]);
-    if (l == 0) {                                          // "assign leaf hash", "assign leaf balance"; instance rows 0, 1
-      ps_put_words(adv + 0 * col_words + 0 * 8, prev[0]);
-      ps_put_words(adv + 1 * col_words + 1 * 8, prev[1]);
-      ps_put_words(a.instance + u * 32, prev[0]);
-      ps_put_words(a.instance + u * 32 + 8, prev[1]);
-    }
-    // "merkle prove layer" row 0: previous node, sibling, index
-    ps_put_words(adv + 0 * col_words + base * 8, prev[0]);
-    ps_put_words(adv + 1 * col_words + base * 8, prev[1]);
-    ps_put_words(adv + 2 * col_words + base * 8, sib[0]);
-    ps_put_words(adv + 3 * col_words + base * 8, sib[1]);
-    fr_small_to_ext(right ? 1u : 0u, w);
-    ps_put_words(adv + 4 * col_words + base * 8, w);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      kids[0][i] = right ? sib[0][i] : prev[0][i];
-      kids[1][i] = right ? sib[1][i] : prev[1][i];
-      kids[2][i] = right ? prev[0][i] : sib[0][i];
-      kids[3][i] = right ? prev[1][i] : sib[1][i];
-    }
-  }
-  fr_add_ext(kids[1], kids[3], sum);
-  // row 1: left, right, their sum; the hash's input row and the pad-and-add output row repeat the four words
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    ps_put_words(adv + j * col_words + (base + 1) * 8, kids[j]);
-    ps_put_words(adv + (5 + j) * col_words + (base + 4) * 8, kids[j]);
-    ps_put_words(adv + (5 + j) * col_words + (base + 5) * 8, kids[j]);
-  }
-  ps_put_words(adv + 4 * col_words + (base + 1) * 8, sum);
-  // the capacity word: "initial state", pad-and-add rows 0 and 2 (the four rate words of the initial state are zero)
-  fe_to_ext_shift(w, ps_load9(a.consts + ((size_t)(a.r_f + a.r_p) * 5 + 25) * 9));
-  ps_put_words(adv + 9 * col_words + (base + 2) * 8, w);
-  ps_put_words(adv + 9 * col_words + (base + 3) * 8, w);
-  ps_put_words(adv + 9 * col_words + (base + 5) * 8, w);
-
-  if (l + 1 == a.depth) {          // "enforce sum to be less than total assets": a = the sum, b = the assets, c = check = 1, LtChip
-    const uint64_t row = lay.lt_row;
-    uint32_t si[8], ai[8], lt;
-    uint64_t diff;
-    ps_put_words(adv + 0 * col_words + row * 8, sum);
-    ps_put_words(adv + 1 * col_words + row * 8, a.assets);
-    ps_put_words(a.instance + u * 32 + 24, a.assets);
-    fr_ext_to_int(sum, si);
-    fr_ext_to_int(a.assets, ai);
-    lt_chip_values(si, ai, lt, diff);
-    fr_small_to_ext(1u, w);
-    ps_put_words(adv + 2 * col_words + row * 8, w);
-    fr_small_to_ext(lt, w);
-    ps_put_words(adv + 11 * col_words + row * 8, w);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      fr_small_to_ext((uint32_t)(diff >> (8 * i)) & 0xffu, w);
-      ps_put_words(adv + (12 + i) * col_words + row * 8, w);
-    }
-  }
-
-  Fr s[5];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) s[j] = fe_from_ext<FrParams>(kids[j]);
-  s[4] = ps_load9(a.consts + ((size_t)(a.r_f + a.r_p) * 5 + 25) * 9);
-  const WitnessSink sink{adv + 5 * col_words + (base + 6) * 8, col_words};
-  poseidon_permute<5>(s, a.consts, a.r_f, a.r_p, sink);
-  if (l + 1 == a.depth) {                                  // the root: instance row 2
-    fe_to_ext_shift(w, s[0]);
-    ps_put_words(a.instance + u * 32 + 16, w);
-  }
-}
-
-// ---- the MerkleTreeV3 and Poseidon circuits' witnesses (DESIGN.md section 14) -------------------------------------------------------
-// The advice columns of circuits.merkle_v3() for one inclusion path (/root/reference/src/chips/merkle_v3.rs:84-172) and of
-// circuits.poseidon() for one hash (src/chips/poseidon/hash_with_instance.rs:78-148), with the Pow5 regions of the section above.
-// Row placement (synthesis.MerkleTreeV3Layout / PoseidonCircuitLayout restate it; tests compare the two):
-//     merkle_v3: row 0 the leaf; level l at 1 + l * level_rows: prove layer (2 rows), initial state (1), pad-and-add (3), permute
-//                state (perm_rows); then 3 constants per level in rc_b[0] (fixed only).
-//     poseidon:  row 0 the private inputs, row 1 their copies, initial state (1), pad-and-add (3), permute state; then 5 constants.
-constexpr uint32_t MERKLE_WITNESS_ADVICE = 7;        // a b c | state[3] | partial_sbox
-constexpr uint32_t POSEIDON_WITNESS_ADVICE = 6;      // state[5] | partial_sbox
-struct Pow5Layout {
-  uint32_t perm_rows, level_rows, const_row, rows_used;
-};
-HM_HD Pow5Layout merkle_witness_layout(uint32_t depth, uint32_t r_f, uint32_t r_p) {
-  Pow5Layout w;
-  w.perm_rows = r_f + r_p / 2 + 1;
-  w.level_rows = 2 + 1 + 3 + w.perm_rows;
-  w.const_row = 1 + depth * w.level_rows;
-  w.rows_used = w.const_row + 3 * depth;
-  return w;
-}
-HM_HD Pow5Layout poseidon_witness_layout(uint32_t r_f, uint32_t r_p) {      // level_rows: everything before the constants
-  Pow5Layout w;
-  w.perm_rows = r_f + r_p / 2 + 1;
-  w.level_rows = 1 + 1 + 1 + 3 + w.perm_rows;
-  w.const_row = w.level_rows;
-  w.rows_used = w.const_row + 5;
-  return w;
-}
-
-struct MerkleWitnessArgs {
-  const uint32_t* leaves;        // m x 8 words
-  const uint32_t* siblings;      // m x depth x 8
-  const uint64_t* indices;       // m: bit l = the path's node is the right child at level l
-  const uint32_t* nodes;         // the built tree (2^(depth+1) - 1 nodes of 8 words), or null
-  const uint32_t* run;           // without a tree: m x (depth - 1) x 8, the path's node after levels 1 .. depth - 1 (merkle_chain_lane)
-  uint32_t* advice;              // m x MERKLE_WITNESS_ADVICE x 2^log_n x 8, cleared
-  uint32_t* instance;            // m x 2 x 8: leaf, root
-  const uint32_t* consts;
-  uint64_t m;
-  uint32_t depth, log_n, r_f, r_p;
-};
-
-// the path's node after level l + 1, for l = 0 .. depth - 2, of user u
-HM_HD void merkle_chain_lane(const MerkleWitnessArgs& a, uint64_t u, uint32_t* run) {
-  uint32_t node[8];
-  ps_get_words(a.leaves + u * 8, node);
-  const uint64_t idx = a.indices[u];
-#pragma unroll 1
-  for (uint32_t l = 0; l + 1 < a.depth; ++l) {
-    uint32_t sib[8], kids[2][8];
-    ps_get_words(a.siblings + (u * a.depth + l) * 8, sib);
-    const bool right = (idx >> l) & 1ull;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      kids[0][i] = right ? sib[i] : node[i];
-      kids[1][i] = right ? node[i] : sib[i];
-    }
-    poseidon_hash_one<3>(kids, a.consts, a.r_f, a.r_p, node);
-    ps_put_words(run + (u * (a.depth - 1) + l) * 8, node);
-  }
-}
-
-// everything level l of user u contributes to the MerkleTreeV3 witness
-HM_HD void merkle_witness_lane(const MerkleWitnessArgs& a, uint64_t u, uint32_t l) {
-  const Pow5Layout lay = merkle_witness_layout(a.depth, a.r_f, a.r_p);
-  const uint64_t col_words = (uint64_t)8 << a.log_n;
-  uint32_t* adv = a.advice + u * MERKLE_WITNESS_ADVICE * col_words;
-  const uint64_t base = 1 + (uint64_t)l * lay.level_rows;
+  uint32_t* adv = a.advice + u * witness_advice(E) * col_words;
+  uint32_t* inst = a.instance + u * (E == 2 ? 4 : 2) * 8;
+  const uint64_t base = E + (uint64_t)l * lay.level_rows;
   const uint64_t idx = a.indices[u] & ((1ull << a.depth) - 1);          // depth <= 32
   const bool right = (idx >> l) & 1ull;
 
-  uint32_t kids[2][8], w[8];
+  uint32_t kids[2 * E][8], w[8];
   {
-    uint32_t prev[8], sib[8];
-    const uint32_t* p = l == 0 ? a.leaves + u * 8
-                        : a.nodes ? a.nodes + (((2ull << a.depth) - (2ull << (a.depth - l))) + (idx >> l)) * 8
-                                  : a.run + (u * (a.depth - 1) + (l - 1)) * 8;
-    ps_get_words(p, prev);
-    ps_get_words(a.siblings + (u * a.depth + l) * 8, sib);
-    if (l == 0) {                                          // "assign leaf"; instance row 0
-      ps_put_words(adv + 0 * col_words + 0 * 8, prev);
-      ps_put_words(a.instance + u * 16, prev);
+    uint32_t prev[E][8], sib[E][8];
+    const uint32_t* p = l == 0 ? a.leaves + u * E * 8
+                        : a.nodes ? a.nodes + (((2ull << a.depth) - (2ull << (a.depth - l))) + (idx >> l)) * E * 8
+                                  : a.run + (u * (a.depth - 1) + (l - 1)) * E * 8;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      ps_get_words(p + e * 8, prev[e]);
+      ps_get_words(a.siblings + ((u * a.depth + l) * E + e) * 8, sib[e]);
+      if (l == 0) {                                          // "assign leaf (hash, balance)"; instance rows 0 .. E - 1
+        ps_put_words(adv + e * col_words + e * 8, prev[e]);
+        ps_put_words(inst + e * 8, prev[e]);
+      }
+      // "merkle prove layer" row 0: previous node, sibling, index
+      ps_put_words(adv + e * col_words + base * 8, prev[e]);
+      ps_put_words(adv + (E + e) * col_words + base * 8, sib[e]);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        kids[e][i] = right ? sib[e][i] : prev[e][i];
+        kids[E + e][i] = right ? prev[e][i] : sib[e][i];
+      }
     }
-    // "merkle prove layer" row 0: previous node, path element, index
-    ps_put_words(adv + 0 * col_words + base * 8, prev);
-    ps_put_words(adv + 1 * col_words + base * 8, sib);
     fr_small_to_ext(right ? 1u : 0u, w);
-    ps_put_words(adv + 2 * col_words + base * 8, w);
+    ps_put_words(adv + 2 * E * col_words + base * 8, w);
+  }
+  // row 1: left, right (the hash's message)
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      kids[0][i] = right ? sib[i] : prev[i];
-      kids[1][i] = right ? prev[i] : sib[i];
+  for (int j = 0; j < 2 * E; ++j) ps_put_words(adv + j * col_words + (base + 1) * 8, kids[j]);
+  if constexpr (E == 2) {                                    // and the sum of their balances
+    uint32_t sum[8];
+    fr_add_ext(kids[1], kids[3], sum);
+    ps_put_words(adv + 4 * col_words + (base + 1) * 8, sum);
+    if (l + 1 == a.depth) {
+      merkle_sum_lt_row(adv + (uint64_t)lay.lt_row * 8, col_words, sum, a.assets);
+      ps_put_words(inst + 24, a.assets);
     }
   }
-  // row 1: left, right; the hash's input row and the pad-and-add output row repeat the two words
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    ps_put_words(adv + j * col_words + (base + 1) * 8, kids[j]);
-    ps_put_words(adv + (3 + j) * col_words + (base + 4) * 8, kids[j]);
-    ps_put_words(adv + (3 + j) * col_words + (base + 5) * 8, kids[j]);
-  }
-  // the capacity word: "initial state", pad-and-add rows 0 and 2 (the two rate words of the initial state are zero)
-  const uint32_t* cap = a.consts + ((size_t)(a.r_f + a.r_p) * 3 + 9) * 9;
-  fe_to_ext_shift(w, ps_load9(cap));
-  ps_put_words(adv + 5 * col_words + (base + 2) * 8, w);
-  ps_put_words(adv + 5 * col_words + (base + 3) * 8, w);
-  ps_put_words(adv + 5 * col_words + (base + 5) * 8, w);
-
-  Fr s[3];
-  s[0] = fe_from_ext<FrParams>(kids[0]);
-  s[1] = fe_from_ext<FrParams>(kids[1]);
-  s[2] = ps_load9(cap);
-  const WitnessSink sink{adv + 3 * col_words + (base + 6) * 8, col_words};
-  poseidon_permute<3>(s, a.consts, a.r_f, a.r_p, sink);
-  if (l + 1 == a.depth) {                                  // the root: instance row 1
+  Fr s[W];
+  pow5_hash_rows<W>(adv + W * col_words + (base + 2) * 8, col_words, kids, a.consts, a.r_f, a.r_p, s);
+  if (l + 1 == a.depth) {                                    // the root: instance row E
     fe_to_ext_shift(w, s[0]);
-    ps_put_words(a.instance + u * 16 + 8, w);
+    ps_put_words(inst + E * 8, w);
   }
 }
 
-struct PoseidonWitnessArgs {
-  const uint32_t* msgs;          // m x 4 x 8 words
-  uint32_t* advice;              // m x POSEIDON_WITNESS_ADVICE x 2^log_n x 8, cleared
-  uint32_t* instance;            // m x 8: the digest
-  const uint32_t* consts;
-  uint64_t m;
-  uint32_t log_n, r_f, r_p;
-};
-
 // the whole Poseidon circuit of message u
-HM_HD void poseidon_witness_lane(const PoseidonWitnessArgs& a, uint64_t u) {
+HM_HD void poseidon_witness_lane(const WitnessArgs& a, uint64_t u) {
   const uint64_t col_words = (uint64_t)8 << a.log_n;
-  uint32_t* adv = a.advice + u * POSEIDON_WITNESS_ADVICE * col_words;
+  uint32_t* adv = a.advice + u * witness_advice(0) * col_words;
   uint32_t msg[4][8], w[8];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    ps_get_words(a.msgs + (u * 4 + j) * 8, msg[j]);
+    ps_get_words(a.leaves + (u * 4 + j) * 8, msg[j]);
     ps_put_words(adv + j * col_words + 0 * 8, msg[j]);     // "load private inputs"
     ps_put_words(adv + j * col_words + 1 * 8, msg[j]);     // "copy input cells to hash input cells"
-    ps_put_words(adv + j * col_words + 4 * 8, msg[j]);     // pad-and-add: the message row and the output row
-    ps_put_words(adv + j * col_words + 5 * 8, msg[j]);
   }
-  const uint32_t* cap = a.consts + ((size_t)(a.r_f + a.r_p) * 5 + 25) * 9;
-  fe_to_ext_shift(w, ps_load9(cap));
-  ps_put_words(adv + 4 * col_words + 2 * 8, w);            // "initial state", pad-and-add rows 0 and 2
-  ps_put_words(adv + 4 * col_words + 3 * 8, w);
-  ps_put_words(adv + 4 * col_words + 5 * 8, w);
   Fr s[5];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) s[j] = fe_from_ext<FrParams>(msg[j]);
-  s[4] = ps_load9(cap);
-  const WitnessSink sink{adv + 6 * 8, col_words};
-  poseidon_permute<5>(s, a.consts, a.r_f, a.r_p, sink);
+  pow5_hash_rows<5>(adv + 2 * 8, col_words, msg, a.consts, a.r_f, a.r_p, s);
   fe_to_ext_shift(w, s[0]);
   ps_put_words(a.instance + u * 8, w);
 }
@@ -653,33 +538,24 @@ __global__ __launch_bounds__(PS_THREADS) void merkle_path_kernel(const uint32_t*
   }
   ps_store_words(out + t * 8, w);
 }
-// one lane per (user, level); the columns were cleared by the caller
-__global__ __launch_bounds__(PS_THREADS) void merkle_sum_witness_kernel(const WitnessArgs a) {
+// a path circuit: one lane per (user, level); the columns were cleared by the caller
+template <int E>
+__global__ __launch_bounds__(PS_THREADS) void merkle_witness_kernel(const WitnessArgs a) {
   const uint64_t t = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
   if (t >= a.m * a.depth) return;
-  merkle_sum_witness_lane(a, t / a.depth, (uint32_t)(t % a.depth));
+  merkle_witness_lane<E>(a, t / a.depth, (uint32_t)(t % a.depth));
 }
 
 // one lane per user: depth - 1 hashes in sequence (paths that come without a tree)
-__global__ __launch_bounds__(PS_THREADS) void merkle_sum_chain_kernel(const WitnessArgs a, uint32_t* __restrict__ run) {
+template <int E>
+__global__ __launch_bounds__(PS_THREADS) void merkle_chain_kernel(const WitnessArgs a, uint32_t* __restrict__ run) {
   const uint64_t u = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
   if (u >= a.m) return;
-  merkle_sum_chain_lane(a, u, run);
+  merkle_chain_lane<E>(a, u, run);
 }
 
-// MerkleTreeV3: one lane per (user, level); the columns were cleared by the caller
-__global__ __launch_bounds__(PS_THREADS) void merkle_witness_kernel(const MerkleWitnessArgs a) {
-  const uint64_t t = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  if (t >= a.m * a.depth) return;
-  merkle_witness_lane(a, t / a.depth, (uint32_t)(t % a.depth));
-}
-__global__ __launch_bounds__(PS_THREADS) void merkle_chain_kernel(const MerkleWitnessArgs a, uint32_t* __restrict__ run) {
-  const uint64_t u = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  if (u >= a.m) return;
-  merkle_chain_lane(a, u, run);
-}
 // the Poseidon circuit: one lane per hash
-__global__ __launch_bounds__(PS_THREADS) void poseidon_witness_kernel(const PoseidonWitnessArgs a) {
+__global__ __launch_bounds__(PS_THREADS) void poseidon_witness_kernel(const WitnessArgs a) {
   const uint64_t u = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
   if (u >= a.m) return;
   poseidon_witness_lane(a, u);

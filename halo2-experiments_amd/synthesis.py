@@ -1,7 +1,8 @@
 """What ``MerkleSumTreeCircuit::synthesize`` decides, for ``circuits.merkle_sum_tree(spec)``: where every region lies, what the fixed
 columns hold, which cells are copy-constrained, and the advice columns themselves -- on Python integers here (``assign_ints``, the
 CPU twin) and on the GPU through the C ABI (``merkle_sum_witness``, csrc/poseidon.inc: one lane per (user, level), the Pow5 chip's
-trace of every Poseidon round written straight into the columns).  DESIGN.md section 13.
+trace of every Poseidon round written straight into the columns).  The Pow5 chip's regions of one hash are stated once, in
+``_Pow5Layout``, for this circuit and the two below.  DESIGN.md section 13.
 
 TRANSCRIBED from the reference (read as text):
     "assign leaf hash", "assign leaf balance"        /root/reference/src/chips/merkle_sum_tree.rs:140-171
@@ -51,7 +52,7 @@ from .poseidon import Spec, default_spec, ints_to_words
 R = FR_MODULUS
 Cell = Tuple[str, int, int]            # (kind, column, row)
 
-# circuits.merkle_sum_tree()'s allocation order (asserted against the constraint system in MerkleSumTreeLayout.__init__)
+# circuits.merkle_sum_tree()'s allocation order (MerkleSumTreeLayout's columns; the names tests and tools import)
 A, B, C, D, E = range(5)
 STATE = tuple(range(5, 10))
 PARTIAL_SBOX, LT = 10, 11
@@ -77,204 +78,8 @@ class Region:
         return range(self.start, self.start + self.height)
 
 
-class MerkleSumTreeLayout:
-    """A pure function of (depth, k, spec); see the module docstring for what is transcribed and what is recalled."""
-
-    def __init__(self, depth: int, k: int, spec: Optional[Spec] = None):
-        spec = default_spec(5) if spec is None else spec
-        if spec.width != 5:
-            raise ValueError("MerkleSumTreeLayout: needs a width-5 spec")
-        if not 1 <= depth <= 32:
-            raise ValueError("MerkleSumTreeLayout: depth must be 1 .. 32")
-        if spec.r_f % 2 or spec.r_p % 2:
-            raise ValueError("MerkleSumTreeLayout: the Pow5 chip needs even r_f and r_p")
-        self.depth, self.k, self.n, self.spec = depth, k, 1 << k, spec
-        self.perm_rows = spec.r_f + spec.r_p // 2 + 1
-        adv = lambda *cols: tuple(("advice", c) for c in cols)
-        regions: List[Region] = [Region("load u8 range check table", 0, 256, (("fixed", U8),))]
-        row = 0
-
-        def place(name: str, height: int, columns) -> Region:
-            nonlocal row
-            regions.append(Region(name, row, height, tuple(columns)))
-            row += height
-            return regions[-1]
-
-        place("assign leaf hash", 1, adv(A))
-        place("assign leaf balance", 1, adv(B))
-        self.level_start: List[int] = []
-        for l in range(depth):
-            self.level_start.append(row)
-            place(f"merkle prove layer {l}", 2, adv(A, B, C, D, E) + (("fixed", BOOL_S), ("fixed", SWAP_S), ("fixed", SUM_S)))
-            place(f"initial state {l}", 1, adv(*STATE))
-            place(f"pad-and-add {l}", 3, adv(*STATE) + (("fixed", S_PAD),))
-            place(f"permute state {l}", self.perm_rows,
-                  adv(*STATE, PARTIAL_SBOX) + tuple(("fixed", c) for c in RC_A + RC_B + (S_FULL, S_PARTIAL)))
-        self.level_rows = 6 + self.perm_rows
-        self.lt_row = row
-        place("enforce sum to be less than total assets", 1, adv(A, B, C, LT, *DIFF) + (("fixed", LT_S),))
-        self.const_row = row
-        place("constants", 5 * depth, (("fixed", RC_B[0]),))
-        self.regions = regions
-        self.used_rows = max(row, 256)
-        if self.used_rows > self.n - BLINDING_ROWS:
-            raise ValueError(f"MerkleSumTreeLayout: depth {depth} needs {self.used_rows} rows, 2^{k} - {BLINDING_ROWS} is fewer "
-                             f"(min_k = {self.min_k(depth, spec)})")
-
-    @staticmethod
-    def rows_needed(depth: int, spec: Optional[Spec] = None) -> int:
-        spec = default_spec(5) if spec is None else spec
-        return max(2 + depth * (6 + spec.r_f + spec.r_p // 2 + 1) + 1 + 5 * depth, 256)
-
-    @classmethod
-    def min_k(cls, depth: int, spec: Optional[Spec] = None) -> int:
-        return (cls.rows_needed(depth, spec) + BLINDING_ROWS - 1).bit_length()
-
-    # rows of level l
-    def prove_row(self, l: int) -> int:
-        return self.level_start[l]
-
-    def init_row(self, l: int) -> int:
-        return self.level_start[l] + 2
-
-    def pad_row(self, l: int) -> int:
-        return self.level_start[l] + 3
-
-    def perm_row(self, l: int) -> int:
-        return self.level_start[l] + 6
-
-    def digest_cell(self, l: int) -> Cell:
-        return ("advice", STATE[0], self.perm_row(l) + self.perm_rows - 1)
-
-    def sum_cell(self, l: int) -> Cell:
-        return ("advice", E, self.prove_row(l) + 1)
-
-    def _round_of_row(self, i: int) -> int:
-        """the (first) round that row i of "permute state" holds"""
-        half, r_p = self.spec.r_f // 2, self.spec.r_p
-        if i < half:
-            return i
-        if i < half + r_p // 2:
-            return half + 2 * (i - half)
-        return half + r_p + (i - half - r_p // 2)
-
-    def check_constraint_system(self, cs: ConstraintSystem) -> None:
-        if (cs.num_advice, cs.num_fixed, cs.num_instance) != (N_ADVICE, N_FIXED, 1):
-            raise ValueError("MerkleSumTreeLayout: the constraint system is not circuits.merkle_sum_tree()")
-
-    def selector_rows(self) -> Dict[int, List[int]]:
-        """fixed column of a selector -> the rows where it is enabled"""
-        half, pairs = self.spec.r_f // 2, self.spec.r_p // 2
-        out: Dict[int, List[int]] = {c: [] for c in (BOOL_S, SWAP_S, SUM_S, LT_S, S_FULL, S_PARTIAL, S_PAD)}
-        for l in range(self.depth):
-            out[BOOL_S].append(self.prove_row(l))
-            out[SWAP_S].append(self.prove_row(l))
-            out[SUM_S].append(self.prove_row(l) + 1)
-            out[S_PAD].append(self.pad_row(l) + 1)
-            p = self.perm_row(l)
-            out[S_FULL] += [p + i for i in range(half)] + [p + half + pairs + i for i in range(half)]
-            out[S_PARTIAL] += [p + half + i for i in range(pairs)]
-        out[LT_S].append(self.lt_row)
-        return out
-
-    def fixed_columns(self) -> List[List[int]]:
-        """The N_FIXED fixed columns as integers: selectors, rc_a / rc_b per "permute state" row, the u8 table, the constants."""
-        rc, _, _ = self.spec.constants()
-        half, pairs = self.spec.r_f // 2, self.spec.r_p // 2
-        cols = [[0] * self.n for _ in range(N_FIXED)]
-        for c, rows in self.selector_rows().items():
-            for r in rows:
-                cols[c][r] = 1
-        for l in range(self.depth):
-            p = self.perm_row(l)
-            for i in range(self.perm_rows - 1):
-                rnd = self._round_of_row(i)
-                for j in range(5):
-                    cols[RC_A[j]][p + i] = rc[rnd][j]
-                    if half <= i < half + pairs:
-                        cols[RC_B[j]][p + i] = rc[rnd + 1][j]
-            for j in range(5):
-                cols[RC_B[0]][self.const_row + 5 * l + j] = (self.spec.rate << 64) if j == 4 else 0
-        for v in range(256):
-            cols[U8][v] = v
-        return cols
-
-    def copies(self) -> List[Tuple[Cell, Cell]]:
-        out: List[Tuple[Cell, Cell]] = [(("advice", A, 0), ("instance", 0, 0)), (("advice", B, 1), ("instance", 0, 1))]   # expose_public 0, 1
-        prev_hash, prev_balance = ("advice", A, 0), ("advice", B, 1)
-        for l in range(self.depth):
-            pr, ini, pad, perm = self.prove_row(l), self.init_row(l), self.pad_row(l), self.perm_row(l)
-            out += [(prev_hash, ("advice", A, pr)), (prev_balance, ("advice", B, pr))]
-            for j in range(5):
-                out.append((("fixed", RC_B[0], self.const_row + 5 * l + j), ("advice", STATE[j], ini)))     # assign_advice_from_constant
-                out.append((("advice", STATE[j], ini), ("advice", STATE[j], pad)))
-                out.append((("advice", STATE[j], pad + 2), ("advice", STATE[j], perm)))
-            for j in range(4):
-                out.append((("advice", j, pr + 1), ("advice", STATE[j], pad + 1)))
-            prev_hash, prev_balance = self.digest_cell(l), self.sum_cell(l)
-        out += [(prev_balance, ("advice", A, self.lt_row)), (("instance", 0, 3), ("advice", B, self.lt_row)),
-                (prev_hash, ("instance", 0, 2))]
-        return out
-
-    def instance(self, leaf: Tuple[int, int], root: int, assets: int) -> List[List[int]]:
-        col = [0] * self.n
-        col[0], col[1], col[2], col[3] = int(leaf[0]) % R, int(leaf[1]) % R, int(root) % R, int(assets) % R
-        return [col]
-
-    def assign_ints(self, leaf: Tuple[int, int], siblings: Sequence[Tuple[int, int]], indices: Sequence[int], assets_sum: int) -> List[List[int]]:
-        """The N_ADVICE advice columns as the chip assigns them.  Nothing is judged: an index of 2 or a sum above the assets
-        gives an unsatisfied witness, as in the reference's negative tests."""
-        if len(siblings) != self.depth or len(indices) != self.depth:
-            raise ValueError("assign_ints: the path must have `depth` siblings and indices")
-        rc, mds, _ = self.spec.constants()
-        half, r_p, rounds = self.spec.r_f // 2, self.spec.r_p, self.spec.r_f + self.spec.r_p
-        cap = self.spec.rate << 64
-        adv = [[0] * self.n for _ in range(N_ADVICE)]
-        h, b = int(leaf[0]) % R, int(leaf[1]) % R
-        adv[A][0], adv[B][1] = h, b
-        total = b
-        for l, ((eh, eb), index) in enumerate(zip(siblings, indices)):
-            eh, eb, index = int(eh) % R, int(eb) % R, int(index) % R
-            pr, ini, pad, perm = self.prove_row(l), self.init_row(l), self.pad_row(l), self.perm_row(l)
-            adv[A][pr], adv[B][pr], adv[C][pr], adv[D][pr], adv[E][pr] = h, b, eh, eb, index
-            msg = [h, b, eh, eb] if index == 0 else [eh, eb, h, b]                         # :227-234
-            for j in range(4):
-                adv[j][pr + 1] = msg[j]
-                adv[STATE[j]][pad + 1] = msg[j]
-                adv[STATE[j]][pad + 2] = msg[j]
-            adv[E][pr + 1] = (msg[1] + msg[3]) % R
-            adv[STATE[4]][ini] = adv[STATE[4]][pad] = adv[STATE[4]][pad + 2] = cap
-            s, row = msg + [cap], 0
-            for r in range(rounds):
-                full = r < half or r >= half + r_p
-                first = full or (r - half) % 2 == 0
-                if first:
-                    for j in range(5):
-                        adv[STATE[j]][perm + row] = s[j]
-                x = [(v + c) % R for v, c in zip(s, rc[r])]
-                x[0] = pow(x[0], 5, R)
-                if first and not full:
-                    adv[PARTIAL_SBOX][perm + row] = x[0]
-                row += first
-                if full:
-                    x[1:] = [pow(v, 5, R) for v in x[1:]]
-                s = [sum(m * v for m, v in zip(mrow, x)) % R for mrow in mds]
-            for j in range(5):
-                adv[STATE[j]][perm + row] = s[j]
-            h, b = s[0], adv[E][pr + 1]
-            total = (total + eb) % R
-        assets = int(assets_sum) % R
-        lt = int(total < assets)
-        diff = (total - assets + (lt << 64)) % R
-        adv[A][self.lt_row], adv[B][self.lt_row], adv[C][self.lt_row], adv[LT][self.lt_row] = b, assets, 1, lt
-        for i, byte in enumerate(diff.to_bytes(32, "little")[:8]):
-            adv[DIFF[i]][self.lt_row] = byte
-        return adv
-
-
-# ---- the two other circuits: MerkleTreeV3 and Poseidon ---------------------------------------------------------------------------
 class _Pow5Layout:
-    """What the two layouts below share: the Pow5 chip's regions of one hash ("initial state" 1 row, "pad-and-add" 3, "permute
+    """What the three layouts below share: the Pow5 chip's regions of one hash ("initial state" 1 row, "pad-and-add" 3, "permute
     state" perm_rows), their selectors, rc_a / rc_b rows, constants, copies and the assignment of the trace.  A subclass names its
     columns (WIDTH, STATE, PARTIAL_SBOX, RC_A, RC_B, S_FULL, S_PARTIAL, S_PAD, N_ADVICE, N_FIXED) and lists ``hash_start``: the
     "initial state" row of every hash; the constants of hash h lie in rc_b[0] at const_row + WIDTH * h."""
@@ -305,10 +110,10 @@ class _Pow5Layout:
         place(f"permute state{tag}", self.perm_rows, adv + (("advice", self.PARTIAL_SBOX),) +
               tuple(("fixed", c) for c in self.RC_A + self.RC_B + (self.S_FULL, self.S_PARTIAL)))
 
-    def _finish(self, row: int, place) -> None:
+    def _finish(self, row: int, place, min_rows: int = 0) -> None:
         self.const_row = row
         place("constants", self.WIDTH * len(self.hash_start), (("fixed", self.RC_B[0]),))
-        self.used_rows = self.const_row + self.WIDTH * len(self.hash_start)
+        self.used_rows = max(self.const_row + self.WIDTH * len(self.hash_start), min_rows)
         if self.used_rows > self.n - BLINDING_ROWS:
             raise ValueError(f"{self.NAME}: {self.used_rows} rows are needed, 2^{self.k} - {BLINDING_ROWS} is fewer")
 
@@ -325,7 +130,14 @@ class _Pow5Layout:
     def digest_cell(self, h: int = 0) -> Cell:
         return ("advice", self.STATE[0], self.perm_row(h) + self.perm_rows - 1)
 
-    _round_of_row = MerkleSumTreeLayout._round_of_row
+    def _round_of_row(self, i: int) -> int:
+        """the (first) round that row i of "permute state" holds"""
+        half, r_p = self.spec.r_f // 2, self.spec.r_p
+        if i < half:
+            return i
+        if i < half + r_p // 2:
+            return half + 2 * (i - half)
+        return half + r_p + (i - half - r_p // 2)
 
     def check_constraint_system(self, cs: ConstraintSystem) -> None:
         if (cs.num_advice, cs.num_fixed, cs.num_instance) != (self.N_ADVICE, self.N_FIXED, 1):
@@ -403,6 +215,117 @@ class _Pow5Layout:
         for j in range(W):
             adv[self.STATE[j]][perm + row] = s[j]
         return s[0]
+
+
+class MerkleSumTreeLayout(_Pow5Layout):
+    """``MerkleSumTreeCircuit::synthesize`` for ``circuits.merkle_sum_tree(spec)``: a pure function of (depth, k, spec); see the
+    module docstring for what is transcribed and what is recalled.  Rows 0, 1 the leaf; level l at 2 + l * level_rows: "merkle prove
+    layer" (2 rows), then the hash's three regions; the less-than row; 5 constants per level at the end; the u8 table in rows 0 .. 255."""
+    NAME = "MerkleSumTreeLayout"
+    WIDTH = 5
+    STATE, PARTIAL_SBOX, N_ADVICE = STATE, PARTIAL_SBOX, N_ADVICE
+    RC_A, RC_B, S_FULL, S_PARTIAL, S_PAD, N_FIXED = RC_A, RC_B, S_FULL, S_PARTIAL, S_PAD, N_FIXED
+    N_INSTANCE_ROWS = 4
+
+    def __init__(self, depth: int, k: int, spec: Optional[Spec] = None):
+        if not 1 <= depth <= 32:
+            raise ValueError("MerkleSumTreeLayout: depth must be 1 .. 32")
+        spec = self._init_pow5(k, spec)
+        self.depth = depth
+        adv = lambda *cols: tuple(("advice", c) for c in cols)
+        regions: List[Region] = [Region("load u8 range check table", 0, 256, (("fixed", U8),))]
+        row = 0
+
+        def place(name: str, height: int, columns) -> Region:
+            nonlocal row
+            regions.append(Region(name, row, height, tuple(columns)))
+            row += height
+            return regions[-1]
+
+        place("assign leaf hash", 1, adv(A))
+        place("assign leaf balance", 1, adv(B))
+        self.level_start: List[int] = []
+        for l in range(depth):
+            self.level_start.append(row)
+            place(f"merkle prove layer {l}", 2, adv(A, B, C, D, E) + (("fixed", BOOL_S), ("fixed", SWAP_S), ("fixed", SUM_S)))
+            self._place_hash(place, f" {l}")
+        self.level_rows = 6 + self.perm_rows
+        self.lt_row = row
+        place("enforce sum to be less than total assets", 1, adv(A, B, C, LT, *DIFF) + (("fixed", LT_S),))
+        self.regions = regions
+        try:
+            self._finish(row, place, min_rows=256)
+        except ValueError as e:
+            raise ValueError(f"{e} (depth {depth}: min_k = {self.min_k(depth, spec)})") from None
+
+    @staticmethod
+    def rows_needed(depth: int, spec: Optional[Spec] = None) -> int:
+        spec = default_spec(5) if spec is None else spec
+        return max(2 + depth * (6 + spec.r_f + spec.r_p // 2 + 1) + 1 + 5 * depth, 256)
+
+    @classmethod
+    def min_k(cls, depth: int, spec: Optional[Spec] = None) -> int:
+        return (cls.rows_needed(depth, spec) + BLINDING_ROWS - 1).bit_length()
+
+    def prove_row(self, l: int) -> int:
+        return self.level_start[l]
+
+    def sum_cell(self, l: int) -> Cell:
+        return ("advice", E, self.prove_row(l) + 1)
+
+    def selector_rows(self) -> Dict[int, List[int]]:
+        out = {BOOL_S: [self.prove_row(l) for l in range(self.depth)], SWAP_S: [self.prove_row(l) for l in range(self.depth)],
+               SUM_S: [self.prove_row(l) + 1 for l in range(self.depth)], LT_S: [self.lt_row]}
+        return self._pow5_selector_rows(out)
+
+    def fixed_columns(self) -> List[List[int]]:
+        """The N_FIXED fixed columns as integers: what every Pow5 layout has, and the u8 table."""
+        cols = super().fixed_columns()
+        cols[U8][:256] = range(256)
+        return cols
+
+    def copies(self) -> List[Tuple[Cell, Cell]]:
+        out: List[Tuple[Cell, Cell]] = [(("advice", A, 0), ("instance", 0, 0)), (("advice", B, 1), ("instance", 0, 1))]   # expose_public 0, 1
+        prev_hash, prev_balance = ("advice", A, 0), ("advice", B, 1)
+        for l in range(self.depth):
+            pr = self.prove_row(l)
+            out += [(prev_hash, ("advice", A, pr)), (prev_balance, ("advice", B, pr))]
+            out += self._pow5_copies(l, [("advice", j, pr + 1) for j in range(4)])
+            prev_hash, prev_balance = self.digest_cell(l), self.sum_cell(l)
+        out += [(prev_balance, ("advice", A, self.lt_row)), (("instance", 0, 3), ("advice", B, self.lt_row)),
+                (prev_hash, ("instance", 0, 2))]
+        return out
+
+    def instance(self, leaf: Tuple[int, int], root: int, assets: int) -> List[List[int]]:
+        col = [0] * self.n
+        col[0], col[1], col[2], col[3] = int(leaf[0]) % R, int(leaf[1]) % R, int(root) % R, int(assets) % R
+        return [col]
+
+    def assign_ints(self, leaf: Tuple[int, int], siblings: Sequence[Tuple[int, int]], indices: Sequence[int], assets_sum: int) -> List[List[int]]:
+        """The N_ADVICE advice columns as the chip assigns them.  Nothing is judged: an index of 2 or a sum above the assets
+        gives an unsatisfied witness, as in the reference's negative tests."""
+        if len(siblings) != self.depth or len(indices) != self.depth:
+            raise ValueError("assign_ints: the path must have `depth` siblings and indices")
+        adv = [[0] * self.n for _ in range(N_ADVICE)]
+        h, b = int(leaf[0]) % R, int(leaf[1]) % R
+        adv[A][0], adv[B][1] = h, b
+        total = b
+        for l, ((eh, eb), index) in enumerate(zip(siblings, indices)):
+            eh, eb, index, pr = int(eh) % R, int(eb) % R, int(index) % R, self.prove_row(l)
+            adv[A][pr], adv[B][pr], adv[C][pr], adv[D][pr], adv[E][pr] = h, b, eh, eb, index
+            msg = [h, b, eh, eb] if index == 0 else [eh, eb, h, b]                         # :227-234
+            for j in range(4):
+                adv[j][pr + 1] = msg[j]
+            adv[E][pr + 1] = b = (msg[1] + msg[3]) % R
+            h = self._pow5_assign(adv, l, msg)
+            total = (total + eb) % R
+        assets = int(assets_sum) % R
+        lt = int(total < assets)
+        diff = (total - assets + (lt << 64)) % R
+        adv[A][self.lt_row], adv[B][self.lt_row], adv[C][self.lt_row], adv[LT][self.lt_row] = b, assets, 1, lt
+        for i, byte in enumerate(diff.to_bytes(32, "little")[:8]):
+            adv[DIFF[i]][self.lt_row] = byte
+        return adv
 
 
 class MerkleTreeV3Layout(_Pow5Layout):
@@ -648,14 +571,59 @@ def permutation_columns(cs: ConstraintSystem, layout: "AnyLayout", omega: int, d
     return out
 
 
-# ---- the witness on the GPU -------------------------------------------------------------------------------------------------------
+# ---- the witnesses on the GPU -----------------------------------------------------------------------------------------------------
+def _c_layout(entry: str, spec: Spec, args: Tuple[int, ...], names: Tuple[str, ...]) -> Dict[str, int]:
+    rows, n_adv, reg = ctypes.c_uint32(0), ctypes.c_uint32(0), (ctypes.c_uint32 * len(names))()
+    _lib.check(getattr(_lib.load(), entry)(spec.r_f, spec.r_p, *args, ctypes.byref(rows), ctypes.byref(n_adv), reg))
+    return {"used_rows": rows.value, "n_advice": n_adv.value, **dict(zip(names, reg))}
+
+
 def c_layout(depth: int, k: int, spec: Optional[Spec] = None) -> Dict[str, int]:
     """``hm_merkle_sum_witness_layout``: the placement the kernel uses (no device needed)."""
-    spec = default_spec(5) if spec is None else spec
-    rows, n_adv, reg = ctypes.c_uint32(0), ctypes.c_uint32(0), (ctypes.c_uint32 * 4)()
-    _lib.check(_lib.load().hm_merkle_sum_witness_layout(spec.r_f, spec.r_p, depth, k, ctypes.byref(rows), ctypes.byref(n_adv), reg))
-    return {"used_rows": rows.value, "n_advice": n_adv.value, "perm_rows": reg[0], "level_rows": reg[1], "lt_row": reg[2],
-            "const_row": reg[3]}
+    return _c_layout("hm_merkle_sum_witness_layout", default_spec(5) if spec is None else spec, (depth, k),
+                     ("perm_rows", "level_rows", "lt_row", "const_row"))
+
+
+def merkle_c_layout(depth: int, k: int, spec: Optional[Spec] = None) -> Dict[str, int]:
+    """``hm_merkle_witness_layout``: the placement the MerkleTreeV3 kernel uses (no device needed)."""
+    return _c_layout("hm_merkle_witness_layout", default_spec(3) if spec is None else spec, (depth, k), ("perm_rows", "level_rows", "const_row"))
+
+
+def poseidon_c_layout(k: int, spec: Optional[Spec] = None) -> Dict[str, int]:
+    """``hm_poseidon_witness_layout``: the placement the Poseidon circuit's kernel uses (level_rows: the rows before the constants)."""
+    return _c_layout("hm_poseidon_witness_layout", default_spec(5) if spec is None else spec, (k,), ("perm_rows", "level_rows", "const_row"))
+
+
+def _witness_out(who: str, out, m: int, n_advice: int, n: int, device):
+    import torch
+
+    if out is None:
+        return torch.empty((m, n_advice, n, 4), dtype=torch.int64, device=device)
+    if not (out.is_cuda and out.is_contiguous() and out.element_size() == 8 and out.numel() == m * n_advice * n * 4):
+        raise ValueError(f"{who}: out must be a contiguous (m, {n_advice}, 2^k, 4) GPU tensor")
+    return out
+
+
+def _path_tensors(who: str, elements: int, leaves, siblings, indices, nodes, out) -> Tuple[int, int]:
+    """the checks of the path circuits' GPU tensors (``elements`` per node) -> (m, depth)"""
+    from .arithmetic import _tensor_rows
+
+    m = _tensor_rows(leaves, 4 * elements, "leaves")
+    if m == 0:
+        raise ValueError(f"{who}: no paths")
+    depth = _tensor_rows(siblings, 4 * elements * m, "siblings")
+    if not (indices.is_cuda and indices.is_contiguous() and indices.element_size() == 8 and indices.numel() == m):
+        raise ValueError(f"{who}: indices must be m 64-bit integers on the GPU")
+    if nodes is not None and not (nodes.is_cuda and nodes.is_contiguous() and nodes.element_size() == 8
+                                  and nodes.numel() == ((2 << depth) - 1) * 4 * elements):
+        raise ValueError(f"{who}: nodes must be the contiguous (2^(depth+1) - 1, {elements}, 4) GPU tensor of a tree of depth {depth}")
+    for name, t in (("siblings", siblings), ("indices", indices), ("nodes", nodes), ("out", out)):
+        if t is not None and t.is_cuda and t.device != leaves.device:
+            raise ValueError(f"{who}: {name} is on {t.device}, leaves on {leaves.device}")
+    for name, t in (("leaves", leaves), ("siblings", siblings), ("nodes", nodes), ("out", out)):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"{who}: {name} must be 16-byte aligned")
+    return m, depth
 
 
 def merkle_sum_witness(spec: Optional[Spec], leaves, siblings, indices, assets_sum: int, k: int, nodes=None, out=None):
@@ -666,29 +634,11 @@ def merkle_sum_witness(spec: Optional[Spec], leaves, siblings, indices, assets_s
     ``out``: an advice tensor to fill instead of a new one (it may be uninitialised)."""
     import torch
 
-    from .arithmetic import _stream_ptr, _tensor_rows
+    from .arithmetic import _stream_ptr
 
     spec = default_spec(5) if spec is None else spec
-    m = _tensor_rows(leaves, 8, "leaves")
-    if m == 0:
-        raise ValueError("merkle_sum_witness: no paths")
-    depth = _tensor_rows(siblings, 8 * m, "siblings")
-    if not (indices.is_cuda and indices.is_contiguous() and indices.element_size() == 8 and indices.numel() == m):
-        raise ValueError("merkle_sum_witness: indices must be m 64-bit integers on the GPU")
-    if nodes is not None and not (nodes.is_cuda and nodes.is_contiguous() and nodes.element_size() == 8
-                                  and nodes.numel() == ((2 << depth) - 1) * 8):
-        raise ValueError(f"merkle_sum_witness: nodes must be the contiguous (2^(depth+1) - 1, 2, 4) GPU tensor of a tree of depth {depth}")
-    for name, t in (("siblings", siblings), ("indices", indices), ("nodes", nodes), ("out", out)):
-        if t is not None and t.is_cuda and t.device != leaves.device:
-            raise ValueError(f"merkle_sum_witness: {name} is on {t.device}, leaves on {leaves.device}")
-    for name, t in (("leaves", leaves), ("siblings", siblings), ("nodes", nodes), ("out", out)):
-        if t is not None and t.data_ptr() % 16:
-            raise ValueError(f"merkle_sum_witness: {name} must be 16-byte aligned")
-    n = 1 << k
-    if out is None:
-        out = torch.empty((m, N_ADVICE, n, 4), dtype=torch.int64, device=leaves.device)
-    elif not (out.is_cuda and out.is_contiguous() and out.element_size() == 8 and out.numel() == m * N_ADVICE * n * 4):
-        raise ValueError("merkle_sum_witness: out must be a contiguous (m, N_ADVICE, 2^k, 4) GPU tensor")
+    m, depth = _path_tensors("merkle_sum_witness", 2, leaves, siblings, indices, nodes, out)
+    out = _witness_out("merkle_sum_witness", out, m, N_ADVICE, 1 << k, leaves.device)
     inst = torch.empty((m, 4, 4), dtype=torch.int64, device=leaves.device)
     assets = np.ascontiguousarray(fr_words(int(assets_sum) % R))
     with torch.cuda.device(leaves.device):
@@ -714,33 +664,6 @@ def merkle_sum_witness_host(spec: Optional[Spec], leaves: np.ndarray, siblings: 
     return adv, inst
 
 
-# ---- the MerkleTreeV3 and Poseidon circuit witnesses on the GPU ---------------------------------------------------------------------
-def merkle_c_layout(depth: int, k: int, spec: Optional[Spec] = None) -> Dict[str, int]:
-    """``hm_merkle_witness_layout``: the placement the MerkleTreeV3 kernel uses (no device needed)."""
-    spec = default_spec(3) if spec is None else spec
-    rows, n_adv, reg = ctypes.c_uint32(0), ctypes.c_uint32(0), (ctypes.c_uint32 * 3)()
-    _lib.check(_lib.load().hm_merkle_witness_layout(spec.r_f, spec.r_p, depth, k, ctypes.byref(rows), ctypes.byref(n_adv), reg))
-    return {"used_rows": rows.value, "n_advice": n_adv.value, "perm_rows": reg[0], "level_rows": reg[1], "const_row": reg[2]}
-
-
-def poseidon_c_layout(k: int, spec: Optional[Spec] = None) -> Dict[str, int]:
-    """``hm_poseidon_witness_layout``: the placement the Poseidon circuit's kernel uses (level_rows: the rows before the constants)."""
-    spec = default_spec(5) if spec is None else spec
-    rows, n_adv, reg = ctypes.c_uint32(0), ctypes.c_uint32(0), (ctypes.c_uint32 * 3)()
-    _lib.check(_lib.load().hm_poseidon_witness_layout(spec.r_f, spec.r_p, k, ctypes.byref(rows), ctypes.byref(n_adv), reg))
-    return {"used_rows": rows.value, "n_advice": n_adv.value, "perm_rows": reg[0], "level_rows": reg[1], "const_row": reg[2]}
-
-
-def _witness_out(who: str, out, m: int, n_advice: int, n: int, device):
-    import torch
-
-    if out is None:
-        return torch.empty((m, n_advice, n, 4), dtype=torch.int64, device=device)
-    if not (out.is_cuda and out.is_contiguous() and out.element_size() == 8 and out.numel() == m * n_advice * n * 4):
-        raise ValueError(f"{who}: out must be a contiguous (m, {n_advice}, 2^k, 4) GPU tensor")
-    return out
-
-
 def merkle_witness(spec: Optional[Spec], leaves, siblings, indices, k: int, nodes=None, out=None):
     """The MerkleTreeV3 witnesses of m inclusion paths: ``leaves`` (m, 4), ``siblings`` (m, depth, 4) as ``hm_merkle_paths_dev``
     writes them with one word per node and ``indices`` (m,) int64 (bit l = right child at level l) are GPU tensors of canonical
@@ -749,24 +672,10 @@ def merkle_witness(spec: Optional[Spec], leaves, siblings, indices, k: int, node
     ``out``: an advice tensor to fill instead of a new one (it may be uninitialised)."""
     import torch
 
-    from .arithmetic import _stream_ptr, _tensor_rows
+    from .arithmetic import _stream_ptr
 
     spec = default_spec(3) if spec is None else spec
-    m = _tensor_rows(leaves, 4, "leaves")
-    if m == 0:
-        raise ValueError("merkle_witness: no paths")
-    depth = _tensor_rows(siblings, 4 * m, "siblings")
-    if not (indices.is_cuda and indices.is_contiguous() and indices.element_size() == 8 and indices.numel() == m):
-        raise ValueError("merkle_witness: indices must be m 64-bit integers on the GPU")
-    if nodes is not None and not (nodes.is_cuda and nodes.is_contiguous() and nodes.element_size() == 8
-                                  and nodes.numel() == ((2 << depth) - 1) * 4):
-        raise ValueError(f"merkle_witness: nodes must be the contiguous (2^(depth+1) - 1, 1, 4) GPU tensor of a tree of depth {depth}")
-    for name, t in (("siblings", siblings), ("indices", indices), ("nodes", nodes), ("out", out)):
-        if t is not None and t.is_cuda and t.device != leaves.device:
-            raise ValueError(f"merkle_witness: {name} is on {t.device}, leaves on {leaves.device}")
-    for name, t in (("leaves", leaves), ("siblings", siblings), ("nodes", nodes), ("out", out)):
-        if t is not None and t.data_ptr() % 16:
-            raise ValueError(f"merkle_witness: {name} must be 16-byte aligned")
+    m, depth = _path_tensors("merkle_witness", 1, leaves, siblings, indices, nodes, out)
     out = _witness_out("merkle_witness", out, m, MerkleTreeV3Layout.N_ADVICE, 1 << k, leaves.device)
     inst = torch.empty((m, 2, 4), dtype=torch.int64, device=leaves.device)
     with torch.cuda.device(leaves.device):

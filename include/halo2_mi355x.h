@@ -545,7 +545,8 @@ int hm_merkle_paths_dev(const void* d_nodes, uint32_t depth, uint32_t words_per_
  * (column c of user u is contiguous), every word of which is written (unassigned cells and the last rows are zero: blinding is the
  * prover's business); d_instance: m x 4 elements (leaf hash, leaf balance, root, assets).  Nothing is judged: a sum above the
  * assets gives an unsatisfied witness.  Asynchronous on `stream`.  Arguments are checked before anything is launched.  Every device
- * pointer must be 16-byte aligned (elements are moved as two 16-byte halves); d_nodes must hold all 2^(depth+1) - 1 nodes of `depth`.
+ * pointer must be 16-byte aligned (elements are moved as two 16-byte halves; d_indices: 8), and one that is not is refused with
+ * HM_ERR_BAD_ARG like every other bad argument; d_nodes must hold all 2^(depth+1) - 1 nodes of `depth`.
  * Host form: m * n_advice * 2^log_n * 32 bytes <= 256 MiB; outputs are written only by the final copies. */
 int hm_merkle_sum_witness_layout(uint32_t r_f, uint32_t r_p, uint32_t depth, uint32_t log_n, uint32_t* out_rows_used,
                                  uint32_t* out_n_advice, uint32_t* out_regions);

@@ -1,4 +1,4 @@
-"""The MerkleSumTree witness on the GPU (csrc/poseidon.inc: merkle_sum_witness_kernel / merkle_sum_chain_kernel) against
+"""The MerkleSumTree witness on the GPU (csrc/poseidon.inc: merkle_witness_kernel<2> / merkle_chain_kernel<2>) against
 synthesis.assign_ints word for word, against the tests' MockProver, and against the gate polynomials of
 circuits.merkle_sum_tree(spec) run by the device GraphEvaluator over every user's columns."""
 import ctypes
@@ -216,6 +216,50 @@ def test_unsatisfiable_inputs_are_filled_and_fail_where_they_should(batch, spec)
         assert batch["check"].rows(adv[u], inst[u]) == {"check == is_lt": [batch["lay"].lt_row]}
 
 
+def _sparse_columns_to_words(cols):
+    """sy.columns_to_words, converting the non-zero cells only (zero is four zero words): most of a witness is unassigned"""
+    out = np.zeros((len(cols), len(cols[0]), 4), dtype=np.uint64)
+    for c, col in enumerate(cols):
+        rows = [r for r, v in enumerate(col) if v]
+        if rows:
+            out[c, rows] = ps.ints_to_words([col[r] for r in rows])
+    return out
+
+
+@pytest.mark.parametrize("depth,m,k,with_tree", [(1, 1, 9, True), (1, 257, 9, True), (1, 257, 9, False), (2, 129, 9, True),
+                                                 (2, 129, 9, False), (3, 86, 9, False)])
+def test_smallest_shapes(spec, depth, m, k, with_tree):
+    """depth 1: the lane of level 0 is also the lane of the last level and the chain has nothing to do; depth 2 without a tree is the
+    shortest chain; m * depth = 257 and 258 cross one workgroup of 256 lanes.  Every word of every user's columns and instance."""
+    lay = sy.MerkleSumTreeLayout(depth, k, spec)
+    rng = random.Random(100 * depth + m)
+    assets = 1 << 60
+    if with_tree:
+        n = 1 << depth
+        tree_leaves = [(rng.randrange(R), rng.randrange(1 << 40)) for _ in range(n)]
+        tree = ps.MerkleSumTree.build(_gpu(ps.ints_to_words([v for leaf in tree_leaves for v in leaf]).reshape(n, 2, 4)), spec)
+        index = [rng.randrange(n) for _ in range(m)]
+        paths = [(tree_leaves[i], list(zip(hashes, balances)), bits) for i, (hashes, balances, bits) in zip(index, tree.paths(index))]
+        nodes = tree.nodes
+    else:
+        paths = [((rng.randrange(R), rng.randrange(1 << 40)), [(rng.randrange(R), rng.randrange(1 << 40)) for _ in range(depth)],
+                  [rng.randrange(2) for _ in range(depth)]) for _ in range(m)]
+        paths[0] = (paths[0][0], paths[0][1], [1] * depth)
+        nodes = None
+    leaves = _gpu(ps.ints_to_words([v for leaf, _, _ in paths for v in leaf]).reshape(m, 2, 4))
+    sibs = _gpu(ps.ints_to_words([v for _, sib, _ in paths for e in sib for v in e]).reshape(m, depth, 2, 4))
+    idx = torch.tensor([sum(b << l for l, b in enumerate(bits)) for _, _, bits in paths], dtype=torch.int64, device="cuda")
+    out = torch.full((m, sy.N_ADVICE, 1 << k, 4), FILL, dtype=torch.int64, device="cuda")
+    adv, inst = sy.merkle_sum_witness(spec, leaves, sibs, idx, assets, k, nodes=nodes, out=out)
+    got, got_inst = adv.cpu().numpy().view(np.uint64), inst.cpu().numpy().view(np.uint64)
+    for u, (leaf, sib, bits) in enumerate(paths):
+        assert np.array_equal(got[u], _sparse_columns_to_words(lay.assign_ints(leaf, sib, bits, assets))), u
+        root = ps.MerkleSumTree.verify_path(leaf, ([h for h, _ in sib], [b for _, b in sib], bits), spec)
+        assert np.array_equal(got_inst[u], ps.ints_to_words(lay.instance(leaf, root[0], assets)[0][:4])), u
+    if with_tree:
+        assert set(_ints(inst[:, 2])) == {tree.root[0]}
+
+
 def test_permutation_columns_on_the_device(spec):
     lay = sy.MerkleSumTreeLayout(5, 9, spec)
     cs = circuits.merkle_sum_tree(spec)
@@ -241,6 +285,10 @@ def test_rejected_arguments_leave_the_output_untouched(spec):
     P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
     I = lambda t: ctypes.cast(ctypes.c_void_p(t.data_ptr()), ctypes.POINTER(ctypes.c_uint64)) if t is not None else None
 
+    class Shifted:                                                # a tensor's address moved by `off` bytes (never dereferenced)
+        def __init__(self, t, off):
+            self.data_ptr = lambda: t.data_ptr() + off
+
     def call(handle=h5, depth=5, log_n=9, lv=leaves, sb=sibs, ix=idx, a=assets, nodes=None, out=adv, ins=inst):
         return lib.hm_merkle_sum_witness_bn256_dev(handle, depth, log_n, 1, P(lv), P(sb), I(ix), _u64(a) if a is not None else None, P(nodes),
                                                    P(out), P(ins), None)
@@ -254,6 +302,8 @@ def test_rejected_arguments_leave_the_output_untouched(spec):
     assert call(depth=31, log_n=11, nodes=adv) == HM_ERR_BAD_ARG  # a built tree has depth <= 30
     for kw in ("lv", "sb", "ix", "a", "out", "ins"):
         assert call(**{kw: None}) == HM_ERR_BAD_ARG, kw
+    for kw, t, off in (("lv", leaves, 8), ("sb", sibs, 8), ("out", adv, 8), ("ins", inst, 8), ("nodes", adv, 8), ("ix", idx, 4)):
+        assert call(**{kw: Shifted(t, off)}) == HM_ERR_BAD_ARG and b"aligned" in lib.hm_last_error(), kw     # the lanes move 16-byte vectors
     too_many = ((1 << 31) // 5) + 1                               # m * depth > 2^31: refused before any pointer is read
     assert lib.hm_merkle_sum_witness_bn256_dev(h5, 5, 9, too_many, P(leaves), P(sibs), I(idx), _u64(assets), None, P(adv), P(inst), None) == HM_ERR_BAD_ARG
     assert b"2^31" in lib.hm_last_error()

@@ -1,4 +1,4 @@
-"""The MerkleTreeV3 and Poseidon circuit witnesses on the GPU (csrc/poseidon.inc: merkle_witness_kernel / merkle_chain_kernel /
+"""The MerkleTreeV3 and Poseidon circuit witnesses on the GPU (csrc/poseidon.inc: merkle_witness_kernel<1> / merkle_chain_kernel<1> /
 poseidon_witness_kernel) against synthesis.assign_ints word for word, against the tests' MockProver, and against the gate
 polynomials of circuits.merkle_v3(spec) / circuits.poseidon(spec) run by the device GraphEvaluator over every user's columns.
 Outputs are prefilled with a sentinel, so a word the call does not write shows."""

@@ -1,5 +1,5 @@
 """Helper of tests/test_witness_v3.py: paths and messages through libhm_hostcheck.so's hc_merkle_witness / hc_poseidon_witness (the
-lane functions of merkle_witness_kernel, merkle_chain_kernel and poseidon_witness_kernel compiled for the host with the limb-bound
+lane functions of merkle_witness_kernel<1>, merkle_chain_kernel<1> and poseidon_witness_kernel compiled for the host with the limb-bound
 checks on), as integer columns."""
 import ctypes
 
