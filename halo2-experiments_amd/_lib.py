@@ -166,6 +166,10 @@ _SIGNATURES = {
     "hm_merkle_sum_tree_build": (ctypes.c_int, [ctypes.c_uint64, _u64p, ctypes.c_uint32, _u64p, _u64p]),
     "hm_merkle_tree_build_dev": (ctypes.c_int, [ctypes.c_uint64, _vp, ctypes.c_uint32, _vp, _vp]),
     "hm_merkle_paths_dev": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64p, ctypes.c_size_t, _vp, _vp]),
+    "hm_merkle_sum_tree_update_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, _vp, _u64p, _vp, ctypes.c_size_t, _u32p, _vp]),
+    "hm_merkle_tree_update_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, _vp, _u64p, _vp, ctypes.c_size_t, _u32p, _vp]),
+    "hm_merkle_roots_bn256_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_size_t, _vp, _vp, _u64p, _vp, _vp]),
+    "hm_merkle_roots_bn256": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_size_t, _u64p, _u64p, _u64p, _u64p]),
     "hm_merkle_sum_witness_layout": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p, _u32p]),
     "hm_merkle_sum_witness_bn256_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, _vp, _vp, _u64p,
                                                       _u64p, _vp, _vp, _vp, _vp]),

@@ -2565,6 +2565,91 @@ int hm_poseidon_witness_bn256(uint64_t handle, uint32_t log_n, size_t m, const u
                       });
 } HM_API_CATCH("hm_poseidon_witness_bn256")
 
+// ---- a built tree updated in place, and the roots of many paths (poseidon.inc: merkle_update_*, merkle_root_lane) -----------------
+static int merkle_update_dev(const char* who, uint64_t handle, uint32_t width, uint32_t depth, void* d_nodes, const uint64_t* d_indices,
+                             const void* d_new_leaves, size_t m, uint32_t* d_counts_or_null, void* stream) {
+  const std::string w(who);
+  if (m && (!d_nodes || !d_indices || !d_new_leaves)) return hm_fail(HM_ERR_BAD_ARG, w + ": null argument");
+  if (depth == 0 || depth > MERKLE_MAX_DEPTH) return hm_fail(HM_ERR_BAD_ARG, w + ": depth must be 1 .. 30");
+  if (m > POSEIDON_MAX_N) return hm_fail(HM_ERR_BAD_ARG, w + ": m > 2^31");
+  if (int rc = witness_aligned(who, {d_nodes, d_new_leaves}, d_indices)) return rc;
+  if ((uintptr_t)d_counts_or_null & 3u) return hm_fail(HM_ERR_BAD_ARG, w + ": d_counts is not 4-byte aligned");
+  const size_t elem_bytes = width == 5 ? 64 : 32;
+  if (m && ranges_overlap(d_new_leaves, m * elem_bytes, d_nodes, (((size_t)2 << depth) - 1) * elem_bytes))
+    return hm_fail(HM_ERR_BAD_ARG, w + ": d_new_leaves overlaps d_nodes");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PoseidonSpec* s = nullptr;
+  if (int rc = merkle_spec(who, *ctx, handle, width, &s)) return rc;
+  return merkle_update_run(*s, (uint32_t*)d_nodes, depth, d_indices, (const uint32_t*)d_new_leaves, m, d_counts_or_null, (hipStream_t)stream);
+}
+
+int hm_merkle_sum_tree_update_dev(uint64_t handle, uint32_t depth, void* d_nodes, const uint64_t* d_indices, const void* d_new_leaves,
+                                  size_t m, uint32_t* d_counts_or_null, void* stream) try {
+  return merkle_update_dev("hm_merkle_sum_tree_update_dev", handle, 5, depth, d_nodes, d_indices, d_new_leaves, m, d_counts_or_null, stream);
+} HM_API_CATCH("hm_merkle_sum_tree_update_dev")
+
+int hm_merkle_tree_update_dev(uint64_t handle, uint32_t depth, void* d_nodes, const uint64_t* d_indices, const void* d_new_leaves, size_t m,
+                              uint32_t* d_counts_or_null, void* stream) try {
+  return merkle_update_dev("hm_merkle_tree_update_dev", handle, 3, depth, d_nodes, d_indices, d_new_leaves, m, d_counts_or_null, stream);
+} HM_API_CATCH("hm_merkle_tree_update_dev")
+
+// what both forms of the roots refuse before anything else
+static int merkle_roots_args(const char* who, uint32_t depth, size_t m, const void* leaves, const void* siblings, const void* indices,
+                             const void* roots) {
+  if (m && (!leaves || !siblings || !indices || !roots)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (depth == 0 || depth > MERKLE_MAX_DEPTH) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": depth must be 1 .. 30");
+  if (m > POSEIDON_MAX_N) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": m > 2^31");
+  return HM_OK;
+}
+
+int hm_merkle_roots_bn256_dev(uint64_t handle, uint32_t depth, size_t m, const void* d_leaves, const void* d_siblings,
+                              const uint64_t* d_indices, void* d_roots, void* stream) try {
+  const char* who = "hm_merkle_roots_bn256_dev";
+  if (int rc = merkle_roots_args(who, depth, m, d_leaves, d_siblings, d_indices, d_roots)) return rc;
+  if (int rc = witness_aligned(who, {d_leaves, d_siblings, d_roots}, d_indices)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PoseidonSpec* s = find_poseidon(*ctx, handle);
+  if (!s) return hm_fail(HM_ERR_NOT_FOUND, std::string(who) + ": unknown spec handle");
+  return merkle_roots_run(*s, depth, m, (const uint32_t*)d_leaves, (const uint32_t*)d_siblings, d_indices, (uint32_t*)d_roots,
+                          (hipStream_t)stream);
+} HM_API_CATCH("hm_merkle_roots_bn256_dev")
+
+int hm_merkle_roots_bn256(uint64_t handle, uint32_t depth, size_t m, const uint64_t* leaves, const uint64_t* siblings,
+                          const uint64_t* indices, uint64_t* roots) try {
+  const char* who = "hm_merkle_roots_bn256";
+  if (int rc = merkle_roots_args(who, depth, m, leaves, siblings, indices, roots)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PoseidonSpec* s = find_poseidon(*ctx, handle);
+  if (!s) return hm_fail(HM_ERR_NOT_FOUND, std::string(who) + ": unknown spec handle");
+  if (m == 0) return HM_OK;
+  hm_fault_point("poseidon_upload");
+  const size_t elem_bytes = s->width == 5 ? 64 : 32;
+  const size_t leaf_bytes = m * elem_bytes, sib_bytes = leaf_bytes * depth, idx_bytes = (m * 8 + 15) / 16 * 16;
+  uint8_t* d_p = (uint8_t*)ctx->io.ensure(2 * leaf_bytes + sib_bytes + idx_bytes);
+  if (!d_p) return hm_fail(HM_ERR_HIP, std::string(who) + ": staging allocation failed");
+  uint8_t *d_sib = d_p + leaf_bytes, *d_idx = d_sib + sib_bytes, *d_roots = d_idx + idx_bytes;
+  int rc = xfer_h2d(*ctx, d_p, leaves, leaf_bytes, "hm_merkle_roots_bn256: upload");
+  if (rc == HM_OK) rc = xfer_h2d(*ctx, d_sib, siblings, sib_bytes, "hm_merkle_roots_bn256: upload");
+  if (rc == HM_OK) rc = xfer_h2d(*ctx, d_idx, indices, m * 8, "hm_merkle_roots_bn256: upload");
+  if (rc != HM_OK) return rc;
+  rc = merkle_roots_run(*s, depth, m, (const uint32_t*)d_p, (const uint32_t*)d_sib, (const uint64_t*)d_idx, (uint32_t*)d_roots, nullptr);
+  if (rc != HM_OK) return rc;
+  HM_HIP_CHECK(hipStreamSynchronize(nullptr));
+  hm_fault_point("poseidon_download");
+  if (xfer_d2h(*ctx, roots, d_roots, leaf_bytes, who) != HM_OK)
+    return hm_fail(HM_ERR_PARTIAL_OUTPUT, std::string(who) + ": copying the roots back failed, the output is partly written: " +
+                                              hm_last_error_string());
+  ctx->calls.h2d_bytes += leaf_bytes + sib_bytes + m * 8;
+  ctx->calls.d2h_bytes += leaf_bytes;
+  return HM_OK;
+} HM_API_CATCH("hm_merkle_roots_bn256")
+
 #ifdef HM_FAULT_INJECTION
 // test build only (libhalo2_mi355x_fi.so; not declared in the public header): the (after + 1)-th passage through the
 // named fault point throws std::runtime_error; point == NULL disarms

@@ -404,6 +404,13 @@ int poseidon_hash_run(const PoseidonSpec& s, const uint32_t* d_in, uint64_t in_s
 int merkle_build_run(const PoseidonSpec& s, uint32_t* d_nodes, uint32_t depth, hipStream_t stream);
 int merkle_paths_run(const uint32_t* d_nodes, uint32_t depth, uint32_t words_per_node, const uint64_t* d_indices, size_t m,
                      uint32_t* d_out, hipStream_t stream);
+// the built tree updated in place: entry p sets leaf d_indices[p] to element p of d_new_leaves, in array order (the last entry of an
+// index wins, an index >= 2^depth is dropped); d_counts: null, or depth + 1 words: live entries, nodes hashed at levels 1 .. depth
+int merkle_update_run(const PoseidonSpec& s, uint32_t* d_nodes, uint32_t depth, const uint64_t* d_indices, const uint32_t* d_new_leaves,
+                      size_t m, uint32_t* d_counts, hipStream_t stream);
+// the roots of m paths (siblings as merkle_paths_run writes them); the spec's width selects the elements per node
+int merkle_roots_run(const PoseidonSpec& s, uint32_t depth, size_t m, const uint32_t* d_leaves, const uint32_t* d_siblings,
+                     const uint64_t* d_indices, uint32_t* d_roots, hipStream_t stream);
 // The witnesses of the three circuits (poseidon.inc).  E, the elements per node, selects the circuit: 2 MerkleSumTree, 1 MerkleTreeV3,
 // 0 the Poseidon circuit (depth is ignored; its level_rows counts every row before the constants).
 // out = rows_used, n_advice, perm_rows, level_rows, lt_row (E = 2 only), const_row

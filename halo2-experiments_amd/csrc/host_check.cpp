@@ -7,8 +7,10 @@
 // and a restatement of its kernel's interpreter loop on these primitives.
 //
 // Build: g++ -O2 -std=c++17 -DHM_BOUNDS -shared -fPIC -o libhm_hostcheck.so host_check.cpp
+#include <algorithm>
 #include <cstring>
 #include <utility>
+#include <vector>
 
 #include "g1.h"
 #include "graph_lower.h"
@@ -573,6 +575,36 @@ int hc_poseidon_witness(const uint32_t* consts, uint32_t r_f, uint32_t r_p, uint
   WitnessArgs a;
   if (int rc = hc_witness_args(0, consts, r_f, r_p, 0, log_n, m, msgs, advice, instance, a)) return rc;
   for (size_t u = 0; u < m; ++u) poseidon_witness_lane(a, u);
+  return 0;
+}
+
+// The plan of a tree update (poseidon.inc: merkle_update_key / _owned / _count, the arithmetic its kernels run) on m host indices,
+// with std::sort in the place of the device's sorting network.  counts: depth + 1 words.
+int hc_merkle_update_plan(uint32_t depth, const uint64_t* indices, size_t m, uint32_t* counts) {
+  if (depth == 0 || depth > 30 || m > ((size_t)1 << 31)) return -1;
+  std::vector<uint64_t> keys(m);
+  for (size_t p = 0; p < m; ++p) keys[p] = merkle_update_key(indices[p], (uint32_t)p, depth);
+  std::sort(keys.begin(), keys.end());
+  uint32_t hist[MU_BINS] = {};
+  for (size_t p = 0; p < m; ++p) {
+    const uint32_t d = merkle_update_owned(p ? keys[p - 1] : 0, keys[p], p == 0, depth);
+    if (d >= MU_BINS) return -2;
+    if (d) ++hist[d];
+  }
+  for (uint32_t l = 0; l <= depth; ++l) counts[l] = merkle_update_count(hist, l);
+  return 0;
+}
+
+// the roots of m paths, lane by lane (merkle_root_lane<E>, the code of the roots kernel); width 5 -> E = 2, 3 -> E = 1
+int hc_merkle_roots(uint32_t width, const uint32_t* consts, uint32_t r_f, uint32_t r_p, uint32_t depth, size_t m, const uint32_t* leaves,
+                    const uint32_t* siblings, const uint64_t* indices, uint32_t* roots) {
+  if ((width != 3 && width != 5) || depth == 0 || depth > 30) return -1;
+  for (size_t u = 0; u < m; ++u) {
+    if (width == 5)
+      merkle_root_lane<2>(leaves, siblings, indices, depth, consts, r_f, r_p, u, roots);
+    else
+      merkle_root_lane<1>(leaves, siblings, indices, depth, consts, r_f, r_p, u, roots);
+  }
   return 0;
 }
 

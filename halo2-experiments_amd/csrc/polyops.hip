@@ -736,6 +736,72 @@ int merkle_paths_run(const uint32_t* d_nodes, uint32_t depth, uint32_t words_per
   return HM_OK;
 }
 
+int merkle_roots_run(const PoseidonSpec& s, uint32_t depth, size_t m, const uint32_t* d_leaves, const uint32_t* d_siblings,
+                     const uint64_t* d_indices, uint32_t* d_roots, hipStream_t stream) {
+  if (m == 0) return HM_OK;
+  hipLaunchKernelGGL(s.width == 5 ? merkle_roots_kernel<2> : merkle_roots_kernel<1>, dim3((unsigned)((m + PS_THREADS - 1) / PS_THREADS)),
+                     dim3(PS_THREADS), 0, stream, d_leaves, d_siblings, d_indices, depth, (uint64_t)m, s.d_consts, s.r_f, s.r_p, d_roots);
+  HM_HIP_CHECK(hipGetLastError());
+  return HM_OK;
+}
+
+static int merkle_update_sort(uint64_t* d_keys, uint64_t n_pow2, hipStream_t stream) {
+  if (n_pow2 < 2) return HM_OK;
+  const uint32_t tiles = (uint32_t)((n_pow2 + MU_TILE - 1) / MU_TILE);
+  const uint64_t in_tile = n_pow2 < MU_TILE ? n_pow2 : (uint64_t)MU_TILE;
+  hipLaunchKernelGGL(merkle_update_sort_tile_kernel, dim3(tiles), dim3(PS_THREADS), 0, stream, d_keys, n_pow2, (uint64_t)2, in_tile);
+  for (uint64_t k = (uint64_t)MU_TILE * 2; k <= n_pow2; k <<= 1) {
+    for (uint64_t j = k / 2; j >= MU_TILE; j >>= 1)
+      hipLaunchKernelGGL(merkle_update_sort_global_kernel, dim3((uint32_t)((n_pow2 / 2 + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0,
+                         stream, d_keys, n_pow2, k, j);
+    hipLaunchKernelGGL(merkle_update_sort_tile_kernel, dim3(tiles), dim3(PS_THREADS), 0, stream, d_keys, n_pow2, k, k);
+  }
+  HM_HIP_CHECK(hipGetLastError());
+  return HM_OK;
+}
+
+// The plan of poseidon.inc as launches: keys, sort, histogram, counts, scatter, then one launch per level over the owners of that
+// level.  Nothing comes back to the host: the grids are sized from min(m, 2^(depth - l)) and the lanes beyond the device-side count
+// return.  Scratch (the keys, the ordered indices, 3 x 32 counters) is stream-ordered, as the witness entry's `run` buffer is.
+static int merkle_update_launch(const PoseidonSpec& s, uint32_t* d_nodes, uint32_t depth, const uint64_t* d_indices,
+                                const uint32_t* d_new_leaves, size_t m, uint32_t* d_counts, uint8_t* ws, uint64_t n_pow2, size_t o_order,
+                                size_t o_small, hipStream_t stream) {
+  uint64_t* d_keys = (uint64_t*)ws;
+  uint32_t *d_order = (uint32_t*)(ws + o_order), *d_hist = (uint32_t*)(ws + o_small), *d_cursor = d_hist + MU_BINS, *d_cnt = d_cursor + MU_BINS;
+  const auto blocks = [](uint64_t lanes) { return dim3((unsigned)((lanes + PS_THREADS - 1) / PS_THREADS)); };
+  HM_HIP_CHECK(hipMemsetAsync(d_hist, 0, MU_BINS * sizeof(uint32_t), stream));
+  hipLaunchKernelGGL(merkle_update_keys_kernel, blocks(n_pow2), dim3(PS_THREADS), 0, stream, d_indices, (uint64_t)m, n_pow2, depth, d_keys);
+  if (int rc = merkle_update_sort(d_keys, n_pow2, stream)) return rc;
+  hipLaunchKernelGGL(merkle_update_hist_kernel, blocks(m), dim3(PS_THREADS), 0, stream, (const uint64_t*)d_keys, (uint64_t)m, depth, d_hist);
+  hipLaunchKernelGGL(merkle_update_plan_kernel, dim3(1), dim3(64), 0, stream, (const uint32_t*)d_hist, depth, d_cursor, d_cnt, d_counts);
+  hipLaunchKernelGGL(s.width == 5 ? merkle_update_scatter_kernel<2> : merkle_update_scatter_kernel<1>, blocks(m), dim3(PS_THREADS), 0, stream,
+                     (const uint64_t*)d_keys, (uint64_t)m, depth, d_cursor, d_order, d_new_leaves, d_nodes);
+  for (uint32_t l = 1; l <= depth; ++l) {
+    const uint64_t level = 1ull << (depth - l), lanes = m < level ? (uint64_t)m : level;
+    hipLaunchKernelGGL(s.width == 5 ? merkle_update_level_kernel<2> : merkle_update_level_kernel<1>, blocks(lanes), dim3(PS_THREADS), 0, stream,
+                       d_nodes, depth, l, (const uint32_t*)d_order, (const uint32_t*)d_cnt, s.d_consts, s.r_f, s.r_p);
+  }
+  HM_HIP_CHECK(hipGetLastError());
+  return HM_OK;
+}
+
+int merkle_update_run(const PoseidonSpec& s, uint32_t* d_nodes, uint32_t depth, const uint64_t* d_indices, const uint32_t* d_new_leaves,
+                      size_t m, uint32_t* d_counts, hipStream_t stream) {
+  if (m == 0) {
+    if (d_counts) HM_HIP_CHECK(hipMemsetAsync(d_counts, 0, (depth + 1) * sizeof(uint32_t), stream));
+    return HM_OK;
+  }
+  uint64_t n_pow2 = 1;
+  while (n_pow2 < m) n_pow2 <<= 1;
+  const size_t o_order = (size_t)n_pow2 * 8, o_small = o_order + ((size_t)m * 4 + 15) / 16 * 16;
+  void* ws = nullptr;
+  HM_HIP_CHECK(hipMallocAsync(&ws, o_small + 3 * MU_BINS * sizeof(uint32_t), stream));
+  int rc = merkle_update_launch(s, d_nodes, depth, d_indices, d_new_leaves, m, d_counts, (uint8_t*)ws, n_pow2, o_order, o_small, stream);
+  const hipError_t fe = hipFreeAsync(ws, stream);
+  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("merkle_update: hipFreeAsync: ") + hipGetErrorString(fe));
+  return rc;
+}
+
 // out = rows_used, n_advice, perm_rows, level_rows, lt_row, const_row
 void witness_rows(uint32_t E, uint32_t depth, uint32_t r_f, uint32_t r_p, uint32_t (&out)[6]) {
   const WitnessLayout w = witness_layout(E, depth, r_f, r_p);

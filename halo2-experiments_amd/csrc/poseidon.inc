@@ -348,6 +348,26 @@ HM_HD void pow5_hash_rows(uint32_t* state0, uint64_t col_words, const uint32_t (
   poseidon_permute<W>(s, consts, r_f, r_p, WitnessSink{state0 + 4 * 8, col_words});
 }
 
+// one level of a path folded upwards: node <- the parent of (node, sibling), `right` = node is the right child
+template <int E>
+HM_HD void merkle_fold_level(uint32_t (&node)[E][8], const uint32_t* sibling, bool right, const uint32_t* consts, uint32_t r_f,
+                             uint32_t r_p) {
+  uint32_t sib[E][8], kids[2 * E][8];
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    ps_get_words(sibling + e * 8, sib[e]);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      kids[e][i] = right ? sib[e][i] : node[e][i];
+      kids[E + e][i] = right ? node[e][i] : sib[e][i];
+    }
+  }
+  if constexpr (E == 2)
+    merkle_sum_node_one(kids, consts, r_f, r_p, node[0], node[1]);
+  else
+    poseidon_hash_one<3>(kids, consts, r_f, r_p, node[0]);
+}
+
 // the path's node after level l + 1, for l = 0 .. depth - 2, of user u: the chain that a built tree makes unnecessary
 template <int E>
 HM_HD void merkle_chain_lane(const WitnessArgs& a, uint64_t u, uint32_t* run) {
@@ -357,24 +377,55 @@ HM_HD void merkle_chain_lane(const WitnessArgs& a, uint64_t u, uint32_t* run) {
   const uint64_t idx = a.indices[u];
 #pragma unroll 1
   for (uint32_t l = 0; l + 1 < a.depth; ++l) {
-    uint32_t sib[E][8], kids[2 * E][8];
-    const bool right = (idx >> l) & 1ull;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      ps_get_words(a.siblings + ((u * a.depth + l) * E + e) * 8, sib[e]);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        kids[e][i] = right ? sib[e][i] : node[e][i];
-        kids[E + e][i] = right ? node[e][i] : sib[e][i];
-      }
-    }
-    if constexpr (E == 2)
-      merkle_sum_node_one(kids, a.consts, a.r_f, a.r_p, node[0], node[1]);
-    else
-      poseidon_hash_one<3>(kids, a.consts, a.r_f, a.r_p, node[0]);
+    merkle_fold_level<E>(node, a.siblings + (u * a.depth + l) * E * 8, (idx >> l) & 1ull, a.consts, a.r_f, a.r_p);
 #pragma unroll
     for (int e = 0; e < E; ++e) ps_put_words(run + ((u * (a.depth - 1) + l) * E + e) * 8, node[e]);
   }
+}
+
+// the same fold finished to the root (compute_merkle_sum_root for E = 2): path u of `depth` siblings in the layout the path kernel
+// writes -> E elements at roots + u * E * 8.  Bit l of the index = the node is the right child at level l; higher bits are ignored.
+template <int E>
+HM_HD void merkle_root_lane(const uint32_t* leaves, const uint32_t* siblings, const uint64_t* indices, uint32_t depth, const uint32_t* consts,
+                            uint32_t r_f, uint32_t r_p, uint64_t u, uint32_t* roots) {
+  uint32_t node[E][8];
+#pragma unroll
+  for (int e = 0; e < E; ++e) ps_get_words(leaves + (u * E + e) * 8, node[e]);
+  const uint64_t idx = indices[u];
+#pragma unroll 1
+  for (uint32_t l = 0; l < depth; ++l)
+    merkle_fold_level<E>(node, siblings + (u * depth + l) * E * 8, (idx >> l) & 1ull, consts, r_f, r_p);
+#pragma unroll
+  for (int e = 0; e < E; ++e) ps_put_words(roots + (u * E + e) * 8, node[e]);
+}
+
+// ---- updating a built tree in place (DESIGN.md section 15) ------------------------------------------------------------------------
+// m entries (leaf index, new leaf) applied in array order.  The plan, all of it a function of the indices alone:
+//   key      entry p -> (index << 32) | ~p, an index >= 2^depth -> MU_DROPPED; sorted ascending, the LAST entry of an index comes
+//            first in its run, and the dropped entries (and the padding of the sort, all ones) come last
+//   owned    the first entry of a run is live.  It owns its path's node at every level l < owned, where owned - 1 is the highest bit in
+//            which its index differs from the live entry before it (depth + 1 for the first): below that bit the two paths are
+//            apart, from it upwards they are one, and the earlier entry has the node.  0 = not live.
+//   counts   the entries ordered by `owned`, largest first (bins by a histogram; the order inside a bin is irrelevant): the owners
+//            of level l are the prefix of length counts[l] = sum of hist[d] over d > l -- one hash per distinct touched node.
+constexpr uint32_t MU_DROPPED = 0xffffffffu;
+constexpr uint32_t MU_BINS = 32;                 // owned <= depth + 1 <= 31
+HM_HD uint64_t merkle_update_key(uint64_t index, uint32_t pos, uint32_t depth) {
+  const uint32_t hi = index < (1ull << depth) ? (uint32_t)index : MU_DROPPED;
+  return ((uint64_t)hi << 32) | (uint32_t)~pos;
+}
+HM_HD uint32_t merkle_update_owned(uint64_t prev_key, uint64_t key, bool first, uint32_t depth) {
+  const uint32_t idx = (uint32_t)(key >> 32), prev = (uint32_t)(prev_key >> 32);
+  if (idx == MU_DROPPED) return 0;
+  if (first) return depth + 1;
+  const uint32_t x = idx ^ prev;
+  return x ? 32u - (uint32_t)__builtin_clz(x) : 0u;
+}
+// counts[l], l = 0 .. depth: the live entries (l = 0), the nodes hashed at level l; also where bin l of the ordered entries starts
+HM_HD uint32_t merkle_update_count(const uint32_t* hist, uint32_t l) {
+  uint32_t above = 0;
+  for (uint32_t d = l + 1; d < MU_BINS; ++d) above += hist[d];
+  return above;
 }
 
 // "enforce sum to be less than total assets" at row0 = word 0 of column a at the less-than row: a = the sum, b = the assets,
@@ -559,5 +610,143 @@ __global__ __launch_bounds__(PS_THREADS) void poseidon_witness_kernel(const Witn
   const uint64_t u = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
   if (u >= a.m) return;
   poseidon_witness_lane(a, u);
+}
+
+// one lane per path: depth hashes in sequence
+template <int E>
+__global__ __launch_bounds__(PS_THREADS) void merkle_roots_kernel(const uint32_t* __restrict__ leaves, const uint32_t* __restrict__ siblings,
+                                                                  const uint64_t* __restrict__ indices, uint32_t depth, uint64_t m,
+                                                                  const uint32_t* __restrict__ consts, uint32_t r_f, uint32_t r_p,
+                                                                  uint32_t* __restrict__ roots) {
+  const uint64_t u = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
+  if (u >= m) return;
+  merkle_root_lane<E>(leaves, siblings, indices, depth, consts, r_f, r_p, u, roots);
+}
+
+// ---- the update's launches (the plan above) ---------------------------------------------------------------------------------------
+// The sort is a bitonic network on the n_pow2 keys (m << 2^depth: it is not where the time goes): every stage with partner distance
+// below MU_TILE runs on a tile in LDS, the others are one launch each.
+constexpr uint32_t MU_TILE = 2048;               // keys per LDS tile: 16 KiB
+
+__global__ __launch_bounds__(PS_THREADS) void merkle_update_keys_kernel(const uint64_t* __restrict__ indices, uint64_t m, uint64_t n_pow2,
+                                                                        uint32_t depth, uint64_t* __restrict__ keys) {
+  const uint64_t t = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
+  if (t >= n_pow2) return;
+  keys[t] = t < m ? merkle_update_key(indices[t], (uint32_t)t, depth) : ~0ull;
+}
+
+// one compare-exchange stage with partner distance j >= MU_TILE of the phase of length k; one lane per pair
+__global__ __launch_bounds__(PS_THREADS) void merkle_update_sort_global_kernel(uint64_t* __restrict__ keys, uint64_t n, uint64_t k, uint64_t j) {
+  const uint64_t t = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
+  if (t >= n / 2) return;
+  const uint64_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+  const uint64_t a = keys[i], b = keys[l];
+  if (((i & k) == 0) ? a > b : a < b) {
+    keys[i] = b;
+    keys[l] = a;
+  }
+}
+
+// every stage with partner distance < MU_TILE of the phases k_first .. k_last (k_first = 2: the whole sort of a tile)
+__global__ __launch_bounds__(PS_THREADS) void merkle_update_sort_tile_kernel(uint64_t* __restrict__ keys, uint64_t n, uint64_t k_first,
+                                                                             uint64_t k_last) {
+  __shared__ uint64_t lds[MU_TILE];
+  const uint64_t base = (uint64_t)blockIdx.x * MU_TILE;
+  const uint32_t tile = n < MU_TILE ? (uint32_t)n : MU_TILE;
+  for (uint32_t e = threadIdx.x; e < tile; e += PS_THREADS) lds[e] = keys[base + e];
+  __syncthreads();
+  for (uint64_t k = k_first; k <= k_last; k <<= 1) {
+    for (uint32_t j = (uint32_t)(k / 2 < tile ? k / 2 : tile / 2); j > 0; j >>= 1) {
+      for (uint32_t t = threadIdx.x; t < tile / 2; t += PS_THREADS) {
+        const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+        const uint64_t a = lds[i], b = lds[l];
+        if ((((base + i) & k) == 0) ? a > b : a < b) {
+          lds[i] = b;
+          lds[l] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (uint32_t e = threadIdx.x; e < tile; e += PS_THREADS) keys[base + e] = lds[e];
+}
+
+// `owned` of the sorted entry p (positions >= m hold padding only)
+__device__ __forceinline__ uint32_t merkle_update_owned_at(const uint64_t* __restrict__ keys, uint64_t p, uint64_t m, uint32_t depth,
+                                                           uint64_t& key) {
+  if (p >= m) return 0;
+  key = keys[p];
+  return merkle_update_owned(p ? keys[p - 1] : 0, key, p == 0, depth);
+}
+
+// hist[d] = the entries with owned = d (a workgroup counts in LDS first)
+__global__ __launch_bounds__(PS_THREADS) void merkle_update_hist_kernel(const uint64_t* __restrict__ keys, uint64_t m, uint32_t depth,
+                                                                        uint32_t* __restrict__ hist) {
+  __shared__ uint32_t cnt[MU_BINS];
+  if (threadIdx.x < MU_BINS) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  uint64_t key = 0;
+  const uint32_t d = merkle_update_owned_at(keys, (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x, m, depth, key);
+  if (d) atomicAdd(&cnt[d], 1u);
+  __syncthreads();
+  if (threadIdx.x < MU_BINS && cnt[threadIdx.x]) atomicAdd(&hist[threadIdx.x], cnt[threadIdx.x]);
+}
+
+// the counts, which are the bins' first cursors as well (bin d starts where the entries that own more levels end), and the caller's copy
+__global__ __launch_bounds__(64) void merkle_update_plan_kernel(const uint32_t* __restrict__ hist, uint32_t depth, uint32_t* __restrict__ cursor,
+                                                                uint32_t* __restrict__ counts, uint32_t* __restrict__ counts_out) {
+  const uint32_t d = threadIdx.x;
+  if (d >= MU_BINS) return;
+  const uint32_t c = merkle_update_count(hist, d);
+  cursor[d] = c;
+  counts[d] = c;
+  if (counts_out && d <= depth) counts_out[d] = c;
+}
+
+// the live entries into their bins (order[] = their leaf indices) and their leaves into level 0
+template <int E>
+__global__ __launch_bounds__(PS_THREADS) void merkle_update_scatter_kernel(const uint64_t* __restrict__ keys, uint64_t m, uint32_t depth,
+                                                                           uint32_t* __restrict__ cursor, uint32_t* __restrict__ order,
+                                                                           const uint32_t* __restrict__ new_leaves,
+                                                                           uint32_t* __restrict__ nodes) {
+  __shared__ uint32_t cnt[MU_BINS], base[MU_BINS];
+  if (threadIdx.x < MU_BINS) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  uint64_t key = 0;
+  const uint32_t d = merkle_update_owned_at(keys, (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x, m, depth, key);
+  const uint32_t rank = d ? atomicAdd(&cnt[d], 1u) : 0u;
+  __syncthreads();
+  if (threadIdx.x < MU_BINS && cnt[threadIdx.x]) base[threadIdx.x] = atomicAdd(&cursor[threadIdx.x], cnt[threadIdx.x]);
+  __syncthreads();
+  if (!d) return;
+  const uint32_t idx = (uint32_t)(key >> 32), pos = ~(uint32_t)key;
+  order[base[d] + rank] = idx;
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    uint32_t w[8];
+    ps_load_words(new_leaves + ((uint64_t)pos * E + e) * 8, w);
+    ps_store_words(nodes + ((uint64_t)idx * E + e) * 8, w);
+  }
+}
+
+// level l: lane t < counts[l] hashes node (order[t] >> l) from its two children one level down
+template <int E>
+__global__ __launch_bounds__(PS_THREADS) void merkle_update_level_kernel(uint32_t* __restrict__ nodes, uint32_t depth, uint32_t l,
+                                                                         const uint32_t* __restrict__ order,
+                                                                         const uint32_t* __restrict__ counts,
+                                                                         const uint32_t* __restrict__ consts, uint32_t r_f, uint32_t r_p) {
+  const uint64_t t = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
+  if (t >= counts[l]) return;
+  const uint64_t node = order[t] >> l;
+  const uint64_t below = (2ull << depth) - (2ull << (depth - (l - 1))) + 2 * node, at = (2ull << depth) - (2ull << (depth - l)) + node;
+  uint32_t kids[2 * E][8], out[E][8];
+#pragma unroll
+  for (int j = 0; j < 2 * E; ++j) ps_load_words(nodes + below * E * 8 + j * 8, kids[j]);
+  if constexpr (E == 2)
+    merkle_sum_node_one(kids, consts, r_f, r_p, out[0], out[1]);
+  else
+    poseidon_hash_one<3>(kids, consts, r_f, r_p, out[0]);
+#pragma unroll
+  for (int e = 0; e < E; ++e) ps_store_words(nodes + (at * E + e) * 8, out[e]);
 }
 #endif

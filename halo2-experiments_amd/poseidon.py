@@ -246,6 +246,17 @@ def poseidon_hash_host(spec: Spec, msgs: np.ndarray) -> np.ndarray:
     return out
 
 
+# ---- the plan of a tree update ------------------------------------------------------------------------------------------------
+def update_plan(depth: int, indices) -> List[int]:
+    """What ``tree.update(indices, ...)`` does on a tree of ``depth``, as depth + 1 counts: the live entries (distinct indices inside
+    [0, 2^depth); an index outside is dropped), then the distinct touched nodes -- the hashes -- at levels 1 .. depth.  Pure host code; the
+    device produces the same numbers (``return_counts=True``).  The order of the entries and their repeats do not change the counts."""
+    if not 1 <= int(depth) <= 30:
+        raise ValueError("update_plan: depth must be 1 .. 30")
+    live = {int(i) for i in indices if 0 <= int(i) < (1 << depth)}
+    return [len({i >> l for i in live}) for l in range(depth + 1)]
+
+
 # ---- trees ------------------------------------------------------------------------------------------------------------------
 def _depth_of(n: int, who: str) -> int:
     if n < 2 or n & (n - 1):
@@ -303,6 +314,88 @@ class _Tree:
                                                        ctypes.cast(ctypes.c_void_p(d_idx.data_ptr()), ctypes.POINTER(ctypes.c_uint64)),
                                                        len(idx), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(_stream_ptr(self.nodes))))
         return to_host(out.reshape(-1, 4)).reshape(len(idx), self.depth, self.ELEMS, 4), idx
+
+
+    def update(self, indices, leaves, return_counts: bool = False):
+        """Set leaf ``indices[p]`` to ``leaves[p]`` for every p, in place on ``nodes``, so that the tree equals ``build`` of the changed
+        leaves: the entries count in array order (of a repeated index the last one lands) and only the nodes on their paths are hashed,
+        ``sum(update_plan(depth, indices)[1:])`` hashes in all.  indices: a sequence or numpy array (an index outside [0, 2^depth)
+        raises IndexError) or a GPU int64 tensor (such an index is dropped on the device); leaves: (m, ELEMS, 4) words, a GPU tensor or a
+        numpy array that is uploaded, not overlapping ``nodes``.  Asynchronous on the current stream; ``return_counts=True`` synchronises
+        and returns the device's depth + 1 counts (``update_plan``).  ``paths``, ``witness`` and ``root`` need no further step.
+
+        ``update`` never switches to a rebuild by itself.  It stays faster than ``build`` while the entries are a small share of the
+        leaves: the plan has ~m (depth - log2 m + 2) hashes for m scattered leaves against 2^depth, but sorts the m entries first
+        (DESIGN.md section 15 has the crossover); for m near 2^depth call ``build``."""
+        import torch
+
+        dev = self.nodes.device
+        if _is_tensor(indices):
+            if not indices.is_cuda or indices.dtype != torch.int64:
+                raise ValueError(f"{type(self).__name__}.update: an index tensor must be int64 on the GPU")
+            d_idx = indices.contiguous().reshape(-1)
+        else:
+            idx = [int(i) for i in np.asarray(indices).reshape(-1)] if isinstance(indices, np.ndarray) else [int(i) for i in indices]
+            if any(not 0 <= i < (1 << self.depth) for i in idx):
+                raise IndexError(f"{type(self).__name__}.update: a leaf index is outside [0, {1 << self.depth})")
+            d_idx = torch.tensor(idx, dtype=torch.int64, device=dev)
+        if not _is_tensor(leaves):
+            leaves = torch.from_numpy(_np(leaves, 4 * self.ELEMS, "leaves").view(np.int64)).to(dev)
+        m = _tensor_rows(leaves, 4 * self.ELEMS, "leaves")
+        if m != d_idx.numel():
+            raise ValueError(f"{type(self).__name__}.update: {d_idx.numel()} indices but {m} leaves")
+        counts = torch.zeros(self.depth + 1, dtype=torch.int32, device=dev) if return_counts else None
+        fn = _lib.load().hm_merkle_sum_tree_update_dev if self.WIDTH == 5 else _lib.load().hm_merkle_tree_update_dev
+        with torch.cuda.device(dev):
+            self.spec.call(fn, self.depth, ctypes.c_void_p(self.nodes.data_ptr()),
+                           ctypes.cast(ctypes.c_void_p(d_idx.data_ptr() if m else None), ctypes.POINTER(ctypes.c_uint64)),
+                           ctypes.c_void_p(leaves.data_ptr() if m else None), m,
+                           ctypes.cast(ctypes.c_void_p(counts.data_ptr() if return_counts else None), ctypes.POINTER(ctypes.c_uint32)),
+                           ctypes.c_void_p(_stream_ptr(self.nodes)))
+        if return_counts:
+            return [int(v) for v in counts.cpu().tolist()]
+        return None
+
+    @classmethod
+    def path_roots(cls, leaves, siblings, indices, spec: Optional[Spec] = None):
+        """The roots that m inclusion paths lead to, one GPU lane per path: leaves (m, ELEMS, 4) words, siblings (m, depth, ELEMS, 4) as
+        ``hm_merkle_paths_dev`` writes them, indices m integers (bit l = the path's node is the RIGHT child at level l; higher bits are
+        ignored) -> (m, ELEMS, 4) words; for the sum tree a root is (hash, balance), the balance summed mod r along the path
+        (``verify_path``).  GPU tensors give a GPU tensor, asynchronously on the current stream; numpy arrays go through the host form
+        and give a numpy array.  Comparing with an expected root is the caller's business."""
+        import torch
+
+        spec = default_spec(cls.WIDTH) if spec is None else spec
+        if spec.width != cls.WIDTH:
+            raise ValueError(f"{cls.__name__}: needs a width-{cls.WIDTH} spec")
+        lib, cols = _lib.load(), 4 * cls.ELEMS
+        if _is_tensor(leaves) != _is_tensor(siblings):
+            raise TypeError(f"{cls.__name__}.path_roots: leaves and siblings must both be GPU tensors or both numpy arrays")
+        if not _is_tensor(leaves):
+            lv, sb = _np(leaves, cols, "leaves"), _np(siblings, cols, "siblings")
+            m = lv.shape[0]
+            ix = np.ascontiguousarray(np.asarray(to_host(indices) if _is_tensor(indices) else indices).reshape(-1).astype(np.uint64))
+            if m == 0 or sb.shape[0] % m or ix.shape[0] != m:
+                raise ValueError(f"{cls.__name__}.path_roots: need m >= 1 leaves, m x depth siblings and m indices")
+            out = np.zeros((m, cls.ELEMS, 4), dtype=np.uint64)
+            spec.call(lib.hm_merkle_roots_bn256, sb.shape[0] // m, m, _ptr(lv), _ptr(sb), _ptr(ix), _ptr(out))
+            return out
+        m = _tensor_rows(leaves, cols, "leaves")
+        rows = _tensor_rows(siblings, cols, "siblings")
+        if _is_tensor(indices):
+            if not indices.is_cuda or indices.dtype != torch.int64:
+                raise ValueError(f"{cls.__name__}.path_roots: an index tensor must be int64 on the GPU")
+            d_idx = indices.contiguous().reshape(-1)
+        else:
+            d_idx = torch.from_numpy(np.asarray(indices).reshape(-1).astype(np.uint64).view(np.int64)).to(leaves.device)
+        if m == 0 or rows % m or d_idx.numel() != m:
+            raise ValueError(f"{cls.__name__}.path_roots: need m >= 1 leaves, m x depth siblings and m indices")
+        out = torch.empty((m, cls.ELEMS, 4), dtype=torch.int64, device=leaves.device)
+        with torch.cuda.device(leaves.device):
+            spec.call(lib.hm_merkle_roots_bn256_dev, rows // m, m, ctypes.c_void_p(leaves.data_ptr()), ctypes.c_void_p(siblings.data_ptr()),
+                      ctypes.cast(ctypes.c_void_p(d_idx.data_ptr()), ctypes.POINTER(ctypes.c_uint64)), ctypes.c_void_p(out.data_ptr()),
+                      ctypes.c_void_p(_stream_ptr(leaves)))
+        return out
 
 
 class MerkleSumTree(_Tree):

@@ -20,7 +20,7 @@ from .arithmetic import (bases_info, batch_invert, best_fft, best_multiexp, best
                          linear_combination, msm_stats, permute_expression_pair, permute_expression_pairs, random_fr, register_bases,
                          release_bases)
 from .domain import EvaluationDomain  # noqa: F401
-from .poseidon import MerkleSumTree, MerkleTree, Spec, poseidon_hash, poseidon_hash_host  # noqa: F401
+from .poseidon import MerkleSumTree, MerkleTree, Spec, poseidon_hash, poseidon_hash_host, update_plan  # noqa: F401
 from .synthesis import (MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, merkle_sum_witness,  # noqa: F401
                         merkle_sum_witness_host, merkle_witness, merkle_witness_host, permutation_columns, poseidon_circuit_witness,
                         poseidon_circuit_witness_host)
@@ -30,6 +30,6 @@ __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_mult
            "g1_decompress", "g1_decompress_host", "g1_check", "g1_check_host", "g_to_lagrange", "msm_stats", "kate_division", "kate_division_batch", "grand_product",
            "grand_product_batch", "batch_invert",
            "linear_combination", "random_fr", "permute_expression_pair", "permute_expression_pairs", "EvaluationDomain",
-           "Spec", "poseidon_hash", "poseidon_hash_host", "MerkleSumTree", "MerkleTree", "MerkleSumTreeLayout", "merkle_sum_witness",
+           "Spec", "poseidon_hash", "poseidon_hash_host", "update_plan", "MerkleSumTree", "MerkleTree", "MerkleSumTreeLayout", "merkle_sum_witness",
            "merkle_sum_witness_host", "permutation_columns", "MerkleTreeV3Layout", "PoseidonCircuitLayout", "merkle_witness",
            "merkle_witness_host", "poseidon_circuit_witness", "poseidon_circuit_witness_host"]

@@ -533,6 +533,29 @@ int hm_merkle_tree_build_dev(uint64_t handle, const void* d_leaves, uint32_t dep
  * words_per_node = elements per node (2 sum tree, 1 plain tree); d_indices is DEVICE memory; an index >= 2^depth yields zeros. */
 int hm_merkle_paths_dev(const void* d_nodes, uint32_t depth, uint32_t words_per_node, const uint64_t* d_indices, size_t m, void* d_out,
                         void* stream);
+/* A built tree updated in place, so that it equals the tree built from the changed leaves.  d_nodes: all 2^(depth+1) - 1 nodes as
+ * the build entries write them; d_indices m u64 and d_new_leaves m leaves (2 elements each for the sum tree, 1 for the plain tree),
+ * both DEVICE memory.  The result is as if the m entries were applied one after another in array order: of a repeated index the last
+ * entry wins; an index >= 2^depth is dropped.  Only the nodes on the paths of the surviving entries are written, one hash per
+ * distinct touched node.  Asynchronous on `stream`, nothing comes back to the host; scratch is the library's, stream-ordered.
+ * d_counts_or_null: depth + 1 u32 in DEVICE memory: the surviving entries, then the nodes hashed at levels 1 .. depth.
+ * HM_ERR_BAD_ARG: NULL with m > 0, depth 0 or above 30, m > 2^31, a handle of another width, a pointer not 16-byte aligned (8 for
+ * d_indices, 4 for the counts), d_new_leaves overlapping the nodes.  m = 0 writes nothing (zeros to the counts).  There is no host
+ * form: it would upload the whole tree to save part of building it. */
+int hm_merkle_sum_tree_update_dev(uint64_t handle, uint32_t depth, void* d_nodes, const uint64_t* d_indices, const void* d_new_leaves,
+                                  size_t m, uint32_t* d_counts_or_null, void* stream);
+int hm_merkle_tree_update_dev(uint64_t handle, uint32_t depth, void* d_nodes, const uint64_t* d_indices, const void* d_new_leaves,
+                              size_t m, uint32_t* d_counts_or_null, void* stream);
+/* The roots of m paths, one lane per path and depth hashes in sequence: leaves m x E elements, siblings m x depth x E elements as
+ * hm_merkle_paths_dev writes them, indices m u64 (bit l = the path's node is the RIGHT child at level l; higher bits are ignored)
+ * -> roots m x E elements.  The handle's width selects E: 5 -> 2, (hash, balance) with the balances summed mod r along the path
+ * (compute_merkle_sum_root); 3 -> 1.  Comparing with an expected root is the caller's business.  0 < depth <= 30, m <= 2^31; _dev:
+ * 16-byte aligned pointers (8 for d_indices), asynchronous on `stream`; the host form goes through the library's staging and
+ * writes `roots` only by its final copy. */
+int hm_merkle_roots_bn256_dev(uint64_t handle, uint32_t depth, size_t m, const void* d_leaves, const void* d_siblings,
+                              const uint64_t* d_indices, void* d_roots, void* stream);
+int hm_merkle_roots_bn256(uint64_t handle, uint32_t depth, size_t m, const uint64_t* leaves, const uint64_t* siblings,
+                          const uint64_t* indices, uint64_t* roots);
 /* The witness of the reference's MerkleSumTree circuit (one inclusion path per user), filled on the GPU: the advice columns as
  * MerkleSumTreeChip::synthesize assigns them, the Pow5 chip's trace of every Poseidon round among them.
  * layout: the rows and columns the call below fills for a spec with r_f / r_p rounds (r_p even); needs no device.  out_regions, unless
