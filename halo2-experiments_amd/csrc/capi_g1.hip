@@ -1,0 +1,114 @@
+// capi_g1.hip -- the G1 entry points of the C ABI outside the MSM: fixed-base multiples, best_fft over G1 (g1_fft.inc) and the SRS point
+// encodings (g1_codec.inc).
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "hm_internal.h"
+
+using namespace hm;
+
+extern "C" {
+
+int hm_g1_fixed_base_mul_dev(const void* d_scalars, size_t n, const uint64_t base_xy[8], void* d_out_xy, void* stream) try {
+  if ((n && (!d_scalars || !d_out_xy)) || !base_xy) return hm_fail(HM_ERR_BAD_ARG, "hm_g1_fixed_base_mul_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return g1_fixed_base_mul_run(*ctx, (const uint32_t*)d_scalars, n, base_xy, (uint32_t*)d_out_xy, (hipStream_t)stream);
+} HM_API_CATCH("hm_g1_fixed_base_mul_dev")
+
+int hm_g1_fft_bn256_dev(void* d_points_xy, const uint64_t omega[4], uint32_t log_n, const uint64_t* scale, void* stream) try {
+  if (!d_points_xy || !omega) return hm_fail(HM_ERR_BAD_ARG, "hm_g1_fft_bn256_dev: null argument");
+  if (log_n > 24) return hm_fail(HM_ERR_BAD_ARG, "hm_g1_fft_bn256_dev: log_n > 24");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return g1_fft_run(*ctx, (uint32_t*)d_points_xy, 16, omega, log_n, scale, (hipStream_t)stream);
+} HM_API_CATCH("hm_g1_fft_bn256_dev")
+
+int hm_g1_fft_bn256(uint64_t* points_xyz, const uint64_t omega[4], uint32_t log_n, const uint64_t* scale) try {
+  if (!points_xyz || !omega) return hm_fail(HM_ERR_BAD_ARG, "hm_g1_fft_bn256: null argument");
+  if (log_n > 24) return hm_fail(HM_ERR_BAD_ARG, "hm_g1_fft_bn256: log_n > 24");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const size_t bytes = ((size_t)96) << log_n;
+  const HostIn in{points_xyz, bytes, 0};
+  const HostOut out{points_xyz, bytes, 0, false};
+  return host_round_trip("hm_g1_fft_bn256", *ctx, "g1_fft", bytes, &in, 1, &out, 1,
+                         [&](uint8_t* d) { return g1_fft_run(*ctx, (uint32_t*)d, 24, omega, log_n, scale, nullptr); });
+} HM_API_CATCH("hm_g1_fft_bn256")
+
+// ---- SRS point encodings (g1_codec.inc) --------------------------------------------------------------------------------------
+static constexpr size_t G1_CODEC_MAX_N = (size_t)1 << 30;
+
+static int g1_codec_args(const char* who, size_t n, const void* in, const void* out, bool has_out, const uint64_t* first_invalid,
+                         bool has_flag) {
+  if ((n && (!in || (has_out && !out))) || (has_flag && !first_invalid)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (n > G1_CODEC_MAX_N) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": n > 2^30");
+  return HM_OK;
+}
+
+int hm_g1_compress_bn256_dev(const void* d_points_xy, size_t n, void* d_out32, void* stream) try {
+  if (int rc = g1_codec_args("hm_g1_compress_bn256_dev", n, d_points_xy, d_out32, true, nullptr, false)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return g1_compress_run((const uint32_t*)d_points_xy, n, (uint32_t*)d_out32, (hipStream_t)stream);
+} HM_API_CATCH("hm_g1_compress_bn256_dev")
+
+int hm_g1_decompress_bn256_dev(const void* d_in32, size_t n, void* d_points_xy, uint64_t* out_first_invalid, void* stream) try {
+  if (int rc = g1_codec_args("hm_g1_decompress_bn256_dev", n, d_in32, d_points_xy, true, out_first_invalid, true)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return g1_decompress_run((const uint32_t*)d_in32, n, (uint32_t*)d_points_xy, out_first_invalid, (hipStream_t)stream);
+} HM_API_CATCH("hm_g1_decompress_bn256_dev")
+
+int hm_g1_check_bn256_dev(const void* d_points_xy, size_t n, uint64_t* out_first_invalid, void* stream) try {
+  if (int rc = g1_codec_args("hm_g1_check_bn256_dev", n, d_points_xy, nullptr, false, out_first_invalid, true)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return g1_check_run((const uint32_t*)d_points_xy, n, out_first_invalid, (hipStream_t)stream);
+} HM_API_CATCH("hm_g1_check_bn256_dev")
+
+// Host forms: input and output share one staging buffer (input first); the caller's output is written only by the last copy.
+int hm_g1_compress_bn256(const uint64_t* points_xy, size_t n, uint8_t* out32) try {
+  if (int rc = g1_codec_args("hm_g1_compress_bn256", n, points_xy, out32, true, nullptr, false)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  if (n == 0) return HM_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const HostIn in{points_xy, n * 64, 0};
+  const HostOut out{out32, n * 32, n * 64, false};
+  return host_round_trip("hm_g1_compress_bn256", *ctx, "g1_codec", n * 96, &in, 1, &out, 1,
+                         [&](uint8_t* d) { return g1_compress_run((const uint32_t*)d, n, (uint32_t*)(d + n * 64), nullptr); });
+} HM_API_CATCH("hm_g1_compress_bn256")
+
+int hm_g1_decompress_bn256(const uint8_t* in32, size_t n, uint64_t* points_xy, uint64_t* out_first_invalid) try {
+  if (int rc = g1_codec_args("hm_g1_decompress_bn256", n, in32, points_xy, true, out_first_invalid, true)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  *out_first_invalid = n;
+  if (n == 0) return HM_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const HostIn in{in32, n * 32, 0};
+  const HostOut out{points_xy, n * 64, n * 32, false};
+  // HM_ERR_INVALID_DATA comes back from the launch: the caller's array is untouched
+  return host_round_trip("hm_g1_decompress_bn256", *ctx, "g1_codec", n * 96, &in, 1, &out, 1, [&](uint8_t* d) {
+    return g1_decompress_run((const uint32_t*)d, n, (uint32_t*)(d + n * 32), out_first_invalid, nullptr);
+  });
+} HM_API_CATCH("hm_g1_decompress_bn256")
+
+int hm_g1_check_bn256(const uint64_t* points_xy, size_t n, uint64_t* out_first_invalid) try {
+  if (int rc = g1_codec_args("hm_g1_check_bn256", n, points_xy, nullptr, false, out_first_invalid, true)) return rc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  *out_first_invalid = n;
+  if (n == 0) return HM_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const HostIn in{points_xy, n * 64, 0};
+  return host_round_trip("hm_g1_check_bn256", *ctx, "g1_codec", n * 64, &in, 1, nullptr, 0,
+                         [&](uint8_t* d) { return g1_check_run((const uint32_t*)d, n, out_first_invalid, nullptr); });
+} HM_API_CATCH("hm_g1_check_bn256")
+
+}  // extern "C"

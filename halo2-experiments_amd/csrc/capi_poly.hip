@@ -1,0 +1,704 @@
+// capi_poly.hip -- the field-side entry points of the C ABI: NTT and evaluation-domain forms, polynomial and vector steps, the lookup
+// argument's columns, the hm_graph_* programs and the quotient entry points.
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "hm_internal.h"
+#include "host_fr.h"
+
+using namespace hm;
+
+extern "C" {
+
+static void count_vector(DeviceCtx& ctx, int kind, uint64_t calls, uint64_t elements) {   // ctx.mu held
+  ctx.calls.vector_calls[kind] += calls;
+  ctx.calls.vector_elements[kind] += elements;
+}
+
+static void count_ntt(DeviceCtx& ctx, uint32_t log_n, size_t batch) {
+  ctx.calls.ntt_calls += batch;
+  ctx.calls.ntt_elements += (uint64_t)batch << log_n;
+  ctx.calls.ntt_by_log[log_n & 31] += batch;
+}
+// the three spans of a host form's round trip (host_round_trip)
+static void count_ntt_spans(DeviceCtx& ctx, const HostSpans& t) {
+  ctx.calls.ntt_h2d_us += t.h2d_us;
+  ctx.calls.ntt_device_us += t.device_us;
+  ctx.calls.ntt_d2h_us += t.d2h_us;
+}
+
+int hm_ntt_bn256_fr_dev(void* d_a, const uint64_t omega[4], uint32_t log_n, void* stream) try {
+  if (!d_a || !omega) return hm_fail(HM_ERR_BAD_ARG, "hm_ntt_bn256_fr_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const int rc = ntt_run(*ctx, (uint32_t*)d_a, omega, log_n, 1, NttFused{}, (hipStream_t)stream);
+  if (rc == HM_OK) count_ntt(*ctx, log_n, 1);
+  return rc;
+} HM_API_CATCH("hm_ntt_bn256_fr_dev")
+
+int hm_ntt_batch_bn256_fr_dev(void* d_a, size_t batch, const uint64_t omega[4], uint32_t log_n, const uint64_t* scale,
+                              const uint64_t* coset, void* stream) try {
+  if ((batch && !d_a) || !omega) return hm_fail(HM_ERR_BAD_ARG, "hm_ntt_batch_bn256_fr_dev: null argument");
+  if (batch > 65535) return hm_fail(HM_ERR_BAD_ARG, "hm_ntt_batch_bn256_fr_dev: batch > 65535");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  NttFused f;
+  f.scale = scale;
+  f.coset = coset;
+  const int rc = ntt_run(*ctx, (uint32_t*)d_a, omega, log_n, (uint32_t)batch, f, (hipStream_t)stream);
+  if (rc == HM_OK) count_ntt(*ctx, log_n, batch);
+  return rc;
+} HM_API_CATCH("hm_ntt_batch_bn256_fr_dev")
+
+// ctx->mu is held by the caller.  The zero part of the padded array is neither written nor read when the plan allows it.
+static int coeff_to_extended_locked(DeviceCtx* ctx, const void* d_coeffs, void* d_ext, size_t batch, const uint64_t extended_omega[4],
+                                    uint32_t log_n, uint32_t log_ext, const uint64_t* coset, void* stream) {
+  NttFused f;
+  f.coset = coset;
+  const uint32_t log_z = log_ext - log_n;
+  int passes = 0;
+  const int first_digit = ntt_plan_first_digit(log_ext, &passes);
+  int rc;
+  if (log_z > 0 && passes >= 2 && (int)log_z <= first_digit) {   // the zero part is never written or read
+    rc = ntt_run(*ctx, (uint32_t*)d_ext, extended_omega, log_ext, (uint32_t)batch, f, (hipStream_t)stream,
+                 (const uint32_t*)d_coeffs, log_z);
+  } else {
+    // small or un-extended domains: materialise the padded arrays, then the ordinary in-place transform
+    const size_t row_in = (size_t)32 << log_n, row_out = (size_t)32 << log_ext;
+    if (log_z) HM_HIP_CHECK(hipMemsetAsync(d_ext, 0, row_out * batch, (hipStream_t)stream));
+    HM_HIP_CHECK(hipMemcpy2DAsync(d_ext, row_out, d_coeffs, row_in, row_in, batch, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    rc = ntt_run(*ctx, (uint32_t*)d_ext, extended_omega, log_ext, (uint32_t)batch, f, (hipStream_t)stream);
+  }
+  if (rc == HM_OK) count_ntt(*ctx, log_ext, batch);
+  return rc;
+}
+
+int hm_coeff_to_extended_bn256_fr_dev(const void* d_coeffs, void* d_ext, size_t batch, const uint64_t extended_omega[4],
+                                      uint32_t log_n, uint32_t log_ext, const uint64_t* coset, void* stream) try {
+  if ((batch && (!d_coeffs || !d_ext)) || !extended_omega)
+    return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_extended_bn256_fr_dev: null argument");
+  if (log_ext < log_n || log_ext > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_extended_bn256_fr_dev: need log_n <= log_ext <= 28");
+  if (batch > 65535) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_extended_bn256_fr_dev: batch > 65535");
+  if (batch == 0) return HM_OK;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return coeff_to_extended_locked(ctx, d_coeffs, d_ext, batch, extended_omega, log_n, log_ext, coset, stream);
+} HM_API_CATCH("hm_coeff_to_extended_bn256_fr_dev")
+
+// Host-pointer forms of the two EvaluationDomain steps that cross PCIe in a drop-in prover: only what upstream's arrays really
+// hold travels -- the 2^log_n coefficients up (never the zero padding), the first `keep` coefficients down (never the part
+// extended_to_coeff truncates).
+int hm_coeff_to_extended_bn256_fr(const uint64_t* coeffs, uint64_t* ext, const uint64_t extended_omega[4], uint32_t log_n,
+                                  uint32_t log_ext, const uint64_t* coset) try {
+  if (!coeffs || !ext || !extended_omega) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_extended_bn256_fr: null argument");
+  if (log_ext < log_n || log_ext > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_extended_bn256_fr: need log_n <= log_ext <= 28");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const size_t bytes_in = (size_t)32 << log_n, bytes_out = (size_t)32 << log_ext;
+  // `ext` is written by the download alone (it may be the very allocation `coeffs` lives in: the input has been uploaded whole).  It is
+  // normally a FRESH allocation (the new Vec of the result): its first-touch page faults are taken by xfer_prefault's threads, under
+  // the transform, or by the lanes' copying threads.
+  const HostIn in{coeffs, bytes_in, bytes_out};
+  const HostOut out{ext, bytes_out, 0, false};
+  HostSpans t;
+  const int rc = host_round_trip("hm_coeff_to_extended_bn256_fr", *ctx, nullptr, bytes_out + bytes_in, &in, 1, &out, 1, [&](uint8_t* d) {
+    const int lrc = coeff_to_extended_locked(ctx, d + bytes_out, d, 1, extended_omega, log_n, log_ext, coset, nullptr);
+    if (lrc == HM_OK && xfer_mode(ext, bytes_out) == 0) xfer_prefault(ext, bytes_out);   // direct copies only
+    return lrc;
+  }, &t);
+  if (rc == HM_OK) count_ntt_spans(*ctx, t);
+  return rc;
+} HM_API_CATCH("hm_coeff_to_extended_bn256_fr")
+
+int hm_extended_to_coeff_bn256_fr(uint64_t* a, size_t keep, const uint64_t extended_omega_inv[4], uint32_t log_ext,
+                                  const uint64_t divisor[4], const uint64_t coset_inv[12]) try {
+  if (!a || !extended_omega_inv || !divisor || !coset_inv) return hm_fail(HM_ERR_BAD_ARG, "hm_extended_to_coeff_bn256_fr: null argument");
+  if (log_ext > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_extended_to_coeff_bn256_fr: log_ext > 28");
+  if (keep > ((size_t)1 << log_ext)) return hm_fail(HM_ERR_BAD_ARG, "hm_extended_to_coeff_bn256_fr: keep exceeds 2^log_ext");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const size_t bytes = (size_t)32 << log_ext;
+  NttFused f;
+  f.scale = divisor;
+  f.post3 = coset_inv;
+  const HostIn in{a, bytes, 0};
+  const HostOut out{a, keep * 32, 0, false};           // the part upstream truncates away is never downloaded
+  HostSpans t;
+  const int rc = host_round_trip("hm_extended_to_coeff_bn256_fr", *ctx, nullptr, bytes, &in, 1, &out, 1,
+                                 [&](uint8_t* d) { return ntt_run(*ctx, (uint32_t*)d, extended_omega_inv, log_ext, 1, f, nullptr); }, &t);
+  if (rc != HM_OK) return rc;
+  count_ntt(*ctx, log_ext, 1);
+  count_ntt_spans(*ctx, t);
+  return HM_OK;
+} HM_API_CATCH("hm_extended_to_coeff_bn256_fr")
+
+int hm_extended_to_coeff_bn256_fr_dev(void* d_a, size_t batch, const uint64_t extended_omega_inv[4], uint32_t log_ext,
+                                      const uint64_t divisor[4], const uint64_t coset_inv[12], void* stream) try {
+  if ((batch && !d_a) || !extended_omega_inv || !divisor || !coset_inv)
+    return hm_fail(HM_ERR_BAD_ARG, "hm_extended_to_coeff_bn256_fr_dev: null argument");
+  if (batch > 65535) return hm_fail(HM_ERR_BAD_ARG, "hm_extended_to_coeff_bn256_fr_dev: batch > 65535");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  NttFused f;
+  f.scale = divisor;
+  f.post3 = coset_inv;
+  const int rc = ntt_run(*ctx, (uint32_t*)d_a, extended_omega_inv, log_ext, (uint32_t)batch, f, (hipStream_t)stream);
+  if (rc == HM_OK) count_ntt(*ctx, log_ext, batch);
+  return rc;
+} HM_API_CATCH("hm_extended_to_coeff_bn256_fr_dev")
+
+int hm_coeff_to_coset_bn256_fr_dev(const void* d_coeffs, void* d_out, size_t batch, const uint64_t omega[4], uint32_t log_n,
+                                   const uint64_t shift[4], int columns_internal, void* stream) try {
+  if ((batch && (!d_coeffs || !d_out)) || !omega || !shift) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_coset_bn256_fr_dev: null argument");
+  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_coset_bn256_fr_dev: log_n > 28");
+  if (batch > 65535) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_coset_bn256_fr_dev: batch > 65535");
+  if (batch == 0) return HM_OK;
+  if (d_coeffs != d_out) {
+    const size_t bytes = ((size_t)32 << log_n) * batch;
+    const char *a = (const char*)d_coeffs, *b = (const char*)d_out;
+    if (a < b + bytes && b < a + bytes)
+      return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_coset_bn256_fr_dev: output partially overlaps the coefficients");
+  }
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const int rc = ntt_coset_run(*ctx, (const uint32_t*)d_coeffs, (uint32_t*)d_out, (uint32_t)batch, omega, log_n, shift, columns_internal != 0,
+                               (hipStream_t)stream);
+  if (rc == HM_OK) count_ntt(*ctx, log_n, batch);
+  return rc;
+} HM_API_CATCH("hm_coeff_to_coset_bn256_fr_dev")
+
+int hm_coeff_to_cosets_bn256_fr_dev(const void* d_coeffs, void* d_out, size_t batch, const uint64_t omega[4], uint32_t log_n,
+                                    const uint64_t* shifts, size_t count, int columns_internal, void* stream) try {
+  if ((batch && count && (!d_coeffs || !d_out)) || !omega || (count && !shifts))
+    return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_cosets_bn256_fr_dev: null argument");
+  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_cosets_bn256_fr_dev: log_n > 28");
+  if (count > 16) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_cosets_bn256_fr_dev: at most 16 cosets per call");
+  if (batch * (count ? count : 1) > 65535) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_cosets_bn256_fr_dev: batch * count > 65535");
+  if (batch == 0 || count == 0) return HM_OK;
+  {
+    const size_t in_bytes = ((size_t)32 << log_n) * batch, out_bytes = in_bytes * count;
+    const char *a = (const char*)d_coeffs, *b = (const char*)d_out;
+    if (a < b + out_bytes && b < a + in_bytes)
+      return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_cosets_bn256_fr_dev: the output overlaps the coefficients");
+  }
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const int rc = ntt_cosets_run(*ctx, (const uint32_t*)d_coeffs, (uint32_t*)d_out, (uint32_t)batch, omega, log_n, shifts, (uint32_t)count,
+                                columns_internal != 0, (hipStream_t)stream);
+  if (rc == HM_OK) count_ntt(*ctx, log_n, batch * count);
+  return rc;
+} HM_API_CATCH("hm_coeff_to_cosets_bn256_fr_dev")
+
+int hm_cosets_to_coeff_bn256_fr_dev(void* d_a, size_t count, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4],
+                                    const uint64_t* shift_invs, void* stream) try {
+  if ((count && (!d_a || !shift_invs)) || !omega_inv || !divisor) return hm_fail(HM_ERR_BAD_ARG, "hm_cosets_to_coeff_bn256_fr_dev: null argument");
+  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_cosets_to_coeff_bn256_fr_dev: log_n > 28");
+  if (count > 16) return hm_fail(HM_ERR_BAD_ARG, "hm_cosets_to_coeff_bn256_fr_dev: at most 16 cosets per call");
+  if (count == 0) return HM_OK;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const int rc = ntt_cosets_inverse_run(*ctx, (uint32_t*)d_a, (uint32_t)count, omega_inv, log_n, divisor, shift_invs, (hipStream_t)stream);
+  if (rc == HM_OK) count_ntt(*ctx, log_n, count);
+  return rc;
+} HM_API_CATCH("hm_cosets_to_coeff_bn256_fr_dev")
+
+int hm_coset_to_coeff_bn256_fr_dev(void* d_a, size_t batch, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4],
+                                   const uint64_t shift_inv[4], void* stream) try {
+  if ((batch && !d_a) || !omega_inv || !divisor || !shift_inv) return hm_fail(HM_ERR_BAD_ARG, "hm_coset_to_coeff_bn256_fr_dev: null argument");
+  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_coset_to_coeff_bn256_fr_dev: log_n > 28");
+  if (batch > 65535) return hm_fail(HM_ERR_BAD_ARG, "hm_coset_to_coeff_bn256_fr_dev: batch > 65535");
+  if (batch == 0) return HM_OK;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const int rc = ntt_coset_inverse_run(*ctx, (uint32_t*)d_a, (uint32_t)batch, omega_inv, log_n, divisor, shift_inv, (hipStream_t)stream);
+  if (rc == HM_OK) count_ntt(*ctx, log_n, batch);
+  return rc;
+} HM_API_CATCH("hm_coset_to_coeff_bn256_fr_dev")
+
+int hm_ntt_bn256_fr(uint64_t* a, const uint64_t omega[4], uint32_t log_n) try {
+  if (!a || !omega) return hm_fail(HM_ERR_BAD_ARG, "hm_ntt_bn256_fr: null argument");
+  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_ntt_bn256_fr: log_n > 28");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const size_t bytes = ((size_t)32) << log_n;
+  const HostIn in{a, bytes, 0};
+  const HostOut out{a, bytes, 0, false};
+  HostSpans t;
+  const int rc = host_round_trip("hm_ntt_bn256_fr", *ctx, nullptr, bytes, &in, 1, &out, 1,
+                                 [&](uint8_t* d) { return ntt_run(*ctx, (uint32_t*)d, omega, log_n, 1, NttFused{}, nullptr); }, &t);
+  if (rc != HM_OK) return rc;
+  count_ntt(*ctx, log_n, 1);
+  count_ntt_spans(*ctx, t);
+  return HM_OK;
+} HM_API_CATCH("hm_ntt_bn256_fr")
+
+int hm_ifft_bn256_fr_dev(void* d_a, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4], void* stream) try {
+  if (!d_a || !omega_inv || !divisor) return hm_fail(HM_ERR_BAD_ARG, "hm_ifft_bn256_fr_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  NttFused f;
+  f.scale = divisor;
+  const int rc = ntt_run(*ctx, (uint32_t*)d_a, omega_inv, log_n, 1, f, (hipStream_t)stream);
+  if (rc == HM_OK) count_ntt(*ctx, log_n, 1);
+  return rc;
+} HM_API_CATCH("hm_ifft_bn256_fr_dev")
+
+int hm_coset_ntt_bn256_fr_dev(void* d_a, const uint64_t omega[4], uint32_t log_n, const uint64_t coset[12], void* stream) try {
+  if (!d_a || !omega || !coset) return hm_fail(HM_ERR_BAD_ARG, "hm_coset_ntt_bn256_fr_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  NttFused f;
+  f.coset = coset;
+  const int rc = ntt_run(*ctx, (uint32_t*)d_a, omega, log_n, 1, f, (hipStream_t)stream);
+  if (rc == HM_OK) count_ntt(*ctx, log_n, 1);
+  return rc;
+} HM_API_CATCH("hm_coset_ntt_bn256_fr_dev")
+
+int hm_eval_polynomial_bn256_fr_dev(const void* d_polys, size_t n, const uint32_t* poly_index, const uint64_t* points, size_t count,
+                                    uint64_t* out, void* stream) try {
+  if ((count && (!points || !out)) || (count && n && !d_polys))
+    return hm_fail(HM_ERR_BAD_ARG, "hm_eval_polynomial_bn256_fr_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  count_vector(*ctx, HM_STAT_EVAL_POLYNOMIAL, count, (uint64_t)count * n);
+  return fr_eval_polynomial_run(*ctx, (const uint32_t*)d_polys, n, poly_index, points, count, out, (hipStream_t)stream);
+} HM_API_CATCH("hm_eval_polynomial_bn256_fr_dev")
+
+int hm_kate_division_bn256_fr_dev(const void* d_poly, size_t n, const uint64_t z[4], void* d_quotient, void* stream) try {
+  if (!z || (n >= 2 && (!d_poly || !d_quotient))) return hm_fail(HM_ERR_BAD_ARG, "hm_kate_division_bn256_fr_dev: null argument");
+  if (n >= 2) {
+    const char *a = (const char*)d_poly, *q = (const char*)d_quotient;
+    if (q < a + n * 32 && a < q + (n - 1) * 32)
+      return hm_fail(HM_ERR_BAD_ARG, "hm_kate_division_bn256_fr_dev: quotient overlaps the polynomial");
+  }
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  count_vector(*ctx, HM_STAT_KATE_DIVISION, 1, n);
+  return fr_kate_division_run(*ctx, (const uint32_t*)d_poly, n, z, (uint32_t*)d_quotient, (hipStream_t)stream);
+} HM_API_CATCH("hm_kate_division_bn256_fr_dev")
+
+int hm_fr_grand_product_dev(const void* d_factors, size_t n, const uint64_t start[4], void* d_out, void* stream) try {
+  if (!start || (n && (!d_factors || !d_out))) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_grand_product_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  count_vector(*ctx, HM_STAT_GRAND_PRODUCT, 1, n);
+  return fr_grand_product_run(*ctx, (const uint32_t*)d_factors, n, start, (uint32_t*)d_out, (hipStream_t)stream);
+} HM_API_CATCH("hm_fr_grand_product_dev")
+
+int hm_kate_division_batch_bn256_fr_dev(const void* const* d_polys, size_t n, const uint64_t* z, void* const* d_quotients, size_t count,
+                                        void* stream) try {
+  if (count == 0) return HM_OK;
+  if (!z || !d_polys || !d_quotients) return hm_fail(HM_ERR_BAD_ARG, "hm_kate_division_batch_bn256_fr_dev: null argument");
+  if (n >= 2) {
+    for (size_t j = 0; j < count; ++j)
+      if (!d_polys[j] || !d_quotients[j]) return hm_fail(HM_ERR_BAD_ARG, "hm_kate_division_batch_bn256_fr_dev: null device pointer");
+    for (size_t j = 0; j < count; ++j)
+      for (size_t i = 0; i < count; ++i)
+        if (ranges_overlap(d_quotients[j], (n - 1) * 32, d_polys[i], n * 32) ||
+            (i != j && ranges_overlap(d_quotients[j], (n - 1) * 32, d_quotients[i], (n - 1) * 32)))
+          return hm_fail(HM_ERR_BAD_ARG, "hm_kate_division_batch_bn256_fr_dev: a quotient overlaps another array of the call");
+  }
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  count_vector(*ctx, HM_STAT_KATE_DIVISION, count, (uint64_t)count * n);
+  return fr_kate_division_batch_run(*ctx, d_polys, n, z, d_quotients, count, (hipStream_t)stream);
+} HM_API_CATCH("hm_kate_division_batch_bn256_fr_dev")
+
+int hm_fr_grand_product_batch_dev(const void* const* d_factors, size_t n, const uint64_t start[4], size_t chain_row, void* const* d_out,
+                                  size_t count, void* stream) try {
+  if (count == 0) return HM_OK;
+  if (!start || !d_factors || !d_out) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_grand_product_batch_dev: null argument");
+  if (n) {
+    for (size_t j = 0; j < count; ++j)
+      if (!d_factors[j] || !d_out[j]) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_grand_product_batch_dev: null device pointer");
+    for (size_t j = 0; j < count; ++j)
+      for (size_t i = 0; i < count; ++i)
+        if (i != j && (ranges_overlap(d_out[j], n * 32, d_factors[i], n * 32) || ranges_overlap(d_out[j], n * 32, d_out[i], n * 32)))
+          return hm_fail(HM_ERR_BAD_ARG, "hm_fr_grand_product_batch_dev: an output overlaps another column of the call");
+    for (size_t j = 0; j < count; ++j)
+      if (d_out[j] != d_factors[j] && ranges_overlap(d_out[j], n * 32, d_factors[j], n * 32))
+        return hm_fail(HM_ERR_BAD_ARG, "hm_fr_grand_product_batch_dev: an output partially overlaps its factors");
+  }
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  count_vector(*ctx, HM_STAT_GRAND_PRODUCT, count, (uint64_t)count * n);
+  return fr_grand_product_batch_run(*ctx, d_factors, n, start, chain_row < n ? chain_row : n, d_out, count, (hipStream_t)stream);
+} HM_API_CATCH("hm_fr_grand_product_batch_dev")
+
+int hm_fr_batch_invert_dev(void* d_values, size_t n, void* stream) try {
+  if (n && !d_values) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_batch_invert_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    count_vector(*ctx, HM_STAT_BATCH_INVERT, 1, n);
+  }
+  return fr_batch_invert_run((uint32_t*)d_values, n, (hipStream_t)stream);
+} HM_API_CATCH("hm_fr_batch_invert_dev")
+
+int hm_fr_linear_combination_dev(const void* const* d_polys, const uint64_t* coeffs, size_t count, size_t n, void* d_out,
+                                 void* stream) try {
+  if ((n && !d_out) || (count && (!d_polys || !coeffs))) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_linear_combination_dev: null argument");
+  if (n)
+    for (size_t j = 0; j < count; ++j)
+      if (!d_polys[j]) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_linear_combination_dev: null polynomial");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    count_vector(*ctx, HM_STAT_LINEAR_COMBINATION, 1, (uint64_t)count * n);
+  }
+  return fr_linear_combination_run(d_polys, coeffs, count, n, (uint32_t*)d_out, (hipStream_t)stream);
+} HM_API_CATCH("hm_fr_linear_combination_dev")
+
+int hm_lookup_permute_bn256_fr_dev(const void* d_input, const void* d_table, size_t rows, void* d_permuted_input,
+                                   void* d_permuted_table, void* stream) try {
+  if (rows && (!d_input || !d_table || !d_permuted_input || !d_permuted_table))
+    return hm_fail(HM_ERR_BAD_ARG, "hm_lookup_permute_bn256_fr_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  count_vector(*ctx, HM_STAT_LOOKUP_PERMUTE, 1, rows);
+  return lookup_permute_run(*ctx, &d_input, &d_table, 1, rows, &d_permuted_input, &d_permuted_table, nullptr, (hipStream_t)stream);
+} HM_API_CATCH("hm_lookup_permute_bn256_fr_dev")
+
+int hm_lookup_permute_batch_bn256_fr_dev(const void* const* d_inputs, const void* const* d_tables, size_t count, size_t rows,
+                                         void* const* d_permuted_inputs, void* const* d_permuted_tables, int* missing, void* stream) try {
+  if (count && (!d_inputs || !d_tables || !d_permuted_inputs || !d_permuted_tables))
+    return hm_fail(HM_ERR_BAD_ARG, "hm_lookup_permute_batch_bn256_fr_dev: null argument");
+  if (rows)
+    for (size_t p = 0; p < count; ++p)
+      if (!d_inputs[p] || !d_tables[p] || !d_permuted_inputs[p] || !d_permuted_tables[p])
+        return hm_fail(HM_ERR_BAD_ARG, "hm_lookup_permute_batch_bn256_fr_dev: null column");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  count_vector(*ctx, HM_STAT_LOOKUP_PERMUTE, count, (uint64_t)count * rows);
+  return lookup_permute_run(*ctx, d_inputs, d_tables, count, rows, d_permuted_inputs, d_permuted_tables, missing, (hipStream_t)stream);
+} HM_API_CATCH("hm_lookup_permute_batch_bn256_fr_dev")
+
+int hm_fr_mul_periodic_dev(void* d_a, size_t n, const uint64_t* pattern, uint32_t period, void* stream) try {
+  if ((n && !d_a) || !pattern) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_mul_periodic_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return fr_mul_periodic_run((uint32_t*)d_a, n, pattern, period, (hipStream_t)stream);
+} HM_API_CATCH("hm_fr_mul_periodic_dev")
+
+int hm_fr_powers_dev(void* d_out, size_t n, const uint64_t x[4], void* stream) try {
+  if ((n && !d_out) || !x) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_powers_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return fr_powers_run((uint32_t*)d_out, n, x, (hipStream_t)stream);
+} HM_API_CATCH("hm_fr_powers_dev")
+
+int hm_graph_create(const uint32_t* calcs, size_t n_calc, const uint64_t* constants, size_t n_const, size_t n_dynamic,
+                    const int32_t* rotations, size_t n_rot, size_t n_columns, uint32_t n_intermediates, uint64_t* out_handle) try {
+  if (!out_handle || (n_calc && !calcs) || (n_const && !constants) || (n_rot && !rotations))
+    return hm_fail(HM_ERR_BAD_ARG, "hm_graph_create: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return graph_create(*ctx, calcs, n_calc, constants, n_const, n_dynamic, rotations, n_rot, n_columns, n_intermediates, out_handle);
+} HM_API_CATCH("hm_graph_create")
+
+static int graph_evaluate_entry(const char* who, uint64_t handle, const void* const* d_columns, size_t n_columns,
+                                const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t log_size, uint32_t segments, void* d_values,
+                                uint32_t flags, void* stream) {
+  if (!d_values || (n_columns && !d_columns) || (n_dynamic && !dynamic_constants))
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  for (auto& g : ctx->graphs)
+    if (g->handle == handle) {
+      count_vector(*ctx, HM_STAT_GRAPH_EVALUATE, 1, log_size < 40 ? (uint64_t)segments << log_size : 0);
+      return graph_evaluate(*ctx, *g, d_columns, n_columns, dynamic_constants, n_dynamic, log_size, segments, d_values, flags,
+                            (hipStream_t)stream);
+    }
+  return hm_fail(HM_ERR_NOT_FOUND, std::string(who) + ": unknown program handle");
+}
+
+int hm_graph_evaluate_dev(uint64_t handle, const void* const* d_columns, size_t n_columns, const uint64_t* dynamic_constants,
+                          size_t n_dynamic, uint32_t log_size, void* d_values, void* stream) try {
+  return graph_evaluate_entry("hm_graph_evaluate_dev", handle, d_columns, n_columns, dynamic_constants, n_dynamic, log_size, 1, d_values, 0, stream);
+} HM_API_CATCH("hm_graph_evaluate_dev")
+
+int hm_graph_evaluate_flags_dev(uint64_t handle, const void* const* d_columns, size_t n_columns, const uint64_t* dynamic_constants,
+                                size_t n_dynamic, uint32_t log_size, void* d_values, uint32_t flags, void* stream) try {
+  return graph_evaluate_entry("hm_graph_evaluate_flags_dev", handle, d_columns, n_columns, dynamic_constants, n_dynamic, log_size, 1, d_values,
+                              flags, stream);
+} HM_API_CATCH("hm_graph_evaluate_flags_dev")
+
+int hm_graph_evaluate_segments_dev(uint64_t handle, const void* const* d_columns, size_t n_columns, const uint64_t* dynamic_constants,
+                                   size_t n_dynamic, uint32_t log_segment, uint32_t segments, void* d_values, uint32_t flags, void* stream) try {
+  return graph_evaluate_entry("hm_graph_evaluate_segments_dev", handle, d_columns, n_columns, dynamic_constants, n_dynamic, log_segment,
+                              segments, d_values, flags, stream);
+} HM_API_CATCH("hm_graph_evaluate_segments_dev")
+
+// ---------------------------------------------------------------------------------------------
+// The quotient h(X) of a proof in ONE call, from coefficient arrays: every column onto `count` cosets of the n-th roots
+// (hm_coeff_to_cosets), the numerator program over count segments of n rows (hm_graph_evaluate_segments), the inverse
+// transforms (hm_cosets_to_coeff), and the recombination with the vanishing division on its matrix -- what upstream's
+// evaluate_h + divide_by_vanishing_poly + extended_to_coeff make of the extended arrays.
+// ---------------------------------------------------------------------------------------------
+// host side of the recombination: u_c = shift_c^n, V^-1 (Gauss-Jordan) with 1 / (u_c - 1) on column c -> rows of 4 * count words
+static int quotient_matrix(const char* who, const uint64_t* shifts, size_t count, uint32_t log_n, std::vector<std::vector<uint64_t>>* rows) {
+  std::vector<host::Fr4> u(count);
+  for (size_t c = 0; c < count; ++c) {
+    host::Fr4 x = host::fr_load(shifts + 4 * c);
+    if (host::fr_is_zero(x)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a coset shift is zero");
+    for (uint32_t b = 0; b < log_n; ++b) x = host::fr_mul(x, x);
+    u[c] = x;
+    if (host::fr_eq(u[c], host::FR_ONE)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a coset lies in the n-th roots (X^n - 1 vanishes on it)");
+    for (size_t b = 0; b < c; ++b)
+      if (host::fr_eq(u[b], u[c])) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": two shifts name the same coset");
+  }
+  const host::Fr4 zero = {{0, 0, 0, 0}};
+  std::vector<std::vector<host::Fr4>> m(count, std::vector<host::Fr4>(2 * count, zero));      // [V | I] -> [I | V^-1]
+  for (size_t a = 0; a < count; ++a) {
+    host::Fr4 p = host::FR_ONE;
+    for (size_t t = 0; t < count; ++t) { m[a][t] = p; p = host::fr_mul(p, u[a]); }
+    m[a][count + a] = host::FR_ONE;
+  }
+  for (size_t col = 0; col < count; ++col) {
+    size_t piv = col;
+    while (piv < count && host::fr_is_zero(m[piv][col])) ++piv;
+    if (piv == count) return hm_fail(HM_ERR_INTERNAL, std::string(who) + ": singular coset matrix");
+    std::swap(m[col], m[piv]);
+    const host::Fr4 inv = host::fr_inv(m[col][col]);
+    for (auto& v : m[col]) v = host::fr_mul(v, inv);
+    for (size_t row = 0; row < count; ++row) {
+      if (row == col || host::fr_is_zero(m[row][col])) continue;
+      const host::Fr4 f = m[row][col];
+      for (size_t c2 = 0; c2 < 2 * count; ++c2) m[row][c2] = host::fr_sub(m[row][c2], host::fr_mul(f, m[col][c2]));
+    }
+  }
+  rows->assign(count, std::vector<uint64_t>(4 * count));
+  for (size_t c = 0; c < count; ++c) {
+    const host::Fr4 tinv = host::fr_inv(host::fr_sub(u[c], host::FR_ONE));
+    for (size_t t = 0; t < count; ++t) {
+      const host::Fr4 v = host::fr_mul(m[t][count + c], tinv);
+      std::memcpy(&(*rows)[t][4 * c], v.l, 32);
+    }
+  }
+  return HM_OK;
+}
+
+// steps 1 - 3 on this device: the columns onto `count` cosets, the numerator over count segments, the inverse transforms ->
+// d_partials (count x n).  ctx.mu held.
+static int quotient_partials(const char* who, DeviceCtx& ctx, uint64_t program, const void* const* d_coeff_columns, const void* const* d_on_cosets,
+                             size_t n_columns, const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t log_n, const uint64_t omega[4],
+                             const uint64_t* shifts, size_t count, void* d_partials, hipStream_t st) {
+  std::vector<size_t> todo;
+  for (size_t i = 0; i < n_columns; ++i) {
+    if (d_on_cosets && d_on_cosets[i]) continue;
+    if (!d_coeff_columns || !d_coeff_columns[i]) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a column has neither coefficients nor coset values");
+    todo.push_back(i);
+  }
+  const uint64_t n = 1ull << log_n;
+  std::vector<host::Fr4> shift_inv(count);
+  for (size_t c = 0; c < count; ++c) {
+    const host::Fr4 x = host::fr_load(shifts + 4 * c);
+    if (host::fr_is_zero(x)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a coset shift is zero");
+    shift_inv[c] = host::fr_inv(x);
+  }
+  const host::Fr4 zero = {{0, 0, 0, 0}};
+  host::Fr4 nn = host::FR_ONE;                                               // n = 2^log_n in Montgomery form: 1 doubled log_n times
+  for (uint32_t b = 0; b < log_n; ++b) nn = host::fr_sub(nn, host::fr_sub(zero, nn));
+  const host::Fr4 n_inv = host::fr_inv(nn);
+  const host::Fr4 om_inv = host::fr_inv(host::fr_load(omega));
+  GraphProgram* g = nullptr;
+  for (auto& gp : ctx.graphs)
+    if (gp->handle == program) g = gp.get();
+  if (!g) return hm_fail(HM_ERR_NOT_FOUND, std::string(who) + ": unknown program handle");
+  if (n_columns != g->n_columns) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the program was built for another number of columns");
+  AuxSlot* slot = aux_acquire(ctx, st);
+  if (!slot) return HM_ERR_HIP;
+  // work: [the columns to transform, side by side: T x n] [those columns on the cosets: T x count x n]
+  const size_t row = (size_t)n * 32;
+  const size_t T = todo.size();
+  uint8_t* work = (uint8_t*)slot->work.ensure(row * (T + T * count) + 32);
+  if (!work) return hm_fail(HM_ERR_HIP, std::string(who) + ": workspace allocation failed");
+  uint8_t* contig = work;
+  uint8_t* on_cosets = contig + row * T;
+  int rc = HM_OK;
+  if (T) {
+    for (size_t j = 0; j < T; ++j)
+      HM_HIP_CHECK(hipMemcpyAsync(contig + row * j, d_coeff_columns[todo[j]], row, hipMemcpyDeviceToDevice, st));
+    rc = ntt_cosets_run(ctx, (const uint32_t*)contig, (uint32_t*)on_cosets, (uint32_t)T, omega, log_n, shifts, (uint32_t)count, true, st);
+    if (rc != HM_OK) return rc;
+    count_ntt(ctx, log_n, T * count);
+  }
+  std::vector<const void*> cols(n_columns);
+  for (size_t i = 0; i < n_columns; ++i) cols[i] = d_on_cosets ? d_on_cosets[i] : nullptr;
+  for (size_t j = 0; j < T; ++j) cols[todo[j]] = on_cosets + row * count * j;
+  HM_HIP_CHECK(hipMemsetAsync(d_partials, 0, row * count, st));                // PreviousValue: upstream starts h at zero
+  rc = graph_evaluate(ctx, *g, cols.data(), n_columns, dynamic_constants, n_dynamic, log_n, (uint32_t)count, d_partials, HM_GRAPH_COLUMNS_INTERNAL, st);
+  if (rc != HM_OK) return rc;
+  count_vector(ctx, HM_STAT_GRAPH_EVALUATE, 1, (uint64_t)count << log_n);
+  rc = ntt_cosets_inverse_run(ctx, (uint32_t*)d_partials, (uint32_t)count, om_inv.l, log_n, n_inv.l, shift_inv[0].l, st);
+  if (rc != HM_OK) return rc;
+  count_ntt(ctx, log_n, count);
+  return aux_release(ctx, slot, st);
+}
+
+static int quotient_check_args(const char* who, const void* out, const uint64_t* omega, const uint64_t* shifts, size_t n_columns,
+                               const void* const* d_coeff_columns, const void* const* d_on_cosets, size_t n_dynamic,
+                               const uint64_t* dynamic_constants, uint32_t log_n, size_t count) {
+  if (!out || !omega || !shifts || (n_columns && !d_coeff_columns && !d_on_cosets) || (n_dynamic && !dynamic_constants))
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (log_n > 28 || log_n == 0) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": log_n must be in 1 .. 28");
+  if (count == 0 || count > 16) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": 1 .. 16 cosets per call");
+  if (n_columns == 0 || n_columns * count > 65535) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": columns x cosets must be in 1 .. 65535");
+  return HM_OK;
+}
+
+int hm_quotient_partials_bn256_fr_dev(uint64_t program, const void* const* d_coeff_columns, const void* const* d_on_cosets, size_t n_columns,
+                                      const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t log_n, const uint64_t omega[4],
+                                      const uint64_t* shifts, size_t count, void* d_partials, void* stream) try {
+  const char* who = "hm_quotient_partials_bn256_fr_dev";
+  const int arc = quotient_check_args(who, d_partials, omega, shifts, n_columns, d_coeff_columns, d_on_cosets, n_dynamic, dynamic_constants, log_n, count);
+  if (arc != HM_OK) return arc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return quotient_partials(who, *ctx, program, d_coeff_columns, d_on_cosets, n_columns, dynamic_constants, n_dynamic, log_n, omega, shifts, count,
+                           d_partials, (hipStream_t)stream);
+} HM_API_CATCH("hm_quotient_partials_bn256_fr_dev")
+
+int hm_quotient_combine_bn256_fr_dev(const void* const* d_partials, const uint64_t* shifts, size_t count, uint32_t log_n, size_t pieces, void* d_h,
+                                     void* stream) try {
+  const char* who = "hm_quotient_combine_bn256_fr_dev";
+  if (!d_partials || !shifts || !d_h) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (log_n > 28 || log_n == 0) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": log_n must be in 1 .. 28");
+  if (count == 0 || count > 64 || pieces == 0 || pieces > count) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": 1 <= pieces <= cosets <= 64");
+  for (size_t c = 0; c < count; ++c) {
+    if (!d_partials[c]) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null partial");
+    // piece t is written before piece t + 1 reads EVERY partial again: h must not share memory with any of them
+    if (ranges_overlap(d_h, ((size_t)32 << log_n) * pieces, d_partials[c], (size_t)32 << log_n))
+      return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": d_h overlaps a partial (recombining in place is not supported)");
+  }
+  std::vector<std::vector<uint64_t>> rows;
+  const int mrc = quotient_matrix(who, shifts, count, log_n, &rows);
+  if (mrc != HM_OK) return mrc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const uint64_t n = 1ull << log_n;
+  for (size_t t = 0; t < pieces; ++t) {
+    const int rc = fr_linear_combination_run(d_partials, rows[t].data(), count, n, (uint32_t*)((uint8_t*)d_h + (size_t)n * 32 * t), (hipStream_t)stream);
+    if (rc != HM_OK) return rc;
+  }
+  count_vector(*ctx, HM_STAT_LINEAR_COMBINATION, pieces, (uint64_t)pieces * count * n);
+  return HM_OK;
+} HM_API_CATCH("hm_quotient_combine_bn256_fr_dev")
+
+int hm_quotient_by_cosets_bn256_fr_dev(uint64_t program, const void* const* d_coeff_columns, const void* const* d_on_cosets, size_t n_columns,
+                                       const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t log_n, const uint64_t omega[4],
+                                       const uint64_t* shifts, size_t count, size_t pieces, void* d_h, void* stream) try {
+  const char* who = "hm_quotient_by_cosets_bn256_fr_dev";
+  const int arc = quotient_check_args(who, d_h, omega, shifts, n_columns, d_coeff_columns, d_on_cosets, n_dynamic, dynamic_constants, log_n, count);
+  if (arc != HM_OK) return arc;
+  if (pieces == 0 || pieces > count) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": 1 <= pieces <= cosets <= 16");
+  std::vector<std::vector<uint64_t>> rows;
+  const int mrc = quotient_matrix(who, shifts, count, log_n, &rows);
+  if (mrc != HM_OK) return mrc;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t n = 1ull << log_n;
+  const size_t row = (size_t)n * 32;
+  // the partials live in the stream's NTT scratch slot? no: that is the transforms' ping-pong buffer.  They get the tail of a
+  // buffer of their own (AuxSlot::table is the scans' scratch: free between calls on this stream)
+  AuxSlot* slot = aux_acquire(*ctx, st);
+  if (!slot) return HM_ERR_HIP;
+  const size_t keep = (size_t)64 * 15 * 28 * 4;             // never shrink below the fixed-base table (see poly.hip)
+  uint8_t* parts_buf = (uint8_t*)slot->table.ensure(row * count > keep ? row * count : keep);
+  if (!parts_buf) return hm_fail(HM_ERR_HIP, std::string(who) + ": workspace allocation failed");
+  int rc = quotient_partials(who, *ctx, program, d_coeff_columns, d_on_cosets, n_columns, dynamic_constants, n_dynamic, log_n, omega, shifts, count,
+                             parts_buf, st);
+  if (rc != HM_OK) return rc;
+  std::vector<const void*> parts(count);
+  for (size_t c = 0; c < count; ++c) parts[c] = parts_buf + row * c;
+  for (size_t t = 0; t < pieces; ++t) {
+    rc = fr_linear_combination_run(parts.data(), rows[t].data(), count, n, (uint32_t*)((uint8_t*)d_h + row * t), st);
+    if (rc != HM_OK) return rc;
+  }
+  count_vector(*ctx, HM_STAT_LINEAR_COMBINATION, pieces, (uint64_t)pieces * count * n);
+  return aux_release(*ctx, slot, st);
+} HM_API_CATCH("hm_quotient_by_cosets_bn256_fr_dev")
+
+int hm_graph_destroy(uint64_t handle) try {
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  for (size_t i = 0; i < ctx->graphs.size(); ++i)
+    if (ctx->graphs[i]->handle == handle) {
+      (void)hipDeviceSynchronize();          // a launch may still read the program (rare call: once per circuit)
+      graph_release(*ctx->graphs[i]);
+      ctx->graphs.erase(ctx->graphs.begin() + i);
+      return HM_OK;
+    }
+  return hm_fail(HM_ERR_NOT_FOUND, "hm_graph_destroy: unknown program handle");
+} HM_API_CATCH("hm_graph_destroy")
+
+int hm_fr_dot_bn256_dev(const void* d_a, const void* d_b, size_t n, uint64_t out[4], void* stream) try {
+  if (!out || (n && (!d_a || !d_b))) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_dot_bn256_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return fr_dot_run(*ctx, (const uint32_t*)d_a, (const uint32_t*)d_b, n, out, (hipStream_t)stream);
+} HM_API_CATCH("hm_fr_dot_bn256_dev")
+
+int hm_fr_affine_sequence_dev(void* d_out, size_t n, const uint64_t a[4], const uint64_t b[4], void* stream) try {
+  if ((n && !d_out) || !a || !b) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_affine_sequence_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return fr_affine_sequence_run((uint32_t*)d_out, n, a, b, (hipStream_t)stream);
+} HM_API_CATCH("hm_fr_affine_sequence_dev")
+
+int hm_fr_random_dev(void* d_out, size_t n, uint64_t seed, void* stream) try {
+  if (n && !d_out) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_random_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return fr_random_run((uint32_t*)d_out, n, seed, (hipStream_t)stream);
+} HM_API_CATCH("hm_fr_random_dev")
+
+int hm_fr_scale_dev(void* d_a, size_t n, const uint64_t c[4], void* stream) try {
+  if ((n && !d_a) || !c) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_scale_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  if (n == 0) return HM_OK;
+  return fr_scale_run((uint32_t*)d_a, c, n, (hipStream_t)stream);     // the constant travels by value: no shared state
+} HM_API_CATCH("hm_fr_scale_dev")
+
+int hm_fr_distribute_powers_dev(void* d_a, size_t n, const uint64_t c3[12], void* stream) try {
+  if ((n && !d_a) || !c3) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_distribute_powers_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  if (n == 0) return HM_OK;
+  return fr_mul_pattern3_run((uint32_t*)d_a, c3, n, (hipStream_t)stream);
+} HM_API_CATCH("hm_fr_distribute_powers_dev")
+
+}  // extern "C"

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <chrono>
 #include <cstring>
 #include <exception>
 #include <functional>
@@ -75,6 +76,14 @@ inline bool spawn_or_false(JoinOnExit& pool, const char* point, F&& f) {
   }
 }
 const std::string& hm_last_error_string();   // the calling thread's message (workers carry theirs back to the caller's thread)
+
+inline double now_us() {
+  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const char *pa = (const char*)a, *pb = (const char*)b;
+  return pa < pb + b_bytes && pb < pa + a_bytes;
+}
 
 struct NttTables {
   uint32_t log_n = 0;
@@ -275,7 +284,7 @@ struct DeviceCtx {
   std::mutex live_mu;                                 // ... one counting call at a time (never taken under mu)
   std::mutex batch_h_mu;                              // ... which belong to ONE _h batch call at a time (taken before mu, never under it)
   uint64_t next_handle = 1;
-  // drop-in MSM: the converted bases of the previous call, keyed by a digest of the WHOLE host array (capi.hip)
+  // drop-in MSM: the converted bases of the previous call, keyed by a digest of the WHOLE host array (capi_msm.hip, digest.hip)
   size_t cached_host_n = 0;
   const void* cached_xy = nullptr;
   uint64_t cached_digest[4] = {0, 0, 0, 0};
@@ -289,7 +298,7 @@ struct DeviceCtx {
 AuxSlot* aux_acquire(DeviceCtx& ctx, hipStream_t stream);
 int aux_release(DeviceCtx& ctx, AuxSlot* slot, hipStream_t stream);
 
-DeviceCtx* ctx_for_current_device();
+DeviceCtx* ctx_for_current_device();     // capi.hip; null (and the message set) without a gfx950 device
 
 // xfer.hip.  Synchronous; the device side must be idle on the range (the callers synchronise their stream first).  May be called
 // with or without ctx.mu held (takes ctx.xfer.mu, never ctx.mu).  d2h failures leave `dst` partly written.
@@ -305,11 +314,29 @@ int xfer_host_register(const void* p, size_t bytes);   // hm_host_register / hm_
 int xfer_host_unregister(const void* p);
 size_t xfer_host_ranges();
 
-// capi.hip: the one-device bodies the multi-device layer runs per part (Jacobian results, so that partials fold)
+// The round trip of a host-pointer form through ctx.io, the ONE implementation of the drop-in contract's ordering (xfer.hip).  The
+// caller holds ctx.mu and lays the staging buffer out itself: `at` is a byte offset into it, outputs may alias inputs (the in-place
+// forms) and may download less than the device holds.  In order: fault point "<fault_prefix>_upload" (none when null), the staging
+// allocation, the uploads, launch(staging) on the null stream (a non-zero code goes back as it is), the stream synchronisation, fault
+// point "<fault_prefix>_download" (when there is an output), the buffered outputs into a local buffer (a failure returns its plain
+// code: nothing of the caller's is written yet), the direct outputs (a failure is HM_ERR_PARTIAL_OUTPUT), the buffered outputs to
+// their destinations.  Only then do ctx.calls.h2d_bytes / d2h_bytes grow, by the bytes copied.
+struct HostIn { const void* src; size_t bytes, at; };
+struct HostOut { void* dst; size_t bytes, at; bool buffered; };      // buffered: small (a root, an instance); bytes == 0: skipped
+struct HostSpans { double h2d_us = 0, device_us = 0, d2h_us = 0; };
+using HostLaunch = std::function<int(uint8_t* staging)>;
+int host_round_trip(const char* who, DeviceCtx& ctx, const char* fault_prefix, size_t staging_bytes, const HostIn* in, size_t n_in,
+                    const HostOut* out, size_t n_out, const HostLaunch& launch, HostSpans* spans = nullptr);
+inline size_t pad64(size_t bytes) { return (bytes + 63) / 64 * 64; }
+
+// capi_msm.hip: the one-device bodies the multi-device layer runs per part (Jacobian results, so that partials fold)
 int msm_h_local(uint64_t handle, size_t offset, const uint64_t* scalars, size_t n, uint64_t jac[12], int* is_id);
 std::vector<int> msm_device_list();            // copy of hm_set_msm_devices' list (empty: one device)
 constexpr size_t kMinShardPoints = 1 << 14;    // below this many points per device a split only adds latency
 constexpr size_t kSliceBasesFrom = (size_t)1 << 22;   // base sets from this size are SLICED over the devices, smaller ones replicated
+bool drop_parked_bases(DeviceCtx& ctx);        // hipFree every parked base buffer (an allocation failed); true when there was anything; ctx.mu held
+// digest.hip: keyed digest over EVERY word of n external points -> out = { poly1, poly2, words, parts }
+void digest_bases(const uint64_t* bases, size_t n, uint64_t out[4]);
 
 // multi.hip: single-process multi-GPU layer over the one-device entry points (hm_set_msm_devices).  A handle with
 // HM_MULTI_HANDLE_BIT names a base set registered on several devices; every form that takes a handle dispatches on it.

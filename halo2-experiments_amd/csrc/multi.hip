@@ -131,7 +131,7 @@ int run_per_device(const std::vector<int>& devs, const std::function<int(size_t)
   return HM_OK;
 }
 
-// layout: 0 the library's default, 1 the fixed-base table, 2 plain (capi.hip: BaseLayout) -- every part through the public
+// layout: 0 the library's default, 1 the fixed-base table, 2 plain (capi_msm.hip: BaseLayout) -- every part through the public
 // one-device entry of that layout (on a worker thread those stay on one device: multi_worker_flag)
 int multi_register(const uint64_t* bases_host, const void* d_bases, size_t n, void* stream, int layout, const std::vector<int>& devs,
                    uint64_t* out_handle) {

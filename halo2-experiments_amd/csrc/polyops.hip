@@ -655,7 +655,7 @@ int fr_mul_periodic_run(uint32_t* d_a, uint64_t n, const uint64_t* pattern_ext, 
 // ---------------------------------------------------------------------------------------------
 #include "poseidon.inc"
 
-// the constants were validated by the caller (capi.hip: canonical, the shape of the spec)
+// the constants were validated by the caller (capi_hash.hip: canonical, the shape of the spec)
 int poseidon_spec_create(DeviceCtx& ctx, uint32_t width, uint32_t rate, uint32_t r_f, uint32_t r_p, const uint64_t* rc_ext,
                          const uint64_t* mds_ext, uint64_t* out_handle) {
   const size_t n_rc = (size_t)(r_f + r_p) * width, n_mds = (size_t)width * width;

@@ -1,5 +1,6 @@
 // xfer.hip -- the host <-> device copies of the host-pointer entry points (hm_msm_bn256_g1*, hm_ntt_bn256_fr, hm_coeff_to_extended /
-// hm_extended_to_coeff, the batch call's scalar uploads, hm_copy_to_device / hm_copy_to_host).
+// hm_extended_to_coeff, the batch call's scalar uploads, hm_copy_to_device / hm_copy_to_host), and host_round_trip: the one sequence
+// of staging, uploads, launch, downloads and byte counting that every host-pointer form outside the MSM goes through.
 //
 // Two paths.  DIRECT: hipMemcpy on the caller's pointers.  LANES: the library's own pinned staging, four lanes (up to 8 by
 // HALO2_MI355X_XFER_LANES), each a host thread with its own stream and two 2 MiB pinned slots moving one contiguous share of the
@@ -438,6 +439,54 @@ int xfer_h2d(DeviceCtx& ctx, void* d_dst, const void* src, size_t bytes, const c
 }
 int xfer_d2h(DeviceCtx& ctx, void* dst, const void* d_src, size_t bytes, const char* who) {
   return xfer_run(ctx, false, const_cast<void*>(d_src), dst, bytes, who);
+}
+
+// The round trip of a host-pointer form (hm_internal.h).  Out of line on purpose: the fault-injection library links this translation
+// unit built with its fault points, and an inline copy from a unit built without them could be the one the linker keeps.
+int host_round_trip(const char* who, DeviceCtx& ctx, const char* fault_prefix, size_t staging_bytes, const HostIn* in, size_t n_in,
+                    const HostOut* out, size_t n_out, const HostLaunch& launch, HostSpans* spans) {
+  const std::string w(who);
+  if (fault_prefix) hm_fault_point((std::string(fault_prefix) + "_upload").c_str());
+  uint8_t* d = (uint8_t*)ctx.io.ensure(staging_bytes);
+  if (!d) return hm_fail(HM_ERR_HIP, w + ": staging allocation failed");
+  size_t up = 0, down = 0, held = 0;
+  const double t0 = now_us();
+  for (size_t i = 0; i < n_in; ++i) {
+    const int rc = xfer_h2d(ctx, d + in[i].at, in[i].src, in[i].bytes, (w + ": upload").c_str());
+    if (rc != HM_OK) return rc;
+    up += in[i].bytes;
+  }
+  const double t1 = now_us();
+  if (const int rc = launch(d)) return rc;
+  HM_HIP_CHECK(hipStreamSynchronize(nullptr));
+  const double t2 = now_us();
+  if (fault_prefix && n_out) hm_fault_point((std::string(fault_prefix) + "_download").c_str());
+  for (size_t i = 0; i < n_out; ++i) {
+    down += out[i].bytes;
+    if (out[i].buffered) held += out[i].bytes;
+  }
+  std::vector<uint8_t> small(held);
+  held = 0;
+  for (size_t i = 0; i < n_out; ++i) {
+    if (!out[i].buffered) continue;
+    const int rc = xfer_d2h(ctx, small.data() + held, d + out[i].at, out[i].bytes, who);
+    if (rc != HM_OK) return rc;                       // nothing of the caller's has been written yet
+    held += out[i].bytes;
+  }
+  // from here on the caller's arrays are being written: a failure is NOT one a caller may answer by running its CPU body on them
+  for (size_t i = 0; i < n_out; ++i)
+    if (!out[i].buffered && xfer_d2h(ctx, out[i].dst, d + out[i].at, out[i].bytes, who) != HM_OK)
+      return hm_fail(HM_ERR_PARTIAL_OUTPUT, w + ": copying the result back failed, the caller's output is partly written: " + hm_last_error_string());
+  held = 0;
+  for (size_t i = 0; i < n_out; ++i) {
+    if (!out[i].buffered) continue;
+    std::memcpy(out[i].dst, small.data() + held, out[i].bytes);
+    held += out[i].bytes;
+  }
+  ctx.calls.h2d_bytes += up;
+  ctx.calls.d2h_bytes += down;
+  if (spans) *spans = HostSpans{t1 - t0, t2 - t1, now_us() - t2};
+  return HM_OK;
 }
 
 }  // namespace hm

@@ -273,3 +273,23 @@ def test_downsize_and_from_monomial():
         for p in (big, ref, mono):
             if p is not None:
                 p.release()
+
+
+def _pcie_bytes():
+    st = _lib.Stats()
+    _lib.check(_lib.load().hm_get_stats(ctypes.byref(st)))
+    return np.array([st.h2d_bytes, st.d2h_bytes], dtype=np.int64)
+
+
+def test_host_form_counts_the_bytes_it_moves():
+    """hm_get_stats' h2d_bytes / d2h_bytes of hm_g1_fft_bn256 at 2^2 points: 96 bytes per point each way."""
+    rng = random.Random(22)
+    aff = _to_np(h.g1_fixed_base_mul(h.random_fr(4, 22), G1_GENERATOR))
+    xyz = _jacobian_host(aff, rng, ())
+    dev = _to_dev(aff.copy())
+    w = fr_words(o.fr_omega(2))
+    h.g1_fft(dev, w, 2)
+    b0 = _pcie_bytes()
+    h.g1_fft_host(xyz, w, 2)
+    assert (_pcie_bytes() - b0).tolist() == [4 * 96, 4 * 96]
+    assert np.array_equal(xyz, _expected_jacobian(_to_np(dev)))

@@ -340,3 +340,27 @@ def test_path_roots_equals_host_verify_path_at_depth_5(cls, other):
             assert got[u] == P.MerkleTree.verify_path(leaves[u][0], ([s[0] for s in sibs[u]], bits), spec), u
     if E == 2 and not other:
         assert got[1] == (100 + 10 + 50 + 60 + 90 + 90) % R                # the fixture's balances
+
+
+def _pcie_bytes():
+    st = _lib.Stats()
+    _lib.check(_lib.load().hm_get_stats(ctypes.byref(st)))
+    return np.array([st.h2d_bytes, st.d2h_bytes], dtype=np.int64)
+
+
+@pytest.mark.parametrize("cls", DEFAULT_TREES)
+def test_host_form_of_the_roots_counts_the_bytes_it_moves(cls):
+    """hm_get_stats' h2d_bytes / d2h_bytes of hm_merkle_roots_bn256 at m = 3, depth 2: leaves, siblings and 24 bytes of indices up
+    (the indices are padded in the staging buffer, not in the count), the roots down."""
+    rng = random.Random(32)
+    spec, elem = _spec(cls.WIDTH, False), 32 * cls.ELEMS
+    leaves = _leaf_ints(rng, 4, cls.ELEMS)
+    nodes = _host_nodes(cls, spec, leaves)
+    idx = [2, 0, 3]
+    sibs = [nodes[i ^ 1] for i in idx], [nodes[4 + ((i >> 1) ^ 1)] for i in idx]
+    lv = _leaf_words([leaves[i] for i in idx], cls.ELEMS)
+    sb = _leaf_words([sibs[l][p] for p in range(3) for l in range(2)], cls.ELEMS)
+    b0 = _pcie_bytes()
+    roots = cls.path_roots(lv, sb, np.array(idx, dtype=np.uint64), spec)
+    assert (_pcie_bytes() - b0).tolist() == [3 * elem + 6 * elem + 24, 3 * elem]
+    assert np.array_equal(roots.reshape(3, -1), np.tile(_leaf_words([nodes[-1]], cls.ELEMS).reshape(1, -1), (3, 1)))

@@ -886,3 +886,48 @@ def test_a_polynomial_below_q_n_is_recovered_from_any_q_cosets(pyref, k, j):
         dom.combine_cosets([pieces[0]], cosets=[e])
     with pytest.raises(ValueError):
         dom.combine_cosets([pieces[0], pieces[1]], cosets=[1, 1])
+
+
+def _pcie_bytes():
+    st = _lib.Stats()
+    _lib.check(_lib.load().hm_get_stats(ctypes.byref(st)))
+    return np.array([st.h2d_bytes, st.d2h_bytes], dtype=np.int64)
+
+
+def test_host_forms_count_the_bytes_they_move(cref, pyref):
+    """hm_get_stats' h2d_bytes / d2h_bytes grow by what each host form really copies: hm_ntt_bn256_fr at 2^4, hm_coeff_to_extended_bn256_fr
+    from 2^3 to 2^5 (the padding never travels), hm_extended_to_coeff_bn256_fr at 2^4 keeping 5 coefficients (the tail is neither
+    downloaded nor touched)."""
+    lib, o, R = _lib.load(), pyref, pyref.R
+    u64 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    a = rand_fr_gpu(16, 9100).cpu().numpy().view(np.uint64).copy()
+    w4 = fr_words(o.fr_omega(4))
+    exp = cref.best_fft(a, w4, 4)
+    b0 = _pcie_bytes()
+    _lib.check(lib.hm_ntt_bn256_fr(u64(a), u64(w4), 4))
+    assert (_pcie_bytes() - b0).tolist() == [16 * 32, 16 * 32] and np.array_equal(a, exp)
+
+    coeffs = rand_fr_gpu(8, 9101).cpu().numpy().view(np.uint64).copy()
+    g = 7
+    coset = np.concatenate([fr_words(1), fr_words(g), fr_words(g * g % R)])
+    w5 = fr_words(o.fr_omega(5))
+    pad = np.zeros((32, 4), dtype=np.uint64)
+    pad[:8] = coeffs
+    exp = cref.best_fft(cref.fr_mul(pad, _pattern3([1, g, g * g % R], 32)), w5, 5)
+    ext = np.full((32, 4), 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)
+    b0 = _pcie_bytes()
+    _lib.check(lib.hm_coeff_to_extended_bn256_fr(u64(coeffs), u64(ext), u64(w5), 3, 5, u64(coset)))
+    assert (_pcie_bytes() - b0).tolist() == [8 * 32, 32 * 32] and np.array_equal(ext, exp)
+
+    sentinel = 0x0A5A5A5A5A5A5A5A                     # in every word: a canonical element (the top word is below the modulus's)
+    x = rand_fr_gpu(16, 9102).cpu().numpy().view(np.uint64).copy()
+    x[5:] = sentinel                                  # beyond `keep`: uploaded (it is input), never written back
+    w4_inv, div, gi = pow(o.fr_omega(4), R - 2, R), pow(16, R - 2, R), pow(g, R - 2, R)
+    inv = cref.fr_mul(cref.best_fft(x, fr_words(w4_inv), 4), np.tile(fr_words(div), (16, 1)))
+    exp = cref.fr_mul(inv, _pattern3([1, gi, gi * gi % R], 16))
+    coset_inv = np.concatenate([fr_words(1), fr_words(gi), fr_words(gi * gi % R)])
+    got = x.copy()
+    b0 = _pcie_bytes()
+    _lib.check(lib.hm_extended_to_coeff_bn256_fr(u64(got), 5, u64(fr_words(w4_inv)), 4, u64(fr_words(div)), u64(coset_inv)))
+    assert (_pcie_bytes() - b0).tolist() == [16 * 32, 5 * 32]
+    assert np.array_equal(got[:5], exp[:5]) and (got[5:] == sentinel).all()

@@ -270,3 +270,39 @@ def test_fault_points_leave_the_outputs_as_they_were_and_the_next_call_works():
         assert fi.hm_poseidon_destroy(h) == HM_OK
     finally:
         fi.hm_test_arm_fault(None, 0)
+
+
+def _pcie_bytes():
+    st = _lib.Stats()
+    _lib.check(_lib.load().hm_get_stats(ctypes.byref(st)))
+    return np.array([st.h2d_bytes, st.d2h_bytes], dtype=np.int64)
+
+
+def test_host_forms_count_the_bytes_they_move():
+    """hm_get_stats' h2d_bytes / d2h_bytes: hm_poseidon_hash_bn256_fr at n = 3 for both widths, hm_merkle_sum_tree_build at depth 2
+    with the root alone (64 bytes come back) and with every node (the root is then counted with them and once more on its own)."""
+    lib = _lib.load()
+    rng = random.Random(3)
+    for width in (3, 5):
+        spec = P.default_spec(width)
+        rc, mds, _ = spec.constants()
+        msgs = _messages(rng, 3, width - 1)
+        b0 = _pcie_bytes()
+        got = P.poseidon_hash_host(spec, _words(msgs))
+        assert (_pcie_bytes() - b0).tolist() == [3 * (width - 1) * 32, 3 * 32]
+        assert chk.from_words(got) == [chk.digest(m, rc, mds, 8, 56) for m in msgs]
+    spec = P.default_spec(5)
+    rc, mds, _ = spec.constants()
+    leaves = [(rng.randrange(R), rng.randrange(R)) for _ in range(4)]
+    exp = [node for level in chk.sum_tree(leaves, rc, mds, 8, 56) for node in level]
+    lw = chk.to_words([v for leaf in leaves for v in leaf])
+    root, nodes = np.zeros((2, 4), dtype=np.uint64), np.zeros((7, 2, 4), dtype=np.uint64)
+    b0 = _pcie_bytes()
+    assert lib.hm_merkle_sum_tree_build(ctypes.c_uint64(spec.handle()), _u64(lw), 2, _u64(root), None) == HM_OK
+    assert (_pcie_bytes() - b0).tolist() == [4 * 64, 64] and tuple(chk.from_words(root)) == exp[-1]
+    root[:] = 0
+    b0 = _pcie_bytes()
+    assert lib.hm_merkle_sum_tree_build(ctypes.c_uint64(spec.handle()), _u64(lw), 2, _u64(root), _u64(nodes)) == HM_OK
+    assert (_pcie_bytes() - b0).tolist() == [4 * 64, 64 + 7 * 64]
+    vals = chk.from_words(nodes)
+    assert list(zip(vals[0::2], vals[1::2])) == exp and tuple(chk.from_words(root)) == exp[-1]

@@ -258,3 +258,24 @@ def _default_bytes(params):
     f = io.BytesIO()
     params.write(f)
     return f.getvalue()
+
+
+def _pcie_bytes():
+    st = _lib.Stats()
+    _lib.check(_lib.load().hm_get_stats(ctypes.byref(st)))
+    return np.array([st.h2d_bytes, st.d2h_bytes], dtype=np.int64)
+
+
+def test_host_forms_count_the_bytes_they_move():
+    """hm_get_stats' h2d_bytes / d2h_bytes per host form at n = 3: 64-byte points one way, 32-byte encodings the other; the check
+    downloads nothing."""
+    aff = _np(h.g1_fixed_base_mul(h.random_fr(3, 3), G1_GENERATOR)).copy()
+    b0 = _pcie_bytes()
+    comp = h.g1_compress_host(aff)
+    assert (_pcie_bytes() - b0).tolist() == [3 * 64, 3 * 32]
+    b0 = _pcie_bytes()
+    assert np.array_equal(h.g1_decompress_host(comp), aff)
+    assert (_pcie_bytes() - b0).tolist() == [3 * 32, 3 * 64]
+    b0 = _pcie_bytes()
+    h.g1_check_host(aff)
+    assert (_pcie_bytes() - b0).tolist() == [3 * 64, 0]

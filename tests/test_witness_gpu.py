@@ -358,3 +358,32 @@ def test_fault_points_of_the_host_form(spec):
         assert fi.hm_poseidon_destroy(h) == HM_OK
     finally:
         fi.hm_test_arm_fault(None, 0)
+
+
+def _pcie_bytes():
+    st = _lib.Stats()
+    _lib.check(_lib.load().hm_get_stats(ctypes.byref(st)))
+    return np.array([st.h2d_bytes, st.d2h_bytes], dtype=np.int64)
+
+
+def _smallest_k(layout, *args):
+    """the smallest log_n the layout call accepts"""
+    rows, n_adv = ctypes.c_uint32(), ctypes.c_uint32()
+    return next(k for k in range(1, 25) if layout(*args, k, ctypes.byref(rows), ctypes.byref(n_adv), None) == HM_OK)
+
+
+def test_host_form_counts_the_bytes_it_moves(spec):
+    """hm_get_stats' h2d_bytes / d2h_bytes of hm_merkle_sum_witness_bn256 at m = 3, depth 2 and the smallest 2^k the layout accepts:
+    leaves, siblings and 24 bytes of indices up (padded to 64 in the staging buffer, not in the count), columns and instance down;
+    the columns equal the device form's."""
+    k = _smallest_k(_lib.load().hm_merkle_sum_witness_layout, 8, 56, 2)
+    rng = random.Random(23)
+    leaves = _gpu(ps.ints_to_words([rng.randrange(R) if e == 0 else rng.randrange(1 << 20) for _ in range(3) for e in range(2)]).reshape(3, 2, 4))
+    sibs = _gpu(ps.ints_to_words([rng.randrange(R) if e == 0 else rng.randrange(1 << 20) for _ in range(6) for e in range(2)]).reshape(3, 2, 2, 4))
+    idx = torch.tensor([2, 0, 3], dtype=torch.int64, device="cuda")
+    adv, inst = sy.merkle_sum_witness(spec, leaves, sibs, idx, 1 << 40, k)
+    host = lambda t: t.cpu().numpy().view(np.uint64)
+    b0 = _pcie_bytes()
+    h_adv, h_inst = sy.merkle_sum_witness_host(spec, host(leaves), host(sibs), host(idx), 1 << 40, k)
+    assert (_pcie_bytes() - b0).tolist() == [3 * 64 + 6 * 64 + 24, 3 * sy.N_ADVICE * (32 << k) + 3 * 128]
+    assert np.array_equal(h_adv, host(adv)) and np.array_equal(h_inst, host(inst))

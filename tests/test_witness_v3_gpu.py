@@ -388,3 +388,37 @@ def test_fault_points_of_the_host_forms(spec):
             assert fi.hm_poseidon_destroy(h) == HM_OK
     finally:
         fi.hm_test_arm_fault(None, 0)
+
+
+def _pcie_bytes():
+    st = _lib.Stats()
+    _lib.check(_lib.load().hm_get_stats(ctypes.byref(st)))
+    return np.array([st.h2d_bytes, st.d2h_bytes], dtype=np.int64)
+
+
+def _smallest_k(layout, *args):
+    """the smallest log_n the layout call accepts"""
+    rows, n_adv = ctypes.c_uint32(), ctypes.c_uint32()
+    return next(k for k in range(1, 25) if layout(*args, k, ctypes.byref(rows), ctypes.byref(n_adv), None) == HM_OK)
+
+
+def test_host_forms_count_the_bytes_they_move(spec):
+    """hm_get_stats' h2d_bytes / d2h_bytes of hm_merkle_witness_bn256 (m = 3, depth 2) and hm_poseidon_witness_bn256 (m = 3) at the
+    smallest 2^k their layouts accept: the inputs up as they are (24 bytes of indices: padded to 64 in the staging buffer, not in
+    the count), columns and instance down; the columns equal the device forms'."""
+    lib = _lib.load()
+    rng = random.Random(33)
+    k = _smallest_k(lib.hm_merkle_witness_layout, 8, 56, 2)
+    leaves, sibs, idx = _path_tensors([(rng.randrange(R), [rng.randrange(R), rng.randrange(R)], i) for i in (2, 0, 3)])
+    adv, inst = sy.merkle_witness(spec, leaves, sibs, idx, k)
+    b0 = _pcie_bytes()
+    h_adv, h_inst = sy.merkle_witness_host(spec, _words(leaves), _words(sibs), _words(idx), k)
+    assert (_pcie_bytes() - b0).tolist() == [3 * 32 + 6 * 32 + 24, 3 * V3.N_ADVICE * (32 << k) + 3 * 64]
+    assert np.array_equal(h_adv, _words(adv)) and np.array_equal(h_inst, _words(inst))
+    k = _smallest_k(lib.hm_poseidon_witness_layout, 8, 56)
+    msgs = _gpu(ps.ints_to_words([rng.randrange(R) for _ in range(12)]).reshape(3, 4, 4))
+    adv, inst = sy.poseidon_circuit_witness(None, msgs, k)
+    b0 = _pcie_bytes()
+    h_adv, h_inst = sy.poseidon_circuit_witness_host(None, _words(msgs), k)
+    assert (_pcie_bytes() - b0).tolist() == [3 * 128, 3 * PC.N_ADVICE * (32 << k) + 3 * 32]
+    assert np.array_equal(h_adv, _words(adv)) and np.array_equal(h_inst, _words(inst))
