@@ -448,6 +448,14 @@ int merkle_witness_run(uint32_t E, const PoseidonSpec& s, uint32_t depth, uint32
                        uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream);
 int poseidon_witness_run(const PoseidonSpec& s, uint32_t log_n, size_t m, const uint32_t* d_msgs, uint32_t* d_advice, uint32_t* d_instance,
                          hipStream_t stream);
+// keygen's permutation assembly (keygen.inc).  d_copies: m pairs of cell ids, a cell being column * 2^k + row; d_sigma_cells receives
+// columns * 2^k ids (it is the union-find's parent array on the way); a pair with an id out of range is dropped and counted in
+// *d_dropped (null: not counted).  Asynchronous on `stream`; the arguments were checked by the caller (capi_keygen.hip).
+int perm_assemble_run(const uint32_t* d_copies, size_t m, uint32_t columns, uint32_t k, uint32_t* d_sigma_cells, uint32_t* d_dropped,
+                      hipStream_t stream);
+// d_out[c] = delta^j' * omega^i' (external words) for d_sigma_cells[c] = j' * 2^k + i'
+int perm_columns_run(const uint32_t* d_sigma_cells, uint32_t columns, uint32_t k, const uint64_t omega_ext[4], const uint64_t delta_ext[4],
+                     uint32_t* d_out, hipStream_t stream);
 
 // lookup.hip
 int lookup_permute_run(DeviceCtx& ctx, const void* const* d_inputs, const void* const* d_tables, size_t pairs, uint64_t rows,

@@ -19,6 +19,7 @@
 namespace hm {
 #include "g1_codec.inc"   // the per-point SRS codec formulas (its kernels are HIP-only)
 #include "poseidon.inc"   // the per-hash Poseidon / Merkle node functions (likewise)
+#include "keygen.inc"     // the permutation assembly's key packing and link rule (likewise)
 }
 
 using namespace hm;
@@ -604,6 +605,40 @@ int hc_merkle_roots(uint32_t width, const uint32_t* consts, uint32_t r_f, uint32
       merkle_root_lane<2>(leaves, siblings, indices, depth, consts, r_f, r_p, u, roots);
     else
       merkle_root_lane<1>(leaves, siblings, indices, depth, consts, r_f, r_p, u, roots);
+  }
+  return 0;
+}
+
+// The permutation assembly (keygen.inc: perm_key / perm_link, the arithmetic its kernels run) on m host copies: a sequential
+// union-find that hooks the larger root under the smaller, as the device's does, and std::sort in the place of the sorting network.
+// sigma_cells: columns * 2^k words; *dropped: the pairs with an id out of range.
+int hc_permutation_assemble(const uint32_t* copies, size_t m, uint32_t columns, uint32_t k, uint32_t* sigma_cells, uint32_t* dropped) {
+  if (columns == 0 || k > 32 || ((uint64_t)columns << k) > ((uint64_t)1 << 32) || m > ((size_t)1 << 30)) return -1;
+  const uint64_t cells = (uint64_t)columns << k;
+  for (uint64_t c = 0; c < cells; ++c) sigma_cells[c] = (uint32_t)c;
+  uint32_t* parent = sigma_cells;                       // the forest lives in the output, as on the device
+  const auto find = [&](uint32_t x) {
+    while (parent[x] != x) x = parent[x] = parent[parent[x]];
+    return x;
+  };
+  std::vector<uint64_t> keys;
+  keys.reserve(2 * m);
+  *dropped = 0;
+  for (size_t t = 0; t < m; ++t) {
+    const uint32_t a = copies[2 * t], b = copies[2 * t + 1];
+    if (a >= cells || b >= cells) {
+      ++*dropped;
+      continue;
+    }
+    const uint32_t ra = find(a), rb = find(b);
+    if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
+  }
+  for (size_t t = 0; t < 2 * m; ++t)
+    if (copies[t] < cells && copies[t ^ 1] < cells) keys.push_back(perm_key(find(copies[t]), copies[t]));
+  std::sort(keys.begin(), keys.end());
+  for (size_t p = 0; p < keys.size(); ++p) {
+    uint32_t cell, target;
+    if (perm_link(keys[p], p + 1 < keys.size() ? keys[p + 1] : PERM_PAD, cell, target)) sigma_cells[cell] = target;
   }
   return 0;
 }

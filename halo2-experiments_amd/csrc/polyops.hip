@@ -859,4 +859,78 @@ int poseidon_witness_run(const PoseidonSpec& s, uint32_t log_n, size_t m, const 
   return HM_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// keygen's permutation assembly: the plan and its kernels in keygen.inc
+// ---------------------------------------------------------------------------------------------
+#include "keygen.inc"
+
+static int perm_assemble_launch(const uint32_t* d_copies, uint64_t m, uint64_t cells, uint32_t* d_sigma_cells, uint32_t* d_dropped,
+                                uint64_t* d_keys, uint64_t n_pow2, hipStream_t stream) {
+  const auto blocks = [](uint64_t lanes) { return dim3((unsigned)((lanes + PS_THREADS - 1) / PS_THREADS)); };
+  hipLaunchKernelGGL(perm_union_kernel, blocks(m), dim3(PS_THREADS), 0, stream, (const uint2*)d_copies, m, cells, d_sigma_cells);
+  hipLaunchKernelGGL(perm_keys_kernel, blocks(n_pow2), dim3(PS_THREADS), 0, stream, d_copies, m, n_pow2, cells,
+                     (const uint32_t*)d_sigma_cells, d_keys, d_dropped);
+  if (int rc = merkle_update_sort(d_keys, n_pow2, stream)) return rc;
+  hipLaunchKernelGGL(perm_link_kernel, blocks(2 * m), dim3(PS_THREADS), 0, stream, (const uint64_t*)d_keys, 2 * m, n_pow2, d_sigma_cells);
+  HM_HIP_CHECK(hipGetLastError());
+  return HM_OK;
+}
+
+// A fixed chain of launches: identity, union, keys, the sort's stages, links.  Nothing comes back to the host; the keys are
+// stream-ordered scratch, as merkle_update_run's.
+int perm_assemble_run(const uint32_t* d_copies, size_t m, uint32_t columns, uint32_t k, uint32_t* d_sigma_cells, uint32_t* d_dropped,
+                      hipStream_t stream) {
+  const uint64_t cells = (uint64_t)columns << k;
+  if (d_dropped) HM_HIP_CHECK(hipMemsetAsync(d_dropped, 0, sizeof(uint32_t), stream));
+  hipLaunchKernelGGL(perm_identity_kernel, dim3((unsigned)((cells + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, stream,
+                     d_sigma_cells, cells);
+  HM_HIP_CHECK(hipGetLastError());
+  if (m == 0) return HM_OK;
+  uint64_t n_pow2 = 2;
+  while (n_pow2 < 2 * (uint64_t)m) n_pow2 <<= 1;
+  void* keys = nullptr;
+  HM_HIP_CHECK(hipMallocAsync(&keys, (size_t)n_pow2 * 8, stream));
+  int rc = perm_assemble_launch(d_copies, m, cells, d_sigma_cells, d_dropped, (uint64_t*)keys, n_pow2, stream);
+  const hipError_t fe = hipFreeAsync(keys, stream);
+  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("permutation_assemble: hipFreeAsync: ") + hipGetErrorString(fe));
+  return rc;
+}
+
+// out[c] = delta^j' * omega^i' for sigma_cells[c] = j' * n + i', both factors from tables of external words; an id >= cells (no
+// assembly writes one) gives zero, which no cell stands for
+__global__ __launch_bounds__(PO_THREADS) void perm_columns_kernel(const uint32_t* __restrict__ sigma_cells, uint64_t cells, uint32_t k,
+                                                                  const uint32_t* __restrict__ omega_pow, const uint32_t* __restrict__ delta_pow,
+                                                                  PoFr k32_int, uint32_t* __restrict__ out) {
+  const uint64_t c = (uint64_t)blockIdx.x * PO_THREADS + threadIdx.x;
+  if (c >= cells) return;
+  const uint32_t s = sigma_cells[c];
+  if (s >= cells) {
+    uint4* dst = reinterpret_cast<uint4*>(out + c * 8);
+    dst[0] = dst[1] = make_uint4(0, 0, 0, 0);
+    return;
+  }
+  const uint64_t row = (uint64_t)s & (((uint64_t)1 << k) - 1), col = (uint64_t)s >> k;
+  po_store_canonical(out, c, fe_mul(po_load_raw(omega_pow, row), fe_mul(po_load_raw(delta_pow, col), po_arg(k32_int))));
+}
+
+int perm_columns_run(const uint32_t* d_sigma_cells, uint32_t columns, uint32_t k, const uint64_t omega_ext[4], const uint64_t delta_ext[4],
+                     uint32_t* d_out, hipStream_t stream) {
+  const uint64_t n = (uint64_t)1 << k, cells = (uint64_t)columns << k;
+  void* tables = nullptr;
+  HM_HIP_CHECK(hipMallocAsync(&tables, (size_t)(n + columns) * 32, stream));
+  uint32_t *d_omega = (uint32_t*)tables, *d_delta = d_omega + n * 8;
+  int rc = fr_powers_run(d_omega, n, omega_ext, stream);
+  if (rc == HM_OK) rc = fr_powers_run(d_delta, columns, delta_ext, stream);
+  if (rc == HM_OK) {
+    PoFr k32;
+    host::fr_to_internal9(host::FR_32, k32.l);
+    hipLaunchKernelGGL(perm_columns_kernel, dim3((unsigned)((cells + PO_THREADS - 1) / PO_THREADS)), dim3(PO_THREADS), 0, stream, d_sigma_cells,
+                       cells, k, (const uint32_t*)d_omega, (const uint32_t*)d_delta, k32, d_out);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("permutation_columns: ") + hipGetErrorString(e));
+  }
+  const hipError_t fe = hipFreeAsync(tables, stream);
+  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("permutation_columns: hipFreeAsync: ") + hipGetErrorString(fe));
+  return rc;
+}
+
 }  // namespace hm

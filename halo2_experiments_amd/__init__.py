@@ -5,7 +5,7 @@ Host-side mirror of ``halo2_proofs::arithmetic`` (``best_multiexp``, ``best_fft`
 
 The sources live in ``halo2-experiments_amd/`` (the directory name the project layout prescribes; not a valid
 Python identifier): this package is the importable name, and its ``__path__`` points there, so every submodule
-(``_lib``, ``arithmetic``, ``domain``, ``kzg``, ``poseidon``, ``replay``, ``sharding``, ``synthesis``) is an ordinary module of this package
+(``_lib``, ``arithmetic``, ``domain``, ``keygen``, ``kzg``, ``poseidon``, ``replay``, ``sharding``, ``synthesis``) is an ordinary module of this package
 with an ordinary ``__spec__`` / ``__file__``.
 """
 import os as _os
@@ -20,6 +20,8 @@ from .arithmetic import (bases_info, batch_invert, best_fft, best_multiexp, best
                          linear_combination, msm_stats, permute_expression_pair, permute_expression_pairs, random_fr, register_bases,
                          release_bases)
 from .domain import EvaluationDomain  # noqa: F401
+from .keygen import (ProvingKey, VerifyingKey, copy_pairs, keygen_pk, keygen_vk, permutation_cells_dev,  # noqa: F401
+                     permutation_columns_dev)
 from .poseidon import MerkleSumTree, MerkleTree, Spec, poseidon_hash, poseidon_hash_host, update_plan  # noqa: F401
 from .synthesis import (MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, merkle_sum_witness,  # noqa: F401
                         merkle_sum_witness_host, merkle_witness, merkle_witness_host, permutation_columns, poseidon_circuit_witness,
@@ -32,4 +34,5 @@ __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_mult
            "linear_combination", "random_fr", "permute_expression_pair", "permute_expression_pairs", "EvaluationDomain",
            "Spec", "poseidon_hash", "poseidon_hash_host", "update_plan", "MerkleSumTree", "MerkleTree", "MerkleSumTreeLayout", "merkle_sum_witness",
            "merkle_sum_witness_host", "permutation_columns", "MerkleTreeV3Layout", "PoseidonCircuitLayout", "merkle_witness",
-           "merkle_witness_host", "poseidon_circuit_witness", "poseidon_circuit_witness_host"]
+           "merkle_witness_host", "poseidon_circuit_witness", "poseidon_circuit_witness_host", "copy_pairs", "permutation_cells_dev",
+           "permutation_columns_dev", "keygen_vk", "keygen_pk", "VerifyingKey", "ProvingKey"]

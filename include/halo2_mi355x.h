@@ -602,6 +602,23 @@ int hm_poseidon_witness_bn256_dev(uint64_t handle, uint32_t log_n, size_t m, con
                                   void* stream);
 int hm_poseidon_witness_bn256(uint64_t handle, uint32_t log_n, size_t m, const uint64_t* msgs, uint64_t* advice, uint64_t* instance);
 
+/* keygen's permutation argument (permutation::keygen::Assembly) on the device.  A cell id is j * 2^k + i: column j of the
+ * `columns` equality-enabled columns, row i; columns * 2^k <= 2^32.
+ * assemble: d_copies holds m copy constraints as pairs of cell ids (DEVICE memory, 8-byte aligned).  d_sigma_cells receives
+ * columns * 2^k ids, the permutation as cells: a cell no copy names maps to itself; the members of every class of cells joined
+ * by copies, by ascending id, each map to the next one and the last to the first.  The result depends on the set of copies
+ * alone, not on their order or on scheduling.  m = 0 gives the identity.  A pair with an id >= columns * 2^k is dropped, and counted
+ * in *d_dropped_or_null (one u32 in DEVICE memory, set by every call) unless that is NULL.
+ * columns: d_out[c] = delta^j' * omega^i' for d_sigma_cells[c] = j' * 2^k + i', c < columns * 2^k: the `columns` sigma columns
+ * in Lagrange form, back to back (an id out of range gives zero); omega and delta are 4 Montgomery words each in HOST memory.
+ * Both are asynchronous on `stream`, a fixed chain of launches with stream-ordered scratch of the library's; nothing comes back
+ * to the host.  HM_ERR_BAD_ARG, before anything is launched: NULL with work to do, columns = 0, columns * 2^k > 2^32, 2 m > 2^31,
+ * a pointer that is not aligned (d_copies 8, d_out 16, the others 4), an output overlapping its input. */
+int hm_permutation_assemble_dev(const uint32_t* d_copies, size_t m, uint32_t columns, uint32_t k, uint32_t* d_sigma_cells,
+                                uint32_t* d_dropped_or_null, void* stream);
+int hm_permutation_columns_bn256_fr_dev(const uint32_t* d_sigma_cells, uint32_t columns, uint32_t k, const uint64_t omega[4],
+                                        const uint64_t delta[4], void* d_out, void* stream);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 
 typedef struct hm_msm_stats {
