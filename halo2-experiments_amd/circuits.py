@@ -97,6 +97,35 @@ class ConstraintSystem:
             d = max(d, degree(p))
         return d
 
+    def queries(self) -> Tuple[List[Tuple[int, int]], List[Tuple[int, int]], List[Tuple[int, int]]]:
+        """(advice, fixed, instance) queries as (column, rotation) lists: the evaluations a proof carries.  In order of first use in
+        the gate polynomials, then in the lookups' input and table expressions, then every equality column at rotation 0 (upstream's
+        ``enable_equality`` queries it).  Upstream's order is that of the ``meta.query_*`` calls inside its chips; this one is a
+        function of the expressions alone."""
+        found: Dict[str, List[Tuple[int, int]]] = {"advice": [], "fixed": [], "instance": []}
+        kinds = {Advice: "advice", Fixed: "fixed", Instance: "instance"}
+
+        def walk(e: Expression) -> None:
+            if type(e) in kinds:
+                q = (e.column, e.rotation)
+                if q not in found[kinds[type(e)]]:
+                    found[kinds[type(e)]].append(q)
+            elif isinstance(e, (Sum, Product)):
+                walk(e.a)
+                walk(e.b)
+            elif isinstance(e, (Negated, Scaled)):
+                walk(e.a)
+
+        for p in self.polynomials():
+            walk(p)
+        for ins, tabs in self.lookups:
+            for e in list(ins) + list(tabs):
+                walk(e)
+        for kind, index in self.equality:
+            if (index, 0) not in found[kind]:
+                found[kind].append((index, 0))
+        return found["advice"], found["fixed"], found["instance"]
+
     def permutation_chunk_len(self) -> int:
         return self.degree() - 2
 

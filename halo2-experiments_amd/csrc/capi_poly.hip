@@ -371,6 +371,30 @@ int hm_fr_linear_combination_dev(const void* const* d_polys, const uint64_t* coe
   return fr_linear_combination_run(d_polys, coeffs, count, n, (uint32_t*)d_out, (hipStream_t)stream);
 } HM_API_CATCH("hm_fr_linear_combination_dev")
 
+int hm_shplonk_set_quotient_bn256_fr_dev(const void* const* d_polys, const uint64_t* weights, size_t m, size_t n, const uint64_t* points,
+                                         size_t t, const uint64_t scale[4], void* d_out, int accumulate, void* stream) try {
+  const char* who = "hm_shplonk_set_quotient_bn256_fr_dev";
+  if (!d_polys || !weights || !points || !scale || !d_out) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (m == 0) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": no polynomial");
+  if (t == 0 || t > (size_t)HM_SHPLONK_MAX_POINTS) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": need 1 <= t <= HM_SHPLONK_MAX_POINTS");
+  if (n < t + 1 || n > ((size_t)1 << 32)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": need t + 1 <= n <= 2^32");
+  if ((uintptr_t)d_out & 15) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the output is not 16-byte aligned");
+  for (size_t j = 0; j < m; ++j)
+    if (!d_polys[j] || ((uintptr_t)d_polys[j] & 15)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a null or misaligned polynomial");
+  for (size_t a = 0; a < t; ++a)
+    for (size_t b = a + 1; b < t; ++b)
+      if (host::fr_eq(host::fr_load(points + a * 4), host::fr_load(points + b * 4)))
+        return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": two equal points");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    count_vector(*ctx, HM_STAT_LINEAR_COMBINATION, 1, (uint64_t)m * n);
+    count_vector(*ctx, HM_STAT_KATE_DIVISION, t, (uint64_t)t * n);
+  }
+  return fr_shplonk_set_quotient_run(d_polys, weights, m, n, points, (uint32_t)t, scale, (uint32_t*)d_out, accumulate != 0, (hipStream_t)stream);
+} HM_API_CATCH("hm_shplonk_set_quotient_bn256_fr_dev")
+
 int hm_lookup_permute_bn256_fr_dev(const void* d_input, const void* d_table, size_t rows, void* d_permuted_input,
                                    void* d_permuted_table, void* stream) try {
   if (rows && (!d_input || !d_table || !d_permuted_input || !d_permuted_table))

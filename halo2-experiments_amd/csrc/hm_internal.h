@@ -411,6 +411,8 @@ int fr_eval_polynomial_run(DeviceCtx& ctx, const uint32_t* d_polys, uint64_t n, 
 // polyops.hip
 int fr_kate_division_run(DeviceCtx& ctx, const uint32_t* d_a, uint64_t n, const uint64_t z_ext[4], uint32_t* d_q, hipStream_t stream);
 int fr_grand_product_run(DeviceCtx& ctx, const uint32_t* d_m, uint64_t n, const uint64_t start_ext[4], uint32_t* d_out, hipStream_t stream);
+int fr_shplonk_set_quotient_run(const void* const* d_polys, const uint64_t* weights_ext, size_t m, uint64_t n, const uint64_t* points_ext,
+                                uint32_t t, const uint64_t scale_ext[4], uint32_t* d_out, bool accumulate, hipStream_t stream);
 int fr_kate_division_batch_run(DeviceCtx& ctx, const void* const* d_a, uint64_t n, const uint64_t* z_ext, void* const* d_q, size_t count,
                                hipStream_t stream);
 int fr_grand_product_batch_run(DeviceCtx& ctx, const void* const* d_m, uint64_t n, const uint64_t start_ext[4], uint64_t chain_row,

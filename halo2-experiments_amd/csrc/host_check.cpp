@@ -20,6 +20,7 @@ namespace hm {
 #include "g1_codec.inc"   // the per-point SRS codec formulas (its kernels are HIP-only)
 #include "poseidon.inc"   // the per-hash Poseidon / Merkle node functions (likewise)
 #include "keygen.inc"     // the permutation assembly's key packing and link rule (likewise)
+#include "shplonk.inc"    // the SHPLONK set quotient's plan, coefficients and row formula (likewise)
 }
 
 using namespace hm;
@@ -524,6 +525,45 @@ int hc_poseidon(int op, uint32_t width, const uint32_t* consts, uint32_t r_f, ui
     }
   }
   return 0;
+}
+
+// The SHPLONK set quotient (shplonk.inc), what of it runs without a GPU.
+//   hc_shplonk_plan: plan[0..2] = B, G, lanes and plan[3] = the scratch words of one point, for n rows.
+//   hc_shplonk_coefficients: d[l] = scale / prod_{l' != l} (pts[l] - pts[l']) (external words) -> 0; -1 when the set is refused
+//     (t out of range, two equal points, a word not below r).
+//   hc_shplonk_row_bounds: the row formula with t = SHQ_T_MAX terms, every quotient value DECLARED at its class maximum (< 3r), the
+//     coefficients at the class of a converted constant and the accumulated word at the raw 2^256 class -> 1 when the result is inside
+//     the class the canonical store expects; report[0] = its bound.  A violated precondition aborts.
+void hc_shplonk_plan(uint64_t n, uint64_t* plan) {
+  const ShqPlan p = shq_plan(n);
+  plan[0] = p.B, plan[1] = p.G, plan[2] = p.lanes, plan[3] = shq_scan_words(p);
+}
+int hc_shplonk_coefficients(uint32_t t, const uint64_t* pts_ext, const uint64_t* scale_ext, uint64_t* d_ext) {
+  if (t > (uint32_t)SHQ_T_MAX) return -1;
+  host::Fr4 pts[SHQ_T_MAX], d[SHQ_T_MAX];
+  for (uint32_t l = 0; l < t; ++l) pts[l] = host::fr_load(pts_ext + 4 * l);
+  if (!shq_coefficients(t, pts, host::fr_load(scale_ext), d)) return -1;
+  for (uint32_t l = 0; l < t; ++l) std::memcpy(d_ext + 4 * l, d[l].l, 32);
+  return 0;
+}
+int hc_shplonk_row_bounds(const uint64_t* a_ext, double* report) {
+  typedef Fe<FrParams> F;
+  uint32_t wa[8];
+  std::memcpy(wa, a_ext, 32);
+  F raw = fe_unpack<FrParams>(wa);                 // declared: any 256-bit word pattern; run at the largest one
+  raw.l[8] = (1u << 24) - 1;
+  for (int i = 0; i < 8; ++i) raw.l[i] = MASK29;
+  F q[SHQ_T_MAX], d[SHQ_T_MAX];
+  for (int l = 0; l < SHQ_T_MAX; ++l) {
+    q[l] = load_ext<FrParams>(a_ext);
+    force_bounds(q[l], 3.0);
+    d[l] = load_ext<FrParams>(a_ext);
+    force_bounds(d[l], 1.0);
+  }
+  const F row = shq_row<SHQ_T_MAX>(q, d, true, raw);
+  report[0] = row.vb;
+  (void)fe_canonical(row);
+  return row.vb <= 3.0 ? 1 : 0;
 }
 
 }  // extern "C"

@@ -423,6 +423,11 @@ __global__ __launch_bounds__(PO_THREADS) void fr_lincomb_kernel(LcArgs args, uin
 }
 
 // ---------------------------------------------------------------------------------------------
+// the SHPLONK set quotient: the plan, the coefficients and the kernels in shplonk.inc
+// ---------------------------------------------------------------------------------------------
+#include "shplonk.inc"
+
+// ---------------------------------------------------------------------------------------------
 // a[i] *= pattern[i mod P]: EvaluationDomain::divide_by_vanishing_poly (the inverse vanishing polynomial takes only
 // 2^(extended_k - k) values on the extended coset), P a power of two <= PP_MAX, the pattern by value
 // ---------------------------------------------------------------------------------------------
@@ -522,6 +527,60 @@ int fr_kate_division_run(DeviceCtx& ctx, const uint32_t* d_a, uint64_t n, const 
   const void* a = d_a;
   void* q = d_q;
   return fr_kate_division_batch_run(ctx, &a, n, z_ext, &q, 1, stream);
+}
+
+template <int T>
+static void shq_launch(const ShqPlan& p, const uint32_t* d_n, uint64_t n, const ShqArgs& args, const PoPoints& pts, uint32_t* incl,
+                       uint32_t* wg_total, uint32_t* carry, uint32_t* d_out, int accumulate, hipStream_t stream) {
+  hipLaunchKernelGGL(fr_shq_chunks_kernel<T>, dim3(p.G), dim3(PO_THREADS), 0, stream, d_n, n, args, p.B, incl, wg_total);
+  hipLaunchKernelGGL(fr_kate_join_kernel, dim3(T), dim3(PO_THREADS), 0, stream, (const uint32_t*)wg_total, p.G, pts, p.B, carry);
+  hipLaunchKernelGGL(fr_shq_replay_kernel<T>, dim3(p.G), dim3(PO_THREADS), 0, stream, d_n, n, args, p.B, (const uint32_t*)incl,
+                     (const uint32_t*)carry, d_out, accumulate);
+}
+
+// d_out (+)= scale * (N - R) / Z_S for N = sum_j weights[j] * d_polys[j] (shplonk.inc).  The route: N is first combined into
+// stream-ordered scratch by fr_linear_combination_run (LC_MAX terms per launch, any m), then scanned for all t points at once, the
+// joins of the t points by fr_kate_join_kernel as t columns.  The arguments were validated by the caller (capi_poly.hip) except for the
+// points themselves: two equal ones are refused here, before anything is launched.
+int fr_shplonk_set_quotient_run(const void* const* d_polys, const uint64_t* weights_ext, size_t m, uint64_t n, const uint64_t* points_ext,
+                                uint32_t t, const uint64_t scale_ext[4], uint32_t* d_out, bool accumulate, hipStream_t stream) {
+  host::Fr4 pts4[SHQ_T_MAX], d4[SHQ_T_MAX];
+  if (t == 0 || t > (uint32_t)SHQ_T_MAX) return hm_fail(HM_ERR_BAD_ARG, "shplonk_set_quotient: need 1 <= t <= 4 points");
+  for (uint32_t l = 0; l < t; ++l) pts4[l] = host::fr_load(points_ext + (size_t)l * 4);
+  if (!shq_coefficients(t, pts4, host::fr_load(scale_ext), d4))
+    return hm_fail(HM_ERR_BAD_ARG, "shplonk_set_quotient: two equal points, or a point or the scale is not canonical");
+  const ShqPlan p = shq_plan(n);
+  if (p.G > PO_THREADS) return hm_fail(HM_ERR_INTERNAL, "shplonk_set_quotient: plan exceeds one joining workgroup");
+  ShqArgs args;
+  PoPoints pts;
+  std::memset(&args, 0, sizeof args);
+  std::memset(&pts, 0, sizeof pts);
+  for (uint32_t l = 0; l < t; ++l) {
+    host::fr_to_internal9(pts4[l], args.z[l].l);
+    host::fr_to_internal9(d4[l], args.d[l].l);
+    pts.z[l] = args.z[l];
+  }
+  const size_t n_bytes = (size_t)n * 32, per_point = (size_t)shq_scan_words(p);
+  void* ws = nullptr;
+  HM_HIP_CHECK(hipMallocAsync(&ws, n_bytes + (size_t)t * per_point * sizeof(uint32_t), stream));
+  uint32_t* d_n = (uint32_t*)ws;
+  uint32_t* incl = (uint32_t*)((uint8_t*)ws + n_bytes);
+  uint32_t* wg_total = incl + (size_t)t * ((size_t)p.G * PO_THREADS + 1) * 9;
+  uint32_t* carry = wg_total + (size_t)t * p.G * 9;
+  int rc = fr_linear_combination_run(d_polys, weights_ext, m, n, d_n, stream);
+  if (rc == HM_OK) {
+    const int acc = accumulate ? 1 : 0;
+    switch (t) {
+      case 1: shq_launch<1>(p, d_n, n, args, pts, incl, wg_total, carry, d_out, acc, stream); break;
+      case 2: shq_launch<2>(p, d_n, n, args, pts, incl, wg_total, carry, d_out, acc, stream); break;
+      case 3: shq_launch<3>(p, d_n, n, args, pts, incl, wg_total, carry, d_out, acc, stream); break;
+      default: shq_launch<4>(p, d_n, n, args, pts, incl, wg_total, carry, d_out, acc, stream); break;
+    }
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("shplonk_set_quotient: ") + hipGetErrorString(e));
+  }
+  const hipError_t fe = hipFreeAsync(ws, stream);
+  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("shplonk_set_quotient: hipFreeAsync: ") + hipGetErrorString(fe));
+  return rc;
 }
 
 // `count` running products over n rows; chain_row >= n: every column starts from `start`; chain_row < n: column j + 1 starts

@@ -5,7 +5,7 @@ cells into the sigma columns.  The fixed columns, ``l0`` / ``l_last`` / ``l_acti
 from the ``EvaluationDomain`` calls, the commitments from the batch MSM.  Everything a key holds is a device tensor except the
 commitments.  ``synthesis.permutation_cells`` / ``permutation_columns`` are the CPU twins the tests compare against.
 
-Not here: the transcript representation, selector compression, ``verify_proof``."""
+Not here: selector compression.  ``create_proof`` / ``verify_proof``: ``prover`` / ``verifier`` (section 17)."""
 from __future__ import annotations
 
 import ctypes

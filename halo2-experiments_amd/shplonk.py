@@ -1,0 +1,271 @@
+"""The SHPLONK multiopen of ``halo2_proofs::poly::kzg::multiopen`` (``ProverSHPLONK`` / ``VerifierSHPLONK``; RECALLED from upstream
+tag v2023_02_02, not pinned against its bytes): the rotation sets, the prover on the GPU and the verifier on host integers.
+
+  - ``construct_intermediate_sets``: every commitment's set of points (ordered as integers, upstream's ``BTreeSet<F>``), the distinct
+    sets in order of first appearance with their commitments in order of first appearance, and the super point set (RECALLED).
+  - prover: y, v are squeezed; per set i the device adds v^i * (sum_j y^j P_ij - R_i) / Z_i to h through ONE call of
+    ``hm_shplonk_set_quotient_bn256_fr_dev`` (csrc/shplonk.inc); h is committed, u squeezed; one more call with t = 1 divides
+    sum_i v^i Z_{T \\ S_i}(u) sum_j y^j P_ij - Z_T(u) h by (X - u) and scales by 1 / Z_{T \\ S_0}(u), upstream's normalisation; the
+    result is committed.  The constants R_i(u) of upstream's linearisation do not enter: kate_division drops a constant (RECALLED order of
+    the transcript: y, v, [h], u, [h']).
+  - verifier: the same sets from the claimed evaluations; L = [h'], R = sum_i v^i z_i (sum_j y^j C_ij - r_i G) - Z_T(u) / z_0' [h]
+    + u [h'], with z_i normalised as upstream does, and the final check is e(L, [s]G2) = e(R, G2).
+
+``set_quotient_ints`` is the integer twin of the kernel, stated the long way (interpolate, subtract, divide point by point);
+``set_quotient_kate_ints`` is the identity the kernel computes by.  They play the role ``assign_ints`` plays for the witnesses."""
+from __future__ import annotations
+
+import ctypes
+from typing import Hashable, List, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+from .arithmetic import FQ_MODULUS, _is_tensor, _ptr, _stream_ptr, _tensor_rows
+from .domain import FR_MODULUS, fr_words
+from .pairing import G1_GEN, g1_msm
+
+R = FR_MODULUS
+MAX_POINTS = 4                      # HM_SHPLONK_MAX_POINTS
+_LANES_MAX, _THREADS = 65536, 256
+
+
+# ---- integers ---------------------------------------------------------------------------------------------------------------------------
+def kate_ints(a: Sequence[int], z: int) -> List[int]:
+    """``kate_division``: the quotient of a(X) - a(z) by X - z, len(a) - 1 coefficients"""
+    q, acc = [0] * (len(a) - 1), 0
+    for i in range(len(a) - 1, 0, -1):
+        acc = (a[i] + z * acc) % R
+        q[i - 1] = acc
+    return q
+
+
+def eval_ints(a: Sequence[int], x: int) -> int:
+    acc = 0
+    for c in reversed(a):
+        acc = (acc * x + c) % R
+    return acc
+
+
+def lagrange_interpolate_ints(points: Sequence[int], evals: Sequence[int]) -> List[int]:
+    """the coefficients of the polynomial of degree < t through (points[l], evals[l])"""
+    t = len(points)
+    out = [0] * t
+    for l in range(t):
+        num, den = [1], 1
+        for k in range(t):
+            if k == l:
+                continue
+            num = [(a - points[k] * b) % R for a, b in zip([0] + num, num + [0])]
+            den = den * (points[l] - points[k]) % R
+        c = evals[l] * pow(den, -1, R) % R
+        for i, a in enumerate(num):
+            out[i] = (out[i] + c * a) % R
+    return out
+
+
+def vanishing_eval(points, x: int) -> int:
+    acc = 1
+    for p in points:
+        acc = acc * (x - p) % R
+    return acc
+
+
+def _check_points(points) -> List[int]:
+    pts = [int(p) % R for p in points]
+    if not 1 <= len(pts) <= MAX_POINTS:
+        raise ValueError(f"set quotient: need 1 <= t <= {MAX_POINTS} points")
+    if len(set(pts)) != len(pts):
+        raise ValueError("set quotient: two equal points")
+    return pts
+
+
+def _combine_ints(polys, weights, n):
+    if not polys or len(polys) != len(weights):
+        raise ValueError("set quotient: one weight per polynomial, at least one polynomial")
+    return [sum(w * p[i] for w, p in zip(weights, polys)) % R for i in range(n)]
+
+
+def set_quotient_ints(polys, weights, points, scale: int = 1) -> List[int]:
+    """scale * (N - R) / Z_S for N = sum_j weights[j] polys[j], as n coefficients (the top t are zero): upstream's chain --
+    interpolate R over the points from N's evaluations, subtract, divide by (X - p) point after point."""
+    pts = _check_points(points)
+    n = len(polys[0])
+    if n < len(pts) + 1:
+        raise ValueError("set quotient: need n >= t + 1")
+    num = _combine_ints(polys, weights, n)
+    r = lagrange_interpolate_ints(pts, [eval_ints(num, p) for p in pts])
+    for i, c in enumerate(r):
+        num[i] = (num[i] - c) % R
+    for p in pts:
+        assert eval_ints(num, p) == 0
+        num = kate_ints(num, p)
+    return [scale * c % R for c in num] + [0] * len(pts)
+
+
+def set_quotient_coefficients(points, scale: int = 1) -> List[int]:
+    """d_l = scale / prod_{l' != l} (p_l - p_l'): the partial fractions of scale / Z_S (csrc/shplonk.inc: shq_coefficients)"""
+    pts = _check_points(points)
+    out = []
+    for l, p in enumerate(pts):
+        den = 1
+        for k, q in enumerate(pts):
+            if k != l:
+                den = den * (p - q) % R
+        out.append(scale * pow(den, -1, R) % R)
+    return out
+
+
+def set_quotient_kate_ints(polys, weights, points, scale: int = 1) -> List[int]:
+    """the same n coefficients by the identity the kernel uses: sum_l d_l * kate(N, p_l)"""
+    n = len(polys[0])
+    d = set_quotient_coefficients(points, scale)
+    num = _combine_ints(polys, weights, n)
+    qs = [kate_ints(num, int(p) % R) for p in points]
+    return [sum(dl * q[i] for dl, q in zip(d, qs)) % R for i in range(n - 1)] + [0]
+
+
+def set_quotient_plan(n: int) -> Tuple[int, int, int]:
+    """(B, G, lanes) of the kernel's scans for n rows (csrc/shplonk.inc: shq_plan): a lane owns B consecutive rows, a workgroup 256
+    lanes.  n <= 4 B is one lane; the last chunk is ragged when B does not divide n; n > 256 B needs a second workgroup."""
+    b = -(-n // _LANES_MAX)
+    if b < 4:
+        b = 4 if n >= 4 else 1
+    lanes = -(-n // b)
+    return b, -(-lanes // _THREADS), lanes
+
+
+# ---- the rotation sets ------------------------------------------------------------------------------------------------------------------
+def construct_intermediate_sets(queries):
+    """``queries``: (commitment key, point, eval) triples in the order the prover / verifier lists them.  Returns
+    (rotation_sets, super_point_set): rotation_sets = [(points, [(key, evals)])] with the points of a set in ascending integer order,
+    the evals of a commitment in its points' order, the sets and the commitments in order of first appearance; the super point set as
+    an ascending list."""
+    queries = [(key, int(pt) % R, ev) for key, pt, ev in queries]
+    by_key: dict = {}
+    evals: dict = {}
+    for key, pt, ev in queries:
+        by_key.setdefault(key, set()).add(pt)
+        evals.setdefault((key, pt), ev)                # upstream's get_eval finds the first matching query
+    sets: List[Tuple[tuple, list]] = []
+    for key, pts in by_key.items():                    # dicts keep insertion order: first appearance
+        pts_t = tuple(sorted(pts))
+        for have, keys in sets:
+            if have == pts_t:
+                keys.append(key)
+                break
+        else:
+            sets.append((pts_t, [key]))
+    rotation_sets = [(list(pts), [(key, [evals[(key, p)] for p in pts]) for key in keys]) for pts, keys in sets]
+    return rotation_sets, sorted({pt for _, pt, _ in queries})
+
+
+# ---- the device entry -------------------------------------------------------------------------------------------------------------------
+def _words(values) -> np.ndarray:
+    return np.ascontiguousarray(np.stack([fr_words(int(v) % R) for v in values]))
+
+
+def set_quotient(polys, weights, points, scale: int = 1, out=None, accumulate: bool = False):
+    """``out (+)= scale * (sum_j weights[j] polys[j] - R) / prod_l (X - points[l])`` on the device, one call of
+    ``hm_shplonk_set_quotient_bn256_fr_dev``: ``polys`` a list of (n, 4) GPU tensors, ``weights`` / ``points`` / ``scale`` integers.
+    Rows at and above n - t come out zero (left alone when accumulating).  Returns ``out`` (a new tensor when None)."""
+    import torch
+
+    polys = list(polys)
+    if not polys:
+        raise ValueError("set_quotient: no polynomial")
+    if len(weights) != len(polys):
+        raise ValueError("set_quotient: one weight per polynomial")
+    pts = _check_points(points)
+    n = _tensor_rows(polys[0], 4, "polys") if _is_tensor(polys[0]) else -1
+    for p in polys:
+        if not _is_tensor(p) or _tensor_rows(p, 4, "polys") != n:
+            raise ValueError("set_quotient: polynomials must be GPU tensors of one length")
+    if n < len(pts) + 1:
+        raise ValueError("set_quotient: need n >= t + 1")
+    if out is None:
+        if accumulate:
+            raise ValueError("set_quotient: nothing to accumulate into")
+        out = torch.empty((n, 4), dtype=torch.int64, device=polys[0].device)
+    elif not _is_tensor(out) or _tensor_rows(out, 4, "out") != n:
+        raise ValueError("set_quotient: out differs in length")
+    ptrs = (ctypes.c_void_p * len(polys))(*[p.data_ptr() for p in polys])
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.load().hm_shplonk_set_quotient_bn256_fr_dev(ptrs, _ptr(_words(weights)), len(polys), n, _ptr(_words(pts)), len(pts),
+                                                                    _ptr(fr_words(int(scale) % R)), ctypes.c_void_p(out.data_ptr()),
+                                                                    1 if accumulate else 0, ctypes.c_void_p(_stream_ptr(out))))
+    return out
+
+
+# ---- prover and verifier ----------------------------------------------------------------------------------------------------------------
+_FQ_RINV = pow(1 << 256, -1, FQ_MODULUS)
+
+
+def g1_words_to_int(words):
+    """(x, y) integers of 12 (or 8) Montgomery words of a normalised G1; None for the identity (all-zero z, or (0, 0))"""
+    w = [int(v) for v in np.asarray(words, dtype=np.uint64).reshape(-1)]
+    if len(w) == 12 and not any(w[8:]):
+        return None
+    x, y = (sum(w[4 * c + i] << (64 * i) for i in range(4)) * _FQ_RINV % FQ_MODULUS for c in range(2))
+    return None if (x, y) == (0, 0) else (x, y)
+
+
+def _powers(base: int, count: int) -> List[int]:
+    out, acc = [], 1
+    for _ in range(count):
+        out.append(acc)
+        acc = acc * base % R
+    return out
+
+
+def create_opening(params, transcript, queries, polys: dict) -> None:
+    """``ProverSHPLONK::create_proof``.  ``queries``: (key, point, eval) triples; ``polys[key]``: the (n, 4) coefficient tensor on the GPU
+    that ``key`` commits.  Writes [h] and [h'] to ``transcript``."""
+    y = transcript.squeeze_challenge()
+    v = transcript.squeeze_challenge()
+    rotation_sets, super_points = construct_intermediate_sets(queries)
+    h = None
+    for i, (pts, members) in enumerate(rotation_sets):
+        cols = [polys[key] for key, _ in members]
+        h = set_quotient(cols, _powers(y, len(cols)), pts, scale=pow(v, i, R), out=h, accumulate=i > 0)
+    transcript.write_point(g1_words_to_int(params.commit(h)))
+    u = transcript.squeeze_challenge()
+    zt = vanishing_eval(super_points, u)
+    cols, weights, z0 = [], [], None
+    for i, (pts, members) in enumerate(rotation_sets):
+        z_i = vanishing_eval([p for p in super_points if p not in pts], u)
+        z0 = z_i if i == 0 else z0
+        for j, (key, _) in enumerate(members):
+            cols.append(polys[key])
+            weights.append(pow(v, i, R) * z_i % R * pow(y, j, R) % R)
+    final = set_quotient(cols + [h], weights + [-zt % R], [u], scale=pow(z0, -1, R))
+    transcript.write_point(g1_words_to_int(params.commit(final)))
+
+
+def verify_opening(transcript, queries, commitments: dict):
+    """``VerifierSHPLONK::verify_proof`` up to the pairing: reads [h] and [h'] and returns the two G1 points (L, R) with
+    e(L, [s]G2) = e(R, G2) for a valid opening -- equivalently s * L == R.  ``commitments[key]``: the (x, y) point of ``key``.  Host integers only."""
+    y = transcript.squeeze_challenge()
+    v = transcript.squeeze_challenge()
+    h1 = transcript.read_point()
+    u = transcript.squeeze_challenge()
+    h2 = transcript.read_point()
+    rotation_sets, super_points = construct_intermediate_sets(queries)
+    zt = vanishing_eval(super_points, u)
+    scalars, points, r_outer, z0_inv = [], [], 0, None
+    for i, (pts, members) in enumerate(rotation_sets):
+        z_i = vanishing_eval([p for p in super_points if p not in pts], u)
+        if i == 0:
+            z0_inv, z_i = pow(z_i, -1, R), 1
+        else:
+            z_i = z_i * z0_inv % R
+        outer = pow(v, i, R) * z_i % R
+        for j, (key, evals) in enumerate(members):
+            yj = pow(y, j, R)
+            r_eval = eval_ints(lagrange_interpolate_ints(pts, evals), u)
+            scalars.append(outer * yj % R)
+            points.append(commitments[key])
+            r_outer = (r_outer + outer * yj % R * r_eval) % R
+    scalars += [-r_outer % R, -z0_inv * zt % R, u]
+    points += [G1_GEN, h1, h2]
+    return h2, g1_msm(scalars, points)

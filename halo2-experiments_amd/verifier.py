@@ -1,0 +1,218 @@
+"""``verify_proof`` of ``halo2_proofs::plonk`` over KZG with the SHPLONK multiopen, on host integers alone: it needs no GPU.  It shares
+the transcript and the constraint system with ``prover`` and nothing else: the proof is read through ``Blake2bRead`` in the order the
+prover wrote it (RECALLED from upstream, see ``prover``), the gate, permutation and lookup expressions are evaluated at x by a small
+recursive evaluator over ``evaluation.Expression``, the quotient identity fixes h(x), and ``shplonk.verify_opening`` leaves two G1 points
+L, R with e(L, [s]G2) = e(R, G2) -- checked by ``pairing.pairing_check`` against the parameters' G2 points, or, when the caller knows
+the trapdoor s (tests), by s * L == R in G1."""
+from __future__ import annotations
+
+import hashlib
+import struct
+
+from . import evaluation as ev
+from .domain import FR_MODULUS
+from .keygen import FR_DELTA, VerifyingKey
+from .kzg import g2_from_bytes
+from .pairing import g1_add, g1_mul, g1_neg, g1_on_curve, pairing_check
+from .shplonk import g1_words_to_int, verify_opening
+from .transcript import Blake2bRead, TranscriptError
+
+R = FR_MODULUS
+
+
+def _vk_digest(vk: VerifyingKey) -> int:
+    """``prover.vk_digest``, stated again: the verifier imports nothing from the prover"""
+    cs = vk.cs
+    hsh = hashlib.blake2b(digest_size=64, person=b"Halo2-Verify-Key")
+    hsh.update(struct.pack("<5I", vk.domain.k, cs.num_fixed, cs.num_advice, cs.num_instance, len(cs.equality)))
+    for kind, index in cs.equality:
+        hsh.update(kind.encode() + struct.pack("<I", index))
+    for com in list(vk.fixed_commitments) + list(vk.permutation_commitments):
+        p = g1_words_to_int(com)
+        hsh.update(bytes(64) if p is None else p[0].to_bytes(32, "little") + p[1].to_bytes(32, "little"))
+    return int.from_bytes(hsh.digest(), "little") % R
+
+
+def proof_length(cs) -> int:
+    """the bytes of a proof of ``cs``, counted from the constraint system: 32 per point and per scalar"""
+    adv_q, fix_q, _ = cs.queries()
+    P, nsets, L = len(cs.equality), cs.permutation_sets(), len(cs.lookups)
+    points = cs.num_advice + 2 * L + nsets + L + 1 + (cs.degree() - 1) + 2
+    scalars = len(adv_q) + len(fix_q) + 1 + P + (3 * nsets - 1 if nsets else 0) + 5 * L
+    return 32 * (points + scalars)
+
+
+def evaluate_expression(e, leaf, scalars) -> int:
+    """e at one point: ``leaf(kind, column, rotation)`` gives the columns' evaluations, ``scalars`` beta / gamma / theta"""
+    if isinstance(e, ev.Constant):
+        return e.value % R
+    if isinstance(e, ev.Fixed):
+        return leaf("fixed", e.column, e.rotation)
+    if isinstance(e, ev.Advice):
+        return leaf("advice", e.column, e.rotation)
+    if isinstance(e, ev.Instance):
+        return leaf("instance", e.column, e.rotation)
+    if isinstance(e, ev.ProofScalar):
+        return scalars[e.name]
+    if isinstance(e, ev.Negated):
+        return -evaluate_expression(e.a, leaf, scalars) % R
+    if isinstance(e, ev.Sum):
+        return (evaluate_expression(e.a, leaf, scalars) + evaluate_expression(e.b, leaf, scalars)) % R
+    if isinstance(e, ev.Product):
+        return evaluate_expression(e.a, leaf, scalars) * evaluate_expression(e.b, leaf, scalars) % R
+    if isinstance(e, ev.Scaled):
+        return evaluate_expression(e.a, leaf, scalars) * e.factor % R
+    raise ValueError(f"verify_proof: no value for {type(e).__name__}")
+
+
+def _instance_columns(cs, instance):
+    single = len(instance) > 0 and isinstance(instance[0], int)
+    cols = [list(instance)] if single else [list(c) for c in instance]
+    if len(cols) != cs.num_instance:
+        raise ValueError(f"instance: {cs.num_instance} column(s) expected")
+    return [[int(v) % R for v in c] for c in cols]
+
+
+def verify_proof(params, vk: VerifyingKey, instance, proof: bytes, trapdoor: int = None) -> bool:
+    """True when ``proof`` is a valid proof of ``vk``'s circuit for ``instance`` (a list of integers for a one-column system, or one
+    list per instance column).  ``params`` needs ``g2`` / ``s_g2`` only.  A malformed proof -- short or long, a point off the curve, a
+    scalar not below r -- is False, not an exception."""
+    try:
+        return _verify(params, vk, instance, proof, trapdoor)
+    except TranscriptError:
+        return False
+
+
+def _verify(params, vk, instance, proof, trapdoor) -> bool:
+    cs, dom = vk.cs, vk.domain
+    n, omega, blinding = 1 << dom.k, dom.omega, cs.blinding_factors
+    P, chunk, nsets, L = len(cs.equality), cs.permutation_chunk_len(), cs.permutation_sets(), len(cs.lookups)
+    deg, last = cs.degree(), -(blinding + 1)
+    if len(proof) != proof_length(cs):
+        return False
+    inst_cols = _instance_columns(cs, instance)
+    t = Blake2bRead(proof)
+    t.common_scalar(_vk_digest(vk))
+    for values in inst_cols:
+        for v in values:
+            t.common_scalar(v)
+    com = {}
+    for c in range(cs.num_advice):
+        com[("advice", c)] = t.read_point()
+    theta = t.squeeze_challenge()
+    for j in range(L):
+        com[("lookup_a", j)] = t.read_point()
+        com[("lookup_s", j)] = t.read_point()
+    beta = t.squeeze_challenge()
+    gamma = t.squeeze_challenge()
+    for i in range(nsets):
+        com[("perm_z", i)] = t.read_point()
+    for j in range(L):
+        com[("lookup_z", j)] = t.read_point()
+    com[("random",)] = t.read_point()
+    y = t.squeeze_challenge()
+    h_pieces = [t.read_point() for _ in range(deg - 1)]
+    x = t.squeeze_challenge()
+    rot = lambda r: x * pow(omega, r, R) % R
+
+    adv_q, fix_q, inst_q = cs.queries()
+    evals = {}
+    for c, r in adv_q:
+        evals[(("advice", c), rot(r))] = t.read_scalar()
+    for c, r in fix_q:
+        evals[(("fixed", c), rot(r))] = t.read_scalar()
+    evals[(("random",), x)] = t.read_scalar()
+    for j in range(P):
+        evals[(("sigma", j), x)] = t.read_scalar()
+    for i in range(nsets):
+        for r in (0, 1) + ((last,) if i + 1 < nsets else ()):
+            evals[(("perm_z", i), rot(r))] = t.read_scalar()
+    for j in range(L):
+        for key, r in ((("lookup_z", j), 0), (("lookup_z", j), 1), (("lookup_a", j), 0), (("lookup_a", j), -1), (("lookup_s", j), 0)):
+            evals[(key, rot(r))] = t.read_scalar()
+
+    # ---- the Lagrange values the arguments and the instance columns need ---------------------------------------------------------------------
+    xn = pow(x, n, R)
+    n_inv = pow(n, -1, R)
+
+    def lagrange_at(i: int, point: int) -> int:          # l_i(point) = omega^i (point^n - 1) / (n (point - omega^i))
+        w = pow(omega, i, R)
+        if point == w:
+            return 1
+        return w * (pow(point, n, R) - 1) % R * n_inv % R * pow(point - w, -1, R) % R
+
+    l0 = lagrange_at(0, x)
+    l_last = lagrange_at(n - blinding - 1, x)
+    l_blind = sum(lagrange_at(i, x) for i in range(n - blinding, n)) % R
+    l_active = (1 - l_last - l_blind) % R
+
+    def instance_eval(c: int, r: int) -> int:
+        pt = rot(r)
+        return sum(v * lagrange_at(i, pt) for i, v in enumerate(inst_cols[c]) if v) % R
+
+    # ---- h(x) from the identity: the expressions in the prover's order, folded in y ---------------------------------------------------------------
+    nf = cs.num_fixed
+    sigma0, z0 = nf, nf + P
+    i_l0, i_last, i_active, i_x, lookup0 = z0 + nsets, z0 + nsets + 1, z0 + nsets + 2, z0 + nsets + 3, z0 + nsets + 4
+    special = {i_l0: l0, i_last: l_last, i_active: l_active, i_x: x}
+
+    def leaf(kind: str, column: int, r: int) -> int:
+        if kind == "instance":
+            return instance_eval(column, r)
+        if kind == "advice":
+            return evals[(("advice", column), rot(r))]
+        if column < nf:
+            return evals[(("fixed", column), rot(r))]
+        if column in special:
+            return special[column]
+        if column < z0:
+            return evals[(("sigma", column - sigma0), rot(r))]
+        if column < i_l0:
+            return evals[(("perm_z", column - z0), rot(r))]
+        j, part = divmod(column - lookup0, 3)
+        return evals[((("lookup_z", "lookup_a", "lookup_s")[part], j), rot(r))]
+
+    F = ev.Fixed
+    kind = {"advice": ev.Advice, "fixed": ev.Fixed, "instance": ev.Instance}
+    exprs = list(cs.polynomials())
+    exprs += ev.permutation_expressions([kind[kd](i) for kd, i in cs.equality], [F(sigma0 + j) for j in range(P)],
+                                        [lambda r, i=i: F(z0 + i, r) for i in range(nsets)], F(i_l0), F(i_last), F(i_active), F(i_x), chunk,
+                                        FR_DELTA, last)
+    for j, (ins, tabs) in enumerate(cs.lookups):
+        b = lookup0 + 3 * j
+        exprs += ev.lookup_expressions(ins, tabs, lambda r, b=b: F(b, r), lambda r, b=b: F(b + 1, r), lambda r, b=b: F(b + 2, r), F(i_l0),
+                                       F(i_last), F(i_active))
+    scalars = {"Beta": beta, "Gamma": gamma, "Theta": theta}
+    acc = 0
+    for e in exprs:
+        acc = (acc * y + evaluate_expression(e, leaf, scalars)) % R
+    if xn == 1:
+        return False
+    hx = acc * pow(xn - 1, -1, R) % R
+    h_com = None
+    for piece in reversed(h_pieces):                       # sum_i x^(n i) [h_i]
+        h_com = g1_add(g1_mul(xn, h_com) if h_com is not None else None, piece)
+    com[("h",)] = h_com
+    for c, point in enumerate(vk.fixed_commitments):
+        com[("fixed", c)] = g1_words_to_int(point)
+    for j, point in enumerate(vk.permutation_commitments):
+        com[("sigma", j)] = g1_words_to_int(point)
+
+    # ---- the multiopen --------------------------------------------------------------------------------------------------------------------------------
+    q = lambda key, pt: (key, pt, evals[(key, pt)])
+    queries = [q(("advice", c), rot(r)) for c, r in adv_q]
+    queries += [qq for i in range(nsets) for qq in (q(("perm_z", i), x), q(("perm_z", i), rot(1)))]
+    queries += [q(("perm_z", i), rot(last)) for i in reversed(range(nsets - 1))]
+    for j in range(L):
+        queries += [q(("lookup_z", j), x), q(("lookup_a", j), x), q(("lookup_s", j), x), q(("lookup_a", j), rot(-1)), q(("lookup_z", j), rot(1))]
+    queries += [q(("fixed", c), rot(r)) for c, r in fix_q] + [q(("sigma", j), x) for j in range(P)]
+    queries += [(("h",), x, hx), q(("random",), x)]
+    if any(com[key] is None for key, _, _ in queries):
+        return False                                         # the identity cannot be absorbed or opened
+    left, right = verify_opening(t, queries, com)
+    if t.remaining():
+        return False
+    if trapdoor is not None:
+        return g1_mul(trapdoor, left) == right
+    g2, s_g2 = g2_from_bytes(params.g2), g2_from_bytes(params.s_g2)
+    return g1_on_curve(left) and pairing_check([(left, s_g2), (g1_neg(right), g2)])

@@ -5,7 +5,7 @@ Host-side mirror of ``halo2_proofs::arithmetic`` (``best_multiexp``, ``best_fft`
 
 The sources live in ``halo2-experiments_amd/`` (the directory name the project layout prescribes; not a valid
 Python identifier): this package is the importable name, and its ``__path__`` points there, so every submodule
-(``_lib``, ``arithmetic``, ``domain``, ``keygen``, ``kzg``, ``poseidon``, ``replay``, ``sharding``, ``synthesis``) is an ordinary module of this package
+(``_lib``, ``arithmetic``, ``domain``, ``keygen``, ``kzg``, ``pairing``, ``poseidon``, ``prover``, ``replay``, ``sharding``, ``shplonk``, ``synthesis``, ``transcript``, ``verifier``) is an ordinary module of this package
 with an ordinary ``__spec__`` / ``__file__``.
 """
 import os as _os
@@ -22,10 +22,15 @@ from .arithmetic import (bases_info, batch_invert, best_fft, best_multiexp, best
 from .domain import EvaluationDomain  # noqa: F401
 from .keygen import (ProvingKey, VerifyingKey, copy_pairs, keygen_pk, keygen_vk, permutation_cells_dev,  # noqa: F401
                      permutation_columns_dev)
+from .pairing import pairing_check  # noqa: F401
 from .poseidon import MerkleSumTree, MerkleTree, Spec, poseidon_hash, poseidon_hash_host, update_plan  # noqa: F401
+from .prover import create_proof  # noqa: F401
+from .shplonk import construct_intermediate_sets, set_quotient, set_quotient_ints  # noqa: F401
 from .synthesis import (MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, merkle_sum_witness,  # noqa: F401
                         merkle_sum_witness_host, merkle_witness, merkle_witness_host, permutation_columns, poseidon_circuit_witness,
                         poseidon_circuit_witness_host)
+from .transcript import Blake2bRead, Blake2bWrite  # noqa: F401
+from .verifier import verify_proof  # noqa: F401
 
 __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_multiexp_submit", "best_multiexp_wait", "best_fft",
            "register_bases", "release_bases", "bases_info", "g1_fixed_base_mul", "g1_fft", "g1_fft_host", "g1_compress", "g1_compress_host",
@@ -35,4 +40,6 @@ __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_mult
            "Spec", "poseidon_hash", "poseidon_hash_host", "update_plan", "MerkleSumTree", "MerkleTree", "MerkleSumTreeLayout", "merkle_sum_witness",
            "merkle_sum_witness_host", "permutation_columns", "MerkleTreeV3Layout", "PoseidonCircuitLayout", "merkle_witness",
            "merkle_witness_host", "poseidon_circuit_witness", "poseidon_circuit_witness_host", "copy_pairs", "permutation_cells_dev",
-           "permutation_columns_dev", "keygen_vk", "keygen_pk", "VerifyingKey", "ProvingKey"]
+           "permutation_columns_dev", "keygen_vk", "keygen_pk", "VerifyingKey", "ProvingKey",
+           "create_proof", "verify_proof", "Blake2bWrite", "Blake2bRead", "pairing_check", "construct_intermediate_sets",
+           "set_quotient", "set_quotient_ints"]

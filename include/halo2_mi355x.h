@@ -358,6 +358,23 @@ int hm_fr_batch_invert_dev(void* d_values, size_t n, void* stream);
 int hm_fr_linear_combination_dev(const void* const* d_polys, const uint64_t* coeffs, size_t count, size_t n, void* d_out,
                                  void* stream);
 
+/* The set quotient of the SHPLONK multiopen (upstream poly/kzg/multiopen/shplonk/prover.rs): for one rotation set with the
+ * t distinct points `points` and N(X) = sum_{j < m} weights[j] * d_polys[j](X),
+ *     d_out[i] (+)= scale * ((N - R) / prod_l (X - points[l]))[i]   for i < n - t,     deg R < t, R(points[l]) = N(points[l]),
+ * the same words upstream's interpolate / subtract / divide chain gives.  It is computed as sum_l c_l * kate_division(N,
+ * points[l]) with c_l = 1 / prod_{l' != l} (points[l] - points[l']): t scans over one read of N, no R, no evaluation.  t = 1 is
+ * scale * kate_division(N, points[0]), the multiopen's final quotient.
+ *   d_polys: host array of m device pointers (n x 4 u64 each, 16-byte aligned, canonical); weights: host, m x 4 u64; points:
+ *   host, t x 4 u64; scale: host, 4 u64 (all canonical Montgomery words); d_out: n x 4 u64 on the device.
+ *   accumulate = 0: rows [0, n - t) are written and rows [n - t, n) are written as zero;  != 0: the quotient is added to rows
+ *   [0, n - t) and the rows above (to which it adds zero) are left alone.  d_out may be one of d_polys.
+ * HM_ERR_BAD_ARG, with d_out untouched: a null or misaligned pointer, m = 0, t = 0, t > HM_SHPLONK_MAX_POINTS, n < t + 1, two
+ * equal points, a point or the scale not below r.  Scratch (N and the scans' carries) is allocated and freed in stream order;
+ * nothing is read back.  Asynchronous on `stream`. */
+#define HM_SHPLONK_MAX_POINTS 4
+int hm_shplonk_set_quotient_bn256_fr_dev(const void* const* d_polys, const uint64_t* weights, size_t m, size_t n, const uint64_t* points,
+                                         size_t t, const uint64_t scale[4], void* d_out, int accumulate, void* stream);
+
 /* The permuted columns of one lookup argument (upstream plonk/lookup/prover.rs: permute_expression_pair): from the first
  * `rows` (= usable rows) entries of the compressed input and table columns, d_permuted_input[0 .. rows) = the input values
  * sorted by their canonical integers, d_permuted_table[0 .. rows) = the table values arranged so that every row where the

@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""create_proof / verify_proof end to end and the SHPLONK multiopen alone, on one MI355X.
+
+(a) MerkleSumTree depth 5 / k = 9 (the reference's test_full_prover) and depth 20 / k = 10: ParamsKZG.setup, keygen, a GPU witness,
+    then create_proof and verify_proof (pairing route) wall-clock, with the time inside shplonk.create_opening split out.
+(b) the multiopen of the k = 18 MerkleSumTree shape (the rotation sets of that constraint system, random polynomials): the route of
+    hm_shplonk_set_quotient_bn256_fr_dev -- one call per rotation set into h, one for the final quotient -- against the same two
+    polynomials composed from the kernels that existed before it: linear_combination, eval_polynomial, host interpolation, one
+    kate_division per point.  The results are compared word for word; the commitments are left out of both.
+Five repeats each: median and min .. max.  Prints one JSON object."""
+import json
+import os
+import random
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import halo2_experiments_amd as h                                         # noqa: E402
+from halo2_experiments_amd import circuits, poseidon as ps, prover, shplonk as sh   # noqa: E402
+from halo2_experiments_amd.domain import FR_MODULUS as R, EvaluationDomain, fr_words   # noqa: E402
+from halo2_experiments_amd.kzg import ParamsKZG                            # noqa: E402
+import prover_cases as pc                                                  # noqa: E402
+
+REPEATS = 5
+
+
+def spread(ms):
+    return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3)}
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, (time.perf_counter() - t0) * 1e3
+
+
+def end_to_end(name):
+    cs, lay, advice, instance, _ = pc.build(name)
+    params = ParamsKZG.setup(lay.k, pc.SRS_S)
+    vk = h.keygen_vk(params, cs, lay)
+    pk = h.keygen_pk(params, vk, cs, lay, cosets=False)
+    inner = []
+    real = prover.create_opening
+
+    def timed(*a, **kw):
+        _, ms = wall(lambda: real(*a, **kw))
+        inner.append(ms)
+    prover.create_opening = timed
+    try:
+        h.create_proof(params, pk, advice, instance, 1)                    # warm-up: program compiles, allocator pools
+        inner.clear()
+        prove, verify = [], []
+        for rep in range(REPEATS):
+            proof, ms = wall(lambda: h.create_proof(params, pk, advice, instance, 2 + rep))
+            prove.append(ms)
+            ok, ms = wall(lambda: h.verify_proof(params, vk, instance, proof))
+            assert ok
+            verify.append(ms)
+    finally:
+        prover.create_opening = real
+        params.release()
+    return {"k": lay.k, "proof_bytes": len(proof), "create_proof": spread(prove), "of_which_shplonk": spread(inner), "verify_proof": spread(verify)}
+
+
+def k18_sets():
+    """the rotation sets of the MerkleSumTree constraint system as (points, keys), with the prover's order of queries"""
+    cs = circuits.merkle_sum_tree(ps.default_spec(5))
+    dom = EvaluationDomain(cs.degree(), 18)
+    x = 0x123456789ABCDEF % R
+    rot = lambda r: x * pow(dom.omega, r, R) % R
+    adv_q, fix_q, _ = cs.queries()
+    nsets, L, P, last = cs.permutation_sets(), len(cs.lookups), len(cs.equality), -(cs.blinding_factors + 1)
+    q = [(("advice", c), rot(r), 0) for c, r in adv_q]
+    q += [qq for i in range(nsets) for qq in ((("perm_z", i), x, 0), (("perm_z", i), rot(1), 0))]
+    q += [(("perm_z", i), rot(last), 0) for i in reversed(range(nsets - 1))]
+    for j in range(L):
+        q += [(("lookup_z", j), x, 0), (("lookup_a", j), x, 0), (("lookup_s", j), x, 0), (("lookup_a", j), rot(-1), 0), (("lookup_z", j), rot(1), 0)]
+    q += [(("fixed", c), rot(r), 0) for c, r in fix_q] + [(("sigma", j), x, 0) for j in range(P)] + [(("h",), x, 0), (("random",), x, 0)]
+    sets, super_points = sh.construct_intermediate_sets(q)
+    return [(pts, [key for key, _ in members]) for pts, members in sets], super_points
+
+
+def multiopen_k18():
+    n = 1 << 18
+    sets, super_points = k18_sets()
+    keys = [key for _, members in sets for key in members]
+    polys = {key: h.random_fr(n, 100 + i) for i, key in enumerate(keys)}
+    rng = random.Random(18)
+    y, v, u = (rng.randrange(2, R) for _ in range(3))
+    zt = sh.vanishing_eval(super_points, u)
+    z = [sh.vanishing_eval([p for p in super_points if p not in pts], u) for pts, _ in sets]
+    w = lambda values: np.stack([fr_words(c % R) for c in values])
+    zeros = lambda rows: torch.zeros((rows, 4), dtype=torch.int64, device="cuda")
+
+    def final_terms(hx):
+        cols, weights = [], []
+        for i, (pts, members) in enumerate(sets):
+            for j, key in enumerate(members):
+                cols.append(polys[key])
+                weights.append(pow(v, i, R) * z[i] % R * pow(y, j, R) % R)
+        return cols + [hx], weights + [-zt % R]
+
+    def new_route():
+        hx = None
+        for i, (pts, members) in enumerate(sets):
+            hx = sh.set_quotient([polys[k] for k in members], [pow(y, j, R) for j in range(len(members))], pts, pow(v, i, R), out=hx, accumulate=i > 0)
+        cols, weights = final_terms(hx)
+        return hx, sh.set_quotient(cols, weights, [u], pow(z[0], -1, R))
+
+    def composed_route():
+        hx = zeros(n)
+        for i, (pts, members) in enumerate(sets):
+            t = len(pts)
+            num = h.linear_combination([polys[k] for k in members], w([pow(y, j, R) for j in range(len(members))]))
+            evals = ps.words_to_ints(h.eval_polynomial(num.reshape(1, n, 4), w(pts), poly_index=np.zeros(t, dtype=np.uint32)))
+            r = zeros(n)
+            r[:t] = torch.from_numpy(ps.ints_to_words(sh.lagrange_interpolate_ints(pts, evals)).view(np.int64)).cuda()
+            qx = h.linear_combination([num, r], w([1, R - 1]))
+            for p in pts:
+                qx = h.kate_division(qx, fr_words(p))
+            h.linear_combination([hx, torch.cat([qx, zeros(t)])], w([1, pow(v, i, R)]), out=hx)
+        cols, weights = final_terms(hx)
+        lx = h.linear_combination(cols, w(weights))
+        fin = h.linear_combination([h.kate_division(lx, fr_words(u))], w([pow(z[0], -1, R)]))
+        return hx, torch.cat([fin, zeros(1)])
+
+    a, b = new_route(), composed_route()
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), "the two routes differ"
+    new, old = [], []
+    for _ in range(REPEATS):
+        new.append(wall(new_route)[1])
+        old.append(wall(composed_route)[1])
+    return {"n": n, "sets": [{"points": len(pts), "polynomials": len(members)} for pts, members in sets],
+            "set_quotient_entry": spread(new), "composed_from_existing_kernels": spread(old)}
+
+
+if __name__ == "__main__":
+    torch.cuda.init()
+    out = {"merkle_sum_d5_k9": end_to_end("merkle_sum_d5_k9"), "merkle_sum_d20_k10": end_to_end("merkle_sum_d20_k10"),
+           "multiopen_k18": multiopen_k18()}
+    print(json.dumps(out))
