@@ -187,6 +187,14 @@ _SIGNATURES = {
     "hm_poseidon_witness_bn256": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_size_t, _u64p, _u64p, _u64p]),
     "hm_permutation_assemble_dev": (ctypes.c_int, [_u32p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p, _vp]),
     "hm_permutation_columns_bn256_fr_dev": (ctypes.c_int, [_u32p, ctypes.c_uint32, ctypes.c_uint32, _u64p, _u64p, _vp, _vp]),
+    "hm_mock_gates_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), _u64p, _u32p, ctypes.c_size_t, _u64p, ctypes.c_size_t,
+                                         ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp,
+                                         _u64p, _vp]),
+    "hm_mock_copies_dev": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _u64p, _u32p, ctypes.c_size_t, _u32p, ctypes.c_size_t, _vp,
+                                          ctypes.c_size_t, ctypes.c_uint32, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp, _u64p, _vp]),
+    "hm_mock_lookup_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), _u64p, _u32p, ctypes.c_size_t, _u64p, ctypes.c_size_t,
+                                          ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_uint32, _vp, _vp, ctypes.c_size_t, _vp, _vp,
+                                          _u64p, _vp]),
     "hm_extended_to_coeff_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p, _u64p, _vp]),
     "hm_eval_polynomial_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32), _u64p, ctypes.c_size_t,
                                                        _u64p, _vp]),

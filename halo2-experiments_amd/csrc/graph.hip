@@ -22,36 +22,16 @@
 #include <map>
 
 #include "g1.h"
+#include "graph_interp.h"
 #include "graph_lower.h"
 #include "hm_internal.h"
 #include "host_fr.h"
 
 namespace hm {
 
-constexpr int GE_THREADS = 256;
-
 // the instruction encoding (GraphOp, GraphSrc, GraphCalc, GF_*, GE_CAP ...), graph_validate and graph_lower_host: graph_lower.h,
-// shared with the host replay of host_check.cpp
-
-__device__ __forceinline__ Fr ge_reduce(const Fr& lazy) { return fe_reduce_small(fe_norm(lazy)); }   // any lazy sum < 2^261 -> < 3r
-
-__device__ __forceinline__ Fr ge_from_ext(const uint32_t* __restrict__ p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 lo = q[0], hi = q[1];
-  const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  return fe_mul(fe_unpack<FrParams>(w), fe_const<FrParams>(FrParams::EXT2INT));
-}
-// A column that already holds INTERNAL-form words (32 x the external value, canonical: what the coset NTT writes when
-// its fused constants are pre-multiplied by 32) needs no conversion product: a third of the MerkleSumTree program's
-// multiplications were conversions of column loads.
-__device__ __forceinline__ Fr ge_from_internal(const uint32_t* __restrict__ p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 lo = q[0], hi = q[1];
-  const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  Fr r = fe_unpack<FrParams>(w);
-  HM_DECLARE(r, GE_COLUMN_BOUND);
-  return r;
-}
+// shared with the host replay of host_check.cpp; the interpreter body (ge_fetch, ge_reduce, ge_run and the column-word loads):
+// graph_interp.h, shared with the witness checker's kernel (mock.inc)
 
 // The call's column table and per-call constants (2.6 KiB) travel through a DEVICE buffer of the stream's AuxSlot,
 // filled by a stream-ordered copy ahead of the launch.  Rounds 1-2 passed the struct by value, and a variant with a
@@ -73,41 +53,26 @@ struct GraphColumns {
   uint32_t n_static;              // constants [0, n_static) come from the program, [n_static, ..) from dyn
 };
 
+// where graph_evaluate_kernel's lane takes what the program names (graph_interp.h: Source)
 template <bool INTERNAL>
-__device__ __forceinline__ Fr ge_fetch(uint32_t src, const GraphColumns* __restrict__ columns, const uint32_t* __restrict__ consts,
-                                       const int32_t* __restrict__ rotations, const uint32_t* __restrict__ scratch, uint32_t T,
-                                       uint32_t lane_slot, uint64_t idx, uint64_t mask, const uint32_t* __restrict__ prev) {
-  const uint32_t kind = gsrc_kind(src), index = gsrc_index(src);
-  Fr r;
-  if (kind == GSRC_INTER) {
-    const uint32_t* p = scratch + (size_t)index * 9 * T + lane_slot;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) r.l[i] = p[(size_t)i * T];
-    HM_DECLARE(r, GE_CAP);
-  } else if (kind == GSRC_CONST) {
-    if (index >= columns->n_static) {
-      const uint32_t d = (index - columns->n_static) * 9;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) r.l[i] = columns->dyn[d + i];
-    } else {
-      const uint32_t* p = consts + (size_t)index * 9;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) r.l[i] = p[i];
-    }
-    HM_DECLARE(r, 1.0);
-  } else if (kind == GSRC_COLUMN) {
+struct EvalSource {
+  const GraphColumns* __restrict__ columns;
+  const int32_t* __restrict__ rotations;
+  uint64_t idx, mask;
+  const uint32_t* __restrict__ prev;
+  __device__ __forceinline__ uint32_t n_static() const { return columns->n_static; }
+  __device__ __forceinline__ uint32_t dyn(uint32_t word) const { return columns->dyn[word]; }
+  __device__ __forceinline__ Fr column(uint32_t src) const {
     // two's complement: a negative rotation wraps -- inside the row's SEGMENT (mask = segment length - 1; one segment = the
     // whole domain in the ordinary call, one coset of the extended domain in hm_graph_evaluate_segments_dev)
     uint64_t row = (idx & ~mask) | ((idx + (uint64_t)(int64_t)rotations[gsrc_rot(src)]) & mask);
     const uint32_t lr = gsrc_log_rows(src);          // a short column (the vanishing polynomial's inverse pattern) is periodic
     if (lr != 0) row &= (1ull << lr) - 1ull;
     const uint32_t* cell = columns->p[gsrc_column(src)] + row * 8;
-    r = INTERNAL ? ge_from_internal(cell) : ge_from_ext(cell);
-  } else {
-    r = ge_from_ext(prev);
+    return INTERNAL ? ge_from_internal(cell) : ge_from_ext(cell);
   }
-  return r;
-}
+  __device__ __forceinline__ Fr previous() const { return ge_from_ext(prev); }
+};
 
 template <bool INTERNAL>
 __global__ __launch_bounds__(GE_THREADS) void graph_evaluate_kernel(const GraphColumns* __restrict__ columns,
@@ -121,65 +86,8 @@ __global__ __launch_bounds__(GE_THREADS) void graph_evaluate_kernel(const GraphC
   const uint64_t mask = (1ull << log_segment) - 1;
   for (uint64_t idx = lane_slot; idx < size; idx += T) {
     uint32_t* vrow = values + idx * 8;
-    Fr prev = fe_zero<FrParams>();                         // the previous calculation's result, in registers
-    HM_DECLARE(prev, 3.0);
-    for (uint32_t k = 0; k < n_calc; ++k) {
-      const GraphCalc cc = calcs[k];                       // the same words for every lane: scalar loads
-      const uint32_t op = cc.op & 0xffu;
-      auto src = [&](uint32_t word, uint32_t flag) -> Fr {
-        if (cc.op & flag) return prev;                     // wave-uniform branch
-        return ge_fetch<INTERNAL>(word, columns, consts, rotations, scratch, T, lane_slot, idx, mask, vrow);
-      };
-      const Fr a = src(cc.a, GF_A_PREV);
-      Fr out;
-      const bool lazy = (cc.op & GF_NO_REDUCE) != 0, wide = (cc.op & GF_SUB_WIDE) != 0;      // wave-uniform
-      auto settle = [&](const Fr& t) -> Fr { return lazy ? fe_norm(t) : ge_reduce(t); };
-      // hc_graph_replay (host_check.cpp) restates this switch for the HM_BOUNDS build; tests/test_graph_programs_gpu.py holds
-      // the two to the same words
-      switch (op) {
-        case GOP_ADD:
-          out = settle(fe_add(a, src(cc.b, GF_B_PREV)));
-          break;
-        case GOP_SUB: {
-          const Fr b = src(cc.b, GF_B_PREV);
-          out = wide ? ge_reduce(fe_sub<20, 29>(a, b)) : settle(fe_sub<4, 29>(a, b));
-          break;
-        }
-        case GOP_MUL:
-          out = fe_mul(a, src(cc.b, GF_B_PREV));
-          break;
-        case GOP_SQUARE:
-          out = fe_sqr(a);
-          break;
-        case GOP_DOUBLE:
-          out = settle(fe_dbl(a));
-          break;
-        case GOP_NEGATE:
-          out = wide ? ge_reduce(fe_sub<20, 29>(fe_zero<FrParams>(), a)) : settle(fe_sub<4, 29>(fe_zero<FrParams>(), a));
-          break;
-        case GOP_MULADD: {   // a * b + c (one Horner step)
-          const Fr b = src(cc.b, GF_B_PREV);
-          const Fr c = src(cc.c, GF_C_PREV);
-          out = settle(fe_add(fe_mul(a, b), c));
-          break;
-        }
-        default:             // GOP_STORE
-          out = a;
-          break;
-      }
-      if (!(cc.op & GF_NO_STORE)) {
-        uint32_t* p = scratch + (size_t)cc.target * 9 * T + lane_slot;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) p[(size_t)i * T] = out.l[i];
-      }
-      prev = out;
-    }
-    // the graph's value: its last calculation (upstream GraphEvaluator::evaluate), or the given source
-    Fr res = fe_zero<FrParams>();
-    if (result_prev)
-      res = prev;
-    else if (n_calc != 0 || gsrc_kind(result_src) != GSRC_INTER)
-      res = ge_fetch<INTERNAL>(result_src, columns, consts, rotations, scratch, T, lane_slot, idx, mask, vrow);
+    const EvalSource<INTERNAL> from{columns, rotations, idx, mask, vrow};
+    const Fr res = ge_run(from, consts, calcs, n_calc, result_src, result_prev, scratch, T, lane_slot);
     uint32_t w[8];
     fe_to_ext(w, ge_reduce(res));
     uint4* dst = reinterpret_cast<uint4*>(vrow);

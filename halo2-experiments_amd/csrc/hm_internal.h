@@ -463,6 +463,27 @@ int perm_columns_run(const uint32_t* d_sigma_cells, uint32_t columns, uint32_t k
 int lookup_permute_run(DeviceCtx& ctx, const void* const* d_inputs, const void* const* d_tables, size_t pairs, uint64_t rows,
                        void* const* d_out_inputs, void* const* d_out_tables, int* missing, hipStream_t stream);
 
+// the sorted canonical keys of the first `live` (>= 1) elements of d_values, for a binary search (mock.inc): d_ws, of
+// lookup_sorted_keys_bytes(live) bytes and 256-byte aligned, starts with the keys -- the next power of two of them, all-ones behind
+// the live ones.  Asynchronous on `stream`.
+size_t lookup_sorted_keys_bytes(uint64_t live);
+int lookup_sorted_keys_run(DeviceCtx& ctx, const uint32_t* d_values, uint64_t live, uint8_t* d_ws, hipStream_t stream);
+
+// mock.inc: the batched witness checker.  MockTable: per column of the program's table its base, the words from one user's column
+// to the next user's (0: shared) and the rows present (cells above read as zero) -- HOST arrays.  MockSink: where failures go, all
+// DEVICE memory of the caller's: `cap` records, one counter that keeps counting past cap, one byte per user.
+struct MockTable { const void* const* bases; const uint64_t* strides; const uint32_t* rows; size_t n; };
+struct MockSink { uint64_t* d_records; uint64_t cap; uint64_t* d_counter; uint8_t* d_user_flags; };
+// program `g` on the (user, row < usable) lanes of m users, or on the n_list lanes of d_list (records of an earlier pass); a lane
+// fails when its value is != 0, or, with d_table_values (2^k elements of which the first `usable` are the table), when its value
+// is not in the table.  The arguments were checked by the caller (capi_mock.hip).
+int mock_program_run(DeviceCtx& ctx, GraphProgram& g, const MockTable& t, const uint64_t* dyn_ext, size_t n_dyn, uint32_t k,
+                     uint32_t usable, size_t m, uint32_t user_base, const uint64_t* d_list, size_t n_list, const uint32_t* d_table_values,
+                     const MockSink& out, hipStream_t stream);
+// d_pairs: n_copies pairs of cell ids (permutation column j * 2^k + row); perm[j]: the table entry that column is
+int mock_copies_run(DeviceCtx& ctx, const MockTable& t, const uint32_t* perm, size_t n_perm, const uint32_t* d_pairs, size_t n_copies,
+                    uint32_t k, size_t m, const MockSink& out, hipStream_t stream);
+
 // msm.hip
 int msm_convert_bases(const uint32_t* d_bases_ext, uint32_t* d_xy, uint8_t* d_inf, size_t n, hipStream_t stream);
 // out_windows: host buffer of W x 12 u64 external Jacobian + flags

@@ -15,6 +15,7 @@
 #include "g1.h"
 #include "graph_lower.h"
 #include "host_fr.h"
+#include "mock_check.h"   // the witness checker's key search, value key and record packing (its kernels are HIP-only)
 
 namespace hm {
 #include "g1_codec.inc"   // the per-point SRS codec formulas (its kernels are HIP-only)
@@ -681,6 +682,31 @@ int hc_permutation_assemble(const uint32_t* copies, size_t m, uint32_t columns, 
     if (perm_link(keys[p], p + 1 < keys.size() ? keys[p + 1] : PERM_PAD, cell, target)) sigma_cells[cell] = target;
   }
   return 0;
+}
+
+// The witness checker's rules (mock_check.h): found[i] / at[i] = whether and where (lower bound) keys[i] lies in `sorted` (n ascending
+// 256-bit keys); the canonical key of Montgomery words as graph_check_kernel makes it of a lane's value (conversion, reduction, one
+// product); a record packed and taken apart again.
+int hc_mock_key_search(const uint32_t* sorted, uint64_t n, const uint32_t* keys, size_t count, uint8_t* found, uint64_t* at) {
+  for (size_t i = 0; i < count; ++i) {
+    found[i] = mock_key_found(sorted, n, keys + 8 * i) ? 1 : 0;
+    at[i] = mock_key_lower_bound(sorted, n, keys + 8 * i);
+  }
+  return 0;
+}
+int hc_mock_value_key(const uint32_t* ext, uint32_t* key) {
+  uint32_t w[8], out[8];
+  std::memcpy(w, ext, sizeof w);
+  const Fr x = fe_from_ext<FrParams>(w);
+  mock_value_key(out, fe_reduce_small(fe_norm(x)));
+  std::memcpy(key, out, sizeof out);
+  return 0;
+}
+uint64_t hc_mock_record(uint32_t user, uint32_t index, uint32_t* user_back, uint32_t* index_back) {
+  const uint64_t rec = mock_record(user, index);
+  *user_back = mock_record_user(rec);
+  *index_back = mock_record_index(rec);
+  return rec;
 }
 
 }  // extern "C"

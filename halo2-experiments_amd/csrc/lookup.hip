@@ -17,13 +17,17 @@
 //   5  fill      S'[row] = A'[row] at first occurrences, else the (m - 1 - rank)-th leftover value; back to Montgomery
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "g1.h"
+#include "graph_interp.h"
+#include "graph_lower.h"
 #include "hm_internal.h"
 #include "host_fr.h"
+#include "mock_check.h"
 
 namespace hm {
 
@@ -446,6 +450,36 @@ static int lk_compact(const uint32_t* d_flags, uint64_t n, uint64_t stride, uint
   return HM_OK;
 }
 
+// the keys of ONE column, converted and sorted with the kernels above, for the witness checker's binary search (mock.hip)
+size_t lookup_sorted_keys_bytes(uint64_t live) {
+  uint64_t n2 = 1;
+  while (n2 < live) n2 <<= 1;
+  return (((size_t)n2 * 32 + 255) & ~(size_t)255) + LK_KB_WORDS * 4;
+}
+int lookup_sorted_keys_run(DeviceCtx& ctx, const uint32_t* d_values, uint64_t live, uint8_t* d_ws, hipStream_t stream) {
+  if (live == 0 || live >= ((uint64_t)1 << 31)) return hm_fail(HM_ERR_BAD_ARG, "lookup keys: need 1 <= rows < 2^31");
+  uint64_t n2 = 1;
+  while (n2 < live) n2 <<= 1;
+  if (!ctx.lookup_attr_set) {
+    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(lk_sort_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)(8 * LK_TILE * 4)));
+    ctx.lookup_attr_set = true;
+  }
+  uint32_t* keys = (uint32_t*)d_ws;
+  uint32_t* kbits = (uint32_t*)(d_ws + (((size_t)n2 * 32 + 255) & ~(size_t)255));      // written by the conversion, not read here
+  LkFr to_canon;
+  const host::Fr4 one_int = {{1, 0, 0, 0}};                         // as lookup_permute_run: the integer 1 read as Montgomery words = 2^-256
+  host::fr_to_internal9(one_int, to_canon.l);
+  LkPtrs ptr;
+  std::memset(&ptr, 0, sizeof ptr);
+  ptr.in[0] = d_values;
+  HM_HIP_CHECK(hipMemsetAsync(kbits, 0, LK_KB_WORDS * 4, stream));
+  hipLaunchKernelGGL(lk_convert_kernel, dim3((uint32_t)((n2 + LK_THREADS - 1) / LK_THREADS), 1), dim3(LK_THREADS), 0, stream, ptr, keys, n2 * 8,
+                     live, n2, to_canon, kbits);
+  HM_HIP_CHECK(hipGetLastError());
+  return lk_sort(keys, n2, 1, n2 * 8, stream);
+}
+
 // `pairs` lookups of the same length through one launch chain.  d_inputs[p], d_tables[p]: columns of which the first
 // `rows` entries are read; d_out_inputs[p], d_out_tables[p]: rows [0, rows) written.  missing[p] (optional) tells which
 // lookup failed.  Returns HM_ERR_NOT_FOUND when an input value is missing from its table (upstream:
@@ -553,5 +587,7 @@ int lookup_permute_run(DeviceCtx& ctx, const void* const* d_inputs, const void* 
   if (result == HM_ERR_INTERNAL) return hm_fail(HM_ERR_INTERNAL, "lookup permute: leftover / repeated counts differ");
   return rrc;
 }
+
+#include "mock.inc"       // the batched witness checker: its lookup pass searches keys sorted by the code above
 
 }  // namespace hm

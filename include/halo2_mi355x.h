@@ -636,6 +636,43 @@ int hm_permutation_assemble_dev(const uint32_t* d_copies, size_t m, uint32_t col
 int hm_permutation_columns_bn256_fr_dev(const uint32_t* d_sigma_cells, uint32_t columns, uint32_t k, const uint64_t omega[4],
                                         const uint64_t delta[4], void* d_out, void* stream);
 
+/* MockProver::verify for a BATCH of witnesses on the device: does every user's witness satisfy the constraint system?  Three passes
+ * over one batched column table, the program's table (fixed, then advice, then instance) with m users behind every entry: column i
+ * starts at column_bases[i] (DEVICE memory, 16-byte aligned), user u's copy lies column_strides[i] u32 words further per user (a
+ * multiple of 4; 0: one column shared by all users, i.e. a fixed column), and holds column_rows[i] <= 2^k elements of 4 Montgomery
+ * words -- a cell above them reads as zero, so an instance column is given as it is, never padded.  The three arrays are HOST memory.
+ * gates: the hm_graph_create program `graph` runs on one lane per (user, row < usable_rows); a rotation wraps modulo 2^k inside the
+ *   user's own columns; PreviousValue is zero; a lane whose value is not zero is a failure.  With d_lanes_or_null (DEVICE memory,
+ *   n_lanes records of an earlier call) only those lanes run; a record naming a user or row outside the batch is skipped.
+ * copies: d_copies (DEVICE memory, 8-byte aligned) holds n_copies pairs of cell ids as hm_permutation_assemble_dev takes them,
+ *   permutation column j being entry permutation_columns[j] (HOST memory) of the table; one lane per (user, copy) compares the two
+ *   cells' words.  A copy between two shared columns is checked for user 0 only; a pair naming a column >= n_permutation is skipped.
+ * lookup: `graph` is the input expression of one lookup; d_table_values holds 2^k elements (DEVICE memory, 16-byte aligned) whose
+ *   first usable_rows are the table.  They are brought to canonical integers and sorted once per call; a lane fails when its
+ *   value's canonical integer is not among them.  user_base is added to the user index of every record and flag of the call.
+ * Failures: a record is user << 32 | row (gates, lookup) or user << 32 | copy index.  Every wave adds its failures to *d_counter (one
+ * u64, DEVICE memory) with one atomic and writes the records whose slot is below cap into d_records (cap u64, DEVICE memory); the
+ * counter keeps counting past cap, so it is exact.  The counter is the caller's: zero it before the first call; calls add to it and
+ * append behind the records already there.  d_user_flags[user] (DEVICE bytes, one per user) is set to 1 for a user with a failure and
+ * otherwise left alone.  No other device memory of the caller's is written.  The launches are asynchronous on `stream`; the call then
+ * waits for the stream to read the counter back into *out_total.
+ * HM_ERR_BAD_ARG, with nothing written or launched: NULL arguments, no or more than 256 columns, k > 30, m == 0, cap == 0, a column
+ * with more than 2^k rows, a pointer or stride that is not aligned, usable_rows 0 or above 2^k, m * usable_rows > 2^32, a lane list that
+ * is empty or not 8-byte aligned, a permutation column outside the table, n_copies == 0, a program built for another number of columns
+ * or per-call constants.  HM_ERR_NOT_FOUND: an unknown program handle. */
+int hm_mock_gates_dev(uint64_t graph, const void* const* column_bases, const uint64_t* column_strides, const uint32_t* column_rows,
+                      size_t n_columns, const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t k, uint32_t usable_rows, size_t m,
+                      const uint64_t* d_lanes_or_null, size_t n_lanes, uint64_t* d_records, size_t cap, uint64_t* d_counter,
+                      uint8_t* d_user_flags, uint64_t* out_total, void* stream);
+int hm_mock_copies_dev(const void* const* column_bases, const uint64_t* column_strides, const uint32_t* column_rows, size_t n_columns,
+                       const uint32_t* permutation_columns, size_t n_permutation, const uint32_t* d_copies, size_t n_copies, uint32_t k,
+                       size_t m, uint64_t* d_records, size_t cap, uint64_t* d_counter, uint8_t* d_user_flags, uint64_t* out_total,
+                       void* stream);
+int hm_mock_lookup_dev(uint64_t graph, const void* const* column_bases, const uint64_t* column_strides, const uint32_t* column_rows,
+                       size_t n_columns, const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t k, uint32_t usable_rows, size_t m,
+                       uint32_t user_base, const void* d_table_values, uint64_t* d_records, size_t cap, uint64_t* d_counter,
+                       uint8_t* d_user_flags, uint64_t* out_total, void* stream);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 
 typedef struct hm_msm_stats {
