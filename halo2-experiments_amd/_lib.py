@@ -5,6 +5,8 @@ import ctypes
 import os
 import subprocess
 
+from . import _header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # eight commitments in flight need more than the HIP runtime's default of 4 hardware queues (capi.hip sets the same
@@ -14,11 +16,6 @@ LIB_PATH = os.environ.get("HALO2_MI355X_LIB") or os.path.join(CSRC, "libhalo2_mi
 HOSTCHECK_PATH = os.path.join(CSRC, "libhm_hostcheck.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "halo2_mi355x.h")
 
-_u64p = ctypes.POINTER(ctypes.c_uint64)
-_u32p = ctypes.POINTER(ctypes.c_uint32)
-_vp = ctypes.c_void_p
-NO_CHAIN = ctypes.c_size_t(-1).value      # HM_NO_CHAIN of the header
-
 
 class Halo2Mi355xError(RuntimeError):
     def __init__(self, code: int, message: str):
@@ -26,32 +23,59 @@ class Halo2Mi355xError(RuntimeError):
         self.code = code
 
 
-class MsmStats(ctypes.Structure):
-    _fields_ = [("digits_ms", ctypes.c_double), ("sort_ms", ctypes.c_double), ("accumulate_ms", ctypes.c_double),
-                ("reduce_ms", ctypes.c_double), ("total_ms", ctypes.c_double), ("accumulate_kernel_ms", ctypes.c_double),
-                ("pairs", ctypes.c_uint64),
-                ("tasks", ctypes.c_uint64), ("window_bits", ctypes.c_uint32), ("windows", ctypes.c_uint32)]
+# ---- everything the header states, derived from it at import (no library load, no GPU) ----------------------------------------
+with open(HEADER_PATH) as _f:
+    _FUNCTIONS, _STRUCT_FIELDS, _DEFINES = _header.parse_header(_f.read())
+
+_SCALARS = {"c_int": ctypes.c_int, "c_long": ctypes.c_long, "usize": ctypes.c_size_t, "u64": ctypes.c_uint64, "u32": ctypes.c_uint32,
+            "i32": ctypes.c_int32, "u8": ctypes.c_uint8, "f64": ctypes.c_double, "c_char": ctypes.c_char}
 
 
-class Stats(ctypes.Structure):
-    """hm_stats: per-call counters since start / hm_reset_stats (include/halo2_mi355x.h)."""
-    _fields_ = [("msm_calls", ctypes.c_uint64), ("msm_points", ctypes.c_uint64), ("ntt_calls", ctypes.c_uint64),
-                ("ntt_elements", ctypes.c_uint64), ("msm_calls_by_log2", ctypes.c_uint64 * 32),
-                ("ntt_calls_by_log2", ctypes.c_uint64 * 32), ("msm_h2d_us", ctypes.c_double), ("msm_device_us", ctypes.c_double),
-                ("msm_host_us", ctypes.c_double), ("ntt_h2d_us", ctypes.c_double), ("ntt_device_us", ctypes.c_double),
-                ("ntt_d2h_us", ctypes.c_double), ("h2d_bytes", ctypes.c_uint64), ("d2h_bytes", ctypes.c_uint64),
-                ("vector_calls", ctypes.c_uint64 * 8), ("vector_elements", ctypes.c_uint64 * 8),
-                ("coset_table_bytes", ctypes.c_uint64), ("coset_tables", ctypes.c_uint64),
-                ("ntt_table_bytes", ctypes.c_uint64), ("ntt_tables", ctypes.c_uint64),
-                ("host_copies_direct", ctypes.c_uint64), ("host_copies_staged", ctypes.c_uint64), ("host_ranges_registered", ctypes.c_uint64)]
-    KINDS = ("eval_polynomial", "graph_evaluate", "kate_division", "grand_product", "batch_invert", "linear_combination", "lookup_permute")
+_STRUCTS = {}           # canonical base type ('HmStats') -> the ctypes twin of that struct
 
 
-class BasesInfo(ctypes.Structure):
-    """hm_bases_info (include/halo2_mi355x.h)."""
-    _fields_ = [("n", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("parked_bytes", ctypes.c_uint64),
-                ("default_tables_dropped", ctypes.c_uint64), ("table_windows", ctypes.c_uint32), ("table_window_bits", ctypes.c_uint32),
-                ("devices", ctypes.c_uint32), ("sliced", ctypes.c_uint32)]
+def _struct(name: str, cname: str, **extra):
+    """The ctypes twin of one of the header's structs: field names, order, types and array lengths as declared there."""
+    fields = [(f, _SCALARS[base] * count if count else _SCALARS[base]) for f, base, count in _STRUCT_FIELDS[cname]]
+    cls = type(name, (ctypes.Structure,), dict(extra, _fields_=fields, __doc__=f"{cname} (include/halo2_mi355x.h)"))
+    _STRUCTS[_header.STRUCTS[cname]] = cls
+    return cls
+
+
+def _define(text: str) -> int:
+    """'-4' -> -4; '(size_t)-1' -> the value as that type holds it"""
+    cast, _, digits = text.rpartition(")")
+    return _SCALARS[_header.C_SCALARS[cast[1:]]](int(digits)).value if cast else int(digits)
+
+
+# every HM_* define is a module constant: HM_OK, HM_ERR_NOT_FOUND, HM_SHPLONK_MAX_POINTS, HM_GRAPH_COLUMNS_INTERNAL, HM_NO_CHAIN ...
+globals().update({name: _define(text) for name, text in _DEFINES})
+NO_CHAIN = HM_NO_CHAIN      # noqa: F821
+
+MsmStats = _struct("MsmStats", "hm_msm_stats")
+BasesInfo = _struct("BasesInfo", "hm_bases_info")
+# hm_stats: per-call counters since start / hm_reset_stats; vector_calls[HM_STAT_x] and vector_elements[HM_STAT_x] belong to KINDS[x]
+Stats = _struct("Stats", "hm_stats", KINDS=tuple(name[len("HM_STAT_"):].lower() for _, name in sorted(
+    (_define(text), name) for name, text in _DEFINES if name.startswith("HM_STAT_"))))
+
+
+def _ctype(canon: str):
+    """The ctypes type of a canonical C type ('u64 c' = const uint64_t*, see _header.py) -- the one statement of the mapping:
+    a scalar is its ctypes scalar; void* and uint8_t* (byte buffers have no word type) are c_void_p; char* is c_char_p; T* of a
+    scalar or struct T is POINTER(T); any pointer to pointer (a table of addresses) is POINTER(c_void_p)."""
+    base, *ptrs = canon.split()
+    if not ptrs:
+        return _SCALARS[base]
+    if len(ptrs) > 1:
+        return ctypes.POINTER(ctypes.c_void_p)
+    if base in ("c_void", "u8"):
+        return ctypes.c_void_p
+    if base == "c_char":
+        return ctypes.c_char_p
+    return ctypes.POINTER(_SCALARS.get(base) or _STRUCTS[base])
+
+
+_SIGNATURES = {name: (_ctype(ret), [_ctype(t) for t, _ in params]) for name, ret, params in _FUNCTIONS}
 
 
 def build(force: bool = False) -> str:
@@ -63,147 +87,16 @@ def build(force: bool = False) -> str:
     return LIB_PATH
 
 
-_SIGNATURES = {
-    "hm_device_count": (ctypes.c_int, []),
-    "hm_set_device": (ctypes.c_int, [ctypes.c_int]),
-    "hm_shutdown": (ctypes.c_int, []),
-    "hm_last_error": (ctypes.c_char_p, []),
-    "hm_version": (ctypes.c_char_p, []),
-    "hm_msm_bn256_g1": (ctypes.c_int, [_u64p, _u64p, ctypes.c_size_t, _u64p, ctypes.POINTER(ctypes.c_int)]),
-    "hm_msm_bn256_g1_jacobian": (ctypes.c_int, [_u64p, _u64p, ctypes.c_size_t, _u64p]),
-    "hm_register_bases": (ctypes.c_int, [_u64p, ctypes.c_size_t, _u64p]),
-    "hm_release_bases": (ctypes.c_int, [ctypes.c_uint64]),
-    "hm_msm_bn256_g1_h": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_size_t, _u64p, ctypes.c_size_t, _u64p,
-                                          ctypes.POINTER(ctypes.c_int)]),
-    "hm_register_bases_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _u64p]),
-    "hm_register_bases_precomp": (ctypes.c_int, [_u64p, ctypes.c_size_t, _u64p]),
-    "hm_register_bases_precomp_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _u64p]),
-    "hm_register_bases_plain": (ctypes.c_int, [_u64p, ctypes.c_size_t, _u64p]),
-    "hm_register_bases_plain_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _u64p]),
-    "hm_get_bases_info": (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(BasesInfo)]),
-    "hm_msm_bn256_g1_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _u64p]),
-    "hm_msm_submit_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _u64p]),
-    "hm_msm_wait": (ctypes.c_int, [ctypes.c_uint64, _u64p]),
-    "hm_msm_batch_bn256_g1_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t,
-                                                 ctypes.c_size_t, _vp, _u64p]),
-    "hm_msm_batch_bn256_g1_h": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t,
-                                              ctypes.c_size_t, _u64p]),
-    "hm_g1_sum": (ctypes.c_int, [_u64p, ctypes.c_size_t, _u64p]),
-    "hm_coeff_to_extended_bn256_fr_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, _u64p, ctypes.c_uint32,
-                                                         ctypes.c_uint32, _u64p, ctypes.c_void_p]),
-    "hm_coeff_to_coset_bn256_fr_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p, ctypes.c_int, _vp]),
-    "hm_coset_to_coeff_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p, _u64p, _vp]),
-    "hm_coeff_to_cosets_bn256_fr_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p, ctypes.c_size_t, ctypes.c_int, _vp]),
-    "hm_cosets_to_coeff_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p, _u64p, _vp]),
-    "hm_msm_set_window": (ctypes.c_int, [ctypes.c_int]),
-    "hm_msm_set_phase_timing": (ctypes.c_int, [ctypes.c_int]),
-    "hm_set_host_base_cache": (ctypes.c_int, [ctypes.c_int]),
-    "hm_set_fixed_base_threshold": (ctypes.c_int, [ctypes.c_uint32]),
-    "hm_set_msm_devices": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
-    "hm_ntt_bn256_fr": (ctypes.c_int, [_u64p, _u64p, ctypes.c_uint32]),
-    "hm_set_host_copies": (ctypes.c_int, [ctypes.c_int]),
-    "hm_host_register": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
-    "hm_host_unregister": (ctypes.c_int, [ctypes.c_void_p]),
-    "hm_device_malloc": (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
-    "hm_device_free": (ctypes.c_int, [ctypes.c_void_p]),
-    "hm_copy_to_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
-    "hm_copy_to_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
-    "hm_copy_many_to_device": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t]),
-    "hm_copy_many_to_host": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t]),
-    "hm_device_synchronize": (ctypes.c_int, []),
-    "hm_coeff_to_extended_bn256_fr": (ctypes.c_int, [_u64p, _u64p, _u64p, ctypes.c_uint32, ctypes.c_uint32, _u64p]),
-    "hm_extended_to_coeff_bn256_fr": (ctypes.c_int, [_u64p, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p, _u64p]),
-    "hm_ntt_bn256_fr_dev": (ctypes.c_int, [_vp, _u64p, ctypes.c_uint32, _vp]),
-    "hm_ntt_batch_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p, _u64p, _vp]),
-    "hm_ifft_bn256_fr_dev": (ctypes.c_int, [_vp, _u64p, ctypes.c_uint32, _u64p, _vp]),
-    "hm_coset_ntt_bn256_fr_dev": (ctypes.c_int, [_vp, _u64p, ctypes.c_uint32, _u64p, _vp]),
-    "hm_graph_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, _u64p, ctypes.c_size_t, ctypes.c_size_t,
-                                       ctypes.POINTER(ctypes.c_int32), ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, _u64p]),
-    "hm_graph_evaluate_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, _u64p, ctypes.c_size_t,
-                                             ctypes.c_uint32, _vp, _vp]),
-    "hm_graph_evaluate_flags_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, _u64p, ctypes.c_size_t,
-                                                   ctypes.c_uint32, _vp, ctypes.c_uint32, _vp]),
-    "hm_graph_evaluate_segments_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, _u64p, ctypes.c_size_t,
-                                                      ctypes.c_uint32, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp]),
-    "hm_quotient_by_cosets_bn256_fr_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, _u64p, ctypes.c_size_t,
-                                                          ctypes.c_uint32, _u64p, _u64p, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
-    "hm_quotient_partials_bn256_fr_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, _u64p,
-                                                         ctypes.c_size_t, ctypes.c_uint32, _u64p, _u64p, ctypes.c_size_t, _vp, _vp]),
-    "hm_quotient_combine_bn256_fr_dev": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _u64p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_size_t, _vp, _vp]),
-    "hm_graph_destroy": (ctypes.c_int, [ctypes.c_uint64]),
-    "hm_fr_powers_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, _vp]),
-    "hm_fr_mul_periodic_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, ctypes.c_uint32, _vp]),
-    "hm_lookup_permute_bn256_fr_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
-    "hm_lookup_permute_batch_bn256_fr_dev": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t,
-                                                          ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
-                                                          ctypes.POINTER(ctypes.c_int), _vp]),
-    "hm_kate_division_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, _vp, _vp]),
-    "hm_fr_grand_product_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, _vp, _vp]),
-    "hm_kate_division_batch_bn256_fr_dev": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_size_t, _u64p, ctypes.POINTER(_vp), ctypes.c_size_t, _vp]),
-    "hm_fr_grand_product_batch_dev": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_size_t, _u64p, ctypes.c_size_t, ctypes.POINTER(_vp),
-                                                     ctypes.c_size_t, _vp]),
-    "hm_fr_batch_invert_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp]),
-    "hm_fr_linear_combination_dev": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _u64p, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
-    "hm_shplonk_set_quotient_bn256_fr_dev": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _u64p, ctypes.c_size_t, ctypes.c_size_t, _u64p,
-                                                            ctypes.c_size_t, _u64p, _vp, ctypes.c_int, _vp]),
-    "hm_fr_random_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_uint64, _vp]),
-    "hm_fr_affine_sequence_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, _u64p, _vp]),
-    "hm_fr_dot_bn256_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _u64p, _vp]),
-    "hm_fr_scale_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, _vp]),
-    "hm_fr_distribute_powers_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, _vp]),
-    "hm_g1_fixed_base_mul_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, _vp, _vp]),
-    "hm_g1_fft_bn256_dev": (ctypes.c_int, [_vp, _u64p, ctypes.c_uint32, _u64p, _vp]),
-    "hm_g1_fft_bn256": (ctypes.c_int, [_u64p, _u64p, ctypes.c_uint32, _u64p]),
-    "hm_g1_compress_bn256_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp]),
-    "hm_g1_decompress_bn256_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _u64p, _vp]),
-    "hm_g1_check_bn256_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, _vp]),
-    "hm_g1_compress_bn256": (ctypes.c_int, [_u64p, ctypes.c_size_t, _vp]),
-    "hm_g1_decompress_bn256": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, _u64p]),
-    "hm_g1_check_bn256": (ctypes.c_int, [_u64p, ctypes.c_size_t, _u64p]),
-    "hm_poseidon_create": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u64p, _u64p, _u64p]),
-    "hm_poseidon_destroy": (ctypes.c_int, [ctypes.c_uint64]),
-    "hm_poseidon_hash_bn256_fr_dev": (ctypes.c_int, [ctypes.c_uint64, _vp, ctypes.c_size_t, _vp, _vp]),
-    "hm_poseidon_hash_bn256_fr": (ctypes.c_int, [ctypes.c_uint64, _u64p, ctypes.c_size_t, _u64p]),
-    "hm_merkle_sum_tree_build_dev": (ctypes.c_int, [ctypes.c_uint64, _vp, ctypes.c_uint32, _vp, _vp]),
-    "hm_merkle_sum_tree_build": (ctypes.c_int, [ctypes.c_uint64, _u64p, ctypes.c_uint32, _u64p, _u64p]),
-    "hm_merkle_tree_build_dev": (ctypes.c_int, [ctypes.c_uint64, _vp, ctypes.c_uint32, _vp, _vp]),
-    "hm_merkle_paths_dev": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64p, ctypes.c_size_t, _vp, _vp]),
-    "hm_merkle_sum_tree_update_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, _vp, _u64p, _vp, ctypes.c_size_t, _u32p, _vp]),
-    "hm_merkle_tree_update_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, _vp, _u64p, _vp, ctypes.c_size_t, _u32p, _vp]),
-    "hm_merkle_roots_bn256_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_size_t, _vp, _vp, _u64p, _vp, _vp]),
-    "hm_merkle_roots_bn256": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_size_t, _u64p, _u64p, _u64p, _u64p]),
-    "hm_merkle_sum_witness_layout": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p, _u32p]),
-    "hm_merkle_sum_witness_bn256_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, _vp, _vp, _u64p,
-                                                      _u64p, _vp, _vp, _vp, _vp]),
-    "hm_merkle_sum_witness_bn256": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, _u64p, _u64p, _u64p,
-                                                  _u64p, _u64p, _u64p]),
-    "hm_merkle_witness_layout": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p, _u32p]),
-    "hm_merkle_witness_bn256_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, _vp, _vp, _u64p, _vp,
-                                                  _vp, _vp, _vp]),
-    "hm_merkle_witness_bn256": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, _u64p, _u64p, _u64p,
-                                              _u64p, _u64p]),
-    "hm_poseidon_witness_layout": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p, _u32p]),
-    "hm_poseidon_witness_bn256_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
-    "hm_poseidon_witness_bn256": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_size_t, _u64p, _u64p, _u64p]),
-    "hm_permutation_assemble_dev": (ctypes.c_int, [_u32p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p, _vp]),
-    "hm_permutation_columns_bn256_fr_dev": (ctypes.c_int, [_u32p, ctypes.c_uint32, ctypes.c_uint32, _u64p, _u64p, _vp, _vp]),
-    "hm_mock_gates_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), _u64p, _u32p, ctypes.c_size_t, _u64p, ctypes.c_size_t,
-                                         ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp,
-                                         _u64p, _vp]),
-    "hm_mock_copies_dev": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _u64p, _u32p, ctypes.c_size_t, _u32p, ctypes.c_size_t, _vp,
-                                          ctypes.c_size_t, ctypes.c_uint32, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp, _u64p, _vp]),
-    "hm_mock_lookup_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), _u64p, _u32p, ctypes.c_size_t, _u64p, ctypes.c_size_t,
-                                          ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_uint32, _vp, _vp, ctypes.c_size_t, _vp, _vp,
-                                          _u64p, _vp]),
-    "hm_extended_to_coeff_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p, _u64p, _vp]),
-    "hm_eval_polynomial_bn256_fr_dev": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32), _u64p, ctypes.c_size_t,
-                                                       _u64p, _vp]),
-    "hm_get_msm_stats": (ctypes.c_int, [ctypes.POINTER(MsmStats)]),
-    "hm_get_stats": (ctypes.c_int, [ctypes.POINTER(Stats)]),
-    "hm_reset_stats": (ctypes.c_int, []),
-}
-
 _lib = None
+
+
+def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
+    """Give every entry point of the header its restype and argtypes; a symbol the library lacks raises."""
+    for name, (res, args) in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return lib
 
 
 def load() -> ctypes.CDLL:
@@ -220,12 +113,7 @@ def load() -> ctypes.CDLL:
             import torch  # noqa: F401
         except ImportError:
             pass
-        lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = lib
+        _lib = _bind(ctypes.CDLL(LIB_PATH))
     return _lib
 
 
@@ -240,11 +128,7 @@ def load_fi() -> ctypes.CDLL:
     global _fi
     if _fi is None:
         load()                                   # torch's HIP runtime first, as for the product library
-        lib = ctypes.CDLL(FI_LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
+        lib = _bind(ctypes.CDLL(FI_LIB_PATH))
         lib.hm_test_arm_fault.restype = ctypes.c_int
         lib.hm_test_arm_fault.argtypes = [ctypes.c_char_p, ctypes.c_long]
         _fi = lib
@@ -252,5 +136,5 @@ def load_fi() -> ctypes.CDLL:
 
 
 def check(rc: int) -> None:
-    if rc != 0:
+    if rc != HM_OK:      # noqa: F821
         raise Halo2Mi355xError(rc, load().hm_last_error().decode())

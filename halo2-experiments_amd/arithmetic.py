@@ -17,45 +17,9 @@ from typing import Optional, Union
 import numpy as np
 
 from . import _lib
-
-_u64p = ctypes.POINTER(ctypes.c_uint64)
-
-
-def _is_tensor(x) -> bool:
-    return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
-
-
-def _np(a, cols: int, name: str, writable: bool = False) -> np.ndarray:
-    arr = np.asarray(a)
-    if arr.dtype != np.uint64:
-        raise TypeError(f"{name} must be uint64 limbs, got {arr.dtype}")
-    arr = arr.reshape(-1, cols)
-    if not arr.flags["C_CONTIGUOUS"]:
-        if writable:
-            raise ValueError(f"{name} must be C-contiguous to be transformed in place")
-        arr = np.ascontiguousarray(arr)
-    return arr
-
-
-def _ptr(arr: np.ndarray):
-    return arr.ctypes.data_as(_u64p)
-
-
-def _stream_ptr(t) -> int:
-    import torch
-
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _tensor_rows(t, cols: int, name: str) -> int:
-    if not t.is_cuda:
-        raise ValueError(f"{name}: torch tensors must live on the GPU (pass numpy arrays for host data)")
-    if t.element_size() != 8 or not t.is_contiguous():
-        raise ValueError(f"{name}: need a contiguous 64-bit integer tensor")
-    if t.numel() % cols:
-        raise ValueError(f"{name}: size is not a multiple of {cols} words")
-    return t.numel() // cols
-
+from ._marshal import _is_tensor, _np, _ptr, _ptr_array, _stream_ptr, _tensor_rows, _u32p
+from .bn256 import (FQ_MODULUS, FQ_ONE_MONT, FR_MODULUS, FR_ROOT_OF_UNITY, FR_S, G1_GENERATOR, fq_words,  # noqa: F401  (re-exported)
+                    fr_words)
 
 class BasesHandle:
     """A device-resident, pre-converted base set (``ParamsKZG::g`` / ``g_lagrange``)."""
@@ -187,7 +151,7 @@ def best_multiexp_batch(columns, bases: BasesHandle, offset: int = 0) -> np.ndar
     for c in cols:
         if _tensor_rows(c, 4, "columns") != n:
             raise ValueError("best_multiexp_batch: every column must have the same length")
-    ptrs = (ctypes.c_void_p * len(cols))(*[c.data_ptr() for c in cols])
+    ptrs = _ptr_array(cols)
     _lib.check(_lib.load().hm_msm_batch_bn256_g1_dev(ctypes.c_uint64(bases.handle), offset, ptrs, n, len(cols),
                                                      ctypes.c_void_p(_stream_ptr(cols[0])), _ptr(out)))
     return out
@@ -239,7 +203,7 @@ def eval_polynomial(polys, points, poly_index=None) -> np.ndarray:
         raise ValueError("eval_polynomial: more points than polynomials (pass poly_index)")
     out = np.zeros((q, 4), dtype=np.uint64)
     _lib.check(lib.hm_eval_polynomial_bn256_fr_dev(
-        ctypes.c_void_p(polys.data_ptr()), n, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if idx is not None else None,
+        ctypes.c_void_p(polys.data_ptr()), n, idx.ctypes.data_as(_u32p) if idx is not None else None,
         _ptr(pts), q, _ptr(out), ctypes.c_void_p(_stream_ptr(polys))))
     return out
 
@@ -279,10 +243,6 @@ def grand_product(factors, start, out=None):
     _lib.check(lib.hm_fr_grand_product_dev(ctypes.c_void_p(factors.data_ptr()), n, _ptr(st), ctypes.c_void_p(out.data_ptr()),
                                            ctypes.c_void_p(_stream_ptr(factors))))
     return out
-
-
-def _ptr_array(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
 def kate_division_batch(polys, zs):
@@ -425,12 +385,12 @@ def permute_expression_pairs(input_columns, table_columns, usable_rows: int, bli
         raise ValueError("permute_expression_pairs: usable_rows out of range")
     outs = [(torch.empty((n, 4), dtype=torch.int64, device=ins[0].device), torch.empty((n, 4), dtype=torch.int64, device=ins[0].device))
             for _ in ins]
-    arr = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    arr = _ptr_array
     missing = (ctypes.c_int * len(ins))()
     st = ctypes.c_void_p(_stream_ptr(ins[0]))
     rc = lib.hm_lookup_permute_batch_bn256_fr_dev(arr(ins), arr(tabs), len(ins), usable_rows, arr([o[0] for o in outs]),
                                                   arr([o[1] for o in outs]), missing, st)
-    if rc != 0:
+    if rc != _lib.HM_OK:
         err = _lib.Halo2Mi355xError(rc, lib.hm_last_error().decode())
         err.missing = [i for i in range(len(ins)) if missing[i]]
         raise err
@@ -492,8 +452,6 @@ def g1_fft_host(xyz: np.ndarray, omega, log_n: int, scale=None) -> None:
 def g_to_lagrange(g, k: int):
     """``halo2_proofs::arithmetic::g_to_lagrange``: the Lagrange basis [L_i(s)]G1 from the monomial points g[i] = [s^i]G1 (a (2^k, 8)
     GPU tensor), as a new tensor.  omega^-1 = ROOT_OF_UNITY_INV squared S - k times, n^-1 = TWO_INV^k, as upstream computes them."""
-    from .domain import FR_MODULUS, FR_ROOT_OF_UNITY, FR_S, fr_words
-
     r = FR_MODULUS
     omega_inv = pow(FR_ROOT_OF_UNITY, -1, r)
     for _ in range(k, FR_S):
@@ -505,7 +463,7 @@ def g_to_lagrange(g, k: int):
 
 
 # ---- SRS point encodings (ParamsKZG.read / write) ----------------------------------------------------------
-HM_ERR_INVALID_DATA = -7
+HM_ERR_INVALID_DATA = _lib.HM_ERR_INVALID_DATA
 
 
 class InvalidPointError(ValueError):
@@ -630,18 +588,3 @@ def msm_stats() -> dict:
     st = _lib.MsmStats()
     _lib.check(_lib.load().hm_get_msm_stats(ctypes.byref(st)))
     return {k: getattr(st, k) for k, _ in st._fields_}
-
-
-FQ_MODULUS = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
-
-
-def fq_words(v: int) -> np.ndarray:
-    """Canonical integer -> 4 Montgomery limbs of Fq (the bytes Rust's ``Fq`` holds)."""
-    m = (v % FQ_MODULUS) * (1 << 256) % FQ_MODULUS
-    return np.array([(m >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
-
-
-# Montgomery one of Fq (2^256 mod p): the z coordinate of a normalised G1
-FQ_ONE_MONT = fq_words(1)
-# bn256::G1Affine::generator() = (1, 2)
-G1_GENERATOR = np.concatenate([fq_words(1), fq_words(2)])

@@ -20,20 +20,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .arithmetic import _np, _ptr, _stream_ptr, _tensor_rows
-
-FR_MODULUS = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
-FR_S = 28
-FR_GENERATOR = 7
-FR_ROOT_OF_UNITY = pow(FR_GENERATOR, (FR_MODULUS - 1) >> FR_S, FR_MODULUS)
-FR_ZETA = 0x30644E72E131A029048B6E193FD84104CC37A73FEC2BC5E9B8CA0B2D36636F23
-_MONT = 1 << 256
-
-
-def fr_words(v: int) -> np.ndarray:
-    """Canonical integer -> 4 Montgomery limbs (the bytes Rust's ``Fr`` holds)."""
-    m = (v % FR_MODULUS) * _MONT % FR_MODULUS
-    return np.array([(m >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+from ._marshal import _np, _ptr, _stream_ptr, _tensor_rows
+from .bn256 import FR_GENERATOR, FR_MODULUS, FR_ROOT_OF_UNITY, FR_S, FR_ZETA, fr_words  # noqa: F401  (re-exported)
 
 
 def _vandermonde_inverse(nodes, r):

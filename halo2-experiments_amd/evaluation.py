@@ -27,7 +27,7 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .arithmetic import _ptr, _stream_ptr, _tensor_rows
+from ._marshal import _ptr, _ptr_array, _stream_ptr, _tensor_rows, _u32p
 from .domain import FR_MODULUS, fr_words
 
 R = FR_MODULUS
@@ -311,7 +311,7 @@ class CompiledGraph:
         consts = np.stack([fr_words(c) for c in constants]) if constants else np.zeros((0, 4), dtype=np.uint64)
         rots = np.array(rotations, dtype=np.int32)
         h = ctypes.c_uint64(0)
-        _lib.check(lib.hm_graph_create(self.calcs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), self.calcs.shape[0],
+        _lib.check(lib.hm_graph_create(self.calcs.ctypes.data_as(_u32p), self.calcs.shape[0],
                                        _ptr(consts) if len(constants) else None, len(constants), n_dynamic,
                                        rots.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if len(rotations) else None,
                                        len(rotations), n_columns, n_intermediates, ctypes.byref(h)))
@@ -343,7 +343,7 @@ class CompiledGraph:
         dyn = np.stack([fr_words(v) for v in list(challenges) + [beta, gamma, theta, y]])
         _lib.check(_lib.load().hm_graph_evaluate_segments_dev(ctypes.c_uint64(self.handle), ptrs, len(columns), _ptr(dyn), dyn.shape[0],
                                                               seg.bit_length() - 1, segments, ctypes.c_void_p(values.data_ptr()),
-                                                              1 if columns_internal else 0, ctypes.c_void_p(_stream_ptr(values))))
+                                                              _lib.HM_GRAPH_COLUMNS_INTERNAL if columns_internal else 0, ctypes.c_void_p(_stream_ptr(values))))
 
     def _quotient_args(self, domain, coeff_columns, cosets, challenges, beta, gamma, theta, y, on_cosets, who):
         cosets = list(range(domain.min_cosets())) if cosets is None else [int(c) for c in cosets]
@@ -472,7 +472,7 @@ def quotient_combine(domain, partials: Sequence, cosets: Sequence[int], pieces: 
         raise ValueError("quotient_combine: one (n, 4) partial per coset")
     pieces = len(cosets) if pieces is None else pieces
     out = torch.empty((pieces * domain.n, 4), dtype=parts[0].dtype, device=parts[0].device)
-    ptrs = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
+    ptrs = _ptr_array(parts)
     shifts = np.stack([fr_words(domain.coset_shift(c)) for c in cosets])
     _lib.check(_lib.load().hm_quotient_combine_bn256_fr_dev(ptrs, _ptr(shifts), len(parts), domain.k, pieces, ctypes.c_void_p(out.data_ptr()),
                                                            ctypes.c_void_p(_stream_ptr(out))))

@@ -15,7 +15,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .arithmetic import _is_tensor, _ptr, _stream_ptr, best_multiexp_batch
+from ._marshal import _dev_ptr, _is_tensor, _ptr, _stream_ptr, _u32p
+from .arithmetic import best_multiexp_batch
 from .circuits import ConstraintSystem
 from .domain import FR_GENERATOR, FR_MODULUS, FR_S, EvaluationDomain, fr_words
 from .kzg import ParamsKZG
@@ -23,11 +24,10 @@ from .poseidon import ints_to_words
 
 R = FR_MODULUS
 FR_DELTA = pow(FR_GENERATOR, 1 << FR_S, R)          # ``Fr::DELTA``: generates the cosets the permutation argument's columns stand on
-_u32p = ctypes.POINTER(ctypes.c_uint32)
 
 
 def _u32(t):
-    return ctypes.cast(ctypes.c_void_p(t.data_ptr()), _u32p)
+    return _dev_ptr(t, _u32p)
 
 
 def copy_pairs(cs: ConstraintSystem, layout) -> np.ndarray:

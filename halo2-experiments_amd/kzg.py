@@ -33,10 +33,12 @@ from typing import BinaryIO, Optional
 import numpy as np
 
 from . import _lib
-from .arithmetic import (FQ_MODULUS, G1_GENERATOR, BasesHandle, InvalidPointError, _is_tensor, _ptr, _stream_ptr, best_multiexp,
+from ._marshal import _is_tensor, _ptr, _stream_ptr
+from .arithmetic import (BasesHandle, InvalidPointError, best_multiexp,
                          best_multiexp_submit, best_multiexp_wait, g1_check_host, g1_compress, g1_compress_host, g1_decompress,
                          g1_fixed_base_mul, g_to_lagrange, register_bases, release_bases)
-from .domain import FR_MODULUS, EvaluationDomain, fr_words
+from .bn256 import FQ_MODULUS, FR_MODULUS, G1_GENERATOR, fq_ints, fq_words, fr_words
+from .domain import EvaluationDomain
 
 _P = FQ_MODULUS
 # bn256::G2Affine::generator() (the alt_bn128 G2 generator of EIP-197), x = x0 + x1 u, y = y0 + y1 u, u^2 = -1
@@ -88,7 +90,7 @@ def g2_mul(k: int, p=G2_GENERATOR):
 
 
 def _fq_mont_bytes(v: int) -> bytes:
-    return (v % _P * (1 << 256) % _P).to_bytes(32, "little")
+    return fq_words(v).tobytes()
 
 
 def g2_bytes(p) -> bytes:
@@ -177,8 +179,7 @@ def g2_from_bytes(data: bytes, check: bool = False):
         raise ValueError("g2_from_bytes: coordinate >= p")
     if not any(words):
         return None
-    rinv = pow(1 << 256, -1, _P)
-    c = [w * rinv % _P for w in words]
+    c = fq_ints(np.frombuffer(data, dtype=np.uint64))
     p = ((c[0], c[1]), (c[2], c[3]))
     if check and not g2_on_curve(p):
         raise ValueError("g2_from_bytes: not on the curve")

@@ -37,6 +37,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from ._marshal import _dev_ptr, _ptr, _stream_ptr, _u32p
 from .circuits import ConstraintSystem
 from .domain import FR_MODULUS, fr_words
 from .evaluation import Advice, Expression, Fixed, GraphEvaluator, Instance, Negated, Product, Scaled, Sum
@@ -45,8 +46,6 @@ from .poseidon import ints_to_words
 
 R = FR_MODULUS
 KINDS = ("gate", "copy", "lookup")
-_u64p = ctypes.POINTER(ctypes.c_uint64)
-_u32p = ctypes.POINTER(ctypes.c_uint32)
 
 
 class NotSatisfied(AssertionError):
@@ -261,15 +260,13 @@ class MockProver:
         """what every pass of one call shares: the batch, its table, the per-call constants, the flag array"""
         import torch
 
-        from .arithmetic import _stream_ptr
-
         advice, insts, m = self._batch(advice, instance)
         d = self._dev
         y = random.Random(seed).randrange(1, R)
         dyn = np.ascontiguousarray(np.stack([fr_words(v) for v in (0, 0, 0, y)]))
         with torch.cuda.device(d.device):
             flags = torch.zeros(m, dtype=torch.uint8, device=d.device)
-        return types.SimpleNamespace(advice=advice, insts=insts, m=m, dyn=dyn, dynp=dyn.ctypes.data_as(_u64p), flags=flags,
+        return types.SimpleNamespace(advice=advice, insts=insts, m=m, dyn=dyn, dynp=_ptr(dyn), flags=flags,
                                      table=self._table(advice, insts), stream=ctypes.c_void_p(_stream_ptr(advice)), out=ctypes.c_uint64(0))
 
     def _gates(self, c, prog, lanes):
@@ -278,10 +275,8 @@ class MockProver:
 
         def launch(rec, cap, counter):
             _lib.check(_lib.load().hm_mock_gates_dev(ctypes.c_uint64(prog.handle), bases, strides, rows, count, c.dynp, 4, self.k, self.usable, c.m,
-                                                     ctypes.c_void_p(lanes.data_ptr()) if lanes is not None else None,
-                                                     lanes.numel() if lanes is not None else 0, ctypes.c_void_p(rec.data_ptr()), cap,
-                                                     ctypes.c_void_p(counter.data_ptr()), ctypes.c_void_p(c.flags.data_ptr()),
-                                                     ctypes.byref(c.out), c.stream))
+                                                     _dev_ptr(lanes), lanes.numel() if lanes is not None else 0, _dev_ptr(rec), cap,
+                                                     _dev_ptr(counter), ctypes.c_void_p(c.flags.data_ptr()), ctypes.byref(c.out), c.stream))
             return c.out.value
         return launch
 
@@ -324,8 +319,8 @@ class MockProver:
             if d.pairs is not None:
                 def launch(rec, cap, counter):
                     _lib.check(lib.hm_mock_copies_dev(bases, strides, rows, count, self._perm.ctypes.data_as(_u32p), len(self._perm),
-                                                      ctypes.c_void_p(d.pairs.data_ptr()), len(self._pairs), self.k, m,
-                                                      ctypes.c_void_p(rec.data_ptr()), cap, ctypes.c_void_p(counter.data_ptr()),
+                                                      _dev_ptr(d.pairs, _u32p), len(self._pairs), self.k, m,
+                                                      _dev_ptr(rec), cap, _dev_ptr(counter),
                                                       ctypes.c_void_p(flags.data_ptr()), ctypes.byref(out_total), stream))
                     return out_total.value
                 total["copy"], rec = self._collect(launch, cap0)
@@ -344,8 +339,8 @@ class MockProver:
                                 cols.append(col)
                             lk.table.evaluate(cols, table)
                         _lib.check(lib.hm_mock_lookup_dev(ctypes.c_uint64(lk.input.handle), tb[0], tb[1], tb[2], tb[3], dynp, 4, self.k, self.usable,
-                                                          count_u, u, ctypes.c_void_p(table.data_ptr()), ctypes.c_void_p(rec.data_ptr()), cap,
-                                                          ctypes.c_void_p(counter.data_ptr()), ctypes.c_void_p(flags.data_ptr()),
+                                                          count_u, u, ctypes.c_void_p(table.data_ptr()), _dev_ptr(rec), cap,
+                                                          _dev_ptr(counter), ctypes.c_void_p(flags.data_ptr()),
                                                           ctypes.byref(out_total), stream))
                     return out_total.value
                 t, rec = self._collect(launch, cap0)

@@ -10,8 +10,7 @@ Also here: G1 on host integers (affine tuples, ``None`` = identity) for the veri
 through bilinearity, non-degeneracy and e(P, Q)^r = 1, which no wrong Miller loop or exponent survives."""
 from __future__ import annotations
 
-from .arithmetic import FQ_MODULUS
-from .domain import FR_MODULUS
+from .bn256 import FQ_MODULUS, FR_MODULUS
 from .kzg import G2_GENERATOR, _fq2_inv, _fq2_mul, _fq2_sub, g2_on_curve
 
 P = FQ_MODULUS

@@ -19,23 +19,13 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .arithmetic import _is_tensor, _np, _ptr, _stream_ptr, _tensor_rows, to_host
-from .domain import FR_MODULUS, fr_words
+from ._marshal import _dev_ptr, _is_tensor, _np, _ptr, _stream_ptr, _tensor_rows, _u32p
+from .arithmetic import to_host
+from .bn256 import FR_MODULUS, fr_array, fr_ints
 
 R = FR_MODULUS
-_R_INV = pow(1 << 256, -1, R)
-_HM_ERR_NOT_FOUND = -4
-
-
-def words_to_ints(words) -> List[int]:
-    """(…, 4) uint64 Montgomery words -> canonical integers, flattened."""
-    w = np.ascontiguousarray(np.asarray(words).view(np.uint64).reshape(-1, 4))
-    return [int.from_bytes(row.tobytes(), "little") * _R_INV % R for row in w]
-
-
-def ints_to_words(values: Sequence[int]) -> np.ndarray:
-    """canonical integers -> (n, 4) uint64 Montgomery words"""
-    return np.stack([fr_words(int(v)) for v in values]) if len(values) else np.zeros((0, 4), dtype=np.uint64)
+words_to_ints = fr_ints          # (…, 4) uint64 Montgomery words -> canonical integers, flattened
+ints_to_words = fr_array         # canonical integers -> (n, 4) uint64 Montgomery words
 
 
 # ---- the constant generator ---------------------------------------------------------------------------------------------------
@@ -176,7 +166,7 @@ class Spec:
     def call(self, fn, *args) -> None:
         """``fn(handle, *args)`` checked; a handle that died with its context (``hm_shutdown``) is made again once."""
         rc = fn(ctypes.c_uint64(self.handle()), *args)
-        if rc == _HM_ERR_NOT_FOUND:
+        if rc == _lib.HM_ERR_NOT_FOUND:
             self._handles = {}
             rc = fn(ctypes.c_uint64(self.handle()), *args)
         _lib.check(rc)
@@ -311,7 +301,7 @@ class _Tree:
         out = torch.empty((len(idx), self.depth, self.ELEMS, 4), dtype=torch.int64, device=self.nodes.device)
         with torch.cuda.device(self.nodes.device):
             _lib.check(_lib.load().hm_merkle_paths_dev(ctypes.c_void_p(self.nodes.data_ptr()), self.depth, self.ELEMS,
-                                                       ctypes.cast(ctypes.c_void_p(d_idx.data_ptr()), ctypes.POINTER(ctypes.c_uint64)),
+                                                       _dev_ptr(d_idx),
                                                        len(idx), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(_stream_ptr(self.nodes))))
         return to_host(out.reshape(-1, 4)).reshape(len(idx), self.depth, self.ELEMS, 4), idx
 
@@ -348,9 +338,9 @@ class _Tree:
         fn = _lib.load().hm_merkle_sum_tree_update_dev if self.WIDTH == 5 else _lib.load().hm_merkle_tree_update_dev
         with torch.cuda.device(dev):
             self.spec.call(fn, self.depth, ctypes.c_void_p(self.nodes.data_ptr()),
-                           ctypes.cast(ctypes.c_void_p(d_idx.data_ptr() if m else None), ctypes.POINTER(ctypes.c_uint64)),
+                           _dev_ptr(d_idx if m else None),
                            ctypes.c_void_p(leaves.data_ptr() if m else None), m,
-                           ctypes.cast(ctypes.c_void_p(counts.data_ptr() if return_counts else None), ctypes.POINTER(ctypes.c_uint32)),
+                           _dev_ptr(counts, _u32p),
                            ctypes.c_void_p(_stream_ptr(self.nodes)))
         if return_counts:
             return [int(v) for v in counts.cpu().tolist()]
@@ -393,7 +383,7 @@ class _Tree:
         out = torch.empty((m, cls.ELEMS, 4), dtype=torch.int64, device=leaves.device)
         with torch.cuda.device(leaves.device):
             spec.call(lib.hm_merkle_roots_bn256_dev, rows // m, m, ctypes.c_void_p(leaves.data_ptr()), ctypes.c_void_p(siblings.data_ptr()),
-                      ctypes.cast(ctypes.c_void_p(d_idx.data_ptr()), ctypes.POINTER(ctypes.c_uint64)), ctypes.c_void_p(out.data_ptr()),
+                      _dev_ptr(d_idx), ctypes.c_void_p(out.data_ptr()),
                       ctypes.c_void_p(_stream_ptr(leaves)))
         return out
 
@@ -442,7 +432,7 @@ class MerkleSumTree(_Tree):
         sib = torch.empty((len(idx), self.depth, 2, 4), dtype=torch.int64, device=self.nodes.device)
         with torch.cuda.device(self.nodes.device):
             _lib.check(_lib.load().hm_merkle_paths_dev(ctypes.c_void_p(self.nodes.data_ptr()), self.depth, 2,
-                                                       ctypes.cast(ctypes.c_void_p(d_idx.data_ptr()), ctypes.POINTER(ctypes.c_uint64)),
+                                                       _dev_ptr(d_idx),
                                                        len(idx), ctypes.c_void_p(sib.data_ptr()), ctypes.c_void_p(_stream_ptr(self.nodes))))
         leaves = self.nodes[d_idx].contiguous()
         return merkle_sum_witness(self.spec, leaves, sib, d_idx, assets_sum, k, nodes=self.nodes, out=out)
@@ -495,7 +485,7 @@ class MerkleTree(_Tree):
         sib = torch.empty((len(idx), self.depth, 4), dtype=torch.int64, device=self.nodes.device)
         with torch.cuda.device(self.nodes.device):
             _lib.check(_lib.load().hm_merkle_paths_dev(ctypes.c_void_p(self.nodes.data_ptr()), self.depth, 1,
-                                                       ctypes.cast(ctypes.c_void_p(d_idx.data_ptr()), ctypes.POINTER(ctypes.c_uint64)),
+                                                       _dev_ptr(d_idx),
                                                        len(idx), ctypes.c_void_p(sib.data_ptr()), ctypes.c_void_p(_stream_ptr(self.nodes))))
         leaves = self.nodes[d_idx].contiguous()
         return merkle_witness(self.spec, leaves, sib, d_idx, k, nodes=self.nodes, out=out)

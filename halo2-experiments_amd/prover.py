@@ -19,7 +19,8 @@ import struct
 import numpy as np
 
 from . import circuits, evaluation as ev
-from .arithmetic import (_is_tensor, batch_invert, best_multiexp_batch, eval_polynomial, grand_product_batch, linear_combination,
+from ._marshal import _is_tensor
+from .arithmetic import (batch_invert, best_multiexp_batch, eval_polynomial, grand_product_batch, linear_combination,
                          permute_expression_pairs, random_fr)
 from .domain import FR_MODULUS, FR_ZETA, fr_words
 from .keygen import FR_DELTA, ProvingKey, VerifyingKey

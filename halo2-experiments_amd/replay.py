@@ -44,7 +44,8 @@ import numpy as np
 from .arithmetic import (G1_GENERATOR, to_host, batch_invert, best_multiexp, best_multiexp_submit, best_multiexp_wait, eval_polynomial,
                          g1_fixed_base_mul, grand_product_batch, kate_division, kate_division_batch, linear_combination, permute_expression_pairs, register_bases,
                          release_bases)
-from .domain import EvaluationDomain, FR_MODULUS, fr_words
+from .bn256 import FR_MODULUS, FR_RADIX, fr_words
+from .domain import EvaluationDomain
 from .kzg import ParamsKZG
 from .sharding import (_NO_GROUP, coset_owners, gather_coset_partials, job_owner, job_parallel_multiexp_batch, shard_range, sharded_multiexp,
                        sharded_multiexp_batch)
@@ -98,14 +99,14 @@ def _sparse_column(n, used_rows, seed, device):
     import torch
 
     from . import _lib
-    from .arithmetic import _ptr, _stream_ptr
+    from ._marshal import _ptr, _stream_ptr
     col = torch.zeros((n, 4), dtype=torch.int64, device=device)
     g = torch.Generator(device=device)
     g.manual_seed(seed)
     col[:used_rows, 0] = torch.randint(1, 1 << 16, (used_rows,), dtype=torch.int64, device=device, generator=g)
     col[: used_rows // 2, 0] = 1
     # raw word v read as a Montgomery word is the field element v / R; times R gives v, stored as v*R
-    _lib.check(_lib.load().hm_fr_scale_dev(ctypes.c_void_p(col.data_ptr()), n, _ptr(fr_words((1 << 256) % FR_MODULUS)),
+    _lib.check(_lib.load().hm_fr_scale_dev(ctypes.c_void_p(col.data_ptr()), n, _ptr(fr_words(FR_RADIX)),
                                            ctypes.c_void_p(_stream_ptr(col))))
     col[n - 6:] = _rand_fr(6, seed + 1, device)
     return col
@@ -259,7 +260,7 @@ def run_replay(shape_name: str, device=None, group=None, include_host_pointer_es
     # a range-check lookup: the table holds 0 .. 2^16 - 1 (repeated), the input column values of that range
     lookup_table = torch.zeros((n, 4), dtype=torch.int64, device=device)
     lookup_table[:, 0] = torch.arange(n, device=device) % min(n - 7, 1 << 16)
-    lookup_table = linear_combination([lookup_table], np.stack([fr_words((1 << 256) % FR_MODULUS)]))
+    lookup_table = linear_combination([lookup_table], np.stack([fr_words(FR_RADIX)]))
     lookup_input = lookup_table[torch.randperm(n, device=device)].contiguous()
     lookup_input[n - 7:] = lookup_table[:7]            # (rows beyond the usable ones are not read)
     for st in slots[1:]:                               # the devices beyond the first build the z / permuted columns themselves

@@ -20,9 +20,9 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .domain import FR_MODULUS, fr_words
+from ._marshal import _ptr, _u32p, _vp
+from .bn256 import FR_MODULUS, fr_words
 
-_vp = ctypes.c_void_p
 FR_ONE = fr_words(1)
 
 
@@ -48,7 +48,7 @@ class _Sys:
 
 
 sys = _Sys()
-HM_OK = 0
+HM_OK = _lib.HM_OK
 
 
 def _last_error() -> str:
@@ -62,10 +62,6 @@ def entry_points_of_the_rust_file(path: str) -> List[str]:
         if m.group(1) not in seen:
             seen.append(m.group(1))
     return seen
-
-
-def _u64p(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
 
 
 def _host(a) -> np.ndarray:
@@ -176,7 +172,7 @@ class DeviceDomain:
         if count == 0 or (first + count) * self.n() > a.len:
             return False
         w, d = fr_words(self.omega_inv), fr_words(self.ifft_divisor)
-        return sys.hm_ntt_batch_bn256_fr_dev(_vp(a.ptr + first * self.n() * 32), count, _u64p(w), self.k, _u64p(d), None, None) == HM_OK
+        return sys.hm_ntt_batch_bn256_fr_dev(_vp(a.ptr + first * self.n() * 32), count, _ptr(w), self.k, _ptr(d), None, None) == HM_OK
 
     def coeff_to_extended(self, a: DevicePoly, internal: bool) -> Optional[DevicePoly]:
         if a.len == 0 or a.len % self.n():
@@ -186,16 +182,16 @@ class DeviceDomain:
         if ext is None:
             return None
         coset = self._coset_words(32 if internal else 1)
-        rc = sys.hm_coeff_to_extended_bn256_fr_dev(_vp(a.ptr), _vp(ext.ptr), batch, _u64p(fr_words(self.extended_omega)), self.k, self.extended_k,
-                                                   _u64p(coset), None)
+        rc = sys.hm_coeff_to_extended_bn256_fr_dev(_vp(a.ptr), _vp(ext.ptr), batch, _ptr(fr_words(self.extended_omega)), self.k, self.extended_k,
+                                                   _ptr(coset), None)
         return ext if rc == HM_OK else None
 
     def extended_to_coeff(self, a: DevicePoly) -> bool:
         if a.len == 0 or a.len % self.extended_len():
             return False
         c = np.concatenate([FR_ONE, fr_words(self.g_coset_inv), fr_words(self.g_coset)])
-        return sys.hm_extended_to_coeff_bn256_fr_dev(_vp(a.ptr), a.len // self.extended_len(), _u64p(fr_words(self.extended_omega_inv)), self.extended_k,
-                                                     _u64p(fr_words(self.extended_ifft_divisor)), _u64p(c), None) == HM_OK
+        return sys.hm_extended_to_coeff_bn256_fr_dev(_vp(a.ptr), a.len // self.extended_len(), _ptr(fr_words(self.extended_omega_inv)), self.extended_k,
+                                                     _ptr(fr_words(self.extended_ifft_divisor)), _ptr(c), None) == HM_OK
 
     def coset_shift(self, j: int) -> int:
         return self.g_coset * pow(self.extended_omega, j, FR_MODULUS) % FR_MODULUS
@@ -203,7 +199,7 @@ class DeviceDomain:
 
 def commit_dev(handle: int, scalars: DevicePoly) -> Optional[np.ndarray]:
     xyz = np.zeros(12, dtype=np.uint64)
-    if sys.hm_msm_bn256_g1_dev(ctypes.c_uint64(handle), 0, _vp(scalars.ptr), scalars.len, None, _u64p(xyz)) != HM_OK:
+    if sys.hm_msm_bn256_g1_dev(ctypes.c_uint64(handle), 0, _vp(scalars.ptr), scalars.len, None, _ptr(xyz)) != HM_OK:
         return None
     return xyz
 
@@ -216,7 +212,7 @@ def commit_batch_dev(handle: int, columns: Sequence[DevicePoly]) -> Optional[np.
         return None
     ptrs = (_vp * len(columns))(*[c.ptr for c in columns])
     out = np.zeros((len(columns), 12), dtype=np.uint64)
-    if sys.hm_msm_batch_bn256_g1_dev(ctypes.c_uint64(handle), 0, ptrs, n, len(columns), None, _u64p(out)) != HM_OK:
+    if sys.hm_msm_batch_bn256_g1_dev(ctypes.c_uint64(handle), 0, ptrs, n, len(columns), None, _ptr(out)) != HM_OK:
         return None
     return out
 
@@ -228,7 +224,7 @@ def commit_pieces_dev(handle: int, polys: DevicePoly, n: int, first: int, count:
         return None
     ptrs = (_vp * count)(*[polys.ptr + i * n * 32 for i in range(first, first + count)])
     out = np.zeros((count, 12), dtype=np.uint64)
-    if sys.hm_msm_batch_bn256_g1_dev(ctypes.c_uint64(handle), 0, ptrs, n, count, None, _u64p(out)) != HM_OK:
+    if sys.hm_msm_batch_bn256_g1_dev(ctypes.c_uint64(handle), 0, ptrs, n, count, None, _ptr(out)) != HM_OK:
         return None
     return out
 
@@ -240,7 +236,7 @@ def commit_indexed_dev(handle: int, polys: DevicePoly, n: int, indices: Sequence
         return None
     ptrs = (_vp * len(indices))(*[polys.ptr + i * n * 32 for i in indices])
     out = np.zeros((len(indices), 12), dtype=np.uint64)
-    if sys.hm_msm_batch_bn256_g1_dev(ctypes.c_uint64(handle), 0, ptrs, n, len(indices), None, _u64p(out)) != HM_OK:
+    if sys.hm_msm_batch_bn256_g1_dev(ctypes.c_uint64(handle), 0, ptrs, n, len(indices), None, _ptr(out)) != HM_OK:
         return None
     return out
 
@@ -250,7 +246,7 @@ def eval_polynomial_dev(polys: DevicePoly, n: int, points) -> Optional[np.ndarra
     if n == 0 or polys.len < n * points.shape[0]:
         return None
     out = np.empty((points.shape[0], 4), dtype=np.uint64)
-    if sys.hm_eval_polynomial_bn256_fr_dev(_vp(polys.ptr), n, None, _u64p(points), points.shape[0], _u64p(out), None) != HM_OK:
+    if sys.hm_eval_polynomial_bn256_fr_dev(_vp(polys.ptr), n, None, _ptr(points), points.shape[0], _ptr(out), None) != HM_OK:
         return None
     return out
 
@@ -268,7 +264,7 @@ class QuotientProgram:
         constants = _host(constants) if len(constants) else np.zeros((0, 4), dtype=np.uint64)
         rotations = np.ascontiguousarray(rotations, dtype=np.int32)
         h = ctypes.c_uint64(0)
-        rc = sys.hm_graph_create(calcs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), calcs.shape[0], _u64p(constants), constants.shape[0], n_dynamic,
+        rc = sys.hm_graph_create(calcs.ctypes.data_as(_u32p), calcs.shape[0], _ptr(constants), constants.shape[0], n_dynamic,
                                  rotations.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), rotations.shape[0], n_columns, n_intermediates,
                                  ctypes.byref(h))
         return cls(h.value, n_columns, n_dynamic) if rc == HM_OK else None
@@ -283,8 +279,8 @@ class QuotientProgram:
             return None
         w = fr_words(domain.omega)
         for slot, i in enumerate(which):
-            if sys.hm_coeff_to_cosets_bn256_fr_dev(_vp(table.ptr + i * n * 32), _vp(kept.ptr + slot * len(cosets) * n * 32), 1, _u64p(w), domain.k,
-                                                   _u64p(shifts), len(cosets), 1, None) != HM_OK:
+            if sys.hm_coeff_to_cosets_bn256_fr_dev(_vp(table.ptr + i * n * 32), _vp(kept.ptr + slot * len(cosets) * n * 32), 1, _ptr(w), domain.k,
+                                                   _ptr(shifts), len(cosets), 1, None) != HM_OK:
                 return None
         return kept
 
@@ -307,8 +303,8 @@ class QuotientProgram:
         h = DevicePoly.new(len(cosets) * n)
         if h is None:
             return None
-        rc = sys.hm_quotient_by_cosets_bn256_fr_dev(ctypes.c_uint64(self.handle), ptrs, pre, self.n_columns, _u64p(dynamic), dynamic.shape[0], domain.k,
-                                                    _u64p(fr_words(domain.omega)), _u64p(shifts), len(cosets), len(cosets), _vp(h.ptr), None)
+        rc = sys.hm_quotient_by_cosets_bn256_fr_dev(ctypes.c_uint64(self.handle), ptrs, pre, self.n_columns, _ptr(dynamic), dynamic.shape[0], domain.k,
+                                                    _ptr(fr_words(domain.omega)), _ptr(shifts), len(cosets), len(cosets), _vp(h.ptr), None)
         return h if rc == HM_OK else None
 
     def quotient_by_cosets(self, domain: DeviceDomain, columns: Sequence[DevicePoly], dynamic, cosets: Sequence[int]) -> Optional[DevicePoly]:

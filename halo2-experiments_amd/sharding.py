@@ -15,14 +15,14 @@ every rank by ``hm_g1_sum`` -- EC addition is not an RCCL reduction operator, so
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from typing import Callable, Optional, Tuple
 
 import numpy as np
 
 from . import _lib
-from .arithmetic import _ptr, best_multiexp
+from ._marshal import _ptr
+from .arithmetic import best_multiexp
 
 
 def shard_range(n: int, rank: int, world: int) -> Tuple[int, int]:

@@ -18,15 +18,13 @@ from __future__ import annotations
 import ctypes
 from typing import Hashable, List, Sequence, Tuple
 
-import numpy as np
-
 from . import _lib
-from .arithmetic import FQ_MODULUS, _is_tensor, _ptr, _stream_ptr, _tensor_rows
-from .domain import FR_MODULUS, fr_words
+from ._marshal import _is_tensor, _ptr, _ptr_array, _stream_ptr, _tensor_rows
+from .bn256 import FR_MODULUS, fr_array, fr_words, g1_ints
 from .pairing import G1_GEN, g1_msm
 
 R = FR_MODULUS
-MAX_POINTS = 4                      # HM_SHPLONK_MAX_POINTS
+MAX_POINTS = _lib.HM_SHPLONK_MAX_POINTS
 _LANES_MAX, _THREADS = 65536, 256
 
 
@@ -161,10 +159,6 @@ def construct_intermediate_sets(queries):
 
 
 # ---- the device entry -------------------------------------------------------------------------------------------------------------------
-def _words(values) -> np.ndarray:
-    return np.ascontiguousarray(np.stack([fr_words(int(v) % R) for v in values]))
-
-
 def set_quotient(polys, weights, points, scale: int = 1, out=None, accumulate: bool = False):
     """``out (+)= scale * (sum_j weights[j] polys[j] - R) / prod_l (X - points[l])`` on the device, one call of
     ``hm_shplonk_set_quotient_bn256_fr_dev``: ``polys`` a list of (n, 4) GPU tensors, ``weights`` / ``points`` / ``scale`` integers.
@@ -189,25 +183,15 @@ def set_quotient(polys, weights, points, scale: int = 1, out=None, accumulate: b
         out = torch.empty((n, 4), dtype=torch.int64, device=polys[0].device)
     elif not _is_tensor(out) or _tensor_rows(out, 4, "out") != n:
         raise ValueError("set_quotient: out differs in length")
-    ptrs = (ctypes.c_void_p * len(polys))(*[p.data_ptr() for p in polys])
     with torch.cuda.device(out.device):
-        _lib.check(_lib.load().hm_shplonk_set_quotient_bn256_fr_dev(ptrs, _ptr(_words(weights)), len(polys), n, _ptr(_words(pts)), len(pts),
+        _lib.check(_lib.load().hm_shplonk_set_quotient_bn256_fr_dev(_ptr_array(polys), _ptr(fr_array(weights)), len(polys), n, _ptr(fr_array(pts)), len(pts),
                                                                     _ptr(fr_words(int(scale) % R)), ctypes.c_void_p(out.data_ptr()),
                                                                     1 if accumulate else 0, ctypes.c_void_p(_stream_ptr(out))))
     return out
 
 
 # ---- prover and verifier ----------------------------------------------------------------------------------------------------------------
-_FQ_RINV = pow(1 << 256, -1, FQ_MODULUS)
-
-
-def g1_words_to_int(words):
-    """(x, y) integers of 12 (or 8) Montgomery words of a normalised G1; None for the identity (all-zero z, or (0, 0))"""
-    w = [int(v) for v in np.asarray(words, dtype=np.uint64).reshape(-1)]
-    if len(w) == 12 and not any(w[8:]):
-        return None
-    x, y = (sum(w[4 * c + i] << (64 * i) for i in range(4)) * _FQ_RINV % FQ_MODULUS for c in range(2))
-    return None if (x, y) == (0, 0) else (x, y)
+g1_words_to_int = g1_ints        # 12 (or 8) Montgomery words of a normalised G1 -> (x, y) integers, None for the identity
 
 
 def _powers(base: int, count: int) -> List[int]:

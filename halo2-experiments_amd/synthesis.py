@@ -44,9 +44,9 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _lib
-from .arithmetic import _ptr
+from ._marshal import _dev_ptr, _ptr, _stream_ptr, _tensor_rows
+from .bn256 import FR_MODULUS, fr_array, fr_words
 from .circuits import ConstraintSystem, merkle_sum_tree
-from .domain import FR_MODULUS, fr_words
 from .poseidon import Spec, default_spec, ints_to_words
 
 R = FR_MODULUS
@@ -548,8 +548,6 @@ def permutation_columns(cs: ConstraintSystem, layout: "AnyLayout", omega: int, d
     ``hm_fr_scale_dev``, the cells of the copy cycles scattered in."""
     import torch
 
-    from .arithmetic import _stream_ptr
-
     lib, n, P = _lib.load(), layout.n, len(cs.equality)
     out = torch.empty((P, n, 4), dtype=torch.int64, device=device)
     with torch.cuda.device(out.device):
@@ -606,8 +604,6 @@ def _witness_out(who: str, out, m: int, n_advice: int, n: int, device):
 
 def _path_tensors(who: str, elements: int, leaves, siblings, indices, nodes, out) -> Tuple[int, int]:
     """the checks of the path circuits' GPU tensors (``elements`` per node) -> (m, depth)"""
-    from .arithmetic import _tensor_rows
-
     m = _tensor_rows(leaves, 4 * elements, "leaves")
     if m == 0:
         raise ValueError(f"{who}: no paths")
@@ -634,8 +630,6 @@ def merkle_sum_witness(spec: Optional[Spec], leaves, siblings, indices, assets_s
     ``out``: an advice tensor to fill instead of a new one (it may be uninitialised)."""
     import torch
 
-    from .arithmetic import _stream_ptr
-
     spec = default_spec(5) if spec is None else spec
     m, depth = _path_tensors("merkle_sum_witness", 2, leaves, siblings, indices, nodes, out)
     out = _witness_out("merkle_sum_witness", out, m, N_ADVICE, 1 << k, leaves.device)
@@ -643,7 +637,7 @@ def merkle_sum_witness(spec: Optional[Spec], leaves, siblings, indices, assets_s
     assets = np.ascontiguousarray(fr_words(int(assets_sum) % R))
     with torch.cuda.device(leaves.device):
         spec.call(_lib.load().hm_merkle_sum_witness_bn256_dev, depth, k, m, ctypes.c_void_p(leaves.data_ptr()),
-                  ctypes.c_void_p(siblings.data_ptr()), ctypes.cast(ctypes.c_void_p(indices.data_ptr()), ctypes.POINTER(ctypes.c_uint64)),
+                  ctypes.c_void_p(siblings.data_ptr()), _dev_ptr(indices),
                   _ptr(assets), ctypes.c_void_p(nodes.data_ptr()) if nodes is not None else None,
                   ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(inst.data_ptr()), ctypes.c_void_p(_stream_ptr(leaves)))
     return out, inst
@@ -672,15 +666,13 @@ def merkle_witness(spec: Optional[Spec], leaves, siblings, indices, k: int, node
     ``out``: an advice tensor to fill instead of a new one (it may be uninitialised)."""
     import torch
 
-    from .arithmetic import _stream_ptr
-
     spec = default_spec(3) if spec is None else spec
     m, depth = _path_tensors("merkle_witness", 1, leaves, siblings, indices, nodes, out)
     out = _witness_out("merkle_witness", out, m, MerkleTreeV3Layout.N_ADVICE, 1 << k, leaves.device)
     inst = torch.empty((m, 2, 4), dtype=torch.int64, device=leaves.device)
     with torch.cuda.device(leaves.device):
         spec.call(_lib.load().hm_merkle_witness_bn256_dev, depth, k, m, ctypes.c_void_p(leaves.data_ptr()),
-                  ctypes.c_void_p(siblings.data_ptr()), ctypes.cast(ctypes.c_void_p(indices.data_ptr()), ctypes.POINTER(ctypes.c_uint64)),
+                  ctypes.c_void_p(siblings.data_ptr()), _dev_ptr(indices),
                   ctypes.c_void_p(nodes.data_ptr()) if nodes is not None else None,
                   ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(inst.data_ptr()), ctypes.c_void_p(_stream_ptr(leaves)))
     return out, inst
@@ -705,8 +697,6 @@ def poseidon_circuit_witness(spec: Optional[Spec], msgs, k: int, out=None):
     """The Poseidon circuit's witnesses of m messages: ``msgs`` (m, 4, 4) GPU tensor of canonical Montgomery words
     -> (advice (m, 6, 2^k, 4), instance (m, 1, 4)); every word written; asynchronous on the current stream."""
     import torch
-
-    from .arithmetic import _stream_ptr, _tensor_rows
 
     spec = default_spec(5) if spec is None else spec
     m = _tensor_rows(msgs, 16, "msgs")
@@ -738,6 +728,4 @@ def poseidon_circuit_witness_host(spec: Optional[Spec], msgs: np.ndarray, k: int
     return adv, inst
 
 
-def columns_to_words(cols: Sequence[Sequence[int]]) -> np.ndarray:
-    """integer columns -> (len(cols), n, 4) uint64 Montgomery words (what the device tensors hold)"""
-    return np.stack([ints_to_words(c) for c in cols])
+columns_to_words = fr_array      # integer columns -> (len(cols), n, 4) uint64 Montgomery words (what the device tensors hold)

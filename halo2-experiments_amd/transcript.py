@@ -16,8 +16,7 @@ from __future__ import annotations
 
 import hashlib
 
-from .arithmetic import FQ_MODULUS
-from .domain import FR_MODULUS
+from .bn256 import FQ_MODULUS, FR_MODULUS
 
 PREFIX_CHALLENGE, PREFIX_POINT, PREFIX_SCALAR = b"\x00", b"\x01", b"\x02"
 PERSONAL = b"Halo2-Transcript"

@@ -199,12 +199,66 @@ def test_rust_bindings_agree_with_the_header_in_arity_and_types():
             assert m, f"{path}: struct {gen.STRUCTS[cname]} missing"
             rust_fields = re.findall(r"pub (\w+): (\[\w+; \d+\]|\w+),", m.group(1))
             assert rust_fields == [(f, f"[{b}; {c}]" if c else b) for f, b, c in fields], f"{path}: {cname} fields differ"
-    # ctypes: the Python binding's arity must agree too
-    for name, (ret, params) in want.items():
-        assert len(_lib._SIGNATURES[name][1]) == len(params), name
-    # hm_stats / hm_msm_stats against the ctypes structures used by the tests
-    assert [f for f, _, _ in c_structs["hm_msm_stats"]] == [f for f, _ in _lib.MsmStats._fields_]
-    assert [f for f, _, _ in c_structs["hm_stats"]] == [f for f, _ in _lib.Stats._fields_]
+
+
+def test_ctypes_binding_is_the_header_read_through_the_rust_file():
+    """halo2_experiments_amd._lib derives its ctypes table from the header with the package's C parser.  Here every entry is held to
+    the SAME mapping applied to what the Rust parser -- a second, independent one -- reads from the generated extern block, and
+    one entry per type class is pinned literally, so that neither the parser nor the mapping can drift unseen."""
+    gen = _gen()
+    root = os.path.join(os.path.dirname(os.path.abspath(_lib.HEADER_PATH)), "..")
+    r_funcs = gen.parse_rust_extern(open(os.path.join(root, "rust/halo2-mi355x-sys/src/lib.rs")).read())
+    assert {f[0] for f in r_funcs} == set(_lib._SIGNATURES) == set(declared_symbols())
+    for name, ret, params in r_funcs:
+        res, args = _lib._SIGNATURES[name]
+        assert res is _lib._ctype(ret), f"{name}: restype {res} but the extern block says {ret}"
+        assert len(args) == len(params), name
+        for i, (got, (canon, pname)) in enumerate(zip(args, params)):
+            assert got is _lib._ctype(canon), f"{name}: argument {i} ({pname}) is {got} but the extern block says {canon}"
+    c = ctypes
+    u64p, u32p, vp, vpp = c.POINTER(c.c_uint64), c.POINTER(c.c_uint32), c.c_void_p, c.POINTER(c.c_void_p)
+    pins = {
+        "hm_msm_bn256_g1": (c.c_int, [u64p, u64p, c.c_size_t, u64p, c.POINTER(c.c_int)]),                # scalars and pointers to them
+        "hm_last_error": (c.c_char_p, []),                                                                # const char* return
+        "hm_lookup_permute_batch_bn256_fr_dev": (c.c_int, [vpp, vpp, c.c_size_t, c.c_size_t, vpp, vpp, c.POINTER(c.c_int), vp]),   # tables of addresses
+        "hm_get_stats": (c.c_int, [c.POINTER(_lib.Stats)]),                                               # pointer to a struct
+        "hm_g1_compress_bn256": (c.c_int, [u64p, c.c_size_t, vp]),                                        # uint8_t*: a byte buffer
+        "hm_mock_gates_dev": (c.c_int, [c.c_uint64, vpp, u64p, u32p, c.c_size_t, u64p, c.c_size_t, c.c_uint32, c.c_uint32, c.c_size_t,
+                                        u64p, c.c_size_t, u64p, c.c_size_t, u64p, vp, u64p, vp]),
+    }
+    for name, (res, args) in pins.items():
+        assert _lib._SIGNATURES[name][0] is res and _lib._SIGNATURES[name][1] == args, name
+    with pytest.raises(ValueError, match="unknown C type"):
+        gen.parse_header("int hm_new_entry(const float* x);")
+    # the ctypes structures: field names, order, types and array lengths are the header's
+    _, c_structs, _ = gen.parse_header(open(_lib.HEADER_PATH).read())
+    scalars = {"u64": c.c_uint64, "u32": c.c_uint32, "f64": c.c_double}
+    for cname, cls in (("hm_msm_stats", _lib.MsmStats), ("hm_stats", _lib.Stats), ("hm_bases_info", _lib.BasesInfo)):
+        assert issubclass(cls, c.Structure)
+        assert [(f, t, 0) if not hasattr(t, "_length_") else (f, t._type_, t._length_) for f, t in cls._fields_] == \
+            [(f, scalars[b], n) for f, b, n in c_structs[cname]], cname
+    assert c.sizeof(_lib.Stats) == 8 * (4 + 64 + 6 + 2 + 16 + 4 + 3) and c.sizeof(_lib.MsmStats) == 8 * 8 + 8 and c.sizeof(_lib.BasesInfo) == 48
+    assert _lib.Stats.KINDS == ("eval_polynomial", "graph_evaluate", "kate_division", "grand_product", "batch_invert", "linear_combination",
+                                "lookup_permute")
+
+
+def test_every_define_of_the_header_is_a_constant_of_the_binding():
+    text = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
+    names = re.findall(r"#define\s+(HM_\w+)\s+\S", text)
+    assert len(names) >= 18 and "HM_NO_CHAIN" in names and "HM_ERR_INVALID_DATA" in names
+    gen = _gen()
+    parsed = dict(gen.parse_header(open(_lib.HEADER_PATH).read())[2])
+    assert list(parsed) == names                                             # the parser misses none, HM_NO_CHAIN's cast included
+    for name in names:
+        value = getattr(_lib, name)
+        assert isinstance(value, int), name
+        if name != "HM_NO_CHAIN":
+            assert value == int(parsed[name]), name
+    assert _lib.HM_NO_CHAIN == _lib.NO_CHAIN == ctypes.c_size_t(-1).value
+    assert (_lib.HM_OK, _lib.HM_ERR_BAD_ARG, _lib.HM_ERR_NO_DEVICE, _lib.HM_ERR_NOT_FOUND, _lib.HM_ERR_INVALID_DATA) == (0, -1, -2, -4, -7)
+    assert (_lib.HM_SHPLONK_MAX_POINTS, _lib.HM_GRAPH_COLUMNS_INTERNAL, _lib.HM_STAT_LOOKUP_PERMUTE) == (4, 1, 6)
+    from halo2_experiments_amd import arithmetic, rust_glue, shplonk
+    assert arithmetic.HM_ERR_INVALID_DATA == -7 and shplonk.MAX_POINTS == 4 and rust_glue.HM_OK == 0       # the public aliases
 
 
 def test_generated_rust_files_are_up_to_date():

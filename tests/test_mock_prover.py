@@ -178,7 +178,9 @@ def test_entry_points_are_declared_bound_and_check_their_arguments():
     base = a.ctypes.data + (-a.ctypes.data) % 16
     bases, strides, rows = (ctypes.c_void_p * 1)(base), (ctypes.c_uint64 * 1)(0), (ctypes.c_uint32 * 1)(16)
     vp = ctypes.c_void_p
-    good = dict(graph=ctypes.c_uint64(1), bases=bases, strides=strides, rows=rows, n=1, k=4, usable=10, m=1, rec=vp(base), cap=4, counter=vp(base + 64),
+    u64 = lambda addr: ctypes.cast(vp(addr), ctypes.POINTER(ctypes.c_uint64))       # the record and counter arguments are uint64_t*
+    u32 = lambda addr: ctypes.cast(vp(addr), ctypes.POINTER(ctypes.c_uint32))
+    good = dict(graph=ctypes.c_uint64(1), bases=bases, strides=strides, rows=rows, n=1, k=4, usable=10, m=1, rec=u64(base), cap=4, counter=u64(base + 64),
                 flags=vp(base + 128))
 
     def gates(**kw):
@@ -187,16 +189,16 @@ def test_entry_points_are_declared_bound_and_check_their_arguments():
                                      g["rec"], g["cap"], g["counter"], g["flags"], ctypes.byref(out), None)
 
     refused = [dict(m=0), dict(cap=0), dict(rows=(ctypes.c_uint32 * 1)(17)), dict(bases=(ctypes.c_void_p * 1)(base + 8)), dict(k=31),
-               dict(usable=0), dict(usable=17), dict(rec=vp(base + 4)), dict(counter=None), dict(n=0), dict(n=257),
+               dict(usable=0), dict(usable=17), dict(rec=u64(base + 4)), dict(counter=None), dict(n=0), dict(n=257),
                dict(strides=(ctypes.c_uint64 * 1)(2)), dict(bases=None)]
     for kw in refused:
         assert gates(**kw) == -1, kw
         assert b"hm_mock_gates_dev" in lib.hm_last_error()
     perm = (ctypes.c_uint32 * 1)(0)
-    assert lib.hm_mock_copies_dev(bases, strides, rows, 1, perm, 1, vp(base), 0, 4, 1, vp(base), 4, vp(base + 64), vp(base + 128), ctypes.byref(out), None) == -1
-    assert lib.hm_mock_copies_dev(bases, strides, rows, 1, (ctypes.c_uint32 * 1)(1), 1, vp(base), 3, 4, 1, vp(base), 4, vp(base + 64), vp(base + 128),
+    assert lib.hm_mock_copies_dev(bases, strides, rows, 1, perm, 1, u32(base), 0, 4, 1, u64(base), 4, u64(base + 64), vp(base + 128), ctypes.byref(out), None) == -1
+    assert lib.hm_mock_copies_dev(bases, strides, rows, 1, (ctypes.c_uint32 * 1)(1), 1, u32(base), 3, 4, 1, u64(base), 4, u64(base + 64), vp(base + 128),
                                   ctypes.byref(out), None) == -1
-    assert lib.hm_mock_lookup_dev(ctypes.c_uint64(1), bases, strides, rows, 1, None, 0, 4, 10, 1, 0, None, vp(base), 4, vp(base + 64), vp(base + 128),
+    assert lib.hm_mock_lookup_dev(ctypes.c_uint64(1), bases, strides, rows, 1, None, 0, 4, 10, 1, 0, None, u64(base), 4, u64(base + 64), vp(base + 128),
                                   ctypes.byref(out), None) == -1
     assert out.value == 77 and not a.any()
     if lib.hm_device_count() == 0:                                                       # valid-looking arguments: no device, no fallback

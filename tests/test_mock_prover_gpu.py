@@ -227,14 +227,15 @@ def test_the_record_buffer_ends_at_its_capacity(synthetic):
     dyn = np.ascontiguousarray(ps.ints_to_words([0, 0, 0, 12345]).reshape(4, 4))
     out = ctypes.c_uint64(0)
     vp = ctypes.c_void_p
+    u64 = lambda addr: ctypes.cast(vp(addr), ctypes.POINTER(ctypes.c_uint64))       # lanes, records and counter are uint64_t*
     lib = _lib.load()
     for cap, lanes in ((4, None), (4, torch.tensor([(64 << 32) | 9, (3 << 32) | 0, (65 << 32) | 0, (1 << 32) | 10], dtype=torch.int64, device="cuda"))):
         rec.fill_(FILL)
         counter.zero_()
         flags.zero_()
         _lib.check(lib.hm_mock_gates_dev(ctypes.c_uint64(dev.combined.handle), bases, strides, rows, count, dyn.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
-                                         4, 4, 10, m, vp(lanes.data_ptr()) if lanes is not None else None, 0 if lanes is None else lanes.numel(),
-                                         vp(rec.data_ptr()), cap, vp(counter.data_ptr()), vp(flags.data_ptr()), ctypes.byref(out), None))
+                                         4, 4, 10, m, u64(lanes.data_ptr()) if lanes is not None else None, 0 if lanes is None else lanes.numel(),
+                                         u64(rec.data_ptr()), cap, u64(counter.data_ptr()), vp(flags.data_ptr()), ctypes.byref(out), None))
         assert bool((rec[4:] == FILL).all()) and not bool(flags[m:].any())
         if lanes is None:
             assert out.value == counter.item() == m * 10 and bool(flags[:m].all())
@@ -255,17 +256,19 @@ def test_rejected_arguments_leave_everything_untouched(synthetic):
     flags = torch.full((m,), 7, dtype=torch.uint8, device="cuda")
     dyn = np.ascontiguousarray(ps.ints_to_words([0, 0, 0, 12345]).reshape(4, 4))
     dynp, vp, lib = dyn.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.c_void_p, _lib.load()
+    u64 = lambda addr: ctypes.cast(vp(addr), ctypes.POINTER(ctypes.c_uint64))       # records and counter are uint64_t*
     pairs = dev.pairs
     perm = mp._perm.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
     table = dev.lookups[0].shared
 
     def call(which, bases=bases, rows=rows, m=m, cap=8, rec_ptr=rec.data_ptr()):
         out = ctypes.c_uint64(99)
-        tail = (vp(rec_ptr), cap, vp(counter.data_ptr()), vp(flags.data_ptr()), ctypes.byref(out), None)
+        tail = (u64(rec_ptr), cap, u64(counter.data_ptr()), vp(flags.data_ptr()), ctypes.byref(out), None)
         if which == "gates":
             rc = lib.hm_mock_gates_dev(ctypes.c_uint64(dev.combined.handle), bases, strides, rows, count, dynp, 4, 4, 10, m, None, 0, *tail)
         elif which == "copies":
-            rc = lib.hm_mock_copies_dev(bases, strides, rows, count, perm, len(mp._perm), vp(pairs.data_ptr()), len(mp._pairs), 4, m, *tail)
+            rc = lib.hm_mock_copies_dev(bases, strides, rows, count, perm, len(mp._perm), ctypes.cast(vp(pairs.data_ptr()), ctypes.POINTER(ctypes.c_uint32)),
+                                        len(mp._pairs), 4, m, *tail)
         else:
             rc = lib.hm_mock_lookup_dev(ctypes.c_uint64(dev.lookups[0].input.handle), bases, strides, rows, count, dynp, 4, 4, 10, m, 0,
                                         vp(table.data_ptr()), *tail)
@@ -277,8 +280,8 @@ def test_rejected_arguments_leave_everything_untouched(synthetic):
         for kw in (dict(bases=misaligned), dict(m=0), dict(cap=0), dict(rows=long_instance), dict(rec_ptr=rec.data_ptr() + 4)):
             assert call(which, **kw) == (-1, 99), (which, kw)
             assert which.encode() in lib.hm_last_error()
-    assert lib.hm_mock_gates_dev(ctypes.c_uint64(1 << 40), bases, strides, rows, count, dynp, 4, 4, 10, m, None, 0, vp(rec.data_ptr()), 8,
-                                 vp(counter.data_ptr()), vp(flags.data_ptr()), ctypes.byref(ctypes.c_uint64(0)), None) == -4      # unknown handle
+    assert lib.hm_mock_gates_dev(ctypes.c_uint64(1 << 40), bases, strides, rows, count, dynp, 4, 4, 10, m, None, 0, u64(rec.data_ptr()), 8,
+                                 u64(counter.data_ptr()), vp(flags.data_ptr()), ctypes.byref(ctypes.c_uint64(0)), None) == -4      # unknown handle
     torch.cuda.synchronize()
     assert bool((rec == FILL).all()) and counter.item() == 41 and bool((flags == 7).all())
     assert call("gates")[0] == 0 and counter.item() == 41 + 30               # and the same arguments, not refused, do write
