@@ -21,6 +21,8 @@
 #pragma once
 #include <stdint.h>
 
+#include <utility>
+
 #if defined(__HIPCC__)
 #define HM_HD __host__ __device__ __forceinline__
 #else
@@ -282,6 +284,213 @@ HM_HD Fe<F> fe_sqr(const Fe<F>& a) {
   }
 #endif
   return r;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Montgomery products in lockstep, radix 2^261.  Product scanning: column k of the 17 is
+//   carry_in + sum_i a_i * b_(k-i) + sum_(i<k) m_i * MOD_(k-i)          (+ m_k * MOD_0 for k < 9)
+// in ONE 64-bit accumulator; m_k = -column * MOD^-1 mod 2^29 clears the low 29 bits of columns 0..8, columns
+// 9..16 give the output limbs, and `>> 29` is the carry that STARTS the next column's chain: it rides the
+// 64-bit addend of the first v_mad_u64_u32 and costs no instruction, where the operand scanning above pays a
+// v_lshl_add_u64 per round and per output limb (16 per product).  The compiler would move the carry back to
+// the end of the sum, so on the device every accumulation and shift is pinned with an empty asm.  Each pin
+// costs an s_nop where the next instruction reads the pinned register (the compiler's wait state after inline
+// asm); with several independent products advanced together the scheduler has another chain's mad to put
+// there.  Measured (tools/ubench/mont_forms.hip, profiles/r07_a_mont_forms.txt): two products in lockstep
+// +3.9 % products/s over operand scanning at 4 waves per SIMD; ONE pinned chain is not told apart from
+// operand scanning (+0.9 %, inside its own spread), and ntt_pass_kernel<11> spills to scratch with it -- so
+// the single products above keep their form and only the hot mixed addition of the bucket accumulation kernel
+// (g1.h: g1x_madd_fast<true>) comes here.
+// Same integers as operand scanning, column by column, hence the same limbs bit for bit
+// (tests/test_mont_forms_host.py).  Output: normalised limbs, value < (sum of the products)/2^261 + MOD.
+//
+// Column bound (HM_BOUNDS precondition): carry_in = (a column) >> 29 < 2^35; at most 9 (a*b + c*d: 18) products
+// a_i * b_j <= A*B; at most 9 products m_i * MOD_j < 2^58.  The precondition of the single products keeps an
+// allowance of 2^40 for carries, which covers 2^35: 9*A*B + 9*2^58 + 2^40 < 2^64.  The accumulator only grows
+// within a column, so the column's total is its maximum.
+// ---------------------------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(HM_BOUNDS)
+#define HM_PIN(x) asm("" : "+v"(x))
+#else
+#define HM_PIN(x) ((void)0)
+#endif
+
+// the a*b terms of a column, by kind of product
+template <class F>
+struct MontMul {  // a * b
+  const Fe<F>&a, &b;
+  HM_HD static constexpr int terms(int k) { return (k < 8 ? k : 8) - (k > 8 ? k - 8 : 0) + 1; }
+  HM_HD uint64_t term(int k, int s) const {
+    const int i = (k > 8 ? k - 8 : 0) + s;
+    return (uint64_t)a.l[i] * b.l[k - i];
+  }
+};
+template <class F>
+struct MontMul2 {  // a * b + c * d
+  const Fe<F>&a, &b, &c, &d;
+  HM_HD static constexpr int terms(int k) { return 2 * MontMul<F>::terms(k); }
+  HM_HD uint64_t term(int k, int s) const {
+    const int n = MontMul<F>::terms(k), i = (k > 8 ? k - 8 : 0) + (s < n ? s : s - n);
+    return s < n ? (uint64_t)a.l[i] * b.l[k - i] : (uint64_t)c.l[i] * d.l[k - i];
+  }
+};
+template <class F>
+struct MontSqr {  // a * a as a_i * (2 a_j) for i < j plus the squares: 45 products; d = the doubled limbs
+  const Fe<F>& a;
+  const uint32_t (&d)[9];
+  HM_HD static constexpr int pairs(int k) { return (k + 1) / 2 - (k > 8 ? k - 8 : 0); }
+  HM_HD static constexpr int terms(int k) { return pairs(k) + (k % 2 == 0 ? 1 : 0); }
+  HM_HD uint64_t term(int k, int s) const {
+    const int i = (k > 8 ? k - 8 : 0) + s;
+    return s < pairs(k) ? (uint64_t)a.l[i] * d[k - i] : (uint64_t)a.l[k / 2] * a.l[k / 2];
+  }
+};
+
+template <class F, class P>
+struct MontLane {  // one product under way
+  P p;
+  uint64_t acc;
+  uint32_t m[9];
+  Fe<F> r;
+};
+template <class F, class P>
+HM_HD void mont_step_ab(MontLane<F, P>& L, int k, int s) {
+  if (s < P::terms(k)) {
+    L.acc += L.p.term(k, s);
+    HM_PIN(L.acc);
+  }
+}
+template <class F, class P>
+HM_HD void mont_step_mp(MontLane<F, P>& L, int k, int i) {
+  L.acc += (uint64_t)L.m[i] * F::MOD[k - i];
+  HM_PIN(L.acc);
+}
+template <class F, class P>
+HM_HD void mont_step_end(MontLane<F, P>& L, int k) {
+  if (k < 9) {
+    L.m[k] = ((uint32_t)L.acc * F::INV29) & MASK29;
+    L.acc += (uint64_t)L.m[k] * F::MOD[0];
+    HM_PIN(L.acc);
+  } else {
+    L.r.l[k - 9] = (uint32_t)L.acc & MASK29;
+  }
+  L.acc >>= 29;
+  HM_PIN(L.acc);
+}
+// one column of all the lanes' products, their accumulations interleaved (K a template parameter: every bound
+// below is a constant, so the loops unroll whatever the lanes hold)
+template <int K, class F, class... P>
+HM_HD void mont_column(MontLane<F, P>&... L) {
+#pragma unroll
+  for (int s = 0; s < 18; ++s) (mont_step_ab(L, K, s), ...);
+#pragma unroll
+  for (int i = (K > 8 ? K - 8 : 0); i <= (K < 8 ? K - 1 : 8); ++i) (mont_step_mp(L, K, i), ...);
+  (mont_step_end(L, K), ...);
+}
+template <class F, int... Ks, class... P>
+HM_HD void mont_columns(std::integer_sequence<int, Ks...>, MontLane<F, P>&... L) {
+  (mont_column<Ks, F>(L...), ...);
+}
+template <class F, class... P>
+HM_HD void mont_run(MontLane<F, P>&... L) {
+  ((L.acc = 0), ...);
+  mont_columns<F>(std::make_integer_sequence<int, 17>{}, L...);
+  ((L.r.l[8] = (uint32_t)L.acc), ...);
+}
+
+#ifdef HM_BOUNDS
+template <class F>
+inline long double fe_limb_max(const Fe<F>& a) { return (long double)(a.lb > a.tb ? a.lb : a.tb); }
+// sum_ab = the largest sum of one product a_i * b_j per row: A*B (fe_mul, fe_sqr), A*B + C*D (fe_mul2)
+inline void mont_check_column(long double sum_ab, const char* what) {
+  HM_CHECK(9.0L * sum_ab + 9.0L * 288230376151711744.0L + 1099511627776.0L < 18446744073709551616.0L, what);
+}
+template <class F>
+inline void mont_set_result(Fe<F>& r, double vb_products, const char* what) {
+  const double vb = vb_products * mod_as_double<F>() / std::ldexp(1.0, 261) + 1.0;
+  set_bounds(r, vb, MASK29, top_bound_from_value<F>(vb));
+  HM_CHECK(r.l[8] <= r.tb, what);
+}
+#define HM_MUL_PRE(a, b) mont_check_column(fe_limb_max(a) * fe_limb_max(b), "fe_mul column sum may overflow 64 bits")
+#define HM_MUL_POST(r, a, b) mont_set_result(r, (a).vb * (b).vb, "fe_mul result exceeds its bound")
+#define HM_MUL2_PRE(a, b, c, d) \
+  mont_check_column(fe_limb_max(a) * fe_limb_max(b) + fe_limb_max(c) * fe_limb_max(d), "fe_mul2 column sum may overflow 64 bits")
+#define HM_MUL2_POST(r, a, b, c, d) mont_set_result(r, (a).vb * (b).vb + (c).vb * (d).vb, "fe_mul2 result exceeds its bound")
+#define HM_SQR_PRE(a)                                                                   \
+  do {                                                                                  \
+    HM_CHECK(2.0L * fe_limb_max(a) < 4294967296.0L, "fe_sqr doubled limb overflows");   \
+    mont_check_column(fe_limb_max(a) * fe_limb_max(a), "fe_sqr column sum may overflow 64 bits"); \
+  } while (0)
+#define HM_SQR_POST(r, a) mont_set_result(r, (a).vb * (a).vb, "fe_sqr result exceeds its bound")
+#else
+#define HM_MUL_PRE(a, b) ((void)0)
+#define HM_MUL_POST(r, a, b) ((void)0)
+#define HM_MUL2_PRE(a, b, c, d) ((void)0)
+#define HM_MUL2_POST(r, a, b, c, d) ((void)0)
+#define HM_SQR_PRE(a) ((void)0)
+#define HM_SQR_POST(r, a) ((void)0)
+#endif
+
+// the doubled limbs of a square
+template <class F>
+HM_HD void fe_doubled_limbs(uint32_t (&d)[9], const Fe<F>& a) {
+#pragma unroll
+  for (int j = 0; j < 9; ++j) d[j] = a.l[j] << 1;
+}
+// Independent products advanced in lockstep: the same results as the single calls, limb for limb.
+template <class F>
+HM_HD void fe_mul_x2(Fe<F>& r0, Fe<F>& r1, const Fe<F>& a0, const Fe<F>& b0, const Fe<F>& a1, const Fe<F>& b1) {
+  HM_MUL_PRE(a0, b0);
+  HM_MUL_PRE(a1, b1);
+  MontLane<F, MontMul<F>> L0{{a0, b0}}, L1{{a1, b1}};
+  mont_run<F>(L0, L1);
+  HM_MUL_POST(L0.r, a0, b0);
+  HM_MUL_POST(L1.r, a1, b1);
+  r0 = L0.r;
+  r1 = L1.r;
+}
+template <class F>
+HM_HD void fe_mul_x3(Fe<F>& r0, Fe<F>& r1, Fe<F>& r2, const Fe<F>& a0, const Fe<F>& b0, const Fe<F>& a1, const Fe<F>& b1,
+                     const Fe<F>& a2, const Fe<F>& b2) {
+  HM_MUL_PRE(a0, b0);
+  HM_MUL_PRE(a1, b1);
+  HM_MUL_PRE(a2, b2);
+  MontLane<F, MontMul<F>> L0{{a0, b0}}, L1{{a1, b1}}, L2{{a2, b2}};
+  mont_run<F>(L0, L1, L2);
+  HM_MUL_POST(L0.r, a0, b0);
+  HM_MUL_POST(L1.r, a1, b1);
+  HM_MUL_POST(L2.r, a2, b2);
+  r0 = L0.r;
+  r1 = L1.r;
+  r2 = L2.r;
+}
+template <class F>
+HM_HD void fe_sqr_x2(Fe<F>& r0, Fe<F>& r1, const Fe<F>& a0, const Fe<F>& a1) {
+  HM_SQR_PRE(a0);
+  HM_SQR_PRE(a1);
+  uint32_t d0[9], d1[9];
+  fe_doubled_limbs(d0, a0);
+  fe_doubled_limbs(d1, a1);
+  MontLane<F, MontSqr<F>> L0{{a0, d0}}, L1{{a1, d1}};
+  mont_run<F>(L0, L1);
+  HM_SQR_POST(L0.r, a0);
+  HM_SQR_POST(L1.r, a1);
+  r0 = L0.r;
+  r1 = L1.r;
+}
+// r0 = a0 * b0 beside r1 = a * b + c * d
+template <class F>
+HM_HD void fe_mul_mul2(Fe<F>& r0, Fe<F>& r1, const Fe<F>& a0, const Fe<F>& b0, const Fe<F>& a, const Fe<F>& b, const Fe<F>& c,
+                       const Fe<F>& d) {
+  HM_MUL_PRE(a0, b0);
+  HM_MUL2_PRE(a, b, c, d);
+  MontLane<F, MontMul<F>> L0{{a0, b0}};
+  MontLane<F, MontMul2<F>> L1{{a, b, c, d}};
+  mont_run<F>(L0, L1);
+  HM_MUL_POST(L0.r, a0, b0);
+  HM_MUL2_POST(L1.r, a, b, c, d);
+  r0 = L0.r;
+  r1 = L1.r;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -255,13 +255,28 @@ HM_HD G1Xyzz g1x_from_jac(const G1Jac& p) {
 // untouched in the exceptional case X1 = U2 (a repeated base in one bucket, or a base and its
 // negative): the caller finishes such a chain with the general Jacobian law.  Keeping that case OUT
 // of this function keeps the hot loop free of its code and of the register merge of its result.
+//
+// LOCKSTEP: the eleven products as four groups of independent products advanced together (ff29.h: fe_mul_x2 ...):
+// (U2, S2), (PP, R^2), (PPP, Q, ZZ3), (ZZZ3, Y3).  Same values, limb for limb; S2 and R^2 are then computed before
+// the exit instead of after it.  For the bucket accumulation kernel of the general pipeline, where four waves per
+// SIMD keep the VALU saturated: 3.7 % faster there (profiles/r07_a_step_ab.txt).  Chains of a few lanes
+// (msm_small at 2^12 .. 2^14) run 7 - 9 % slower with it (profiles/r07_a_small_ab.txt), so every other caller
+// keeps the single products.
+template <bool LOCKSTEP = false>
 HM_HD bool g1x_madd_fast(G1Xyzz& acc, const G1Aff& q, bool neg) {
   HM_G1_CHECK(acc, "g1x_madd_fast input outside class");
-  const Fq u2 = fe_mul(q.x, acc.zz);
+  Fq u2, s2p, pp, rr, ppp, qq, zz3, zzz3, y3;
+  if constexpr (LOCKSTEP) {
+    fe_mul_x2(u2, s2p, q.x, acc.zz, q.y, acc.zzz);
+  } else {
+    u2 = fe_mul(q.x, acc.zz);
+  }
   const Fq pp0 = fe_norm(fe_sub<9, 29>(u2, acc.x));          // P = U2 - X1
-  const Fq pp = fe_sqr(pp0);                                  // PP
-  if (fe_is_zero_mod(pp)) return false;
-  const Fq s2p = fe_mul(q.y, acc.zzz);
+  if constexpr (!LOCKSTEP) {
+    pp = fe_sqr(pp0);                                         // PP
+    if (fe_is_zero_mod(pp)) return false;
+    s2p = fe_mul(q.y, acc.zzz);
+  }
   Fq s2;                                                      // +-S2, limbs <= 2^30
   {
     const Fq s2n = fe_sub<3, 29>(fe_zero<FqParams>(), s2p);
@@ -272,17 +287,30 @@ HM_HD bool g1x_madd_fast(G1Xyzz& acc, const G1Aff& q, bool neg) {
 #endif
   }
   const Fq r = fe_norm(fe_sub<4, 29>(s2, acc.y));             // R = +-S2 - Y1
-  const Fq ppp = fe_mul(pp0, pp);
-  const Fq qq = fe_mul(acc.x, pp);                            // Q = X1 * PP
-  const Fq rr = fe_sqr(r);
+  if constexpr (LOCKSTEP) {
+    fe_sqr_x2(pp, rr, pp0, r);                                // PP, R^2
+    if (fe_is_zero_mod(pp)) return false;
+    fe_mul_x3(ppp, qq, zz3, pp0, pp, acc.x, pp, acc.zz, pp);  // PPP, Q = X1 * PP, ZZ3 = ZZ1 * PP
+  } else {
+    ppp = fe_mul(pp0, pp);
+    qq = fe_mul(acc.x, pp);                                   // Q = X1 * PP
+    rr = fe_sqr(r);
+  }
   const Fq t2 = fe_add(ppp, fe_dbl(qq));                      // PPP + 2Q  (limbs < 3*2^29)
   const Fq x3 = fe_norm(fe_sub<6, 31>(rr, t2));               // R^2 - PPP - 2Q
   const Fq vx = fe_sub<9, 29>(qq, x3);                        // Q - X3, left lazy (limbs < 2^30.6): only a multiplicand of the fused product
   const Fq ny = fe_sub<4, 29>(fe_zero<FqParams>(), acc.y);    // -Y1 (limbs < 2^30)
-  acc.y = fe_mul2(r, vx, ny, ppp);                            // R (Q - X3) - Y1 PPP
+  if constexpr (LOCKSTEP) {
+    fe_mul_mul2(zzz3, y3, acc.zzz, ppp, r, vx, ny, ppp);      // ZZZ1 * PPP, R (Q - X3) - Y1 PPP
+  } else {
+    y3 = fe_mul2(r, vx, ny, ppp);                             // R (Q - X3) - Y1 PPP
+    zz3 = fe_mul(acc.zz, pp);
+    zzz3 = fe_mul(acc.zzz, ppp);
+  }
   acc.x = x3;
-  acc.zz = fe_mul(acc.zz, pp);
-  acc.zzz = fe_mul(acc.zzz, ppp);
+  acc.y = y3;
+  acc.zz = zz3;
+  acc.zzz = zzz3;
   return true;
 }
 

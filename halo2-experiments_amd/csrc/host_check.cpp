@@ -192,6 +192,15 @@ int hc_xyzz_bounds_closure(const uint64_t* pj, const uint64_t* q_aff, double* re
   force_bounds(q.y, 2.0);
   G1Xyzz r = p;
   if (!g1x_madd_fast(r, q, true)) return 0;
+  {
+    // the lockstep form of the hot kernel: every product's precondition is checked again inside it; the same limbs and
+    // bounds within the class must come out
+    G1Xyzz rl = p;
+    if (!g1x_madd_fast<true>(rl, q, true)) return 0;
+    for (int i = 0; i < 9; ++i)
+      if (rl.x.l[i] != r.x.l[i] || rl.y.l[i] != r.y.l[i] || rl.zz.l[i] != r.zz.l[i] || rl.zzz.l[i] != r.zzz.l[i]) return 0;
+    if (rl.x.vb > HM_XYZZ_XB || rl.y.vb > HM_XYZZ_YB || rl.zz.vb > 2.0 || rl.zzz.vb > 2.0) return 0;
+  }
   const G1Jac j = g1x_to_jac(p);
   report[0] = r.x.vb; report[1] = r.y.vb; report[2] = r.zz.vb; report[3] = r.zzz.vb;
   report[4] = j.x.vb; report[5] = j.y.vb; report[6] = j.z.vb;

@@ -1249,11 +1249,13 @@ __global__ __launch_bounds__(ORDER_THREADS) void msm_task_order_kernel(const uin
 // ---------------------------------------------------------------------------------------------
 // K3: bucket accumulation -- one lane per task, serial chain of mixed additions
 // ---------------------------------------------------------------------------------------------
-#ifdef HM_K3_WAVES            // A/B only (tools/ab_build.sh): force an occupancy, i.e. a register budget, on the hot kernel
-#define HM_K3_OCC __attribute__((amdgpu_waves_per_eu(HM_K3_WAVES, HM_K3_WAVES)))
-#else
-#define HM_K3_OCC
+// Four waves per SIMD, stated: the lockstep products of g1x_madd_fast leave the register allocator free to take 129
+// VGPRs (three waves) without it; told the budget it uses 121, no scratch.  HM_K3_WAVES: another budget for A/B
+// (tools/ab_build.sh).
+#ifndef HM_K3_WAVES
+#define HM_K3_WAVES 4
 #endif
+#define HM_K3_OCC __attribute__((amdgpu_waves_per_eu(HM_K3_WAVES, HM_K3_WAVES)))
 __global__ __launch_bounds__(ACC_THREADS) HM_K3_OCC void msm_accumulate_kernel(const uint32_t* __restrict__ sorted,
                                                                      const uint32_t* __restrict__ task_bucket,
                                                                      const uint32_t* __restrict__ task_order,
@@ -1279,7 +1281,7 @@ __global__ __launch_bounds__(ACC_THREADS) HM_K3_OCC void msm_accumulate_kernel(c
     end = start + L < bucket_end ? start + L : bucket_end;
   }
   if (start >= end) return;       // no task for this lane (the kernel has no barriers)
-  const G1Jac res = accumulate_chain(sorted, xy, start, end, stage, lane);
+  const G1Jac res = accumulate_chain<true>(sorted, xy, start, end, stage, lane);   // lockstep products: g1.h
   store_jac(partial + (size_t)t * PT_WORDS, res);
 }
 

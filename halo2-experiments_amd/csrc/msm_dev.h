@@ -72,7 +72,8 @@ __device__ __forceinline__ void stage_base_async(const uint32_t* xy, uint32_t id
 // (end > start), the accumulator living in registers; the NEXT base is gathered by LDS-DMA while the
 // current addition runs.  The first point is peeled, so the loop body is one straight line with a
 // single exit: a lane that meets an equal-x pair (a repeated base, or a base and its negative) leaves
-// the loop and finishes its chain with the general Jacobian law.
+// the loop and finishes its chain with the general Jacobian law.  LOCKSTEP: g1.h, g1x_madd_fast.
+template <bool LOCKSTEP = false>
 __device__ __forceinline__ G1Jac accumulate_chain(const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ xy,
                                                   uint32_t start, uint32_t end, uint4 (*stage)[ACC_THREADS], uint32_t lane) {
   // First point of the chain: a plain load; the accumulator is never the identity inside the hot loop.
@@ -104,7 +105,7 @@ __device__ __forceinline__ G1Jac accumulate_chain(const uint32_t* __restrict__ s
     G1Aff q;
     q.x = fe_unpack<FqParams>(wx);
     q.y = fe_unpack<FqParams>(wy);
-    if (!g1x_madd_fast(acc, q, neg)) {                        // equal x: a repeated base or a base and its negative
+    if (!g1x_madd_fast<LOCKSTEP>(acc, q, neg)) {                        // equal x: a repeated base or a base and its negative
       general = true;
       break;
     }

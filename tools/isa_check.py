@@ -11,6 +11,8 @@
 
     python tools/isa_check.py                  # summary of every object
     python tools/isa_check.py ntt.o --dump     # the offending instructions with context
+    python tools/isa_check.py --k3 [msm.o ...] # the bucket accumulation kernel: VGPRs, scratch, and the instruction mix of its loops
+                                               # (wide mads, 64-bit adds, 64-bit shifts, compiler nops); the first is the hot one
 """
 import os
 import re
@@ -101,7 +103,67 @@ def summary(obj: str):
     return rows
 
 
+def _code_object(obj_path: str, tmp: str) -> str:
+    fat, co = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "dev.co")
+    subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj_path, os.path.join(tmp, "copy.o")], check=True, capture_output=True)
+    subprocess.run([f"{LLVM}/clang-offload-bundler", "--type=o", f"--input={fat}", f"--targets={TARGET}", "--unbundle", f"--output={co}"],
+                   check=True, capture_output=True)
+    return co
+
+
+def k3_report(obj_path: str, kernel: str = "msm_accumulate_kernel"):
+    """VGPRs / scratch of the kernel from the code object's metadata, and the instruction mix of every loop that holds curve
+    arithmetic (a loop = the address range of a backward branch, whose target is computed from the branch's own address and its
+    16-bit offset; nested loops are listed each).  In K3 the first such loop is accumulate_chain's chain of mixed additions
+    (g1x_madd_fast: the hot loop), the later ones finish a chain by the general law after an exceptional case."""
+    with tempfile.TemporaryDirectory(prefix="hm_isa_") as tmp:
+        co = _code_object(obj_path, tmp)
+        notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
+        dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co], check=True, capture_output=True, text=True).stdout
+    meta = {}
+    for entry in notes.split("- .agpr_count:")[1:]:
+        if re.search(r"\.name:\s+\S*" + re.escape(kernel), entry):
+            for key in ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count"):
+                m = re.search(r"\." + key + r":\s+(\d+)", entry)
+                meta[key] = int(m.group(1)) if m else None
+    insts, inside = [], False                              # (address, mnemonic, operands)
+    for line in dis.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
+        if m:
+            inside = kernel in m.group(1) and not m.group(1).endswith(".kd")
+            continue
+        m = re.match(r"^\s+(\S+)\s*(.*?)\s*//\s*([0-9A-Fa-f]+):", line)
+        if inside and m:
+            insts.append((int(m.group(3), 16), m.group(1), m.group(2)))
+    loops = []                                             # (first address, last address) of every backward branch
+    for addr, op, args in insts:
+        if op.startswith("s_cbranch") or op == "s_branch":
+            off = int(args.split()[-1])
+            target = addr + 4 + 4 * (off - 65536 if off >= 32768 else off)
+            if target <= addr:
+                loops.append((target, addr))
+    rows = []
+    for lo, hi in sorted(loops):
+        body = [op for addr, op, _ in insts if lo <= addr <= hi]
+        count = lambda name: sum(1 for x in body if x == name)
+        if count("v_mad_u64_u32") >= 100:                  # the loops that hold curve arithmetic
+            rows.append(dict(loop=f"{lo:#x}..{hi:#x}", instructions=len(body), valu=sum(1 for x in body if x.startswith("v_")),
+                             v_mad_u64_u32=count("v_mad_u64_u32"), v_lshl_add_u64=count("v_lshl_add_u64"),
+                             v_lshrrev_b64=count("v_lshrrev_b64"), s_nop=count("s_nop")))
+    return dict(meta, instructions=len(insts)), rows
+
+
 def main():
+    if "--k3" in sys.argv:
+        objs = [a for a in sys.argv[1:] if not a.startswith("--")] or [os.path.join(CSRC, "msm.o")]
+        bad = 0
+        for obj in objs:
+            r, loops = k3_report(obj if os.path.exists(obj) else os.path.join(CSRC, obj))
+            print(obj, " ".join(f"{k}={v}" for k, v in r.items()))
+            for row in loops:
+                print("   ", " ".join(f"{k}={v}" for k, v in row.items()))
+            bad += r["vgpr_count"] > 128 or r["private_segment_fixed_size"] != 0      # four waves per SIMD, no scratch
+        sys.exit(1 if bad else 0)
     objs = [a for a in sys.argv[1:] if not a.startswith("--")] or OBJECTS
     dump = "--dump" in sys.argv
     bad = 0
