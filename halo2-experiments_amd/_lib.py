@@ -14,6 +14,7 @@ CSRC = os.path.join(_HERE, "csrc")
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 LIB_PATH = os.environ.get("HALO2_MI355X_LIB") or os.path.join(CSRC, "libhalo2_mi355x.so")   # override: A/B builds
 HOSTCHECK_PATH = os.path.join(CSRC, "libhm_hostcheck.so")
+DEVCHECK_PATH = os.path.join(CSRC, "libhm_devcheck.so")      # test-only: csrc/unit_ops.h on the device (tests/test_unit_ops_gpu.py)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "halo2_mi355x.h")
 
 

@@ -666,7 +666,8 @@ HM_HD Fe<F> fe_unpack(const uint32_t (&w)[8]) {
   r.l[7] = ((w[6] >> 11) | (w[7] << 21)) & MASK29;
   r.l[8] = w[7] >> 8;
 #ifdef HM_BOUNDS
-  set_bounds(r, std::ldexp(1.0, 256) / mod_as_double<F>(), MASK29, (1u << 24) - 1);
+  // 2^256 / MOD rounded UP (the quotient of two rounded doubles may fall below the ratio, and 2^256 - 1 must lie under the bound)
+  set_bounds(r, std::ldexp(1.0, 256) / mod_as_double<F>() * (1.0 + std::ldexp(1.0, -50)), MASK29, (1u << 24) - 1);
 #endif
   return r;
 }
