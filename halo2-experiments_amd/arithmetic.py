@@ -365,10 +365,12 @@ def permute_expression_pair(input_column, table_column, usable_rows: int, blindi
     return out_a, out_s
 
 
-def permute_expression_pairs(input_columns, table_columns, usable_rows: int, blinding_seed: int = 0):
+def permute_expression_pairs(input_columns, table_columns, usable_rows: int, blinding_seed: int = 0, blinding_seeds=None):
     """``permute_expression_pair`` for all lookup arguments of a circuit in one call (their sorts run side by side on the
     device).  Returns a list of (permuted_input, permuted_table) tensors.  A lookup whose input holds a value its table
-    lacks raises ``Halo2Mi355xError`` (NOT_FOUND) carrying the indices in ``.missing``."""
+    lacks raises ``Halo2Mi355xError`` (NOT_FOUND) carrying the indices in ``.missing``.  Pair i draws its blinding rows from
+    ``blinding_seed + 2 i`` and ``+ 2 i + 1``; ``blinding_seeds`` (one per pair) names the first of the two instead -- the
+    lookups of several circuits in one call, each circuit with its own seed."""
     import torch
 
     lib = _lib.load()
@@ -383,6 +385,9 @@ def permute_expression_pairs(input_columns, table_columns, usable_rows: int, bli
             raise ValueError("permute_expression_pairs: columns must be GPU tensors of one length")
     if not 0 <= usable_rows <= n:
         raise ValueError("permute_expression_pairs: usable_rows out of range")
+    seeds = [blinding_seed + 2 * i for i in range(len(ins))] if blinding_seeds is None else [int(v) for v in blinding_seeds]
+    if len(seeds) != len(ins):
+        raise ValueError("permute_expression_pairs: one blinding seed per pair")
     outs = [(torch.empty((n, 4), dtype=torch.int64, device=ins[0].device), torch.empty((n, 4), dtype=torch.int64, device=ins[0].device))
             for _ in ins]
     arr = _ptr_array
@@ -397,9 +402,9 @@ def permute_expression_pairs(input_columns, table_columns, usable_rows: int, bli
     tail = n - usable_rows
     if tail:
         for i, (oa, os_) in enumerate(outs):
-            _lib.check(lib.hm_fr_random_dev(ctypes.c_void_p(oa.data_ptr() + usable_rows * 32), tail, ctypes.c_uint64(blinding_seed + 2 * i), st))
+            _lib.check(lib.hm_fr_random_dev(ctypes.c_void_p(oa.data_ptr() + usable_rows * 32), tail, ctypes.c_uint64(seeds[i] & 0xFFFFFFFFFFFFFFFF), st))
             _lib.check(lib.hm_fr_random_dev(ctypes.c_void_p(os_.data_ptr() + usable_rows * 32), tail,
-                                            ctypes.c_uint64((blinding_seed + 2 * i + 1) ^ 0x9E3779B97F4A7C15), st))
+                                            ctypes.c_uint64(((seeds[i] + 1) ^ 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF), st))
     return outs
 
 

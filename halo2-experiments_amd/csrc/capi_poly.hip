@@ -479,6 +479,23 @@ int hm_graph_evaluate_segments_dev(uint64_t handle, const void* const* d_columns
                               segments, d_values, flags, stream);
 } HM_API_CATCH("hm_graph_evaluate_segments_dev")
 
+int hm_graph_evaluate_circuits_dev(uint64_t handle, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
+                                   size_t circuits, const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t log_size, uint32_t segments,
+                                   void* d_values, uint32_t flags, void* stream) try {
+  if (!d_values || (n_columns && (!column_bases || !column_strides)) || (n_dynamic && !dynamic_constants))
+    return hm_fail(HM_ERR_BAD_ARG, "hm_graph_evaluate_circuits_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  for (auto& g : ctx->graphs)
+    if (g->handle == handle) {
+      count_vector(*ctx, HM_STAT_GRAPH_EVALUATE, 1, log_size < 32 && circuits < (1ull << 32) ? ((uint64_t)segments << log_size) * circuits : 0);
+      return graph_evaluate_circuits(*ctx, *g, column_bases, column_strides, n_columns, circuits, dynamic_constants, n_dynamic, log_size, segments,
+                                     d_values, flags, (hipStream_t)stream);
+    }
+  return hm_fail(HM_ERR_NOT_FOUND, "hm_graph_evaluate_circuits_dev: unknown program handle");
+} HM_API_CATCH("hm_graph_evaluate_circuits_dev")
+
 // ---------------------------------------------------------------------------------------------
 // The quotient h(X) of a proof in ONE call, from coefficient arrays: every column onto `count` cosets of the n-th roots
 // (hm_coeff_to_cosets), the numerator program over count segments of n rows (hm_graph_evaluate_segments), the inverse

@@ -124,6 +124,7 @@ int graph_create(DeviceCtx& ctx, const uint32_t* calcs5, size_t n_calc, const ui
   g->n_dynamic = (uint32_t)n_dynamic;
   g->n_intermediates = n_intermediates;
   g->calcs5.assign(calcs5, calcs5 + 5 * n_calc);
+  g->consts_ext.assign(constants_ext, constants_ext + 4 * n_const_static);
   // constants -> internal form
   std::vector<uint32_t> c9(std::max<size_t>(n_const_static, 1) * 9, 0);
   for (size_t i = 0; i < n_const_static; ++i) host::fr_to_internal9(host::fr_load(constants_ext + 4 * i), &c9[9 * i]);
@@ -205,6 +206,167 @@ int graph_evaluate(DeviceCtx& ctx, GraphProgram& g, const void* const* d_columns
     hipLaunchKernelGGL(graph_evaluate_kernel<false>, dim3(blocks), dim3(GE_THREADS), 0, stream, (const GraphColumns*)d_cols,
                        (const uint32_t*)g.d_consts, (const int32_t*)g.d_rot, (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src,
                        v.result_prev, (uint32_t*)buf, (uint32_t*)d_values, size, log_size);
+  HM_HIP_CHECK(hipGetLastError());
+  return aux_release(ctx, slot, stream);
+}
+
+// ---- several circuits of one constraint system in one launch (hm_graph_evaluate_circuits_dev) ----
+// The program is linear in PreviousValue (graph_lower.h: graph_linear_shape): value = Prev * f^T + G(row).  `circuits`
+// successive evaluations on the same values therefore fold as acc = acc * f^T + G_c(row), c = 0 .. circuits - 1, and the G_c
+// are independent: one lane per (circuit, row) runs the program with PreviousValue = 0.  A workgroup covers 256 / C rows x
+// C circuits (C a power of two the host chooses so that the grid fills the chip when rows alone do not); the C partials of
+// a row meet in LDS, and the lane of circuit 0 folds them into an accumulator it keeps in registers across the groups of C
+// circuits.  No partial goes to HBM.  Bounds: a partial is ge_reduce'd (< 3r) before it is written to LDS, the accumulator
+// enters as a product output (ge_from_ext, < 3r), f^T is a canonical constant (< r); fe_mul takes inputs < 18r and leaves
+// < 3r, the sum is < 6r and ge_reduce brings it back below 3r: the classes of one non-lazy MulAdd step of ge_run
+// (host_check.cpp: hc_graph_circuits_replay tracks them).  Rows run fastest inside a workgroup (thread = circuit * rows + row),
+// so that a wave reads consecutive cells of a column.
+struct GraphCircuitColumns {
+  const uint32_t* p[GE_MAX_COLUMNS];
+  uint64_t stride[GE_MAX_COLUMNS];   // u32 words from circuit c's column to circuit c + 1's; 0: one column for all circuits
+  uint32_t dyn[GE_MAX_DYN * 9];
+  uint32_t fold[9];                  // f^T, internal form
+  uint32_t n_static;
+};
+
+template <bool INTERNAL>
+struct CircuitSource {
+  const GraphCircuitColumns* __restrict__ columns;
+  const int32_t* __restrict__ rotations;
+  uint64_t idx, mask, circuit;
+  __device__ __forceinline__ uint32_t n_static() const { return columns->n_static; }
+  __device__ __forceinline__ uint32_t dyn(uint32_t word) const { return columns->dyn[word]; }
+  __device__ __forceinline__ Fr column(uint32_t src) const {
+    uint64_t row = (idx & ~mask) | ((idx + (uint64_t)(int64_t)rotations[gsrc_rot(src)]) & mask);
+    const uint32_t lr = gsrc_log_rows(src);
+    if (lr != 0) row &= (1ull << lr) - 1ull;
+    const uint32_t col = gsrc_column(src);
+    const uint32_t* cell = columns->p[col] + columns->stride[col] * circuit + row * 8;
+    return INTERNAL ? ge_from_internal(cell) : ge_from_ext(cell);
+  }
+  __device__ __forceinline__ Fr previous() const { return fe_zero<FrParams>(); }
+};
+
+template <bool INTERNAL>
+__global__ __launch_bounds__(GE_THREADS) void graph_circuits_kernel(const GraphCircuitColumns* __restrict__ columns,
+                                                                    const uint32_t* __restrict__ consts,
+                                                                    const int32_t* __restrict__ rotations,
+                                                                    const GraphCalc* __restrict__ calcs, uint32_t n_calc, uint32_t result_src,
+                                                                    uint32_t result_prev, uint32_t* __restrict__ scratch,
+                                                                    uint32_t* __restrict__ values, uint64_t size, uint32_t log_segment,
+                                                                    uint32_t circuits, uint32_t log_c) {
+  __shared__ uint32_t part[9 * GE_THREADS];            // [word][thread]: the group's partials
+  const uint32_t C = 1u << log_c, rows_per = GE_THREADS >> log_c;
+  const uint32_t T = gridDim.x * GE_THREADS;
+  const uint32_t lane_slot = blockIdx.x * GE_THREADS + threadIdx.x;
+  const uint32_t r = threadIdx.x & (rows_per - 1), cl = threadIdx.x / rows_per;
+  const uint64_t mask = (1ull << log_segment) - 1;
+  Fr fold;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) fold.l[i] = columns->fold[i];
+  HM_DECLARE(fold, 1.0);
+  // the trip counts of both loops are the same for every thread of the workgroup: the barriers are reached by all
+  for (uint64_t base = (uint64_t)blockIdx.x * rows_per; base < size; base += (uint64_t)gridDim.x * rows_per) {
+    const uint64_t idx = base + r;
+    const bool live = idx < size, folds = live && cl == 0;
+    uint32_t* vrow = values + idx * 8;
+    Fr acc = fe_zero<FrParams>();
+    if (folds) acc = ge_from_ext(vrow);
+    for (uint32_t c0 = 0; c0 < circuits; c0 += C) {
+      if (live && c0 + cl < circuits) {
+        const CircuitSource<INTERNAL> from{columns, rotations, idx, mask, (uint64_t)(c0 + cl)};
+        const Fr g = ge_reduce(ge_run(from, consts, calcs, n_calc, result_src, result_prev, scratch, T, lane_slot));
+#pragma unroll
+        for (int i = 0; i < 9; ++i) part[i * GE_THREADS + threadIdx.x] = g.l[i];
+      }
+      __syncthreads();
+      if (folds) {
+        const uint32_t here = circuits - c0 < C ? circuits - c0 : C;
+        for (uint32_t j = 0; j < here; ++j) {
+          Fr p;
+#pragma unroll
+          for (int i = 0; i < 9; ++i) p.l[i] = part[i * GE_THREADS + j * rows_per + r];
+          HM_DECLARE(p, 3.0);
+          acc = ge_reduce(fe_add(fe_mul(acc, fold), p));
+        }
+      }
+      __syncthreads();
+    }
+    if (folds) {
+      uint32_t w[8];
+      fe_to_ext(w, acc);
+      uint4* dst = reinterpret_cast<uint4*>(vrow);
+      dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+      dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    }
+  }
+}
+
+int graph_evaluate_circuits(DeviceCtx& ctx, GraphProgram& g, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
+                            size_t circuits, const uint64_t* dyn_ext, size_t n_dyn, uint32_t log_size, uint32_t segments, void* d_values,
+                            uint32_t flags, hipStream_t stream) {
+  if (flags & ~(uint32_t)HM_GRAPH_COLUMNS_INTERNAL) return hm_fail(HM_ERR_BAD_ARG, "graph: unknown flag");
+  if (circuits == 0) return hm_fail(HM_ERR_BAD_ARG, "graph: circuits must be >= 1");
+  if (n_columns > GE_MAX_COLUMNS) return hm_fail(HM_ERR_BAD_ARG, "graph: more columns than the column table holds");
+  if (n_columns != g.n_columns) return hm_fail(HM_ERR_BAD_ARG, "graph: the program was built for another number of columns");
+  if (n_dyn != g.n_dynamic) return hm_fail(HM_ERR_BAD_ARG, "graph: the program was built for another number of per-call constants");
+  if (log_size > 30) return hm_fail(HM_ERR_BAD_ARG, "graph: log_size > 30");
+  if (segments == 0 || ((uint64_t)segments << log_size) > (1ull << 32)) return hm_fail(HM_ERR_BAD_ARG, "graph: segments must be >= 1 and rows <= 2^32");
+  const uint64_t size = (uint64_t)segments << log_size;
+  if (circuits > (1ull << 32) / size) return hm_fail(HM_ERR_BAD_ARG, "graph: circuits * rows > 2^32");
+  if ((uintptr_t)d_values % 16) return hm_fail(HM_ERR_BAD_ARG, "graph: the values are not 16-byte aligned");
+  for (size_t i = 0; i < n_columns; ++i) {
+    if (!column_bases[i]) return hm_fail(HM_ERR_BAD_ARG, "graph: null column pointer");
+    if ((uintptr_t)column_bases[i] % 16) return hm_fail(HM_ERR_BAD_ARG, "graph: a column base is not 16-byte aligned");
+    if (column_strides[i] % 4) return hm_fail(HM_ERR_BAD_ARG, "graph: a column stride is not a multiple of 4 words");
+  }
+  uint32_t factor_src = 0, steps = 0;
+  if (const char* why = graph_linear_shape(g.calcs5.data(), g.calcs5.size() / 5, g.n_intermediates, &factor_src, &steps))
+    return hm_fail(HM_ERR_BAD_ARG, why);
+  const bool internal_cols = (flags & HM_GRAPH_COLUMNS_INTERNAL) != 0;
+  GraphVariant& v = g.variant[internal_cols ? 1 : 0];
+  if (!v.ready) {
+    const int rc = graph_lower(g, internal_cols, v);
+    if (rc != HM_OK) return rc;
+  }
+  // f^steps on the host (Montgomery words in, Montgomery words out); steps >= 1
+  const uint32_t fi = gsrc_index(factor_src);
+  const host::Fr4 f = host::fr_load(fi < g.n_static ? &g.consts_ext[4 * (size_t)fi] : dyn_ext + 4 * (size_t)(fi - g.n_static));
+  host::Fr4 f_pow = f;
+  for (uint32_t i = 1; i < steps; ++i) f_pow = host::fr_mul(f_pow, f);
+  // C circuits side by side in a workgroup: as many as it takes for the grid to reach graph_evaluate's block count, no more
+  // than the circuits there are.  circuits = 1 gives C = 1: graph_evaluate_kernel's shape.
+  static const uint32_t max_blocks = [] { const char* e = std::getenv("HALO2_MI355X_GRAPH_BLOCKS"); return (uint32_t)(e && *e ? std::atoi(e) : 1280); }();
+  uint32_t log_c = 0;
+  while (log_c < 8 && (1ull << log_c) < circuits && ((size << log_c) + GE_THREADS - 1) / GE_THREADS < max_blocks) ++log_c;
+  const uint64_t rows_per = GE_THREADS >> log_c;
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>((size + rows_per - 1) / rows_per, max_blocks);
+  const uint32_t T = blocks * GE_THREADS;
+  AuxSlot* slot = aux_acquire(ctx, stream);
+  if (!slot) return HM_ERR_HIP;
+  const size_t b_scratch = (size_t)v.n_slots * 9 * T * 4;
+  uint8_t* buf = (uint8_t*)slot->scratch.ensure(b_scratch);
+  if (!buf) return hm_fail(HM_ERR_HIP, "graph: scratch allocation failed");
+  GraphCircuitColumns cols;
+  std::memset(&cols, 0, sizeof cols);
+  for (size_t i = 0; i < n_columns; ++i) {
+    cols.p[i] = (const uint32_t*)column_bases[i];
+    cols.stride[i] = column_strides[i];
+  }
+  cols.n_static = g.n_static;
+  for (size_t i = 0; i < n_dyn; ++i) host::fr_to_internal9(host::fr_load(dyn_ext + 4 * i), &cols.dyn[9 * i]);
+  host::fr_to_internal9(f_pow, cols.fold);
+  GraphCircuitColumns* d_cols = (GraphCircuitColumns*)slot->args.ensure(sizeof(GraphCircuitColumns));
+  if (!d_cols) return hm_fail(HM_ERR_HIP, "graph: argument buffer allocation failed");
+  HM_HIP_CHECK(hipMemcpyAsync(d_cols, &cols, sizeof cols, hipMemcpyHostToDevice, stream));
+  if (internal_cols)
+    hipLaunchKernelGGL(graph_circuits_kernel<true>, dim3(blocks), dim3(GE_THREADS), 0, stream, (const GraphCircuitColumns*)d_cols,
+                       (const uint32_t*)g.d_consts, (const int32_t*)g.d_rot, (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src,
+                       v.result_prev, (uint32_t*)buf, (uint32_t*)d_values, size, log_size, (uint32_t)circuits, log_c);
+  else
+    hipLaunchKernelGGL(graph_circuits_kernel<false>, dim3(blocks), dim3(GE_THREADS), 0, stream, (const GraphCircuitColumns*)d_cols,
+                       (const uint32_t*)g.d_consts, (const int32_t*)g.d_rot, (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src,
+                       v.result_prev, (uint32_t*)buf, (uint32_t*)d_values, size, log_size, (uint32_t)circuits, log_c);
   HM_HIP_CHECK(hipGetLastError());
   return aux_release(ctx, slot, stream);
 }

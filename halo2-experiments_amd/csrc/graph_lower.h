@@ -83,6 +83,44 @@ inline const char* graph_validate(const uint32_t* calcs5, size_t n_calc, size_t 
   return nullptr;
 }
 
+// What hm_graph_evaluate_circuits_dev admits, checked on a VALIDATED program as it was created: a value that is linear in
+// PreviousValue the way GraphEvaluator.add_custom_gates builds it.  PreviousValue occurs once in the whole program, as the
+// start of the Horner (MulAdd) chain that ends in the last calculation; every step of the chain has the same factor, a
+// constant (of the program or of the call); no step's value is read by anything but the next step.  The value is then
+// Prev * f^steps + G(row), with G what the program leaves for Prev = 0.  -> nullptr and (factor source word, steps), or
+// the reason the program is refused.
+inline const char* graph_linear_shape(const uint32_t* calcs5, size_t n_calc, uint32_t n_intermediates, uint32_t* factor_src, uint32_t* steps) {
+  if (n_calc == 0) return "graph: an empty program is not linear in PreviousValue";
+  auto nsrc_of = [](uint32_t op) { return op == GOP_MULADD ? 3 : (op <= GOP_MUL ? 2 : 1); };
+  std::vector<uint32_t> defined_by(n_intermediates, 0xffffffffu), reads(n_intermediates, 0);
+  size_t prev_reads = 0;
+  for (size_t k = 0; k < n_calc; ++k) {
+    const uint32_t* c = calcs5 + 5 * k;
+    for (int j = 0; j < nsrc_of(c[0]); ++j) {
+      if (gsrc_kind(c[1 + j]) == GSRC_PREV) ++prev_reads;
+      if (gsrc_kind(c[1 + j]) == GSRC_INTER) ++reads[gsrc_index(c[1 + j])];
+    }
+    defined_by[c[4]] = (uint32_t)k;
+  }
+  if (prev_reads != 1) return "graph: PreviousValue must be read exactly once";
+  const uint32_t* last = calcs5 + 5 * (n_calc - 1);
+  if (last[0] != GOP_MULADD || gsrc_kind(last[2]) != GSRC_CONST) return "graph: the last calculation must be a Horner step with a constant factor";
+  if (reads[last[4]] != 0) return "graph: the value of the Horner chain is read inside the program";
+  const uint32_t factor = last[2];
+  uint32_t count = 0;
+  for (const uint32_t* c = last;;) {
+    if (c[0] != GOP_MULADD || c[2] != factor) return "graph: the Horner chain from PreviousValue must use one factor";
+    ++count;
+    if (gsrc_kind(c[1]) == GSRC_PREV) break;
+    if (gsrc_kind(c[1]) != GSRC_INTER) return "graph: PreviousValue is not the start of the final Horner chain";
+    if (reads[gsrc_index(c[1])] != 1) return "graph: a step of the Horner chain is read outside the chain";
+    c = calcs5 + 5 * defined_by[gsrc_index(c[1])];
+  }
+  *factor_src = factor;
+  *steps = count;
+  return nullptr;
+}
+
 struct GraphLowered {       // a validated program lowered for one column format, still on the host
   std::vector<GraphCalc> calcs;
   std::vector<double> bound;              // per lowered calculation: the static bound (units of r) of the value it leaves

@@ -227,6 +227,7 @@ struct GraphProgram {       // a compiled evaluate_h program (graph.hip): the va
   uint32_t* d_consts = nullptr;
   int32_t* d_rot = nullptr;
   std::vector<uint32_t> calcs5;      // as given to hm_graph_create
+  std::vector<uint64_t> consts_ext;  // its constants as given (graph_evaluate_circuits raises the Horner factor to a power on the host)
   uint32_t n_intermediates = 0, n_static = 0, n_dynamic = 0;
   size_t n_columns = 0;
   GraphVariant variant[2];           // [0] external-form columns, [1] internal-form columns (HM_GRAPH_COLUMNS_INTERNAL)
@@ -398,6 +399,9 @@ int graph_create(DeviceCtx& ctx, const uint32_t* calcs5, size_t n_calc, const ui
                  uint64_t* out_handle);
 int graph_evaluate(DeviceCtx& ctx, GraphProgram& g, const void* const* d_columns, size_t n_columns, const uint64_t* dyn_ext,
                    size_t n_dyn, uint32_t log_size, uint32_t segments, void* d_values, uint32_t flags, hipStream_t stream);
+int graph_evaluate_circuits(DeviceCtx& ctx, GraphProgram& g, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
+                            size_t circuits, const uint64_t* dyn_ext, size_t n_dyn, uint32_t log_size, uint32_t segments, void* d_values,
+                            uint32_t flags, hipStream_t stream);
 void graph_release(GraphProgram& g);
 
 // poly.hip

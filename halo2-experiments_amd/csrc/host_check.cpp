@@ -116,6 +116,65 @@ GFr gr_from_internal(const uint32_t* p) {                                       
 }
 const char* g_graph_error = "";
 
+// One row of the LOWERED program, as ge_run (graph_interp.h) runs it for a lane: THIS LOOP RESTATES THAT SWITCH, primitive for
+// primitive and in its order.  fetch(src): ge_fetch;  slots: the lane's scratch;  tracked_bound[k]: the largest bound seen for
+// calculation k's result.  -> the program's value, not yet reduced.
+template <class Fetch>
+GFr gr_run(const GraphLowered& low, std::vector<GFr>& slots, Fetch&& fetch, double* tracked_bound) {
+  const size_t n = low.calcs.size();
+  GFr prev = fe_zero<FrParams>();
+  HM_DECLARE(prev, 3.0);
+  for (size_t k = 0; k < n; ++k) {
+    const GraphCalc cc = low.calcs[k];
+    const uint32_t op = cc.op & 0xffu;
+    auto src = [&](uint32_t word, uint32_t flag) -> GFr { return (cc.op & flag) ? prev : fetch(word); };
+    const GFr a = src(cc.a, GF_A_PREV);
+    GFr out;
+    const bool lazy = (cc.op & GF_NO_REDUCE) != 0, wide = (cc.op & GF_SUB_WIDE) != 0;
+    auto settle = [&](const GFr& t) -> GFr { return lazy ? fe_norm(t) : gr_reduce(t); };
+    switch (op) {
+      case GOP_ADD:
+        out = settle(fe_add(a, src(cc.b, GF_B_PREV)));
+        break;
+      case GOP_SUB: {
+        const GFr b = src(cc.b, GF_B_PREV);
+        out = wide ? gr_reduce(fe_sub<20, 29>(a, b)) : settle(fe_sub<4, 29>(a, b));
+        break;
+      }
+      case GOP_MUL:
+        out = fe_mul(a, src(cc.b, GF_B_PREV));
+        break;
+      case GOP_SQUARE:
+        out = fe_sqr(a);
+        break;
+      case GOP_DOUBLE:
+        out = settle(fe_dbl(a));
+        break;
+      case GOP_NEGATE:
+        out = wide ? gr_reduce(fe_sub<20, 29>(fe_zero<FrParams>(), a)) : settle(fe_sub<4, 29>(fe_zero<FrParams>(), a));
+        break;
+      case GOP_MULADD: {
+        const GFr b = src(cc.b, GF_B_PREV);
+        const GFr c = src(cc.c, GF_C_PREV);
+        out = settle(fe_add(fe_mul(a, b), c));
+        break;
+      }
+      default:
+        out = a;
+        break;
+    }
+    if (!(cc.op & GF_NO_STORE)) slots[cc.target] = out;
+    if (out.vb > tracked_bound[k]) tracked_bound[k] = out.vb;
+    prev = out;
+  }
+  GFr res = fe_zero<FrParams>();
+  if (low.result_prev)
+    res = prev;
+  else if (n != 0 || gsrc_kind(low.result_src) != GSRC_INTER)
+    res = fetch(low.result_src);
+  return res;
+}
+
 }  // namespace
 
 extern "C" {
@@ -292,8 +351,8 @@ int hc_graph_bounds_closure(const uint64_t* a_ext, double* report) {
 }
 
 // The GraphEvaluator without a GPU: validate and lower a program exactly as hm_graph_create / graph_evaluate do (graph_lower.h is the
-// code they run), then interpret the LOWERED program row by row as graph_evaluate_kernel does -- THIS LOOP RESTATES THAT KERNEL'S
-// switch (graph.hip), primitive for primitive and in its order; tests/test_graph_programs_gpu.py holds the two to the same words.
+// code they run), then interpret the LOWERED program row by row as graph_evaluate_kernel does (gr_run above restates ge_run's switch);
+// tests/test_graph_programs_gpu.py holds the two to the same words.
 // Column loads, constants and PreviousValue enter at the class maxima the kernel declares; a value in a slot keeps the bound the
 // tracker gave it (the kernel re-declares it at GE_CAP, which the caller checks against the static bound instead), and the slots keep
 // their contents from row to row, as a lane's slots do in the grid-stride loop.
@@ -365,56 +424,7 @@ int hc_graph_replay(const uint32_t* calcs5, size_t n_calc, const uint64_t* const
       }
       return r;
     };
-    GFr prev = fe_zero<FrParams>();
-    HM_DECLARE(prev, 3.0);
-    for (size_t k = 0; k < n; ++k) {
-      const GraphCalc cc = low.calcs[k];
-      const uint32_t op = cc.op & 0xffu;
-      auto src = [&](uint32_t word, uint32_t flag) -> GFr { return (cc.op & flag) ? prev : fetch(word); };
-      const GFr a = src(cc.a, GF_A_PREV);
-      GFr out;
-      const bool lazy = (cc.op & GF_NO_REDUCE) != 0, wide = (cc.op & GF_SUB_WIDE) != 0;
-      auto settle = [&](const GFr& t) -> GFr { return lazy ? fe_norm(t) : gr_reduce(t); };
-      switch (op) {
-        case GOP_ADD:
-          out = settle(fe_add(a, src(cc.b, GF_B_PREV)));
-          break;
-        case GOP_SUB: {
-          const GFr b = src(cc.b, GF_B_PREV);
-          out = wide ? gr_reduce(fe_sub<20, 29>(a, b)) : settle(fe_sub<4, 29>(a, b));
-          break;
-        }
-        case GOP_MUL:
-          out = fe_mul(a, src(cc.b, GF_B_PREV));
-          break;
-        case GOP_SQUARE:
-          out = fe_sqr(a);
-          break;
-        case GOP_DOUBLE:
-          out = settle(fe_dbl(a));
-          break;
-        case GOP_NEGATE:
-          out = wide ? gr_reduce(fe_sub<20, 29>(fe_zero<FrParams>(), a)) : settle(fe_sub<4, 29>(fe_zero<FrParams>(), a));
-          break;
-        case GOP_MULADD: {
-          const GFr b = src(cc.b, GF_B_PREV);
-          const GFr c = src(cc.c, GF_C_PREV);
-          out = settle(fe_add(fe_mul(a, b), c));
-          break;
-        }
-        default:
-          out = a;
-          break;
-      }
-      if (!(cc.op & GF_NO_STORE)) slots[cc.target] = out;
-      if (out.vb > tracked_bound[k]) tracked_bound[k] = out.vb;
-      prev = out;
-    }
-    GFr res = fe_zero<FrParams>();
-    if (low.result_prev)
-      res = prev;
-    else if (n != 0 || gsrc_kind(low.result_src) != GSRC_INTER)
-      res = fetch(low.result_src);
+    const GFr res = gr_run(low, slots, fetch, tracked_bound);
     uint32_t w[8];
     fe_to_ext(w, gr_reduce(res));
     std::memcpy(vrow, w, 32);
@@ -422,6 +432,105 @@ int hc_graph_replay(const uint32_t* calcs5, size_t n_calc, const uint64_t* const
   return rc;
 }
 const char* hc_graph_last_error() { return g_graph_error; }
+
+// graph_linear_shape (graph_lower.h) on a validated program: what hm_graph_evaluate_circuits_dev admits.  -> 0 and out = {factor
+// source word, Horner steps}; -1: refused (hc_graph_last_error).
+int hc_graph_linear_shape(const uint32_t* calcs5, size_t n_calc, size_t n_const_static, size_t n_dynamic, size_t n_rot, size_t n_columns,
+                          uint32_t n_intermediates, uint32_t* out) {
+  g_graph_error = "";
+  const char* why = graph_validate(calcs5, n_calc, n_const_static, n_dynamic, n_rot, n_columns, n_intermediates);
+  if (!why) why = graph_linear_shape(calcs5, n_calc, n_intermediates, &out[0], &out[1]);
+  if (why) g_graph_error = why;
+  return why ? -1 : 0;
+}
+
+// graph_circuits_kernel (graph.hip) without a GPU: per row, every circuit's program with PreviousValue = 0 (gr_run), the partial
+// reduced as it is before it goes to LDS and RE-DECLARED at the class the kernel declares when it reads it back (< 3r), then the
+// fold acc = ge_reduce(acc * f^T + partial) from the entry value, in the kernel's order.  Arguments as hc_graph_replay, and:
+// circuits;  column_strides[i]: u32 words from circuit c's column i to circuit c + 1's (0: shared);  column_rows[i]: the rows ONE
+// circuit's column holds.  fold_bound: {largest partial as reduced, largest accumulator entering the product, largest sum before
+// its reduction, largest accumulator stored}.  -> 0; -1 refused; -2 a column read past column_rows.
+int hc_graph_circuits_replay(const uint32_t* calcs5, size_t n_calc, const uint64_t* constants_ext, size_t n_const_static, const uint64_t* dyn_ext,
+                             size_t n_dynamic, const int32_t* rotations, size_t n_rot, const uint32_t* const* columns,
+                             const uint64_t* column_strides, const uint64_t* column_rows, size_t n_columns, size_t circuits,
+                             uint32_t n_intermediates, uint32_t log_segment, uint32_t segments, uint32_t flags, uint32_t* values,
+                             double* tracked_bound, double* fold_bound) {
+  g_graph_error = "";
+  const char* why = graph_validate(calcs5, n_calc, n_const_static, n_dynamic, n_rot, n_columns, n_intermediates);
+  uint32_t factor_src = 0, steps = 0;
+  if (!why) why = graph_linear_shape(calcs5, n_calc, n_intermediates, &factor_src, &steps);
+  if (!why && (flags & ~1u)) why = "graph: unknown flag";
+  if (!why && log_segment > 30) why = "graph: log_size > 30";
+  if (!why && (segments == 0 || ((uint64_t)segments << log_segment) > (1ull << 32))) why = "graph: segments must be >= 1 and rows <= 2^32";
+  if (!why && (circuits == 0 || circuits > (1ull << 32) / ((uint64_t)segments << log_segment))) why = "graph: circuits * rows > 2^32";
+  if (why) {
+    g_graph_error = why;
+    return -1;
+  }
+  const bool internal_cols = (flags & 1u) != 0;
+  GraphLowered low;
+  graph_lower_host(calcs5, n_calc, n_intermediates, internal_cols, low);
+  for (size_t k = 0; k < low.calcs.size(); ++k) tracked_bound[k] = 0.0;
+  std::vector<uint32_t> consts((n_const_static + n_dynamic + 1) * 9, 0);
+  for (size_t i = 0; i < n_const_static; ++i) host::fr_to_internal9(host::fr_load(constants_ext + 4 * i), &consts[9 * i]);
+  for (size_t i = 0; i < n_dynamic; ++i) host::fr_to_internal9(host::fr_load(dyn_ext + 4 * i), &consts[9 * (n_const_static + i)]);
+  const uint32_t fi = gsrc_index(factor_src);
+  const host::Fr4 f = host::fr_load(fi < n_const_static ? constants_ext + 4 * (size_t)fi : dyn_ext + 4 * (size_t)(fi - n_const_static));
+  host::Fr4 f_pow = f;
+  for (uint32_t i = 1; i < steps; ++i) f_pow = host::fr_mul(f_pow, f);
+  GFr fold;
+  host::fr_to_internal9(f_pow, fold.l);
+  HM_DECLARE(fold, 1.0);
+  GFr stale;
+  for (int i = 0; i < 9; ++i) stale.l[i] = 0x5a5a5a5u;
+  stale.l[8] = 0x5a5u;
+  HM_DECLARE(stale, GE_CAP);
+  std::vector<GFr> slots(low.n_slots, stale);
+  const uint64_t size = (uint64_t)segments << log_segment, mask = (1ull << log_segment) - 1;
+  for (int i = 0; i < 4; ++i) fold_bound[i] = 0.0;
+  int rc = 0;
+  for (uint64_t idx = 0; idx < size && rc == 0; ++idx) {
+    uint32_t* vrow = values + idx * 8;
+    GFr acc = gr_from_ext(vrow);
+    for (size_t circuit = 0; circuit < circuits && rc == 0; ++circuit) {
+      auto fetch = [&](uint32_t src) -> GFr {                     // graph.hip: ge_fetch over CircuitSource
+        const uint32_t kind = gsrc_kind(src), index = gsrc_index(src);
+        GFr r;
+        if (kind == GSRC_INTER) {
+          r = slots[index];
+        } else if (kind == GSRC_CONST) {
+          for (int i = 0; i < 9; ++i) r.l[i] = consts[(size_t)index * 9 + i];
+          HM_DECLARE(r, 1.0);
+        } else if (kind == GSRC_COLUMN) {
+          uint64_t row = (idx & ~mask) | ((idx + (uint64_t)(int64_t)rotations[gsrc_rot(src)]) & mask);
+          const uint32_t lr = gsrc_log_rows(src), col = gsrc_column(src);
+          if (lr != 0) row &= (1ull << lr) - 1ull;
+          if (row >= column_rows[col]) {
+            rc = -2;
+            return fe_zero<FrParams>();
+          }
+          const uint32_t* cell = columns[col] + column_strides[col] * circuit + row * 8;
+          r = internal_cols ? gr_from_internal(cell) : gr_from_ext(cell);
+        } else {
+          r = fe_zero<FrParams>();                                // CircuitSource::previous
+        }
+        return r;
+      };
+      GFr part = gr_reduce(gr_run(low, slots, fetch, tracked_bound));
+      if (part.vb > fold_bound[0]) fold_bound[0] = part.vb;
+      HM_DECLARE(part, 3.0);                                      // as read back from LDS
+      if (acc.vb > fold_bound[1]) fold_bound[1] = acc.vb;
+      const GFr sum = fe_add(fe_mul(acc, fold), part);
+      if (sum.vb > fold_bound[2]) fold_bound[2] = sum.vb;
+      acc = gr_reduce(sum);
+    }
+    if (acc.vb > fold_bound[3]) fold_bound[3] = acc.vb;
+    uint32_t w[8];
+    fe_to_ext(w, acc);
+    std::memcpy(vrow, w, 32);
+  }
+  return rc;
+}
 
 int hc_fr_vector_bounds_closure(const uint64_t* a_ext, const uint64_t* b_ext, double* report) {
   typedef Fe<FrParams> F;

@@ -298,6 +298,40 @@ class GraphEvaluator:
                     num_challenges=num_challenges, short_columns=dict(short_columns))
 
 
+def linear_in_previous(calcs: np.ndarray) -> Tuple[int, int]:
+    """What ``hm_graph_evaluate_circuits_dev`` admits, on the five-word calculations (the check of ``graph_lower.h``, stated again so
+    that a wrong program never reaches the library): PreviousValue is read exactly once, as the start of the MulAdd chain that ends
+    in the last calculation; every step has the same constant factor and is read by the next step only.  -> (factor source word,
+    steps): the program's value is Prev * factor^steps + G(row).  Anything else raises ValueError."""
+    calcs = np.asarray(calcs, dtype=np.uint32).reshape(-1, 5)
+    if len(calcs) == 0:
+        raise ValueError("evaluate_circuits: an empty program is not linear in PreviousValue")
+    nsrc = lambda op: 3 if op == 7 else (2 if op <= 2 else 1)
+    defined_by, reads, prev_reads = {}, {}, 0
+    for k, c in enumerate(calcs.tolist()):
+        for s in c[1:1 + nsrc(c[0])]:
+            if s >> 30 == 3:
+                prev_reads += 1
+            elif s >> 30 == 1:
+                reads[s & 0xfffff] = reads.get(s & 0xfffff, 0) + 1
+        defined_by[c[4]] = k
+    if prev_reads != 1:
+        raise ValueError("evaluate_circuits: the program must read PreviousValue exactly once")
+    c = calcs[-1].tolist()
+    if c[0] != 7 or c[2] >> 30 != 0 or reads.get(c[4], 0):
+        raise ValueError("evaluate_circuits: the last calculation must be the end of a Horner chain with a constant factor")
+    factor, steps = c[2], 0
+    while True:
+        if c[0] != 7 or c[2] != factor:
+            raise ValueError("evaluate_circuits: the Horner chain from PreviousValue must use one factor")
+        steps += 1
+        if c[1] >> 30 == 3:
+            return factor, steps
+        if c[1] >> 30 != 1 or reads.get(c[1] & 0xfffff, 0) != 1:
+            raise ValueError("evaluate_circuits: PreviousValue must start the final Horner chain, whose steps nothing else reads")
+        c = calcs[defined_by[c[1] & 0xfffff]].tolist()
+
+
 class CompiledGraph:
     """A program uploaded to the device (``hm_graph_create``); ``evaluate`` = upstream's per-row loop of evaluate_h."""
 
@@ -344,6 +378,63 @@ class CompiledGraph:
         _lib.check(_lib.load().hm_graph_evaluate_segments_dev(ctypes.c_uint64(self.handle), ptrs, len(columns), _ptr(dyn), dyn.shape[0],
                                                               seg.bit_length() - 1, segments, ctypes.c_void_p(values.data_ptr()),
                                                               _lib.HM_GRAPH_COLUMNS_INTERNAL if columns_internal else 0, ctypes.c_void_p(_stream_ptr(values))))
+
+    def evaluate_circuits(self, columns: Sequence, strides_or_stacked, values, circuits: int, challenges: Sequence[int] = (), beta: int = 0,
+                          gamma: int = 0, theta: int = 0, y: int = 0, columns_internal: bool = False, segments: int = 1) -> None:
+        """``circuits`` successive ``evaluate`` calls on the same ``values`` in one launch (``hm_graph_evaluate_circuits_dev``), call c
+        reading circuit c's columns.  ``columns[i]``: a (circuits, size, 4) GPU tensor -- one column per circuit, stacked -- or a
+        (size, 4) tensor that every circuit shares (a short column: its 2^log rows).  ``strides_or_stacked``: None to take that from
+        the tensors' shapes, or one entry per column: True / False for stacked / shared, or an integer stride in u32 words between
+        one circuit's column and the next one's inside a larger tensor (0 = shared; ``columns[i]`` is then circuit 0's column).
+        The program must be linear in PreviousValue (``linear_in_previous``): anything else raises ValueError before any call."""
+        linear_in_previous(self.calcs)
+        size = _tensor_rows(values, 4, "values")
+        if circuits < 1:
+            raise ValueError("evaluate_circuits: circuits must be >= 1")
+        if segments < 1 or size % segments:
+            raise ValueError("evaluate_circuits: the rows must be a whole number of segments")
+        seg = size // segments
+        if seg & (seg - 1) or seg == 0:
+            raise ValueError("evaluate_circuits: the (segment of the) domain must be a power of two")
+        if len(columns) != self.n_columns or len(challenges) != self.num_challenges:
+            raise ValueError("evaluate_circuits: column / challenge count differs from the compiled program's")
+        hints = list(strides_or_stacked) if strides_or_stacked is not None else [None] * len(columns)
+        if len(hints) != len(columns):
+            raise ValueError("evaluate_circuits: one stride (or stacked flag) per column")
+        keep, ptrs, strides = [], [], []
+        for i, (c, hint) in enumerate(zip(columns, hints)):
+            want = (1 << self.short_columns[i]) if i in self.short_columns else size
+            if hint is None:
+                hint = c.dim() == 3
+            if isinstance(hint, bool):
+                if hint:
+                    if c.dim() != 3 or tuple(c.shape) != (circuits, want, 4):
+                        raise ValueError(f"evaluate_circuits: stacked column {i} must be ({circuits}, {want}, 4)")
+                    c = c.contiguous()
+                    stride = want * 8
+                else:
+                    if _tensor_rows(c, 4, "column") != want:
+                        raise ValueError(f"evaluate_circuits: column {i} must hold {want} rows")
+                    stride = 0
+                    if want == 1 and i in self.short_columns:      # encoded as two rows (GraphEvaluator.lower): the same row twice
+                        c = c.reshape(1, 4).expand(2, 4).contiguous()
+            else:
+                stride = int(hint)
+                if _tensor_rows(c, 4, "column") != want:
+                    raise ValueError(f"evaluate_circuits: column {i} must hold {want} rows (circuit 0's)")
+                if want == 1 and i in self.short_columns:
+                    if stride:
+                        raise ValueError(f"evaluate_circuits: the one-row column {i} must be shared")
+                    c = c.reshape(1, 4).expand(2, 4).contiguous()
+            keep.append(c)
+            ptrs.append(c.data_ptr())
+            strides.append(stride)
+        ptr_arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+        stride_arr = (ctypes.c_uint64 * max(len(strides), 1))(*strides)
+        dyn = np.stack([fr_words(v) for v in list(challenges) + [beta, gamma, theta, y]])
+        _lib.check(_lib.load().hm_graph_evaluate_circuits_dev(
+            ctypes.c_uint64(self.handle), ptr_arr, stride_arr, len(ptrs), circuits, _ptr(dyn), dyn.shape[0], seg.bit_length() - 1, segments,
+            ctypes.c_void_p(values.data_ptr()), _lib.HM_GRAPH_COLUMNS_INTERNAL if columns_internal else 0, ctypes.c_void_p(_stream_ptr(values))))
 
     def _quotient_args(self, domain, coeff_columns, cosets, challenges, beta, gamma, theta, y, on_cosets, who):
         cosets = list(range(domain.min_cosets())) if cosets is None else [int(c) for c in cosets]

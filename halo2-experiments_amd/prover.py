@@ -1,16 +1,35 @@
-"""``create_proof`` of ``halo2_proofs::plonk`` for one circuit over KZG with the SHPLONK multiopen, every polynomial step on the
-device entry points that existed before it plus the set-quotient kernel of ``shplonk``.
+"""``create_proof`` of ``halo2_proofs::plonk`` over KZG with the SHPLONK multiopen, for one circuit (``create_proof``) or for m circuits of
+one constraint system in a single transcript (``create_proof_multi``, upstream's ``&[circuit; m]``): ONE body of protocol code,
+``_create_proof``, with every polynomial step on the device entry points (DESIGN.md sections 17 and 19).
 
-The order of the transcript is RECALLED from upstream tag v2023_02_02 (plonk/prover.rs) and not pinned against its bytes: the vk digest;
-the instance values as scalars (the KZG path does not commit them); the advice commitments; theta; per lookup the permuted input and
-table; beta, gamma; the permutation z columns, then the lookup z columns; the vanishing argument's random polynomial; y; the h
-pieces; x; the evaluations -- advice, fixed, random polynomial, permutation common, permutation z, lookups --; SHPLONK.  The order
-of the advice / fixed queries is this project's own (``ConstraintSystem.queries``: first use in the gates, then the lookups, then the
-equality columns), since upstream's depends on the order of ``meta.query_*`` calls inside chips that are not in this tree.  The vk
-digest is Blake2b-512 (``person = b"Halo2-Verify-Key"``) over k, the column counts, the equality list and the commitments, reduced
-mod r: upstream hashes the ``Debug`` print of its own struct, which cannot be reproduced here.
+The order of the transcript is RECALLED from upstream tag v2023_02_02 (plonk/prover.rs) and not pinned against its bytes.  All circuits
+share theta, beta, gamma, y and x:
 
-Nothing but the blinding is random, and it comes from ``random_fr(seed + ...)``: a seed fixes the bytes."""
+    1. the vk digest;  2. per circuit, its instance values as scalars (the KZG path does not commit them);  3. per circuit, its advice
+    commitments;  4. theta;  5. per circuit, per lookup: the permuted input, then the permuted table;  6. beta, gamma;  7. per circuit,
+    the permutation z columns;  8. per circuit, the lookup z columns;  9. ONE random polynomial of the vanishing argument;  10. y;
+    11. the h pieces;  12. x;  13. the evaluations -- per circuit the advice; fixed; random polynomial; sigma; per circuit the
+    permutation z; per circuit the lookups;  14. SHPLONK over the queries -- per circuit: advice, permutation z, lookups; once: fixed,
+    sigma, h, random polynomial.
+
+h folds in y through circuit 0's gates, permutation and lookup terms, then circuit 1's, and so on; the division by X^n - 1 happens
+once.  The order of the advice / fixed queries is this project's own (``ConstraintSystem.queries``: first use in the gates, then the
+lookups, then the equality columns), since upstream's depends on the order of ``meta.query_*`` calls inside chips that are not in this
+tree.  The vk digest is Blake2b-512 (``person = b"Halo2-Verify-Key"``) over k, the column counts, the equality list and the
+commitments, reduced mod r: upstream hashes the ``Debug`` print of its own struct, which cannot be reproduced here.
+
+Per phase ONE batched call carries all circuits: ``best_multiexp_batch`` over m x columns, one stacked ``lagrange_to_coeff`` /
+``coeff_to_extended``, one ``permute_expression_pairs``, one ``batch_invert`` per argument, one ``eval_polynomial``, the set quotients with
+more polynomials per set; the helper graph programs are compiled once per proof and run with the circuits as segments; h comes from
+``CompiledGraph.evaluate_circuits`` with the shared columns at stride 0, in chunks of circuits chained through PreviousValue when the
+circuits' own extended columns pass ``H_COLUMN_BUDGET`` (2 GiB, the witness writers' convention).  The permutation products are one
+``grand_product_batch`` per circuit: its chain runs from one column set to the next and must start at 1 in every circuit.
+
+Nothing but the blinding is random, and it comes from ``random_fr(seed + ...)``: a seed fixes the bytes.  ``base`` = the low 48 bits of
+``seed`` shifted by 10 (58 bits; ``create_proof``'s derivation, kept so that its bytes stay) names the streams of circuit 0: + 0 advice,
++ 0x40 + 2 j / + 1 the permuted columns of lookup j, + 0x80 + i the permutation z, + 0xC0 + j the lookup z, + 0x100 the random
+polynomial (drawn once per proof).  Circuit c uses ``base | c << 58``: the 6 bits above the base, hence at most 64 circuits; no two
+circuits of a proof and no two seeds (mod 2^48) share a stream."""
 from __future__ import annotations
 
 import hashlib
@@ -65,18 +84,40 @@ def _dev(values, device):
     return torch.from_numpy(ints_to_words(values).view(np.int64)).to(device)
 
 
-def _run(exprs, columns, n, counts, **scalars):
-    """the value of one expression list (folded in y; a single expression is itself) on the n rows of the domain"""
-    import torch
-    g = ev.GraphEvaluator()
-    g.add_custom_gates(exprs)
-    prog = g.compile(*counts)
-    out = torch.zeros((n, 4), dtype=torch.int64, device=columns[0].device)
-    try:
-        prog.evaluate(list(columns), out, **scalars)
-    finally:
-        prog.destroy()
-    return out
+class _Programs:
+    """the helper graph programs of one proof -- compressed lookups, permutation numerators and denominators, products -- compiled once
+    each, whatever the number of circuits, and destroyed together"""
+
+    def __init__(self):
+        self._progs, self._shared = {}, {}
+
+    def run(self, name, exprs, counts, columns, m, n, **scalars):
+        """the value of one expression (an expression list folded in y) on the n rows of each of the m circuits in ONE launch: a column
+        is (m, n, 4) -- one per circuit -- or (n, 4), shared; the circuits are the segments of ``CompiledGraph.evaluate``, so a
+        rotation wraps inside its circuit.  -> (m, n, 4)"""
+        import torch
+        if name not in self._progs:
+            g = ev.GraphEvaluator()
+            g.add_custom_gates(exprs)
+            self._progs[name] = g.compile(*counts)
+        def rows(c):
+            if c.dim() == 3:
+                return c.reshape(m * n, 4)
+            if m == 1:
+                return c
+            key = (c.data_ptr(), m)                      # a shared column, once per circuit: copied once per proof
+            if key not in self._shared:
+                self._shared[key] = (c, c.expand(m, n, 4).reshape(m * n, 4))
+            return self._shared[key][1]
+        cols = [rows(c) for c in columns]
+        out = torch.zeros((m * n, 4), dtype=torch.int64, device=cols[0].device)
+        self._progs[name].evaluate(cols, out, segments=m, **scalars)
+        return out.reshape(m, n, 4)
+
+    def destroy(self):
+        for prog in self._progs.values():
+            prog.destroy()
+        self._progs, self._shared = {}, {}
 
 
 def _compress(exprs):
@@ -86,148 +127,216 @@ def _compress(exprs):
     return acc
 
 
+MAX_CIRCUITS = 64                   # the circuit's number sits in the 6 seed bits above the 58 of ``base``
+H_COLUMN_BUDGET = 2 << 30           # bytes of per-circuit extended columns in flight in the h step (the witness writers' 2 GiB)
+
+
 def create_proof(params, pk: ProvingKey, advice, instance, seed: int, _trace: dict = None) -> bytes:
     """The proof bytes for the witness ``advice`` -- the (num_advice, n, 4) device tensor a witness writer returns for one circuit --
     and its ``instance`` values.  One circuit per proof: a list of several witnesses, or a 4-dimensional tensor holding more than
-    one, raises ValueError.  ``_trace``: a dict that receives the committed polynomials and their commitments (tests)."""
-    import torch
-
+    one, raises ValueError (``create_proof_multi`` takes several).  ``_trace``: a dict that receives the committed polynomials and
+    their commitments (tests)."""
     if isinstance(advice, (list, tuple)):
         if len(advice) != 1:
-            raise ValueError("create_proof: one circuit per proof (multi-circuit proofs are out of scope)")
+            raise ValueError("create_proof: one circuit per proof (create_proof_multi proves several)")
         advice = advice[0]
     if _is_tensor(advice) and advice.dim() == 4:
         if advice.shape[0] != 1:
-            raise ValueError("create_proof: one circuit per proof (multi-circuit proofs are out of scope)")
+            raise ValueError("create_proof: one circuit per proof (create_proof_multi proves several)")
         advice = advice[0]
+    trace = None if _trace is None else {}
+    proof = _create_proof("create_proof", params, pk, [advice], [instance], seed, trace)
+    if _trace is not None:                                 # one circuit: its keys without the circuit's number
+        strip = lambda key: key[:2] if len(key) == 3 else key
+        lag = trace["lagrange"]
+        _trace.update(polys={strip(key): p for key, p in trace["polys"].items()}, commits={strip(key): p for key, p in trace["commits"].items()},
+                      lagrange={"advice": lag["advice"][0], "perm_z": lag["perm_z"][0], "lookup_z": lag["lookup_z"][0], "permuted": lag["permuted"][0]},
+                      pieces=trace["pieces"], challenges=trace["challenges"])
+    return proof
+
+
+def create_proof_multi(params, pk: ProvingKey, advice, instances, seed: int, _trace: dict = None) -> bytes:
+    """ONE proof for m circuits of ``pk``'s constraint system (upstream ``create_proof(params, pk, &[circuit; m], &[instances; m])``):
+    ``advice`` is the (m, num_advice, n, 4) GPU tensor a witness writer returns, or a list of m (num_advice, n, 4) tensors;
+    ``instances`` holds m entries, each in the form ``create_proof`` takes.  1 <= m <= 64.  All circuits share theta, beta, gamma, y
+    and x; with m = 1 the bytes are ``create_proof``'s.  ``_trace``: as in ``create_proof``, the keys of what belongs to one circuit
+    carrying its number as a third element (("advice", column, circuit) ...) and ``lagrange`` holding one entry per circuit."""
+    if _is_tensor(advice):
+        if advice.dim() != 4:
+            raise ValueError("create_proof_multi: advice must be a (m, num_advice, n, 4) GPU tensor or a list of m (num_advice, n, 4) tensors")
+        advice = [advice[c] for c in range(advice.shape[0])]
+    elif not isinstance(advice, (list, tuple)):
+        raise ValueError("create_proof_multi: advice must be a (m, num_advice, n, 4) GPU tensor or a list of m (num_advice, n, 4) tensors")
+    advice = list(advice)
+    if not 1 <= len(advice) <= MAX_CIRCUITS:
+        raise ValueError(f"create_proof_multi: between 1 and {MAX_CIRCUITS} circuits per proof")
+    if _is_tensor(instances) or isinstance(instances, np.ndarray) or len(instances) != len(advice):
+        raise ValueError(f"create_proof_multi: {len(advice)} circuit(s) need {len(advice)} instance entries")
+    return _create_proof("create_proof_multi", params, pk, advice, list(instances), seed, _trace)
+
+
+def _create_proof(who, params, pk, advice, instances, seed, _trace) -> bytes:
+    import torch
+
+    m = len(advice)
     vk = pk.vk
     cs, dom = vk.cs, vk.domain
     k, n = dom.k, 1 << dom.k
     if params.k != k:
-        raise ValueError("create_proof: the parameters and the key differ in k")
-    if not _is_tensor(advice) or not advice.is_cuda or tuple(advice.shape) != (cs.num_advice, n, 4):
-        raise ValueError(f"create_proof: advice must be a ({cs.num_advice}, {n}, 4) GPU tensor")
-    device = advice.device
+        raise ValueError(f"{who}: the parameters and the key differ in k")
+    for a in advice:
+        if not _is_tensor(a) or not a.is_cuda or tuple(a.shape) != (cs.num_advice, n, 4):
+            raise ValueError(f"{who}: advice must be a ({cs.num_advice}, {n}, 4) GPU tensor" + (" per circuit" if m > 1 else ""))
+    device = advice[0].device
+    A, I = cs.num_advice, cs.num_instance
     blinding, deg = cs.blinding_factors, cs.degree()
     usable = n - blinding - 1
     omega, delta = dom.omega, FR_DELTA
     P, chunk, nsets, L = len(cs.equality), cs.permutation_chunk_len(), cs.permutation_sets(), len(cs.lookups)
-    counts = (cs.num_fixed, cs.num_advice, cs.num_instance)
-    base = (int(seed) & 0xFFFFFFFFFFFF) << 10      # the seeds of the blinding: advice, permuted columns, z columns, random polynomial
+    counts = (cs.num_fixed, A, I)
+    # the seeds of the blinding: advice, permuted columns, z columns, random polynomial; the circuit's number above the 58 bits of the base
+    base = (int(seed) & 0xFFFFFFFFFFFF) << 10
+    bases = [base | (c << 58) for c in range(m)]
     d = lambda values: _dev(values, device)
+    ck = lambda kind, index, c: (kind, index, c)            # the key of what belongs to circuit c
     commits = {}
+    progs = _Programs()
 
-    def commit_lagrange(key_cols):
-        com = best_multiexp_batch([c for _, c in key_cols], params.g_lagrange_handle)
+    def commit(key_cols, handle):
+        com = best_multiexp_batch([c for _, c in key_cols], handle)
         for (key, _), c in zip(key_cols, com):
             commits[key] = g1_words_to_int(c)
             transcript.write_point(commits[key])
 
-    def commit_coeff(key_cols):
-        com = best_multiexp_batch([c for _, c in key_cols], params.g_handle)
-        for (key, _), c in zip(key_cols, com):
-            commits[key] = g1_words_to_int(c)
-            transcript.write_point(commits[key])
+    commit_lagrange = lambda key_cols: commit(key_cols, params.g_lagrange_handle)
+    commit_coeff = lambda key_cols: commit(key_cols, params.g_handle)
 
     # ---- the columns -----------------------------------------------------------------------------------------------------------------------
-    adv = advice.clone()
-    adv[:, usable:] = random_fr(cs.num_advice * (n - usable), base, device, shape=(cs.num_advice, n - usable, 4))
-    inst_cols = instance_values(cs, instance)
-    inst = torch.zeros((cs.num_instance, n, 4), dtype=torch.int64, device=device)
-    for c, values in enumerate(inst_cols):
-        if len(values) > usable:
-            raise ValueError("create_proof: too many instance values")
-        if values:
-            inst[c, :len(values)] = d(values)
+    adv = torch.stack(list(advice), dim=1)                                   # (A, m, n, 4), a copy: adv[i] is column i of every circuit
+    for c in range(m):
+        adv[:, c, usable:] = random_fr(A * (n - usable), bases[c], device, shape=(A, n - usable, 4))
+    inst_cols = [instance_values(cs, instance) for instance in instances]
+    inst = torch.zeros((I, m, n, 4), dtype=torch.int64, device=device)
+    for c in range(m):
+        for i, values in enumerate(inst_cols[c]):
+            if len(values) > usable:
+                raise ValueError(f"{who}: too many instance values")
+            if values:
+                inst[i, c, :len(values)] = d(values)
     fixed = pk.fixed_values
-    table = [fixed[i] for i in range(cs.num_fixed)] + [adv[i] for i in range(cs.num_advice)] + [inst[i] for i in range(cs.num_instance)]
+    table = [fixed[i] for i in range(cs.num_fixed)] + [adv[i] for i in range(A)] + [inst[i] for i in range(I)]
 
     transcript = Blake2bWrite()
     transcript.common_scalar(vk_digest(vk))
-    for values in inst_cols:
-        for v in values:
-            transcript.common_scalar(v)
-    commit_lagrange([(("advice", c), adv[c]) for c in range(cs.num_advice)])
+    for c in range(m):
+        for values in inst_cols[c]:
+            for v in values:
+                transcript.common_scalar(v)
+    commit_lagrange([(ck("advice", i, c), adv[i, c]) for c in range(m) for i in range(A)])
     theta = transcript.squeeze_challenge()
 
-    # ---- the lookups: permuted columns -------------------------------------------------------------------------------------------------------
-    lk_in = [_run([_compress(ins)], table, n, counts, theta=theta) for ins, _ in cs.lookups]
-    lk_tab = [_run([_compress(tabs)], table, n, counts, theta=theta) for _, tabs in cs.lookups]
-    permuted = permute_expression_pairs(lk_in, lk_tab, usable, blinding_seed=base + 0x40) if L else []
-    commit_lagrange([pair for j, (a, s) in enumerate(permuted) for pair in ((("lookup_a", j), a), (("lookup_s", j), s))])
-    beta = transcript.squeeze_challenge()
-    gamma = transcript.squeeze_challenge()
+    try:
+        # ---- the lookups: permuted columns (lookup j of circuit c at index c L + j) ------------------------------------------------------------
+        lk_in = [progs.run(("in", j), [_compress(ins)], counts, table, m, n, theta=theta) for j, (ins, _) in enumerate(cs.lookups)]
+        lk_tab = [progs.run(("tab", j), [_compress(tabs)], counts, table, m, n, theta=theta) for j, (_, tabs) in enumerate(cs.lookups)]
+        order = [(c, j) for c in range(m) for j in range(L)]
+        permuted = permute_expression_pairs([lk_in[j][c] for c, j in order], [lk_tab[j][c] for c, j in order], usable,
+                                            blinding_seeds=[bases[c] + 0x40 + 2 * j for c, j in order]) if L else []
+        commit_lagrange([pair for (c, j), (a, s) in zip(order, permuted) for pair in ((ck("lookup_a", j, c), a), (ck("lookup_s", j, c), s))])
+        beta = transcript.squeeze_challenge()
+        gamma = transcript.squeeze_challenge()
 
-    # ---- the permutation argument: one z per chunk of columns, chained at the last usable row ----------------------------------------------
-    by_kind = {"advice": adv, "fixed": fixed, "instance": inst}
-    perm_cols = [by_kind[kind][c] for kind, c in cs.equality]
-    sigma = pk.permutation_values
-    acc, xs = 1, []
-    for _ in range(n):
-        xs.append(acc)
-        acc = acc * omega % R
-    x_col = d(xs)
-    mul2 = [ev.Advice(0) * ev.Advice(1)]
-    factors = []
-    for s0 in range(0, P, chunk):
-        cc, ss = perm_cols[s0:s0 + chunk], [sigma[j] for j in range(s0, min(s0 + chunk, P))]
-        w = len(cc)
-        den_e = num_e = None
-        for j in range(w):
-            de = ev.Advice(j) + ev.BETA * ev.Advice(w + j) + ev.GAMMA
-            ne = ev.Advice(j) + ev.BETA * ev.Advice(2 * w) * pow(delta, s0 + j, R) + ev.GAMMA
-            den_e = de if den_e is None else den_e * de
-            num_e = ne if num_e is None else num_e * ne
-        cols = cc + ss + [x_col]
-        den = _run([den_e], cols, n, (0, len(cols), 0), beta=beta, gamma=gamma)
-        num = _run([num_e], cols, n, (0, len(cols), 0), beta=beta, gamma=gamma)
-        batch_invert(den)
-        factors.append(_run(mul2, [num, den], n, (0, 2, 0)))
-    zs = grand_product_batch(factors, fr_words(1), chain_row=usable) if factors else []
-    for i, z in enumerate(zs):
-        z[usable + 1:] = random_fr(n - usable - 1, base + 0x80 + i, device)
-    commit_lagrange([(("perm_z", i), z) for i, z in enumerate(zs)])
+        # ---- the permutation argument: one z per chunk of columns, chained at the last usable row inside its circuit ---------------------------
+        by_kind = {"advice": lambda i: adv[i], "fixed": lambda i: fixed[i], "instance": lambda i: inst[i]}
+        perm_cols = [by_kind[kind](i) for kind, i in cs.equality]
+        sigma = pk.permutation_values
+        acc, xs = 1, []
+        for _ in range(n):
+            xs.append(acc)
+            acc = acc * omega % R
+        x_col = d(xs)
+        mul2 = [ev.Advice(0) * ev.Advice(1)]
+        factors = []                                                        # per set: (m, n, 4)
+        for s0 in range(0, P, chunk):
+            cc, ss = perm_cols[s0:s0 + chunk], [sigma[j] for j in range(s0, min(s0 + chunk, P))]
+            w = len(cc)
+            den_e = num_e = None
+            for j in range(w):
+                de = ev.Advice(j) + ev.BETA * ev.Advice(w + j) + ev.GAMMA
+                ne = ev.Advice(j) + ev.BETA * ev.Advice(2 * w) * pow(delta, s0 + j, R) + ev.GAMMA
+                den_e = de if den_e is None else den_e * de
+                num_e = ne if num_e is None else num_e * ne
+            cols = cc + ss + [x_col]
+            den = progs.run(("den", s0), [den_e], (0, len(cols), 0), cols, m, n, beta=beta, gamma=gamma)
+            num = progs.run(("num", s0), [num_e], (0, len(cols), 0), cols, m, n, beta=beta, gamma=gamma)
+            batch_invert(den.reshape(m * n, 4))
+            factors.append(progs.run("mul2", mul2, (0, 2, 0), [num, den], m, n))
+        # the chain of grand_product_batch runs from one set to the next, so a circuit's sets are one call
+        zs = [grand_product_batch([f[c] for f in factors], fr_words(1), chain_row=usable) if factors else [] for c in range(m)]
+        for c in range(m):
+            for i, z in enumerate(zs[c]):
+                z[usable + 1:] = random_fr(n - usable - 1, bases[c] + 0x80 + i, device)
+        commit_lagrange([(ck("perm_z", i, c), z) for c in range(m) for i, z in enumerate(zs[c])])
 
-    # ---- the lookup arguments' z ----------------------------------------------------------------------------------------------------------------
-    pair = [(ev.Advice(0) + ev.BETA) * (ev.Advice(1) + ev.GAMMA)]
-    lk_factors = []
-    for j, (a_perm, s_perm) in enumerate(permuted):
-        num = _run(pair, [lk_in[j], lk_tab[j]], n, (0, 2, 0), beta=beta, gamma=gamma)
-        den = _run(pair, [a_perm, s_perm], n, (0, 2, 0), beta=beta, gamma=gamma)
-        batch_invert(den)
-        lk_factors.append(_run(mul2, [num, den], n, (0, 2, 0)))
-    lk_z = grand_product_batch(lk_factors, fr_words(1)) if lk_factors else []
-    for j, z in enumerate(lk_z):
-        z[usable + 1:] = random_fr(n - usable - 1, base + 0xC0 + j, device)
-    commit_lagrange([(("lookup_z", j), z) for j, z in enumerate(lk_z)])
+        # ---- the lookup arguments' z ----------------------------------------------------------------------------------------------------------------
+        pair = [(ev.Advice(0) + ev.BETA) * (ev.Advice(1) + ev.GAMMA)]
+        lk_z = [[] for _ in range(m)]
+        if L:
+            stacked = lambda ts: torch.stack(list(ts))                    # (m L, n, 4): the lookups of all circuits as the segments
+            num = progs.run("pair", pair, (0, 2, 0), [stacked(lk_in[j][c] for c, j in order), stacked(lk_tab[j][c] for c, j in order)], m * L, n,
+                            beta=beta, gamma=gamma)
+            den = progs.run("pair", pair, (0, 2, 0), [stacked(a for a, _ in permuted), stacked(s for _, s in permuted)], m * L, n,
+                            beta=beta, gamma=gamma)
+            batch_invert(den.reshape(m * L * n, 4))
+            lk_factors = progs.run("mul2", mul2, (0, 2, 0), [num, den], m * L, n)
+            flat = grand_product_batch([lk_factors[i] for i in range(m * L)], fr_words(1))
+            for (c, j), z in zip(order, flat):
+                z[usable + 1:] = random_fr(n - usable - 1, bases[c] + 0xC0 + j, device)
+                lk_z[c].append(z)
+        commit_lagrange([(ck("lookup_z", j, c), z) for c in range(m) for j, z in enumerate(lk_z[c])])
+    finally:
+        progs.destroy()
+    perm_of = [[permuted[c * L + j] for j in range(L)] for c in range(m)]
 
-    # ---- the vanishing argument's random polynomial, then h -------------------------------------------------------------------------------------
+    # ---- the vanishing argument's random polynomial (one per proof), then h ------------------------------------------------------------------------
     random_poly = random_fr(n, base + 0x100, device)
     commit_coeff([(("random",), random_poly)])
     y = transcript.squeeze_challenge()
 
-    g, tab = circuits.evaluate_h_program(cs, k, dom.extended_k, delta)
-    lookups3 = [c for j in range(L) for c in (lk_z[j], permuted[j][0], permuted[j][1])]
-    lagrange = zs + lookups3 + [adv[c] for c in range(cs.num_advice)] + [inst[c] for c in range(cs.num_instance)]
-    var_coeffs = dom.lagrange_to_coeff(torch.stack(lagrange))
-    z_polys, lk_polys = var_coeffs[:nsets], var_coeffs[nsets:nsets + 3 * L]
-    adv_polys, inst_polys = var_coeffs[nsets + 3 * L:nsets + 3 * L + cs.num_advice], var_coeffs[nsets + 3 * L + cs.num_advice:]
+    g, tab = circuits.evaluate_h_program(cs, k, dom.extended_k, delta, divide=False)
+    V = nsets + 3 * L + A + I                                               # the columns of its own that a circuit brings to h
+    lagrange = [col for c in range(m)
+                for col in zs[c] + [t for j in range(L) for t in (lk_z[c][j], perm_of[c][j][0], perm_of[c][j][1])] + [adv[i, c] for i in range(A)]
+                + [inst[i, c] for i in range(I)]]
+    var_coeffs = dom.lagrange_to_coeff(torch.stack(lagrange)).reshape(m, V, n, 4)
+    z_polys, lk_polys = var_coeffs[:, :nsets], var_coeffs[:, nsets:nsets + 3 * L]
+    adv_polys = var_coeffs[:, nsets + 3 * L:nsets + 3 * L + A]
     sel = dom.lagrange_to_coeff(torch.stack([pk.l0, pk.l_last, pk.l_active]))
     x_poly = d([0, 1] + [0] * (n - 2)).reshape(1, n, 4)
-    coeffs = torch.cat([pk.fixed_polys, pk.permutation_polys, z_polys, sel, x_poly, lk_polys, adv_polys, inst_polys])
-    n_fixed_entries = tab.t_inv
-    assert coeffs.shape[0] == n_fixed_entries + cs.num_advice + cs.num_instance
-    ext = dom.coeff_to_extended(coeffs)
+    shared = dom.coeff_to_extended(torch.cat([pk.fixed_polys, pk.permutation_polys, sel, x_poly]))
+    n_shared = shared.shape[0]
+    assert n_shared + nsets + 3 * L == tab.t_inv
     rot_scale = 1 << (dom.extended_k - k)
-    t_inv = d([pow((pow(FR_ZETA * pow(dom.extended_omega, i, R) % R, n, R) - 1) % R, -1, R) for i in range(rot_scale)])
-    prog = g.compile(tab.num_fixed_entries, cs.num_advice, cs.num_instance, rot_scale=rot_scale, short_columns=tab.short_columns)
-    h_ext = torch.zeros((dom.extended_len(), 4), dtype=torch.int64, device=device)
+    en = dom.extended_len()
+    unread = torch.zeros((max(rot_scale, 2), 4), dtype=torch.int64, device=device)[:rot_scale]     # the table's t_inv entry: divide=False never reads it
+    prog = g.compile(tab.num_fixed_entries, A, I, rot_scale=rot_scale, short_columns=tab.short_columns)
+    h_ext = torch.zeros((en, 4), dtype=torch.int64, device=device)
+    # the program's table: fixed, sigma | z | l0, l_last, l_active, x | lookups | t_inv || advice | instance
+    n_fs = cs.num_fixed + P
+    step = max(1, H_COLUMN_BUDGET // max(V * en * 32, 1))                   # circuits whose extended columns are in flight together
     try:
-        prog.evaluate([ext[i] for i in range(n_fixed_entries)] + [t_inv] + [ext[i] for i in range(n_fixed_entries, coeffs.shape[0])], h_ext,
-                      beta=beta, gamma=gamma, theta=theta, y=y)
+        for c0 in range(0, m, step):
+            mc = min(step, m - c0)
+            ext = dom.coeff_to_extended(var_coeffs[c0:c0 + mc].reshape(mc * V, n, 4)).reshape(mc, V, en, 4)
+            own = lambda v: ext[0, v]
+            cols = ([shared[i] for i in range(n_fs)] + [own(i) for i in range(nsets)] + [shared[i] for i in range(n_fs, n_shared)]
+                    + [own(nsets + i) for i in range(3 * L)] + [unread] + [own(nsets + 3 * L + i) for i in range(A + I)])
+            strides = ([0] * n_fs + [V * en * 8] * nsets + [0] * (n_shared - n_fs) + [V * en * 8] * (3 * L) + [0] + [V * en * 8] * (A + I))
+            prog.evaluate_circuits(cols, strides, h_ext, mc, beta=beta, gamma=gamma, theta=theta, y=y)     # chained through PreviousValue
+            del ext
     finally:
         prog.destroy()
-    del ext
+    dom.divide_by_vanishing_poly(h_ext)
     h_coeff = dom.extended_to_coeff(h_ext)                      # ((deg - 1) n, 4): in place on h_ext
     pieces = [h_coeff[i * n:(i + 1) * n] for i in range(deg - 1)]
     commit_coeff([(("h_piece", i), p) for i, p in enumerate(pieces)])
@@ -238,23 +347,31 @@ def create_proof(params, pk: ProvingKey, advice, instance, seed: int, _trace: di
     last = -(blinding + 1)
     rot = lambda r: x * pow(omega, r, R) % R
     polys = {("random",): random_poly}
-    for c in range(cs.num_advice):
-        polys[("advice", c)] = adv_polys[c]
-    for c in range(cs.num_fixed):
-        polys[("fixed", c)] = pk.fixed_polys[c]
+    for c in range(m):
+        for i in range(A):
+            polys[ck("advice", i, c)] = adv_polys[c, i]
+    for i in range(cs.num_fixed):
+        polys[("fixed", i)] = pk.fixed_polys[i]
     for j in range(P):
         polys[("sigma", j)] = pk.permutation_polys[j]
-    for i in range(nsets):
-        polys[("perm_z", i)] = z_polys[i]
-    for j in range(L):
-        polys[("lookup_z", j)], polys[("lookup_a", j)], polys[("lookup_s", j)] = lk_polys[3 * j], lk_polys[3 * j + 1], lk_polys[3 * j + 2]
+    for c in range(m):
+        for i in range(nsets):
+            polys[ck("perm_z", i, c)] = z_polys[c, i]
+    for c in range(m):
+        for j in range(L):
+            polys[ck("lookup_z", j, c)], polys[ck("lookup_a", j, c)], polys[ck("lookup_s", j, c)] = (
+                lk_polys[c, 3 * j], lk_polys[c, 3 * j + 1], lk_polys[c, 3 * j + 2])
     polys[("h",)] = linear_combination(pieces, np.stack([fr_words(pow(x, n * i, R)) for i in range(deg - 1)]))
-    wanted = [(("advice", c), rot(r)) for c, r in adv_q] + [(("fixed", c), rot(r)) for c, r in fix_q] + [(("random",), x)]
+    wanted = [(ck("advice", i, c), rot(r)) for c in range(m) for i, r in adv_q]
+    wanted += [(("fixed", i), rot(r)) for i, r in fix_q] + [(("random",), x)]
     wanted += [(("sigma", j), x) for j in range(P)]
-    for i in range(nsets):
-        wanted += [(("perm_z", i), x), (("perm_z", i), rot(1))] + ([(("perm_z", i), rot(last))] if i + 1 < nsets else [])
-    for j in range(L):
-        wanted += [(("lookup_z", j), x), (("lookup_z", j), rot(1)), (("lookup_a", j), x), (("lookup_a", j), rot(-1)), (("lookup_s", j), x)]
+    for c in range(m):
+        for i in range(nsets):
+            wanted += [(ck("perm_z", i, c), x), (ck("perm_z", i, c), rot(1))] + ([(ck("perm_z", i, c), rot(last))] if i + 1 < nsets else [])
+    for c in range(m):
+        for j in range(L):
+            wanted += [(ck("lookup_z", j, c), x), (ck("lookup_z", j, c), rot(1)), (ck("lookup_a", j, c), x), (ck("lookup_a", j, c), rot(-1)),
+                       (ck("lookup_s", j, c), x)]
     keys = list(polys)
     stack = torch.stack([polys[key] for key in keys])
     index = {key: i for i, key in enumerate(keys)}
@@ -268,15 +385,19 @@ def create_proof(params, pk: ProvingKey, advice, instance, seed: int, _trace: di
 
     # ---- the multiopen: upstream's order of queries ---------------------------------------------------------------------------------------------
     q = lambda key, pt: (key, pt, evals[(key, pt)])
-    queries = [q(("advice", c), rot(r)) for c, r in adv_q]
-    queries += [qq for i in range(nsets) for qq in (q(("perm_z", i), x), q(("perm_z", i), rot(1)))]
-    queries += [q(("perm_z", i), rot(last)) for i in reversed(range(nsets - 1))]
-    for j in range(L):
-        queries += [q(("lookup_z", j), x), q(("lookup_a", j), x), q(("lookup_s", j), x), q(("lookup_a", j), rot(-1)), q(("lookup_z", j), rot(1))]
-    queries += [q(("fixed", c), rot(r)) for c, r in fix_q] + [q(("sigma", j), x) for j in range(P)]
+    queries = []
+    for c in range(m):
+        queries += [q(ck("advice", i, c), rot(r)) for i, r in adv_q]
+        queries += [qq for i in range(nsets) for qq in (q(ck("perm_z", i, c), x), q(ck("perm_z", i, c), rot(1)))]
+        queries += [q(ck("perm_z", i, c), rot(last)) for i in reversed(range(nsets - 1))]
+        for j in range(L):
+            queries += [q(ck("lookup_z", j, c), x), q(ck("lookup_a", j, c), x), q(ck("lookup_s", j, c), x), q(ck("lookup_a", j, c), rot(-1)),
+                        q(ck("lookup_z", j, c), rot(1))]
+    queries += [q(("fixed", i), rot(r)) for i, r in fix_q] + [q(("sigma", j), x) for j in range(P)]
     queries += [(("h",), x, hx), q(("random",), x)]
     create_opening(params, transcript, queries, polys)
     if _trace is not None:
-        _trace.update(polys=polys, commits=commits, lagrange={"advice": adv, "perm_z": zs, "lookup_z": lk_z, "permuted": permuted},
+        _trace.update(polys=polys, commits=commits,
+                      lagrange={"advice": [adv[:, c] for c in range(m)], "perm_z": zs, "lookup_z": lk_z, "permuted": perm_of},
                       pieces=pieces, challenges=dict(theta=theta, beta=beta, gamma=gamma, y=y, x=x))
     return transcript.finalize()

@@ -3,7 +3,9 @@ the transcript and the constraint system with ``prover`` and nothing else: the p
 prover wrote it (RECALLED from upstream, see ``prover``), the gate, permutation and lookup expressions are evaluated at x by a small
 recursive evaluator over ``evaluation.Expression``, the quotient identity fixes h(x), and ``shplonk.verify_opening`` leaves two G1 points
 L, R with e(L, [s]G2) = e(R, G2) -- checked by ``pairing.pairing_check`` against the parameters' G2 points, or, when the caller knows
-the trapdoor s (tests), by s * L == R in G1."""
+the trapdoor s (tests), by s * L == R in G1.  ``verify_proof_multi`` reads a ``create_proof_multi`` proof of m circuits the same way
+(per circuit where the prover writes per circuit), folds every circuit's expressions into one running value in y,
+and makes one opening check; ``verify_proof`` is its m = 1 case."""
 from __future__ import annotations
 
 import hashlib
@@ -33,12 +35,12 @@ def _vk_digest(vk: VerifyingKey) -> int:
     return int.from_bytes(hsh.digest(), "little") % R
 
 
-def proof_length(cs) -> int:
-    """the bytes of a proof of ``cs``, counted from the constraint system: 32 per point and per scalar"""
+def proof_length(cs, circuits: int = 1) -> int:
+    """the bytes of a proof of ``circuits`` circuits of ``cs``, counted from the constraint system: 32 per point and per scalar"""
     adv_q, fix_q, _ = cs.queries()
     P, nsets, L = len(cs.equality), cs.permutation_sets(), len(cs.lookups)
-    points = cs.num_advice + 2 * L + nsets + L + 1 + (cs.degree() - 1) + 2
-    scalars = len(adv_q) + len(fix_q) + 1 + P + (3 * nsets - 1 if nsets else 0) + 5 * L
+    points = circuits * (cs.num_advice + 2 * L + nsets + L) + 1 + (cs.degree() - 1) + 2
+    scalars = circuits * (len(adv_q) + (3 * nsets - 1 if nsets else 0) + 5 * L) + len(fix_q) + 1 + P
     return 32 * (points + scalars)
 
 
@@ -78,37 +80,55 @@ def verify_proof(params, vk: VerifyingKey, instance, proof: bytes, trapdoor: int
     list per instance column).  ``params`` needs ``g2`` / ``s_g2`` only.  A malformed proof -- short or long, a point off the curve, a
     scalar not below r -- is False, not an exception."""
     try:
-        return _verify(params, vk, instance, proof, trapdoor)
+        return _verify(params, vk, [instance], proof, trapdoor)
     except TranscriptError:
         return False
 
 
-def _verify(params, vk, instance, proof, trapdoor) -> bool:
+def verify_proof_multi(params, vk: VerifyingKey, instances, proof: bytes, trapdoor: int = None) -> bool:
+    """True when ``proof`` is a valid ``create_proof_multi`` proof that every entry of ``instances`` -- one per circuit, each in the
+    form ``verify_proof`` takes -- has a witness satisfying ``vk``'s circuit.  The proof is read in the prover's order (per circuit
+    where the prover writes per circuit); the expression list is evaluated once per circuit, with that circuit's evaluations and
+    instance values, into ONE running value folded in y; one opening, one pairing check.  Malformed: False, as in ``verify_proof``."""
+    try:
+        return _verify(params, vk, list(instances), proof, trapdoor)
+    except TranscriptError:
+        return False
+
+
+def _verify(params, vk, instances, proof, trapdoor) -> bool:
     cs, dom = vk.cs, vk.domain
     n, omega, blinding = 1 << dom.k, dom.omega, cs.blinding_factors
     P, chunk, nsets, L = len(cs.equality), cs.permutation_chunk_len(), cs.permutation_sets(), len(cs.lookups)
     deg, last = cs.degree(), -(blinding + 1)
-    if len(proof) != proof_length(cs):
+    m = len(instances)
+    if m < 1 or len(proof) != proof_length(cs, m):
         return False
-    inst_cols = _instance_columns(cs, instance)
+    inst_cols = [_instance_columns(cs, instance) for instance in instances]
+    M = range(m)
     t = Blake2bRead(proof)
     t.common_scalar(_vk_digest(vk))
-    for values in inst_cols:
-        for v in values:
-            t.common_scalar(v)
-    com = {}
-    for c in range(cs.num_advice):
-        com[("advice", c)] = t.read_point()
+    for c in M:
+        for values in inst_cols[c]:
+            for v in values:
+                t.common_scalar(v)
+    com = {}                                               # what belongs to circuit c: (kind, index, c)
+    for c in M:
+        for i in range(cs.num_advice):
+            com[("advice", i, c)] = t.read_point()
     theta = t.squeeze_challenge()
-    for j in range(L):
-        com[("lookup_a", j)] = t.read_point()
-        com[("lookup_s", j)] = t.read_point()
+    for c in M:
+        for j in range(L):
+            com[("lookup_a", j, c)] = t.read_point()
+            com[("lookup_s", j, c)] = t.read_point()
     beta = t.squeeze_challenge()
     gamma = t.squeeze_challenge()
-    for i in range(nsets):
-        com[("perm_z", i)] = t.read_point()
-    for j in range(L):
-        com[("lookup_z", j)] = t.read_point()
+    for c in M:
+        for i in range(nsets):
+            com[("perm_z", i, c)] = t.read_point()
+    for c in M:
+        for j in range(L):
+            com[("lookup_z", j, c)] = t.read_point()
     com[("random",)] = t.read_point()
     y = t.squeeze_challenge()
     h_pieces = [t.read_point() for _ in range(deg - 1)]
@@ -117,19 +137,22 @@ def _verify(params, vk, instance, proof, trapdoor) -> bool:
 
     adv_q, fix_q, inst_q = cs.queries()
     evals = {}
-    for c, r in adv_q:
-        evals[(("advice", c), rot(r))] = t.read_scalar()
-    for c, r in fix_q:
-        evals[(("fixed", c), rot(r))] = t.read_scalar()
+    for c in M:
+        for i, r in adv_q:
+            evals[(("advice", i, c), rot(r))] = t.read_scalar()
+    for i, r in fix_q:
+        evals[(("fixed", i), rot(r))] = t.read_scalar()
     evals[(("random",), x)] = t.read_scalar()
     for j in range(P):
         evals[(("sigma", j), x)] = t.read_scalar()
-    for i in range(nsets):
-        for r in (0, 1) + ((last,) if i + 1 < nsets else ()):
-            evals[(("perm_z", i), rot(r))] = t.read_scalar()
-    for j in range(L):
-        for key, r in ((("lookup_z", j), 0), (("lookup_z", j), 1), (("lookup_a", j), 0), (("lookup_a", j), -1), (("lookup_s", j), 0)):
-            evals[(key, rot(r))] = t.read_scalar()
+    for c in M:
+        for i in range(nsets):
+            for r in (0, 1) + ((last,) if i + 1 < nsets else ()):
+                evals[(("perm_z", i, c), rot(r))] = t.read_scalar()
+    for c in M:
+        for j in range(L):
+            for kd, r in (("lookup_z", 0), ("lookup_z", 1), ("lookup_a", 0), ("lookup_a", -1), ("lookup_s", 0)):
+                evals[((kd, j, c), rot(r))] = t.read_scalar()
 
     # ---- the Lagrange values the arguments and the instance columns need ---------------------------------------------------------------------
     xn = pow(x, n, R)
@@ -146,9 +169,9 @@ def _verify(params, vk, instance, proof, trapdoor) -> bool:
     l_blind = sum(lagrange_at(i, x) for i in range(n - blinding, n)) % R
     l_active = (1 - l_last - l_blind) % R
 
-    def instance_eval(c: int, r: int) -> int:
+    def instance_eval(circuit: int, column: int, r: int) -> int:
         pt = rot(r)
-        return sum(v * lagrange_at(i, pt) for i, v in enumerate(inst_cols[c]) if v) % R
+        return sum(v * lagrange_at(i, pt) for i, v in enumerate(inst_cols[circuit][column]) if v) % R
 
     # ---- h(x) from the identity: the expressions in the prover's order, folded in y ---------------------------------------------------------------
     nf = cs.num_fixed
@@ -156,21 +179,23 @@ def _verify(params, vk, instance, proof, trapdoor) -> bool:
     i_l0, i_last, i_active, i_x, lookup0 = z0 + nsets, z0 + nsets + 1, z0 + nsets + 2, z0 + nsets + 3, z0 + nsets + 4
     special = {i_l0: l0, i_last: l_last, i_active: l_active, i_x: x}
 
-    def leaf(kind: str, column: int, r: int) -> int:
-        if kind == "instance":
-            return instance_eval(column, r)
-        if kind == "advice":
-            return evals[(("advice", column), rot(r))]
-        if column < nf:
-            return evals[(("fixed", column), rot(r))]
-        if column in special:
-            return special[column]
-        if column < z0:
-            return evals[(("sigma", column - sigma0), rot(r))]
-        if column < i_l0:
-            return evals[(("perm_z", column - z0), rot(r))]
-        j, part = divmod(column - lookup0, 3)
-        return evals[((("lookup_z", "lookup_a", "lookup_s")[part], j), rot(r))]
+    def leaf_of(c: int):
+        def leaf(kind: str, column: int, r: int) -> int:
+            if kind == "instance":
+                return instance_eval(c, column, r)
+            if kind == "advice":
+                return evals[(("advice", column, c), rot(r))]
+            if column < nf:
+                return evals[(("fixed", column), rot(r))]
+            if column in special:
+                return special[column]
+            if column < z0:
+                return evals[(("sigma", column - sigma0), rot(r))]
+            if column < i_l0:
+                return evals[(("perm_z", column - z0, c), rot(r))]
+            j, part = divmod(column - lookup0, 3)
+            return evals[((("lookup_z", "lookup_a", "lookup_s")[part], j, c), rot(r))]
+        return leaf
 
     F = ev.Fixed
     kind = {"advice": ev.Advice, "fixed": ev.Fixed, "instance": ev.Instance}
@@ -184,8 +209,10 @@ def _verify(params, vk, instance, proof, trapdoor) -> bool:
                                        F(i_last), F(i_active))
     scalars = {"Beta": beta, "Gamma": gamma, "Theta": theta}
     acc = 0
-    for e in exprs:
-        acc = (acc * y + evaluate_expression(e, leaf, scalars)) % R
+    for c in M:                                            # circuit 0's gates, permutation and lookup terms, then circuit 1's ...
+        leaf = leaf_of(c)
+        for e in exprs:
+            acc = (acc * y + evaluate_expression(e, leaf, scalars)) % R
     if xn == 1:
         return False
     hx = acc * pow(xn - 1, -1, R) % R
@@ -200,12 +227,15 @@ def _verify(params, vk, instance, proof, trapdoor) -> bool:
 
     # ---- the multiopen --------------------------------------------------------------------------------------------------------------------------------
     q = lambda key, pt: (key, pt, evals[(key, pt)])
-    queries = [q(("advice", c), rot(r)) for c, r in adv_q]
-    queries += [qq for i in range(nsets) for qq in (q(("perm_z", i), x), q(("perm_z", i), rot(1)))]
-    queries += [q(("perm_z", i), rot(last)) for i in reversed(range(nsets - 1))]
-    for j in range(L):
-        queries += [q(("lookup_z", j), x), q(("lookup_a", j), x), q(("lookup_s", j), x), q(("lookup_a", j), rot(-1)), q(("lookup_z", j), rot(1))]
-    queries += [q(("fixed", c), rot(r)) for c, r in fix_q] + [q(("sigma", j), x) for j in range(P)]
+    queries = []
+    for c in M:
+        queries += [q(("advice", i, c), rot(r)) for i, r in adv_q]
+        queries += [qq for i in range(nsets) for qq in (q(("perm_z", i, c), x), q(("perm_z", i, c), rot(1)))]
+        queries += [q(("perm_z", i, c), rot(last)) for i in reversed(range(nsets - 1))]
+        for j in range(L):
+            queries += [q(("lookup_z", j, c), x), q(("lookup_a", j, c), x), q(("lookup_s", j, c), x), q(("lookup_a", j, c), rot(-1)),
+                        q(("lookup_z", j, c), rot(1))]
+    queries += [q(("fixed", i), rot(r)) for i, r in fix_q] + [q(("sigma", j), x) for j in range(P)]
     queries += [(("h",), x, hx), q(("random",), x)]
     if any(com[key] is None for key, _, _ in queries):
         return False                                         # the identity cannot be absorbed or opened

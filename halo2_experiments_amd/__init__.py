@@ -25,13 +25,13 @@ from .keygen import (ProvingKey, VerifyingKey, copy_pairs, keygen_pk, keygen_vk,
 from .mock_prover import MockProver, MockResult, NotSatisfied  # noqa: F401
 from .pairing import pairing_check  # noqa: F401
 from .poseidon import MerkleSumTree, MerkleTree, Spec, poseidon_hash, poseidon_hash_host, update_plan  # noqa: F401
-from .prover import create_proof  # noqa: F401
+from .prover import create_proof, create_proof_multi  # noqa: F401
 from .shplonk import construct_intermediate_sets, set_quotient, set_quotient_ints  # noqa: F401
 from .synthesis import (MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, merkle_sum_witness,  # noqa: F401
                         merkle_sum_witness_host, merkle_witness, merkle_witness_host, permutation_columns, poseidon_circuit_witness,
                         poseidon_circuit_witness_host)
 from .transcript import Blake2bRead, Blake2bWrite  # noqa: F401
-from .verifier import verify_proof  # noqa: F401
+from .verifier import verify_proof, verify_proof_multi  # noqa: F401
 
 __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_multiexp_submit", "best_multiexp_wait", "best_fft",
            "register_bases", "release_bases", "bases_info", "g1_fixed_base_mul", "g1_fft", "g1_fft_host", "g1_compress", "g1_compress_host",
@@ -42,5 +42,5 @@ __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_mult
            "merkle_sum_witness_host", "permutation_columns", "MerkleTreeV3Layout", "PoseidonCircuitLayout", "merkle_witness",
            "merkle_witness_host", "poseidon_circuit_witness", "poseidon_circuit_witness_host", "copy_pairs", "permutation_cells_dev",
            "permutation_columns_dev", "keygen_vk", "keygen_pk", "VerifyingKey", "ProvingKey",
-           "create_proof", "verify_proof", "Blake2bWrite", "Blake2bRead", "pairing_check", "construct_intermediate_sets",
+           "create_proof", "create_proof_multi", "verify_proof", "verify_proof_multi", "Blake2bWrite", "Blake2bRead", "pairing_check", "construct_intermediate_sets",
            "set_quotient", "set_quotient_ints", "MockProver", "MockResult", "NotSatisfied"]

@@ -469,6 +469,21 @@ int hm_graph_evaluate_flags_dev(uint64_t handle, const void* const* d_columns, s
  * unscaled.  segments = 1 is hm_graph_evaluate_flags_dev. */
 int hm_graph_evaluate_segments_dev(uint64_t handle, const void* const* d_columns, size_t n_columns, const uint64_t* dynamic_constants,
                                    size_t n_dynamic, uint32_t log_segment, uint32_t segments, void* d_values, uint32_t flags, void* stream);
+/* Several circuits of ONE constraint system in one launch: d_values holds PreviousValue on entry and, on return, word for word
+ * what `circuits` successive hm_graph_evaluate_segments_dev calls on the same d_values would leave, call c reading circuit c's
+ * columns.  Column i of circuit c starts column_strides[i] u32 words times c behind column_bases[i] (the convention of
+ * hm_mock_gates_dev); a stride of 0 names a column all circuits share (fixed, permutation, l_0 / l_last / l_active, the coset
+ * column, a short periodic column).  Both arrays are host memory; a base must be 16-byte aligned and a stride a multiple of 4
+ * words.  log_size, segments and flags as in hm_graph_evaluate_segments_dev; circuits * rows <= 2^32.
+ * The program must be linear in PreviousValue the way a Horner fold of gate polynomials is: PreviousValue is read exactly once,
+ * as the start of the MulAdd chain that ends in the last calculation; every step of that chain multiplies by the same constant
+ * (of the program or of the call) and is read by the next step only.  Its value is then Prev * f^T + G(row); the entry counts T
+ * on the program as it was created, raises f to it on the host, and folds acc = acc * f^T + G_c(row) over the circuits on the
+ * device, one lane per (circuit, row).  Any other program, circuits == 0, a misaligned base or stride, or counts other than the
+ * program's: HM_ERR_BAD_ARG, nothing launched. */
+int hm_graph_evaluate_circuits_dev(uint64_t handle, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
+                                   size_t circuits, const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t log_size, uint32_t segments,
+                                   void* d_values, uint32_t flags, void* stream);
 
 /* Inputs and known answer of the benchmark of SURVEY.md §8d, without leaving the device:
  *   hm_fr_random_dev           out[i] uniform in [0, r) (Fr::random): one xoshiro256** stream per element, seeded by

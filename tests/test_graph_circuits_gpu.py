@@ -1,0 +1,204 @@
+"""GPU suite of hm_graph_evaluate_circuits_dev: ``CompiledGraph.evaluate_circuits`` against the loop of
+``evaluate`` calls it replaces -- all words equal -- on the undivided evaluate_h program of the three circuits at k = 4 .. 6 (extended
+by 8: 128 .. 512 rows, less than one workgroup's rows up to several) and on a hand-made three-term program; 1, 2, 3, 5, 17 and 64
+circuits (an odd count ends in a partly filled group of circuits, 17 and 64 take more than one group), a non-zero PreviousValue on
+entry, one and two segments, both column formats, the short inverse-vanishing column present and shared.  All columns shared: the
+closed form Prev f^(T m) + G sum_i f^(T i) in Python integers.  Spot rows against oracle/graph_ref chained through PreviousValue.
+Every argument error, with the values untouched."""
+import ctypes
+import random
+
+import numpy as np
+import pytest
+import torch
+
+import graph_circuits_common as gc
+import graph_programs as gp
+import halo2_experiments_amd as h
+import prover_cases as pc
+from halo2_experiments_amd import _lib, circuits, evaluation as ev
+from halo2_experiments_amd.domain import FR_MODULUS as R, fr_words
+
+pytestmark = pytest.mark.gpu
+
+COUNTS = [1, 2, 3, 5, 17, 64]
+CIRCUITS = ["poseidon_k6", "merkle_v3_d5_k8", "merkle_sum_d5_k9"]          # the constraint systems; k is this file's own
+DELTA = pow(7, 1 << 28, R)
+
+
+def host(t):
+    torch.cuda.synchronize()
+    return t.cpu().numpy().view(np.uint64)
+
+
+# ---- the three circuits' evaluate_h numerator ---------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module", params=[(name, k) for name in CIRCUITS for k in (4, 5, 6)], ids=lambda p: f"{p[0]}-k{p[1]}")
+def numerator(request):
+    """the compiled program, 64 circuits' worth of random columns (the columns a circuit owns stacked, the others shared) and the
+    result of the loop of single evaluations after 1, 2, 3, 5, 17 and 64 circuits, per (segments, column format)"""
+    name, k = request.param
+    cs, _ = pc.constraint_system(name)
+    ek = k + 3
+    rows = 1 << ek
+    g, lay = circuits.evaluate_h_program(cs, k, ek, DELTA, divide=False)
+    n_cols = lay.num_fixed_entries + cs.num_advice + cs.num_instance
+    nsets, L = cs.permutation_sets(), len(cs.lookups)
+    own = set(range(lay.z0, lay.z0 + nsets)) | set(range(lay.lookup0, lay.lookup0 + 3 * L)) | set(range(lay.num_fixed_entries, n_cols))
+    assert lay.short_columns == {lay.t_inv: 3} and lay.t_inv not in own
+    m_max = max(COUNTS)
+    seed = 1000 * k + len(name)
+    cols = []
+    for i in range(n_cols):
+        if i in own:
+            cols.append(h.random_fr(m_max * rows, seed + i, "cuda", shape=(m_max, rows, 4)))
+        else:
+            cols.append(h.random_fr(8 if i == lay.t_inv else rows, seed + i, "cuda"))
+    rng = random.Random(seed)
+    scalars = dict(beta=rng.randrange(R), gamma=rng.randrange(R), theta=rng.randrange(R), y=rng.randrange(R))
+    prev = h.random_fr(rows, seed + 999, "cuda")
+    prog = g.compile(lay.num_fixed_entries, cs.num_advice, cs.num_instance, rot_scale=8, short_columns=lay.short_columns)
+    loop = {}
+    for segments in (1, 2):
+        for internal in (False, True):
+            values = prev.clone()
+            for c in range(m_max):
+                prog.evaluate([col[c] if i in own else col for i, col in enumerate(cols)], values, columns_internal=internal, segments=segments,
+                              **scalars)
+                if c + 1 in COUNTS:
+                    loop[(segments, internal, c + 1)] = host(values).copy()
+    yield dict(prog=prog, cols=cols, own=own, rows=rows, prev=prev, scalars=scalars, loop=loop)
+    prog.destroy()
+
+
+@pytest.mark.parametrize("m", COUNTS)
+def test_the_entry_equals_the_loop_of_single_evaluations(numerator, m):
+    c = numerator
+    for segments in (1, 2):
+        for internal in (False, True):
+            values = c["prev"].clone()
+            if internal:      # the strides named in words, the columns as circuit 0's
+                cols = [col[0] if i in c["own"] else col for i, col in enumerate(c["cols"])]
+                strides = [c["rows"] * 8 if i in c["own"] else 0 for i in range(len(cols))]
+            else:             # stacked tensors: the strides follow from the shapes
+                cols, strides = [col[:m] if i in c["own"] else col for i, col in enumerate(c["cols"])], None
+            c["prog"].evaluate_circuits(cols, strides, values, m, columns_internal=internal, segments=segments, **c["scalars"])
+            assert np.array_equal(host(values), c["loop"][(segments, internal, m)]), (m, segments, internal)
+
+
+# ---- the hand-made three-term program -----------------------------------------------------------------------------------------------------
+def device_stacked(cs, internal):
+    """-> (circuit 0's column per table entry, strides in words, the whole stacked tensors those are views of)"""
+    whole, strides = [], []
+    for words, stride in gc.stacked_words(cs, internal, repeat_one_row=False):
+        whole.append(gp.to_device(words))
+        strides.append(stride)
+    return [t[:stride // 8] if stride else t for t, stride in zip(whole, strides)], strides, whole
+
+
+@pytest.fixture(scope="module")
+def three():
+    p = gc.three_terms()
+    prog = p.compile()
+    yield p, prog
+    prog.destroy()
+
+
+@pytest.mark.parametrize("m", COUNTS)
+@pytest.mark.parametrize("seg,segments", [(64, 1), (256, 2), (2, 1)])
+def test_three_terms_against_the_loop(three, m, seg, segments):
+    p, prog = three
+    cs = gc.make_circuits(31 * m + seg, seg, segments, m, shared=(0,))
+    d0 = cs.data[0]
+    for internal in (False, True):
+        loop = gp.to_device(gp.words(d0.previous))
+        for d in cs.data:
+            prog.evaluate(gp.device_columns(d, internal), loop, columns_internal=internal, segments=segments, **d0.scalars())
+        keep, strides, whole = device_stacked(cs, internal)
+        values = gp.to_device(gp.words(d0.previous))
+        prog.evaluate_circuits(keep, strides, values, m, columns_internal=internal, segments=segments, **d0.scalars())
+        assert np.array_equal(host(values), host(loop)), (m, seg, segments, internal)
+
+
+def test_three_circuits_against_the_oracle_on_spot_rows(three):
+    p, prog = three
+    cs = gc.make_circuits(77, 64, 2, 3)
+    d0 = cs.data[0]
+    rows = [0, 1, 63, 64, 65, 100, 127]                                      # both ends of both segments: every rotation wraps somewhere
+    want = gp.words(gc.chained_oracle(p, cs, rows))
+    for internal in (False, True):
+        keep, strides, whole = device_stacked(cs, internal)
+        values = gp.to_device(gp.words(d0.previous))
+        prog.evaluate_circuits(keep, strides, values, 3, columns_internal=internal, segments=2, **d0.scalars())
+        assert np.array_equal(host(values)[rows], want), internal
+
+
+@pytest.mark.parametrize("m", [1, 3, 64])
+def test_identical_circuits_give_the_closed_form(three, m):
+    """every column at stride 0: Prev f^(T m) + G sum_{i < m} f^(T i), f = 7 and T = 3 for this program"""
+    p, prog = three
+    cs = gc.make_circuits(5, 64, 1, m, all_shared=True)
+    d0 = cs.data[0]
+    factor, steps = ev.linear_in_previous(p.lower()["calcs"])
+    f = p.lower()["constants"][factor & 0xFFFFF]
+    assert (f, steps) == (7, 3)
+    G = gp.oracle_values(p, d0, previous=[0] * d0.size)
+    ft = pow(f, steps, R)
+    geometric = sum(pow(ft, i, R) for i in range(m)) % R
+    want = [(prev * pow(ft, m, R) + g * geometric) % R for prev, g in zip(d0.previous, G)]
+    keep, strides, whole = device_stacked(cs, False)
+    assert strides == [0] * len(strides)
+    values = gp.to_device(gp.words(d0.previous))
+    prog.evaluate_circuits(keep, strides, values, m, **d0.scalars())
+    assert np.array_equal(host(values), gp.words(want))
+
+
+# ---- argument errors ------------------------------------------------------------------------------------------------------------------------
+def test_argument_errors_launch_nothing(three):
+    p, prog = three
+    lib = _lib.load()
+    fn = lib.hm_graph_evaluate_circuits_dev
+    cs = gc.make_circuits(3, 64, 1, 2)
+    d0 = cs.data[0]
+    keep, strides, whole = device_stacked(cs, False)
+    values = gp.to_device(gp.words(d0.previous))
+    before = host(values).copy()
+    sc = d0.scalars()
+    dyn = np.stack([fr_words(v) for v in list(sc["challenges"]) + [sc["beta"], sc["gamma"], sc["theta"], sc["y"]]])
+    dynp = dyn.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    n = len(keep)
+
+    def call(handle=prog.handle, ptrs=None, strd=None, n_columns=n, circuits=2, dyn_ptr=dynp, n_dyn=dyn.shape[0], log_size=6, segments=1,
+             vals=values.data_ptr(), flags=0, null_columns=False, null_strides=False):
+        ptrs = [t.data_ptr() for t in keep] if ptrs is None else ptrs
+        strd = strides if strd is None else strd
+        pa = None if null_columns else (ctypes.c_void_p * len(ptrs))(*ptrs)
+        sa = None if null_strides else (ctypes.c_uint64 * len(strd))(*strd)
+        rc = fn(ctypes.c_uint64(handle), pa, sa, n_columns, circuits, dyn_ptr, n_dyn, log_size, segments, ctypes.c_void_p(vals), flags, None)
+        assert np.array_equal(host(values), before), "the values changed"
+        return rc
+
+    BAD, NOT_FOUND = _lib.HM_ERR_BAD_ARG, _lib.HM_ERR_NOT_FOUND
+    assert call(null_columns=True) == BAD and call(null_strides=True) == BAD and call(dyn_ptr=None) == BAD and call(vals=None) == BAD
+    assert call(circuits=0) == BAD
+    # the same arguments without a fault are accepted (the last lines)
+    assert call(ptrs=[keep[0].data_ptr()] * 257, strd=[0] * 257, n_columns=257) == BAD                     # > GE_MAX_COLUMNS
+    assert call(ptrs=[keep[0].data_ptr() + 8] + [t.data_ptr() for t in keep[1:]]) == BAD                  # a base off 16 bytes
+    odd = list(strides)
+    odd[gp.NF] = 64 * 8 + 2
+    assert call(strd=odd) == BAD                                                                          # a stride off 4 words
+    assert call(circuits=(1 << 32) // 64 + 1) == BAD                                                      # circuits * rows > 2^32
+    assert call(circuits=(1 << 26) + 1, log_size=6, segments=1) == BAD
+    assert call(ptrs=[t.data_ptr() for t in keep[:-1]], strd=strides[:-1], n_columns=n - 1) == BAD        # another column count
+    assert call(n_dyn=dyn.shape[0] - 1) == BAD                                                            # another constant count
+    assert call(flags=2) == BAD and call(segments=0) == BAD
+    assert call(handle=1 << 40) == NOT_FOUND
+    for bad_program in gc.not_admitted():
+        other = bad_program.compile()
+        try:
+            assert call(handle=other.handle) == BAD, bad_program.name
+            assert b"graph:" in lib.hm_last_error()
+        finally:
+            other.destroy()
+    values2 = gp.to_device(gp.words(d0.previous))
+    prog.evaluate_circuits(keep, strides, values2, 2, **sc)
+    assert not np.array_equal(host(values2), before)

@@ -7,7 +7,12 @@
     hm_shplonk_set_quotient_bn256_fr_dev -- one call per rotation set into h, one for the final quotient -- against the same two
     polynomials composed from the kernels that existed before it: linear_combination, eval_polynomial, host interpolation, one
     kate_division per point.  The results are compared word for word; the commitments are left out of both.
+(c) ``--circuits m``: instead of (a) and (b), m users' MerkleSumTree witnesses at depth 20 / k = 10 and depth 5 / k = 9 (DESIGN.md section
+    19): create_proof_multi against m separate create_proof calls in the same run, and the h step alone -- the undivided numerator over
+    the extended domain through CompiledGraph.evaluate_circuits against the loop of m evaluate calls on the same columns (equal word for
+    word).
 Five repeats each: median and min .. max.  Prints one JSON object."""
+import argparse
 import json
 import os
 import random
@@ -26,6 +31,7 @@ from halo2_experiments_amd import circuits, poseidon as ps, prover, shplonk as s
 from halo2_experiments_amd.domain import FR_MODULUS as R, EvaluationDomain, fr_words   # noqa: E402
 from halo2_experiments_amd.kzg import ParamsKZG                            # noqa: E402
 import prover_cases as pc                                                  # noqa: E402
+import prover_multi_cases as pmc                                           # noqa: E402
 
 REPEATS = 5
 
@@ -68,6 +74,68 @@ def end_to_end(name):
         prover.create_opening = real
         params.release()
     return {"k": lay.k, "proof_bytes": len(proof), "create_proof": spread(prove), "of_which_shplonk": spread(inner), "verify_proof": spread(verify)}
+
+
+def h_step(cs, dom, m):
+    """the numerator of h for m circuits on random extended columns, laid out as create_proof_multi lays them out: what a circuit owns
+    stacked per circuit, the rest shared"""
+    from halo2_experiments_amd.keygen import FR_DELTA
+    g, lay = circuits.evaluate_h_program(cs, dom.k, dom.extended_k, FR_DELTA, divide=False)
+    en, scale = dom.extended_len(), 1 << (dom.extended_k - dom.k)
+    n_cols = lay.num_fixed_entries + cs.num_advice + cs.num_instance
+    nsets, L = cs.permutation_sets(), len(cs.lookups)
+    own = set(range(lay.z0, lay.z0 + nsets)) | set(range(lay.lookup0, lay.lookup0 + 3 * L)) | set(range(lay.num_fixed_entries, n_cols))
+    cols = [h.random_fr(m * en, 50 + i, shape=(m, en, 4)) if i in own else h.random_fr(scale if i == lay.t_inv else en, 50 + i) for i in range(n_cols)]
+    prev = h.random_fr(en, 49)
+    scalars = dict(beta=3, gamma=5, theta=7, y=11)
+    prog = g.compile(lay.num_fixed_entries, cs.num_advice, cs.num_instance, rot_scale=scale, short_columns=lay.short_columns)
+    per_circuit = [[col[c] if i in own else col for i, col in enumerate(cols)] for c in range(m)]
+
+    def loop():
+        values = prev.clone()
+        for c in range(m):
+            prog.evaluate(per_circuit[c], values, **scalars)
+        return values
+
+    def entry():
+        values = prev.clone()
+        prog.evaluate_circuits(cols, None, values, m, **scalars)
+        return values
+    try:
+        assert torch.equal(loop(), entry()), "the entry and the loop differ"
+        one, many = [], []
+        for _ in range(REPEATS):
+            many.append(wall(loop)[1])
+            one.append(wall(entry)[1])
+    finally:
+        prog.destroy()
+    return {"rows": en, "lanes": m * en, "program_calculations": int(prog.calcs.shape[0]), "evaluate_circuits": spread(one),
+            "loop_of_evaluate": spread(many)}
+
+
+def multi(name, m):
+    cs, lay, advice, instances = pmc.build_multi(name, m)
+    params = ParamsKZG.setup(lay.k, pc.SRS_S)
+    vk = h.keygen_vk(params, cs, lay)
+    pk = h.keygen_pk(params, vk, cs, lay, cosets=False)
+    try:
+        h.create_proof_multi(params, pk, advice, instances, 1)                 # warm-up
+        h.create_proof(params, pk, advice[0], instances[0], 1)
+        one, separate, verify = [], [], []
+        for rep in range(REPEATS):
+            proof, ms = wall(lambda: h.create_proof_multi(params, pk, advice, instances, 2 + rep))
+            one.append(ms)
+            _, ms = wall(lambda: [h.create_proof(params, pk, advice[c], instances[c], 2 + rep) for c in range(m)])
+            separate.append(ms)
+        for rep in range(2):
+            ok, ms = wall(lambda: h.verify_proof_multi(params, vk, instances, proof))
+            assert ok
+            verify.append(ms)
+        out = {"k": lay.k, "circuits": m, "proof_bytes": len(proof), "create_proof_multi": spread(one),
+               "separate_create_proof_calls": spread(separate), "verify_proof_multi": spread(verify), "h_step": h_step(cs, vk.domain, m)}
+    finally:
+        params.release()
+    return out
 
 
 def k18_sets():
@@ -143,7 +211,13 @@ def multiopen_k18():
 
 
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--circuits", type=int, default=0, help="m: time create_proof_multi and the h step for m circuits (1 .. 64) instead")
+    args = ap.parse_args()
     torch.cuda.init()
+    if args.circuits:
+        print(json.dumps({name: multi(name, args.circuits) for name in ("merkle_sum_d20_k10", "merkle_sum_d5_k9")}))
+        sys.exit(0)
     out = {"merkle_sum_d5_k9": end_to_end("merkle_sum_d5_k9"), "merkle_sum_d20_k10": end_to_end("merkle_sum_d20_k10"),
            "multiopen_k18": multiopen_k18()}
     print(json.dumps(out))
