@@ -1,0 +1,729 @@
+"""``halo2_proofs::plonk::BatchVerifier`` (``plonk/verifier/batch.rs``; RECALLED from upstream, not pinned against its source: the idea is
+mirrored, not the bytes): many proofs of ONE verifying key are checked with ONE pairing.  Proof b leaves two G1 points (h2_b, R_b) with
+e(h2_b, [s]G2) = e(R_b, G2) -- what ``shplonk.verify_opening`` returns; with a random weight r_b per proof the batch checks
+
+    e(sum_b r_b h2_b, [s]G2) = e(sum_b r_b R_b, G2)
+
+which a batch holding a proof that fails passes with probability 1 / r.  Scope: single-circuit proofs (``create_proof``) of one ``vk``;
+a batch of ``create_proof_multi`` proofs is out of scope.
+
+Where the work is done:
+
+  - the device reads the proofs (``hm_verify_read_proofs_dev``, csrc/verify_read.inc): one lane per (proof, 32-byte slot) decompresses a
+    point -- one square root -- or checks a scalar < r.  Every point position is known from the constraint system (``ProofLayout``),
+    so all points are decompressed before any challenge exists;
+  - the host runs the Blake2b transcript of every proof with ``hashlib``, in the order of ``verifier._verify`` / ``verify_opening``, on
+    the proof's own x bytes and the y bytes the device returned: theta, beta, gamma, y, x, the multiopen's y', v, u -- one record per
+    proof, uploaded with its weight r_b;
+  - the device computes, one lane per proof (``hm_verify_terms_dev``, csrc/verify_terms.inc, driven by a ``TermsPlan``), x^n, l0, l_last,
+    l_active and the instance columns' evaluations at x, the numerator by the ``GraphEvaluator`` interpreter on the proof's value row,
+    h(x), and per rotation set the multiopen's scalars: r_b x the scalar of every point (``terms_from_challenges`` is the integer twin;
+    the rotation sets are taken symbolically on ROTATIONS, see ``ProofLayout``).  An instance column may have 64 rows at most;
+  - the device sums: every proof's own points (advice, lookup, permutation, random, h pieces, [h]) lie in one array, behind them the
+    points all proofs share (fixed and sigma commitments, the generator; their scalars are the column sums of a (B, shared) array,
+    ``hm_verify_column_sum_dev``), behind them the [h'] of every proof; the array is registered once as a plain base set and the sums are
+    MSMs over offsets into it, folded with ``hm_g1_sum``;
+  - one ``pairing.pairing_check`` (or, with the trapdoor, s * L == R in G1).
+
+``proof_terms_ints`` is the integer twin of the whole per-proof part, ``read_proof_ints`` of the read kernel; neither needs a device.
+
+Two places where the symbolic form answers differently from ``verify_proof``, each of probability about 2^-254 for an honest or a
+dishonest prover alike (x is a hash output): x = 0, where all rotations of x coincide, is reported as a failing proof; and h pieces whose
+combination sum_i x^(n i) [h_i] is the identity are summed as they are, where ``verify_proof`` refuses to open the identity."""
+from __future__ import annotations
+
+import ctypes
+import hashlib
+import secrets
+import time
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib, evaluation as ev
+from .bn256 import FQ_MODULUS, FR_MODULUS, fr_array, g1_words
+from .keygen import FR_DELTA, VerifyingKey
+from .kzg import g2_from_bytes
+from .pairing import G1_GEN, g1_mul, g1_neg, g1_on_curve, pairing_check
+from .shplonk import g1_words_to_int
+from .transcript import PERSONAL, PREFIX_CHALLENGE, PREFIX_POINT, PREFIX_SCALAR, TranscriptError, g1_decompress_int
+from .verifier import _instance_columns, _vk_digest, evaluate_expression, proof_length
+
+R, P = FR_MODULUS, FQ_MODULUS
+VR_POINT, VR_TAIL = 1 << 31, 1 << 30          # csrc/verify_read.inc: the slot table's bits
+
+
+class MalformedProof(ValueError):
+    """What ``verify_proof`` answers False to on structural grounds: a wrong length, a scalar >= r, an x >= p or off the curve, an
+    all-zero point, x^n = 1 (and x = 0, see the module's note)."""
+
+
+# ---- what a constraint system fixes: the slots of a proof, its queries and its rotation sets ---------------------------------------------
+class ProofLayout:
+    """Everything about a single-circuit proof that the constraint system and n = 2^k fix, built once per ``vk``:
+
+      ``point_keys``   the commitments in the order the proof holds them: advice, lookup a' / s', permutation z, lookup z, random, the
+                       h pieces, then -- behind the evaluations -- [h] and [h'].  All but the last are the proof's OWN points.
+      ``eval_keys``    (commitment key, rotation mod n) of the evaluations, in the proof's order.
+      ``slot_table``   one u32 per 32-byte slot as ``hm_verify_read_proofs_dev`` takes it.
+      ``sets``         the rotation sets of the multiopen, [(rotations, [commitment keys])], and ``super_rotations``: grouping and order
+                       of first appearance as ``shplonk.construct_intermediate_sets`` finds them on the real points x * omega^rotation.
+                       Two rotations give one point exactly when they agree mod n (x != 0), so the sets need no challenge; inside a set
+                       the points stand in ascending ROTATION here and in ascending integer order there, which changes no scalar.
+      ``shared_keys``  the points all proofs share: the fixed commitments, the sigma commitments, the generator."""
+
+    def __init__(self, cs, k: int):
+        self.cs, self.k, self.n = cs, k, 1 << k
+        n = self.n
+        adv_q, fix_q, _ = cs.queries()
+        self.P, self.nsets, self.L = len(cs.equality), cs.permutation_sets(), len(cs.lookups)
+        P_, nsets, L = self.P, self.nsets, self.L
+        self.pieces = cs.degree() - 1
+        self.last = -(cs.blinding_factors + 1)
+        last = self.last
+        pts = [("advice", i) for i in range(cs.num_advice)]
+        for j in range(L):
+            pts += [("lookup_a", j), ("lookup_s", j)]
+        pts += [("perm_z", i) for i in range(nsets)] + [("lookup_z", j) for j in range(L)] + [("random",)]
+        pts += [("h_piece", i) for i in range(self.pieces)]
+        self.points_before_evals = len(pts)
+        evs = [(("advice", i), r % n) for i, r in adv_q] + [(("fixed", i), r % n) for i, r in fix_q] + [(("random",), 0)]
+        evs += [(("sigma", j), 0) for j in range(P_)]
+        for i in range(nsets):
+            evs += [(("perm_z", i), r % n) for r in (0, 1) + ((last,) if i + 1 < nsets else ())]
+        for j in range(L):
+            evs += [((kd, j), r % n) for kd, r in (("lookup_z", 0), ("lookup_z", 1), ("lookup_a", 0), ("lookup_a", -1), ("lookup_s", 0))]
+        self.point_keys = pts + [("h1",), ("h2",)]
+        self.eval_keys = evs
+        self.eval_index = {}
+        for at, key in enumerate(evs):
+            self.eval_index.setdefault(key, at)
+        self.n_points, self.own_points, self.n_scalars = len(self.point_keys), len(self.point_keys) - 1, len(evs)
+        self.slots = self.n_points + self.n_scalars
+        if 32 * self.slots != proof_length(cs):
+            raise AssertionError("ProofLayout: the slots do not add up to proof_length")
+        table = [VR_POINT | i for i in range(self.points_before_evals)] + list(range(self.n_scalars))
+        table += [VR_POINT | (self.n_points - 2), VR_POINT | VR_TAIL | (self.n_points - 1)]
+        self.slot_table = np.array(table, dtype=np.uint32)
+        self.point_slots = [s for s, e in enumerate(table) if e & VR_POINT]
+        self.scalar_slots = [s for s, e in enumerate(table) if not e & VR_POINT]
+
+        # the queries in the order verifier._verify lists them; ("h",) stands for sum_i x^(n i) [h_i]
+        q = [(("advice", i), r % n) for i, r in adv_q]
+        q += [qq for i in range(nsets) for qq in ((("perm_z", i), 0), (("perm_z", i), 1))]
+        q += [(("perm_z", i), last % n) for i in reversed(range(nsets - 1))]
+        for j in range(L):
+            q += [(("lookup_z", j), 0), (("lookup_a", j), 0), (("lookup_s", j), 0), (("lookup_a", j), (-1) % n), (("lookup_z", j), 1)]
+        q += [(("fixed", i), r % n) for i, r in fix_q] + [(("sigma", j), 0) for j in range(P_)]
+        q += [(("h",), 0), (("random",), 0)]
+        self.queries = q
+        by_key: dict = {}
+        for key, rot in q:
+            by_key.setdefault(key, [])
+            if rot not in by_key[key]:
+                by_key[key].append(rot)
+        sets: List[Tuple[tuple, list]] = []
+        for key, rots in by_key.items():
+            rots_t = tuple(sorted(rots))
+            for have, keys in sets:
+                if have == rots_t:
+                    keys.append(key)
+                    break
+            else:
+                sets.append((rots_t, [key]))
+        self.sets = [(list(rots), keys) for rots, keys in sets]
+        self.super_rotations = sorted({rot for _, rot in q})
+        self.shared_keys = [("fixed", c) for c in range(cs.num_fixed)] + [("sigma", j) for j in range(P_)] + [("g",)]
+        self.shared_index = {key: i for i, key in enumerate(self.shared_keys)}
+        self.own_index = {key: i for i, key in enumerate(self.point_keys)}
+
+        # the expressions of the identity, in the prover's order (verifier._verify builds the same list)
+        nf = cs.num_fixed
+        self.sigma0, self.z0 = nf, nf + P_
+        z0 = self.z0
+        self.i_l0, self.i_last, self.i_active, self.i_x, self.lookup0 = z0 + nsets, z0 + nsets + 1, z0 + nsets + 2, z0 + nsets + 3, z0 + nsets + 4
+        F = ev.Fixed
+        kind = {"advice": ev.Advice, "fixed": ev.Fixed, "instance": ev.Instance}
+        exprs = list(cs.polynomials())
+        exprs += ev.permutation_expressions([kind[kd](i) for kd, i in cs.equality], [F(self.sigma0 + j) for j in range(P_)],
+                                            [lambda r, i=i: F(z0 + i, r) for i in range(nsets)], F(self.i_l0), F(self.i_last),
+                                            F(self.i_active), F(self.i_x), cs.permutation_chunk_len(), FR_DELTA, last)
+        for j, (ins, tabs) in enumerate(cs.lookups):
+            b = self.lookup0 + 3 * j
+            exprs += ev.lookup_expressions(ins, tabs, lambda r, b=b: F(b, r), lambda r, b=b: F(b + 1, r), lambda r, b=b: F(b + 2, r),
+                                           F(self.i_l0), F(self.i_last), F(self.i_active))
+        self.exprs = exprs
+
+
+def read_proof_ints(layout: ProofLayout, proof: bytes):
+    """The integer twin of the read kernel: (points, scalars) of ``proof`` in the layout's order -- points as (x, y) -- or
+    ``MalformedProof`` for a wrong length, a scalar >= r, an x >= p or off the curve, the all-zero point."""
+    if len(proof) != 32 * layout.slots:
+        raise MalformedProof("the proof has the wrong length")
+    points, scalars = [], []
+    for s in range(layout.slots):
+        data = proof[32 * s:32 * s + 32]
+        if layout.slot_table[s] & VR_POINT:
+            try:
+                p = g1_decompress_int(data)
+            except TranscriptError as e:
+                raise MalformedProof(str(e)) from None
+            if p is None:
+                raise MalformedProof("point: the identity cannot be absorbed")
+            points.append(p)
+        else:
+            v = int.from_bytes(data, "little")
+            if v >= R:
+                raise MalformedProof("scalar: not below r")
+            scalars.append(v)
+    return points, scalars
+
+
+def transcript_challenges(layout: ProofLayout, vk_digest: int, inst_cols, proof: bytes, y_bytes: Sequence[bytes]) -> dict:
+    """The Blake2b transcript of one proof, absorbed in the order of ``verifier._verify`` and ``shplonk.verify_opening``:
+    ``y_bytes[j]`` the 32 canonical bytes of y of the proof's point j (x stands in the proof).  -> theta, beta, gamma, y, x and the
+    multiopen's y' (``y2``), v, u."""
+    st = hashlib.blake2b(digest_size=64, person=PERSONAL)
+    slot = [0]
+    point = [0]
+
+    def scalar(v: int) -> None:
+        st.update(PREFIX_SCALAR + v.to_bytes(32, "little"))
+
+    def points(count: int) -> None:
+        for _ in range(count):
+            at = 32 * slot[0]
+            st.update(PREFIX_POINT + proof[at:at + 31] + bytes([proof[at + 31] & 0x7F]) + y_bytes[point[0]])
+            slot[0] += 1
+            point[0] += 1
+
+    def squeeze() -> int:
+        st.update(PREFIX_CHALLENGE)
+        return int.from_bytes(st.copy().digest(), "little") % R
+
+    cs = layout.cs
+    scalar(vk_digest)
+    for values in inst_cols:
+        for v in values:
+            scalar(v)
+    ch = {}
+    points(cs.num_advice)
+    ch["theta"] = squeeze()
+    points(2 * layout.L)
+    ch["beta"] = squeeze()
+    ch["gamma"] = squeeze()
+    points(layout.nsets + layout.L + 1)
+    ch["y"] = squeeze()
+    points(layout.pieces)
+    ch["x"] = squeeze()
+    for _ in range(layout.n_scalars):
+        at = 32 * slot[0]
+        st.update(PREFIX_SCALAR + proof[at:at + 32])
+        slot[0] += 1
+    ch["y2"] = squeeze()
+    ch["v"] = squeeze()
+    points(1)
+    ch["u"] = squeeze()
+    return ch
+
+
+def terms_from_challenges(layout: ProofLayout, omega: int, inst_cols, evals: Sequence[int], ch: dict, details: Optional[dict] = None):
+    """The scalars of one proof's R = sum own[j] * (point j of the proof) + sum shared[i] * (shared point i), from its evaluations (in
+    the proof's order) and its challenges: ``own`` has one entry per point of ``layout.point_keys`` ([h'] last, with u), ``shared`` one
+    per ``layout.shared_keys``.  ``MalformedProof`` when x^n = 1 (or x = 0).  ``details``, when given, receives what the device keeps in
+    its value row: l0, l_last, l_active, the instance evaluations by (column, rotation), the numerator and h(x)."""
+    cs, n = layout.cs, layout.n
+    x, y = ch["x"], ch["y"]
+    xn = pow(x, n, R)
+    if xn == 1 or x == 0:
+        raise MalformedProof("x^n = 1: the quotient cannot be taken" if x else "x = 0")
+    wpow = lambda r: pow(omega, r % n, R)
+    n_inv = pow(n, -1, R)
+    zh = (xn - 1) * n_inv % R                                    # (point^n - 1) / n, the same for every rotation of x
+
+    def lagrange_at(i: int, rot: int) -> int:                     # l_i(x omega^rot): never a zero denominator, since x^n != 1
+        w = wpow(i)
+        return w * zh % R * pow(x * wpow(rot) - w, -1, R) % R
+
+    blinding = cs.blinding_factors
+    l0, l_last = lagrange_at(0, 0), lagrange_at(n - blinding - 1, 0)
+    l_blind = sum(lagrange_at(i, 0) for i in range(n - blinding, n)) % R
+    l_active = (1 - l_last - l_blind) % R
+    special = {layout.i_l0: l0, layout.i_last: l_last, layout.i_active: l_active, layout.i_x: x}
+    ev_at = lambda key, r: evals[layout.eval_index[(key, r % n)]]
+    nf = cs.num_fixed
+
+    def leaf(kind: str, column: int, r: int) -> int:
+        if kind == "instance":
+            value = sum(v * lagrange_at(i, r) for i, v in enumerate(inst_cols[column]) if v) % R
+            if details is not None:
+                details.setdefault("instance", {})[(column, r % n)] = value
+            return value
+        if kind == "advice":
+            return ev_at(("advice", column), r)
+        if column < nf:
+            return ev_at(("fixed", column), r)
+        if column in special:
+            return special[column]
+        if column < layout.z0:
+            return ev_at(("sigma", column - layout.sigma0), r)
+        if column < layout.i_l0:
+            return ev_at(("perm_z", column - layout.z0), r)
+        j, part = divmod(column - layout.lookup0, 3)
+        return ev_at((("lookup_z", "lookup_a", "lookup_s")[part], j), r)
+
+    scalars = {"Beta": ch["beta"], "Gamma": ch["gamma"], "Theta": ch["theta"]}
+    acc = 0
+    for e in layout.exprs:
+        acc = (acc * y + evaluate_expression(e, leaf, scalars)) % R
+    hx = acc * pow(xn - 1, -1, R) % R
+    if details is not None:
+        details.update(l0=l0, l_last=l_last, l_active=l_active, numerator=acc, hx=hx)
+
+    # ---- the multiopen's scalars, per rotation set ---------------------------------------------------------------------------------
+    y2, v, u = ch["y2"], ch["v"], ch["u"]
+    pt = {rot: x * wpow(rot) % R for rot in layout.super_rotations}
+    diff = {rot: (u - p) % R for rot, p in pt.items()}            # u - point; zero only when u hits a point
+    zt = 1
+    for d in diff.values():
+        zt = zt * d % R
+    own, shared = [0] * layout.n_points, [0] * len(layout.shared_keys)
+    r_outer, z0_inv, v_i = 0, None, 1
+    for i, (rots, keys) in enumerate(layout.sets):
+        z_i = 1
+        for rot in layout.super_rotations:
+            if rot not in rots:
+                z_i = z_i * diff[rot] % R
+        if i == 0:
+            if z_i == 0:
+                raise MalformedProof("u is a point of the opening")
+            z0_inv, z_i = pow(z_i, -1, R), 1
+        else:
+            z_i = z_i * z0_inv % R
+        outer = v_i * z_i % R
+        v_i = v_i * v % R
+        basis = []                                                # the Lagrange basis of the set's points at u
+        for l, rl in enumerate(rots):
+            num = den = 1
+            for m, rm in enumerate(rots):
+                if m != l:
+                    num = num * diff[rm] % R
+                    den = den * (pt[rl] - pt[rm]) % R
+            basis.append(num * pow(den, -1, R) % R)
+        yj = 1
+        for key in keys:
+            coeff = outer * yj % R
+            yj = yj * y2 % R
+            values = [hx] if key == ("h",) else [ev_at(key, rot) for rot in rots]
+            r_outer = (r_outer + coeff * sum(b * e for b, e in zip(basis, values))) % R
+            if key == ("h",):
+                xp = 1
+                for piece in range(layout.pieces):
+                    own[layout.own_index[("h_piece", piece)]] = coeff * xp % R
+                    xp = xp * xn % R
+            elif key in layout.shared_index:
+                shared[layout.shared_index[key]] = coeff
+            else:
+                own[layout.own_index[key]] = coeff
+    shared[layout.shared_index[("g",)]] = -r_outer % R
+    own[layout.own_index[("h1",)]] = -z0_inv * zt % R
+    own[layout.own_index[("h2",)]] = u
+    return own, shared
+
+
+# ---- the plan of the terms kernel (csrc/verify_terms.inc) ---------------------------------------------------------------------------------
+VT_NO_SLOT, VT_T_SHARED, VT_T_H = 0xFFFFFFFF, 1 << 31, 1 << 30
+VT_MAX_VALS, VT_MAX_INST_ROWS, VT_MAX_SUPER, VT_MAX_T = 256, 64, 32, 8
+RECORD = ("theta", "beta", "gamma", "y", "x", "y2", "v", "u")          # then r_b: the per-proof record of hm_verify_terms_dev
+
+
+def _internal_words(v: int) -> List[int]:
+    """the 9 limbs of 29 bits of v * 2^261 mod r: a constant as the kernels hold it"""
+    m = v % R * (1 << 261) % R
+    return [(m >> (29 * i)) & 0x1FFFFFFF for i in range(9)]
+
+
+class TermsPlan:
+    """What ``hm_verify_terms_dev`` needs beside the proofs, built once per constraint system and instance shape: the program of the
+    gate, permutation and lookup expressions folded in y -- ``layout.exprs`` through ``GraphEvaluator.add_custom_gates``, lowered from
+    the constraint system alone, undivided, with beta, gamma, theta, y as per-call constants (``lowered``: the arguments of
+    ``hm_graph_create``) -- and the plan words (``words``; csrc/verify_terms.inc states the layout): where a (column, rotation) of the
+    program stands in a proof's value row, the instance queries, the rotation sets on rotations, the constants in internal form.
+    ``inst_rows[c]``: the rows given of instance column c (at most 64).  Needs no device."""
+
+    def __init__(self, layout: ProofLayout, omega: int, inst_rows: Sequence[int]):
+        cs, n = layout.cs, layout.n
+        inst_rows = [int(r) for r in inst_rows]
+        if len(inst_rows) != cs.num_instance:
+            raise ValueError(f"TermsPlan: {cs.num_instance} instance column(s) expected")
+        if any(r > VT_MAX_INST_ROWS for r in inst_rows):
+            raise ValueError(f"TermsPlan: an instance column longer than {VT_MAX_INST_ROWS} rows")
+        g = ev.GraphEvaluator()
+        g.add_custom_gates(layout.exprs)
+        num_fixed = layout.lookup0 + 3 * layout.L
+        self.lowered = g.lower(num_fixed, cs.num_advice, cs.num_instance)
+        rotations, n_cols = list(g.rotations), self.lowered["n_columns"]
+        n_rot = max(len(rotations), 1)
+        used = set()                                              # the (column, rotation index) pairs the program reads
+        for op, a, b, c, _ in self.lowered["calcs"].tolist():
+            for s in (a, b, c)[:3 if op == 7 else 2 if op <= 2 else 1]:
+                if s >> 30 == 2:
+                    used.add((s & 0x3FFF, (s >> 20) & 1023))
+        s_l0 = layout.n_scalars
+        s_inst = s_l0 + 4
+        inst_first = num_fixed + cs.num_advice
+        inst_queries = sorted((col - inst_first, rotations[ri] % n) for col, ri in used if col >= inst_first)
+        inst_queries = sorted(set(inst_queries))
+        s_hx = s_inst + len(inst_queries)
+        n_vals = s_hx + 1
+        if n_vals > VT_MAX_VALS:
+            raise ValueError(f"TermsPlan: more than {VT_MAX_VALS} value slots")
+        if len(layout.super_rotations) > VT_MAX_SUPER or any(len(rots) > VT_MAX_T for rots, _ in layout.sets):
+            raise ValueError("TermsPlan: more rotations than the kernel's workspace holds")
+
+        def slot_of(col: int, rot: int) -> int:
+            if col >= inst_first:
+                return s_inst + inst_queries.index((col - inst_first, rot))
+            if col >= num_fixed:
+                return layout.eval_index[(("advice", col - num_fixed), rot)]
+            if col < cs.num_fixed:
+                return layout.eval_index[(("fixed", col), rot)]
+            if layout.i_l0 <= col <= layout.i_x:
+                return s_l0 + col - layout.i_l0
+            if col < layout.z0:
+                return layout.eval_index[(("sigma", col - layout.sigma0), rot)]
+            if col < layout.i_l0:
+                return layout.eval_index[(("perm_z", col - layout.z0), rot)]
+            j, part = divmod(col - layout.lookup0, 3)
+            return layout.eval_index[((("lookup_z", "lookup_a", "lookup_s")[part], j), rot)]
+
+        colmap = [VT_NO_SLOT] * (n_cols * n_rot)
+        for col, ri in used:
+            colmap[col * n_rot + ri] = slot_of(col, rotations[ri] % n)
+
+        consts: List[int] = [pow(n, -1, R)]
+
+        def const(v: int) -> int:
+            consts.append(v % R)
+            return len(consts) - 1
+
+        w = lambda e: pow(omega, e % n, R)
+        blinding = cs.blinding_factors
+        lagrange_rows = [0, n - blinding - 1] + list(range(n - blinding, n))
+        c_lagrange = len(consts)
+        for i in lagrange_rows:
+            const(w(i))
+        c_rows = len(consts)
+        for i in range(max(inst_rows, default=0)):
+            const(w(i))
+        c_super = len(consts)
+        for rot in layout.super_rotations:
+            const(w(rot))
+        inst_off = [sum(inst_rows[:c]) for c in range(cs.num_instance)]
+        inst_words: List[int] = []
+        for col, rot in inst_queries:
+            inst_words += [inst_off[col], inst_rows[col], const(w(rot))]
+        set_words: List[int] = []
+        for rots, keys in layout.sets:
+            sup = [layout.super_rotations.index(r) for r in rots]
+            dinv = []
+            for rl in rots:                                       # 1 / prod_{m != l} (omega^r_l - omega^r_m); the x^(t-1) is the lane's
+                den = 1
+                for rm in rots:
+                    if rm != rl:
+                        den = den * (w(rl) - w(rm)) % R
+                dinv.append(const(pow(den, -1, R)))
+            set_words += [len(rots), sum(1 << s for s in sup), len(keys)] + sup + dinv
+            for key in keys:
+                if key == ("h",):
+                    if len(rots) != 1:
+                        raise AssertionError("TermsPlan: h is opened at x alone")
+                    set_words += [VT_T_H | layout.own_index[("h_piece", 0)], s_hx]
+                elif key in layout.shared_index:
+                    set_words += [VT_T_SHARED | layout.shared_index[key]] + [layout.eval_index[(key, r)] for r in rots]
+                else:
+                    set_words += [layout.own_index[key]] + [layout.eval_index[(key, r)] for r in rots]
+        header = 24
+        off_colmap = header
+        off_inst = off_colmap + len(colmap)
+        off_sets = off_inst + len(inst_words)
+        off_consts = off_sets + len(set_words)
+        head = [layout.k, layout.n_scalars, n_vals, len(lagrange_rows), len(inst_queries), len(layout.super_rotations), len(layout.sets),
+                layout.pieces, layout.own_points, len(layout.shared_keys), n_rot, n_cols, off_colmap, off_inst, off_sets, sum(inst_rows),
+                c_lagrange, c_rows, c_super, s_l0, s_inst, s_hx, len(consts), off_consts]
+        assert len(head) == header
+        body = head + colmap + inst_words + set_words + [limb for v in consts for limb in _internal_words(v)]
+        self.words = np.array(body, dtype=np.uint32)
+        self.inst_rows, self.inst_queries, self.n_vals, self.n_columns = inst_rows, inst_queries, n_vals, n_cols
+        self.s_l0, self.s_inst, self.s_hx = s_l0, s_inst, s_hx
+        self.inst_elems = max(sum(inst_rows), 1)                  # the instance array is never empty: one zero element at least
+
+    def instance_row(self, inst_cols) -> List[int]:
+        """one proof's instance values as the kernel reads them: column after column, every column padded to the plan's rows"""
+        row: List[int] = []
+        for values, rows in zip(inst_cols, self.inst_rows):
+            if len(values) > rows:
+                raise ValueError("TermsPlan: an instance column longer than the plan's")
+            row += list(values) + [0] * (rows - len(values))
+        return row or [0]
+
+
+def proof_terms_ints(vk: VerifyingKey, instance, proof: bytes, layout: Optional[ProofLayout] = None):
+    """The integer twin of the per-proof part, without r_b: (challenges, own scalars, shared scalars, points) of one proof in the device
+    layout -- sum own[j] * points[j] + sum shared[i] * (shared point i) is the R of ``verify_opening`` and points[-1] its L.  Raises
+    ``MalformedProof`` where ``verify_proof`` is False on structural grounds."""
+    layout = layout or ProofLayout(vk.cs, vk.domain.k)
+    inst_cols = _instance_columns(vk.cs, instance)
+    points, evals = read_proof_ints(layout, proof)
+    ch = transcript_challenges(layout, _vk_digest(vk), inst_cols, proof, [p[1].to_bytes(32, "little") for p in points])
+    own, shared = terms_from_challenges(layout, vk.domain.omega, inst_cols, evals, ch)
+    return ch, own, shared, points
+
+
+def shared_points(vk: VerifyingKey, layout: ProofLayout):
+    """the (x, y) points of ``layout.shared_keys``; None for a commitment that is the identity"""
+    return [g1_words_to_int(c) for c in vk.fixed_commitments] + [g1_words_to_int(c) for c in vk.permutation_commitments] + [G1_GEN]
+
+
+def derive_randomizer(seed, index: int) -> int:
+    """r_b in [1, r) from (seed, index) by Blake2b: the same seed gives the same weights"""
+    raw = seed if isinstance(seed, (bytes, bytearray)) else str(seed).encode()
+    d = hashlib.blake2b(bytes(raw) + index.to_bytes(8, "little"), digest_size=64, person=b"Halo2-BatchRand").digest()
+    return int.from_bytes(d, "little") % (R - 1) + 1
+
+
+# ---- the public object ---------------------------------------------------------------------------------------------------------------------
+class BatchVerifier:
+    """Collects single-circuit proofs of one ``vk`` and checks them together (the module's docstring says how).
+
+    ``params`` needs ``g2`` / ``s_g2`` only.  ``add_proof(instance, proof)`` takes what ``verify_proof`` takes and returns the proof's
+    index.  ``finalize(trapdoor=None)`` is True when every added proof verifies -- one pairing check for the whole batch, or with the
+    trapdoor s * L == R in G1; an empty batch is True.  A malformed proof (wrong length, a scalar >= r, an x >= p or off the curve, an
+    all-zero point, x^n = 1) makes ``finalize`` False and is kept out of the sums; it raises nothing.  ``failing(trapdoor=None)`` names
+    the proofs that do not verify: the malformed ones, and among the others those found by bisection -- each step sums a contiguous
+    sub-range of the batch on the device and makes one check, O(f log B) checks for f failing proofs.  Every proof has a weight r_b in
+    [1, r): from ``secrets`` when ``seed`` is None, else derived from (seed, index); ``randomizers`` shows them.
+    A batch of ``create_proof_multi`` proofs is out of scope, and an instance column may hold 64 rows at most (the terms kernel's
+    limit; ``finalize`` raises ValueError beyond it).  ``close()`` gives the numerator's program back to the library."""
+
+    def __init__(self, params, vk: VerifyingKey, seed=None):
+        self.params, self.vk, self.seed = params, vk, seed
+        self.layout = ProofLayout(vk.cs, vk.domain.k)
+        self._digest = _vk_digest(vk)
+        self._shared = shared_points(vk, self.layout)
+        # verify_proof opens no identity: with a queried fixed or sigma commitment that is one, no proof of this vk verifies
+        self._vk_ok = all(self._shared[self.layout.shared_index[key]] is not None for key, _ in self.layout.queries
+                          if key in self.layout.shared_index)
+        self._proofs: List[bytes] = []
+        self._instances: list = []
+        self._rand: List[int] = []
+        self._state = None
+        self._plans: dict = {}                                   # instance shape -> TermsPlan (the program is the same for all)
+        self._program = None                                     # the hm_graph_create program of the numerator, made on first use
+        self.msm_calls = 0                                       # MSMs launched so far (tests, tools/batch_verify_time.py)
+        self.timings: dict = {}                                  # seconds of the last preparation and check, by phase
+
+    def __len__(self) -> int:
+        return len(self._proofs)
+
+    @property
+    def randomizers(self) -> Tuple[int, ...]:
+        return tuple(self._rand)
+
+    def add_proof(self, instance, proof: bytes) -> int:
+        self._instances.append(_instance_columns(self.vk.cs, instance))
+        self._proofs.append(bytes(proof))
+        i = len(self._proofs) - 1
+        self._rand.append(secrets.randbelow(R - 1) + 1 if self.seed is None else derive_randomizer(self.seed, i))
+        self._state = None
+        return i
+
+    def malformed(self) -> List[int]:
+        """The indices the HOST pre-checks refuse, without a device: the integer twins of the read kernel and of the terms."""
+        out = []
+        for b, (inst, proof) in enumerate(zip(self._instances, self._proofs)):
+            try:
+                proof_terms_ints(self.vk, inst, proof, self.layout)
+            except MalformedProof:
+                out.append(b)
+        return out
+
+    # ---- the device part ------------------------------------------------------------------------------------------------------------------
+    def _plan_for(self, inst_rows: Sequence[int]) -> "TermsPlan":
+        key = tuple(inst_rows)
+        if key not in self._plans:
+            self._plans[key] = TermsPlan(self.layout, self.vk.domain.omega, inst_rows)
+        if self._program is None:
+            self._program = ev.CompiledGraph(**self._plans[key].lowered)
+        return self._plans[key]
+
+    def close(self) -> None:
+        """give the numerator's program back to the library (also done when the object is collected)"""
+        if self._program is not None:
+            program, self._program = self._program, None
+            program.destroy()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                        # the library may be gone at interpreter shutdown
+            pass
+
+    def _prepare(self) -> dict:
+        if self._state is not None:
+            return self._state
+        import torch
+
+        lay, B = self.layout, len(self._proofs)
+        lib, dev = _lib.load(), torch.device("cuda", torch.cuda.current_device())
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        t0 = time.perf_counter()
+        bad = [len(p) != 32 * lay.slots for p in self._proofs] if self._vk_ok else [True] * B
+        raw = np.zeros((B, 32 * lay.slots), dtype=np.uint8)
+        for b, p in enumerate(self._proofs):
+            if len(p) == 32 * lay.slots:
+                raw[b] = np.frombuffer(p, dtype=np.uint8)
+        n_shared, own = len(lay.shared_keys), lay.own_points
+        d_proofs = torch.from_numpy(raw).to(dev)
+        d_table = torch.from_numpy(lay.slot_table.view(np.int32)).to(dev)     # uploaded once per batch: a device table, not a kernel argument
+        d_bases = torch.zeros((B * own + n_shared + B, 8), dtype=torch.int64, device=dev)
+        d_ybytes = torch.zeros((B, lay.n_points, 32), dtype=torch.uint8, device=dev)
+        d_scalars = torch.zeros((B, lay.n_scalars, 4), dtype=torch.int64, device=dev)
+        d_bad = torch.zeros(B, dtype=torch.int32, device=dev)
+        d_tail = d_bases[B * own + n_shared:]
+        _lib.check(lib.hm_verify_read_proofs_dev(vp(d_proofs), B, ctypes.cast(vp(d_table), ctypes.POINTER(ctypes.c_uint32)), lay.slots, own,
+                                                 lay.n_points, lay.n_scalars, vp(d_bases), vp(d_tail), vp(d_ybytes), vp(d_scalars),
+                                                 ctypes.cast(vp(d_bad), ctypes.POINTER(ctypes.c_uint32)), stream))
+        shared_words = np.stack([g1_words(p) for p in self._shared]).view(np.int64)
+        d_bases[B * own:B * own + n_shared] = torch.from_numpy(shared_words).to(dev)
+        ybytes = d_ybytes.cpu().numpy()
+        dev_bad = d_bad.cpu().numpy()
+        t1 = time.perf_counter()
+
+        # the transcripts: everything a proof's challenges depend on is on the host now
+        zero_record = [0] * (len(RECORD) + 1)
+        records, inst_rows = [zero_record] * B, [None] * B
+        plan = self._plan_for([max((len(inst[c]) for inst in self._instances), default=0) for c in range(self.vk.cs.num_instance)])
+        t_plan = time.perf_counter() - t1
+        for b in range(B):
+            bad[b] = bad[b] or bool(dev_bad[b])
+            inst_rows[b] = plan.instance_row(self._instances[b])
+            if not bad[b]:
+                ch = transcript_challenges(lay, self._digest, self._instances[b], self._proofs[b], [bytes(row) for row in ybytes[b]])
+                records[b] = [ch[name] for name in RECORD] + [self._rand[b]]
+        t2 = time.perf_counter()
+        up = lambda rows: torch.from_numpy(fr_array(rows).view(np.int64)).to(dev)
+        d_records, d_inst = up(records), up(inst_rows)
+        d_bad.copy_(torch.tensor([int(x) for x in bad], dtype=torch.int32))
+        d_own = torch.empty((B * own, 4), dtype=torch.int64, device=dev)
+        d_shared = torch.empty((B, n_shared, 4), dtype=torch.int64, device=dev)
+        d_h2_r, d_h2_l = torch.empty((B, 4), dtype=torch.int64, device=dev), torch.empty((B, 4), dtype=torch.int64, device=dev)
+        t3 = time.perf_counter()
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        _lib.check(lib.hm_verify_terms_dev(ctypes.c_uint64(self._program.handle), plan.words.ctypes.data_as(u32p), len(plan.words),
+                                           plan.n_columns, 4, B, vp(d_records), vp(d_scalars), vp(d_inst), ctypes.cast(vp(d_bad), u32p),
+                                           vp(d_own), vp(d_shared), vp(d_h2_r), vp(d_h2_l), stream))
+        bad = [bool(x) for x in d_bad.cpu().numpy()]              # the terms kernel flags x^n = 1 and its kin
+        t4 = time.perf_counter()
+        st = dict(B=B, bad=bad, d_bases=d_bases, d_scalars=d_scalars, d_own=d_own, d_shared=d_shared, d_h2_r=d_h2_r, d_h2_l=d_h2_l,
+                  d_sum=torch.zeros((n_shared, 4), dtype=torch.int64, device=dev), ybytes=ybytes)
+        self.timings = dict(read=t1 - t0, plan=t_plan, transcript=t2 - t1 - t_plan, upload=t3 - t2, terms=t4 - t3, msm=0.0, pairing=0.0)
+        self._state = st
+        return st
+
+    def column_sum(self, lo: int, hi: int):
+        """sum of rows [lo, hi) of the (B, shared) array of r_b x shared scalars, on the device: a (shared, 4) tensor"""
+        import torch
+
+        st = self._prepare()
+        out = st["d_sum"]
+        _lib.check(_lib.load().hm_verify_column_sum_dev(ctypes.c_void_p(st["d_shared"].data_ptr()), st["B"], len(self.layout.shared_keys), lo, hi,
+                                                        ctypes.c_void_p(out.data_ptr()),
+                                                        ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)))
+        return out
+
+    def _sums(self, handle, lo: int, hi: int):
+        """(L, R) of the proofs [lo, hi) as (x, y) integers: four MSMs over offsets into the registered array, folded on the host"""
+        from .arithmetic import best_multiexp
+
+        st, own, n_shared = self._state, self.layout.own_points, len(self.layout.shared_keys)
+        B = st["B"]
+        parts = [best_multiexp(st["d_own"][lo * own:hi * own], handle, offset=lo * own),
+                 best_multiexp(self.column_sum(lo, hi), handle, offset=B * own),
+                 best_multiexp(st["d_h2_r"][lo:hi], handle, offset=B * own + n_shared + lo)]
+        left = best_multiexp(st["d_h2_l"][lo:hi], handle, offset=B * own + n_shared + lo)
+        self.msm_calls += 4
+        right = np.zeros(12, dtype=np.uint64)
+        stacked = np.ascontiguousarray(np.stack(parts))
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        _lib.check(_lib.load().hm_g1_sum(stacked.ctypes.data_as(u64p), len(parts), right.ctypes.data_as(u64p)))
+        return g1_words_to_int(left), g1_words_to_int(right)
+
+    def _check(self, handle, lo: int, hi: int, trapdoor) -> bool:
+        """the one check of the well-formed proofs in [lo, hi) (malformed ones hold zero rows); vacuously True when there are none"""
+        if all(self._state["bad"][lo:hi]):
+            return True
+        t0 = time.perf_counter()
+        left, right = self._sums(handle, lo, hi)
+        t1 = time.perf_counter()
+        if trapdoor is not None:
+            ok = g1_mul(trapdoor, left) == right
+        else:
+            g2, s_g2 = g2_from_bytes(self.params.g2), g2_from_bytes(self.params.s_g2)
+            ok = g1_on_curve(left) and pairing_check([(left, s_g2), (g1_neg(right), g2)])
+        self.timings["msm"] += t1 - t0
+        self.timings["pairing"] += time.perf_counter() - t1
+        return ok
+
+    def _with_bases(self, fn):
+        from .arithmetic import register_bases, release_bases
+
+        st = self._prepare()
+        if all(st["bad"]):
+            return fn(None)
+        handle = register_bases(st["d_bases"], plain=True)
+        try:
+            return fn(handle)
+        finally:
+            release_bases(handle)
+
+    def finalize(self, trapdoor: int = None) -> bool:
+        if not self._proofs:
+            return True
+        st = self._prepare()
+        if any(st["bad"]):
+            return False
+        return self._with_bases(lambda handle: self._check(handle, 0, st["B"], trapdoor))
+
+    def failing(self, trapdoor: int = None) -> List[int]:
+        if not self._proofs:
+            return []
+        st = self._prepare()
+        out = [b for b, bad in enumerate(st["bad"]) if bad]
+
+        def bisect(handle, lo: int, hi: int, known_failing: bool) -> None:
+            if not known_failing and self._check(handle, lo, hi, trapdoor):
+                return
+            if hi - lo == 1:
+                out.append(lo)
+                return
+            mid = (lo + hi) // 2
+            left_ok = self._check(handle, lo, mid, trapdoor)
+            if not left_ok:
+                bisect(handle, lo, mid, True)
+            bisect(handle, mid, hi, left_ok)                        # the range failed: with a passing left half the right half fails
+
+        self._with_bases(lambda handle: bisect(handle, 0, st["B"], False))
+        return sorted(out)
+
+
+def verify_proofs(params, vk: VerifyingKey, instances, proofs, seed=None, trapdoor: int = None) -> bool:
+    """True when every ``proofs[i]`` is a valid single-circuit proof of ``vk`` for ``instances[i]``: one ``BatchVerifier``, one check"""
+    instances, proofs = list(instances), list(proofs)
+    if len(instances) != len(proofs):
+        raise ValueError("verify_proofs: one instance per proof")
+    bv = BatchVerifier(params, vk, seed)
+    for instance, proof in zip(instances, proofs):
+        bv.add_proof(instance, proof)
+    return bv.finalize(trapdoor)

@@ -488,6 +488,12 @@ int mock_program_run(DeviceCtx& ctx, GraphProgram& g, const MockTable& t, const 
 int mock_copies_run(DeviceCtx& ctx, const MockTable& t, const uint32_t* perm, size_t n_perm, const uint32_t* d_pairs, size_t n_copies,
                     uint32_t k, size_t m, const MockSink& out, hipStream_t stream);
 
+// lookup.hip (verify_terms.inc): r_b x the scalars of every proof of a batch, one lane per proof; `plan` (host memory) is checked word
+// by word before anything is launched and uploaded with the call.  Asynchronous on `stream`.
+int verify_terms_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
+                     const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst, uint32_t* d_bad, uint32_t* d_own,
+                     uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream);
+
 // msm.hip
 int msm_convert_bases(const uint32_t* d_bases_ext, uint32_t* d_xy, uint8_t* d_inf, size_t n, hipStream_t stream);
 // out_windows: host buffer of W x 12 u64 external Jacobian + flags
@@ -535,5 +541,11 @@ int g1_fft_run(DeviceCtx& ctx, uint32_t* d_points, uint32_t words, const uint64_
 int g1_compress_run(const uint32_t* d_xy, size_t n, uint32_t* d_out32, hipStream_t stream);
 int g1_decompress_run(const uint32_t* d_in32, size_t n, uint32_t* d_xy, uint64_t* first_invalid, hipStream_t stream);
 int g1_check_run(const uint32_t* d_xy, size_t n, uint64_t* first_invalid, hipStream_t stream);
+// A batch of proofs (verify_read.inc): every 32-byte slot of n_proofs proofs read by the kinds of the device table (points decompressed,
+// scalars checked), and the sum of rows [lo, hi) of every column of a (rows, cols) array of Fr words.  Both asynchronous on `stream`.
+int verify_read_run(const uint32_t* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots, uint32_t own_points,
+                    uint32_t n_points, uint32_t n_scalars, uint32_t* d_points, uint32_t* d_tail, uint32_t* d_ybytes, uint32_t* d_scalars,
+                    uint32_t* d_bad, hipStream_t stream);
+int verify_colsum_run(const uint32_t* d_rows, uint32_t cols, size_t lo, size_t hi, uint32_t* d_out, hipStream_t stream);
 
 }  // namespace hm

@@ -19,6 +19,8 @@
 
 namespace hm {
 #include "g1_codec.inc"   // the per-point SRS codec formulas (its kernels are HIP-only)
+#include "verify_read.inc"   // the batch verifier's per-slot read and its column sum (likewise)
+#include "verify_terms.inc"  // ... and the two phases of its per-proof terms around the interpreter's run (likewise)
 #include "poseidon.inc"   // the per-hash Poseidon / Merkle node functions (likewise)
 #include "keygen.inc"     // the permutation assembly's key packing and link rule (likewise)
 #include "shplonk.inc"    // the SHPLONK set quotient's plan, coefficients and row formula (likewise)
@@ -616,6 +618,62 @@ void hc_g1_codec(int op, const uint32_t* in, uint32_t* out, int* valid, size_t n
       valid[i] = g1_check_one(a, b) ? 1 : 0;
     }
   }
+}
+
+// The batch verifier's read (verify_read.inc) on n slots, the exact per-slot code of its kernel.  kinds[i] != 0: a point slot, 8 words
+// in, 24 out (x, y Montgomery, then the canonical words of y); 0: a scalar slot, 8 in, the first 8 of the 24 out.  valid[i] = 1 / 0.
+// Every input enters at the 2^256 class, so one slot of each kind proves the bounds for all inputs.
+void hc_verify_read(const uint8_t* kinds, const uint32_t* in, uint32_t* out, int* valid, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    uint32_t a[8], o1[8] = {0}, o2[8] = {0}, o3[8] = {0};
+    std::memcpy(a, in + 8 * i, 32);
+    valid[i] = (kinds[i] ? proof_point_one(a, o1, o2, o3) : proof_scalar_one(a, o1)) ? 1 : 0;
+    std::memcpy(out + 24 * i, o1, 32);
+    std::memcpy(out + 24 * i + 8, o2, 32);
+    std::memcpy(out + 24 * i + 16, o3, 32);
+  }
+}
+
+// ... and its column sum: rows x cols Montgomery words -> cols sums over rows [lo, hi), by the kernel's step, join and finish (the rows
+// dealt to `lanes` partial sums as the kernel deals them to its threads, then folded as its tree folds them).
+int hc_verify_column_sum(const uint32_t* rows, size_t n_rows, uint32_t cols, size_t lo, size_t hi, uint32_t lanes, uint32_t* out) {
+  if (lo > hi || hi > n_rows || lanes == 0 || (lanes & (lanes - 1))) return -1;
+  for (uint32_t c = 0; c < cols; ++c) {
+    std::vector<Fr> part(lanes, fe_zero<FrParams>());
+    for (size_t r = lo; r < hi; ++r) {
+      uint32_t w[8];
+      std::memcpy(w, rows + (r * cols + c) * 8, 32);
+      Fr& acc = part[(r - lo) % lanes];
+      acc = colsum_step(acc, w);
+    }
+    for (uint32_t s = lanes / 2; s > 0; s >>= 1)
+      for (uint32_t t = 0; t < s; ++t) {
+        Fr o = part[t + s];
+        HM_DECLARE(o, 3.0);
+        part[t] = colsum_join(part[t], o);
+      }
+    uint32_t w[8];
+    colsum_finish(part[0], w);
+    std::memcpy(out + (size_t)c * 8, w, 32);
+  }
+  return 0;
+}
+
+// The batch verifier's terms (verify_terms.inc) for ONE proof, the exact lane code of its kernel on a workspace of one lane: phase a,
+// then -- the interpreter's run is hc_graph_replay's business -- the numerator as the caller gives it (4 Montgomery words), then
+// phase b.  vals: the value row as phase a left it (n_vals x 8 words, h(x) filled in by phase b).  -> 1 / 0: the lane's ok flag; -1
+// with *why set when the plan fails its check.
+int hc_verify_terms(const uint32_t* plan, size_t n_words, size_t n_columns, const uint32_t* rec, const uint32_t* evals, const uint32_t* inst,
+                    const uint32_t* numerator, uint32_t* vals, uint32_t* own, uint32_t* shared, uint32_t* h2r, uint32_t* h2l, const char** why) {
+  *why = vt_plan_problem(plan, n_words, n_columns);
+  if (*why) return -1;
+  std::vector<uint32_t> ws((size_t)vt_ws_program(plan) * 9, 0);
+  const VtMem m{ws.data(), 1, 0};
+  bool ok = vt_phase_a(plan, m, rec, evals, inst);
+  Fr num = vt_from_ext(numerator);
+  ok = vt_phase_b(plan, m, num, own, shared, h2r, h2l) && ok;
+  for (uint32_t s = 0; s < plan[VT_N_VALS]; ++s) vt_to_ext(vals + 8 * (size_t)s, vt_load(m, s));
+  return ok ? 1 : 0;
 }
 
 // Poseidon (poseidon.inc) on n messages, the exact per-hash code of its kernels.  consts: the spec's block as the library lays it out

@@ -589,5 +589,7 @@ int lookup_permute_run(DeviceCtx& ctx, const void* const* d_inputs, const void* 
 }
 
 #include "mock.inc"       // the batched witness checker: its lookup pass searches keys sorted by the code above
+#define HM_VERIFY_TERMS_KERNELS
+#include "verify_terms.inc"   // the batch verifier's per-proof terms: the same interpreter on one lane per proof
 
 }  // namespace hm

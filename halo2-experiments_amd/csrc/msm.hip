@@ -1677,6 +1677,7 @@ __global__ __launch_bounds__(ACC_THREADS) void g1_fixed_base_mul_kernel(const ui
 
 #include "g1_fft.inc"   // best_fft over G1: g1_fft_run below
 #include "g1_codec.inc" // SRS point encodings: g1_compress_run / g1_decompress_run / g1_check_run below
+#include "verify_read.inc" // a batch of proofs read slot by slot, and the column sums of its shared scalars: verify_*_run below
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -2563,6 +2564,26 @@ int g1_check_run(const uint32_t* d_xy, size_t n, uint64_t* first_invalid, hipStr
   return g1_codec_validating_run("g1_check", n, first_invalid, stream, [&](dim3 grid, unsigned long long* flag) {
     hipLaunchKernelGGL(g1_check_kernel, grid, dim3(ACC_THREADS), 0, stream, d_xy, n, flag);
   });
+}
+
+// A batch of proofs (verify_read.inc).  Both are asynchronous on `stream`; every index the read kernel takes from the device table is
+// checked there against the sizes given here.
+int verify_read_run(const uint32_t* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots, uint32_t own_points,
+                    uint32_t n_points, uint32_t n_scalars, uint32_t* d_points, uint32_t* d_tail, uint32_t* d_ybytes, uint32_t* d_scalars,
+                    uint32_t* d_bad, hipStream_t stream) {
+  const uint64_t lanes = (uint64_t)n_proofs * slots;
+  if (lanes == 0) return HM_OK;
+  hipLaunchKernelGGL(verify_read_kernel, dim3((uint32_t)((lanes + ACC_THREADS - 1) / ACC_THREADS)), dim3(ACC_THREADS), 0, stream, d_proofs,
+                     d_slot_table, slots, lanes, own_points, n_points, n_scalars, d_points, d_tail, d_ybytes, d_scalars, d_bad);
+  HM_HIP_CHECK(hipGetLastError());
+  return HM_OK;
+}
+
+int verify_colsum_run(const uint32_t* d_rows, uint32_t cols, size_t lo, size_t hi, uint32_t* d_out, hipStream_t stream) {
+  if (cols == 0) return HM_OK;
+  hipLaunchKernelGGL(verify_colsum_kernel, dim3(cols), dim3(COLSUM_THREADS), 0, stream, d_rows, cols, (uint64_t)lo, (uint64_t)hi, d_out);
+  HM_HIP_CHECK(hipGetLastError());
+  return HM_OK;
 }
 
 }  // namespace hm

@@ -234,6 +234,13 @@ def verify_opening(transcript, queries, commitments: dict):
     h1 = transcript.read_point()
     u = transcript.squeeze_challenge()
     h2 = transcript.read_point()
+    scalars, points = opening_terms(queries, commitments, y, v, u, h1, h2)
+    return h2, g1_msm(scalars, points)
+
+
+def opening_terms(queries, commitments: dict, y: int, v: int, u: int, h1, h2):
+    """The scalars and the points whose sum is the R of ``verify_opening``, for the challenges y, v, u and the points [h] = ``h1``,
+    [h'] = ``h2``: one term per commitment in the order of the rotation sets, then the generator, [h] and [h']."""
     rotation_sets, super_points = construct_intermediate_sets(queries)
     zt = vanishing_eval(super_points, u)
     scalars, points, r_outer, z0_inv = [], [], 0, None
@@ -252,4 +259,4 @@ def verify_opening(transcript, queries, commitments: dict):
             r_outer = (r_outer + outer * yj % R * r_eval) % R
     scalars += [-r_outer % R, -z0_inv * zt % R, u]
     points += [G1_GEN, h1, h2]
-    return h2, g1_msm(scalars, points)
+    return scalars, points

@@ -688,6 +688,52 @@ int hm_mock_lookup_dev(uint64_t graph, const void* const* column_bases, const ui
                        uint32_t user_base, const void* d_table_values, uint64_t* d_records, size_t cap, uint64_t* d_counter,
                        uint8_t* d_user_flags, uint64_t* out_total, void* stream);
 
+/* ---- a batch of proofs: what halo2_proofs::plonk::BatchVerifier does per proof around its one pairing ------------------------------
+ *
+ * read: n_proofs proofs of `slots` 32-byte slots each lie one behind the other in d_proofs (DEVICE memory, 16-byte aligned).  What a
+ * slot holds is the same for every proof of one constraint system and stands in d_slot_table (DEVICE memory, one u32 per slot):
+ * bit 31 set for a compressed G1 point, clear for a scalar; bits 0 .. 29 the slot's index among the proof's points, or among its
+ * scalars; bit 30, on a point, sends it to the tail.  One lane per (proof, slot):
+ *   a point is decompressed as by hm_g1_decompress_bn256_dev, into 8 u64 affine Montgomery words (the hm_register_bases layout): at row
+ *     b * own_points + index of d_points_xy, or with bit 30 at row b of d_tail_xy; the 32 canonical bytes of its y go to row
+ *     b * points + index of d_y_bytes (the transcript absorbs x, which the proof holds, then y);
+ *   a scalar must be below r and is written as 4 Montgomery words to row b * scalars + index of d_scalars.
+ * A slot that cannot be read -- x >= p, x^3 + 3 not a square, the 32 zero bytes of the identity, a scalar >= r, a table entry whose
+ * index lies outside its array (index >= points, >= own_points without bit 30, >= scalars) -- sets d_bad[b] (one u32 per proof, zeroed
+ * by the caller) to 1; its outputs are zeros, or for a table entry outside its array are left alone.  Asynchronous on `stream`.
+ * HM_ERR_BAD_ARG, with nothing launched: NULL arguments, n_proofs 0 or above 2^24, slots 0 or above 2^16, points + scalars != slots,
+ * own_points > points, a buffer that is not aligned.
+ *
+ * column sum: d_out[c] = the sum mod r of rows lo .. hi - 1 of column c of d_rows, an (n_rows, columns) array of Montgomery Fr words
+ * (DEVICE memory, 16-byte aligned; d_out: columns x 4 u64): the contributions of the proofs lo .. hi - 1 to the points all proofs
+ * share.  lo == hi gives zeros.  Asynchronous on `stream`.  HM_ERR_BAD_ARG, with nothing launched: NULL arguments, columns 0 or above
+ * 2^16, lo > hi, hi > n_rows, n_rows > 2^24, a buffer that is not aligned. */
+int hm_verify_read_proofs_dev(const void* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots, uint32_t own_points,
+                              uint32_t points, uint32_t scalars, void* d_points_xy, void* d_tail_xy, void* d_y_bytes, void* d_scalars,
+                              uint32_t* d_bad, void* stream);
+int hm_verify_column_sum_dev(const void* d_rows, size_t n_rows, uint32_t columns, size_t lo, size_t hi, void* d_out, void* stream);
+/* terms: one lane per proof computes r_b x the scalar of every point of the proof's opening check, from d_records (n_proofs x 9
+ * elements: theta, beta, gamma, y, x, the multiopen's y', v, u, and the weight r_b), d_scalars (the evaluations, as the read call left
+ * them) and d_instance (the instance values, column after column, every column padded to the plan's row count) -- all 4 Montgomery
+ * words per element, DEVICE memory.  `plan` (HOST memory, n_plan_words u32; csrc/verify_terms.inc states its layout) is built once per
+ * constraint system: where a (column, rotation) of the program stands in the proof's value row, the instance queries, the rotation sets
+ * of the multiopen taken on rotations, the constants.  It is checked word by word -- every index it holds must lie inside its array --
+ * and uploaded with the call.  `graph` is the hm_graph_create program of the gate, permutation and lookup expressions folded in y,
+ * undivided, lowered from the constraint system alone; n_columns / n_dynamic are its own counts (its per-call constants must be beta,
+ * gamma, theta, y).  The lane computes x^n, l0, l_last, l_active and the instance columns' evaluations at x, runs the program on its
+ * value row (PreviousValue zero), divides by x^n - 1, and per rotation set the multiopen's scalars.
+ * Output (DEVICE memory, written for every proof): d_own, n_proofs x own points x 4 words, the proof's own points in the proof's
+ * order ([h] last, the h pieces weighted by the powers of x^n); d_shared, n_proofs x shared points x 4, its row of the shared points'
+ * array; d_h2_r / d_h2_l, n_proofs x 4 each: r_b u and r_b, the weights of [h'] in the two sums.  A proof whose d_bad[b] is set on
+ * entry, or that would divide by zero (x^n = 1, x = 0, u on a point of the opening), gets all-zero rows and d_bad[b] = 1: a zero is
+ * never inverted into a fault.  Asynchronous on `stream`.
+ * HM_ERR_BAD_ARG, with nothing launched: NULL arguments, n_proofs 0 or above 2^20, a plan that fails its check -- among the reasons an
+ * instance column longer than 64 rows and more than 256 value slots --, column or constant counts that are not the program's, an
+ * unknown program handle. */
+int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
+                        const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad, void* d_own, void* d_shared,
+                        void* d_h2_r, void* d_h2_l, void* stream);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 
 typedef struct hm_msm_stats {
