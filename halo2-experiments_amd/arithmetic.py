@@ -19,7 +19,7 @@ import numpy as np
 from . import _lib
 from ._marshal import _is_tensor, _np, _ptr, _ptr_array, _stream_ptr, _tensor_rows, _u32p
 from .bn256 import (FQ_MODULUS, FQ_ONE_MONT, FR_MODULUS, FR_ROOT_OF_UNITY, FR_S, G1_GENERATOR, fq_words,  # noqa: F401  (re-exported)
-                    fr_words)
+                    fr_array, fr_words)
 
 class BasesHandle:
     """A device-resident, pre-converted base set (``ParamsKZG::g`` / ``g_lagrange``)."""
@@ -335,6 +335,39 @@ def linear_combination(polys, coeffs, out=None):
     _lib.check(lib.hm_fr_linear_combination_dev(ptrs, _ptr(cs) if len(polys) else None, len(polys), n, ctypes.c_void_p(out.data_ptr()),
                                                 ctypes.c_void_p(_stream_ptr(ref))))
     return out
+
+
+def linear_combination_batch(polys, coeffs, outs=None):
+    """``linear_combination`` for a batch of independent proofs in one launch chain (``hm_fr_linear_combination_batch_dev``):
+    ``polys[b]`` the list of proof b's (n, 4) GPU tensors -- the same count for every proof, the same tensor allowed in several proofs
+    -- ``coeffs[b]`` its integers; ``outs[b]`` may be one of proof b's own inputs, never another proof's input or output.  Returns
+    the list of outputs (new tensors when ``outs`` is None), word for word the loop of ``linear_combination``."""
+    import torch
+
+    polys = [list(p) for p in polys]
+    proofs = len(polys)
+    if proofs == 0:
+        return []
+    count = len(polys[0])
+    if any(len(p) != count for p in polys) or len(coeffs) != proofs or any(len(c) != count for c in coeffs):
+        raise ValueError("linear_combination_batch: every proof needs the same number of polynomials and one coefficient for each")
+    if count == 0 and outs is None:
+        raise ValueError("linear_combination_batch: nothing to combine and no output to clear")
+    ref = polys[0][0] if count else outs[0]
+    n = _tensor_rows(ref, 4, "polys")
+    for p in (q for row in polys for q in row):
+        if not _is_tensor(p) or _tensor_rows(p, 4, "polys") != n:
+            raise ValueError("linear_combination_batch: polynomials must be GPU tensors of one length")
+    if outs is None:
+        outs = list(torch.empty((proofs, n, 4), dtype=torch.int64, device=ref.device))
+    elif len(outs) != proofs or any(not _is_tensor(o) or _tensor_rows(o, 4, "outs") != n for o in outs):
+        raise ValueError("linear_combination_batch: one output of the polynomials' length per proof")
+    flat = [p for row in polys for p in row]
+    cs = fr_array([int(c) % FR_MODULUS for row in coeffs for c in row]) if count else None
+    ptrs = (ctypes.c_void_p * max(len(flat), 1))(*[p.data_ptr() for p in flat])
+    _lib.check(_lib.load().hm_fr_linear_combination_batch_dev(ptrs, _ptr(cs) if count else None, count, n, _ptr_array(list(outs)), proofs,
+                                                              ctypes.c_void_p(_stream_ptr(ref))))
+    return list(outs)
 
 
 def permute_expression_pair(input_column, table_column, usable_rows: int, blinding_seed: int = 0):

@@ -395,6 +395,56 @@ int hm_shplonk_set_quotient_bn256_fr_dev(const void* const* d_polys, const uint6
   return fr_shplonk_set_quotient_run(d_polys, weights, m, n, points, (uint32_t)t, scale, (uint32_t*)d_out, accumulate != 0, (hipStream_t)stream);
 } HM_API_CATCH("hm_shplonk_set_quotient_bn256_fr_dev")
 
+int hm_fr_linear_combination_batch_dev(const void* const* d_polys, const uint64_t* coeffs, size_t count, size_t n, void* const* d_outs,
+                                       size_t proofs, void* stream) try {
+  const char* who = "hm_fr_linear_combination_batch_dev";
+  if ((proofs && !d_outs) || (proofs && count && (!d_polys || !coeffs))) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (n) {
+    for (size_t b = 0; b < proofs; ++b)
+      if (!d_outs[b]) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null output");
+    for (size_t j = 0; j < proofs * count; ++j)
+      if (!d_polys[j]) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null polynomial");
+    if (const char* why = fr_batch_alias_check(d_polys, count, d_outs, proofs)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": " + why);
+  }
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    count_vector(*ctx, HM_STAT_LINEAR_COMBINATION, proofs, (uint64_t)proofs * count * n);
+  }
+  return fr_linear_combination_batch_run(d_polys, coeffs, count, n, d_outs, proofs, (hipStream_t)stream);
+} HM_API_CATCH("hm_fr_linear_combination_batch_dev")
+
+int hm_shplonk_set_quotient_batch_bn256_fr_dev(const void* const* d_polys, const uint64_t* weights, size_t m, size_t n, const uint64_t* points,
+                                               size_t t, const uint64_t* scales, void* const* d_outs, int accumulate, size_t proofs,
+                                               void* stream) try {
+  const char* who = "hm_shplonk_set_quotient_batch_bn256_fr_dev";
+  if (!d_polys || !weights || !points || !scales || !d_outs) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (proofs == 0) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": no proof");
+  if (m == 0) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": no polynomial");
+  if (t == 0 || t > (size_t)HM_SHPLONK_MAX_POINTS) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": need 1 <= t <= HM_SHPLONK_MAX_POINTS");
+  if (n < t + 1 || n > ((size_t)1 << 32)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": need t + 1 <= n <= 2^32");
+  for (size_t b = 0; b < proofs; ++b) {
+    if (!d_outs[b] || ((uintptr_t)d_outs[b] & 15)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a null or misaligned output");
+    for (size_t j = 0; j < m; ++j)
+      if (!d_polys[b * m + j] || ((uintptr_t)d_polys[b * m + j] & 15))
+        return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a null or misaligned polynomial");
+    for (size_t a = 0; a < t; ++a)
+      for (size_t c = a + 1; c < t; ++c)
+        if (host::fr_eq(host::fr_load(points + (b * t + a) * 4), host::fr_load(points + (b * t + c) * 4)))
+          return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": two equal points");
+  }
+  if (const char* why = fr_batch_alias_check(d_polys, m, d_outs, proofs)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": " + why);
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    count_vector(*ctx, HM_STAT_LINEAR_COMBINATION, proofs, (uint64_t)proofs * m * n);
+    count_vector(*ctx, HM_STAT_KATE_DIVISION, proofs * t, (uint64_t)proofs * t * n);
+  }
+  return fr_shplonk_set_quotient_batch_run(d_polys, weights, m, n, points, (uint32_t)t, scales, d_outs, accumulate != 0, proofs, (hipStream_t)stream);
+} HM_API_CATCH("hm_shplonk_set_quotient_batch_bn256_fr_dev")
+
 int hm_lookup_permute_bn256_fr_dev(const void* d_input, const void* d_table, size_t rows, void* d_permuted_input,
                                    void* d_permuted_table, void* stream) try {
   if (rows && (!d_input || !d_table || !d_permuted_input || !d_permuted_table))
@@ -495,6 +545,23 @@ int hm_graph_evaluate_circuits_dev(uint64_t handle, const void* const* column_ba
     }
   return hm_fail(HM_ERR_NOT_FOUND, "hm_graph_evaluate_circuits_dev: unknown program handle");
 } HM_API_CATCH("hm_graph_evaluate_circuits_dev")
+
+int hm_graph_evaluate_proofs_dev(uint64_t handle, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
+                                 size_t proofs, const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t log_size, uint32_t segments,
+                                 void* d_values, uint64_t values_stride, uint32_t flags, void* stream) try {
+  if (!d_values || (n_columns && (!column_bases || !column_strides)) || (n_dynamic && !dynamic_constants))
+    return hm_fail(HM_ERR_BAD_ARG, "hm_graph_evaluate_proofs_dev: null argument");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  for (auto& g : ctx->graphs)
+    if (g->handle == handle) {
+      count_vector(*ctx, HM_STAT_GRAPH_EVALUATE, 1, log_size < 32 && proofs < (1ull << 32) ? ((uint64_t)segments << log_size) * proofs : 0);
+      return graph_evaluate_proofs(*ctx, *g, column_bases, column_strides, n_columns, proofs, dynamic_constants, n_dynamic, log_size, segments,
+                                   d_values, values_stride, flags, (hipStream_t)stream);
+    }
+  return hm_fail(HM_ERR_NOT_FOUND, "hm_graph_evaluate_proofs_dev: unknown program handle");
+} HM_API_CATCH("hm_graph_evaluate_proofs_dev")
 
 // ---------------------------------------------------------------------------------------------
 // The quotient h(X) of a proof in ONE call, from coefficient arrays: every column onto `count` cosets of the n-th roots

@@ -371,4 +371,130 @@ int graph_evaluate_circuits(DeviceCtx& ctx, GraphProgram& g, const void* const* 
   return aux_release(ctx, slot, stream);
 }
 
+// ---- several INDEPENDENT proofs of one constraint system in one launch (hm_graph_evaluate_proofs_dev) ----
+// Every proof has its own per-call constants (theta, beta, gamma, y of its own transcript), its own columns (or a shared one at
+// stride 0) and its own values: nothing is folded across proofs, PreviousValue is the proof's own, and any program is admitted.
+// One lane per (proof, row), rows fastest (graph_lower.h: graph_proofs_*), so that a wave reads consecutive cells of a column.  The
+// constants come from a device table of proofs x n_dynamic x 9 internal words that follows the column table in the slot's argument
+// buffer.  A wave straddles proofs when a proof has fewer than 64 rows, so the table is read with an ordinary per-lane load
+// (dyn_row is a per-lane pointer; nothing assumes it uniform).  The arithmetic is ge_run's, unchanged: no bound class arises
+// that graph_evaluate_kernel does not have (constants enter as canonical internal words, < r; columns and PreviousValue as there).
+struct GraphProofColumns {
+  const uint32_t* p[GE_MAX_COLUMNS];
+  uint64_t stride[GE_MAX_COLUMNS];   // u32 words from proof b's column to proof b + 1's; 0: one column for all proofs
+  uint32_t n_static, n_dynamic;
+};
+
+template <bool INTERNAL>
+struct ProofSource {
+  const GraphProofColumns* __restrict__ columns;
+  const int32_t* __restrict__ rotations;
+  const uint32_t* __restrict__ dyn_table;
+  uint64_t mask;
+  uint32_t idx, proof, n_dynamic;             // idx: the row inside the proof (rows <= 2^32 and idx < rows)
+  const uint32_t* __restrict__ prev;
+  __device__ __forceinline__ uint32_t n_static() const { return columns->n_static; }
+  __device__ __forceinline__ uint32_t dyn(uint32_t word) const { return dyn_table[graph_proofs_dyn(proof, n_dynamic, word)]; }   // per lane
+  __device__ __forceinline__ Fr column(uint32_t src) const {
+    const uint64_t row = graph_proofs_row(idx, (int64_t)rotations[gsrc_rot(src)], mask, gsrc_log_rows(src));
+    const uint32_t col = gsrc_column(src);
+    const uint32_t* cell = columns->p[col] + graph_proofs_cell(proof, row, columns->stride[col]);
+    return INTERNAL ? ge_from_internal(cell) : ge_from_ext(cell);
+  }
+  __device__ __forceinline__ Fr previous() const { return ge_from_ext(prev); }
+};
+
+template <bool INTERNAL>
+__global__ __launch_bounds__(GE_THREADS) void graph_proofs_kernel(const GraphProofColumns* __restrict__ columns,
+                                                                  const uint32_t* __restrict__ dyn_table,
+                                                                  const uint32_t* __restrict__ consts,
+                                                                  const int32_t* __restrict__ rotations,
+                                                                  const GraphCalc* __restrict__ calcs, uint32_t n_calc, uint32_t result_src,
+                                                                  uint32_t result_prev, uint32_t* __restrict__ scratch,
+                                                                  uint32_t* __restrict__ values, uint64_t values_stride, uint64_t size,
+                                                                  uint64_t lanes, uint32_t log_segment) {
+  const uint32_t T = gridDim.x * GE_THREADS;
+  const uint32_t lane_slot = blockIdx.x * GE_THREADS + threadIdx.x;
+  const uint64_t mask = (1ull << log_segment) - 1;
+  const uint32_t n_dynamic = columns->n_dynamic;
+  for (uint64_t lane = lane_slot; lane < lanes; lane += T) {
+    const uint32_t proof = graph_proofs_proof(lane, size), idx = (uint32_t)(lane - (uint64_t)proof * size);
+    uint32_t* vrow = values + graph_proofs_cell(proof, idx, values_stride);
+    const ProofSource<INTERNAL> from{columns, rotations, dyn_table, mask, idx, proof, n_dynamic, vrow};
+    const Fr res = ge_run(from, consts, calcs, n_calc, result_src, result_prev, scratch, T, lane_slot);
+    uint32_t w[8];
+    fe_to_ext(w, ge_reduce(res));
+    uint4* dst = reinterpret_cast<uint4*>(vrow);
+    dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+  }
+}
+
+int graph_evaluate_proofs(DeviceCtx& ctx, GraphProgram& g, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
+                          size_t proofs, const uint64_t* dyn_ext, size_t n_dyn, uint32_t log_size, uint32_t segments, void* d_values,
+                          uint64_t values_stride, uint32_t flags, hipStream_t stream) {
+  if (flags & ~(uint32_t)HM_GRAPH_COLUMNS_INTERNAL) return hm_fail(HM_ERR_BAD_ARG, "graph: unknown flag");
+  if (proofs == 0) return hm_fail(HM_ERR_BAD_ARG, "graph: proofs must be >= 1");
+  if (n_columns > GE_MAX_COLUMNS) return hm_fail(HM_ERR_BAD_ARG, "graph: more columns than the column table holds");
+  if (n_columns != g.n_columns) return hm_fail(HM_ERR_BAD_ARG, "graph: the program was built for another number of columns");
+  if (n_dyn != g.n_dynamic) return hm_fail(HM_ERR_BAD_ARG, "graph: the program was built for another number of per-call constants");
+  if (log_size > 30) return hm_fail(HM_ERR_BAD_ARG, "graph: log_size > 30");
+  if (segments == 0 || ((uint64_t)segments << log_size) > (1ull << 32)) return hm_fail(HM_ERR_BAD_ARG, "graph: segments must be >= 1 and rows <= 2^32");
+  const uint64_t size = (uint64_t)segments << log_size;
+  if (proofs > (1ull << 32) / size) return hm_fail(HM_ERR_BAD_ARG, "graph: proofs * rows > 2^32");
+  if ((uintptr_t)d_values % 16) return hm_fail(HM_ERR_BAD_ARG, "graph: the values are not 16-byte aligned");
+  if (proofs > 1 && (values_stride < size * 8 || values_stride % 4))
+    return hm_fail(HM_ERR_BAD_ARG, "graph: the values stride must be a multiple of 4 words and hold the rows of one proof");
+  for (size_t i = 0; i < n_columns; ++i) {
+    if (!column_bases[i]) return hm_fail(HM_ERR_BAD_ARG, "graph: null column pointer");
+    if ((uintptr_t)column_bases[i] % 16) return hm_fail(HM_ERR_BAD_ARG, "graph: a column base is not 16-byte aligned");
+    if (column_strides[i] % 4) return hm_fail(HM_ERR_BAD_ARG, "graph: a column stride is not a multiple of 4 words");
+  }
+  const bool internal_cols = (flags & HM_GRAPH_COLUMNS_INTERNAL) != 0;
+  GraphVariant& v = g.variant[internal_cols ? 1 : 0];
+  if (!v.ready) {
+    const int rc = graph_lower(g, internal_cols, v);
+    if (rc != HM_OK) return rc;
+  }
+  // graph_evaluate's grid cap and scratch rule, the lanes being proofs * rows
+  static const uint32_t max_blocks = [] { const char* e = std::getenv("HALO2_MI355X_GRAPH_BLOCKS"); return (uint32_t)(e && *e ? std::atoi(e) : 1280); }();
+  const uint64_t lanes = (uint64_t)proofs * size;
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>((lanes + GE_THREADS - 1) / GE_THREADS, max_blocks);
+  const uint32_t T = blocks * GE_THREADS;
+  AuxSlot* slot = aux_acquire(ctx, stream);
+  if (!slot) return HM_ERR_HIP;
+  const size_t b_scratch = (size_t)v.n_slots * 9 * T * 4;
+  uint8_t* buf = (uint8_t*)slot->scratch.ensure(b_scratch);
+  if (!buf) return hm_fail(HM_ERR_HIP, "graph: scratch allocation failed");
+  // the argument block: the column table, then the constant table (one upload)
+  const size_t n_table = std::max<size_t>(proofs * n_dyn, 1) * 9;
+  std::vector<uint32_t> block(sizeof(GraphProofColumns) / 4 + n_table, 0);
+  GraphProofColumns& cols = *reinterpret_cast<GraphProofColumns*>(block.data());
+  for (size_t i = 0; i < n_columns; ++i) {
+    cols.p[i] = (const uint32_t*)column_bases[i];
+    cols.stride[i] = column_strides[i];
+  }
+  cols.n_static = g.n_static;
+  cols.n_dynamic = (uint32_t)n_dyn;
+  uint32_t* table = block.data() + sizeof(GraphProofColumns) / 4;
+  for (size_t i = 0; i < proofs * n_dyn; ++i) host::fr_to_internal9(host::fr_load(dyn_ext + 4 * i), table + 9 * i);
+  uint8_t* d_block = (uint8_t*)slot->args.ensure(block.size() * 4);
+  if (!d_block) return hm_fail(HM_ERR_HIP, "graph: argument buffer allocation failed");
+  // pageable source: the runtime has taken its copy of `block` when this returns (graph_evaluate)
+  HM_HIP_CHECK(hipMemcpyAsync(d_block, block.data(), block.size() * 4, hipMemcpyHostToDevice, stream));
+  const GraphProofColumns* d_cols = (const GraphProofColumns*)d_block;
+  const uint32_t* d_table = (const uint32_t*)(d_block + sizeof(GraphProofColumns));
+  const uint64_t vstride = proofs > 1 ? values_stride : 0;
+  if (internal_cols)
+    hipLaunchKernelGGL(graph_proofs_kernel<true>, dim3(blocks), dim3(GE_THREADS), 0, stream, d_cols, d_table, (const uint32_t*)g.d_consts,
+                       (const int32_t*)g.d_rot, (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src, v.result_prev, (uint32_t*)buf,
+                       (uint32_t*)d_values, vstride, size, lanes, log_size);
+  else
+    hipLaunchKernelGGL(graph_proofs_kernel<false>, dim3(blocks), dim3(GE_THREADS), 0, stream, d_cols, d_table, (const uint32_t*)g.d_consts,
+                       (const int32_t*)g.d_rot, (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src, v.result_prev, (uint32_t*)buf,
+                       (uint32_t*)d_values, vstride, size, lanes, log_size);
+  HM_HIP_CHECK(hipGetLastError());
+  return aux_release(ctx, slot, stream);
+}
+
 }  // namespace hm

@@ -50,6 +50,22 @@ constexpr double GE_CAP = 16.0, GE_COLUMN_BOUND = 6.0;     // a packed 256-bit w
 constexpr uint32_t GE_MAX_COLUMNS = 256;
 constexpr uint32_t GE_MAX_DYN = 16;
 
+// The address rule of hm_graph_evaluate_proofs_dev (graph.hip: graph_proofs_kernel), one lane per (proof, row) with the rows running
+// fastest: lane -> (proof, row of the proof); (row, rotation) -> the row a column source reads, wrapped inside the row's segment
+// and then inside a short column's period, exactly as in the single evaluation; (proof, row, column stride) -> the cell's u32 word
+// behind the column's base (stride 0: one column for all proofs); (proof, word) -> the word of the per-proof constant table
+// (proofs x n_dynamic x 9 internal words).  Nothing here ever adds a proof's rows to another proof's: a rotation at the last row of
+// proof b lands on proof b's first row.  host_check.cpp runs the same functions (hc_graph_proofs_address).
+// (proofs * rows <= 2^32, so a lane fits 32 bits, and rows = 2^32 leaves room for proof 0 alone: a 32-bit division)
+HM_GRAPH_HD uint32_t graph_proofs_proof(uint64_t lane, uint64_t rows) { return rows >> 32 ? 0u : (uint32_t)lane / (uint32_t)rows; }
+HM_GRAPH_HD uint64_t graph_proofs_row(uint64_t row, int64_t rotation, uint64_t segment_mask, uint32_t log_rows) {
+  uint64_t r = (row & ~segment_mask) | ((row + (uint64_t)rotation) & segment_mask);      // two's complement: a negative rotation wraps
+  if (log_rows != 0) r &= (1ull << log_rows) - 1ull;
+  return r;
+}
+HM_GRAPH_HD uint64_t graph_proofs_cell(uint64_t proof, uint64_t row, uint64_t stride_words) { return stride_words * proof + row * 8; }
+HM_GRAPH_HD uint64_t graph_proofs_dyn(uint64_t proof, uint32_t n_dynamic, uint32_t word) { return proof * (n_dynamic * 9u) + word; }
+
 inline bool graph_src_ok(uint32_t s, size_t n_const, size_t n_inter, size_t n_cols, size_t n_rot) {
   switch (gsrc_kind(s)) {
     case GSRC_CONST: return gsrc_index(s) < n_const;

@@ -402,6 +402,9 @@ int graph_evaluate(DeviceCtx& ctx, GraphProgram& g, const void* const* d_columns
 int graph_evaluate_circuits(DeviceCtx& ctx, GraphProgram& g, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
                             size_t circuits, const uint64_t* dyn_ext, size_t n_dyn, uint32_t log_size, uint32_t segments, void* d_values,
                             uint32_t flags, hipStream_t stream);
+int graph_evaluate_proofs(DeviceCtx& ctx, GraphProgram& g, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
+                          size_t proofs, const uint64_t* dyn_ext, size_t n_dyn, uint32_t log_size, uint32_t segments, void* d_values,
+                          uint64_t values_stride, uint32_t flags, hipStream_t stream);
 void graph_release(GraphProgram& g);
 
 // poly.hip
@@ -425,6 +428,13 @@ int fr_batch_invert_run(uint32_t* d_v, uint64_t n, hipStream_t stream);
 int fr_mul_periodic_run(uint32_t* d_a, uint64_t n, const uint64_t* pattern_ext, uint32_t period, hipStream_t stream);
 int fr_linear_combination_run(const void* const* d_polys, const uint64_t* coeffs_ext, size_t count, uint64_t n, uint32_t* d_out,
                               hipStream_t stream);
+// the same for `proofs` independent proofs in one launch chain (blockIdx.y = the proof); nullptr, or why the pointers are refused
+const char* fr_batch_alias_check(const void* const* d_polys, size_t count, void* const* d_outs, size_t proofs);
+int fr_linear_combination_batch_run(const void* const* d_polys, const uint64_t* coeffs_ext, size_t count, uint64_t n, void* const* d_outs,
+                                    size_t proofs, hipStream_t stream);
+int fr_shplonk_set_quotient_batch_run(const void* const* d_polys, const uint64_t* weights_ext, size_t m, uint64_t n, const uint64_t* points_ext,
+                                      uint32_t t, const uint64_t* scales_ext, void* const* d_outs, bool accumulate, size_t proofs,
+                                      hipStream_t stream);
 // Poseidon and Merkle trees (poseidon.inc).  Everything is asynchronous on `stream`; pointers are device memory of u32 words.
 int poseidon_spec_create(DeviceCtx& ctx, uint32_t width, uint32_t rate, uint32_t r_f, uint32_t r_p, const uint64_t* rc_ext,
                          const uint64_t* mds_ext, uint64_t* out_handle);

@@ -723,6 +723,15 @@ int hc_shplonk_coefficients(uint32_t t, const uint64_t* pts_ext, const uint64_t*
   for (uint32_t l = 0; l < t; ++l) std::memcpy(d_ext + 4 * l, d[l].l, 32);
   return 0;
 }
+// hm_graph_evaluate_proofs_dev's address rule (graph_lower.h: graph_proofs_*), as the kernel applies it to one lane and one column
+// source: out = { proof, row of the proof, the row the source reads, the cell's u32 word behind the column base, the word of the
+// constant table for `word` of that proof }
+void hc_graph_proofs_address(uint64_t lane, uint64_t rows, uint32_t log_segment, int64_t rotation, uint32_t log_rows, uint64_t stride_words,
+                             uint32_t n_dynamic, uint32_t word, uint64_t* out) {
+  const uint64_t proof = graph_proofs_proof(lane, rows), idx = lane - proof * rows;
+  const uint64_t row = graph_proofs_row(idx, rotation, ((uint64_t)1 << log_segment) - 1, log_rows);
+  out[0] = proof, out[1] = idx, out[2] = row, out[3] = graph_proofs_cell(proof, row, stride_words), out[4] = graph_proofs_dyn(proof, n_dynamic, word);
+}
 int hc_shplonk_row_bounds(const uint64_t* a_ext, double* report) {
   typedef Fe<FrParams> F;
   uint32_t wa[8];

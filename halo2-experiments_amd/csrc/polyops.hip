@@ -16,7 +16,9 @@
 // of 32 (K32), which makes them true internal values, while the running product stays "external read as internal".
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
+#include <string>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -152,13 +154,10 @@ __global__ __launch_bounds__(PO_THREADS) void fr_kate_chunks_kernel(PoCols cols,
 }
 
 // one workgroup: E_g = sum_{g' > g} W_g' Y^(g'-g-1), Y = z^(256 B)
-__global__ __launch_bounds__(PO_THREADS) void fr_kate_join_kernel(const uint32_t* __restrict__ wg_total, uint32_t G, PoPoints pts, uint32_t B,
-                                                                  uint32_t* __restrict__ carry) {
-  __shared__ uint32_t lds[9 * PO_THREADS];
+__device__ __forceinline__ void po_kate_join_body(uint32_t* lds, const uint32_t* __restrict__ wg_total, uint32_t G, const Fr& z, uint32_t B,
+                                                  uint32_t* __restrict__ carry) {
   const uint32_t t = threadIdx.x;
-  wg_total += (size_t)blockIdx.x * G * 9;                  // one joining workgroup per column
-  carry += (size_t)blockIdx.x * G * 9;
-  Fr Y = po_pow_small(po_arg(pts.z[blockIdx.x]), B);
+  Fr Y = po_pow_small(z, B);
 #pragma unroll 1
   for (int k = 0; k < 8; ++k) Y = fe_sqr(Y);
   Fr v = fe_zero<FrParams>();
@@ -166,6 +165,12 @@ __global__ __launch_bounds__(PO_THREADS) void fr_kate_join_kernel(const uint32_t
   if (t + 1 < G) v = po_load9(wg_total + (size_t)(t + 1) * 9, 3.0);     // exclusive: lane g starts from W_{g+1}
   v = po_suffix_scan_uniform(lds, v, Y);
   if (t < G) po_store9(carry + (size_t)t * 9, v);
+}
+__global__ __launch_bounds__(PO_THREADS) void fr_kate_join_kernel(const uint32_t* __restrict__ wg_total, uint32_t G, PoPoints pts, uint32_t B,
+                                                                  uint32_t* __restrict__ carry) {
+  __shared__ uint32_t lds[9 * PO_THREADS];
+  // one joining workgroup per column
+  po_kate_join_body(lds, wg_total + (size_t)blockIdx.x * G * 9, G, po_arg(pts.z[blockIdx.x]), B, carry + (size_t)blockIdx.x * G * 9);
 }
 
 __global__ __launch_bounds__(PO_THREADS) void fr_kate_replay_kernel(PoCols cols, uint64_t n, PoPoints pts, uint32_t B,
@@ -418,6 +423,33 @@ __global__ __launch_bounds__(PO_THREADS) void fr_lincomb_kernel(LcArgs args, uin
     const Fr term = fe_mul(po_load_raw(args.poly[j], i), po_arg(args.c[j]));   // < 2r, normalised
     acc = fe_add(acc, term);
     if ((j & 3u) == 3u) acc = fe_reduce_small(fe_norm(acc));                    // every four terms (limbs < 5 * 2^29): back below 3r
+  }
+  po_store_canonical(out, i, fe_reduce_small(fe_norm(acc)));
+}
+
+// The same for a batch of independent proofs, blockIdx.y = the proof: proof b's terms [first, first + k) of its `count` ordered
+// (pointer, coefficient) pairs come from a device table uploaded with the call (the index is wave-uniform: scalar loads); with
+// `reenter` the running sum in outs[b] enters first with coefficient 1, as in the chain of fr_lincomb_kernel launches.  At most
+// LC_MAX terms per launch, reduced every four: the bounds of fr_lincomb_kernel.
+__global__ __launch_bounds__(PO_THREADS) void fr_lincomb_batch_kernel(const uint32_t* const* __restrict__ polys, const uint32_t* __restrict__ coeffs,
+                                                                      uint32_t* const* __restrict__ outs, uint32_t count, uint32_t first, uint32_t k,
+                                                                      int reenter, PoFr one_int, uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * PO_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const size_t b = blockIdx.y;
+  uint32_t* out = outs[b];
+  Fr acc = fe_zero<FrParams>();
+  HM_DECLARE(acc, 0.0);
+  uint32_t pos = 0;
+  if (reenter) {
+    acc = fe_mul(po_load_raw(out, i), po_arg(one_int));
+    pos = 1;
+  }
+  for (uint32_t j = 0; j < k; ++j, ++pos) {
+    const size_t e = b * count + first + j;
+    const Fr term = fe_mul(po_load_raw(polys[e], i), po_load9(coeffs + e * 9, 1.0));   // < 2r, normalised
+    acc = fe_add(acc, term);
+    if ((pos & 3u) == 3u) acc = fe_reduce_small(fe_norm(acc));
   }
   po_store_canonical(out, i, fe_reduce_small(fe_norm(acc)));
 }
@@ -695,6 +727,142 @@ int fr_linear_combination_run(const void* const* d_polys, const uint64_t* coeffs
   }
   HM_HIP_CHECK(hipGetLastError());
   return HM_OK;
+}
+
+// What a batch of proofs may share: an input may occur in any number of proofs (the fixed and sigma polynomials do), and d_outs[b] may
+// be one of proof b's OWN inputs; an output that is another proof's input or output would make the batch differ from the loop of
+// single calls, and is refused.  nullptr, or the reason.
+const char* fr_batch_alias_check(const void* const* d_polys, size_t count, void* const* d_outs, size_t proofs) {
+  std::vector<const void*> outs(d_outs, d_outs + proofs);
+  std::sort(outs.begin(), outs.end());
+  if (std::adjacent_find(outs.begin(), outs.end()) != outs.end()) return "two proofs share an output";
+  for (size_t b = 0; b < proofs; ++b)
+    for (size_t j = 0; j < count; ++j) {
+      const void* p = d_polys[b * count + j];
+      if (p != (const void*)d_outs[b] && std::binary_search(outs.begin(), outs.end(), p)) return "an output is another proof's input";
+    }
+  return nullptr;
+}
+
+constexpr size_t PO_PROOFS_MAX = 65535;       // blockIdx.y
+
+// proofs x fr_linear_combination_run in one launch chain; the pointers were validated by the caller (capi_poly.hip: nulls, aliasing)
+int fr_linear_combination_batch_run(const void* const* d_polys, const uint64_t* coeffs_ext, size_t count, uint64_t n, void* const* d_outs,
+                                    size_t proofs, hipStream_t stream) {
+  if (n == 0 || proofs == 0) return HM_OK;
+  if (proofs > PO_PROOFS_MAX) return hm_fail(HM_ERR_BAD_ARG, "linear_combination_batch: more than 65535 proofs in one call");
+  // per proof, the terms that read its output first: they must all be consumed by the FIRST launch (fr_linear_combination_run)
+  const size_t terms = proofs * count;
+  std::vector<uint64_t> ptrs(terms + proofs);
+  std::vector<uint32_t> c9(std::max<size_t>(terms, 1) * 9);
+  for (size_t b = 0; b < proofs; ++b) {
+    size_t at = b * count, self = 0;
+    for (int pass = 0; pass < 2; ++pass)
+      for (size_t j = 0; j < count; ++j) {
+        const bool is_out = d_polys[b * count + j] == (const void*)d_outs[b];
+        if (is_out != (pass == 0)) continue;
+        self += is_out;
+        ptrs[at] = (uint64_t)(uintptr_t)d_polys[b * count + j];
+        host::fr_to_internal9(host::fr_load(coeffs_ext + (b * count + j) * 4), &c9[at * 9]);
+        ++at;
+      }
+    if (self > (size_t)LC_MAX) return hm_fail(HM_ERR_BAD_ARG, "linear_combination: the output appears among the inputs more than 24 times");
+    ptrs[terms + b] = (uint64_t)(uintptr_t)d_outs[b];
+  }
+  const size_t b_ptrs = ptrs.size() * 8, b_c9 = c9.size() * 4;
+  void* tab = nullptr;
+  HM_HIP_CHECK(hipMallocAsync(&tab, b_ptrs + b_c9, stream));
+  int rc = HM_OK;
+  // pageable sources: the runtime has taken its copies when these return
+  if (hipMemcpyAsync(tab, ptrs.data(), b_ptrs, hipMemcpyHostToDevice, stream) != hipSuccess ||
+      hipMemcpyAsync((uint8_t*)tab + b_ptrs, c9.data(), b_c9, hipMemcpyHostToDevice, stream) != hipSuccess)
+    rc = hm_fail(HM_ERR_HIP, "linear_combination_batch: upload failed");
+  if (rc == HM_OK) {
+    const uint32_t* const* d_p = (const uint32_t* const*)tab;
+    uint32_t* const* d_o = (uint32_t* const*)((uint64_t*)tab + terms);
+    const uint32_t* d_c = (const uint32_t*)((uint8_t*)tab + b_ptrs);
+    PoFr one;
+    host::fr_to_internal9(host::FR_ONE, one.l);
+    const dim3 grid((uint32_t)((n + PO_THREADS - 1) / PO_THREADS), (uint32_t)proofs);
+    size_t done = 0;
+    bool first = true;
+    do {                                                     // count == 0: one launch that writes zeroes
+      const uint32_t room = (uint32_t)LC_MAX - (first ? 0 : 1);
+      const uint32_t k = (uint32_t)std::min<size_t>(room, count - done);
+      hipLaunchKernelGGL(fr_lincomb_batch_kernel, grid, dim3(PO_THREADS), 0, stream, d_p, d_c, d_o, (uint32_t)count, (uint32_t)done, k,
+                         first ? 0 : 1, one, n);
+      done += k;
+      first = false;
+    } while (done < count);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("linear_combination_batch: ") + hipGetErrorString(e));
+  }
+  const hipError_t fe = hipFreeAsync(tab, stream);
+  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("linear_combination_batch: hipFreeAsync: ") + hipGetErrorString(fe));
+  return rc;
+}
+
+template <int T>
+static void shq_launch_batch(const ShqPlan& p, const uint32_t* d_n, uint64_t n, const ShqArgs* table, uint32_t* scan, uint64_t scan_stride,
+                             uint32_t* const* outs, int accumulate, uint32_t proofs, hipStream_t stream) {
+  hipLaunchKernelGGL(fr_shq_chunks_batch_kernel<T>, dim3(p.G, proofs), dim3(PO_THREADS), 0, stream, d_n, n, table, p.B, scan, scan_stride);
+  hipLaunchKernelGGL(fr_shq_join_batch_kernel, dim3(T, proofs), dim3(PO_THREADS), 0, stream, scan, scan_stride, p.G, (uint32_t)T, table, p.B);
+  hipLaunchKernelGGL(fr_shq_replay_batch_kernel<T>, dim3(p.G, proofs), dim3(PO_THREADS), 0, stream, d_n, n, table, p.B, (const uint32_t*)scan,
+                     scan_stride, outs, accumulate);
+}
+
+// proofs x fr_shplonk_set_quotient_run as ONE launch chain: every proof's N into one workspace by the batched linear combination,
+// then chunks / joins / replay with the proof in blockIdx.y; per-proof points and coefficients in a device table inside the same
+// allocation.  Every proof's points are checked (shq_coefficients) before anything is launched.
+int fr_shplonk_set_quotient_batch_run(const void* const* d_polys, const uint64_t* weights_ext, size_t m, uint64_t n, const uint64_t* points_ext,
+                                      uint32_t t, const uint64_t* scales_ext, void* const* d_outs, bool accumulate, size_t proofs,
+                                      hipStream_t stream) {
+  if (t == 0 || t > (uint32_t)SHQ_T_MAX) return hm_fail(HM_ERR_BAD_ARG, "shplonk_set_quotient: need 1 <= t <= 4 points");
+  if (proofs == 0) return HM_OK;
+  if (proofs > PO_PROOFS_MAX) return hm_fail(HM_ERR_BAD_ARG, "shplonk_set_quotient_batch: more than 65535 proofs in one call");
+  std::vector<ShqArgs> table(proofs);
+  std::memset(table.data(), 0, proofs * sizeof(ShqArgs));
+  for (size_t b = 0; b < proofs; ++b) {
+    host::Fr4 pts4[SHQ_T_MAX], d4[SHQ_T_MAX];
+    for (uint32_t l = 0; l < t; ++l) pts4[l] = host::fr_load(points_ext + (b * t + l) * 4);
+    if (!shq_coefficients(t, pts4, host::fr_load(scales_ext + b * 4), d4))
+      return hm_fail(HM_ERR_BAD_ARG, "shplonk_set_quotient: two equal points, or a point or the scale is not canonical");
+    for (uint32_t l = 0; l < t; ++l) {
+      host::fr_to_internal9(pts4[l], table[b].z[l].l);
+      host::fr_to_internal9(d4[l], table[b].d[l].l);
+    }
+  }
+  const ShqPlan p = shq_plan(n);
+  if (p.G > PO_THREADS) return hm_fail(HM_ERR_INTERNAL, "shplonk_set_quotient: plan exceeds one joining workgroup");
+  const size_t n_bytes = (size_t)n * 32, scan_stride = (size_t)t * (size_t)shq_scan_words(p);
+  // one workspace: every proof's N, the output pointers, the (points, coefficients) table, every proof's scans
+  const size_t o_outs = proofs * n_bytes, o_table = o_outs + proofs * sizeof(void*), o_scan = o_table + proofs * sizeof(ShqArgs);
+  void* ws = nullptr;
+  HM_HIP_CHECK(hipMallocAsync(&ws, o_scan + proofs * scan_stride * sizeof(uint32_t), stream));
+  uint8_t* base = (uint8_t*)ws;
+  std::vector<void*> d_ns(proofs);
+  for (size_t b = 0; b < proofs; ++b) d_ns[b] = base + b * n_bytes;
+  int rc = HM_OK;
+  if (hipMemcpyAsync(base + o_table, table.data(), proofs * sizeof(ShqArgs), hipMemcpyHostToDevice, stream) != hipSuccess ||
+      hipMemcpyAsync(base + o_outs, d_outs, proofs * sizeof(void*), hipMemcpyHostToDevice, stream) != hipSuccess)
+    rc = hm_fail(HM_ERR_HIP, "shplonk_set_quotient_batch: upload failed");
+  if (rc == HM_OK) rc = fr_linear_combination_batch_run(d_polys, weights_ext, m, n, d_ns.data(), proofs, stream);
+  if (rc == HM_OK) {
+    const int acc = accumulate ? 1 : 0;
+    const uint32_t* d_n = (const uint32_t*)base;
+    const ShqArgs* d_table = (const ShqArgs*)(base + o_table);
+    uint32_t* scan = (uint32_t*)(base + o_scan);
+    uint32_t* const* outs = (uint32_t* const*)(base + o_outs);
+    switch (t) {
+      case 1: shq_launch_batch<1>(p, d_n, n, d_table, scan, scan_stride, outs, acc, (uint32_t)proofs, stream); break;
+      case 2: shq_launch_batch<2>(p, d_n, n, d_table, scan, scan_stride, outs, acc, (uint32_t)proofs, stream); break;
+      case 3: shq_launch_batch<3>(p, d_n, n, d_table, scan, scan_stride, outs, acc, (uint32_t)proofs, stream); break;
+      default: shq_launch_batch<4>(p, d_n, n, d_table, scan, scan_stride, outs, acc, (uint32_t)proofs, stream); break;
+    }
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("shplonk_set_quotient_batch: ") + hipGetErrorString(e));
+  }
+  const hipError_t fe = hipFreeAsync(ws, stream);
+  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("shplonk_set_quotient_batch: hipFreeAsync: ") + hipGetErrorString(fe));
+  return rc;
 }
 
 int fr_mul_periodic_run(uint32_t* d_a, uint64_t n, const uint64_t* pattern_ext, uint32_t period, hipStream_t stream) {

@@ -88,9 +88,8 @@ struct ShqArgs {
 // barrier follows its last read).  Scratch of point l: incl + l * (G * 256 + 1) * 9, wg_total + l * G * 9 -- the layout
 // fr_kate_join_kernel expects of its columns.
 template <int T>
-__global__ __launch_bounds__(PO_THREADS) void fr_shq_chunks_kernel(const uint32_t* __restrict__ a, uint64_t n, ShqArgs args, uint32_t B,
-                                                                   uint32_t* __restrict__ incl, uint32_t* __restrict__ wg_total) {
-  __shared__ uint32_t lds[9 * PO_THREADS];
+__device__ __forceinline__ void shq_chunks_body(uint32_t* lds, const uint32_t* __restrict__ a, uint64_t n, const ShqArgs& args, uint32_t B,
+                                                uint32_t* __restrict__ incl, uint32_t* __restrict__ wg_total) {
   const uint32_t t = threadIdx.x;
   const uint64_t L = (uint64_t)blockIdx.x * PO_THREADS + t;
   const uint64_t lo = L * B, hi = lo + B < n ? lo + B : n;
@@ -115,13 +114,19 @@ __global__ __launch_bounds__(PO_THREADS) void fr_shq_chunks_kernel(const uint32_
     if (t == 0) po_store9(wg_total + ((size_t)l * gridDim.x + blockIdx.x) * 9, s);
   });
 }
+template <int T>
+__global__ __launch_bounds__(PO_THREADS) void fr_shq_chunks_kernel(const uint32_t* __restrict__ a, uint64_t n, ShqArgs args, uint32_t B,
+                                                                   uint32_t* __restrict__ incl, uint32_t* __restrict__ wg_total) {
+  __shared__ uint32_t lds[9 * PO_THREADS];
+  shq_chunks_body<T>(lds, a, n, args, B, incl, wg_total);
+}
 
 // Every lane replays its chunk for all T points at once and writes the combined row.  Rows at and above n - T are zero in the sum:
 // written as zero, or left alone when accumulating.
 template <int T>
-__global__ __launch_bounds__(PO_THREADS) void fr_shq_replay_kernel(const uint32_t* __restrict__ a, uint64_t n, ShqArgs args, uint32_t B,
-                                                                   const uint32_t* __restrict__ incl, const uint32_t* __restrict__ carry,
-                                                                   uint32_t* __restrict__ out, int accumulate) {
+__device__ __forceinline__ void shq_replay_body(const uint32_t* __restrict__ a, uint64_t n, const ShqArgs& args, uint32_t B,
+                                                const uint32_t* __restrict__ incl, const uint32_t* __restrict__ carry,
+                                                uint32_t* __restrict__ out, int accumulate) {
   const uint32_t t = threadIdx.x;
   const uint64_t L = (uint64_t)blockIdx.x * PO_THREADS + t;
   const uint64_t lo = L * B;
@@ -156,5 +161,44 @@ __global__ __launch_bounds__(PO_THREADS) void fr_shq_replay_kernel(const uint32_
     for (int l = 0; l < T; ++l) cur[l] = fe_reduce_small(fe_norm(fe_add(fe_mul(cur[l], z[l]), raw)));
     emit(i - 1);
   }
+}
+template <int T>
+__global__ __launch_bounds__(PO_THREADS) void fr_shq_replay_kernel(const uint32_t* __restrict__ a, uint64_t n, ShqArgs args, uint32_t B,
+                                                                   const uint32_t* __restrict__ incl, const uint32_t* __restrict__ carry,
+                                                                   uint32_t* __restrict__ out, int accumulate) {
+  shq_replay_body<T>(a, n, args, B, incl, carry, out, accumulate);
+}
+
+// ---- the same chain for a batch of independent proofs (hm_shplonk_set_quotient_batch_bn256_fr_dev): blockIdx.y = the proof ----
+// Proof b's combined polynomial N_b is row b of `a` (n x 8 words each), its points and coefficients entry b of a device table that was
+// uploaded with the call (wave-uniform: scalar loads), its scans' scratch the b-th block of `scan_stride` words (the single chain's
+// layout inside: incl, wg_total, carry), its output outs[b].  The bodies are the single chain's, so are the bounds.
+template <int T>
+__global__ __launch_bounds__(PO_THREADS) void fr_shq_chunks_batch_kernel(const uint32_t* __restrict__ a, uint64_t n,
+                                                                         const ShqArgs* __restrict__ table, uint32_t B,
+                                                                         uint32_t* __restrict__ scan, uint64_t scan_stride) {
+  __shared__ uint32_t lds[9 * PO_THREADS];
+  const size_t b = blockIdx.y;
+  uint32_t* incl = scan + b * scan_stride;
+  uint32_t* wg_total = incl + (size_t)T * ((size_t)gridDim.x * PO_THREADS + 1) * 9;
+  shq_chunks_body<T>(lds, a + b * n * 8, n, table[b], B, incl, wg_total);
+}
+template <int T>
+__global__ __launch_bounds__(PO_THREADS) void fr_shq_replay_batch_kernel(const uint32_t* __restrict__ a, uint64_t n,
+                                                                         const ShqArgs* __restrict__ table, uint32_t B,
+                                                                         const uint32_t* __restrict__ scan, uint64_t scan_stride,
+                                                                         uint32_t* const* __restrict__ outs, int accumulate) {
+  const size_t b = blockIdx.y;
+  const uint32_t* incl = scan + b * scan_stride;
+  const uint32_t* carry = incl + (size_t)T * ((size_t)gridDim.x * PO_THREADS + 1) * 9 + (size_t)T * gridDim.x * 9;
+  shq_replay_body<T>(a + b * n * 8, n, table[b], B, incl, carry, outs[b], accumulate);
+}
+// the joins: blockIdx.x = the point, blockIdx.y = the proof
+__global__ __launch_bounds__(PO_THREADS) void fr_shq_join_batch_kernel(uint32_t* __restrict__ scan, uint64_t scan_stride, uint32_t G, uint32_t t_points,
+                                                                       const ShqArgs* __restrict__ table, uint32_t B) {
+  __shared__ uint32_t lds[9 * PO_THREADS];
+  uint32_t* wg_total = scan + (size_t)blockIdx.y * scan_stride + (size_t)t_points * ((size_t)G * PO_THREADS + 1) * 9;
+  uint32_t* carry = wg_total + (size_t)t_points * G * 9;
+  po_kate_join_body(lds, wg_total + (size_t)blockIdx.x * G * 9, G, po_arg(table[blockIdx.y].z[blockIdx.x]), B, carry + (size_t)blockIdx.x * G * 9);
 }
 #endif

@@ -27,7 +27,7 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._marshal import _ptr, _ptr_array, _stream_ptr, _tensor_rows, _u32p
+from ._marshal import _is_tensor, _ptr, _ptr_array, _stream_ptr, _tensor_rows, _u32p
 from .domain import FR_MODULUS, fr_words
 
 R = FR_MODULUS
@@ -435,6 +435,68 @@ class CompiledGraph:
         _lib.check(_lib.load().hm_graph_evaluate_circuits_dev(
             ctypes.c_uint64(self.handle), ptr_arr, stride_arr, len(ptrs), circuits, _ptr(dyn), dyn.shape[0], seg.bit_length() - 1, segments,
             ctypes.c_void_p(values.data_ptr()), _lib.HM_GRAPH_COLUMNS_INTERNAL if columns_internal else 0, ctypes.c_void_p(_stream_ptr(values))))
+
+    def evaluate_proofs(self, columns: Sequence, values, constants: Sequence[dict], columns_internal: bool = False, segments: int = 1) -> None:
+        """``len(constants)`` INDEPENDENT ``evaluate`` calls in one launch (``hm_graph_evaluate_proofs_dev``): proof b reads its own
+        per-call constants ``constants[b]`` -- a dict with any of ``challenges``, ``beta``, ``gamma``, ``theta``, ``y``, as ``evaluate``
+        takes them -- its own columns and its own ``values[b]`` (PreviousValue on entry, the program's value on return).
+        ``values``: a (proofs, size, 4) GPU tensor.  ``columns[i]``: a (proofs, size, 4) tensor -- one column per proof, contiguous or
+        a slice whose rows are contiguous -- or a (size, 4) tensor every proof shares (a short column: its 2^log rows); a pair
+        ``(tensor, stride)`` names proof 0's column and the u32 words to the next proof's (0: shared).  Any program is admitted."""
+        proofs = len(constants)
+        if proofs < 1:
+            raise ValueError("evaluate_proofs: at least one proof")
+        if not _is_tensor(values) or values.dim() != 3 or values.shape[0] != proofs or values.shape[2] != 4:
+            raise ValueError(f"evaluate_proofs: values must be a ({proofs}, size, 4) GPU tensor")
+        size = values.shape[1]
+        if values.stride(2) != 1 or values.stride(1) != 4 or (proofs > 1 and values.stride(0) < size * 4):
+            raise ValueError("evaluate_proofs: the rows of a proof's values must be contiguous")
+        if segments < 1 or size % segments:
+            raise ValueError("evaluate_proofs: the rows must be a whole number of segments")
+        seg = size // segments
+        if seg & (seg - 1) or seg == 0:
+            raise ValueError("evaluate_proofs: the (segment of the) domain must be a power of two")
+        if len(columns) != self.n_columns:
+            raise ValueError("evaluate_proofs: column count differs from the compiled program's")
+        keep, ptrs, strides = [], [], []
+        for i, c in enumerate(columns):
+            want = (1 << self.short_columns[i]) if i in self.short_columns else size
+            if isinstance(c, tuple):
+                c, stride = c[0], int(c[1])
+                if _tensor_rows(c, 4, "column") != want:
+                    raise ValueError(f"evaluate_proofs: column {i} must hold {want} rows (proof 0's)")
+            elif c.dim() == 3:
+                if tuple(c.shape) != (proofs, want, 4):
+                    raise ValueError(f"evaluate_proofs: stacked column {i} must be ({proofs}, {want}, 4)")
+                if c.stride(2) != 1 or c.stride(1) != 4:
+                    c = c.contiguous()
+                stride = c.stride(0) * 2 if proofs > 1 else 0
+                c = c[0]
+            else:
+                if _tensor_rows(c, 4, "column") != want:
+                    raise ValueError(f"evaluate_proofs: column {i} must hold {want} rows")
+                stride = 0
+            if want == 1 and i in self.short_columns:          # encoded as two rows (GraphEvaluator.lower): the same row twice
+                if stride:
+                    raise ValueError(f"evaluate_proofs: the one-row column {i} must be shared")
+                c = c.reshape(1, 4).expand(2, 4).contiguous()
+            keep.append(c)
+            ptrs.append(c.data_ptr())
+            strides.append(stride)
+        rows = []
+        for cst in constants:
+            extra = set(cst) - {"challenges", "beta", "gamma", "theta", "y"}
+            ch = list(cst.get("challenges", ()))
+            if extra or len(ch) != self.num_challenges:
+                raise ValueError("evaluate_proofs: a proof's constants are challenges (the program's count), beta, gamma, theta, y")
+            rows += [fr_words(v) for v in ch + [cst.get("beta", 0), cst.get("gamma", 0), cst.get("theta", 0), cst.get("y", 0)]]
+        dyn = np.ascontiguousarray(np.stack(rows))
+        ptr_arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+        stride_arr = (ctypes.c_uint64 * max(len(strides), 1))(*strides)
+        _lib.check(_lib.load().hm_graph_evaluate_proofs_dev(
+            ctypes.c_uint64(self.handle), ptr_arr, stride_arr, len(ptrs), proofs, _ptr(dyn), dyn.shape[0] // proofs, seg.bit_length() - 1, segments,
+            ctypes.c_void_p(values.data_ptr()), values.stride(0) * 2 if proofs > 1 else size * 8,
+            _lib.HM_GRAPH_COLUMNS_INTERNAL if columns_internal else 0, ctypes.c_void_p(_stream_ptr(values))))
 
     def _quotient_args(self, domain, coeff_columns, cosets, challenges, beta, gamma, theta, y, on_cosets, who):
         cosets = list(range(domain.min_cosets())) if cosets is None else [int(c) for c in cosets]

@@ -190,6 +190,49 @@ def set_quotient(polys, weights, points, scale: int = 1, out=None, accumulate: b
     return out
 
 
+def set_quotient_batch(polys, weights, points, scales, outs=None, accumulate: bool = False):
+    """``set_quotient`` for a batch of independent proofs in ONE launch chain (``hm_shplonk_set_quotient_batch_bn256_fr_dev``): per proof b
+    ``polys[b]`` (the same count m for all; the same tensor may occur in several proofs), ``weights[b]``, ``points[b]`` (the same
+    count t for all) and ``scales[b]``.  ``outs[b]`` may be one of proof b's own inputs, never another proof's input or output.
+    Returns the list of outputs (new tensors when ``outs`` is None), word for word the loop of ``set_quotient``."""
+    import torch
+
+    polys = [list(p) for p in polys]
+    proofs = len(polys)
+    if proofs == 0:
+        return []
+    m = len(polys[0])
+    if m == 0 or any(len(p) != m for p in polys):
+        raise ValueError("set_quotient_batch: every proof needs the same number (>= 1) of polynomials")
+    if len(weights) != proofs or any(len(w) != m for w in weights):
+        raise ValueError("set_quotient_batch: one weight per polynomial")
+    if len(points) != proofs or len(scales) != proofs:
+        raise ValueError("set_quotient_batch: one point set and one scale per proof")
+    pts = [_check_points(p) for p in points]
+    t = len(pts[0])
+    if any(len(p) != t for p in pts):
+        raise ValueError("set_quotient_batch: every proof needs the same number of points")
+    n = _tensor_rows(polys[0][0], 4, "polys") if _is_tensor(polys[0][0]) else -1
+    for p in (q for row in polys for q in row):
+        if not _is_tensor(p) or _tensor_rows(p, 4, "polys") != n:
+            raise ValueError("set_quotient_batch: polynomials must be GPU tensors of one length")
+    if n < t + 1:
+        raise ValueError("set_quotient_batch: need n >= t + 1")
+    if outs is None:
+        if accumulate:
+            raise ValueError("set_quotient_batch: nothing to accumulate into")
+        outs = list(torch.empty((proofs, n, 4), dtype=torch.int64, device=polys[0][0].device))
+    elif len(outs) != proofs or any(not _is_tensor(o) or _tensor_rows(o, 4, "outs") != n for o in outs):
+        raise ValueError("set_quotient_batch: one output of the polynomials' length per proof")
+    outs = list(outs)
+    with torch.cuda.device(outs[0].device):
+        _lib.check(_lib.load().hm_shplonk_set_quotient_batch_bn256_fr_dev(
+            _ptr_array([p for row in polys for p in row]), _ptr(fr_array([[int(w) % R for w in row] for row in weights])), m, n,
+            _ptr(fr_array(pts)), t, _ptr(fr_array([int(s) % R for s in scales])), _ptr_array(outs), 1 if accumulate else 0, proofs,
+            ctypes.c_void_p(_stream_ptr(outs[0]))))
+    return outs
+
+
 # ---- prover and verifier ----------------------------------------------------------------------------------------------------------------
 g1_words_to_int = g1_ints        # 12 (or 8) Montgomery words of a normalised G1 -> (x, y) integers, None for the identity
 
@@ -224,6 +267,63 @@ def create_opening(params, transcript, queries, polys: dict) -> None:
             weights.append(pow(v, i, R) * z_i % R * pow(y, j, R) % R)
     final = set_quotient(cols + [h], weights + [-zt % R], [u], scale=pow(z0, -1, R))
     transcript.write_point(g1_words_to_int(params.commit(final)))
+
+
+def create_openings(params, transcripts, queries_per_proof, polys_per_proof) -> None:
+    """``create_opening`` for m independent proofs of one structure, every device step batched over the proofs: one
+    ``set_quotient_batch`` per rotation set, one for the final division, and two ``best_multiexp_batch`` calls.  ``transcripts[b]``,
+    ``queries_per_proof[b]`` and ``polys_per_proof[b]`` are what ``create_opening`` takes for proof b.  Every proof lists the same keys at
+    the same rotations in the same order, so the rotation sets -- which keys, in what order, and which of a proof's queries gives
+    each point -- are derived once, from proof 0; the points themselves differ per proof.  (A set's quotient and a vanishing product
+    are symmetric in the points, so the integer order of proof 0's points serves every proof.)"""
+    from .arithmetic import best_multiexp_batch
+
+    m = len(transcripts)
+    if m == 0:
+        return
+    if len(queries_per_proof) != m or len(polys_per_proof) != m:
+        raise ValueError("create_openings: one query list and one polynomial table per transcript")
+    q0 = [(key, int(pt) % R) for key, pt, _ in queries_per_proof[0]]
+    for qs in queries_per_proof:
+        if [key for key, _, _ in qs] != [key for key, _ in q0]:
+            raise ValueError("create_openings: every proof must list the same keys in the same order")
+    rotation_sets, super_points = construct_intermediate_sets(queries_per_proof[0])
+    where = {}                                             # proof 0's point -> the first query that names it
+    for i, (_, pt) in enumerate(q0):
+        where.setdefault(pt, i)
+    point = lambda b, pt0: int(queries_per_proof[b][where[pt0]][1]) % R
+    sets = [([where[p] for p in pts], [key for key, _ in members]) for pts, members in rotation_sets]
+    for b in range(m):
+        if len({point(b, p) for p in super_points}) != len(super_points):
+            raise ValueError(f"create_openings: proof {b}'s points do not have the structure of proof 0's")
+    ys = [tr.squeeze_challenge() for tr in transcripts]
+    vs = [tr.squeeze_challenge() for tr in transcripts]
+    hs = None
+    for i, (at, keys) in enumerate(sets):
+        hs = set_quotient_batch([[polys_per_proof[b][key] for key in keys] for b in range(m)], [_powers(ys[b], len(keys)) for b in range(m)],
+                                [[int(queries_per_proof[b][q][1]) % R for q in at] for b in range(m)], [pow(vs[b], i, R) for b in range(m)],
+                                outs=hs, accumulate=i > 0)
+    for tr, com in zip(transcripts, best_multiexp_batch(hs, params.g_handle)):
+        tr.write_point(g1_words_to_int(com))
+    us = [tr.squeeze_challenge() for tr in transcripts]
+    cols, weights, scales = [], [], []
+    for b in range(m):
+        sp = [point(b, p) for p in super_points]
+        zt = vanishing_eval(sp, us[b])
+        cb, wb, z0 = [], [], None
+        for i, (at, keys) in enumerate(sets):
+            mine = {int(queries_per_proof[b][q][1]) % R for q in at}
+            z_i = vanishing_eval([p for p in sp if p not in mine], us[b])
+            z0 = z_i if i == 0 else z0
+            for j, key in enumerate(keys):
+                cb.append(polys_per_proof[b][key])
+                wb.append(pow(vs[b], i, R) * z_i % R * pow(ys[b], j, R) % R)
+        cols.append(cb + [hs[b]])
+        weights.append(wb + [-zt % R])
+        scales.append(pow(z0, -1, R))
+    finals = set_quotient_batch(cols, weights, [[u] for u in us], scales)
+    for tr, com in zip(transcripts, best_multiexp_batch(finals, params.g_handle)):
+        tr.write_point(g1_words_to_int(com))
 
 
 def verify_opening(transcript, queries, commitments: dict):

@@ -17,7 +17,7 @@ from .arithmetic import (bases_info, batch_invert, best_fft, best_multiexp, best
                          best_multiexp_wait, eval_polynomial, g1_check, g1_check_host, g1_compress, g1_compress_host,
                          g1_decompress, g1_decompress_host, g1_fft, g1_fft_host, g1_fixed_base_mul, g_to_lagrange, grand_product, grand_product_batch, kate_division,
                          kate_division_batch,
-                         linear_combination, msm_stats, permute_expression_pair, permute_expression_pairs, random_fr, register_bases,
+                         linear_combination, linear_combination_batch, msm_stats, permute_expression_pair, permute_expression_pairs, random_fr, register_bases,
                          release_bases)
 from .batch_verifier import BatchVerifier, verify_proofs  # noqa: F401
 from .domain import EvaluationDomain  # noqa: F401
@@ -26,8 +26,8 @@ from .keygen import (ProvingKey, VerifyingKey, copy_pairs, keygen_pk, keygen_vk,
 from .mock_prover import MockProver, MockResult, NotSatisfied  # noqa: F401
 from .pairing import pairing_check  # noqa: F401
 from .poseidon import MerkleSumTree, MerkleTree, Spec, poseidon_hash, poseidon_hash_host, update_plan  # noqa: F401
-from .prover import create_proof, create_proof_multi  # noqa: F401
-from .shplonk import construct_intermediate_sets, set_quotient, set_quotient_ints  # noqa: F401
+from .prover import create_proof, create_proof_multi, create_proofs  # noqa: F401
+from .shplonk import construct_intermediate_sets, create_openings, set_quotient, set_quotient_batch, set_quotient_ints  # noqa: F401
 from .synthesis import (MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, merkle_sum_witness,  # noqa: F401
                         merkle_sum_witness_host, merkle_witness, merkle_witness_host, permutation_columns, poseidon_circuit_witness,
                         poseidon_circuit_witness_host)
@@ -43,5 +43,5 @@ __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_mult
            "merkle_sum_witness_host", "permutation_columns", "MerkleTreeV3Layout", "PoseidonCircuitLayout", "merkle_witness",
            "merkle_witness_host", "poseidon_circuit_witness", "poseidon_circuit_witness_host", "copy_pairs", "permutation_cells_dev",
            "permutation_columns_dev", "keygen_vk", "keygen_pk", "VerifyingKey", "ProvingKey",
-           "create_proof", "create_proof_multi", "verify_proof", "verify_proof_multi", "Blake2bWrite", "Blake2bRead", "pairing_check", "construct_intermediate_sets",
-           "set_quotient", "set_quotient_ints", "MockProver", "MockResult", "NotSatisfied", "BatchVerifier", "verify_proofs"]
+           "create_proof", "create_proof_multi", "create_proofs", "verify_proof", "verify_proof_multi", "Blake2bWrite", "Blake2bRead", "pairing_check", "construct_intermediate_sets",
+           "set_quotient", "set_quotient_batch", "set_quotient_ints", "create_openings", "linear_combination_batch", "MockProver", "MockResult", "NotSatisfied", "BatchVerifier", "verify_proofs"]

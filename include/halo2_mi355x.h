@@ -375,6 +375,21 @@ int hm_fr_linear_combination_dev(const void* const* d_polys, const uint64_t* coe
 int hm_shplonk_set_quotient_bn256_fr_dev(const void* const* d_polys, const uint64_t* weights, size_t m, size_t n, const uint64_t* points,
                                          size_t t, const uint64_t scale[4], void* d_out, int accumulate, void* stream);
 
+/* The two entries above for a batch of `proofs` INDEPENDENT proofs of one structure (count / m, t and n the same for all, the values
+ * each proof's own), word for word the loop of the single entry over b, as ONE launch chain whose grid has a proof dimension:
+ *   d_polys: host array of proofs x count (proofs x m) device pointers, proof b's at [b * count, (b + 1) * count); the same pointer may
+ *   occur in several proofs (the fixed and permutation polynomials of a proving key do);  coeffs / weights: host, proofs x count x 4 u64;
+ *   points: host, proofs x t x 4 u64;  scales: host, proofs x 4 u64;  d_outs: host array of `proofs` device pointers.
+ * The per-proof coefficients, points and partial fractions travel in a device table uploaded with the call, and all proofs share one
+ * stream-ordered workspace allocation.  d_outs[b] may be one of proof b's own inputs.  HM_ERR_BAD_ARG with nothing launched and every
+ * output untouched: what the single entry refuses, in any proof; d_outs[b] equal to another proof's input or output; proofs = 0
+ * (set quotient) or proofs > 65535.  Asynchronous on `stream`. */
+int hm_fr_linear_combination_batch_dev(const void* const* d_polys, const uint64_t* coeffs, size_t count, size_t n, void* const* d_outs,
+                                       size_t proofs, void* stream);
+int hm_shplonk_set_quotient_batch_bn256_fr_dev(const void* const* d_polys, const uint64_t* weights, size_t m, size_t n, const uint64_t* points,
+                                               size_t t, const uint64_t* scales, void* const* d_outs, int accumulate, size_t proofs,
+                                               void* stream);
+
 /* The permuted columns of one lookup argument (upstream plonk/lookup/prover.rs: permute_expression_pair): from the first
  * `rows` (= usable rows) entries of the compressed input and table columns, d_permuted_input[0 .. rows) = the input values
  * sorted by their canonical integers, d_permuted_table[0 .. rows) = the table values arranged so that every row where the
@@ -484,6 +499,18 @@ int hm_graph_evaluate_segments_dev(uint64_t handle, const void* const* d_columns
 int hm_graph_evaluate_circuits_dev(uint64_t handle, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
                                    size_t circuits, const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t log_size, uint32_t segments,
                                    void* d_values, uint32_t flags, void* stream);
+
+/* Several INDEPENDENT proofs of one constraint system in one launch, each with its own per-call constants (the theta, beta, gamma, y
+ * of its own transcript): for every b < proofs the call leaves in d_values + b * values_stride (u32 words) what
+ * hm_graph_evaluate_segments_dev leaves when it is called with row b of dynamic_constants (host, proofs x n_dynamic x 4 u64) and with
+ * column i at column_bases[i] + b * column_strides[i] (u32 words; 0: one column for all proofs).  PreviousValue is read from proof b's
+ * own values; nothing is folded across proofs, and ANY program is admitted.  One lane per (proof, row); a rotation wraps inside its
+ * segment of its own proof.  Bases and d_values 16-byte aligned, strides multiples of 4 words, proofs * rows <= 2^32.
+ * HM_ERR_BAD_ARG, nothing launched: proofs == 0, a values_stride below the rows of one proof (8 words a row) unless proofs == 1, a
+ * misaligned base or stride, counts other than the program's. */
+int hm_graph_evaluate_proofs_dev(uint64_t handle, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
+                                 size_t proofs, const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t log_size, uint32_t segments,
+                                 void* d_values, uint64_t values_stride, uint32_t flags, void* stream);
 
 /* Inputs and known answer of the benchmark of SURVEY.md §8d, without leaving the device:
  *   hm_fr_random_dev           out[i] uniform in [0, r) (Fr::random): one xoshiro256** stream per element, seeded by

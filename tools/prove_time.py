@@ -11,6 +11,11 @@
     19): create_proof_multi against m separate create_proof calls in the same run, and the h step alone -- the undivided numerator over
     the extended domain through CompiledGraph.evaluate_circuits against the loop of m evaluate calls on the same columns (equal word for
     word).
+(d) ``--proofs m[,m...]``: instead, m users' witnesses at depth 20 / k = 10 and depth 5 / k = 9: create_proofs -- m
+    independent proofs in one batched pass -- against the loop of m create_proof calls in the same run (the bytes are compared), and two
+    of its steps alone, each against its loop: the h numerator through CompiledGraph.evaluate_proofs against m evaluate calls with
+    per-proof constants on the same columns, and the multiopen (shplonk.create_openings inside create_proofs against the m
+    create_opening calls inside the loop, both timed in a second pass of their own).
 Five repeats each: median and min .. max.  Prints one JSON object."""
 import argparse
 import json
@@ -138,6 +143,90 @@ def multi(name, m):
     return out
 
 
+def h_step_proofs(cs, dom, m):
+    """the numerator of h for m independent proofs on random extended columns, laid out as create_proofs lays them out (what a proof
+    owns stacked per proof, the rest shared at stride 0), every proof with its own beta, gamma, theta, y"""
+    from halo2_experiments_amd.keygen import FR_DELTA
+    g, lay = circuits.evaluate_h_program(cs, dom.k, dom.extended_k, FR_DELTA, divide=False)
+    en, scale = dom.extended_len(), 1 << (dom.extended_k - dom.k)
+    n_cols = lay.num_fixed_entries + cs.num_advice + cs.num_instance
+    nsets, L = cs.permutation_sets(), len(cs.lookups)
+    own = set(range(lay.z0, lay.z0 + nsets)) | set(range(lay.lookup0, lay.lookup0 + 3 * L)) | set(range(lay.num_fixed_entries, n_cols))
+    cols = [h.random_fr(m * en, 50 + i, shape=(m, en, 4)) if i in own else h.random_fr(scale if i == lay.t_inv else en, 50 + i) for i in range(n_cols)]
+    rng = random.Random(m)
+    scalars = [dict(beta=rng.randrange(R), gamma=rng.randrange(R), theta=rng.randrange(R), y=rng.randrange(R)) for _ in range(m)]
+    prog = g.compile(lay.num_fixed_entries, cs.num_advice, cs.num_instance, rot_scale=scale, short_columns=lay.short_columns)
+    per_proof = [[col[b] if i in own else col for i, col in enumerate(cols)] for b in range(m)]
+    zeros = lambda: torch.zeros((m, en, 4), dtype=torch.int64, device="cuda")
+
+    def loop():
+        values = zeros()
+        for b in range(m):
+            prog.evaluate(per_proof[b], values[b], **scalars[b])
+        return values
+
+    def entry():
+        values = zeros()
+        prog.evaluate_proofs(cols, values, scalars)
+        return values
+    try:
+        assert torch.equal(loop(), entry()), "the entry and the loop differ"
+        one, many = [], []
+        for _ in range(REPEATS):
+            many.append(wall(loop)[1])
+            one.append(wall(entry)[1])
+    finally:
+        prog.destroy()
+    return {"rows": en, "lanes": m * en, "program_calculations": int(prog.calcs.shape[0]), "evaluate_proofs": spread(one),
+            "loop_of_evaluate": spread(many)}
+
+
+def proofs(name, m):
+    cs, lay, advice, instances = pmc.build_multi(name, m)
+    params = ParamsKZG.setup(lay.k, pc.SRS_S)
+    vk = h.keygen_vk(params, cs, lay)
+    pk = h.keygen_pk(params, vk, cs, lay, cosets=False)
+    seeds = lambda rep: [1000 * rep + b for b in range(m)]
+    batched = lambda rep: h.create_proofs(params, pk, advice, instances, seeds(rep))
+    looped = lambda rep: [h.create_proof(params, pk, advice[b], instances[b], seeds(rep)[b]) for b in range(m)]
+    inner = []
+    real_one, real_many = prover.create_opening, prover.create_openings
+
+    def timed(real):
+        def run(*a, **kw):
+            inner.append(wall(lambda: real(*a, **kw))[1])
+        return run
+    try:
+        assert batched(1) == looped(1), "create_proofs and the loop of create_proof differ"      # and the warm-up of both
+        one, separate = [], []
+        for rep in range(REPEATS):
+            out, ms = wall(lambda: batched(2 + rep))
+            one.append(ms)
+            _, ms = wall(lambda: looped(2 + rep))
+            separate.append(ms)
+        ok, verify_ms = wall(lambda: h.verify_proofs(params, vk, instances, out))
+        assert ok
+        # the multiopen alone, in a pass of its own: the synchronisation around it would count against the totals above
+        prover.create_opening, prover.create_openings = timed(real_one), timed(real_many)
+        open_batched, open_looped = [], []
+        for rep in range(REPEATS):
+            inner.clear()
+            batched(2 + rep)
+            open_batched.append(sum(inner))
+            inner.clear()
+            looped(2 + rep)
+            open_looped.append(sum(inner))
+        res = {"k": lay.k, "proofs": m, "proof_bytes": len(out[0]), "create_proofs": spread(one), "loop_of_create_proof": spread(separate),
+               "per_proof_ms": {"create_proofs": round(statistics.median(one) / m, 3), "loop": round(statistics.median(separate) / m, 3)},
+               "verify_proofs_once_ms": round(verify_ms, 3),
+               "multiopen": {"create_openings": spread(open_batched), "loop_of_create_opening": spread(open_looped)},
+               "h_step": h_step_proofs(cs, vk.domain, m)}
+    finally:
+        prover.create_opening, prover.create_openings = real_one, real_many
+        params.release()
+    return res
+
+
 def k18_sets():
     """the rotation sets of the MerkleSumTree constraint system as (points, keys), with the prover's order of queries"""
     cs = circuits.merkle_sum_tree(ps.default_spec(5))
@@ -213,8 +302,14 @@ def multiopen_k18():
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--circuits", type=int, default=0, help="m: time create_proof_multi and the h step for m circuits (1 .. 64) instead")
+    ap.add_argument("--proofs", default="", help="m[,m...]: time create_proofs against the loop of m create_proof calls, with the h step and the "
+                    "multiopen split out, for every listed m instead")
     args = ap.parse_args()
     torch.cuda.init()
+    if args.proofs:
+        print(json.dumps({f"proofs_{m}": {name: proofs(name, int(m)) for name in ("merkle_sum_d20_k10", "merkle_sum_d5_k9")}
+                          for m in args.proofs.split(",")}))
+        sys.exit(0)
     if args.circuits:
         print(json.dumps({name: multi(name, args.circuits) for name in ("merkle_sum_d20_k10", "merkle_sum_d5_k9")}))
         sys.exit(0)
