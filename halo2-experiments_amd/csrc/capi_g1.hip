@@ -1,5 +1,5 @@
-// capi_g1.hip -- the G1 entry points of the C ABI outside the MSM: fixed-base multiples, best_fft over G1 (g1_fft.inc) and the SRS point
-// encodings (g1_codec.inc).
+// capi_g1.hip -- the G1 entry points of the C ABI outside the MSM: fixed-base multiples, best_fft over G1 (g1_fft.inc), all KZG openings
+// of a polynomial (kzg_open.inc) and the SRS point encodings (g1_codec.inc).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -39,6 +39,44 @@ int hm_g1_fft_bn256(uint64_t* points_xyz, const uint64_t omega[4], uint32_t log_
   return host_round_trip("hm_g1_fft_bn256", *ctx, "g1_fft", bytes, &in, 1, &out, 1,
                          [&](uint8_t* d) { return g1_fft_run(*ctx, (uint32_t*)d, 24, omega, log_n, scale, nullptr); });
 } HM_API_CATCH("hm_g1_fft_bn256")
+
+// ---- all KZG openings of a polynomial on its domain (kzg_open.inc) ---------------------------------------------------------------
+int hm_kzg_open_table_bn256_dev(const void* d_g_xy, uint32_t log_n, void* d_table_xy, void* stream) try {
+  if (!d_g_xy || !d_table_xy) return hm_fail(HM_ERR_BAD_ARG, "hm_kzg_open_table_bn256_dev: null argument");
+  if (log_n > 23) return hm_fail(HM_ERR_BAD_ARG, "hm_kzg_open_table_bn256_dev: log_n > 23");
+  if (ranges_overlap(d_g_xy, (size_t)64 << log_n, d_table_xy, (size_t)128 << log_n))
+    return hm_fail(HM_ERR_BAD_ARG, "hm_kzg_open_table_bn256_dev: the table overlaps the points");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return kzg_open_table_run(*ctx, (const uint32_t*)d_g_xy, log_n, (uint32_t*)d_table_xy, (hipStream_t)stream);
+} HM_API_CATCH("hm_kzg_open_table_bn256_dev")
+
+static int kzg_open_all_entry(const char* who, const void* d_table_xy, const void* d_coeffs, uint32_t log_n, size_t count, void* d_proofs_xy,
+                              double* part_ms, void* stream) {
+  if (!d_table_xy || (count && (!d_coeffs || !d_proofs_xy))) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (log_n > 23) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": log_n > 23");
+  if (count > 65535) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": count > 65535");
+  const size_t n = (size_t)1 << log_n;
+  if (count && (ranges_overlap(d_proofs_xy, count * n * 64, d_table_xy, n * 128) || ranges_overlap(d_proofs_xy, count * n * 64, d_coeffs, count * n * 32)))
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the proofs overlap an input");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return kzg_open_all_run(*ctx, (const uint32_t*)d_table_xy, (const uint32_t*)d_coeffs, log_n, count, (uint32_t*)d_proofs_xy,
+                          (hipStream_t)stream, part_ms);
+}
+
+int hm_kzg_open_all_bn256_dev(const void* d_table_xy, const void* d_coeffs, uint32_t log_n, size_t count, void* d_proofs_xy,
+                              void* stream) try {
+  return kzg_open_all_entry("hm_kzg_open_all_bn256_dev", d_table_xy, d_coeffs, log_n, count, d_proofs_xy, nullptr, stream);
+} HM_API_CATCH("hm_kzg_open_all_bn256_dev")
+
+int hm_kzg_open_all_timed_bn256_dev(const void* d_table_xy, const void* d_coeffs, uint32_t log_n, size_t count, void* d_proofs_xy,
+                                    double out_part_ms[7], void* stream) try {
+  if (!out_part_ms || count == 0) return hm_fail(HM_ERR_BAD_ARG, "hm_kzg_open_all_timed_bn256_dev: null argument or no polynomial");
+  return kzg_open_all_entry("hm_kzg_open_all_timed_bn256_dev", d_table_xy, d_coeffs, log_n, count, d_proofs_xy, out_part_ms, stream);
+} HM_API_CATCH("hm_kzg_open_all_timed_bn256_dev")
 
 // ---- SRS point encodings (g1_codec.inc) --------------------------------------------------------------------------------------
 static constexpr size_t G1_CODEC_MAX_N = (size_t)1 << 30;

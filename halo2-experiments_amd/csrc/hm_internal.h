@@ -546,6 +546,13 @@ int g1_fixed_base_mul_run(DeviceCtx& ctx, const uint32_t* d_scalars_ext, size_t 
 // Jacobian external (z = 0 = identity; outputs (x, y, 1) / zeros).  scale_ext: optional Fr Montgomery words multiplied into every output.
 int g1_fft_run(DeviceCtx& ctx, uint32_t* d_points, uint32_t words, const uint64_t omega_ext[4], uint32_t log_n,
                const uint64_t* scale_ext, hipStream_t stream);
+// All KZG openings of a polynomial on its domain (kzg_open.inc; FK20), n = 2^log_n <= 2^23, asynchronous on `stream`.  table: the
+// G1 FFT of size 2n of the reversed first n monomial points (16-word affine external, (0, 0) = identity), written from them by
+// kzg_open_table_run; open_all: `count` polynomials of n x 8 Fr words back to back -> count x n affine proofs, proof t the opening at
+// omega_n^t.  part_ms: null, or 7 doubles for the step times of the last polynomial (the call then waits for `stream`).
+int kzg_open_table_run(DeviceCtx& ctx, const uint32_t* d_g_xy, uint32_t log_n, uint32_t* d_table_xy, hipStream_t stream);
+int kzg_open_all_run(DeviceCtx& ctx, const uint32_t* d_table_xy, const uint32_t* d_coeffs, uint32_t log_n, size_t count,
+                     uint32_t* d_proofs_xy, hipStream_t stream, double* part_ms = nullptr);
 // SRS point encodings (g1_codec.inc): 16-word affine external points <-> 8-word compressed encodings.  compress is asynchronous;
 // decompress / check wait for `stream` and answer HM_ERR_INVALID_DATA with the smallest invalid index in *first_invalid (n if none).
 int g1_compress_run(const uint32_t* d_xy, size_t n, uint32_t* d_out32, hipStream_t stream);

@@ -1676,6 +1676,7 @@ __global__ __launch_bounds__(ACC_THREADS) void g1_fixed_base_mul_kernel(const ui
 }
 
 #include "g1_fft.inc"   // best_fft over G1: g1_fft_run below
+#include "kzg_open.inc" // all KZG openings of a polynomial on its domain (FK20): kzg_open_table_run / kzg_open_all_run
 #include "g1_codec.inc" // SRS point encodings: g1_compress_run / g1_decompress_run / g1_check_run below
 #include "verify_read.inc" // a batch of proofs read slot by slot, and the column sums of its shared scalars: verify_*_run below
 

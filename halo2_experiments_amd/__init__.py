@@ -5,7 +5,7 @@ Host-side mirror of ``halo2_proofs::arithmetic`` (``best_multiexp``, ``best_fft`
 
 The sources live in ``halo2-experiments_amd/`` (the directory name the project layout prescribes; not a valid
 Python identifier): this package is the importable name, and its ``__path__`` points there, so every submodule
-(``_header``, ``_lib``, ``_marshal``, ``arithmetic``, ``batch_verifier``, ``bn256``, ``domain``, ``keygen``, ``kzg``, ``mock_prover``, ``pairing``, ``poseidon``, ``prover``, ``replay``, ``sharding``, ``shplonk``, ``synthesis``, ``transcript``, ``verifier``) is an ordinary module of this package
+(``_header``, ``_lib``, ``_marshal``, ``arithmetic``, ``batch_verifier``, ``bn256``, ``domain``, ``keygen``, ``kzg``, ``mock_prover``, ``openings``, ``pairing``, ``poseidon``, ``prover``, ``replay``, ``sharding``, ``shplonk``, ``synthesis``, ``transcript``, ``verifier``) is an ordinary module of this package
 with an ordinary ``__spec__`` / ``__file__``.
 """
 import os as _os
@@ -24,6 +24,7 @@ from .domain import EvaluationDomain  # noqa: F401
 from .keygen import (ProvingKey, VerifyingKey, copy_pairs, keygen_pk, keygen_vk, permutation_cells_dev,  # noqa: F401
                      permutation_columns_dev)
 from .mock_prover import MockProver, MockResult, NotSatisfied  # noqa: F401
+from .openings import OpeningTable, open_all, open_all_ints, open_at, verify_opening, verify_openings  # noqa: F401
 from .pairing import pairing_check  # noqa: F401
 from .poseidon import MerkleSumTree, MerkleTree, Spec, poseidon_hash, poseidon_hash_host, update_plan  # noqa: F401
 from .prover import create_proof, create_proof_multi, create_proofs  # noqa: F401
@@ -44,4 +45,5 @@ __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_mult
            "merkle_witness_host", "poseidon_circuit_witness", "poseidon_circuit_witness_host", "copy_pairs", "permutation_cells_dev",
            "permutation_columns_dev", "keygen_vk", "keygen_pk", "VerifyingKey", "ProvingKey",
            "create_proof", "create_proof_multi", "create_proofs", "verify_proof", "verify_proof_multi", "Blake2bWrite", "Blake2bRead", "pairing_check", "construct_intermediate_sets",
-           "set_quotient", "set_quotient_batch", "set_quotient_ints", "create_openings", "linear_combination_batch", "MockProver", "MockResult", "NotSatisfied", "BatchVerifier", "verify_proofs"]
+           "set_quotient", "set_quotient_batch", "set_quotient_ints", "create_openings", "linear_combination_batch", "MockProver", "MockResult", "NotSatisfied", "BatchVerifier", "verify_proofs",
+           "OpeningTable", "open_all", "open_all_ints", "open_at", "verify_opening", "verify_openings"]

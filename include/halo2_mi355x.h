@@ -544,6 +544,26 @@ int hm_g1_fft_bn256_dev(void* d_points_xy, const uint64_t omega[4], uint32_t log
  * the device: every error code but HM_ERR_PARTIAL_OUTPUT (that copy itself failed) leaves it exactly as it was. */
 int hm_g1_fft_bn256(uint64_t* points_xyz, const uint64_t omega[4], uint32_t log_n, const uint64_t* scale);
 
+/* ---- All KZG openings of a polynomial on its domain (Feist / Khovratovich, "FK20") ---------------------------------------- */
+
+/* f = sum_{j<n} f_j X^j with n = 2^log_n <= 2^23, g[i] = [s^i]G1 the monomial SRS points, omega the 2^log_n-th root of unity of
+ * EvaluationDomain (ROOT_OF_UNITY squared 28 - log_n times).  Proof t is the opening of the commitment of f at omega^t:
+ * [(f(s) - f(omega^t)) / (s - omega^t)]G1.  All n of them cost one Fr NTT of size 2n, 2n scalar multiplications and two FFTs over
+ * G1 (sizes 2n and n).  Points are n x 8 u64 affine Montgomery, (0,0) = identity, as for hm_g1_fft_bn256_dev; device pointers;
+ * asynchronous on `stream`; working memory is allocated per call, stream-ordered on `stream`.
+ *
+ * table: from the first n points of g, the 2n points the other call multiplies into (the G1 FFT of size 2n of g reversed and padded
+ *        with identities) -- the SRS alone, built once per size.  d_table_xy: 2n x 8 u64; it may not overlap d_g_xy.
+ * open_all: `count` <= 65535 polynomials in coefficient form, back to back at d_coeffs (count x n x 4 u64 Montgomery) ->
+ *        count x n proofs at d_proofs_xy, row t of a polynomial its opening at omega^t.  The output may overlap neither input.
+ * open_all_timed: the same, and out_part_ms receives the device milliseconds of the LAST polynomial's seven steps (coefficient
+ *        arrangement, NTT, load-multiply, the stages of size 2n, truncation, the stages of size n, store); waits for `stream`.
+ * HM_ERR_BAD_ARG for a null pointer, log_n > 23, count > 65535 or overlapping input and output. */
+int hm_kzg_open_table_bn256_dev(const void* d_g_xy, uint32_t log_n, void* d_table_xy, void* stream);
+int hm_kzg_open_all_bn256_dev(const void* d_table_xy, const void* d_coeffs, uint32_t log_n, size_t count, void* d_proofs_xy, void* stream);
+int hm_kzg_open_all_timed_bn256_dev(const void* d_table_xy, const void* d_coeffs, uint32_t log_n, size_t count, void* d_proofs_xy,
+                                    double out_part_ms[7], void* stream);
+
 /* ---- SRS point encodings: ParamsKZG::read / write (compressed G1 and the checked raw format) ---------------------------- */
 
 /* Compressed G1, 32 bytes: canonical x little-endian (Fq::to_bytes), bit 7 of byte 31 = parity of canonical y; the identity is 32
