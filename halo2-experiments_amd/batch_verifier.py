@@ -40,11 +40,11 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib, evaluation as ev
+from . import _lib, device_pairing, evaluation as ev
 from .bn256 import FQ_MODULUS, FR_MODULUS, fr_array, g1_words
 from .keygen import FR_DELTA, VerifyingKey
 from .kzg import g2_from_bytes
-from .pairing import G1_GEN, g1_mul, g1_neg, g1_on_curve, pairing_check
+from .pairing import G1_GEN, g1_mul, g1_neg, g1_on_curve
 from .shplonk import g1_words_to_int
 from .transcript import PERSONAL, PREFIX_CHALLENGE, PREFIX_POINT, PREFIX_SCALAR, TranscriptError, g1_decompress_int
 from .verifier import _instance_columns, _vk_digest, evaluate_expression, proof_length
@@ -504,10 +504,14 @@ class BatchVerifier:
     sub-range of the batch on the device and makes one check, O(f log B) checks for f failing proofs.  Every proof has a weight r_b in
     [1, r): from ``secrets`` when ``seed`` is None, else derived from (seed, index); ``randomizers`` shows them.
     A batch of ``create_proof_multi`` proofs is out of scope, and an instance column may hold 64 rows at most (the terms kernel's
-    limit; ``finalize`` raises ValueError beyond it).  ``close()`` gives the numerator's program back to the library."""
+    limit; ``finalize`` raises ValueError beyond it).  ``close()`` gives the numerator's program back to the library.
+    ``pairing="device"`` runs the pairing of every check on the GPU (``device_pairing``) instead of on host integers: the same
+    booleans, and ``timings["pairing"]`` keeps its meaning."""
 
-    def __init__(self, params, vk: VerifyingKey, seed=None):
-        self.params, self.vk, self.seed = params, vk, seed
+    def __init__(self, params, vk: VerifyingKey, seed=None, pairing: str = "host"):
+        if pairing not in device_pairing.MODES:
+            raise ValueError(f"BatchVerifier: pairing must be one of {device_pairing.MODES}, got {pairing!r}")
+        self.params, self.vk, self.seed, self.pairing = params, vk, seed, pairing
         self.layout = ProofLayout(vk.cs, vk.domain.k)
         self._digest = _vk_digest(vk)
         self._shared = shared_points(vk, self.layout)
@@ -671,7 +675,7 @@ class BatchVerifier:
             ok = g1_mul(trapdoor, left) == right
         else:
             g2, s_g2 = g2_from_bytes(self.params.g2), g2_from_bytes(self.params.s_g2)
-            ok = g1_on_curve(left) and pairing_check([(left, s_g2), (g1_neg(right), g2)])
+            ok = g1_on_curve(left) and device_pairing.check([(left, s_g2), (g1_neg(right), g2)], self.pairing)
         self.timings["msm"] += t1 - t0
         self.timings["pairing"] += time.perf_counter() - t1
         return ok
@@ -718,12 +722,13 @@ class BatchVerifier:
         return sorted(out)
 
 
-def verify_proofs(params, vk: VerifyingKey, instances, proofs, seed=None, trapdoor: int = None) -> bool:
-    """True when every ``proofs[i]`` is a valid single-circuit proof of ``vk`` for ``instances[i]``: one ``BatchVerifier``, one check"""
+def verify_proofs(params, vk: VerifyingKey, instances, proofs, seed=None, trapdoor: int = None, pairing: str = "host") -> bool:
+    """True when every ``proofs[i]`` is a valid single-circuit proof of ``vk`` for ``instances[i]``: one ``BatchVerifier``, one check
+    (``pairing``: where that check's pairing runs, as on ``BatchVerifier``)"""
     instances, proofs = list(instances), list(proofs)
     if len(instances) != len(proofs):
         raise ValueError("verify_proofs: one instance per proof")
-    bv = BatchVerifier(params, vk, seed)
+    bv = BatchVerifier(params, vk, seed, pairing=pairing)
     for instance, proof in zip(instances, proofs):
         bv.add_proof(instance, proof)
     return bv.finalize(trapdoor)

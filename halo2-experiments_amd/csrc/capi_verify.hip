@@ -1,5 +1,6 @@
 // capi_verify.hip -- the batch verifier's entry points of the C ABI: the proofs of a batch read slot by slot on the device and the
-// column sums of their shared scalars (verify_read.inc), and the per-proof terms of the opening checks (verify_terms.inc).
+// column sums of their shared scalars (verify_read.inc), the per-proof terms of the opening checks (verify_terms.inc), and the pairing
+// product checks that end every verifier (pairing.inc).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -71,5 +72,29 @@ int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_word
                           (const uint32_t*)d_instance, d_bad, (uint32_t*)d_own, (uint32_t*)d_shared, (uint32_t*)d_h2_r, (uint32_t*)d_h2_l,
                           (hipStream_t)stream);
 } HM_API_CATCH("hm_verify_terms_dev")
+
+// ---- pairing product checks (pairing.inc, lookup.hip) ------------------------------------------------------------------------------
+static constexpr size_t PAIRING_MAX_CHECKS = (size_t)1 << 20, PAIRING_MAX_PAIRS = (size_t)1 << 24;
+
+size_t hm_pairing_work_bytes(size_t n_pairs, size_t n_checks) {
+  if (n_checks == 0 || n_checks > PAIRING_MAX_CHECKS || n_pairs > PAIRING_MAX_PAIRS) return 0;
+  return pairing_work_words(n_pairs, n_checks) * sizeof(uint32_t);
+}
+
+int hm_pairing_check_bn256_dev(const void* d_g1_xy, const void* d_g2_xy, size_t n_pairs, const uint32_t* d_offsets, size_t n_checks,
+                               void* d_gt, uint32_t* d_status, void* d_work, size_t work_bytes, void* stream) try {
+  const std::string who = "hm_pairing_check_bn256_dev";
+  if (!d_g1_xy || !d_g2_xy || !d_offsets || !d_status || !d_work) return hm_fail(HM_ERR_BAD_ARG, who + ": null argument");
+  if (n_checks == 0 || n_checks > PAIRING_MAX_CHECKS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n_checks <= 2^20");
+  if (n_pairs > PAIRING_MAX_PAIRS) return hm_fail(HM_ERR_BAD_ARG, who + ": need n_pairs <= 2^24");
+  if (work_bytes < hm_pairing_work_bytes(n_pairs, n_checks)) return hm_fail(HM_ERR_BAD_ARG, who + ": the workspace is shorter than hm_pairing_work_bytes");
+  if (((uintptr_t)d_g1_xy | (uintptr_t)d_g2_xy | (uintptr_t)d_gt | (uintptr_t)d_work) & 15u)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": a buffer is not 16-byte aligned");
+  if (((uintptr_t)d_offsets | (uintptr_t)d_status) & 3u) return hm_fail(HM_ERR_BAD_ARG, who + ": d_offsets / d_status is not 4-byte aligned");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return pairing_check_run((const uint32_t*)d_g1_xy, (const uint32_t*)d_g2_xy, n_pairs, d_offsets, n_checks, (uint32_t*)d_gt, d_status,
+                           (uint32_t*)d_work, (hipStream_t)stream);
+} HM_API_CATCH("hm_pairing_check_bn256_dev")
 
 }  // extern "C"

@@ -565,4 +565,10 @@ int verify_read_run(const uint32_t* d_proofs, size_t n_proofs, const uint32_t* d
                     uint32_t* d_bad, hipStream_t stream);
 int verify_colsum_run(const uint32_t* d_rows, uint32_t cols, size_t lo, size_t hi, uint32_t* d_out, hipStream_t stream);
 
+// pairing.inc (lookup.hip): the Miller loops of n_pairs pairs, then product and final exponentiation of n_checks checks, in d_work
+// (pairing_work_words u32 words); both launches asynchronous on `stream`
+size_t pairing_work_words(size_t n_pairs, size_t n_checks);
+int pairing_check_run(const uint32_t* d_g1, const uint32_t* d_g2, size_t n_pairs, const uint32_t* d_offsets, size_t n_checks, uint32_t* d_gt,
+                      uint32_t* d_status, uint32_t* d_work, hipStream_t stream);
+
 }  // namespace hm

@@ -24,6 +24,7 @@ namespace hm {
 #include "poseidon.inc"   // the per-hash Poseidon / Merkle node functions (likewise)
 #include "keygen.inc"     // the permutation assembly's key packing and link rule (likewise)
 #include "shplonk.inc"    // the SHPLONK set quotient's plan, coefficients and row formula (likewise)
+#include "pairing.inc"    // the pairing's tower, Miller lane and final exponentiation (likewise)
 }
 
 using namespace hm;
@@ -892,6 +893,90 @@ uint64_t hc_mock_record(uint32_t user, uint32_t index, uint32_t* user_back, uint
   *user_back = mock_record_user(rec);
   *index_back = mock_record_index(rec);
   return rec;
+}
+
+// The pairing (pairing.inc): an Fq12 travels as 48 u64, the canonical Montgomery words of its 12 Fq in pairing.py's coefficient order,
+// and stands in a slot of a one-lane workspace while the device's own functions run on it under bound tracking.
+namespace {
+void pf_slot_from_ext(const PfRef& d, const uint64_t* w) {
+  for (uint32_t c = 0; c < 12; ++c) pf_store(d, c * 8u, load_ext<FqParams>(w + 4 * c));
+}
+void pf_slot_to_ext(uint64_t* w, const PfRef& a) {
+  for (uint32_t c = 0; c < 12; ++c) store_ext(w + 4 * c, pf_load(a, c * 8u));
+}
+Fq2 f2_from_ext(const uint64_t* w) { return Fq2{load_ext<FqParams>(w), load_ext<FqParams>(w + 4)}; }
+}  // namespace
+
+// op 0: a b; 1: a^2; 2: a times the line b (only b's w^0, w^1, w^3 are read); 3: conj a; 4 / 5 / 6: a^p, a^(p^2), a^(p^3); 7: 1 / a;
+// 8: a b over b's even powers (with a's odd powers zero: the Fq6 product); 9: a^x and 11: a^2 for a in the cyclotomic subgroup; 10: the
+// final exponentiation of a.  -1: no such op.
+int hc_f12_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out) {
+  std::vector<uint32_t> ws((size_t)PF_CHECK_SLOTS * PF_WORDS, 0);
+  const PfLane lane{ws.data(), 1};
+  const PfRef x = lane.slot(0), y = lane.slot(1), d = lane.slot(2);
+  pf_slot_from_ext(x, a);
+  if (b) pf_slot_from_ext(y, b);
+  PfRef r = d;
+  switch (op) {
+    case 0: f12_mul<false>(d, x, y); break;
+    case 1: f12_mul<true>(d, x, x); break;
+    case 2: f12_mul<false>(d, x, y, PF_LINE_MASK); break;
+    case 3: f12_conj(x); r = x; break;
+    case 4: f12_frob<1>(d, x); break;
+    case 5: f12_frob<2>(d, x); break;
+    case 6: f12_frob<3>(d, x); break;
+    case 7: f12_inv(d, x, lane.slot(9), lane.slot(10)); break;
+    case 8: f12_mul<false>(d, x, y, 0x15u); break;
+    case 9: f12_pow_x(d, x, lane.slot(10)); break;
+    case 10: pf_final_exponentiation(lane); r = lane.slot(PF_RESULT); break;
+    case 11: f12_cyc_sqr(d, x); break;
+    default: return -1;
+  }
+  pf_slot_to_ext(out, r);
+  return 0;
+}
+
+// Fq2 on 8 u64 (c0, c1).  op 0: a b; 1: a^2; 2: 1 / a; 3: (9 + u) a; 4: a + b; 5: a - b; 6: conj a
+int hc_f2_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out) {
+  const Fq2 x = f2_from_ext(a), y = b ? f2_from_ext(b) : f2_zero();
+  Fq2 r;
+  switch (op) {
+    case 0: r = f2_mul(x, y); break;
+    case 1: r = f2_sqr(x); break;
+    case 2: r = f2_inv(x); break;
+    case 3: r = f2_mul_xi(x); break;
+    case 4: r = f2_add(x, y); break;
+    case 5: r = f2_sub(x, y); break;
+    case 6: r = f2_conj(x); break;
+    default: return -1;
+  }
+  store_ext(out, r.c0);
+  store_ext(out + 4, r.c1);
+  return 0;
+}
+
+// the compiled-in constants: 36 Frobenius factors (map n = 1 .. 3, power k = 0 .. 5, component c0 / c1), then b' of the twist: 38 x 4 u64
+void hc_pairing_constants(uint64_t* out) {
+  for (int i = 0; i < 36; ++i) store_ext(out + 4 * i, fe_const<FqParams>(PairingParams::FROB[i]));
+  store_ext(out + 144, fe_const<FqParams>(PairingParams::TWIST_B0));
+  store_ext(out + 148, fe_const<FqParams>(PairingParams::TWIST_B1));
+}
+
+// One whole check on host memory by the lane functions of the two kernels, in the kernels' layout (lane-minor, stride n_pairs):
+// g1 n_pairs x 8 u64, g2 n_pairs x 16 u64 -> the status (0 / 1 / 2) and the GT value (48 u64).
+int hc_pairing_product(const uint64_t* g1, const uint64_t* g2, size_t n_pairs, uint64_t* gt) {
+  std::vector<uint32_t> pair_ws((size_t)PF_PAIR_SLOTS * PF_WORDS * (n_pairs + 1), 0), flags(n_pairs + 1, 0);
+  std::vector<uint32_t> check_ws((size_t)PF_CHECK_SLOTS * PF_WORDS, 0);
+  for (size_t i = 0; i < n_pairs; ++i) {
+    uint32_t p[16], q[32];
+    std::memcpy(p, g1 + 8 * i, sizeof p);
+    std::memcpy(q, g2 + 16 * i, sizeof q);
+    flags[i] = pf_miller_lane(p, q, PfLane{pair_ws.data() + i, n_pairs});
+  }
+  uint32_t w[PF_WORDS];
+  const uint32_t status = pf_finish_lane(0, n_pairs, n_pairs, PfLane{pair_ws.data(), n_pairs}, flags.data(), PfLane{check_ws.data(), 1}, w);
+  std::memcpy(gt, w, sizeof w);
+  return (int)status;
 }
 
 }  // extern "C"

@@ -591,5 +591,6 @@ int lookup_permute_run(DeviceCtx& ctx, const void* const* d_inputs, const void* 
 #include "mock.inc"       // the batched witness checker: its lookup pass searches keys sorted by the code above
 #define HM_VERIFY_TERMS_KERNELS
 #include "verify_terms.inc"   // the batch verifier's per-proof terms: the same interpreter on one lane per proof
+#include "pairing.inc"        // batched pairing product checks: pairing_check_run / pairing_work_words
 
 }  // namespace hm

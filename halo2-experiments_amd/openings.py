@@ -28,7 +28,8 @@ from .arithmetic import InvalidPointError, best_multiexp, eval_polynomial, g1_ch
 from .bn256 import FR_MODULUS, FR_ROOT_OF_UNITY, FR_S, fr_array, fr_int, fr_words, g1_ints
 from .domain import EvaluationDomain
 from .kzg import g2_from_bytes
-from .pairing import G1_GEN, g1_add, g1_mul, g1_neg, g1_on_curve, pairing_check
+from . import device_pairing
+from .pairing import G1_GEN, g1_add, g1_mul, g1_neg, g1_on_curve
 
 R = FR_MODULUS
 LOG_N_MAX = 23                      # the circulant has 2n points and best_fft over G1 takes 2^24
@@ -162,19 +163,19 @@ def _point(p):
     return g1_ints(w.view(np.uint64) if w.dtype == np.int64 else w)
 
 
-def verify_opening(params, commitment, z, value, proof) -> bool:
+def verify_opening(params, commitment, z, value, proof, pairing: str = "host") -> bool:
     """e(pi, [s]G2) = e(C - [y]G + [z]pi, G2) on host integers: one pairing check, no G2 arithmetic.  ``commitment`` / ``proof``:
     (x, y) integers, None for the identity, or 8 / 12 affine words; ``z`` / ``value``: integers or 4 words.  A point off the curve
-    gives False."""
+    gives False.  ``pairing="device"`` runs the pairing check on the GPU (``device_pairing``): the same boolean."""
     c, pi = _point(commitment), _point(proof)
     if not g1_on_curve(c) or not g1_on_curve(pi):
         return False
     zz, y = _scalar_int(z), _scalar_int(value)
     rhs = g1_add(g1_add(c, g1_neg(g1_mul(y, G1_GEN))), g1_mul(zz, pi))
-    return pairing_check([(pi, g2_from_bytes(params.s_g2)), (g1_neg(rhs), g2_from_bytes(params.g2))])
+    return device_pairing.check([(pi, g2_from_bytes(params.s_g2)), (g1_neg(rhs), g2_from_bytes(params.g2))], pairing)
 
 
-def verify_openings(params, commitment, indices, values, proofs, seed=None, k: int = None) -> bool:
+def verify_openings(params, commitment, indices, values, proofs, seed=None, k: int = None, pairing: str = "host") -> bool:
     """The openings of one commitment at omega_n^(indices[b]) with the claimed ``values[b]`` and ``proofs[b]`` (a (B, 8) GPU tensor, as
     ``open_all`` returns it or rows gathered from it), checked together with one pairing: with weights r_b and n = 2^k (``k``
     defaults to params.k),
@@ -182,7 +183,8 @@ def verify_openings(params, commitment, indices, values, proofs, seed=None, k: i
         L = sum r_b pi_b,   R = (sum r_b) C - (sum r_b y_b) G + sum (r_b omega^(i_b)) pi_b,   e(L, [s]G2) = e(R, G2).
 
     The two sums over the proofs are MSMs on the device tensor, after ``g1_check``: an invalid point gives False.  r_b in [1, r) comes
-    from ``secrets`` when ``seed`` is None, else from (seed, b) as ``batch_verifier.derive_randomizer`` makes it."""
+    from ``secrets`` when ``seed`` is None, else from (seed, b) as ``batch_verifier.derive_randomizer`` makes it.
+    ``pairing="device"`` runs that one pairing check on the GPU (``device_pairing``): the same boolean."""
     from .batch_verifier import derive_randomizer
 
     k = params.k if k is None else int(k)
@@ -213,7 +215,7 @@ def verify_openings(params, commitment, indices, values, proofs, seed=None, k: i
     finally:
         release_bases(handle)
     right = g1_add(g1_add(g1_mul(sum(rs) % R, c), g1_neg(g1_mul(sum(r * y for r, y in zip(rs, ys)) % R, G1_GEN))), moved)
-    return pairing_check([(left, g2_from_bytes(params.s_g2)), (g1_neg(right), g2_from_bytes(params.g2))])
+    return device_pairing.check([(left, g2_from_bytes(params.s_g2)), (g1_neg(right), g2_from_bytes(params.g2))], pairing)
 
 
 # ---- the twin on host integers -------------------------------------------------------------------------------------------------------------

@@ -781,6 +781,26 @@ int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_word
                         const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad, void* d_own, void* d_shared,
                         void* d_h2_r, void* d_h2_l, void* stream);
 
+/* ---- pairing product checks: for every check c, is the product of e(P_i, Q_i) over its pairs 1? -------------------------------------
+ *
+ * The optimal ate pairing on BN256, one lane per pair for the Miller loops and one lane per check for the product and the final
+ * exponentiation.  d_g1_xy: n_pairs x 8 u64, affine Montgomery words, (0, 0) = the identity.  d_g2_xy: n_pairs x 16 u64, the
+ * Montgomery words of x.c0, x.c1, y.c0, y.c1 over Fq2 = Fq[u] / (u^2 + 1) on the twist y^2 = x^3 + 3 / (9 + u); sixteen zero words =
+ * the identity.  d_offsets: n_checks + 1 entries; check c owns the pairs [d_offsets[c], d_offsets[c + 1]).
+ * d_status[c]: 1 the product is 1 (an empty check, and one of identities only, is the product 1); 0 it is not; 2 the check holds a
+ * malformed pair -- a coordinate word >= p, a point off its curve (no subgroup check on G2) -- or its offsets decrease or pass
+ * n_pairs; such a pair is never multiplied in and nothing faults.  A pair with an identity on either side contributes 1.
+ * d_gt: NULL, or n_checks x 48 u64: the value after the final exponentiation, the canonical Montgomery words of the 12 Fq of
+ * ((a0, a1, a2), (b0, b1, b2)) in Fq12 = Fq6[w] / (w^2 - v), Fq6 = Fq2[v] / (v^3 - 9 - u); zeros with status 2.
+ * d_work: hm_pairing_work_bytes(n_pairs, n_checks) bytes of DEVICE memory, 16-byte aligned, contents arbitrary: three Fq12 and a flag
+ * word per pair, eleven Fq12 per check (the Miller values alone, n_pairs x 48 u64, do not suffice: an Fq12 never stands in registers).
+ * All DEVICE memory; d_g1_xy, d_g2_xy, d_gt 16-byte aligned, d_offsets and d_status 4-byte.  Asynchronous on `stream`: two launches,
+ * nothing read back.  HM_ERR_BAD_ARG, with nothing launched: NULL arguments (d_gt excepted), n_checks 0 or above 2^20, n_pairs above
+ * 2^24, work_bytes below hm_pairing_work_bytes, a buffer that is not aligned.  hm_pairing_work_bytes is 0 outside those ranges. */
+int hm_pairing_check_bn256_dev(const void* d_g1_xy, const void* d_g2_xy, size_t n_pairs, const uint32_t* d_offsets, size_t n_checks,
+                               void* d_gt, uint32_t* d_status, void* d_work, size_t work_bytes, void* stream);
+size_t hm_pairing_work_bytes(size_t n_pairs, size_t n_checks);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 
 typedef struct hm_msm_stats {
