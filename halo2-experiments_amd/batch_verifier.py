@@ -14,7 +14,8 @@ Where the work is done:
     so all points are decompressed before any challenge exists;
   - the host runs the Blake2b transcript of every proof with ``hashlib``, in the order of ``verifier._verify`` / ``verify_opening``, on
     the proof's own x bytes and the y bytes the device returned: theta, beta, gamma, y, x, the multiopen's y', v, u -- one record per
-    proof, uploaded with its weight r_b;
+    proof, uploaded with its weight r_b.  With ``transcript="device"`` one lane per proof runs it between the two kernels instead
+    (``hm_verify_transcript_dev``, csrc/transcript.inc, walking ``ProofLayout.transcript_schedule``) and nothing travels;
   - the device computes, one lane per proof (``hm_verify_terms_dev``, csrc/verify_terms.inc, driven by a ``TermsPlan``), x^n, l0, l_last,
     l_active and the instance columns' evaluations at x, the numerator by the ``GraphEvaluator`` interpreter on the proof's value row,
     h(x), and per rotation set the multiopen's scalars: r_b x the scalar of every point (``terms_from_challenges`` is the integer twin;
@@ -40,7 +41,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib, device_pairing, evaluation as ev
+from . import _lib, device_pairing, device_transcript, evaluation as ev
 from .bn256 import FQ_MODULUS, FR_MODULUS, fr_array, g1_words
 from .keygen import FR_DELTA, VerifyingKey
 from .kzg import g2_from_bytes
@@ -153,6 +154,15 @@ class ProofLayout:
             exprs += ev.lookup_expressions(ins, tabs, lambda r, b=b: F(b, r), lambda r, b=b: F(b + 1, r), lambda r, b=b: F(b + 2, r),
                                            F(self.i_l0), F(self.i_last), F(self.i_active))
         self.exprs = exprs
+
+    def transcript_schedule(self) -> List[Tuple[int, int]]:
+        """The (absorb a slots, squeeze s challenges) pairs of a single-circuit proof's transcript over its slots in order, from the
+        counts ``transcript_challenges`` uses: advice | theta | 2L | beta, gamma | sets + L + 1 | y | pieces | x | evaluations | y', v
+        | [h] | u, and a last pair that absorbs [h'] behind the last challenge, as ``Blake2bRead`` does."""
+        pairs = [(self.cs.num_advice, 1), (2 * self.L, 2), (self.nsets + self.L + 1, 1), (self.pieces, 1), (self.n_scalars, 2), (1, 1), (1, 0)]
+        if sum(a for a, _ in pairs) != self.slots or sum(s for _, s in pairs) != len(RECORD):
+            raise AssertionError("ProofLayout: the transcript's schedule does not cover the proof's slots and the eight challenges")
+        return pairs
 
 
 def read_proof_ints(layout: ProofLayout, proof: bytes):
@@ -506,12 +516,18 @@ class BatchVerifier:
     A batch of ``create_proof_multi`` proofs is out of scope, and an instance column may hold 64 rows at most (the terms kernel's
     limit; ``finalize`` raises ValueError beyond it).  ``close()`` gives the numerator's program back to the library.
     ``pairing="device"`` runs the pairing of every check on the GPU (``device_pairing``) instead of on host integers: the same
-    booleans, and ``timings["pairing"]`` keeps its meaning."""
+    booleans, and ``timings["pairing"]`` keeps its meaning.
+    ``transcript="device"`` runs the Blake2b transcripts on the GPU too (``device_transcript``): read, transcript and terms are queued
+    on one stream with no wait and no copy between them, and the flags of the batch are the one download.  The same booleans, sums and
+    ``failing()`` lists.  ``timings`` keeps its keys, but ``read``, ``transcript`` and ``terms`` are then the wall times of QUEUEING
+    each call -- the device's work surfaces in ``terms``, which ends with the download -- and only their sum means anything."""
 
-    def __init__(self, params, vk: VerifyingKey, seed=None, pairing: str = "host"):
+    def __init__(self, params, vk: VerifyingKey, seed=None, pairing: str = "host", transcript: str = "host"):
         if pairing not in device_pairing.MODES:
             raise ValueError(f"BatchVerifier: pairing must be one of {device_pairing.MODES}, got {pairing!r}")
-        self.params, self.vk, self.seed, self.pairing = params, vk, seed, pairing
+        if transcript not in device_transcript.MODES:
+            raise ValueError(f"BatchVerifier: transcript must be one of {device_transcript.MODES}, got {transcript!r}")
+        self.params, self.vk, self.seed, self.pairing, self.transcript = params, vk, seed, pairing, transcript
         self.layout = ProofLayout(vk.cs, vk.domain.k)
         self._digest = _vk_digest(vk)
         self._shared = shared_points(vk, self.layout)
@@ -576,6 +592,8 @@ class BatchVerifier:
     def _prepare(self) -> dict:
         if self._state is not None:
             return self._state
+        if self.transcript == "device":
+            return self._prepare_on_device()
         import torch
 
         lay, B = self.layout, len(self._proofs)
@@ -633,6 +651,61 @@ class BatchVerifier:
         st = dict(B=B, bad=bad, d_bases=d_bases, d_scalars=d_scalars, d_own=d_own, d_shared=d_shared, d_h2_r=d_h2_r, d_h2_l=d_h2_l,
                   d_sum=torch.zeros((n_shared, 4), dtype=torch.int64, device=dev), ybytes=ybytes)
         self.timings = dict(read=t1 - t0, plan=t_plan, transcript=t2 - t1 - t_plan, upload=t3 - t2, terms=t4 - t3, msm=0.0, pairing=0.0)
+        self._state = st
+        return st
+
+    def _prepare_on_device(self) -> dict:
+        """``_prepare`` with the transcripts on the device: everything the three kernels read is uploaded first, then read, transcript
+        and terms are queued on the current stream, and the flags are downloaded once, behind the terms."""
+        import torch
+
+        lay, B = self.layout, len(self._proofs)
+        lib, dev = _lib.load(), torch.device("cuda", torch.cuda.current_device())
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        t0 = time.perf_counter()
+        bad = [len(p) != 32 * lay.slots for p in self._proofs] if self._vk_ok else [True] * B
+        raw = np.zeros((B, 32 * lay.slots), dtype=np.uint8)
+        for b, p in enumerate(self._proofs):
+            if len(p) == 32 * lay.slots:
+                raw[b] = np.frombuffer(p, dtype=np.uint8)
+        n_shared, own = len(lay.shared_keys), lay.own_points
+        t1 = time.perf_counter()
+        plan = self._plan_for([max((len(inst[c]) for inst in self._instances), default=0) for c in range(self.vk.cs.num_instance)])
+        t2 = time.perf_counter()
+        up = lambda rows: torch.from_numpy(fr_array(rows).view(np.int64)).to(dev)
+        records = np.zeros((B, len(RECORD) + 1, 4), dtype=np.uint64)          # the challenges are the device's; r_b stands behind them
+        records[:, len(RECORD)] = fr_array(self._rand)
+        d_records, d_inst = torch.from_numpy(records.view(np.int64)).to(dev), up([plan.instance_row(inst) for inst in self._instances])
+        preamble = device_transcript.upload_preamble(self._digest, self._instances, dev)
+        d_proofs = torch.from_numpy(raw).to(dev)
+        d_table = torch.from_numpy(lay.slot_table.view(np.int32)).to(dev)
+        d_bad = torch.tensor([int(x) for x in bad], dtype=torch.int32, device=dev)   # the read kernel only ever sets a flag
+        d_bases = torch.zeros((B * own + n_shared + B, 8), dtype=torch.int64, device=dev)
+        shared_words = np.stack([g1_words(p) for p in self._shared]).view(np.int64)
+        d_bases[B * own:B * own + n_shared] = torch.from_numpy(shared_words).to(dev)
+        d_ybytes = torch.zeros((B, lay.n_points, 32), dtype=torch.uint8, device=dev)
+        d_scalars = torch.zeros((B, lay.n_scalars, 4), dtype=torch.int64, device=dev)
+        d_own = torch.empty((B * own, 4), dtype=torch.int64, device=dev)
+        d_shared = torch.empty((B, n_shared, 4), dtype=torch.int64, device=dev)
+        d_h2_r, d_h2_l = torch.empty((B, 4), dtype=torch.int64, device=dev), torch.empty((B, 4), dtype=torch.int64, device=dev)
+        d_tail = d_bases[B * own + n_shared:]
+        t3 = time.perf_counter()
+        _lib.check(lib.hm_verify_read_proofs_dev(vp(d_proofs), B, ctypes.cast(vp(d_table), u32p), lay.slots, own, lay.n_points, lay.n_scalars,
+                                                 vp(d_bases), vp(d_tail), vp(d_ybytes), vp(d_scalars), ctypes.cast(vp(d_bad), u32p), stream))
+        t4 = time.perf_counter()
+        device_transcript.challenges(lay, self._digest, self._instances, d_proofs, d_ybytes, d_bad, d_records, preamble=preamble, d_table=d_table)
+        t5 = time.perf_counter()
+        _lib.check(lib.hm_verify_terms_dev(ctypes.c_uint64(self._program.handle), plan.words.ctypes.data_as(u32p), len(plan.words),
+                                           plan.n_columns, 4, B, vp(d_records), vp(d_scalars), vp(d_inst), ctypes.cast(vp(d_bad), u32p),
+                                           vp(d_own), vp(d_shared), vp(d_h2_r), vp(d_h2_l), stream))
+        bad = [bool(x) for x in d_bad.cpu().numpy()]              # the one download: what the three kernels flagged
+        t6 = time.perf_counter()
+        st = dict(B=B, bad=bad, d_bases=d_bases, d_scalars=d_scalars, d_own=d_own, d_shared=d_shared, d_h2_r=d_h2_r, d_h2_l=d_h2_l,
+                  d_sum=torch.zeros((n_shared, 4), dtype=torch.int64, device=dev), d_ybytes=d_ybytes,
+                  d_proofs=d_proofs, d_table=d_table, d_records=d_records, preamble=preamble)   # what the transcript call took (tools/batch_verify_time.py)
+        self.timings = dict(read=t1 - t0 + t4 - t3, plan=t2 - t1, transcript=t5 - t4, upload=t3 - t2, terms=t6 - t5, msm=0.0, pairing=0.0)
         self._state = st
         return st
 
@@ -722,13 +795,14 @@ class BatchVerifier:
         return sorted(out)
 
 
-def verify_proofs(params, vk: VerifyingKey, instances, proofs, seed=None, trapdoor: int = None, pairing: str = "host") -> bool:
+def verify_proofs(params, vk: VerifyingKey, instances, proofs, seed=None, trapdoor: int = None, pairing: str = "host",
+                  transcript: str = "host") -> bool:
     """True when every ``proofs[i]`` is a valid single-circuit proof of ``vk`` for ``instances[i]``: one ``BatchVerifier``, one check
-    (``pairing``: where that check's pairing runs, as on ``BatchVerifier``)"""
+    (``pairing`` / ``transcript``: where that check's pairing and the proofs' transcripts run, as on ``BatchVerifier``)"""
     instances, proofs = list(instances), list(proofs)
     if len(instances) != len(proofs):
         raise ValueError("verify_proofs: one instance per proof")
-    bv = BatchVerifier(params, vk, seed, pairing=pairing)
+    bv = BatchVerifier(params, vk, seed, pairing=pairing, transcript=transcript)
     for instance, proof in zip(instances, proofs):
         bv.add_proof(instance, proof)
     return bv.finalize(trapdoor)

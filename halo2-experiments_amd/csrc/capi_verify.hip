@@ -1,6 +1,6 @@
 // capi_verify.hip -- the batch verifier's entry points of the C ABI: the proofs of a batch read slot by slot on the device and the
 // column sums of their shared scalars (verify_read.inc), the per-proof terms of the opening checks (verify_terms.inc), and the pairing
-// product checks that end every verifier (pairing.inc).
+// product checks that end every verifier (pairing.inc), and Blake2b-512 with the proofs' transcripts on it (transcript.inc).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -11,6 +11,7 @@
 
 namespace hm {
 #include "verify_terms.inc"   // the plan's layout and its check (the kernels are in lookup.hip)
+#include "transcript.inc"     // the schedule's check (likewise)
 }
 using namespace hm;
 
@@ -72,6 +73,44 @@ int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_word
                           (const uint32_t*)d_instance, d_bad, (uint32_t*)d_own, (uint32_t*)d_shared, (uint32_t*)d_h2_r, (uint32_t*)d_h2_l,
                           (hipStream_t)stream);
 } HM_API_CATCH("hm_verify_terms_dev")
+
+// ---- Blake2b-512 and the transcripts of a batch (transcript.inc, lookup.hip) ----------------------------------------------------------
+int hm_blake2b512_dev(const void* d_msgs, size_t stride, const uint32_t* d_lens, size_t n, const uint8_t* personal16, void* d_out,
+                      void* stream) try {
+  const std::string who = "hm_blake2b512_dev";
+  if (!d_msgs || !d_lens || !d_out) return hm_fail(HM_ERR_BAD_ARG, who + ": null argument");
+  if (n == 0 || n > VERIFY_MAX_PROOFS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n <= 2^24");
+  if (stride == 0 || stride > 0xffffffffull) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= stride < 2^32");
+  if (((uintptr_t)d_lens | (uintptr_t)d_out) & 3u) return hm_fail(HM_ERR_BAD_ARG, who + ": d_lens / d_out is not 4-byte aligned");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return blake2b_run((const uint8_t*)d_msgs, stride, d_lens, n, personal16, (uint32_t*)d_out, (hipStream_t)stream);
+} HM_API_CATCH("hm_blake2b512_dev")
+
+int hm_verify_transcript_dev(const void* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots, uint32_t points,
+                             const void* d_y_bytes, const void* d_preamble, const uint32_t* d_preamble_counts, uint32_t preamble_stride,
+                             const uint32_t* schedule, size_t n_schedule_pairs, uint32_t* d_bad_in_out, void* d_records,
+                             uint32_t record_elems, void* stream) try {
+  const std::string who = "hm_verify_transcript_dev";
+  if (!d_proofs || !d_slot_table || !d_y_bytes || !d_preamble || !d_preamble_counts || !schedule || !d_bad_in_out || !d_records)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": null argument");
+  if (n_proofs == 0 || n_proofs > VERIFY_MAX_PROOFS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n_proofs <= 2^24");
+  if (slots == 0 || slots > VERIFY_MAX_SLOTS || points > slots) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= slots <= 2^16 and points <= slots");
+  if (preamble_stride == 0 || preamble_stride > VERIFY_MAX_SLOTS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= preamble_stride <= 2^16");
+  if (record_elems == 0 || record_elems > VERIFY_MAX_SLOTS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= record_elems <= 2^16");
+  if (n_schedule_pairs == 0 || n_schedule_pairs > VERIFY_MAX_SLOTS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n_schedule_pairs <= 2^16");
+  if (((uintptr_t)d_proofs | (uintptr_t)d_y_bytes | (uintptr_t)d_preamble | (uintptr_t)d_records) & 15u)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": a buffer is not 16-byte aligned");
+  if (((uintptr_t)d_slot_table | (uintptr_t)d_preamble_counts | (uintptr_t)d_bad_in_out) & 3u)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": d_slot_table / d_preamble_counts / d_bad_in_out is not 4-byte aligned");
+  if (const char* why = tr_schedule_problem(schedule, n_schedule_pairs, slots, record_elems)) return hm_fail(HM_ERR_BAD_ARG, why);
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return verify_transcript_run(*ctx, (const uint32_t*)d_proofs, n_proofs, d_slot_table, slots, points, (const uint32_t*)d_y_bytes,
+                               (const uint32_t*)d_preamble, d_preamble_counts, preamble_stride, schedule, n_schedule_pairs, d_bad_in_out,
+                               (uint32_t*)d_records, record_elems, (hipStream_t)stream);
+} HM_API_CATCH("hm_verify_transcript_dev")
 
 // ---- pairing product checks (pairing.inc, lookup.hip) ------------------------------------------------------------------------------
 static constexpr size_t PAIRING_MAX_CHECKS = (size_t)1 << 20, PAIRING_MAX_PAIRS = (size_t)1 << 24;

@@ -571,4 +571,14 @@ size_t pairing_work_words(size_t n_pairs, size_t n_checks);
 int pairing_check_run(const uint32_t* d_g1, const uint32_t* d_g2, size_t n_pairs, const uint32_t* d_offsets, size_t n_checks, uint32_t* d_gt,
                       uint32_t* d_status, uint32_t* d_work, hipStream_t stream);
 
+// transcript.inc (lookup.hip): Blake2b-512 of n messages at a fixed byte stride (personal16: host memory or null), and the transcripts
+// of n_proofs proofs -- `schedule` (host memory, n_pairs pairs) is checked before anything is launched and uploaded with the call.
+// Both asynchronous on `stream`.
+int blake2b_run(const uint8_t* d_msgs, size_t stride, const uint32_t* d_lens, size_t n, const uint8_t* personal16, uint32_t* d_out,
+                hipStream_t stream);
+int verify_transcript_run(DeviceCtx& ctx, const uint32_t* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots,
+                          uint32_t n_points, const uint32_t* d_ybytes, const uint32_t* d_preamble, const uint32_t* d_counts, uint32_t stride,
+                          const uint32_t* schedule, size_t n_pairs, uint32_t* d_bad, uint32_t* d_records, uint32_t record_elems,
+                          hipStream_t stream);
+
 }  // namespace hm

@@ -25,6 +25,7 @@ namespace hm {
 #include "keygen.inc"     // the permutation assembly's key packing and link rule (likewise)
 #include "shplonk.inc"    // the SHPLONK set quotient's plan, coefficients and row formula (likewise)
 #include "pairing.inc"    // the pairing's tower, Miller lane and final exponentiation (likewise)
+#include "transcript.inc" // Blake2b-512, its streaming absorber and the transcript lane of a proof (likewise)
 }
 
 using namespace hm;
@@ -658,6 +659,67 @@ int hc_verify_column_sum(const uint32_t* rows, size_t n_rows, uint32_t cols, siz
     std::memcpy(out + (size_t)c * 8, w, 32);
   }
   return 0;
+}
+
+// Blake2b and the transcripts (transcript.inc), the exact lane code of its kernels on a block of 32 host words.
+//   hc_blake2b_compress: h <- F(h, the 128 bytes of `block`, t, last).
+//   hc_blake2b: n messages at a byte stride -> n x 64 digest bytes; personal16 null or 16 bytes.
+//   hc_transcript_stream: ops[i] = 0 a squeeze (prefix byte 0, then a digest of a COPY: 64 bytes to `digests`), 1 a 65-byte record
+//     (prefix 1 and 16 words of `data`), 2 a 33-byte record (prefix 2 and 8 words); positions[i] = the bytes in the block after op i.
+//   hc_fr_from_wide: n digests of 64 bytes -> n x 8 Montgomery words of the little-endian integer mod r.
+//   hc_verify_transcript: tr_proof_one on proof b of a batch, arguments as hm_verify_transcript_dev's (all host memory).
+void hc_blake2b_compress(uint64_t* h, const uint8_t* block, uint64_t t, int last) {
+  uint64_t hh[8], m[16];
+  std::memcpy(hh, h, 64);
+  std::memcpy(m, block, 128);
+  blake2b_compress(hh, m, t, last != 0);
+  std::memcpy(h, hh, 64);
+}
+void hc_blake2b(const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t n, const uint8_t* personal16, uint8_t* out) {
+  uint64_t personal[2] = {0, 0};
+  if (personal16) std::memcpy(personal, personal16, 16);
+  for (size_t i = 0; i < n; ++i) {
+    uint32_t block[32] = {0}, digest[16];
+    b2_hash_lane(B2Buf{block, 1}, msgs + i * stride, lens[i], personal[0], personal[1], digest);
+    std::memcpy(out + 64 * i, digest, 64);
+  }
+}
+void hc_transcript_stream(const uint8_t* ops, size_t n_ops, const uint32_t* data, uint8_t* digests, uint32_t* positions) {
+  uint32_t block[32] = {0};
+  const B2Buf buf{block, 1};
+  B2State s;
+  b2_init(s, TR_PERSONAL_LO, TR_PERSONAL_HI);
+  for (size_t i = 0; i < n_ops; ++i) {
+    const uint32_t words = ops[i] == 0 ? 0 : ops[i] == 1 ? 16 : 8;
+    b2_push(s, buf, ops[i], 1);
+    for (uint32_t k = 0; k < words; ++k) b2_push(s, buf, *data++, 4);
+    if (words == 0) {
+      uint64_t d[8];
+      b2_final(s, buf, d);
+      std::memcpy(digests, d, 64);
+      digests += 64;
+    }
+    positions[i] = s.pos;
+  }
+}
+void hc_fr_from_wide(const uint8_t* digests, size_t n, uint32_t* out) {
+  for (size_t i = 0; i < n; ++i) {
+    uint64_t d[8];
+    uint32_t w[8];
+    std::memcpy(d, digests + 64 * i, 64);
+    fr_from_wide(d, w);
+    std::memcpy(out + 8 * i, w, 32);
+  }
+}
+void hc_verify_transcript(size_t b, const uint32_t* proofs, const uint32_t* slot_table, uint32_t slots, uint32_t points, const uint32_t* ybytes,
+                          const uint32_t* preamble, const uint32_t* counts, uint32_t stride, const uint32_t* schedule, uint32_t n_pairs,
+                          uint32_t* bad, uint32_t* records, uint32_t record_elems) {
+  uint32_t block[B2_BLOCK_WORDS + TR_STAGE_WORDS] = {0};
+  tr_proof_one(B2Buf{block, 1}, b, proofs, slot_table, slots, points, ybytes, preamble, counts, stride, schedule, n_pairs, bad, records,
+               record_elems);
+}
+const char* hc_transcript_schedule_problem(const uint32_t* schedule, size_t n_pairs, uint32_t slots, uint32_t record_elems) {
+  return tr_schedule_problem(schedule, n_pairs, slots, record_elems);
 }
 
 // The batch verifier's terms (verify_terms.inc) for ONE proof, the exact lane code of its kernel on a workspace of one lane: phase a,

@@ -592,5 +592,7 @@ int lookup_permute_run(DeviceCtx& ctx, const void* const* d_inputs, const void* 
 #define HM_VERIFY_TERMS_KERNELS
 #include "verify_terms.inc"   // the batch verifier's per-proof terms: the same interpreter on one lane per proof
 #include "pairing.inc"        // batched pairing product checks: pairing_check_run / pairing_work_words
+#define HM_TRANSCRIPT_KERNELS
+#include "transcript.inc"     // Blake2b-512 and the batch verifier's transcripts, one lane per proof: blake2b_run / verify_transcript_run
 
 }  // namespace hm

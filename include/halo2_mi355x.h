@@ -780,6 +780,35 @@ int hm_verify_column_sum_dev(const void* d_rows, size_t n_rows, uint32_t columns
 int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
                         const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad, void* d_own, void* d_shared,
                         void* d_h2_r, void* d_h2_l, void* stream);
+/* Blake2b-512 (RFC 7693, 64-byte digest, no key), one lane per message: message i is the d_lens[i] bytes at d_msgs + i * stride
+ * (DEVICE memory, any alignment; d_lens: n u32, DEVICE memory), personal16 the 16 personalisation bytes (HOST memory, read before the
+ * call returns) or NULL for none; d_out: n x 64 digest bytes (DEVICE memory, 4-byte aligned).  The lengths lie on the device, so the
+ * call cannot refuse one: a message whose length is above `stride` gets 64 zero bytes and nothing of it is read.  Asynchronous on
+ * `stream`.  HM_ERR_BAD_ARG, with nothing launched: NULL arguments (personal16 excepted), n 0 or above 2^24, stride 0 or above
+ * 2^32 - 1, d_lens or d_out not 4-byte aligned.
+ *
+ * transcript: one lane per proof runs the proof's Blake2b transcript (personalisation "Halo2-Transcript"; every absorption behind
+ * a prefix byte: 0 a squeeze, 1 a point, 2 a scalar) and leaves its challenges where hm_verify_terms_dev reads them.  d_proofs,
+ * d_slot_table, slots and points are those of hm_verify_read_proofs_dev, d_y_bytes what that call wrote.  Proof b first absorbs
+ * d_preamble_counts[b] scalars from row b of d_preamble (n_proofs x preamble_stride x 32 canonical little-endian bytes: the digest
+ * of the verifying key, then the instance values; the counts may differ from proof to proof), then walks `schedule` (HOST memory,
+ * n_schedule_pairs pairs of u32: absorb a slots, then squeeze s challenges) over its slots in order: a point slot absorbs the
+ * proof's x bytes with bit 7 of byte 31 cleared and the 32 y bytes of that point, a scalar slot its 32 bytes.  A squeeze absorbs the
+ * prefix byte into the running state and finalises a COPY of it; the 64 digest bytes, a little-endian integer, are reduced mod r.
+ * Challenge j goes to element j of row b of d_records (n_proofs x record_elems x 4 Montgomery words); the elements behind the
+ * schedule's challenges are left alone (the caller's r_b).  A proof whose d_bad_in_out[b] is set on entry is not hashed and gets zero
+ * challenges; a preamble count above preamble_stride, or a point slot whose table index is not below `points`, sets d_bad_in_out[b]
+ * with zero challenges, and nothing is read outside the arrays.  All DEVICE memory but the schedule; d_proofs, d_y_bytes,
+ * d_preamble, d_records 16-byte aligned, the u32 arrays 4-byte.  The schedule is checked and uploaded with the call.  Asynchronous
+ * on `stream`.  HM_ERR_BAD_ARG, with nothing launched: NULL arguments, n_proofs 0 or above 2^24, slots 0 or above 2^16, points >
+ * slots, preamble_stride, record_elems or n_schedule_pairs 0 or above 2^16, a schedule whose absorbed slots do not sum to `slots` or
+ * whose squeezes exceed record_elems, a buffer that is not aligned. */
+int hm_blake2b512_dev(const void* d_msgs, size_t stride, const uint32_t* d_lens, size_t n, const uint8_t* personal16, void* d_out,
+                      void* stream);
+int hm_verify_transcript_dev(const void* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots, uint32_t points,
+                             const void* d_y_bytes, const void* d_preamble, const uint32_t* d_preamble_counts, uint32_t preamble_stride,
+                             const uint32_t* schedule, size_t n_schedule_pairs, uint32_t* d_bad_in_out, void* d_records,
+                             uint32_t record_elems, void* stream);
 
 /* ---- pairing product checks: for every check c, is the product of e(P_i, Q_i) over its pairs 1? -------------------------------------
  *
