@@ -83,6 +83,11 @@ class ConstraintSystem:
     lookups: List[Tuple[List[Expression], List[Expression]]]          # (input expressions, table expressions)
     equality: List[Tuple[str, int]]
     blinding_factors: int = 5
+    # advice columns whose last rows (row >= n - blinding_factors - 1) the prover leaves ZERO instead of drawing blinding for them:
+    # their commitment is then ``commit_lagrange`` of the witness column itself -- deterministic, and not hiding
+    unblinded_advice: Tuple[int, ...] = ()
+    # what the system was built with, where a caller needs it back (overflow_check_v2: max_bits, acc_cols)
+    parameters: Dict[str, int] = field(default_factory=dict)
 
     def polynomials(self) -> List[Expression]:
         return [p for _, polys in self.gates for p in polys]
@@ -284,8 +289,45 @@ def poseidon(spec=None) -> ConstraintSystem:
                             cols.num_fixed, cols.num_advice, cols.num_instance, gates, [], cols.equality)
 
 
+def overflow_check_v2(max_bits: int = 4, acc_cols: int = 4, unblinded_value: bool = False) -> ConstraintSystem:
+    """OverflowCheckCircuitV2::configure, /root/reference/src/circuits/overflow_check_v2.rs:21-39, with OverflowChipV2::configure,
+    /root/reference/src/chips/overflow_check_v2.rs:31-78 (TRANSCRIBED; the reference instantiates <4, 4> only): advice 0 the value,
+    advice 1 .. acc_cols its limbs of max_bits bits, most significant first; fixed 0 the range column 0 .. 2^max_bits - 1, fixed 1
+    the selector; an instance column that stays empty; equality on the limb columns only, and no copies.  One gate,
+    sum limb_i * 2^(max_bits * (acc_cols - 1 - i)) = value, and one lookup per limb column into the range column.  On every row where
+    the selector is set the value is below 2^(max_bits * acc_cols); with max_bits * acc_cols <= 253 the limb sum cannot wrap mod r.
+
+    unblinded_value: ``unblinded_advice = (0,)`` -- the prover leaves the last rows of the value column zero, so the proof's first
+    commitment is ``params.commit_lagrange`` of the value column padded with zeros: the commitment ``open_all`` / ``open_at`` open.
+    The trade-off: that commitment is deterministic, which is what a published balance commitment wants (every user checks an
+    opening of the SAME point) and what blinding would break; it hides nothing beyond what the discrete logarithm hides, so equal
+    columns give equal commitments and a guessed column can be confirmed."""
+    if not 1 <= max_bits <= 16:
+        raise ValueError("overflow_check_v2: max_bits must be 1 .. 16")
+    if acc_cols < 1 or max_bits * acc_cols > 253:
+        raise ValueError("overflow_check_v2: acc_cols must be at least 1 and max_bits * acc_cols at most 253 (the limb sum must not wrap mod r)")
+    cols = _Columns()
+    value = cols.advice()                                                      # circuits/overflow_check_v2.rs:22-26
+    limbs = [cols.advice() for _ in range(acc_cols)]
+    rng = cols.fixed()                                                         # :27
+    selector = cols.selector()                                                 # :28
+    cols.instance()                                                            # :29
+    for col in limbs:                                                          # chips/overflow_check_v2.rs:39
+        cols.enable_equality("advice", col)
+    total: Expression = Advice(limbs[acc_cols - 1])                            # :50-56
+    for i in range(acc_cols - 1):
+        total = total + Advice(limbs[i]) * Constant(1 << (max_bits * (acc_cols - 1 - i)))
+    gates = [("equality check between decomposed value and value", [Fixed(selector) * (total - Advice(value))])]   # :41-59
+    lookups = [([Advice(col)], [Fixed(rng)]) for col in limbs]                 # :63-69
+    return ConstraintSystem(f"OverflowCheckV2<{max_bits}, {acc_cols}>", "circuits/overflow_check_v2.rs:21-39, chips/overflow_check_v2.rs:31-78",
+                            cols.num_fixed, cols.num_advice, cols.num_instance, gates, lookups, cols.equality,
+                            unblinded_advice=(value,) if unblinded_value else (), parameters=dict(max_bits=max_bits, acc_cols=acc_cols))
+
+
 CONSTRAINT_SYSTEMS: Dict[str, Callable[[], ConstraintSystem]] = {
     "poseidon_k11": poseidon, "merkle_v3_k17": merkle_v3, "merkle_sum_tree_k18": merkle_sum_tree,
+    # the reference's own shape of the range check: MockProver at k = 5 (/root/reference/src/circuits/overflow_check_v2.rs:66-90)
+    "overflow_check_v2_k5": overflow_check_v2,
     # the ONE configuration the reference proves for real: test_full_prover, k = 9, a depth-5 path
     # (/root/reference/src/circuits/merkle_sum_tree.rs:345-358, path :172-212) -- the same constraint system as k = 18
     "merkle_sum_tree_k9": merkle_sum_tree,

@@ -399,4 +399,77 @@ int hm_merkle_roots_bn256(uint64_t handle, uint32_t depth, size_t m, const uint6
   });
 } HM_API_CATCH("hm_merkle_roots_bn256")
 
+// ---- the range-check circuit's witness (range.inc: range_witness_lane) ---------------------------------------------------------------
+// what the layout and both forms of the witness refuse; -> n_advice and the rows of the table
+static int range_witness_layout(const char* who, uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, uint32_t rows, uint32_t* n_advice,
+                                uint32_t* table_rows) {
+  const std::string w(who);
+  if (max_bits == 0 || max_bits > 16) return hm_fail(HM_ERR_BAD_ARG, w + ": max_bits must be 1 .. 16");
+  if (acc_cols == 0 || (uint64_t)max_bits * acc_cols > 253)
+    return hm_fail(HM_ERR_BAD_ARG, w + ": acc_cols must be at least 1 and max_bits * acc_cols at most 253");
+  if (log_n > WITNESS_MAX_LOG_N) return hm_fail(HM_ERR_BAD_ARG, w + ": log_n > 24");
+  if (rows == 0) return hm_fail(HM_ERR_BAD_ARG, w + ": rows must be at least 1");
+  const uint64_t need = rows > (1u << max_bits) ? rows : (1u << max_bits);
+  if (((uint64_t)1 << log_n) < need + 6)
+    return hm_fail(HM_ERR_BAD_ARG, w + ": the circuit needs " + std::to_string(need) + " rows, 2^log_n - 6 is fewer");
+  *n_advice = 1 + acc_cols;
+  *table_rows = 1u << max_bits;
+  return HM_OK;
+}
+
+int hm_range_witness_layout(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, uint32_t rows, uint32_t* out_n_advice,
+                            uint32_t* out_table_rows) try {
+  if (!out_n_advice || !out_table_rows) return hm_fail(HM_ERR_BAD_ARG, "hm_range_witness_layout: null argument");
+  uint32_t n_advice = 0, table_rows = 0;
+  if (int rc = range_witness_layout("hm_range_witness_layout", max_bits, acc_cols, log_n, rows, &n_advice, &table_rows)) return rc;
+  *out_n_advice = n_advice;
+  *out_table_rows = table_rows;
+  return HM_OK;
+} HM_API_CATCH("hm_range_witness_layout")
+
+static int range_witness_args(const char* who, uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows,
+                              const void* values, const void* advice, uint32_t* n_advice) {
+  if (!values || !advice) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (m == 0) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": m must be at least 1");
+  uint32_t table_rows = 0;
+  if (int rc = range_witness_layout(who, max_bits, acc_cols, log_n, rows, n_advice, &table_rows)) return rc;
+  if (m > (POSEIDON_MAX_N >> log_n)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": more than 2^31 rows");
+  return HM_OK;
+}
+
+int hm_range_witness_bn256_fr_dev(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const void* d_values,
+                                  void* d_advice, uint32_t* d_over_or_null, void* stream) try {
+  const char* who = "hm_range_witness_bn256_fr_dev";
+  uint32_t n_advice = 0;
+  if (int rc = range_witness_args(who, max_bits, acc_cols, log_n, m, rows, d_values, d_advice, &n_advice)) return rc;
+  if (int rc = witness_aligned(who, {d_values, d_advice}, nullptr)) return rc;
+  if ((uintptr_t)d_over_or_null & 3u) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": d_over is not 4-byte aligned");
+  if (ranges_overlap(d_values, m * rows * 32, d_advice, m * n_advice * ((size_t)32 << log_n)))
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": d_values overlaps d_advice");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return range_witness_run(max_bits, acc_cols, log_n, m, rows, (const uint32_t*)d_values, (uint32_t*)d_advice, d_over_or_null,
+                           (hipStream_t)stream);
+} HM_API_CATCH("hm_range_witness_bn256_fr_dev")
+
+int hm_range_witness_bn256_fr(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint64_t* values,
+                              uint64_t* advice, uint32_t* over_or_null) try {
+  const char* who = "hm_range_witness_bn256_fr";
+  uint32_t n_advice = 0;
+  if (int rc = range_witness_args(who, max_bits, acc_cols, log_n, m, rows, values, advice, &n_advice)) return rc;
+  const size_t col_bytes = (size_t)32 << log_n;
+  if (m > WITNESS_HOST_MAX_BYTES / ((size_t)n_advice * col_bytes))
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the columns exceed 256 MiB; use the device form");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const size_t in_bytes = pad64(m * rows * 32), adv_bytes = m * n_advice * col_bytes, over_bytes = m * sizeof(uint32_t);
+  const HostIn in{values, m * rows * 32, 0};
+  const HostOut out[2] = {{over_or_null, over_or_null ? over_bytes : 0, in_bytes + adv_bytes, true}, {advice, adv_bytes, in_bytes, false}};
+  return host_round_trip(who, *ctx, "witness", in_bytes + adv_bytes + over_bytes, &in, 1, out, 2, [&](uint8_t* d) {
+    return range_witness_run(max_bits, acc_cols, log_n, m, rows, (const uint32_t*)d, (uint32_t*)(d + in_bytes),
+                             (uint32_t*)(d + in_bytes + adv_bytes), nullptr);
+  });
+} HM_API_CATCH("hm_range_witness_bn256_fr")
+
 }  // extern "C"

@@ -464,6 +464,11 @@ int merkle_witness_run(uint32_t E, const PoseidonSpec& s, uint32_t depth, uint32
                        uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream);
 int poseidon_witness_run(const PoseidonSpec& s, uint32_t log_n, size_t m, const uint32_t* d_msgs, uint32_t* d_advice, uint32_t* d_instance,
                          hipStream_t stream);
+// The range-check circuit's witness (range.inc): column 0 the m x rows values, columns 1 .. acc_cols their limbs of max_bits bits, most
+// significant first; every row of every column is written; d_over: null, or m counters of the values with higher bits.  Asynchronous
+// on `stream`; the arguments were checked by the caller (capi_hash.hip).
+int range_witness_run(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint32_t* d_values,
+                      uint32_t* d_advice, uint32_t* d_over, hipStream_t stream);
 // keygen's permutation assembly (keygen.inc).  d_copies: m pairs of cell ids, a cell being column * 2^k + row; d_sigma_cells receives
 // columns * 2^k ids (it is the union-find's parent array on the way); a pair with an id out of range is dropped and counted in
 // *d_dropped (null: not counted).  Asynchronous on `stream`; the arguments were checked by the caller (capi_keygen.hip).

@@ -22,6 +22,7 @@ namespace hm {
 #include "verify_read.inc"   // the batch verifier's per-slot read and its column sum (likewise)
 #include "verify_terms.inc"  // ... and the two phases of its per-proof terms around the interpreter's run (likewise)
 #include "poseidon.inc"   // the per-hash Poseidon / Merkle node functions (likewise)
+#include "range.inc"      // the range-check witness's lane function (likewise)
 #include "keygen.inc"     // the permutation assembly's key packing and link rule (likewise)
 #include "shplonk.inc"    // the SHPLONK set quotient's plan, coefficients and row formula (likewise)
 #include "pairing.inc"    // the pairing's tower, Miller lane and final exponentiation (likewise)
@@ -865,6 +866,18 @@ int hc_poseidon_witness(const uint32_t* consts, uint32_t r_f, uint32_t r_p, uint
   WitnessArgs a;
   if (int rc = hc_witness_args(0, consts, r_f, r_p, 0, log_n, m, msgs, advice, instance, a)) return rc;
   for (size_t u = 0; u < m; ++u) poseidon_witness_lane(a, u);
+  return 0;
+}
+
+// the lanes of range_witness_kernel, one after the other; over: m counters
+int hc_range_witness(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint32_t* values, uint32_t* advice,
+                     uint32_t* over) {
+  if (max_bits == 0 || max_bits > RANGE_MAX_BITS || acc_cols == 0 || max_bits * acc_cols > RANGE_MAX_VALUE_BITS || log_n > 24 || rows == 0 ||
+      rows > ((uint64_t)1 << log_n))
+    return -1;
+  const RangeArgs a{values, advice, over, (uint64_t)m << log_n, max_bits, acc_cols, log_n, rows};
+  for (size_t c = 0; c < m; ++c) over[c] = 0;
+  for (uint64_t idx = 0; idx < a.lanes; ++idx) over[idx >> log_n] += range_witness_lane(a, idx) ? 1u : 0u;
   return 0;
 }
 

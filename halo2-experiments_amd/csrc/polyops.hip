@@ -1087,6 +1087,11 @@ int poseidon_witness_run(const PoseidonSpec& s, uint32_t log_n, size_t m, const 
 }
 
 // ---------------------------------------------------------------------------------------------
+// the range-check circuit's witness: the lane function, kernel and launch in range.inc
+// ---------------------------------------------------------------------------------------------
+#include "range.inc"
+
+// ---------------------------------------------------------------------------------------------
 // keygen's permutation assembly: the plan and its kernels in keygen.inc
 // ---------------------------------------------------------------------------------------------
 #include "keygen.inc"

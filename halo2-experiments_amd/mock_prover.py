@@ -208,12 +208,16 @@ class MockProver:
         if advice.device != d.device or not advice.is_contiguous():
             raise ValueError(f"MockProver: advice must be contiguous and on {d.device}")
         if instance is None:
-            instance = []
+            instance = [None] * cs.num_instance
         insts = list(instance) if isinstance(instance, (list, tuple)) else [instance]
         if len(insts) != cs.num_instance:
             raise ValueError(f"MockProver: {len(insts)} instance columns given, the constraint system has {cs.num_instance}")
         out = []
         for t in insts:
+            # a column without values (None, an empty list or an (m, 0, 4) tensor): every cell reads as zero, which one zero row says
+            if t is None or (isinstance(t, (list, tuple)) and len(t) == 0) or (torch.is_tensor(t) and t.numel() == 0):
+                out.append(torch.zeros((m, 1, 4), dtype=torch.int64, device=d.device))
+                continue
             if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int64 and t.device == d.device):
                 raise ValueError(f"MockProver: an instance column must be an int64 GPU tensor on {d.device}")
             if t.dim() == 2 and m == 1:

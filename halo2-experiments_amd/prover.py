@@ -25,7 +25,9 @@ more polynomials per set; the helper graph programs are compiled once per proof 
 circuits' own extended columns pass ``H_COLUMN_BUDGET`` (2 GiB, the witness writers' convention).  The permutation products are one
 ``grand_product_batch`` per circuit: its chain runs from one column set to the next and must start at 1 in every circuit.
 
-Nothing but the blinding is random, and it comes from ``random_fr(seed + ...)``: a seed fixes the bytes.  ``base`` = the low 48 bits of
+Nothing but the blinding is random, and it comes from ``random_fr(seed + ...)``: a seed fixes the bytes.  The advice columns named in
+``cs.unblinded_advice`` keep zeros in their last rows (the draw for the other columns is what it is without them), so their commitments
+are ``commit_lagrange`` of the witness columns themselves: what ``solvency`` opens.  ``base`` = the low 48 bits of
 ``seed`` shifted by 10 (58 bits; ``create_proof``'s derivation, kept so that its bytes stay) names the streams of circuit 0: + 0 advice,
 + 0x40 + 2 j / + 1 the permuted columns of lookup j, + 0x80 + i the permutation z, + 0xC0 + j the lookup z, + 0x100 the random
 polynomial (drawn once per proof).  Circuit c uses ``base | c << 58``: the 6 bits above the base, hence at most 64 circuits; no two
@@ -235,6 +237,8 @@ def _create_proof(who, params, pk, advice, instances, seed, _trace) -> bytes:
     adv = torch.stack(list(advice), dim=1)                                   # (A, m, n, 4), a copy: adv[i] is column i of every circuit
     for c in range(m):
         adv[:, c, usable:] = random_fr(A * (n - usable), bases[c], device, shape=(A, n - usable, 4))
+    for i in cs.unblinded_advice:                                            # the draw above is the same with or without them
+        adv[i, :, usable:] = 0
     inst_cols = [instance_values(cs, instance) for instance in instances]
     inst = torch.zeros((I, m, n, 4), dtype=torch.int64, device=device)
     for c in range(m):
@@ -496,6 +500,8 @@ def _create_proofs(who, params, pk, advice, instances, seeds) -> list:
     adv = torch.stack(list(advice), dim=1)                                   # (A, m, n, 4), a copy: adv[i] is column i of every proof
     for b in every:
         adv[:, b, usable:] = random_fr(A * (n - usable), bases[b], device, shape=(A, n - usable, 4))
+    for i in cs.unblinded_advice:
+        adv[i, :, usable:] = 0
     inst_cols = [instance_values(cs, instance) for instance in instances]
     inst = torch.zeros((I, m, n, 4), dtype=torch.int64, device=device)
     for b in every:

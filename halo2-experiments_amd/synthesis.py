@@ -44,7 +44,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _lib
-from ._marshal import _dev_ptr, _ptr, _stream_ptr, _tensor_rows
+from ._marshal import _dev_ptr, _ptr, _stream_ptr, _tensor_rows, _u32p
 from .bn256 import FR_MODULUS, fr_array, fr_words
 from .circuits import ConstraintSystem, merkle_sum_tree
 from .poseidon import Spec, default_spec, ints_to_words
@@ -500,8 +500,85 @@ class PoseidonCircuitLayout(_Pow5Layout):
         return adv
 
 
+class RangeCheckLayout:
+    """``OverflowCheckCircuitV2::synthesize`` for ``circuits.overflow_check_v2(max_bits, acc_cols)``, with ``rows`` values instead of
+    the reference's three.  TRANSCRIBED (read as text):
+        chip.load: the range table, fixed column ``range`` rows 0 .. 2^max_bits - 1     /root/reference/src/chips/overflow_check_v2.rs:116-133
+        chip.assign: one region of one row per value -- selector, value, limbs          :80-114, src/circuits/overflow_check_v2.rs:41-59
+    The regions follow one another from row 0: value i on row i, the selector on rows 0 .. rows - 1.  There are no copies and the
+    instance column is empty.  The rest of ``range`` is zero, which is a legal table entry, and so are the limbs of the unused rows.
+
+    One deviation from the reference: it calls ``decompose_bigInt_to_ubits(value, MAX_BITS, ACC_COLS)`` against the signature
+    (value, number_of_limbs, bit_len) (chips/utils.rs) -- the two arguments swapped, harmless at its only instantiation <4, 4>.  Here
+    the decomposition is what the gate needs: ``acc_cols`` limbs of ``max_bits`` bits each."""
+    NAME = "RangeCheckLayout"
+    VALUE, RANGE, SELECTOR = 0, 0, 1          # advice 0; fixed 0, 1 (circuits.overflow_check_v2()'s allocation order)
+    N_FIXED = 2
+
+    def __init__(self, k: int, max_bits: int = 4, acc_cols: int = 4, rows: int = 1):
+        if not 1 <= max_bits <= 16:
+            raise ValueError("RangeCheckLayout: max_bits must be 1 .. 16")
+        if acc_cols < 1 or max_bits * acc_cols > 253:
+            raise ValueError("RangeCheckLayout: acc_cols must be at least 1 and max_bits * acc_cols at most 253")
+        if rows < 1:
+            raise ValueError("RangeCheckLayout: rows must be at least 1")
+        self.k, self.n, self.max_bits, self.acc_cols, self.rows = k, 1 << k, max_bits, acc_cols, rows
+        self.N_ADVICE = 1 + acc_cols
+        self.LIMBS = tuple(range(1, 1 + acc_cols))
+        self.table_rows = 1 << max_bits
+        self.used_rows = self.rows_needed(max_bits, rows)
+        if self.used_rows > self.n - BLINDING_ROWS:
+            raise ValueError(f"RangeCheckLayout: {self.used_rows} rows are needed, 2^{k} - {BLINDING_ROWS} is fewer "
+                             f"(min_k = {self.min_k(max_bits, rows)})")
+        cols = (("advice", self.VALUE),) + tuple(("advice", c) for c in self.LIMBS) + (("fixed", self.SELECTOR),)
+        self.regions = [Region(f"load range check table of {max_bits} bits", 0, self.table_rows, (("fixed", self.RANGE),))]
+        self.regions += [Region("assign decomposed values", i, 1, cols) for i in range(rows)]
+
+    @staticmethod
+    def rows_needed(max_bits: int, rows: int) -> int:
+        return max(rows, 1 << max_bits)
+
+    @classmethod
+    def min_k(cls, max_bits: int, rows: int) -> int:
+        return (cls.rows_needed(max_bits, rows) + BLINDING_ROWS - 1).bit_length()
+
+    def check_constraint_system(self, cs: ConstraintSystem) -> None:
+        if (cs.num_advice, cs.num_fixed, cs.num_instance) != (self.N_ADVICE, self.N_FIXED, 1) or \
+                list(cs.equality) != [("advice", c) for c in self.LIMBS] or len(cs.lookups) != self.acc_cols:
+            raise ValueError(f"RangeCheckLayout: the constraint system is not circuits.overflow_check_v2(max_bits, {self.acc_cols})")
+
+    def selector_rows(self) -> Dict[int, List[int]]:
+        return {self.SELECTOR: list(range(self.rows))}
+
+    def fixed_columns(self) -> List[List[int]]:
+        cols = [[0] * self.n for _ in range(self.N_FIXED)]
+        cols[self.RANGE][:self.table_rows] = range(self.table_rows)
+        cols[self.SELECTOR][:self.rows] = [1] * self.rows
+        return cols
+
+    def copies(self) -> List[Tuple[Cell, Cell]]:
+        return []
+
+    def instance(self) -> List[List[int]]:
+        return [[]]
+
+    def assign_ints(self, values: Sequence[int]) -> List[List[int]]:
+        """The 1 + acc_cols advice columns as the chip assigns them.  Nothing is judged: the limbs are the low max_bits * acc_cols
+        bits of the value, so a value at or above 2^(max_bits * acc_cols) gives a witness that fails the gate."""
+        if len(values) != self.rows:
+            raise ValueError(f"assign_ints: {self.rows} values expected")
+        adv = [[0] * self.n for _ in range(self.N_ADVICE)]
+        mask = (1 << self.max_bits) - 1
+        for row, v in enumerate(values):
+            v = int(v) % R
+            adv[self.VALUE][row] = v
+            for i, c in enumerate(self.LIMBS):
+                adv[c][row] = (v >> (self.max_bits * (self.acc_cols - 1 - i))) & mask
+        return adv
+
+
 # ---- keygen's permutation columns -----------------------------------------------------------------------------------------------
-AnyLayout = Union[MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout]      # anything with ``n`` and ``copies()``
+AnyLayout = Union[MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, RangeCheckLayout]      # anything with ``n`` and ``copies()``
 
 
 def permutation_cells(cs: ConstraintSystem, layout: "AnyLayout") -> List[List[Tuple[int, int]]]:
@@ -726,6 +803,62 @@ def poseidon_circuit_witness_host(spec: Optional[Spec], msgs: np.ndarray, k: int
     inst = np.zeros((m, 1, 4), dtype=np.uint64)
     spec.call(_lib.load().hm_poseidon_witness_bn256, k, m, _ptr(ms), _ptr(adv), _ptr(inst))
     return adv, inst
+
+
+def range_c_layout(k: int, max_bits: int = 4, acc_cols: int = 4, rows: int = 1) -> Dict[str, int]:
+    """``hm_range_witness_layout``: the numbers the range-check kernel uses (no device needed), beside ``RangeCheckLayout``'s;
+    ValueError when the two differ."""
+    n_adv, table_rows = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    _lib.check(_lib.load().hm_range_witness_layout(max_bits, acc_cols, k, rows, ctypes.byref(n_adv), ctypes.byref(table_rows)))
+    lay = RangeCheckLayout(k, max_bits, acc_cols, rows)
+    out = {"n_advice": n_adv.value, "table_rows": table_rows.value}
+    if out != {"n_advice": lay.N_ADVICE, "table_rows": lay.table_rows}:
+        raise ValueError(f"range_c_layout: the C layout {out} is not RangeCheckLayout's")
+    return out
+
+
+def range_witness(values, k: int, max_bits: int = 4, acc_cols: int = 4, out=None):
+    """The range-check witnesses of m circuits: ``values`` (m, rows, 4) -- or (rows, 4), one circuit -- GPU tensor of canonical
+    Montgomery words -> (advice (m, 1 + acc_cols, 2^k, 4), over (m,) int32: per circuit the values at or above
+    2^(max_bits * acc_cols), whose limbs are their low bits only); every word written, rows >= ``rows`` zero; asynchronous on the
+    current stream.  ``out``: an advice tensor to fill instead of a new one (it may be uninitialised)."""
+    import torch
+
+    if not (_is_cuda_words(values) and values.dim() in (2, 3) and values.shape[-1] == 4):
+        raise ValueError("range_witness: values must be a contiguous (m, rows, 4) or (rows, 4) 64-bit GPU tensor")
+    m, rows = (1, values.shape[0]) if values.dim() == 2 else (values.shape[0], values.shape[1])
+    if m == 0 or rows == 0:
+        raise ValueError("range_witness: no values")
+    if out is not None and out.is_cuda and out.device != values.device:
+        raise ValueError(f"range_witness: out is on {out.device}, values on {values.device}")
+    for name, t in (("values", values), ("out", out)):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"range_witness: {name} must be 16-byte aligned")
+    out = _witness_out("range_witness", out, m, 1 + acc_cols, 1 << k, values.device)
+    over = torch.empty(m, dtype=torch.int32, device=values.device)
+    with torch.cuda.device(values.device):
+        _lib.check(_lib.load().hm_range_witness_bn256_fr_dev(max_bits, acc_cols, k, m, rows, ctypes.c_void_p(values.data_ptr()),
+                                                            ctypes.c_void_p(out.data_ptr()), _dev_ptr(over, _u32p),
+                                                            ctypes.c_void_p(_stream_ptr(values))))
+    return out, over
+
+
+def range_witness_host(values: np.ndarray, k: int, max_bits: int = 4, acc_cols: int = 4):
+    """``range_witness`` on a numpy (m, rows, 4) array through the host-pointer form (columns below 256 MiB)."""
+    vs = np.ascontiguousarray(np.asarray(values, dtype=np.uint64))
+    if vs.ndim == 2:
+        vs = vs.reshape(1, -1, 4)
+    if vs.ndim != 3 or vs.shape[2] != 4 or vs.shape[0] == 0 or vs.shape[1] == 0:
+        raise ValueError("range_witness_host: values must be a non-empty (m, rows, 4) array")
+    m, rows = vs.shape[0], vs.shape[1]
+    adv = np.zeros((m, 1 + acc_cols, 1 << k, 4), dtype=np.uint64)
+    over = np.zeros(m, dtype=np.uint32)
+    _lib.check(_lib.load().hm_range_witness_bn256_fr(max_bits, acc_cols, k, m, rows, _ptr(vs), _ptr(adv), over.ctypes.data_as(_u32p)))
+    return adv, over
+
+
+def _is_cuda_words(t) -> bool:
+    return hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and t.element_size() == 8
 
 
 columns_to_words = fr_array      # integer columns -> (len(cols), n, 4) uint64 Montgomery words (what the device tensors hold)

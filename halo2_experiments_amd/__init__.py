@@ -5,7 +5,7 @@ Host-side mirror of ``halo2_proofs::arithmetic`` (``best_multiexp``, ``best_fft`
 
 The sources live in ``halo2-experiments_amd/`` (the directory name the project layout prescribes; not a valid
 Python identifier): this package is the importable name, and its ``__path__`` points there, so every submodule
-(``_header``, ``_lib``, ``_marshal``, ``arithmetic``, ``batch_verifier``, ``bn256``, ``device_pairing``, ``device_transcript``, ``domain``, ``keygen``, ``kzg``, ``mock_prover``, ``openings``, ``pairing``, ``poseidon``, ``prover``, ``replay``, ``sharding``, ``shplonk``, ``synthesis``, ``transcript``, ``verifier``) is an ordinary module of this package
+(``_header``, ``_lib``, ``_marshal``, ``arithmetic``, ``batch_verifier``, ``bn256``, ``device_pairing``, ``device_transcript``, ``domain``, ``keygen``, ``kzg``, ``mock_prover``, ``openings``, ``pairing``, ``poseidon``, ``prover``, ``replay``, ``sharding``, ``shplonk``, ``solvency``, ``synthesis``, ``transcript``, ``verifier``) is an ordinary module of this package
 with an ordinary ``__spec__`` / ``__file__``.
 """
 import os as _os
@@ -29,9 +29,10 @@ from .pairing import pairing_check  # noqa: F401
 from .poseidon import MerkleSumTree, MerkleTree, Spec, poseidon_hash, poseidon_hash_host, update_plan  # noqa: F401
 from .prover import create_proof, create_proof_multi, create_proofs  # noqa: F401
 from .shplonk import construct_intermediate_sets, create_openings, set_quotient, set_quotient_batch, set_quotient_ints  # noqa: F401
-from .synthesis import (MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, merkle_sum_witness,  # noqa: F401
+from .solvency import BalanceProof, prove_balances, user_openings, verify_balances, verify_user, verify_users  # noqa: F401
+from .synthesis import (MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, RangeCheckLayout, merkle_sum_witness,  # noqa: F401
                         merkle_sum_witness_host, merkle_witness, merkle_witness_host, permutation_columns, poseidon_circuit_witness,
-                        poseidon_circuit_witness_host)
+                        poseidon_circuit_witness_host, range_c_layout, range_witness, range_witness_host)
 from .transcript import Blake2bRead, Blake2bWrite  # noqa: F401
 from .verifier import verify_proof, verify_proof_multi  # noqa: F401
 
@@ -46,4 +47,6 @@ __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_mult
            "permutation_columns_dev", "keygen_vk", "keygen_pk", "VerifyingKey", "ProvingKey",
            "create_proof", "create_proof_multi", "create_proofs", "verify_proof", "verify_proof_multi", "Blake2bWrite", "Blake2bRead", "pairing_check", "construct_intermediate_sets",
            "set_quotient", "set_quotient_batch", "set_quotient_ints", "create_openings", "linear_combination_batch", "MockProver", "MockResult", "NotSatisfied", "BatchVerifier", "verify_proofs",
-           "OpeningTable", "open_all", "open_all_ints", "open_at", "verify_opening", "verify_openings"]
+           "OpeningTable", "open_all", "open_all_ints", "open_at", "verify_opening", "verify_openings",
+           "RangeCheckLayout", "range_witness", "range_witness_host", "range_c_layout", "BalanceProof", "prove_balances", "verify_balances",
+           "user_openings", "verify_user", "verify_users"]

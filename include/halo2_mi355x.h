@@ -681,6 +681,26 @@ int hm_poseidon_witness_bn256_dev(uint64_t handle, uint32_t log_n, size_t m, con
                                   void* stream);
 int hm_poseidon_witness_bn256(uint64_t handle, uint32_t log_n, size_t m, const uint64_t* msgs, uint64_t* advice, uint64_t* instance);
 
+/* The witness of the range-check circuit (the reference's OverflowChipV2): advice column 0 holds the values, columns 1 .. acc_cols
+ * their limbs of max_bits bits, most significant first, so that sum limb_i * 2^(max_bits * (acc_cols - 1 - i)) = value whenever the
+ * value is below 2^(max_bits * acc_cols).
+ * layout: needs no device; *out_n_advice = 1 + acc_cols, *out_table_rows = 2^max_bits, the rows of the fixed range column.
+ * witness: m circuits of `rows` values each; d_values m x rows canonical elements; d_advice m x (1 + acc_cols) x 2^log_n elements
+ * (column c of circuit u is contiguous), every word of which is written: rows >= `rows` are zero (blinding is the prover's business).
+ * The limbs are the low max_bits * acc_cols bits of the value; nothing is judged: a larger value gives a witness that fails the gate,
+ * and d_over_or_null, unless NULL, receives per circuit the number of such values (m u32, set by every call).  Asynchronous on
+ * `stream`; no stream-ordered memory of the library's is used.
+ * HM_ERR_BAD_ARG, before anything is written or launched: a NULL pointer other than d_over_or_null, max_bits outside 1 .. 16,
+ * acc_cols = 0, max_bits * acc_cols > 253, log_n above 24, rows = 0, max(rows, 2^max_bits) > 2^log_n - 6, m = 0, m * 2^log_n > 2^31,
+ * a device pointer that is not 16-byte aligned (d_over: 4), d_values overlapping d_advice; the host form: more than 256 MiB of columns.
+ * Host form: outputs are written only by the final copies. */
+int hm_range_witness_layout(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, uint32_t rows, uint32_t* out_n_advice,
+                            uint32_t* out_table_rows);
+int hm_range_witness_bn256_fr_dev(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const void* d_values,
+                                  void* d_advice, uint32_t* d_over_or_null, void* stream);
+int hm_range_witness_bn256_fr(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint64_t* values,
+                              uint64_t* advice, uint32_t* over_or_null);
+
 /* keygen's permutation argument (permutation::keygen::Assembly) on the device.  A cell id is j * 2^k + i: column j of the
  * `columns` equality-enabled columns, row i; columns * 2^k <= 2^32.
  * assemble: d_copies holds m copy constraints as pairs of cell ids (DEVICE memory, 8-byte aligned).  d_sigma_cells receives

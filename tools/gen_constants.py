@@ -54,6 +54,9 @@ def field(name, mod):
     out += "  static constexpr uint32_t MOD32[8] = {%s};\n" % ", ".join("0x%08xu" % ((mod >> (32 * i)) & 0xFFFFFFFF) for i in range(8))
     out += "  static constexpr uint32_t TOPMOD = %du;      // MOD >> 232\n" % (mod >> 232)
     out += "  static constexpr uint32_t QK = %du;  // floor(2^53 / (TOPMOD + 1))\n" % ((1 << 53) // ((mod >> 232) + 1))
+    # a small plain integer l < 2^16 into external form without a Montgomery product (csrc/range.inc): l * INT2EXT - q * MOD with
+    # q = (l * EXTQ32) >> 32, which is floor(l * INT2EXT / MOD) or one less
+    out += "  static constexpr uint32_t EXTQ32 = %du;  // floor((2^256 mod MOD) * 2^32 / MOD)\n" % ((((1 << 256) % mod) << 32) // mod)
     out += "};\n"
     return out
 
