@@ -32,9 +32,20 @@ def keys(request):
     params.release()
 
 
-@pytest.mark.parametrize("m", [1, 2, 3])
+@pytest.mark.parametrize("m", [1, 2, 3, 65])
 def test_every_proof_has_create_proofs_bytes(keys, m):
     c = keys
+    if m == 65:
+        # one wavefront of proofs and one more: the SAME witness under seeds 0 .. 64, each proof create_proof's bytes for its seed
+        if c["name"] != "poseidon_k6":
+            assert c["name"] == "merkle_sum_d5_k9"     # the small circuit alone
+            return
+        same = c["advice"][:1].expand(m, -1, -1, -1).contiguous()
+        proofs = h.create_proofs(c["params"], c["pk"], same, [c["instances"][0]] * m, list(range(m)))
+        assert len(proofs) == m == len(set(proofs))
+        for b in range(m):
+            assert proofs[b] == h.create_proof(c["params"], c["pk"], c["advice"][0], c["instances"][0], b), b
+        return
     proofs = h.create_proofs(c["params"], c["pk"], c["advice"][:m], c["instances"][:m], SEEDS[:m])
     assert isinstance(proofs, list) and len(proofs) == m
     for b in range(m):
