@@ -739,6 +739,17 @@ int hc_verify_terms(const uint32_t* plan, size_t n_words, size_t n_columns, cons
   for (uint32_t s = 0; s < plan[VT_N_VALS]; ++s) vt_to_ext(vals + 8 * (size_t)s, vt_load(m, s));
   return ok ? 1 : 0;
 }
+// Phase a alone: the nine record slots as the lane's workspace holds them, limb by limb (9 x 9 words).  ge_run reads four of them as
+// constants, which it takes for canonical: below r, where everything else kept in the workspace is merely below 3r.
+int hc_verify_terms_record(const uint32_t* plan, size_t n_words, size_t n_columns, const uint32_t* rec, const uint32_t* evals,
+                           const uint32_t* inst, uint32_t* limbs) {
+  if (vt_plan_problem(plan, n_words, n_columns)) return -1;
+  std::vector<uint32_t> ws((size_t)vt_ws_program(plan) * 9, 0);
+  const VtMem m{ws.data(), 1, 0};
+  const bool ok = vt_phase_a(plan, m, rec, evals, inst);
+  for (uint32_t j = 0; j < VT_REC * 9; ++j) limbs[j] = ws[(size_t)plan[VT_N_VALS] * 9 + j];
+  return ok ? 1 : 0;
+}
 
 // Poseidon (poseidon.inc) on n messages, the exact per-hash code of its kernels.  consts: the spec's block as the library lays it out
 // on the device (rc, mds, capacity word; 9 limbs each, canonical internal form).  op 0: n x (width - 1) elements -> n digests;
