@@ -1,5 +1,5 @@
-// capi_g1.hip -- the G1 entry points of the C ABI outside the MSM: fixed-base multiples, best_fft over G1 (g1_fft.inc), all KZG openings
-// of a polynomial (kzg_open.inc) and the SRS point encodings (g1_codec.inc).
+// capi_g1.hip -- the G1 entry points of the C ABI outside the MSM: fixed-base multiples, best_fft over G1 (g1_fft.hip), all KZG openings
+// of a polynomial (g1_fft.hip) and the SRS point encodings (g1_codec.hip).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -40,7 +40,7 @@ int hm_g1_fft_bn256(uint64_t* points_xyz, const uint64_t omega[4], uint32_t log_
                          [&](uint8_t* d) { return g1_fft_run(*ctx, (uint32_t*)d, 24, omega, log_n, scale, nullptr); });
 } HM_API_CATCH("hm_g1_fft_bn256")
 
-// ---- all KZG openings of a polynomial on its domain (kzg_open.inc) ---------------------------------------------------------------
+// ---- all KZG openings of a polynomial on its domain (g1_fft.hip) ---------------------------------------------------------------
 int hm_kzg_open_table_bn256_dev(const void* d_g_xy, uint32_t log_n, void* d_table_xy, void* stream) try {
   if (!d_g_xy || !d_table_xy) return hm_fail(HM_ERR_BAD_ARG, "hm_kzg_open_table_bn256_dev: null argument");
   if (log_n > 23) return hm_fail(HM_ERR_BAD_ARG, "hm_kzg_open_table_bn256_dev: log_n > 23");

@@ -1,5 +1,5 @@
 // capi_mock.hip -- the witness checker's entry points of the C ABI: the gates, the copy constraints and the lookups of a batch of
-// witnesses checked on the device (mock.inc), failures appended to the caller's record buffer.
+// witnesses checked on the device (mock.hip), failures appended to the caller's record buffer.
 #include <hip/hip_runtime.h>
 
 #include <string>

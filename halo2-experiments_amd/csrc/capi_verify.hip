@@ -10,7 +10,7 @@
 #include "hm_internal.h"
 
 namespace hm {
-#include "verify_terms.inc"   // the plan's layout and its check (the kernels are in lookup.hip)
+#include "verify_terms.inc"   // the plan's layout and its check (the kernels are in verify.hip)
 #include "transcript.inc"     // the schedule's check (likewise)
 }
 using namespace hm;

@@ -1,6 +1,6 @@
-// g1_codec.inc -- the SRS point encodings of ParamsKZG::read / write: the kernels of g1_compress_run, g1_decompress_run and
-// g1_check_run (msm.hip, included from inside namespace hm there, so that they fall under msm.o's ISA checks).  DESIGN.md section 11.
-// The per-point functions are host-callable too: host_check.cpp includes this file (without the kernels) for the bound proof.
+// g1_codec.inc -- the SRS point encodings of ParamsKZG::read / write: the per-point functions of g1_compress_run, g1_decompress_run
+// and g1_check_run (g1_codec.hip holds the kernels and the drivers; verify.hip decompresses a proof's points with them).  DESIGN.md
+// section 11.  They are host-callable: host_check.cpp includes this file for the bound proof.  Included inside namespace hm.
 //
 //   compressed G1 (32 bytes): canonical x little-endian, bit 7 of byte 31 = parity of canonical y; the identity is 32 zero bytes
 //   raw G1 (64 bytes):        x, y as external Montgomery words, (0, 0) = identity (the library's affine layout)
@@ -62,7 +62,7 @@ HM_HD bool fq_equal(const Fq& a, const Fq& b) {   // both canonical
   return d == 0;
 }
 
-// one point each: the formula sequences of the kernels below, also built on the host with bound tracking (host_check.cpp)
+// one point each: the formula sequences of the kernels, also built on the host with bound tracking (host_check.cpp)
 // affine external words -> compressed words.  Input is trusted (the library's own points).
 HM_HD void g1_compress_one(const uint32_t (&wx)[8], const uint32_t (&wy)[8], uint32_t (&v)[8]) {
   uint32_t any = 0;
@@ -120,47 +120,3 @@ HM_HD bool g1_check_one(const uint32_t (&wx)[8], const uint32_t (&wy)[8]) {
   }
   return ok;
 }
-
-#if defined(__HIPCC__)
-__global__ __launch_bounds__(ACC_THREADS) void g1_compress_kernel(const uint32_t* __restrict__ xy, uint32_t* __restrict__ out, size_t n) {
-  const size_t i = (size_t)blockIdx.x * ACC_THREADS + threadIdx.x;
-  if (i >= n) return;
-  const uint4* q = reinterpret_cast<const uint4*>(xy + i * 16);
-  const uint4 a = q[0], b = q[1], c = q[2], d = q[3];
-  const uint32_t wx[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  const uint32_t wy[8] = {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
-  uint32_t v[8];
-  g1_compress_one(wx, wy, v);
-  uint4* o = reinterpret_cast<uint4*>(out + i * 8);
-  o[0] = make_uint4(v[0], v[1], v[2], v[3]);
-  o[1] = make_uint4(v[4], v[5], v[6], v[7]);
-}
-
-// invalid entries -> (0, 0) and atomicMin(first_bad, i)
-__global__ __launch_bounds__(ACC_THREADS) void g1_decompress_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ xy, size_t n,
-                                                                    unsigned long long* __restrict__ first_bad) {
-  const size_t i = (size_t)blockIdx.x * ACC_THREADS + threadIdx.x;
-  if (i >= n) return;
-  const uint4* q = reinterpret_cast<const uint4*>(in + i * 8);
-  const uint4 a = q[0], b = q[1];
-  const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  uint32_t ox[8], oy[8];
-  if (!g1_decompress_one(w, ox, oy)) atomicMin(first_bad, (unsigned long long)i);
-  uint4* o = reinterpret_cast<uint4*>(xy + i * 16);
-  o[0] = make_uint4(ox[0], ox[1], ox[2], ox[3]);
-  o[1] = make_uint4(ox[4], ox[5], ox[6], ox[7]);
-  o[2] = make_uint4(oy[0], oy[1], oy[2], oy[3]);
-  o[3] = make_uint4(oy[4], oy[5], oy[6], oy[7]);
-}
-
-__global__ __launch_bounds__(ACC_THREADS) void g1_check_kernel(const uint32_t* __restrict__ xy, size_t n,
-                                                               unsigned long long* __restrict__ first_bad) {
-  const size_t i = (size_t)blockIdx.x * ACC_THREADS + threadIdx.x;
-  if (i >= n) return;
-  const uint4* q = reinterpret_cast<const uint4*>(xy + i * 16);
-  const uint4 a = q[0], b = q[1], c = q[2], d = q[3];
-  const uint32_t wx[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  const uint32_t wy[8] = {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
-  if (!g1_check_one(wx, wy)) atomicMin(first_bad, (unsigned long long)i);
-}
-#endif

@@ -31,7 +31,7 @@ namespace hm {
 
 // the instruction encoding (GraphOp, GraphSrc, GraphCalc, GF_*, GE_CAP ...), graph_validate and graph_lower_host: graph_lower.h,
 // shared with the host replay of host_check.cpp; the interpreter body (ge_fetch, ge_reduce, ge_run and the column-word loads):
-// graph_interp.h, shared with the witness checker's kernel (mock.inc)
+// graph_interp.h, shared with the witness checker's kernel (mock.hip)
 
 // The call's column table and per-call constants (2.6 KiB) travel through a DEVICE buffer of the stream's AuxSlot,
 // filled by a stream-ordered copy ahead of the launch.  Rounds 1-2 passed the struct by value, and a variant with a

@@ -1,5 +1,5 @@
 // graph_interp.h -- the interpreter body of the device GraphEvaluator, shared by graph_evaluate_kernel (graph.hip: one lane per
-// row of a domain, the value stored) and graph_check_kernel (mock.inc: one lane per (user, row) of a witness batch, the value
+// row of a domain, the value stored) and graph_check_kernel (mock.hip: one lane per (user, row) of a witness batch, the value
 // only tested).  What differs between the two is where a column cell, a per-call constant and PreviousValue come from: a
 // `Source` answers those three questions, everything else -- the decode, the arithmetic, the [slot][word][lane] scratch of the
 // intermediates -- is the one body below.  Device code only; include after g1.h and graph_lower.h.

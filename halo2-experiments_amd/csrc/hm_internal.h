@@ -435,7 +435,11 @@ int fr_linear_combination_batch_run(const void* const* d_polys, const uint64_t* 
 int fr_shplonk_set_quotient_batch_run(const void* const* d_polys, const uint64_t* weights_ext, size_t m, uint64_t n, const uint64_t* points_ext,
                                       uint32_t t, const uint64_t* scales_ext, void* const* d_outs, bool accumulate, size_t proofs,
                                       hipStream_t stream);
-// Poseidon and Merkle trees (poseidon.inc).  Everything is asynchronous on `stream`; pointers are device memory of u32 words.
+// keygen's sigma columns: d_out[c] = delta^j' * omega^i' (external words) for d_sigma_cells[c] = j' * 2^k + i'
+int perm_columns_run(const uint32_t* d_sigma_cells, uint32_t columns, uint32_t k, const uint64_t omega_ext[4], const uint64_t delta_ext[4],
+                     uint32_t* d_out, hipStream_t stream);
+
+// poseidon.hip: Poseidon and Merkle trees.  Everything is asynchronous on `stream`; pointers are device memory of u32 words.
 int poseidon_spec_create(DeviceCtx& ctx, uint32_t width, uint32_t rate, uint32_t r_f, uint32_t r_p, const uint64_t* rc_ext,
                          const uint64_t* mds_ext, uint64_t* out_handle);
 void poseidon_spec_release(PoseidonSpec& s);
@@ -454,7 +458,9 @@ int merkle_update_run(const PoseidonSpec& s, uint32_t* d_nodes, uint32_t depth, 
 // the roots of m paths (siblings as merkle_paths_run writes them); the spec's width selects the elements per node
 int merkle_roots_run(const PoseidonSpec& s, uint32_t depth, size_t m, const uint32_t* d_leaves, const uint32_t* d_siblings,
                      const uint64_t* d_indices, uint32_t* d_roots, hipStream_t stream);
-// The witnesses of the three circuits (poseidon.inc).  E, the elements per node, selects the circuit: 2 MerkleSumTree, 1 MerkleTreeV3,
+// ascending bitonic sort of n_pow2 64-bit keys in place (the Merkle update's network; keygen.hip sorts its endpoint keys with it)
+int merkle_update_sort(uint64_t* d_keys, uint64_t n_pow2, hipStream_t stream);
+// The witnesses of the three circuits.  E, the elements per node, selects the circuit: 2 MerkleSumTree, 1 MerkleTreeV3,
 // 0 the Poseidon circuit (depth is ignored; its level_rows counts every row before the constants).
 // out = rows_used, n_advice, perm_rows, level_rows, lt_row (E = 2 only), const_row
 void witness_rows(uint32_t E, uint32_t depth, uint32_t r_f, uint32_t r_p, uint32_t (&out)[6]);
@@ -464,31 +470,30 @@ int merkle_witness_run(uint32_t E, const PoseidonSpec& s, uint32_t depth, uint32
                        uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream);
 int poseidon_witness_run(const PoseidonSpec& s, uint32_t log_n, size_t m, const uint32_t* d_msgs, uint32_t* d_advice, uint32_t* d_instance,
                          hipStream_t stream);
-// The range-check circuit's witness (range.inc): column 0 the m x rows values, columns 1 .. acc_cols their limbs of max_bits bits, most
+
+// range.hip: the range-check circuit's witness: column 0 the m x rows values, columns 1 .. acc_cols their limbs of max_bits bits, most
 // significant first; every row of every column is written; d_over: null, or m counters of the values with higher bits.  Asynchronous
 // on `stream`; the arguments were checked by the caller (capi_hash.hip).
 int range_witness_run(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint32_t* d_values,
                       uint32_t* d_advice, uint32_t* d_over, hipStream_t stream);
-// keygen's permutation assembly (keygen.inc).  d_copies: m pairs of cell ids, a cell being column * 2^k + row; d_sigma_cells receives
+
+// keygen.hip: keygen's permutation assembly.  d_copies: m pairs of cell ids, a cell being column * 2^k + row; d_sigma_cells receives
 // columns * 2^k ids (it is the union-find's parent array on the way); a pair with an id out of range is dropped and counted in
 // *d_dropped (null: not counted).  Asynchronous on `stream`; the arguments were checked by the caller (capi_keygen.hip).
 int perm_assemble_run(const uint32_t* d_copies, size_t m, uint32_t columns, uint32_t k, uint32_t* d_sigma_cells, uint32_t* d_dropped,
                       hipStream_t stream);
-// d_out[c] = delta^j' * omega^i' (external words) for d_sigma_cells[c] = j' * 2^k + i'
-int perm_columns_run(const uint32_t* d_sigma_cells, uint32_t columns, uint32_t k, const uint64_t omega_ext[4], const uint64_t delta_ext[4],
-                     uint32_t* d_out, hipStream_t stream);
 
 // lookup.hip
 int lookup_permute_run(DeviceCtx& ctx, const void* const* d_inputs, const void* const* d_tables, size_t pairs, uint64_t rows,
                        void* const* d_out_inputs, void* const* d_out_tables, int* missing, hipStream_t stream);
 
-// the sorted canonical keys of the first `live` (>= 1) elements of d_values, for a binary search (mock.inc): d_ws, of
+// the sorted canonical keys of the first `live` (>= 1) elements of d_values, for a binary search (mock.hip): d_ws, of
 // lookup_sorted_keys_bytes(live) bytes and 256-byte aligned, starts with the keys -- the next power of two of them, all-ones behind
 // the live ones.  Asynchronous on `stream`.
 size_t lookup_sorted_keys_bytes(uint64_t live);
 int lookup_sorted_keys_run(DeviceCtx& ctx, const uint32_t* d_values, uint64_t live, uint8_t* d_ws, hipStream_t stream);
 
-// mock.inc: the batched witness checker.  MockTable: per column of the program's table its base, the words from one user's column
+// mock.hip: the batched witness checker.  MockTable: per column of the program's table its base, the words from one user's column
 // to the next user's (0: shared) and the rows present (cells above read as zero) -- HOST arrays.  MockSink: where failures go, all
 // DEVICE memory of the caller's: `cap` records, one counter that keeps counting past cap, one byte per user.
 struct MockTable { const void* const* bases; const uint64_t* strides; const uint32_t* rows; size_t n; };
@@ -502,12 +507,6 @@ int mock_program_run(DeviceCtx& ctx, GraphProgram& g, const MockTable& t, const 
 // d_pairs: n_copies pairs of cell ids (permutation column j * 2^k + row); perm[j]: the table entry that column is
 int mock_copies_run(DeviceCtx& ctx, const MockTable& t, const uint32_t* perm, size_t n_perm, const uint32_t* d_pairs, size_t n_copies,
                     uint32_t k, size_t m, const MockSink& out, hipStream_t stream);
-
-// lookup.hip (verify_terms.inc): r_b x the scalars of every proof of a batch, one lane per proof; `plan` (host memory) is checked word
-// by word before anything is launched and uploaded with the call.  Asynchronous on `stream`.
-int verify_terms_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
-                     const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst, uint32_t* d_bad, uint32_t* d_own,
-                     uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream);
 
 // msm.hip
 int msm_convert_bases(const uint32_t* d_bases_ext, uint32_t* d_xy, uint8_t* d_inf, size_t n, hipStream_t stream);
@@ -547,36 +546,39 @@ int msm_precompute(uint32_t* d_table, const uint8_t* d_inf, size_t n, uint32_t c
 void host_sum_points(const uint64_t* pts, size_t count, uint64_t out_jac_ext[12], int* out_is_identity);
 int g1_fixed_base_mul_run(DeviceCtx& ctx, const uint32_t* d_scalars_ext, size_t n, const uint64_t base_affine_ext[8],
                           uint32_t* d_out_affine_ext, hipStream_t stream);
+
+// g1_fft.hip
 // best_fft over G1 in place on n = 2^log_n <= 2^24 points of `words` u32 each: 16 affine external ((0, 0) = identity) or 24
 // Jacobian external (z = 0 = identity; outputs (x, y, 1) / zeros).  scale_ext: optional Fr Montgomery words multiplied into every output.
 int g1_fft_run(DeviceCtx& ctx, uint32_t* d_points, uint32_t words, const uint64_t omega_ext[4], uint32_t log_n,
                const uint64_t* scale_ext, hipStream_t stream);
-// All KZG openings of a polynomial on its domain (kzg_open.inc; FK20), n = 2^log_n <= 2^23, asynchronous on `stream`.  table: the
+// All KZG openings of a polynomial on its domain (FK20), n = 2^log_n <= 2^23, asynchronous on `stream`.  table: the
 // G1 FFT of size 2n of the reversed first n monomial points (16-word affine external, (0, 0) = identity), written from them by
 // kzg_open_table_run; open_all: `count` polynomials of n x 8 Fr words back to back -> count x n affine proofs, proof t the opening at
 // omega_n^t.  part_ms: null, or 7 doubles for the step times of the last polynomial (the call then waits for `stream`).
 int kzg_open_table_run(DeviceCtx& ctx, const uint32_t* d_g_xy, uint32_t log_n, uint32_t* d_table_xy, hipStream_t stream);
 int kzg_open_all_run(DeviceCtx& ctx, const uint32_t* d_table_xy, const uint32_t* d_coeffs, uint32_t log_n, size_t count,
                      uint32_t* d_proofs_xy, hipStream_t stream, double* part_ms = nullptr);
-// SRS point encodings (g1_codec.inc): 16-word affine external points <-> 8-word compressed encodings.  compress is asynchronous;
+
+// g1_codec.hip: SRS point encodings: 16-word affine external points <-> 8-word compressed encodings.  compress is asynchronous;
 // decompress / check wait for `stream` and answer HM_ERR_INVALID_DATA with the smallest invalid index in *first_invalid (n if none).
 int g1_compress_run(const uint32_t* d_xy, size_t n, uint32_t* d_out32, hipStream_t stream);
 int g1_decompress_run(const uint32_t* d_in32, size_t n, uint32_t* d_xy, uint64_t* first_invalid, hipStream_t stream);
 int g1_check_run(const uint32_t* d_xy, size_t n, uint64_t* first_invalid, hipStream_t stream);
-// A batch of proofs (verify_read.inc): every 32-byte slot of n_proofs proofs read by the kinds of the device table (points decompressed,
+
+// verify.hip: the device side of a batch verification
+// A batch of proofs: every 32-byte slot of n_proofs proofs read by the kinds of the device table (points decompressed,
 // scalars checked), and the sum of rows [lo, hi) of every column of a (rows, cols) array of Fr words.  Both asynchronous on `stream`.
 int verify_read_run(const uint32_t* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots, uint32_t own_points,
                     uint32_t n_points, uint32_t n_scalars, uint32_t* d_points, uint32_t* d_tail, uint32_t* d_ybytes, uint32_t* d_scalars,
                     uint32_t* d_bad, hipStream_t stream);
 int verify_colsum_run(const uint32_t* d_rows, uint32_t cols, size_t lo, size_t hi, uint32_t* d_out, hipStream_t stream);
-
-// pairing.inc (lookup.hip): the Miller loops of n_pairs pairs, then product and final exponentiation of n_checks checks, in d_work
-// (pairing_work_words u32 words); both launches asynchronous on `stream`
-size_t pairing_work_words(size_t n_pairs, size_t n_checks);
-int pairing_check_run(const uint32_t* d_g1, const uint32_t* d_g2, size_t n_pairs, const uint32_t* d_offsets, size_t n_checks, uint32_t* d_gt,
-                      uint32_t* d_status, uint32_t* d_work, hipStream_t stream);
-
-// transcript.inc (lookup.hip): Blake2b-512 of n messages at a fixed byte stride (personal16: host memory or null), and the transcripts
+// r_b x the scalars of every proof of a batch, one lane per proof; `plan` (host memory) is checked word by word before anything is
+// launched and uploaded with the call.  Asynchronous on `stream`.
+int verify_terms_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
+                     const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst, uint32_t* d_bad, uint32_t* d_own,
+                     uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream);
+// Blake2b-512 of n messages at a fixed byte stride (personal16: host memory or null), and the transcripts
 // of n_proofs proofs -- `schedule` (host memory, n_pairs pairs) is checked before anything is launched and uploaded with the call.
 // Both asynchronous on `stream`.
 int blake2b_run(const uint8_t* d_msgs, size_t stride, const uint32_t* d_lens, size_t n, const uint8_t* personal16, uint32_t* d_out,
@@ -585,5 +587,11 @@ int verify_transcript_run(DeviceCtx& ctx, const uint32_t* d_proofs, size_t n_pro
                           uint32_t n_points, const uint32_t* d_ybytes, const uint32_t* d_preamble, const uint32_t* d_counts, uint32_t stride,
                           const uint32_t* schedule, size_t n_pairs, uint32_t* d_bad, uint32_t* d_records, uint32_t record_elems,
                           hipStream_t stream);
+
+// pairing.hip: the Miller loops of n_pairs pairs, then product and final exponentiation of n_checks checks, in d_work
+// (pairing_work_words u32 words); both launches asynchronous on `stream`
+size_t pairing_work_words(size_t n_pairs, size_t n_checks);
+int pairing_check_run(const uint32_t* d_g1, const uint32_t* d_g2, size_t n_pairs, const uint32_t* d_offsets, size_t n_checks, uint32_t* d_gt,
+                      uint32_t* d_status, uint32_t* d_work, hipStream_t stream);
 
 }  // namespace hm

@@ -15,18 +15,18 @@
 #include "g1.h"
 #include "graph_lower.h"
 #include "host_fr.h"
-#include "mock_check.h"   // the witness checker's key search, value key and record packing (its kernels are HIP-only)
+#include "mock_check.h"   // the witness checker's key search, value key and record packing (its kernels: mock.hip)
 
 namespace hm {
-#include "g1_codec.inc"   // the per-point SRS codec formulas (its kernels are HIP-only)
-#include "verify_read.inc"   // the batch verifier's per-slot read and its column sum (likewise)
-#include "verify_terms.inc"  // ... and the two phases of its per-proof terms around the interpreter's run (likewise)
-#include "poseidon.inc"   // the per-hash Poseidon / Merkle node functions (likewise)
-#include "range.inc"      // the range-check witness's lane function (likewise)
-#include "keygen.inc"     // the permutation assembly's key packing and link rule (likewise)
-#include "shplonk.inc"    // the SHPLONK set quotient's plan, coefficients and row formula (likewise)
-#include "pairing.inc"    // the pairing's tower, Miller lane and final exponentiation (likewise)
-#include "transcript.inc" // Blake2b-512, its streaming absorber and the transcript lane of a proof (likewise)
+#include "g1_codec.inc"   // the per-point SRS codec formulas (the kernels: g1_codec.hip)
+#include "verify_read.inc"   // the batch verifier's per-slot read and its column sum (verify.hip)
+#include "verify_terms.inc"  // ... and the two phases of its per-proof terms around the interpreter's run (verify.hip)
+#include "poseidon.inc"   // the per-hash Poseidon / Merkle node functions (poseidon.hip)
+#include "range.inc"      // the range-check witness's lane function (range.hip)
+#include "keygen.inc"     // the permutation assembly's key packing and link rule (keygen.hip)
+#include "shplonk.inc"    // the SHPLONK set quotient's plan, coefficients and row formula (polyops.hip)
+#include "pairing.inc"    // the pairing's tower, Miller lane and final exponentiation (pairing.hip)
+#include "transcript.inc" // Blake2b-512, its streaming absorber and the transcript lane of a proof (verify.hip)
 }
 
 using namespace hm;

@@ -23,11 +23,8 @@
 #include <vector>
 
 #include "g1.h"
-#include "graph_interp.h"
-#include "graph_lower.h"
 #include "hm_internal.h"
 #include "host_fr.h"
-#include "mock_check.h"
 
 namespace hm {
 
@@ -587,12 +584,5 @@ int lookup_permute_run(DeviceCtx& ctx, const void* const* d_inputs, const void* 
   if (result == HM_ERR_INTERNAL) return hm_fail(HM_ERR_INTERNAL, "lookup permute: leftover / repeated counts differ");
   return rrc;
 }
-
-#include "mock.inc"       // the batched witness checker: its lookup pass searches keys sorted by the code above
-#define HM_VERIFY_TERMS_KERNELS
-#include "verify_terms.inc"   // the batch verifier's per-proof terms: the same interpreter on one lane per proof
-#include "pairing.inc"        // batched pairing product checks: pairing_check_run / pairing_work_words
-#define HM_TRANSCRIPT_KERNELS
-#include "transcript.inc"     // Blake2b-512 and the batch verifier's transcripts, one lane per proof: blake2b_run / verify_transcript_run
 
 }  // namespace hm

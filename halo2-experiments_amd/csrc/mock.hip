@@ -1,4 +1,4 @@
-// mock.inc -- MockProver::verify for a BATCH of witnesses on the device (upstream halo2_proofs dev.rs: every gate polynomial on
+// mock.hip -- MockProver::verify for a BATCH of witnesses on the device (upstream halo2_proofs dev.rs: every gate polynomial on
 // every usable row, both cells of every copy constraint, every lookup input in its table; mock_prover.py is the caller).
 //
 // The witnesses of m users lie as the witness kernels leave them: m x num_advice x n elements of advice, m x rows_i of every
@@ -14,7 +14,21 @@
 // Failures are APPENDED: one ballot per wave, one atomicAdd per wave with a failure on the call's counter, every failing lane
 // writes its record if its slot is below the capacity -- the counter keeps counting, so the total is exact whatever the
 // capacity -- and sets its user's byte in a flag array.  Nothing else is written.
-// Included by lookup.hip inside namespace hm, behind the sort it uses (lookup_sorted_keys_run).
+// The kernels and the drivers mock_program_run / mock_copies_run; the sorted keys come from lookup.hip (lookup_sorted_keys_run).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include "g1.h"
+#include "graph_interp.h"
+#include "graph_lower.h"
+#include "hm_internal.h"
+#include "host_fr.h"
+#include "mock_check.h"
+
+namespace hm {
 
 struct CheckColumns {
   const uint32_t* p[GE_MAX_COLUMNS];
@@ -240,3 +254,4 @@ int mock_copies_run(DeviceCtx& ctx, const MockTable& t, const uint32_t* perm, si
   return aux_release(ctx, slot, stream);
 }
 
+}  // namespace hm

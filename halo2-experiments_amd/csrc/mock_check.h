@@ -1,4 +1,4 @@
-// mock_check.h -- the rules of the witness checker (mock.inc) that the host states too (host_check.cpp: hc_mock_key_search, hc_mock_value_key,
+// mock_check.h -- the rules of the witness checker (mock.hip) that the host states too (host_check.cpp: hc_mock_key_search, hc_mock_value_key,
 // hc_mock_record; tests/test_mock_prover.py): how a value becomes a key, how a key is searched in the sorted table keys, and how
 // a failure is packed into a record.
 #pragma once

@@ -24,9 +24,9 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "fq_inverse.h"
 #include "hm_internal.h"
 #include "host_fq.h"
-#include "host_fr.h"
 #include "msm_dev.h"
 
 namespace hm {
@@ -1522,23 +1522,6 @@ __global__ void g1_fixed_table_kernel(G1AffineWords base_ext, uint32_t* __restri
   }
 }
 
-__device__ __forceinline__ Fq fq_inverse(const Fq& a) {  // a^(p-2), a a product output
-  // exponent p - 2 in 29-bit limbs
-  uint32_t e[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) e[i] = FqParams::MOD[i];
-  e[0] -= 2;  // MOD[0] is odd and > 2: no borrow
-  Fq acc = fe_one<FqParams>();
-  for (int i = 8; i >= 0; --i) {
-    const int top = i == 8 ? 24 : 28;
-    for (int bit = top; bit >= 0; --bit) {
-      acc = fe_sqr(acc);
-      if ((e[i] >> bit) & 1) acc = fe_mul(acc, a);
-    }
-  }
-  return acc;
-}
-
 // Precomputed multiples for a fixed base set: table[j*n + i] = 2^(c*j) * P_i (affine, internal
 // packed), j < W.  With them every window's digit indexes its own copy of the point and ALL windows
 // share one set of 2^(c-1) buckets, so the window size is no longer capped by W bucket sets (c = 22,
@@ -1674,11 +1657,6 @@ __global__ __launch_bounds__(ACC_THREADS) void g1_fixed_base_mul_kernel(const ui
   o[2] = make_uint4(oy[0], oy[1], oy[2], oy[3]);
   o[3] = make_uint4(oy[4], oy[5], oy[6], oy[7]);
 }
-
-#include "g1_fft.inc"   // best_fft over G1: g1_fft_run below
-#include "kzg_open.inc" // all KZG openings of a polynomial on its domain (FK20): kzg_open_table_run / kzg_open_all_run
-#include "g1_codec.inc" // SRS point encodings: g1_compress_run / g1_decompress_run / g1_check_run below
-#include "verify_read.inc" // a batch of proofs read slot by slot, and the column sums of its shared scalars: verify_*_run below
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -2462,129 +2440,6 @@ int g1_fixed_base_mul_run(DeviceCtx& ctx, const uint32_t* d_scalars_ext, size_t 
                      stream, d_scalars_ext, (const uint32_t*)d_table, d_out_affine_ext, n);
   HM_HIP_CHECK(hipGetLastError());
   return aux_release(ctx, slot, stream);
-}
-
-// best_fft over G1 (g1_fft.inc), in place on `d_points`: WORDS = 16 u32 per point (affine external, (0, 0) = identity) or 24
-// (Jacobian external, z = 0 = identity; written back as (x, y, 1) / zeros).  The working buffer (n Jacobian records) and the
-// twiddle table (n / 2 canonical omega^j) are allocated per call, stream-ordered on `stream`, and freed behind the last kernel.
-int g1_fft_run(DeviceCtx& ctx, uint32_t* d_points, uint32_t words, const uint64_t omega_ext[4], uint32_t log_n,
-               const uint64_t* scale_ext, hipStream_t stream) {
-  (void)ctx;
-  if (log_n > G1_FFT_LOG_MAX) return hm_fail(HM_ERR_BAD_ARG, "g1_fft: log_n > 24");
-  if (words != 16 && words != 24) return hm_fail(HM_ERR_BAD_ARG, "g1_fft: point layout must be 16 or 24 words");
-  const size_t n = (size_t)1 << log_n, half = n / 2;
-  G1FftScale scale{};
-  if (scale_ext) {
-    const host::Fr4 one_int = {{1, 0, 0, 0}};
-    const host::Fr4 v = host::fr_mul(host::fr_load(scale_ext), one_int);    // Montgomery words -> canonical integer
-    std::memcpy(scale.w, v.l, 32);
-    scale.on = 1;
-  }
-  const size_t work_bytes = n * PT_WORDS * 4, tw_bytes = half * 32;
-  void* mem = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&mem, work_bytes + tw_bytes, stream));
-  uint32_t* work = (uint32_t*)mem;
-  uint32_t* tw = work + n * PT_WORDS;
-  const dim3 all((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS)), pairs((uint32_t)((half + ACC_THREADS - 1) / ACC_THREADS));
-  int rc = HM_OK;
-  if (half) {
-    rc = fr_powers_run(tw, half, omega_ext, stream);
-    if (rc == HM_OK) {
-      hipLaunchKernelGGL(g1_fft_twiddle_kernel, dim3((uint32_t)((half + 255) / 256)), dim3(256), 0, stream, tw, half);
-      if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: twiddle kernel launch failed");
-    }
-  }
-  if (rc == HM_OK) {
-    if (words == 16) hipLaunchKernelGGL(g1_fft_load_kernel<16>, all, dim3(ACC_THREADS), 0, stream, d_points, work, log_n);
-    else hipLaunchKernelGGL(g1_fft_load_kernel<24>, all, dim3(ACC_THREADS), 0, stream, d_points, work, log_n);
-    if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: load kernel launch failed");
-  }
-  for (uint32_t s = 0; rc == HM_OK && s < log_n; ++s) {
-    if (log_n - 1 - s >= 6) hipLaunchKernelGGL(g1_fft_stage_kernel<true>, pairs, dim3(ACC_THREADS), 0, stream, work, tw, log_n, s);
-    else hipLaunchKernelGGL(g1_fft_stage_kernel<false>, pairs, dim3(ACC_THREADS), 0, stream, work, tw, log_n, s);
-    if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: stage kernel launch failed");
-  }
-  if (rc == HM_OK) {
-    if (words == 16) hipLaunchKernelGGL(g1_fft_store_kernel<16>, all, dim3(ACC_THREADS), 0, stream, work, d_points, log_n, scale);
-    else hipLaunchKernelGGL(g1_fft_store_kernel<24>, all, dim3(ACC_THREADS), 0, stream, work, d_points, log_n, scale);
-    if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: store kernel launch failed");
-  }
-  const hipError_t fe = hipFreeAsync(mem, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("g1_fft: hipFreeAsync: ") + hipGetErrorString(fe));
-  return rc;
-}
-
-// SRS point encodings (g1_codec.inc).  Compression is asynchronous on `stream`.
-int g1_compress_run(const uint32_t* d_xy, size_t n, uint32_t* d_out32, hipStream_t stream) {
-  if (n == 0) return HM_OK;
-  hipLaunchKernelGGL(g1_compress_kernel, dim3((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS)), dim3(ACC_THREADS), 0, stream, d_xy,
-                     d_out32, n);
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
-}
-
-// The validating kernels lower one device word (allocated per call, stream-ordered, all ones) to the smallest invalid index; this waits for
-// `stream`, reads it back and answers HM_ERR_INVALID_DATA with *first_invalid set, or HM_OK with *first_invalid = n.
-template <class Launch>
-static int g1_codec_validating_run(const char* who, size_t n, uint64_t* first_invalid, hipStream_t stream, Launch launch) {
-  *first_invalid = n;
-  if (n == 0) return HM_OK;
-  void* mem = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&mem, sizeof(unsigned long long), stream));
-  unsigned long long* flag = (unsigned long long*)mem;
-  unsigned long long bad = ~0ull;
-  int rc = HM_OK;
-  const hipError_t me = hipMemsetAsync(flag, 0xff, sizeof(bad), stream);
-  if (me != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": hipMemsetAsync: " + hipGetErrorString(me));
-  if (rc == HM_OK) {
-    launch(dim3((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS)), flag);
-    if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": kernel launch failed");
-  }
-  if (rc == HM_OK) {
-    const hipError_t ce = hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, stream);
-    if (ce != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": reading the flag: " + hipGetErrorString(ce));
-  }
-  const hipError_t fe = hipFreeAsync(mem, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": hipFreeAsync: " + hipGetErrorString(fe));
-  const hipError_t se = hipStreamSynchronize(stream);
-  if (rc == HM_OK && se != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": " + hipGetErrorString(se));
-  if (rc == HM_OK && bad < n) {
-    *first_invalid = bad;
-    rc = hm_fail(HM_ERR_INVALID_DATA, std::string(who) + ": invalid point at index " + std::to_string(bad));
-  }
-  return rc;
-}
-
-int g1_decompress_run(const uint32_t* d_in32, size_t n, uint32_t* d_xy, uint64_t* first_invalid, hipStream_t stream) {
-  return g1_codec_validating_run("g1_decompress", n, first_invalid, stream, [&](dim3 grid, unsigned long long* flag) {
-    hipLaunchKernelGGL(g1_decompress_kernel, grid, dim3(ACC_THREADS), 0, stream, d_in32, d_xy, n, flag);
-  });
-}
-
-int g1_check_run(const uint32_t* d_xy, size_t n, uint64_t* first_invalid, hipStream_t stream) {
-  return g1_codec_validating_run("g1_check", n, first_invalid, stream, [&](dim3 grid, unsigned long long* flag) {
-    hipLaunchKernelGGL(g1_check_kernel, grid, dim3(ACC_THREADS), 0, stream, d_xy, n, flag);
-  });
-}
-
-// A batch of proofs (verify_read.inc).  Both are asynchronous on `stream`; every index the read kernel takes from the device table is
-// checked there against the sizes given here.
-int verify_read_run(const uint32_t* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots, uint32_t own_points,
-                    uint32_t n_points, uint32_t n_scalars, uint32_t* d_points, uint32_t* d_tail, uint32_t* d_ybytes, uint32_t* d_scalars,
-                    uint32_t* d_bad, hipStream_t stream) {
-  const uint64_t lanes = (uint64_t)n_proofs * slots;
-  if (lanes == 0) return HM_OK;
-  hipLaunchKernelGGL(verify_read_kernel, dim3((uint32_t)((lanes + ACC_THREADS - 1) / ACC_THREADS)), dim3(ACC_THREADS), 0, stream, d_proofs,
-                     d_slot_table, slots, lanes, own_points, n_points, n_scalars, d_points, d_tail, d_ybytes, d_scalars, d_bad);
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
-}
-
-int verify_colsum_run(const uint32_t* d_rows, uint32_t cols, size_t lo, size_t hi, uint32_t* d_out, hipStream_t stream) {
-  if (cols == 0) return HM_OK;
-  hipLaunchKernelGGL(verify_colsum_kernel, dim3(cols), dim3(COLSUM_THREADS), 0, stream, d_rows, cols, (uint64_t)lo, (uint64_t)hi, d_out);
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
 }
 
 }  // namespace hm

@@ -17,8 +17,8 @@
 //            (p^4 - p^2 + 1) / r = l0 + l1 p + l2 p^2 + p^3, l2 = 6x^2 + 1, l1 = -36x^3 - 18x^2 - 12x + 1, l0 = -36x^3 - 30x^2 - 18x - 2:
 //            three powers by x, a short product chain, conjugation for the negative exponents; the squares behind the easy part
 //            are cyclotomic (Granger-Scott: 9 Fq2 squares).
-// Included by lookup.hip inside namespace hm.  Everything but the two kernels is host-callable: host_check.cpp includes this file for
-// the bound proof and for the comparison with the oracle on a machine without a GPU.
+// Included inside namespace hm by pairing.hip, which holds the two kernels and their driver.  Everything here is host-callable:
+// host_check.cpp includes this file for the bound proof and for the comparison with the oracle on a machine without a GPU.
 
 struct Fq2 {
   Fq c0, c1;
@@ -467,60 +467,3 @@ HM_HD uint32_t pf_finish_lane(uint64_t lo, uint64_t hi, uint64_t n_pairs, const 
   }
   return diff == 0 ? 1u : 0u;
 }
-
-#if defined(__HIPCC__)
-constexpr int PF_THREADS = 64;
-
-__global__ __launch_bounds__(PF_THREADS) void pairing_miller_kernel(const uint32_t* __restrict__ g1, const uint32_t* __restrict__ g2,
-                                                                    uint64_t n_pairs, uint32_t* __restrict__ slots,
-                                                                    uint32_t* __restrict__ flags) {
-  const uint64_t i = (uint64_t)blockIdx.x * PF_THREADS + threadIdx.x;
-  if (i >= n_pairs) return;
-  uint32_t p[16], q[32];
-  {
-    const uint4* s = reinterpret_cast<const uint4*>(g1 + i * 16);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint4 v = s[k];
-      p[4 * k] = v.x, p[4 * k + 1] = v.y, p[4 * k + 2] = v.z, p[4 * k + 3] = v.w;
-    }
-    const uint4* t = reinterpret_cast<const uint4*>(g2 + i * 32);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const uint4 v = t[k];
-      q[4 * k] = v.x, q[4 * k + 1] = v.y, q[4 * k + 2] = v.z, q[4 * k + 3] = v.w;
-    }
-  }
-  flags[i] = pf_miller_lane(p, q, PfLane{slots + i, (size_t)n_pairs});
-}
-
-__global__ __launch_bounds__(PF_THREADS) void pairing_finish_kernel(const uint32_t* __restrict__ offsets, uint64_t n_pairs, uint64_t n_checks,
-                                                                    uint32_t* __restrict__ pair_slots, const uint32_t* __restrict__ flags,
-                                                                    uint32_t* __restrict__ check_slots, uint32_t* __restrict__ gt,
-                                                                    uint32_t* __restrict__ status) {
-  const uint64_t c = (uint64_t)blockIdx.x * PF_THREADS + threadIdx.x;
-  if (c >= n_checks) return;
-  status[c] = pf_finish_lane(offsets[c], offsets[c + 1], n_pairs, PfLane{pair_slots, (size_t)n_pairs}, flags,
-                             PfLane{check_slots + c, (size_t)n_checks}, gt ? gt + c * PF_WORDS : nullptr);
-}
-
-// words of the workspace: the pairs' slots, their flags, the checks' slots
-size_t pairing_work_words(size_t n_pairs, size_t n_checks) {
-  return (size_t)PF_PAIR_SLOTS * PF_WORDS * n_pairs + n_pairs + (size_t)PF_CHECK_SLOTS * PF_WORDS * n_checks;
-}
-
-int pairing_check_run(const uint32_t* d_g1, const uint32_t* d_g2, size_t n_pairs, const uint32_t* d_offsets, size_t n_checks, uint32_t* d_gt,
-                      uint32_t* d_status, uint32_t* d_work, hipStream_t stream) {
-  uint32_t* pair_slots = d_work;
-  uint32_t* flags = pair_slots + (size_t)PF_PAIR_SLOTS * PF_WORDS * n_pairs;
-  uint32_t* check_slots = flags + n_pairs;
-  if (n_pairs) {
-    pairing_miller_kernel<<<(unsigned)((n_pairs + PF_THREADS - 1) / PF_THREADS), PF_THREADS, 0, stream>>>(d_g1, d_g2, n_pairs, pair_slots, flags);
-    HM_HIP_CHECK(hipGetLastError());
-  }
-  pairing_finish_kernel<<<(unsigned)((n_checks + PF_THREADS - 1) / PF_THREADS), PF_THREADS, 0, stream>>>(d_offsets, n_pairs, n_checks, pair_slots,
-                                                                                                       flags, check_slots, d_gt, d_status);
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
-}
-#endif

@@ -455,9 +455,142 @@ __global__ __launch_bounds__(PO_THREADS) void fr_lincomb_batch_kernel(const uint
 }
 
 // ---------------------------------------------------------------------------------------------
-// the SHPLONK set quotient: the plan, the coefficients and the kernels in shplonk.inc
+// the SHPLONK set quotient: the plan, the coefficients and the row formula in shplonk.inc, the kernels here
 // ---------------------------------------------------------------------------------------------
 #include "shplonk.inc"
+
+// f(integral_constant<l>) for l = 0 .. T - 1, spelled out: the per-point state lives in arrays that must stay in registers, and the
+// loops around a workgroup scan or a square-and-multiply are not unrolled by the pragma
+template <int I, int T, class F>
+__device__ __forceinline__ void shq_each(F&& f) {
+  if constexpr (I < T) {
+    f(std::integral_constant<int, I>{});
+    shq_each<I + 1, T>(f);
+  }
+}
+
+struct ShqArgs {
+  PoFr z[SHQ_T_MAX];       // the points, true internal form
+  PoFr d[SHQ_T_MAX];       // scale * c_l, true internal form
+};
+
+// S_L of every point from ONE read of the lane's chunk, then one workgroup scan per point (the LDS planes are reused: the scan's last
+// barrier follows its last read).  Scratch of point l: incl + l * (G * 256 + 1) * 9, wg_total + l * G * 9 -- the layout
+// fr_kate_join_kernel expects of its columns.
+template <int T>
+__device__ __forceinline__ void shq_chunks_body(uint32_t* lds, const uint32_t* __restrict__ a, uint64_t n, const ShqArgs& args, uint32_t B,
+                                                uint32_t* __restrict__ incl, uint32_t* __restrict__ wg_total) {
+  const uint32_t t = threadIdx.x;
+  const uint64_t L = (uint64_t)blockIdx.x * PO_THREADS + t;
+  const uint64_t lo = L * B, hi = lo + B < n ? lo + B : n;
+  Fr z[T], acc[T];
+#pragma unroll
+  for (int l = 0; l < T; ++l) {
+    z[l] = po_arg(args.z[l]);
+    acc[l] = fe_zero<FrParams>();
+    HM_DECLARE(acc[l], 0.0);
+  }
+  for (uint64_t j = hi; j > lo; --j) {
+    const Fr raw = po_load_raw(a, j - 1);
+#pragma unroll
+    for (int l = 0; l < T; ++l) acc[l] = fe_add(fe_mul(acc[l], z[l]), raw);
+  }
+  const size_t lanes = (size_t)gridDim.x * PO_THREADS + 1;
+  shq_each<0, T>([&](auto lc) {
+    constexpr int l = decltype(lc)::value;
+    Fr s = fe_reduce_small(fe_norm(acc[l]));
+    s = po_suffix_scan_uniform(lds, s, po_pow_small(z[l], B));
+    po_store9(incl + ((size_t)l * lanes + L) * 9, s);
+    if (t == 0) po_store9(wg_total + ((size_t)l * gridDim.x + blockIdx.x) * 9, s);
+  });
+}
+template <int T>
+__global__ __launch_bounds__(PO_THREADS) void fr_shq_chunks_kernel(const uint32_t* __restrict__ a, uint64_t n, ShqArgs args, uint32_t B,
+                                                                   uint32_t* __restrict__ incl, uint32_t* __restrict__ wg_total) {
+  __shared__ uint32_t lds[9 * PO_THREADS];
+  shq_chunks_body<T>(lds, a, n, args, B, incl, wg_total);
+}
+
+// Every lane replays its chunk for all T points at once and writes the combined row.  Rows at and above n - T are zero in the sum:
+// written as zero, or left alone when accumulating.
+template <int T>
+__device__ __forceinline__ void shq_replay_body(const uint32_t* __restrict__ a, uint64_t n, const ShqArgs& args, uint32_t B,
+                                                const uint32_t* __restrict__ incl, const uint32_t* __restrict__ carry,
+                                                uint32_t* __restrict__ out, int accumulate) {
+  const uint32_t t = threadIdx.x;
+  const uint64_t L = (uint64_t)blockIdx.x * PO_THREADS + t;
+  const uint64_t lo = L * B;
+  if (lo >= n) return;
+  const uint64_t hi = lo + B < n ? lo + B : n;
+  const size_t lanes = (size_t)gridDim.x * PO_THREADS + 1;
+  Fr z[T], d[T], cur[T];
+  shq_each<0, T>([&](auto lc) {
+    constexpr int l = decltype(lc)::value;
+    z[l] = po_arg(args.z[l]);
+    d[l] = po_arg(args.d[l]);
+    // T_L = (inclusive value of the next lane in this workgroup) + y^(255 - t) * E_g, as in fr_kate_replay_kernel
+    Fr Tl = fe_mul(po_load9(carry + ((size_t)l * gridDim.x + blockIdx.x) * 9, 3.0), po_pow_small(po_pow_small(z[l], B), PO_THREADS - 1 - t));
+    if (t + 1 < PO_THREADS) Tl = fe_add(Tl, po_load9(incl + ((size_t)l * lanes + L + 1) * 9, 3.0));
+    cur[l] = fe_reduce_small(fe_norm(Tl));                  // Q_l[hi - 1]
+  });
+  const auto emit = [&](uint64_t i) {
+    if (i + T < n) {
+      Fr old = fe_zero<FrParams>();
+      if (accumulate) old = po_load_raw(out, i);
+      po_store_canonical(out, i, shq_row<T>(cur, d, accumulate != 0, old));
+    } else if (!accumulate) {
+      uint4* dst = reinterpret_cast<uint4*>(out + i * 8);
+      dst[0] = make_uint4(0, 0, 0, 0);
+      dst[1] = make_uint4(0, 0, 0, 0);
+    }
+  };
+  emit(hi - 1);
+  for (uint64_t i = hi - 1; i > lo; --i) {                  // Q_l[i - 1] = a[i] + p_l Q_l[i]
+    const Fr raw = po_load_raw(a, i);
+#pragma unroll
+    for (int l = 0; l < T; ++l) cur[l] = fe_reduce_small(fe_norm(fe_add(fe_mul(cur[l], z[l]), raw)));
+    emit(i - 1);
+  }
+}
+template <int T>
+__global__ __launch_bounds__(PO_THREADS) void fr_shq_replay_kernel(const uint32_t* __restrict__ a, uint64_t n, ShqArgs args, uint32_t B,
+                                                                   const uint32_t* __restrict__ incl, const uint32_t* __restrict__ carry,
+                                                                   uint32_t* __restrict__ out, int accumulate) {
+  shq_replay_body<T>(a, n, args, B, incl, carry, out, accumulate);
+}
+
+// ---- the same chain for a batch of independent proofs (hm_shplonk_set_quotient_batch_bn256_fr_dev): blockIdx.y = the proof ----
+// Proof b's combined polynomial N_b is row b of `a` (n x 8 words each), its points and coefficients entry b of a device table that was
+// uploaded with the call (wave-uniform: scalar loads), its scans' scratch the b-th block of `scan_stride` words (the single chain's
+// layout inside: incl, wg_total, carry), its output outs[b].  The bodies are the single chain's, so are the bounds.
+template <int T>
+__global__ __launch_bounds__(PO_THREADS) void fr_shq_chunks_batch_kernel(const uint32_t* __restrict__ a, uint64_t n,
+                                                                         const ShqArgs* __restrict__ table, uint32_t B,
+                                                                         uint32_t* __restrict__ scan, uint64_t scan_stride) {
+  __shared__ uint32_t lds[9 * PO_THREADS];
+  const size_t b = blockIdx.y;
+  uint32_t* incl = scan + b * scan_stride;
+  uint32_t* wg_total = incl + (size_t)T * ((size_t)gridDim.x * PO_THREADS + 1) * 9;
+  shq_chunks_body<T>(lds, a + b * n * 8, n, table[b], B, incl, wg_total);
+}
+template <int T>
+__global__ __launch_bounds__(PO_THREADS) void fr_shq_replay_batch_kernel(const uint32_t* __restrict__ a, uint64_t n,
+                                                                         const ShqArgs* __restrict__ table, uint32_t B,
+                                                                         const uint32_t* __restrict__ scan, uint64_t scan_stride,
+                                                                         uint32_t* const* __restrict__ outs, int accumulate) {
+  const size_t b = blockIdx.y;
+  const uint32_t* incl = scan + b * scan_stride;
+  const uint32_t* carry = incl + (size_t)T * ((size_t)gridDim.x * PO_THREADS + 1) * 9 + (size_t)T * gridDim.x * 9;
+  shq_replay_body<T>(a + b * n * 8, n, table[b], B, incl, carry, outs[b], accumulate);
+}
+// the joins: blockIdx.x = the point, blockIdx.y = the proof
+__global__ __launch_bounds__(PO_THREADS) void fr_shq_join_batch_kernel(uint32_t* __restrict__ scan, uint64_t scan_stride, uint32_t G, uint32_t t_points,
+                                                                       const ShqArgs* __restrict__ table, uint32_t B) {
+  __shared__ uint32_t lds[9 * PO_THREADS];
+  uint32_t* wg_total = scan + (size_t)blockIdx.y * scan_stride + (size_t)t_points * ((size_t)G * PO_THREADS + 1) * 9;
+  uint32_t* carry = wg_total + (size_t)t_points * G * 9;
+  po_kate_join_body(lds, wg_total + (size_t)blockIdx.x * G * 9, G, po_arg(table[blockIdx.y].z[blockIdx.x]), B, carry + (size_t)blockIdx.x * G * 9);
+}
 
 // ---------------------------------------------------------------------------------------------
 // a[i] *= pattern[i mod P]: EvaluationDomain::divide_by_vanishing_poly (the inverse vanishing polynomial takes only
@@ -878,256 +1011,8 @@ int fr_mul_periodic_run(uint32_t* d_a, uint64_t n, const uint64_t* pattern_ext, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Poseidon over Fr and the Merkle (sum) trees built from it: kernels and per-hash functions in poseidon.inc
+// keygen's sigma columns from the assembled cell ids (the assembly itself is keygen.hip)
 // ---------------------------------------------------------------------------------------------
-#include "poseidon.inc"
-
-// the constants were validated by the caller (capi_hash.hip: canonical, the shape of the spec)
-int poseidon_spec_create(DeviceCtx& ctx, uint32_t width, uint32_t rate, uint32_t r_f, uint32_t r_p, const uint64_t* rc_ext,
-                         const uint64_t* mds_ext, uint64_t* out_handle) {
-  const size_t n_rc = (size_t)(r_f + r_p) * width, n_mds = (size_t)width * width;
-  std::vector<uint32_t> h((n_rc + n_mds + 1) * 9);
-  for (size_t i = 0; i < n_rc + n_mds; ++i) {
-    const uint64_t* w = i < n_rc ? rc_ext + i * 4 : mds_ext + (i - n_rc) * 4;
-    host::fr_to_internal9(host::fr_load(w), &h[i * 9]);
-  }
-  // the capacity word of ConstantLength<L>, L = rate: the field element L * 2^64, as L additions of ONE and 64 doublings
-  // (a + b written as a - (0 - b): host_fr.h has no addition)
-  host::Fr4 cap = {{0, 0, 0, 0}};
-  const host::Fr4 zero = {{0, 0, 0, 0}};
-  for (uint32_t k = 0; k < rate; ++k) cap = host::fr_sub(cap, host::fr_sub(zero, host::FR_ONE));
-  for (int k = 0; k < 64; ++k) cap = host::fr_sub(cap, host::fr_sub(zero, cap));
-  host::fr_to_internal9(cap, &h[(n_rc + n_mds) * 9]);
-  auto s = std::make_unique<PoseidonSpec>();
-  s->width = width;
-  s->rate = rate;
-  s->r_f = r_f;
-  s->r_p = r_p;
-  HM_HIP_CHECK(hipMalloc((void**)&s->d_consts, h.size() * sizeof(uint32_t)));
-  if (hipError_t e = hipMemcpy(s->d_consts, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice); e != hipSuccess) {
-    poseidon_spec_release(*s);
-    return hm_fail(HM_ERR_HIP, std::string("hm_poseidon_create: ") + hipGetErrorString(e));
-  }
-  s->handle = ctx.next_handle++;
-  *out_handle = s->handle;
-  ctx.poseidon.push_back(std::move(s));
-  return HM_OK;
-}
-
-void poseidon_spec_release(PoseidonSpec& s) {
-  if (s.d_consts) (void)hipFree(s.d_consts);
-  s.d_consts = nullptr;
-}
-
-int poseidon_hash_run(const PoseidonSpec& s, const uint32_t* d_in, uint64_t in_stride, uint32_t* d_out, uint64_t out_stride, size_t n,
-                      hipStream_t stream) {
-  if (n == 0) return HM_OK;
-  const dim3 grid((unsigned)((n + PS_THREADS - 1) / PS_THREADS));
-  if (s.width == 3)
-    hipLaunchKernelGGL(poseidon_hash_kernel<3>, grid, dim3(PS_THREADS), 0, stream, d_in, in_stride, d_out, out_stride, (uint64_t)n,
-                       s.d_consts, s.r_f, s.r_p);
-  else
-    hipLaunchKernelGGL(poseidon_hash_kernel<5>, grid, dim3(PS_THREADS), 0, stream, d_in, in_stride, d_out, out_stride, (uint64_t)n,
-                       s.d_consts, s.r_f, s.r_p);
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
-}
-
-// One launch per level: level l reads only level l - 1, so the chain is depth launches in stream order.  The levels that no longer
-// fill the chip each take one hash latency whatever the launch shape (a node needs both children finished), so a single small kernel
-// for the top would save only the launch gaps.
-int merkle_build_run(const PoseidonSpec& s, uint32_t* d_nodes, uint32_t depth, hipStream_t stream) {
-  const uint32_t words = s.width == 5 ? 16 : 8;
-  uint64_t below = 0;                                   // first node of level l - 1
-  for (uint32_t l = 1; l <= depth; ++l) {
-    const uint64_t n = 1ull << (depth - l), start = below + 2 * n;
-    if (s.width == 5) {
-      hipLaunchKernelGGL(merkle_sum_level_kernel, dim3((unsigned)((n + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, stream,
-                         d_nodes + below * words, d_nodes + start * words, n, s.d_consts, s.r_f, s.r_p);
-      HM_HIP_CHECK(hipGetLastError());
-    } else if (int rc = poseidon_hash_run(s, d_nodes + below * words, 16, d_nodes + start * words, 8, n, stream)) {
-      return rc;
-    }
-    below = start;
-  }
-  return HM_OK;
-}
-
-int merkle_paths_run(const uint32_t* d_nodes, uint32_t depth, uint32_t words_per_node, const uint64_t* d_indices, size_t m,
-                     uint32_t* d_out, hipStream_t stream) {
-  const uint64_t lanes = (uint64_t)m * depth * words_per_node;
-  if (lanes == 0) return HM_OK;
-  hipLaunchKernelGGL(merkle_path_kernel, dim3((unsigned)((lanes + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, stream, d_nodes,
-                     depth, words_per_node, d_indices, (uint64_t)m, d_out);
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
-}
-
-int merkle_roots_run(const PoseidonSpec& s, uint32_t depth, size_t m, const uint32_t* d_leaves, const uint32_t* d_siblings,
-                     const uint64_t* d_indices, uint32_t* d_roots, hipStream_t stream) {
-  if (m == 0) return HM_OK;
-  hipLaunchKernelGGL(s.width == 5 ? merkle_roots_kernel<2> : merkle_roots_kernel<1>, dim3((unsigned)((m + PS_THREADS - 1) / PS_THREADS)),
-                     dim3(PS_THREADS), 0, stream, d_leaves, d_siblings, d_indices, depth, (uint64_t)m, s.d_consts, s.r_f, s.r_p, d_roots);
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
-}
-
-static int merkle_update_sort(uint64_t* d_keys, uint64_t n_pow2, hipStream_t stream) {
-  if (n_pow2 < 2) return HM_OK;
-  const uint32_t tiles = (uint32_t)((n_pow2 + MU_TILE - 1) / MU_TILE);
-  const uint64_t in_tile = n_pow2 < MU_TILE ? n_pow2 : (uint64_t)MU_TILE;
-  hipLaunchKernelGGL(merkle_update_sort_tile_kernel, dim3(tiles), dim3(PS_THREADS), 0, stream, d_keys, n_pow2, (uint64_t)2, in_tile);
-  for (uint64_t k = (uint64_t)MU_TILE * 2; k <= n_pow2; k <<= 1) {
-    for (uint64_t j = k / 2; j >= MU_TILE; j >>= 1)
-      hipLaunchKernelGGL(merkle_update_sort_global_kernel, dim3((uint32_t)((n_pow2 / 2 + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0,
-                         stream, d_keys, n_pow2, k, j);
-    hipLaunchKernelGGL(merkle_update_sort_tile_kernel, dim3(tiles), dim3(PS_THREADS), 0, stream, d_keys, n_pow2, k, k);
-  }
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
-}
-
-// The plan of poseidon.inc as launches: keys, sort, histogram, counts, scatter, then one launch per level over the owners of that
-// level.  Nothing comes back to the host: the grids are sized from min(m, 2^(depth - l)) and the lanes beyond the device-side count
-// return.  Scratch (the keys, the ordered indices, 3 x 32 counters) is stream-ordered, as the witness entry's `run` buffer is.
-static int merkle_update_launch(const PoseidonSpec& s, uint32_t* d_nodes, uint32_t depth, const uint64_t* d_indices,
-                                const uint32_t* d_new_leaves, size_t m, uint32_t* d_counts, uint8_t* ws, uint64_t n_pow2, size_t o_order,
-                                size_t o_small, hipStream_t stream) {
-  uint64_t* d_keys = (uint64_t*)ws;
-  uint32_t *d_order = (uint32_t*)(ws + o_order), *d_hist = (uint32_t*)(ws + o_small), *d_cursor = d_hist + MU_BINS, *d_cnt = d_cursor + MU_BINS;
-  const auto blocks = [](uint64_t lanes) { return dim3((unsigned)((lanes + PS_THREADS - 1) / PS_THREADS)); };
-  HM_HIP_CHECK(hipMemsetAsync(d_hist, 0, MU_BINS * sizeof(uint32_t), stream));
-  hipLaunchKernelGGL(merkle_update_keys_kernel, blocks(n_pow2), dim3(PS_THREADS), 0, stream, d_indices, (uint64_t)m, n_pow2, depth, d_keys);
-  if (int rc = merkle_update_sort(d_keys, n_pow2, stream)) return rc;
-  hipLaunchKernelGGL(merkle_update_hist_kernel, blocks(m), dim3(PS_THREADS), 0, stream, (const uint64_t*)d_keys, (uint64_t)m, depth, d_hist);
-  hipLaunchKernelGGL(merkle_update_plan_kernel, dim3(1), dim3(64), 0, stream, (const uint32_t*)d_hist, depth, d_cursor, d_cnt, d_counts);
-  hipLaunchKernelGGL(s.width == 5 ? merkle_update_scatter_kernel<2> : merkle_update_scatter_kernel<1>, blocks(m), dim3(PS_THREADS), 0, stream,
-                     (const uint64_t*)d_keys, (uint64_t)m, depth, d_cursor, d_order, d_new_leaves, d_nodes);
-  for (uint32_t l = 1; l <= depth; ++l) {
-    const uint64_t level = 1ull << (depth - l), lanes = m < level ? (uint64_t)m : level;
-    hipLaunchKernelGGL(s.width == 5 ? merkle_update_level_kernel<2> : merkle_update_level_kernel<1>, blocks(lanes), dim3(PS_THREADS), 0, stream,
-                       d_nodes, depth, l, (const uint32_t*)d_order, (const uint32_t*)d_cnt, s.d_consts, s.r_f, s.r_p);
-  }
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
-}
-
-int merkle_update_run(const PoseidonSpec& s, uint32_t* d_nodes, uint32_t depth, const uint64_t* d_indices, const uint32_t* d_new_leaves,
-                      size_t m, uint32_t* d_counts, hipStream_t stream) {
-  if (m == 0) {
-    if (d_counts) HM_HIP_CHECK(hipMemsetAsync(d_counts, 0, (depth + 1) * sizeof(uint32_t), stream));
-    return HM_OK;
-  }
-  uint64_t n_pow2 = 1;
-  while (n_pow2 < m) n_pow2 <<= 1;
-  const size_t o_order = (size_t)n_pow2 * 8, o_small = o_order + ((size_t)m * 4 + 15) / 16 * 16;
-  void* ws = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&ws, o_small + 3 * MU_BINS * sizeof(uint32_t), stream));
-  int rc = merkle_update_launch(s, d_nodes, depth, d_indices, d_new_leaves, m, d_counts, (uint8_t*)ws, n_pow2, o_order, o_small, stream);
-  const hipError_t fe = hipFreeAsync(ws, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("merkle_update: hipFreeAsync: ") + hipGetErrorString(fe));
-  return rc;
-}
-
-// out = rows_used, n_advice, perm_rows, level_rows, lt_row, const_row
-void witness_rows(uint32_t E, uint32_t depth, uint32_t r_f, uint32_t r_p, uint32_t (&out)[6]) {
-  const WitnessLayout w = witness_layout(E, depth, r_f, r_p);
-  out[0] = w.rows_used, out[1] = witness_advice(E), out[2] = w.perm_rows, out[3] = w.level_rows, out[4] = w.lt_row, out[5] = w.const_row;
-}
-
-static WitnessArgs witness_args(const PoseidonSpec& s, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* d_leaves,
-                                uint32_t* d_advice, uint32_t* d_instance) {
-  WitnessArgs a{};
-  a.leaves = d_leaves, a.advice = d_advice, a.instance = d_instance, a.consts = s.d_consts;
-  a.m = m, a.depth = depth, a.log_n = log_n, a.r_f = s.r_f, a.r_p = s.r_p;
-  return a;
-}
-
-// The columns are cleared, then every (user, level) lane writes its cells; without a tree a chain launch (one lane per user,
-// depth - 1 hashes in sequence) first leaves the path's running nodes in stream-ordered scratch.
-int merkle_witness_run(uint32_t E, const PoseidonSpec& s, uint32_t depth, uint32_t log_n, size_t m, const uint32_t* d_leaves,
-                       const uint32_t* d_siblings, const uint64_t* d_indices, const uint64_t* assets_ext, const uint32_t* d_nodes,
-                       uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream) {
-  if (m == 0) return HM_OK;
-  const std::string who = E == 2 ? "merkle_sum_witness: " : "merkle_witness: ";
-  WitnessArgs a = witness_args(s, depth, log_n, m, d_leaves, d_advice, d_instance);
-  a.siblings = d_siblings, a.indices = d_indices, a.nodes = d_nodes;
-  if (E == 2) std::memcpy(a.assets, assets_ext, 32);
-  HM_HIP_CHECK(hipMemsetAsync(d_advice, 0, (size_t)m * witness_advice(E) * ((size_t)32 << log_n), stream));
-  void* run = nullptr;
-  int rc = HM_OK;
-  if (!d_nodes && depth > 1) {
-    HM_HIP_CHECK(hipMallocAsync(&run, (size_t)m * (depth - 1) * E * 32, stream));
-    a.run = (const uint32_t*)run;
-    hipLaunchKernelGGL(E == 2 ? merkle_chain_kernel<2> : merkle_chain_kernel<1>, dim3((unsigned)((m + PS_THREADS - 1) / PS_THREADS)),
-                       dim3(PS_THREADS), 0, stream, a, (uint32_t*)run);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, who + hipGetErrorString(e));
-  }
-  if (rc == HM_OK) {
-    const uint64_t lanes = (uint64_t)m * depth;
-    hipLaunchKernelGGL(E == 2 ? merkle_witness_kernel<2> : merkle_witness_kernel<1>, dim3((unsigned)((lanes + PS_THREADS - 1) / PS_THREADS)),
-                       dim3(PS_THREADS), 0, stream, a);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, who + hipGetErrorString(e));
-  }
-  if (run) {
-    const hipError_t fe = hipFreeAsync(run, stream);
-    if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, who + "hipFreeAsync: " + hipGetErrorString(fe));
-  }
-  return rc;
-}
-
-int poseidon_witness_run(const PoseidonSpec& s, uint32_t log_n, size_t m, const uint32_t* d_msgs, uint32_t* d_advice, uint32_t* d_instance,
-                         hipStream_t stream) {
-  if (m == 0) return HM_OK;
-  const WitnessArgs a = witness_args(s, 0, log_n, m, d_msgs, d_advice, d_instance);
-  HM_HIP_CHECK(hipMemsetAsync(d_advice, 0, (size_t)m * witness_advice(0) * ((size_t)32 << log_n), stream));
-  hipLaunchKernelGGL(poseidon_witness_kernel, dim3((unsigned)((m + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, stream, a);
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// the range-check circuit's witness: the lane function, kernel and launch in range.inc
-// ---------------------------------------------------------------------------------------------
-#include "range.inc"
-
-// ---------------------------------------------------------------------------------------------
-// keygen's permutation assembly: the plan and its kernels in keygen.inc
-// ---------------------------------------------------------------------------------------------
-#include "keygen.inc"
-
-static int perm_assemble_launch(const uint32_t* d_copies, uint64_t m, uint64_t cells, uint32_t* d_sigma_cells, uint32_t* d_dropped,
-                                uint64_t* d_keys, uint64_t n_pow2, hipStream_t stream) {
-  const auto blocks = [](uint64_t lanes) { return dim3((unsigned)((lanes + PS_THREADS - 1) / PS_THREADS)); };
-  hipLaunchKernelGGL(perm_union_kernel, blocks(m), dim3(PS_THREADS), 0, stream, (const uint2*)d_copies, m, cells, d_sigma_cells);
-  hipLaunchKernelGGL(perm_keys_kernel, blocks(n_pow2), dim3(PS_THREADS), 0, stream, d_copies, m, n_pow2, cells,
-                     (const uint32_t*)d_sigma_cells, d_keys, d_dropped);
-  if (int rc = merkle_update_sort(d_keys, n_pow2, stream)) return rc;
-  hipLaunchKernelGGL(perm_link_kernel, blocks(2 * m), dim3(PS_THREADS), 0, stream, (const uint64_t*)d_keys, 2 * m, n_pow2, d_sigma_cells);
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
-}
-
-// A fixed chain of launches: identity, union, keys, the sort's stages, links.  Nothing comes back to the host; the keys are
-// stream-ordered scratch, as merkle_update_run's.
-int perm_assemble_run(const uint32_t* d_copies, size_t m, uint32_t columns, uint32_t k, uint32_t* d_sigma_cells, uint32_t* d_dropped,
-                      hipStream_t stream) {
-  const uint64_t cells = (uint64_t)columns << k;
-  if (d_dropped) HM_HIP_CHECK(hipMemsetAsync(d_dropped, 0, sizeof(uint32_t), stream));
-  hipLaunchKernelGGL(perm_identity_kernel, dim3((unsigned)((cells + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, stream,
-                     d_sigma_cells, cells);
-  HM_HIP_CHECK(hipGetLastError());
-  if (m == 0) return HM_OK;
-  uint64_t n_pow2 = 2;
-  while (n_pow2 < 2 * (uint64_t)m) n_pow2 <<= 1;
-  void* keys = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&keys, (size_t)n_pow2 * 8, stream));
-  int rc = perm_assemble_launch(d_copies, m, cells, d_sigma_cells, d_dropped, (uint64_t*)keys, n_pow2, stream);
-  const hipError_t fe = hipFreeAsync(keys, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("permutation_assemble: hipFreeAsync: ") + hipGetErrorString(fe));
-  return rc;
-}
-
 // out[c] = delta^j' * omega^i' for sigma_cells[c] = j' * n + i', both factors from tables of external words; an id >= cells (no
 // assembly writes one) gives zero, which no cell stands for
 __global__ __launch_bounds__(PO_THREADS) void perm_columns_kernel(const uint32_t* __restrict__ sigma_cells, uint64_t cells, uint32_t k,

@@ -1,8 +1,8 @@
 // poseidon.inc -- Poseidon over BN256 Fr (halo2_gadgets::poseidon::primitives, P128Pow5T3-style specs: x^5 S-box, R_F full and
 // R_P partial rounds) for ConstantLength<L> messages with L = RATE, and the Merkle (sum) trees the reference builds from it
-// (/root/reference/src/circuits/merkle_sum_tree.rs:118-150, src/chips/merkle_v3.rs).  Included by polyops.hip from inside
-// namespace hm, so that the kernels fall under polyops.o's ISA checks; host_check.cpp includes it too (without the kernels)
-// for the bound proof of the 64-round chain.  DESIGN.md section 12.
+// (/root/reference/src/circuits/merkle_sum_tree.rs:118-150, src/chips/merkle_v3.rs).  Included inside namespace hm by
+// poseidon.hip, which holds the kernels and the drivers, by range.hip for the word helpers, and by host_check.cpp for the bound
+// proof of the 64-round chain.  DESIGN.md section 12.
 //
 // One hash per lane, the WIDTH state words in registers.  The constants of a spec (hm_poseidon_create) live in device memory
 // in the internal form of ff29.h, canonical:
@@ -524,229 +524,3 @@ HM_HD void poseidon_witness_lane(const WitnessArgs& a, uint64_t u) {
   fe_to_ext_shift(w, s[0]);
   ps_put_words(a.instance + u * 8, w);
 }
-
-#if defined(__HIPCC__)
-constexpr int PS_THREADS = 256;
-
-__device__ __forceinline__ void ps_load_words(const uint32_t* __restrict__ p, uint32_t (&w)[8]) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 lo = q[0], hi = q[1];
-  w[0] = lo.x; w[1] = lo.y; w[2] = lo.z; w[3] = lo.w;
-  w[4] = hi.x; w[5] = hi.y; w[6] = hi.z; w[7] = hi.w;
-}
-__device__ __forceinline__ void ps_store_words(uint32_t* __restrict__ p, const uint32_t (&w)[8]) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(w[0], w[1], w[2], w[3]);
-  q[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-
-// message i = the W - 1 consecutive elements at in + i * in_stride (u32 words), digest i at out + i * out_stride: a flat
-// message array (strides 8 (W - 1), 8) and a level of the plain width-3 tree (strides 16, 8) are the same launch
-template <int W>
-__global__ __launch_bounds__(PS_THREADS) void poseidon_hash_kernel(const uint32_t* __restrict__ in, uint64_t in_stride,
-                                                                   uint32_t* __restrict__ out, uint64_t out_stride, uint64_t n,
-                                                                   const uint32_t* __restrict__ consts, uint32_t r_f, uint32_t r_p) {
-  const uint64_t i = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  if (i >= n) return;
-  uint32_t msg[W - 1][8], d[8];
-#pragma unroll
-  for (int j = 0; j < W - 1; ++j) ps_load_words(in + i * in_stride + j * 8, msg[j]);
-  poseidon_hash_one<W>(msg, consts, r_f, r_p, d);
-  ps_store_words(out + i * out_stride, d);
-}
-
-// node i of a level of the sum tree from nodes 2i, 2i + 1 of the level below (16 words per node: hash, balance)
-__global__ __launch_bounds__(PS_THREADS) void merkle_sum_level_kernel(const uint32_t* __restrict__ below, uint32_t* __restrict__ level,
-                                                                      uint64_t n, const uint32_t* __restrict__ consts, uint32_t r_f,
-                                                                      uint32_t r_p) {
-  const uint64_t i = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  if (i >= n) return;
-  uint32_t kids[4][8], hash[8], balance[8];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) ps_load_words(below + i * 32 + j * 8, kids[j]);
-  fr_add_ext(kids[1], kids[3], balance);                 // merkle_sum_node_one, the balance stored before the hash runs: it does
-  ps_store_words(level + i * 16 + 8, balance);           // not stay in registers across the permutation
-  poseidon_hash_one<5>(kids, consts, r_f, r_p, hash);
-  ps_store_words(level + i * 16, hash);
-}
-
-// sibling nodes of `m` leaves, bottom up: out[(p * depth + l) * words ..] = node ((index_p >> l) ^ 1) of level l, where level l
-// starts at node 2^(depth+1) - 2^(depth-l+1) of `nodes`.  One lane per (leaf, level, element).  An index >= 2^depth gives zeros.
-__global__ __launch_bounds__(PS_THREADS) void merkle_path_kernel(const uint32_t* __restrict__ nodes, uint32_t depth, uint32_t words_per_node,
-                                                                 const uint64_t* __restrict__ indices, uint64_t m,
-                                                                 uint32_t* __restrict__ out) {
-  const uint64_t t = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  const uint64_t per_path = (uint64_t)depth * words_per_node;
-  if (t >= m * per_path) return;
-  const uint64_t p = t / per_path, rest = t % per_path;
-  const uint32_t l = (uint32_t)(rest / words_per_node), e = (uint32_t)(rest % words_per_node);
-  const uint64_t idx = indices[p];
-  uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (idx < (1ull << depth)) {
-    const uint64_t level_start = (2ull << depth) - (2ull << (depth - l));
-    const uint64_t node = level_start + ((idx >> l) ^ 1ull);
-    ps_load_words(nodes + (node * words_per_node + e) * 8, w);
-  }
-  ps_store_words(out + t * 8, w);
-}
-// a path circuit: one lane per (user, level); the columns were cleared by the caller
-template <int E>
-__global__ __launch_bounds__(PS_THREADS) void merkle_witness_kernel(const WitnessArgs a) {
-  const uint64_t t = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  if (t >= a.m * a.depth) return;
-  merkle_witness_lane<E>(a, t / a.depth, (uint32_t)(t % a.depth));
-}
-
-// one lane per user: depth - 1 hashes in sequence (paths that come without a tree)
-template <int E>
-__global__ __launch_bounds__(PS_THREADS) void merkle_chain_kernel(const WitnessArgs a, uint32_t* __restrict__ run) {
-  const uint64_t u = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  if (u >= a.m) return;
-  merkle_chain_lane<E>(a, u, run);
-}
-
-// the Poseidon circuit: one lane per hash
-__global__ __launch_bounds__(PS_THREADS) void poseidon_witness_kernel(const WitnessArgs a) {
-  const uint64_t u = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  if (u >= a.m) return;
-  poseidon_witness_lane(a, u);
-}
-
-// one lane per path: depth hashes in sequence
-template <int E>
-__global__ __launch_bounds__(PS_THREADS) void merkle_roots_kernel(const uint32_t* __restrict__ leaves, const uint32_t* __restrict__ siblings,
-                                                                  const uint64_t* __restrict__ indices, uint32_t depth, uint64_t m,
-                                                                  const uint32_t* __restrict__ consts, uint32_t r_f, uint32_t r_p,
-                                                                  uint32_t* __restrict__ roots) {
-  const uint64_t u = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  if (u >= m) return;
-  merkle_root_lane<E>(leaves, siblings, indices, depth, consts, r_f, r_p, u, roots);
-}
-
-// ---- the update's launches (the plan above) ---------------------------------------------------------------------------------------
-// The sort is a bitonic network on the n_pow2 keys (m << 2^depth: it is not where the time goes): every stage with partner distance
-// below MU_TILE runs on a tile in LDS, the others are one launch each.
-constexpr uint32_t MU_TILE = 2048;               // keys per LDS tile: 16 KiB
-
-__global__ __launch_bounds__(PS_THREADS) void merkle_update_keys_kernel(const uint64_t* __restrict__ indices, uint64_t m, uint64_t n_pow2,
-                                                                        uint32_t depth, uint64_t* __restrict__ keys) {
-  const uint64_t t = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  if (t >= n_pow2) return;
-  keys[t] = t < m ? merkle_update_key(indices[t], (uint32_t)t, depth) : ~0ull;
-}
-
-// one compare-exchange stage with partner distance j >= MU_TILE of the phase of length k; one lane per pair
-__global__ __launch_bounds__(PS_THREADS) void merkle_update_sort_global_kernel(uint64_t* __restrict__ keys, uint64_t n, uint64_t k, uint64_t j) {
-  const uint64_t t = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  if (t >= n / 2) return;
-  const uint64_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-  const uint64_t a = keys[i], b = keys[l];
-  if (((i & k) == 0) ? a > b : a < b) {
-    keys[i] = b;
-    keys[l] = a;
-  }
-}
-
-// every stage with partner distance < MU_TILE of the phases k_first .. k_last (k_first = 2: the whole sort of a tile)
-__global__ __launch_bounds__(PS_THREADS) void merkle_update_sort_tile_kernel(uint64_t* __restrict__ keys, uint64_t n, uint64_t k_first,
-                                                                             uint64_t k_last) {
-  __shared__ uint64_t lds[MU_TILE];
-  const uint64_t base = (uint64_t)blockIdx.x * MU_TILE;
-  const uint32_t tile = n < MU_TILE ? (uint32_t)n : MU_TILE;
-  for (uint32_t e = threadIdx.x; e < tile; e += PS_THREADS) lds[e] = keys[base + e];
-  __syncthreads();
-  for (uint64_t k = k_first; k <= k_last; k <<= 1) {
-    for (uint32_t j = (uint32_t)(k / 2 < tile ? k / 2 : tile / 2); j > 0; j >>= 1) {
-      for (uint32_t t = threadIdx.x; t < tile / 2; t += PS_THREADS) {
-        const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-        const uint64_t a = lds[i], b = lds[l];
-        if ((((base + i) & k) == 0) ? a > b : a < b) {
-          lds[i] = b;
-          lds[l] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  for (uint32_t e = threadIdx.x; e < tile; e += PS_THREADS) keys[base + e] = lds[e];
-}
-
-// `owned` of the sorted entry p (positions >= m hold padding only)
-__device__ __forceinline__ uint32_t merkle_update_owned_at(const uint64_t* __restrict__ keys, uint64_t p, uint64_t m, uint32_t depth,
-                                                           uint64_t& key) {
-  if (p >= m) return 0;
-  key = keys[p];
-  return merkle_update_owned(p ? keys[p - 1] : 0, key, p == 0, depth);
-}
-
-// hist[d] = the entries with owned = d (a workgroup counts in LDS first)
-__global__ __launch_bounds__(PS_THREADS) void merkle_update_hist_kernel(const uint64_t* __restrict__ keys, uint64_t m, uint32_t depth,
-                                                                        uint32_t* __restrict__ hist) {
-  __shared__ uint32_t cnt[MU_BINS];
-  if (threadIdx.x < MU_BINS) cnt[threadIdx.x] = 0;
-  __syncthreads();
-  uint64_t key = 0;
-  const uint32_t d = merkle_update_owned_at(keys, (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x, m, depth, key);
-  if (d) atomicAdd(&cnt[d], 1u);
-  __syncthreads();
-  if (threadIdx.x < MU_BINS && cnt[threadIdx.x]) atomicAdd(&hist[threadIdx.x], cnt[threadIdx.x]);
-}
-
-// the counts, which are the bins' first cursors as well (bin d starts where the entries that own more levels end), and the caller's copy
-__global__ __launch_bounds__(64) void merkle_update_plan_kernel(const uint32_t* __restrict__ hist, uint32_t depth, uint32_t* __restrict__ cursor,
-                                                                uint32_t* __restrict__ counts, uint32_t* __restrict__ counts_out) {
-  const uint32_t d = threadIdx.x;
-  if (d >= MU_BINS) return;
-  const uint32_t c = merkle_update_count(hist, d);
-  cursor[d] = c;
-  counts[d] = c;
-  if (counts_out && d <= depth) counts_out[d] = c;
-}
-
-// the live entries into their bins (order[] = their leaf indices) and their leaves into level 0
-template <int E>
-__global__ __launch_bounds__(PS_THREADS) void merkle_update_scatter_kernel(const uint64_t* __restrict__ keys, uint64_t m, uint32_t depth,
-                                                                           uint32_t* __restrict__ cursor, uint32_t* __restrict__ order,
-                                                                           const uint32_t* __restrict__ new_leaves,
-                                                                           uint32_t* __restrict__ nodes) {
-  __shared__ uint32_t cnt[MU_BINS], base[MU_BINS];
-  if (threadIdx.x < MU_BINS) cnt[threadIdx.x] = 0;
-  __syncthreads();
-  uint64_t key = 0;
-  const uint32_t d = merkle_update_owned_at(keys, (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x, m, depth, key);
-  const uint32_t rank = d ? atomicAdd(&cnt[d], 1u) : 0u;
-  __syncthreads();
-  if (threadIdx.x < MU_BINS && cnt[threadIdx.x]) base[threadIdx.x] = atomicAdd(&cursor[threadIdx.x], cnt[threadIdx.x]);
-  __syncthreads();
-  if (!d) return;
-  const uint32_t idx = (uint32_t)(key >> 32), pos = ~(uint32_t)key;
-  order[base[d] + rank] = idx;
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    uint32_t w[8];
-    ps_load_words(new_leaves + ((uint64_t)pos * E + e) * 8, w);
-    ps_store_words(nodes + ((uint64_t)idx * E + e) * 8, w);
-  }
-}
-
-// level l: lane t < counts[l] hashes node (order[t] >> l) from its two children one level down
-template <int E>
-__global__ __launch_bounds__(PS_THREADS) void merkle_update_level_kernel(uint32_t* __restrict__ nodes, uint32_t depth, uint32_t l,
-                                                                         const uint32_t* __restrict__ order,
-                                                                         const uint32_t* __restrict__ counts,
-                                                                         const uint32_t* __restrict__ consts, uint32_t r_f, uint32_t r_p) {
-  const uint64_t t = (uint64_t)blockIdx.x * PS_THREADS + threadIdx.x;
-  if (t >= counts[l]) return;
-  const uint64_t node = order[t] >> l;
-  const uint64_t below = (2ull << depth) - (2ull << (depth - (l - 1))) + 2 * node, at = (2ull << depth) - (2ull << (depth - l)) + node;
-  uint32_t kids[2 * E][8], out[E][8];
-#pragma unroll
-  for (int j = 0; j < 2 * E; ++j) ps_load_words(nodes + below * E * 8 + j * 8, kids[j]);
-  if constexpr (E == 2)
-    merkle_sum_node_one(kids, consts, r_f, r_p, out[0], out[1]);
-  else
-    poseidon_hash_one<3>(kids, consts, r_f, r_p, out[0]);
-#pragma unroll
-  for (int e = 0; e < E; ++e) ps_store_words(nodes + (at * E + e) * 8, out[e]);
-}
-#endif

@@ -19,8 +19,8 @@
 //              pairs over the proof's slots; a point slot absorbs prefix 1, x (the proof's bytes without the sign bit) and the y bytes
 //              the read kernel left, a scalar slot prefix 2 and its bytes.  Every record goes through ONE b2_push site and every
 //              squeeze through ONE b2_final site: the compression is inlined twice per kernel, not once per kind of record.
-// Included by lookup.hip inside namespace hm (capi_verify.hip takes the schedule's check from it); the lane functions are
-// host-callable: host_check.cpp includes this file (without the kernels) and runs them with the bound tracking on.
+// Included inside namespace hm by verify.hip, which holds the two kernels and their drivers, and by capi_verify.hip for the schedule's
+// check; the lane functions are host-callable: host_check.cpp includes this file and runs them with the bound tracking on.
 
 constexpr uint32_t TR_THREADS = 64;                              // one wave per block: 8 or 12 KiB of LDS, no barrier anywhere
 constexpr uint32_t TR_SCALAR = 2, TR_POINT = 1, TR_CHALLENGE = 0;   // the prefix bytes (transcript.py)
@@ -267,64 +267,3 @@ inline const char* tr_schedule_problem(const uint32_t* sched, size_t n_pairs, ui
   if (squeezed > record_elems) return "transcript: the schedule squeezes more challenges than a record holds";
   return nullptr;
 }
-
-#if defined(__HIPCC__) && defined(HM_TRANSCRIPT_KERNELS)   // lookup.hip alone holds the kernels
-__global__ __launch_bounds__(TR_THREADS) void blake2b_kernel(const uint8_t* __restrict__ msgs, uint64_t stride, const uint32_t* __restrict__ lens,
-                                                             uint64_t n, uint64_t personal_lo, uint64_t personal_hi, uint32_t* __restrict__ out) {
-  __shared__ uint32_t block[B2_BLOCK_WORDS][TR_THREADS];
-  const uint64_t i = (uint64_t)blockIdx.x * TR_THREADS + threadIdx.x;
-  if (i >= n) return;
-  uint32_t* digest = out + i * 16;
-  const uint32_t len = lens[i];
-  if (len > stride) {                                            // a length that leaves the message's room: zeros, nothing read
-#pragma unroll
-    for (int k = 0; k < 16; ++k) digest[k] = 0;
-    return;
-  }
-  b2_hash_lane(B2Buf{&block[0][threadIdx.x], TR_THREADS}, msgs + i * stride, len, personal_lo, personal_hi, digest);
-}
-
-__global__ __launch_bounds__(TR_THREADS) void verify_transcript_kernel(const uint32_t* __restrict__ proofs, uint32_t n_proofs,
-                                                                       const uint32_t* __restrict__ slot_table, uint32_t slots,
-                                                                       uint32_t n_points, const uint32_t* __restrict__ ybytes,
-                                                                       const uint32_t* __restrict__ preamble,
-                                                                       const uint32_t* __restrict__ counts, uint32_t stride,
-                                                                       const uint32_t* __restrict__ sched, uint32_t n_pairs,
-                                                                       uint32_t* __restrict__ bad, uint32_t* __restrict__ records,
-                                                                       uint32_t record_elems) {
-  __shared__ uint32_t block[B2_BLOCK_WORDS + TR_STAGE_WORDS][TR_THREADS];
-  const uint32_t b = blockIdx.x * TR_THREADS + threadIdx.x;
-  if (b >= n_proofs) return;
-  tr_proof_one(B2Buf{&block[0][threadIdx.x], TR_THREADS}, b, proofs, slot_table, slots, n_points, ybytes, preamble, counts, stride, sched,
-               n_pairs, bad, records, record_elems);
-}
-
-// the arguments were checked by the caller (capi_verify.hip)
-int blake2b_run(const uint8_t* d_msgs, size_t stride, const uint32_t* d_lens, size_t n, const uint8_t* personal16, uint32_t* d_out,
-                hipStream_t stream) {
-  uint64_t personal[2] = {0, 0};
-  if (personal16) std::memcpy(personal, personal16, 16);
-  hipLaunchKernelGGL(blake2b_kernel, dim3((uint32_t)((n + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, stream, d_msgs, (uint64_t)stride,
-                     d_lens, (uint64_t)n, personal[0], personal[1], d_out);
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
-}
-
-int verify_transcript_run(DeviceCtx& ctx, const uint32_t* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots,
-                          uint32_t n_points, const uint32_t* d_ybytes, const uint32_t* d_preamble, const uint32_t* d_counts, uint32_t stride,
-                          const uint32_t* schedule, size_t n_pairs, uint32_t* d_bad, uint32_t* d_records, uint32_t record_elems,
-                          hipStream_t stream) {
-  if (const char* why = tr_schedule_problem(schedule, n_pairs, slots, record_elems)) return hm_fail(HM_ERR_BAD_ARG, why);
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  uint32_t* d_sched = (uint32_t*)slot->args.ensure(n_pairs * 8);
-  if (!d_sched) return hm_fail(HM_ERR_HIP, "verify transcript: schedule allocation failed");
-  // pageable source: the runtime has taken its copy of the schedule when this returns (as the terms plan)
-  HM_HIP_CHECK(hipMemcpyAsync(d_sched, schedule, n_pairs * 8, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(verify_transcript_kernel, dim3((uint32_t)((n_proofs + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, stream, d_proofs,
-                     (uint32_t)n_proofs, d_slot_table, slots, n_points, d_ybytes, d_preamble, d_counts, stride, (const uint32_t*)d_sched,
-                     (uint32_t)n_pairs, d_bad, d_records, record_elems);
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
-}
-#endif

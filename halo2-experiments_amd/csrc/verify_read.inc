@@ -11,8 +11,8 @@
 //   colsum   out[c] = sum of rows [lo, hi) of column c of a (rows, cols) array of Montgomery Fr words: the proofs' contributions to the
 //            points they share (fixed and sigma commitments, the generator).  Montgomery words add as integers mod r, so the sum needs
 //            no product: a workgroup per column, one lazy sum per lane, a tree in LDS.
-// Included by msm.hip inside namespace hm, behind g1_codec.inc.  The per-slot functions are host-callable: host_check.cpp includes this
-// file (without the kernels) for the bound proof.
+// The per-slot functions of the two kernels, which verify.hip holds with their drivers.  Included inside namespace hm, behind
+// g1_codec.inc; the functions are host-callable: host_check.cpp includes this file for the bound proof.
 
 constexpr uint32_t VR_POINT = 1u << 31, VR_TAIL = 1u << 30, VR_INDEX = VR_TAIL - 1u;
 
@@ -56,84 +56,3 @@ HM_HD bool proof_point_one(const uint32_t (&in)[8], uint32_t (&ox)[8], uint32_t 
 HM_HD Fr colsum_step(const Fr& acc, const uint32_t (&w)[8]) { return fe_reduce_small(fe_norm(fe_add(acc, fe_unpack<FrParams>(w)))); }
 HM_HD Fr colsum_join(const Fr& a, const Fr& b) { return fe_reduce_small(fe_norm(fe_add(a, b))); }
 HM_HD void colsum_finish(const Fr& acc, uint32_t (&w)[8]) { fe_pack(w, fe_canonical(acc)); }
-
-#if defined(__HIPCC__)
-__device__ __forceinline__ void vr_load8(const uint32_t* __restrict__ p, uint32_t (&w)[8]) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 a = q[0], b = q[1];
-  w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w, w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w;
-}
-__device__ __forceinline__ void vr_store8(uint32_t* __restrict__ p, const uint32_t (&w)[8]) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(w[0], w[1], w[2], w[3]);
-  q[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-
-__global__ __launch_bounds__(ACC_THREADS) void verify_read_kernel(const uint32_t* __restrict__ proofs, const uint32_t* __restrict__ slot_table,
-                                                                  uint32_t slots, uint64_t lanes, uint32_t own_points, uint32_t n_points,
-                                                                  uint32_t n_scalars, uint32_t* __restrict__ points, uint32_t* __restrict__ tail,
-                                                                  uint32_t* __restrict__ ybytes, uint32_t* __restrict__ scalars,
-                                                                  uint32_t* __restrict__ bad) {
-  const uint64_t i = (uint64_t)blockIdx.x * ACC_THREADS + threadIdx.x;
-  if (i >= lanes) return;
-  const uint64_t b = i / slots;
-  const uint32_t entry = slot_table[i % slots], index = entry & VR_INDEX;
-  uint32_t w[8];
-  vr_load8(proofs + i * 8, w);
-  bool ok;
-  if (entry & VR_POINT) {
-    const bool in_tail = (entry & VR_TAIL) != 0;
-    ok = index < n_points && (in_tail || index < own_points);
-    if (ok) {
-      uint32_t ox[8], oy[8], ycan[8];
-      ok = proof_point_one(w, ox, oy, ycan);
-      uint32_t* dst = in_tail ? tail + b * 16 : points + (b * own_points + index) * 16;
-      vr_store8(dst, ox);
-      vr_store8(dst + 8, oy);
-      vr_store8(ybytes + (b * n_points + index) * 8, ycan);
-    }
-  } else {
-    ok = index < n_scalars;
-    if (ok) {
-      uint32_t out[8];
-      ok = proof_scalar_one(w, out);
-      vr_store8(scalars + (b * n_scalars + index) * 8, out);
-    }
-  }
-  if (!ok) atomicOr(bad + b, 1u);
-}
-
-constexpr int COLSUM_THREADS = 256;
-
-__global__ __launch_bounds__(COLSUM_THREADS) void verify_colsum_kernel(const uint32_t* __restrict__ rows, uint32_t cols, uint64_t lo, uint64_t hi,
-                                                                       uint32_t* __restrict__ out) {
-  __shared__ uint32_t sh[9][COLSUM_THREADS];
-  const uint32_t c = blockIdx.x, t = threadIdx.x;
-  Fr acc = fe_zero<FrParams>();
-  for (uint64_t r = lo + t; r < hi; r += COLSUM_THREADS) {
-    uint32_t w[8];
-    vr_load8(rows + (r * cols + c) * 8, w);
-    acc = colsum_step(acc, w);
-  }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) sh[k][t] = acc.l[k];
-  __syncthreads();
-  for (uint32_t s = COLSUM_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      Fr o;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) o.l[k] = sh[k][t + s];
-      HM_DECLARE(o, 3.0);
-      acc = colsum_join(acc, o);
-#pragma unroll
-      for (int k = 0; k < 9; ++k) sh[k][t] = acc.l[k];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    uint32_t w[8];
-    colsum_finish(acc, w);
-    vr_store8(out + (size_t)c * 8, w);
-  }
-}
-#endif

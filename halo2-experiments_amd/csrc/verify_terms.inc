@@ -26,7 +26,7 @@
 //             proof's own points (the h commitment expanded into its pieces with the powers of x^n), its row of the shared points'
 //             array, and r_b u, r_b for [h'].
 // The two phases are host-callable: host_check.cpp runs them under bound tracking (hc_verify_terms) with the numerator given.
-// Included by lookup.hip inside namespace hm, behind mock.inc.
+// Included inside namespace hm by verify.hip, which holds the kernel and its driver, and by capi_verify.hip for the plan's check.
 
 enum : uint32_t {
   VT_K, VT_N_SCALARS, VT_N_VALS, VT_N_LAGRANGE, VT_N_INSTQ, VT_N_SUPER, VT_N_SETS, VT_PIECES, VT_N_OWN, VT_N_SHARED, VT_N_ROT, VT_N_COLS,
@@ -266,84 +266,3 @@ HM_HD bool vt_phase_b(const uint32_t* plan, const VtMem& m, const Fr& num, uint3
   vt_to_ext(h2l, rb);
   return ok;
 }
-
-#if defined(__HIPCC__) && defined(HM_VERIFY_TERMS_KERNELS)   // lookup.hip alone holds the kernel
-struct VerifySource {
-  const uint32_t* __restrict__ plan;
-  VtMem m;
-  uint32_t static_consts;
-  __device__ __forceinline__ uint32_t n_static() const { return static_consts; }
-  // the program's per-call constants are beta, gamma, theta, y, in that order (evaluation.GraphEvaluator.lower)
-  __device__ __forceinline__ uint32_t dyn(uint32_t word) const {
-    const uint32_t j = word / 9, limb = word - 9 * j;
-    const uint32_t rec = j == 0 ? VT_BETA : j == 1 ? VT_GAMMA : j == 2 ? VT_THETA : VT_Y;
-    return m.ws[((size_t)(plan[VT_N_VALS] + rec) * 9 + limb) * m.T + m.lane];
-  }
-  __device__ __forceinline__ Fr column(uint32_t src) const {
-    const uint32_t col = gsrc_column(src), rot = gsrc_rot(src);
-    uint32_t slot = VT_NO_SLOT;
-    if (col < plan[VT_N_COLS] && rot < plan[VT_N_ROT]) slot = plan[plan[VT_OFF_COLMAP] + col * plan[VT_N_ROT] + rot];
-    if (slot >= plan[VT_N_VALS]) return fe_zero<FrParams>();
-    return vt_load(m, slot);
-  }
-  __device__ __forceinline__ Fr previous() const { return fe_zero<FrParams>(); }
-};
-
-__global__ __launch_bounds__(GE_THREADS) void verify_terms_kernel(const uint32_t* __restrict__ plan, const uint32_t* __restrict__ consts,
-                                                                  const GraphCalc* __restrict__ calcs, uint32_t n_calc, uint32_t result_src,
-                                                                  uint32_t result_prev, uint32_t n_static, uint32_t* __restrict__ ws,
-                                                                  uint32_t n_proofs, const uint32_t* __restrict__ records,
-                                                                  const uint32_t* __restrict__ evals, const uint32_t* __restrict__ inst,
-                                                                  uint32_t* __restrict__ bad, uint32_t* __restrict__ own,
-                                                                  uint32_t* __restrict__ shared, uint32_t* __restrict__ h2r,
-                                                                  uint32_t* __restrict__ h2l) {
-  const uint32_t T = gridDim.x * GE_THREADS, lane = blockIdx.x * GE_THREADS + threadIdx.x;
-  if (lane >= n_proofs) return;
-  const size_t b = lane;
-  uint32_t* my_own = own + b * plan[VT_N_OWN] * 8;
-  uint32_t* my_shared = shared + b * plan[VT_N_SHARED] * 8;
-  vt_zero_rows(my_own, plan[VT_N_OWN]);
-  vt_zero_rows(my_shared, plan[VT_N_SHARED]);
-  vt_zero_rows(h2r + b * 8, 1);
-  vt_zero_rows(h2l + b * 8, 1);
-  if (bad[b]) return;
-  const VtMem m{ws, T, lane};
-  bool ok = vt_phase_a(plan, m, records + b * VT_REC * 8, evals + b * plan[VT_N_SCALARS] * 8, inst + b * plan[VT_INST_ELEMS] * 8);
-  const VerifySource from{plan, m, n_static};
-  const Fr num = ge_reduce(ge_run(from, consts, calcs, n_calc, result_src, result_prev, ws + (size_t)vt_ws_program(plan) * 9 * T, T, lane));
-  ok = vt_phase_b(plan, m, num, my_own, my_shared, h2r + b * 8, h2l + b * 8) && ok;
-  if (!ok) {
-    bad[b] = 1;
-    vt_zero_rows(my_own, plan[VT_N_OWN]);
-    vt_zero_rows(my_shared, plan[VT_N_SHARED]);
-    vt_zero_rows(h2r + b * 8, 1);
-    vt_zero_rows(h2l + b * 8, 1);
-  }
-}
-
-// the arguments were checked by the caller (capi_verify.hip) -- but for the plan, which is checked here, before anything is launched
-int verify_terms_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
-                     const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst, uint32_t* d_bad, uint32_t* d_own,
-                     uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream) {
-  GraphVariant& v = g.variant[0];
-  if (!v.ready) return hm_fail(HM_ERR_INTERNAL, "verify terms: the program has no lowered form");
-  if (n_columns != g.n_columns) return hm_fail(HM_ERR_BAD_ARG, "verify terms: the program was built for another number of columns");
-  if (n_dynamic != g.n_dynamic || n_dynamic != 4)
-    return hm_fail(HM_ERR_BAD_ARG, "verify terms: the program must take beta, gamma, theta, y as its per-call constants");
-  if (const char* why = vt_plan_problem(plan, n_words, n_columns)) return hm_fail(HM_ERR_BAD_ARG, why);
-  const uint32_t blocks = (uint32_t)((n_proofs + GE_THREADS - 1) / GE_THREADS), T = blocks * GE_THREADS;
-  const size_t slots = (size_t)vt_ws_program(plan) + v.n_slots;
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  uint32_t* ws = (uint32_t*)slot->scratch.ensure(slots * 9 * T * 4);
-  uint32_t* d_plan = (uint32_t*)slot->args.ensure(n_words * 4);
-  if (!ws || !d_plan) return hm_fail(HM_ERR_HIP, "verify terms: workspace allocation failed");
-  // pageable source: the runtime has taken its copy of the plan when this returns (as the witness checker's table)
-  HM_HIP_CHECK(hipMemcpyAsync(d_plan, plan, n_words * 4, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(verify_terms_kernel, dim3(blocks), dim3(GE_THREADS), 0, stream, (const uint32_t*)d_plan, (const uint32_t*)g.d_consts,
-                     (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src, v.result_prev, g.n_static, ws, (uint32_t)n_proofs, d_records, d_evals,
-                     d_inst, d_bad, d_own, d_shared, d_h2r, d_h2l);
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
-}
-#endif

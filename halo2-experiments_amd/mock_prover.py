@@ -1,4 +1,4 @@
-"""``MockProver`` of ``halo2_proofs::dev`` for a BATCH of witnesses on the GPU (csrc/mock.inc): does every
+"""``MockProver`` of ``halo2_proofs::dev`` for a BATCH of witnesses on the GPU (csrc/mock.hip): does every
 user's witness satisfy the constraint system -- every gate polynomial on every usable row, both cells of every copy constraint,
 every lookup input in its table -- and if not, which gate, row, copy or lookup of which user fails.
 

@@ -2,7 +2,7 @@
 
 The direct KZG form of a proof of solvency: commit to the balance column with one MSM; user i's proof is the opening of that
 commitment at omega^i; the total is n f(0), one more opening.  One opening is a ``kate_division`` and an MSM (``open_at``); all n of
-them at once cost one Fr NTT of size 2n, 2n scalar multiplications and two FFTs over G1 (``open_all``; csrc/kzg_open.inc, DESIGN.md
+them at once cost one Fr NTT of size 2n, 2n scalar multiplications and two FFTs over G1 (``open_all``; csrc/g1_fft.hip, DESIGN.md
 section 22):
 
     f = sum_{j<n} f_j X^j, g_i = [s^i]G1:   pi_t = [(f(s) - f(w^t)) / (s - w^t)]G1 = sum_m w^(tm) h_m,   w = omega_n,

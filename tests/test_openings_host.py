@@ -1,4 +1,4 @@
-"""CPU checks of the KZG openings (halo2_experiments_amd/openings.py, csrc/kzg_open.inc): the integer twin's two routes against
+"""CPU checks of the KZG openings (halo2_experiments_amd/openings.py, csrc/g1_fft.hip): the integer twin's two routes against
 the closed form for a known s, the argument checks of the entry points before any device is needed, and verify_opening on proofs
 made with integers."""
 import ctypes

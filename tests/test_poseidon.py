@@ -275,12 +275,12 @@ def test_trees_refuse_leaf_counts_that_are_not_powers_of_two():
 
 # ---- what the compiler made of the kernels --------------------------------------------------------------------------------------
 
-def test_the_poseidon_kernels_are_in_polyops_without_scratch():
+def test_the_poseidon_kernels_are_in_poseidon_o_without_scratch():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import isa_check
-    if not os.path.exists(os.path.join(isa_check.CSRC, "polyops.o")):
+    if not os.path.exists(os.path.join(isa_check.CSRC, "poseidon.o")):
         _lib.build()
-    rows = isa_check.summary("polyops.o")
+    rows = isa_check.summary("poseidon.o")
     for kernel in ("poseidon_hash_kernelILi3", "poseidon_hash_kernelILi5", "merkle_sum_level_kernel", "merkle_path_kernel"):
         hits = [r for name, r in rows.items() if kernel in name]
         assert len(hits) == 1, kernel

@@ -1,4 +1,4 @@
-"""``verify_terms_kernel`` (csrc/verify_terms.inc) on the GPU against its integer twin, on records no transcript produces
+"""``verify_terms_kernel`` (csrc/verify.hip over verify_terms.inc) on the GPU against its integer twin, on records no transcript produces
 (tests/verify_terms_cases.py): the program is made with ``evaluation.CompiledGraph(**plan.lowered)`` and ``hm_verify_terms_dev`` is
 called directly, as ``BatchVerifier._prepare`` calls it -- no SRS, key or proof.
 

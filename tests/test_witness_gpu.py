@@ -1,4 +1,4 @@
-"""The MerkleSumTree witness on the GPU (csrc/poseidon.inc: merkle_witness_kernel<2> / merkle_chain_kernel<2>) against
+"""The MerkleSumTree witness on the GPU (csrc/poseidon.hip: merkle_witness_kernel<2> / merkle_chain_kernel<2>) against
 synthesis.assign_ints word for word, against the tests' MockProver, and against the gate polynomials of
 circuits.merkle_sum_tree(spec) run by the device GraphEvaluator over every user's columns."""
 import ctypes

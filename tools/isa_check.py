@@ -13,7 +13,12 @@
     python tools/isa_check.py ntt.o --dump     # the offending instructions with context
     python tools/isa_check.py --k3 [msm.o ...] # the bucket accumulation kernel: VGPRs, scratch, and the instruction mix of its loops
                                                # (wide mads, 64-bit adds, 64-bit shifts, compiler nops); the first is the hot one
+    python tools/isa_check.py --digest         # per kernel: object, SHA-256 of its instructions, mangled name -- what has to stay equal
+                                               # when kernels only move between translation units (sort, drop column 1, diff)
+
+The objects are the ones csrc/Makefile names (its print-objs / print-api-objs targets): no list of translation units is kept here.
 """
+import hashlib
 import os
 import re
 import subprocess
@@ -24,7 +29,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "halo2-experiments_amd", "csrc")
 LLVM = "/opt/rocm/lib/llvm/bin"
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
-OBJECTS = ["capi.o", "capi_msm.o", "capi_poly.o", "capi_g1.o", "capi_hash.o", "digest.o", "multi.o", "xfer.o", "ntt.o", "poly.o", "polyops.o", "lookup.o", "graph.o", "msm.o", "msm_small.o"]
+
+
+def _makefile_list(target: str):
+    return subprocess.run(["make", "-s", "--no-print-directory", "-C", CSRC, target], check=True, capture_output=True, text=True).stdout.split()
+
+
+OBJECTS = _makefile_list("print-objs")             # every translation unit of the library
+API_OBJECTS = _makefile_list("print-api-objs")     # ... of which these are host only
 
 _VMEM = re.compile(r"^\s*(global_|flat_|buffer_|scratch_)(load|store|atomic)\w*\s+(.*)$")
 _SLOAD = re.compile(r"^\s*s_load_dword(?:x\d+)?\s+\S+,\s*(s\[\d+:\d+\])")
@@ -103,6 +115,24 @@ def summary(obj: str):
     return rows
 
 
+def digest(insts) -> str:
+    """SHA-256 of a kernel's instruction text without the two things that depend on where the kernel lies in its object: the literal
+    of the s_add_u32 / s_addc_u32 pair behind an s_getpc_b64 (the pc-relative distance to the object's constants) and the s_nop 0
+    padding behind the last instruction."""
+    body, pcrel = [], 0
+    for ins in insts:
+        if ins.startswith("s_getpc_b64"):
+            pcrel = 2
+        elif pcrel and re.match(r"s_addc?_u32\s", ins):
+            ins, pcrel = ins.rsplit(",", 1)[0] + ", <pcrel>", pcrel - 1
+        else:
+            pcrel = 0
+        body.append(ins)
+    while body and body[-1] in ("s_nop 0", "..."):     # "...": objdump's mark for the zero fill behind an object's last kernel
+        body.pop()
+    return hashlib.sha256("\n".join(body).encode()).hexdigest()
+
+
 def _code_object(obj_path: str, tmp: str) -> str:
     fat, co = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "dev.co")
     subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj_path, os.path.join(tmp, "copy.o")], check=True, capture_output=True)
@@ -165,6 +195,12 @@ def main():
             bad += r["vgpr_count"] > 128 or r["private_segment_fixed_size"] != 0      # four waves per SIMD, no scratch
         sys.exit(1 if bad else 0)
     objs = [a for a in sys.argv[1:] if not a.startswith("--")] or OBJECTS
+    if "--digest" in sys.argv:
+        for obj in objs:
+            for name, insts in kernels(device_disassembly(os.path.join(CSRC, obj))).items():
+                if insts and not name.endswith(".kd"):
+                    print(f"{obj:14s} {digest(insts)} {name}")
+        return
     dump = "--dump" in sys.argv
     bad = 0
     for obj in objs:

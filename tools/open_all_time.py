@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Device time of open_all (all KZG openings of a polynomial on its domain; csrc/kzg_open.inc) at k = 10, 14, 18, 20, the median of
+"""Device time of open_all (all KZG openings of a polynomial on its domain; csrc/g1_fft.hip) at k = 10, 14, 18, 20, the median of
 five, split into its parts, and in the same session what it is compared with:
 
 * the floor: g1_fft through the existing entry (hm_g1_fft_bn256_dev, no scale) at sizes 2n and n.  Their sum is what the two stage
