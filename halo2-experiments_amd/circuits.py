@@ -8,6 +8,8 @@ What is transcribed from files of the reference (read as text; cited per gate) a
     MerkleTreeV3   /root/reference/src/chips/merkle_v3.rs:30-82           bool / swap gates, column set: TRANSCRIBED
     Poseidon       /root/reference/src/chips/poseidon/hash.rs:45-72       which columns PoseidonChip::configure allocates
                    (partial_sbox, rc_a, rc_b, equality on the hash inputs, constants in rc_b[0]): TRANSCRIBED
+    OverflowCheckV2, SafeAccumulator   the reference's experiments 16 and 17 (``overflow_check_v2``, ``safe_accumulator`` below cite their
+                   lines; IsZeroChip and range_check with the latter): TRANSCRIBED
     Pow5Chip       halo2_gadgets::poseidon::Pow5Chip::configure ("full round", "partial rounds", "pad-and-add" gates): RECALLED --
                    the crate is a git dependency that is not in this image (/root/reference/Cargo.toml:11)
     LtChip         zkevm-circuits gadgets::less_than::LtChip::configure ("lt gate": lhs - rhs - sum diff_i 256^i + lt * 2^(8 N);
@@ -322,6 +324,68 @@ def overflow_check_v2(max_bits: int = 4, acc_cols: int = 4, unblinded_value: boo
     return ConstraintSystem(f"OverflowCheckV2<{max_bits}, {acc_cols}>", "circuits/overflow_check_v2.rs:21-39, chips/overflow_check_v2.rs:31-78",
                             cols.num_fixed, cols.num_advice, cols.num_instance, gates, lookups, cols.equality,
                             unblinded_advice=(value,) if unblinded_value else (), parameters=dict(max_bits=max_bits, acc_cols=acc_cols))
+
+
+def range_check(value: Expression, range_: int) -> Expression:
+    """chips/utils.rs:73-77: value * (1 - value) * (2 - value) * ... * (range - 1 - value), zero exactly on 0 .. range - 1."""
+    acc = value
+    for i in range(1, range_):
+        acc = acc * (Constant(i) - value)
+    return acc
+
+
+def safe_accumulator(max_bits: int = 4, acc_cols: int = 4) -> ConstraintSystem:
+    """SafeAccumulatorCircuit::configure, /root/reference/src/circuits/safe_accumulator.rs:21-50, with SafeACcumulatorChip::configure,
+    /root/reference/src/chips/safe_accumulator.rs:36-173, IsZeroChip::configure, /root/reference/src/chips/is_zero.rs:26-55, and
+    range_check / range_check_vec, /root/reference/src/chips/utils.rs:73-90 (TRANSCRIBED; the reference instantiates <4, 4> only).
+
+    A running total of ``acc_cols`` limbs of ``max_bits`` bits.  Advice 0 is update_value, advice 1 left_most_inv, advice
+    2 .. 1 + A the carries add_carries[0 .. A - 1], advice 2 + A .. 1 + 2 A the limbs accumulate[0 .. A - 1], most significant first;
+    fixed 0, 1, 2 the selectors add, overflow, bool (the circuit's allocation order); one instance column.  Equality in the chip's
+    order: the accumulate columns, the carry columns, the instance column.  Gates in creation order:
+        "is_zero"                   s_over * acc[0] * (1 - acc[0] * inv)                                            is_zero.rs:34-49
+        "bool constraint"           s_bool * c * (1 - c), one per carry column                                      safe_accumulator.rs:62-73
+        "accumulation constraint"   the list of :153-161 in its order: the add-value polynomial (:112-117), the range check of the
+                                    value (:118), the A - 1 limb-carry polynomials (:141-148), s_over * (1 - is_zero_expr)
+                                    (:150-151), the range checks of the previous row's limbs (:158) and of this row's (:159)
+    The accumulate columns are queried at Rotation::prev and Rotation::cur.  range_check(v, 2^b) is a product of 2^b linear factors,
+    so the degree is 2^max_bits + 1 (17 at <4, 4>) and the extended domain is 2^max_bits times the domain."""
+    if not 1 <= max_bits <= 4:
+        raise ValueError("safe_accumulator: max_bits must be 1 .. 4 (the gate degree is 2^max_bits + 1)")
+    if acc_cols < 2 or max_bits * acc_cols > 64:
+        raise ValueError("safe_accumulator: acc_cols must be at least 2 and max_bits * acc_cols at most 64")
+    cols = _Columns()
+    value = cols.advice()                                                      # circuits/safe_accumulator.rs:22
+    inv = cols.advice()                                                        # :23
+    carries = [cols.advice() for _ in range(acc_cols)]                         # :24-29
+    acc = [cols.advice() for _ in range(acc_cols)]                             # :30-35
+    s_add, s_over, s_bool = cols.selector(), cols.selector(), cols.selector()  # :36-38
+    inst = cols.instance()                                                     # :39
+    A, one = Advice, Constant(1)
+    is_zero_expr = one - A(acc[0]) * A(inv)                                    # is_zero.rs:47
+    gates = [("is_zero", [Fixed(s_over) * A(acc[0]) * is_zero_expr])]          # chips/safe_accumulator.rs:49-54, is_zero.rs:48
+    for col in acc:                                                            # :57
+        cols.enable_equality("advice", col)
+    for col in carries:                                                        # :58
+        cols.enable_equality("advice", col)
+    cols.enable_equality("instance", inst)                                     # :60
+    gates.append(("bool constraint", [Fixed(s_bool) * A(c) * (one - A(c)) for c in carries]))                        # :62-73
+    prev = [A(c, -1) for c in acc]                                             # :82-84
+    carry = [A(c) for c in carries]                                            # :85-87
+    cur = [A(c) for c in acc]                                                  # :88-90
+    shift = Constant(1 << max_bits)                                            # :92
+    last = acc_cols - 1
+    polys = [Fixed(s_add) * ((A(value) + prev[last]) - (carry[last] * shift + cur[last]))]                           # :112-117
+    polys.append(Fixed(s_add) * range_check(A(value), 1 << max_bits))                                                # :118
+    polys += [Fixed(s_add) * ((cur[i] + carry[i] * shift) - (prev[i] + carry[i + 1])) for i in range(acc_cols - 1)]  # :141-148
+    polys.append(Fixed(s_over) * (one - is_zero_expr))                                                               # :150-151
+    polys += [Fixed(s_over) * range_check(e, 1 << max_bits) for e in prev]                                           # :158
+    polys += [Fixed(s_over) * range_check(e, 1 << max_bits) for e in cur]                                            # :159
+    gates.append(("accumulation constraint", polys))
+    return ConstraintSystem(f"SafeAccumulator<{max_bits}, {acc_cols}>",
+                            "circuits/safe_accumulator.rs:21-50, chips/safe_accumulator.rs:36-173, chips/is_zero.rs:26-55, chips/utils.rs:73-90",
+                            cols.num_fixed, cols.num_advice, cols.num_instance, gates, [], cols.equality,
+                            parameters=dict(max_bits=max_bits, acc_cols=acc_cols))
 
 
 CONSTRAINT_SYSTEMS: Dict[str, Callable[[], ConstraintSystem]] = {

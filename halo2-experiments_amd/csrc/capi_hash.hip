@@ -472,4 +472,100 @@ int hm_range_witness_bn256_fr(uint32_t max_bits, uint32_t acc_cols, uint32_t log
   });
 } HM_API_CATCH("hm_range_witness_bn256_fr")
 
+// ---- the SafeAccumulator circuit's witness (accumulator.inc: accumulator_row) -----------------------------------------------------
+// what the layout and both forms of the witness refuse; -> n_advice
+static int accumulator_witness_layout(const char* who, uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, uint32_t rows, uint32_t* n_advice) {
+  const std::string w(who);
+  if (max_bits == 0 || max_bits > 4) return hm_fail(HM_ERR_BAD_ARG, w + ": max_bits must be 1 .. 4");
+  if (acc_cols < 2 || (uint64_t)max_bits * acc_cols > 64)
+    return hm_fail(HM_ERR_BAD_ARG, w + ": acc_cols must be at least 2 and max_bits * acc_cols at most 64");
+  if (log_n > WITNESS_MAX_LOG_N) return hm_fail(HM_ERR_BAD_ARG, w + ": log_n > 24");
+  if (rows == 0) return hm_fail(HM_ERR_BAD_ARG, w + ": rows must be at least 1");
+  if (((uint64_t)1 << log_n) < (uint64_t)rows + 1 + 6)
+    return hm_fail(HM_ERR_BAD_ARG, w + ": the circuit needs " + std::to_string((uint64_t)rows + 1) + " rows, 2^log_n - 6 is fewer");
+  *n_advice = 2 + 2 * acc_cols;
+  return HM_OK;
+}
+
+int hm_accumulator_witness_layout(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, uint32_t rows, uint32_t* out_n_advice,
+                                  uint32_t* out_used_rows) try {
+  if (!out_n_advice || !out_used_rows) return hm_fail(HM_ERR_BAD_ARG, "hm_accumulator_witness_layout: null argument");
+  uint32_t n_advice = 0;
+  if (int rc = accumulator_witness_layout("hm_accumulator_witness_layout", max_bits, acc_cols, log_n, rows, &n_advice)) return rc;
+  *out_n_advice = n_advice;
+  *out_used_rows = rows + 1;
+  return HM_OK;
+} HM_API_CATCH("hm_accumulator_witness_layout")
+
+static int accumulator_witness_args(const char* who, uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows,
+                                    std::initializer_list<const void*> needed, uint32_t* n_advice) {
+  for (const void* p : needed)
+    if (!p) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (m == 0 || m > 65535) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": m must be 1 .. 65535");
+  if (int rc = accumulator_witness_layout(who, max_bits, acc_cols, log_n, rows, n_advice)) return rc;
+  if (m > (POSEIDON_MAX_N >> log_n)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": more than 2^31 rows");
+  return HM_OK;
+}
+
+static int accumulator_witness_dev(const char* who, uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows,
+                                   const void* d_values, const uint64_t* d_initial, void* d_advice, uint64_t* d_finals, uint32_t* d_over_or_null,
+                                   void* stream, double* part_ms) {
+  uint32_t n_advice = 0;
+  if (int rc = accumulator_witness_args(who, max_bits, acc_cols, log_n, m, rows, {d_values, d_initial, d_advice, d_finals}, &n_advice)) return rc;
+  if (int rc = witness_aligned(who, {d_values, d_advice}, nullptr)) return rc;
+  if (((uintptr_t)d_initial | (uintptr_t)d_finals) & 7u) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": d_initial or d_finals is not 8-byte aligned");
+  if ((uintptr_t)d_over_or_null & 3u) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": d_over is not 4-byte aligned");
+  const size_t adv_bytes = m * n_advice * ((size_t)32 << log_n), limb_bytes = m * acc_cols * sizeof(uint64_t);
+  if (ranges_overlap(d_values, m * rows * 32, d_advice, adv_bytes) || ranges_overlap(d_initial, limb_bytes, d_advice, adv_bytes) ||
+      ranges_overlap(d_finals, limb_bytes, d_advice, adv_bytes) || ranges_overlap(d_finals, limb_bytes, d_values, m * rows * 32) ||
+      ranges_overlap(d_finals, limb_bytes, d_initial, limb_bytes))
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": an output overlaps an input or the other output");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  uint64_t inverses[15 * 4];
+  host::fr_small_inverses((1u << max_bits) - 1, inverses);
+  return accumulator_witness_run(max_bits, acc_cols, log_n, m, rows, (const uint32_t*)d_values, d_initial, inverses, (uint32_t*)d_advice, d_finals,
+                                 d_over_or_null, (hipStream_t)stream, part_ms);
+}
+
+int hm_accumulator_witness_bn256_fr_dev(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const void* d_values,
+                                        const uint64_t* d_initial, void* d_advice, uint64_t* d_finals, uint32_t* d_over_or_null,
+                                        void* stream) try {
+  return accumulator_witness_dev("hm_accumulator_witness_bn256_fr_dev", max_bits, acc_cols, log_n, m, rows, d_values, d_initial, d_advice, d_finals,
+                                 d_over_or_null, stream, nullptr);
+} HM_API_CATCH("hm_accumulator_witness_bn256_fr_dev")
+
+int hm_accumulator_witness_timed_bn256_fr_dev(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const void* d_values,
+                                              const uint64_t* d_initial, void* d_advice, uint64_t* d_finals, uint32_t* d_over_or_null,
+                                              void* stream, double out_part_ms[4]) try {
+  if (!out_part_ms) return hm_fail(HM_ERR_BAD_ARG, "hm_accumulator_witness_timed_bn256_fr_dev: null argument");
+  return accumulator_witness_dev("hm_accumulator_witness_timed_bn256_fr_dev", max_bits, acc_cols, log_n, m, rows, d_values, d_initial, d_advice,
+                                 d_finals, d_over_or_null, stream, out_part_ms);
+} HM_API_CATCH("hm_accumulator_witness_timed_bn256_fr_dev")
+
+int hm_accumulator_witness_bn256_fr(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint64_t* values,
+                                    const uint64_t* initial, uint64_t* advice, uint64_t* finals, uint32_t* over_or_null) try {
+  const char* who = "hm_accumulator_witness_bn256_fr";
+  uint32_t n_advice = 0;
+  if (int rc = accumulator_witness_args(who, max_bits, acc_cols, log_n, m, rows, {values, initial, advice, finals}, &n_advice)) return rc;
+  const size_t col_bytes = (size_t)32 << log_n;
+  if (m > WITNESS_HOST_MAX_BYTES / ((size_t)n_advice * col_bytes))
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the columns exceed 256 MiB; use the device form");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  uint64_t inverses[15 * 4];
+  host::fr_small_inverses((1u << max_bits) - 1, inverses);
+  const size_t val_bytes = pad64(m * rows * 32), limb_bytes = pad64(m * acc_cols * sizeof(uint64_t)), adv_bytes = m * n_advice * col_bytes;
+  const size_t adv_at = val_bytes + limb_bytes, fin_at = adv_at + adv_bytes, over_at = fin_at + limb_bytes;
+  const HostIn in[2] = {{values, m * rows * 32, 0}, {initial, m * acc_cols * sizeof(uint64_t), val_bytes}};
+  const HostOut out[3] = {{over_or_null, over_or_null ? m * sizeof(uint32_t) : 0, over_at, true},
+                          {finals, m * acc_cols * sizeof(uint64_t), fin_at, true},
+                          {advice, adv_bytes, adv_at, false}};
+  return host_round_trip(who, *ctx, "witness", over_at + m * sizeof(uint32_t), in, 2, out, 3, [&](uint8_t* d) {
+    return accumulator_witness_run(max_bits, acc_cols, log_n, m, rows, (const uint32_t*)d, (const uint64_t*)(d + val_bytes), inverses,
+                                   (uint32_t*)(d + adv_at), (uint64_t*)(d + fin_at), (uint32_t*)(d + over_at), nullptr);
+  });
+} HM_API_CATCH("hm_accumulator_witness_bn256_fr")
+
 }  // extern "C"

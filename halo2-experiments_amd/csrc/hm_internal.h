@@ -477,6 +477,16 @@ int poseidon_witness_run(const PoseidonSpec& s, uint32_t log_n, size_t m, const 
 int range_witness_run(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint32_t* d_values,
                       uint32_t* d_advice, uint32_t* d_over, hipStream_t stream);
 
+// accumulator.hip: the SafeAccumulator circuit's witness: m running totals of acc_cols limbs of max_bits bits (max_bits * acc_cols <= 64),
+// row 0 the initial limbs, row r the value r, the top limb's inverse, the carries and the limbs after adding it; every row of every
+// column is written.  inverses_ext: HOST memory, the 2^max_bits - 1 inverses of 1 .. 2^max_bits - 1 (host_fr.h: fr_small_inverses);
+// d_finals: m x acc_cols plain limbs; d_over: null, or m counters of the failing rows.  Asynchronous on `stream`, stream-ordered
+// scratch of its own; the arguments were checked by the caller (capi_hash.hip).  part_ms: null, or 4 doubles for the device times of
+// the four launches (reduce, scan, rows, count); the call then waits for `stream`.
+int accumulator_witness_run(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint32_t* d_values,
+                            const uint64_t* d_initial, const uint64_t* inverses_ext, uint32_t* d_advice, uint64_t* d_finals, uint32_t* d_over,
+                            hipStream_t stream, double* part_ms = nullptr);
+
 // keygen.hip: keygen's permutation assembly.  d_copies: m pairs of cell ids, a cell being column * 2^k + row; d_sigma_cells receives
 // columns * 2^k ids (it is the union-find's parent array on the way); a pair with an id out of range is dropped and counted in
 // *d_dropped (null: not counted).  Asynchronous on `stream`; the arguments were checked by the caller (capi_keygen.hip).

@@ -23,6 +23,7 @@ namespace hm {
 #include "verify_terms.inc"  // ... and the two phases of its per-proof terms around the interpreter's run (verify.hip)
 #include "poseidon.inc"   // the per-hash Poseidon / Merkle node functions (poseidon.hip)
 #include "range.inc"      // the range-check witness's lane function (range.hip)
+#include "accumulator.inc" // the accumulator witness's row function (accumulator.hip)
 #include "keygen.inc"     // the permutation assembly's key packing and link rule (keygen.hip)
 #include "shplonk.inc"    // the SHPLONK set quotient's plan, coefficients and row formula (polyops.hip)
 #include "pairing.inc"    // the pairing's tower, Miller lane and final exponentiation (pairing.hip)
@@ -889,6 +890,37 @@ int hc_range_witness(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_
   const RangeArgs a{values, advice, over, (uint64_t)m << log_n, max_bits, acc_cols, log_n, rows};
   for (size_t c = 0; c < m; ++c) over[c] = 0;
   for (uint64_t idx = 0; idx < a.lanes; ++idx) over[idx >> log_n] += range_witness_lane(a, idx) ? 1u : 0u;
+  return 0;
+}
+
+// The accumulator witness with the rows of a circuit one after the other: what accumulator.hip's four launches compute, S_(r-1)
+// carried from row to row instead of scanned.  initial: m x acc_cols plain limbs; finals: the same shape; over: m counters.
+int hc_accumulator_witness(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint32_t* values,
+                           const uint64_t* initial, uint32_t* advice, uint64_t* finals, uint32_t* over) {
+  if (max_bits == 0 || max_bits > ACC_MAX_BITS || acc_cols < 2 || max_bits * acc_cols > ACC_MAX_WIDTH || log_n > 24 || rows == 0 ||
+      (uint64_t)rows + 1 > ((uint64_t)1 << log_n))
+    return -1;
+  uint64_t inverses[15 * 4];
+  host::fr_small_inverses((1u << max_bits) - 1, inverses);
+  const AccArgs a{values, initial, (const uint32_t*)inverses, advice, finals, max_bits, acc_cols, log_n, rows};
+  const uint64_t n = (uint64_t)1 << log_n, col_words = n * 8;
+  const uint32_t n_cols = 2 + 2 * acc_cols;
+  for (size_t c = 0; c < m; ++c) {
+    uint32_t* base = advice + c * n_cols * col_words;
+    uint64_t s;
+    over[c] = acc_initial_state(a, c, s) ? 1u : 0u;
+    acc_zero_cells(base, col_words, 0, 2 + acc_cols);
+    for (uint32_t i = 0; i < acc_cols; ++i) acc_initial_cell(a, c, i);
+    for (uint64_t t = 1; t <= rows; ++t) {
+      uint32_t w[8];
+      ps_get_words(values + (c * rows + (t - 1)) * 8, w);
+      uint64_t s_new;
+      over[c] += accumulator_row(a, base + t * 8, s, w, s_new) ? 1u : 0u;
+      s = s_new;
+    }
+    acc_write_finals(a, c, s);
+    for (uint64_t t = (uint64_t)rows + 1; t < n; ++t) acc_zero_cells(base + t * 8, col_words, 0, n_cols);
+  }
   return 0;
 }
 

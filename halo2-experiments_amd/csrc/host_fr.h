@@ -87,6 +87,17 @@ static inline Fr4 fr_inv(const Fr4& a) {   // a^(r-2); zero stays zero
   return acc;
 }
 
+// out[j] = (j + 1)^-1 for j < count, Montgomery words: the table the SafeAccumulator witness reads its top limb's inverse from
+static inline void fr_small_inverses(uint32_t count, uint64_t* out) {
+  const Fr4 zero = {{0, 0, 0, 0}}, minus_one = fr_sub(zero, FR_ONE);
+  Fr4 x = zero;
+  for (uint32_t j = 0; j < count; ++j) {
+    x = fr_sub(x, minus_one);
+    const Fr4 inv = fr_inv(x);
+    memcpy(out + (size_t)j * 4, inv.l, 32);
+  }
+}
+
 static inline Fr4 fr_load(const uint64_t w[4]) {
   Fr4 r;
   memcpy(r.l, w, 32);

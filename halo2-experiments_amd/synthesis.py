@@ -577,8 +577,145 @@ class RangeCheckLayout:
         return adv
 
 
+class SafeAccumulatorLayout:
+    """``SafeAccumulatorCircuit::synthesize`` for ``circuits.safe_accumulator(max_bits, acc_cols)`` with ``rows`` added values, as
+    ONE running table (DESIGN.md section 26) -- the table the reference's README draws and its gate at ``Rotation::prev`` is written
+    for.  TRANSCRIBED (read as text):
+        chip.assign: value, previous limbs, carries, inverse, updated limbs         /root/reference/src/chips/safe_accumulator.rs:175-260
+        the loop over the values and expose_public                                  /root/reference/src/circuits/safe_accumulator.rs:52-90
+        is_zero_chip.assign: the inverse, or 0                                      /root/reference/src/chips/is_zero.rs:57-66
+    Row 0 holds the initial accumulate limbs and nothing else; row r, 1 <= r <= rows, holds value r, the inverse of the top limb,
+    the carries and the limbs after adding value r.  All three selectors are set on rows 1 .. rows.  There are ``acc_cols`` copies:
+    accumulate column i on row ``rows`` to instance row i (instance row 0 is the most significant limb).  rows + 1 <= 2^k - 6.
+
+    Two deviations from the reference:
+      * it opens a new two-row region per value and assigns the previous limbs into it again without a copy constraint, and its
+        ``offset`` arithmetic breaks from the third value on (circuits/safe_accumulator.rs:72-82, chips/safe_accumulator.rs:190-251:
+        the value and the inverse go to row 1, the carries and limbs to row offset + 1).  For one value the running table is the
+        reference's region cell for cell; for more it is one table whose row r - 1 IS the previous state of row r.
+      * its config keeps only two of its three selectors and never enables ``bool_selector`` (chips/safe_accumulator.rs:170,
+        :190-191), so the carries are not constrained to be bits and the accumulator is unsound (any field
+        element that balances the limb polynomials passes as a carry).  Here the bool selector is set on every accumulating row, as the
+        reference's README says it is meant to be."""
+    NAME = "SafeAccumulatorLayout"
+    VALUE, INV = 0, 1                         # advice 0, 1 (circuits.safe_accumulator()'s allocation order)
+    S_ADD, S_OVER, S_BOOL = 0, 1, 2           # fixed 0 .. 2
+    N_FIXED = 3
+
+    def __init__(self, k: int, max_bits: int = 4, acc_cols: int = 4, rows: int = 1):
+        if not 1 <= max_bits <= 4:
+            raise ValueError("SafeAccumulatorLayout: max_bits must be 1 .. 4")
+        if acc_cols < 2 or max_bits * acc_cols > 64:
+            raise ValueError("SafeAccumulatorLayout: acc_cols must be at least 2 and max_bits * acc_cols at most 64")
+        if rows < 1:
+            raise ValueError("SafeAccumulatorLayout: rows must be at least 1")
+        self.k, self.n, self.max_bits, self.acc_cols, self.rows = k, 1 << k, max_bits, acc_cols, rows
+        self.N_ADVICE = 2 + 2 * acc_cols
+        self.CARRIES = tuple(range(2, 2 + acc_cols))
+        self.ACC = tuple(range(2 + acc_cols, 2 + 2 * acc_cols))
+        self.width = max_bits * acc_cols
+        self.used_rows = self.rows_needed(rows)
+        if self.used_rows > self.n - BLINDING_ROWS:
+            raise ValueError(f"SafeAccumulatorLayout: {self.used_rows} rows are needed, 2^{k} - {BLINDING_ROWS} is fewer "
+                             f"(min_k = {self.min_k(rows)})")
+        cols = tuple(("advice", c) for c in range(self.N_ADVICE)) + tuple(("fixed", c) for c in range(self.N_FIXED))
+        self.regions = [Region("calculate accumulates", 0, self.used_rows, cols)]
+
+    @staticmethod
+    def rows_needed(rows: int) -> int:
+        return rows + 1
+
+    @classmethod
+    def min_k(cls, rows: int) -> int:
+        return (cls.rows_needed(rows) + BLINDING_ROWS - 1).bit_length()
+
+    def check_constraint_system(self, cs: ConstraintSystem) -> None:
+        equality = [("advice", c) for c in self.ACC + self.CARRIES] + [("instance", 0)]
+        if (cs.num_advice, cs.num_fixed, cs.num_instance) != (self.N_ADVICE, self.N_FIXED, 1) or list(cs.equality) != equality or \
+                cs.parameters != dict(max_bits=self.max_bits, acc_cols=self.acc_cols):
+            raise ValueError(f"SafeAccumulatorLayout: the constraint system is not circuits.safe_accumulator({self.max_bits}, {self.acc_cols})")
+
+    def selector_rows(self) -> Dict[int, List[int]]:
+        return {s: list(range(1, self.rows + 1)) for s in (self.S_ADD, self.S_OVER, self.S_BOOL)}
+
+    def fixed_columns(self) -> List[List[int]]:
+        cols = [[0] * self.n for _ in range(self.N_FIXED)]
+        for s, rows in self.selector_rows().items():
+            for r in rows:
+                cols[s][r] = 1
+        return cols
+
+    def copies(self) -> List[Tuple[Cell, Cell]]:
+        return [(("advice", c, self.rows), ("instance", 0, i)) for i, c in enumerate(self.ACC)]
+
+    def state(self, initial: Sequence[int]) -> int:
+        """the initial limbs read as one integer below 2^(max_bits * acc_cols)"""
+        if len(initial) != self.acc_cols:
+            raise ValueError(f"SafeAccumulatorLayout: {self.acc_cols} initial limbs expected")
+        s = 0
+        for limb in initial:
+            s = (s << self.max_bits) + int(limb)
+        return s % (1 << self.width)
+
+    def limbs(self, s: int) -> List[int]:
+        mask = (1 << self.max_bits) - 1
+        return [(s >> (self.max_bits * (self.acc_cols - 1 - i))) & mask for i in range(self.acc_cols)]
+
+    def finals(self, initial: Sequence[int], values: Sequence[int]) -> List[int]:
+        """the limbs after the last value"""
+        s = self.state(initial)
+        for v in values:
+            s = (s + int(v) % R) % (1 << self.width)
+        return self.limbs(s)
+
+    def instance(self, initial: Sequence[int], values: Sequence[int]) -> List[List[int]]:
+        return [self.finals(initial, values)]
+
+    def assign_ints(self, initial: Sequence[int], values: Sequence[int]) -> List[List[int]]:
+        """The 2 + 2 acc_cols advice columns -- the definition of the witness.  Nothing is judged: with b = max_bits, A = acc_cols and
+        W = b A, S_0 is the initial limbs read as one integer mod 2^W, v_r the value's plain integer mod 2^W, S_r = (S_(r-1) + v_r) mod
+        2^W; the limbs of row r are those of S_r; c[A-1] = (prev[A-1] + v_r >= 2^b), c[i] = (prev[i] + c[i+1] >= 2^b) for
+        1 <= i < A - 1, c[0] = 0 (the reference's ``idx > 0``); inv is the inverse of the top limb mod r, or 0; the value column holds
+        the value as given, and row 0 the initial limbs as given.  The witness satisfies the system exactly when every value and every
+        initial limb is below 2^b and the top limb is 0 on every row 0 .. rows: the usable capacity is b (A - 1) bits."""
+        if len(values) != self.rows:
+            raise ValueError(f"assign_ints: {self.rows} values expected")
+        b, A = self.max_bits, self.acc_cols
+        adv = [[0] * self.n for _ in range(self.N_ADVICE)]
+        s = self.state(initial)
+        for i, c in enumerate(self.ACC):
+            adv[c][0] = int(initial[i]) % R
+        for r, value in enumerate(values, start=1):
+            value = int(value) % R
+            v = value % (1 << self.width)
+            prev = self.limbs(s)
+            s = (s + v) % (1 << self.width)
+            cur = self.limbs(s)
+            carry = [0] * A
+            carry[A - 1] = int(prev[A - 1] + v >= 1 << b)
+            for i in range(A - 2, 0, -1):
+                carry[i] = int(prev[i] + carry[i + 1] >= 1 << b)
+            adv[self.VALUE][r] = value
+            adv[self.INV][r] = pow(cur[0], R - 2, R) if cur[0] else 0
+            for i in range(A):
+                adv[self.CARRIES[i]][r] = carry[i]
+                adv[self.ACC[i]][r] = cur[i]
+        return adv
+
+    def over(self, initial: Sequence[int], values: Sequence[int]) -> int:
+        """what the GPU witness counts: the rows whose value is at or above 2^b or whose top limb is not zero, plus 1 when an initial
+        limb is at or above 2^b or the initial top limb is not zero"""
+        s = self.state(initial)
+        count = int(any(int(x) >> self.max_bits for x in initial) or int(initial[0]) != 0)
+        for v in values:
+            v = int(v) % R
+            s = (s + v) % (1 << self.width)
+            count += int(v >> self.max_bits != 0 or self.limbs(s)[0] != 0)
+        return count
+
+
 # ---- keygen's permutation columns -----------------------------------------------------------------------------------------------
-AnyLayout = Union[MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, RangeCheckLayout]      # anything with ``n`` and ``copies()``
+AnyLayout = Union[MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, RangeCheckLayout, SafeAccumulatorLayout]      # anything with ``n`` and ``copies()``
 
 
 def permutation_cells(cs: ConstraintSystem, layout: "AnyLayout") -> List[List[Tuple[int, int]]]:
@@ -855,6 +992,84 @@ def range_witness_host(values: np.ndarray, k: int, max_bits: int = 4, acc_cols: 
     over = np.zeros(m, dtype=np.uint32)
     _lib.check(_lib.load().hm_range_witness_bn256_fr(max_bits, acc_cols, k, m, rows, _ptr(vs), _ptr(adv), over.ctypes.data_as(_u32p)))
     return adv, over
+
+
+ACCUMULATOR_BLOCK_ROWS = 256          # csrc/accumulator.hip: ACC_THREADS, the table rows one block of the accumulator kernels takes
+
+
+def accumulator_c_layout(k: int, max_bits: int = 4, acc_cols: int = 4, rows: int = 1) -> Dict[str, int]:
+    """``hm_accumulator_witness_layout``: the numbers the accumulator kernels use (no device needed), beside
+    ``SafeAccumulatorLayout``'s; ValueError when the two differ."""
+    n_adv, used = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    _lib.check(_lib.load().hm_accumulator_witness_layout(max_bits, acc_cols, k, rows, ctypes.byref(n_adv), ctypes.byref(used)))
+    lay = SafeAccumulatorLayout(k, max_bits, acc_cols, rows)
+    out = {"n_advice": n_adv.value, "used_rows": used.value}
+    if out != {"n_advice": lay.N_ADVICE, "used_rows": lay.used_rows}:
+        raise ValueError(f"accumulator_c_layout: the C layout {out} is not SafeAccumulatorLayout's")
+    return out
+
+
+def _accumulator_shapes(who: str, values_shape, initial_shape, k: int, max_bits: int, acc_cols: int) -> Tuple[int, int]:
+    """what both forms of the accumulator witness refuse before anything is launched -> (m, rows)"""
+    SafeAccumulatorLayout(max(k, 3), max_bits, acc_cols, 1)          # the parameter limits, stated once
+    if len(values_shape) != 3 or values_shape[2] != 4 or values_shape[0] == 0 or values_shape[1] == 0:
+        raise ValueError(f"{who}: values must be a non-empty (m, rows, 4) array of 64-bit words")
+    m, rows = values_shape[0], values_shape[1]
+    if tuple(initial_shape) != (m, acc_cols):
+        raise ValueError(f"{who}: initial must be (m, acc_cols) = ({m}, {acc_cols}) plain limbs, not {tuple(initial_shape)}")
+    if m > 65535:
+        raise ValueError(f"{who}: at most 65535 circuits a call")
+    SafeAccumulatorLayout(k, max_bits, acc_cols, rows)               # rows + 1 <= 2^k - 6
+    return m, rows
+
+
+def accumulator_witness(values, initial, k: int, max_bits: int = 4, acc_cols: int = 4, out=None, parts: Optional[list] = None):
+    """The SafeAccumulator witnesses of m circuits: ``values`` (m, rows, 4) GPU tensor of canonical Montgomery words, ``initial``
+    (m, acc_cols) int64 GPU tensor of plain limb integers, most significant first -> (advice (m, 2 + 2 acc_cols, 2^k, 4), finals
+    (m, acc_cols) int64: the plain final limbs, which are the instance, over (m,) int32: per circuit the rows whose value is at or
+    above 2^max_bits or whose top limb is not zero, plus 1 for a bad initial state); every word written, rows above ``rows`` zero;
+    asynchronous on the current stream.  ``out``: an advice tensor to fill instead of a new one (it may be uninitialised).
+    ``parts``: a list that receives the device milliseconds of the call's four launches (block totals, their scan, the rows, the
+    counters); the call then waits for the stream (``hm_accumulator_witness_timed_bn256_fr_dev``; tools/accumulator_witness_time.py).
+    ValueError, with nothing launched: wrong shapes, rows + 1 > 2^k - 6, max_bits * acc_cols > 64."""
+    import torch
+
+    if not (_is_cuda_words(values) and _is_cuda_words(initial)):
+        raise ValueError("accumulator_witness: values and initial must be contiguous 64-bit GPU tensors")
+    m, rows = _accumulator_shapes("accumulator_witness", tuple(values.shape), tuple(initial.shape), k, max_bits, acc_cols)
+    for name, t in (("initial", initial), ("out", out)):
+        if t is not None and t.is_cuda and t.device != values.device:
+            raise ValueError(f"accumulator_witness: {name} is on {t.device}, values on {values.device}")
+    for name, t in (("values", values), ("out", out)):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"accumulator_witness: {name} must be 16-byte aligned")
+    out = _witness_out("accumulator_witness", out, m, 2 + 2 * acc_cols, 1 << k, values.device)
+    finals = torch.empty((m, acc_cols), dtype=torch.int64, device=values.device)
+    over = torch.empty(m, dtype=torch.int32, device=values.device)
+    args = (max_bits, acc_cols, k, m, rows, ctypes.c_void_p(values.data_ptr()), _dev_ptr(initial), ctypes.c_void_p(out.data_ptr()),
+            _dev_ptr(finals), _dev_ptr(over, _u32p), ctypes.c_void_p(_stream_ptr(values)))
+    with torch.cuda.device(values.device):
+        if parts is None:
+            _lib.check(_lib.load().hm_accumulator_witness_bn256_fr_dev(*args))
+        else:
+            ms = (ctypes.c_double * 4)()
+            _lib.check(_lib.load().hm_accumulator_witness_timed_bn256_fr_dev(*args, ms))
+            parts[:] = list(ms)
+    return out, finals, over
+
+
+def accumulator_witness_host(values: np.ndarray, initial: np.ndarray, k: int, max_bits: int = 4, acc_cols: int = 4):
+    """``accumulator_witness`` on numpy arrays, (m, rows, 4) words and (m, acc_cols) limbs, through the host-pointer form (columns
+    below 256 MiB)."""
+    vs = np.ascontiguousarray(np.asarray(values, dtype=np.uint64))
+    init = np.ascontiguousarray(np.asarray(initial, dtype=np.uint64))
+    m, rows = _accumulator_shapes("accumulator_witness_host", vs.shape, init.shape, k, max_bits, acc_cols)
+    adv = np.zeros((m, 2 + 2 * acc_cols, 1 << k, 4), dtype=np.uint64)
+    finals = np.zeros((m, acc_cols), dtype=np.uint64)
+    over = np.zeros(m, dtype=np.uint32)
+    _lib.check(_lib.load().hm_accumulator_witness_bn256_fr(max_bits, acc_cols, k, m, rows, _ptr(vs), _ptr(init), _ptr(adv), _ptr(finals),
+                                                          over.ctypes.data_as(_u32p)))
+    return adv, finals, over
 
 
 def _is_cuda_words(t) -> bool:

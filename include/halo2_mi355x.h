@@ -701,6 +701,37 @@ int hm_range_witness_bn256_fr_dev(uint32_t max_bits, uint32_t acc_cols, uint32_t
 int hm_range_witness_bn256_fr(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint64_t* values,
                               uint64_t* advice, uint32_t* over_or_null);
 
+/* The witness of the accumulator circuit (the reference's SafeAccumulator): a running total of acc_cols limbs of max_bits bits, most
+ * significant first, W = max_bits * acc_cols <= 64 bits in all.  Advice column 0 holds the added values, column 1 the inverse of the
+ * top limb (0 when that limb is 0), columns 2 .. 1 + acc_cols the binary carries, columns 2 + acc_cols .. 1 + 2 acc_cols the limbs.
+ * Row 0 holds the initial limbs as given (every other cell of it zero); row r, 1 <= r <= rows, the value r and the state after adding
+ * it: S_r = (S_(r-1) + (value_r mod 2^W)) mod 2^W, S_0 the initial limbs read as one integer mod 2^W; carry[acc_cols - 1] =
+ * (limb + value >= 2^max_bits), carry[i] = (limb_i of S_(r-1) + carry[i + 1] >= 2^max_bits), carry[0] = 0.
+ * layout: needs no device; *out_n_advice = 2 + 2 acc_cols, *out_used_rows = rows + 1.
+ * witness: m circuits of `rows` values each; d_values m x rows canonical elements; d_initial m x acc_cols plain limb integers;
+ * d_advice m x (2 + 2 acc_cols) x 2^log_n elements (column c of circuit u is contiguous), every word of which is written: rows above
+ * `rows` are zero; d_finals m x acc_cols: the plain limbs of S_rows, which are the circuit's instance.  Nothing is judged: a value at
+ * or above 2^max_bits, an initial limb at or above 2^max_bits or a total that reaches the top limb gives a witness that fails its
+ * gates; d_over_or_null, m counters in DEVICE memory set by every call, counts per circuit the rows r >= 1 whose value is at or above
+ * 2^max_bits or whose top limb is not zero, plus 1 when an initial limb is at or above 2^max_bits or the initial top limb is not zero.
+ * Asynchronous on `stream`: four launches with stream-ordered scratch of the library's; no kernel waits for another block.
+ * HM_ERR_BAD_ARG, before anything is launched: NULL (d_over excepted), max_bits outside 1 .. 4, acc_cols < 2, max_bits * acc_cols > 64,
+ * log_n above 24, rows = 0, rows + 1 > 2^log_n - 6, m = 0 or above 65535, m * 2^log_n > 2^31, a device pointer that is not aligned
+ * (d_values, d_advice: 16; d_initial, d_finals: 8; d_over: 4), an output overlapping an input; the host form: more than 256 MiB of
+ * columns.  Host form: outputs are written only by the final copies. */
+int hm_accumulator_witness_layout(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, uint32_t rows, uint32_t* out_n_advice,
+                                  uint32_t* out_used_rows);
+int hm_accumulator_witness_bn256_fr_dev(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const void* d_values,
+                                        const uint64_t* d_initial, void* d_advice, uint64_t* d_finals, uint32_t* d_over_or_null,
+                                        void* stream);
+int hm_accumulator_witness_bn256_fr(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint64_t* values,
+                                    const uint64_t* initial, uint64_t* advice, uint64_t* finals, uint32_t* over_or_null);
+/* The device form, and out_part_ms receives the device milliseconds of its four launches (the block totals, their scan, the rows, the
+ * counters; the last is 0 without d_over); waits for `stream`.  For tools/accumulator_witness_time.py. */
+int hm_accumulator_witness_timed_bn256_fr_dev(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const void* d_values,
+                                              const uint64_t* d_initial, void* d_advice, uint64_t* d_finals, uint32_t* d_over_or_null,
+                                              void* stream, double out_part_ms[4]);
+
 /* keygen's permutation argument (permutation::keygen::Assembly) on the device.  A cell id is j * 2^k + i: column j of the
  * `columns` equality-enabled columns, row i; columns * 2^k <= 2^32.
  * assemble: d_copies holds m copy constraints as pairs of cell ids (DEVICE memory, 8-byte aligned).  d_sigma_cells receives
