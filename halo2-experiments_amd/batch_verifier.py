@@ -26,6 +26,11 @@ Where the work is done:
     MSMs over offsets into it, folded with ``hm_g1_sum``;
   - one ``pairing.pairing_check`` (or, with the trapdoor, s * L == R in G1).
 
+``encoding="evm"`` (``ProofLayout``, ``BatchVerifier``, ``verify_proofs``) takes proofs in the second wire format, a Keccak transcript
+over uncompressed big-endian points and scalars (``transcript`` states it): the read is ``hm_verify_read_proofs_evm_dev`` -- a curve
+check in place of the square root, no y bytes --, the transcript absorbs the proof verbatim (``keccak256`` on the host,
+``hm_verify_transcript_evm_dev`` on the device; csrc/keccak.inc), and everything behind the challenges is the same code.
+
 ``proof_terms_ints`` is the integer twin of the whole per-proof part, ``read_proof_ints`` of the read kernel; neither needs a device.
 
 Two places where the symbolic form answers differently from ``verify_proof``, each of probability about 2^-254 for an honest or a
@@ -47,11 +52,13 @@ from .keygen import FR_DELTA, VerifyingKey
 from .kzg import g2_from_bytes
 from .pairing import G1_GEN, g1_mul, g1_neg, g1_on_curve
 from .shplonk import g1_words_to_int
-from .transcript import PERSONAL, PREFIX_CHALLENGE, PREFIX_POINT, PREFIX_SCALAR, TranscriptError, g1_decompress_int
+from .transcript import (PERSONAL, PREFIX_CHALLENGE, PREFIX_POINT, PREFIX_SCALAR, TranscriptError, check_encoding, g1_decompress_int,
+                         g1_uncompressed_int, keccak256)
 from .verifier import _instance_columns, _vk_digest, evaluate_expression, proof_length
 
 R, P = FR_MODULUS, FQ_MODULUS
 VR_POINT, VR_TAIL = 1 << 31, 1 << 30          # csrc/verify_read.inc: the slot table's bits
+EVM_POINT, EVM_TAIL, EVM_SKIP = 1 << 31, 1 << 30, 1 << 29   # csrc/keccak.inc: the bits of an "evm" layout's table (x slot, tail, y slot)
 
 
 class MalformedProof(ValueError):
@@ -71,9 +78,14 @@ class ProofLayout:
                        of first appearance as ``shplonk.construct_intermediate_sets`` finds them on the real points x * omega^rotation.
                        Two rotations give one point exactly when they agree mod n (x != 0), so the sets need no challenge; inside a set
                        the points stand in ascending ROTATION here and in ascending integer order there, which changes no scalar.
-      ``shared_keys``  the points all proofs share: the fixed commitments, the sigma commitments, the generator."""
+      ``shared_keys``  the points all proofs share: the fixed commitments, the sigma commitments, the generator.
 
-    def __init__(self, cs, k: int):
+    ``encoding="evm"``: a point takes two 32-byte slots, x then y, so ``slots`` = 2 points + scalars, and ``slot_table`` is of the kind
+    ``hm_verify_read_proofs_evm_dev`` takes: EVM_POINT | index on the x slot of an own point, EVM_POINT | EVM_TAIL on that of [h'],
+    EVM_SKIP on every y slot, the index on a scalar slot.  ``point_slots`` are then the x slots.  Everything else is the same."""
+
+    def __init__(self, cs, k: int, encoding: str = "halo2"):
+        self.encoding = check_encoding(encoding, "ProofLayout")
         self.cs, self.k, self.n = cs, k, 1 << k
         n = self.n
         adv_q, fix_q, _ = cs.queries()
@@ -100,14 +112,18 @@ class ProofLayout:
         for at, key in enumerate(evs):
             self.eval_index.setdefault(key, at)
         self.n_points, self.own_points, self.n_scalars = len(self.point_keys), len(self.point_keys) - 1, len(evs)
-        self.slots = self.n_points + self.n_scalars
-        if 32 * self.slots != proof_length(cs):
+        self.slots = (2 if encoding == "evm" else 1) * self.n_points + self.n_scalars
+        if 32 * self.slots != proof_length(cs, 1, encoding):
             raise AssertionError("ProofLayout: the slots do not add up to proof_length")
-        table = [VR_POINT | i for i in range(self.points_before_evals)] + list(range(self.n_scalars))
-        table += [VR_POINT | (self.n_points - 2), VR_POINT | VR_TAIL | (self.n_points - 1)]
+        if encoding == "evm":
+            table = [e for i in range(self.points_before_evals) for e in (EVM_POINT | i, EVM_SKIP)] + list(range(self.n_scalars))
+            table += [EVM_POINT | (self.n_points - 2), EVM_SKIP, EVM_POINT | EVM_TAIL | (self.n_points - 1), EVM_SKIP]
+        else:
+            table = [VR_POINT | i for i in range(self.points_before_evals)] + list(range(self.n_scalars))
+            table += [VR_POINT | (self.n_points - 2), VR_POINT | VR_TAIL | (self.n_points - 1)]
         self.slot_table = np.array(table, dtype=np.uint32)
         self.point_slots = [s for s, e in enumerate(table) if e & VR_POINT]
-        self.scalar_slots = [s for s, e in enumerate(table) if not e & VR_POINT]
+        self.scalar_slots = [s for s, e in enumerate(table) if not e & (VR_POINT | (EVM_SKIP if encoding == "evm" else 0))]
 
         # the queries in the order verifier._verify lists them; ("h",) stands for sum_i x^(n i) [h_i]
         q = [(("advice", i), r % n) for i, r in adv_q]
@@ -158,8 +174,11 @@ class ProofLayout:
     def transcript_schedule(self) -> List[Tuple[int, int]]:
         """The (absorb a slots, squeeze s challenges) pairs of a single-circuit proof's transcript over its slots in order, from the
         counts ``transcript_challenges`` uses: advice | theta | 2L | beta, gamma | sets + L + 1 | y | pieces | x | evaluations | y', v
-        | [h] | u, and a last pair that absorbs [h'] behind the last challenge, as ``Blake2bRead`` does."""
-        pairs = [(self.cs.num_advice, 1), (2 * self.L, 2), (self.nsets + self.L + 1, 1), (self.pieces, 1), (self.n_scalars, 2), (1, 1), (1, 0)]
+        | [h] | u, and a last pair that absorbs [h'] behind the last challenge, as ``Blake2bRead`` does.  The counts are SLOTS: in an
+        "evm" layout a point counts twice."""
+        w = 2 if self.encoding == "evm" else 1
+        pairs = [(w * self.cs.num_advice, 1), (w * 2 * self.L, 2), (w * (self.nsets + self.L + 1), 1), (w * self.pieces, 1),
+                 (self.n_scalars, 2), (w, 1), (w, 0)]
         if sum(a for a, _ in pairs) != self.slots or sum(s for _, s in pairs) != len(RECORD):
             raise AssertionError("ProofLayout: the transcript's schedule does not cover the proof's slots and the eight challenges")
         return pairs
@@ -167,10 +186,25 @@ class ProofLayout:
 
 def read_proof_ints(layout: ProofLayout, proof: bytes):
     """The integer twin of the read kernel: (points, scalars) of ``proof`` in the layout's order -- points as (x, y) -- or
-    ``MalformedProof`` for a wrong length, a scalar >= r, an x >= p or off the curve, the all-zero point."""
+    ``MalformedProof`` for a wrong length, a scalar >= r, an x >= p or off the curve, the all-zero point.  An "evm" layout reads the
+    other encoding: a coordinate >= p, a point off the curve (the 64 zero bytes among them), a scalar >= r."""
     if len(proof) != 32 * layout.slots:
         raise MalformedProof("the proof has the wrong length")
     points, scalars = [], []
+    if layout.encoding == "evm":
+        for s in range(layout.slots):
+            entry = int(layout.slot_table[s])
+            if entry & EVM_POINT:
+                try:
+                    points.append(g1_uncompressed_int(proof[32 * s:32 * s + 64]))
+                except TranscriptError as e:
+                    raise MalformedProof(str(e)) from None
+            elif not entry & EVM_SKIP:
+                v = int.from_bytes(proof[32 * s:32 * s + 32], "big")
+                if v >= R:
+                    raise MalformedProof("scalar: not below r")
+                scalars.append(v)
+        return points, scalars
     for s in range(layout.slots):
         data = proof[32 * s:32 * s + 32]
         if layout.slot_table[s] & VR_POINT:
@@ -189,10 +223,28 @@ def read_proof_ints(layout: ProofLayout, proof: bytes):
     return points, scalars
 
 
-def transcript_challenges(layout: ProofLayout, vk_digest: int, inst_cols, proof: bytes, y_bytes: Sequence[bytes]) -> dict:
+def _keccak_challenges(layout: ProofLayout, vk_digest: int, inst_cols, proof: bytes) -> dict:
+    """``transcript_challenges`` of an "evm" layout: the preamble big-endian, then the proof's slots verbatim by the layout's schedule;
+    the buffer rules are ``transcript``'s"""
+    buf = bytearray(vk_digest.to_bytes(32, "big") + b"".join(int(v).to_bytes(32, "big") for values in inst_cols for v in values))
+    out, at = [], 0
+    for absorb, squeeze in layout.transcript_schedule():
+        buf += proof[at:at + 32 * absorb]
+        at += 32 * absorb
+        for _ in range(squeeze):
+            h = keccak256(bytes(buf) + (b"\x01" if len(buf) == 32 else b""))
+            buf = bytearray(h)
+            out.append(int.from_bytes(h, "big") % R)
+    return dict(zip(RECORD, out))
+
+
+def transcript_challenges(layout: ProofLayout, vk_digest: int, inst_cols, proof: bytes, y_bytes: Optional[Sequence[bytes]] = None) -> dict:
     """The Blake2b transcript of one proof, absorbed in the order of ``verifier._verify`` and ``shplonk.verify_opening``:
     ``y_bytes[j]`` the 32 canonical bytes of y of the proof's point j (x stands in the proof).  -> theta, beta, gamma, y, x and the
-    multiopen's y' (``y2``), v, u."""
+    multiopen's y' (``y2``), v, u.  With an "evm" layout the Keccak transcript, which absorbs the proof verbatim and takes no
+    ``y_bytes``."""
+    if layout.encoding == "evm":
+        return _keccak_challenges(layout, vk_digest, inst_cols, proof)
     st = hashlib.blake2b(digest_size=64, person=PERSONAL)
     slot = [0]
     point = [0]
@@ -485,7 +537,7 @@ def proof_terms_ints(vk: VerifyingKey, instance, proof: bytes, layout: Optional[
     layout = layout or ProofLayout(vk.cs, vk.domain.k)
     inst_cols = _instance_columns(vk.cs, instance)
     points, evals = read_proof_ints(layout, proof)
-    ch = transcript_challenges(layout, _vk_digest(vk), inst_cols, proof, [p[1].to_bytes(32, "little") for p in points])
+    ch = transcript_challenges(layout, _vk_digest(vk), inst_cols, proof, [p[1].to_bytes(32, "little") for p in points])   # y_bytes: "halo2" only
     own, shared = terms_from_challenges(layout, vk.domain.omega, inst_cols, evals, ch)
     return ch, own, shared, points
 
@@ -520,15 +572,20 @@ class BatchVerifier:
     ``transcript="device"`` runs the Blake2b transcripts on the GPU too (``device_transcript``): read, transcript and terms are queued
     on one stream with no wait and no copy between them, and the flags of the batch are the one download.  The same booleans, sums and
     ``failing()`` lists.  ``timings`` keeps its keys, but ``read``, ``transcript`` and ``terms`` are then the wall times of QUEUEING
-    each call -- the device's work surfaces in ``terms``, which ends with the download -- and only their sum means anything."""
+    each call -- the device's work surfaces in ``terms``, which ends with the download -- and only their sum means anything.
+    ``encoding="evm"`` takes proofs in the other wire format (``create_proof(..., encoding="evm")``): the device reads uncompressed
+    big-endian points with a curve check in place of the square root (``hm_verify_read_proofs_evm_dev``), the transcript is Keccak
+    (``hm_verify_transcript_evm_dev`` with ``transcript="device"``), and terms, sums and pairing are the same calls as before."""
 
-    def __init__(self, params, vk: VerifyingKey, seed=None, pairing: str = "host", transcript: str = "host"):
+    def __init__(self, params, vk: VerifyingKey, seed=None, pairing: str = "host", transcript: str = "host", encoding: str = "halo2"):
+        check_encoding(encoding, "BatchVerifier")
         if pairing not in device_pairing.MODES:
             raise ValueError(f"BatchVerifier: pairing must be one of {device_pairing.MODES}, got {pairing!r}")
         if transcript not in device_transcript.MODES:
             raise ValueError(f"BatchVerifier: transcript must be one of {device_transcript.MODES}, got {transcript!r}")
         self.params, self.vk, self.seed, self.pairing, self.transcript = params, vk, seed, pairing, transcript
-        self.layout = ProofLayout(vk.cs, vk.domain.k)
+        self.encoding = encoding
+        self.layout = ProofLayout(vk.cs, vk.domain.k, encoding)
         self._digest = _vk_digest(vk)
         self._shared = shared_points(vk, self.layout)
         # verify_proof opens no identity: with a queried fixed or sigma commitment that is one, no proof of this vk verifies
@@ -589,6 +646,20 @@ class BatchVerifier:
         except Exception:                                        # the library may be gone at interpreter shutdown
             pass
 
+    def _queue_read(self, d_proofs, d_table, d_bases, d_tail, d_ybytes, d_scalars, d_bad, stream) -> None:
+        """the read kernel of the layout's encoding on the current stream; ``d_ybytes`` is None for "evm", which has no such array"""
+        lay, B, lib = self.layout, d_proofs.shape[0], _lib.load()
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        if self.encoding == "evm":
+            _lib.check(lib.hm_verify_read_proofs_evm_dev(vp(d_proofs), B, ctypes.cast(vp(d_table), u32p), lay.slots, lay.own_points,
+                                                         lay.n_scalars, vp(d_bases), vp(d_tail), vp(d_scalars), ctypes.cast(vp(d_bad), u32p),
+                                                         stream))
+        else:
+            _lib.check(lib.hm_verify_read_proofs_dev(vp(d_proofs), B, ctypes.cast(vp(d_table), u32p), lay.slots, lay.own_points, lay.n_points,
+                                                     lay.n_scalars, vp(d_bases), vp(d_tail), vp(d_ybytes), vp(d_scalars),
+                                                     ctypes.cast(vp(d_bad), u32p), stream))
+
     def _prepare(self) -> dict:
         if self._state is not None:
             return self._state
@@ -610,16 +681,15 @@ class BatchVerifier:
         d_proofs = torch.from_numpy(raw).to(dev)
         d_table = torch.from_numpy(lay.slot_table.view(np.int32)).to(dev)     # uploaded once per batch: a device table, not a kernel argument
         d_bases = torch.zeros((B * own + n_shared + B, 8), dtype=torch.int64, device=dev)
-        d_ybytes = torch.zeros((B, lay.n_points, 32), dtype=torch.uint8, device=dev)
+        evm = self.encoding == "evm"
+        d_ybytes = None if evm else torch.zeros((B, lay.n_points, 32), dtype=torch.uint8, device=dev)
         d_scalars = torch.zeros((B, lay.n_scalars, 4), dtype=torch.int64, device=dev)
         d_bad = torch.zeros(B, dtype=torch.int32, device=dev)
         d_tail = d_bases[B * own + n_shared:]
-        _lib.check(lib.hm_verify_read_proofs_dev(vp(d_proofs), B, ctypes.cast(vp(d_table), ctypes.POINTER(ctypes.c_uint32)), lay.slots, own,
-                                                 lay.n_points, lay.n_scalars, vp(d_bases), vp(d_tail), vp(d_ybytes), vp(d_scalars),
-                                                 ctypes.cast(vp(d_bad), ctypes.POINTER(ctypes.c_uint32)), stream))
+        self._queue_read(d_proofs, d_table, d_bases, d_tail, d_ybytes, d_scalars, d_bad, stream)
         shared_words = np.stack([g1_words(p) for p in self._shared]).view(np.int64)
         d_bases[B * own:B * own + n_shared] = torch.from_numpy(shared_words).to(dev)
-        ybytes = d_ybytes.cpu().numpy()
+        ybytes = None if evm else d_ybytes.cpu().numpy()
         dev_bad = d_bad.cpu().numpy()
         t1 = time.perf_counter()
 
@@ -632,7 +702,8 @@ class BatchVerifier:
             bad[b] = bad[b] or bool(dev_bad[b])
             inst_rows[b] = plan.instance_row(self._instances[b])
             if not bad[b]:
-                ch = transcript_challenges(lay, self._digest, self._instances[b], self._proofs[b], [bytes(row) for row in ybytes[b]])
+                ch = transcript_challenges(lay, self._digest, self._instances[b], self._proofs[b],
+                                           None if evm else [bytes(row) for row in ybytes[b]])
                 records[b] = [ch[name] for name in RECORD] + [self._rand[b]]
         t2 = time.perf_counter()
         up = lambda rows: torch.from_numpy(fr_array(rows).view(np.int64)).to(dev)
@@ -678,22 +749,21 @@ class BatchVerifier:
         records = np.zeros((B, len(RECORD) + 1, 4), dtype=np.uint64)          # the challenges are the device's; r_b stands behind them
         records[:, len(RECORD)] = fr_array(self._rand)
         d_records, d_inst = torch.from_numpy(records.view(np.int64)).to(dev), up([plan.instance_row(inst) for inst in self._instances])
-        preamble = device_transcript.upload_preamble(self._digest, self._instances, dev)
+        preamble = device_transcript.upload_preamble(self._digest, self._instances, dev, self.encoding)
         d_proofs = torch.from_numpy(raw).to(dev)
         d_table = torch.from_numpy(lay.slot_table.view(np.int32)).to(dev)
         d_bad = torch.tensor([int(x) for x in bad], dtype=torch.int32, device=dev)   # the read kernel only ever sets a flag
         d_bases = torch.zeros((B * own + n_shared + B, 8), dtype=torch.int64, device=dev)
         shared_words = np.stack([g1_words(p) for p in self._shared]).view(np.int64)
         d_bases[B * own:B * own + n_shared] = torch.from_numpy(shared_words).to(dev)
-        d_ybytes = torch.zeros((B, lay.n_points, 32), dtype=torch.uint8, device=dev)
+        d_ybytes = None if self.encoding == "evm" else torch.zeros((B, lay.n_points, 32), dtype=torch.uint8, device=dev)
         d_scalars = torch.zeros((B, lay.n_scalars, 4), dtype=torch.int64, device=dev)
         d_own = torch.empty((B * own, 4), dtype=torch.int64, device=dev)
         d_shared = torch.empty((B, n_shared, 4), dtype=torch.int64, device=dev)
         d_h2_r, d_h2_l = torch.empty((B, 4), dtype=torch.int64, device=dev), torch.empty((B, 4), dtype=torch.int64, device=dev)
         d_tail = d_bases[B * own + n_shared:]
         t3 = time.perf_counter()
-        _lib.check(lib.hm_verify_read_proofs_dev(vp(d_proofs), B, ctypes.cast(vp(d_table), u32p), lay.slots, own, lay.n_points, lay.n_scalars,
-                                                 vp(d_bases), vp(d_tail), vp(d_ybytes), vp(d_scalars), ctypes.cast(vp(d_bad), u32p), stream))
+        self._queue_read(d_proofs, d_table, d_bases, d_tail, d_ybytes, d_scalars, d_bad, stream)
         t4 = time.perf_counter()
         device_transcript.challenges(lay, self._digest, self._instances, d_proofs, d_ybytes, d_bad, d_records, preamble=preamble, d_table=d_table)
         t5 = time.perf_counter()
@@ -796,13 +866,15 @@ class BatchVerifier:
 
 
 def verify_proofs(params, vk: VerifyingKey, instances, proofs, seed=None, trapdoor: int = None, pairing: str = "host",
-                  transcript: str = "host") -> bool:
+                  transcript: str = "host", encoding: str = "halo2") -> bool:
     """True when every ``proofs[i]`` is a valid single-circuit proof of ``vk`` for ``instances[i]``: one ``BatchVerifier``, one check
-    (``pairing`` / ``transcript``: where that check's pairing and the proofs' transcripts run, as on ``BatchVerifier``)"""
+    (``pairing`` / ``transcript``: where that check's pairing and the proofs' transcripts run, ``encoding``: the proofs' wire format,
+    as on ``BatchVerifier``)"""
+    check_encoding(encoding, "verify_proofs")
     instances, proofs = list(instances), list(proofs)
     if len(instances) != len(proofs):
         raise ValueError("verify_proofs: one instance per proof")
-    bv = BatchVerifier(params, vk, seed, pairing=pairing, transcript=transcript)
+    bv = BatchVerifier(params, vk, seed, pairing=pairing, transcript=transcript, encoding=encoding)
     for instance, proof in zip(instances, proofs):
         bv.add_proof(instance, proof)
     return bv.finalize(trapdoor)

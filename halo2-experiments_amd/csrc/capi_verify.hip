@@ -112,6 +112,58 @@ int hm_verify_transcript_dev(const void* d_proofs, size_t n_proofs, const uint32
                                (uint32_t*)d_records, record_elems, (hipStream_t)stream);
 } HM_API_CATCH("hm_verify_transcript_dev")
 
+// ---- the EVM encoding: Keccak-256, the uncompressed read and the transcripts of a batch (keccak.inc) ---------------------------------
+int hm_keccak256_dev(const void* d_msgs, size_t stride, const uint32_t* d_lens, size_t n, void* d_out, void* stream) try {
+  const std::string who = "hm_keccak256_dev";
+  if (!d_msgs || !d_lens || !d_out) return hm_fail(HM_ERR_BAD_ARG, who + ": null argument");
+  if (n == 0 || n > VERIFY_MAX_PROOFS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n <= 2^24");
+  if (stride == 0 || stride > 0xffffffffull) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= stride < 2^32");
+  if (((uintptr_t)d_lens | (uintptr_t)d_out) & 3u) return hm_fail(HM_ERR_BAD_ARG, who + ": d_lens / d_out is not 4-byte aligned");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return keccak256_run((const uint8_t*)d_msgs, stride, d_lens, n, (uint32_t*)d_out, (hipStream_t)stream);
+} HM_API_CATCH("hm_keccak256_dev")
+
+int hm_verify_read_proofs_evm_dev(const void* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots, uint32_t own_points,
+                                  uint32_t scalars, void* d_points_xy, void* d_tail_xy, void* d_scalars, uint32_t* d_bad, void* stream) try {
+  const std::string who = "hm_verify_read_proofs_evm_dev";
+  if (!d_proofs || !d_slot_table || !d_points_xy || !d_tail_xy || !d_scalars || !d_bad) return hm_fail(HM_ERR_BAD_ARG, who + ": null argument");
+  if (n_proofs == 0 || n_proofs > VERIFY_MAX_PROOFS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n_proofs <= 2^24");
+  if (slots == 0 || slots > VERIFY_MAX_SLOTS || 2 * (uint64_t)own_points + scalars > slots)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= slots <= 2^16 and 2 own_points + scalars <= slots");
+  if (((uintptr_t)d_proofs | (uintptr_t)d_points_xy | (uintptr_t)d_tail_xy | (uintptr_t)d_scalars) & 15u)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": a buffer is not 16-byte aligned");
+  if (((uintptr_t)d_slot_table | (uintptr_t)d_bad) & 3u) return hm_fail(HM_ERR_BAD_ARG, who + ": d_slot_table / d_bad is not 4-byte aligned");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return verify_read_evm_run((const uint32_t*)d_proofs, n_proofs, d_slot_table, slots, own_points, scalars, (uint32_t*)d_points_xy,
+                             (uint32_t*)d_tail_xy, (uint32_t*)d_scalars, d_bad, (hipStream_t)stream);
+} HM_API_CATCH("hm_verify_read_proofs_evm_dev")
+
+int hm_verify_transcript_evm_dev(const void* d_proofs, size_t n_proofs, uint32_t slots, const void* d_preamble,
+                                 const uint32_t* d_preamble_counts, uint32_t preamble_stride, const uint32_t* schedule,
+                                 size_t n_schedule_pairs, uint32_t* d_bad_in_out, void* d_records, uint32_t record_elems, void* stream) try {
+  const std::string who = "hm_verify_transcript_evm_dev";
+  if (!d_proofs || !d_preamble || !d_preamble_counts || !schedule || !d_bad_in_out || !d_records)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": null argument");
+  if (n_proofs == 0 || n_proofs > VERIFY_MAX_PROOFS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n_proofs <= 2^24");
+  if (slots == 0 || slots > VERIFY_MAX_SLOTS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= slots <= 2^16");
+  if (preamble_stride == 0 || preamble_stride > VERIFY_MAX_SLOTS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= preamble_stride <= 2^16");
+  if (record_elems == 0 || record_elems > VERIFY_MAX_SLOTS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= record_elems <= 2^16");
+  if (n_schedule_pairs == 0 || n_schedule_pairs > VERIFY_MAX_SLOTS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n_schedule_pairs <= 2^16");
+  if (((uintptr_t)d_proofs | (uintptr_t)d_preamble | (uintptr_t)d_records) & 15u)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": a buffer is not 16-byte aligned");
+  if (((uintptr_t)d_preamble_counts | (uintptr_t)d_bad_in_out) & 3u)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": d_preamble_counts / d_bad_in_out is not 4-byte aligned");
+  if (const char* why = tr_schedule_problem(schedule, n_schedule_pairs, slots, record_elems)) return hm_fail(HM_ERR_BAD_ARG, why);
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return verify_transcript_evm_run(*ctx, (const uint32_t*)d_proofs, n_proofs, slots, (const uint32_t*)d_preamble, d_preamble_counts,
+                                   preamble_stride, schedule, n_schedule_pairs, d_bad_in_out, (uint32_t*)d_records, record_elems,
+                                   (hipStream_t)stream);
+} HM_API_CATCH("hm_verify_transcript_evm_dev")
+
 // ---- pairing product checks (pairing.inc, lookup.hip) ------------------------------------------------------------------------------
 static constexpr size_t PAIRING_MAX_CHECKS = (size_t)1 << 20, PAIRING_MAX_PAIRS = (size_t)1 << 24;
 

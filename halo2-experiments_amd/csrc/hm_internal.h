@@ -597,6 +597,13 @@ int verify_transcript_run(DeviceCtx& ctx, const uint32_t* d_proofs, size_t n_pro
                           uint32_t n_points, const uint32_t* d_ybytes, const uint32_t* d_preamble, const uint32_t* d_counts, uint32_t stride,
                           const uint32_t* schedule, size_t n_pairs, uint32_t* d_bad, uint32_t* d_records, uint32_t record_elems,
                           hipStream_t stream);
+// Keccak-256 and the EVM encoding's read and transcripts (keccak.inc), as their Blake2b and compressed siblings above
+int keccak256_run(const uint8_t* d_msgs, size_t stride, const uint32_t* d_lens, size_t n, uint32_t* d_out, hipStream_t stream);
+int verify_read_evm_run(const uint32_t* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots, uint32_t own_points,
+                        uint32_t n_scalars, uint32_t* d_points, uint32_t* d_tail, uint32_t* d_scalars, uint32_t* d_bad, hipStream_t stream);
+int verify_transcript_evm_run(DeviceCtx& ctx, const uint32_t* d_proofs, size_t n_proofs, uint32_t slots, const uint32_t* d_preamble,
+                              const uint32_t* d_counts, uint32_t stride, const uint32_t* schedule, size_t n_pairs, uint32_t* d_bad,
+                              uint32_t* d_records, uint32_t record_elems, hipStream_t stream);
 
 // pairing.hip: the Miller loops of n_pairs pairs, then product and final exponentiation of n_checks checks, in d_work
 // (pairing_work_words u32 words); both launches asynchronous on `stream`

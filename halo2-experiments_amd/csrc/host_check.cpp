@@ -28,6 +28,7 @@ namespace hm {
 #include "shplonk.inc"    // the SHPLONK set quotient's plan, coefficients and row formula (polyops.hip)
 #include "pairing.inc"    // the pairing's tower, Miller lane and final exponentiation (pairing.hip)
 #include "transcript.inc" // Blake2b-512, its streaming absorber and the transcript lane of a proof (verify.hip)
+#include "keccak.inc"     // Keccak-256, the EVM encoding's read and the transcript lane of such a proof (verify.hip)
 }
 
 using namespace hm;
@@ -722,6 +723,58 @@ void hc_verify_transcript(size_t b, const uint32_t* proofs, const uint32_t* slot
 }
 const char* hc_transcript_schedule_problem(const uint32_t* schedule, size_t n_pairs, uint32_t slots, uint32_t record_elems) {
   return tr_schedule_problem(schedule, n_pairs, slots, record_elems);
+}
+
+// Keccak-256 and the EVM encoding (keccak.inc), the exact lane code of its kernels on a block of 34 host words.
+//   hc_keccak256: n messages at a byte stride -> n x 32 digest bytes, with the padding's domain byte as given (0x01 Keccak, 0x06 SHA-3).
+//   hc_keccak_stream: ops[i] = 0 a squeeze (kc_squeeze_restart: 32 digest bytes to `digests`), 1 a word of 32 bytes absorbed (8 words
+//     of `data`); positions[i] = the bytes in the block after op i.
+//   hc_keccak_challenge: n digests of 32 bytes -> n x 8 Montgomery words of the big-endian integer mod r.
+//   hc_evm_read: evm_read_slot on every slot of one proof -> 1 when every slot was read, 0 otherwise.
+//   hc_verify_transcript_evm: evm_proof_one on proof b of a batch, arguments as hm_verify_transcript_evm_dev's (all host memory).
+void hc_keccak256(const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t n, uint32_t domain, uint8_t* out) {
+  for (size_t i = 0; i < n; ++i) {
+    uint32_t block[KC_BLOCK_WORDS] = {0}, digest[8];
+    kc_hash_lane(KcBuf{block, 1}, msgs + i * stride, lens[i], domain, digest);
+    std::memcpy(out + 32 * i, digest, 32);
+  }
+}
+void hc_keccak_stream(const uint8_t* ops, size_t n_ops, const uint32_t* data, uint8_t* digests, uint32_t* positions) {
+  uint32_t block[KC_BLOCK_WORDS] = {0};
+  const KcBuf buf{block, 1};
+  KcState s;
+  kc_init(s);
+  for (size_t i = 0; i < n_ops; ++i) {
+    if (ops[i]) {
+      for (int k = 0; k < 8; ++k) kc_push_word(s, buf, *data++);
+    } else {
+      uint32_t d[8];
+      kc_squeeze_restart(s, buf, d);
+      std::memcpy(digests, d, 32);
+      digests += 32;
+    }
+    positions[i] = s.pos;
+  }
+}
+void hc_keccak_challenge(const uint8_t* digests, size_t n, uint32_t* out) {
+  for (size_t i = 0; i < n; ++i) {
+    uint32_t d[8], w[8];
+    std::memcpy(d, digests + 32 * i, 32);
+    kc_challenge(d, w);
+    std::memcpy(out + 8 * i, w, 32);
+  }
+}
+int hc_evm_read(const uint32_t* proof, const uint32_t* slot_table, uint32_t slots, uint32_t own_points, uint32_t scalars, uint32_t* points,
+                uint32_t* tail, uint32_t* out_scalars) {
+  int ok = 1;
+  for (uint32_t s = 0; s < slots; ++s)
+    if (!evm_read_slot(proof, s, slots, slot_table[s], own_points, scalars, points, tail, out_scalars)) ok = 0;
+  return ok;
+}
+void hc_verify_transcript_evm(size_t b, const uint32_t* proofs, uint32_t slots, const uint32_t* preamble, const uint32_t* counts, uint32_t stride,
+                              const uint32_t* schedule, uint32_t n_pairs, uint32_t* bad, uint32_t* records, uint32_t record_elems) {
+  uint32_t block[KC_BLOCK_WORDS] = {0};
+  evm_proof_one(KcBuf{block, 1}, b, proofs, slots, preamble, counts, stride, schedule, n_pairs, bad, records, record_elems);
 }
 
 // The batch verifier's terms (verify_terms.inc) for ONE proof, the exact lane code of its kernel on a workspace of one lane: phase a,

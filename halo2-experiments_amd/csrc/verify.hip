@@ -2,6 +2,8 @@
 //   verify_read_run, verify_colsum_run    a batch of proofs read slot by slot, the column sums of its shared scalars (verify_read.inc)
 //   verify_terms_run                      the per-proof terms of the opening checks, one lane per proof (verify_terms.inc)
 //   blake2b_run, verify_transcript_run    Blake2b-512 and the proofs' transcripts on it, one lane per proof (transcript.inc)
+//   keccak256_run, verify_read_evm_run,   Keccak-256, and the read and the transcripts of proofs in the EVM encoding: uncompressed
+//   verify_transcript_evm_run             big-endian points, a Keccak transcript that absorbs the proof verbatim (keccak.inc)
 // The .inc files hold the per-slot, per-proof and per-message functions, the plan's and the schedule's checks: host_check.cpp and
 // capi_verify.hip compile them too.
 #include <hip/hip_runtime.h>
@@ -20,6 +22,7 @@ namespace hm {
 #include "verify_read.inc"
 #include "verify_terms.inc"
 #include "transcript.inc"
+#include "keccak.inc"
 
 // ---- the read and the column sums ------------------------------------------------------------
 __device__ __forceinline__ void vr_load8(const uint32_t* __restrict__ p, uint32_t (&w)[8]) {
@@ -257,6 +260,82 @@ int verify_transcript_run(DeviceCtx& ctx, const uint32_t* d_proofs, size_t n_pro
   hipLaunchKernelGGL(verify_transcript_kernel, dim3((uint32_t)((n_proofs + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, stream, d_proofs,
                      (uint32_t)n_proofs, d_slot_table, slots, n_points, d_ybytes, d_preamble, d_counts, stride, (const uint32_t*)d_sched,
                      (uint32_t)n_pairs, d_bad, d_records, record_elems);
+  HM_HIP_CHECK(hipGetLastError());
+  return aux_release(ctx, slot, stream);
+}
+
+// ---- the EVM encoding: Keccak-256, the uncompressed read, the transcripts ---------------------
+__global__ __launch_bounds__(KC_THREADS) void keccak256_kernel(const uint8_t* __restrict__ msgs, uint64_t stride, const uint32_t* __restrict__ lens,
+                                                               uint64_t n, uint32_t* __restrict__ out) {
+  __shared__ uint32_t block[KC_BLOCK_WORDS][KC_THREADS];
+  const uint64_t i = (uint64_t)blockIdx.x * KC_THREADS + threadIdx.x;
+  if (i >= n) return;
+  uint32_t* digest = out + i * 8;
+  const uint32_t len = lens[i];
+  if (len > stride) {                                            // a length that leaves the message's room: zeros, nothing read
+#pragma unroll
+    for (int k = 0; k < 8; ++k) digest[k] = 0;
+    return;
+  }
+  kc_hash_lane(KcBuf{&block[0][threadIdx.x], KC_THREADS}, msgs + i * stride, len, KC_DOMAIN, digest);
+}
+
+__global__ __launch_bounds__(ACC_THREADS) void verify_read_evm_kernel(const uint32_t* __restrict__ proofs, const uint32_t* __restrict__ slot_table,
+                                                                      uint32_t slots, uint64_t lanes, uint32_t own_points, uint32_t n_scalars,
+                                                                      uint32_t* __restrict__ points, uint32_t* __restrict__ tail,
+                                                                      uint32_t* __restrict__ scalars, uint32_t* __restrict__ bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * ACC_THREADS + threadIdx.x;
+  if (i >= lanes) return;
+  const uint64_t b = i / slots;
+  const uint32_t slot = (uint32_t)(i - b * slots);
+  if (!evm_read_slot(proofs + b * slots * 8, slot, slots, slot_table[slot], own_points, n_scalars, points + b * own_points * 16, tail + b * 16,
+                     scalars + b * n_scalars * 8))
+    atomicOr(bad + b, 1u);
+}
+
+__global__ __launch_bounds__(KC_THREADS) void verify_transcript_evm_kernel(const uint32_t* __restrict__ proofs, uint32_t n_proofs, uint32_t slots,
+                                                                           const uint32_t* __restrict__ preamble,
+                                                                           const uint32_t* __restrict__ counts, uint32_t stride,
+                                                                           const uint32_t* __restrict__ sched, uint32_t n_pairs,
+                                                                           uint32_t* __restrict__ bad, uint32_t* __restrict__ records,
+                                                                           uint32_t record_elems) {
+  __shared__ uint32_t block[KC_BLOCK_WORDS][KC_THREADS];
+  const uint32_t b = blockIdx.x * KC_THREADS + threadIdx.x;
+  if (b >= n_proofs) return;
+  evm_proof_one(KcBuf{&block[0][threadIdx.x], KC_THREADS}, b, proofs, slots, preamble, counts, stride, sched, n_pairs, bad, records, record_elems);
+}
+
+// the arguments were checked by the caller (capi_verify.hip)
+int keccak256_run(const uint8_t* d_msgs, size_t stride, const uint32_t* d_lens, size_t n, uint32_t* d_out, hipStream_t stream) {
+  hipLaunchKernelGGL(keccak256_kernel, dim3((uint32_t)((n + KC_THREADS - 1) / KC_THREADS)), dim3(KC_THREADS), 0, stream, d_msgs, (uint64_t)stride,
+                     d_lens, (uint64_t)n, d_out);
+  HM_HIP_CHECK(hipGetLastError());
+  return HM_OK;
+}
+
+int verify_read_evm_run(const uint32_t* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots, uint32_t own_points,
+                        uint32_t n_scalars, uint32_t* d_points, uint32_t* d_tail, uint32_t* d_scalars, uint32_t* d_bad, hipStream_t stream) {
+  const uint64_t lanes = (uint64_t)n_proofs * slots;
+  if (lanes == 0) return HM_OK;
+  hipLaunchKernelGGL(verify_read_evm_kernel, dim3((uint32_t)((lanes + ACC_THREADS - 1) / ACC_THREADS)), dim3(ACC_THREADS), 0, stream, d_proofs,
+                     d_slot_table, slots, lanes, own_points, n_scalars, d_points, d_tail, d_scalars, d_bad);
+  HM_HIP_CHECK(hipGetLastError());
+  return HM_OK;
+}
+
+int verify_transcript_evm_run(DeviceCtx& ctx, const uint32_t* d_proofs, size_t n_proofs, uint32_t slots, const uint32_t* d_preamble,
+                              const uint32_t* d_counts, uint32_t stride, const uint32_t* schedule, size_t n_pairs, uint32_t* d_bad,
+                              uint32_t* d_records, uint32_t record_elems, hipStream_t stream) {
+  if (const char* why = tr_schedule_problem(schedule, n_pairs, slots, record_elems)) return hm_fail(HM_ERR_BAD_ARG, why);
+  AuxSlot* slot = aux_acquire(ctx, stream);
+  if (!slot) return HM_ERR_HIP;
+  uint32_t* d_sched = (uint32_t*)slot->args.ensure(n_pairs * 8);
+  if (!d_sched) return hm_fail(HM_ERR_HIP, "verify transcript: schedule allocation failed");
+  // pageable source: the runtime has taken its copy of the schedule when this returns (as the terms plan)
+  HM_HIP_CHECK(hipMemcpyAsync(d_sched, schedule, n_pairs * 8, hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(verify_transcript_evm_kernel, dim3((uint32_t)((n_proofs + KC_THREADS - 1) / KC_THREADS)), dim3(KC_THREADS), 0, stream,
+                     d_proofs, (uint32_t)n_proofs, slots, d_preamble, d_counts, stride, (const uint32_t*)d_sched, (uint32_t)n_pairs, d_bad,
+                     d_records, record_elems);
   HM_HIP_CHECK(hipGetLastError());
   return aux_release(ctx, slot, stream);
 }

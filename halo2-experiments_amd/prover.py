@@ -54,7 +54,7 @@ from .domain import FR_MODULUS, FR_ZETA, fr_words
 from .keygen import FR_DELTA, ProvingKey, VerifyingKey
 from .poseidon import ints_to_words, words_to_ints
 from .shplonk import create_opening, create_openings, g1_words_to_int
-from .transcript import Blake2bWrite
+from .transcript import WRITERS, check_encoding
 
 R = FR_MODULUS
 
@@ -153,11 +153,13 @@ MAX_CIRCUITS = 64                   # the circuit's number sits in the 6 seed bi
 H_COLUMN_BUDGET = 2 << 30           # bytes of per-circuit extended columns in flight in the h step (the witness writers' 2 GiB)
 
 
-def create_proof(params, pk: ProvingKey, advice, instance, seed: int, _trace: dict = None) -> bytes:
+def create_proof(params, pk: ProvingKey, advice, instance, seed: int, _trace: dict = None, encoding: str = "halo2") -> bytes:
     """The proof bytes for the witness ``advice`` -- the (num_advice, n, 4) device tensor a witness writer returns for one circuit --
     and its ``instance`` values.  One circuit per proof: a list of several witnesses, or a 4-dimensional tensor holding more than
     one, raises ValueError (``create_proof_multi`` takes several).  ``_trace``: a dict that receives the committed polynomials and
-    their commitments (tests)."""
+    their commitments (tests).  ``encoding``: "halo2" -- Blake2b transcript, compressed points, little-endian scalars -- or "evm" --
+    Keccak transcript, uncompressed big-endian points and scalars (``transcript`` states both); the protocol is the same."""
+    check_encoding(encoding, "create_proof")
     if isinstance(advice, (list, tuple)):
         if len(advice) != 1:
             raise ValueError("create_proof: one circuit per proof (create_proof_multi proves several)")
@@ -167,7 +169,7 @@ def create_proof(params, pk: ProvingKey, advice, instance, seed: int, _trace: di
             raise ValueError("create_proof: one circuit per proof (create_proof_multi proves several)")
         advice = advice[0]
     trace = None if _trace is None else {}
-    proof = _create_proof("create_proof", params, pk, [advice], [instance], seed, trace)
+    proof = _create_proof("create_proof", params, pk, [advice], [instance], seed, trace, encoding)
     if _trace is not None:                                 # one circuit: its keys without the circuit's number
         strip = lambda key: key[:2] if len(key) == 3 else key
         lag = trace["lagrange"]
@@ -197,7 +199,7 @@ def create_proof_multi(params, pk: ProvingKey, advice, instances, seed: int, _tr
     return _create_proof("create_proof_multi", params, pk, advice, list(instances), seed, _trace)
 
 
-def _create_proof(who, params, pk, advice, instances, seed, _trace) -> bytes:
+def _create_proof(who, params, pk, advice, instances, seed, _trace, encoding: str = "halo2") -> bytes:
     import torch
 
     m = len(advice)
@@ -250,7 +252,7 @@ def _create_proof(who, params, pk, advice, instances, seed, _trace) -> bytes:
     fixed = pk.fixed_values
     table = [fixed[i] for i in range(cs.num_fixed)] + [adv[i] for i in range(A)] + [inst[i] for i in range(I)]
 
-    transcript = Blake2bWrite()
+    transcript = WRITERS[encoding]()
     transcript.common_scalar(vk_digest(vk))
     for c in range(m):
         for values in inst_cols[c]:
@@ -427,13 +429,14 @@ def _create_proof(who, params, pk, advice, instances, seed, _trace) -> bytes:
     return transcript.finalize()
 
 
-def create_proofs(params, pk: ProvingKey, advice, instances, seeds) -> list:
+def create_proofs(params, pk: ProvingKey, advice, instances, seeds, encoding: str = "halo2") -> list:
     """m independent proofs of ``pk``'s constraint system in one batched pass: ``create_proofs(...)[b] == create_proof(params, pk,
     advice[b], instances[b], seeds[b])``, byte for byte.  ``advice``: the (m, num_advice, n, 4) GPU tensor a witness writer returns, or
     a list of m (num_advice, n, 4) tensors; ``instances``: m entries, each in the form ``create_proof`` takes; ``seeds``: m integers,
     pairwise distinct mod 2^48 (two proofs with one seed would share their blinding: ValueError), or ONE integer s standing for
-    s, s + 1, ...  m >= 1, no upper limit."""
+    s, s + 1, ...  m >= 1, no upper limit.  ``encoding``: as in ``create_proof``."""
     who = "create_proofs"
+    check_encoding(encoding, who)
     if _is_tensor(advice):
         if advice.dim() != 4:
             raise ValueError(f"{who}: advice must be a (m, num_advice, n, 4) GPU tensor or a list of m (num_advice, n, 4) tensors")
@@ -453,10 +456,10 @@ def create_proofs(params, pk: ProvingKey, advice, instances, seeds) -> list:
         raise ValueError(f"{who}: {m} proof(s) need {m} seeds")
     if len({s & 0xFFFFFFFFFFFF for s in seeds}) != m:
         raise ValueError(f"{who}: the seeds must be pairwise distinct mod 2^48 (two proofs would share their blinding)")
-    return _create_proofs(who, params, pk, advice, list(instances), seeds)
+    return _create_proofs(who, params, pk, advice, list(instances), seeds, encoding)
 
 
-def _create_proofs(who, params, pk, advice, instances, seeds) -> list:
+def _create_proofs(who, params, pk, advice, instances, seeds, encoding: str = "halo2") -> list:
     """The protocol of ``_create_proof`` (module docstring, steps 1 - 14) for m transcripts of one circuit each; the comments name the
     step.  What belongs to proof b carries b where ``_create_proof`` carries the circuit's number; the key inside a proof is circuit 0's."""
     import torch
@@ -514,7 +517,7 @@ def _create_proofs(who, params, pk, advice, instances, seeds) -> list:
     table = [fixed[i] for i in range(cs.num_fixed)] + [adv[i] for i in range(A)] + [inst[i] for i in range(I)]
 
     digest = vk_digest(vk)
-    transcripts = [Blake2bWrite() for _ in every]
+    transcripts = [WRITERS[encoding]() for _ in every]
     for b, tr in enumerate(transcripts):
         tr.common_scalar(digest)
         for values in inst_cols[b]:

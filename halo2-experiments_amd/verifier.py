@@ -17,7 +17,7 @@ from .keygen import FR_DELTA, VerifyingKey
 from .kzg import g2_from_bytes
 from .pairing import g1_add, g1_mul, g1_neg, g1_on_curve, pairing_check
 from .shplonk import g1_words_to_int, verify_opening
-from .transcript import Blake2bRead, TranscriptError
+from .transcript import READERS, TranscriptError, check_encoding
 
 R = FR_MODULUS
 
@@ -35,13 +35,15 @@ def _vk_digest(vk: VerifyingKey) -> int:
     return int.from_bytes(hsh.digest(), "little") % R
 
 
-def proof_length(cs, circuits: int = 1) -> int:
-    """the bytes of a proof of ``circuits`` circuits of ``cs``, counted from the constraint system: 32 per point and per scalar"""
+def proof_length(cs, circuits: int = 1, encoding: str = "halo2") -> int:
+    """the bytes of a proof of ``circuits`` circuits of ``cs``, counted from the constraint system: 32 per point and per scalar, or
+    with ``encoding="evm"`` 64 per point and 32 per scalar"""
+    check_encoding(encoding, "proof_length")
     adv_q, fix_q, _ = cs.queries()
     P, nsets, L = len(cs.equality), cs.permutation_sets(), len(cs.lookups)
     points = circuits * (cs.num_advice + 2 * L + nsets + L) + 1 + (cs.degree() - 1) + 2
     scalars = circuits * (len(adv_q) + (3 * nsets - 1 if nsets else 0) + 5 * L) + len(fix_q) + 1 + P
-    return 32 * (points + scalars)
+    return 32 * ((2 if encoding == "evm" else 1) * points + scalars)
 
 
 def evaluate_expression(e, leaf, scalars) -> int:
@@ -75,12 +77,14 @@ def _instance_columns(cs, instance):
     return [[int(v) % R for v in c] for c in cols]
 
 
-def verify_proof(params, vk: VerifyingKey, instance, proof: bytes, trapdoor: int = None) -> bool:
+def verify_proof(params, vk: VerifyingKey, instance, proof: bytes, trapdoor: int = None, encoding: str = "halo2") -> bool:
     """True when ``proof`` is a valid proof of ``vk``'s circuit for ``instance`` (a list of integers for a one-column system, or one
     list per instance column).  ``params`` needs ``g2`` / ``s_g2`` only.  A malformed proof -- short or long, a point off the curve, a
-    scalar not below r -- is False, not an exception."""
+    scalar not below r -- is False, not an exception.  ``encoding``: the proof's wire format, as ``create_proof`` names it; a proof
+    in the other one is a malformed proof."""
+    check_encoding(encoding, "verify_proof")
     try:
-        return _verify(params, vk, [instance], proof, trapdoor)
+        return _verify(params, vk, [instance], proof, trapdoor, encoding)
     except TranscriptError:
         return False
 
@@ -96,17 +100,17 @@ def verify_proof_multi(params, vk: VerifyingKey, instances, proof: bytes, trapdo
         return False
 
 
-def _verify(params, vk, instances, proof, trapdoor) -> bool:
+def _verify(params, vk, instances, proof, trapdoor, encoding: str = "halo2") -> bool:
     cs, dom = vk.cs, vk.domain
     n, omega, blinding = 1 << dom.k, dom.omega, cs.blinding_factors
     P, chunk, nsets, L = len(cs.equality), cs.permutation_chunk_len(), cs.permutation_sets(), len(cs.lookups)
     deg, last = cs.degree(), -(blinding + 1)
     m = len(instances)
-    if m < 1 or len(proof) != proof_length(cs, m):
+    if m < 1 or len(proof) != proof_length(cs, m, encoding):
         return False
     inst_cols = [_instance_columns(cs, instance) for instance in instances]
     M = range(m)
-    t = Blake2bRead(proof)
+    t = READERS[encoding](proof)
     t.common_scalar(_vk_digest(vk))
     for c in M:
         for values in inst_cols[c]:

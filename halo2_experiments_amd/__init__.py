@@ -33,7 +33,7 @@ from .solvency import BalanceProof, prove_balances, user_openings, verify_balanc
 from .synthesis import (MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, RangeCheckLayout, merkle_sum_witness,  # noqa: F401
                         merkle_sum_witness_host, merkle_witness, merkle_witness_host, permutation_columns, poseidon_circuit_witness,
                         poseidon_circuit_witness_host, range_c_layout, range_witness, range_witness_host)
-from .transcript import Blake2bRead, Blake2bWrite  # noqa: F401
+from .transcript import Blake2bRead, Blake2bWrite, KeccakRead, KeccakWrite, keccak256  # noqa: F401
 from .verifier import verify_proof, verify_proof_multi  # noqa: F401
 
 __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_multiexp_submit", "best_multiexp_wait", "best_fft",
@@ -45,7 +45,7 @@ __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_mult
            "merkle_sum_witness_host", "permutation_columns", "MerkleTreeV3Layout", "PoseidonCircuitLayout", "merkle_witness",
            "merkle_witness_host", "poseidon_circuit_witness", "poseidon_circuit_witness_host", "copy_pairs", "permutation_cells_dev",
            "permutation_columns_dev", "keygen_vk", "keygen_pk", "VerifyingKey", "ProvingKey",
-           "create_proof", "create_proof_multi", "create_proofs", "verify_proof", "verify_proof_multi", "Blake2bWrite", "Blake2bRead", "pairing_check", "construct_intermediate_sets",
+           "create_proof", "create_proof_multi", "create_proofs", "verify_proof", "verify_proof_multi", "Blake2bWrite", "Blake2bRead", "KeccakWrite", "KeccakRead", "keccak256", "pairing_check", "construct_intermediate_sets",
            "set_quotient", "set_quotient_batch", "set_quotient_ints", "create_openings", "linear_combination_batch", "MockProver", "MockResult", "NotSatisfied", "BatchVerifier", "verify_proofs",
            "OpeningTable", "open_all", "open_all_ints", "open_at", "verify_opening", "verify_openings",
            "RangeCheckLayout", "range_witness", "range_witness_host", "range_c_layout", "BalanceProof", "prove_balances", "verify_balances",

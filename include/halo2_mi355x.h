@@ -860,6 +860,48 @@ int hm_verify_transcript_dev(const void* d_proofs, size_t n_proofs, const uint32
                              const void* d_y_bytes, const void* d_preamble, const uint32_t* d_preamble_counts, uint32_t preamble_stride,
                              const uint32_t* schedule, size_t n_schedule_pairs, uint32_t* d_bad_in_out, void* d_records,
                              uint32_t record_elems, void* stream);
+/* The same three steps for proofs in the EVM encoding (snark-verifier's EvmTranscript, as recalled: csrc/keccak.inc and transcript.py
+ * state the rules): a point stands uncompressed, x then y, 32 big-endian canonical bytes each, a scalar as 32 big-endian bytes, and
+ * the transcript is Keccak-256 over the proof's own bytes.
+ *
+ * Keccak-256 (Keccak-f[1600], rate 136, padding byte 0x01 -- Ethereum's, not SHA-3's 0x06 --, 32-byte digest), one lane per message:
+ * message i is the d_lens[i] bytes at d_msgs + i * stride (DEVICE memory, any alignment; d_lens: n u32, DEVICE memory); d_out: n x 32
+ * digest bytes (DEVICE memory, 4-byte aligned).  A message whose length is above `stride` gets 32 zero bytes and nothing of it is
+ * read.  Asynchronous on `stream`.  HM_ERR_BAD_ARG, with nothing launched: NULL arguments, n 0 or above 2^24, stride 0 or above
+ * 2^32 - 1, d_lens or d_out not 4-byte aligned.
+ *
+ * read: as hm_verify_read_proofs_dev, one lane per (proof, 32-byte slot), on a table of its own kind (DEVICE memory, one u32 per
+ * slot): bit 31 set on the x slot of a point, whose y is the next slot -- bits 0 .. 28 the point's index among the proof's own
+ * points, or bit 30 for the tail --; bit 29 set on a y slot, which the lane of its x slot reads; neither set on a scalar, bits 0 ..
+ * 28 its index.  A point is byte-reversed, both coordinates checked below p and the point on y^2 = x^3 + 3 (no square root), and
+ * written as 8 u64 affine Montgomery words to row b * own_points + index of d_points_xy, or to row b of d_tail_xy; a scalar is
+ * byte-reversed, checked below r and written as 4 Montgomery words to row b * scalars + index of d_scalars: bit for bit what
+ * hm_verify_read_proofs_dev leaves for the same points and scalars.  There is no d_y_bytes.  A slot that cannot be read -- a
+ * coordinate >= p, a point off the curve (the 64 zero bytes are one), a scalar >= r -- sets d_bad[b] and leaves zeros; a table entry
+ * outside its array (a point index >= own_points without bit 30, a scalar index >= scalars, an x slot that is the proof's last)
+ * sets d_bad[b], and nothing is read or written for it.  Asynchronous on `stream`.  HM_ERR_BAD_ARG, with nothing launched: NULL
+ * arguments, n_proofs 0 or above 2^24, slots 0 or above 2^16, 2 own_points + scalars > slots, a buffer that is not aligned (d_proofs,
+ * d_points_xy, d_tail_xy, d_scalars 16-byte; the u32 arrays 4-byte).
+ *
+ * transcript: one lane per proof.  Proof b absorbs d_preamble_counts[b] words from row b of d_preamble (n_proofs x preamble_stride x
+ * 32 BIG-endian bytes: the digest of the verifying key, then the instance values), then walks `schedule` (HOST memory, pairs of u32:
+ * absorb a slots, then squeeze s challenges; checked as hm_verify_transcript_dev checks its own) over its slots in order; a slot is
+ * absorbed as the 32 bytes that stand in the proof.  A squeeze appends one byte 0x01 if and only if exactly 32 bytes were absorbed
+ * since the last squeeze (the previous digest counts), pads, permutes, and restarts the sponge with the 32 digest bytes as its first
+ * bytes; the digest, a big-endian integer, is reduced mod r.  Challenge j goes to element j of row b of d_records (n_proofs x
+ * record_elems x 4 Montgomery words); the elements behind the schedule's challenges are left alone.  A proof whose d_bad_in_out[b] is
+ * set on entry is not hashed and gets zero challenges; a preamble count above preamble_stride sets d_bad_in_out[b] with zero
+ * challenges, and nothing is read outside the arrays.  The call needs nothing hm_verify_read_proofs_evm_dev writes but the flags, so
+ * it may be queued before it.  All DEVICE memory but the schedule; d_proofs, d_preamble, d_records 16-byte aligned, the u32 arrays
+ * 4-byte.  Asynchronous on `stream`.  HM_ERR_BAD_ARG, with nothing launched: NULL arguments, n_proofs 0 or above 2^24, slots,
+ * preamble_stride, record_elems or n_schedule_pairs 0 or above 2^16, a schedule whose absorbed slots do not sum to `slots` or whose
+ * squeezes exceed record_elems, a buffer that is not aligned. */
+int hm_keccak256_dev(const void* d_msgs, size_t stride, const uint32_t* d_lens, size_t n, void* d_out, void* stream);
+int hm_verify_read_proofs_evm_dev(const void* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots, uint32_t own_points,
+                                  uint32_t scalars, void* d_points_xy, void* d_tail_xy, void* d_scalars, uint32_t* d_bad, void* stream);
+int hm_verify_transcript_evm_dev(const void* d_proofs, size_t n_proofs, uint32_t slots, const void* d_preamble,
+                                 const uint32_t* d_preamble_counts, uint32_t preamble_stride, const uint32_t* schedule,
+                                 size_t n_schedule_pairs, uint32_t* d_bad_in_out, void* d_records, uint32_t record_elems, void* stream);
 
 /* ---- pairing product checks: for every check c, is the product of e(P_i, Q_i) over its pairs 1? -------------------------------------
  *

@@ -12,8 +12,14 @@ over at most 16 of the same proofs, per proof.  Prints one JSON object; ``--out 
 host: the figures above).  With more than one combination every one is measured in the SAME session, under ``modes`` by
 "transcript/pairing"; in device mode ``read``, ``transcript`` and ``terms`` of the split are the times of queueing each call and only
 their sum means anything.  With a device transcript the record also holds ``transcript_kernel_ms``: ``hm_verify_transcript_dev``
-alone, on a prepared batch, timed with events around the call."""
+alone, on a prepared batch, timed with events around the call, and ``read_kernel_ms``: the read kernel alone, likewise.
+
+``--encoding halo2|evm|both`` chooses the proofs' wire format (default halo2: the figures above).  With ``evm``, or ``both``, the
+rows stand under ``modes`` by "transcript/pairing/encoding"; ``both`` proves the same witnesses with the same seeds in the two
+encodings and interleaves them per B in one session, so that the "halo2" rows are the yardstick of the "evm" rows beside them.  The
+host transcript of "evm" is Keccak in pure Python (about half a millisecond per 136-byte block): large B is slow there."""
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -38,8 +44,31 @@ def spread(ms):
     return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3)}
 
 
+def read_kernel_ms(bv, repeats):
+    """the read kernel of the batch's encoding alone on the proofs a prepared device-mode batch keeps: events around the call, one
+    warm-up; the outputs go to arrays of their own"""
+    st, lay = bv._prepare(), bv.layout
+    B, dev = st["B"], st["d_proofs"].device
+    d_bases = torch.zeros((B * lay.own_points + B, 8), dtype=torch.int64, device=dev)
+    d_ybytes = None if st["d_ybytes"] is None else torch.zeros_like(st["d_ybytes"])
+    d_scalars, d_bad = torch.zeros_like(st["d_scalars"]), torch.zeros(B, dtype=torch.int32, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    ms = []
+    for i in range(repeats + 1):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        bv._queue_read(st["d_proofs"], st["d_table"], d_bases, d_bases[B * lay.own_points:], d_ybytes, d_scalars, d_bad, stream)
+        end.record()
+        end.synchronize()
+        if i:
+            ms.append(start.elapsed_time(end))
+    assert torch.equal(d_scalars, st["d_scalars"]) and not d_bad.any()
+    return spread(ms)
+
+
 def transcript_kernel_ms(bv, repeats):
-    """hm_verify_transcript_dev alone on the arrays a prepared device-mode batch keeps: events around the call, one warm-up"""
+    """hm_verify_transcript_dev (or its "evm" sibling) alone on the arrays a prepared device-mode batch keeps: events around the call,
+    one warm-up"""
     from halo2_experiments_amd import device_transcript as dt
 
     st = bv._prepare()
@@ -58,29 +87,32 @@ def transcript_kernel_ms(bv, repeats):
     return spread(ms)
 
 
-def circuit(name, sizes, repeats, modes=(("host", "host"),)):
+def circuit(name, sizes, repeats, modes=(("host", "host"),), encodings=("halo2",)):
     cs, lay, advice, instance, _ = pc.build(name)
     params = ParamsKZG.setup(lay.k, pc.SRS_S)
     vk = h.keygen_vk(params, cs, lay)
     pk = h.keygen_pk(params, vk, cs, lay, cosets=False)
     try:
-        proofs = [h.create_proof(params, pk, advice, instance, seed) for seed in (2, 3, 4, 5)]
-        out = {"k": lay.k, "proof_bytes": len(proofs[0]), "batches": {}}
+        made = {e: [h.create_proof(params, pk, advice, instance, seed, encoding=e) for seed in (2, 3, 4, 5)] for e in encodings}
+        plain = encodings == ("halo2",)                          # the record's shape before there was a second encoding
+        out = {"k": lay.k, "proof_bytes": len(made[encodings[0]][0]) if plain else {e: len(made[e][0]) for e in encodings}, "batches": {}}
         single = []
         for i in range(min(16, max(sizes))):
             t0 = time.perf_counter()
-            assert h.verify_proof(params, vk, instance, proofs[i % 4])
+            assert h.verify_proof(params, vk, instance, made[encodings[0]][i % 4], encoding=encodings[0])
             single.append((time.perf_counter() - t0) * 1e3)
-        out["verify_proof_per_proof"] = dict(spread(single), proofs=len(single))
-        for transcript, pairing in modes:
-            h.verify_proofs(params, vk, [instance], proofs[:1], transcript=transcript, pairing=pairing)   # warm-up: library load, allocator pools
+        out["verify_proof_per_proof"] = dict(spread(single), proofs=len(single), encoding=encodings[0])
+        runs = [(t, p, e) for t, p in modes for e in encodings]  # the encodings of one mode stand side by side
+        for transcript, pairing, encoding in runs:                # warm-up: library load, allocator pools
+            h.verify_proofs(params, vk, [instance], made[encoding][:1], transcript=transcript, pairing=pairing, encoding=encoding)
         for B in sizes:
-            for transcript, pairing in modes:
+            for transcript, pairing, encoding in runs:
+                proofs = made[encoding]
                 total, split = [], {p: [] for p in PHASES}
                 for _ in range(repeats):
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
-                    bv = h.BatchVerifier(params, vk, transcript=transcript, pairing=pairing)
+                    bv = h.BatchVerifier(params, vk, transcript=transcript, pairing=pairing, encoding=encoding)
                     for b in range(B):
                         bv.add_proof(instance, proofs[b % 4])
                     ok = bv.finalize()
@@ -94,12 +126,15 @@ def circuit(name, sizes, repeats, modes=(("host", "host"),)):
                 row["against_verify_proof_loop"] = round(out["verify_proof_per_proof"]["median_ms"] * B / statistics.median(total), 2)
                 if transcript == "device":
                     row["transcript_kernel_ms"] = transcript_kernel_ms(bv, repeats)
-                if len(modes) == 1:
+                    row["read_kernel_ms"] = read_kernel_ms(bv, repeats)
+                if len(runs) == 1 and plain:
                     out["batches"][str(B)] = row
                 else:
-                    out.setdefault("modes", {}).setdefault(f"{transcript}/{pairing}", {})[str(B)] = row
+                    key = f"{transcript}/{pairing}" if plain else f"{transcript}/{pairing}/{encoding}"
+                    out.setdefault("modes", {}).setdefault(key, {})[str(B)] = row
                 bv.close()
-        if len(modes) > 1:
+                print(f"{name} B={B} {transcript}/{pairing}/{encoding}: {row['finalize']['median_ms']} ms", file=sys.stderr, flush=True)
+        if "modes" in out:
             del out["batches"]
     finally:
         params.release()
@@ -112,17 +147,21 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=REPEATS)
     ap.add_argument("--transcript", choices=("host", "device", "both"), default="host")
     ap.add_argument("--pairing", choices=("host", "device", "both"), default="host")
+    ap.add_argument("--encoding", choices=("halo2", "evm", "both"), default="halo2")
+    ap.add_argument("--circuits", default="merkle_sum_d20_k10,poseidon_k6")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     sizes = tuple(int(s) for s in args.sizes.split(","))
     both = lambda choice: ("host", "device") if choice == "both" else (choice,)
     modes = tuple((t, p) for p in both(args.pairing) for t in both(args.transcript))
+    encodings = ("halo2", "evm") if args.encoding == "both" else (args.encoding,)
     torch.cuda.init()
     result = {"tool": "tools/batch_verify_time.py", "repeats": args.repeats, "modes_measured": [f"{t}/{p}" for t, p in modes],
-              "host": "the Blake2b transcripts and the pairing, unless the mode (transcript/pairing) says device; everything else (read, "
-                      "terms, column sum, MSMs) on the device",
-              "merkle_sum_d20_k10": circuit("merkle_sum_d20_k10", sizes, args.repeats, modes),
-              "poseidon_k6": circuit("poseidon_k6", sizes, args.repeats, modes)}
+              "encodings_measured": list(encodings),
+              "host": "the transcripts (Blake2b by hashlib; Keccak in pure Python) and the pairing, unless the mode (transcript/pairing) says "
+                      "device; everything else (read, terms, column sum, MSMs) on the device"}
+    for name in args.circuits.split(","):
+        result[name] = circuit(name, sizes, args.repeats, modes, encodings)
     text = json.dumps(result)
     print(text)
     if args.out:
