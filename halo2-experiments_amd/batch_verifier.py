@@ -33,6 +33,12 @@ check in place of the square root, no y bytes --, the transcript absorbs the pro
 
 ``proof_terms_ints`` is the integer twin of the whole per-proof part, ``read_proof_ints`` of the read kernel; neither needs a device.
 
+A verdict PER PROOF (``verdicts``, ``failing(method="each")``, ``verify_each``) takes the other road behind the same preparation: one
+workgroup per proof sums the proof's own pair (L_b, R_b) (``hm_verify_proof_sums_dev``, csrc/verify_sums.inc; ``proof_sums_ints`` is
+the integer twin), and one pairing call checks e(L_b, [s]G2) = e(R_b, G2) for every proof at once.  The weights r_b stay in the scalar
+arrays, so the per-proof sums equal ``_sums(handle, b, b + 1)`` as group elements; a verdict does not depend on r_b, which multiplies
+both sides of the proof's own equation.
+
 Two places where the symbolic form answers differently from ``verify_proof``, each of probability about 2^-254 for an honest or a
 dishonest prover alike (x is a hash output): x = 0, where all rotations of x coincide, is reported as a failing proof; and h pieces whose
 combination sum_i x^(n i) [h_i] is the identity are summed as they are, where ``verify_proof`` refuses to open the identity."""
@@ -50,7 +56,7 @@ from . import _lib, device_pairing, device_transcript, evaluation as ev
 from .bn256 import FQ_MODULUS, FR_MODULUS, fr_array, g1_words
 from .keygen import FR_DELTA, VerifyingKey
 from .kzg import g2_from_bytes
-from .pairing import G1_GEN, g1_mul, g1_neg, g1_on_curve
+from .pairing import G1_GEN, g1_msm, g1_mul, g1_neg, g1_on_curve
 from .shplonk import g1_words_to_int
 from .transcript import (PERSONAL, PREFIX_CHALLENGE, PREFIX_POINT, PREFIX_SCALAR, TranscriptError, check_encoding, g1_decompress_int,
                          g1_uncompressed_int, keccak256)
@@ -397,6 +403,7 @@ def terms_from_challenges(layout: ProofLayout, omega: int, inst_cols, evals: Seq
 VT_NO_SLOT, VT_T_SHARED, VT_T_H = 0xFFFFFFFF, 1 << 31, 1 << 30
 VT_MAX_VALS, VT_MAX_INST_ROWS, VT_MAX_SUPER, VT_MAX_T = 256, 64, 32, 8
 RECORD = ("theta", "beta", "gamma", "y", "x", "y2", "v", "u")          # then r_b: the per-proof record of hm_verify_terms_dev
+VERDICT_CHUNK = 1 << 16                                                # proofs per pairing call of ``verdicts``: the largest measured size
 
 
 def _internal_words(v: int) -> List[int]:
@@ -542,6 +549,17 @@ def proof_terms_ints(vk: VerifyingKey, instance, proof: bytes, layout: Optional[
     return ch, own, shared, points
 
 
+def proof_sums_ints(vk: VerifyingKey, instance, proof: bytes, layout: Optional[ProofLayout] = None, weight: int = 1):
+    """The integer twin of the per-proof sums: (L, R) of one proof as (x, y) integers (None = the identity), L = weight * [h'] and
+    R = weight * (sum own[j] * points[j] + sum shared[i] * (shared point i)), from ``proof_terms_ints`` and ``g1_msm``; the proof
+    verifies exactly when s * L == R, whatever the weight in [1, r).  Needs no device.  ``MalformedProof`` as ``proof_terms_ints``."""
+    layout = layout or ProofLayout(vk.cs, vk.domain.k)
+    _, own, shared, points = proof_terms_ints(vk, instance, proof, layout)
+    w = weight % R
+    scalars = [w * v % R for v in list(own) + list(shared)]
+    return g1_mul(w, points[-1]), g1_msm(scalars, list(points) + shared_points(vk, layout))
+
+
 def shared_points(vk: VerifyingKey, layout: ProofLayout):
     """the (x, y) points of ``layout.shared_keys``; None for a commitment that is the identity"""
     return [g1_words_to_int(c) for c in vk.fixed_commitments] + [g1_words_to_int(c) for c in vk.permutation_commitments] + [G1_GEN]
@@ -563,7 +581,10 @@ class BatchVerifier:
     trapdoor s * L == R in G1; an empty batch is True.  A malformed proof (wrong length, a scalar >= r, an x >= p or off the curve, an
     all-zero point, x^n = 1) makes ``finalize`` False and is kept out of the sums; it raises nothing.  ``failing(trapdoor=None)`` names
     the proofs that do not verify: the malformed ones, and among the others those found by bisection -- each step sums a contiguous
-    sub-range of the batch on the device and makes one check, O(f log B) checks for f failing proofs.  Every proof has a weight r_b in
+    sub-range of the batch on the device and makes one check, O(f log B) checks for f failing proofs.  ``verdicts(trapdoor=None)`` gives
+    one boolean per proof without bisection -- the per-proof sums in one launch, then one pairing check per proof, all in one call with
+    ``pairing="device"`` -- and ``failing(method="each")`` names its False entries: the same lists, at a cost that does not grow with
+    the number of failing proofs.  Every proof has a weight r_b in
     [1, r): from ``secrets`` when ``seed`` is None, else derived from (seed, index); ``randomizers`` shows them.
     A batch of ``create_proof_multi`` proofs is out of scope, and an instance column may hold 64 rows at most (the terms kernel's
     limit; ``finalize`` raises ValueError beyond it).  ``close()`` gives the numerator's program back to the library.
@@ -598,6 +619,7 @@ class BatchVerifier:
         self._plans: dict = {}                                   # instance shape -> TermsPlan (the program is the same for all)
         self._program = None                                     # the hm_graph_create program of the numerator, made on first use
         self.msm_calls = 0                                       # MSMs launched so far (tests, tools/batch_verify_time.py)
+        self.sums_calls = 0                                      # per-proof sums launches so far (``proof_sums``)
         self.timings: dict = {}                                  # seconds of the last preparation and check, by phase
 
     def __len__(self) -> int:
@@ -720,8 +742,9 @@ class BatchVerifier:
         bad = [bool(x) for x in d_bad.cpu().numpy()]              # the terms kernel flags x^n = 1 and its kin
         t4 = time.perf_counter()
         st = dict(B=B, bad=bad, d_bases=d_bases, d_scalars=d_scalars, d_own=d_own, d_shared=d_shared, d_h2_r=d_h2_r, d_h2_l=d_h2_l,
-                  d_sum=torch.zeros((n_shared, 4), dtype=torch.int64, device=dev), ybytes=ybytes)
-        self.timings = dict(read=t1 - t0, plan=t_plan, transcript=t2 - t1 - t_plan, upload=t3 - t2, terms=t4 - t3, msm=0.0, pairing=0.0)
+                  d_sum=torch.zeros((n_shared, 4), dtype=torch.int64, device=dev), ybytes=ybytes, d_bad=d_bad)
+        self.timings = dict(read=t1 - t0, plan=t_plan, transcript=t2 - t1 - t_plan, upload=t3 - t2, terms=t4 - t3, msm=0.0, pairing=0.0,
+                            sums=0.0, verdict_pairing=0.0)
         self._state = st
         return st
 
@@ -773,9 +796,10 @@ class BatchVerifier:
         bad = [bool(x) for x in d_bad.cpu().numpy()]              # the one download: what the three kernels flagged
         t6 = time.perf_counter()
         st = dict(B=B, bad=bad, d_bases=d_bases, d_scalars=d_scalars, d_own=d_own, d_shared=d_shared, d_h2_r=d_h2_r, d_h2_l=d_h2_l,
-                  d_sum=torch.zeros((n_shared, 4), dtype=torch.int64, device=dev), d_ybytes=d_ybytes,
+                  d_sum=torch.zeros((n_shared, 4), dtype=torch.int64, device=dev), d_ybytes=d_ybytes, d_bad=d_bad,
                   d_proofs=d_proofs, d_table=d_table, d_records=d_records, preamble=preamble)   # what the transcript call took (tools/batch_verify_time.py)
-        self.timings = dict(read=t1 - t0 + t4 - t3, plan=t2 - t1, transcript=t5 - t4, upload=t3 - t2, terms=t6 - t5, msm=0.0, pairing=0.0)
+        self.timings = dict(read=t1 - t0 + t4 - t3, plan=t2 - t1, transcript=t5 - t4, upload=t3 - t2, terms=t6 - t5, msm=0.0, pairing=0.0,
+                            sums=0.0, verdict_pairing=0.0)
         self._state = st
         return st
 
@@ -843,7 +867,91 @@ class BatchVerifier:
             return False
         return self._with_bases(lambda handle: self._check(handle, 0, st["B"], trapdoor))
 
-    def failing(self, trapdoor: int = None) -> List[int]:
+    # ---- a verdict per proof: the per-proof sums, then one pairing check per proof in one call ---------------------------------------------
+    def proof_sums(self):
+        """The (B, 2, 8) device tensor of ``hm_verify_proof_sums_dev``: row [b, 0] is L_b = r_b [h']_b, row [b, 1] is -R_b, affine
+        Montgomery words, (0, 0) for the identity; two zero rows for a malformed proof.  One launch for the whole batch, made once per
+        prepared state (``sums_calls`` counts the launches); nothing is launched when every proof is malformed, and an empty
+        batch gives an empty (0, 2, 8) tensor; ``msm_calls`` is not touched.  ``timings["sums"]`` is the wall time of QUEUEING the call: the device's work surfaces in the download behind it."""
+        import torch
+
+        if not self._proofs:                                     # nothing to prepare: an empty (0, 2, 8) tensor, no launch
+            return torch.zeros((0, 2, 8), dtype=torch.int64, device="cuda" if torch.cuda.is_available() else "cpu")
+        st = self._prepare()
+        if "d_pairs" in st:
+            return st["d_pairs"]
+        lay, B = self.layout, st["B"]
+        dev = st["d_bases"].device
+        d_pairs = torch.zeros((B, 2, 8), dtype=torch.int64, device=dev)
+        if not all(st["bad"]):
+            t0 = time.perf_counter()
+            vp = lambda t: ctypes.c_void_p(t.data_ptr())
+            _lib.check(_lib.load().hm_verify_proof_sums_dev(vp(st["d_bases"]), B, lay.own_points, len(lay.shared_keys), vp(st["d_own"]),
+                                                            vp(st["d_shared"]), vp(st["d_h2_r"]), vp(st["d_h2_l"]),
+                                                            ctypes.cast(vp(st["d_bad"]), ctypes.POINTER(ctypes.c_uint32)), vp(d_pairs),
+                                                            ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            self.sums_calls += 1
+            self.timings["sums"] += time.perf_counter() - t0
+        st["d_pairs"] = d_pairs
+        return d_pairs
+
+    def verdicts(self, trapdoor: int = None) -> List[bool]:
+        """One boolean per added proof, in order: does THIS proof verify -- what ``verify_proof`` answers, without bisection.  A
+        malformed proof is False from its flag (its rows are identities, which a pairing would pass).  For the others the per-proof
+        sums (``proof_sums``) are checked per proof: with ``pairing="device"`` as ONE ``device_pairing.run_device`` call over all of
+        them (per 65 536 proofs, the largest measured size), two pairs per check -- (L_b, [s]G2), (-R_b, G2) --, the G2 array filled on
+        the device and the status words the one download; with ``pairing="host"`` the points are downloaded and
+        ``pairing.pairing_check`` runs per proof, which is correct but costs about 36 ms PER PROOF on host integers; with the trapdoor
+        s * L_b == R_b on host integers.  An empty batch gives [].  ``timings["verdict_pairing"]`` is the wall time of the checks,
+        the download included."""
+        import torch
+
+        if not self._proofs:
+            return []
+        st = self._prepare()
+        B = st["B"]
+        good = [b for b in range(B) if not st["bad"][b]]
+        out = [False] * B
+        if not good:
+            return out
+        d_pairs = self.proof_sums()
+        t0 = time.perf_counter()
+        if trapdoor is None and self.pairing == "device":
+            dev = d_pairs.device
+            g2_words = np.frombuffer(bytes(self.params.s_g2) + bytes(self.params.g2), dtype=np.int64).reshape(2, 16)
+            d_g2_pair = torch.from_numpy(g2_words.copy()).to(dev)
+            d_good = None if len(good) == B else torch.tensor(good, dtype=torch.int64, device=dev)
+            status = []
+            for lo in range(0, len(good), VERDICT_CHUNK):
+                n = min(VERDICT_CHUNK, len(good) - lo)
+                rows = d_pairs[lo:lo + n] if d_good is None else d_pairs.index_select(0, d_good[lo:lo + n])
+                d_off = torch.arange(0, 2 * n + 1, 2, dtype=torch.int32, device=dev)
+                status.append(device_pairing.run_device(rows.reshape(2 * n, 8), d_g2_pair.repeat(n, 1), d_off, n))
+            for b, s in zip(good, torch.cat(status).cpu().numpy()):
+                out[b] = int(s) == 1
+        else:
+            rows = d_pairs.cpu().numpy().view(np.uint64)
+            if trapdoor is None:
+                from .pairing import pairing_check
+
+                g2, s_g2 = g2_from_bytes(self.params.g2), g2_from_bytes(self.params.s_g2)
+            for b in good:
+                left, neg_right = g1_words_to_int(rows[b, 0]), g1_words_to_int(rows[b, 1])
+                if trapdoor is not None:
+                    out[b] = g1_mul(trapdoor, left) == g1_neg(neg_right)
+                else:
+                    out[b] = g1_on_curve(left) and pairing_check([(left, s_g2), (neg_right, g2)])
+        self.timings["verdict_pairing"] += time.perf_counter() - t0
+        return out
+
+    def failing(self, trapdoor: int = None, method: str = "bisect") -> List[int]:
+        """The indices of the proofs that do not verify.  ``method="bisect"`` (the default): the malformed ones, and the others by
+        bisection, O(f log B) checks of four MSMs and one pairing each -- the cheaper way for a batch expected to be clean.
+        ``method="each"``: the indices where ``verdicts()`` is False, one sums launch and one pairing call whatever f is."""
+        if method not in ("bisect", "each"):
+            raise ValueError(f"BatchVerifier.failing: method must be 'bisect' or 'each', got {method!r}")
+        if method == "each":
+            return [b for b, ok in enumerate(self.verdicts(trapdoor)) if not ok]
         if not self._proofs:
             return []
         st = self._prepare()
@@ -878,3 +986,17 @@ def verify_proofs(params, vk: VerifyingKey, instances, proofs, seed=None, trapdo
     for instance, proof in zip(instances, proofs):
         bv.add_proof(instance, proof)
     return bv.finalize(trapdoor)
+
+
+def verify_each(params, vk: VerifyingKey, instances, proofs, seed=None, trapdoor: int = None, pairing: str = "host",
+                transcript: str = "host", encoding: str = "halo2") -> List[bool]:
+    """[is ``proofs[i]`` a valid single-circuit proof of ``vk`` for ``instances[i]``]: one ``BatchVerifier``, its ``verdicts`` -- the
+    per-proof sums in one launch and, with ``pairing="device"``, one pairing call for all proofs (keywords as on ``verify_proofs``)"""
+    check_encoding(encoding, "verify_each")
+    instances, proofs = list(instances), list(proofs)
+    if len(instances) != len(proofs):
+        raise ValueError("verify_each: one instance per proof")
+    bv = BatchVerifier(params, vk, seed, pairing=pairing, transcript=transcript, encoding=encoding)
+    for instance, proof in zip(instances, proofs):
+        bv.add_proof(instance, proof)
+    return bv.verdicts(trapdoor)

@@ -19,6 +19,7 @@ extern "C" {
 
 static constexpr size_t VERIFY_MAX_PROOFS = (size_t)1 << 24;
 static constexpr uint32_t VERIFY_MAX_SLOTS = 1u << 16;
+static constexpr size_t PAIRING_MAX_CHECKS = (size_t)1 << 20, PAIRING_MAX_PAIRS = (size_t)1 << 24;
 
 int hm_verify_read_proofs_dev(const void* d_proofs, size_t n_proofs, const uint32_t* d_slot_table, uint32_t slots, uint32_t own_points,
                               uint32_t points, uint32_t scalars, void* d_points_xy, void* d_tail_xy, void* d_y_bytes, void* d_scalars,
@@ -73,6 +74,24 @@ int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_word
                           (const uint32_t*)d_instance, d_bad, (uint32_t*)d_own, (uint32_t*)d_shared, (uint32_t*)d_h2_r, (uint32_t*)d_h2_l,
                           (hipStream_t)stream);
 } HM_API_CATCH("hm_verify_terms_dev")
+
+// ---- the per-proof sums (verify_sums.inc, verify.hip) -------------------------------------------------------------------------------
+int hm_verify_proof_sums_dev(const void* d_bases_xy, size_t n_proofs, uint32_t own_points, uint32_t shared_points, const void* d_own,
+                             const void* d_shared, const void* d_h2_r, const void* d_h2_l, const uint32_t* d_bad, void* d_pairs_xy,
+                             void* stream) try {
+  const std::string who = "hm_verify_proof_sums_dev";
+  if (!d_bases_xy || !d_own || !d_shared || !d_h2_r || !d_h2_l || !d_bad || !d_pairs_xy) return hm_fail(HM_ERR_BAD_ARG, who + ": null argument");
+  if (n_proofs == 0 || n_proofs > PAIRING_MAX_CHECKS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n_proofs <= 2^20");
+  if ((uint64_t)own_points + shared_points == 0 || (uint64_t)own_points + shared_points > VERIFY_MAX_SLOTS)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= own_points + shared_points <= 2^16");
+  if (((uintptr_t)d_bases_xy | (uintptr_t)d_own | (uintptr_t)d_shared | (uintptr_t)d_h2_r | (uintptr_t)d_h2_l | (uintptr_t)d_pairs_xy) & 15u)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": a buffer is not 16-byte aligned");
+  if ((uintptr_t)d_bad & 3u) return hm_fail(HM_ERR_BAD_ARG, who + ": d_bad is not 4-byte aligned");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return verify_sums_run((const uint32_t*)d_bases_xy, n_proofs, own_points, shared_points, (const uint32_t*)d_own, (const uint32_t*)d_shared,
+                         (const uint32_t*)d_h2_r, (const uint32_t*)d_h2_l, d_bad, (uint32_t*)d_pairs_xy, (hipStream_t)stream);
+} HM_API_CATCH("hm_verify_proof_sums_dev")
 
 // ---- Blake2b-512 and the transcripts of a batch (transcript.inc, lookup.hip) ----------------------------------------------------------
 int hm_blake2b512_dev(const void* d_msgs, size_t stride, const uint32_t* d_lens, size_t n, const uint8_t* personal16, void* d_out,
@@ -165,8 +184,6 @@ int hm_verify_transcript_evm_dev(const void* d_proofs, size_t n_proofs, uint32_t
 } HM_API_CATCH("hm_verify_transcript_evm_dev")
 
 // ---- pairing product checks (pairing.inc, lookup.hip) ------------------------------------------------------------------------------
-static constexpr size_t PAIRING_MAX_CHECKS = (size_t)1 << 20, PAIRING_MAX_PAIRS = (size_t)1 << 24;
-
 size_t hm_pairing_work_bytes(size_t n_pairs, size_t n_checks) {
   if (n_checks == 0 || n_checks > PAIRING_MAX_CHECKS || n_pairs > PAIRING_MAX_PAIRS) return 0;
   return pairing_work_words(n_pairs, n_checks) * sizeof(uint32_t);

@@ -1,11 +1,11 @@
 // fq_inverse.h -- the Fermat inversion in Fq that ends every Jacobian -> affine normalisation on the device (msm.hip: the fixed-base
-// tables and products; g1_fft.hip: the store kernel).
+// tables and products; g1_fft.hip: the store kernel; verify.hip: the per-proof sums).  Host-callable for host_check.cpp.
 #pragma once
 #include "g1.h"
 
 namespace hm {
 
-__device__ __forceinline__ Fq fq_inverse(const Fq& a) {  // a^(p-2), a a product output
+HM_HD Fq fq_inverse(const Fq& a) {  // a^(p-2), a a product output
   // exponent p - 2 in 29-bit limbs
   uint32_t e[9];
 #pragma unroll

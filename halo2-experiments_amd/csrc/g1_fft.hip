@@ -22,6 +22,7 @@
 #include <string>
 
 #include "fq_inverse.h"
+#include "g1_mul.h"
 #include "hm_internal.h"
 #include "host_fr.h"
 #include "msm_dev.h"
@@ -30,21 +31,7 @@ namespace hm {
 
 constexpr uint32_t G1_FFT_LOG_MAX = 24;
 
-// [e] b for a 256-bit integer e (8 words, little-endian), left to right; leading zero bits cost a flag test each
-__device__ __forceinline__ G1Jac g1_mul_words(const G1Jac& b, const uint32_t (&e_in)[8]) {
-  uint32_t e[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) e[k] = e_in[k];
-  G1Jac acc = g1_identity();
-  for (int bit = 0; bit < 256; ++bit) {
-    acc = g1_double(acc);
-    if (e[7] >> 31) acc = g1_add(acc, b);
-#pragma unroll
-    for (int k = 7; k > 0; --k) e[k] = (e[k] << 1) | (e[k - 1] >> 31);
-    e[0] <<= 1;
-  }
-  return acc;
-}
+// g1_mul_words, the double-and-add of every product below, is g1_mul.h's (the per-proof sums of verify.hip run its twin there)
 
 // -P: Y -> 6p - Y (Y < 5p, normalised limbs), brought back under 3p so that the point stays inside the Jacobian class
 __device__ __forceinline__ G1Jac g1_neg(const G1Jac& p) {

@@ -12,7 +12,9 @@
 #include <utility>
 #include <vector>
 
+#include "fq_inverse.h"
 #include "g1.h"
+#include "g1_mul.h"
 #include "graph_lower.h"
 #include "host_fr.h"
 #include "mock_check.h"   // the witness checker's key search, value key and record packing (its kernels: mock.hip)
@@ -21,6 +23,7 @@ namespace hm {
 #include "g1_codec.inc"   // the per-point SRS codec formulas (the kernels: g1_codec.hip)
 #include "verify_read.inc"   // the batch verifier's per-slot read and its column sum (verify.hip)
 #include "verify_terms.inc"  // ... and the two phases of its per-proof terms around the interpreter's run (verify.hip)
+#include "verify_sums.inc"   // ... and the lane, fold and finish functions of its per-proof sums (verify.hip)
 #include "poseidon.inc"   // the per-hash Poseidon / Merkle node functions (poseidon.hip)
 #include "range.inc"      // the range-check witness's lane function (range.hip)
 #include "accumulator.inc" // the accumulator witness's row function (accumulator.hip)
@@ -662,6 +665,55 @@ int hc_verify_column_sum(const uint32_t* rows, size_t n_rows, uint32_t cols, siz
     std::memcpy(out + (size_t)c * 8, w, 32);
   }
   return 0;
+}
+
+// The per-proof sums (verify_sums.inc): proof b of a batch by the kernel's own lane functions -- `lanes` partial sums dealt as the
+// kernel deals the terms to its threads, record `lanes` for L, the halving fold as a plain loop, the two finishing lanes -- with every
+// accumulator re-declared at the Jacobian class maxima where the kernel reads it back from LDS.  Arguments as
+// hm_verify_proof_sums_dev's (all host memory); pairs: the proof's 2 rows of 16 words.  fold_doublings (may be null): how many steps
+// of the fold added two equal points -- g1_add then returns g1_double_nz of its first operand, limb for limb -- so that a test can
+// tell that its rows reach that branch.
+static bool same_limbs(const G1Jac& a, const G1Jac& b) {
+  for (int i = 0; i < 9; ++i)
+    if (a.x.l[i] != b.x.l[i] || a.y.l[i] != b.y.l[i] || a.z.l[i] != b.z.l[i]) return false;
+  return a.inf == b.inf;
+}
+int hc_verify_proof_sums(const uint32_t* bases, size_t n_proofs, uint32_t own_points, uint32_t shared_points, const uint32_t* own,
+                         const uint32_t* shared, const uint32_t* h2_r, const uint32_t* h2_l, const uint32_t* bad, size_t b, uint32_t lanes,
+                         uint32_t* pairs, uint32_t* fold_doublings) {
+  if (fold_doublings) *fold_doublings = 0;
+  if (b >= n_proofs || lanes < 2 || (lanes & (lanes - 1))) return -1;
+  if (bad[b]) {
+    std::memset(pairs, 0, 2 * VS_ROW_WORDS * 4);
+    return 0;
+  }
+  const VsArgs a{bases, own, shared, h2_r, h2_l, (uint64_t)n_proofs, own_points, shared_points};
+  std::vector<uint32_t> tree((size_t)(lanes + 1) * VS_ACC_WORDS, 0u);
+  uint32_t* left = tree.data() + (size_t)lanes * VS_ACC_WORDS;
+  for (uint32_t t = 0; t < lanes; ++t) vs_lane(a, b, t, lanes, tree.data() + (size_t)t * VS_ACC_WORDS, left);
+  for (uint32_t off = lanes / 2; off > 0; off >>= 1)
+    for (uint32_t t = 0; t < off; ++t) {
+      const G1Jac x = vs_load_acc(tree.data() + (size_t)t * VS_ACC_WORDS), y = vs_load_acc(tree.data() + (size_t)(t + off) * VS_ACC_WORDS);
+      if (fold_doublings && !x.inf && !y.inf && same_limbs(g1_add(x, y), g1_double_nz(x))) ++*fold_doublings;
+      vs_fold_step(tree.data(), t, off);
+    }
+  vs_finish(tree.data(), true, pairs + VS_ROW_WORDS);
+  vs_finish(left, false, pairs);
+  return 0;
+}
+
+// The two double-and-add loops of g1_mul.h on one affine base (16 Montgomery words, not the identity) and one 256-bit integer (8
+// words): 1 when g1_mul_words and g1_mul_words_by_field give the same limbs and flag; row: the product as vs_finish writes it.
+int hc_g1_mul_words_pair(const uint32_t* base, const uint32_t* e_words, uint32_t* row) {
+  const G1Jac p = vs_load_base(base);
+  if (p.inf) return -1;
+  uint32_t e[8];
+  std::memcpy(e, e_words, 32);
+  const G1Jac whole = g1_mul_words(p, e), by_field = g1_mul_words_by_field(p, e);
+  uint32_t record[VS_ACC_WORDS];
+  vs_store_acc(record, by_field.inf ? g1_identity() : by_field);
+  vs_finish(record, false, row);
+  return (whole.inf && by_field.inf) || same_limbs(whole, by_field) ? 1 : 0;
 }
 
 // Blake2b and the transcripts (transcript.inc), the exact lane code of its kernels on a block of 32 host words.

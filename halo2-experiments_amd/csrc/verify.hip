@@ -1,6 +1,7 @@
 // verify.hip -- the device side of a batch verification (batch_verifier.py is the caller): the kernels and the drivers
 //   verify_read_run, verify_colsum_run    a batch of proofs read slot by slot, the column sums of its shared scalars (verify_read.inc)
 //   verify_terms_run                      the per-proof terms of the opening checks, one lane per proof (verify_terms.inc)
+//   verify_sums_run                       the two G1 points of every proof's own check, one workgroup per proof (verify_sums.inc)
 //   blake2b_run, verify_transcript_run    Blake2b-512 and the proofs' transcripts on it, one lane per proof (transcript.inc)
 //   keccak256_run, verify_read_evm_run,   Keccak-256, and the read and the transcripts of proofs in the EVM encoding: uncompressed
 //   verify_transcript_evm_run             big-endian points, a Keccak transcript that absorbs the proof verbatim (keccak.inc)
@@ -11,6 +12,8 @@
 #include <cstring>
 #include <string>
 
+#include "fq_inverse.h"
+#include "g1_mul.h"
 #include "graph_interp.h"
 #include "graph_lower.h"
 #include "hm_internal.h"
@@ -21,6 +24,7 @@ namespace hm {
 #include "g1_codec.inc"      // the decompression of a point slot (g1_decompress_one)
 #include "verify_read.inc"
 #include "verify_terms.inc"
+#include "verify_sums.inc"
 #include "transcript.inc"
 #include "keccak.inc"
 
@@ -202,6 +206,38 @@ int verify_terms_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size
                      d_inst, d_bad, d_own, d_shared, d_h2r, d_h2l);
   HM_HIP_CHECK(hipGetLastError());
   return aux_release(ctx, slot, stream);
+}
+
+// ---- the per-proof sums -----------------------------------------------------------------------
+// One workgroup per proof (verify_sums.inc): the lanes' partial sums, the fold through LDS, then lanes 0 and 1 normalise -R_b and L_b.
+// The flag is the same for the whole workgroup, so a flagged proof leaves before the first barrier.
+__global__ __launch_bounds__(VS_THREADS) void verify_sums_kernel(VsArgs a, const uint32_t* __restrict__ bad, uint32_t* __restrict__ out) {
+  __shared__ __align__(16) uint32_t tree[(VS_THREADS + 1) * VS_ACC_WORDS];
+  const uint64_t b = blockIdx.x;
+  const uint32_t t = threadIdx.x;
+  uint32_t* rows = out + b * 2 * VS_ROW_WORDS;
+  if (bad[b]) {
+    if (t < 2 * VS_ROW_WORDS) rows[t] = 0;
+    return;
+  }
+  uint32_t* left = tree + VS_THREADS * VS_ACC_WORDS;
+  vs_lane(a, b, t, VS_THREADS, tree + t * VS_ACC_WORDS, left);
+  __syncthreads();
+  for (uint32_t off = VS_THREADS / 2; off > 0; off >>= 1) {
+    if (t < off) vs_fold_step(tree, t, off);
+    __syncthreads();
+  }
+  if (t < 2) vs_finish(t == 0 ? tree : left, t == 0, rows + (t == 0 ? VS_ROW_WORDS : 0));
+}
+
+// the arguments were checked by the caller (capi_verify.hip): one launch, asynchronous on `stream`
+int verify_sums_run(const uint32_t* d_bases, size_t n_proofs, uint32_t own_points, uint32_t shared_points, const uint32_t* d_own,
+                    const uint32_t* d_shared, const uint32_t* d_h2r, const uint32_t* d_h2l, const uint32_t* d_bad, uint32_t* d_pairs,
+                    hipStream_t stream) {
+  const VsArgs a{d_bases, d_own, d_shared, d_h2r, d_h2l, (uint64_t)n_proofs, own_points, shared_points};
+  hipLaunchKernelGGL(verify_sums_kernel, dim3((uint32_t)n_proofs), dim3(VS_THREADS), 0, stream, a, d_bad, d_pairs);
+  HM_HIP_CHECK(hipGetLastError());
+  return HM_OK;
 }
 
 // ---- Blake2b and the transcripts -------------------------------------------------------------

@@ -66,6 +66,35 @@ def run(checks, want_gt: bool = False):
     return status, gt
 
 
+def run_device(d_g1, d_g2, d_offsets, n_checks: int):
+    """The call of ``run`` on arrays that already lie on the device -- ``d_g1`` (n_pairs, 8) and ``d_g2`` (n_pairs, 16) int64 Montgomery
+    words, ``d_offsets`` (n_checks + 1) int32 -- queued on the current stream: -> the (n_checks,) int32 status tensor, not downloaded
+    (1 the product is 1, 0 it is not, 2 a point off its curve).  Nothing is marshalled and nothing waits.  The three tensors must be
+    contiguous, of these dtypes and shapes, and on one device -- the raw pointers go to the library --; ValueError otherwise."""
+    import torch
+
+    for t, dtype, cols, name in ((d_g1, torch.int64, 8, "d_g1"), (d_g2, torch.int64, 16, "d_g2"), (d_offsets, torch.int32, None, "d_offsets")):
+        if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.device == d_g1.device):
+            raise ValueError(f"pairing checks: {name} must be a contiguous {dtype} tensor on the device of d_g1")
+        if cols is not None and (t.dim() != 2 or t.shape[1] != cols):
+            raise ValueError(f"pairing checks: {name} must have the shape (n_pairs, {cols})")
+    n_pairs, n_checks = int(d_g1.shape[0]), int(n_checks)
+    if d_g2.shape[0] != n_pairs or d_offsets.dim() != 1 or d_offsets.numel() != n_checks + 1:
+        raise ValueError("pairing checks: one G2 point per G1 point and n_checks + 1 offsets")
+    if n_pairs == 0:
+        raise ValueError("pairing checks: the arrays hold no pair (the entry takes no null pointer)")
+    lib = _lib.load()
+    work_bytes = lib.hm_pairing_work_bytes(n_pairs, n_checks)
+    if work_bytes == 0:
+        raise ValueError("pairing checks: need 1 .. 2^20 checks and at most 2^24 pairs in one call")
+    d_work = torch.empty((work_bytes + 7) // 8, dtype=torch.int64, device=d_g1.device)
+    d_status = torch.empty(n_checks, dtype=torch.int32, device=d_g1.device)
+    _lib.check(lib.hm_pairing_check_bn256_dev(_vp(d_g1.data_ptr()), _vp(d_g2.data_ptr()), n_pairs, _dev_ptr(d_offsets, _u32p), n_checks,
+                                              _vp(None), _dev_ptr(d_status, _u32p), _vp(d_work.data_ptr()), work_bytes,
+                                              _vp(_stream_ptr(d_work))))
+    return d_status
+
+
 def _raise_on_malformed(status: Sequence[int]) -> None:
     bad = [c for c, s in enumerate(status) if s == 2]
     if bad:

@@ -19,7 +19,7 @@ from .arithmetic import (bases_info, batch_invert, best_fft, best_multiexp, best
                          kate_division_batch,
                          linear_combination, linear_combination_batch, msm_stats, permute_expression_pair, permute_expression_pairs, random_fr, register_bases,
                          release_bases)
-from .batch_verifier import BatchVerifier, verify_proofs  # noqa: F401
+from .batch_verifier import BatchVerifier, verify_each, verify_proofs  # noqa: F401
 from .domain import EvaluationDomain  # noqa: F401
 from .keygen import (ProvingKey, VerifyingKey, copy_pairs, keygen_pk, keygen_vk, permutation_cells_dev,  # noqa: F401
                      permutation_columns_dev)
@@ -46,7 +46,7 @@ __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_mult
            "merkle_witness_host", "poseidon_circuit_witness", "poseidon_circuit_witness_host", "copy_pairs", "permutation_cells_dev",
            "permutation_columns_dev", "keygen_vk", "keygen_pk", "VerifyingKey", "ProvingKey",
            "create_proof", "create_proof_multi", "create_proofs", "verify_proof", "verify_proof_multi", "Blake2bWrite", "Blake2bRead", "KeccakWrite", "KeccakRead", "keccak256", "pairing_check", "construct_intermediate_sets",
-           "set_quotient", "set_quotient_batch", "set_quotient_ints", "create_openings", "linear_combination_batch", "MockProver", "MockResult", "NotSatisfied", "BatchVerifier", "verify_proofs",
+           "set_quotient", "set_quotient_batch", "set_quotient_ints", "create_openings", "linear_combination_batch", "MockProver", "MockResult", "NotSatisfied", "BatchVerifier", "verify_proofs", "verify_each",
            "OpeningTable", "open_all", "open_all_ints", "open_at", "verify_opening", "verify_openings",
            "RangeCheckLayout", "range_witness", "range_witness_host", "range_c_layout", "BalanceProof", "prove_balances", "verify_balances",
            "user_openings", "verify_user", "verify_users"]

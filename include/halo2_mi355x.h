@@ -831,6 +831,21 @@ int hm_verify_column_sum_dev(const void* d_rows, size_t n_rows, uint32_t columns
 int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
                         const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad, void* d_own, void* d_shared,
                         void* d_h2_r, void* d_h2_l, void* stream);
+/* per-proof sums: the two G1 points of every proof's OWN opening check, one workgroup per proof, all proofs in one launch -- what a
+ * verdict per proof needs where the MSMs above sum over proofs.  d_bases_xy: (n_proofs * own_points + shared_points + n_proofs) x 8
+ * u64, affine Montgomery words, (0, 0) = the identity: the own points of every proof as hm_verify_read_proofs_dev left them, then the
+ * points all proofs share, then every proof's tail point [h'].  d_own (n_proofs * own_points x 4 words), d_shared (n_proofs x
+ * shared_points x 4), d_h2_r, d_h2_l (n_proofs x 4 each): the Montgomery Fr words hm_verify_terms_dev wrote.  d_bad: n_proofs u32,
+ * read only.  Output d_pairs_xy, n_proofs x 2 x 8 u64: row 2b is L_b = h2_l[b] [h']_b, row 2b + 1 is -R_b with
+ * R_b = sum_j own[b, j] P[b, j] + sum_k shared[b, k] S_k + h2_r[b] [h']_b, both canonical affine Montgomery words, (0, 0) for the
+ * identity -- the d_g1_xy layout of hm_pairing_check_bn256_dev, so that (L_b, [s]G2), (-R_b, G2) is check b of one pairing call.
+ * Every addition is the complete one: repeated bases, opposite terms, identity bases and zero scalars give the group's answer.  A
+ * proof whose d_bad[b] is set gets two zero rows and nothing of it is multiplied.  All DEVICE memory, 16-byte aligned, d_bad 4-byte.
+ * Asynchronous on `stream`: one launch.  HM_ERR_BAD_ARG, with nothing launched: NULL arguments, n_proofs 0 or above 2^20 (the pairing
+ * entry's cap), own_points + shared_points 0 or above 2^16 (either may be 0 alone), a buffer that is not aligned. */
+int hm_verify_proof_sums_dev(const void* d_bases_xy, size_t n_proofs, uint32_t own_points, uint32_t shared_points, const void* d_own,
+                             const void* d_shared, const void* d_h2_r, const void* d_h2_l, const uint32_t* d_bad, void* d_pairs_xy,
+                             void* stream);
 /* Blake2b-512 (RFC 7693, 64-byte digest, no key), one lane per message: message i is the d_lens[i] bytes at d_msgs + i * stride
  * (DEVICE memory, any alignment; d_lens: n u32, DEVICE memory), personal16 the 16 personalisation bytes (HOST memory, read before the
  * call returns) or NULL for none; d_out: n x 64 digest bytes (DEVICE memory, 4-byte aligned).  The lengths lie on the device, so the
