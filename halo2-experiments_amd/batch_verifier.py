@@ -4,8 +4,8 @@ e(h2_b, [s]G2) = e(R_b, G2) -- what ``shplonk.verify_opening`` returns; with a r
 
     e(sum_b r_b h2_b, [s]G2) = e(sum_b r_b R_b, G2)
 
-which a batch holding a proof that fails passes with probability 1 / r.  Scope: single-circuit proofs (``create_proof``) of one ``vk``;
-a batch of ``create_proof_multi`` proofs is out of scope.
+which a batch holding a proof that fails passes with probability 1 / r.  Scope: proofs of one ``vk``, single-circuit
+(``create_proof``) or, with ``circuits=m``, multi-circuit (``create_proof_multi``, every proof of the batch holding m circuits).
 
 Where the work is done:
 
@@ -32,6 +32,15 @@ check in place of the square root, no y bytes --, the transcript absorbs the pro
 ``hm_verify_transcript_evm_dev`` on the device; csrc/keccak.inc), and everything behind the challenges is the same code.
 
 ``proof_terms_ints`` is the integer twin of the whole per-proof part, ``read_proof_ints`` of the read kernel; neither needs a device.
+
+``circuits=m`` (``ProofLayout``, ``BatchVerifier``, ``verify_proofs``, ``verify_each``; 2 <= m <= 64) takes ``create_proof_multi``
+proofs: the layout lists the points and evaluations in the order ``verifier._verify`` reads m circuits -- per-circuit keys are
+(kind, index, circuit) --, read, transcript, column sums, MSMs, per-proof sums and pairing are the same calls on the longer lists,
+and the terms are ``hm_verify_terms_multi_dev``: ONE WAVEFRONT per proof, lane c = circuit c, driven by a ``MultiTermsPlan``.  A
+lane runs the single-circuit phases and the same numerator program on its own circuit's value row; the proof's numerator
+sum_c y^(E (m - 1 - c)) N_c and the sum of coeff x r_eval meet by cross-lane moves inside the wave.  The twins take a list of m
+instances.  With ``circuits=1`` everything is as before, and the old terms entry is the one called.  The one combination left out
+is multi-circuit proofs in the "evm" encoding, which ``create_proof_multi`` does not write: ValueError.
 
 A verdict PER PROOF (``verdicts``, ``failing(method="each")``, ``verify_each``) takes the other road behind the same preparation: one
 workgroup per proof sums the proof's own pair (L_b, R_b) (``hm_verify_proof_sums_dev``, csrc/verify_sums.inc; ``proof_sums_ints`` is
@@ -65,6 +74,7 @@ from .verifier import _instance_columns, _vk_digest, evaluate_expression, proof_
 R, P = FR_MODULUS, FQ_MODULUS
 VR_POINT, VR_TAIL = 1 << 31, 1 << 30          # csrc/verify_read.inc: the slot table's bits
 EVM_POINT, EVM_TAIL, EVM_SKIP = 1 << 31, 1 << 30, 1 << 29   # csrc/keccak.inc: the bits of an "evm" layout's table (x slot, tail, y slot)
+MAX_CIRCUITS = 64                                            # prover.MAX_CIRCUITS, stated again: the lanes of one gfx950 wavefront
 
 
 class MalformedProof(ValueError):
@@ -74,7 +84,8 @@ class MalformedProof(ValueError):
 
 # ---- what a constraint system fixes: the slots of a proof, its queries and its rotation sets ---------------------------------------------
 class ProofLayout:
-    """Everything about a single-circuit proof that the constraint system and n = 2^k fix, built once per ``vk``:
+    """Everything about a proof that the constraint system, n = 2^k and the number of circuits in the proof fix, built once per
+    ``vk`` (``circuits=1``, a ``create_proof`` proof, unless said otherwise; ``circuits=m``: the last paragraph):
 
       ``point_keys``   the commitments in the order the proof holds them: advice, lookup a' / s', permutation z, lookup z, random, the
                        h pieces, then -- behind the evaluations -- [h] and [h'].  All but the last are the proof's OWN points.
@@ -88,10 +99,25 @@ class ProofLayout:
 
     ``encoding="evm"``: a point takes two 32-byte slots, x then y, so ``slots`` = 2 points + scalars, and ``slot_table`` is of the kind
     ``hm_verify_read_proofs_evm_dev`` takes: EVM_POINT | index on the x slot of an own point, EVM_POINT | EVM_TAIL on that of [h'],
-    EVM_SKIP on every y slot, the index on a scalar slot.  ``point_slots`` are then the x slots.  Everything else is the same."""
+    EVM_SKIP on every y slot, the index on a scalar slot.  ``point_slots`` are then the x slots.  Everything else is the same.
 
-    def __init__(self, cs, k: int, encoding: str = "halo2"):
+    ``circuits=m`` > 1, a ``create_proof_multi`` proof, every list in the order of ``verifier._verify`` with m instances: the points
+    are the advice of circuit 0 .. m - 1, then lookup a' / s' per circuit, permutation z per circuit, lookup z per circuit, then
+    random, the h pieces, [h], [h']; the evaluations the advice evaluations per circuit, then fixed, random, sigma, then the
+    permutation and the lookup evaluations per circuit.  A per-circuit key is (kind, index, circuit); shared keys stay as they are.
+    The rotation sets are the single-circuit ones in the same order (circuit 0's queries come first), the members of a set circuit
+    0's keys, circuit 1's, ..., then the shared ones.  ``lane`` is the single-circuit layout of the same system (the layout itself
+    when m = 1).  ``encoding="evm"`` with m > 1 raises ValueError."""
+
+    def __init__(self, cs, k: int, encoding: str = "halo2", circuits: int = 1):
         self.encoding = check_encoding(encoding, "ProofLayout")
+        m = int(circuits)
+        if not 1 <= m <= MAX_CIRCUITS:
+            raise ValueError(f"ProofLayout: need 1 <= circuits <= {MAX_CIRCUITS}, got {circuits!r}")
+        if m > 1 and encoding == "evm":
+            raise ValueError("ProofLayout: a multi-circuit proof has no \"evm\" encoding (create_proof_multi writes none)")
+        self.circuits = m
+        self.lane = self if m == 1 else ProofLayout(cs, k, encoding)       # what ONE circuit of the proof looks like
         self.cs, self.k, self.n = cs, k, 1 << k
         n = self.n
         adv_q, fix_q, _ = cs.queries()
@@ -100,18 +126,23 @@ class ProofLayout:
         self.pieces = cs.degree() - 1
         self.last = -(cs.blinding_factors + 1)
         last = self.last
-        pts = [("advice", i) for i in range(cs.num_advice)]
-        for j in range(L):
-            pts += [("lookup_a", j), ("lookup_s", j)]
-        pts += [("perm_z", i) for i in range(nsets)] + [("lookup_z", j) for j in range(L)] + [("random",)]
+        M = range(m)
+        per = (lambda key, c: key) if m == 1 else (lambda key, c: key + (c,))   # a per-circuit key: (kind, index, circuit) when m > 1
+        pts = [per(("advice", i), c) for c in M for i in range(cs.num_advice)]
+        for c in M:
+            for j in range(L):
+                pts += [per(("lookup_a", j), c), per(("lookup_s", j), c)]
+        pts += [per(("perm_z", i), c) for c in M for i in range(nsets)] + [per(("lookup_z", j), c) for c in M for j in range(L)] + [("random",)]
         pts += [("h_piece", i) for i in range(self.pieces)]
         self.points_before_evals = len(pts)
-        evs = [(("advice", i), r % n) for i, r in adv_q] + [(("fixed", i), r % n) for i, r in fix_q] + [(("random",), 0)]
+        evs = [(per(("advice", i), c), r % n) for c in M for i, r in adv_q] + [(("fixed", i), r % n) for i, r in fix_q] + [(("random",), 0)]
         evs += [(("sigma", j), 0) for j in range(P_)]
-        for i in range(nsets):
-            evs += [(("perm_z", i), r % n) for r in (0, 1) + ((last,) if i + 1 < nsets else ())]
-        for j in range(L):
-            evs += [((kd, j), r % n) for kd, r in (("lookup_z", 0), ("lookup_z", 1), ("lookup_a", 0), ("lookup_a", -1), ("lookup_s", 0))]
+        for c in M:
+            for i in range(nsets):
+                evs += [(per(("perm_z", i), c), r % n) for r in (0, 1) + ((last,) if i + 1 < nsets else ())]
+        for c in M:
+            for j in range(L):
+                evs += [(per((kd, j), c), r % n) for kd, r in (("lookup_z", 0), ("lookup_z", 1), ("lookup_a", 0), ("lookup_a", -1), ("lookup_s", 0))]
         self.point_keys = pts + [("h1",), ("h2",)]
         self.eval_keys = evs
         self.eval_index = {}
@@ -119,7 +150,7 @@ class ProofLayout:
             self.eval_index.setdefault(key, at)
         self.n_points, self.own_points, self.n_scalars = len(self.point_keys), len(self.point_keys) - 1, len(evs)
         self.slots = (2 if encoding == "evm" else 1) * self.n_points + self.n_scalars
-        if 32 * self.slots != proof_length(cs, 1, encoding):
+        if 32 * self.slots != proof_length(cs, m, encoding):
             raise AssertionError("ProofLayout: the slots do not add up to proof_length")
         if encoding == "evm":
             table = [e for i in range(self.points_before_evals) for e in (EVM_POINT | i, EVM_SKIP)] + list(range(self.n_scalars))
@@ -132,11 +163,14 @@ class ProofLayout:
         self.scalar_slots = [s for s, e in enumerate(table) if not e & (VR_POINT | (EVM_SKIP if encoding == "evm" else 0))]
 
         # the queries in the order verifier._verify lists them; ("h",) stands for sum_i x^(n i) [h_i]
-        q = [(("advice", i), r % n) for i, r in adv_q]
-        q += [qq for i in range(nsets) for qq in ((("perm_z", i), 0), (("perm_z", i), 1))]
-        q += [(("perm_z", i), last % n) for i in reversed(range(nsets - 1))]
-        for j in range(L):
-            q += [(("lookup_z", j), 0), (("lookup_a", j), 0), (("lookup_s", j), 0), (("lookup_a", j), (-1) % n), (("lookup_z", j), 1)]
+        q = []
+        for c in M:
+            q += [(per(("advice", i), c), r % n) for i, r in adv_q]
+            q += [qq for i in range(nsets) for qq in ((per(("perm_z", i), c), 0), (per(("perm_z", i), c), 1))]
+            q += [(per(("perm_z", i), c), last % n) for i in reversed(range(nsets - 1))]
+            for j in range(L):
+                q += [(per(("lookup_z", j), c), 0), (per(("lookup_a", j), c), 0), (per(("lookup_s", j), c), 0),
+                      (per(("lookup_a", j), c), (-1) % n), (per(("lookup_z", j), c), 1)]
         q += [(("fixed", i), r % n) for i, r in fix_q] + [(("sigma", j), 0) for j in range(P_)]
         q += [(("h",), 0), (("random",), 0)]
         self.queries = q
@@ -178,12 +212,12 @@ class ProofLayout:
         self.exprs = exprs
 
     def transcript_schedule(self) -> List[Tuple[int, int]]:
-        """The (absorb a slots, squeeze s challenges) pairs of a single-circuit proof's transcript over its slots in order, from the
+        """The (absorb a slots, squeeze s challenges) pairs of a proof's transcript over its slots in order, from the
         counts ``transcript_challenges`` uses: advice | theta | 2L | beta, gamma | sets + L + 1 | y | pieces | x | evaluations | y', v
         | [h] | u, and a last pair that absorbs [h'] behind the last challenge, as ``Blake2bRead`` does.  The counts are SLOTS: in an
-        "evm" layout a point counts twice."""
-        w = 2 if self.encoding == "evm" else 1
-        pairs = [(w * self.cs.num_advice, 1), (w * 2 * self.L, 2), (w * (self.nsets + self.L + 1), 1), (w * self.pieces, 1),
+        "evm" layout a point counts twice, and with ``circuits = m`` the per-circuit counts (advice, 2L, sets + L) are taken m times."""
+        w, m = 2 if self.encoding == "evm" else 1, self.circuits
+        pairs = [(w * m * self.cs.num_advice, 1), (w * m * 2 * self.L, 2), (w * (m * (self.nsets + self.L) + 1), 1), (w * self.pieces, 1),
                  (self.n_scalars, 2), (w, 1), (w, 0)]
         if sum(a for a, _ in pairs) != self.slots or sum(s for _, s in pairs) != len(RECORD):
             raise AssertionError("ProofLayout: the transcript's schedule does not cover the proof's slots and the eight challenges")
@@ -229,6 +263,26 @@ def read_proof_ints(layout: ProofLayout, proof: bytes):
     return points, scalars
 
 
+def _per_circuit(layout: ProofLayout, inst_cols) -> list:
+    """the instance columns circuit by circuit: a single-circuit layout takes one circuit's columns, a multi-circuit one a list of m"""
+    if layout.circuits == 1:
+        return [inst_cols]
+    per = list(inst_cols)
+    if len(per) != layout.circuits:
+        raise ValueError(f"a layout of {layout.circuits} circuits takes {layout.circuits} instances, got {len(per)}")
+    return per
+
+
+def _layout_instances(layout: ProofLayout, instance):
+    """what ``add_proof`` and the twins are given, as instance columns: one circuit's, or with a multi-circuit layout a list of m"""
+    if layout.circuits == 1:
+        return _instance_columns(layout.cs, instance)
+    per = [_instance_columns(layout.cs, one) for one in instance]
+    if len(per) != layout.circuits:
+        raise ValueError(f"a proof of {layout.circuits} circuits takes {layout.circuits} instances, got {len(per)}")
+    return per
+
+
 def _keccak_challenges(layout: ProofLayout, vk_digest: int, inst_cols, proof: bytes) -> dict:
     """``transcript_challenges`` of an "evm" layout: the preamble big-endian, then the proof's slots verbatim by the layout's schedule;
     the buffer rules are ``transcript``'s"""
@@ -269,18 +323,19 @@ def transcript_challenges(layout: ProofLayout, vk_digest: int, inst_cols, proof:
         st.update(PREFIX_CHALLENGE)
         return int.from_bytes(st.copy().digest(), "little") % R
 
-    cs = layout.cs
+    cs, m = layout.cs, layout.circuits
     scalar(vk_digest)
-    for values in inst_cols:
-        for v in values:
-            scalar(v)
+    for columns in _per_circuit(layout, inst_cols):
+        for values in columns:
+            for v in values:
+                scalar(v)
     ch = {}
-    points(cs.num_advice)
+    points(m * cs.num_advice)
     ch["theta"] = squeeze()
-    points(2 * layout.L)
+    points(m * 2 * layout.L)
     ch["beta"] = squeeze()
     ch["gamma"] = squeeze()
-    points(layout.nsets + layout.L + 1)
+    points(m * (layout.nsets + layout.L) + 1)
     ch["y"] = squeeze()
     points(layout.pieces)
     ch["x"] = squeeze()
@@ -300,7 +355,9 @@ def terms_from_challenges(layout: ProofLayout, omega: int, inst_cols, evals: Seq
     the proof's order) and its challenges: ``own`` has one entry per point of ``layout.point_keys`` ([h'] last, with u), ``shared`` one
     per ``layout.shared_keys``.  ``MalformedProof`` when x^n = 1 (or x = 0).  ``details``, when given, receives what the device keeps in
     its value row: l0, l_last, l_active, the instance evaluations by (column, rotation), the numerator and h(x)."""
-    cs, n = layout.cs, layout.n
+    cs, n, m = layout.cs, layout.n, layout.circuits
+    insts = _per_circuit(layout, inst_cols)
+    per = (lambda key, c: key) if m == 1 else (lambda key, c: key + (c,))
     x, y = ch["x"], ch["y"]
     xn = pow(x, n, R)
     if xn == 1 or x == 0:
@@ -321,32 +378,40 @@ def terms_from_challenges(layout: ProofLayout, omega: int, inst_cols, evals: Seq
     ev_at = lambda key, r: evals[layout.eval_index[(key, r % n)]]
     nf = cs.num_fixed
 
-    def leaf(kind: str, column: int, r: int) -> int:
-        if kind == "instance":
-            value = sum(v * lagrange_at(i, r) for i, v in enumerate(inst_cols[column]) if v) % R
-            if details is not None:
-                details.setdefault("instance", {})[(column, r % n)] = value
-            return value
-        if kind == "advice":
-            return ev_at(("advice", column), r)
-        if column < nf:
-            return ev_at(("fixed", column), r)
-        if column in special:
-            return special[column]
-        if column < layout.z0:
-            return ev_at(("sigma", column - layout.sigma0), r)
-        if column < layout.i_l0:
-            return ev_at(("perm_z", column - layout.z0), r)
-        j, part = divmod(column - layout.lookup0, 3)
-        return ev_at((("lookup_z", "lookup_a", "lookup_s")[part], j), r)
+    def leaf_of(c: int):
+        def leaf(kind: str, column: int, r: int) -> int:
+            if kind == "instance":
+                value = sum(v * lagrange_at(i, r) for i, v in enumerate(insts[c][column]) if v) % R
+                if details is not None:
+                    details.setdefault("instance", {})[per((column, r % n), c)] = value
+                return value
+            if kind == "advice":
+                return ev_at(per(("advice", column), c), r)
+            if column < nf:
+                return ev_at(("fixed", column), r)
+            if column in special:
+                return special[column]
+            if column < layout.z0:
+                return ev_at(("sigma", column - layout.sigma0), r)
+            if column < layout.i_l0:
+                return ev_at(per(("perm_z", column - layout.z0), c), r)
+            j, part = divmod(column - layout.lookup0, 3)
+            return ev_at(per((("lookup_z", "lookup_a", "lookup_s")[part], j), c), r)
+        return leaf
 
     scalars = {"Beta": ch["beta"], "Gamma": ch["gamma"], "Theta": ch["theta"]}
-    acc = 0
-    for e in layout.exprs:
-        acc = (acc * y + evaluate_expression(e, leaf, scalars)) % R
+    acc, numerators = 0, []
+    for c in range(m):                                            # ONE running value: circuit 0's expressions, then circuit 1's, ...
+        leaf, own_fold = leaf_of(c), 0
+        for e in layout.exprs:
+            value = evaluate_expression(e, leaf, scalars)
+            acc, own_fold = (acc * y + value) % R, (own_fold * y + value) % R
+        numerators.append(own_fold)                               # N_c: what lane c of the device computes; acc = sum_c y^(E (m-1-c)) N_c
     hx = acc * pow(xn - 1, -1, R) % R
     if details is not None:
         details.update(l0=l0, l_last=l_last, l_active=l_active, numerator=acc, hx=hx)
+        if m > 1:
+            details["numerators"] = numerators
 
     # ---- the multiopen's scalars, per rotation set ---------------------------------------------------------------------------------
     y2, v, u = ch["y2"], ch["v"], ch["u"]
@@ -537,12 +602,89 @@ class TermsPlan:
         return row or [0]
 
 
+VM_HDR = 12                                                       # csrc/verify_terms.inc: the words of a multi plan's header
+
+
+class MultiTermsPlan:
+    """What ``hm_verify_terms_multi_dev`` needs beside the proofs of a multi-circuit layout: the ``TermsPlan`` of ONE circuit
+    (``lane``: every lane of the wavefront walks it on its own value row) wrapped in the words that say where circuit c stands in
+    the proof -- the segments of its evaluations among the proof's scalars, the groups of own rows it answers for, and per
+    rotation set how many members belong to a circuit and every member's (target, stride) in the proof's point order
+    (csrc/verify_terms.inc, second half, states the layout).  ``lowered`` is the lane's: the same program as the single-circuit
+    kernel runs.  ``inst_rows[c]``: the rows given of instance column c, the same for every circuit.  Needs no device."""
+
+    def __init__(self, layout: ProofLayout, omega: int, inst_rows: Sequence[int]):
+        m, one, cs = layout.circuits, layout.lane, layout.cs
+        self.lane = TermsPlan(one, omega, inst_rows)
+        per = (lambda key, c: key) if m == 1 else (lambda key, c: key + (c,))
+        own_kinds = ("advice", "lookup_a", "lookup_s", "perm_z", "lookup_z")
+        adv_q, fix_q, _ = cs.queries()
+        n_adv, n_mid = len(adv_q), len(fix_q) + 1 + layout.P
+        n_perm, n_look = (3 * layout.nsets - 1 if layout.nsets else 0), 5 * layout.L
+        segments = [(n_adv, 0, n_adv), (n_mid, m * n_adv, 0), (n_perm, m * n_adv + n_mid, n_perm),
+                    (n_look, m * n_adv + n_mid + m * n_perm, n_look)]
+        slot = 0
+        for count, base, stride in segments:                      # the formula against the layout's own lists, circuit by circuit
+            for i in range(count):
+                key, rot = one.eval_keys[slot]
+                for c in range(m):
+                    want = (per(key, c) if key[0] in own_kinds else key, rot)
+                    if layout.eval_keys[base + c * stride + i] != want:
+                        raise AssertionError("MultiTermsPlan: the segments and the layout's evaluations disagree")
+                slot += 1
+        if slot != one.n_scalars:
+            raise AssertionError("MultiTermsPlan: the segments do not fill a lane's evaluations")
+        segments = [s for s in segments if s[0]]
+        rows_of = {"advice": cs.num_advice, "lookup_a": 2 * layout.L, "lookup_s": 2 * layout.L, "perm_z": layout.nsets, "lookup_z": layout.L}
+        groups, at = [], 0
+        for count in (cs.num_advice, 2 * layout.L, layout.nsets, layout.L):
+            if count:
+                groups.append((at, count))
+            at += m * count
+        own_tail = at
+        if layout.point_keys[own_tail] != ("random",):
+            raise AssertionError("MultiTermsPlan: the proof's own rows do not begin where the circuits' end")
+        member_words: List[int] = []
+        for (rots, keys), (rots_m, keys_m) in zip(one.sets, layout.sets):
+            mine = [key for key in keys if key[0] in own_kinds]
+            if keys[:len(mine)] != mine or rots != rots_m or keys_m != [per(key, c) for c in range(m) for key in mine] + keys[len(mine):]:
+                raise AssertionError("MultiTermsPlan: a rotation set is not circuit 0's members, circuit 1's, ..., then the proof's")
+            member_words.append(len(mine))
+            for key in keys:
+                if key == ("h",):
+                    member_words += [VT_T_H | layout.own_index[("h_piece", 0)], 0]
+                elif key in layout.shared_index:
+                    member_words += [VT_T_SHARED | layout.shared_index[key], 0]
+                elif key[0] in own_kinds:
+                    member_words += [layout.own_index[per(key, 0)], rows_of[key[0]]]
+                else:
+                    member_words += [layout.own_index[key], 0]
+        if len(one.sets) != len(layout.sets):
+            raise AssertionError("MultiTermsPlan: the later circuits open a rotation set of their own")
+        off_seg = VM_HDR
+        off_groups = off_seg + 3 * len(segments)
+        off_members = off_groups + 2 * len(groups)
+        off_lane = off_members + len(member_words)
+        head = [m, len(layout.exprs), layout.n_scalars, layout.own_points, own_tail, len(segments), off_seg, len(groups), off_groups,
+                off_members, off_lane, len(self.lane.words)]
+        assert len(head) == VM_HDR
+        body = head + [w for s in segments for w in s] + [w for g in groups for w in g] + member_words
+        self.words = np.concatenate([np.array(body, dtype=np.uint32), self.lane.words])
+        self.circuits, self.off_lane = m, off_lane
+        self.lowered, self.n_columns, self.n_vals = self.lane.lowered, self.lane.n_columns, self.lane.n_vals
+        self.inst_rows, self.inst_elems = self.lane.inst_rows, self.lane.inst_elems
+
+    def instance_row(self, inst_cols) -> List[int]:
+        """one CIRCUIT's instance values as its lane reads them (``TermsPlan.instance_row``)"""
+        return self.lane.instance_row(inst_cols)
+
+
 def proof_terms_ints(vk: VerifyingKey, instance, proof: bytes, layout: Optional[ProofLayout] = None):
     """The integer twin of the per-proof part, without r_b: (challenges, own scalars, shared scalars, points) of one proof in the device
     layout -- sum own[j] * points[j] + sum shared[i] * (shared point i) is the R of ``verify_opening`` and points[-1] its L.  Raises
     ``MalformedProof`` where ``verify_proof`` is False on structural grounds."""
     layout = layout or ProofLayout(vk.cs, vk.domain.k)
-    inst_cols = _instance_columns(vk.cs, instance)
+    inst_cols = _layout_instances(layout, instance)
     points, evals = read_proof_ints(layout, proof)
     ch = transcript_challenges(layout, _vk_digest(vk), inst_cols, proof, [p[1].to_bytes(32, "little") for p in points])   # y_bytes: "halo2" only
     own, shared = terms_from_challenges(layout, vk.domain.omega, inst_cols, evals, ch)
@@ -574,7 +716,9 @@ def derive_randomizer(seed, index: int) -> int:
 
 # ---- the public object ---------------------------------------------------------------------------------------------------------------------
 class BatchVerifier:
-    """Collects single-circuit proofs of one ``vk`` and checks them together (the module's docstring says how).
+    """Collects proofs of one ``vk`` and checks them together (the module's docstring says how): single-circuit proofs, or with
+    ``circuits=m`` (2 .. 64) ``create_proof_multi`` proofs of m circuits each -- ``add_proof(instances, proof)`` then takes the m
+    instances of the proof, and everything below means per PROOF what it means for single-circuit proofs.
 
     ``params`` needs ``g2`` / ``s_g2`` only.  ``add_proof(instance, proof)`` takes what ``verify_proof`` takes and returns the proof's
     index.  ``finalize(trapdoor=None)`` is True when every added proof verifies -- one pairing check for the whole batch, or with the
@@ -586,7 +730,7 @@ class BatchVerifier:
     ``pairing="device"`` -- and ``failing(method="each")`` names its False entries: the same lists, at a cost that does not grow with
     the number of failing proofs.  Every proof has a weight r_b in
     [1, r): from ``secrets`` when ``seed`` is None, else derived from (seed, index); ``randomizers`` shows them.
-    A batch of ``create_proof_multi`` proofs is out of scope, and an instance column may hold 64 rows at most (the terms kernel's
+    An instance column may hold 64 rows at most (the terms kernel's
     limit; ``finalize`` raises ValueError beyond it).  ``close()`` gives the numerator's program back to the library.
     ``pairing="device"`` runs the pairing of every check on the GPU (``device_pairing``) instead of on host integers: the same
     booleans, and ``timings["pairing"]`` keeps its meaning.
@@ -596,9 +740,11 @@ class BatchVerifier:
     each call -- the device's work surfaces in ``terms``, which ends with the download -- and only their sum means anything.
     ``encoding="evm"`` takes proofs in the other wire format (``create_proof(..., encoding="evm")``): the device reads uncompressed
     big-endian points with a curve check in place of the square root (``hm_verify_read_proofs_evm_dev``), the transcript is Keccak
-    (``hm_verify_transcript_evm_dev`` with ``transcript="device"``), and terms, sums and pairing are the same calls as before."""
+    (``hm_verify_transcript_evm_dev`` with ``transcript="device"``), and terms, sums and pairing are the same calls as before;
+    multi-circuit proofs in this encoding are the one combination left out (``circuits`` > 1 with "evm": ValueError)."""
 
-    def __init__(self, params, vk: VerifyingKey, seed=None, pairing: str = "host", transcript: str = "host", encoding: str = "halo2"):
+    def __init__(self, params, vk: VerifyingKey, seed=None, pairing: str = "host", transcript: str = "host", encoding: str = "halo2",
+                 circuits: int = 1):
         check_encoding(encoding, "BatchVerifier")
         if pairing not in device_pairing.MODES:
             raise ValueError(f"BatchVerifier: pairing must be one of {device_pairing.MODES}, got {pairing!r}")
@@ -606,7 +752,8 @@ class BatchVerifier:
             raise ValueError(f"BatchVerifier: transcript must be one of {device_transcript.MODES}, got {transcript!r}")
         self.params, self.vk, self.seed, self.pairing, self.transcript = params, vk, seed, pairing, transcript
         self.encoding = encoding
-        self.layout = ProofLayout(vk.cs, vk.domain.k, encoding)
+        self.layout = ProofLayout(vk.cs, vk.domain.k, encoding, circuits)   # ValueError: circuits outside 1 .. 64, or "evm" with several
+        self.circuits = self.layout.circuits
         self._digest = _vk_digest(vk)
         self._shared = shared_points(vk, self.layout)
         # verify_proof opens no identity: with a queried fixed or sigma commitment that is one, no proof of this vk verifies
@@ -630,7 +777,7 @@ class BatchVerifier:
         return tuple(self._rand)
 
     def add_proof(self, instance, proof: bytes) -> int:
-        self._instances.append(_instance_columns(self.vk.cs, instance))
+        self._instances.append(_layout_instances(self.layout, instance))
         self._proofs.append(bytes(proof))
         i = len(self._proofs) - 1
         self._rand.append(secrets.randbelow(R - 1) + 1 if self.seed is None else derive_randomizer(self.seed, i))
@@ -648,10 +795,11 @@ class BatchVerifier:
         return out
 
     # ---- the device part ------------------------------------------------------------------------------------------------------------------
-    def _plan_for(self, inst_rows: Sequence[int]) -> "TermsPlan":
-        key = tuple(inst_rows)
+    def _plan_for(self, inst_rows: Sequence[int]):
+        key = tuple(inst_rows) if self.circuits == 1 else (tuple(inst_rows), self.circuits)
         if key not in self._plans:
-            self._plans[key] = TermsPlan(self.layout, self.vk.domain.omega, inst_rows)
+            make = TermsPlan if self.circuits == 1 else MultiTermsPlan
+            self._plans[key] = make(self.layout, self.vk.domain.omega, inst_rows)
         if self._program is None:
             self._program = ev.CompiledGraph(**self._plans[key].lowered)
         return self._plans[key]
@@ -667,6 +815,26 @@ class BatchVerifier:
             self.close()
         except Exception:                                        # the library may be gone at interpreter shutdown
             pass
+
+    def _circuit_instances(self) -> list:
+        """the instance columns of every circuit of every proof, proof after proof: what the plan's rows are sized and filled from"""
+        return list(self._instances) if self.circuits == 1 else [one for inst in self._instances for one in inst]
+
+    def _preamble_instances(self) -> list:
+        """per proof, the columns its transcript absorbs behind the key's digest: circuit 0's, then circuit 1's, ..."""
+        return self._instances if self.circuits == 1 else [[col for one in inst for col in one] for inst in self._instances]
+
+    def _queue_terms(self, plan, B: int, d_records, d_scalars, d_inst, d_bad, d_own, d_shared, d_h2_r, d_h2_l, stream) -> None:
+        """the terms kernel on ``stream``: ``hm_verify_terms_dev``, or for multi-circuit proofs ``hm_verify_terms_multi_dev``"""
+        lib = _lib.load()
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        head = (ctypes.c_uint64(self._program.handle), plan.words.ctypes.data_as(u32p), len(plan.words), plan.n_columns, 4, B)
+        tail = (vp(d_records), vp(d_scalars), vp(d_inst), ctypes.cast(vp(d_bad), u32p), vp(d_own), vp(d_shared), vp(d_h2_r), vp(d_h2_l), stream)
+        if self.circuits == 1:
+            _lib.check(lib.hm_verify_terms_dev(*head, *tail))
+        else:
+            _lib.check(lib.hm_verify_terms_multi_dev(*head, self.circuits, *tail))
 
     def _queue_read(self, d_proofs, d_table, d_bases, d_tail, d_ybytes, d_scalars, d_bad, stream) -> None:
         """the read kernel of the layout's encoding on the current stream; ``d_ybytes`` is None for "evm", which has no such array"""
@@ -717,12 +885,12 @@ class BatchVerifier:
 
         # the transcripts: everything a proof's challenges depend on is on the host now
         zero_record = [0] * (len(RECORD) + 1)
-        records, inst_rows = [zero_record] * B, [None] * B
-        plan = self._plan_for([max((len(inst[c]) for inst in self._instances), default=0) for c in range(self.vk.cs.num_instance)])
+        records = [zero_record] * B
+        plan = self._plan_for([max((len(inst[c]) for inst in self._circuit_instances()), default=0) for c in range(self.vk.cs.num_instance)])
         t_plan = time.perf_counter() - t1
+        inst_rows = [plan.instance_row(inst) for inst in self._circuit_instances()]
         for b in range(B):
             bad[b] = bad[b] or bool(dev_bad[b])
-            inst_rows[b] = plan.instance_row(self._instances[b])
             if not bad[b]:
                 ch = transcript_challenges(lay, self._digest, self._instances[b], self._proofs[b],
                                            None if evm else [bytes(row) for row in ybytes[b]])
@@ -735,10 +903,7 @@ class BatchVerifier:
         d_shared = torch.empty((B, n_shared, 4), dtype=torch.int64, device=dev)
         d_h2_r, d_h2_l = torch.empty((B, 4), dtype=torch.int64, device=dev), torch.empty((B, 4), dtype=torch.int64, device=dev)
         t3 = time.perf_counter()
-        u32p = ctypes.POINTER(ctypes.c_uint32)
-        _lib.check(lib.hm_verify_terms_dev(ctypes.c_uint64(self._program.handle), plan.words.ctypes.data_as(u32p), len(plan.words),
-                                           plan.n_columns, 4, B, vp(d_records), vp(d_scalars), vp(d_inst), ctypes.cast(vp(d_bad), u32p),
-                                           vp(d_own), vp(d_shared), vp(d_h2_r), vp(d_h2_l), stream))
+        self._queue_terms(plan, B, d_records, d_scalars, d_inst, d_bad, d_own, d_shared, d_h2_r, d_h2_l, stream)
         bad = [bool(x) for x in d_bad.cpu().numpy()]              # the terms kernel flags x^n = 1 and its kin
         t4 = time.perf_counter()
         st = dict(B=B, bad=bad, d_bases=d_bases, d_scalars=d_scalars, d_own=d_own, d_shared=d_shared, d_h2_r=d_h2_r, d_h2_l=d_h2_l,
@@ -766,13 +931,13 @@ class BatchVerifier:
                 raw[b] = np.frombuffer(p, dtype=np.uint8)
         n_shared, own = len(lay.shared_keys), lay.own_points
         t1 = time.perf_counter()
-        plan = self._plan_for([max((len(inst[c]) for inst in self._instances), default=0) for c in range(self.vk.cs.num_instance)])
+        plan = self._plan_for([max((len(inst[c]) for inst in self._circuit_instances()), default=0) for c in range(self.vk.cs.num_instance)])
         t2 = time.perf_counter()
         up = lambda rows: torch.from_numpy(fr_array(rows).view(np.int64)).to(dev)
         records = np.zeros((B, len(RECORD) + 1, 4), dtype=np.uint64)          # the challenges are the device's; r_b stands behind them
         records[:, len(RECORD)] = fr_array(self._rand)
-        d_records, d_inst = torch.from_numpy(records.view(np.int64)).to(dev), up([plan.instance_row(inst) for inst in self._instances])
-        preamble = device_transcript.upload_preamble(self._digest, self._instances, dev, self.encoding)
+        d_records, d_inst = torch.from_numpy(records.view(np.int64)).to(dev), up([plan.instance_row(inst) for inst in self._circuit_instances()])
+        preamble = device_transcript.upload_preamble(self._digest, self._preamble_instances(), dev, self.encoding)
         d_proofs = torch.from_numpy(raw).to(dev)
         d_table = torch.from_numpy(lay.slot_table.view(np.int32)).to(dev)
         d_bad = torch.tensor([int(x) for x in bad], dtype=torch.int32, device=dev)   # the read kernel only ever sets a flag
@@ -788,16 +953,15 @@ class BatchVerifier:
         t3 = time.perf_counter()
         self._queue_read(d_proofs, d_table, d_bases, d_tail, d_ybytes, d_scalars, d_bad, stream)
         t4 = time.perf_counter()
-        device_transcript.challenges(lay, self._digest, self._instances, d_proofs, d_ybytes, d_bad, d_records, preamble=preamble, d_table=d_table)
+        device_transcript.challenges(lay, self._digest, self._preamble_instances(), d_proofs, d_ybytes, d_bad, d_records, preamble=preamble, d_table=d_table)
         t5 = time.perf_counter()
-        _lib.check(lib.hm_verify_terms_dev(ctypes.c_uint64(self._program.handle), plan.words.ctypes.data_as(u32p), len(plan.words),
-                                           plan.n_columns, 4, B, vp(d_records), vp(d_scalars), vp(d_inst), ctypes.cast(vp(d_bad), u32p),
-                                           vp(d_own), vp(d_shared), vp(d_h2_r), vp(d_h2_l), stream))
+        self._queue_terms(plan, B, d_records, d_scalars, d_inst, d_bad, d_own, d_shared, d_h2_r, d_h2_l, stream)
         bad = [bool(x) for x in d_bad.cpu().numpy()]              # the one download: what the three kernels flagged
         t6 = time.perf_counter()
         st = dict(B=B, bad=bad, d_bases=d_bases, d_scalars=d_scalars, d_own=d_own, d_shared=d_shared, d_h2_r=d_h2_r, d_h2_l=d_h2_l,
                   d_sum=torch.zeros((n_shared, 4), dtype=torch.int64, device=dev), d_ybytes=d_ybytes, d_bad=d_bad,
-                  d_proofs=d_proofs, d_table=d_table, d_records=d_records, preamble=preamble)   # what the transcript call took (tools/batch_verify_time.py)
+                  d_proofs=d_proofs, d_table=d_table, d_records=d_records, preamble=preamble,   # what the transcript call took (tools/batch_verify_time.py)
+                  d_inst=d_inst, plan=plan)                                                     # ... and the terms call
         self.timings = dict(read=t1 - t0 + t4 - t3, plan=t2 - t1, transcript=t5 - t4, upload=t3 - t2, terms=t6 - t5, msm=0.0, pairing=0.0,
                             sums=0.0, verdict_pairing=0.0)
         self._state = st
@@ -974,29 +1138,29 @@ class BatchVerifier:
 
 
 def verify_proofs(params, vk: VerifyingKey, instances, proofs, seed=None, trapdoor: int = None, pairing: str = "host",
-                  transcript: str = "host", encoding: str = "halo2") -> bool:
+                  transcript: str = "host", encoding: str = "halo2", circuits: int = 1) -> bool:
     """True when every ``proofs[i]`` is a valid single-circuit proof of ``vk`` for ``instances[i]``: one ``BatchVerifier``, one check
     (``pairing`` / ``transcript``: where that check's pairing and the proofs' transcripts run, ``encoding``: the proofs' wire format,
-    as on ``BatchVerifier``)"""
+    ``circuits=m``: every proof is a ``create_proof_multi`` proof and ``instances[i]`` its m instances, as on ``BatchVerifier``)"""
     check_encoding(encoding, "verify_proofs")
     instances, proofs = list(instances), list(proofs)
     if len(instances) != len(proofs):
         raise ValueError("verify_proofs: one instance per proof")
-    bv = BatchVerifier(params, vk, seed, pairing=pairing, transcript=transcript, encoding=encoding)
+    bv = BatchVerifier(params, vk, seed, pairing=pairing, transcript=transcript, encoding=encoding, circuits=circuits)
     for instance, proof in zip(instances, proofs):
         bv.add_proof(instance, proof)
     return bv.finalize(trapdoor)
 
 
 def verify_each(params, vk: VerifyingKey, instances, proofs, seed=None, trapdoor: int = None, pairing: str = "host",
-                transcript: str = "host", encoding: str = "halo2") -> List[bool]:
+                transcript: str = "host", encoding: str = "halo2", circuits: int = 1) -> List[bool]:
     """[is ``proofs[i]`` a valid single-circuit proof of ``vk`` for ``instances[i]``]: one ``BatchVerifier``, its ``verdicts`` -- the
     per-proof sums in one launch and, with ``pairing="device"``, one pairing call for all proofs (keywords as on ``verify_proofs``)"""
     check_encoding(encoding, "verify_each")
     instances, proofs = list(instances), list(proofs)
     if len(instances) != len(proofs):
         raise ValueError("verify_each: one instance per proof")
-    bv = BatchVerifier(params, vk, seed, pairing=pairing, transcript=transcript, encoding=encoding)
+    bv = BatchVerifier(params, vk, seed, pairing=pairing, transcript=transcript, encoding=encoding, circuits=circuits)
     for instance, proof in zip(instances, proofs):
         bv.add_proof(instance, proof)
     return bv.verdicts(trapdoor)

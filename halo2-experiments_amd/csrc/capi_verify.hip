@@ -75,6 +75,32 @@ int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_word
                           (hipStream_t)stream);
 } HM_API_CATCH("hm_verify_terms_dev")
 
+int hm_verify_terms_multi_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
+                              uint32_t circuits, const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad,
+                              void* d_own, void* d_shared, void* d_h2_r, void* d_h2_l, void* stream) try {
+  const std::string who = "hm_verify_terms_multi_dev";
+  if (!plan || !d_records || !d_scalars || !d_instance || !d_bad || !d_own || !d_shared || !d_h2_r || !d_h2_l)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": null argument");
+  if (circuits == 0 || circuits > VM_MAX_CIRCUITS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= circuits <= 64");
+  if (n_proofs == 0 || n_proofs > ((size_t)1 << 16)) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n_proofs <= 2^16");
+  if (n_plan_words > ((size_t)1 << 24)) return hm_fail(HM_ERR_BAD_ARG, who + ": the plan is longer than 2^24 words");
+  if (n_columns == 0 || n_columns > GE_MAX_COLUMNS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 .. 256 columns");
+  if (((uintptr_t)d_records | (uintptr_t)d_scalars | (uintptr_t)d_instance | (uintptr_t)d_own | (uintptr_t)d_shared | (uintptr_t)d_h2_r |
+       (uintptr_t)d_h2_l | (uintptr_t)d_bad) & 3u)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": a buffer is not 4-byte aligned");
+  if (const char* why = vtm_plan_problem(plan, n_plan_words, n_columns, circuits)) return hm_fail(HM_ERR_BAD_ARG, why);
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  GraphProgram* g = nullptr;
+  for (auto& have : ctx->graphs)
+    if (have->handle == graph) g = have.get();
+  if (!g) return hm_fail(HM_ERR_BAD_ARG, who + ": unknown program handle");
+  return verify_terms_multi_run(*ctx, *g, plan, n_plan_words, n_columns, n_dynamic, n_proofs, circuits, (const uint32_t*)d_records,
+                                (const uint32_t*)d_scalars, (const uint32_t*)d_instance, d_bad, (uint32_t*)d_own, (uint32_t*)d_shared,
+                                (uint32_t*)d_h2_r, (uint32_t*)d_h2_l, (hipStream_t)stream);
+} HM_API_CATCH("hm_verify_terms_multi_dev")
+
 // ---- the per-proof sums (verify_sums.inc, verify.hip) -------------------------------------------------------------------------------
 int hm_verify_proof_sums_dev(const void* d_bases_xy, size_t n_proofs, uint32_t own_points, uint32_t shared_points, const void* d_own,
                              const void* d_shared, const void* d_h2_r, const void* d_h2_l, const uint32_t* d_bad, void* d_pairs_xy,

@@ -588,6 +588,11 @@ int verify_colsum_run(const uint32_t* d_rows, uint32_t cols, size_t lo, size_t h
 int verify_terms_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
                      const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst, uint32_t* d_bad, uint32_t* d_own,
                      uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream);
+// The same for proofs of `circuits` circuits each (create_proof_multi): one wavefront per proof, lane c is circuit c; `plan` is the
+// multi plan (verify_terms.inc, vtm_plan_problem).  Asynchronous on `stream`.
+int verify_terms_multi_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic,
+                           size_t n_proofs, uint32_t circuits, const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst,
+                           uint32_t* d_bad, uint32_t* d_own, uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream);
 // The pair (L_b, -R_b) of every proof's own opening check, one workgroup per proof (verify_sums.inc): 2 rows of affine Montgomery
 // words per proof, zeros for a proof whose flag is set.  Asynchronous on `stream`.
 int verify_sums_run(const uint32_t* d_bases, size_t n_proofs, uint32_t own_points, uint32_t shared_points, const uint32_t* d_own,

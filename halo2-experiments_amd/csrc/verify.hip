@@ -1,6 +1,7 @@
 // verify.hip -- the device side of a batch verification (batch_verifier.py is the caller): the kernels and the drivers
 //   verify_read_run, verify_colsum_run    a batch of proofs read slot by slot, the column sums of its shared scalars (verify_read.inc)
 //   verify_terms_run                      the per-proof terms of the opening checks, one lane per proof (verify_terms.inc)
+//   verify_terms_multi_run                the same for multi-circuit proofs: a wavefront per proof, a lane per circuit
 //   verify_sums_run                       the two G1 points of every proof's own check, one workgroup per proof (verify_sums.inc)
 //   blake2b_run, verify_transcript_run    Blake2b-512 and the proofs' transcripts on it, one lane per proof (transcript.inc)
 //   keccak256_run, verify_read_evm_run,   Keccak-256, and the read and the transcripts of proofs in the EVM encoding: uncompressed
@@ -202,6 +203,97 @@ int verify_terms_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size
   // pageable source: the runtime has taken its copy of the plan when this returns (as the witness checker's table)
   HM_HIP_CHECK(hipMemcpyAsync(d_plan, plan, n_words * 4, hipMemcpyHostToDevice, stream));
   hipLaunchKernelGGL(verify_terms_kernel, dim3(blocks), dim3(GE_THREADS), 0, stream, (const uint32_t*)d_plan, (const uint32_t*)g.d_consts,
+                     (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src, v.result_prev, g.n_static, ws, (uint32_t)n_proofs, d_records, d_evals,
+                     d_inst, d_bad, d_own, d_shared, d_h2r, d_h2l);
+  HM_HIP_CHECK(hipGetLastError());
+  return aux_release(ctx, slot, stream);
+}
+
+// ---- the terms of multi-circuit proofs: a wavefront per proof, a lane per circuit ---------------
+// The sum over the lanes of ONE wavefront, by cross-lane moves alone: every lane of the wave calls it (an idle lane brings zero), every
+// lane returns lane 0's total.  No LDS, no atomics, nothing leaves the wave.
+__device__ __forceinline__ Fr vtm_wave_sum(Fr acc) {
+  static_assert(VM_MAX_CIRCUITS == 64, "a gfx950 wavefront has 64 lanes");
+  for (int off = 32; off > 0; off >>= 1) {
+    Fr other;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) other.l[i] = __shfl_down(acc.l[i], off, 64);
+    HM_DECLARE(other, 3.0);
+    acc = vt_add(acc, other);                                    // lanes at and above 64 - off add their own word: never read below
+  }
+#pragma unroll
+  for (int i = 0; i < 9; ++i) acc.l[i] = __shfl(acc.l[i], 0, 64);
+  return acc;
+}
+
+__global__ __launch_bounds__(GE_THREADS) void verify_terms_multi_kernel(const uint32_t* __restrict__ mp, const uint32_t* __restrict__ consts,
+                                                                        const GraphCalc* __restrict__ calcs, uint32_t n_calc,
+                                                                        uint32_t result_src, uint32_t result_prev, uint32_t n_static,
+                                                                        uint32_t* __restrict__ ws, uint32_t n_proofs,
+                                                                        const uint32_t* __restrict__ records, const uint32_t* __restrict__ evals,
+                                                                        const uint32_t* __restrict__ inst, uint32_t* __restrict__ bad,
+                                                                        uint32_t* __restrict__ own, uint32_t* __restrict__ shared,
+                                                                        uint32_t* __restrict__ h2r, uint32_t* __restrict__ h2l) {
+  static_assert(GE_THREADS % 64 == 0, "whole wavefronts per workgroup");
+  const uint32_t T = gridDim.x * GE_THREADS, lane = blockIdx.x * GE_THREADS + threadIdx.x;
+  const size_t b = lane / 64;                                    // the same for a whole wavefront
+  const uint32_t c = lane % 64;
+  if (b >= n_proofs) return;
+  const uint32_t* lp = vtm_lane_plan(mp);
+  const uint32_t circuits = mp[VM_CIRCUITS];
+  const bool active = c < circuits;
+  uint32_t* my_own = own + b * mp[VM_N_OWN] * 8;
+  uint32_t* my_shared = shared + b * lp[VT_N_SHARED] * 8;
+  vtm_zero_lane(mp, c, my_own, my_shared, h2r + b * 8, h2l + b * 8);
+  if (bad[b]) return;
+  const VtMem m{ws, T, lane};
+  bool ok = true;
+  Fr term = fe_zero<FrParams>();
+  HM_DECLARE(term, 3.0);
+  if (active) {
+    ok = vtm_phase_a(mp, m, c, records + b * VT_REC * 8, evals + b * mp[VM_N_SCALARS] * 8, inst + (b * circuits + c) * lp[VT_INST_ELEMS] * 8);
+    const VerifySource from{lp, m, n_static};
+    const Fr fold = ge_reduce(ge_run(from, consts, calcs, n_calc, result_src, result_prev, ws + (size_t)vt_ws_program(lp) * 9 * T, T, lane));
+    term = vtm_numerator_term(mp, m, c, fold);
+  }
+  const Fr num = vtm_wave_sum(term);
+  VtmShare mine{fe_zero<FrParams>(), fe_zero<FrParams>(), fe_zero<FrParams>(), true};
+  HM_DECLARE(mine.r_outer, 3.0);
+  if (active) {
+    mine = vtm_phase_b(mp, m, c, num, my_own, my_shared);
+    ok = ok && mine.ok;
+  }
+  const Fr r_outer = vtm_wave_sum(mine.r_outer);
+  const bool failed = __ballot(active && !ok) != 0;               // any lane of the proof
+  if (failed) {
+    vtm_zero_lane(mp, c, my_own, my_shared, h2r + b * 8, h2l + b * 8);
+    if (c == 0) bad[b] = 1;
+  } else if (c == 0) {
+    vtm_finish(mp, m, r_outer, mine, my_own, my_shared, h2r + b * 8, h2l + b * 8);
+  }
+}
+
+// as verify_terms_run, for proofs of `circuits` circuits each: T = 64 lanes per proof
+int verify_terms_multi_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic,
+                           size_t n_proofs, uint32_t circuits, const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst,
+                           uint32_t* d_bad, uint32_t* d_own, uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream) {
+  GraphVariant& v = g.variant[0];
+  if (!v.ready) return hm_fail(HM_ERR_INTERNAL, "verify terms multi: the program has no lowered form");
+  if (n_columns != g.n_columns) return hm_fail(HM_ERR_BAD_ARG, "verify terms multi: the program was built for another number of columns");
+  if (n_dynamic != g.n_dynamic || n_dynamic != 4)
+    return hm_fail(HM_ERR_BAD_ARG, "verify terms multi: the program must take beta, gamma, theta, y as its per-call constants");
+  if (const char* why = vtm_plan_problem(plan, n_words, n_columns, circuits)) return hm_fail(HM_ERR_BAD_ARG, why);
+  const size_t lanes = n_proofs * 64;
+  const uint32_t blocks = (uint32_t)((lanes + GE_THREADS - 1) / GE_THREADS), T = blocks * GE_THREADS;
+  const size_t slots = (size_t)vt_ws_program(vtm_lane_plan(plan)) + v.n_slots;
+  AuxSlot* slot = aux_acquire(ctx, stream);
+  if (!slot) return HM_ERR_HIP;
+  uint32_t* ws = (uint32_t*)slot->scratch.ensure(slots * 9 * T * 4);
+  uint32_t* d_plan = (uint32_t*)slot->args.ensure(n_words * 4);
+  if (!ws || !d_plan) return hm_fail(HM_ERR_HIP, "verify terms multi: workspace allocation failed");
+  // pageable source: the runtime has taken its copy of the plan when this returns (as verify_terms_run)
+  HM_HIP_CHECK(hipMemcpyAsync(d_plan, plan, n_words * 4, hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(verify_terms_multi_kernel, dim3(blocks), dim3(GE_THREADS), 0, stream, (const uint32_t*)d_plan, (const uint32_t*)g.d_consts,
                      (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src, v.result_prev, g.n_static, ws, (uint32_t)n_proofs, d_records, d_evals,
                      d_inst, d_bad, d_own, d_shared, d_h2r, d_h2l);
   HM_HIP_CHECK(hipGetLastError());

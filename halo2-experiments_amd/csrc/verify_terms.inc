@@ -27,6 +27,7 @@
 //             array, and r_b u, r_b for [h'].
 // The two phases are host-callable: host_check.cpp runs them under bound tracking (hc_verify_terms) with the numerator given.
 // Included inside namespace hm by verify.hip, which holds the kernel and its driver, and by capi_verify.hip for the plan's check.
+// A multi-circuit proof takes a wavefront, one lane per circuit: the second half of this file (vtm_*, DESIGN.md section 29).
 
 enum : uint32_t {
   VT_K, VT_N_SCALARS, VT_N_VALS, VT_N_LAGRANGE, VT_N_INSTQ, VT_N_SUPER, VT_N_SETS, VT_PIECES, VT_N_OWN, VT_N_SHARED, VT_N_ROT, VT_N_COLS,
@@ -159,11 +160,19 @@ HM_HD Fr vt_inv(const Fr& a) {
 }
 
 // -> false when x^n = 1 or x = 0 (the lane is then flagged; what it computes is defined, and discarded)
+// phase a behind the loads: the record and the evaluations stand in the workspace (the multi-circuit kernel gathers them itself)
+HM_HD bool vt_phase_a_rest(const uint32_t* plan, const VtMem& m, const uint32_t* inst);
+
 HM_HD bool vt_phase_a(const uint32_t* plan, const VtMem& m, const uint32_t* rec, const uint32_t* evals, const uint32_t* inst) {
-  const uint32_t* cst = plan + plan[VT_OFF_CONSTS];
-  const uint32_t wc = plan[VT_N_VALS], s_l0 = plan[VT_S_L0];
+  const uint32_t wc = plan[VT_N_VALS];
   for (uint32_t j = 0; j < VT_REC; ++j) vt_store(m, wc + j, fe_canonical(vt_from_ext(rec + 8 * (size_t)j)));   // canonical: ge_run reads four of them as constants
   for (uint32_t j = 0; j < plan[VT_N_SCALARS]; ++j) vt_store(m, j, vt_from_ext(evals + 8 * (size_t)j));
+  return vt_phase_a_rest(plan, m, inst);
+}
+
+HM_HD bool vt_phase_a_rest(const uint32_t* plan, const VtMem& m, const uint32_t* inst) {
+  const uint32_t* cst = plan + plan[VT_OFF_CONSTS];
+  const uint32_t wc = plan[VT_N_VALS], s_l0 = plan[VT_S_L0];
   const Fr x = vt_load(m, wc + VT_X), one = fe_one<FrParams>();
   Fr xn = x;
   for (uint32_t i = 0; i < plan[VT_K]; ++i) xn = fe_sqr(xn);
@@ -265,4 +274,225 @@ HM_HD bool vt_phase_b(const uint32_t* plan, const VtMem& m, const Fr& num, uint3
   vt_to_ext(h2r, fe_mul(u, rb));
   vt_to_ext(h2l, rb);
   return ok;
+}
+
+// ---- a multi-circuit proof (create_proof_multi): one WAVEFRONT per proof, lane c = circuit c ------------------------------------------
+// The multi plan (batch_verifier.MultiTermsPlan) wraps the plan of ONE circuit -- the LANE plan, the words above, checked by
+// vt_plan_problem as they are -- and says where a lane finds its circuit in the proof:
+//   header      VM_* below; VM_N_SCALARS / VM_N_OWN are the PROOF's counts, VM_OWN_TAIL its first own row no circuit owns (random, the
+//               h pieces, [h]), VM_EXPRS the E expressions one circuit folds in y
+//   segments    VM_N_SEG x (count, base, stride): the lane's evaluation slots in order -- the next `count` slots of lane c are the
+//               proof's scalars base + c * stride + i
+//   groups      VM_N_GROUPS x (base, count): lane c owns the own rows base + c * count + i (its advice, lookup and permutation points)
+//   members     per rotation set of the lane plan, in its order: p, the members that belong to a circuit (they stand first in the
+//               set), then (target, stride) per member: circuit c's row is target + c * stride; a member behind the first p is the
+//               proof's (a shared point, the h pieces, the random point), stride 0, target as in the lane plan
+// Inside a set the members of the PROOF stand circuit 0's first, then circuit 1's, ..., then the proof's own: member j of circuit c has
+// y'^(c p + j), member j of the proof's y'^(m p + j - p).  The numerator is upstream's one running value
+// N = sum_c y^(E (m - 1 - c)) N_c with N_c the lane's own fold, and sum coeff * r_eval is summed over the lanes likewise: the kernel
+// folds both with cross-lane moves (verify.hip), hc_verify_terms_multi with plain loops.  Lane 0 writes what belongs to the proof.
+enum : uint32_t {
+  VM_CIRCUITS, VM_EXPRS, VM_N_SCALARS, VM_N_OWN, VM_OWN_TAIL, VM_N_SEG, VM_OFF_SEG, VM_N_GROUPS, VM_OFF_GROUPS, VM_OFF_MEMBERS, VM_OFF_LANE,
+  VM_LANE_WORDS, VM_HDR
+};
+constexpr uint32_t VM_MAX_CIRCUITS = 64;                         // the lanes of a gfx950 wavefront, and prover.MAX_CIRCUITS
+
+HM_HD const uint32_t* vtm_lane_plan(const uint32_t* mp) { return mp + mp[VM_OFF_LANE]; }
+
+// nullptr, or why the multi plan is refused: after this every index a lane of ANY circuit takes from it lies inside its array
+inline const char* vtm_plan_problem(const uint32_t* p, size_t n_words, size_t n_columns, uint32_t circuits) {
+  if (circuits == 0 || circuits > VM_MAX_CIRCUITS) return "verify terms multi: need 1 <= circuits <= 64";
+  if (n_words < VM_HDR) return "verify terms multi: the plan is shorter than its header";
+  if (p[VM_CIRCUITS] != circuits) return "verify terms multi: the plan was built for another number of circuits";
+  const uint64_t words = n_words, last = circuits - 1;
+  if (p[VM_OFF_LANE] < VM_HDR || p[VM_OFF_LANE] > words || p[VM_LANE_WORDS] > words - p[VM_OFF_LANE])
+    return "verify terms multi: the lane plan lies outside the plan";
+  const uint32_t* lp = p + p[VM_OFF_LANE];
+  if (const char* why = vt_plan_problem(lp, p[VM_LANE_WORDS], n_columns)) return why;
+  if (p[VM_EXPRS] == 0 || p[VM_EXPRS] > (1u << 20)) return "verify terms multi: need 1 .. 2^20 expressions";
+  const uint32_t n_scalars = p[VM_N_SCALARS], n_own = p[VM_N_OWN], own_tail = p[VM_OWN_TAIL];
+  if (n_scalars == 0 || n_scalars > (1u << 22) || n_own == 0 || n_own > (1u << 22) || own_tail >= n_own)
+    return "verify terms multi: output sizes out of range";
+  if (p[VM_OFF_SEG] > words || (uint64_t)p[VM_N_SEG] * 3 > words - p[VM_OFF_SEG]) return "verify terms multi: the segments lie outside the plan";
+  uint64_t filled = 0;
+  for (uint32_t s = 0; s < p[VM_N_SEG]; ++s) {
+    const uint32_t* e = p + p[VM_OFF_SEG] + 3 * (size_t)s;
+    const uint64_t first = e[1] + last * e[2];                   // the LAST circuit's first scalar
+    if (first > n_scalars || e[0] > n_scalars - first) return "verify terms multi: a per-circuit stride leaves the proof's scalars";
+    filled += e[0];
+  }
+  if (filled != lp[VT_N_SCALARS]) return "verify terms multi: the segments do not fill the lane's evaluations";
+  if (p[VM_OFF_GROUPS] > words || (uint64_t)p[VM_N_GROUPS] * 2 > words - p[VM_OFF_GROUPS]) return "verify terms multi: the groups lie outside the plan";
+  for (uint32_t g = 0; g < p[VM_N_GROUPS]; ++g) {
+    const uint32_t* e = p + p[VM_OFF_GROUPS] + 2 * (size_t)g;
+    if (e[0] + (uint64_t)circuits * e[1] > own_tail) return "verify terms multi: a per-circuit stride leaves the proof's own rows";
+  }
+  uint64_t at = lp[VT_OFF_SETS], ext = p[VM_OFF_MEMBERS];
+  for (uint32_t i = 0; i < lp[VT_N_SETS]; ++i) {
+    const uint32_t t = lp[at], members = lp[at + 2];             // inside the lane plan: vt_plan_problem walked them
+    at += 3 + 2ull * t + (uint64_t)members * (1 + t);
+    if (ext + 1 + 2ull * members > words) return "verify terms multi: the members lie outside the plan";
+    const uint32_t per = p[ext];
+    if (per > members) return "verify terms multi: a set with more per-circuit members than members";
+    for (uint32_t j = 0; j < members; ++j) {
+      const uint32_t target = p[ext + 1 + 2ull * j], stride = p[ext + 2 + 2ull * j], index = target & VT_T_INDEX;
+      if (j < per) {
+        if ((target & (VT_T_SHARED | VT_T_H)) || index + last * stride >= own_tail)
+          return "verify terms multi: a per-circuit stride leaves the proof's own rows";
+      } else if (stride != 0 || (target & VT_T_H ? ((target & VT_T_SHARED) || index > n_own || lp[VT_PIECES] > n_own - index)
+                                                 : (index >= (target & VT_T_SHARED ? lp[VT_N_SHARED] : n_own)))) {
+        return "verify terms multi: a member's target out of range";
+      }
+    }
+    ext += 1 + 2ull * members;
+  }
+  return nullptr;
+}
+
+// a^e for an exponent every lane shares (a plan word): the bit tests are wave-uniform
+HM_HD Fr vtm_pow_uniform(const Fr& a, uint32_t e) {
+  Fr r = fe_one<FrParams>();
+  for (uint32_t bit = 32; bit-- > 0;) {
+    if (e >> bit) r = fe_sqr(r);                                 // nothing to square before the top bit
+    if ((e >> bit) & 1u) r = fe_mul(r, a);
+  }
+  return r;
+}
+// a^e, e < 64, for an exponent of the lane's own: six squarings and six products on every lane, the product kept by a select
+HM_HD Fr vtm_pow_lane(const Fr& a, uint32_t e) {
+  Fr r = fe_one<FrParams>();
+  for (uint32_t bit = 6; bit-- > 0;) {
+    r = fe_sqr(r);
+    const Fr with = fe_mul(r, a);
+    if ((e >> bit) & 1u) r = with;                               // a select: both values exist on every lane
+  }
+  return r;
+}
+
+// the rows lane c answers for, zeroed by the lane that may write them later (one lane's stores keep their order)
+HM_HD void vtm_zero_lane(const uint32_t* mp, uint32_t c, uint32_t* own, uint32_t* shared, uint32_t* h2r, uint32_t* h2l) {
+  if (c < mp[VM_CIRCUITS])
+    for (uint32_t g = 0; g < mp[VM_N_GROUPS]; ++g) {
+      const uint32_t* e = mp + mp[VM_OFF_GROUPS] + 2 * (size_t)g;
+      vt_zero_rows(own + 8 * ((size_t)e[0] + (size_t)c * e[1]), e[1]);
+    }
+  if (c == 0) {
+    vt_zero_rows(own + 8 * (size_t)mp[VM_OWN_TAIL], mp[VM_N_OWN] - mp[VM_OWN_TAIL]);
+    vt_zero_rows(shared, vtm_lane_plan(mp)[VT_N_SHARED]);
+    vt_zero_rows(h2r, 1);
+    vt_zero_rows(h2l, 1);
+  }
+}
+
+// phase a of lane c: the proof's record, the lane's evaluations gathered by the segments, then vt_phase_a_rest on its instance values
+HM_HD bool vtm_phase_a(const uint32_t* mp, const VtMem& m, uint32_t c, const uint32_t* rec, const uint32_t* evals, const uint32_t* inst) {
+  const uint32_t* lp = vtm_lane_plan(mp);
+  const uint32_t wc = lp[VT_N_VALS];
+  for (uint32_t j = 0; j < VT_REC; ++j) vt_store(m, wc + j, fe_canonical(vt_from_ext(rec + 8 * (size_t)j)));
+  uint32_t slot = 0;
+  for (uint32_t s = 0; s < mp[VM_N_SEG]; ++s) {
+    const uint32_t* e = mp + mp[VM_OFF_SEG] + 3 * (size_t)s;
+    const uint32_t* from = evals + 8 * ((size_t)e[1] + (size_t)c * e[2]);
+    for (uint32_t i = 0; i < e[0]; ++i) vt_store(m, slot++, vt_from_ext(from + 8 * (size_t)i));
+  }
+  return vt_phase_a_rest(lp, m, inst);
+}
+
+// lane c's term of the numerator: y^(E (m - 1 - c)) N_c
+HM_HD Fr vtm_numerator_term(const uint32_t* mp, const VtMem& m, uint32_t c, const Fr& own_fold) {
+  const Fr y_e = vtm_pow_uniform(vt_load(m, vtm_lane_plan(mp)[VT_N_VALS] + VT_Y), mp[VM_EXPRS]);
+  return fe_mul(own_fold, vtm_pow_lane(y_e, mp[VM_CIRCUITS] - 1 - c));
+}
+
+struct VtmShare {
+  Fr r_outer, z0_inv, zt;                                        // the lane's share of sum coeff * r_eval; 1 / z_0 and the vanishing value at u
+  bool ok;
+};
+
+// num: the PROOF's numerator, below 3r.  Lane c writes r_b x the scalars of circuit c's points; lane 0 those of the proof's as well.
+HM_HD VtmShare vtm_phase_b(const uint32_t* mp, const VtMem& m, uint32_t c, const Fr& num, uint32_t* own, uint32_t* shared) {
+  const uint32_t* plan = vtm_lane_plan(mp);
+  const uint32_t* cst = plan + plan[VT_OFF_CONSTS];
+  const uint32_t wc = plan[VT_N_VALS], wd = vt_ws_diff(plan), wb = vt_ws_basis(plan), n_super = plan[VT_N_SUPER];
+  vt_store(m, plan[VT_S_HX], fe_mul(num, vt_load(m, wc + VT_XN1_INV)));
+  const Fr x = vt_load(m, wc + VT_X), y2 = vt_load(m, wc + VT_Y2), v = vt_load(m, wc + VT_V), u = vt_load(m, wc + VT_U);
+  const Fr rb = vt_load(m, wc + VT_RB), xn = vt_load(m, wc + VT_XN), one = fe_one<FrParams>();
+  const Fr x_inv = vt_inv(x);
+  VtmShare out;
+  out.zt = one;
+  for (uint32_t s = 0; s < n_super; ++s) {
+    const Fr d = vt_sub(u, fe_mul(x, vt_const(cst, plan[VT_C_SUPER] + s)));
+    vt_store(m, wd + s, d);
+    out.zt = fe_mul(out.zt, d);
+  }
+  out.r_outer = fe_zero<FrParams>(), out.z0_inv = fe_zero<FrParams>(), out.ok = true;
+  Fr v_i = one;
+  size_t at = plan[VT_OFF_SETS];
+  const uint32_t* ext = mp + mp[VM_OFF_MEMBERS];
+  for (uint32_t i = 0; i < plan[VT_N_SETS]; ++i) {
+    const uint32_t t = plan[at], mask = plan[at + 1], members = plan[at + 2], per = ext[0];
+    const uint32_t* sup = plan + at + 3;
+    const uint32_t* dinv = sup + t;
+    at += 3 + 2 * (size_t)t;
+    Fr z = one;
+    for (uint32_t s = 0; s < n_super; ++s)
+      if (!((mask >> s) & 1u)) z = fe_mul(z, vt_load(m, wd + s));
+    if (i == 0) {
+      out.ok = !fe_is_zero_mod(z);
+      out.z0_inv = vt_inv(z);
+      z = one;
+    } else {
+      z = fe_mul(z, out.z0_inv);
+    }
+    const Fr outer = fe_mul(v_i, z);
+    v_i = fe_mul(v_i, v);
+    Fr xs = one;
+    for (uint32_t l = 1; l < t; ++l) xs = fe_mul(xs, x_inv);
+    for (uint32_t l = 0; l < t; ++l) {
+      Fr b = fe_mul(vt_const(cst, dinv[l]), xs);
+      for (uint32_t k = 0; k < t; ++k)
+        if (k != l) b = fe_mul(b, vt_load(m, wd + sup[k]));
+      vt_store(m, wb + l, b);
+    }
+    const Fr y_per = vtm_pow_uniform(y2, per);                   // y'^p: one circuit's step inside this set
+    const Fr y_tail = vtm_pow_uniform(y_per, mp[VM_CIRCUITS]);   // where the proof's members begin
+    Fr yj = vtm_pow_lane(y_per, c);
+    for (uint32_t j = 0; j < members; ++j) {
+      const uint32_t target = ext[1 + 2 * (size_t)j], index = (target & VT_T_INDEX) + c * ext[2 + 2 * (size_t)j];
+      const uint32_t* slots = plan + at + 1;
+      at += 1 + (size_t)t;
+      if (j == per) yj = y_tail;
+      if (j >= per && c != 0) continue;                          // the proof's members are lane 0's
+      const Fr coeff = fe_mul(outer, yj);
+      yj = fe_mul(yj, y2);
+      Fr r_eval = fe_zero<FrParams>();
+      for (uint32_t l = 0; l < t; ++l) r_eval = vt_add(r_eval, fe_mul(vt_load(m, wb + l), vt_load(m, slots[l])));
+      out.r_outer = vt_add(out.r_outer, fe_mul(coeff, r_eval));
+      Fr weighted = fe_mul(coeff, rb);
+      if (target & VT_T_H) {
+        for (uint32_t p = 0; p < plan[VT_PIECES]; ++p) {
+          vt_to_ext(own + 8 * (size_t)(index + p), weighted);
+          weighted = fe_mul(weighted, xn);
+        }
+      } else if (target & VT_T_SHARED) {
+        vt_to_ext(shared + 8 * (size_t)index, weighted);
+      } else {
+        vt_to_ext(own + 8 * (size_t)index, weighted);
+      }
+    }
+    ext += 1 + 2 * (size_t)members;
+  }
+  return out;
+}
+
+// lane 0, behind the fold: r_outer is the sum of every lane's share
+HM_HD void vtm_finish(const uint32_t* mp, const VtMem& m, const Fr& r_outer, const VtmShare& mine, uint32_t* own, uint32_t* shared, uint32_t* h2r,
+                      uint32_t* h2l) {
+  const uint32_t* plan = vtm_lane_plan(mp);
+  const uint32_t wc = plan[VT_N_VALS];
+  const Fr u = vt_load(m, wc + VT_U), rb = vt_load(m, wc + VT_RB);
+  vt_to_ext(shared + 8 * (size_t)(plan[VT_N_SHARED] - 1), vt_neg(fe_mul(r_outer, rb)));              // the generator
+  vt_to_ext(own + 8 * (size_t)(mp[VM_N_OWN] - 1), vt_neg(fe_mul(fe_mul(mine.z0_inv, mine.zt), rb))); // [h]
+  vt_to_ext(h2r, fe_mul(u, rb));
+  vt_to_ext(h2l, rb);
 }

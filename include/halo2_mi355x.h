@@ -831,6 +831,22 @@ int hm_verify_column_sum_dev(const void* d_rows, size_t n_rows, uint32_t columns
 int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
                         const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad, void* d_own, void* d_shared,
                         void* d_h2_r, void* d_h2_l, void* stream);
+/* terms of multi-circuit proofs (create_proof_multi): as hm_verify_terms_dev, for n_proofs proofs of `circuits` circuits each, 1 <=
+ * circuits <= 64.  One WAVEFRONT per proof, lane c is circuit c: a lane computes x^n, the Lagrange values and the instance evaluations
+ * of its own circuit, runs the SAME program on its own value row -- its circuit's evaluations, the shared ones, its instance
+ * evaluations -- and the proof's numerator sum_c y^(E (circuits - 1 - c)) N_c (E expressions per circuit) and the sum of
+ * coeff x r_eval meet by cross-lane moves inside the wave: no atomics, nothing leaves the wavefront.  Lanes at and above `circuits`
+ * take no part.  `plan` is the multi plan (csrc/verify_terms.inc, second half): the single-circuit plan of one lane, and where a lane
+ * finds its circuit's scalars and own rows in the proof; it is checked word by word, the per-circuit strides for the LAST circuit.
+ * d_records: n_proofs x 9 elements as above; d_scalars: n_proofs x (the proof's scalars) in the proof's order; d_instance: n_proofs x
+ * circuits rows, each as hm_verify_terms_dev takes one.  Output as above, per PROOF: d_own n_proofs x (the proof's own points) x 4
+ * words in the proof's point order, d_shared, d_h2_r, d_h2_l.  If any lane of a proof would divide by zero, or d_bad[b] is set on
+ * entry, the proof gets all-zero rows and d_bad[b] = 1.  At circuits = 1 the words are hm_verify_terms_dev's.  Asynchronous on `stream`.
+ * HM_ERR_BAD_ARG, with nothing launched: NULL arguments, circuits 0 or above 64, n_proofs 0 or above 2^16, a buffer that is not
+ * 4-byte aligned, a plan that fails its check or was built for another `circuits`, an unknown program handle. */
+int hm_verify_terms_multi_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
+                              uint32_t circuits, const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad,
+                              void* d_own, void* d_shared, void* d_h2_r, void* d_h2_l, void* stream);
 /* per-proof sums: the two G1 points of every proof's OWN opening check, one workgroup per proof, all proofs in one launch -- what a
  * verdict per proof needs where the MSMs above sum over proofs.  d_bases_xy: (n_proofs * own_points + shared_points + n_proofs) x 8
  * u64, affine Montgomery words, (0, 0) = the identity: the own points of every proof as hm_verify_read_proofs_dev left them, then the

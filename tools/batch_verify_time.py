@@ -17,7 +17,15 @@ alone, on a prepared batch, timed with events around the call, and ``read_kernel
 ``--encoding halo2|evm|both`` chooses the proofs' wire format (default halo2: the figures above).  With ``evm``, or ``both``, the
 rows stand under ``modes`` by "transcript/pairing/encoding"; ``both`` proves the same witnesses with the same seeds in the two
 encodings and interleaves them per B in one session, so that the "halo2" rows are the yardstick of the "evm" rows beside them.  The
-host transcript of "evm" is Keccak in pure Python (about half a millisecond per 136-byte block): large B is slow there."""
+host transcript of "evm" is Keccak in pure Python (about half a millisecond per 136-byte block): large B is slow there.
+
+``--circuits`` names the constraint systems; an INTEGER among its entries is a number of circuits per proof instead (``--circuits
+1,4,16,64``, with or without names beside them) and asks for the multi-circuit measurement in place of the one
+above: for every m and every B of ``--sizes``, in one session with the routes alternating, everything on the device --
+``finalize()`` and ``verdicts()`` of B ``create_proof_multi`` proofs of m circuits (``BatchVerifier(circuits=m)``); the same two over
+the B * m single-circuit proofs of the same witnesses (``create_proofs``), the yardstick; the host ``verify_proof_multi`` per proof,
+the oracle; and the terms kernel alone, events around the call on the prepared batch: ``hm_verify_terms_multi_dev`` on the B proofs,
+``hm_verify_terms_dev`` on B and on B * m single-circuit proofs."""
 import argparse
 import ctypes
 import json
@@ -85,6 +93,121 @@ def transcript_kernel_ms(bv, repeats):
             ms.append(start.elapsed_time(end))
     assert torch.equal(d_records, st["d_records"]) and not d_bad.any()
     return spread(ms)
+
+
+def terms_kernel_ms(bv, repeats):
+    """the terms kernel alone -- the entry the batch's ``circuits`` chooses -- on the arrays a prepared device-mode batch keeps: events
+    around the call, one warm-up; the outputs go to arrays of their own"""
+    st = bv._prepare()
+    dev = st["d_records"].device
+    out = [torch.empty_like(st[name]) for name in ("d_own", "d_shared", "d_h2_r", "d_h2_l")]
+    d_bad = torch.zeros(st["B"], dtype=torch.int32, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    ms = []
+    for i in range(repeats + 1):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        bv._queue_terms(st["plan"], st["B"], st["d_records"], st["d_scalars"], st["d_inst"], d_bad, *out, stream)
+        end.record()
+        end.synchronize()
+        if i:
+            ms.append(start.elapsed_time(end))
+    assert torch.equal(out[0], st["d_own"]) and torch.equal(out[1], st["d_shared"]) and not d_bad.any()
+    return spread(ms)
+
+
+def multi_circuit(name, counts, sizes, repeats):
+    """the multi-circuit measurement of one constraint system (the module's docstring): {m: {B: row}}"""
+    import prover_multi_cases as pmc
+
+    out, params, key = {"circuits_per_proof": {}}, None, None
+    try:
+        for m in counts:
+            cs, lay, adv, instances = pmc.build_multi(name, m)
+            if params is None:
+                params = ParamsKZG.setup(lay.k, pc.SRS_S)
+                vk = h.keygen_vk(params, cs, lay)
+                key = (vk, h.keygen_pk(params, vk, cs, lay, cosets=False))
+                out["k"] = lay.k
+            vk, pk = key
+            multi = [h.create_proof_multi(params, pk, adv, instances, seed) for seed in (2, 3)]
+            singles = h.create_proofs(params, pk, adv, instances, 100)
+            inst_arg = instances if m > 1 else instances[0]
+            oracle = []
+            for proof in multi[:1 if m >= 16 else 2]:
+                t0 = time.perf_counter()
+                assert h.verify_proof_multi(params, vk, instances, proof)
+                oracle.append((time.perf_counter() - t0) * 1e3)
+            rows = {"proof_bytes": len(multi[0]), "single_proof_bytes": len(singles[0]),
+                    "verify_proof_multi_per_proof": dict(spread(oracle), proofs=len(oracle))}
+
+            def route(B, which):
+                """one fresh BatchVerifier, everything on the device: (finalize ms from the constructor on, verdicts ms, the object,
+                the ms of the constructor and the add_proof calls alone)"""
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                if which == "multi":
+                    bv = h.BatchVerifier(params, vk, transcript="device", pairing="device", circuits=m)
+                    for b in range(B):
+                        bv.add_proof(inst_arg, multi[b % 2])
+                else:
+                    bv = h.BatchVerifier(params, vk, transcript="device", pairing="device")
+                    for b in range(B * m):
+                        bv.add_proof(instances[b % m], singles[b % m])
+                t_added = time.perf_counter()
+                ok = bv.finalize()
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                verdicts = bv.verdicts()
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+                assert ok and all(verdicts)
+                return (t1 - t0) * 1e3, (t2 - t1) * 1e3, bv, (t_added - t0) * 1e3
+
+            for which in ("multi", "single"):                    # warm-up: library load, allocator pools, the plans
+                route(1, which)[2].close()
+            phases = PHASES + ("sums", "verdict_pairing")
+            for B in sizes:
+                times = {which: ([], []) for which in ("multi", "single")}
+                split = {which: {p: [] for p in ("layout_and_add",) + phases} for which in ("multi", "single")}
+                kept = {}
+                for _ in range(repeats):
+                    for which in ("multi", "single"):            # the routes alternate inside every repeat
+                        fin, ver, bv, added = route(B, which)
+                        times[which][0].append(fin)
+                        times[which][1].append(ver)
+                        split[which]["layout_and_add"].append(added)
+                        for p in phases:
+                            split[which][p].append(bv.timings[p] * 1e3)
+                        if which in kept:
+                            kept[which].close()
+                        kept[which] = bv
+                row = {"multi": {"proofs": B, "finalize": spread(times["multi"][0]), "verdicts_after_finalize": spread(times["multi"][1]),
+                                 "terms_kernel_ms": terms_kernel_ms(kept["multi"], repeats)},
+                       "single_yardstick": {"proofs": B * m, "finalize": spread(times["single"][0]),
+                                            "verdicts_after_finalize": spread(times["single"][1]),
+                                            "terms_kernel_ms": terms_kernel_ms(kept["single"], repeats)}}
+                for which, route_name in (("multi", "multi"), ("single", "single_yardstick")):
+                    row[route_name]["split_median_ms"] = {p: round(statistics.median(v), 3) for p, v in split[which].items()}
+                for bv in kept.values():
+                    bv.close()
+                lanes = h.BatchVerifier(params, vk, transcript="device", pairing="device")     # the single-circuit kernel on B lanes
+                for b in range(B):
+                    lanes.add_proof(instances[b % m], singles[b % m])
+                row["single_terms_kernel_ms_at_B_proofs"] = terms_kernel_ms(lanes, repeats)
+                lanes.close()
+                row["per_circuit_ms"] = {"multi": round(row["multi"]["finalize"]["median_ms"] / (B * m), 4),
+                                         "single_yardstick": round(row["single_yardstick"]["finalize"]["median_ms"] / (B * m), 4),
+                                         "verify_proof_multi": round(rows["verify_proof_multi_per_proof"]["median_ms"] / m, 4)}
+                rows[str(B)] = row
+                print(f"{name} m={m} B={B}: multi {row['multi']['finalize']['median_ms']} ms, {B * m} singles "
+                      f"{row['single_yardstick']['finalize']['median_ms']} ms, terms {row['multi']['terms_kernel_ms']['median_ms']} / "
+                      f"{row['single_terms_kernel_ms_at_B_proofs']['median_ms']} ms", file=sys.stderr, flush=True)
+            out["circuits_per_proof"][str(m)] = rows
+    finally:
+        if params is not None:
+            params.release()
+    return out
 
 
 def circuit(name, sizes, repeats, modes=(("host", "host"),), encodings=("halo2",)):
@@ -160,8 +283,15 @@ if __name__ == "__main__":
               "encodings_measured": list(encodings),
               "host": "the transcripts (Blake2b by hashlib; Keccak in pure Python) and the pairing, unless the mode (transcript/pairing) says "
                       "device; everything else (read, terms, column sum, MSMs) on the device"}
-    for name in args.circuits.split(","):
-        result[name] = circuit(name, sizes, args.repeats, modes, encodings)
+    entries = args.circuits.split(",")
+    counts = [int(e) for e in entries if e.isdigit()]
+    names = [e for e in entries if not e.isdigit()] or ["merkle_sum_d20_k10", "poseidon_k6"]
+    if counts:
+        result.update(modes_measured=["device/device"], encodings_measured=["halo2"], circuits_per_proof=counts,
+                      routes="multi: B create_proof_multi proofs of m circuits; single_yardstick: the B * m single-circuit proofs of the "
+                             "same witnesses; both finalize() then verdicts() on a fresh BatchVerifier, transcript and pairing on the device")
+    for name in names:
+        result[name] = multi_circuit(name, counts, sizes, args.repeats) if counts else circuit(name, sizes, args.repeats, modes, encodings)
     text = json.dumps(result)
     print(text)
     if args.out:
