@@ -1,5 +1,6 @@
 // capi_verify.hip -- the batch verifier's entry points of the C ABI: the proofs of a batch read slot by slot on the device and the
-// column sums of their shared scalars (verify_read.inc), the per-proof terms of the opening checks (verify_terms.inc), and the pairing
+// column sums of their shared scalars (verify_read.inc), the per-proof terms of the opening checks (verify_terms.inc; the single- and
+// the multi-circuit entry are one function, verify_terms_entry), the per-proof sums (verify_sums.inc), and the pairing
 // product checks that end every verifier (pairing.inc), and Blake2b-512 with the proofs' transcripts on it (transcript.inc).
 #include <hip/hip_runtime.h>
 
@@ -50,19 +51,25 @@ int hm_verify_column_sum_dev(const void* d_rows, size_t n_rows, uint32_t columns
   return verify_colsum_run((const uint32_t*)d_rows, columns, lo, hi, (uint32_t*)d_out, (hipStream_t)stream);
 } HM_API_CATCH("hm_verify_column_sum_dev")
 
-int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
-                        const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad, void* d_own, void* d_shared,
-                        void* d_h2_r, void* d_h2_l, void* stream) try {
-  const std::string who = "hm_verify_terms_dev";
+// ---- the per-proof terms (verify_terms.inc, verify.hip): ONE entry behind the two of the ABI ------------------------------------------
+// multi: proofs of `circuits` circuits each (a circuits of 0 is the caller's mistake there, so it cannot stand for "single"), else
+// single-circuit proofs and `circuits` is not looked at.  proof_bits: log2 of the most proofs a call takes.  The checks keep their order.
+static int verify_terms_entry(const std::string& who, uint32_t circuits, bool multi, unsigned proof_bits, uint64_t graph, const uint32_t* plan,
+                              size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs, const void* d_records,
+                              const void* d_scalars, const void* d_instance, uint32_t* d_bad, void* d_own, void* d_shared, void* d_h2_r,
+                              void* d_h2_l, void* stream) {
   if (!plan || !d_records || !d_scalars || !d_instance || !d_bad || !d_own || !d_shared || !d_h2_r || !d_h2_l)
     return hm_fail(HM_ERR_BAD_ARG, who + ": null argument");
-  if (n_proofs == 0 || n_proofs > ((size_t)1 << 20)) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n_proofs <= 2^20");
+  if (multi && (circuits == 0 || circuits > VM_MAX_CIRCUITS)) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= circuits <= 64");
+  if (n_proofs == 0 || n_proofs > ((size_t)1 << proof_bits))
+    return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n_proofs <= 2^" + std::to_string(proof_bits));
   if (n_plan_words > ((size_t)1 << 24)) return hm_fail(HM_ERR_BAD_ARG, who + ": the plan is longer than 2^24 words");
   if (n_columns == 0 || n_columns > GE_MAX_COLUMNS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 .. 256 columns");
   if (((uintptr_t)d_records | (uintptr_t)d_scalars | (uintptr_t)d_instance | (uintptr_t)d_own | (uintptr_t)d_shared | (uintptr_t)d_h2_r |
        (uintptr_t)d_h2_l | (uintptr_t)d_bad) & 3u)
     return hm_fail(HM_ERR_BAD_ARG, who + ": a buffer is not 4-byte aligned");
-  if (const char* why = vt_plan_problem(plan, n_plan_words, n_columns)) return hm_fail(HM_ERR_BAD_ARG, why);
+  if (const char* why = multi ? vtm_plan_problem(plan, n_plan_words, n_columns, circuits) : vt_plan_problem(plan, n_plan_words, n_columns))
+    return hm_fail(HM_ERR_BAD_ARG, why);
   DeviceCtx* ctx = ctx_for_current_device();
   if (!ctx) return HM_ERR_NO_DEVICE;
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -70,35 +77,27 @@ int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_word
   for (auto& have : ctx->graphs)
     if (have->handle == graph) g = have.get();
   if (!g) return hm_fail(HM_ERR_BAD_ARG, who + ": unknown program handle");
-  return verify_terms_run(*ctx, *g, plan, n_plan_words, n_columns, n_dynamic, n_proofs, (const uint32_t*)d_records, (const uint32_t*)d_scalars,
-                          (const uint32_t*)d_instance, d_bad, (uint32_t*)d_own, (uint32_t*)d_shared, (uint32_t*)d_h2_r, (uint32_t*)d_h2_l,
+  const uint32_t *records = (const uint32_t*)d_records, *evals = (const uint32_t*)d_scalars, *inst = (const uint32_t*)d_instance;
+  uint32_t *own = (uint32_t*)d_own, *shared = (uint32_t*)d_shared, *h2r = (uint32_t*)d_h2_r, *h2l = (uint32_t*)d_h2_l;
+  if (multi)
+    return verify_terms_multi_run(*ctx, *g, plan, n_plan_words, n_columns, n_dynamic, n_proofs, circuits, records, evals, inst, d_bad, own, shared,
+                                  h2r, h2l, (hipStream_t)stream);
+  return verify_terms_run(*ctx, *g, plan, n_plan_words, n_columns, n_dynamic, n_proofs, records, evals, inst, d_bad, own, shared, h2r, h2l,
                           (hipStream_t)stream);
+}
+
+int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
+                        const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad, void* d_own, void* d_shared,
+                        void* d_h2_r, void* d_h2_l, void* stream) try {
+  return verify_terms_entry("hm_verify_terms_dev", 0, false, 20, graph, plan, n_plan_words, n_columns, n_dynamic, n_proofs, d_records, d_scalars,
+                            d_instance, d_bad, d_own, d_shared, d_h2_r, d_h2_l, stream);
 } HM_API_CATCH("hm_verify_terms_dev")
 
 int hm_verify_terms_multi_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
                               uint32_t circuits, const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad,
                               void* d_own, void* d_shared, void* d_h2_r, void* d_h2_l, void* stream) try {
-  const std::string who = "hm_verify_terms_multi_dev";
-  if (!plan || !d_records || !d_scalars || !d_instance || !d_bad || !d_own || !d_shared || !d_h2_r || !d_h2_l)
-    return hm_fail(HM_ERR_BAD_ARG, who + ": null argument");
-  if (circuits == 0 || circuits > VM_MAX_CIRCUITS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= circuits <= 64");
-  if (n_proofs == 0 || n_proofs > ((size_t)1 << 16)) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n_proofs <= 2^16");
-  if (n_plan_words > ((size_t)1 << 24)) return hm_fail(HM_ERR_BAD_ARG, who + ": the plan is longer than 2^24 words");
-  if (n_columns == 0 || n_columns > GE_MAX_COLUMNS) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 .. 256 columns");
-  if (((uintptr_t)d_records | (uintptr_t)d_scalars | (uintptr_t)d_instance | (uintptr_t)d_own | (uintptr_t)d_shared | (uintptr_t)d_h2_r |
-       (uintptr_t)d_h2_l | (uintptr_t)d_bad) & 3u)
-    return hm_fail(HM_ERR_BAD_ARG, who + ": a buffer is not 4-byte aligned");
-  if (const char* why = vtm_plan_problem(plan, n_plan_words, n_columns, circuits)) return hm_fail(HM_ERR_BAD_ARG, why);
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  GraphProgram* g = nullptr;
-  for (auto& have : ctx->graphs)
-    if (have->handle == graph) g = have.get();
-  if (!g) return hm_fail(HM_ERR_BAD_ARG, who + ": unknown program handle");
-  return verify_terms_multi_run(*ctx, *g, plan, n_plan_words, n_columns, n_dynamic, n_proofs, circuits, (const uint32_t*)d_records,
-                                (const uint32_t*)d_scalars, (const uint32_t*)d_instance, d_bad, (uint32_t*)d_own, (uint32_t*)d_shared,
-                                (uint32_t*)d_h2_r, (uint32_t*)d_h2_l, (hipStream_t)stream);
+  return verify_terms_entry("hm_verify_terms_multi_dev", circuits, true, 16, graph, plan, n_plan_words, n_columns, n_dynamic, n_proofs, d_records,
+                            d_scalars, d_instance, d_bad, d_own, d_shared, d_h2_r, d_h2_l, stream);
 } HM_API_CATCH("hm_verify_terms_multi_dev")
 
 // ---- the per-proof sums (verify_sums.inc, verify.hip) -------------------------------------------------------------------------------

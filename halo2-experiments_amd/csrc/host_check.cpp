@@ -845,7 +845,7 @@ int hc_verify_terms(const uint32_t* plan, size_t n_words, size_t n_columns, cons
   for (uint32_t s = 0; s < plan[VT_N_VALS]; ++s) vt_to_ext(vals + 8 * (size_t)s, vt_load(m, s));
   return ok ? 1 : 0;
 }
-// The terms of ONE multi-circuit proof (verify_terms.inc, second half): the lane code of verify_terms_multi_kernel on a workspace of
+// The terms of ONE multi-circuit proof (verify_terms.inc): the lane code of verify_terms_multi_kernel on a workspace of
 // 64 lanes, lane c = circuit c, with the two cross-lane folds as plain loops over the lanes.  plan: the multi plan; evals: the proof's
 // scalars in the proof's order; inst: circuits rows; numerators: N_c of every circuit (circuits x 4 Montgomery words), as
 // hc_verify_terms is given its one; vals: circuits x n_vals x 8 words, every lane's value row.  -> 1 / 0: no lane failed / one did
@@ -858,7 +858,7 @@ int hc_verify_terms_multi(const uint32_t* plan, size_t n_words, size_t n_columns
   const uint32_t* lp = vtm_lane_plan(plan);
   const uint32_t T = VM_MAX_CIRCUITS;
   std::vector<uint32_t> ws((size_t)vt_ws_program(lp) * 9 * T, 0);
-  for (uint32_t c = 0; c < T; ++c) vtm_zero_lane(plan, c, own, shared, h2r, h2l);
+  for (uint32_t c = 0; c < T; ++c) vt_zero_lane(lp, VtmLane{plan, c}, own, shared, h2r, h2l);
   bool ok = true;
   Fr num = fe_zero<FrParams>();
   HM_DECLARE(num, 3.0);
@@ -872,16 +872,16 @@ int hc_verify_terms_multi(const uint32_t* plan, size_t n_words, size_t n_columns
   VtmShare first{};
   for (uint32_t c = 0; c < circuits; ++c) {
     const VtMem m{ws.data(), T, c};
-    const VtmShare mine = vtm_phase_b(plan, m, c, num, own, shared);
+    const VtmShare mine = vt_set_walk(lp, m, VtmLane{plan, c}, num, own, shared);
     ok = ok && mine.ok;
     r_outer = vt_add(r_outer, mine.r_outer);
     if (c == 0) first = mine;
     for (uint32_t s = 0; s < lp[VT_N_VALS]; ++s) vt_to_ext(vals + 8 * ((size_t)c * lp[VT_N_VALS] + s), vt_load(m, s));
   }
   if (ok) {
-    vtm_finish(plan, VtMem{ws.data(), T, 0}, r_outer, first, own, shared, h2r, h2l);
+    vt_finish(lp, plan[VM_N_OWN], VtMem{ws.data(), T, 0}, r_outer, first, own, shared, h2r, h2l);
   } else {
-    for (uint32_t c = 0; c < T; ++c) vtm_zero_lane(plan, c, own, shared, h2r, h2l);
+    for (uint32_t c = 0; c < T; ++c) vt_zero_lane(lp, VtmLane{plan, c}, own, shared, h2r, h2l);
   }
   return ok ? 1 : 0;
 }

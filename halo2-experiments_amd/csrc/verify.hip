@@ -1,7 +1,8 @@
 // verify.hip -- the device side of a batch verification (batch_verifier.py is the caller): the kernels and the drivers
 //   verify_read_run, verify_colsum_run    a batch of proofs read slot by slot, the column sums of its shared scalars (verify_read.inc)
 //   verify_terms_run                      the per-proof terms of the opening checks, one lane per proof (verify_terms.inc)
-//   verify_terms_multi_run                the same for multi-circuit proofs: a wavefront per proof, a lane per circuit
+//   verify_terms_multi_run                the same for multi-circuit proofs: a wavefront per proof, a lane per circuit.  Two kernels
+//                                         and two launch shapes over one phase-b walk, behind one driver (verify_terms_launch)
 //   verify_sums_run                       the two G1 points of every proof's own check, one workgroup per proof (verify_sums.inc)
 //   blake2b_run, verify_transcript_run    Blake2b-512 and the proofs' transcripts on it, one lane per proof (transcript.inc)
 //   keccak256_run, verify_read_evm_run,   Keccak-256, and the read and the transcripts of proofs in the EVM encoding: uncompressed
@@ -164,10 +165,7 @@ __global__ __launch_bounds__(GE_THREADS) void verify_terms_kernel(const uint32_t
   const size_t b = lane;
   uint32_t* my_own = own + b * plan[VT_N_OWN] * 8;
   uint32_t* my_shared = shared + b * plan[VT_N_SHARED] * 8;
-  vt_zero_rows(my_own, plan[VT_N_OWN]);
-  vt_zero_rows(my_shared, plan[VT_N_SHARED]);
-  vt_zero_rows(h2r + b * 8, 1);
-  vt_zero_rows(h2l + b * 8, 1);
+  vt_zero_lane(plan, VtSingle{}, my_own, my_shared, h2r + b * 8, h2l + b * 8);
   if (bad[b]) return;
   const VtMem m{ws, T, lane};
   bool ok = vt_phase_a(plan, m, records + b * VT_REC * 8, evals + b * plan[VT_N_SCALARS] * 8, inst + b * plan[VT_INST_ELEMS] * 8);
@@ -176,37 +174,8 @@ __global__ __launch_bounds__(GE_THREADS) void verify_terms_kernel(const uint32_t
   ok = vt_phase_b(plan, m, num, my_own, my_shared, h2r + b * 8, h2l + b * 8) && ok;
   if (!ok) {
     bad[b] = 1;
-    vt_zero_rows(my_own, plan[VT_N_OWN]);
-    vt_zero_rows(my_shared, plan[VT_N_SHARED]);
-    vt_zero_rows(h2r + b * 8, 1);
-    vt_zero_rows(h2l + b * 8, 1);
+    vt_zero_lane(plan, VtSingle{}, my_own, my_shared, h2r + b * 8, h2l + b * 8);
   }
-}
-
-// the arguments were checked by the caller (capi_verify.hip) -- but for the plan, which is checked here, before anything is launched
-int verify_terms_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
-                     const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst, uint32_t* d_bad, uint32_t* d_own,
-                     uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream) {
-  GraphVariant& v = g.variant[0];
-  if (!v.ready) return hm_fail(HM_ERR_INTERNAL, "verify terms: the program has no lowered form");
-  if (n_columns != g.n_columns) return hm_fail(HM_ERR_BAD_ARG, "verify terms: the program was built for another number of columns");
-  if (n_dynamic != g.n_dynamic || n_dynamic != 4)
-    return hm_fail(HM_ERR_BAD_ARG, "verify terms: the program must take beta, gamma, theta, y as its per-call constants");
-  if (const char* why = vt_plan_problem(plan, n_words, n_columns)) return hm_fail(HM_ERR_BAD_ARG, why);
-  const uint32_t blocks = (uint32_t)((n_proofs + GE_THREADS - 1) / GE_THREADS), T = blocks * GE_THREADS;
-  const size_t slots = (size_t)vt_ws_program(plan) + v.n_slots;
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  uint32_t* ws = (uint32_t*)slot->scratch.ensure(slots * 9 * T * 4);
-  uint32_t* d_plan = (uint32_t*)slot->args.ensure(n_words * 4);
-  if (!ws || !d_plan) return hm_fail(HM_ERR_HIP, "verify terms: workspace allocation failed");
-  // pageable source: the runtime has taken its copy of the plan when this returns (as the witness checker's table)
-  HM_HIP_CHECK(hipMemcpyAsync(d_plan, plan, n_words * 4, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(verify_terms_kernel, dim3(blocks), dim3(GE_THREADS), 0, stream, (const uint32_t*)d_plan, (const uint32_t*)g.d_consts,
-                     (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src, v.result_prev, g.n_static, ws, (uint32_t)n_proofs, d_records, d_evals,
-                     d_inst, d_bad, d_own, d_shared, d_h2r, d_h2l);
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
 }
 
 // ---- the terms of multi-circuit proofs: a wavefront per proof, a lane per circuit ---------------
@@ -244,7 +213,8 @@ __global__ __launch_bounds__(GE_THREADS) void verify_terms_multi_kernel(const ui
   const bool active = c < circuits;
   uint32_t* my_own = own + b * mp[VM_N_OWN] * 8;
   uint32_t* my_shared = shared + b * lp[VT_N_SHARED] * 8;
-  vtm_zero_lane(mp, c, my_own, my_shared, h2r + b * 8, h2l + b * 8);
+  const VtmLane me{mp, c};
+  vt_zero_lane(lp, me, my_own, my_shared, h2r + b * 8, h2l + b * 8);
   if (bad[b]) return;
   const VtMem m{ws, T, lane};
   bool ok = true;
@@ -260,44 +230,67 @@ __global__ __launch_bounds__(GE_THREADS) void verify_terms_multi_kernel(const ui
   VtmShare mine{fe_zero<FrParams>(), fe_zero<FrParams>(), fe_zero<FrParams>(), true};
   HM_DECLARE(mine.r_outer, 3.0);
   if (active) {
-    mine = vtm_phase_b(mp, m, c, num, my_own, my_shared);
+    mine = vt_set_walk(lp, m, me, num, my_own, my_shared);
     ok = ok && mine.ok;
   }
   const Fr r_outer = vtm_wave_sum(mine.r_outer);
   const bool failed = __ballot(active && !ok) != 0;               // any lane of the proof
   if (failed) {
-    vtm_zero_lane(mp, c, my_own, my_shared, h2r + b * 8, h2l + b * 8);
+    vt_zero_lane(lp, me, my_own, my_shared, h2r + b * 8, h2l + b * 8);
     if (c == 0) bad[b] = 1;
   } else if (c == 0) {
-    vtm_finish(mp, m, r_outer, mine, my_own, my_shared, h2r + b * 8, h2l + b * 8);
+    vt_finish(lp, mp[VM_N_OWN], m, r_outer, mine, my_own, my_shared, h2r + b * 8, h2l + b * 8);
   }
 }
 
-// as verify_terms_run, for proofs of `circuits` circuits each: T = 64 lanes per proof
-int verify_terms_multi_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic,
-                           size_t n_proofs, uint32_t circuits, const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst,
-                           uint32_t* d_bad, uint32_t* d_own, uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream) {
+// ---- the drivers of the two terms kernels -------------------------------------------------------
+using VerifyTermsKernel = decltype(&verify_terms_kernel);         // the two kernels take the same arguments
+
+// What both drivers do behind their plan's check (`why`: its verdict, reported behind the program's own checks as before): `what`
+// opens every message, `lane_plan` sizes a lane's workspace, `lanes` is the launch's width.  The arguments were checked by the caller
+// (capi_verify.hip) -- but for the plan, which is checked before anything is launched.
+static int verify_terms_launch(const char* what, const char* why, DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words,
+                               const uint32_t* lane_plan, size_t n_columns, size_t n_dynamic, size_t n_proofs, size_t lanes,
+                               VerifyTermsKernel kernel, const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst,
+                               uint32_t* d_bad, uint32_t* d_own, uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream) {
+  const std::string who = what;
   GraphVariant& v = g.variant[0];
-  if (!v.ready) return hm_fail(HM_ERR_INTERNAL, "verify terms multi: the program has no lowered form");
-  if (n_columns != g.n_columns) return hm_fail(HM_ERR_BAD_ARG, "verify terms multi: the program was built for another number of columns");
+  if (!v.ready) return hm_fail(HM_ERR_INTERNAL, who + ": the program has no lowered form");
+  if (n_columns != g.n_columns) return hm_fail(HM_ERR_BAD_ARG, who + ": the program was built for another number of columns");
   if (n_dynamic != g.n_dynamic || n_dynamic != 4)
-    return hm_fail(HM_ERR_BAD_ARG, "verify terms multi: the program must take beta, gamma, theta, y as its per-call constants");
-  if (const char* why = vtm_plan_problem(plan, n_words, n_columns, circuits)) return hm_fail(HM_ERR_BAD_ARG, why);
-  const size_t lanes = n_proofs * 64;
+    return hm_fail(HM_ERR_BAD_ARG, who + ": the program must take beta, gamma, theta, y as its per-call constants");
+  if (why) return hm_fail(HM_ERR_BAD_ARG, why);
   const uint32_t blocks = (uint32_t)((lanes + GE_THREADS - 1) / GE_THREADS), T = blocks * GE_THREADS;
-  const size_t slots = (size_t)vt_ws_program(vtm_lane_plan(plan)) + v.n_slots;
+  const size_t slots = (size_t)vt_ws_program(lane_plan) + v.n_slots;
   AuxSlot* slot = aux_acquire(ctx, stream);
   if (!slot) return HM_ERR_HIP;
   uint32_t* ws = (uint32_t*)slot->scratch.ensure(slots * 9 * T * 4);
   uint32_t* d_plan = (uint32_t*)slot->args.ensure(n_words * 4);
-  if (!ws || !d_plan) return hm_fail(HM_ERR_HIP, "verify terms multi: workspace allocation failed");
-  // pageable source: the runtime has taken its copy of the plan when this returns (as verify_terms_run)
+  if (!ws || !d_plan) return hm_fail(HM_ERR_HIP, who + ": workspace allocation failed");
+  // pageable source: the runtime has taken its copy of the plan when this returns (as the witness checker's table)
   HM_HIP_CHECK(hipMemcpyAsync(d_plan, plan, n_words * 4, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(verify_terms_multi_kernel, dim3(blocks), dim3(GE_THREADS), 0, stream, (const uint32_t*)d_plan, (const uint32_t*)g.d_consts,
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(GE_THREADS), 0, stream, (const uint32_t*)d_plan, (const uint32_t*)g.d_consts,
                      (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src, v.result_prev, g.n_static, ws, (uint32_t)n_proofs, d_records, d_evals,
                      d_inst, d_bad, d_own, d_shared, d_h2r, d_h2l);
   HM_HIP_CHECK(hipGetLastError());
   return aux_release(ctx, slot, stream);
+}
+
+// one lane per proof
+int verify_terms_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
+                     const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst, uint32_t* d_bad, uint32_t* d_own,
+                     uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream) {
+  return verify_terms_launch("verify terms", vt_plan_problem(plan, n_words, n_columns), ctx, g, plan, n_words, plan, n_columns, n_dynamic,
+                             n_proofs, n_proofs, verify_terms_kernel, d_records, d_evals, d_inst, d_bad, d_own, d_shared, d_h2r, d_h2l, stream);
+}
+
+// proofs of `circuits` circuits each: 64 lanes per proof
+int verify_terms_multi_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic,
+                           size_t n_proofs, uint32_t circuits, const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst,
+                           uint32_t* d_bad, uint32_t* d_own, uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream) {
+  const char* why = vtm_plan_problem(plan, n_words, n_columns, circuits);
+  return verify_terms_launch("verify terms multi", why, ctx, g, plan, n_words, why ? plan : vtm_lane_plan(plan), n_columns, n_dynamic, n_proofs,
+                             n_proofs * 64, verify_terms_multi_kernel, d_records, d_evals, d_inst, d_bad, d_own, d_shared, d_h2r, d_h2l, stream);
 }
 
 // ---- the per-proof sums -----------------------------------------------------------------------

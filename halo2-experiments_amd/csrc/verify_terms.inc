@@ -2,7 +2,7 @@
 // caller, DESIGN.md section 20): from a proof's evaluations, its instance values and its challenges to r_b x the scalar of every point
 // of its opening check.
 //
-// A PLAN, built once per constraint system on the host (batch_verifier.TermsPlan) and checked word by word before every launch
+// A PLAN, built once per constraint system on the host (proof_layout.TermsPlan) and checked word by word before every launch
 // (vt_plan_problem), drives every loop: a header, a (column, rotation index) -> value slot map, the instance queries, the rotation sets
 // and a block of constants in internal form (1 / n, the powers of omega the Lagrange values and the rotations need, the inverse of
 // every prod_{m != l} (omega^r_l - omega^r_m) of a set).  It travels into the slot's argument buffer with the call, as the witness
@@ -26,8 +26,11 @@
 //             proof's own points (the h commitment expanded into its pieces with the powers of x^n), its row of the shared points'
 //             array, and r_b u, r_b for [h'].
 // The two phases are host-callable: host_check.cpp runs them under bound tracking (hc_verify_terms) with the numerator given.
-// Included inside namespace hm by verify.hip, which holds the kernel and its driver, and by capi_verify.hip for the plan's check.
-// A multi-circuit proof takes a wavefront, one lane per circuit: the second half of this file (vtm_*, DESIGN.md section 29).
+// Included inside namespace hm by verify.hip, which holds the kernels and their driver, and by capi_verify.hip for the plans' checks.
+// A multi-circuit proof takes a wavefront, one lane per circuit (DESIGN.md section 29): the middle of this file holds its plan, its
+// phase a and its numerator term (vtm_*).  Phase b stands last and is written ONCE: vt_set_walk walks the rotation sets for the lane
+// of either road (VtSingle / VtmLane, chosen at compile time) and returns the lane's share, vt_finish writes the generator's scalar,
+// [h]'s, h2_r and h2_l from the summed shares, vt_zero_lane zeroes what a lane may write; vt_phase_b is walk + finish for one circuit.
 
 enum : uint32_t {
   VT_K, VT_N_SCALARS, VT_N_VALS, VT_N_LAGRANGE, VT_N_INSTQ, VT_N_SUPER, VT_N_SETS, VT_PIECES, VT_N_OWN, VT_N_SHARED, VT_N_ROT, VT_N_COLS,
@@ -204,80 +207,8 @@ HM_HD bool vt_phase_a_rest(const uint32_t* plan, const VtMem& m, const uint32_t*
   return ok;
 }
 
-// num: the numerator, below 3r.  -> false when u hits a point of the first set's complement (z_0 = 0)
-HM_HD bool vt_phase_b(const uint32_t* plan, const VtMem& m, const Fr& num, uint32_t* own, uint32_t* shared, uint32_t* h2r, uint32_t* h2l) {
-  const uint32_t* cst = plan + plan[VT_OFF_CONSTS];
-  const uint32_t wc = plan[VT_N_VALS], wd = vt_ws_diff(plan), wb = vt_ws_basis(plan), n_super = plan[VT_N_SUPER];
-  vt_store(m, plan[VT_S_HX], fe_mul(num, vt_load(m, wc + VT_XN1_INV)));
-  const Fr x = vt_load(m, wc + VT_X), y2 = vt_load(m, wc + VT_Y2), v = vt_load(m, wc + VT_V), u = vt_load(m, wc + VT_U);
-  const Fr rb = vt_load(m, wc + VT_RB), xn = vt_load(m, wc + VT_XN), one = fe_one<FrParams>();
-  const Fr x_inv = vt_inv(x);
-  Fr zt = one;
-  for (uint32_t s = 0; s < n_super; ++s) {
-    const Fr d = vt_sub(u, fe_mul(x, vt_const(cst, plan[VT_C_SUPER] + s)));
-    vt_store(m, wd + s, d);
-    zt = fe_mul(zt, d);
-  }
-  Fr r_outer = fe_zero<FrParams>(), v_i = one, z0_inv = fe_zero<FrParams>();
-  bool ok = true;
-  size_t at = plan[VT_OFF_SETS];
-  for (uint32_t i = 0; i < plan[VT_N_SETS]; ++i) {
-    const uint32_t t = plan[at], mask = plan[at + 1], members = plan[at + 2];
-    const uint32_t* sup = plan + at + 3;
-    const uint32_t* dinv = sup + t;
-    at += 3 + 2 * (size_t)t;
-    Fr z = one;
-    for (uint32_t s = 0; s < n_super; ++s)
-      if (!((mask >> s) & 1u)) z = fe_mul(z, vt_load(m, wd + s));
-    if (i == 0) {
-      ok = !fe_is_zero_mod(z);
-      z0_inv = vt_inv(z);
-      z = one;
-    } else {
-      z = fe_mul(z, z0_inv);
-    }
-    const Fr outer = fe_mul(v_i, z);
-    v_i = fe_mul(v_i, v);
-    Fr xs = one;                                                 // x^-(t-1): the points are x omega^r, the constants hold the omega part
-    for (uint32_t l = 1; l < t; ++l) xs = fe_mul(xs, x_inv);
-    for (uint32_t l = 0; l < t; ++l) {                           // the Lagrange basis of the set's points at u
-      Fr b = fe_mul(vt_const(cst, dinv[l]), xs);
-      for (uint32_t k = 0; k < t; ++k)
-        if (k != l) b = fe_mul(b, vt_load(m, wd + sup[k]));
-      vt_store(m, wb + l, b);
-    }
-    Fr yj = one;
-    for (uint32_t j = 0; j < members; ++j) {
-      const uint32_t target = plan[at], index = target & VT_T_INDEX;
-      const uint32_t* slots = plan + at + 1;
-      at += 1 + (size_t)t;
-      const Fr coeff = fe_mul(outer, yj);
-      yj = fe_mul(yj, y2);
-      Fr r_eval = fe_zero<FrParams>();
-      for (uint32_t l = 0; l < t; ++l) r_eval = vt_add(r_eval, fe_mul(vt_load(m, wb + l), vt_load(m, slots[l])));
-      r_outer = vt_add(r_outer, fe_mul(coeff, r_eval));
-      Fr weighted = fe_mul(coeff, rb);
-      if (target & VT_T_H) {                                     // [h] = sum_p x^(n p) [h_p]
-        for (uint32_t p = 0; p < plan[VT_PIECES]; ++p) {
-          vt_to_ext(own + 8 * (size_t)(index + p), weighted);
-          weighted = fe_mul(weighted, xn);
-        }
-      } else if (target & VT_T_SHARED) {
-        vt_to_ext(shared + 8 * (size_t)index, weighted);
-      } else {
-        vt_to_ext(own + 8 * (size_t)index, weighted);
-      }
-    }
-  }
-  vt_to_ext(shared + 8 * (size_t)(plan[VT_N_SHARED] - 1), vt_neg(fe_mul(r_outer, rb)));              // the generator
-  vt_to_ext(own + 8 * (size_t)(plan[VT_N_OWN] - 1), vt_neg(fe_mul(fe_mul(z0_inv, zt), rb)));         // [h]
-  vt_to_ext(h2r, fe_mul(u, rb));
-  vt_to_ext(h2l, rb);
-  return ok;
-}
-
 // ---- a multi-circuit proof (create_proof_multi): one WAVEFRONT per proof, lane c = circuit c ------------------------------------------
-// The multi plan (batch_verifier.MultiTermsPlan) wraps the plan of ONE circuit -- the LANE plan, the words above, checked by
+// The multi plan (proof_layout.MultiTermsPlan) wraps the plan of ONE circuit -- the LANE plan, the words above, checked by
 // vt_plan_problem as they are -- and says where a lane finds its circuit in the proof:
 //   header      VM_* below; VM_N_SCALARS / VM_N_OWN are the PROOF's counts, VM_OWN_TAIL its first own row no circuit owns (random, the
 //               h pieces, [h]), VM_EXPRS the E expressions one circuit folds in y
@@ -369,21 +300,6 @@ HM_HD Fr vtm_pow_lane(const Fr& a, uint32_t e) {
   return r;
 }
 
-// the rows lane c answers for, zeroed by the lane that may write them later (one lane's stores keep their order)
-HM_HD void vtm_zero_lane(const uint32_t* mp, uint32_t c, uint32_t* own, uint32_t* shared, uint32_t* h2r, uint32_t* h2l) {
-  if (c < mp[VM_CIRCUITS])
-    for (uint32_t g = 0; g < mp[VM_N_GROUPS]; ++g) {
-      const uint32_t* e = mp + mp[VM_OFF_GROUPS] + 2 * (size_t)g;
-      vt_zero_rows(own + 8 * ((size_t)e[0] + (size_t)c * e[1]), e[1]);
-    }
-  if (c == 0) {
-    vt_zero_rows(own + 8 * (size_t)mp[VM_OWN_TAIL], mp[VM_N_OWN] - mp[VM_OWN_TAIL]);
-    vt_zero_rows(shared, vtm_lane_plan(mp)[VT_N_SHARED]);
-    vt_zero_rows(h2r, 1);
-    vt_zero_rows(h2l, 1);
-  }
-}
-
 // phase a of lane c: the proof's record, the lane's evaluations gathered by the segments, then vt_phase_a_rest on its instance values
 HM_HD bool vtm_phase_a(const uint32_t* mp, const VtMem& m, uint32_t c, const uint32_t* rec, const uint32_t* evals, const uint32_t* inst) {
   const uint32_t* lp = vtm_lane_plan(mp);
@@ -404,14 +320,48 @@ HM_HD Fr vtm_numerator_term(const uint32_t* mp, const VtMem& m, uint32_t c, cons
   return fe_mul(own_fold, vtm_pow_lane(y_e, mp[VM_CIRCUITS] - 1 - c));
 }
 
-struct VtmShare {
-  Fr r_outer, z0_inv, zt;                                        // the lane's share of sum coeff * r_eval; 1 / z_0 and the vanishing value at u
-  bool ok;
+// ---- phase b: ONE walk over the rotation sets for both roads ----------------------------------------------------------------------------
+// Who walks: the one lane of a single-circuit proof, or lane c of a multi-circuit proof's wavefront.  The choice is made at compile
+// time (if constexpr on Lane::multi), so the single-circuit instantiation holds none of the multi-circuit work.
+struct VtSingle {
+  static constexpr bool multi = false;
+};
+struct VtmLane {
+  static constexpr bool multi = true;
+  const uint32_t* mp;                                            // the multi plan; the `plan` beside it is its lane plan
+  uint32_t c;
 };
 
-// num: the PROOF's numerator, below 3r.  Lane c writes r_b x the scalars of circuit c's points; lane 0 those of the proof's as well.
-HM_HD VtmShare vtm_phase_b(const uint32_t* mp, const VtMem& m, uint32_t c, const Fr& num, uint32_t* own, uint32_t* shared) {
-  const uint32_t* plan = vtm_lane_plan(mp);
+// the rows this lane answers for, zeroed by the lane that may write them later (one lane's stores keep their order): its circuit's
+// groups, and -- the single lane, or lane 0 -- what belongs to the proof.  Called before the work and again when the proof fails.
+template <class Lane>
+HM_HD void vt_zero_lane(const uint32_t* plan, const Lane& lane, uint32_t* own, uint32_t* shared, uint32_t* h2r, uint32_t* h2l) {
+  uint32_t first = 0, n_own = plan[VT_N_OWN];
+  if constexpr (Lane::multi) {
+    const uint32_t* mp = lane.mp;
+    if (lane.c < mp[VM_CIRCUITS])
+      for (uint32_t g = 0; g < mp[VM_N_GROUPS]; ++g) {
+        const uint32_t* e = mp + mp[VM_OFF_GROUPS] + 2 * (size_t)g;
+        vt_zero_rows(own + 8 * ((size_t)e[0] + (size_t)lane.c * e[1]), e[1]);
+      }
+    if (lane.c != 0) return;
+    first = mp[VM_OWN_TAIL], n_own = mp[VM_N_OWN];
+  }
+  vt_zero_rows(own + 8 * (size_t)first, n_own - first);
+  vt_zero_rows(shared, plan[VT_N_SHARED]);
+  vt_zero_rows(h2r, 1);
+  vt_zero_rows(h2l, 1);
+}
+
+struct VtmShare {
+  Fr r_outer, z0_inv, zt;                                        // the lane's share of sum coeff * r_eval; 1 / z_0 and the vanishing value at u
+  bool ok;                                                       // false when u hits a point of the first set's complement (z_0 = 0)
+};
+
+// num: the PROOF's numerator, below 3r.  The lane writes r_b x the scalars of its own points: all of them for a single-circuit
+// proof; circuit c's for lane c of a multi-circuit proof, and lane 0 those of the proof's as well.
+template <class Lane>
+HM_HD VtmShare vt_set_walk(const uint32_t* plan, const VtMem& m, const Lane& lane, const Fr& num, uint32_t* own, uint32_t* shared) {
   const uint32_t* cst = plan + plan[VT_OFF_CONSTS];
   const uint32_t wc = plan[VT_N_VALS], wd = vt_ws_diff(plan), wb = vt_ws_basis(plan), n_super = plan[VT_N_SUPER];
   vt_store(m, plan[VT_S_HX], fe_mul(num, vt_load(m, wc + VT_XN1_INV)));
@@ -428,9 +378,10 @@ HM_HD VtmShare vtm_phase_b(const uint32_t* mp, const VtMem& m, uint32_t c, const
   out.r_outer = fe_zero<FrParams>(), out.z0_inv = fe_zero<FrParams>(), out.ok = true;
   Fr v_i = one;
   size_t at = plan[VT_OFF_SETS];
-  const uint32_t* ext = mp + mp[VM_OFF_MEMBERS];
+  const uint32_t* ext = nullptr;                                 // the multi plan's member words of the current set
+  if constexpr (Lane::multi) ext = lane.mp + lane.mp[VM_OFF_MEMBERS];
   for (uint32_t i = 0; i < plan[VT_N_SETS]; ++i) {
-    const uint32_t t = plan[at], mask = plan[at + 1], members = plan[at + 2], per = ext[0];
+    const uint32_t t = plan[at], mask = plan[at + 1], members = plan[at + 2];
     const uint32_t* sup = plan + at + 3;
     const uint32_t* dinv = sup + t;
     at += 3 + 2 * (size_t)t;
@@ -446,30 +397,38 @@ HM_HD VtmShare vtm_phase_b(const uint32_t* mp, const VtMem& m, uint32_t c, const
     }
     const Fr outer = fe_mul(v_i, z);
     v_i = fe_mul(v_i, v);
-    Fr xs = one;
+    Fr xs = one;                                                 // x^-(t-1): the points are x omega^r, the constants hold the omega part
     for (uint32_t l = 1; l < t; ++l) xs = fe_mul(xs, x_inv);
-    for (uint32_t l = 0; l < t; ++l) {
+    for (uint32_t l = 0; l < t; ++l) {                           // the Lagrange basis of the set's points at u
       Fr b = fe_mul(vt_const(cst, dinv[l]), xs);
       for (uint32_t k = 0; k < t; ++k)
         if (k != l) b = fe_mul(b, vt_load(m, wd + sup[k]));
       vt_store(m, wb + l, b);
     }
-    const Fr y_per = vtm_pow_uniform(y2, per);                   // y'^p: one circuit's step inside this set
-    const Fr y_tail = vtm_pow_uniform(y_per, mp[VM_CIRCUITS]);   // where the proof's members begin
-    Fr yj = vtm_pow_lane(y_per, c);
+    Fr yj = one, y_tail = one;
+    uint32_t per = 0;
+    if constexpr (Lane::multi) {
+      per = ext[0];
+      const Fr y_per = vtm_pow_uniform(y2, per);                 // y'^p: one circuit's step inside this set
+      y_tail = vtm_pow_uniform(y_per, lane.mp[VM_CIRCUITS]);     // where the proof's members begin
+      yj = vtm_pow_lane(y_per, lane.c);
+    }
     for (uint32_t j = 0; j < members; ++j) {
-      const uint32_t target = ext[1 + 2 * (size_t)j], index = (target & VT_T_INDEX) + c * ext[2 + 2 * (size_t)j];
+      uint32_t target = plan[at], index = target & VT_T_INDEX;
       const uint32_t* slots = plan + at + 1;
       at += 1 + (size_t)t;
-      if (j == per) yj = y_tail;
-      if (j >= per && c != 0) continue;                          // the proof's members are lane 0's
+      if constexpr (Lane::multi) {
+        target = ext[1 + 2 * (size_t)j], index = (target & VT_T_INDEX) + lane.c * ext[2 + 2 * (size_t)j];
+        if (j == per) yj = y_tail;
+        if (j >= per && lane.c != 0) continue;                   // the proof's members are lane 0's
+      }
       const Fr coeff = fe_mul(outer, yj);
       yj = fe_mul(yj, y2);
       Fr r_eval = fe_zero<FrParams>();
       for (uint32_t l = 0; l < t; ++l) r_eval = vt_add(r_eval, fe_mul(vt_load(m, wb + l), vt_load(m, slots[l])));
       out.r_outer = vt_add(out.r_outer, fe_mul(coeff, r_eval));
       Fr weighted = fe_mul(coeff, rb);
-      if (target & VT_T_H) {
+      if (target & VT_T_H) {                                     // [h] = sum_p x^(n p) [h_p]
         for (uint32_t p = 0; p < plan[VT_PIECES]; ++p) {
           vt_to_ext(own + 8 * (size_t)(index + p), weighted);
           weighted = fe_mul(weighted, xn);
@@ -480,19 +439,26 @@ HM_HD VtmShare vtm_phase_b(const uint32_t* mp, const VtMem& m, uint32_t c, const
         vt_to_ext(own + 8 * (size_t)index, weighted);
       }
     }
-    ext += 1 + 2 * (size_t)members;
+    if constexpr (Lane::multi) ext += 1 + 2 * (size_t)members;
   }
   return out;
 }
 
-// lane 0, behind the fold: r_outer is the sum of every lane's share
-HM_HD void vtm_finish(const uint32_t* mp, const VtMem& m, const Fr& r_outer, const VtmShare& mine, uint32_t* own, uint32_t* shared, uint32_t* h2r,
-                      uint32_t* h2l) {
-  const uint32_t* plan = vtm_lane_plan(mp);
+// behind the walk (lane 0, behind the fold): r_outer is the sum of every lane's share, n_own the PROOF's own rows
+HM_HD void vt_finish(const uint32_t* plan, uint32_t n_own, const VtMem& m, const Fr& r_outer, const VtmShare& mine, uint32_t* own,
+                     uint32_t* shared, uint32_t* h2r, uint32_t* h2l) {
   const uint32_t wc = plan[VT_N_VALS];
   const Fr u = vt_load(m, wc + VT_U), rb = vt_load(m, wc + VT_RB);
   vt_to_ext(shared + 8 * (size_t)(plan[VT_N_SHARED] - 1), vt_neg(fe_mul(r_outer, rb)));              // the generator
-  vt_to_ext(own + 8 * (size_t)(mp[VM_N_OWN] - 1), vt_neg(fe_mul(fe_mul(mine.z0_inv, mine.zt), rb))); // [h]
+  vt_to_ext(own + 8 * (size_t)(n_own - 1), vt_neg(fe_mul(fe_mul(mine.z0_inv, mine.zt), rb)));        // [h]
   vt_to_ext(h2r, fe_mul(u, rb));
   vt_to_ext(h2l, rb);
 }
+
+// phase b of a single-circuit proof: the walk, then the finish on its own share.  -> the share's ok
+HM_HD bool vt_phase_b(const uint32_t* plan, const VtMem& m, const Fr& num, uint32_t* own, uint32_t* shared, uint32_t* h2r, uint32_t* h2l) {
+  const VtmShare mine = vt_set_walk(plan, m, VtSingle{}, num, own, shared);
+  vt_finish(plan, plan[VT_N_OWN], m, mine.r_outer, mine, own, shared, h2r, h2l);
+  return mine.ok;
+}
+

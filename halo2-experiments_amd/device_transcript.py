@@ -3,7 +3,7 @@ one lane per message, and one lane per proof of a batch that absorbs the proof's
 leaves the eight challenges, reduced mod r, in the records ``hm_verify_terms_dev`` reads -- nothing comes back to the host.
 For proofs in the "evm" encoding the same with Keccak-256 (``hm_keccak256_dev`` / ``hm_verify_transcript_evm_dev``, csrc/keccak.inc).
 
-``batch_verifier.transcript_challenges`` (``hashlib``) stays the oracle and the default; ``BatchVerifier(transcript="device")`` is
+``proof_layout.transcript_challenges`` (``hashlib``) stays the oracle and the default; ``BatchVerifier(transcript="device")`` is
 what calls ``challenges``."""
 from __future__ import annotations
 

@@ -183,9 +183,9 @@ def verify_openings(params, commitment, indices, values, proofs, seed=None, k: i
         L = sum r_b pi_b,   R = (sum r_b) C - (sum r_b y_b) G + sum (r_b omega^(i_b)) pi_b,   e(L, [s]G2) = e(R, G2).
 
     The two sums over the proofs are MSMs on the device tensor, after ``g1_check``: an invalid point gives False.  r_b in [1, r) comes
-    from ``secrets`` when ``seed`` is None, else from (seed, b) as ``batch_verifier.derive_randomizer`` makes it.
+    from ``secrets`` when ``seed`` is None, else from (seed, b) as ``proof_layout.derive_randomizer`` makes it.
     ``pairing="device"`` runs that one pairing check on the GPU (``device_pairing``): the same boolean."""
-    from .batch_verifier import derive_randomizer
+    from .proof_layout import derive_randomizer
 
     k = params.k if k is None else int(k)
     idx = [int(i) for i in indices]

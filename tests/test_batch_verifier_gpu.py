@@ -124,6 +124,28 @@ def test_scalar_arrays_equal_the_weighted_twin(case):
         assert (got_r[b], got_l[b]) == (rb * o[own] % R, rb)
 
 
+def test_both_transcript_modes_prepare_one_state(poseidon):
+    """one preparation for both modes: the same keys, every device array equal, ybytes / preamble filled in their own mode only"""
+    c = poseidon
+    members = tiled(c, 5)
+    members[3] = (members[3][0], put(members[3][1], 0, P.to_bytes(32, "little")))            # a malformed point
+    states = {}
+    for mode in ("host", "device"):
+        bv = h.BatchVerifier(c["params"], c["vk"], seed=5, transcript=mode)
+        for inst, proof in members:
+            bv.add_proof(inst, proof)
+        states[mode] = bv._prepare()
+    a, b = states["host"], states["device"]
+    assert set(a) == set(b) == {"B", "bad", "d_bases", "d_scalars", "d_own", "d_shared", "d_h2_r", "d_h2_l", "d_sum", "d_bad", "d_ybytes",
+                                "d_proofs", "d_table", "d_records", "d_inst", "plan", "ybytes", "preamble"}
+    assert a["B"] == b["B"] == 5 and a["bad"] == b["bad"] == [False, False, False, True, False]
+    for key in a:
+        if key.startswith("d_"):
+            assert torch.equal(a[key], b[key]), key
+    assert a["ybytes"] is not None and b["ybytes"] is None and a["preamble"] is None and b["preamble"] is not None
+    assert np.array_equal(a["ybytes"], b["d_ybytes"].cpu().numpy())
+
+
 # ---- whole batches ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("count", [1, 2, 3, 64, 65, 257])
 def test_valid_batches(poseidon, count):
