@@ -96,14 +96,12 @@ __device__ __forceinline__ uint32_t effective_task_len(const uint32_t* __restric
 struct MsmGroupScalars {
   const uint32_t* s[HM_MSM_GROUP];
 };
-__global__ void msm_digits_kernel(MsmGroupScalars list, const uint8_t* __restrict__ inf,
-                                  int32_t* __restrict__ digits, size_t n, uint32_t c, uint32_t W, uint32_t n_wide) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t* __restrict__ scalars = list.s[blockIdx.y];
-  digits += (size_t)blockIdx.y * W * n;
-  const uint4* q = reinterpret_cast<const uint4*>(scalars + i * 8);
-  const uint4 lo = q[0], hi = q[1];
+// One point's W digits: digits[w * n + i] (0 for a base flagged as the identity).  COUNT: each non-zero digit is also
+// counted in its window's row of `hist` (LDS, W x NC counters): coarse bin = (|digit| - 1) >> fb, as the first sort level bins it.
+template <bool COUNT>
+__device__ __forceinline__ void msm_digits_point(const uint4 lo, const uint4 hi, bool skip, int32_t* __restrict__ digits, size_t n,
+                                                 size_t i, uint32_t c, uint32_t W, uint32_t n_wide, uint32_t* hist, uint32_t fb,
+                                                 uint32_t NC) {
   const uint32_t w_in[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
   // s_mont * 32 * 2^-261 = s_mont * 2^-256 = the canonical scalar (Fr::to_repr)
   Fr k32 = fe_zero<FrParams>();
@@ -117,7 +115,6 @@ __global__ void msm_digits_kernel(MsmGroupScalars list, const uint8_t* __restric
     for (int k = 0; k < 8; ++k) v[k] = t[k];
     v[8] = 0;
   }
-  const bool skip = inf[i] != 0;
   uint32_t carry = 0;
   for (uint32_t w = 0; w < W; ++w) {
     const uint32_t bits = w < n_wide ? c : c - 1;
@@ -134,9 +131,76 @@ __global__ void msm_digits_kernel(MsmGroupScalars list, const uint8_t* __restric
     // a narrow window's digit is DOUBLED and its table entry holds half the weight (2^(offset - 1) P): its points then
     // spread over the even buckets of the whole range instead of filling the lower half only (every coarse region of
     // the sort gets the same share: the lower half would hold seven times the upper one at c = 22, W = 12)
-    digits[(size_t)w * n + i] = skip ? 0 : (w < n_wide ? sd : 2 * sd);
+    const int32_t out = skip ? 0 : (w < n_wide ? sd : 2 * sd);
+    digits[(size_t)w * n + i] = out;
+    if constexpr (COUNT) {
+      if (out != 0) (void)lds_inc(hist + (size_t)w * NC, ((uint32_t)(out < 0 ? -out : out) - 1u) >> fb);
+    }
 #pragma unroll
     for (int k = 0; k < 8; ++k) v[k] = __funnelshift_r(v[k], v[k + 1], bits);
+  }
+}
+
+// COUNT = false: one lane per point (blockIdx.x * blockDim.x + threadIdx.x), nothing but the digits.
+// COUNT = true: the first sort level's coarse-bin counts come out of the same pass (a shared bucket set whose first-level
+// chunks each lie inside one window: n a multiple of the chunk).  The digit is in a register when it is stored, so the
+// histogram pass that would read all W n of them back (msm_part1_hist_kernel) is not launched.  Workgroup pc = blockIdx.x
+// takes the points [pc * chunk, + chunk) through ALL windows: W first-level chunks.  It keeps W x NC counters in LDS
+// (24 KiB at c = 22: W = 12, NC = 512) and ends by writing its W rows of chist with plain stores, row
+// set * G + w * (n / chunk) + pc: exactly what msm_part1_hist_kernel's workgroup (g, set) writes.  No global atomics,
+// nothing to zero first.  At 2^24 points that is one workgroup of 1024 lanes per CU; every lane requests its next scalar
+// before it works on the current one, which keeps the loads in flight that the short-lived workgroups of the plain form
+// get from their number.  The host launches this form only where n is a multiple of the chunk.
+constexpr int DIGITS_THREADS = 256;
+constexpr int DIGITS_COUNT_THREADS = 1024;
+template <bool COUNT>
+__global__ __launch_bounds__(COUNT ? DIGITS_COUNT_THREADS : DIGITS_THREADS) void msm_digits_kernel(
+    MsmGroupScalars list, const uint8_t* __restrict__ inf, int32_t* __restrict__ digits, size_t n, uint32_t c, uint32_t W,
+    uint32_t n_wide, uint32_t* __restrict__ chist, size_t chunk, uint32_t G, uint32_t fb, uint32_t NC) {
+  const uint32_t* __restrict__ scalars = list.s[blockIdx.y];
+  digits += (size_t)blockIdx.y * W * n;
+  if constexpr (!COUNT) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4* q = reinterpret_cast<const uint4*>(scalars + i * 8);
+    msm_digits_point<false>(q[0], q[1], inf[i] != 0, digits, n, i, c, W, n_wide, nullptr, 0, 0);
+  } else {
+    extern __shared__ uint32_t hist[];
+    const uint32_t pc = blockIdx.x;
+    for (uint32_t k = threadIdx.x; k < W * NC; k += DIGITS_COUNT_THREADS) hist[k] = 0;
+    __syncthreads();
+    const size_t lo = (size_t)pc * chunk, hi = lo + chunk < n ? lo + chunk : n;
+    size_t i = lo + threadIdx.x;
+    uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0;
+    bool skip = true;
+    if (i < hi) {
+      const uint4* q = reinterpret_cast<const uint4*>(scalars + i * 8);
+      q0 = q[0];
+      q1 = q[1];
+      skip = inf[i] != 0;
+    }
+    while (i < hi) {
+      const size_t in = i + DIGITS_COUNT_THREADS;
+      uint4 n0 = q0, n1 = q1;
+      bool nskip = true;
+      if (in < hi) {
+        const uint4* q = reinterpret_cast<const uint4*>(scalars + in * 8);
+        n0 = q[0];
+        n1 = q[1];
+        nskip = inf[in] != 0;
+      }
+      msm_digits_point<true>(q0, q1, skip, digits, n, i, c, W, n_wide, hist, fb, NC);
+      q0 = n0;
+      q1 = n1;
+      skip = nskip;
+      i = in;
+    }
+    __syncthreads();
+    const size_t cpw = n / chunk;                              // chunks per window
+    for (uint32_t w = 0; w < W; ++w) {
+      uint32_t* out = chist + ((size_t)blockIdx.y * G + (size_t)w * cpw + pc) * NC;
+      for (uint32_t b = threadIdx.x; b < NC; b += DIGITS_COUNT_THREADS) out[b] = hist[(size_t)w * NC + b];
+    }
   }
 }
 
@@ -1289,6 +1353,9 @@ __global__ __launch_bounds__(ACC_THREADS) HM_K3_OCC void msm_accumulate_kernel(c
 // K3b: bucket = sum of its task partials.  Buckets with at most FINALIZE_SERIAL partials are
 // summed by one lane; longer ones (hot buckets that K3 split into many tasks) are queued for
 // the workgroup-per-bucket kernel below so that no single lane walks a long chain.
+// `multi_only`: the reduction reads a one-task bucket straight from its partial and an empty one as the identity
+// (load_bucket_value), so only buckets with two or more partials are summed and stored here: for uniform scalars a task
+// is a bucket, and the pass would otherwise copy 112 B in and 112 B out for every one of them.
 constexpr uint32_t FINALIZE_SERIAL = 8;
 constexpr uint32_t FINALIZE_SLICE = 2048;   // partials one workgroup sums in the first level of a very hot bucket
 __global__ __launch_bounds__(ACC_THREADS) void msm_bucket_finalize_kernel(const uint32_t* __restrict__ partial,
@@ -1297,14 +1364,16 @@ __global__ __launch_bounds__(ACC_THREADS) void msm_bucket_finalize_kernel(const 
                                                                           uint32_t* __restrict__ big_count,
                                                                           uint32_t* __restrict__ big_list,
                                                                           uint2* __restrict__ slice_list,
-                                                                          const uint32_t* __restrict__ totals) {
+                                                                          const uint32_t* __restrict__ totals,
+                                                                          uint32_t multi_only) {
   const uint32_t b = blockIdx.x * ACC_THREADS + threadIdx.x;
   if (b >= NBT) return;
   if (totals[2]) {                         // overflow flag: no partial was written; leave an identity in every bucket
-    store_jac(bucket + (size_t)b * PT_WORDS, g1_identity());
+    if (!multi_only) store_jac(bucket + (size_t)b * PT_WORDS, g1_identity());   // (multi_only: the reader sees the flag itself)
     return;
   }
   const uint32_t lo = toff[b], hi = toff[b + 1];
+  if (multi_only && hi - lo < 2) return;
   if (hi - lo > FINALIZE_SERIAL) {
     big_list[atomicAdd(big_count, 1u)] = b;
     if (hi - lo > FINALIZE_SLICE) {   // very hot: its partials are first summed slice by slice, many workgroups
@@ -1363,6 +1432,29 @@ __global__ __launch_bounds__(WIN_THREADS) void msm_bucket_finalize_big_kernel(co
 // ---------------------------------------------------------------------------------------------
 // K4: per-window sum_b b * B_b
 // ---------------------------------------------------------------------------------------------
+// Where the reduction of a shared bucket set finds bucket gb (its index over all sets).  toff == nullptr: in bucket[gb], the
+// finalize pass wrote every bucket.  Else (msm_bucket_finalize_kernel's multi_only): no task = the identity, one task = that
+// task's partial, more = bucket[gb]; `none` (the overflow flag totals[2]: no partial was written) = identities everywhere.
+// The two task offsets are read one element ahead of the record (bucket_tasks), so that the record's address is known
+// when its load is issued.
+struct BucketTasks {
+  uint32_t lo, hi;
+};
+__device__ __forceinline__ BucketTasks bucket_tasks(const uint32_t* __restrict__ toff, uint32_t gb) {
+  BucketTasks r{0, 0};
+  if (toff != nullptr) {
+    r.lo = toff[gb];
+    r.hi = toff[gb + 1];
+  }
+  return r;
+}
+__device__ __forceinline__ G1Jac load_bucket_value(const uint32_t* __restrict__ bucket, const uint32_t* __restrict__ partial,
+                                                   const uint32_t* __restrict__ toff, bool none, BucketTasks tk, uint32_t gb) {
+  if (toff == nullptr) return load_jac(bucket + (size_t)gb * PT_WORDS);
+  if (none || tk.hi == tk.lo) return g1_identity();
+  return load_jac(tk.hi - tk.lo == 1 ? partial + (size_t)tk.lo * PT_WORDS : bucket + (size_t)gb * PT_WORDS);
+}
+
 // K4a: one lane per segment of SEG consecutive buckets [lo, lo+SEG): running sums give
 // sum (b - lo + 1) B_b; the remaining (lo - 1) * (sum B_b) is a short double-and-add.
 __global__ __launch_bounds__(ACC_THREADS) void msm_reduce_segments_kernel(const uint32_t* __restrict__ bucket,
@@ -1424,28 +1516,103 @@ __global__ __launch_bounds__(WIN_THREADS) void msm_sum_points_kernel(const uint3
 // bit, and the host fold, which doubles its way down 255 bits anyway, reads the c - 1 records S_p as windows of one bit.
 // Launch 1: workgroup `blk` < H sums row hi = blk, the others column lo = blk - H.
 // blockIdx.y = the bucket set (a group of MSMs over one table: one set each, NB + 1 bucket records and H + M sums apart)
+// (the buckets are read through load_bucket_value; `totals` = the chain's totals words, [2] the overflow flag)
 __global__ __launch_bounds__(WIN_THREADS) void msm_reduce_rowcol_kernel(const uint32_t* __restrict__ bucket, uint32_t* __restrict__ sums,
-                                                                        uint32_t m, uint32_t h) {
+                                                                        uint32_t m, uint32_t h, const uint32_t* __restrict__ partial,
+                                                                        const uint32_t* __restrict__ toff,
+                                                                        const uint32_t* __restrict__ totals) {
   __shared__ uint32_t tree[WIN_THREADS * PT_WORDS];
   const uint32_t M = 1u << m, H = 1u << h, blk = blockIdx.x, t = threadIdx.x;
-  bucket += (size_t)blockIdx.y * ((size_t)M * H + 1) * PT_WORDS;
+  const uint32_t b1 = blockIdx.y * (M * H + 1u) + 1u;                  // bucket b = j + 1 of this set, over all sets
   sums += (size_t)blockIdx.y * ((size_t)M + H) * PT_WORDS;
+  const bool none = toff != nullptr && totals[2] != 0;
   const bool row = blk < H;
   const uint32_t count = row ? M : H;                                  // elements of this sum
   const uint32_t first = row ? blk * M : blk - H, stride = row ? 1u : M;
-  const uint32_t* b1 = bucket + PT_WORDS;                              // bucket b = j + 1
   G1Jac acc = g1_identity();
   if (t < count) {
-    G1Jac cur = load_jac(b1 + (size_t)(first + t * stride) * PT_WORDS);
+    G1Jac cur = load_bucket_value(bucket, partial, toff, none, bucket_tasks(toff, b1 + first + t * stride), b1 + first + t * stride);
+    BucketTasks tk = t + WIN_THREADS < count ? bucket_tasks(toff, b1 + first + (t + WIN_THREADS) * stride) : BucketTasks{0, 0};
     for (uint32_t e = t; e < count; e += WIN_THREADS) {                // the next record is requested before the addition starts
-      const uint32_t en = e + WIN_THREADS;
-      const G1Jac nxt = en < count ? load_jac(b1 + (size_t)(first + en * stride) * PT_WORDS) : g1_identity();
+      const uint32_t en = e + WIN_THREADS, en2 = en + WIN_THREADS;
+      const G1Jac nxt = en < count ? load_bucket_value(bucket, partial, toff, none, tk, b1 + first + en * stride) : g1_identity();
+      if (en2 < count) tk = bucket_tasks(toff, b1 + first + en2 * stride);
       acc = g1_add(acc, cur);
       cur = nxt;
     }
   }
   const G1Jac r = block_sum_points_upto(tree, acc, count < WIN_THREADS ? count : WIN_THREADS);
   if (t == 0) store_jac(sums + (size_t)blk * PT_WORDS, r);
+}
+
+// The same H + M sums with ONE WAVE per workgroup and no tree wider than it: where the launch still gives every SIMD two
+// waves (H + M / 2 >= 2048: c >= 22), the 8-level trees of the form above are what it pays for -- a general addition is
+// ~3 700 dependent instructions, and a tree level keeps a whole wave issuing for 128, 64, ... 1 useful lanes.
+//   workgroup blk < H        row hi = blk: lane l sums the M / 64 elements lo = l, l + 64, ... then a 6-level tree of the wave;
+//   workgroup H + cp         columns 2 cp and 2 cp + 1, one per half wave: lane l of a half sums the H / 32 elements
+//                            hi = l, l + 32, ... then a 5-level tree inside the half.
+// Wave-additions issued at c = 22 (M = 2048, H = 1024): rows 1024 x (32 + 6), column pairs 1024 x (32 + 5) = 76 800 for
+// 2 x 2^21 / 64 = 65 536 useful: 1.17 x (the workgroup form: (4 x 8 + 9) x 1024 + (4 x 4 + 9) x 2048 = 93 184, 1.42 x).
+constexpr int WAVE_THREADS = 64;
+// acc += q, field by field: g1_add's `return p` / `return q` copy whole records, and with them the three padding bytes behind
+// the identity flag, which this kernel's loop then carries through a stack slot (12 bytes of scratch for nothing)
+__device__ __forceinline__ void jac_set(G1Jac& d, const G1Jac& s) {
+  d.x = s.x;
+  d.y = s.y;
+  d.z = s.z;
+  d.inf = s.inf;
+}
+__device__ __forceinline__ void jac_accumulate(G1Jac& acc, const G1Jac& q) {
+  if (q.inf) return;
+  if (acc.inf) {
+    jac_set(acc, q);
+    return;
+  }
+  const G1Jac r = g1_add_nz(acc, q);
+  jac_set(acc, r);
+}
+// Two waves per SIMD, stated: eight one-wave workgroups per CU and no more, so that the 2 048 of c = 22 spread over all
+// 256 CUs instead of filling some CUs three deep (the register budget would allow it) while others stand idle.
+__global__ __launch_bounds__(WAVE_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void msm_reduce_rowcol_wave_kernel(const uint32_t* __restrict__ bucket,
+                                                                              uint32_t* __restrict__ sums, uint32_t m, uint32_t h,
+                                                                              const uint32_t* __restrict__ partial,
+                                                                              const uint32_t* __restrict__ toff,
+                                                                              const uint32_t* __restrict__ totals) {
+  __shared__ uint32_t tree[WAVE_THREADS * PT_WORDS];
+  const uint32_t M = 1u << m, H = 1u << h, blk = blockIdx.x, t = threadIdx.x;
+  const uint32_t b1 = blockIdx.y * (M * H + 1u) + 1u;                  // bucket b = j + 1 of this set, over all sets
+  sums += (size_t)blockIdx.y * ((size_t)M + H) * PT_WORDS;
+  const bool none = toff != nullptr && totals[2] != 0;
+  const bool row = blk < H;
+  const uint32_t width = row ? 64u : 32u;                              // lanes per sum
+  const uint32_t l = t & (width - 1u);
+  const uint32_t count = row ? M : H;                                  // elements of this lane's sum
+  const uint32_t sum_index = row ? blk : H + 2u * (blk - H) + (t >> 5);   // where it goes: rows, then columns
+  const uint32_t first = row ? blk * M : sum_index - H, stride = row ? 1u : M;
+  G1Jac acc = g1_identity();
+  if (l < count) {
+    G1Jac cur = load_bucket_value(bucket, partial, toff, none, bucket_tasks(toff, b1 + first + l * stride), b1 + first + l * stride);
+    BucketTasks tk = l + width < count ? bucket_tasks(toff, b1 + first + (l + width) * stride) : BucketTasks{0, 0};
+    for (uint32_t e = l; e < count; e += width) {                      // the next record is requested before the addition starts
+      const uint32_t en = e + width, en2 = en + width;
+      const G1Jac nxt = en < count ? load_bucket_value(bucket, partial, toff, none, tk, b1 + first + en * stride) : g1_identity();
+      if (en2 < count) tk = bucket_tasks(toff, b1 + first + en2 * stride);
+      jac_accumulate(acc, cur);
+      jac_set(cur, nxt);
+    }
+  }
+  store_jac(tree + t * PT_WORDS, acc);                                 // lanes past `count` hold the identity
+  __syncthreads();
+  for (uint32_t off = width / 2; off > 0; off >>= 1) {
+    if (l < off) {
+      G1Jac a = load_jac(tree + t * PT_WORDS);
+      jac_accumulate(a, load_jac(tree + (t + off) * PT_WORDS));
+      store_jac(tree + t * PT_WORDS, a);
+    }
+    __syncthreads();
+  }
+  const G1Jac r = load_jac(tree + (t & ~(width - 1u)) * PT_WORDS);
+  if (l == 0) store_jac(sums + (size_t)sum_index * PT_WORDS, r);
 }
 
 // Launch 2: workgroup p sums the rows / columns whose weight has bit p and writes the record the host fold reads.
@@ -1796,12 +1963,13 @@ struct BigRegionPlan {      // cooperative handling of sort regions that hold fa
 template <class ITEM>
 static int launch_sort(const int32_t* d_digits, uint32_t* d_chist, uint32_t* d_ctot, uint32_t* d_cstart, void* d_tmp,
                        uint32_t* d_bcnt, size_t sn, size_t chunk, uint32_t G, uint32_t SW, uint32_t fb, uint32_t ib, uint32_t cb,
-                       uint32_t NC, uint32_t NBP, const BigRegionPlan& br, hipStream_t stream) {
+                       uint32_t NC, uint32_t NBP, const BigRegionPlan& br, bool counted, hipStream_t stream) {
   const size_t lds_fine = (size_t)4 << fb;
   if (cb) {
     const size_t lds_coarse = (size_t)NC * 4;
-    hipLaunchKernelGGL(msm_part1_hist_kernel, dim3(G, SW), dim3(SORT_THREADS), lds_coarse, stream, d_digits, d_chist, sn, chunk,
-                       fb, NC);
+    if (!counted)      // else the digits kernel left the coarse-bin counts behind (msm_digits_kernel<true>)
+      hipLaunchKernelGGL(msm_part1_hist_kernel, dim3(G, SW), dim3(SORT_THREADS), lds_coarse, stream, d_digits, d_chist, sn, chunk,
+                         fb, NC);
     hipLaunchKernelGGL(msm_part1_scan_kernel, dim3(SW * NC), dim3(64), 0, stream, d_chist, d_ctot, G, NC, SW);
     hipLaunchKernelGGL(msm_part1_starts_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t*)d_ctot, d_cstart, SW * NC);
     static const bool big_tiles = [] { const char* v = std::getenv("HALO2_MI355X_P1_BIG_TILES"); return !(v && *v == '0'); }();
@@ -1884,7 +2052,8 @@ int msm_launch_digits(const uint32_t* d_scalars_ext, const uint8_t* d_inf, int32
                       hipStream_t stream) {
   MsmGroupScalars one;
   for (auto& p : one.s) p = d_scalars_ext;
-  hipLaunchKernelGGL(msm_digits_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, one, d_inf, d_digits, n, c, W, W);
+  hipLaunchKernelGGL(msm_digits_kernel<false>, dim3((uint32_t)((n + DIGITS_THREADS - 1) / DIGITS_THREADS)), dim3(DIGITS_THREADS), 0, stream,
+                     one, d_inf, d_digits, n, c, W, W, (uint32_t*)nullptr, (size_t)0, 0u, 0u, 0u);
   HM_HIP_CHECK(hipGetLastError());
   return HM_OK;
 }
@@ -1999,6 +2168,18 @@ static int msm_issue(DeviceCtx& ctx, int slot, const uint32_t* const* d_scalars_
   const bool k4_2d = single_set && NB >= 16 && !k4_chain_only;
   const uint32_t k4_m = (c - 1 + 1) / 2, k4_h = (c - 1) - k4_m;        // M = 2^m columns, H = 2^h rows, M * H = NB
   if (group > 1 && !k4_2d) return hm_fail(HM_ERR_INTERNAL, "msm: a table group needs the two-launch bucket reduction");
+  // Two A/B switches of the shared set's reduction, read at every call so that one process can run both arms:
+  // HALO2_MI355X_K3B_COPY=1: msm_bucket_finalize_kernel writes every bucket and the reduction reads only those (else it
+  // reads one-task buckets from their partials: load_bucket_value).  HALO2_MI355X_K4_WAVE_SUMS: 0 = the workgroup form of
+  // the row / column sums, 1 = the one-wave form at every size; unset = the one-wave form where its H + M / 2 waves give
+  // each of the chip's 1 024 SIMDs two (c >= 22; below, the wide trees' shorter critical path wins).
+  bool direct_buckets = false, wave_sums = false;
+  if (k4_2d) {
+    const char* v = std::getenv("HALO2_MI355X_K3B_COPY");
+    direct_buckets = !(v && *v == '1');
+    v = std::getenv("HALO2_MI355X_K4_WAVE_SUMS");
+    wave_sums = v && *v ? *v == '1' : ((1u << k4_h) + (1u << (k4_m - 1))) * SW >= 2048u;
+  }
   const uint32_t RW = k4_2d ? c - 1 : SW;                               // records the host fold reads (per bucket set of a table)
   const uint32_t res_stride = 4 + RW * 32;                              // words per element of a group: the totals, then its records
   // sort plan: item = [fine bucket bits | sign | item index]
@@ -2040,6 +2221,17 @@ static int msm_issue(DeviceCtx& ctx, int slot, const uint32_t* const* d_scalars_
   }
   if (ps.nsc == 0 && sn >= (1u << 15) && (c - 1) - fb < 5) fb = c - 1 > 5 ? c - 1 - 5 : 0;   // >= 32 regions per set: enough workgroups
   const uint32_t cb = (c - 1) - fb, NC = 1u << cb;
+  // Coarse-bin counts from the digits pass (msm_digits_kernel<true>): a shared bucket set with a first sort level whose
+  // chunks each lie inside one window, 32-bit items, the vector-load sort -- and a workgroup per chunk of points for every
+  // one of the chip's 256 CUs (2^24 points): the form has n / chunk workgroups, and below that it loses more in the digits
+  // kernel than the histogram pass costs (2^20 points, 16 workgroups: 0.37 against 0.03 ms).  HALO2_MI355X_DIGITS_COUNT:
+  // 0 = the separate histogram pass, 1 = the counting form wherever it is valid (A/B and tests; read at every call, so that
+  // one process can run both arms).
+  bool digits_count = false;
+  if (single_set && cb != 0 && !wide_items && !sort_v1() && n % chunk == 0 && (size_t)G * chunk == sn && (size_t)W * NC * 4 <= 48 * 1024) {
+    const char* v = std::getenv("HALO2_MI355X_DIGITS_COUNT");
+    digits_count = v && *v ? *v == '1' : (n / chunk) * group >= 256;
+  }
 
   // ---- workspace ----------------------------------------------------------------------------
   auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -2174,8 +2366,12 @@ static int msm_issue(DeviceCtx& ctx, int slot, const uint32_t* const* d_scalars_
   {
     MsmGroupScalars list;
     for (uint32_t e = 0; e < (uint32_t)HM_MSM_GROUP; ++e) list.s[e] = d_scalars_list[e < group ? e : 0];
-    hipLaunchKernelGGL(msm_digits_kernel, dim3((uint32_t)((n + 255) / 256), group), dim3(256), 0, stream, list, d_inf, d_digits, n, c, W,
-                       n_wide);
+    if (digits_count)
+      hipLaunchKernelGGL(msm_digits_kernel<true>, dim3((uint32_t)(n / chunk), group), dim3(DIGITS_COUNT_THREADS), (size_t)W * NC * 4,
+                         stream, list, d_inf, d_digits, n, c, W, n_wide, d_chist, chunk, G, fb, NC);
+    else
+      hipLaunchKernelGGL(msm_digits_kernel<false>, dim3((uint32_t)((n + DIGITS_THREADS - 1) / DIGITS_THREADS), group), dim3(DIGITS_THREADS), 0,
+                         stream, list, d_inf, d_digits, n, c, W, n_wide, (uint32_t*)nullptr, (size_t)0, 0u, 0u, 0u);
   }
   HM_HIP_CHECK(hipGetLastError());
   if (pt) HM_HIP_CHECK(hipEventRecord(ev[1], stream));
@@ -2190,9 +2386,9 @@ static int msm_issue(DeviceCtx& ctx, int slot, const uint32_t* const* d_scalars_
     }
     const int rc = wide_items
                        ? launch_sort<uint64_t>(d_digits, d_chist, d_ctot, d_cstart, d_tmp, d_bcnt, sn, chunk, G, SW, fb, ib, cb,
-                                               NC, NBP, br, stream)
+                                               NC, NBP, br, digits_count, stream)
                        : launch_sort<uint32_t>(d_digits, d_chist, d_ctot, d_cstart, d_tmp, d_bcnt, sn, chunk, G, SW, fb, ib, cb,
-                                               NC, NBP, br, stream);
+                                               NC, NBP, br, digits_count, stream);
     if (rc != HM_OK) return rc;
   }
   // pair count for effective_task_len: the first sort level leaves it behind its region starts; an
@@ -2247,7 +2443,7 @@ static int msm_issue(DeviceCtx& ctx, int slot, const uint32_t* const* d_scalars_
   if (pt) HM_HIP_CHECK(hipEventRecord(ev[6], stream));
   hipLaunchKernelGGL(msm_bucket_finalize_kernel, dim3((NBT + ACC_THREADS - 1) / ACC_THREADS), dim3(ACC_THREADS), 0, stream,
                      (const uint32_t*)d_partial, (const uint32_t*)d_toff, d_bucket, NBT, d_big_count, d_big_list, d_slices,
-                     (const uint32_t*)d_tot);
+                     (const uint32_t*)d_tot, direct_buckets ? 1u : 0u);
   HM_HIP_CHECK(hipGetLastError());
   {
     uint32_t slice_grid = (uint32_t)(T_max / FINALIZE_SLICE + 1);       // upper bound on the number of full slices
@@ -2265,8 +2461,14 @@ static int msm_issue(DeviceCtx& ctx, int slot, const uint32_t* const* d_scalars_
 
   // ---- K4 ------------------------------------------------------------------------------------
   if (k4_2d) {
-    hipLaunchKernelGGL(msm_reduce_rowcol_kernel, dim3((1u << k4_m) + (1u << k4_h), SW), dim3(WIN_THREADS), 0, stream,
-                       (const uint32_t*)d_bucket, d_seg, k4_m, k4_h);
+    const uint32_t* rd_partial = direct_buckets ? (const uint32_t*)d_partial : (const uint32_t*)nullptr;
+    const uint32_t* rd_toff = direct_buckets ? (const uint32_t*)d_toff : (const uint32_t*)nullptr;
+    if (wave_sums)
+      hipLaunchKernelGGL(msm_reduce_rowcol_wave_kernel, dim3((1u << k4_h) + (1u << (k4_m - 1)), SW), dim3(WAVE_THREADS), 0, stream,
+                         (const uint32_t*)d_bucket, d_seg, k4_m, k4_h, rd_partial, rd_toff, (const uint32_t*)d_tot);
+    else
+      hipLaunchKernelGGL(msm_reduce_rowcol_kernel, dim3((1u << k4_m) + (1u << k4_h), SW), dim3(WIN_THREADS), 0, stream,
+                         (const uint32_t*)d_bucket, d_seg, k4_m, k4_h, rd_partial, rd_toff, (const uint32_t*)d_tot);
     hipLaunchKernelGGL(msm_reduce_bits_kernel, dim3(RW, SW), dim3(WIN_THREADS), 0, stream, (const uint32_t*)d_seg, k4_m, k4_h, d_win,
                        res_stride);
     HM_HIP_CHECK(hipGetLastError());
