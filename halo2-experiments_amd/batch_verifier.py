@@ -48,7 +48,17 @@ A verdict PER PROOF (``verdicts``, ``failing(method="each")``, ``verify_each``) 
 workgroup per proof sums the proof's own pair (L_b, R_b) (``hm_verify_proof_sums_dev``, csrc/verify_sums.inc; ``proof_sums_ints`` is
 the integer twin), and one pairing call checks e(L_b, [s]G2) = e(R_b, G2) for every proof at once.  The weights r_b stay in the scalar
 arrays, so the per-proof sums equal ``_sums(handle, b, b + 1)`` as group elements; a verdict does not depend on r_b, which multiplies
-both sides of the proof's own equation."""
+both sides of the proof's own equation.
+
+``multiopen="gwc"`` (``ProofLayout``, ``BatchVerifier``, ``verify_proofs``; single-circuit, both encodings, all four ``pairing`` x
+``transcript`` modes) takes proofs that end in the GWC multiopen (``gwc``): q witness points W_i behind the evaluations, all of them own
+points, seven challenges.  Read and transcript are the same kernels on the layout's table and schedule; the terms are
+``hm_verify_terms_gwc_dev`` driven by a ``GwcTermsPlan`` -- the same phase a and numerator, the point groups' phase b --, which also
+leaves r_b u_b^i in ``d_w_left``.  The check is e(sum_b sum_i r_b u_b^i W_bi, [s]G2) = e(sum_b R_b, G2): the left sum ONE MSM of the W
+points (copied behind the shared points, where SHPLONK's tail points stand) against ``d_w_left``, the right sum the own-points MSM
+and the shared column sums -- three MSMs per check.  The gap left: a verdict per proof (``verdicts``, ``failing(method="each")``,
+``verify_each``, ``proof_sums``) raises ValueError, since the per-proof sums kernel writes L_b from ONE tail point; and
+multi-circuit GWC batches (``circuits`` > 1: ValueError)."""
 from __future__ import annotations
 
 import ctypes
@@ -63,12 +73,12 @@ from .bn256 import fr_array, g1_words
 from .keygen import VerifyingKey
 from .kzg import g2_from_bytes
 from .pairing import g1_mul, g1_neg, g1_on_curve
-from .proof_layout import (EVM_POINT, EVM_SKIP, EVM_TAIL, MAX_CIRCUITS, RECORD, VM_HDR, VR_POINT, VR_TAIL, VT_MAX_INST_ROWS,  # noqa: F401
-                           VT_MAX_SUPER, VT_MAX_T, VT_MAX_VALS, VT_NO_SLOT, VT_T_H, VT_T_SHARED, MalformedProof, MultiTermsPlan, ProofLayout, R,
-                           TermsPlan, _instance_columns, _layout_instances, derive_randomizer, proof_sums_ints, proof_terms_ints,
+from .proof_layout import (EVM_POINT, EVM_SKIP, EVM_TAIL, GWC_RECORD, MAX_CIRCUITS, RECORD, VM_HDR, VR_POINT, VR_TAIL,  # noqa: F401
+                           VT_MAX_INST_ROWS, VT_MAX_SUPER, VT_MAX_T, VT_MAX_VALS, VT_NO_SLOT, VT_T_H, VT_T_SHARED, GwcTermsPlan, MalformedProof,
+                           MultiTermsPlan, ProofLayout, R, TermsPlan, _instance_columns, _layout_instances, derive_randomizer, proof_sums_ints, proof_terms_ints,
                            read_proof_ints, shared_points, terms_from_challenges, transcript_challenges)
 from .shplonk import g1_words_to_int
-from .transcript import check_encoding
+from .transcript import check_encoding, check_multiopen
 from .verifier import _vk_digest
 
 VERDICT_CHUNK = 1 << 16                                                # proofs per pairing call of ``verdicts``: the largest measured size
@@ -108,15 +118,18 @@ class BatchVerifier:
     multi-circuit proofs in this encoding are the one combination left out (``circuits`` > 1 with "evm": ValueError)."""
 
     def __init__(self, params, vk: VerifyingKey, seed=None, pairing: str = "host", transcript: str = "host", encoding: str = "halo2",
-                 circuits: int = 1):
+                 circuits: int = 1, multiopen: str = "shplonk"):
         check_encoding(encoding, "BatchVerifier")
+        check_multiopen(multiopen, "BatchVerifier")
+        if multiopen == "gwc" and circuits != 1:
+            raise ValueError("BatchVerifier: multi-circuit batches with the \"gwc\" multiopen are not supported (circuits > 1)")
         if pairing not in device_pairing.MODES:
             raise ValueError(f"BatchVerifier: pairing must be one of {device_pairing.MODES}, got {pairing!r}")
         if transcript not in device_transcript.MODES:
             raise ValueError(f"BatchVerifier: transcript must be one of {device_transcript.MODES}, got {transcript!r}")
         self.params, self.vk, self.seed, self.pairing, self.transcript = params, vk, seed, pairing, transcript
-        self.encoding = encoding
-        self.layout = ProofLayout(vk.cs, vk.domain.k, encoding, circuits)   # ValueError: circuits outside 1 .. 64, or "evm" with several
+        self.encoding, self.multiopen = encoding, multiopen
+        self.layout = ProofLayout(vk.cs, vk.domain.k, encoding, circuits, multiopen)   # ValueError: circuits outside 1 .. 64, or "evm" with several
         self.circuits = self.layout.circuits
         self._digest = _vk_digest(vk)
         self._shared = shared_points(vk, self.layout)
@@ -162,7 +175,7 @@ class BatchVerifier:
     def _plan_for(self, inst_rows: Sequence[int]):
         key = tuple(inst_rows) if self.circuits == 1 else (tuple(inst_rows), self.circuits)
         if key not in self._plans:
-            make = TermsPlan if self.circuits == 1 else MultiTermsPlan
+            make = GwcTermsPlan if self.multiopen == "gwc" else TermsPlan if self.circuits == 1 else MultiTermsPlan
             self._plans[key] = make(self.layout, self.vk.domain.omega, inst_rows)
         if self._program is None:
             self._program = ev.CompiledGraph(**self._plans[key].lowered)
@@ -189,11 +202,16 @@ class BatchVerifier:
         return self._instances if self.circuits == 1 else [[col for one in inst for col in one] for inst in self._instances]
 
     def _queue_terms(self, plan, B: int, d_records, d_scalars, d_inst, d_bad, d_own, d_shared, d_h2_r, d_h2_l, stream) -> None:
-        """the terms kernel on ``stream``: ``hm_verify_terms_dev``, or for multi-circuit proofs ``hm_verify_terms_multi_dev``"""
+        """the terms kernel on ``stream``: ``hm_verify_terms_dev``, for multi-circuit proofs ``hm_verify_terms_multi_dev``, for GWC
+        proofs ``hm_verify_terms_gwc_dev`` (``d_h2_r`` is then ``d_w_left`` and ``d_h2_l`` None)"""
         lib = _lib.load()
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         u32p = ctypes.POINTER(ctypes.c_uint32)
         head = (ctypes.c_uint64(self._program.handle), plan.words.ctypes.data_as(u32p), len(plan.words), plan.n_columns, 4, B)
+        if self.multiopen == "gwc":
+            _lib.check(lib.hm_verify_terms_gwc_dev(*head, vp(d_records), vp(d_scalars), vp(d_inst), ctypes.cast(vp(d_bad), u32p), vp(d_own),
+                                                   vp(d_shared), vp(d_h2_r), stream))
+            return
         tail = (vp(d_records), vp(d_scalars), vp(d_inst), ctypes.cast(vp(d_bad), u32p), vp(d_own), vp(d_shared), vp(d_h2_r), vp(d_h2_l), stream)
         if self.circuits == 1:
             _lib.check(lib.hm_verify_terms_dev(*head, *tail))
@@ -227,7 +245,9 @@ class BatchVerifier:
         lay, B, on_device, evm = self.layout, len(self._proofs), self.transcript == "device", self.encoding == "evm"
         dev = torch.device("cuda", torch.cuda.current_device())
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        n_shared, own, n_ch = len(lay.shared_keys), lay.own_points, len(RECORD)
+        n_shared, own, n_ch = len(lay.shared_keys), lay.own_points, len(lay.record)
+        gwc = self.multiopen == "gwc"
+        q = len(lay.groups) if gwc else 1                         # points per proof behind the shared ones: the W_i, or the tail [h']
         up = lambda words: torch.from_numpy(words.view(np.int64)).to(dev)
         new = lambda fill, *shape, dtype=torch.int64: fill(shape, dtype=dtype, device=dev)
         t = [time.perf_counter()]
@@ -251,15 +271,20 @@ class BatchVerifier:
                   d_proofs=torch.from_numpy(raw).to(dev),
                   d_table=torch.from_numpy(lay.slot_table.view(np.int32)).to(dev),   # a device table, not a kernel argument
                   d_bad=torch.tensor([int(x) for x in bad], dtype=torch.int32, device=dev),   # the kernels only ever set a flag
-                  d_bases=new(torch.zeros, B * own + n_shared + B, 8))
+                  d_bases=new(torch.zeros, B * own + n_shared + B * q, 8))
         st["d_bases"][B * own:B * own + n_shared] = up(np.stack([g1_words(p) for p in self._shared]))
         st.update(d_ybytes=None if evm else new(torch.zeros, B, lay.n_points, 32, dtype=torch.uint8),
                   d_scalars=new(torch.zeros, B, lay.n_scalars, 4), d_own=new(torch.empty, B * own, 4),
-                  d_shared=new(torch.empty, B, n_shared, 4), d_h2_r=new(torch.empty, B, 4), d_h2_l=new(torch.empty, B, 4),
-                  d_sum=new(torch.zeros, n_shared, 4))
+                  d_shared=new(torch.empty, B, n_shared, 4), d_h2_r=None if gwc else new(torch.empty, B, 4),
+                  d_h2_l=None if gwc else new(torch.empty, B, 4), d_sum=new(torch.zeros, n_shared, 4))
+        if gwc:                                                   # the one key a "gwc" state has beyond the others: r_b u^i per witness
+            st["d_w_left"] = new(torch.empty, B, q, 4)
         lap()                                                     # t[3]: allocated and uploaded
         self._queue_read(st["d_proofs"], st["d_table"], st["d_bases"], st["d_bases"][B * own + n_shared:], st["d_ybytes"], st["d_scalars"],
                          st["d_bad"], stream)
+        if gwc:                                                   # no slot has a tail bit: the region behind the shared points was the tail
+            # buffer nothing is routed to; now it takes the W points, proof after proof, for the left sum's one MSM
+            st["d_bases"][B * own + n_shared:] = st["d_bases"][:B * own].view(B, own, 8)[:, own - q:].reshape(B * q, 8)
         if not on_device:                                         # everything a proof's challenges depend on comes to the host
             st["ybytes"] = None if evm else st["d_ybytes"].cpu().numpy()
             flagged = st["d_bad"].cpu().numpy()
@@ -272,13 +297,13 @@ class BatchVerifier:
                 if not flagged[b]:
                     ch = transcript_challenges(lay, self._digest, self._instances[b], self._proofs[b],
                                                None if evm else [bytes(row) for row in st["ybytes"][b]])
-                    records[b, :n_ch] = fr_array([ch[name] for name in RECORD])
+                    records[b, :n_ch] = fr_array([ch[name] for name in lay.record])
         lap()                                                     # t[5]: the challenges
         if not on_device:
             st["d_records"] = up(records)
         lap()                                                     # t[6]: the host's records uploaded
-        self._queue_terms(plan, B, st["d_records"], st["d_scalars"], st["d_inst"], st["d_bad"], st["d_own"], st["d_shared"], st["d_h2_r"],
-                          st["d_h2_l"], stream)
+        self._queue_terms(plan, B, st["d_records"], st["d_scalars"], st["d_inst"], st["d_bad"], st["d_own"], st["d_shared"],
+                          st["d_w_left"] if gwc else st["d_h2_r"], st["d_h2_l"], stream)
         st["bad"] = [bool(x) for x in st["d_bad"].cpu().numpy()]  # device mode's one download: what the three kernels flagged
         lap()                                                     # t[7]: terms
         read, upload = t[1] - t[0] + t[4] - t[3], t[3] - t[2] + t[6] - t[5]
@@ -301,16 +326,22 @@ class BatchVerifier:
         return out
 
     def _sums(self, handle, lo: int, hi: int):
-        """(L, R) of the proofs [lo, hi) as (x, y) integers: four MSMs over offsets into the registered array, folded on the host"""
+        """(L, R) of the proofs [lo, hi) as (x, y) integers: four MSMs (three under "gwc") over offsets into the registered array,
+        folded on the host"""
         from .arithmetic import best_multiexp
 
         st, own, n_shared = self._state, self.layout.own_points, len(self.layout.shared_keys)
         B = st["B"]
         parts = [best_multiexp(st["d_own"][lo * own:hi * own], handle, offset=lo * own),
-                 best_multiexp(self.column_sum(lo, hi), handle, offset=B * own),
-                 best_multiexp(st["d_h2_r"][lo:hi], handle, offset=B * own + n_shared + lo)]
-        left = best_multiexp(st["d_h2_l"][lo:hi], handle, offset=B * own + n_shared + lo)
-        self.msm_calls += 4
+                 best_multiexp(self.column_sum(lo, hi), handle, offset=B * own)]
+        if self.multiopen == "gwc":                                # three MSMs: the W rows of d_own carry r_b u^i z_i, d_w_left r_b u^i
+            q = len(self.layout.groups)
+            left = best_multiexp(st["d_w_left"][lo:hi].reshape((hi - lo) * q, 4), handle, offset=B * own + n_shared + lo * q)
+            self.msm_calls += 3
+        else:
+            parts.append(best_multiexp(st["d_h2_r"][lo:hi], handle, offset=B * own + n_shared + lo))
+            left = best_multiexp(st["d_h2_l"][lo:hi], handle, offset=B * own + n_shared + lo)
+            self.msm_calls += 4
         right = np.zeros(12, dtype=np.uint64)
         stacked = np.ascontiguousarray(np.stack(parts))
         u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -361,6 +392,7 @@ class BatchVerifier:
         batch gives an empty (0, 2, 8) tensor; ``msm_calls`` is not touched.  ``timings["sums"]`` is the wall time of QUEUEING the call: the device's work surfaces in the download behind it."""
         import torch
 
+        self._no_verdicts("proof_sums")
         if not self._proofs:                                     # nothing to prepare: an empty (0, 2, 8) tensor, no launch
             return torch.zeros((0, 2, 8), dtype=torch.int64, device="cuda" if torch.cuda.is_available() else "cpu")
         st = self._prepare()
@@ -381,6 +413,12 @@ class BatchVerifier:
         st["d_pairs"] = d_pairs
         return d_pairs
 
+    def _no_verdicts(self, who: str) -> None:
+        """the per-proof road is SHPLONK's: the sums kernel writes L_b from one tail point, a GWC proof has q witness points"""
+        if self.multiopen == "gwc":
+            raise ValueError(f"BatchVerifier.{who}: per-proof verdicts are not available with the \"gwc\" multiopen "
+                             "(finalize and failing() by bisection are)")
+
     def verdicts(self, trapdoor: int = None) -> List[bool]:
         """One boolean per added proof, in order: does THIS proof verify -- what ``verify_proof`` answers, without bisection.  A
         malformed proof is False from its flag (its rows are identities, which a pairing would pass).  For the others the per-proof
@@ -392,6 +430,7 @@ class BatchVerifier:
         the download included."""
         import torch
 
+        self._no_verdicts("verdicts")
         if not self._proofs:
             return []
         st = self._prepare()
@@ -437,6 +476,7 @@ class BatchVerifier:
         if method not in ("bisect", "each"):
             raise ValueError(f"BatchVerifier.failing: method must be 'bisect' or 'each', got {method!r}")
         if method == "each":
+            self._no_verdicts("failing(method=\"each\")")
             return [b for b, ok in enumerate(self.verdicts(trapdoor)) if not ok]
         if not self._proofs:
             return []
@@ -462,6 +502,7 @@ class BatchVerifier:
 def _batch_of(who: str, params, vk: VerifyingKey, instances, proofs, seed, **modes) -> BatchVerifier:
     """the ``BatchVerifier`` behind ``verify_proofs`` and ``verify_each``: one proof added per (instance, proof)"""
     check_encoding(modes["encoding"], who)
+    check_multiopen(modes.get("multiopen", "shplonk"), who)
     instances, proofs = list(instances), list(proofs)
     if len(instances) != len(proofs):
         raise ValueError(f"{who}: one instance per proof")
@@ -472,18 +513,23 @@ def _batch_of(who: str, params, vk: VerifyingKey, instances, proofs, seed, **mod
 
 
 def verify_proofs(params, vk: VerifyingKey, instances, proofs, seed=None, trapdoor: int = None, pairing: str = "host",
-                  transcript: str = "host", encoding: str = "halo2", circuits: int = 1) -> bool:
+                  transcript: str = "host", encoding: str = "halo2", circuits: int = 1, multiopen: str = "shplonk") -> bool:
     """True when every ``proofs[i]`` is a valid single-circuit proof of ``vk`` for ``instances[i]``: one ``BatchVerifier``, one check
     (``pairing`` / ``transcript``: where that check's pairing and the proofs' transcripts run, ``encoding``: the proofs' wire format,
-    ``circuits=m``: every proof is a ``create_proof_multi`` proof and ``instances[i]`` its m instances, as on ``BatchVerifier``)"""
+    ``circuits=m``: every proof is a ``create_proof_multi`` proof and ``instances[i]`` its m instances, ``multiopen``: the scheme
+    the proofs end in, as on ``BatchVerifier``)"""
     return _batch_of("verify_proofs", params, vk, instances, proofs, seed, pairing=pairing, transcript=transcript, encoding=encoding,
-                     circuits=circuits).finalize(trapdoor)
+                     circuits=circuits, multiopen=multiopen).finalize(trapdoor)
 
 
 def verify_each(params, vk: VerifyingKey, instances, proofs, seed=None, trapdoor: int = None, pairing: str = "host",
-                transcript: str = "host", encoding: str = "halo2", circuits: int = 1) -> List[bool]:
+                transcript: str = "host", encoding: str = "halo2", circuits: int = 1, multiopen: str = "shplonk") -> List[bool]:
     """[is ``proofs[i]`` a valid single-circuit proof of ``vk`` for ``instances[i]``]: one ``BatchVerifier``, its ``verdicts`` -- the
-    per-proof sums in one launch and, with ``pairing="device"``, one pairing call for all proofs (keywords as on ``verify_proofs``)"""
+    per-proof sums in one launch and, with ``pairing="device"``, one pairing call for all proofs (keywords as on ``verify_proofs``;
+    ``multiopen="gwc"`` raises ValueError: no verdict per proof under GWC)"""
+    check_multiopen(multiopen, "verify_each")
+    if multiopen == "gwc":
+        raise ValueError("verify_each: per-proof verdicts are not available with the \"gwc\" multiopen")
     return _batch_of("verify_each", params, vk, instances, proofs, seed, pairing=pairing, transcript=transcript, encoding=encoding,
                      circuits=circuits).verdicts(trapdoor)
 

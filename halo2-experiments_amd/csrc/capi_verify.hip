@@ -51,15 +51,19 @@ int hm_verify_column_sum_dev(const void* d_rows, size_t n_rows, uint32_t columns
   return verify_colsum_run((const uint32_t*)d_rows, columns, lo, hi, (uint32_t*)d_out, (hipStream_t)stream);
 } HM_API_CATCH("hm_verify_column_sum_dev")
 
-// ---- the per-proof terms (verify_terms.inc, verify.hip): ONE entry behind the two of the ABI ------------------------------------------
-// multi: proofs of `circuits` circuits each (a circuits of 0 is the caller's mistake there, so it cannot stand for "single"), else
-// single-circuit proofs and `circuits` is not looked at.  proof_bits: log2 of the most proofs a call takes.  The checks keep their order.
-static int verify_terms_entry(const std::string& who, uint32_t circuits, bool multi, unsigned proof_bits, uint64_t graph, const uint32_t* plan,
+// ---- the per-proof terms (verify_terms.inc, verify.hip): ONE entry behind the three of the ABI ----------------------------------------
+// road: VT_MULTI, proofs of `circuits` circuits each (a circuits of 0 is the caller's mistake there, so it cannot stand for "single");
+// VT_SINGLE, single-circuit SHPLONK proofs, and VT_GWC, single-circuit GWC proofs (d_h2_r is then d_w_left and d_h2_l is given the
+// same pointer, which nothing reads): `circuits` is not looked at.  proof_bits: log2 of the most proofs a call takes.  The checks keep
+// their order.
+enum VtRoad { VT_SINGLE, VT_MULTI, VT_GWC };
+static int verify_terms_entry(const std::string& who, uint32_t circuits, VtRoad road, unsigned proof_bits, uint64_t graph, const uint32_t* plan,
                               size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs, const void* d_records,
                               const void* d_scalars, const void* d_instance, uint32_t* d_bad, void* d_own, void* d_shared, void* d_h2_r,
                               void* d_h2_l, void* stream) {
   if (!plan || !d_records || !d_scalars || !d_instance || !d_bad || !d_own || !d_shared || !d_h2_r || !d_h2_l)
     return hm_fail(HM_ERR_BAD_ARG, who + ": null argument");
+  const bool multi = road == VT_MULTI;
   if (multi && (circuits == 0 || circuits > VM_MAX_CIRCUITS)) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= circuits <= 64");
   if (n_proofs == 0 || n_proofs > ((size_t)1 << proof_bits))
     return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n_proofs <= 2^" + std::to_string(proof_bits));
@@ -68,7 +72,9 @@ static int verify_terms_entry(const std::string& who, uint32_t circuits, bool mu
   if (((uintptr_t)d_records | (uintptr_t)d_scalars | (uintptr_t)d_instance | (uintptr_t)d_own | (uintptr_t)d_shared | (uintptr_t)d_h2_r |
        (uintptr_t)d_h2_l | (uintptr_t)d_bad) & 3u)
     return hm_fail(HM_ERR_BAD_ARG, who + ": a buffer is not 4-byte aligned");
-  if (const char* why = multi ? vtm_plan_problem(plan, n_plan_words, n_columns, circuits) : vt_plan_problem(plan, n_plan_words, n_columns))
+  if (const char* why = multi            ? vtm_plan_problem(plan, n_plan_words, n_columns, circuits)
+                        : road == VT_GWC ? vg_plan_problem(plan, n_plan_words, n_columns)
+                                         : vt_plan_problem(plan, n_plan_words, n_columns))
     return hm_fail(HM_ERR_BAD_ARG, why);
   DeviceCtx* ctx = ctx_for_current_device();
   if (!ctx) return HM_ERR_NO_DEVICE;
@@ -82,6 +88,9 @@ static int verify_terms_entry(const std::string& who, uint32_t circuits, bool mu
   if (multi)
     return verify_terms_multi_run(*ctx, *g, plan, n_plan_words, n_columns, n_dynamic, n_proofs, circuits, records, evals, inst, d_bad, own, shared,
                                   h2r, h2l, (hipStream_t)stream);
+  if (road == VT_GWC)
+    return verify_terms_gwc_run(*ctx, *g, plan, n_plan_words, n_columns, n_dynamic, n_proofs, records, evals, inst, d_bad, own, shared, h2r,
+                                (hipStream_t)stream);
   return verify_terms_run(*ctx, *g, plan, n_plan_words, n_columns, n_dynamic, n_proofs, records, evals, inst, d_bad, own, shared, h2r, h2l,
                           (hipStream_t)stream);
 }
@@ -89,16 +98,23 @@ static int verify_terms_entry(const std::string& who, uint32_t circuits, bool mu
 int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
                         const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad, void* d_own, void* d_shared,
                         void* d_h2_r, void* d_h2_l, void* stream) try {
-  return verify_terms_entry("hm_verify_terms_dev", 0, false, 20, graph, plan, n_plan_words, n_columns, n_dynamic, n_proofs, d_records, d_scalars,
+  return verify_terms_entry("hm_verify_terms_dev", 0, VT_SINGLE, 20, graph, plan, n_plan_words, n_columns, n_dynamic, n_proofs, d_records, d_scalars,
                             d_instance, d_bad, d_own, d_shared, d_h2_r, d_h2_l, stream);
 } HM_API_CATCH("hm_verify_terms_dev")
 
 int hm_verify_terms_multi_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
                               uint32_t circuits, const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad,
                               void* d_own, void* d_shared, void* d_h2_r, void* d_h2_l, void* stream) try {
-  return verify_terms_entry("hm_verify_terms_multi_dev", circuits, true, 16, graph, plan, n_plan_words, n_columns, n_dynamic, n_proofs, d_records,
+  return verify_terms_entry("hm_verify_terms_multi_dev", circuits, VT_MULTI, 16, graph, plan, n_plan_words, n_columns, n_dynamic, n_proofs, d_records,
                             d_scalars, d_instance, d_bad, d_own, d_shared, d_h2_r, d_h2_l, stream);
 } HM_API_CATCH("hm_verify_terms_multi_dev")
+
+int hm_verify_terms_gwc_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
+                            const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad, void* d_own, void* d_shared,
+                            void* d_w_left, void* stream) try {
+  return verify_terms_entry("hm_verify_terms_gwc_dev", 0, VT_GWC, 20, graph, plan, n_plan_words, n_columns, n_dynamic, n_proofs, d_records,
+                            d_scalars, d_instance, d_bad, d_own, d_shared, d_w_left, d_w_left, stream);
+} HM_API_CATCH("hm_verify_terms_gwc_dev")
 
 // ---- the per-proof sums (verify_sums.inc, verify.hip) -------------------------------------------------------------------------------
 int hm_verify_proof_sums_dev(const void* d_bases_xy, size_t n_proofs, uint32_t own_points, uint32_t shared_points, const void* d_own,

@@ -593,6 +593,11 @@ int verify_terms_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size
 int verify_terms_multi_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic,
                            size_t n_proofs, uint32_t circuits, const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst,
                            uint32_t* d_bad, uint32_t* d_own, uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream);
+// The same for proofs that end in the GWC multiopen, one lane per proof: `plan` is a GWC plan (verify_terms.inc, vg_plan_problem),
+// the records hold 8 elements, d_w_left (n_proofs x q x 4 words) receives r_b u^i.  Asynchronous on `stream`.
+int verify_terms_gwc_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic,
+                         size_t n_proofs, const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst, uint32_t* d_bad,
+                         uint32_t* d_own, uint32_t* d_shared, uint32_t* d_w_left, hipStream_t stream);
 // The pair (L_b, -R_b) of every proof's own opening check, one workgroup per proof (verify_sums.inc): 2 rows of affine Montgomery
 // words per proof, zeros for a proof whose flag is set.  Asynchronous on `stream`.
 int verify_sums_run(const uint32_t* d_bases, size_t n_proofs, uint32_t own_points, uint32_t shared_points, const uint32_t* d_own,

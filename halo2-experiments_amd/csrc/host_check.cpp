@@ -845,6 +845,22 @@ int hc_verify_terms(const uint32_t* plan, size_t n_words, size_t n_columns, cons
   for (uint32_t s = 0; s < plan[VT_N_VALS]; ++s) vt_to_ext(vals + 8 * (size_t)s, vt_load(m, s));
   return ok ? 1 : 0;
 }
+// The terms of ONE proof that ends in the GWC multiopen: the lane code of verify_terms_gwc_kernel on a workspace of one lane, as
+// hc_verify_terms.  rec: 8 elements (theta, beta, gamma, y, x, v, u, r_b); w_left: q x 8 words.  -> 1 / 0: the lane's ok flag (all
+// rows zero on 0, as the kernel leaves them); -1 with *why set when the plan fails vg_plan_problem.
+int hc_verify_terms_gwc(const uint32_t* plan, size_t n_words, size_t n_columns, const uint32_t* rec, const uint32_t* evals, const uint32_t* inst,
+                        const uint32_t* numerator, uint32_t* vals, uint32_t* own, uint32_t* shared, uint32_t* w_left, const char** why) {
+  *why = vg_plan_problem(plan, n_words, n_columns);
+  if (*why) return -1;
+  std::vector<uint32_t> ws((size_t)vt_ws_program(plan) * 9, 0);
+  const VtMem m{ws.data(), 1, 0};
+  vg_zero_lane(plan, own, shared, w_left);
+  const bool ok = vg_phase_a(plan, m, rec, evals, inst);
+  vg_phase_b(plan, m, vt_from_ext(numerator), own, shared, w_left);
+  for (uint32_t s = 0; s < plan[VT_N_VALS]; ++s) vt_to_ext(vals + 8 * (size_t)s, vt_load(m, s));
+  if (!ok) vg_zero_lane(plan, own, shared, w_left);
+  return ok ? 1 : 0;
+}
 // The terms of ONE multi-circuit proof (verify_terms.inc): the lane code of verify_terms_multi_kernel on a workspace of
 // 64 lanes, lane c = circuit c, with the two cross-lane folds as plain loops over the lanes.  plan: the multi plan; evals: the proof's
 // scalars in the proof's order; inst: circuits rows; numerators: N_c of every circuit (circuits x 4 Montgomery words), as

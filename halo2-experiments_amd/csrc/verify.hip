@@ -3,6 +3,8 @@
 //   verify_terms_run                      the per-proof terms of the opening checks, one lane per proof (verify_terms.inc)
 //   verify_terms_multi_run                the same for multi-circuit proofs: a wavefront per proof, a lane per circuit.  Two kernels
 //                                         and two launch shapes over one phase-b walk, behind one driver (verify_terms_launch)
+//   verify_terms_gwc_run                  the terms of proofs that end in the GWC multiopen: one lane per proof, the same phase a and
+//                                         numerator, the point groups' phase b (vg_phase_b), the same driver
 //   verify_sums_run                       the two G1 points of every proof's own check, one workgroup per proof (verify_sums.inc)
 //   blake2b_run, verify_transcript_run    Blake2b-512 and the proofs' transcripts on it, one lane per proof (transcript.inc)
 //   keccak256_run, verify_read_evm_run,   Keccak-256, and the read and the transcripts of proofs in the EVM encoding: uncompressed
@@ -243,8 +245,38 @@ __global__ __launch_bounds__(GE_THREADS) void verify_terms_multi_kernel(const ui
   }
 }
 
-// ---- the drivers of the two terms kernels -------------------------------------------------------
-using VerifyTermsKernel = decltype(&verify_terms_kernel);         // the two kernels take the same arguments
+// ---- the terms of GWC proofs: one lane per proof, the point groups in place of the rotation sets ---
+// The arguments are verify_terms_kernel's, so that one driver launches all three: `w_left` (n_proofs x q x 4 words, r_b u^i) stands
+// where that kernel takes h2r, and the last pointer is not looked at.
+__global__ __launch_bounds__(GE_THREADS) void verify_terms_gwc_kernel(const uint32_t* __restrict__ plan, const uint32_t* __restrict__ consts,
+                                                                      const GraphCalc* __restrict__ calcs, uint32_t n_calc, uint32_t result_src,
+                                                                      uint32_t result_prev, uint32_t n_static, uint32_t* __restrict__ ws,
+                                                                      uint32_t n_proofs, const uint32_t* __restrict__ records,
+                                                                      const uint32_t* __restrict__ evals, const uint32_t* __restrict__ inst,
+                                                                      uint32_t* __restrict__ bad, uint32_t* __restrict__ own,
+                                                                      uint32_t* __restrict__ shared, uint32_t* __restrict__ w_left,
+                                                                      uint32_t* __restrict__) {
+  const uint32_t T = gridDim.x * GE_THREADS, lane = blockIdx.x * GE_THREADS + threadIdx.x;
+  if (lane >= n_proofs) return;
+  const size_t b = lane;
+  uint32_t* my_own = own + b * plan[VT_N_OWN] * 8;
+  uint32_t* my_shared = shared + b * plan[VT_N_SHARED] * 8;
+  uint32_t* my_left = w_left + b * plan[VT_N_SETS] * 8;
+  vg_zero_lane(plan, my_own, my_shared, my_left);
+  if (bad[b]) return;
+  const VtMem m{ws, T, lane};
+  const bool ok = vg_phase_a(plan, m, records + b * VG_REC * 8, evals + b * plan[VT_N_SCALARS] * 8, inst + b * plan[VT_INST_ELEMS] * 8);
+  const VerifySource from{plan, m, n_static};
+  const Fr num = ge_reduce(ge_run(from, consts, calcs, n_calc, result_src, result_prev, ws + (size_t)vt_ws_program(plan) * 9 * T, T, lane));
+  vg_phase_b(plan, m, num, my_own, my_shared, my_left);
+  if (!ok) {
+    bad[b] = 1;
+    vg_zero_lane(plan, my_own, my_shared, my_left);
+  }
+}
+
+// ---- the drivers of the terms kernels -----------------------------------------------------------
+using VerifyTermsKernel = decltype(&verify_terms_kernel);         // the three kernels take the same arguments
 
 // What both drivers do behind their plan's check (`why`: its verdict, reported behind the program's own checks as before): `what`
 // opens every message, `lane_plan` sizes a lane's workspace, `lanes` is the launch's width.  The arguments were checked by the caller
@@ -291,6 +323,15 @@ int verify_terms_multi_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan
   const char* why = vtm_plan_problem(plan, n_words, n_columns, circuits);
   return verify_terms_launch("verify terms multi", why, ctx, g, plan, n_words, why ? plan : vtm_lane_plan(plan), n_columns, n_dynamic, n_proofs,
                              n_proofs * 64, verify_terms_multi_kernel, d_records, d_evals, d_inst, d_bad, d_own, d_shared, d_h2r, d_h2l, stream);
+}
+
+// GWC proofs, one lane per proof: d_w_left takes the place of d_h2r, and there is no d_h2l
+int verify_terms_gwc_run(DeviceCtx& ctx, GraphProgram& g, const uint32_t* plan, size_t n_words, size_t n_columns, size_t n_dynamic,
+                         size_t n_proofs, const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst, uint32_t* d_bad,
+                         uint32_t* d_own, uint32_t* d_shared, uint32_t* d_w_left, hipStream_t stream) {
+  return verify_terms_launch("verify terms gwc", vg_plan_problem(plan, n_words, n_columns), ctx, g, plan, n_words, plan, n_columns, n_dynamic,
+                             n_proofs, n_proofs, verify_terms_gwc_kernel, d_records, d_evals, d_inst, d_bad, d_own, d_shared, d_w_left, nullptr,
+                             stream);
 }
 
 // ---- the per-proof sums -----------------------------------------------------------------------

@@ -46,8 +46,9 @@ HM_HD uint32_t vt_ws_diff(const uint32_t* plan) { return plan[VT_N_VALS] + VT_RE
 HM_HD uint32_t vt_ws_basis(const uint32_t* plan) { return vt_ws_diff(plan) + plan[VT_N_SUPER]; }
 HM_HD uint32_t vt_ws_program(const uint32_t* plan) { return vt_ws_basis(plan) + VT_MAX_T; }
 
-// nullptr, or why the plan is refused: after this every index the kernel takes from the plan lies inside its array
-inline const char* vt_plan_problem(const uint32_t* p, size_t n_words, size_t n_columns) {
+// nullptr, or why the plan is refused, for everything in front of the sets: the header, the column map, the instance queries and the
+// constants -- the words a SHPLONK plan and a GWC plan (vg_plan_problem) share
+inline const char* vt_plan_head_problem(const uint32_t* p, size_t n_words, size_t n_columns) {
   if (n_words < VT_HDR) return "verify terms: the plan is shorter than its header";
   if (p[VT_K] == 0 || p[VT_K] > 28) return "verify terms: need 1 <= k <= 28";
   const uint32_t n_vals = p[VT_N_VALS], n_consts = p[VT_N_CONSTS], n_super = p[VT_N_SUPER];
@@ -78,6 +79,14 @@ inline const char* vt_plan_problem(const uint32_t* p, size_t n_words, size_t n_c
     if (e[0] > p[VT_INST_ELEMS] || e[1] > p[VT_INST_ELEMS] - e[0] || e[2] >= n_consts || !consts_ok(p[VT_C_ROWS], e[1]))
       return "verify terms: an instance query out of range";
   }
+  return nullptr;
+}
+
+// nullptr, or why the plan is refused: after this every index the kernel takes from the plan lies inside its array
+inline const char* vt_plan_problem(const uint32_t* p, size_t n_words, size_t n_columns) {
+  if (const char* why = vt_plan_head_problem(p, n_words, n_columns)) return why;
+  const uint64_t words = n_words;
+  const uint32_t n_vals = p[VT_N_VALS], n_consts = p[VT_N_CONSTS], n_super = p[VT_N_SUPER];
   uint64_t at = p[VT_OFF_SETS];
   for (uint32_t i = 0; i < p[VT_N_SETS]; ++i) {
     if (at + 3 > words) return "verify terms: the sets lie outside the plan";
@@ -462,3 +471,100 @@ HM_HD bool vt_phase_b(const uint32_t* plan, const VtMem& m, const Fr& num, uint3
   return mine.ok;
 }
 
+
+// ---- the GWC multiopen (gwc.py; DESIGN.md section 30): one lane per proof, its own phase b ------------------------------------------------
+// A GWC plan (proof_layout.GwcTermsPlan) is a SHPLONK plan up to VT_OFF_SETS: the same header, column map, instance queries and
+// constants, so phase a, the numerator's Source and the workspace are the ones above.  VT_N_SUPER = VT_N_SETS = q, the number of
+// distinct query points, at most VT_MAX_SUPER.  At VT_OFF_SETS stand the q POINT GROUPS in order of first appearance in the query list:
+//   per group    (c, w_row, members): the constant index of omega^rot -- the group's point is z_i = x omega^rot --, the own row of the
+//                witness W_i, the number of members
+//   per member   (target, slot): the target as in a rotation set (VT_T_SHARED | row of the shared array, VT_T_H | the first h piece's
+//                own row, or an own row), the value slot of the member's evaluation at the group's point (VT_S_HX for h)
+// The record has EIGHT elements, theta, beta, gamma, y, x, v, u, r_b (what the schedule-driven transcript kernels leave for seven
+// challenges, then the caller's weight): the first five stand where the SHPLONK record has them, so the Source's dyn() and phase a's
+// rest read the same slots.  The check is e(sum_i u^i W_i, [s]G2) = e(sum_i u^i z_i W_i + sum_i u^i sum_j v^j C_ij - (sum u^i v^j e_ij) G, G2):
+// a commitment opened at several points is a member of several groups, so a member's scalar is ADDED to its row (the rows start at
+// zero).  No Lagrange basis, and no inversion besides phase a's.
+enum : uint32_t { VG_V = 5, VG_U = 6, VG_RB = 7, VG_REC = 8 };
+
+// nullptr, or why the GWC plan is refused: after this every index the kernel takes from the plan lies inside its array
+inline const char* vg_plan_problem(const uint32_t* p, size_t n_words, size_t n_columns) {
+  if (const char* why = vt_plan_head_problem(p, n_words, n_columns)) return why;
+  const uint64_t words = n_words;
+  const uint32_t n_vals = p[VT_N_VALS], n_consts = p[VT_N_CONSTS], groups = p[VT_N_SETS];
+  if (groups > VT_MAX_SUPER || groups != p[VT_N_SUPER]) return "verify terms gwc: need 1 .. 32 point groups, one per rotation";
+  if (groups > p[VT_N_OWN]) return "verify terms gwc: more witness points than own points";
+  uint64_t at = p[VT_OFF_SETS];
+  for (uint32_t i = 0; i < groups; ++i) {
+    if (at + 3 > words) return "verify terms gwc: the groups lie outside the plan";
+    const uint32_t members = p[at + 2];
+    if (p[at] >= n_consts) return "verify terms gwc: a group's constant out of range";
+    if (p[at + 1] >= p[VT_N_OWN]) return "verify terms gwc: a witness row out of range";
+    at += 3;
+    if (2ull * members > words - at) return "verify terms gwc: the groups lie outside the plan";
+    for (uint32_t j = 0; j < members; ++j, at += 2) {
+      const uint32_t target = p[at], index = target & VT_T_INDEX;
+      if (target & VT_T_H ? ((target & VT_T_SHARED) || index > p[VT_N_OWN] || p[VT_PIECES] > p[VT_N_OWN] - index)
+                          : (index >= (target & VT_T_SHARED ? p[VT_N_SHARED] : p[VT_N_OWN])))
+        return "verify terms gwc: a member's target out of range";
+      if (p[at + 1] >= n_vals) return "verify terms gwc: a member's evaluation slot out of range";
+    }
+  }
+  return nullptr;
+}
+
+// phase a of a GWC proof: its eight record elements, then the loads and the rest as above
+HM_HD bool vg_phase_a(const uint32_t* plan, const VtMem& m, const uint32_t* rec, const uint32_t* evals, const uint32_t* inst) {
+  const uint32_t wc = plan[VT_N_VALS];
+  for (uint32_t j = 0; j < VG_REC; ++j) vt_store(m, wc + j, fe_canonical(vt_from_ext(rec + 8 * (size_t)j)));
+  for (uint32_t j = 0; j < plan[VT_N_SCALARS]; ++j) vt_store(m, j, vt_from_ext(evals + 8 * (size_t)j));
+  return vt_phase_a_rest(plan, m, inst);
+}
+
+// every row a GWC lane may write, zeroed: before the work (the members' scalars are added) and again when the proof fails
+HM_HD void vg_zero_lane(const uint32_t* plan, uint32_t* own, uint32_t* shared, uint32_t* w_left) {
+  vt_zero_rows(own, plan[VT_N_OWN]);
+  vt_zero_rows(shared, plan[VT_N_SHARED]);
+  vt_zero_rows(w_left, plan[VT_N_SETS]);
+}
+
+// row += a, on Montgomery words (a below 3r)
+HM_HD void vg_add_row(uint32_t* row, const Fr& a) { vt_to_ext(row, vt_add(vt_from_ext(row), a)); }
+
+// num: the numerator, below 3r.  Writes r_b x the scalars of the proof's own points (W_i with u^i z_i), its row of the shared points
+// (the generator last) and r_b u^i to w_left.
+HM_HD void vg_phase_b(const uint32_t* plan, const VtMem& m, const Fr& num, uint32_t* own, uint32_t* shared, uint32_t* w_left) {
+  const uint32_t* cst = plan + plan[VT_OFF_CONSTS];
+  const uint32_t wc = plan[VT_N_VALS];
+  vt_store(m, plan[VT_S_HX], fe_mul(num, vt_load(m, wc + VT_XN1_INV)));
+  const Fr x = vt_load(m, wc + VT_X), v = vt_load(m, wc + VG_V), u = vt_load(m, wc + VG_U), xn = vt_load(m, wc + VT_XN);
+  Fr u_i = vt_load(m, wc + VG_RB);                               // r_b u^i
+  Fr e_sum = fe_zero<FrParams>();
+  HM_DECLARE(e_sum, 3.0);
+  size_t at = plan[VT_OFF_SETS];
+  for (uint32_t i = 0; i < plan[VT_N_SETS]; ++i) {
+    const uint32_t c = plan[at], w_row = plan[at + 1], members = plan[at + 2];
+    at += 3;
+    Fr coeff = u_i;                                              // r_b u^i v^j
+    for (uint32_t j = 0; j < members; ++j, at += 2) {
+      const uint32_t target = plan[at], index = target & VT_T_INDEX;
+      e_sum = vt_add(e_sum, fe_mul(coeff, vt_load(m, plan[at + 1])));
+      if (target & VT_T_H) {                                     // [h] = sum_p x^(n p) [h_p]
+        Fr weighted = coeff;
+        for (uint32_t p = 0; p < plan[VT_PIECES]; ++p) {
+          vg_add_row(own + 8 * (size_t)(index + p), weighted);
+          weighted = fe_mul(weighted, xn);
+        }
+      } else if (target & VT_T_SHARED) {
+        vg_add_row(shared + 8 * (size_t)index, coeff);
+      } else {
+        vg_add_row(own + 8 * (size_t)index, coeff);
+      }
+      coeff = fe_mul(coeff, v);
+    }
+    vt_to_ext(own + 8 * (size_t)w_row, fe_mul(u_i, fe_mul(x, vt_const(cst, c))));   // r_b u^i z_i
+    vt_to_ext(w_left + 8 * (size_t)i, u_i);
+    u_i = fe_mul(u_i, u);
+  }
+  vt_to_ext(shared + 8 * (size_t)(plan[VT_N_SHARED] - 1), vt_neg(e_sum));              // the generator
+}

@@ -9,7 +9,10 @@ Nothing here needs a device.
     of the per-proof sums.  With a layout of m circuits they take a list of m instances;
   - ``TermsPlan`` and ``MultiTermsPlan``: the words ``hm_verify_terms_dev`` / ``hm_verify_terms_multi_dev`` are driven by
     (csrc/verify_terms.inc states their layout), and the numerator's program lowered from the constraint system alone;
-  - ``shared_points``, ``derive_randomizer`` and the constants the kernels' tables and plans share with the C side.
+  - ``shared_points``, ``derive_randomizer`` and the constants the kernels' tables and plans share with the C side;
+  - with ``multiopen="gwc"`` the layout of a proof that ends in the GWC multiopen (``gwc``), its twins -- ``terms_from_challenges``
+    and ``proof_terms_ints`` then also return the scalars u^i of the witness points in L -- and ``GwcTermsPlan``, the words
+    ``hm_verify_terms_gwc_dev`` is driven by.
 
 Two places where the symbolic form answers differently from ``verify_proof``, each of probability about 2^-254 for an honest or a
 dishonest prover alike (x is a hash output): x = 0, where all rotations of x coincide, is reported as a failing proof; and h pieces whose
@@ -26,8 +29,8 @@ from .bn256 import FR_MODULUS
 from .keygen import FR_DELTA, VerifyingKey
 from .pairing import G1_GEN, g1_msm, g1_mul
 from .shplonk import g1_words_to_int
-from .transcript import (PERSONAL, PREFIX_CHALLENGE, PREFIX_POINT, PREFIX_SCALAR, TranscriptError, check_encoding, g1_decompress_int,
-                         g1_uncompressed_int, keccak256)
+from .transcript import (PERSONAL, PREFIX_CHALLENGE, PREFIX_POINT, PREFIX_SCALAR, TranscriptError, check_encoding, check_multiopen,
+                         g1_decompress_int, g1_uncompressed_int, keccak256)
 from .verifier import _instance_columns, _vk_digest, evaluate_expression, proof_length
 
 R = FR_MODULUS
@@ -66,15 +69,25 @@ class ProofLayout:
     permutation and the lookup evaluations per circuit.  A per-circuit key is (kind, index, circuit); shared keys stay as they are.
     The rotation sets are the single-circuit ones in the same order (circuit 0's queries come first), the members of a set circuit
     0's keys, circuit 1's, ..., then the shared ones.  ``lane`` is the single-circuit layout of the same system (the layout itself
-    when m = 1).  ``encoding="evm"`` with m > 1 raises ValueError."""
+    when m = 1).  ``encoding="evm"`` with m > 1 raises ValueError.
 
-    def __init__(self, cs, k: int, encoding: str = "halo2", circuits: int = 1):
+    ``multiopen="gwc"`` (``gwc``; single-circuit only, ``circuits`` > 1 raises ValueError): behind the evaluations the proof holds one
+    witness point per distinct query point, so ``point_keys`` ends in ("w", 0) .. ("w", q - 1).  ALL points are own points: there is no
+    tail point and no slot has a tail bit.  ``groups`` = [(rotation, [member keys])] stands in place of ``sets``: the distinct
+    rotations in order of first appearance in ``queries``, every group's members in list order -- what
+    ``gwc.construct_point_groups`` finds on the real points, by the argument above.  The transcript has seven challenges
+    (``GWC_RECORD``): the schedule ends ... | evaluations | v | q points | u."""
+
+    def __init__(self, cs, k: int, encoding: str = "halo2", circuits: int = 1, multiopen: str = "shplonk"):
         self.encoding = check_encoding(encoding, "ProofLayout")
+        self.multiopen = check_multiopen(multiopen, "ProofLayout")
         m = int(circuits)
         if not 1 <= m <= MAX_CIRCUITS:
             raise ValueError(f"ProofLayout: need 1 <= circuits <= {MAX_CIRCUITS}, got {circuits!r}")
         if m > 1 and encoding == "evm":
             raise ValueError("ProofLayout: a multi-circuit proof has no \"evm\" encoding (create_proof_multi writes none)")
+        if m > 1 and multiopen == "gwc":
+            raise ValueError("ProofLayout: multi-circuit proofs with the \"gwc\" multiopen are not laid out (circuits > 1)")
         self.circuits = m
         self.lane = self if m == 1 else ProofLayout(cs, k, encoding)       # what ONE circuit of the proof looks like
         self.cs, self.k, self.n = cs, k, 1 << k
@@ -102,25 +115,6 @@ class ProofLayout:
         for c in M:
             for j in range(L):
                 evs += [(per((kd, j), c), r % n) for kd, r in (("lookup_z", 0), ("lookup_z", 1), ("lookup_a", 0), ("lookup_a", -1), ("lookup_s", 0))]
-        self.point_keys = pts + [("h1",), ("h2",)]
-        self.eval_keys = evs
-        self.eval_index = {}
-        for at, key in enumerate(evs):
-            self.eval_index.setdefault(key, at)
-        self.n_points, self.own_points, self.n_scalars = len(self.point_keys), len(self.point_keys) - 1, len(evs)
-        self.slots = (2 if encoding == "evm" else 1) * self.n_points + self.n_scalars
-        if 32 * self.slots != proof_length(cs, m, encoding):
-            raise AssertionError("ProofLayout: the slots do not add up to proof_length")
-        if encoding == "evm":
-            table = [e for i in range(self.points_before_evals) for e in (EVM_POINT | i, EVM_SKIP)] + list(range(self.n_scalars))
-            table += [EVM_POINT | (self.n_points - 2), EVM_SKIP, EVM_POINT | EVM_TAIL | (self.n_points - 1), EVM_SKIP]
-        else:
-            table = [VR_POINT | i for i in range(self.points_before_evals)] + list(range(self.n_scalars))
-            table += [VR_POINT | (self.n_points - 2), VR_POINT | VR_TAIL | (self.n_points - 1)]
-        self.slot_table = np.array(table, dtype=np.uint32)
-        self.point_slots = [s for s, e in enumerate(table) if e & VR_POINT]
-        self.scalar_slots = [s for s, e in enumerate(table) if not e & (VR_POINT | (EVM_SKIP if encoding == "evm" else 0))]
-
         # the queries in the order verifier._verify lists them; ("h",) stands for sum_i x^(n i) [h_i]
         q = []
         for c in M:
@@ -133,6 +127,45 @@ class ProofLayout:
         q += [(("fixed", i), r % n) for i, r in fix_q] + [(("sigma", j), 0) for j in range(P_)]
         q += [(("h",), 0), (("random",), 0)]
         self.queries = q
+        gwc = multiopen == "gwc"
+        if gwc:
+            if len(set(q)) != len(q):
+                raise AssertionError("ProofLayout: the query list names a (key, rotation) pair twice")
+            groups: List[Tuple[int, list]] = []
+            for key, rot in q:
+                for have, keys in groups:
+                    if have == rot:
+                        keys.append(key)
+                        break
+                else:
+                    groups.append((rot, [key]))
+            self.groups = groups
+        self.point_keys = pts + ([("w", i) for i in range(len(self.groups))] if gwc else [("h1",), ("h2",)])
+        self.eval_keys = evs
+        self.eval_index = {}
+        for at, key in enumerate(evs):
+            self.eval_index.setdefault(key, at)
+        self.n_points, self.own_points, self.n_scalars = len(self.point_keys), len(self.point_keys) - (0 if gwc else 1), len(evs)
+        self.slots = (2 if encoding == "evm" else 1) * self.n_points + self.n_scalars
+        if 32 * self.slots != proof_length(cs, m, encoding, multiopen, k):
+            raise AssertionError("ProofLayout: the slots do not add up to proof_length")
+        behind = range(self.points_before_evals, self.n_points)          # the multiopen's points, behind the evaluations
+        if encoding == "evm":
+            table = [e for i in range(self.points_before_evals) for e in (EVM_POINT | i, EVM_SKIP)] + list(range(self.n_scalars))
+            if gwc:
+                table += [e for i in behind for e in (EVM_POINT | i, EVM_SKIP)]
+            else:
+                table += [EVM_POINT | (self.n_points - 2), EVM_SKIP, EVM_POINT | EVM_TAIL | (self.n_points - 1), EVM_SKIP]
+        else:
+            table = [VR_POINT | i for i in range(self.points_before_evals)] + list(range(self.n_scalars))
+            if gwc:
+                table += [VR_POINT | i for i in behind]
+            else:
+                table += [VR_POINT | (self.n_points - 2), VR_POINT | VR_TAIL | (self.n_points - 1)]
+        self.slot_table = np.array(table, dtype=np.uint32)
+        self.point_slots = [s for s, e in enumerate(table) if e & VR_POINT]
+        self.scalar_slots = [s for s, e in enumerate(table) if not e & (VR_POINT | (EVM_SKIP if encoding == "evm" else 0))]
+
         by_key: dict = {}
         for key, rot in q:
             by_key.setdefault(key, [])
@@ -147,7 +180,8 @@ class ProofLayout:
                     break
             else:
                 sets.append((rots_t, [key]))
-        self.sets = [(list(rots), keys) for rots, keys in sets]
+        if not gwc:
+            self.sets = [(list(rots), keys) for rots, keys in sets]
         self.super_rotations = sorted({rot for _, rot in q})
         self.shared_keys = [("fixed", c) for c in range(cs.num_fixed)] + [("sigma", j) for j in range(P_)] + [("g",)]
         self.shared_index = {key: i for i, key in enumerate(self.shared_keys)}
@@ -178,13 +212,19 @@ class ProofLayout:
         """The (absorb a slots, squeeze s challenges) pairs of a proof's transcript over its slots in order, from the
         counts ``transcript_challenges`` uses: advice | theta | 2L | beta, gamma | sets + L + 1 | y | pieces | x | evaluations | y', v
         | [h] | u, and a last pair that absorbs [h'] behind the last challenge, as ``Blake2bRead`` does.  The counts are SLOTS: in an
-        "evm" layout a point counts twice, and with ``circuits = m`` the per-circuit counts (advice, 2L, sets + L) are taken m times."""
+        "evm" layout a point counts twice, and with ``circuits = m`` the per-circuit counts (advice, 2L, sets + L) are taken m times.
+        A "gwc" layout ends ... | evaluations | v | the q witness points | u: seven challenges, nothing absorbed behind the last."""
         w, m = 2 if self.encoding == "evm" else 1, self.circuits
-        pairs = [(w * m * self.cs.num_advice, 1), (w * m * 2 * self.L, 2), (w * (m * (self.nsets + self.L) + 1), 1), (w * self.pieces, 1),
-                 (self.n_scalars, 2), (w, 1), (w, 0)]
-        if sum(a for a, _ in pairs) != self.slots or sum(s for _, s in pairs) != len(RECORD):
-            raise AssertionError("ProofLayout: the transcript's schedule does not cover the proof's slots and the eight challenges")
+        pairs = [(w * m * self.cs.num_advice, 1), (w * m * 2 * self.L, 2), (w * (m * (self.nsets + self.L) + 1), 1), (w * self.pieces, 1)]
+        pairs += [(self.n_scalars, 1), (w * len(self.groups), 1)] if self.multiopen == "gwc" else [(self.n_scalars, 2), (w, 1), (w, 0)]
+        if sum(a for a, _ in pairs) != self.slots or sum(s for _, s in pairs) != len(self.record):
+            raise AssertionError("ProofLayout: the transcript's schedule does not cover the proof's slots and its challenges")
         return pairs
+
+    @property
+    def record(self) -> tuple:
+        """the names of the transcript's challenges in order: ``RECORD``, or ``GWC_RECORD`` for a "gwc" layout"""
+        return GWC_RECORD if self.multiopen == "gwc" else RECORD
 
 
 def read_proof_ints(layout: ProofLayout, proof: bytes):
@@ -258,7 +298,7 @@ def _keccak_challenges(layout: ProofLayout, vk_digest: int, inst_cols, proof: by
             h = keccak256(bytes(buf) + (b"\x01" if len(buf) == 32 else b""))
             buf = bytearray(h)
             out.append(int.from_bytes(h, "big") % R)
-    return dict(zip(RECORD, out))
+    return dict(zip(layout.record, out))
 
 
 def transcript_challenges(layout: ProofLayout, vk_digest: int, inst_cols, proof: bytes, y_bytes: Optional[Sequence[bytes]] = None) -> dict:
@@ -306,6 +346,11 @@ def transcript_challenges(layout: ProofLayout, vk_digest: int, inst_cols, proof:
         at = 32 * slot[0]
         st.update(PREFIX_SCALAR + proof[at:at + 32])
         slot[0] += 1
+    if layout.multiopen == "gwc":
+        ch["v"] = squeeze()
+        points(len(layout.groups))
+        ch["u"] = squeeze()
+        return ch
     ch["y2"] = squeeze()
     ch["v"] = squeeze()
     points(1)
@@ -375,6 +420,9 @@ def terms_from_challenges(layout: ProofLayout, omega: int, inst_cols, evals: Seq
         if m > 1:
             details["numerators"] = numerators
 
+    if layout.multiopen == "gwc":
+        return _gwc_terms(layout, wpow, ev_at, hx, xn, ch)
+
     # ---- the multiopen's scalars, per rotation set ---------------------------------------------------------------------------------
     y2, v, u = ch["y2"], ch["v"], ch["u"]
     pt = {rot: x * wpow(rot) % R for rot in layout.super_rotations}
@@ -426,10 +474,40 @@ def terms_from_challenges(layout: ProofLayout, omega: int, inst_cols, evals: Seq
     return own, shared
 
 
+def _gwc_terms(layout: ProofLayout, wpow, ev_at, hx: int, xn: int, ch: dict):
+    """the GWC half of ``terms_from_challenges``: per group i and member j the scalar u^i v^j ADDED to the member's row (a commitment
+    opened at several points is a member of several groups), the generator's -sum u^i v^j e_ij, and u^i z_i on W_i's own row.
+    -> (own, shared, left): ``left[i]`` = u^i, the scalar of W_i in L."""
+    x, v, u = ch["x"], ch["v"], ch["u"]
+    own, shared, left = [0] * layout.n_points, [0] * len(layout.shared_keys), []
+    e_sum, u_i = 0, 1
+    for i, (rot, keys) in enumerate(layout.groups):
+        coeff = u_i
+        for key in keys:
+            e_sum = (e_sum + coeff * (hx if key == ("h",) else ev_at(key, rot))) % R
+            if key == ("h",):
+                xp = 1
+                for piece in range(layout.pieces):
+                    at = layout.own_index[("h_piece", piece)]
+                    own[at] = (own[at] + coeff * xp) % R
+                    xp = xp * xn % R
+            elif key in layout.shared_index:
+                shared[layout.shared_index[key]] = (shared[layout.shared_index[key]] + coeff) % R
+            else:
+                own[layout.own_index[key]] = (own[layout.own_index[key]] + coeff) % R
+            coeff = coeff * v % R
+        own[layout.own_index[("w", i)]] = u_i * x % R * wpow(rot) % R
+        left.append(u_i)
+        u_i = u_i * u % R
+    shared[layout.shared_index[("g",)]] = -e_sum % R
+    return own, shared, left
+
+
 # ---- the plan of the terms kernel (csrc/verify_terms.inc) ---------------------------------------------------------------------------------
 VT_NO_SLOT, VT_T_SHARED, VT_T_H = 0xFFFFFFFF, 1 << 31, 1 << 30
 VT_MAX_VALS, VT_MAX_INST_ROWS, VT_MAX_SUPER, VT_MAX_T = 256, 64, 32, 8
 RECORD = ("theta", "beta", "gamma", "y", "x", "y2", "v", "u")          # then r_b: the per-proof record of hm_verify_terms_dev
+GWC_RECORD = ("theta", "beta", "gamma", "y", "x", "v", "u")            # then r_b: the record of hm_verify_terms_gwc_dev
 
 
 def _internal_words(v: int) -> List[int]:
@@ -473,8 +551,7 @@ class TermsPlan:
         n_vals = s_hx + 1
         if n_vals > VT_MAX_VALS:
             raise ValueError(f"TermsPlan: more than {VT_MAX_VALS} value slots")
-        if len(layout.super_rotations) > VT_MAX_SUPER or any(len(rots) > VT_MAX_T for rots, _ in layout.sets):
-            raise ValueError("TermsPlan: more rotations than the kernel's workspace holds")
+        point_rotations = self._point_rotations(layout)           # the rotations whose omega^rot stand at c_super, in the walk's order
 
         def slot_of(col: int, rot: int) -> int:
             if col >= inst_first:
@@ -512,12 +589,37 @@ class TermsPlan:
         for i in range(max(inst_rows, default=0)):
             const(w(i))
         c_super = len(consts)
-        for rot in layout.super_rotations:
+        for rot in point_rotations:
             const(w(rot))
         inst_off = [sum(inst_rows[:c]) for c in range(cs.num_instance)]
         inst_words: List[int] = []
         for col, rot in inst_queries:
             inst_words += [inst_off[col], inst_rows[col], const(w(rot))]
+        set_words, n_sets = self._opening_words(layout, const, w, c_super, s_hx)
+        header = 24
+        off_colmap = header
+        off_inst = off_colmap + len(colmap)
+        off_sets = off_inst + len(inst_words)
+        off_consts = off_sets + len(set_words)
+        head = [layout.k, layout.n_scalars, n_vals, len(lagrange_rows), len(inst_queries), len(point_rotations), n_sets,
+                layout.pieces, layout.own_points, len(layout.shared_keys), n_rot, n_cols, off_colmap, off_inst, off_sets, sum(inst_rows),
+                c_lagrange, c_rows, c_super, s_l0, s_inst, s_hx, len(consts), off_consts]
+        assert len(head) == header
+        body = head + colmap + inst_words + set_words + [limb for v in consts for limb in _internal_words(v)]
+        self.words = np.array(body, dtype=np.uint32)
+        self.inst_rows, self.inst_queries, self.n_vals, self.n_columns = inst_rows, inst_queries, n_vals, n_cols
+        self.s_l0, self.s_inst, self.s_hx = s_l0, s_inst, s_hx
+        self.inst_elems = max(sum(inst_rows), 1)                  # the instance array is never empty: one zero element at least
+
+    def _point_rotations(self, layout: ProofLayout) -> List[int]:
+        if layout.multiopen != "shplonk":
+            raise ValueError("TermsPlan: the layout's multiopen is not \"shplonk\" (GwcTermsPlan walks a \"gwc\" layout)")
+        if len(layout.super_rotations) > VT_MAX_SUPER or any(len(rots) > VT_MAX_T for rots, _ in layout.sets):
+            raise ValueError("TermsPlan: more rotations than the kernel's workspace holds")
+        return layout.super_rotations
+
+    def _opening_words(self, layout: ProofLayout, const, w, c_super: int, s_hx: int):
+        """the words of the multiopen's walk and the number of its sets: here the rotation sets of SHPLONK"""
         set_words: List[int] = []
         for rots, keys in layout.sets:
             sup = [layout.super_rotations.index(r) for r in rots]
@@ -538,20 +640,7 @@ class TermsPlan:
                     set_words += [VT_T_SHARED | layout.shared_index[key]] + [layout.eval_index[(key, r)] for r in rots]
                 else:
                     set_words += [layout.own_index[key]] + [layout.eval_index[(key, r)] for r in rots]
-        header = 24
-        off_colmap = header
-        off_inst = off_colmap + len(colmap)
-        off_sets = off_inst + len(inst_words)
-        off_consts = off_sets + len(set_words)
-        head = [layout.k, layout.n_scalars, n_vals, len(lagrange_rows), len(inst_queries), len(layout.super_rotations), len(layout.sets),
-                layout.pieces, layout.own_points, len(layout.shared_keys), n_rot, n_cols, off_colmap, off_inst, off_sets, sum(inst_rows),
-                c_lagrange, c_rows, c_super, s_l0, s_inst, s_hx, len(consts), off_consts]
-        assert len(head) == header
-        body = head + colmap + inst_words + set_words + [limb for v in consts for limb in _internal_words(v)]
-        self.words = np.array(body, dtype=np.uint32)
-        self.inst_rows, self.inst_queries, self.n_vals, self.n_columns = inst_rows, inst_queries, n_vals, n_cols
-        self.s_l0, self.s_inst, self.s_hx = s_l0, s_inst, s_hx
-        self.inst_elems = max(sum(inst_rows), 1)                  # the instance array is never empty: one zero element at least
+        return set_words, len(layout.sets)
 
     def instance_row(self, inst_cols) -> List[int]:
         """one proof's instance values as the kernel reads them: column after column, every column padded to the plan's rows"""
@@ -561,6 +650,36 @@ class TermsPlan:
                 raise ValueError("TermsPlan: an instance column longer than the plan's")
             row += list(values) + [0] * (rows - len(values))
         return row or [0]
+
+
+class GwcTermsPlan(TermsPlan):
+    """What ``hm_verify_terms_gwc_dev`` needs beside the proofs of a "gwc" layout, a sibling of ``TermsPlan``: the header, the column
+    map, the instance queries and the constants are the same words (VT_N_SUPER = VT_N_SETS = q, the constants at VT_C_SUPER the
+    omega^rot of the groups in their order); at VT_OFF_SETS stand the point groups in place of the rotation sets -- per group
+    (constant index of omega^rot, the own row of W_i, members), then per member (target, evaluation slot), the targets as in
+    ``TermsPlan`` (csrc/verify_terms.inc, at vg_plan_problem, states the layout).  ``lowered`` is the same program."""
+
+    def _point_rotations(self, layout: ProofLayout) -> List[int]:
+        if layout.multiopen != "gwc":
+            raise ValueError("GwcTermsPlan: the layout's multiopen is not \"gwc\"")
+        if len(layout.groups) > VT_MAX_SUPER:
+            raise ValueError(f"GwcTermsPlan: more than {VT_MAX_SUPER} point groups")
+        return [rot for rot, _ in layout.groups]
+
+    def _opening_words(self, layout: ProofLayout, const, w, c_super: int, s_hx: int):
+        words: List[int] = []
+        for i, (rot, keys) in enumerate(layout.groups):
+            words += [c_super + i, layout.own_index[("w", i)], len(keys)]
+            for key in keys:
+                if key == ("h",):
+                    if rot != 0:
+                        raise AssertionError("GwcTermsPlan: h is opened at x alone")
+                    words += [VT_T_H | layout.own_index[("h_piece", 0)], s_hx]
+                elif key in layout.shared_index:
+                    words += [VT_T_SHARED | layout.shared_index[key], layout.eval_index[(key, rot)]]
+                else:
+                    words += [layout.own_index[key], layout.eval_index[(key, rot)]]
+        return words, len(layout.groups)
 
 
 VM_HDR = 12                                                       # csrc/verify_terms.inc: the words of a multi plan's header
@@ -648,8 +767,8 @@ def proof_terms_ints(vk: VerifyingKey, instance, proof: bytes, layout: Optional[
     inst_cols = _layout_instances(layout, instance)
     points, evals = read_proof_ints(layout, proof)
     ch = transcript_challenges(layout, _vk_digest(vk), inst_cols, proof, [p[1].to_bytes(32, "little") for p in points])   # y_bytes: "halo2" only
-    own, shared = terms_from_challenges(layout, vk.domain.omega, inst_cols, evals, ch)
-    return ch, own, shared, points
+    own, shared, *left = terms_from_challenges(layout, vk.domain.omega, inst_cols, evals, ch)
+    return (ch, own, shared, points, *left)
 
 
 def proof_sums_ints(vk: VerifyingKey, instance, proof: bytes, layout: Optional[ProofLayout] = None, weight: int = 1):
@@ -657,10 +776,13 @@ def proof_sums_ints(vk: VerifyingKey, instance, proof: bytes, layout: Optional[P
     R = weight * (sum own[j] * points[j] + sum shared[i] * (shared point i)), from ``proof_terms_ints`` and ``g1_msm``; the proof
     verifies exactly when s * L == R, whatever the weight in [1, r).  Needs no device.  ``MalformedProof`` as ``proof_terms_ints``."""
     layout = layout or ProofLayout(vk.cs, vk.domain.k)
-    _, own, shared, points = proof_terms_ints(vk, instance, proof, layout)
+    _, own, shared, points, *left = proof_terms_ints(vk, instance, proof, layout)
     w = weight % R
     scalars = [w * v % R for v in list(own) + list(shared)]
-    return g1_mul(w, points[-1]), g1_msm(scalars, list(points) + shared_points(vk, layout))
+    right = g1_msm(scalars, list(points) + shared_points(vk, layout))
+    if left:                                                      # a "gwc" layout: L = sum_i u^i W_i over the proof's last q points
+        return g1_msm([w * v % R for v in left[0]], list(points[len(points) - len(left[0]):])), right
+    return g1_mul(w, points[-1]), right
 
 
 def shared_points(vk: VerifyingKey, layout: ProofLayout):

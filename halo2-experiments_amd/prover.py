@@ -37,7 +37,10 @@ circuits of a proof and no two seeds (mod 2^48) share a stream.
 byte ``create_proof(params, pk, advice[b], instances[b], seeds[b])``, with its own transcript, challenges, random polynomial and h.  Its
 body, ``_create_proofs``, follows the protocol order stated above step by step with m = 1 per transcript; what it adds is that every
 device step carries all proofs (``_Programs.run_proofs`` and h through ``CompiledGraph.evaluate_proofs``, the per-proof constants in a
-device table; ``linear_combination_batch``; ``create_openings``)."""
+device table; ``linear_combination_batch``; ``create_openings``).
+
+``multiopen="gwc"`` on the three entries ends the proof in the GWC multiopen instead (step 14: ``gwc.create_opening`` /
+``gwc.create_openings``, one witness point per distinct query point); everything before step 14 is the same code and the same bytes."""
 from __future__ import annotations
 
 import hashlib
@@ -53,8 +56,9 @@ from .arithmetic import (batch_invert, best_multiexp_batch, eval_polynomial, gra
 from .domain import FR_MODULUS, FR_ZETA, fr_words
 from .keygen import FR_DELTA, ProvingKey, VerifyingKey
 from .poseidon import ints_to_words, words_to_ints
+from . import gwc
 from .shplonk import create_opening, create_openings, g1_words_to_int
-from .transcript import WRITERS, check_encoding
+from .transcript import WRITERS, check_encoding, check_multiopen
 
 R = FR_MODULUS
 
@@ -153,13 +157,17 @@ MAX_CIRCUITS = 64                   # the circuit's number sits in the 6 seed bi
 H_COLUMN_BUDGET = 2 << 30           # bytes of per-circuit extended columns in flight in the h step (the witness writers' 2 GiB)
 
 
-def create_proof(params, pk: ProvingKey, advice, instance, seed: int, _trace: dict = None, encoding: str = "halo2") -> bytes:
+def create_proof(params, pk: ProvingKey, advice, instance, seed: int, _trace: dict = None, encoding: str = "halo2",
+                 multiopen: str = "shplonk") -> bytes:
     """The proof bytes for the witness ``advice`` -- the (num_advice, n, 4) device tensor a witness writer returns for one circuit --
     and its ``instance`` values.  One circuit per proof: a list of several witnesses, or a 4-dimensional tensor holding more than
     one, raises ValueError (``create_proof_multi`` takes several).  ``_trace``: a dict that receives the committed polynomials and
     their commitments (tests).  ``encoding``: "halo2" -- Blake2b transcript, compressed points, little-endian scalars -- or "evm" --
-    Keccak transcript, uncompressed big-endian points and scalars (``transcript`` states both); the protocol is the same."""
+    Keccak transcript, uncompressed big-endian points and scalars (``transcript`` states both); the protocol is the same.
+    ``multiopen``: "shplonk", or "gwc" -- the proof then ends in one witness point per distinct query point (``gwc``) where SHPLONK
+    writes two points; everything before the multiopen is byte for byte the same."""
     check_encoding(encoding, "create_proof")
+    check_multiopen(multiopen, "create_proof")
     if isinstance(advice, (list, tuple)):
         if len(advice) != 1:
             raise ValueError("create_proof: one circuit per proof (create_proof_multi proves several)")
@@ -169,7 +177,7 @@ def create_proof(params, pk: ProvingKey, advice, instance, seed: int, _trace: di
             raise ValueError("create_proof: one circuit per proof (create_proof_multi proves several)")
         advice = advice[0]
     trace = None if _trace is None else {}
-    proof = _create_proof("create_proof", params, pk, [advice], [instance], seed, trace, encoding)
+    proof = _create_proof("create_proof", params, pk, [advice], [instance], seed, trace, encoding, multiopen)
     if _trace is not None:                                 # one circuit: its keys without the circuit's number
         strip = lambda key: key[:2] if len(key) == 3 else key
         lag = trace["lagrange"]
@@ -179,12 +187,14 @@ def create_proof(params, pk: ProvingKey, advice, instance, seed: int, _trace: di
     return proof
 
 
-def create_proof_multi(params, pk: ProvingKey, advice, instances, seed: int, _trace: dict = None) -> bytes:
+def create_proof_multi(params, pk: ProvingKey, advice, instances, seed: int, _trace: dict = None, multiopen: str = "shplonk") -> bytes:
     """ONE proof for m circuits of ``pk``'s constraint system (upstream ``create_proof(params, pk, &[circuit; m], &[instances; m])``):
     ``advice`` is the (m, num_advice, n, 4) GPU tensor a witness writer returns, or a list of m (num_advice, n, 4) tensors;
     ``instances`` holds m entries, each in the form ``create_proof`` takes.  1 <= m <= 64.  All circuits share theta, beta, gamma, y
     and x; with m = 1 the bytes are ``create_proof``'s.  ``_trace``: as in ``create_proof``, the keys of what belongs to one circuit
-    carrying its number as a third element (("advice", column, circuit) ...) and ``lagrange`` holding one entry per circuit."""
+    carrying its number as a third element (("advice", column, circuit) ...) and ``lagrange`` holding one entry per circuit.
+    ``multiopen``: as in ``create_proof``."""
+    check_multiopen(multiopen, "create_proof_multi")
     if _is_tensor(advice):
         if advice.dim() != 4:
             raise ValueError("create_proof_multi: advice must be a (m, num_advice, n, 4) GPU tensor or a list of m (num_advice, n, 4) tensors")
@@ -196,10 +206,10 @@ def create_proof_multi(params, pk: ProvingKey, advice, instances, seed: int, _tr
         raise ValueError(f"create_proof_multi: between 1 and {MAX_CIRCUITS} circuits per proof")
     if _is_tensor(instances) or isinstance(instances, np.ndarray) or len(instances) != len(advice):
         raise ValueError(f"create_proof_multi: {len(advice)} circuit(s) need {len(advice)} instance entries")
-    return _create_proof("create_proof_multi", params, pk, advice, list(instances), seed, _trace)
+    return _create_proof("create_proof_multi", params, pk, advice, list(instances), seed, _trace, multiopen=multiopen)
 
 
-def _create_proof(who, params, pk, advice, instances, seed, _trace, encoding: str = "halo2") -> bytes:
+def _create_proof(who, params, pk, advice, instances, seed, _trace, encoding: str = "halo2", multiopen: str = "shplonk") -> bytes:
     import torch
 
     m = len(advice)
@@ -421,7 +431,7 @@ def _create_proof(who, params, pk, advice, instances, seed, _trace, encoding: st
                         q(ck("lookup_z", j, c), rot(1))]
     queries += [q(("fixed", i), rot(r)) for i, r in fix_q] + [q(("sigma", j), x) for j in range(P)]
     queries += [(("h",), x, hx), q(("random",), x)]
-    create_opening(params, transcript, queries, polys)
+    (gwc.create_opening if multiopen == "gwc" else create_opening)(params, transcript, queries, polys)
     if _trace is not None:
         _trace.update(polys=polys, commits=commits,
                       lagrange={"advice": [adv[:, c] for c in range(m)], "perm_z": zs, "lookup_z": lk_z, "permuted": perm_of},
@@ -429,14 +439,15 @@ def _create_proof(who, params, pk, advice, instances, seed, _trace, encoding: st
     return transcript.finalize()
 
 
-def create_proofs(params, pk: ProvingKey, advice, instances, seeds, encoding: str = "halo2") -> list:
+def create_proofs(params, pk: ProvingKey, advice, instances, seeds, encoding: str = "halo2", multiopen: str = "shplonk") -> list:
     """m independent proofs of ``pk``'s constraint system in one batched pass: ``create_proofs(...)[b] == create_proof(params, pk,
     advice[b], instances[b], seeds[b])``, byte for byte.  ``advice``: the (m, num_advice, n, 4) GPU tensor a witness writer returns, or
     a list of m (num_advice, n, 4) tensors; ``instances``: m entries, each in the form ``create_proof`` takes; ``seeds``: m integers,
     pairwise distinct mod 2^48 (two proofs with one seed would share their blinding: ValueError), or ONE integer s standing for
-    s, s + 1, ...  m >= 1, no upper limit.  ``encoding``: as in ``create_proof``."""
+    s, s + 1, ...  m >= 1, no upper limit.  ``encoding``, ``multiopen``: as in ``create_proof``."""
     who = "create_proofs"
     check_encoding(encoding, who)
+    check_multiopen(multiopen, who)
     if _is_tensor(advice):
         if advice.dim() != 4:
             raise ValueError(f"{who}: advice must be a (m, num_advice, n, 4) GPU tensor or a list of m (num_advice, n, 4) tensors")
@@ -456,10 +467,10 @@ def create_proofs(params, pk: ProvingKey, advice, instances, seeds, encoding: st
         raise ValueError(f"{who}: {m} proof(s) need {m} seeds")
     if len({s & 0xFFFFFFFFFFFF for s in seeds}) != m:
         raise ValueError(f"{who}: the seeds must be pairwise distinct mod 2^48 (two proofs would share their blinding)")
-    return _create_proofs(who, params, pk, advice, list(instances), seeds, encoding)
+    return _create_proofs(who, params, pk, advice, list(instances), seeds, encoding, multiopen)
 
 
-def _create_proofs(who, params, pk, advice, instances, seeds, encoding: str = "halo2") -> list:
+def _create_proofs(who, params, pk, advice, instances, seeds, encoding: str = "halo2", multiopen: str = "shplonk") -> list:
     """The protocol of ``_create_proof`` (module docstring, steps 1 - 14) for m transcripts of one circuit each; the comments name the
     step.  What belongs to proof b carries b where ``_create_proof`` carries the circuit's number; the key inside a proof is circuit 0's."""
     import torch
@@ -704,5 +715,5 @@ def _create_proofs(who, params, pk, advice, instances, seeds, encoding: str = "h
         queries += [q(("fixed", i), rot(r)) for i, r in fix_q] + [q(("sigma", j), x[b]) for j in range(P)]
         queries += [q(("h",), x[b]), q(("random",), x[b])]
         queries_of.append(queries)
-    create_openings(params, transcripts, queries_of, polys_of)
+    (gwc.create_openings if multiopen == "gwc" else create_openings)(params, transcripts, queries_of, polys_of)
     return [tr.finalize() for tr in transcripts]

@@ -51,6 +51,16 @@ def check_encoding(encoding, who: str) -> str:
     return encoding
 
 
+MULTIOPENS = ("shplonk", "gwc")
+
+
+def check_multiopen(multiopen, who: str) -> str:
+    """``multiopen`` when it names one of ``MULTIOPENS``; ValueError otherwise, before any other work of ``who``"""
+    if multiopen not in MULTIOPENS:
+        raise ValueError(f"{who}: multiopen must be one of {MULTIOPENS}, got {multiopen!r}")
+    return multiopen
+
+
 class TranscriptError(ValueError):
     """A short read, bytes that are no curve point, or a scalar that is not below r."""
 

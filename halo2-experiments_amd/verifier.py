@@ -5,7 +5,8 @@ recursive evaluator over ``evaluation.Expression``, the quotient identity fixes 
 L, R with e(L, [s]G2) = e(R, G2) -- checked by ``pairing.pairing_check`` against the parameters' G2 points, or, when the caller knows
 the trapdoor s (tests), by s * L == R in G1.  ``verify_proof_multi`` reads a ``create_proof_multi`` proof of m circuits the same way
 (per circuit where the prover writes per circuit), folds every circuit's expressions into one running value in y,
-and makes one opening check; ``verify_proof`` is its m = 1 case."""
+and makes one opening check; ``verify_proof`` is its m = 1 case.  ``multiopen="gwc"`` reads a proof that ends in the GWC multiopen
+(``gwc.verify_opening``) in place of SHPLONK's; everything before the multiopen is the same."""
 from __future__ import annotations
 
 import hashlib
@@ -16,8 +17,9 @@ from .domain import FR_MODULUS
 from .keygen import FR_DELTA, VerifyingKey
 from .kzg import g2_from_bytes
 from .pairing import g1_add, g1_mul, g1_neg, g1_on_curve, pairing_check
+from . import gwc
 from .shplonk import g1_words_to_int, verify_opening
-from .transcript import READERS, TranscriptError, check_encoding
+from .transcript import READERS, TranscriptError, check_encoding, check_multiopen
 
 R = FR_MODULUS
 
@@ -35,13 +37,27 @@ def _vk_digest(vk: VerifyingKey) -> int:
     return int.from_bytes(hsh.digest(), "little") % R
 
 
-def proof_length(cs, circuits: int = 1, encoding: str = "halo2") -> int:
+def opening_points(cs, k: int = None) -> int:
+    """q, the distinct points the multiopen's queries name -- the witness points a "gwc" proof ends in: the distinct rotations of
+    the advice and fixed queries, of the permutation and lookup arguments (0, 1, the last row; 0, -1, 1) and of h and the random
+    polynomial (0).  Two rotations give one point exactly when they agree mod n = 2^k; without ``k`` they are compared as they are,
+    which is the same count whenever every rotation lies within (-n / 2, n / 2)."""
+    adv_q, fix_q, _ = cs.queries()
+    nsets, L = cs.permutation_sets(), len(cs.lookups)
+    rots = [r for _, r in adv_q] + [r for _, r in fix_q] + [0]
+    rots += ([0, 1] if nsets else []) + ([-(cs.blinding_factors + 1)] if nsets > 1 else []) + ([0, -1, 1] if L else [])
+    return len({r % (1 << k) for r in rots} if k is not None else set(rots))
+
+
+def proof_length(cs, circuits: int = 1, encoding: str = "halo2", multiopen: str = "shplonk", k: int = None) -> int:
     """the bytes of a proof of ``circuits`` circuits of ``cs``, counted from the constraint system: 32 per point and per scalar, or
-    with ``encoding="evm"`` 64 per point and 32 per scalar"""
+    with ``encoding="evm"`` 64 per point and 32 per scalar.  ``multiopen="gwc"``: the proof ends in ``opening_points(cs, k)`` points
+    where a SHPLONK proof ends in two."""
     check_encoding(encoding, "proof_length")
+    check_multiopen(multiopen, "proof_length")
     adv_q, fix_q, _ = cs.queries()
     P, nsets, L = len(cs.equality), cs.permutation_sets(), len(cs.lookups)
-    points = circuits * (cs.num_advice + 2 * L + nsets + L) + 1 + (cs.degree() - 1) + 2
+    points = circuits * (cs.num_advice + 2 * L + nsets + L) + 1 + (cs.degree() - 1) + (opening_points(cs, k) if multiopen == "gwc" else 2)
     scalars = circuits * (len(adv_q) + (3 * nsets - 1 if nsets else 0) + 5 * L) + len(fix_q) + 1 + P
     return 32 * ((2 if encoding == "evm" else 1) * points + scalars)
 
@@ -77,36 +93,41 @@ def _instance_columns(cs, instance):
     return [[int(v) % R for v in c] for c in cols]
 
 
-def verify_proof(params, vk: VerifyingKey, instance, proof: bytes, trapdoor: int = None, encoding: str = "halo2") -> bool:
+def verify_proof(params, vk: VerifyingKey, instance, proof: bytes, trapdoor: int = None, encoding: str = "halo2",
+                 multiopen: str = "shplonk") -> bool:
     """True when ``proof`` is a valid proof of ``vk``'s circuit for ``instance`` (a list of integers for a one-column system, or one
     list per instance column).  ``params`` needs ``g2`` / ``s_g2`` only.  A malformed proof -- short or long, a point off the curve, a
     scalar not below r -- is False, not an exception.  ``encoding``: the proof's wire format, as ``create_proof`` names it; a proof
-    in the other one is a malformed proof."""
+    in the other one is a malformed proof.  ``multiopen``: the scheme the proof ends in, as ``create_proof`` names it; a proof of the
+    other scheme has another length, or fails."""
     check_encoding(encoding, "verify_proof")
+    check_multiopen(multiopen, "verify_proof")
     try:
-        return _verify(params, vk, [instance], proof, trapdoor, encoding)
+        return _verify(params, vk, [instance], proof, trapdoor, encoding, multiopen)
     except TranscriptError:
         return False
 
 
-def verify_proof_multi(params, vk: VerifyingKey, instances, proof: bytes, trapdoor: int = None) -> bool:
+def verify_proof_multi(params, vk: VerifyingKey, instances, proof: bytes, trapdoor: int = None, multiopen: str = "shplonk") -> bool:
     """True when ``proof`` is a valid ``create_proof_multi`` proof that every entry of ``instances`` -- one per circuit, each in the
     form ``verify_proof`` takes -- has a witness satisfying ``vk``'s circuit.  The proof is read in the prover's order (per circuit
     where the prover writes per circuit); the expression list is evaluated once per circuit, with that circuit's evaluations and
-    instance values, into ONE running value folded in y; one opening, one pairing check.  Malformed: False, as in ``verify_proof``."""
+    instance values, into ONE running value folded in y; one opening, one pairing check.  Malformed: False, as in ``verify_proof``.
+    ``multiopen``: as in ``verify_proof``."""
+    check_multiopen(multiopen, "verify_proof_multi")
     try:
-        return _verify(params, vk, list(instances), proof, trapdoor)
+        return _verify(params, vk, list(instances), proof, trapdoor, multiopen=multiopen)
     except TranscriptError:
         return False
 
 
-def _verify(params, vk, instances, proof, trapdoor, encoding: str = "halo2") -> bool:
+def _verify(params, vk, instances, proof, trapdoor, encoding: str = "halo2", multiopen: str = "shplonk") -> bool:
     cs, dom = vk.cs, vk.domain
     n, omega, blinding = 1 << dom.k, dom.omega, cs.blinding_factors
     P, chunk, nsets, L = len(cs.equality), cs.permutation_chunk_len(), cs.permutation_sets(), len(cs.lookups)
     deg, last = cs.degree(), -(blinding + 1)
     m = len(instances)
-    if m < 1 or len(proof) != proof_length(cs, m, encoding):
+    if m < 1 or len(proof) != proof_length(cs, m, encoding, multiopen, dom.k):
         return False
     inst_cols = [_instance_columns(cs, instance) for instance in instances]
     M = range(m)
@@ -243,7 +264,7 @@ def _verify(params, vk, instances, proof, trapdoor, encoding: str = "halo2") -> 
     queries += [(("h",), x, hx), q(("random",), x)]
     if any(com[key] is None for key, _, _ in queries):
         return False                                         # the identity cannot be absorbed or opened
-    left, right = verify_opening(t, queries, com)
+    left, right = (gwc.verify_opening if multiopen == "gwc" else verify_opening)(t, queries, com)
     if t.remaining():
         return False
     if trapdoor is not None:

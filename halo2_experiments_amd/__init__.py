@@ -5,7 +5,7 @@ Host-side mirror of ``halo2_proofs::arithmetic`` (``best_multiexp``, ``best_fft`
 
 The sources live in ``halo2-experiments_amd/`` (the directory name the project layout prescribes; not a valid
 Python identifier): this package is the importable name, and its ``__path__`` points there, so every submodule
-(``_header``, ``_lib``, ``_marshal``, ``arithmetic``, ``batch_verifier``, ``bn256``, ``device_pairing``, ``device_transcript``, ``domain``, ``keygen``, ``kzg``, ``mock_prover``, ``openings``, ``pairing``, ``poseidon``, ``proof_layout``, ``prover``, ``replay``, ``sharding``, ``shplonk``, ``solvency``, ``synthesis``, ``transcript``, ``verifier``) is an ordinary module of this package
+(``_header``, ``_lib``, ``_marshal``, ``arithmetic``, ``batch_verifier``, ``bn256``, ``device_pairing``, ``device_transcript``, ``domain``, ``gwc``, ``keygen``, ``kzg``, ``mock_prover``, ``openings``, ``pairing``, ``poseidon``, ``proof_layout``, ``prover``, ``replay``, ``sharding``, ``shplonk``, ``solvency``, ``synthesis``, ``transcript``, ``verifier``) is an ordinary module of this package
 with an ordinary ``__spec__`` / ``__file__``.
 """
 import os as _os

@@ -847,6 +847,24 @@ int hm_verify_terms_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_word
 int hm_verify_terms_multi_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
                               uint32_t circuits, const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad,
                               void* d_own, void* d_shared, void* d_h2_r, void* d_h2_l, void* stream);
+/* terms of proofs that end in the GWC multiopen (ProverGWC / VerifierGWC: one witness point W_i per distinct query point z_i, the
+ * check e(sum_i u^i W_i, [s]G2) = e(sum_i u^i z_i W_i + sum_i u^i sum_j v^j C_ij - (sum_i u^i sum_j v^j e_ij) G, G2)): as
+ * hm_verify_terms_dev, one lane per proof, the same `graph`, the same phase before the multiopen.  d_records: n_proofs x 8 elements
+ * -- theta, beta, gamma, y, x, the multiopen's v, u, and the weight r_b: what hm_verify_transcript_dev / _evm_dev leave with
+ * record_elems = 8 and a schedule of seven challenges.  `plan` is a GWC plan (csrc/verify_terms.inc, at vg_plan_problem): the header,
+ * column map, instance queries and constants of hm_verify_terms_dev's plan, and the q <= 32 point groups -- the constant omega^rot
+ * of z_i = x omega^rot, the own row of W_i, the members' targets and evaluation slots -- in place of the rotation sets.  It is checked
+ * word by word and uploaded with the call.  The lane computes r_b u^i v^j for member j of group i and ADDS it to the member's row (a
+ * commitment opened at several points is a member of several groups; the h commitment is expanded over its pieces by the powers
+ * of x^n), sums the generator's scalar, and has no inversion besides 1 / (x^n - 1) and those of the Lagrange values.
+ * Output (DEVICE memory, written for every proof): d_own, n_proofs x own points x 4 words in the proof's order -- every point of a
+ * GWC proof is an own point, W_i on its row with r_b u^i z_i --; d_shared, n_proofs x shared points x 4, the generator last with
+ * -r_b sum u^i v^j e_ij; d_w_left, n_proofs x q x 4: r_b u^i, the scalars of the W_i in the left sum.  A proof whose d_bad[b] is
+ * set on entry, or with x^n = 1 or x = 0, gets all-zero rows, d_w_left included, and d_bad[b] = 1.  Asynchronous on `stream`.
+ * HM_ERR_BAD_ARG, with nothing launched: as hm_verify_terms_dev, the plan's reasons among them more than 32 point groups. */
+int hm_verify_terms_gwc_dev(uint64_t graph, const uint32_t* plan, size_t n_plan_words, size_t n_columns, size_t n_dynamic, size_t n_proofs,
+                            const void* d_records, const void* d_scalars, const void* d_instance, uint32_t* d_bad, void* d_own, void* d_shared,
+                            void* d_w_left, void* stream);
 /* per-proof sums: the two G1 points of every proof's OWN opening check, one workgroup per proof, all proofs in one launch -- what a
  * verdict per proof needs where the MSMs above sum over proofs.  d_bases_xy: (n_proofs * own_points + shared_points + n_proofs) x 8
  * u64, affine Montgomery words, (0, 0) = the identity: the own points of every proof as hm_verify_read_proofs_dev left them, then the

@@ -19,6 +19,11 @@ rows stand under ``modes`` by "transcript/pairing/encoding"; ``both`` proves the
 encodings and interleaves them per B in one session, so that the "halo2" rows are the yardstick of the "evm" rows beside them.  The
 host transcript of "evm" is Keccak in pure Python (about half a millisecond per 136-byte block): large B is slow there.
 
+``--multiopen shplonk|gwc|both`` chooses the multiopen scheme the proofs end in (default shplonk: the figures above).  With ``gwc``,
+or ``both``, the rows stand under ``modes`` by "transcript/pairing/encoding/multiopen" and every row also holds ``terms_kernel_ms``, the
+terms kernel of its scheme alone (events around the call on the prepared batch); ``both`` proves the same witnesses with the same
+seeds under the two schemes and interleaves them per B in one session, the "shplonk" rows the yardstick of the "gwc" rows beside them.
+
 ``--circuits`` names the constraint systems; an INTEGER among its entries is a number of circuits per proof instead (``--circuits
 1,4,16,64``, with or without names beside them) and asks for the multi-circuit measurement in place of the one
 above: for every m and every B of ``--sizes``, in one session with the routes alternating, everything on the device --
@@ -100,7 +105,9 @@ def terms_kernel_ms(bv, repeats):
     around the call, one warm-up; the outputs go to arrays of their own"""
     st = bv._prepare()
     dev = st["d_records"].device
-    out = [torch.empty_like(st[name]) for name in ("d_own", "d_shared", "d_h2_r", "d_h2_l")]
+    gwc = getattr(bv, "multiopen", "shplonk") == "gwc"             # d_w_left stands where SHPLONK has d_h2_r, and there is no d_h2_l
+    out = [torch.empty_like(st[name]) for name in (("d_own", "d_shared", "d_w_left") if gwc else ("d_own", "d_shared", "d_h2_r", "d_h2_l"))]
+    out += [None] if gwc else []
     d_bad = torch.zeros(st["B"], dtype=torch.int32, device=dev)
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     ms = []
@@ -210,32 +217,39 @@ def multi_circuit(name, counts, sizes, repeats):
     return out
 
 
-def circuit(name, sizes, repeats, modes=(("host", "host"),), encodings=("halo2",)):
+def circuit(name, sizes, repeats, modes=(("host", "host"),), encodings=("halo2",), multiopens=("shplonk",)):
     cs, lay, advice, instance, _ = pc.build(name)
     params = ParamsKZG.setup(lay.k, pc.SRS_S)
     vk = h.keygen_vk(params, cs, lay)
     pk = h.keygen_pk(params, vk, cs, lay, cosets=False)
     try:
-        made = {e: [h.create_proof(params, pk, advice, instance, seed, encoding=e) for seed in (2, 3, 4, 5)] for e in encodings}
-        plain = encodings == ("halo2",)                          # the record's shape before there was a second encoding
-        out = {"k": lay.k, "proof_bytes": len(made[encodings[0]][0]) if plain else {e: len(made[e][0]) for e in encodings}, "batches": {}}
+        schemes = multiopens != ("shplonk",)                     # a second scheme asked for: its name goes into every key
+        made = {(e, mo): [h.create_proof(params, pk, advice, instance, seed, encoding=e, multiopen=mo) for seed in (2, 3, 4, 5)]
+                for e in encodings for mo in multiopens}
+        plain = encodings == ("halo2",) and not schemes          # the record's shape before there was a second encoding or scheme
+        first = (encodings[0], multiopens[0])
+        out = {"k": lay.k, "batches": {},
+               "proof_bytes": len(made[first][0]) if plain else {"/".join(key) if schemes else key[0]: len(p[0]) for key, p in made.items()}}
         single = []
         for i in range(min(16, max(sizes))):
             t0 = time.perf_counter()
-            assert h.verify_proof(params, vk, instance, made[encodings[0]][i % 4], encoding=encodings[0])
+            assert h.verify_proof(params, vk, instance, made[first][i % 4], encoding=first[0], multiopen=first[1])
             single.append((time.perf_counter() - t0) * 1e3)
         out["verify_proof_per_proof"] = dict(spread(single), proofs=len(single), encoding=encodings[0])
-        runs = [(t, p, e) for t, p in modes for e in encodings]  # the encodings of one mode stand side by side
-        for transcript, pairing, encoding in runs:                # warm-up: library load, allocator pools
-            h.verify_proofs(params, vk, [instance], made[encoding][:1], transcript=transcript, pairing=pairing, encoding=encoding)
+        if schemes:
+            out["verify_proof_per_proof"]["multiopen"] = multiopens[0]
+        runs = [(t, p, e, mo) for t, p in modes for e in encodings for mo in multiopens]   # encodings and schemes of one mode side by side
+        for transcript, pairing, encoding, mo in runs:            # warm-up: library load, allocator pools
+            h.verify_proofs(params, vk, [instance], made[(encoding, mo)][:1], transcript=transcript, pairing=pairing, encoding=encoding,
+                            multiopen=mo)
         for B in sizes:
-            for transcript, pairing, encoding in runs:
-                proofs = made[encoding]
+            for transcript, pairing, encoding, mo in runs:
+                proofs = made[(encoding, mo)]
                 total, split = [], {p: [] for p in PHASES}
                 for _ in range(repeats):
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
-                    bv = h.BatchVerifier(params, vk, transcript=transcript, pairing=pairing, encoding=encoding)
+                    bv = h.BatchVerifier(params, vk, transcript=transcript, pairing=pairing, encoding=encoding, multiopen=mo)
                     for b in range(B):
                         bv.add_proof(instance, proofs[b % 4])
                     ok = bv.finalize()
@@ -250,13 +264,15 @@ def circuit(name, sizes, repeats, modes=(("host", "host"),), encodings=("halo2",
                 if transcript == "device":
                     row["transcript_kernel_ms"] = transcript_kernel_ms(bv, repeats)
                     row["read_kernel_ms"] = read_kernel_ms(bv, repeats)
+                if schemes:
+                    row["terms_kernel_ms"] = terms_kernel_ms(bv, repeats)
                 if len(runs) == 1 and plain:
                     out["batches"][str(B)] = row
                 else:
-                    key = f"{transcript}/{pairing}" if plain else f"{transcript}/{pairing}/{encoding}"
+                    key = f"{transcript}/{pairing}" if plain else f"{transcript}/{pairing}/{encoding}" + (f"/{mo}" if schemes else "")
                     out.setdefault("modes", {}).setdefault(key, {})[str(B)] = row
                 bv.close()
-                print(f"{name} B={B} {transcript}/{pairing}/{encoding}: {row['finalize']['median_ms']} ms", file=sys.stderr, flush=True)
+                print(f"{name} B={B} {transcript}/{pairing}/{encoding}/{mo}: {row['finalize']['median_ms']} ms", file=sys.stderr, flush=True)
         if "modes" in out:
             del out["batches"]
     finally:
@@ -271,6 +287,7 @@ if __name__ == "__main__":
     ap.add_argument("--transcript", choices=("host", "device", "both"), default="host")
     ap.add_argument("--pairing", choices=("host", "device", "both"), default="host")
     ap.add_argument("--encoding", choices=("halo2", "evm", "both"), default="halo2")
+    ap.add_argument("--multiopen", choices=("shplonk", "gwc", "both"), default="shplonk")
     ap.add_argument("--circuits", default="merkle_sum_d20_k10,poseidon_k6")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -278,11 +295,14 @@ if __name__ == "__main__":
     both = lambda choice: ("host", "device") if choice == "both" else (choice,)
     modes = tuple((t, p) for p in both(args.pairing) for t in both(args.transcript))
     encodings = ("halo2", "evm") if args.encoding == "both" else (args.encoding,)
+    multiopens = ("shplonk", "gwc") if args.multiopen == "both" else (args.multiopen,)
     torch.cuda.init()
     result = {"tool": "tools/batch_verify_time.py", "repeats": args.repeats, "modes_measured": [f"{t}/{p}" for t, p in modes],
               "encodings_measured": list(encodings),
               "host": "the transcripts (Blake2b by hashlib; Keccak in pure Python) and the pairing, unless the mode (transcript/pairing) says "
                       "device; everything else (read, terms, column sum, MSMs) on the device"}
+    if multiopens != ("shplonk",):
+        result["multiopens_measured"] = list(multiopens)
     entries = args.circuits.split(",")
     counts = [int(e) for e in entries if e.isdigit()]
     names = [e for e in entries if not e.isdigit()] or ["merkle_sum_d20_k10", "poseidon_k6"]
@@ -291,7 +311,7 @@ if __name__ == "__main__":
                       routes="multi: B create_proof_multi proofs of m circuits; single_yardstick: the B * m single-circuit proofs of the "
                              "same witnesses; both finalize() then verdicts() on a fresh BatchVerifier, transcript and pairing on the device")
     for name in names:
-        result[name] = multi_circuit(name, counts, sizes, args.repeats) if counts else circuit(name, sizes, args.repeats, modes, encodings)
+        result[name] = multi_circuit(name, counts, sizes, args.repeats) if counts else circuit(name, sizes, args.repeats, modes, encodings, multiopens)
     text = json.dumps(result)
     print(text)
     if args.out:

@@ -16,6 +16,11 @@
     of its steps alone, each against its loop: the h numerator through CompiledGraph.evaluate_proofs against m evaluate calls with
     per-proof constants on the same columns, and the multiopen (shplonk.create_openings inside create_proofs against the m
     create_opening calls inside the loop, both timed in a second pass of their own).
+(e) ``--multiopen shplonk|gwc|both`` (with ``--proofs m[,m...]``, default 1,16,64): instead, the two multiopen schemes side by side
+     at depth 5 / k = 9 and depth 20 / k = 10: create_proof (m = 1) or create_proofs (m > 1) wall-clock with
+    ``multiopen=`` each scheme, the routes alternating inside every repeat of one session, and in a second pass the multiopen alone
+    (``create_opening`` / ``create_openings`` of ``shplonk`` and of ``gwc``, commitments included); and the polynomial side at the
+    k = 18 shape: the q one-point quotients of GWC beside SHPLONK's set quotients, commitments left out of both.
 Five repeats each: median and min .. max.  Prints one JSON object."""
 import argparse
 import json
@@ -32,7 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 import halo2_experiments_amd as h                                         # noqa: E402
-from halo2_experiments_amd import circuits, poseidon as ps, prover, shplonk as sh   # noqa: E402
+from halo2_experiments_amd import circuits, gwc, poseidon as ps, prover, shplonk as sh   # noqa: E402
 from halo2_experiments_amd.domain import FR_MODULUS as R, EvaluationDomain, fr_words   # noqa: E402
 from halo2_experiments_amd.kzg import ParamsKZG                            # noqa: E402
 import prover_cases as pc                                                  # noqa: E402
@@ -227,8 +232,8 @@ def proofs(name, m):
     return res
 
 
-def k18_sets():
-    """the rotation sets of the MerkleSumTree constraint system as (points, keys), with the prover's order of queries"""
+def k18_queries():
+    """the queries of the MerkleSumTree constraint system at k = 18 in the prover's order, every evaluation 0"""
     cs = circuits.merkle_sum_tree(ps.default_spec(5))
     dom = EvaluationDomain(cs.degree(), 18)
     x = 0x123456789ABCDEF % R
@@ -241,7 +246,12 @@ def k18_sets():
     for j in range(L):
         q += [(("lookup_z", j), x, 0), (("lookup_a", j), x, 0), (("lookup_s", j), x, 0), (("lookup_a", j), rot(-1), 0), (("lookup_z", j), rot(1), 0)]
     q += [(("fixed", c), rot(r), 0) for c, r in fix_q] + [(("sigma", j), x, 0) for j in range(P)] + [(("h",), x, 0), (("random",), x, 0)]
-    sets, super_points = sh.construct_intermediate_sets(q)
+    return q
+
+
+def k18_sets():
+    """the rotation sets of the MerkleSumTree constraint system as (points, keys), with the prover's order of queries"""
+    sets, super_points = sh.construct_intermediate_sets(k18_queries())
     return [(pts, [key for key, _ in members]) for pts, members in sets], super_points
 
 
@@ -299,13 +309,112 @@ def multiopen_k18():
             "set_quotient_entry": spread(new), "composed_from_existing_kernels": spread(old)}
 
 
+def schemes(name, m, multiopens):
+    """(e): m proofs of one shape under every scheme of ``multiopens`` -- totals with the routes alternating, then the multiopen alone"""
+    cs, lay, advice, instances = pmc.build_multi(name, m)
+    params = ParamsKZG.setup(lay.k, pc.SRS_S)
+    vk = h.keygen_vk(params, cs, lay)
+    pk = h.keygen_pk(params, vk, cs, lay, cosets=False)
+    entry = "create_opening" if m == 1 else "create_openings"
+    where = {"shplonk": prover, "gwc": gwc}                       # the module whose attribute the prover calls for the scheme
+    real = {mo: getattr(where[mo], entry) for mo in multiopens}
+    inner = []
+
+    def run(mo, rep):
+        if m == 1:
+            return [h.create_proof(params, pk, advice[0], instances[0], 1000 * rep, multiopen=mo)]
+        return h.create_proofs(params, pk, advice, instances, [1000 * rep + b for b in range(m)], multiopen=mo)
+
+    def timed(fn):
+        def call(*a, **kw):
+            inner.append(wall(lambda: fn(*a, **kw))[1])
+        return call
+    try:
+        sizes = {}
+        for mo in multiopens:                                     # warm-up, and the proofs verify
+            made = run(mo, 1)
+            assert h.verify_proofs(params, vk, instances[:m], made, transcript="device", pairing="device", multiopen=mo)
+            sizes[mo] = len(made[0])
+        totals, opens = {mo: [] for mo in multiopens}, {mo: [] for mo in multiopens}
+        for rep in range(REPEATS):
+            for mo in multiopens:
+                totals[mo].append(wall(lambda: run(mo, 2 + rep))[1])
+        for mo in multiopens:
+            setattr(where[mo], entry, timed(real[mo]))
+        for rep in range(REPEATS):
+            for mo in multiopens:
+                inner.clear()
+                run(mo, 2 + rep)
+                opens[mo].append(sum(inner))
+    finally:
+        for mo in multiopens:
+            setattr(where[mo], entry, real[mo])
+        params.release()
+    return {"k": lay.k, "proofs": m, "entry": "create_proof" if m == 1 else "create_proofs",
+            **{mo: {"proof_bytes": sizes[mo], "total": spread(totals[mo]), "multiopen": spread(opens[mo]),
+                    "per_proof_ms": round(statistics.median(totals[mo]) / m, 3)} for mo in multiopens}}
+
+
+def multiopen_k18_schemes(multiopens):
+    """the polynomial side at k = 18, commitments left out: SHPLONK's set quotients (h, then the final quotient) beside GWC's q one-point
+    quotients on the same polynomials; one GWC quotient is checked against linear_combination + kate_division"""
+    n = 1 << 18
+    queries = k18_queries()
+    sets, super_points = k18_sets()
+    groups = gwc.construct_point_groups(queries)
+    keys = [key for _, members in sets for key in members]
+    polys = {key: h.random_fr(n, 100 + i) for i, key in enumerate(keys)}
+    rng = random.Random(18)
+    y, v, u = (rng.randrange(2, R) for _ in range(3))
+    zt = sh.vanishing_eval(super_points, u)
+    z = [sh.vanishing_eval([p for p in super_points if p not in pts], u) for pts, _ in sets]
+
+    def shplonk_route():
+        hx = None
+        for i, (pts, members) in enumerate(sets):
+            hx = sh.set_quotient([polys[k] for k in members], [pow(y, j, R) for j in range(len(members))], pts, pow(v, i, R), out=hx, accumulate=i > 0)
+        cols, weights = [], []
+        for i, (pts, members) in enumerate(sets):
+            for j, key in enumerate(members):
+                cols.append(polys[key])
+                weights.append(pow(v, i, R) * z[i] % R * pow(y, j, R) % R)
+        return hx, sh.set_quotient(cols + [hx], weights + [-zt % R], [u], pow(z[0], -1, R))
+
+    def gwc_route():
+        return [sh.set_quotient([polys[key] for key, _ in members], [pow(v, j, R) for j in range(len(members))], [pt]) for pt, members in groups]
+
+    pt, members = groups[-1]
+    lc = h.linear_combination([polys[key] for key, _ in members], np.stack([fr_words(pow(v, j, R)) for j in range(len(members))]))
+    want = torch.cat([h.kate_division(lc, fr_words(pt)), torch.zeros((1, 4), dtype=torch.int64, device="cuda")])
+    assert torch.equal(gwc_route()[-1], want), "a GWC quotient differs from linear_combination + kate_division"
+    routes = {"shplonk": shplonk_route, "gwc": gwc_route}
+    times = {mo: [] for mo in multiopens}
+    for mo in multiopens:
+        routes[mo]()
+    for _ in range(REPEATS):
+        for mo in multiopens:
+            times[mo].append(wall(routes[mo])[1])
+    return {"n": n, "sets": [{"points": len(pts), "polynomials": len(members)} for pts, members in sets],
+            "groups": [{"polynomials": len(members)} for _, members in groups], **{mo: spread(times[mo]) for mo in multiopens}}
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--circuits", type=int, default=0, help="m: time create_proof_multi and the h step for m circuits (1 .. 64) instead")
     ap.add_argument("--proofs", default="", help="m[,m...]: time create_proofs against the loop of m create_proof calls, with the h step and the "
                     "multiopen split out, for every listed m instead")
+    ap.add_argument("--multiopen", choices=("shplonk", "gwc", "both"), default="",
+                    help="time the multiopen schemes side by side (create_proof / create_proofs for every m of --proofs, default 1,16,64) instead")
     args = ap.parse_args()
     torch.cuda.init()
+    if args.multiopen:
+        multiopens = ("shplonk", "gwc") if args.multiopen == "both" else (args.multiopen,)
+        out = {"tool": "tools/prove_time.py --multiopen", "repeats": REPEATS, "multiopens_measured": list(multiopens)}
+        for name in ("merkle_sum_d5_k9", "merkle_sum_d20_k10"):
+            out[name] = {f"proofs_{m}": schemes(name, int(m), multiopens) for m in (args.proofs or "1,16,64").split(",")}
+        out["multiopen_k18"] = multiopen_k18_schemes(multiopens)
+        print(json.dumps(out))
+        sys.exit(0)
     if args.proofs:
         print(json.dumps({f"proofs_{m}": {name: proofs(name, int(m)) for name in ("merkle_sum_d20_k10", "merkle_sum_d5_k9")}
                           for m in args.proofs.split(",")}))
