@@ -1,5 +1,5 @@
 // capi_g1.hip -- the G1 entry points of the C ABI outside the MSM: fixed-base multiples, best_fft over G1 (g1_fft.hip), all KZG openings
-// of a polynomial (g1_fft.hip) and the SRS point encodings (g1_codec.hip).
+// of a polynomial (g1_fft.hip), the pairing operands of ledger openings (ledger.hip) and the SRS point encodings (g1_codec.hip).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -77,6 +77,26 @@ int hm_kzg_open_all_timed_bn256_dev(const void* d_table_xy, const void* d_coeffs
   if (!out_part_ms || count == 0) return hm_fail(HM_ERR_BAD_ARG, "hm_kzg_open_all_timed_bn256_dev: null argument or no polynomial");
   return kzg_open_all_entry("hm_kzg_open_all_timed_bn256_dev", d_table_xy, d_coeffs, log_n, count, d_proofs_xy, out_part_ms, stream);
 } HM_API_CATCH("hm_kzg_open_all_timed_bn256_dev")
+
+// ---- ledger openings: every user's pairing operands (ledger.hip) ---------------------------------------------------------------
+int hm_kzg_ledger_pairs_bn256_dev(const void* d_openings_xy, const uint32_t* d_indices, const void* d_ids, const void* d_balances,
+                                  const uint64_t gamma[4], const uint64_t omega[4], const uint64_t c_gamma[8], uint32_t log_n,
+                                  uint32_t assets, size_t n_users, void* d_g1_xy, uint32_t* d_flags, void* stream) try {
+  const std::string who = "hm_kzg_ledger_pairs_bn256_dev";
+  if (!d_openings_xy || !d_indices || !d_ids || (assets && !d_balances) || !gamma || !omega || !c_gamma || !d_g1_xy || !d_flags)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": null argument");
+  if (n_users == 0 || n_users > ((size_t)1 << 20)) return hm_fail(HM_ERR_BAD_ARG, who + ": need 1 <= n_users <= 2^20");
+  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, who + ": log_n > 28");
+  if (assets > (1u << 16)) return hm_fail(HM_ERR_BAD_ARG, who + ": assets > 2^16");
+  if (const char* problem = kzg_ledger_words_problem(gamma, omega, c_gamma)) return hm_fail(HM_ERR_BAD_ARG, who + ": " + problem);
+  if (((uintptr_t)d_openings_xy | (uintptr_t)d_ids | (uintptr_t)d_balances | (uintptr_t)d_g1_xy) & 15u)
+    return hm_fail(HM_ERR_BAD_ARG, who + ": a buffer is not 16-byte aligned");
+  if (((uintptr_t)d_indices | (uintptr_t)d_flags) & 3u) return hm_fail(HM_ERR_BAD_ARG, who + ": d_indices / d_flags is not 4-byte aligned");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return kzg_ledger_pairs_run((const uint32_t*)d_openings_xy, d_indices, (const uint32_t*)d_ids, (const uint32_t*)d_balances, gamma, omega,
+                              c_gamma, log_n, assets, n_users, (uint32_t*)d_g1_xy, d_flags, (hipStream_t)stream);
+} HM_API_CATCH("hm_kzg_ledger_pairs_bn256_dev")
 
 // ---- SRS point encodings (g1_codec.inc) --------------------------------------------------------------------------------------
 static constexpr size_t G1_CODEC_MAX_N = (size_t)1 << 30;

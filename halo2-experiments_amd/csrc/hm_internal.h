@@ -570,6 +570,14 @@ int kzg_open_table_run(DeviceCtx& ctx, const uint32_t* d_g_xy, uint32_t log_n, u
 int kzg_open_all_run(DeviceCtx& ctx, const uint32_t* d_table_xy, const uint32_t* d_coeffs, uint32_t log_n, size_t count,
                      uint32_t* d_proofs_xy, hipStream_t stream, double* part_ms = nullptr);
 
+// ledger.hip: the pair (pi_b, -R_b) of every user's ledger opening check, one lane per user (ledger.inc): 2 rows of affine Montgomery
+// words per user at d_g1 and one flag word at d_flags.  gamma, omega (the 2^log_n-th root of unity) and c_gamma are host words.
+// Arguments checked by the caller, the word arrays with kzg_ledger_words_problem (null: nothing wrong); one launch, asynchronous on `stream`.
+const char* kzg_ledger_words_problem(const uint64_t gamma[4], const uint64_t omega[4], const uint64_t c_gamma[8]);
+int kzg_ledger_pairs_run(const uint32_t* d_openings, const uint32_t* d_indices, const uint32_t* d_ids, const uint32_t* d_balances,
+                         const uint64_t gamma[4], const uint64_t omega[4], const uint64_t c_gamma[8], uint32_t log_n, uint32_t assets,
+                         size_t users, uint32_t* d_g1, uint32_t* d_flags, hipStream_t stream);
+
 // g1_codec.hip: SRS point encodings: 16-word affine external points <-> 8-word compressed encodings.  compress is asynchronous;
 // decompress / check wait for `stream` and answer HM_ERR_INVALID_DATA with the smallest invalid index in *first_invalid (n if none).
 int g1_compress_run(const uint32_t* d_xy, size_t n, uint32_t* d_out32, hipStream_t stream);

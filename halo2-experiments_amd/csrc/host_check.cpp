@@ -24,6 +24,7 @@ namespace hm {
 #include "verify_read.inc"   // the batch verifier's per-slot read and its column sum (verify.hip)
 #include "verify_terms.inc"  // ... and the two phases of its per-proof terms around the interpreter's run (verify.hip)
 #include "verify_sums.inc"   // ... and the lane, fold and finish functions of its per-proof sums (verify.hip)
+#include "ledger.inc"     // the lane function of the ledger openings' pairing operands (ledger.hip)
 #include "poseidon.inc"   // the per-hash Poseidon / Merkle node functions (poseidon.hip)
 #include "range.inc"      // the range-check witness's lane function (range.hip)
 #include "accumulator.inc" // the accumulator witness's row function (accumulator.hip)
@@ -714,6 +715,21 @@ int hc_g1_mul_words_pair(const uint32_t* base, const uint32_t* e_words, uint32_t
   vs_store_acc(record, by_field.inf ? g1_identity() : by_field);
   vs_finish(record, false, row);
   return (whole.inf && by_field.inf) || same_limbs(whole, by_field) ? 1 : 0;
+}
+
+// The pairing operands of one user's ledger opening (ledger.inc): ld_pair, the kernel's own lane function, on host memory.  gamma,
+// omega: 8 Montgomery words each; c_gamma, opening: 16 affine words; id: 8 words; balances: assets x 8 words; rows: 32 words.
+// Returns the user's flag, -1 for arguments the C entry refuses.
+int hc_ledger_pair(const uint32_t* gamma, const uint32_t* omega, const uint32_t* c_gamma, uint32_t log_n, uint32_t assets,
+                   const uint32_t* opening, uint32_t index, const uint32_t* id, const uint32_t* balances, uint32_t* rows) {
+  if (log_n > 28 || assets > LD_MAX_ASSETS) return -1;
+  LdShared s;
+  std::memcpy(s.gamma, gamma, 32);
+  std::memcpy(s.omega, omega, 32);
+  std::memcpy(s.c_gamma, c_gamma, 64);
+  s.k = log_n;
+  s.assets = assets;
+  return (int)ld_pair(s, opening, index, id, balances, rows);
 }
 
 // Blake2b and the transcripts (transcript.inc), the exact lane code of its kernels on a block of 32 host words.

@@ -5,7 +5,7 @@ Host-side mirror of ``halo2_proofs::arithmetic`` (``best_multiexp``, ``best_fft`
 
 The sources live in ``halo2-experiments_amd/`` (the directory name the project layout prescribes; not a valid
 Python identifier): this package is the importable name, and its ``__path__`` points there, so every submodule
-(``_header``, ``_lib``, ``_marshal``, ``arithmetic``, ``batch_verifier``, ``bn256``, ``device_pairing``, ``device_transcript``, ``domain``, ``gwc``, ``keygen``, ``kzg``, ``mock_prover``, ``openings``, ``pairing``, ``poseidon``, ``proof_layout``, ``prover``, ``replay``, ``sharding``, ``shplonk``, ``solvency``, ``synthesis``, ``transcript``, ``verifier``) is an ordinary module of this package
+(``_header``, ``_lib``, ``_marshal``, ``arithmetic``, ``batch_verifier``, ``bn256``, ``device_pairing``, ``device_transcript``, ``domain``, ``gwc``, ``keygen``, ``kzg``, ``ledger``, ``mock_prover``, ``openings``, ``pairing``, ``poseidon``, ``proof_layout``, ``prover``, ``replay``, ``sharding``, ``shplonk``, ``solvency``, ``synthesis``, ``transcript``, ``verifier``) is an ordinary module of this package
 with an ordinary ``__spec__`` / ``__file__``.
 """
 import os as _os
@@ -23,6 +23,8 @@ from .batch_verifier import BatchVerifier, verify_each, verify_proofs  # noqa: F
 from .domain import EvaluationDomain  # noqa: F401
 from .keygen import (ProvingKey, VerifyingKey, copy_pairs, keygen_pk, keygen_vk, permutation_cells_dev,  # noqa: F401
                      permutation_columns_dev)
+from .ledger import (LedgerProof, LedgerStatement, ledger_eta, ledger_gamma, ledger_openings, ledger_statement,  # noqa: F401
+                     prove_ledger, verify_ledger, verify_ledger_user, verify_ledger_users)
 from .mock_prover import MockProver, MockResult, NotSatisfied  # noqa: F401
 from .openings import OpeningTable, open_all, open_all_ints, open_at, verify_opening, verify_openings  # noqa: F401
 from .pairing import pairing_check  # noqa: F401
@@ -49,4 +51,5 @@ __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_mult
            "set_quotient", "set_quotient_batch", "set_quotient_ints", "create_openings", "linear_combination_batch", "MockProver", "MockResult", "NotSatisfied", "BatchVerifier", "verify_proofs", "verify_each",
            "OpeningTable", "open_all", "open_all_ints", "open_at", "verify_opening", "verify_openings",
            "RangeCheckLayout", "range_witness", "range_witness_host", "range_c_layout", "BalanceProof", "prove_balances", "verify_balances",
-           "user_openings", "verify_user", "verify_users"]
+           "user_openings", "verify_user", "verify_users",
+           "LedgerProof", "LedgerStatement", "ledger_statement", "prove_ledger", "verify_ledger", "ledger_gamma", "ledger_eta", "ledger_openings", "verify_ledger_user", "verify_ledger_users"]

@@ -564,6 +564,24 @@ int hm_kzg_open_all_bn256_dev(const void* d_table_xy, const void* d_coeffs, uint
 int hm_kzg_open_all_timed_bn256_dev(const void* d_table_xy, const void* d_coeffs, uint32_t log_n, size_t count, void* d_proofs_xy,
                                     double out_part_ms[7], void* stream);
 
+/* Ledger openings (one id-bound KZG opening per user), one lane per user: the pairing operands of every user's own check.  User b
+ * holds row d_indices[b] of a ledger of 2^log_n rows, the id d_ids[b] (4 u64 Montgomery Fr words), `assets` balances at
+ * d_balances[b] (assets x 4 words) and the opening d_openings_xy[b] (8 u64 affine Montgomery words, (0, 0) = the identity) of
+ * c_gamma = C_id + sum_p gamma^(p+1) C_p at omega^index, with the value y = id + sum_p gamma^(p+1) balance_p.  gamma, omega (the
+ * 2^log_n-th root of unity) and c_gamma are HOST words; c_gamma is the caller's: its words are checked to be canonical, not to lie
+ * on the curve.  Output d_g1_xy, n_users x 2 x 8 u64: row 2b is pi_b, row 2b + 1 is -R_b with R_b = c_gamma + [r - y]G +
+ * [omega^index]pi_b, canonical affine Montgomery words, (0, 0) for the identity -- the d_g1_xy layout of
+ * hm_pairing_check_bn256_dev, so that (pi_b, [s]G2), (-R_b, G2) is check b of one pairing call.  Every addition is the complete one.
+ * d_flags[b] = 1 for a user whose opening has a coordinate word >= p or is off the curve, whose id or balance words are >= r, or
+ * whose index is >= 2^log_n: that user gets two zero rows -- which WOULD pass a pairing, so the flag decides -- and nothing of it is
+ * multiplied; 0 otherwise.  All DEVICE memory but the three word arrays; point and scalar arrays 16-byte aligned, d_indices and d_flags
+ * 4-byte.  Asynchronous on `stream`: one launch.  HM_ERR_BAD_ARG, with nothing launched: NULL arguments (d_balances may be NULL when
+ * assets is 0), n_users 0 or above 2^20 (the pairing entry's cap), log_n > 28, assets > 2^16, gamma or omega not below r, a word of
+ * c_gamma not below p, a buffer that is not aligned. */
+int hm_kzg_ledger_pairs_bn256_dev(const void* d_openings_xy, const uint32_t* d_indices, const void* d_ids, const void* d_balances,
+                                  const uint64_t gamma[4], const uint64_t omega[4], const uint64_t c_gamma[8], uint32_t log_n,
+                                  uint32_t assets, size_t n_users, void* d_g1_xy, uint32_t* d_flags, void* stream);
+
 /* ---- SRS point encodings: ParamsKZG::read / write (compressed G1 and the checked raw format) ---------------------------- */
 
 /* Compressed G1, 32 bytes: canonical x little-endian (Fq::to_bytes), bit 7 of byte 31 = parity of canonical y; the identity is 32
