@@ -46,7 +46,7 @@ from .keygen import ProvingKey, VerifyingKey
 from .kzg import g2_from_bytes
 from .openings import _point, _scalar_int, domain_omega, open_all, open_at, verify_opening
 from .pairing import g1_add, g1_mul, g1_on_curve
-from .prover import create_proof, create_proofs
+from .prover import create_proofs
 from .solvency import _range_parameters
 from .synthesis import BLINDING_ROWS, range_witness
 from .transcript import TranscriptError, check_encoding, check_multiopen, g1_decompress_int, g1_uncompressed_int
@@ -173,7 +173,7 @@ def prove_ledger(params, pk: ProvingKey, ids, balances, seed: int, check: bool =
                  multiopen: str = "shplonk") -> LedgerProof:
     """``balances``: a (rows, 4) GPU tensor of canonical Montgomery words, one asset, or a (P, rows, 4) stack, exactly as
     ``solvency.prove_balances`` takes them; ``ids``: a (rows, 4) GPU tensor, one id per row.  The range witness and the range proofs
-    go through ``range_witness`` and ``create_proof`` / ``create_proofs`` (asset p with seed + p); ``check``, ``encoding`` and
+    go through ``range_witness`` and ``create_proofs`` (asset p with seed + p); ``check``, ``encoding`` and
     ``multiopen`` as there.  An id whose words are not below r raises ValueError; nothing else is checked about ids."""
     import torch
 
@@ -199,8 +199,7 @@ def prove_ledger(params, pk: ProvingKey, ids, balances, seed: int, check: bool =
             if count:
                 raise ValueError(f"{who}: asset {p}: {count} balance(s) at or above 2^{max_bits * acc_cols}")
     empty = [[]]                                             # the instance column holds nothing
-    proofs = ([create_proof(params, pk, advice[0], empty, seed, encoding=encoding, multiopen=multiopen)] if P == 1
-              else create_proofs(params, pk, advice, [empty] * P, seed, encoding=encoding, multiopen=multiopen))
+    proofs = create_proofs(params, pk, advice, [empty] * P, seed, encoding=encoding, multiopen=multiopen)
     columns = torch.zeros((P + 1, n, 4), dtype=torch.int64, device=values.device)
     columns[0, :rows] = ids
     columns[1:] = advice[:, 0]                               # rows >= `rows` are zero

@@ -2,7 +2,7 @@
 (DESIGN.md section 25).  Composition only -- every step is an entry point of another module:
 
     the balance column of an asset, padded with zeros to n = 2^k rows, is advice column 0 of ``circuits.overflow_check_v2(max_bits,
-    acc_cols, unblinded_value=True)``; ``synthesis.range_witness`` writes its limbs; ``create_proof`` / ``create_proofs`` prove that
+    acc_cols, unblinded_value=True)``; ``synthesis.range_witness`` writes its limbs; ``create_proofs`` proves that
     every row under the key's selector is below 2^(max_bits * acc_cols), and -- the value column being unblinded -- the proof's first
     commitment C is ``params.commit_lagrange`` of the padded column: the commitment ``open_all`` / ``open_at`` open.
     f being the column's polynomial, sum_i f(omega^i) = n f(0): the total is one opening of C at 0, user i's balance one at omega^i.
@@ -28,7 +28,7 @@ from .keygen import ProvingKey, VerifyingKey
 from .kzg import g2_from_bytes
 from .openings import _point, _scalar_int, domain_omega, open_all, open_at, verify_opening
 from .pairing import G1_GEN, g1_add, g1_mul, g1_neg, g1_on_curve
-from .prover import create_proof, create_proofs
+from .prover import create_proofs
 from .synthesis import BLINDING_ROWS, range_witness
 from .transcript import TranscriptError, check_encoding, check_multiopen, g1_decompress_int, g1_uncompressed_int
 from .verifier import verify_proof
@@ -64,8 +64,8 @@ def _range_parameters(cs, who: str) -> Tuple[int, int]:
 def prove_balances(params, pk: ProvingKey, balances, seed: int, check: bool = True, encoding: str = "halo2",
                    multiopen: str = "shplonk") -> BalanceProof:
     """``balances``: a (rows, 4) GPU tensor of canonical Montgomery words, one asset, or a (P, rows, 4) stack with one column per asset;
-    rows <= 2^k - 6.  The witness of every asset from ``range_witness``, the range proofs from ``create_proof`` (one asset) or
-    ``create_proofs`` (several; asset p with seed + p), the totals n f(0) with their openings at 0 from ``open_at``.
+    rows <= 2^k - 6.  The witness of every asset from ``range_witness``, the range proofs from ``create_proofs``
+    (asset p with seed + p), the totals n f(0) with their openings at 0 from ``open_at``.
     ``check``: a balance at or above 2^(max_bits * acc_cols) raises ValueError naming the asset and the count; without it the proof
     is made all the same, and does not verify.  ``encoding`` / ``multiopen``: the wire format and the multiopen scheme of the range
     proofs, as ``create_proof`` names them."""
@@ -88,8 +88,7 @@ def prove_balances(params, pk: ProvingKey, balances, seed: int, check: bool = Tr
             if count:
                 raise ValueError(f"{who}: asset {p}: {count} balance(s) at or above 2^{max_bits * acc_cols}")
     empty = [[]]                                             # the instance column holds nothing
-    proofs = ([create_proof(params, pk, advice[0], empty, seed, encoding=encoding, multiopen=multiopen)] if P == 1
-              else create_proofs(params, pk, advice, [empty] * P, seed, encoding=encoding, multiopen=multiopen))
+    proofs = create_proofs(params, pk, advice, [empty] * P, seed, encoding=encoding, multiopen=multiopen)
     columns = advice[:, 0].contiguous()                      # (P, n, 4): rows >= `rows` are zero
     coeffs = EvaluationDomain(2, k).lagrange_to_coeff(columns.clone())
     omega = domain_omega(k)

@@ -15,7 +15,7 @@
     independent proofs in one batched pass -- against the loop of m create_proof calls in the same run (the bytes are compared), and two
     of its steps alone, each against its loop: the h numerator through CompiledGraph.evaluate_proofs against m evaluate calls with
     per-proof constants on the same columns, and the multiopen (shplonk.create_openings inside create_proofs against the m
-    create_opening calls inside the loop, both timed in a second pass of their own).
+    create_opening calls inside the loop, both timed in a second pass of their own; at m = 1 create_proofs too ends in create_opening).
 (e) ``--multiopen shplonk|gwc|both`` (with ``--proofs m[,m...]``, default 1,16,64): instead, the two multiopen schemes side by side
      at depth 5 / k = 9 and depth 20 / k = 10: create_proof (m = 1) or create_proofs (m > 1) wall-clock with
     ``multiopen=`` each scheme, the routes alternating inside every repeat of one session, and in a second pass the multiopen alone
@@ -37,7 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 import halo2_experiments_amd as h                                         # noqa: E402
-from halo2_experiments_amd import circuits, gwc, poseidon as ps, prover, shplonk as sh   # noqa: E402
+from halo2_experiments_amd import circuits, gwc, poseidon as ps, shplonk as sh   # noqa: E402
 from halo2_experiments_amd.domain import FR_MODULUS as R, EvaluationDomain, fr_words   # noqa: E402
 from halo2_experiments_amd.kzg import ParamsKZG                            # noqa: E402
 import prover_cases as pc                                                  # noqa: E402
@@ -64,12 +64,12 @@ def end_to_end(name):
     vk = h.keygen_vk(params, cs, lay)
     pk = h.keygen_pk(params, vk, cs, lay, cosets=False)
     inner = []
-    real = prover.create_opening
+    real = sh.create_opening
 
     def timed(*a, **kw):
         _, ms = wall(lambda: real(*a, **kw))
         inner.append(ms)
-    prover.create_opening = timed
+    sh.create_opening = timed
     try:
         h.create_proof(params, pk, advice, instance, 1)                    # warm-up: program compiles, allocator pools
         inner.clear()
@@ -81,7 +81,7 @@ def end_to_end(name):
             assert ok
             verify.append(ms)
     finally:
-        prover.create_opening = real
+        sh.create_opening = real
         params.release()
     return {"k": lay.k, "proof_bytes": len(proof), "create_proof": spread(prove), "of_which_shplonk": spread(inner), "verify_proof": spread(verify)}
 
@@ -195,7 +195,7 @@ def proofs(name, m):
     batched = lambda rep: h.create_proofs(params, pk, advice, instances, seeds(rep))
     looped = lambda rep: [h.create_proof(params, pk, advice[b], instances[b], seeds(rep)[b]) for b in range(m)]
     inner = []
-    real_one, real_many = prover.create_opening, prover.create_openings
+    real_one, real_many = sh.create_opening, sh.create_openings
 
     def timed(real):
         def run(*a, **kw):
@@ -212,7 +212,7 @@ def proofs(name, m):
         ok, verify_ms = wall(lambda: h.verify_proofs(params, vk, instances, out))
         assert ok
         # the multiopen alone, in a pass of its own: the synchronisation around it would count against the totals above
-        prover.create_opening, prover.create_openings = timed(real_one), timed(real_many)
+        sh.create_opening, sh.create_openings = timed(real_one), timed(real_many)
         open_batched, open_looped = [], []
         for rep in range(REPEATS):
             inner.clear()
@@ -227,7 +227,7 @@ def proofs(name, m):
                "multiopen": {"create_openings": spread(open_batched), "loop_of_create_opening": spread(open_looped)},
                "h_step": h_step_proofs(cs, vk.domain, m)}
     finally:
-        prover.create_opening, prover.create_openings = real_one, real_many
+        sh.create_opening, sh.create_openings = real_one, real_many
         params.release()
     return res
 
@@ -316,7 +316,7 @@ def schemes(name, m, multiopens):
     vk = h.keygen_vk(params, cs, lay)
     pk = h.keygen_pk(params, vk, cs, lay, cosets=False)
     entry = "create_opening" if m == 1 else "create_openings"
-    where = {"shplonk": prover, "gwc": gwc}                       # the module whose attribute the prover calls for the scheme
+    where = {"shplonk": sh, "gwc": gwc}                       # the module whose attribute the prover calls for the scheme
     real = {mo: getattr(where[mo], entry) for mo in multiopens}
     inner = []
 
