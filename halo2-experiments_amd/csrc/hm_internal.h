@@ -199,6 +199,14 @@ struct MsmSlot {            // one in-flight MSM: its workspace, events and host
   uint64_t T_max = 0;
   bool balanced = false;             // windows of unequal widths (msm_small.hip): the host fold shifts by win_bits[w]
   uint8_t win_bits[128] = {};
+  // what msm_finish needs to know of the chain being enqueued: `records` window sums (or one-bit records) per element behind 4 totals
+  // words, `stride` words apart, at d_totals; the caller fills win_bits where `balanced_`
+  void describe(uint32_t records, uint32_t c_, uint32_t W_, uint32_t group_, uint32_t stride, uint64_t T_max_, const uint32_t* d_totals,
+                bool balanced_, bool timed) {
+    SW = records, c = c_, W = W_, group = group_, res_stride = stride, T_max = T_max_;
+    d_tot = d_totals, d_win = d_totals + 4;
+    balanced = balanced_, phase_timed = timed;
+  }
 };
 
 // Transient device state of the stream-asynchronous entry points (NTT ping-pong buffer, fixed-base
@@ -535,10 +543,7 @@ int msm_finish_wait_fold(MsmSlot& sl, uint64_t* out_jac_ext /* 12 words per MSM 
 void msm_finish_record(DeviceCtx& ctx, int slot, double host_us);
 bool msm_phase_timing(bool small_plan);    // hm_msm_set_phase_timing: -1 auto (general pipeline only), 0 never, 1 always
 int msm_slot_prepare(MsmSlot& sl);   // events + pinned landing zone, on first use
-int msm_launch_digits(const uint32_t* d_scalars_ext, const uint8_t* d_inf, int32_t* d_digits, size_t n, uint32_t c, uint32_t W,
-                      hipStream_t stream);
 // msm_small.hip: the five-launch chain for n < 2^19 (plain base sets, c <= 15)
-bool msm_small_applies(size_t n, uint32_t c, bool single_set);
 int msm_issue_small(DeviceCtx& ctx, int slot, const uint32_t* const* d_scalars_list, uint32_t group, const uint32_t* d_xy,
                     const uint8_t* d_inf, size_t n, uint32_t c, hipStream_t stream);
 // live_out[i] = how many 256-row blocks of column i hold a row that survives the digits kernel's compaction (a non-zero

@@ -8,6 +8,9 @@
 //
 // Build: g++ -O2 -std=c++17 -DHM_BOUNDS -shared -fPIC -o libhm_hostcheck.so host_check.cpp
 #include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
 #include <cstring>
 #include <utility>
 #include <vector>
@@ -33,6 +36,7 @@ namespace hm {
 #include "pairing.inc"    // the pairing's tower, Miller lane and final exponentiation (pairing.hip)
 #include "transcript.inc" // Blake2b-512, its streaming absorber and the transcript lane of a proof (verify.hip)
 #include "keccak.inc"     // Keccak-256, the EVM encoding's read and the transcript lane of such a proof (verify.hip)
+#include "msm_plan.inc"   // the MSM's window choice, launch plans and workspace layouts (msm.hip, msm_small.hip)
 }
 
 using namespace hm;
@@ -1272,6 +1276,74 @@ int hc_pairing_product(const uint64_t* g1, const uint64_t* g2, size_t n_pairs, u
   const uint32_t status = pf_finish_lane(0, n_pairs, n_pairs, PfLane{pair_ws.data(), n_pairs}, flags.data(), PfLane{check_ws.data(), 1}, w);
   std::memcpy(gt, w, sizeof w);
   return (int)status;
+}
+
+// The MSM's host side (msm_plan.inc).  knobs: window override, then the three switches (-1 unset, 0, 1).
+namespace {
+MsmKnobs msm_knobs_from(const int64_t* k) {
+  MsmKnobs r;
+  r.window_override = (int)k[0];
+  r.digits_count = (int)k[1];
+  r.k3b_copy = (int)k[2];
+  r.k4_wave_sums = (int)k[3];
+  return r;
+}
+}  // namespace
+
+// out[0] = msm_window, out[1] = the five-launch chain's window (0: it does not apply), out[2] = msm_precomp_window(n),
+// out[3] = msm_table_group_max(n, precomp_c)
+void hc_msm_window(uint64_t n, uint32_t precomp_c, uint64_t live_rows, const int64_t* knobs, uint64_t* out) {
+  const MsmKnobs k = msm_knobs_from(knobs);
+  out[0] = msm_window((size_t)n, precomp_c, (size_t)live_rows, k);
+  out[1] = plan_small_window((size_t)n, precomp_c, (size_t)live_rows, k);
+  out[2] = plan_precomp_window((size_t)n);
+  out[3] = plan_table_group_max((size_t)n, precomp_c);
+}
+
+// msm_plan as flat u64: HC_MSM_SCALARS scalars in the order of tests/test_msm_plan_host.py's PLAN_FIELDS, then (offset, bytes) of
+// every region, then (gx, gy, block, lds, lds_cap) of every launch.  Returns the plan's error code.
+int hc_msm_plan(uint64_t n, uint32_t group, uint32_t precomp_c, const int64_t* knobs, uint64_t* out, uint32_t* counts) {
+  const MsmPlan p = msm_plan((size_t)n, group, precomp_c, msm_knobs_from(knobs));
+  const uint64_t scalars[] = {
+      (uint64_t)p.route, p.single_set, p.group, p.c, p.W, p.n_wide, p.SW, p.sn, p.NB, p.NBP, p.NBT, p.pairs_max, p.L, p.G, p.chunk, p.T_max,
+      p.SEG, p.nseg, p.k4_m, p.k4_h, p.RW, p.res_stride, p.ib, p.fb, p.cb, p.NC, p.ps_G, p.ps_gpc, p.ps_nsc, p.sbits, p.br_big, p.br_slice,
+      p.br_capacity, p.coop_sort, p.direct_buckets, (uint64_t)p.digits, (uint64_t)p.first_level, (uint64_t)p.p1_scatter,
+      (uint64_t)p.p2_scatter, (uint64_t)p.item, (uint64_t)p.tasks, (uint64_t)p.reduction, p.sum_levels, p.sum_count[0], p.sum_count[1],
+      0, 0, p.region[MR_RES].bytes, p.ws_bytes};      // (two retired columns: the levels of segment sums a plan never had)
+  const uint32_t ns = (uint32_t)(sizeof scalars / sizeof scalars[0]);
+  counts[0] = ns, counts[1] = MR_COUNT, counts[2] = ML_COUNT + 2;
+  uint64_t* o = out;
+  for (uint32_t i = 0; i < ns; ++i) *o++ = scalars[i];
+  for (uint32_t r = 0; r < MR_COUNT; ++r) *o++ = p.region[r].off, *o++ = p.region[r].bytes;
+  for (uint32_t l = 0; l < ML_COUNT; ++l) {
+    if (l == ML_TO_EXT)      // the rows keep the two launch slots of those levels, never made
+      for (int k = 0; k < 2; ++k) *o++ = 0, *o++ = 1, *o++ = 0, *o++ = 0, *o++ = MSM_LDS_DEFAULT;
+    const MsmLaunch& q = p.launch[l];
+    *o++ = q.gx, *o++ = q.gy, *o++ = q.block, *o++ = q.lds, *o++ = q.lds_cap;
+  }
+  return p.err;
+}
+
+// msm_small_plan the same way: scalars in the order of SMALL_FIELDS, the regions, then (gx, gy, gz) of the five launches
+int hc_msm_small_plan(uint64_t n, uint32_t group, uint32_t c, uint64_t* out, uint32_t* counts) {
+  const MsmSmallPlan p = msm_small_plan((size_t)n, group, c);
+  const uint64_t scalars[] = {p.group, p.W,   p.wide, p.n_wide, p.NB,    p.pairs_max, p.H,         p.NBh,        p.V,        p.L,
+                              p.SEG,   p.nseg, p.G1n,  p.T_max,  p.ws_stride, p.res_stride, p.ws_bytes, p.launch[MSL_SORT].lds, p.launch[MSL_SORT].lds_cap};
+  const uint32_t ns = (uint32_t)(sizeof scalars / sizeof scalars[0]);
+  counts[0] = ns, counts[1] = MSR_COUNT, counts[2] = MSL_COUNT;
+  uint64_t* o = out;
+  for (uint32_t i = 0; i < ns; ++i) *o++ = scalars[i];
+  for (uint32_t r = 0; r < MSR_COUNT; ++r) *o++ = p.region[r].off, *o++ = p.region[r].bytes;
+  for (uint32_t l = 0; l < MSL_COUNT; ++l) *o++ = p.launch[l].gx, *o++ = p.launch[l].gy, *o++ = p.launch[l].gz;
+  return p.err;
+}
+
+// the constants the plan shares with the kernels, for the test's own formulas
+void hc_msm_constants(uint64_t* out) {
+  const uint64_t v[] = {PT_WORDS, ACC_THREADS, WIN_THREADS, TARGET_TASKS, SORT_THREADS, P1_IPT_DEFAULT, P1_BIG_IPT, P2_TILE, PS_MAX_SC, SCAN_BLOCK,
+                        TASK_KEYS, FINALIZE_SERIAL, FINALIZE_SLICE, SUM_SPAN, SA_THREADS, S_TASK_KEYS, S_MAX_L, MSM_GROUP_MAX, MSM_LDS_DEFAULT,
+                        MSM_LDS_FINE, MSM_LDS_ALL};
+  for (size_t i = 0; i < sizeof v / sizeof v[0]; ++i) out[i] = v[i];
 }
 
 }  // extern "C"

@@ -78,10 +78,7 @@ __global__ void msm_convert_bases_kernel(const uint32_t* __restrict__ ext, uint3
 // first sort level counts the pairs that really exist, and when they are far fewer (zero or repeated
 // digits: flag and selector-like columns) every later kernel derives the same shorter L from that
 // count, so that K3 still gets >= TARGET_TASKS chains to fill the chip with.
-#ifndef HM_TARGET_TASKS      // measurement knob (tools/ab_build.sh)
-#define HM_TARGET_TASKS 327680
-#endif
-constexpr uint32_t TARGET_TASKS = HM_TARGET_TASKS;   // 256 CUs x 4 SIMDs x 5 waves x 64 lanes
+// (TARGET_TASKS and every other size the host plan shares with these kernels: msm_plan.inc)
 __device__ __forceinline__ uint32_t effective_task_len(const uint32_t* __restrict__ pairs, uint32_t L_host) {
   if (pairs == nullptr) return L_host;
   const uint32_t by_fill = pairs[0] / TARGET_TASKS;
@@ -151,8 +148,6 @@ __device__ __forceinline__ void msm_digits_point(const uint4 lo, const uint4 hi,
 // nothing to zero first.  At 2^24 points that is one workgroup of 1024 lanes per CU; every lane requests its next scalar
 // before it works on the current one, which keeps the loads in flight that the short-lived workgroups of the plain form
 // get from their number.  The host launches this form only where n is a multiple of the chunk.
-constexpr int DIGITS_THREADS = 256;
-constexpr int DIGITS_COUNT_THREADS = 1024;
 template <bool COUNT>
 __global__ __launch_bounds__(COUNT ? DIGITS_COUNT_THREADS : DIGITS_THREADS) void msm_digits_kernel(
     MsmGroupScalars list, const uint8_t* __restrict__ inf, int32_t* __restrict__ digits, size_t n, uint32_t c, uint32_t W,
@@ -219,10 +214,6 @@ __global__ __launch_bounds__(COUNT ? DIGITS_COUNT_THREADS : DIGITS_THREADS) void
 // When fine bits + sign + index bits fit 32 bits with cb = 0 (n <= 2^19) part 1 disappears and
 // part 2 reads the digits directly.
 // ---------------------------------------------------------------------------------------------
-#ifndef HM_SORT_THREADS
-#define HM_SORT_THREADS 1024
-#endif
-constexpr int SORT_THREADS = HM_SORT_THREADS;
 
 // Apply f(index, word) to base[lo .. hi) with the whole workgroup, 16 bytes per lane per load:
 // one 4-byte load in flight per lane keeps only ~1 MB outstanding chip-wide (latency-bound at
@@ -346,24 +337,18 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_part1_scatter_kernel(const i
 
 // part 1 scatter, tiled form: the chunk is processed in tiles of 4096 digits that are first
 // counting-sorted by coarse bin inside LDS, so that consecutive lanes append to the same coarse run
-// (sector-complete stores, as in the tiled part-2 scatter below).  Used while NC <= 4096.
-#ifndef HM_P1_IPT
-#define HM_P1_IPT 4
-#endif
-constexpr int P1_IPT_DEFAULT = HM_P1_IPT;
-#ifndef HM_P1_BIG_IPT        // tiles for 512 .. 2048 coarse bins (the shared-bucket-set plan, the plain layout from 2^21 points).
-#define HM_P1_BIG_IPT 16     // Measured at 2^24 on the table, whole sort: 8 items per lane 3.19 ms, 16 (with part 2's 16) 3.00 ms --
-#endif                       // 16 items = a 64-byte run per coarse bin and tile instead of 32 (140 KiB of LDS, one workgroup per CU)
-constexpr int P1_BIG_IPT = HM_P1_BIG_IPT;
-// P1_IPT items per lane and tile: a tile should bring >= 8 items (one 32-byte sector) to every coarse bin, i.e.
-// 4 096 items for <= 512 bins and 8 192 for 1 024 (the shared-bucket-set plan)
-template <class ITEM, int P1_IPT = P1_IPT_DEFAULT>
+// (sector-complete stores, as in the tiled part-2 scatter below).  Used while NC <= 4096, for 64-bit items only: 32-bit items
+// take the vector-load form (msm_part1_scatter_v2_kernel), which alone has the big tiles of P1_BIG_IPT items per lane.
+// P1_IPT items per lane and tile: a tile should bring >= 8 items (one 32-byte sector) to every coarse bin
+template <class ITEM>
 __global__ __launch_bounds__(SORT_THREADS) void msm_part1_scatter_tiled_kernel(const int32_t* __restrict__ digits,
                                                                                const uint32_t* __restrict__ chist,
                                                                                const uint32_t* __restrict__ cstart,
                                                                                ITEM* __restrict__ tmp, size_t n, size_t chunk,
                                                                                uint32_t fb, uint32_t ib, uint32_t NC) {
+  static_assert(sizeof(ITEM) == 8, "no plan selects the tiled first-level scatter for 32-bit items");
   extern __shared__ uint32_t sm[];
+  constexpr int P1_IPT = P1_IPT_DEFAULT;
   constexpr int P1_TILE = SORT_THREADS * P1_IPT;
   const uint32_t g = blockIdx.x, w = blockIdx.y, G = gridDim.x, tid = threadIdx.x;
   uint32_t* gcur = sm;                 // global cursor of every coarse bin for this chunk
@@ -549,12 +534,7 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_part2_scatter_kernel(const I
 // consecutive addresses of a bucket run -- every 32-byte sector of the final array is written by one
 // wave instruction (or two adjacent tiles) instead of by eight separate 4-byte stores spread over the
 // workgroup's lifetime, which is what kept missing L2 once a region had more than ~128 runs.
-#ifndef HM_P2_IPT
-#define HM_P2_IPT 16         // 16 384-item tiles (8: +0.06 ms, 4: +0.35 ms of sort at 2^24)
-#endif
-constexpr int P2_IPT = HM_P2_IPT;
-constexpr int P2_TILE = SORT_THREADS * P2_IPT;
-// LDS of the tiled kernels at their largest plans (part 2: fb = 12; part 1's big tiles: 2 048 coarse bins, 4-byte items):
+// LDS of the tiled and vector-load kernels at their largest plans (part 2: fb = 12; part 1's big tiles: 2 048 coarse bins, 4-byte items):
 // gfx950 has 160 KiB per workgroup
 static_assert(((size_t)3 * 4096 + 32 + P2_TILE) * 4 + (size_t)P2_TILE * 2 <= 160 * 1024, "part-2 tile does not fit the LDS");
 static_assert(((size_t)3 * 2048 + 32 + SORT_THREADS * P1_BIG_IPT) * 4 + (size_t)SORT_THREADS * P1_BIG_IPT * 4 <= 160 * 1024,
@@ -567,7 +547,8 @@ static_assert(((size_t)3 * 2048 + 32 + SORT_THREADS * P1_BIG_IPT) * 4 + (size_t)
 // super-chunk of an item follows from its POSITION in the region: the boundaries are the (already scanned) per-chunk
 // offsets chist[g * NC + bin] at g = 0, gpc, 2 gpc, ...  They go to LDS (at most PS_MAX_SC + 1 words) and every item
 // finds its piece by a binary search.  Half the bytes of the 64-bit items this replaces, at every level of the sort.
-constexpr uint32_t PS_MAX_SC = 1024;
+// Positional items are 32-bit: msm_part2_scatter_v2_kernel places them; the tiled kernel below serves 64-bit items, which carry
+// their whole index.
 struct Positional {
   const uint32_t* chist;    // scanned per-chunk offsets: [set][g][NC] (a shared bucket set is one "window"; a group of MSMs has one set each)
   uint32_t G, gpc, nsc;     // chunks, chunks per super-chunk, super-chunks (0: items carry their whole index)
@@ -580,9 +561,9 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_part2_scatter_tiled_kernel(c
                                                                                uint32_t ib, uint32_t NC, uint32_t NBP, uint32_t big,
                                                                                uint32_t slice, const uint2* __restrict__ list,
                                                                                const uint32_t* __restrict__ list_count,
-                                                                               uint32_t* __restrict__ gcursor, Positional ps) {
+                                                                               uint32_t* __restrict__ gcursor) {
+  static_assert(sizeof(ITEM) == 8, "no plan selects the tiled second-level scatter for 32-bit items");
   extern __shared__ uint32_t sm[];
-  __shared__ uint32_t sc_start[PS_MAX_SC + 1];
   uint32_t hb = blockIdx.x, w = blockIdx.y, sl = 0;
   const uint32_t tid = threadIdx.x;
   if (COOP) {
@@ -606,12 +587,6 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_part2_scatter_tiled_kernel(c
   for (uint32_t b = tid; b < NF; b += SORT_THREADS) { gcur[b] = bo[b]; tcnt[b] = 0; }
   __syncthreads();
   uint32_t lo = cstart[w * NC + hb], hi = cstart[w * NC + hb + 1];
-  const uint32_t region_lo = lo;
-  if (ps.nsc) {                                        // region-relative start of every super-chunk's runs
-    for (uint32_t sc = tid; sc <= ps.nsc; sc += SORT_THREADS)
-      sc_start[sc] = sc < ps.nsc ? ps.chist[((size_t)w * ps.G + (size_t)sc * ps.gpc) * NC + hb] : hi - lo;
-    __syncthreads();
-  }
   if (COOP) {
     lo += sl * slice;
     hi = lo + slice < hi ? lo + slice : hi;
@@ -621,16 +596,6 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_part2_scatter_tiled_kernel(c
   for (uint32_t t0 = lo; t0 < hi; t0 += P2_TILE) {
     const uint32_t tile_n = hi - t0 < (uint32_t)P2_TILE ? hi - t0 : (uint32_t)P2_TILE;
     uint32_t pay[P2_IPT], bin[P2_IPT], rank[P2_IPT];
-    uint32_t sc_tile = 0;
-    if (ps.nsc) {                                      // super-chunk of the tile's first position (the same words for every lane:
-      const uint32_t pos0 = t0 - region_lo;            // broadcast LDS reads); a tile of 4 096 positions crosses few boundaries
-      uint32_t a = 0, b = ps.nsc;                      // invariant: sc_start[a] <= pos0 < sc_start[b]
-      while (b - a > 1) {
-        const uint32_t m = (a + b) >> 1;
-        if (sc_start[m] <= pos0) a = m; else b = m;
-      }
-      sc_tile = a;
-    }
 #pragma unroll
     for (int k = 0; k < P2_IPT; ++k) {
       const uint32_t e = (uint32_t)k * SORT_THREADS + tid;
@@ -638,12 +603,6 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_part2_scatter_tiled_kernel(c
         const ITEM item = tmp[t0 + e];
         bin[k] = (uint32_t)(item >> (ib + 1));
         pay[k] = (uint32_t)(item & imask) | ((uint32_t)((item >> ib) & 1) << 31);
-        if (ps.nsc) {                                  // the largest sc with sc_start[sc] <= position: a few steps from the tile's
-          const uint32_t pos = t0 + e - region_lo;
-          uint32_t a = sc_tile;
-          while (sc_start[a + 1] <= pos) ++a;          // (pos < sc_start[nsc] = the region's size: the walk ends)
-          pay[k] |= a << ib;
-        }
         rank[k] = lds_inc(tcnt, bin[k]);
       }
     }
@@ -1074,9 +1033,6 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_part2_scatter_v2_kernel(cons
 
 // bucket offsets (exclusive scan of counts) and task offsets (exclusive scan of ceil(count / L)):
 // three small launches -- per-block sums, a one-block scan of those, per-block rescan + offset.
-constexpr int SCAN_THREADS = 256;
-constexpr int SCAN_ITEMS = 8;                       // items per lane; a block covers 2048 buckets
-constexpr int SCAN_BLOCK = SCAN_THREADS * SCAN_ITEMS;
 
 __device__ __forceinline__ void block_scan_pair(uint32_t& p, uint32_t& t, uint32_t* s_p, uint32_t* s_t) {
   // inclusive scan over the block of (p, t); returns inclusive values in p, t
@@ -1197,9 +1153,6 @@ __global__ void msm_task_fill_kernel(const uint32_t* __restrict__ toff, uint32_t
 // by length (1024 keys, descending) puts equal-length chains side by side, and starting with the longest
 // also shortens the tail of the launch.  Only the ORDER of execution changes: task t still owns
 // partial[t], so nothing downstream depends on the (atomic, run-to-run varying) order within one key.
-constexpr uint32_t TASK_KEYS = 1024;
-constexpr int ORDER_THREADS = 1024;   // == TASK_KEYS: one LDS counter per lane
-constexpr int ORDER_ITEMS = 4;        // buckets per lane
 constexpr uint32_t ORDER_HOT = 32;    // hot buckets a workgroup fills cooperatively (more fall back to their lane)
 
 __device__ __forceinline__ uint32_t task_key(uint32_t len, uint32_t L) {   // len in [1, L]; key 0 = longest
@@ -1356,8 +1309,6 @@ __global__ __launch_bounds__(ACC_THREADS) HM_K3_OCC void msm_accumulate_kernel(c
 // `multi_only`: the reduction reads a one-task bucket straight from its partial and an empty one as the identity
 // (load_bucket_value), so only buckets with two or more partials are summed and stored here: for uniform scalars a task
 // is a bucket, and the pass would otherwise copy 112 B in and 112 B out for every one of them.
-constexpr uint32_t FINALIZE_SERIAL = 8;
-constexpr uint32_t FINALIZE_SLICE = 2048;   // partials one workgroup sums in the first level of a very hot bucket
 __global__ __launch_bounds__(ACC_THREADS) void msm_bucket_finalize_kernel(const uint32_t* __restrict__ partial,
                                                                           const uint32_t* __restrict__ toff,
                                                                           uint32_t* __restrict__ bucket, uint32_t NBT,
@@ -1491,10 +1442,6 @@ __global__ __launch_bounds__(ACC_THREADS) void msm_reduce_segments_kernel(const 
 
 // K4b: sum `count` points per window down to ceil(count / SUM_SPAN) (one workgroup per span: strided
 // serial sums then an LDS tree); applied until one point per window is left.
-#ifndef HM_SUM_PER_LANE
-#define HM_SUM_PER_LANE 4     // measured: 4 beats 16 by 0.06-0.07 ms at every size (more workgroups, shorter serial sums)
-#endif
-constexpr uint32_t SUM_SPAN = WIN_THREADS * HM_SUM_PER_LANE;
 __global__ __launch_bounds__(WIN_THREADS) void msm_sum_points_kernel(const uint32_t* __restrict__ in, uint32_t count,
                                                                      uint32_t* __restrict__ out, uint32_t out_count) {
   __shared__ uint32_t tree[WIN_THREADS * PT_WORDS];
@@ -1553,7 +1500,6 @@ __global__ __launch_bounds__(WIN_THREADS) void msm_reduce_rowcol_kernel(const ui
 //                            hi = l, l + 32, ... then a 5-level tree inside the half.
 // Wave-additions issued at c = 22 (M = 2048, H = 1024): rows 1024 x (32 + 6), column pairs 1024 x (32 + 5) = 76 800 for
 // 2 x 2^21 / 64 = 65 536 useful: 1.17 x (the workgroup form: (4 x 8 + 9) x 1024 + (4 x 4 + 9) x 2048 = 93 184, 1.42 x).
-constexpr int WAVE_THREADS = 64;
 // acc += q, field by field: g1_add's `return p` / `return q` copy whole records, and with them the three padding bytes behind
 // the identity flag, which this kernel's loop then carries through a stack slot (12 bytes of scratch for nothing)
 __device__ __forceinline__ void jac_set(G1Jac& d, const G1Jac& s) {
@@ -1836,12 +1782,6 @@ int msm_convert_bases(const uint32_t* d_bases_ext, uint32_t* d_xy, uint8_t* d_in
   return HM_OK;
 }
 
-static uint32_t ilog2(size_t n) {
-  uint32_t l = 0;
-  while ((n >> (l + 1)) != 0) ++l;
-  return l;
-}
-
 // host-side Horner over the window sums and affine normalisation (host_fq.h: native 4 x u64
 // arithmetic on the external-format words the reduction kernel wrote)
 // result = sum_w 2^(offset of window w) * S_w: Horner from the top window, shifting by the width of window w
@@ -1888,34 +1828,23 @@ bool msm_phase_timing(bool small_plan) {
 }
 void msm_set_window_override(int c) { g_window_override.store(c, std::memory_order_relaxed); }
 
-// Window size for a precomputed (single bucket set) base set of n points: minimise
-// n * W(c) mixed additions + ~3 * 2^(c-1) addition-equivalents of bucket reduction.
-// The 255 digit bits over W windows as evenly as possible: windows [0, n_wide) are `wide` bits, the others wide - 1.
-// (W - 1 full windows and a short top one would send every point's top digit into the lowest 2^(short - 1) buckets:
-// at 2^24 points, c = 22, 4 096 buckets with 4 192 points each beside a mean of 96.)
-static void balanced_windows(uint32_t W, uint32_t* wide, uint32_t* n_wide) {
-  const uint32_t base = 255 / W, rest = 255 - base * W;
-  *wide = rest ? base + 1 : base;
-  *n_wide = rest ? rest : W;
+// The one reader of what a call is told from outside (msm_plan.inc: MsmKnobs): the window override and the three switches the
+// tests use as their reference arm -- read at every call, so that one process can run both arms.
+static MsmKnobs msm_read_knobs(bool window_only = false) {
+  const auto tri = [](const char* name) {
+    const char* v = std::getenv(name);
+    return v && *v ? (*v == '1' ? 1 : 0) : -1;
+  };
+  MsmKnobs k;
+  k.window_override = g_window_override.load(std::memory_order_relaxed);
+  if (window_only) return k;                      // the window queries of the prover's small path: no environment read
+  k.digits_count = tri("HALO2_MI355X_DIGITS_COUNT");
+  k.k3b_copy = tri("HALO2_MI355X_K3B_COPY");
+  k.k4_wave_sums = tri("HALO2_MI355X_K4_WAVE_SUMS");
+  return k;
 }
 
-uint32_t msm_precomp_window(size_t n) {
-  uint32_t best = 8;
-  double best_cost = 1e300;
-  // (capped at 22: the model knows additions only.  Measured at 2^25 / 2^26, c = 24 against 22: K3 26.6 / 51.4 against
-  // 28.6 / 56.0 ms, but the sort 8.8 / 16.6 against 6.0 / 12.0 -- 2^23 buckets need 4 096 coarse bins, two items per bin
-  // and first-level tile -- and the bucket reduction 2.8 against 1.3: whole MSM 39.2 / 72.2 against 36.5 / 70.5 ms)
-  for (uint32_t c = 8; c <= 22; ++c) {
-    const double W = (double)((255 + c - 1) / c);
-    const double cost = (double)n * W + 3.0 * (double)(1ull << (c - 1));
-    if (cost < best_cost) { best_cost = cost; best = c; }
-  }
-  static const int forced = [] { const char* v = std::getenv("HALO2_MI355X_PRECOMP_C"); return v && *v ? std::atoi(v) : 0; }();   // experiments
-  if (forced >= 8 && forced <= 24) best = (uint32_t)forced;
-  uint32_t wide, n_wide;
-  balanced_windows((255 + best - 1) / best, &wide, &n_wide);     // the widest window of the balanced split (<= best)
-  return wide;
-}
+uint32_t msm_precomp_window(size_t n) { return plan_precomp_window(n); }
 
 int msm_precompute(uint32_t* d_table, const uint8_t* d_inf, size_t n, uint32_t c, uint32_t W, hipStream_t stream) {
   if (n == 0 || W <= 1) return HM_OK;
@@ -1945,117 +1874,68 @@ int msm_precompute(uint32_t* d_table, const uint8_t* d_inf, size_t n, uint32_t c
   return HM_OK;
 }
 
-// HALO2_MI355X_SORT_V1=1: the round-1..3 tiled scatters (one 4-byte load per item) instead of the vector-load form (A/B)
-static bool sort_v1() {
-  static const bool v = [] { const char* e = std::getenv("HALO2_MI355X_SORT_V1"); return e && *e == '1'; }();
-  return v;
-}
+static_assert(MSM_GROUP_MAX == HM_MSM_GROUP, "msm_plan.inc and hm_internal.h disagree about the group size");
 
-struct BigRegionPlan {      // cooperative handling of sort regions that hold far more than their share
-  uint32_t big = 0;         // regions above this many items are split
-  uint32_t slice = 0;       // ... into slices of this many items, one workgroup each
-  uint32_t capacity = 0;    // entries of the work list
-  uint2* list = nullptr;
-  uint32_t* count = nullptr;
-  uint32_t* gcursor = nullptr;   // copy of boff: global per-bucket cursors of the cooperative scatter
+struct MsmWorkspace {       // a slot's workspace under a plan's region table
+  uint8_t* base;
+  const MsmPlan& p;
+  template <class T = uint32_t> T* at(MsmRegion r) const { return (T*)(base + p.region[r].off); }
 };
 
+// The first sort level (where the plan has one) and the bucket counts; regions far above their share go to the cooperative
+// kernels.  64-bit items exist in ONE combination (tests/test_msm_plan_host.py): a first level by histogram, both tiled scatters.
 template <class ITEM>
-static int launch_sort(const int32_t* d_digits, uint32_t* d_chist, uint32_t* d_ctot, uint32_t* d_cstart, void* d_tmp,
-                       uint32_t* d_bcnt, size_t sn, size_t chunk, uint32_t G, uint32_t SW, uint32_t fb, uint32_t ib, uint32_t cb,
-                       uint32_t NC, uint32_t NBP, const BigRegionPlan& br, bool counted, hipStream_t stream) {
-  const size_t lds_fine = (size_t)4 << fb;
-  if (cb) {
-    const size_t lds_coarse = (size_t)NC * 4;
-    if (!counted)      // else the digits kernel left the coarse-bin counts behind (msm_digits_kernel<true>)
-      hipLaunchKernelGGL(msm_part1_hist_kernel, dim3(G, SW), dim3(SORT_THREADS), lds_coarse, stream, d_digits, d_chist, sn, chunk,
-                         fb, NC);
-    hipLaunchKernelGGL(msm_part1_scan_kernel, dim3(SW * NC), dim3(64), 0, stream, d_chist, d_ctot, G, NC, SW);
-    hipLaunchKernelGGL(msm_part1_starts_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t*)d_ctot, d_cstart, SW * NC);
-    static const bool big_tiles = [] { const char* v = std::getenv("HALO2_MI355X_P1_BIG_TILES"); return !(v && *v == '0'); }();
-    static const uint32_t p1_big_from = [] { const char* v = std::getenv("HALO2_MI355X_P1_BIG_FROM"); return (uint32_t)(v && *v ? std::atoi(v) : 512); }();
-    if (sizeof(ITEM) == 4 && NC <= 4096 && !sort_v1()) {      // the vector-load form (32-bit items)
-      if (NC >= (p1_big_from) && NC <= 2048 && big_tiles) {
-        constexpr int TILE = SORT_THREADS * P1_BIG_IPT;
-        hipLaunchKernelGGL((msm_part1_scatter_v2_kernel<P1_BIG_IPT>), dim3(G, SW), dim3(SORT_THREADS), ((size_t)3 * NC + 32 + 2 * TILE) * 4, stream,
-                           d_digits, (const uint32_t*)d_chist, (const uint32_t*)d_cstart, (uint32_t*)d_tmp, sn, chunk, fb, ib, NC);
-      } else {
-        constexpr int TILE = SORT_THREADS * P1_IPT_DEFAULT;
-        hipLaunchKernelGGL((msm_part1_scatter_v2_kernel<P1_IPT_DEFAULT>), dim3(G, SW), dim3(SORT_THREADS), ((size_t)3 * NC + 32 + 2 * TILE) * 4,
-                           stream, d_digits, (const uint32_t*)d_chist, (const uint32_t*)d_cstart, (uint32_t*)d_tmp, sn, chunk, fb, ib, NC);
-      }
-    } else if (NC >= (p1_big_from) && NC <= 2048 && sizeof(ITEM) == 4 && big_tiles) {
-      constexpr int TILE = SORT_THREADS * P1_BIG_IPT;
-      const size_t lds_p1 = ((size_t)3 * NC + 32 + TILE) * 4 + (size_t)TILE * sizeof(ITEM);
-      hipLaunchKernelGGL((msm_part1_scatter_tiled_kernel<ITEM, P1_BIG_IPT>), dim3(G, SW), dim3(SORT_THREADS), lds_p1, stream, d_digits,
-                         (const uint32_t*)d_chist, (const uint32_t*)d_cstart, (ITEM*)d_tmp, sn, chunk, fb, ib, NC);
-    } else if (NC <= 4096) {
-      constexpr int TILE = SORT_THREADS * P1_IPT_DEFAULT;
-      const size_t lds_p1 = ((size_t)3 * NC + 32 + TILE) * 4 + (size_t)TILE * sizeof(ITEM);
-      hipLaunchKernelGGL((msm_part1_scatter_tiled_kernel<ITEM, P1_IPT_DEFAULT>), dim3(G, SW), dim3(SORT_THREADS), lds_p1, stream, d_digits,
-                         (const uint32_t*)d_chist, (const uint32_t*)d_cstart, (ITEM*)d_tmp, sn, chunk, fb, ib, NC);
-    } else {
-      hipLaunchKernelGGL(msm_part1_scatter_kernel<ITEM>, dim3(G, SW), dim3(SORT_THREADS), lds_coarse, stream, d_digits,
-                         (const uint32_t*)d_chist, (const uint32_t*)d_cstart, (ITEM*)d_tmp, sn, chunk, fb, ib, NC);
-    }
-    // regions far above their share go to the cooperative kernels: list them, then count in both forms
-    hipLaunchKernelGGL(msm_big_regions_kernel, dim3((SW * NC + 255) / 256), dim3(256), 0, stream, (const uint32_t*)d_cstart,
-                       SW * NC, br.big, br.slice, br.list, br.count, br.capacity);
-    hipLaunchKernelGGL((msm_part2_hist_kernel<false, ITEM, false>), dim3(NC, SW), dim3(SORT_THREADS), lds_fine, stream,
-                       (const ITEM*)d_tmp, d_digits, (const uint32_t*)d_cstart, d_bcnt, sn, fb, ib, NC, NBP, br.big, br.slice,
-                       (const uint2*)br.list, (const uint32_t*)br.count);
-    hipLaunchKernelGGL((msm_part2_hist_kernel<false, ITEM, true>), dim3(br.capacity), dim3(SORT_THREADS), lds_fine, stream,
-                       (const ITEM*)d_tmp, d_digits, (const uint32_t*)d_cstart, d_bcnt, sn, fb, ib, NC, NBP, br.big, br.slice,
-                       (const uint2*)br.list, (const uint32_t*)br.count);
-  } else {
-    hipLaunchKernelGGL((msm_part2_hist_kernel<true, ITEM, false>), dim3(1, SW), dim3(SORT_THREADS), lds_fine, stream,
-                       (const ITEM*)d_tmp, d_digits, (const uint32_t*)d_cstart, d_bcnt, sn, fb, ib, NC, NBP, 0xffffffffu, 0u,
-                       (const uint2*)nullptr, (const uint32_t*)nullptr);
+static void launch_sort(const MsmPlan& p, const MsmWorkspace& w, hipStream_t stream) {
+  const MsmLaunch* const l = p.launch;
+  int32_t* digits = w.at<int32_t>(MR_DIGITS);
+  uint32_t *chist = w.at(MR_CHIST), *ctot = w.at(MR_CTOT), *cstart = w.at(MR_CSTART), *bcnt = w.at(MR_BCNT), *brcount = w.at(MR_BRCOUNT);
+  ITEM* tmp = w.at<ITEM>(MR_TMP);
+  uint2* brlist = w.at<uint2>(MR_BRLIST);
+  if constexpr (sizeof(ITEM) == 4) {
+    if (p.first_level == MSM_P1_NONE)
+      return launch(msm_part2_hist_kernel<true, ITEM, false>, l[ML_P2_HIST], stream, tmp, digits, cstart, bcnt, p.sn, p.fb, p.ib, p.NC, p.NBP,
+                    0xffffffffu, 0u, (const uint2*)nullptr, (const uint32_t*)nullptr);
   }
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
+  launch(msm_part1_hist_kernel, l[ML_P1_HIST], stream, digits, chist, p.sn, p.chunk, p.fb, p.NC);   // not after the counting digits pass
+  launch(msm_part1_scan_kernel, l[ML_P1_SCAN], stream, chist, ctot, p.G, p.NC, p.SW);
+  launch(msm_part1_starts_kernel, l[ML_P1_STARTS], stream, ctot, cstart, p.SW * p.NC);
+  const auto scatter = [&](auto kernel) { launch(kernel, l[ML_P1_SCATTER], stream, digits, chist, cstart, tmp, p.sn, p.chunk, p.fb, p.ib, p.NC); };
+  if constexpr (sizeof(ITEM) == 8) scatter(msm_part1_scatter_tiled_kernel<ITEM>);
+  else if (p.p1_scatter == MSM_P1S_DIRECT) scatter(msm_part1_scatter_kernel<ITEM>);
+  else if (p.p1_scatter == MSM_P1S_VEC_BIG) scatter(msm_part1_scatter_v2_kernel<P1_BIG_IPT>);
+  else scatter(msm_part1_scatter_v2_kernel<P1_IPT_DEFAULT>);
+  launch(msm_big_regions_kernel, l[ML_BIG_REGIONS], stream, cstart, p.SW * p.NC, p.br_big, p.br_slice, brlist, brcount, p.br_capacity);
+  launch(msm_part2_hist_kernel<false, ITEM, false>, l[ML_P2_HIST], stream, tmp, digits, cstart, bcnt, p.sn, p.fb, p.ib, p.NC, p.NBP, p.br_big,
+         p.br_slice, brlist, brcount);
+  launch(msm_part2_hist_kernel<false, ITEM, true>, l[ML_P2_HIST_COOP], stream, tmp, digits, cstart, bcnt, p.sn, p.fb, p.ib, p.NC, p.NBP,
+         p.br_big, p.br_slice, brlist, brcount);
 }
 
+// The second sort level's scatter, after the scan of the bucket counts.
 template <class ITEM>
-static int launch_sort_scatter(const int32_t* d_digits, const uint32_t* d_cstart, const void* d_tmp, const uint32_t* d_boff,
-                               uint32_t* d_sorted, size_t sn, uint32_t SW, uint32_t fb, uint32_t ib, uint32_t cb, uint32_t NC,
-                               uint32_t NBP, uint32_t NBT, const BigRegionPlan& br, const Positional& ps, hipStream_t stream) {
-  const size_t lds_fine = (size_t)4 << fb;
-  if (cb && (fb <= 11 || (ps.nsc != 0 && fb <= 12)) && sizeof(ITEM) == 4 && !sort_v1()) {
-    const size_t lds_tiled = ((size_t)3 * (1u << fb) + 32 + P2_TILE) * 4 + (size_t)P2_TILE * 2;
-    hipLaunchKernelGGL((msm_part2_scatter_v2_kernel<false>), dim3(NC, SW), dim3(SORT_THREADS), lds_tiled, stream, (const uint32_t*)d_tmp,
-                       d_cstart, d_boff, d_sorted, fb, ib, NC, NBP, br.big, br.slice, (const uint2*)br.list, (const uint32_t*)br.count,
-                       br.gcursor, ps);
-    hipLaunchKernelGGL((msm_part2_scatter_v2_kernel<true>), dim3(br.capacity), dim3(SORT_THREADS), lds_tiled, stream, (const uint32_t*)d_tmp,
-                       d_cstart, d_boff, d_sorted, fb, ib, NC, NBP, br.big, br.slice, (const uint2*)br.list, (const uint32_t*)br.count,
-                       br.gcursor, ps);
-  } else if (cb && (fb <= 11 || (ps.nsc != 0 && fb <= 12))) {      // 2^12 fine counters only where the positional plan asks for them
-    const size_t lds_tiled = ((size_t)3 * (1u << fb) + 32 + P2_TILE) * 4 + (size_t)P2_TILE * 2;
-    hipLaunchKernelGGL((msm_part2_scatter_tiled_kernel<ITEM, false>), dim3(NC, SW), dim3(SORT_THREADS), lds_tiled, stream,
-                       (const ITEM*)d_tmp, d_cstart, d_boff, d_sorted, fb, ib, NC, NBP, br.big, br.slice, (const uint2*)br.list,
-                       (const uint32_t*)br.count, br.gcursor, ps);
-    hipLaunchKernelGGL((msm_part2_scatter_tiled_kernel<ITEM, true>), dim3(br.capacity), dim3(SORT_THREADS), lds_tiled, stream,
-                       (const ITEM*)d_tmp, d_cstart, d_boff, d_sorted, fb, ib, NC, NBP, br.big, br.slice, (const uint2*)br.list,
-                       (const uint32_t*)br.count, br.gcursor, ps);
-  } else if (cb) {
-    hipLaunchKernelGGL((msm_part2_scatter_kernel<false, ITEM>), dim3(NC, SW), dim3(SORT_THREADS), lds_fine, stream,
-                       (const ITEM*)d_tmp, d_digits, d_cstart, d_boff, d_sorted, sn, fb, ib, NC, NBP);
+static void launch_sort_scatter(const MsmPlan& p, const MsmWorkspace& w, hipStream_t stream) {
+  const MsmLaunch &s = p.launch[ML_P2_SCATTER], &sc = p.launch[ML_P2_SCATTER_COOP];
+  const int32_t* digits = w.at<int32_t>(MR_DIGITS);
+  const ITEM* tmp = w.at<ITEM>(MR_TMP);
+  const uint32_t *cstart = w.at(MR_CSTART), *boff = w.at(MR_BOFF), *brcount = w.at(MR_BRCOUNT);
+  const uint2* brlist = w.at<uint2>(MR_BRLIST);
+  uint32_t *sorted = w.at(MR_SORTED), *gcursor = w.at(MR_GCUR);
+  if constexpr (sizeof(ITEM) == 8) {
+    launch(msm_part2_scatter_tiled_kernel<ITEM, false>, s, stream, tmp, cstart, boff, sorted, p.fb, p.ib, p.NC, p.NBP, p.br_big, p.br_slice,
+           brlist, brcount, gcursor);
+    launch(msm_part2_scatter_tiled_kernel<ITEM, true>, sc, stream, tmp, cstart, boff, sorted, p.fb, p.ib, p.NC, p.NBP, p.br_big, p.br_slice,
+           brlist, brcount, gcursor);
+  } else if (p.p2_scatter == MSM_P2S_DIGITS) {
+    launch(msm_part2_scatter_kernel<true, ITEM>, s, stream, tmp, digits, cstart, boff, sorted, p.sn, p.fb, p.ib, p.NC, p.NBP);
+  } else if (p.p2_scatter == MSM_P2S_DIRECT) {
+    launch(msm_part2_scatter_kernel<false, ITEM>, s, stream, tmp, digits, cstart, boff, sorted, p.sn, p.fb, p.ib, p.NC, p.NBP);
   } else {
-    hipLaunchKernelGGL((msm_part2_scatter_kernel<true, ITEM>), dim3(1, SW), dim3(SORT_THREADS), lds_fine, stream,
-                       (const ITEM*)d_tmp, d_digits, d_cstart, d_boff, d_sorted, sn, fb, ib, NC, NBP);
+    const Positional ps{w.at(MR_CHIST), p.ps_G, p.ps_gpc, p.ps_nsc};
+    launch(msm_part2_scatter_v2_kernel<false>, s, stream, tmp, cstart, boff, sorted, p.fb, p.ib, p.NC, p.NBP, p.br_big, p.br_slice, brlist,
+           brcount, gcursor, ps);
+    launch(msm_part2_scatter_v2_kernel<true>, sc, stream, tmp, cstart, boff, sorted, p.fb, p.ib, p.NC, p.NBP, p.br_big, p.br_slice, brlist,
+           brcount, gcursor, ps);
   }
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
-}
-
-int msm_launch_digits(const uint32_t* d_scalars_ext, const uint8_t* d_inf, int32_t* d_digits, size_t n, uint32_t c, uint32_t W,
-                      hipStream_t stream) {
-  MsmGroupScalars one;
-  for (auto& p : one.s) p = d_scalars_ext;
-  hipLaunchKernelGGL(msm_digits_kernel<false>, dim3((uint32_t)((n + DIGITS_THREADS - 1) / DIGITS_THREADS)), dim3(DIGITS_THREADS), 0, stream,
-                     one, d_inf, d_digits, n, c, W, W, (uint32_t*)nullptr, (size_t)0, 0u, 0u, 0u);
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
 }
 
 int msm_slot_prepare(MsmSlot& sl) {
@@ -2067,468 +1947,132 @@ int msm_slot_prepare(MsmSlot& sl) {
   return HM_OK;
 }
 
+// the sort kernels that ask for more dynamic LDS than the default, and how much each may have (per device: a process may drive several GPUs)
+static int msm_set_lds_attributes() {
+  static const void* const kFine[] = {      // the LDS-histogram kernels: MSM_LDS_FINE
+      (const void*)msm_part2_hist_kernel<true, uint32_t, false>,  (const void*)msm_part2_hist_kernel<false, uint32_t, false>,
+      (const void*)msm_part2_hist_kernel<false, uint64_t, false>, (const void*)msm_part2_hist_kernel<false, uint32_t, true>,
+      (const void*)msm_part2_hist_kernel<false, uint64_t, true>,  (const void*)msm_part2_scatter_kernel<true, uint32_t>,
+      (const void*)msm_part2_scatter_kernel<false, uint32_t>,     (const void*)msm_part1_scatter_tiled_kernel<uint64_t>};
+  static const void* const kAll[] = {       // the LDS-sorted tiles of the scatters: MSM_LDS_ALL
+      (const void*)msm_part1_scatter_v2_kernel<P1_IPT_DEFAULT>,         (const void*)msm_part1_scatter_v2_kernel<P1_BIG_IPT>,
+      (const void*)msm_part2_scatter_v2_kernel<false>,                  (const void*)msm_part2_scatter_v2_kernel<true>,
+      (const void*)msm_part2_scatter_tiled_kernel<uint64_t, false>,     (const void*)msm_part2_scatter_tiled_kernel<uint64_t, true>};
+  for (const void* k : kFine) HM_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MSM_LDS_FINE));
+  for (const void* k : kAll) HM_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MSM_LDS_ALL));
+  return HM_OK;
+}
+
 // Enqueue every kernel of one MSM on `stream` using workspace slot `slot`; nothing here waits for
 // the device.  d_xy: n points (plain) or the precomputed table of precomp_W * n points
 // (precomp_c != 0).  msm_finish() later waits for the slot, folds the window sums on the host and
 // fills the statistics.
 // `group` MSMs over the same points in ONE launch chain (group > 1: only on a fixed-base table set below the positional
-// plan's sizes -- msm_table_group_applies -- where every element is one bucket set of the same sort and the same K3 launch).
+// plan's sizes -- msm_table_group_max -- where every element is one bucket set of the same sort and the same K3 launch).
+// Every size, variant, grid and workspace offset is msm_plan's (msm_plan.inc); launches the plan does not make are skipped.
 static int msm_issue(DeviceCtx& ctx, int slot, const uint32_t* const* d_scalars_list, uint32_t group, const uint32_t* d_xy,
                      const uint8_t* d_inf, size_t n, uint32_t precomp_c, hipStream_t stream) {
   MsmSlot& sl = ctx.msm_slots[slot];
-  const uint32_t* d_scalars_ext = d_scalars_list[0];
-  if (n == 0) return HM_OK;
-  if (n >= (1ull << 31)) return hm_fail(HM_ERR_BAD_ARG, "msm: n must be < 2^31");
-  if (group == 0 || group > (uint32_t)HM_MSM_GROUP) return hm_fail(HM_ERR_INTERNAL, "msm: group size out of range");
-  // ---- plan ---------------------------------------------------------------------------------
-  const bool single_set = precomp_c != 0;     // all windows accumulate into ONE bucket set
-  const int window_override = g_window_override.load(std::memory_order_relaxed);
-  uint32_t c;
-  if (single_set) {
-    c = precomp_c;
-  } else if (window_override > 0) {
-    c = (uint32_t)window_override;
-  } else {
-    // Rule of thumb: log2(n) - 3 (mean bucket load ~16: short chains, almost no bucket splitting, few
-    // (point, bucket) pairs), capped at c = 17, whose W = 15 windows cover the 255 digit bits exactly
-    // (18, 19 and 21 leave a top window of 3-8 bits whose few buckets receive all n points, and c = 20's
-    // 6.8 M buckets cost more to reduce than they save).  The table is the measured optimum per size
-    // (tools/msm_sweep.py <k> <c,c,...>): between 2^15 and 2^17 the fixed costs of the sort and of the
-    // bucket reduction move it up to c = 15.
-    static const int8_t kWindow[21] = {4, 4, 4, 4, 4, 4, 4, 4, 5, 6, 7, 8, 9, 10, 10, 13, 15, 15, 15, 16, 17};
-    // the short chain of msm_small.hip (n < 2^19) has cheaper fixed costs per bucket set: its measured optimum is
-    // log2(n) - 3 up to 2^16 (tools/small_tune.sh), then c = 15, whose 17 windows cover the 255 bits exactly
-    static const int8_t kWindowSmall[19] = {4, 4, 4, 4, 4, 4, 4, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 15, 15};
-    const uint32_t lg = ilog2(n);
-    int ci = lg <= 20 ? kWindow[lg] : 17;
-    if (lg <= 18 && msm_small_applies(n, (uint32_t)kWindowSmall[lg], false)) ci = kWindowSmall[lg];
-    c = (uint32_t)ci;
-  }
-  if (c < 2 || c > 24) return hm_fail(HM_ERR_BAD_ARG, "msm: window size out of range");
-  if (msm_small_applies(n, c, single_set)) {
-    if (group != 1) return hm_fail(HM_ERR_INTERNAL, "msm: a table group reached the five-launch plan");
-    return msm_issue_small(ctx, slot, &d_scalars_ext, 1, d_xy, d_inf, n, c, stream);
-  }
-  if (group > 1 && !single_set) return hm_fail(HM_ERR_INTERNAL, "msm: a group needs the fixed-base table's shared bucket set");
-  const uint32_t W = (255 + c - 1) / c;
-  const uint32_t SW = single_set ? group : W;              // bucket sets ("sort windows"): one per MSM on a table, one per window else
-  const size_t sn = single_set ? n * W : n;                // items per bucket set
-  const uint32_t NB = 1u << (c - 1), NBP = NB + 1, NBT = SW * NBP;
-  const uint64_t pairs_max = (uint64_t)n * W * group;      // of the whole chain
-  if (pairs_max >= (1ull << 31)) return hm_fail(HM_ERR_BAD_ARG, "msm: n * windows must be < 2^31");
-  double mean = (double)sn / (double)NB;
-  if (single_set) {
-    // narrow windows fill the even buckets only (msm_digits_kernel): size the tasks for THOSE buckets' load, so that a
-    // bucket stays one task (at c = 22, W = 12: 168 points in an even bucket, 24 in an odd one, 96 on average)
-    uint32_t wide_b, n_wide_b;
-    balanced_windows(W, &wide_b, &n_wide_b);
-    mean = (double)n * n_wide_b / (double)NB + (double)n * (W - n_wide_b) / ((double)NB / 2.0);
-  }
-#ifndef HM_L_MEAN_SCALE      // measurement knobs (tools/ab_build.sh); the defaults are the tuned values
-#define HM_L_MEAN_SCALE 1.0
-#endif
-#ifndef HM_L_SIGMAS
-#define HM_L_SIGMAS 4.0
-#endif
-  uint32_t L = (uint32_t)(HM_L_MEAN_SCALE * mean + HM_L_SIGMAS * std::sqrt(mean) + 8.0);
-  {
-    // small inputs: if one task per bucket would leave the chip (256 CUs x 4 SIMDs x ~5 waves x 64
-    // lanes) mostly idle, cut the tasks shorter so that the launch still fills it (measured: a wave per
-    // SIMD is not enough -- K3 at 2^16..2^18 is 15-40 % slower with one task per bucket)
-    const double target_tasks = (double)TARGET_TASKS;
-    if ((double)pairs_max / (double)L < target_tasks) L = (uint32_t)((double)pairs_max / target_tasks);
-  }
-  if (L < 16) L = 16;
-  // chunks of the first sort level: >= 16 Ki items each, ~64 Ki at scale; G * SW workgroups should
-  // cover the chip several times over (a shared bucket set has SW = 1, so it needs many chunks)
-  uint32_t G = (uint32_t)((sn + 16383) / 16384);
-  if (G < 1) G = 1;
-  const uint32_t g_cap = SW >= 8 ? 256u : 4096u;
-  if (G > g_cap) {
-    G = (uint32_t)((sn + 65535) / 65536);
-    if (G > g_cap) G = g_cap;
-    if (G < 256) G = 256;
-  }
-  size_t chunk = (sn + G - 1) / G;
-  // the device may shorten L (effective_task_len): then tasks <= 2 * TARGET_TASKS + one per bucket
-  // (and never more than one per pair)
-  const uint64_t T_max = std::min<uint64_t>(pairs_max, std::max<uint64_t>(pairs_max / L, 2ull * TARGET_TASKS) + NBT) + 1;
-  // K4a: running-sum chain of 2*SEG additions per lane + a scalar multiple of <= log2(NB) bits
-  // Segment length of K4a, measured per bucket count (the kernel is latency-bound: a lane's chain is
-  // 2*SEG additions plus a log2(NB/SEG)-bit multiple, and the number of lanes decides how well the chip hides it)
-#ifdef HM_SEG_SMALL
-  uint32_t SEG = NB > (1u << 16) ? 32u : HM_SEG_SMALL;
-#else
-  uint32_t SEG = NB > (1u << 16) ? 32u : NB == (1u << 15) ? 16u : NB <= (1u << 13) ? 4u : 8u;
-#endif
-  if (SEG > NB) SEG = NB;
-  const uint32_t nseg = (NB + SEG - 1) / SEG;
-  // a shared bucket set: row / column sums and one record per weight bit instead (msm_reduce_rowcol_kernel)
-  static const bool k4_chain_only = [] { const char* v = std::getenv("HALO2_MI355X_K4_CHAIN"); return v && *v == '1'; }();   // A/B
-  const bool k4_2d = single_set && NB >= 16 && !k4_chain_only;
-  const uint32_t k4_m = (c - 1 + 1) / 2, k4_h = (c - 1) - k4_m;        // M = 2^m columns, H = 2^h rows, M * H = NB
-  if (group > 1 && !k4_2d) return hm_fail(HM_ERR_INTERNAL, "msm: a table group needs the two-launch bucket reduction");
-  // Two A/B switches of the shared set's reduction, read at every call so that one process can run both arms:
-  // HALO2_MI355X_K3B_COPY=1: msm_bucket_finalize_kernel writes every bucket and the reduction reads only those (else it
-  // reads one-task buckets from their partials: load_bucket_value).  HALO2_MI355X_K4_WAVE_SUMS: 0 = the workgroup form of
-  // the row / column sums, 1 = the one-wave form at every size; unset = the one-wave form where its H + M / 2 waves give
-  // each of the chip's 1 024 SIMDs two (c >= 22; below, the wide trees' shorter critical path wins).
-  bool direct_buckets = false, wave_sums = false;
-  if (k4_2d) {
-    const char* v = std::getenv("HALO2_MI355X_K3B_COPY");
-    direct_buckets = !(v && *v == '1');
-    v = std::getenv("HALO2_MI355X_K4_WAVE_SUMS");
-    wave_sums = v && *v ? *v == '1' : ((1u << k4_h) + (1u << (k4_m - 1))) * SW >= 2048u;
-  }
-  const uint32_t RW = k4_2d ? c - 1 : SW;                               // records the host fold reads (per bucket set of a table)
-  const uint32_t res_stride = 4 + RW * 32;                              // words per element of a group: the totals, then its records
-  // sort plan: item = [fine bucket bits | sign | item index]
-  uint32_t ib = ilog2(sn) + ((sn & (sn - 1)) ? 1u : 0u);
-  if (ib == 0) ib = 1;
-  bool wide_items = false;
-  Positional ps{nullptr, 0, 0, 0};
-  uint32_t fb = c - 1 < 31 - ib ? c - 1 : 31 - ib;
-  if (fb > 15) fb = 15;                  // 2^15 LDS counters = 128 KiB is what a workgroup may hold
-#ifndef HM_NO_POSITIONAL
-  if (single_set && c >= 14 && c <= 24 && (c - 1) - fb > 10) {
-    // A shared bucket set has n W items (2^27.6 at 2^24 points) and 2^(c-1) buckets (2^21): fine bits + sign + the item index
-    // do not fit one word with few enough coarse bins (<= 2^12) for the first level's LDS-sorted tiles.  POSITIONAL 32-bit
-    // items: an item keeps the low `sbits` bits of its index, fb fine bucket bits and the sign; its super-chunk (the index
-    // bits above sbits) follows from where it lies in its coarse region (msm_part2_scatter_tiled_kernel).  Chunks of the
-    // first level are 2^16 (or more) consecutive indices, so every chunk lies inside one super-chunk.
-    static const uint32_t cb_first = [] { const char* v = std::getenv("HALO2_MI355X_CB_FIRST"); return (uint32_t)(v && *v ? std::atoi(v) : 9); }();   // A/B: 9 against 10: sort 0.69 / 0.74 ms at 2^22 (c = 20), the same at c = 22; 8 is slower
-    for (uint32_t cb_try = cb_first; cb_try <= 12 && ps.nsc == 0; ++cb_try) {
-      if (c - 1 < cb_try + 5) break;
-      const uint32_t fb_p = c - 1 - cb_try, sbits = 31 - fb_p;
-      if (fb_p > 12 || sbits < 16) continue;                   // the tiled second level holds <= 2^12 fine counters
-      size_t chunk_p = (size_t)1 << 16;
-      while ((sn + chunk_p - 1) / chunk_p > 4096 && chunk_p < ((size_t)1 << sbits)) chunk_p <<= 1;
-      const size_t nsc = (sn + ((size_t)1 << sbits) - 1) >> sbits;
-      if (nsc > PS_MAX_SC || (sn + chunk_p - 1) / chunk_p > 4096) continue;
-      ib = sbits;
-      fb = fb_p;
-      G = (uint32_t)((sn + chunk_p - 1) / chunk_p);
-      chunk = chunk_p;
-      ps.G = G;
-      ps.gpc = (uint32_t)(((size_t)1 << sbits) / chunk_p);
-      ps.nsc = (uint32_t)nsc;
-    }
-  }
-#endif
-  if (ps.nsc == 0 && fb < 5 && c - 1 > fb) {   // too few fine bits left in 32: switch to 64-bit items
-    wide_items = true;
-    fb = c - 1 < 9 ? c - 1 : 9;      // few fine runs per region: the region's write sectors must stay in L2
-  }
-  if (ps.nsc == 0 && sn >= (1u << 15) && (c - 1) - fb < 5) fb = c - 1 > 5 ? c - 1 - 5 : 0;   // >= 32 regions per set: enough workgroups
-  const uint32_t cb = (c - 1) - fb, NC = 1u << cb;
-  // Coarse-bin counts from the digits pass (msm_digits_kernel<true>): a shared bucket set with a first sort level whose
-  // chunks each lie inside one window, 32-bit items, the vector-load sort -- and a workgroup per chunk of points for every
-  // one of the chip's 256 CUs (2^24 points): the form has n / chunk workgroups, and below that it loses more in the digits
-  // kernel than the histogram pass costs (2^20 points, 16 workgroups: 0.37 against 0.03 ms).  HALO2_MI355X_DIGITS_COUNT:
-  // 0 = the separate histogram pass, 1 = the counting form wherever it is valid (A/B and tests; read at every call, so that
-  // one process can run both arms).
-  bool digits_count = false;
-  if (single_set && cb != 0 && !wide_items && !sort_v1() && n % chunk == 0 && (size_t)G * chunk == sn && (size_t)W * NC * 4 <= 48 * 1024) {
-    const char* v = std::getenv("HALO2_MI355X_DIGITS_COUNT");
-    digits_count = v && *v ? *v == '1' : (n / chunk) * group >= 256;
-  }
+  const MsmPlan p = msm_plan(n, group, precomp_c, msm_read_knobs());
+  if (p.err != MSM_PLAN_OK) return hm_fail(p.err, p.err_msg);
+  if (p.route == MSM_ROUTE_EMPTY) return HM_OK;
+  if (p.route == MSM_ROUTE_SMALL) return msm_issue_small(ctx, slot, d_scalars_list, 1, d_xy, d_inf, n, p.c, stream);
+  const MsmLaunch* const l = p.launch;
+  const MsmWorkspace w{(uint8_t*)sl.ws.ensure(p.ws_bytes), p};
+  if (!w.base) return hm_fail(HM_ERR_HIP, "msm: workspace allocation failed");
+  int32_t* d_digits = w.at<int32_t>(MR_DIGITS);
+  uint32_t *d_chist = w.at(MR_CHIST), *d_bcnt = w.at(MR_BCNT), *d_boff = w.at(MR_BOFF), *d_toff = w.at(MR_TOFF), *d_bsum = w.at(MR_BSUM);
+  uint32_t *d_sorted = w.at(MR_SORTED), *d_tb = w.at(MR_TB), *d_torder = w.at(MR_TORDER), *d_khist = w.at(MR_TKEYS), *d_kcursor = d_khist + TASK_KEYS;
+  uint32_t *d_partial = w.at(MR_PARTIAL), *d_bucket = w.at(MR_BUCKET), *d_seg = w.at(MR_SEG), *d_seg2 = w.at(MR_SEG2);
+  uint32_t *d_tot = w.at(MR_RES), *d_win = d_tot + 4;       // per element: 4 totals words, then its records (one D2H copy)
+  uint32_t *d_big_count = w.at(MR_BIG), *d_big_list = d_big_count + 4;
+  uint2* d_slices = w.at<uint2>(MR_SLICES);
+  // pair count for effective_task_len: the first sort level leaves it behind its region starts; an
+  // input small enough to need no first level keeps the host's L
+  const uint32_t* d_pairs = p.cb ? w.at(MR_CSTART) + (size_t)p.SW * p.NC : nullptr;
+  const uint32_t NBT = p.NBT, L = p.L;
 
-  // ---- workspace ----------------------------------------------------------------------------
-  auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += align(bytes); return o; };
-  const size_t o_digits = carve((size_t)W * n * 4 * group);
-  const size_t o_chist = carve((size_t)SW * G * NC * 4);
-  const size_t o_ctot = carve((size_t)SW * NC * 4);
-  const size_t o_cstart = carve(((size_t)SW * NC + 1) * 4);
-  const size_t o_tmp = carve(cb ? pairs_max * (wide_items ? 8 : 4) : 4);
-  const size_t o_bcnt = carve((size_t)NBT * 4);
-  const size_t o_boff = carve((size_t)NBT * 4);
-  const size_t o_toff = carve(((size_t)NBT + 1) * 4);
-  const size_t o_bsum = carve(((size_t)NBT / SCAN_BLOCK + 2) * 8);
-  const size_t o_sorted = carve(pairs_max * 4);
-  const size_t o_tb = carve(T_max * 4);
-  const size_t o_torder = carve(T_max * 4);
-  const size_t o_tkeys = carve(2 * TASK_KEYS * 4);
-  const size_t o_partial = carve(T_max * PT_WORDS * 4);
-  const size_t o_bucket = carve((size_t)NBT * PT_WORDS * 4);
-  const size_t o_seg = carve(k4_2d ? (((size_t)1 << k4_m) + ((size_t)1 << k4_h)) * PT_WORDS * 4 * SW : (size_t)SW * nseg * PT_WORDS * 4);
-  const size_t o_seg2 = carve(((size_t)SW * (nseg / SUM_SPAN + 1)) * PT_WORDS * 4);
-  const size_t o_res = carve((size_t)(single_set ? group : 1u) * res_stride * 4);   // per element: 4 totals words, then its records (one D2H copy)
-  const size_t o_big = carve(((size_t)NBT + 4) * 4);
-  const size_t o_slices = carve((T_max / FINALIZE_SLICE + T_max / (FINALIZE_SERIAL + 1) + 2) * 8);
-  // cooperative sort of oversized regions (hot buckets): split anything above 4x the mean region
-  BigRegionPlan br;
-  {
-    const uint64_t mean_region = pairs_max / ((uint64_t)NC * SW) + 1;
-    uint64_t slice = (mean_region + P2_TILE - 1) / P2_TILE * P2_TILE;
-    if (slice < 4 * (uint64_t)P2_TILE) slice = 4 * (uint64_t)P2_TILE;
-    br.slice = (uint32_t)slice;
-    br.big = (uint32_t)(4 * slice);
-    br.capacity = (uint32_t)(pairs_max / slice + pairs_max / br.big + 2);
-  }
-  const bool coop_sort = cb != 0 && (fb <= 11 || (ps.nsc != 0 && fb <= 12));
-  const size_t o_brlist = carve(coop_sort ? (size_t)br.capacity * 8 : 8);
-  const size_t o_brcount = carve(16);
-  const size_t o_gcur = carve(coop_sort ? (size_t)NBT * 4 : 4);
-  uint8_t* ws = (uint8_t*)sl.ws.ensure(off);
-  if (!ws) return hm_fail(HM_ERR_HIP, "msm: workspace allocation failed");
-  int32_t* d_digits = (int32_t*)(ws + o_digits);
-  uint32_t* d_chist = (uint32_t*)(ws + o_chist);
-  uint32_t* d_ctot = (uint32_t*)(ws + o_ctot);
-  uint32_t* d_cstart = (uint32_t*)(ws + o_cstart);
-  void* d_tmp = (void*)(ws + o_tmp);
-  uint32_t* d_bcnt = (uint32_t*)(ws + o_bcnt);
-  uint32_t* d_boff = (uint32_t*)(ws + o_boff);
-  uint32_t* d_toff = (uint32_t*)(ws + o_toff);
-  uint32_t* d_bsum = (uint32_t*)(ws + o_bsum);
-  uint32_t* d_sorted = (uint32_t*)(ws + o_sorted);
-  uint32_t* d_tb = (uint32_t*)(ws + o_tb);
-  uint32_t* d_torder = (uint32_t*)(ws + o_torder);
-  uint32_t* d_khist = (uint32_t*)(ws + o_tkeys);
-  uint32_t* d_kcursor = d_khist + TASK_KEYS;
-  uint32_t* d_partial = (uint32_t*)(ws + o_partial);
-  uint32_t* d_bucket = (uint32_t*)(ws + o_bucket);
-  uint32_t* d_seg = (uint32_t*)(ws + o_seg);
-  uint32_t* d_seg2 = (uint32_t*)(ws + o_seg2);
-  uint32_t* d_tot = (uint32_t*)(ws + o_res);
-  uint32_t* d_win = d_tot + 4;
-  uint32_t* d_big_count = (uint32_t*)(ws + o_big);
-  uint32_t* d_big_list = d_big_count + 4;
-  uint2* d_slices = (uint2*)(ws + o_slices);
-  br.list = (uint2*)(ws + o_brlist);
-  br.count = (uint32_t*)(ws + o_brcount);
-  br.gcursor = (uint32_t*)(ws + o_gcur);
-  if (!coop_sort) br.big = 0xffffffffu;    // the non-tiled scatter has no cooperative form: nothing is "big"
-
-  if (!ctx.msm_attr_set) {   // per device: a process may drive several GPUs
-    const int lds_max = 32768 * 4;
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part2_hist_kernel<true, uint32_t, false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part2_hist_kernel<false, uint32_t, false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part2_hist_kernel<false, uint64_t, false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part2_hist_kernel<false, uint32_t, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part2_hist_kernel<false, uint64_t, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part2_scatter_kernel<true, uint32_t>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part2_scatter_kernel<false, uint32_t>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part2_scatter_kernel<false, uint64_t>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part1_scatter_tiled_kernel<uint32_t, P1_IPT_DEFAULT>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part1_scatter_tiled_kernel<uint64_t, P1_IPT_DEFAULT>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part1_scatter_tiled_kernel<uint32_t, P1_BIG_IPT>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    const int lds_all = 160 * 1024 - 6 * 1024;     // what a workgroup may ask for dynamically beside the v2 kernels' static tables
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part1_scatter_v2_kernel<P1_IPT_DEFAULT>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_all));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part1_scatter_v2_kernel<P1_BIG_IPT>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_all));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part2_scatter_v2_kernel<false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_all));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_part2_scatter_v2_kernel<true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_all));
-    ctx.msm_attr_set = true;
-  }
+  int rc = ctx.msm_attr_set ? HM_OK : msm_set_lds_attributes();      // per device: a process may drive several GPUs
+  if (rc == HM_OK) rc = msm_slot_prepare(sl);
+  if (rc != HM_OK) return rc;
+  ctx.msm_attr_set = true;
   hipEvent_t* ev = sl.ev;
-  {
-    const int rc = msm_slot_prepare(sl);
-    if (rc != HM_OK) return rc;
-  }
-  sl.SW = RW;                                     // what the host fold reads: window sums, or one-bit records of a shared set
-  sl.c = c;
-  sl.W = W;
-  sl.balanced = k4_2d;                            // ... which weigh one bit each
-  if (k4_2d) std::memset(sl.win_bits, 1, RW);
-  sl.group = group;
-  sl.res_stride = res_stride;
+  const bool k4_2d = p.reduction != MSM_RED_CHAIN, wide_items = p.item == MSM_ITEM_U64;
+  // the host fold reads window sums, or the one-bit records of a shared set
+  sl.describe(p.RW, p.c, p.W, group, p.res_stride, p.T_max, d_tot, k4_2d, msm_phase_timing(false));
+  if (k4_2d) std::memset(sl.win_bits, 1, p.RW);
   sl.live_ptr = nullptr;                          // the general pipeline writes all over the workspace
-  sl.phase_timed = msm_phase_timing(false);
   const bool pt = sl.phase_timed;
-  sl.T_max = T_max;
-  sl.d_win = d_win;
-  sl.d_tot = d_tot;
   HM_HIP_CHECK(hipEventRecord(ev[0], stream));
 
-  // ---- K0 ------------------------------------------------------------------------------------
-  uint32_t n_wide = W;                                       // a shared bucket set: the balanced split its table was built for
-  if (single_set) {
-    uint32_t wide;
-    balanced_windows(W, &wide, &n_wide);
-    if (wide != c) return hm_fail(HM_ERR_INTERNAL, "msm: the base set's table was built for another window split");
-  }
-  {
-    MsmGroupScalars list;
-    for (uint32_t e = 0; e < (uint32_t)HM_MSM_GROUP; ++e) list.s[e] = d_scalars_list[e < group ? e : 0];
-    if (digits_count)
-      hipLaunchKernelGGL(msm_digits_kernel<true>, dim3((uint32_t)(n / chunk), group), dim3(DIGITS_COUNT_THREADS), (size_t)W * NC * 4,
-                         stream, list, d_inf, d_digits, n, c, W, n_wide, d_chist, chunk, G, fb, NC);
-    else
-      hipLaunchKernelGGL(msm_digits_kernel<false>, dim3((uint32_t)((n + DIGITS_THREADS - 1) / DIGITS_THREADS), group), dim3(DIGITS_THREADS), 0,
-                         stream, list, d_inf, d_digits, n, c, W, n_wide, (uint32_t*)nullptr, (size_t)0, 0u, 0u, 0u);
-  }
+  // ---- K0: digits ----------------------------------------------------------------------------
+  MsmGroupScalars list;
+  for (uint32_t e = 0; e < (uint32_t)HM_MSM_GROUP; ++e) list.s[e] = d_scalars_list[e < group ? e : 0];
+  if (p.digits == MSM_DIGITS_COUNTING)
+    launch(msm_digits_kernel<true>, l[ML_DIGITS], stream, list, d_inf, d_digits, n, p.c, p.W, p.n_wide, d_chist, p.chunk, p.G, p.fb, p.NC);
+  else
+    launch(msm_digits_kernel<false>, l[ML_DIGITS], stream, list, d_inf, d_digits, n, p.c, p.W, p.n_wide, (uint32_t*)nullptr, (size_t)0, 0u, 0u, 0u);
   HM_HIP_CHECK(hipGetLastError());
   if (pt) HM_HIP_CHECK(hipEventRecord(ev[1], stream));
 
-  // ---- K2 ------------------------------------------------------------------------------------
-  {
-    {
-      const uint32_t blocks = (uint32_t)std::min<size_t>(((size_t)NBT + 255) / 256, 2048);
-      hipLaunchKernelGGL(msm_init_counters_kernel, dim3(blocks < 4 ? 4 : blocks), dim3(256), 0, stream, d_bcnt, (size_t)NBT,
-                         cb ? br.count : (uint32_t*)nullptr, d_khist, TASK_KEYS, d_big_count);
-      HM_HIP_CHECK(hipGetLastError());
-    }
-    const int rc = wide_items
-                       ? launch_sort<uint64_t>(d_digits, d_chist, d_ctot, d_cstart, d_tmp, d_bcnt, sn, chunk, G, SW, fb, ib, cb,
-                                               NC, NBP, br, digits_count, stream)
-                       : launch_sort<uint32_t>(d_digits, d_chist, d_ctot, d_cstart, d_tmp, d_bcnt, sn, chunk, G, SW, fb, ib, cb,
-                                               NC, NBP, br, digits_count, stream);
-    if (rc != HM_OK) return rc;
-  }
-  // pair count for effective_task_len: the first sort level leaves it behind its region starts; an
-  // input small enough to need no first level keeps the host's L
-  const uint32_t* d_pairs = cb ? (const uint32_t*)(d_cstart + (size_t)SW * NC) : (const uint32_t*)nullptr;
-  {
-    const uint32_t nblocks = (NBT + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    hipLaunchKernelGGL(msm_scan_partial_kernel, dim3(nblocks), dim3(SCAN_THREADS), 0, stream, (const uint32_t*)d_bcnt,
-                       d_bsum, NBT, d_pairs, L);
-    hipLaunchKernelGGL(msm_scan_blocksums_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, d_bsum, nblocks, d_tot,
-                       (uint32_t)std::min<uint64_t>(T_max, 0xffffffffull));
-    hipLaunchKernelGGL(msm_scan_final_kernel, dim3(nblocks), dim3(SCAN_THREADS), 0, stream, (const uint32_t*)d_bcnt,
-                       (const uint32_t*)d_bsum, d_boff, d_toff, (const uint32_t*)d_tot, NBT, d_pairs, L,
-                       coop_sort ? br.gcursor : (uint32_t*)nullptr);
-    HM_HIP_CHECK(hipGetLastError());
-  }
-  {
-    ps.chist = d_chist;
-    const int rc = wide_items ? launch_sort_scatter<uint64_t>(d_digits, d_cstart, d_tmp, d_boff, d_sorted, sn, SW, fb, ib, cb, NC,
-                                                              NBP, NBT, br, ps, stream)
-                              : launch_sort_scatter<uint32_t>(d_digits, d_cstart, d_tmp, d_boff, d_sorted, sn, SW, fb, ib, cb, NC,
-                                                              NBP, NBT, br, ps, stream);
-    if (rc != HM_OK) return rc;
-  }
-  if (pairs_max < (1u << 19)) {
-    // small inputs: three more launches cost more than the idle lanes they would save
-    hipLaunchKernelGGL(msm_task_fill_kernel, dim3((NBT + 255) / 256), dim3(256), 0, stream, (const uint32_t*)d_toff, d_tb, d_torder,
-                       NBT, (const uint32_t*)d_tot);
-  } else {
-    const uint32_t og = (NBT + ORDER_THREADS * ORDER_ITEMS - 1) / (ORDER_THREADS * ORDER_ITEMS);
-    hipLaunchKernelGGL(msm_task_hist_kernel, dim3(og), dim3(ORDER_THREADS), 0, stream, (const uint32_t*)d_bcnt, NBT,
-                       d_pairs, L, d_khist);
-    hipLaunchKernelGGL(msm_task_keyscan_kernel, dim3(1), dim3(ORDER_THREADS), 0, stream, (const uint32_t*)d_khist, d_kcursor);
-    hipLaunchKernelGGL(msm_task_order_kernel, dim3(og), dim3(ORDER_THREADS), 0, stream, (const uint32_t*)d_bcnt,
-                       (const uint32_t*)d_toff, NBT, d_pairs, L, d_kcursor, d_tb, d_torder, (const uint32_t*)d_tot);
-  }
+  // ---- K2: sort, scan, task order ------------------------------------------------------------
+  launch(msm_init_counters_kernel, l[ML_INIT], stream, d_bcnt, (size_t)NBT, p.cb ? w.at(MR_BRCOUNT) : (uint32_t*)nullptr, d_khist, TASK_KEYS,
+         d_big_count);
+  HM_HIP_CHECK(hipGetLastError());
+  wide_items ? launch_sort<uint64_t>(p, w, stream) : launch_sort<uint32_t>(p, w, stream);
+  launch(msm_scan_partial_kernel, l[ML_SCAN_PARTIAL], stream, d_bcnt, d_bsum, NBT, d_pairs, L);
+  launch(msm_scan_blocksums_kernel, l[ML_SCAN_BLOCKSUMS], stream, d_bsum, l[ML_SCAN_PARTIAL].gx, d_tot, (uint32_t)std::min<uint64_t>(p.T_max, 0xffffffffull));
+  launch(msm_scan_final_kernel, l[ML_SCAN_FINAL], stream, d_bcnt, d_bsum, d_boff, d_toff, d_tot, NBT, d_pairs, L,
+         p.coop_sort ? w.at(MR_GCUR) : (uint32_t*)nullptr);
+  HM_HIP_CHECK(hipGetLastError());
+  wide_items ? launch_sort_scatter<uint64_t>(p, w, stream) : launch_sort_scatter<uint32_t>(p, w, stream);
+  // small inputs fill the task list in bucket order (three more launches cost more than the idle lanes they would save); else by length
+  launch(msm_task_fill_kernel, l[ML_TASK_FILL], stream, d_toff, d_tb, d_torder, NBT, d_tot);
+  launch(msm_task_hist_kernel, l[ML_TASK_HIST], stream, d_bcnt, NBT, d_pairs, L, d_khist);
+  launch(msm_task_keyscan_kernel, l[ML_TASK_KEYSCAN], stream, d_khist, d_kcursor);
+  launch(msm_task_order_kernel, l[ML_TASK_ORDER], stream, d_bcnt, d_toff, NBT, d_pairs, L, d_kcursor, d_tb, d_torder, d_tot);
   HM_HIP_CHECK(hipGetLastError());
   if (pt) HM_HIP_CHECK(hipEventRecord(ev[2], stream));
 
-  // ---- K3 ------------------------------------------------------------------------------------
-  // The exact task count T stays on the device (d_tot[1]); the grid covers its host-side bound: for
-  // uniform scalars every bucket holds one task (T ~ NBT), else at most pairs / L more.  Surplus
+  // ---- K3: accumulate, then one point per bucket -----------------------------------------------
+  // The exact task count T stays on the device (d_tot[1]); the grid covers its host-side bound (the plan's T_max): surplus
   // single-wave workgroups exit at once.
   if (pt) HM_HIP_CHECK(hipEventRecord(ev[5], stream));
-  {
-    const uint64_t t_grid = T_max;
-    hipLaunchKernelGGL(msm_accumulate_kernel, dim3((uint32_t)((t_grid + ACC_THREADS - 1) / ACC_THREADS)), dim3(ACC_THREADS), 0,
-                       stream, (const uint32_t*)d_sorted, (const uint32_t*)d_tb, (const uint32_t*)d_torder, (const uint32_t*)d_boff,
-                       (const uint32_t*)d_bcnt, (const uint32_t*)d_toff, d_xy, d_partial, (const uint32_t*)d_tot, d_pairs, L);
-    HM_HIP_CHECK(hipGetLastError());
-  }
-  if (pt) HM_HIP_CHECK(hipEventRecord(ev[6], stream));
-  hipLaunchKernelGGL(msm_bucket_finalize_kernel, dim3((NBT + ACC_THREADS - 1) / ACC_THREADS), dim3(ACC_THREADS), 0, stream,
-                     (const uint32_t*)d_partial, (const uint32_t*)d_toff, d_bucket, NBT, d_big_count, d_big_list, d_slices,
-                     (const uint32_t*)d_tot, direct_buckets ? 1u : 0u);
+  launch(msm_accumulate_kernel, l[ML_ACCUMULATE], stream, d_sorted, d_tb, d_torder, d_boff, d_bcnt, d_toff, d_xy, d_partial, d_tot, d_pairs, L);
   HM_HIP_CHECK(hipGetLastError());
-  {
-    uint32_t slice_grid = (uint32_t)(T_max / FINALIZE_SLICE + 1);       // upper bound on the number of full slices
-    if (slice_grid > 2048) slice_grid = 2048;                           // both kernels stride over their queues
-    hipLaunchKernelGGL(msm_bucket_finalize_slices_kernel, dim3(slice_grid), dim3(WIN_THREADS), 0, stream, d_partial,
-                       (const uint32_t*)d_toff, (const uint32_t*)d_big_count, (const uint2*)d_slices);
-    uint32_t big_grid = (uint32_t)(T_max / (FINALIZE_SERIAL + 1) + 1);  // upper bound on the number of queued buckets
-    if (big_grid > 2048) big_grid = 2048;
-    hipLaunchKernelGGL(msm_bucket_finalize_big_kernel, dim3(big_grid), dim3(WIN_THREADS), 0, stream,
-                       (const uint32_t*)d_partial, (const uint32_t*)d_toff, d_bucket, (const uint32_t*)d_big_count,
-                       (const uint32_t*)d_big_list);
-    HM_HIP_CHECK(hipGetLastError());
-  }
+  if (pt) HM_HIP_CHECK(hipEventRecord(ev[6], stream));
+  launch(msm_bucket_finalize_kernel, l[ML_FINALIZE], stream, d_partial, d_toff, d_bucket, NBT, d_big_count, d_big_list, d_slices, d_tot,
+         p.direct_buckets ? 1u : 0u);
+  HM_HIP_CHECK(hipGetLastError());
+  launch(msm_bucket_finalize_slices_kernel, l[ML_FINALIZE_SLICES], stream, d_partial, d_toff, d_big_count, d_slices);   // both stride over their queues
+  launch(msm_bucket_finalize_big_kernel, l[ML_FINALIZE_BIG], stream, d_partial, d_toff, d_bucket, d_big_count, d_big_list);
+  HM_HIP_CHECK(hipGetLastError());
   if (pt) HM_HIP_CHECK(hipEventRecord(ev[3], stream));
 
-  // ---- K4 ------------------------------------------------------------------------------------
-  if (k4_2d) {
-    const uint32_t* rd_partial = direct_buckets ? (const uint32_t*)d_partial : (const uint32_t*)nullptr;
-    const uint32_t* rd_toff = direct_buckets ? (const uint32_t*)d_toff : (const uint32_t*)nullptr;
-    if (wave_sums)
-      hipLaunchKernelGGL(msm_reduce_rowcol_wave_kernel, dim3((1u << k4_h) + (1u << (k4_m - 1)), SW), dim3(WAVE_THREADS), 0, stream,
-                         (const uint32_t*)d_bucket, d_seg, k4_m, k4_h, rd_partial, rd_toff, (const uint32_t*)d_tot);
+  // ---- K4: reduce ------------------------------------------------------------------------------
+  if (k4_2d) {     // a shared bucket set: row / column sums, then one record per weight bit
+    const uint32_t* rd_partial = p.direct_buckets ? d_partial : nullptr;
+    const uint32_t* rd_toff = p.direct_buckets ? d_toff : nullptr;
+    if (p.reduction == MSM_RED_ROWCOL_WAVE)
+      launch(msm_reduce_rowcol_wave_kernel, l[ML_ROWCOL], stream, d_bucket, d_seg, p.k4_m, p.k4_h, rd_partial, rd_toff, d_tot);
     else
-      hipLaunchKernelGGL(msm_reduce_rowcol_kernel, dim3((1u << k4_m) + (1u << k4_h), SW), dim3(WIN_THREADS), 0, stream,
-                         (const uint32_t*)d_bucket, d_seg, k4_m, k4_h, rd_partial, rd_toff, (const uint32_t*)d_tot);
-    hipLaunchKernelGGL(msm_reduce_bits_kernel, dim3(RW, SW), dim3(WIN_THREADS), 0, stream, (const uint32_t*)d_seg, k4_m, k4_h, d_win,
-                       res_stride);
-    HM_HIP_CHECK(hipGetLastError());
-  } else {
-  hipLaunchKernelGGL(msm_reduce_segments_kernel, dim3((SW * nseg + ACC_THREADS - 1) / ACC_THREADS), dim3(ACC_THREADS), 0,
-                     stream, (const uint32_t*)d_bucket, d_seg, SW, NB, NBP, SEG, nseg);
+      launch(msm_reduce_rowcol_kernel, l[ML_ROWCOL], stream, d_bucket, d_seg, p.k4_m, p.k4_h, rd_partial, rd_toff, d_tot);
+    launch(msm_reduce_bits_kernel, l[ML_BITS], stream, d_seg, p.k4_m, p.k4_h, d_win, p.res_stride);
+  } else {         // a bucket set per window: running sums per segment, then sums of the segments' points
+    launch(msm_reduce_segments_kernel, l[ML_SEGMENTS], stream, d_bucket, d_seg, p.SW, p.NB, p.NBP, p.SEG, p.nseg);
+    uint32_t *cur = d_seg, *nxt = d_seg2;
+    for (uint32_t lv = 0; lv < p.sum_levels; ++lv, std::swap(cur, nxt))
+      launch(msm_sum_points_kernel, l[ML_SUM_0 + lv], stream, cur, p.sum_count[lv], nxt, l[ML_SUM_0 + lv].gx);
+    launch(msm_windows_to_ext_kernel, l[ML_TO_EXT], stream, cur, p.SW, d_win);
+  }
   HM_HIP_CHECK(hipGetLastError());
-  {
-    uint32_t* cur = d_seg;
-    uint32_t* nxt = d_seg2;
-    uint32_t count = nseg;
-    while (count > 1) {
-      const uint32_t out_count = (count + SUM_SPAN - 1) / SUM_SPAN;
-      hipLaunchKernelGGL(msm_sum_points_kernel, dim3(out_count, SW), dim3(WIN_THREADS), 0, stream, (const uint32_t*)cur, count, nxt,
-                         out_count);
-      HM_HIP_CHECK(hipGetLastError());
-      uint32_t* t = cur; cur = nxt; nxt = t;
-      count = out_count;
-    }
-    hipLaunchKernelGGL(msm_windows_to_ext_kernel, dim3((SW + 63) / 64), dim3(64), 0, stream, (const uint32_t*)cur, SW, d_win);
-    HM_HIP_CHECK(hipGetLastError());
-  }
-  }
-  if (RW > 128) return hm_fail(HM_ERR_INTERNAL, "msm: more than 128 windows");
   // pinned landing zone, so that this copy (and therefore msm_enqueue) does not wait for the device
-  HM_HIP_CHECK(hipMemcpyAsync(sl.totals(), d_tot, (size_t)(single_set ? group : 1u) * res_stride * 4, hipMemcpyDeviceToHost, stream));
+  HM_HIP_CHECK(hipMemcpyAsync(sl.totals(), d_tot, p.region[MR_RES].bytes, hipMemcpyDeviceToHost, stream));
   HM_HIP_CHECK(hipEventRecord(ev[4], stream));
   return HM_OK;
 }
 
-int msm_enqueue(DeviceCtx& ctx, int slot, const uint32_t* d_scalars_ext, const uint32_t* d_xy, const uint8_t* d_inf, size_t n,
-                uint32_t precomp_c, hipStream_t stream) {
-  MsmSlot& sl = ctx.msm_slots[slot];
-  sl.n = n;
-  sl.stream = stream;
-  sl.group = 1;
-  if (n == 0) return HM_OK;
-  return msm_issue(ctx, slot, &d_scalars_ext, 1, d_xy, d_inf, n, precomp_c, stream);
-}
-
-// Several DENSE commitments over one fixed-base table in one chain of the general pipeline: every element is a bucket set
-// of the same sort launches, the same K3 launch and the same two reduction launches (HALO2_MI355X_GROUP_DENSE: how many,
-// default 8; 1 = a chain each).  Applies where a single such MSM runs the general pipeline on the table (not the five-launch
-// plan) and the whole chain's (point, bucket) pairs stay below 2^31.
-uint32_t msm_table_group_max(size_t n, uint32_t precomp_c) {
-  static const uint32_t want = [] {
-    const char* v = std::getenv("HALO2_MI355X_GROUP_DENSE");
-    const int g = v && *v ? std::atoi(v) : 8;
-    return (uint32_t)(g < 1 ? 1 : g > HM_MSM_GROUP ? HM_MSM_GROUP : g);
-  }();
-  static const bool k4_chain_only = [] { const char* v = std::getenv("HALO2_MI355X_K4_CHAIN"); return v && *v == '1'; }();
-  // (from 2^19 points a commitment fills the chip by itself, and the positional sort plan of the larger sizes has only been
-  //  exercised one bucket set at a time)
-  if (precomp_c < 6 || n == 0 || n >= ((size_t)1 << 19) || k4_chain_only || msm_small_applies(n, precomp_c, true)) return 1;
-  const uint64_t per = (uint64_t)n * ((255 + precomp_c - 1) / precomp_c);
-  uint32_t g = want;
-  while (g > 1 && per * g >= (1ull << 31)) --g;
-  while (g > 1 && per * g * 4 > ((uint64_t)3 << 30)) --g;       // keep a chain's item arrays below 3 GiB each
-  return g;
-}
+uint32_t msm_table_group_max(size_t n, uint32_t precomp_c) { return plan_table_group_max(n, precomp_c); }
 int msm_enqueue_table_group(DeviceCtx& ctx, int slot, const uint32_t* const* d_scalars_list, uint32_t group, const uint32_t* d_xy,
                             const uint8_t* d_inf, size_t n, uint32_t precomp_c, hipStream_t stream) {
   MsmSlot& sl = ctx.msm_slots[slot];
@@ -2540,18 +2084,14 @@ int msm_enqueue_table_group(DeviceCtx& ctx, int slot, const uint32_t* const* d_s
   return msm_issue(ctx, slot, d_scalars_list, group, d_xy, d_inf, n, precomp_c, stream);
 }
 
-// The window plan of the five-launch chain for n points, or 0 when it does not apply (n >= 2^19, a precomputed set,
-// an override outside its range): the same choice msm_issue makes for a single MSM.
-// `live_rows` (0 = unknown): an upper bound on the rows that survive the digits kernel's compaction -- the window is
-// picked for THOSE (an advice column with 1 100 used rows of 2^18 is a 2^10-point MSM: c = 7, not 15: its buckets are
-// then dense, and the reduction's per-bucket scalar multiple has 7 bits instead of 14)
+int msm_enqueue(DeviceCtx& ctx, int slot, const uint32_t* d_scalars_ext, const uint32_t* d_xy, const uint8_t* d_inf, size_t n,
+                uint32_t precomp_c, hipStream_t stream) {
+  return msm_enqueue_table_group(ctx, slot, &d_scalars_ext, 1, d_xy, d_inf, n, precomp_c, stream);      // a group of one, on either layout
+}
+
+// the five-launch chain's window for n points sized for `live_rows` of them, or 0 when that chain does not apply (msm_plan.inc)
 static uint32_t small_plan_window(size_t n, uint32_t precomp_c, size_t live_rows = 0) {
-  if (precomp_c != 0 || n == 0 || n >= (1u << 19)) return 0;
-  static const int8_t kWindowSmallPlan[19] = {4, 4, 4, 4, 4, 4, 4, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 15, 15};
-  const int window_override = g_window_override.load(std::memory_order_relaxed);
-  const size_t sized_for = live_rows != 0 && live_rows < n ? live_rows : n;
-  const uint32_t c = window_override ? (uint32_t)window_override : (uint32_t)kWindowSmallPlan[ilog2(sized_for)];
-  return msm_small_applies(n, c, false) ? c : 0;
+  return plan_small_window(n, precomp_c, live_rows, msm_read_knobs(true));
 }
 bool msm_group_applies(size_t n, uint32_t precomp_c) { return small_plan_window(n, precomp_c) != 0; }
 

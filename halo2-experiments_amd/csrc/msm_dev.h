@@ -3,11 +3,22 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+
 #include "g1.h"
 
 namespace hm {
 
-constexpr int PT_WORDS = 28;  // device Jacobian record: 27 limbs + identity flag
+#include "msm_plan.inc"   // PT_WORDS, the thread counts and tile sizes: one definition for the kernels and the host plan
+
+// One launch of a plan: its grid, block and dynamic LDS are the plan's; a launch the plan does not make (gx == 0) is skipped.
+template <class K, class... A>
+static void launch(K kernel, const MsmLaunch& l, hipStream_t stream, A... args) {
+  if (l.gx) hipLaunchKernelGGL(kernel, dim3(l.gx, l.gy, l.gz), dim3(l.block), l.lds, stream, args...);
+}
 
 __device__ __forceinline__ G1Jac load_jac(const uint32_t* p) {
   const uint4* q = reinterpret_cast<const uint4*>(p);
@@ -51,8 +62,6 @@ __device__ __forceinline__ G1Aff load_base(const uint32_t* xy, uint32_t idx) {
   r.y = fe_unpack<FqParams>(wy);
   return r;
 }
-
-constexpr int ACC_THREADS = 64;
 
 typedef __attribute__((address_space(3))) void hm_lds_void;
 typedef __attribute__((address_space(1))) const void hm_gbl_void;
@@ -124,7 +133,6 @@ __device__ __forceinline__ G1Jac accumulate_chain(const uint32_t* __restrict__ s
 }
 
 // Workgroup-wide sum of one point per lane through an LDS tree; the result is valid in lane 0.
-constexpr int WIN_THREADS = 256;
 __device__ __forceinline__ G1Jac block_sum_points(uint32_t* tree, G1Jac acc) {
   const uint32_t t = threadIdx.x;
   store_jac(tree + t * PT_WORDS, acc);

@@ -40,14 +40,11 @@
 
 namespace hm {
 
-constexpr int SA_THREADS = 256;       // A: one lane per scalar
-constexpr int SS_THREADS = 1024;      // B: one workgroup per (window, bucket range)
-constexpr uint32_t S_TASK_KEYS = 1024;
+// (SA_THREADS, SS_THREADS, S_TASK_KEYS and S_MAX_L: msm_plan.inc)
 constexpr uint32_t S_HOT = 32;
 constexpr uint32_t S_FINALIZE_SERIAL = 12;   // partials of one bucket its own lane sums; more go to a group of lanes
 constexpr uint32_t S_HOT_PER_LANE = 4;       // partials per lane of such a group
 constexpr uint32_t S_HOT_LIST = 64;
-constexpr uint32_t S_MAX_L = 1023;
 
 // ---- A: digits, balanced window widths ----------------------------------------------------------
 // Window w is `wide` bits for w < n_wide, else wide - 1 bits (n_wide * wide + (W - n_wide) * (wide - 1) = 255).
@@ -559,116 +556,34 @@ int msm_count_live_blocks(DeviceCtx& ctx, const void* const* d_columns, size_t c
 }
 
 // ---- host ----------------------------------------------------------------------------------------
-static int env_int(const char* name, int dflt) {
-  const char* v = std::getenv(name);
-  return v && *v ? std::atoi(v) : dflt;
-}
-
-bool msm_small_applies(size_t n, uint32_t c, bool single_set) {
-  static const int enabled = env_int("HALO2_MI355X_SMALL_PLAN", 1);     // 0: measurement only (A/B against the general pipeline)
-  return enabled && !single_set && n >= 1 && n < (1u << 19) && c >= 2 && c <= 15;
-}
-
+// Every size, the workspace layout and the grids come from msm_small_plan (msm_plan.inc).
 int msm_issue_small(DeviceCtx& ctx, int slot, const uint32_t* const* d_scalars_list, uint32_t group, const uint32_t* d_xy,
                     const uint8_t* d_inf, size_t n, uint32_t c, hipStream_t stream) {
   MsmSlot& sl = ctx.msm_slots[slot];
-  if (group < 1 || group > (uint32_t)HM_MSM_GROUP) return hm_fail(HM_ERR_INTERNAL, "msm (small plan): bad group size");
-  static const int env_L = env_int("HALO2_MI355X_SMALL_L", 0), env_seg = env_int("HALO2_MI355X_SMALL_SEG", 0),
-                   env_H = env_int("HALO2_MI355X_SMALL_H", 0);
-  const uint32_t W = (255 + c - 1) / c;
-  if (W > 128) return hm_fail(HM_ERR_INTERNAL, "msm: more than 128 windows");
-  // balanced widths: n_wide windows of `wide` bits, the rest of wide - 1 (wide <= c)
-  const uint32_t base_bits = 255 / W, n_wide_raw = 255 - base_bits * W;
-  const uint32_t wide = n_wide_raw ? base_bits + 1 : base_bits, n_wide = n_wide_raw ? n_wide_raw : W;
-  const uint32_t NB = 1u << (wide - 1);
-  const uint64_t pairs_max = (uint64_t)n * W;
-  // bucket-range splits per window: more sort workgroups once one workgroup per window streams too long
-  uint32_t H = 1;
-  while (H < 8 && (uint64_t)n / H > (1u << 15) && NB / (2 * H) >= 64) H *= 2;
-  if (env_H > 0) H = (uint32_t)env_H;
-  while (H > 1 && NB / H < 2) H /= 2;
-  const uint32_t NBh = NB / H, V = W * H;
-  // Task length.  K3's chain costs L mixed additions, D then sums ~mean/L Jacobian partials per bucket (1.6x
-  // the instructions each): short tasks only pay while they are needed to fill the chip.
-  const double mean = (double)n / (double)NB;
-  uint32_t L = (uint32_t)(mean + 4.0 * std::sqrt(mean) + 8.0);
-  {
-    uint64_t by_fill = pairs_max / 327680;
-    if (by_fill < 16) by_fill = 16;          // measured (tools/small_tune.sh): 12 .. 16 beats 8 at every size below 2^18
-    if (by_fill < L) L = (uint32_t)by_fill;
-  }
-  if (env_L > 0) L = (uint32_t)env_L;
-  if (L < 2) L = 2;
-  if (L > S_MAX_L) L = S_MAX_L;
-  // D's segment length: at most one 256-lane workgroup per CU over all virtual windows -- one wave per SIMD;
-  // what costs is the depth of a lane's chain (2 SEG additions + a log2(NB)-bit multiple), not the work
-  uint32_t SEG = 2;
-  while (SEG < NBh && (uint64_t)V * ((NBh / SEG + WIN_THREADS - 1) / WIN_THREADS) > 256) ++SEG;
-  // a group multiplies the workgroups: then count WAVES with a segment to sum -- one per SIMD (1024) over the whole group
-  // (never fewer than one wave per virtual window and element: 64 segments there is the coarsest useful cut)
-  if (group > 1)
-    while (SEG < NBh && (NBh + SEG - 1) / SEG > 64 && (uint64_t)V * group * (((NBh + SEG - 1) / SEG + 63) / 64) > 1024) ++SEG;
-  if (env_seg > 0) SEG = (uint32_t)env_seg;
-  if (SEG > NBh) SEG = NBh;
-  const uint32_t nseg = (NBh + SEG - 1) / SEG;
-  const uint32_t G1n = (nseg + WIN_THREADS - 1) / WIN_THREADS;
-  // sum over all buckets of ceil(cnt / L) <= pairs / L + number of buckets
-  const uint64_t T_max = pairs_max / L + (uint64_t)V * NBh + 64;
-
-  auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += align(bytes); return o; };
-  const size_t o_digits = carve((size_t)((n + SA_THREADS - 1) / SA_THREADS * SA_THREADS) * W * 4);   // rows padded to whole blocks
-  const size_t o_toff = carve((size_t)V * (NBh + 2) * 4);
-  const size_t o_gctr = carve(16);
-  const size_t o_nz = carve((size_t)V * NBh * 4);
-  const size_t o_nzc = carve((size_t)V * 4);
-  const size_t o_desc = carve(T_max * 16);
-  const size_t o_sorted = carve(pairs_max * 4);
-  const size_t o_partial = carve(T_max * PT_WORDS * 4);
-  const size_t o_seg1 = carve((size_t)V * G1n * PT_WORDS * 4);
-  const size_t o_blkidx = carve(((n + SA_THREADS - 1) / SA_THREADS) * 4);
-  const size_t ws_stride = off;                                   // one element's arrays; the group's results follow them all
-  const uint32_t res_stride = 4 + W * 32;                         // words per element: totals, then the window sums
-  const size_t o_res = ws_stride * group;
-  const size_t o_live = o_res + (((size_t)group * res_stride * 4 + 255) & ~(size_t)255);     // the group's survivor counters, together
+  const MsmSmallPlan p = msm_small_plan(n, group, c);
+  if (p.err != MSM_PLAN_OK) return hm_fail(p.err, p.err_msg);
+  const uint32_t W = p.W, wide = p.wide, n_wide = p.n_wide, H = p.H, NBh = p.NBh, L = p.L, SEG = p.SEG, G1n = p.G1n, res_stride = p.res_stride;
+  const size_t ws_stride = p.ws_stride;
   const size_t cap_before = sl.ws.cap;
-  uint8_t* ws = (uint8_t*)sl.ws.ensure(o_live + (size_t)HM_MSM_GROUP * 4);
+  uint8_t* ws = (uint8_t*)sl.ws.ensure(p.ws_bytes);
   if (sl.ws.cap != cap_before) sl.live_ptr = nullptr;             // a fresh allocation (even at the old address) holds no cleared counters
   if (!ws) return hm_fail(HM_ERR_HIP, "msm (small plan): workspace allocation failed");
-  int32_t* d_digits = (int32_t*)(ws + o_digits);
-  uint32_t* d_toff = (uint32_t*)(ws + o_toff);
-  uint32_t* d_gctr = (uint32_t*)(ws + o_gctr);
-  uint32_t* d_nz = (uint32_t*)(ws + o_nz);
-  uint32_t* d_nzc = (uint32_t*)(ws + o_nzc);
-  uint4* d_desc = (uint4*)(ws + o_desc);
-  uint32_t* d_sorted = (uint32_t*)(ws + o_sorted);
-  uint32_t* d_partial = (uint32_t*)(ws + o_partial);
-  uint32_t* d_seg1 = (uint32_t*)(ws + o_seg1);
-  uint32_t* d_blkidx = (uint32_t*)(ws + o_blkidx);
-  uint32_t* d_live = (uint32_t*)(ws + o_live);
-  uint32_t* d_tot = (uint32_t*)(ws + o_res);
-  uint32_t* d_win = d_tot + 4;
+  const auto at = [&](MsmSmallRegion r) { return (uint32_t*)(ws + p.region[r].off); };
+  int32_t* d_digits = (int32_t*)at(MSR_DIGITS);
+  uint4* d_desc = (uint4*)at(MSR_DESC);
+  uint32_t *d_toff = at(MSR_TOFF), *d_gctr = at(MSR_GCTR), *d_nz = at(MSR_NZ), *d_nzc = at(MSR_NZC), *d_sorted = at(MSR_SORTED);
+  uint32_t *d_partial = at(MSR_PARTIAL), *d_seg1 = at(MSR_SEG1), *d_blkidx = at(MSR_BLKIDX), *d_live = at(MSR_LIVE);
+  uint32_t* d_tot = at(MSR_RES);
 
-  const size_t lds_sort = ((size_t)((NBh + 1 + 31) & ~31u) + 2 * S_TASK_KEYS + 32) * 4;
   if (!ctx.msm_small_attr_set) {
     HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_s_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(((size_t)16416 + 2 * S_TASK_KEYS + 32) * 4)));
+                                     (int)MSM_S_LDS_SORT));
     ctx.msm_small_attr_set = true;
   }
-  int rc = msm_slot_prepare(sl);
+  const int rc = msm_slot_prepare(sl);
   if (rc != HM_OK) return rc;
   hipEvent_t* ev = sl.ev;
-  sl.SW = W;
-  sl.c = wide;
-  sl.W = W;
-  sl.T_max = T_max;
-  sl.d_win = d_win;
-  sl.d_tot = d_tot;
-  sl.balanced = true;
-  sl.group = group;
-  sl.res_stride = res_stride;
-  sl.phase_timed = msm_phase_timing(true);
+  sl.describe(W, wide, W, group, res_stride, p.T_max, d_tot, true, msm_phase_timing(true));
   const bool pt = sl.phase_timed;
   for (uint32_t w = 0; w < W; ++w) sl.win_bits[w] = (uint8_t)(w < n_wide ? wide : wide - 1);
 
@@ -681,30 +596,26 @@ int msm_issue_small(DeviceCtx& ctx, int slot, const uint32_t* const* d_scalars_l
   if (!counters_clean) HM_HIP_CHECK(hipMemsetAsync(d_live, 0, (size_t)HM_MSM_GROUP * 4, stream));
   SmallGroupScalars gs;
   for (uint32_t e = 0; e < (uint32_t)HM_MSM_GROUP; ++e) gs.s[e] = d_scalars_list[e < group ? e : 0];
-  hipLaunchKernelGGL(msm_s_digits_kernel, dim3((uint32_t)((n + SA_THREADS - 1) / SA_THREADS), group), dim3(SA_THREADS), 0, stream,
-                     gs, d_inf, d_digits, (uint32_t)n, wide, n_wide, W, d_gctr, d_blkidx, d_live, ws_stride);
+  launch(msm_s_digits_kernel, p.launch[MSL_DIGITS], stream, gs, d_inf, d_digits, (uint32_t)n, wide, n_wide, W, d_gctr, d_blkidx, d_live, ws_stride);
   HM_HIP_CHECK(hipGetLastError());
   if (pt) HM_HIP_CHECK(hipEventRecord(ev[1], stream));
-  hipLaunchKernelGGL(msm_s_sort_kernel, dim3(V, group), dim3(SS_THREADS), lds_sort, stream, (const int32_t*)d_digits, d_toff, d_gctr, d_desc,
-                     d_sorted, d_nz, d_nzc, (uint32_t)n, NBh, H, L, (const uint32_t*)d_blkidx, (const uint32_t*)d_live, ws_stride);
+  launch(msm_s_sort_kernel, p.launch[MSL_SORT], stream, d_digits, d_toff, d_gctr, d_desc, d_sorted, d_nz, d_nzc, (uint32_t)n, NBh, H, L, d_blkidx,
+         d_live, ws_stride);
   HM_HIP_CHECK(hipGetLastError());
   if (pt) HM_HIP_CHECK(hipEventRecord(ev[2], stream));
   if (pt) HM_HIP_CHECK(hipEventRecord(ev[5], stream));
-  hipLaunchKernelGGL(msm_s_accumulate_kernel, dim3((uint32_t)((T_max + ACC_THREADS - 1) / ACC_THREADS), group), dim3(ACC_THREADS), 0, stream,
-                     (const uint32_t*)d_sorted, (const uint4*)d_desc, (const uint32_t*)d_gctr, d_xy, d_partial, ws_stride);
+  launch(msm_s_accumulate_kernel, p.launch[MSL_ACCUMULATE], stream, d_sorted, d_desc, d_gctr, d_xy, d_partial, ws_stride);
   HM_HIP_CHECK(hipGetLastError());
   if (pt) HM_HIP_CHECK(hipEventRecord(ev[6], stream));
   if (pt) HM_HIP_CHECK(hipEventRecord(ev[3], stream));
-  hipLaunchKernelGGL(msm_s_reduce1_kernel, dim3(G1n, V, group), dim3(WIN_THREADS), 0, stream, d_partial, (const uint32_t*)d_toff,
-                     (const uint32_t*)d_nz, (const uint32_t*)d_nzc, d_seg1, NBh, H, SEG, G1n, ws_stride);
+  launch(msm_s_reduce1_kernel, p.launch[MSL_REDUCE1], stream, d_partial, d_toff, d_nz, d_nzc, d_seg1, NBh, H, SEG, G1n, ws_stride);
   // The last kernel writes the chain's results STRAIGHT into the slot's pinned, device-mapped landing zone: no D2H copy.
   // (A hipMemcpyAsync of a group's 17.5 KiB blocked the SUBMITTING thread whenever three such copies were already
   // outstanding -- the fourth chain of a sparse phase was enqueued 6.8 ms late: tools/phase_mix.py, HALO2 trace -- the
   // general pipeline's 144-byte copies do not.)  The results are visible to the host once ev[4] has completed.
   uint32_t* d_land = nullptr;
   HM_HIP_CHECK(hipHostGetDevicePointer((void**)&d_land, sl.h_land, 0));
-  hipLaunchKernelGGL(msm_s_reduce2_kernel, dim3(W, group), dim3(WIN_THREADS), 0, stream, (const uint32_t*)d_seg1, H * G1n, d_land + 4,
-                     (const uint32_t*)d_gctr, d_land, ws_stride, res_stride, d_live);
+  launch(msm_s_reduce2_kernel, p.launch[MSL_REDUCE2], stream, d_seg1, p.segs_per_window, d_land + 4, d_gctr, d_land, ws_stride, res_stride, d_live);
   HM_HIP_CHECK(hipGetLastError());
   HM_HIP_CHECK(hipEventRecord(ev[4], stream));
   sl.live_ptr = d_live;

@@ -1173,3 +1173,50 @@ def test_host_pointer_forms_through_both_copy_paths(cref, mode):
             assert st1.host_copies_staged == st0.host_copies_staged and st1.host_copies_direct > st0.host_copies_direct
     finally:
         _lib.check(lib.hm_set_host_copies(0))
+
+
+# ---- the routes of the launch plan (csrc/msm_plan.inc), pinned against the parent of the plan refactor --------------------------------
+@pytest.fixture(scope="module")
+def plan_pins():
+    """the host plan through libhm_hostcheck.so, and `pairs` / `tasks` as the library gave them before the plan became a function
+    of its own (tests/golden/msm_stats_parent.json, written by tests/golden/gen_msm_stats_parent.py)"""
+    import json
+    import os
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    sys.path.insert(0, os.path.join(here, "golden"))
+    import gen_msm_plans
+    with open(os.path.join(here, "golden", "msm_stats_parent.json")) as f:
+        return gen_msm_plans, gen_msm_plans.Planner(), json.load(f)["cases"]
+
+
+@pytest.mark.parametrize("case", ["small_plan_1000", "small_group_of_three_4096", "general_plain_2p19_77", "table_2p17",
+                                  "table_2p17_group_of_three", "table_2p20"])
+def test_routes_of_the_launch_plan_against_the_parent(plan_pins, case):
+    """One case per route, on seeded inputs of bench.bench_inputs: the result is the closed form, the window the library used is
+    the host plan's, and the pair and task counts are the parent's -- `tasks` moves as soon as the task length L or the bound
+    T_max of the plan drift."""
+    import msm_stats_cases
+    gen, pl, parent = plan_pins
+    n, layout, columns = msm_stats_cases.CASES[case]
+    got, exp, st = msm_stats_cases.run_case(case)
+    assert np.array_equal(got, exp)
+    if layout == "table":
+        if n == (1 << 17) and not st["window_bits"] >= 17:      # the threshold size only: above it a registration without a table fails below
+            pytest.skip(f"the registration did not build a fixed-base table with a shared bucket set: {st}")
+        c = pl.window(n)[2]
+        row = dict(zip(gen.PLAN_COLUMNS, (int(x) for x in pl.plan_row(n, columns, c))))
+        assert row["err"] == 0 and row["route"] == gen.ENUMS["route"].index("general") and row["SW"] == columns
+        want = (row["c"], row["W"])
+    elif n < (1 << 19):
+        c = pl.window(n, 0, n)[1]                     # dense columns: every 256-row block survives
+        row = dict(zip(gen.SMALL_COLUMNS, (int(x) for x in pl.small_row(n, columns, n, 0, c))))
+        assert row["err"] == 0
+        want = (row["wide"], row["W"])                # the five-launch chain reports the width of its balanced windows
+    else:
+        row = dict(zip(gen.PLAN_COLUMNS, (int(x) for x in pl.plan_row(n, 1, 0))))
+        assert row["err"] == 0 and row["route"] == gen.ENUMS["route"].index("general")
+        want = (row["c"], row["W"])
+    assert (st["window_bits"], st["windows"]) == want
+    assert (st["pairs"], st["tasks"]) == (parent[case]["pairs"], parent[case]["tasks"])
+    assert (st["window_bits"], st["windows"]) == (parent[case]["window_bits"], parent[case]["windows"])
