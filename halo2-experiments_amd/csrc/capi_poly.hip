@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 
+#include "graph_lower.h"
 #include "hm_internal.h"
 #include "host_fr.h"
 
@@ -495,72 +496,55 @@ int hm_graph_create(const uint32_t* calcs, size_t n_calc, const uint64_t* consta
   return graph_create(*ctx, calcs, n_calc, constants, n_const, n_dynamic, rotations, n_rot, n_columns, n_intermediates, out_handle);
 } HM_API_CATCH("hm_graph_create")
 
-static int graph_evaluate_entry(const char* who, uint64_t handle, const void* const* d_columns, size_t n_columns,
-                                const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t log_size, uint32_t segments, void* d_values,
-                                uint32_t flags, void* stream) {
-  if (!d_values || (n_columns && !d_columns) || (n_dynamic && !dynamic_constants))
+// every hm_graph_evaluate*_dev: null arguments, the context and its lock, the program, the call counter, graph_run
+static int graph_entry(const char* who, uint64_t handle, const GraphCall& c, void* stream) {
+  if (!c.d_values || (c.n_columns && (!c.bases || (c.kind != GRAPH_SINGLE && !c.strides))) || (c.n_dyn && !c.dyn_ext))
     return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
   DeviceCtx* ctx = ctx_for_current_device();
   if (!ctx) return HM_ERR_NO_DEVICE;
   std::lock_guard<std::mutex> lk(ctx->mu);
   for (auto& g : ctx->graphs)
     if (g->handle == handle) {
-      count_vector(*ctx, HM_STAT_GRAPH_EVALUATE, 1, log_size < 40 ? (uint64_t)segments << log_size : 0);
-      return graph_evaluate(*ctx, *g, d_columns, n_columns, dynamic_constants, n_dynamic, log_size, segments, d_values, flags,
-                            (hipStream_t)stream);
+      const bool countable = c.kind == GRAPH_SINGLE ? c.log_size < 40 : c.log_size < 32 && c.units < (1ull << 32);
+      count_vector(*ctx, HM_STAT_GRAPH_EVALUATE, 1, countable ? ((uint64_t)c.segments << c.log_size) * c.units : 0);
+      return graph_run(*ctx, *g, c, (hipStream_t)stream);
     }
   return hm_fail(HM_ERR_NOT_FOUND, std::string(who) + ": unknown program handle");
 }
 
 int hm_graph_evaluate_dev(uint64_t handle, const void* const* d_columns, size_t n_columns, const uint64_t* dynamic_constants,
                           size_t n_dynamic, uint32_t log_size, void* d_values, void* stream) try {
-  return graph_evaluate_entry("hm_graph_evaluate_dev", handle, d_columns, n_columns, dynamic_constants, n_dynamic, log_size, 1, d_values, 0, stream);
+  return graph_entry("hm_graph_evaluate_dev", handle,
+                     {GRAPH_SINGLE, n_columns, 1, n_dynamic, log_size, 1, 0, d_values, 0, d_columns, nullptr, dynamic_constants}, stream);
 } HM_API_CATCH("hm_graph_evaluate_dev")
 
 int hm_graph_evaluate_flags_dev(uint64_t handle, const void* const* d_columns, size_t n_columns, const uint64_t* dynamic_constants,
                                 size_t n_dynamic, uint32_t log_size, void* d_values, uint32_t flags, void* stream) try {
-  return graph_evaluate_entry("hm_graph_evaluate_flags_dev", handle, d_columns, n_columns, dynamic_constants, n_dynamic, log_size, 1, d_values,
-                              flags, stream);
+  return graph_entry("hm_graph_evaluate_flags_dev", handle,
+                     {GRAPH_SINGLE, n_columns, 1, n_dynamic, log_size, 1, flags, d_values, 0, d_columns, nullptr, dynamic_constants}, stream);
 } HM_API_CATCH("hm_graph_evaluate_flags_dev")
 
 int hm_graph_evaluate_segments_dev(uint64_t handle, const void* const* d_columns, size_t n_columns, const uint64_t* dynamic_constants,
                                    size_t n_dynamic, uint32_t log_segment, uint32_t segments, void* d_values, uint32_t flags, void* stream) try {
-  return graph_evaluate_entry("hm_graph_evaluate_segments_dev", handle, d_columns, n_columns, dynamic_constants, n_dynamic, log_segment,
-                              segments, d_values, flags, stream);
+  return graph_entry("hm_graph_evaluate_segments_dev", handle,
+                     {GRAPH_SINGLE, n_columns, 1, n_dynamic, log_segment, segments, flags, d_values, 0, d_columns, nullptr, dynamic_constants}, stream);
 } HM_API_CATCH("hm_graph_evaluate_segments_dev")
 
 int hm_graph_evaluate_circuits_dev(uint64_t handle, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
                                    size_t circuits, const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t log_size, uint32_t segments,
                                    void* d_values, uint32_t flags, void* stream) try {
-  if (!d_values || (n_columns && (!column_bases || !column_strides)) || (n_dynamic && !dynamic_constants))
-    return hm_fail(HM_ERR_BAD_ARG, "hm_graph_evaluate_circuits_dev: null argument");
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  for (auto& g : ctx->graphs)
-    if (g->handle == handle) {
-      count_vector(*ctx, HM_STAT_GRAPH_EVALUATE, 1, log_size < 32 && circuits < (1ull << 32) ? ((uint64_t)segments << log_size) * circuits : 0);
-      return graph_evaluate_circuits(*ctx, *g, column_bases, column_strides, n_columns, circuits, dynamic_constants, n_dynamic, log_size, segments,
-                                     d_values, flags, (hipStream_t)stream);
-    }
-  return hm_fail(HM_ERR_NOT_FOUND, "hm_graph_evaluate_circuits_dev: unknown program handle");
+  return graph_entry("hm_graph_evaluate_circuits_dev", handle,
+                     {GRAPH_CIRCUITS, n_columns, circuits, n_dynamic, log_size, segments, flags, d_values, 0, column_bases, column_strides, dynamic_constants},
+                     stream);
 } HM_API_CATCH("hm_graph_evaluate_circuits_dev")
 
 int hm_graph_evaluate_proofs_dev(uint64_t handle, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
                                  size_t proofs, const uint64_t* dynamic_constants, size_t n_dynamic, uint32_t log_size, uint32_t segments,
                                  void* d_values, uint64_t values_stride, uint32_t flags, void* stream) try {
-  if (!d_values || (n_columns && (!column_bases || !column_strides)) || (n_dynamic && !dynamic_constants))
-    return hm_fail(HM_ERR_BAD_ARG, "hm_graph_evaluate_proofs_dev: null argument");
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  for (auto& g : ctx->graphs)
-    if (g->handle == handle) {
-      count_vector(*ctx, HM_STAT_GRAPH_EVALUATE, 1, log_size < 32 && proofs < (1ull << 32) ? ((uint64_t)segments << log_size) * proofs : 0);
-      return graph_evaluate_proofs(*ctx, *g, column_bases, column_strides, n_columns, proofs, dynamic_constants, n_dynamic, log_size, segments,
-                                   d_values, values_stride, flags, (hipStream_t)stream);
-    }
-  return hm_fail(HM_ERR_NOT_FOUND, "hm_graph_evaluate_proofs_dev: unknown program handle");
+  return graph_entry("hm_graph_evaluate_proofs_dev", handle,
+                     {GRAPH_PROOFS, n_columns, proofs, n_dynamic, log_size, segments, flags, d_values, values_stride, column_bases, column_strides,
+                      dynamic_constants},
+                     stream);
 } HM_API_CATCH("hm_graph_evaluate_proofs_dev")
 
 // ---------------------------------------------------------------------------------------------
@@ -661,7 +645,8 @@ static int quotient_partials(const char* who, DeviceCtx& ctx, uint64_t program, 
   for (size_t i = 0; i < n_columns; ++i) cols[i] = d_on_cosets ? d_on_cosets[i] : nullptr;
   for (size_t j = 0; j < T; ++j) cols[todo[j]] = on_cosets + row * count * j;
   HM_HIP_CHECK(hipMemsetAsync(d_partials, 0, row * count, st));                // PreviousValue: upstream starts h at zero
-  rc = graph_evaluate(ctx, *g, cols.data(), n_columns, dynamic_constants, n_dynamic, log_n, (uint32_t)count, d_partials, HM_GRAPH_COLUMNS_INTERNAL, st);
+  rc = graph_run(ctx, *g, {GRAPH_SINGLE, n_columns, 1, n_dynamic, log_n, (uint32_t)count, HM_GRAPH_COLUMNS_INTERNAL, d_partials, 0, cols.data(), nullptr,
+                           dynamic_constants}, st);
   if (rc != HM_OK) return rc;
   count_vector(ctx, HM_STAT_GRAPH_EVALUATE, 1, (uint64_t)count << log_n);
   rc = ntt_cosets_inverse_run(ctx, (uint32_t*)d_partials, (uint32_t)count, om_inv.l, log_n, n_inv.l, shift_inv[0].l, st);

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 #include <map>
 
@@ -46,12 +47,12 @@ namespace hm {
 // pointer to a device copy (every table access an ordinary global load, a 72-byte argument block whatever the program's
 // shape), and tests/test_isa.py asserts on the built objects that no kernel of the library addresses a vector memory
 // instruction through its kernarg pointer.  tests/test_evaluation.py runs 256 columns, short-period columns and 16
-// per-call constants through it.
-struct GraphColumns {
-  const uint32_t* p[GE_MAX_COLUMNS];
-  uint32_t dyn[GE_MAX_DYN * 9];   // challenges, beta, gamma, theta, y ... of THIS proof, internal form
-  uint32_t n_static;              // constants [0, n_static) come from the program, [n_static, ..) from dyn
-};
+// per-call constants through it.  The three argument blocks (GraphColumns, GraphCircuitColumns, GraphProofColumns): graph_lower.h.
+static_assert(GE_THREADS == 256 && HM_GRAPH_COLUMNS_INTERNAL == 1, "graph_lower.h: graph_launch_plan, graph_check_call");
+static_assert(offsetof(GraphColumns, p) == 0 && offsetof(GraphCircuitColumns, p) == 0 && offsetof(GraphProofColumns, p) == 0 &&
+                  offsetof(GraphCircuitColumns, stride) == sizeof(void*) * GE_MAX_COLUMNS &&
+                  offsetof(GraphProofColumns, stride) == sizeof(void*) * GE_MAX_COLUMNS,
+              "graph_run fills the pointers, then the strides, of whichever block the kind has");
 
 // where graph_evaluate_kernel's lane takes what the program names (graph_interp.h: Source)
 template <bool INTERNAL>
@@ -63,11 +64,7 @@ struct EvalSource {
   __device__ __forceinline__ uint32_t n_static() const { return columns->n_static; }
   __device__ __forceinline__ uint32_t dyn(uint32_t word) const { return columns->dyn[word]; }
   __device__ __forceinline__ Fr column(uint32_t src) const {
-    // two's complement: a negative rotation wraps -- inside the row's SEGMENT (mask = segment length - 1; one segment = the
-    // whole domain in the ordinary call, one coset of the extended domain in hm_graph_evaluate_segments_dev)
-    uint64_t row = (idx & ~mask) | ((idx + (uint64_t)(int64_t)rotations[gsrc_rot(src)]) & mask);
-    const uint32_t lr = gsrc_log_rows(src);          // a short column (the vanishing polynomial's inverse pattern) is periodic
-    if (lr != 0) row &= (1ull << lr) - 1ull;
+    const uint64_t row = graph_source_row(idx, (int64_t)rotations[gsrc_rot(src)], mask, gsrc_log_rows(src));
     const uint32_t* cell = columns->p[gsrc_column(src)] + row * 8;
     return INTERNAL ? ge_from_internal(cell) : ge_from_ext(cell);
   }
@@ -88,11 +85,7 @@ __global__ __launch_bounds__(GE_THREADS) void graph_evaluate_kernel(const GraphC
     uint32_t* vrow = values + idx * 8;
     const EvalSource<INTERNAL> from{columns, rotations, idx, mask, vrow};
     const Fr res = ge_run(from, consts, calcs, n_calc, result_src, result_prev, scratch, T, lane_slot);
-    uint32_t w[8];
-    fe_to_ext(w, ge_reduce(res));
-    uint4* dst = reinterpret_cast<uint4*>(vrow);
-    dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    ge_store_ext(vrow, ge_reduce(res));
   }
 }
 
@@ -157,59 +150,6 @@ void graph_release(GraphProgram& g) {
   }
 }
 
-// rows = segments << log_segment; rotations wrap inside a segment (segments == 1: the ordinary evaluation over 2^log_segment rows)
-int graph_evaluate(DeviceCtx& ctx, GraphProgram& g, const void* const* d_columns, size_t n_columns, const uint64_t* dyn_ext,
-                   size_t n_dyn, uint32_t log_size, uint32_t segments, void* d_values, uint32_t flags, hipStream_t stream) {
-  if (flags & ~(uint32_t)HM_GRAPH_COLUMNS_INTERNAL) return hm_fail(HM_ERR_BAD_ARG, "graph: unknown flag");
-  const bool internal_cols = (flags & HM_GRAPH_COLUMNS_INTERNAL) != 0;
-  GraphVariant& v = g.variant[internal_cols ? 1 : 0];
-  if (!v.ready) {
-    const int rc = graph_lower(g, internal_cols, v);
-    if (rc != HM_OK) return rc;
-  }
-  if (n_columns != g.n_columns) return hm_fail(HM_ERR_BAD_ARG, "graph: the program was built for another number of columns");
-  if (n_dyn != g.n_dynamic) return hm_fail(HM_ERR_BAD_ARG, "graph: the program was built for another number of per-call constants");
-  if (log_size > 30) return hm_fail(HM_ERR_BAD_ARG, "graph: log_size > 30");
-  if (segments == 0 || ((uint64_t)segments << log_size) > (1ull << 32)) return hm_fail(HM_ERR_BAD_ARG, "graph: segments must be >= 1 and rows <= 2^32");
-  const uint64_t size = (uint64_t)segments << log_size;
-  // enough lanes to fill the chip, few enough that the intermediates' scratch stays cache-sized
-  // 93 VGPRs: five waves per SIMD fit, i.e. five 256-lane workgroups per CU -- the interpreter's loads from the scratch
-  // (Infinity Cache latency) need them: measured on the MerkleSumTree program over 2^21 rows, 512 / 768 / 1024 / 1280 / 2048
-  // workgroups: 12.4 / 10.5 / 10.3 / 9.9 / 10.0 ms.  At 1280 the kernel issues 4.6e11 VALU wave-instructions per second
-  // (SQ_INSTS_VALU 4.21e9 in 9.2 ms): it is bound by VALU issue like K3 and the NTT, no longer by its scratch traffic.
-  static const uint32_t max_blocks = [] { const char* v = std::getenv("HALO2_MI355X_GRAPH_BLOCKS"); return (uint32_t)(v && *v ? std::atoi(v) : 1280); }();
-  uint32_t blocks = (uint32_t)std::min<uint64_t>((size + GE_THREADS - 1) / GE_THREADS, max_blocks);
-  const uint32_t T = blocks * GE_THREADS;
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  const size_t b_scratch = (size_t)v.n_slots * 9 * T * 4;
-  uint8_t* buf = (uint8_t*)slot->scratch.ensure(b_scratch);
-  if (!buf) return hm_fail(HM_ERR_HIP, "graph: scratch allocation failed");
-  GraphColumns cols;
-  std::memset(&cols, 0, sizeof cols);
-  for (size_t i = 0; i < n_columns; ++i) {
-    if (!d_columns[i]) return hm_fail(HM_ERR_BAD_ARG, "graph: null column pointer");
-    cols.p[i] = (const uint32_t*)d_columns[i];
-  }
-  cols.n_static = g.n_static;
-  for (size_t i = 0; i < n_dyn; ++i) host::fr_to_internal9(host::fr_load(dyn_ext + 4 * i), &cols.dyn[9 * i]);
-  GraphColumns* d_cols = (GraphColumns*)slot->args.ensure(sizeof(GraphColumns));
-  if (!d_cols) return hm_fail(HM_ERR_HIP, "graph: argument buffer allocation failed");
-  // pageable source: the runtime has taken its copy of `cols` when this returns; the copy itself is ordered on `stream`
-  // ahead of the launch and behind the previous launch that read the buffer
-  HM_HIP_CHECK(hipMemcpyAsync(d_cols, &cols, sizeof cols, hipMemcpyHostToDevice, stream));
-  if (internal_cols)
-    hipLaunchKernelGGL(graph_evaluate_kernel<true>, dim3(blocks), dim3(GE_THREADS), 0, stream, (const GraphColumns*)d_cols,
-                       (const uint32_t*)g.d_consts, (const int32_t*)g.d_rot, (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src,
-                       v.result_prev, (uint32_t*)buf, (uint32_t*)d_values, size, log_size);
-  else
-    hipLaunchKernelGGL(graph_evaluate_kernel<false>, dim3(blocks), dim3(GE_THREADS), 0, stream, (const GraphColumns*)d_cols,
-                       (const uint32_t*)g.d_consts, (const int32_t*)g.d_rot, (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src,
-                       v.result_prev, (uint32_t*)buf, (uint32_t*)d_values, size, log_size);
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
-}
-
 // ---- several circuits of one constraint system in one launch (hm_graph_evaluate_circuits_dev) ----
 // The program is linear in PreviousValue (graph_lower.h: graph_linear_shape): value = Prev * f^T + G(row).  `circuits`
 // successive evaluations on the same values therefore fold as acc = acc * f^T + G_c(row), c = 0 .. circuits - 1, and the G_c
@@ -221,14 +161,6 @@ int graph_evaluate(DeviceCtx& ctx, GraphProgram& g, const void* const* d_columns
 // < 3r, the sum is < 6r and ge_reduce brings it back below 3r: the classes of one non-lazy MulAdd step of ge_run
 // (host_check.cpp: hc_graph_circuits_replay tracks them).  Rows run fastest inside a workgroup (thread = circuit * rows + row),
 // so that a wave reads consecutive cells of a column.
-struct GraphCircuitColumns {
-  const uint32_t* p[GE_MAX_COLUMNS];
-  uint64_t stride[GE_MAX_COLUMNS];   // u32 words from circuit c's column to circuit c + 1's; 0: one column for all circuits
-  uint32_t dyn[GE_MAX_DYN * 9];
-  uint32_t fold[9];                  // f^T, internal form
-  uint32_t n_static;
-};
-
 template <bool INTERNAL>
 struct CircuitSource {
   const GraphCircuitColumns* __restrict__ columns;
@@ -237,9 +169,7 @@ struct CircuitSource {
   __device__ __forceinline__ uint32_t n_static() const { return columns->n_static; }
   __device__ __forceinline__ uint32_t dyn(uint32_t word) const { return columns->dyn[word]; }
   __device__ __forceinline__ Fr column(uint32_t src) const {
-    uint64_t row = (idx & ~mask) | ((idx + (uint64_t)(int64_t)rotations[gsrc_rot(src)]) & mask);
-    const uint32_t lr = gsrc_log_rows(src);
-    if (lr != 0) row &= (1ull << lr) - 1ull;
+    const uint64_t row = graph_source_row(idx, (int64_t)rotations[gsrc_rot(src)], mask, gsrc_log_rows(src));
     const uint32_t col = gsrc_column(src);
     const uint32_t* cell = columns->p[col] + columns->stride[col] * circuit + row * 8;
     return INTERNAL ? ge_from_internal(cell) : ge_from_ext(cell);
@@ -292,83 +222,8 @@ __global__ __launch_bounds__(GE_THREADS) void graph_circuits_kernel(const GraphC
       }
       __syncthreads();
     }
-    if (folds) {
-      uint32_t w[8];
-      fe_to_ext(w, acc);
-      uint4* dst = reinterpret_cast<uint4*>(vrow);
-      dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-      dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
-    }
+    if (folds) ge_store_ext(vrow, acc);
   }
-}
-
-int graph_evaluate_circuits(DeviceCtx& ctx, GraphProgram& g, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
-                            size_t circuits, const uint64_t* dyn_ext, size_t n_dyn, uint32_t log_size, uint32_t segments, void* d_values,
-                            uint32_t flags, hipStream_t stream) {
-  if (flags & ~(uint32_t)HM_GRAPH_COLUMNS_INTERNAL) return hm_fail(HM_ERR_BAD_ARG, "graph: unknown flag");
-  if (circuits == 0) return hm_fail(HM_ERR_BAD_ARG, "graph: circuits must be >= 1");
-  if (n_columns > GE_MAX_COLUMNS) return hm_fail(HM_ERR_BAD_ARG, "graph: more columns than the column table holds");
-  if (n_columns != g.n_columns) return hm_fail(HM_ERR_BAD_ARG, "graph: the program was built for another number of columns");
-  if (n_dyn != g.n_dynamic) return hm_fail(HM_ERR_BAD_ARG, "graph: the program was built for another number of per-call constants");
-  if (log_size > 30) return hm_fail(HM_ERR_BAD_ARG, "graph: log_size > 30");
-  if (segments == 0 || ((uint64_t)segments << log_size) > (1ull << 32)) return hm_fail(HM_ERR_BAD_ARG, "graph: segments must be >= 1 and rows <= 2^32");
-  const uint64_t size = (uint64_t)segments << log_size;
-  if (circuits > (1ull << 32) / size) return hm_fail(HM_ERR_BAD_ARG, "graph: circuits * rows > 2^32");
-  if ((uintptr_t)d_values % 16) return hm_fail(HM_ERR_BAD_ARG, "graph: the values are not 16-byte aligned");
-  for (size_t i = 0; i < n_columns; ++i) {
-    if (!column_bases[i]) return hm_fail(HM_ERR_BAD_ARG, "graph: null column pointer");
-    if ((uintptr_t)column_bases[i] % 16) return hm_fail(HM_ERR_BAD_ARG, "graph: a column base is not 16-byte aligned");
-    if (column_strides[i] % 4) return hm_fail(HM_ERR_BAD_ARG, "graph: a column stride is not a multiple of 4 words");
-  }
-  uint32_t factor_src = 0, steps = 0;
-  if (const char* why = graph_linear_shape(g.calcs5.data(), g.calcs5.size() / 5, g.n_intermediates, &factor_src, &steps))
-    return hm_fail(HM_ERR_BAD_ARG, why);
-  const bool internal_cols = (flags & HM_GRAPH_COLUMNS_INTERNAL) != 0;
-  GraphVariant& v = g.variant[internal_cols ? 1 : 0];
-  if (!v.ready) {
-    const int rc = graph_lower(g, internal_cols, v);
-    if (rc != HM_OK) return rc;
-  }
-  // f^steps on the host (Montgomery words in, Montgomery words out); steps >= 1
-  const uint32_t fi = gsrc_index(factor_src);
-  const host::Fr4 f = host::fr_load(fi < g.n_static ? &g.consts_ext[4 * (size_t)fi] : dyn_ext + 4 * (size_t)(fi - g.n_static));
-  host::Fr4 f_pow = f;
-  for (uint32_t i = 1; i < steps; ++i) f_pow = host::fr_mul(f_pow, f);
-  // C circuits side by side in a workgroup: as many as it takes for the grid to reach graph_evaluate's block count, no more
-  // than the circuits there are.  circuits = 1 gives C = 1: graph_evaluate_kernel's shape.
-  static const uint32_t max_blocks = [] { const char* e = std::getenv("HALO2_MI355X_GRAPH_BLOCKS"); return (uint32_t)(e && *e ? std::atoi(e) : 1280); }();
-  uint32_t log_c = 0;
-  while (log_c < 8 && (1ull << log_c) < circuits && ((size << log_c) + GE_THREADS - 1) / GE_THREADS < max_blocks) ++log_c;
-  const uint64_t rows_per = GE_THREADS >> log_c;
-  const uint32_t blocks = (uint32_t)std::min<uint64_t>((size + rows_per - 1) / rows_per, max_blocks);
-  const uint32_t T = blocks * GE_THREADS;
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  const size_t b_scratch = (size_t)v.n_slots * 9 * T * 4;
-  uint8_t* buf = (uint8_t*)slot->scratch.ensure(b_scratch);
-  if (!buf) return hm_fail(HM_ERR_HIP, "graph: scratch allocation failed");
-  GraphCircuitColumns cols;
-  std::memset(&cols, 0, sizeof cols);
-  for (size_t i = 0; i < n_columns; ++i) {
-    cols.p[i] = (const uint32_t*)column_bases[i];
-    cols.stride[i] = column_strides[i];
-  }
-  cols.n_static = g.n_static;
-  for (size_t i = 0; i < n_dyn; ++i) host::fr_to_internal9(host::fr_load(dyn_ext + 4 * i), &cols.dyn[9 * i]);
-  host::fr_to_internal9(f_pow, cols.fold);
-  GraphCircuitColumns* d_cols = (GraphCircuitColumns*)slot->args.ensure(sizeof(GraphCircuitColumns));
-  if (!d_cols) return hm_fail(HM_ERR_HIP, "graph: argument buffer allocation failed");
-  HM_HIP_CHECK(hipMemcpyAsync(d_cols, &cols, sizeof cols, hipMemcpyHostToDevice, stream));
-  if (internal_cols)
-    hipLaunchKernelGGL(graph_circuits_kernel<true>, dim3(blocks), dim3(GE_THREADS), 0, stream, (const GraphCircuitColumns*)d_cols,
-                       (const uint32_t*)g.d_consts, (const int32_t*)g.d_rot, (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src,
-                       v.result_prev, (uint32_t*)buf, (uint32_t*)d_values, size, log_size, (uint32_t)circuits, log_c);
-  else
-    hipLaunchKernelGGL(graph_circuits_kernel<false>, dim3(blocks), dim3(GE_THREADS), 0, stream, (const GraphCircuitColumns*)d_cols,
-                       (const uint32_t*)g.d_consts, (const int32_t*)g.d_rot, (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src,
-                       v.result_prev, (uint32_t*)buf, (uint32_t*)d_values, size, log_size, (uint32_t)circuits, log_c);
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
 }
 
 // ---- several INDEPENDENT proofs of one constraint system in one launch (hm_graph_evaluate_proofs_dev) ----
@@ -379,12 +234,6 @@ int graph_evaluate_circuits(DeviceCtx& ctx, GraphProgram& g, const void* const* 
 // buffer.  A wave straddles proofs when a proof has fewer than 64 rows, so the table is read with an ordinary per-lane load
 // (dyn_row is a per-lane pointer; nothing assumes it uniform).  The arithmetic is ge_run's, unchanged: no bound class arises
 // that graph_evaluate_kernel does not have (constants enter as canonical internal words, < r; columns and PreviousValue as there).
-struct GraphProofColumns {
-  const uint32_t* p[GE_MAX_COLUMNS];
-  uint64_t stride[GE_MAX_COLUMNS];   // u32 words from proof b's column to proof b + 1's; 0: one column for all proofs
-  uint32_t n_static, n_dynamic;
-};
-
 template <bool INTERNAL>
 struct ProofSource {
   const GraphProofColumns* __restrict__ columns;
@@ -396,7 +245,7 @@ struct ProofSource {
   __device__ __forceinline__ uint32_t n_static() const { return columns->n_static; }
   __device__ __forceinline__ uint32_t dyn(uint32_t word) const { return dyn_table[graph_proofs_dyn(proof, n_dynamic, word)]; }   // per lane
   __device__ __forceinline__ Fr column(uint32_t src) const {
-    const uint64_t row = graph_proofs_row(idx, (int64_t)rotations[gsrc_rot(src)], mask, gsrc_log_rows(src));
+    const uint64_t row = graph_source_row(idx, (int64_t)rotations[gsrc_rot(src)], mask, gsrc_log_rows(src));
     const uint32_t col = gsrc_column(src);
     const uint32_t* cell = columns->p[col] + graph_proofs_cell(proof, row, columns->stride[col]);
     return INTERNAL ? ge_from_internal(cell) : ge_from_ext(cell);
@@ -422,79 +271,85 @@ __global__ __launch_bounds__(GE_THREADS) void graph_proofs_kernel(const GraphPro
     uint32_t* vrow = values + graph_proofs_cell(proof, idx, values_stride);
     const ProofSource<INTERNAL> from{columns, rotations, dyn_table, mask, idx, proof, n_dynamic, vrow};
     const Fr res = ge_run(from, consts, calcs, n_calc, result_src, result_prev, scratch, T, lane_slot);
-    uint32_t w[8];
-    fe_to_ext(w, ge_reduce(res));
-    uint4* dst = reinterpret_cast<uint4*>(vrow);
-    dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    ge_store_ext(vrow, ge_reduce(res));
   }
 }
 
-int graph_evaluate_proofs(DeviceCtx& ctx, GraphProgram& g, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
-                          size_t proofs, const uint64_t* dyn_ext, size_t n_dyn, uint32_t log_size, uint32_t segments, void* d_values,
-                          uint64_t values_stride, uint32_t flags, hipStream_t stream) {
-  if (flags & ~(uint32_t)HM_GRAPH_COLUMNS_INTERNAL) return hm_fail(HM_ERR_BAD_ARG, "graph: unknown flag");
-  if (proofs == 0) return hm_fail(HM_ERR_BAD_ARG, "graph: proofs must be >= 1");
-  if (n_columns > GE_MAX_COLUMNS) return hm_fail(HM_ERR_BAD_ARG, "graph: more columns than the column table holds");
-  if (n_columns != g.n_columns) return hm_fail(HM_ERR_BAD_ARG, "graph: the program was built for another number of columns");
-  if (n_dyn != g.n_dynamic) return hm_fail(HM_ERR_BAD_ARG, "graph: the program was built for another number of per-call constants");
-  if (log_size > 30) return hm_fail(HM_ERR_BAD_ARG, "graph: log_size > 30");
-  if (segments == 0 || ((uint64_t)segments << log_size) > (1ull << 32)) return hm_fail(HM_ERR_BAD_ARG, "graph: segments must be >= 1 and rows <= 2^32");
-  const uint64_t size = (uint64_t)segments << log_size;
-  if (proofs > (1ull << 32) / size) return hm_fail(HM_ERR_BAD_ARG, "graph: proofs * rows > 2^32");
-  if ((uintptr_t)d_values % 16) return hm_fail(HM_ERR_BAD_ARG, "graph: the values are not 16-byte aligned");
-  if (proofs > 1 && (values_stride < size * 8 || values_stride % 4))
-    return hm_fail(HM_ERR_BAD_ARG, "graph: the values stride must be a multiple of 4 words and hold the rows of one proof");
-  for (size_t i = 0; i < n_columns; ++i) {
-    if (!column_bases[i]) return hm_fail(HM_ERR_BAD_ARG, "graph: null column pointer");
-    if ((uintptr_t)column_bases[i] % 16) return hm_fail(HM_ERR_BAD_ARG, "graph: a column base is not 16-byte aligned");
-    if (column_strides[i] % 4) return hm_fail(HM_ERR_BAD_ARG, "graph: a column stride is not a multiple of 4 words");
+// ---- the one driver of the three kinds of call (hm_graph_evaluate*_dev, the quotient routes) ----
+// 93 VGPRs: five waves per SIMD fit, i.e. five 256-lane workgroups per CU -- the interpreter's loads from the scratch
+// (Infinity Cache latency) need them: measured on the MerkleSumTree program over 2^21 rows, 512 / 768 / 1024 / 1280 / 2048
+// workgroups: 12.4 / 10.5 / 10.3 / 9.9 / 10.0 ms.  At 1280 the kernel issues 4.6e11 VALU wave-instructions per second
+// (SQ_INSTS_VALU 4.21e9 in 9.2 ms): it is bound by VALU issue like K3 and the NTT, no longer by its scratch traffic.
+uint32_t graph_max_blocks() {      // the only reader of HALO2_MI355X_GRAPH_BLOCKS (mock.hip asks here); never below one block
+  static const uint32_t max_blocks = [] { const char* v = std::getenv("HALO2_MI355X_GRAPH_BLOCKS"); return std::max<uint32_t>((uint32_t)(v && *v ? std::atoi(v) : 1280), 1); }();
+  return max_blocks;
+}
+
+// In order: the check (graph_lower.h: graph_check_call), for circuits the linear shape and f^steps, the column format's variant, the
+// plan (graph_launch_plan), the argument block on the host -- every refusal and everything that can throw lies before the slot is
+// taken -- then the slot's scratch, the block's upload, the launch.  aux_scope records the slot's event whatever comes of those.
+int graph_run(DeviceCtx& ctx, GraphProgram& g, const GraphCall& c, hipStream_t stream) {
+  if (const char* why = graph_check_call(c, g.n_columns, g.n_dynamic)) return hm_fail(HM_ERR_BAD_ARG, why);
+  host::Fr4 f_pow = host::FR_ONE;
+  if (c.kind == GRAPH_CIRCUITS) {
+    // The program is linear in PreviousValue: f^steps on the host (Montgomery words in, Montgomery words out); steps >= 1
+    uint32_t factor_src = 0, steps = 0;
+    if (const char* why = graph_linear_shape(g.calcs5.data(), g.calcs5.size() / 5, g.n_intermediates, &factor_src, &steps))
+      return hm_fail(HM_ERR_BAD_ARG, why);
+    const uint32_t fi = gsrc_index(factor_src);
+    const host::Fr4 f = host::fr_load(fi < g.n_static ? &g.consts_ext[4 * (size_t)fi] : c.dyn_ext + 4 * (size_t)(fi - g.n_static));
+    f_pow = f;
+    for (uint32_t i = 1; i < steps; ++i) f_pow = host::fr_mul(f_pow, f);
   }
-  const bool internal_cols = (flags & HM_GRAPH_COLUMNS_INTERNAL) != 0;
+  const bool internal_cols = (c.flags & HM_GRAPH_COLUMNS_INTERNAL) != 0;
   GraphVariant& v = g.variant[internal_cols ? 1 : 0];
   if (!v.ready) {
     const int rc = graph_lower(g, internal_cols, v);
     if (rc != HM_OK) return rc;
   }
-  // graph_evaluate's grid cap and scratch rule, the lanes being proofs * rows
-  static const uint32_t max_blocks = [] { const char* e = std::getenv("HALO2_MI355X_GRAPH_BLOCKS"); return (uint32_t)(e && *e ? std::atoi(e) : 1280); }();
-  const uint64_t lanes = (uint64_t)proofs * size;
-  const uint32_t blocks = (uint32_t)std::min<uint64_t>((lanes + GE_THREADS - 1) / GE_THREADS, max_blocks);
-  const uint32_t T = blocks * GE_THREADS;
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  const size_t b_scratch = (size_t)v.n_slots * 9 * T * 4;
-  uint8_t* buf = (uint8_t*)slot->scratch.ensure(b_scratch);
-  if (!buf) return hm_fail(HM_ERR_HIP, "graph: scratch allocation failed");
-  // the argument block: the column table, then the constant table (one upload)
-  const size_t n_table = std::max<size_t>(proofs * n_dyn, 1) * 9;
-  std::vector<uint32_t> block(sizeof(GraphProofColumns) / 4 + n_table, 0);
-  GraphProofColumns& cols = *reinterpret_cast<GraphProofColumns*>(block.data());
-  for (size_t i = 0; i < n_columns; ++i) {
-    cols.p[i] = (const uint32_t*)column_bases[i];
-    cols.stride[i] = column_strides[i];
+  const GraphPlan p = graph_launch_plan(c.kind, (uint64_t)c.segments << c.log_size, c.units, v.n_slots, c.n_dyn, graph_max_blocks());
+  // the argument block: the kind's column table -- p, then stride where the kind has one, then the constants -- and, for proofs,
+  // the constant table behind it (one upload)
+  std::vector<uint32_t> block(p.args_bytes / 4, 0);
+  const uint32_t** ptrs = reinterpret_cast<const uint32_t**>(block.data());
+  uint64_t* strides = reinterpret_cast<uint64_t*>(ptrs + GE_MAX_COLUMNS);
+  for (size_t i = 0; i < c.n_columns; ++i) {
+    ptrs[i] = (const uint32_t*)c.bases[i];
+    if (c.strides) strides[i] = c.strides[i];
   }
-  cols.n_static = g.n_static;
-  cols.n_dynamic = (uint32_t)n_dyn;
-  uint32_t* table = block.data() + sizeof(GraphProofColumns) / 4;
-  for (size_t i = 0; i < proofs * n_dyn; ++i) host::fr_to_internal9(host::fr_load(dyn_ext + 4 * i), table + 9 * i);
-  uint8_t* d_block = (uint8_t*)slot->args.ensure(block.size() * 4);
-  if (!d_block) return hm_fail(HM_ERR_HIP, "graph: argument buffer allocation failed");
-  // pageable source: the runtime has taken its copy of `block` when this returns (graph_evaluate)
-  HM_HIP_CHECK(hipMemcpyAsync(d_block, block.data(), block.size() * 4, hipMemcpyHostToDevice, stream));
-  const GraphProofColumns* d_cols = (const GraphProofColumns*)d_block;
-  const uint32_t* d_table = (const uint32_t*)(d_block + sizeof(GraphProofColumns));
-  const uint64_t vstride = proofs > 1 ? values_stride : 0;
-  if (internal_cols)
-    hipLaunchKernelGGL(graph_proofs_kernel<true>, dim3(blocks), dim3(GE_THREADS), 0, stream, d_cols, d_table, (const uint32_t*)g.d_consts,
-                       (const int32_t*)g.d_rot, (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src, v.result_prev, (uint32_t*)buf,
-                       (uint32_t*)d_values, vstride, size, lanes, log_size);
-  else
-    hipLaunchKernelGGL(graph_proofs_kernel<false>, dim3(blocks), dim3(GE_THREADS), 0, stream, d_cols, d_table, (const uint32_t*)g.d_consts,
-                       (const int32_t*)g.d_rot, (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src, v.result_prev, (uint32_t*)buf,
-                       (uint32_t*)d_values, vstride, size, lanes, log_size);
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
+  uint32_t* dyn = nullptr;
+  if (c.kind == GRAPH_SINGLE) {
+    GraphColumns& cols = *reinterpret_cast<GraphColumns*>(block.data());
+    cols.n_static = g.n_static, dyn = cols.dyn;
+  } else if (c.kind == GRAPH_CIRCUITS) {
+    GraphCircuitColumns& cols = *reinterpret_cast<GraphCircuitColumns*>(block.data());
+    cols.n_static = g.n_static, dyn = cols.dyn;
+    host::fr_to_internal9(f_pow, cols.fold);
+  } else {
+    GraphProofColumns& cols = *reinterpret_cast<GraphProofColumns*>(block.data());
+    cols.n_static = g.n_static, cols.n_dynamic = (uint32_t)c.n_dyn, dyn = block.data() + sizeof(GraphProofColumns) / 4;
+  }
+  for (size_t i = 0; i < (c.kind == GRAPH_PROOFS ? c.units : 1) * c.n_dyn; ++i) host::fr_to_internal9(host::fr_load(c.dyn_ext + 4 * i), dyn + 9 * i);
+  return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
+    uint32_t* buf = (uint32_t*)slot.scratch.ensure(p.scratch_bytes);
+    if (!buf) return hm_fail(HM_ERR_HIP, "graph: scratch allocation failed");
+    uint8_t* d_block = (uint8_t*)slot.args.ensure(p.args_bytes);
+    if (!d_block) return hm_fail(HM_ERR_HIP, "graph: argument buffer allocation failed");
+    // pageable source: the runtime has taken its copy of `block` when this returns; the copy itself is ordered on `stream`
+    // ahead of the launch and behind the previous launch that read the buffer
+    HM_HIP_CHECK(hipMemcpyAsync(d_block, block.data(), p.args_bytes, hipMemcpyHostToDevice, stream));
+    if (c.kind == GRAPH_SINGLE)
+      ge_launch(internal_cols, graph_evaluate_kernel<true>, graph_evaluate_kernel<false>, p.blocks, stream, d_block, g.d_consts, g.d_rot, v.d_calcs,
+                v.n_calc, v.result_src, v.result_prev, buf, c.d_values, p.size, c.log_size);
+    else if (c.kind == GRAPH_CIRCUITS)
+      ge_launch(internal_cols, graph_circuits_kernel<true>, graph_circuits_kernel<false>, p.blocks, stream, d_block, g.d_consts, g.d_rot, v.d_calcs,
+                v.n_calc, v.result_src, v.result_prev, buf, c.d_values, p.size, c.log_size, c.units, p.log_c);
+    else
+      ge_launch(internal_cols, graph_proofs_kernel<true>, graph_proofs_kernel<false>, p.blocks, stream, d_block, d_block + sizeof(GraphProofColumns),
+                g.d_consts, g.d_rot, v.d_calcs, v.n_calc, v.result_src, v.result_prev, buf, c.d_values, c.units > 1 ? c.values_stride : 0, p.size,
+                p.lanes, c.log_size);
+    HM_HIP_CHECK(hipGetLastError());
+    return HM_OK;
+  });
 }
-
 }  // namespace hm

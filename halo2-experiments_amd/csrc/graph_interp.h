@@ -32,6 +32,19 @@ __device__ __forceinline__ Fr ge_from_internal(const uint32_t* __restrict__ p) {
   HM_DECLARE(r, GE_COLUMN_BOUND);
   return r;
 }
+// the store tail of the evaluating kernels: a value < 3r to the 8 external words of its row, as two uint4
+__device__ __forceinline__ void ge_store_ext(uint32_t* row, const Fr& v) {
+  uint32_t w[8];
+  fe_to_ext(w, v);
+  uint4* dst = reinterpret_cast<uint4*>(row);
+  dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+// host: one of two instantiations of a kernel, chosen at run time, on `blocks` workgroups of GE_THREADS lanes
+template <class... P, class... A>
+inline void ge_launch(bool first, void (*a)(P...), void (*b)(P...), uint32_t blocks, hipStream_t stream, A... args) {
+  hipLaunchKernelGGL(first ? a : b, dim3(blocks), dim3(GE_THREADS), 0, stream, (P)args...);
+}
 
 // Source: n_static() / dyn(word) -- the per-call constants behind the program's own; column(src) -- the cell a column source names
 // for this lane; previous() -- PreviousValue.

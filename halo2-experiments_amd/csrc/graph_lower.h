@@ -5,8 +5,10 @@
 // them with bound tracking, so that every decision below is tested on a machine without a GPU
 // (tests/test_graph_lowering_host.py) and against the kernel on one (tests/test_graph_programs_gpu.py).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <map>
 #include <vector>
 
@@ -57,8 +59,11 @@ constexpr uint32_t GE_MAX_DYN = 16;
 // (proofs x n_dynamic x 9 internal words).  Nothing here ever adds a proof's rows to another proof's: a rotation at the last row of
 // proof b lands on proof b's first row.  host_check.cpp runs the same functions (hc_graph_proofs_address).
 // (proofs * rows <= 2^32, so a lane fits 32 bits, and rows = 2^32 leaves room for proof 0 alone: a 32-bit division)
+// graph_source_row is the row rule of all three kernels: segment_mask = segment length - 1 (one segment = the whole domain in the
+// ordinary call, one coset of the extended domain in hm_graph_evaluate_segments_dev); a short column (the vanishing polynomial's
+// inverse pattern) is periodic.
 HM_GRAPH_HD uint32_t graph_proofs_proof(uint64_t lane, uint64_t rows) { return rows >> 32 ? 0u : (uint32_t)lane / (uint32_t)rows; }
-HM_GRAPH_HD uint64_t graph_proofs_row(uint64_t row, int64_t rotation, uint64_t segment_mask, uint32_t log_rows) {
+HM_GRAPH_HD uint64_t graph_source_row(uint64_t row, int64_t rotation, uint64_t segment_mask, uint32_t log_rows) {
   uint64_t r = (row & ~segment_mask) | ((row + (uint64_t)rotation) & segment_mask);      // two's complement: a negative rotation wraps
   if (log_rows != 0) r &= (1ull << log_rows) - 1ull;
   return r;
@@ -135,6 +140,90 @@ inline const char* graph_linear_shape(const uint32_t* calcs5, size_t n_calc, uin
   *factor_src = factor;
   *steps = count;
   return nullptr;
+}
+
+// ---- one call of the evaluator: what it is, whether it is admitted, how it is launched (graph.hip: graph_run) ----
+// The argument blocks as the kernels read them (graph.hip says why they travel through a device buffer).
+struct GraphColumns {
+  const uint32_t* p[GE_MAX_COLUMNS];
+  uint32_t dyn[GE_MAX_DYN * 9];   // challenges, beta, gamma, theta, y ... of THIS proof, internal form
+  uint32_t n_static;              // constants [0, n_static) come from the program, [n_static, ..) from dyn
+};
+struct GraphCircuitColumns {
+  const uint32_t* p[GE_MAX_COLUMNS];
+  uint64_t stride[GE_MAX_COLUMNS];   // u32 words from circuit c's column to circuit c + 1's; 0: one column for all circuits
+  uint32_t dyn[GE_MAX_DYN * 9];
+  uint32_t fold[9];                  // f^T, internal form
+  uint32_t n_static;
+};
+struct GraphProofColumns {           // followed by the constant table: proofs x n_dynamic x 9 internal words
+  const uint32_t* p[GE_MAX_COLUMNS];
+  uint64_t stride[GE_MAX_COLUMNS];   // u32 words from proof b's column to proof b + 1's; 0: one column for all proofs
+  uint32_t n_static, n_dynamic;
+};
+
+enum GraphCallKind : uint32_t { GRAPH_SINGLE = 0, GRAPH_CIRCUITS = 1, GRAPH_PROOFS = 2 };
+struct GraphCall {
+  GraphCallKind kind;
+  size_t n_columns, units, n_dyn;    // units: circuits or proofs (1 for the single kind); n_dyn: per-call constants of ONE unit
+  uint32_t log_size, segments, flags;
+  const void* d_values;
+  uint64_t values_stride;            // u32 words between two proofs' values (the proofs kind with units > 1; unread otherwise)
+  const void* const* bases;          // n_columns device pointers: unit 0's columns
+  const uint64_t* strides;           // u32 words to the next unit's column; null for the single kind
+  const uint64_t* dyn_ext;           // n_dyn (the proofs kind: units * n_dyn) x 4 Montgomery words on the host; not read by the check
+};
+
+// Every refusal of a call that needs no walk of the program, in the order the entries have always applied them: nullptr, or the
+// reason.  The kernels read and write cells as two uint4, whatever the kind: the values and every column base are 16-byte
+// aligned, every stride a multiple of 4 words.  tests/test_graph_plan_host.py holds the table of refusals.
+inline const char* graph_check_call(const GraphCall& c, size_t program_columns, size_t program_dynamic) {
+  if (c.flags & ~1u) return "graph: unknown flag";                                   // HM_GRAPH_COLUMNS_INTERNAL is bit 0
+  if (c.units == 0) return c.kind == GRAPH_PROOFS ? "graph: proofs must be >= 1" : "graph: circuits must be >= 1";
+  if (c.kind != GRAPH_SINGLE && c.n_columns > GE_MAX_COLUMNS) return "graph: more columns than the column table holds";
+  if (c.n_columns != program_columns) return "graph: the program was built for another number of columns";
+  if (c.n_dyn != program_dynamic) return "graph: the program was built for another number of per-call constants";
+  if (c.log_size > 30) return "graph: log_size > 30";
+  if (c.segments == 0 || ((uint64_t)c.segments << c.log_size) > (1ull << 32)) return "graph: segments must be >= 1 and rows <= 2^32";
+  const uint64_t size = (uint64_t)c.segments << c.log_size;
+  if (c.units > (1ull << 32) / size) return c.kind == GRAPH_PROOFS ? "graph: proofs * rows > 2^32" : "graph: circuits * rows > 2^32";
+  if ((uintptr_t)c.d_values % 16) return "graph: the values are not 16-byte aligned";
+  if (c.kind == GRAPH_PROOFS && c.units > 1 && (c.values_stride < size * 8 || c.values_stride % 4))
+    return "graph: the values stride must be a multiple of 4 words and hold the rows of one proof";
+  for (size_t i = 0; i < c.n_columns; ++i) {
+    if (!c.bases[i]) return "graph: null column pointer";
+    if ((uintptr_t)c.bases[i] % 16) return "graph: a column base is not 16-byte aligned";
+    if (c.strides && c.strides[i] % 4) return "graph: a column stride is not a multiple of 4 words";
+  }
+  return nullptr;
+}
+
+// The launch of an admitted call: `size` rows, `units` circuits or proofs, a program lowered to n_slots scratch slots, at most
+// max_blocks workgroups of 256 lanes.  Enough lanes to fill the chip, few enough that the intermediates' scratch
+// ([slot][word][lane], 9 words a slot) stays cache-sized.  single / proofs: one lane per (unit, row).  circuits: C = 2^log_c
+// circuits side by side in a workgroup of 256 / C rows -- as many as it takes for the grid to reach the single kind's block
+// count, no more than the circuits there are (units = 1 gives C = 1: the single kind's shape); `lanes` are those of one group
+// of C circuits.  Swept against the three formulas this replaced and its invariants: tests/test_graph_plan_host.py.
+struct GraphPlan {
+  uint64_t size, lanes;
+  uint32_t blocks, T, log_c, rows_per;
+  size_t scratch_bytes, args_bytes;
+};
+inline GraphPlan graph_launch_plan(GraphCallKind kind, uint64_t size, uint64_t units, uint32_t n_slots, size_t n_dyn, uint32_t max_blocks) {
+  constexpr uint64_t W = 256;                                                           // graph_interp.h: GE_THREADS
+  GraphPlan p{};
+  p.size = size;
+  if (kind == GRAPH_CIRCUITS)
+    while (p.log_c < 8 && (1ull << p.log_c) < units && ((size << p.log_c) + W - 1) / W < max_blocks) ++p.log_c;
+  p.rows_per = (uint32_t)(W >> p.log_c);
+  p.lanes = kind == GRAPH_PROOFS ? units * size : size << p.log_c;
+  p.blocks = (uint32_t)std::min<uint64_t>(kind == GRAPH_CIRCUITS ? (size + p.rows_per - 1) / p.rows_per : (p.lanes + W - 1) / W, max_blocks);
+  p.T = p.blocks * (uint32_t)W;
+  p.scratch_bytes = (size_t)n_slots * 9 * p.T * 4;
+  p.args_bytes = kind == GRAPH_SINGLE     ? sizeof(GraphColumns)
+                 : kind == GRAPH_CIRCUITS ? sizeof(GraphCircuitColumns)
+                                          : sizeof(GraphProofColumns) + std::max<size_t>(units * n_dyn, 1) * 9 * 4;
+  return p;
 }
 
 struct GraphLowered {       // a validated program lowered for one column format, still on the host

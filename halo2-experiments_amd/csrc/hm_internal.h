@@ -235,7 +235,7 @@ struct GraphProgram {       // a compiled evaluate_h program (graph.hip): the va
   uint32_t* d_consts = nullptr;
   int32_t* d_rot = nullptr;
   std::vector<uint32_t> calcs5;      // as given to hm_graph_create
-  std::vector<uint64_t> consts_ext;  // its constants as given (graph_evaluate_circuits raises the Horner factor to a power on the host)
+  std::vector<uint64_t> consts_ext;  // its constants as given (graph_run raises the circuits kind's Horner factor to a power on the host)
   uint32_t n_intermediates = 0, n_static = 0, n_dynamic = 0;
   size_t n_columns = 0;
   GraphVariant variant[2];           // [0] external-form columns, [1] internal-form columns (HM_GRAPH_COLUMNS_INTERNAL)
@@ -306,6 +306,18 @@ struct DeviceCtx {
 // least recently used one behind a device-side wait for its event.  aux_release records the event.
 AuxSlot* aux_acquire(DeviceCtx& ctx, hipStream_t stream);
 int aux_release(DeviceCtx& ctx, AuxSlot* slot, hipStream_t stream);
+// A call's use of its slot with ONE way out: body(slot) enqueues on `stream`, and the slot's event is recorded behind whatever it
+// enqueued, whatever it returns or throws -- a slot left `used` without a recorded event would hand aux_acquire's hipEventQuery /
+// hipStreamWaitEvent a null or stale event.  Refuse arguments before this, not inside.
+template <class Body>
+int aux_scope(DeviceCtx& ctx, hipStream_t stream, Body&& body) {
+  AuxSlot* slot = aux_acquire(ctx, stream);
+  if (!slot) return HM_ERR_HIP;
+  int rc;
+  try { rc = body(*slot); } catch (...) { (void)aux_release(ctx, slot, stream); throw; }
+  const int released = aux_release(ctx, slot, stream);
+  return rc != HM_OK ? rc : released;
+}
 
 DeviceCtx* ctx_for_current_device();     // capi.hip; null (and the message set) without a gfx950 device
 
@@ -405,14 +417,9 @@ int ntt_coset_inverse_run(DeviceCtx& ctx, uint32_t* d_a, uint32_t batch, const u
 int graph_create(DeviceCtx& ctx, const uint32_t* calcs5, size_t n_calc, const uint64_t* constants_ext, size_t n_const_static,
                  size_t n_dynamic, const int32_t* rotations, size_t n_rot, size_t n_columns, uint32_t n_intermediates,
                  uint64_t* out_handle);
-int graph_evaluate(DeviceCtx& ctx, GraphProgram& g, const void* const* d_columns, size_t n_columns, const uint64_t* dyn_ext,
-                   size_t n_dyn, uint32_t log_size, uint32_t segments, void* d_values, uint32_t flags, hipStream_t stream);
-int graph_evaluate_circuits(DeviceCtx& ctx, GraphProgram& g, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
-                            size_t circuits, const uint64_t* dyn_ext, size_t n_dyn, uint32_t log_size, uint32_t segments, void* d_values,
-                            uint32_t flags, hipStream_t stream);
-int graph_evaluate_proofs(DeviceCtx& ctx, GraphProgram& g, const void* const* column_bases, const uint64_t* column_strides, size_t n_columns,
-                          size_t proofs, const uint64_t* dyn_ext, size_t n_dyn, uint32_t log_size, uint32_t segments, void* d_values,
-                          uint64_t values_stride, uint32_t flags, hipStream_t stream);
+struct GraphCall;                // graph_lower.h: what one call asks for
+uint32_t graph_max_blocks();     // HALO2_MI355X_GRAPH_BLOCKS (default 1280), at least 1: the grid cap of every interpreter launch
+int graph_run(DeviceCtx& ctx, GraphProgram& g, const GraphCall& call, hipStream_t stream);     // single, circuits or proofs: graph_lower.h
 void graph_release(GraphProgram& g);
 
 // poly.hip

@@ -365,7 +365,7 @@ int hc_graph_bounds_closure(const uint64_t* a_ext, double* report) {
   return ok;
 }
 
-// The GraphEvaluator without a GPU: validate and lower a program exactly as hm_graph_create / graph_evaluate do (graph_lower.h is the
+// The GraphEvaluator without a GPU: validate and lower a program exactly as hm_graph_create / graph_run do (graph_lower.h is the
 // code they run), then interpret the LOWERED program row by row as graph_evaluate_kernel does (gr_run above restates ge_run's switch);
 // tests/test_graph_programs_gpu.py holds the two to the same words.
 // Column loads, constants and PreviousValue enter at the class maxima the kernel declares; a value in a slot keeps the bound the
@@ -402,7 +402,7 @@ int hc_graph_replay(const uint32_t* calcs5, size_t n_calc, const uint64_t* const
   }
   info[0] = (uint32_t)n, info[1] = low.n_slots, info[2] = low.result_src, info[3] = low.result_prev;
   info[4] = low.stores_of_constants_removed, info[5] = low.stores_of_columns_removed;
-  // constants -> internal form, as graph_create and graph_evaluate convert them
+  // constants -> internal form, as graph_create and graph_run convert them
   std::vector<uint32_t> consts((n_const_static + n_dynamic + 1) * 9, 0);
   for (size_t i = 0; i < n_const_static; ++i) host::fr_to_internal9(host::fr_load(constants_ext + 4 * i), &consts[9 * i]);
   for (size_t i = 0; i < n_dynamic; ++i) host::fr_to_internal9(host::fr_load(dyn_ext + 4 * i), &consts[9 * (n_const_static + i)]);
@@ -986,8 +986,23 @@ int hc_shplonk_coefficients(uint32_t t, const uint64_t* pts_ext, const uint64_t*
 void hc_graph_proofs_address(uint64_t lane, uint64_t rows, uint32_t log_segment, int64_t rotation, uint32_t log_rows, uint64_t stride_words,
                              uint32_t n_dynamic, uint32_t word, uint64_t* out) {
   const uint64_t proof = graph_proofs_proof(lane, rows), idx = lane - proof * rows;
-  const uint64_t row = graph_proofs_row(idx, rotation, ((uint64_t)1 << log_segment) - 1, log_rows);
+  const uint64_t row = graph_source_row(idx, rotation, ((uint64_t)1 << log_segment) - 1, log_rows);
   out[0] = proof, out[1] = idx, out[2] = row, out[3] = graph_proofs_cell(proof, row, stride_words), out[4] = graph_proofs_dyn(proof, n_dynamic, word);
+}
+// The evaluator's call check and launch plan (graph_lower.h), as graph_run asks them.  Addresses travel as integers: bases, and strides
+// unless null (the single kind), hold n_columns words.  -> the reason, or null for an admitted call.
+const char* hc_graph_check_call(uint32_t kind, uint64_t n_columns, uint64_t units, uint64_t n_dyn, uint32_t log_size, uint32_t segments,
+                                uint32_t flags, uint64_t values, uint64_t values_stride, const uint64_t* bases, const uint64_t* strides,
+                                uint64_t program_columns, uint64_t program_dynamic) {
+  static_assert(sizeof(void*) == sizeof(uint64_t), "bases are read as pointers");
+  const GraphCall c{(GraphCallKind)kind, (size_t)n_columns, (size_t)units, (size_t)n_dyn, log_size, segments, flags, (const void*)(uintptr_t)values,
+                    values_stride, reinterpret_cast<const void* const*>(bases), strides, nullptr};
+  return graph_check_call(c, (size_t)program_columns, (size_t)program_dynamic);
+}
+// out = { size, lanes, blocks, T, log_c, rows_per, scratch_bytes, args_bytes }
+void hc_graph_launch_plan(uint32_t kind, uint64_t size, uint64_t units, uint32_t n_slots, uint64_t n_dyn, uint32_t max_blocks, uint64_t* out) {
+  const GraphPlan p = graph_launch_plan((GraphCallKind)kind, size, units, n_slots, (size_t)n_dyn, max_blocks);
+  out[0] = p.size, out[1] = p.lanes, out[2] = p.blocks, out[3] = p.T, out[4] = p.log_c, out[5] = p.rows_per, out[6] = p.scratch_bytes, out[7] = p.args_bytes;
 }
 int hc_shplonk_row_bounds(const uint64_t* a_ext, double* report) {
   typedef Fe<FrParams> F;

@@ -174,14 +174,11 @@ __global__ __launch_bounds__(GE_THREADS) void mock_copies_kernel(const CheckColu
 }
 
 // ---- host ----
-static uint32_t mock_blocks(uint64_t lanes) {
-  // as graph_evaluate: enough lanes to fill the chip, few enough that the intermediates' scratch stays cache-sized
-  static const uint32_t max_blocks = [] { const char* v = std::getenv("HALO2_MI355X_GRAPH_BLOCKS"); return (uint32_t)(v && *v ? std::atoi(v) : 1280); }();
-  return (uint32_t)std::min<uint64_t>((lanes + GE_THREADS - 1) / GE_THREADS, std::max<uint32_t>(max_blocks, 1));
-}
+// as the evaluator's single kind: enough lanes to fill the chip, few enough that the intermediates' scratch stays cache-sized
+static uint32_t mock_blocks(uint64_t lanes) { return graph_launch_plan(GRAPH_SINGLE, lanes, 1, 0, 0, graph_max_blocks()).blocks; }
 
 // the batched table into the slot's argument buffer, ordered on `stream` ahead of the launch that reads it
-static int mock_table_upload(AuxSlot* slot, const MockTable& t, const GraphProgram* g, const uint64_t* dyn_ext, size_t n_dyn,
+static int mock_table_upload(AuxSlot& slot, const MockTable& t, const GraphProgram* g, const uint64_t* dyn_ext, size_t n_dyn,
                              const uint32_t* perm, size_t n_perm, hipStream_t stream, CheckColumns** out) {
   CheckColumns cols;
   std::memset(&cols, 0, sizeof cols);
@@ -193,9 +190,9 @@ static int mock_table_upload(AuxSlot* slot, const MockTable& t, const GraphProgr
   for (size_t j = 0; j < n_perm; ++j) cols.perm[j] = perm[j];
   cols.n_static = g ? g->n_static : 0;
   for (size_t i = 0; i < n_dyn; ++i) host::fr_to_internal9(host::fr_load(dyn_ext + 4 * i), &cols.dyn[9 * i]);
-  CheckColumns* d_cols = (CheckColumns*)slot->args.ensure(sizeof(CheckColumns));
+  CheckColumns* d_cols = (CheckColumns*)slot.args.ensure(sizeof(CheckColumns));
   if (!d_cols) return hm_fail(HM_ERR_HIP, "mock: argument buffer allocation failed");
-  // pageable source: the runtime has taken its copy of `cols` when this returns (as graph_evaluate's table)
+  // pageable source: the runtime has taken its copy of `cols` when this returns (as graph_run's block)
   HM_HIP_CHECK(hipMemcpyAsync(d_cols, &cols, sizeof cols, hipMemcpyHostToDevice, stream));
   *out = d_cols;
   return HM_OK;
@@ -210,48 +207,38 @@ int mock_program_run(DeviceCtx& ctx, GraphProgram& g, const MockTable& t, const 
   if (n_dyn != g.n_dynamic) return hm_fail(HM_ERR_BAD_ARG, "mock: the program was built for another number of per-call constants");
   const uint64_t lanes = d_list ? (uint64_t)n_list : (uint64_t)m * usable;
   if (lanes == 0) return HM_OK;
-  const uint32_t blocks = mock_blocks(lanes), T = blocks * GE_THREADS;
-  uint64_t n2 = 1;
-  while (n2 < usable) n2 <<= 1;
-  const size_t b_scratch = ((size_t)v.n_slots * 9 * T * 4 + 255) & ~(size_t)255;
+  const GraphPlan p = graph_launch_plan(GRAPH_SINGLE, lanes, 1, v.n_slots, 0, graph_max_blocks());
+  const size_t b_scratch = (p.scratch_bytes + 255) & ~(size_t)255;       // the keys behind it stay 256-byte aligned
   const size_t b_keys = d_table_values ? lookup_sorted_keys_bytes(usable) : 0;
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  uint8_t* buf = (uint8_t*)slot->scratch.ensure(b_scratch + b_keys);
-  if (!buf) return hm_fail(HM_ERR_HIP, "mock: scratch allocation failed");
-  uint32_t* d_keys = nullptr;
-  if (d_table_values) {
-    d_keys = (uint32_t*)(buf + b_scratch);
-    if (const int rc = lookup_sorted_keys_run(ctx, d_table_values, usable, buf + b_scratch, stream)) return rc;
-  }
-  CheckColumns* d_cols = nullptr;
-  if (const int rc = mock_table_upload(slot, t, &g, dyn_ext, n_dyn, nullptr, 0, stream, &d_cols)) return rc;
   const CheckSink sink{out.d_records, out.cap, (unsigned long long*)out.d_counter, out.d_user_flags};
-  if (d_table_values)
-    hipLaunchKernelGGL(graph_check_kernel<SINK_NOT_IN_TABLE>, dim3(blocks), dim3(GE_THREADS), 0, stream, (const CheckColumns*)d_cols,
-                       (const uint32_t*)g.d_consts, (const int32_t*)g.d_rot, (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src, v.result_prev,
-                       (uint32_t*)buf, lanes, usable, k, (uint32_t)m, user_base, d_list, (const uint32_t*)d_keys, (uint64_t)usable, sink);
-  else
-    hipLaunchKernelGGL(graph_check_kernel<SINK_NONZERO>, dim3(blocks), dim3(GE_THREADS), 0, stream, (const CheckColumns*)d_cols,
-                       (const uint32_t*)g.d_consts, (const int32_t*)g.d_rot, (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src, v.result_prev,
-                       (uint32_t*)buf, lanes, usable, k, (uint32_t)m, user_base, d_list, (const uint32_t*)nullptr, (uint64_t)0, sink);
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
+  return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
+    uint8_t* buf = (uint8_t*)slot.scratch.ensure(b_scratch + b_keys);
+    if (!buf) return hm_fail(HM_ERR_HIP, "mock: scratch allocation failed");
+    if (d_table_values)
+      if (const int rc = lookup_sorted_keys_run(ctx, d_table_values, usable, buf + b_scratch, stream)) return rc;
+    CheckColumns* d_cols = nullptr;
+    if (const int rc = mock_table_upload(slot, t, &g, dyn_ext, n_dyn, nullptr, 0, stream, &d_cols)) return rc;
+    ge_launch(d_table_values != nullptr, graph_check_kernel<SINK_NOT_IN_TABLE>, graph_check_kernel<SINK_NONZERO>, p.blocks, stream, d_cols, g.d_consts,
+              g.d_rot, v.d_calcs, v.n_calc, v.result_src, v.result_prev, buf, lanes, usable, k, m, user_base, d_list,
+              d_table_values ? buf + b_scratch : nullptr, d_table_values ? usable : 0u, sink);
+    HM_HIP_CHECK(hipGetLastError());
+    return HM_OK;
+  });
 }
 
 int mock_copies_run(DeviceCtx& ctx, const MockTable& t, const uint32_t* perm, size_t n_perm, const uint32_t* d_pairs, size_t n_copies,
                     uint32_t k, size_t m, const MockSink& out, hipStream_t stream) {
   const uint64_t lanes = (uint64_t)m * n_copies;
   if (lanes == 0) return HM_OK;
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  CheckColumns* d_cols = nullptr;
-  if (const int rc = mock_table_upload(slot, t, nullptr, nullptr, 0, perm, n_perm, stream, &d_cols)) return rc;
   const CheckSink sink{out.d_records, out.cap, (unsigned long long*)out.d_counter, out.d_user_flags};
-  hipLaunchKernelGGL(mock_copies_kernel, dim3(mock_blocks(lanes)), dim3(GE_THREADS), 0, stream, (const CheckColumns*)d_cols, d_pairs,
-                     (uint32_t)n_copies, (uint32_t)n_perm, k, lanes, sink);
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
+  return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
+    CheckColumns* d_cols = nullptr;
+    if (const int rc = mock_table_upload(slot, t, nullptr, nullptr, 0, perm, n_perm, stream, &d_cols)) return rc;
+    hipLaunchKernelGGL(mock_copies_kernel, dim3(mock_blocks(lanes)), dim3(GE_THREADS), 0, stream, (const CheckColumns*)d_cols, d_pairs,
+                       (uint32_t)n_copies, (uint32_t)n_perm, k, lanes, sink);
+    HM_HIP_CHECK(hipGetLastError());
+    return HM_OK;
+  });
 }
 
 }  // namespace hm

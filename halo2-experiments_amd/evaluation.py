@@ -351,6 +351,47 @@ class CompiledGraph:
                                        len(rotations), n_columns, n_intermediates, ctypes.byref(h)))
         self.handle = h.value
 
+    # ---- what evaluate, evaluate_circuits and evaluate_proofs share ----
+    def _shape(self, who: str, size: int, segments: int, n_columns: int, n_challenges: int = None) -> int:
+        """-> log2 of the segment's rows, or ValueError in ``who``'s name"""
+        if segments < 1 or size % segments:
+            raise ValueError(f"{who}: the rows must be a whole number of segments")
+        seg = size // segments
+        if seg & (seg - 1) or seg == 0:
+            raise ValueError(f"{who}: the (segment of the) domain must be a power of two")
+        if n_challenges is None:
+            if n_columns != self.n_columns:
+                raise ValueError(f"{who}: column count differs from the compiled program's")
+        elif n_columns != self.n_columns or n_challenges != self.num_challenges:
+            raise ValueError(f"{who}: column / challenge count differs from the compiled program's")
+        return seg.bit_length() - 1
+
+    def _column_table(self, who: str, columns: Sequence, size: int, place):
+        """``place(i, column, want)`` -> (unit 0's (want, 4) column, u32 words to the next unit's), ``want`` being the rows column i
+        must hold (a short column: its 2^log rows).  -> (the tensors to keep alive, the pointer array, the stride array)"""
+        keep, strides = [], []
+        for i, c in enumerate(columns):
+            want = (1 << self.short_columns[i]) if i in self.short_columns else size
+            c, stride = place(i, c, want)
+            if want == 1 and i in self.short_columns:          # encoded as two rows (GraphEvaluator.lower): the same row twice
+                if stride:
+                    raise ValueError(f"{who}: the one-row column {i} must be shared")
+                c = c.reshape(1, 4).expand(2, 4).contiguous()
+            keep.append(c)
+            strides.append(stride)
+        return (keep, (ctypes.c_void_p * max(len(keep), 1))(*[c.data_ptr() for c in keep]),
+                (ctypes.c_uint64 * max(len(strides), 1))(*strides))
+
+    @staticmethod
+    def _flat(who: str, i: int, c, want: int, whose: str = ""):
+        if _tensor_rows(c, 4, "column") != want:
+            raise ValueError(f"{who}: column {i} must hold {want} rows{whose}")
+        return c
+
+    @staticmethod
+    def _constant_rows(challenges, beta, gamma, theta, y) -> list:
+        return [fr_words(v) for v in list(challenges) + [beta, gamma, theta, y]]
+
     def evaluate(self, columns: Sequence, values, challenges: Sequence[int] = (), beta: int = 0, gamma: int = 0, theta: int = 0,
                  y: int = 0, columns_internal: bool = False, segments: int = 1) -> None:
         """``columns``: GPU tensors (size, 4), fixed then advice then instance; ``values``: (size, 4) GPU tensor holding
@@ -359,24 +400,11 @@ class CompiledGraph:
         ``segments`` > 1: the rows are that many back-to-back blocks of size / segments rows (a power of two) and a rotation
         wraps inside its block -- several cosets of the extended domain in one launch (``EvaluationDomain.coeff_to_cosets``)."""
         size = _tensor_rows(values, 4, "values")
-        if segments < 1 or size % segments:
-            raise ValueError("evaluate: the rows must be a whole number of segments")
-        seg = size // segments
-        if seg & (seg - 1) or seg == 0:
-            raise ValueError("evaluate: the (segment of the) domain must be a power of two")
-        if len(columns) != self.n_columns or len(challenges) != self.num_challenges:
-            raise ValueError("evaluate: column / challenge count differs from the compiled program's")
-        columns = list(columns)
-        for i, c in enumerate(columns):
-            want = (1 << self.short_columns[i]) if i in self.short_columns else size
-            if _tensor_rows(c, 4, "column") != want:
-                raise ValueError(f"evaluate: column {i} must hold {want} rows")
-            if want == 1 and i in self.short_columns:          # encoded as two rows (GraphEvaluator.lower): the same row twice
-                columns[i] = c.reshape(1, 4).expand(2, 4).contiguous()
-        ptrs = (ctypes.c_void_p * max(len(columns), 1))(*[c.data_ptr() for c in columns])
-        dyn = np.stack([fr_words(v) for v in list(challenges) + [beta, gamma, theta, y]])
-        _lib.check(_lib.load().hm_graph_evaluate_segments_dev(ctypes.c_uint64(self.handle), ptrs, len(columns), _ptr(dyn), dyn.shape[0],
-                                                              seg.bit_length() - 1, segments, ctypes.c_void_p(values.data_ptr()),
+        log_seg = self._shape("evaluate", size, segments, len(columns), len(challenges))
+        keep, ptrs, _ = self._column_table("evaluate", columns, size, lambda i, c, want: (self._flat("evaluate", i, c, want), 0))
+        dyn = np.stack(self._constant_rows(challenges, beta, gamma, theta, y))
+        _lib.check(_lib.load().hm_graph_evaluate_segments_dev(ctypes.c_uint64(self.handle), ptrs, len(keep), _ptr(dyn), dyn.shape[0],
+                                                              log_seg, segments, ctypes.c_void_p(values.data_ptr()),
                                                               _lib.HM_GRAPH_COLUMNS_INTERNAL if columns_internal else 0, ctypes.c_void_p(_stream_ptr(values))))
 
     def evaluate_circuits(self, columns: Sequence, strides_or_stacked, values, circuits: int, challenges: Sequence[int] = (), beta: int = 0,
@@ -387,53 +415,30 @@ class CompiledGraph:
         the tensors' shapes, or one entry per column: True / False for stacked / shared, or an integer stride in u32 words between
         one circuit's column and the next one's inside a larger tensor (0 = shared; ``columns[i]`` is then circuit 0's column).
         The program must be linear in PreviousValue (``linear_in_previous``): anything else raises ValueError before any call."""
+        who = "evaluate_circuits"
         linear_in_previous(self.calcs)
         size = _tensor_rows(values, 4, "values")
         if circuits < 1:
-            raise ValueError("evaluate_circuits: circuits must be >= 1")
-        if segments < 1 or size % segments:
-            raise ValueError("evaluate_circuits: the rows must be a whole number of segments")
-        seg = size // segments
-        if seg & (seg - 1) or seg == 0:
-            raise ValueError("evaluate_circuits: the (segment of the) domain must be a power of two")
-        if len(columns) != self.n_columns or len(challenges) != self.num_challenges:
-            raise ValueError("evaluate_circuits: column / challenge count differs from the compiled program's")
+            raise ValueError(f"{who}: circuits must be >= 1")
+        log_seg = self._shape(who, size, segments, len(columns), len(challenges))
         hints = list(strides_or_stacked) if strides_or_stacked is not None else [None] * len(columns)
         if len(hints) != len(columns):
-            raise ValueError("evaluate_circuits: one stride (or stacked flag) per column")
-        keep, ptrs, strides = [], [], []
-        for i, (c, hint) in enumerate(zip(columns, hints)):
-            want = (1 << self.short_columns[i]) if i in self.short_columns else size
-            if hint is None:
-                hint = c.dim() == 3
-            if isinstance(hint, bool):
-                if hint:
-                    if c.dim() != 3 or tuple(c.shape) != (circuits, want, 4):
-                        raise ValueError(f"evaluate_circuits: stacked column {i} must be ({circuits}, {want}, 4)")
-                    c = c.contiguous()
-                    stride = want * 8
-                else:
-                    if _tensor_rows(c, 4, "column") != want:
-                        raise ValueError(f"evaluate_circuits: column {i} must hold {want} rows")
-                    stride = 0
-                    if want == 1 and i in self.short_columns:      # encoded as two rows (GraphEvaluator.lower): the same row twice
-                        c = c.reshape(1, 4).expand(2, 4).contiguous()
-            else:
-                stride = int(hint)
-                if _tensor_rows(c, 4, "column") != want:
-                    raise ValueError(f"evaluate_circuits: column {i} must hold {want} rows (circuit 0's)")
-                if want == 1 and i in self.short_columns:
-                    if stride:
-                        raise ValueError(f"evaluate_circuits: the one-row column {i} must be shared")
-                    c = c.reshape(1, 4).expand(2, 4).contiguous()
-            keep.append(c)
-            ptrs.append(c.data_ptr())
-            strides.append(stride)
-        ptr_arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
-        stride_arr = (ctypes.c_uint64 * max(len(strides), 1))(*strides)
-        dyn = np.stack([fr_words(v) for v in list(challenges) + [beta, gamma, theta, y]])
+            raise ValueError(f"{who}: one stride (or stacked flag) per column")
+
+        def place(i, c, want):
+            hint = c.dim() == 3 if hints[i] is None else hints[i]
+            if not isinstance(hint, bool):                     # a stride in words; the column is circuit 0's
+                return self._flat(who, i, c, want, " (circuit 0's)"), int(hint)
+            if not hint:
+                return self._flat(who, i, c, want), 0
+            if c.dim() != 3 or tuple(c.shape) != (circuits, want, 4):
+                raise ValueError(f"{who}: stacked column {i} must be ({circuits}, {want}, 4)")
+            return c.contiguous(), want * 8
+
+        keep, ptrs, strides = self._column_table(who, columns, size, place)
+        dyn = np.stack(self._constant_rows(challenges, beta, gamma, theta, y))
         _lib.check(_lib.load().hm_graph_evaluate_circuits_dev(
-            ctypes.c_uint64(self.handle), ptr_arr, stride_arr, len(ptrs), circuits, _ptr(dyn), dyn.shape[0], seg.bit_length() - 1, segments,
+            ctypes.c_uint64(self.handle), ptrs, strides, len(keep), circuits, _ptr(dyn), dyn.shape[0], log_seg, segments,
             ctypes.c_void_p(values.data_ptr()), _lib.HM_GRAPH_COLUMNS_INTERNAL if columns_internal else 0, ctypes.c_void_p(_stream_ptr(values))))
 
     def evaluate_proofs(self, columns: Sequence, values, constants: Sequence[dict], columns_internal: bool = False, segments: int = 1) -> None:
@@ -443,58 +448,39 @@ class CompiledGraph:
         ``values``: a (proofs, size, 4) GPU tensor.  ``columns[i]``: a (proofs, size, 4) tensor -- one column per proof, contiguous or
         a slice whose rows are contiguous -- or a (size, 4) tensor every proof shares (a short column: its 2^log rows); a pair
         ``(tensor, stride)`` names proof 0's column and the u32 words to the next proof's (0: shared).  Any program is admitted."""
+        who = "evaluate_proofs"
         proofs = len(constants)
         if proofs < 1:
-            raise ValueError("evaluate_proofs: at least one proof")
+            raise ValueError(f"{who}: at least one proof")
         if not _is_tensor(values) or values.dim() != 3 or values.shape[0] != proofs or values.shape[2] != 4:
-            raise ValueError(f"evaluate_proofs: values must be a ({proofs}, size, 4) GPU tensor")
+            raise ValueError(f"{who}: values must be a ({proofs}, size, 4) GPU tensor")
         size = values.shape[1]
         if values.stride(2) != 1 or values.stride(1) != 4 or (proofs > 1 and values.stride(0) < size * 4):
-            raise ValueError("evaluate_proofs: the rows of a proof's values must be contiguous")
-        if segments < 1 or size % segments:
-            raise ValueError("evaluate_proofs: the rows must be a whole number of segments")
-        seg = size // segments
-        if seg & (seg - 1) or seg == 0:
-            raise ValueError("evaluate_proofs: the (segment of the) domain must be a power of two")
-        if len(columns) != self.n_columns:
-            raise ValueError("evaluate_proofs: column count differs from the compiled program's")
-        keep, ptrs, strides = [], [], []
-        for i, c in enumerate(columns):
-            want = (1 << self.short_columns[i]) if i in self.short_columns else size
-            if isinstance(c, tuple):
-                c, stride = c[0], int(c[1])
-                if _tensor_rows(c, 4, "column") != want:
-                    raise ValueError(f"evaluate_proofs: column {i} must hold {want} rows (proof 0's)")
-            elif c.dim() == 3:
-                if tuple(c.shape) != (proofs, want, 4):
-                    raise ValueError(f"evaluate_proofs: stacked column {i} must be ({proofs}, {want}, 4)")
-                if c.stride(2) != 1 or c.stride(1) != 4:
-                    c = c.contiguous()
-                stride = c.stride(0) * 2 if proofs > 1 else 0
-                c = c[0]
-            else:
-                if _tensor_rows(c, 4, "column") != want:
-                    raise ValueError(f"evaluate_proofs: column {i} must hold {want} rows")
-                stride = 0
-            if want == 1 and i in self.short_columns:          # encoded as two rows (GraphEvaluator.lower): the same row twice
-                if stride:
-                    raise ValueError(f"evaluate_proofs: the one-row column {i} must be shared")
-                c = c.reshape(1, 4).expand(2, 4).contiguous()
-            keep.append(c)
-            ptrs.append(c.data_ptr())
-            strides.append(stride)
+            raise ValueError(f"{who}: the rows of a proof's values must be contiguous")
+        log_seg = self._shape(who, size, segments, len(columns))
+
+        def place(i, c, want):
+            if isinstance(c, tuple):                           # (proof 0's column, stride in words)
+                return self._flat(who, i, c[0], want, " (proof 0's)"), int(c[1])
+            if c.dim() != 3:
+                return self._flat(who, i, c, want), 0
+            if tuple(c.shape) != (proofs, want, 4):
+                raise ValueError(f"{who}: stacked column {i} must be ({proofs}, {want}, 4)")
+            if c.stride(2) != 1 or c.stride(1) != 4:
+                c = c.contiguous()
+            return c[0], c.stride(0) * 2 if proofs > 1 else 0
+
+        keep, ptrs, strides = self._column_table(who, columns, size, place)
         rows = []
         for cst in constants:
             extra = set(cst) - {"challenges", "beta", "gamma", "theta", "y"}
             ch = list(cst.get("challenges", ()))
             if extra or len(ch) != self.num_challenges:
-                raise ValueError("evaluate_proofs: a proof's constants are challenges (the program's count), beta, gamma, theta, y")
-            rows += [fr_words(v) for v in ch + [cst.get("beta", 0), cst.get("gamma", 0), cst.get("theta", 0), cst.get("y", 0)]]
+                raise ValueError(f"{who}: a proof's constants are challenges (the program's count), beta, gamma, theta, y")
+            rows += self._constant_rows(ch, cst.get("beta", 0), cst.get("gamma", 0), cst.get("theta", 0), cst.get("y", 0))
         dyn = np.ascontiguousarray(np.stack(rows))
-        ptr_arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
-        stride_arr = (ctypes.c_uint64 * max(len(strides), 1))(*strides)
         _lib.check(_lib.load().hm_graph_evaluate_proofs_dev(
-            ctypes.c_uint64(self.handle), ptr_arr, stride_arr, len(ptrs), proofs, _ptr(dyn), dyn.shape[0] // proofs, seg.bit_length() - 1, segments,
+            ctypes.c_uint64(self.handle), ptrs, strides, len(keep), proofs, _ptr(dyn), dyn.shape[0] // proofs, log_seg, segments,
             ctypes.c_void_p(values.data_ptr()), values.stride(0) * 2 if proofs > 1 else size * 8,
             _lib.HM_GRAPH_COLUMNS_INTERNAL if columns_internal else 0, ctypes.c_void_p(_stream_ptr(values))))
 

@@ -431,7 +431,9 @@ int hm_fr_powers_dev(void* d_out, size_t n, const uint64_t x[4], void* stream);
  * vanishing-polynomial pattern of divide_by_vanishing_poly (period 2^(extended_k - k)) is such a column, so the division is
  * the program's last multiplication.
  * hm_graph_create validates the program, assigns intermediates to a minimal number of slots by liveness and uploads it;
- * evaluation is asynchronous on `stream` and may run concurrently on different streams. */
+ * evaluation is asynchronous on `stream` and may run concurrently on different streams.  d_values and every column pointer
+ * must be 16-byte aligned (a cell is moved as two 16-byte halves): one that is not is refused with HM_ERR_BAD_ARG, by
+ * hm_graph_evaluate_dev, hm_graph_evaluate_flags_dev and hm_graph_evaluate_segments_dev alike. */
 int hm_graph_create(const uint32_t* calcs, size_t n_calc, const uint64_t* constants, size_t n_const, size_t n_dynamic,
                     const int32_t* rotations, size_t n_rot, size_t n_columns, uint32_t n_intermediates, uint64_t* out_handle);
 int hm_graph_evaluate_dev(uint64_t handle, const void* const* d_columns, size_t n_columns, const uint64_t* dynamic_constants,

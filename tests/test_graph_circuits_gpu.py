@@ -202,3 +202,36 @@ def test_argument_errors_launch_nothing(three):
     values2 = gp.to_device(gp.words(d0.previous))
     prog.evaluate_circuits(keep, strides, values2, 2, **sc)
     assert not np.array_equal(host(values2), before)
+
+
+def test_a_good_call_on_a_second_stream_follows_a_refused_one(three):
+    """64 rows, 2 circuits: a call refused on one stream leaves no stream slot behind it -- the same call without the fault, on another
+    stream, gives what it gives on the default stream"""
+    p, prog = three
+    cs = gc.make_circuits(3, 64, 1, 2)
+    d0 = cs.data[0]
+    keep, strides, whole = device_stacked(cs, False)
+    sc = d0.scalars()
+    dyn = np.stack([fr_words(v) for v in list(sc["challenges"]) + [sc["beta"], sc["gamma"], sc["theta"], sc["y"]]])
+    want = gp.to_device(gp.words(d0.previous))
+    prog.evaluate_circuits(keep, strides, want, 2, **sc)
+    values = gp.to_device(gp.words(d0.previous))
+    before = host(values).copy()
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    odd = list(strides)
+    odd[gp.NF] = 64 * 8 + 2
+    for ptrs, strd in (([keep[0].data_ptr() + 8] + [t.data_ptr() for t in keep[1:]], strides), ([t.data_ptr() for t in keep], odd)):
+        rc = _lib.load().hm_graph_evaluate_circuits_dev(
+            ctypes.c_uint64(prog.handle), (ctypes.c_void_p * len(ptrs))(*ptrs), (ctypes.c_uint64 * len(strd))(*strd), len(ptrs), 2,
+            dyn.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), dyn.shape[0], 6, 1, ctypes.c_void_p(values.data_ptr()), 0,
+            ctypes.c_void_p(sa.cuda_stream))
+        assert rc == _lib.HM_ERR_BAD_ARG and b"graph:" in _lib.load().hm_last_error()
+        sa.synchronize()
+        assert np.array_equal(host(values), before)
+        again = gp.to_device(gp.words(d0.previous))
+        torch.cuda.synchronize()
+        with torch.cuda.stream(sb):
+            prog.evaluate_circuits(keep, strides, again, 2, **sc)
+        sb.synchronize()
+        assert np.array_equal(host(again), host(want))
+    assert not np.array_equal(host(want), before)

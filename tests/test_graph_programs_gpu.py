@@ -140,3 +140,42 @@ def test_two_handles_alternating_on_two_streams(hc):
     finally:
         ha.destroy()
         hb.destroy()
+
+
+@pytest.mark.gpu
+def test_argument_errors_of_the_single_entry_launch_nothing(hc):
+    """hm_graph_evaluate_segments_dev on a 64-row program: the values or one column base 8 bytes off 16, an unknown flag, no segments,
+    log_size 31, another column count and a null column are refused on the host with HM_ERR_BAD_ARG and a ``graph:`` reason, the values
+    bit for bit as before (nothing misaligned is ever launched); the same arguments without the fault are accepted and give the host
+    replay's words."""
+    import ctypes
+    from halo2_experiments_amd import _lib
+    p = gp.random_program(7003)
+    d = gp.make_data(random.Random(64), 64, 1)
+    cols = [c if c.shape[0] > 1 else c.expand(2, 4).contiguous() for c in gp.device_columns(d, False)]     # the one-row column twice
+    values = gp.to_device(gp.words(d.previous))
+    before = gp.device_values(values).copy()
+    sc = d.scalars()
+    dyn = gp.words(list(sc["challenges"]) + [sc["beta"], sc["gamma"], sc["theta"], sc["y"]])
+    lib = _lib.load()
+    prog = p.compile()
+
+    def call(ptrs=None, n_columns=len(cols), log_size=6, segments=1, vals=values.data_ptr(), flags=0):
+        ptrs = [c.data_ptr() for c in cols] if ptrs is None else ptrs
+        return lib.hm_graph_evaluate_segments_dev(ctypes.c_uint64(prog.handle), (ctypes.c_void_p * len(ptrs))(*ptrs), n_columns,
+                                                  dyn.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), dyn.shape[0], log_size, segments,
+                                                  ctypes.c_void_p(vals), flags, None)
+
+    try:
+        good = [c.data_ptr() for c in cols]
+        for fault in (dict(vals=values.data_ptr() + 8), dict(ptrs=good[:gp.NF] + [good[gp.NF] + 8] + good[gp.NF + 1:]), dict(flags=2),
+                      dict(segments=0), dict(log_size=31), dict(ptrs=good[:-1], n_columns=len(cols) - 1),
+                      dict(ptrs=good[:gp.NF] + [None] + good[gp.NF + 1:])):
+            assert call(**fault) == _lib.HM_ERR_BAD_ARG, fault
+            assert b"graph:" in lib.hm_last_error(), fault
+            assert np.array_equal(gp.device_values(values), before), fault
+        assert call() == _lib.HM_OK
+        assert np.array_equal(gp.device_values(values), gp.host_replay(hc, p, d, False).values)
+        assert not np.array_equal(gp.device_values(values), before)
+    finally:
+        prog.destroy()

@@ -264,3 +264,36 @@ def test_argument_errors_launch_nothing(constants_program):
         assert np.array_equal(host(values2), host(loop_of_single_calls(other, cols, prev.clone(), scalars, False, 1)))
     finally:
         other.destroy()
+
+
+def test_a_good_call_on_a_second_stream_follows_a_refused_one(constants_program):
+    """64 rows, 2 proofs: a call refused on one stream leaves no stream slot behind it -- the same call without the fault, on another
+    stream, gives what it gives on the default stream"""
+    p, prog = constants_program
+    size, proofs = 64, 2
+    cols, prev, scalars = random_inputs(43, size, proofs)
+    flat = [c[0] if c.dim() == 3 else (c if c.shape[0] > 1 else c.expand(2, 4).contiguous()) for c in cols]
+    strides = [size * 8 if c.dim() == 3 else 0 for c in cols]
+    dyn = np.stack([fr_words(v) for sc in scalars for v in sc["challenges"] + [sc["beta"], sc["gamma"], sc["theta"], sc["y"]]])
+    want = prev.clone()
+    prog.evaluate_proofs(cols, want, scalars)
+    values = prev.clone()
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    good = [t.data_ptr() for t in flat]
+    for ptrs, vals, vstride in (([good[0] + 8] + good[1:], values.data_ptr(), size * 8), (good, values.data_ptr() + 8, size * 8),
+                                (good, values.data_ptr(), size * 8 - 4)):
+        rc = _lib.load().hm_graph_evaluate_proofs_dev(
+            ctypes.c_uint64(prog.handle), (ctypes.c_void_p * N_COLS)(*ptrs), (ctypes.c_uint64 * N_COLS)(*strides), N_COLS, proofs,
+            dyn.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), dyn.shape[0] // proofs, 6, 1, ctypes.c_void_p(vals), vstride, 0,
+            ctypes.c_void_p(sa.cuda_stream))
+        assert rc == _lib.HM_ERR_BAD_ARG and b"graph:" in _lib.load().hm_last_error()
+        sa.synchronize()
+        assert np.array_equal(host(values), host(prev))
+        again = prev.clone()
+        torch.cuda.synchronize()
+        with torch.cuda.stream(sb):
+            prog.evaluate_proofs(cols, again, scalars)
+        sb.synchronize()
+        assert np.array_equal(host(again), host(want))
+    assert not np.array_equal(host(want), host(prev))
