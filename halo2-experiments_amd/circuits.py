@@ -326,6 +326,48 @@ def overflow_check_v2(max_bits: int = 4, acc_cols: int = 4, unblinded_value: boo
                             unblinded_advice=(value,) if unblinded_value else (), parameters=dict(max_bits=max_bits, acc_cols=acc_cols))
 
 
+def sorted_column(max_bits: int = 4, acc_cols: int = 4) -> ConstraintSystem:
+    """"This committed column holds pairwise distinct ids" (DESIGN.md section 32).  This circuit is the project's own: it is NOT
+    transcribed from the reference, which has nothing of the kind; only its shape follows ``overflow_check_v2``, whose limb
+    decomposition and range lookups it uses.  Advice 0 is the id, ``unblinded_advice = (0,)``, so a proof's first commitment is
+    ``params.commit_lagrange`` of the id column padded with zeros -- the very point ``ledger.py`` publishes and ``open_all`` opens;
+    advice 1 .. acc_cols are the limbs of the gap to the next row, max_bits bits each, most significant first; fixed 0 the range
+    column 0 .. 2^max_bits - 1, fixed 1 the selector; an instance column that stays empty; equality on the limb columns only, and no
+    copies.  One gate, with B = max_bits * acc_cols,
+
+        sel * (id[i+1] - id[i] - 1 - sum_j limb_j[i] * 2^(max_bits * (acc_cols - 1 - j))),
+
+    and one lookup per limb column into the range column, so every limb is in [0, 2^max_bits).  ``synthesis.SortedColumnLayout`` sets
+    the selector on rows 0 .. rows - 2 of a column with ``rows`` live rows.
+
+    What it proves.  On those rows id[i+1] - id[i] - 1 = d_i mod r for an integer 0 <= d_i < 2^B, so id[i] = id[0] + s_i mod r with
+    the integers s_0 = 0 and s_i = s_(i-1) + d_(i-1) + 1: 0 = s_0 < s_1 < .. < s_(rows-1) <= (rows - 1) * 2^B < 2^(k + B).  With
+    B + k <= 253 every s_i is below 2^253 < r, so no two of them agree mod r, and the ids are pairwise distinct WHATEVER id[0] is --
+    a run that wraps past r (r - 2, r - 1, 0, 1) stays distinct.  B <= 253 is checked here, as in ``overflow_check_v2``; B + k <= 253
+    needs k and is checked by the layout.  Nothing else is claimed: the ids need not be small, only apart by less than 2^B in sorted
+    order, which ids below 2^B always are (128-bit hashes at (16, 8))."""
+    if not 1 <= max_bits <= 16:
+        raise ValueError("sorted_column: max_bits must be 1 .. 16")
+    if acc_cols < 1 or max_bits * acc_cols > 253:
+        raise ValueError("sorted_column: acc_cols must be at least 1 and max_bits * acc_cols at most 253 (the limb sum must not wrap mod r)")
+    cols = _Columns()
+    ident = cols.advice()
+    limbs = [cols.advice() for _ in range(acc_cols)]
+    rng = cols.fixed()
+    selector = cols.selector()
+    cols.instance()
+    for col in limbs:
+        cols.enable_equality("advice", col)
+    total: Expression = Advice(limbs[acc_cols - 1])
+    for i in range(acc_cols - 1):
+        total = total + Advice(limbs[i]) * Constant(1 << (max_bits * (acc_cols - 1 - i)))
+    gates = [("next id is this id plus one plus the decomposed gap", [Fixed(selector) * (Advice(ident, 1) - Advice(ident) - Constant(1) - total)])]
+    lookups = [([Advice(col)], [Fixed(rng)]) for col in limbs]
+    return ConstraintSystem(f"SortedColumn<{max_bits}, {acc_cols}>", "this project's own (DESIGN.md section 32)",
+                            cols.num_fixed, cols.num_advice, cols.num_instance, gates, lookups, cols.equality,
+                            unblinded_advice=(ident,), parameters=dict(max_bits=max_bits, acc_cols=acc_cols, sorted=True))
+
+
 def range_check(value: Expression, range_: int) -> Expression:
     """chips/utils.rs:73-77: value * (1 - value) * (2 - value) * ... * (range - 1 - value), zero exactly on 0 .. range - 1."""
     acc = value

@@ -472,6 +472,84 @@ int hm_range_witness_bn256_fr(uint32_t max_bits, uint32_t acc_cols, uint32_t log
   });
 } HM_API_CATCH("hm_range_witness_bn256_fr")
 
+// ---- the sorted-column circuit's witness (sorted.inc: sorted_witness_lane) and the argsort of an id column -----------------------------
+// what the layout and both forms of the witness refuse: the range check's limits, and max_bits * acc_cols + log_n <= 253, without
+// which two ids of one column could agree mod r although every gap is in range
+static int sorted_witness_layout(const char* who, uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, uint32_t rows, uint32_t* n_advice,
+                                 uint32_t* table_rows) {
+  if (int rc = range_witness_layout(who, max_bits, acc_cols, log_n, rows, n_advice, table_rows)) return rc;
+  if ((uint64_t)max_bits * acc_cols + log_n > 253)
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": max_bits * acc_cols + log_n must be at most 253 (the gaps' sum must not wrap mod r)");
+  return HM_OK;
+}
+
+int hm_sorted_witness_layout(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, uint32_t rows, uint32_t* out_n_advice,
+                             uint32_t* out_table_rows) try {
+  if (!out_n_advice || !out_table_rows) return hm_fail(HM_ERR_BAD_ARG, "hm_sorted_witness_layout: null argument");
+  uint32_t n_advice = 0, table_rows = 0;
+  if (int rc = sorted_witness_layout("hm_sorted_witness_layout", max_bits, acc_cols, log_n, rows, &n_advice, &table_rows)) return rc;
+  *out_n_advice = n_advice;
+  *out_table_rows = table_rows;
+  return HM_OK;
+} HM_API_CATCH("hm_sorted_witness_layout")
+
+static int sorted_witness_args(const char* who, uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows,
+                               const void* ids, const void* advice, uint32_t* n_advice) {
+  if (!ids || !advice) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (m == 0) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": m must be at least 1");
+  uint32_t table_rows = 0;
+  if (int rc = sorted_witness_layout(who, max_bits, acc_cols, log_n, rows, n_advice, &table_rows)) return rc;
+  if (m > (POSEIDON_MAX_N >> log_n)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": more than 2^31 rows");
+  return HM_OK;
+}
+
+int hm_sorted_witness_bn256_fr_dev(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const void* d_ids,
+                                   void* d_advice, uint32_t* d_over_or_null, void* stream) try {
+  const char* who = "hm_sorted_witness_bn256_fr_dev";
+  uint32_t n_advice = 0;
+  if (int rc = sorted_witness_args(who, max_bits, acc_cols, log_n, m, rows, d_ids, d_advice, &n_advice)) return rc;
+  if (int rc = witness_aligned(who, {d_ids, d_advice}, nullptr)) return rc;
+  if ((uintptr_t)d_over_or_null & 3u) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": d_over is not 4-byte aligned");
+  if (ranges_overlap(d_ids, m * rows * 32, d_advice, m * n_advice * ((size_t)32 << log_n)))
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": d_ids overlaps d_advice");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return sorted_witness_run(max_bits, acc_cols, log_n, m, rows, (const uint32_t*)d_ids, (uint32_t*)d_advice, d_over_or_null,
+                            (hipStream_t)stream);
+} HM_API_CATCH("hm_sorted_witness_bn256_fr_dev")
+
+int hm_sorted_witness_bn256_fr(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint64_t* ids,
+                               uint64_t* advice, uint32_t* over_or_null) try {
+  const char* who = "hm_sorted_witness_bn256_fr";
+  uint32_t n_advice = 0;
+  if (int rc = sorted_witness_args(who, max_bits, acc_cols, log_n, m, rows, ids, advice, &n_advice)) return rc;
+  const size_t col_bytes = (size_t)32 << log_n;
+  if (m > WITNESS_HOST_MAX_BYTES / ((size_t)n_advice * col_bytes))
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the columns exceed 256 MiB; use the device form");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const size_t in_bytes = pad64(m * rows * 32), adv_bytes = m * n_advice * col_bytes, over_bytes = m * sizeof(uint32_t);
+  const HostIn in{ids, m * rows * 32, 0};
+  const HostOut out[2] = {{over_or_null, over_or_null ? over_bytes : 0, in_bytes + adv_bytes, true}, {advice, adv_bytes, in_bytes, false}};
+  return host_round_trip(who, *ctx, "witness", in_bytes + adv_bytes + over_bytes, &in, 1, out, 2, [&](uint8_t* d) {
+    return sorted_witness_run(max_bits, acc_cols, log_n, m, rows, (const uint32_t*)d, (uint32_t*)(d + in_bytes),
+                              (uint32_t*)(d + in_bytes + adv_bytes), nullptr);
+  });
+} HM_API_CATCH("hm_sorted_witness_bn256_fr")
+
+int hm_fr_argsort_bn256_dev(const void* d_values, size_t n, uint64_t* d_perm, void* stream) try {
+  const char* who = "hm_fr_argsort_bn256_dev";
+  if (!d_values || !d_perm) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (n == 0 || n > ((size_t)1 << 26)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": n must be 1 .. 2^26");
+  if (((uintptr_t)d_values & 15u) || ((uintptr_t)d_perm & 7u))
+    return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a device pointer is not aligned (d_values: 16, d_perm: 8)");
+  if (ranges_overlap(d_values, n * 32, d_perm, n * 8)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": d_values overlaps d_perm");
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return fr_argsort_run((const uint32_t*)d_values, n, d_perm, (hipStream_t)stream);
+} HM_API_CATCH("hm_fr_argsort_bn256_dev")
+
 // ---- the SafeAccumulator circuit's witness (accumulator.inc: accumulator_row) -----------------------------------------------------
 // what the layout and both forms of the witness refuse; -> n_advice
 static int accumulator_witness_layout(const char* who, uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, uint32_t rows, uint32_t* n_advice) {

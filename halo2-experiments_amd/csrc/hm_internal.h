@@ -492,6 +492,15 @@ int poseidon_witness_run(const PoseidonSpec& s, uint32_t log_n, size_t m, const 
 int range_witness_run(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint32_t* d_values,
                       uint32_t* d_advice, uint32_t* d_over, hipStream_t stream);
 
+// sorted.hip: the sorted-column circuit's witness: column 0 the m x rows ids, columns 1 .. acc_cols the limbs of id[i+1] - id[i] - 1
+// mod r on rows 0 .. rows - 2, most significant first; every row of every column is written; d_over: null, or m counters of the gaps
+// with higher bits.  Asynchronous on `stream`; the arguments were checked by the caller (capi_hash.hip).
+int sorted_witness_run(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint32_t* d_ids,
+                       uint32_t* d_advice, uint32_t* d_over, hipStream_t stream);
+// d_perm[0 .. n): the rows of the n canonical Montgomery elements of d_values in the order of their canonical integers, equal
+// elements by ascending row.  Asynchronous on `stream`, stream-ordered scratch of its own; 1 <= n <= 2^26 checked by the caller.
+int fr_argsort_run(const uint32_t* d_values, size_t n, uint64_t* d_perm, hipStream_t stream);
+
 // accumulator.hip: the SafeAccumulator circuit's witness: m running totals of acc_cols limbs of max_bits bits (max_bits * acc_cols <= 64),
 // row 0 the initial limbs, row r the value r, the top limb's inverse, the carries and the limbs after adding it; every row of every
 // column is written.  inverses_ext: HOST memory, the 2^max_bits - 1 inverses of 1 .. 2^max_bits - 1 (host_fr.h: fr_small_inverses);

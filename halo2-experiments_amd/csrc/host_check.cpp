@@ -30,6 +30,7 @@ namespace hm {
 #include "ledger.inc"     // the lane function of the ledger openings' pairing operands (ledger.hip)
 #include "poseidon.inc"   // the per-hash Poseidon / Merkle node functions (poseidon.hip)
 #include "range.inc"      // the range-check witness's lane function (range.hip)
+#include "sorted.inc"     // the sorted-column witness's lane function and the argsort's record order (sorted.hip)
 #include "accumulator.inc" // the accumulator witness's row function (accumulator.hip)
 #include "keygen.inc"     // the permutation assembly's key packing and link rule (keygen.hip)
 #include "shplonk.inc"    // the SHPLONK set quotient's plan, coefficients and row formula (polyops.hip)
@@ -1087,6 +1088,26 @@ int hc_range_witness(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_
   for (size_t c = 0; c < m; ++c) over[c] = 0;
   for (uint64_t idx = 0; idx < a.lanes; ++idx) over[idx >> log_n] += range_witness_lane(a, idx) ? 1u : 0u;
   return 0;
+}
+
+// the lanes of sorted_witness_kernel, one after the other; over: m counters
+int hc_sorted_witness(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint32_t* ids, uint32_t* advice,
+                      uint32_t* over) {
+  if (max_bits == 0 || max_bits > RANGE_MAX_BITS || acc_cols == 0 || max_bits * acc_cols + log_n > RANGE_MAX_VALUE_BITS || log_n > 24 ||
+      rows == 0 || rows > ((uint64_t)1 << log_n))
+    return -1;
+  const SortedArgs a{ids, advice, over, (uint64_t)m << log_n, max_bits, acc_cols, log_n, rows};
+  for (size_t c = 0; c < m; ++c) over[c] = 0;
+  for (uint64_t idx = 0; idx < a.lanes; ++idx) over[idx >> log_n] += sorted_witness_lane(a, idx) ? 1u : 0u;
+  return 0;
+}
+
+// sorted_record_less on two records of 9 words: the order the argsort's network sorts by
+int hc_sorted_record_less(const uint32_t* a, const uint32_t* b) {
+  uint32_t x[9], y[9];
+  std::memcpy(x, a, 36);
+  std::memcpy(y, b, 36);
+  return sorted_record_less(x, y) ? 1 : 0;
 }
 
 // The accumulator witness with the rows of a circuit one after the other: what accumulator.hip's four launches compute, S_(r-1)

@@ -24,8 +24,15 @@ statement of this feature, which hashed the commitments only and opened C_gamma 
 ``ledger_openings``) are checked with all values zero, and a combined value of zero at a gamma drawn after the commitments pins
 every column to zero there.
 
-What it does not prove: that the ids are distinct.  A duplicate id is caught by the two users comparing their rows, not by the
-circuit; the module checks nothing about ids beyond their canonical form.  Commitments are deterministic (nothing is hidden), as in
+That the ids are pairwise distinct -- so that no row, id included, can be handed to two users and carry their liability once -- is
+proved under a second key, and only under it: ``prove_ledger(..., id_pk=)`` adds ``id_proof``, a proof of ``circuits.sorted_column``
+whose first commitment is C_id itself (the id column is unblinded there), and ``verify_ledger(..., id_vk=)`` checks it and that
+commitment.  The circuit wants the rows in ascending id order with neighbours less than 2^(max_bits * acc_cols) apart, and then
+max_bits * acc_cols + k <= 253 makes any two ids differ (``circuits.sorted_column`` has the argument); ``ledger_order`` gives the
+permutation that brings a ledger into that order.  The selector reaches rows 0 .. rows - 2, so the statement is about the ``rows`` live
+rows: pass ``rows`` to ``verify_ledger_user`` / ``verify_ledger_users`` as well, which then refuse an index at or behind it.  Without
+the second key nothing of this is proved, as before: a duplicate id is then caught by the two users comparing their rows, not by a
+circuit, and the module checks nothing about ids beyond their canonical form.  Commitments are deterministic (nothing is hidden), as in
 solvency.py.  ``verify_ledger_user`` on host integers is the oracle; ``verify_ledger_users`` builds every user's pairing operands in
 one kernel (csrc/ledger.inc: one lane per user) and checks them with one ``device_pairing.run_device`` call."""
 from __future__ import annotations
@@ -48,7 +55,7 @@ from .openings import _point, _scalar_int, domain_omega, open_all, open_at, veri
 from .pairing import g1_add, g1_mul, g1_on_curve
 from .prover import create_proofs
 from .solvency import _range_parameters
-from .synthesis import BLINDING_ROWS, range_witness
+from .synthesis import BLINDING_ROWS, range_witness, sorted_witness
 from .transcript import TranscriptError, check_encoding, check_multiopen, g1_decompress_int, g1_uncompressed_int
 from .verifier import verify_proof
 
@@ -63,7 +70,8 @@ class LedgerProof:
     """Published: ``id_commitment`` and ``commitments[p]`` ((x, y) integers, None for a zero column), ``range_proofs[p]`` the bytes
     of asset p's range proof, ``id_total`` and ``totals[p]`` the column sums as integers, ``zero_opening`` the opening of C_eta at 0
     (8 affine words).  The prover's own: ``columns``, the padded id and balance columns, a (P + 1, n, 4) GPU tensor from which
-    ``ledger_openings`` makes the users' openings."""
+    ``ledger_openings`` makes the users' openings.  With an id key (module docstring): ``id_proof``, the bytes of the sorted-column
+    proof over the id column, and ``rows``, the live rows it speaks about -- both published."""
     id_commitment: Optional[Tuple[int, int]]
     commitments: List[Optional[Tuple[int, int]]]
     range_proofs: List[bytes]
@@ -71,6 +79,8 @@ class LedgerProof:
     totals: List[int]
     zero_opening: np.ndarray
     columns: object = None
+    id_proof: bytes = None
+    rows: int = None
 
 
 # ---- the statement on host integers ---------------------------------------------------------------------------------------------------
@@ -169,12 +179,41 @@ def _words_canonical(w: np.ndarray) -> np.ndarray:
     return lt
 
 
+ARGSORT_TILE = 1024                  # csrc/sorted.hip: SRT_TILE, the records one workgroup sorts in LDS
+
+
+def _sorted_parameters(cs, who: str) -> Tuple[int, int]:
+    p = cs.parameters
+    if not (p.get("sorted") is True and "max_bits" in p and "acc_cols" in p and tuple(cs.unblinded_advice) == (0,)):
+        raise ValueError(f"{who}: the id key is not of circuits.sorted_column")
+    return p["max_bits"], p["acc_cols"]
+
+
+def ledger_order(ids):
+    """The permutation that brings a ledger into the order ``prove_ledger(..., id_pk=)`` wants: ``ids`` (rows, 4) GPU tensor of
+    canonical Montgomery words -> (rows,) int64 GPU tensor, the rows sorted by the ids' canonical integers, equal ids by ascending row
+    (a function of the input alone; ``hm_fr_argsort_bn256_dev``).  The caller applies it: ``ids[perm]``, ``balances[:, perm]``."""
+    import torch
+
+    if not (_is_tensor(ids) and ids.is_cuda and ids.dtype == torch.int64 and ids.dim() == 2 and ids.shape[1] == 4 and ids.shape[0] >= 1):
+        raise ValueError("ledger_order: ids must be a (rows, 4) int64 GPU tensor with at least one row")
+    ids = ids.contiguous()
+    perm = torch.empty(ids.shape[0], dtype=torch.int64, device=ids.device)
+    with torch.cuda.device(ids.device):
+        _lib.check(_lib.load().hm_fr_argsort_bn256_dev(_vp(ids.data_ptr()), ids.shape[0], _dev_ptr(perm), _vp(_stream_ptr(ids))))
+    return perm
+
+
 def prove_ledger(params, pk: ProvingKey, ids, balances, seed: int, check: bool = True, encoding: str = "halo2",
-                 multiopen: str = "shplonk") -> LedgerProof:
+                 multiopen: str = "shplonk", id_pk: ProvingKey = None) -> LedgerProof:
     """``balances``: a (rows, 4) GPU tensor of canonical Montgomery words, one asset, or a (P, rows, 4) stack, exactly as
     ``solvency.prove_balances`` takes them; ``ids``: a (rows, 4) GPU tensor, one id per row.  The range witness and the range proofs
     go through ``range_witness`` and ``create_proofs`` (asset p with seed + p); ``check``, ``encoding`` and
-    ``multiopen`` as there.  An id whose words are not below r raises ValueError; nothing else is checked about ids."""
+    ``multiopen`` as there.  An id whose words are not below r raises ValueError; nothing else is checked about ids unless
+    ``id_pk`` is given: a proving key of ``circuits.sorted_column`` made with ``SortedColumnLayout(k, max_bits, acc_cols, rows)`` for
+    these very ``rows``.  Then the ids, as passed, go through ``sorted_witness`` and ``create_proofs`` (seed + P), the proof's bytes and
+    ``rows`` are stored, and ``check`` raises ValueError when a gap does not fit -- the ids are not in ascending order, not distinct,
+    or neighbours are 2^(max_bits * acc_cols) or more apart; ``ledger_order`` gives the order."""
     import torch
 
     who = "prove_ledger"
@@ -182,6 +221,8 @@ def prove_ledger(params, pk: ProvingKey, ids, balances, seed: int, check: bool =
     check_multiopen(multiopen, who)
     cs = pk.vk.cs
     max_bits, acc_cols = _range_parameters(cs, who)
+    if cs.parameters.get("sorted"):
+        raise ValueError(f"{who}: pk is a key of circuits.sorted_column; it belongs in id_pk")
     if not (_is_tensor(balances) and balances.is_cuda and balances.dim() in (2, 3) and balances.shape[-1] == 4):
         raise ValueError(f"{who}: balances must be a (rows, 4) or (P, rows, 4) GPU tensor")
     values = (balances.unsqueeze(0) if balances.dim() == 2 else balances).contiguous()
@@ -199,7 +240,17 @@ def prove_ledger(params, pk: ProvingKey, ids, balances, seed: int, check: bool =
             if count:
                 raise ValueError(f"{who}: asset {p}: {count} balance(s) at or above 2^{max_bits * acc_cols}")
     empty = [[]]                                             # the instance column holds nothing
+    id_proof = None
+    if id_pk is not None:
+        id_bits, id_cols = _sorted_parameters(id_pk.vk.cs, who)
+        id_advice, id_over = sorted_witness(ids.contiguous(), k, id_bits, id_cols)
+        bad = int(id_over.cpu()[0]) if check else 0
+        if bad:
+            raise ValueError(f"{who}: {bad} gap(s) between neighbouring ids do not fit {id_bits * id_cols} bits: the ids are not in "
+                             "ascending order, not distinct, or too far apart (ledger_order gives the permutation that sorts them)")
     proofs = create_proofs(params, pk, advice, [empty] * P, seed, encoding=encoding, multiopen=multiopen)
+    if id_pk is not None:
+        id_proof = bytes(create_proofs(params, id_pk, id_advice, [empty], seed + P, encoding=encoding, multiopen=multiopen)[0])
     columns = torch.zeros((P + 1, n, 4), dtype=torch.int64, device=values.device)
     columns[0, :rows] = ids
     columns[1:] = advice[:, 0]                               # rows >= `rows` are zero
@@ -209,7 +260,9 @@ def prove_ledger(params, pk: ProvingKey, ids, balances, seed: int, check: bool =
     eta = ledger_eta(k, points[0], points[1:], sums[0], sums[1:])                             # after the sums are fixed
     combined = linear_combination([coeffs[j] for j in range(P + 1)], fr_array([pow(eta, j, R) for j in range(P + 1)]))
     _, zero_opening = open_at(params, combined, 0)
-    return LedgerProof(points[0], points[1:], list(proofs), sums[0], sums[1:], zero_opening, columns)
+    if id_pk is None:
+        return LedgerProof(points[0], points[1:], list(proofs), sums[0], sums[1:], zero_opening, columns)
+    return LedgerProof(points[0], points[1:], list(proofs), sums[0], sums[1:], zero_opening, columns, id_proof, rows)
 
 
 def ledger_openings(params, proof_or_columns):
@@ -257,15 +310,24 @@ def verify_ledger_totals(params, public, id_total: int, totals, zero_opening, pa
 
 
 def verify_ledger(params, vk: VerifyingKey, proof: LedgerProof, pairing: str = "host", tail=None, encoding: str = "halo2",
-                  multiopen: str = "shplonk") -> bool:
+                  multiopen: str = "shplonk", id_vk: VerifyingKey = None) -> bool:
     """Per asset: the range proof verifies and its first commitment is ``proof.commitments[p]``; then the one opening of C_eta at 0
     yields (id_total + sum_p eta^(p+1) totals[p]) / n, eta = ``ledger_eta`` of the commitments and these very sums.  ``tail``: six (8,) openings -- rows n - 6 .. n - 1 of ``ledger_openings``
     -- checked with the id and every balance zero (see the module docstring).  ``pairing``: where the opening checks run;
-    ``encoding`` / ``multiopen``: the range proofs' wire format and multiopen scheme."""
+    ``encoding`` / ``multiopen``: the range proofs' wire format and multiopen scheme.  ``id_vk``: a verifying key of
+    ``circuits.sorted_column`` (its parameters carry ``sorted=True``; anything else raises ValueError) made for the ledger's live rows;
+    then False unless ``proof.id_proof`` verifies under it and its first commitment, decoded as the balance commitments are, is
+    ``proof.id_commitment`` -- the ids of rows 0 .. rows - 1 are pairwise distinct (module docstring)."""
     who = "verify_ledger"
     check_encoding(encoding, who)
     check_multiopen(multiopen, who)
     _range_parameters(vk.cs, who)
+    if vk.cs.parameters.get("sorted"):
+        raise ValueError(f"{who}: vk is a key of circuits.sorted_column; it belongs in id_vk")
+    if id_vk is not None:
+        _sorted_parameters(id_vk.cs, who)
+        if id_vk.domain.k != vk.domain.k:
+            raise ValueError(f"{who}: id_vk is a key for k = {id_vk.domain.k}, vk for k = {vk.domain.k}")
     P = len(proof.commitments)
     if P < 1 or not (len(proof.range_proofs) == len(proof.totals) == P):
         return False
@@ -281,6 +343,16 @@ def verify_ledger(params, vk: VerifyingKey, proof: LedgerProof, pairing: str = "
             return False
         if first != _point(proof.commitments[p]):
             return False
+    if id_vk is not None:
+        ip = proof.id_proof
+        if not isinstance(ip, (bytes, bytearray)) or not verify_proof(params, id_vk, [[]], bytes(ip), encoding=encoding, multiopen=multiopen):
+            return False
+        try:
+            first = g1_uncompressed_int(bytes(ip[:64])) if encoding == "evm" else g1_decompress_int(bytes(ip[:32]))
+        except TranscriptError:
+            return False
+        if first != _point(proof.id_commitment):
+            return False
     _, _, _, _, c_gamma = _statement(params, proof, k, who)
     if c_gamma is False or not verify_ledger_totals(params, proof, proof.id_total, proof.totals, proof.zero_opening, pairing=pairing, k=k):
         return False
@@ -294,10 +366,11 @@ def verify_ledger(params, vk: VerifyingKey, proof: LedgerProof, pairing: str = "
     return True
 
 
-def verify_ledger_user(params, public, i: int, user_id, balances, opening, pairing: str = "host", k: int = None) -> bool:
+def verify_ledger_user(params, public, i: int, user_id, balances, opening, pairing: str = "host", k: int = None, rows: int = None) -> bool:
     """User i's own check on host integers -- the oracle of ``verify_ledger_users``.  ``public``: a ``LedgerProof``,
     (id_commitment, commitments) or a ``LedgerStatement``; ``user_id`` and every entry of ``balances`` (one per asset): an integer or 4 words; ``opening``:
-    (x, y) integers, None, or 8 affine words.  k = params.k unless given."""
+    (x, y) integers, None, or 8 affine words.  k = params.k unless given.  ``rows``: the ledger's live rows, as the id proof's key was
+    made for them; an index at or behind it is False -- the distinctness proved under the id key does not reach such a row."""
     who = "verify_ledger_user"
     k, _, cs, gamma, c_gamma = _statement(params, public, k, who)
     if not 0 <= int(i) < 1 << k:
@@ -305,7 +378,7 @@ def verify_ledger_user(params, public, i: int, user_id, balances, opening, pairi
     bal = [_scalar_int(b) for b in balances]
     if len(bal) != len(cs):
         raise ValueError(f"{who}: one balance per asset")
-    if c_gamma is False:
+    if c_gamma is False or (rows is not None and int(i) >= int(rows)):
         return False
     y = combined_value(gamma, _scalar_int(user_id), bal)
     return verify_opening(params, c_gamma, pow(domain_omega(k), int(i), R), y, opening, pairing=pairing)
@@ -392,7 +465,7 @@ def ledger_pairs(params, public, indices, ids, balances, openings, k: int = None
     return k, (d_g1, d_flags, d_g2)
 
 
-def verify_ledger_users(params, public, indices, ids, balances, openings, k: int = None) -> List[bool]:
+def verify_ledger_users(params, public, indices, ids, balances, openings, k: int = None, rows: int = None) -> List[bool]:
     """``verify_ledger_user`` for B users on the device, every answer that user's own: ``public`` as for ``verify_ledger_user``
     (a ``LedgerStatement`` spares the host products of C_gamma); ``indices`` B rows, ``ids`` (B, 4),
     ``balances`` (B, P, 4) and ``openings`` (B, 8) words, each an int64 GPU tensor or a uint64 array.  One upload of what lies on the
@@ -400,7 +473,9 @@ def verify_ledger_users(params, public, indices, ids, balances, openings, k: int
     device, one ``device_pairing.run_device`` call with the offsets 0, 2, 4, .., one download of statuses and flags; user b passes
     when its status is 1 and its flag is 0 -- a flagged user's rows are identities and WOULD pass the pairing, so the flag decides.
     Flagged: an opening with a coordinate word >= p or off the curve, an id or balance word pattern >= r.  A row outside the domain
-    or a wrong shape or dtype raises ValueError before any launch; B = 0 gives []; a commitment off the curve gives all False."""
+    or a wrong shape or dtype raises ValueError before any launch; B = 0 gives []; a commitment off the curve gives all False.
+    ``rows``: as for ``verify_ledger_user`` -- a user whose index is at or behind it is flagged on the host, as a malformed user is
+    flagged by the kernel, and comes back False whatever its pairing says."""
     import torch
 
     k, made = ledger_pairs(params, public, indices, ids, balances, openings, k)
@@ -409,9 +484,15 @@ def verify_ledger_users(params, public, indices, ids, balances, openings, k: int
     B = len(indices)
     if made is False:
         return [False] * B
+    outside = None
+    if rows is not None:                                     # the indices are a flat sequence of integers: ledger_pairs has checked
+        outside = np.asarray(indices.cpu() if _is_tensor(indices) else indices) >= int(rows)
     d_g1, d_flags, d_g2 = made
     with torch.cuda.device(d_g1.device):
         d_off = torch.arange(0, 2 * B + 1, 2, dtype=torch.int32, device=d_g1.device)
         d_status = device_pairing.run_device(d_g1, d_g2, d_off, B)
         both = torch.stack([d_status, d_flags]).cpu().numpy()
-    return ((both[0] == 1) & (both[1] == 0)).tolist()
+    verdicts = (both[0] == 1) & (both[1] == 0)
+    if outside is not None:
+        verdicts &= ~outside
+    return verdicts.tolist()

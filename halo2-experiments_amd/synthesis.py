@@ -577,6 +577,99 @@ class RangeCheckLayout:
         return adv
 
 
+class SortedColumnLayout:
+    """The rows of ``circuits.sorted_column(max_bits, acc_cols)`` for an id column with ``rows`` live rows; the
+    project's own, modelled on ``RangeCheckLayout``.  The range table on rows 0 .. 2^max_bits - 1 of fixed 0; id i on row i, with the
+    limbs of the gap to id i + 1 beside it and the selector set, for i = 0 .. rows - 2; row rows - 1 holds the last id alone (no
+    selector: it has no next id, and the gate must not reach the zero padding).  No copies, an empty instance column.
+
+    With B = max_bits * acc_cols the gate gives id[i] = id[0] + s_i mod r for integers 0 = s_0 < s_1 < .. < s_(rows-1) <
+    2^(k + B); the layout refuses B + k > 253, under which those sums stay below r and the ids are pairwise distinct whatever id[0]
+    is (the argument in full: ``circuits.sorted_column``)."""
+    NAME = "SortedColumnLayout"
+    ID, RANGE, SELECTOR = 0, 0, 1             # advice 0; fixed 0, 1 (circuits.sorted_column()'s allocation order)
+    N_FIXED = 2
+
+    def __init__(self, k: int, max_bits: int = 4, acc_cols: int = 4, rows: int = 1):
+        if not 1 <= max_bits <= 16:
+            raise ValueError("SortedColumnLayout: max_bits must be 1 .. 16")
+        if acc_cols < 1 or max_bits * acc_cols > 253:
+            raise ValueError("SortedColumnLayout: acc_cols must be at least 1 and max_bits * acc_cols at most 253")
+        if max_bits * acc_cols + k > 253:
+            raise ValueError(f"SortedColumnLayout: max_bits * acc_cols + k = {max_bits * acc_cols + k} exceeds 253: the sum of up to 2^k "
+                             "gaps of max_bits * acc_cols bits could reach r, and two ids could then agree mod r")
+        if rows < 1:
+            raise ValueError("SortedColumnLayout: rows must be at least 1")
+        self.k, self.n, self.max_bits, self.acc_cols, self.rows = k, 1 << k, max_bits, acc_cols, rows
+        self.width = max_bits * acc_cols
+        self.N_ADVICE = 1 + acc_cols
+        self.LIMBS = tuple(range(1, 1 + acc_cols))
+        self.table_rows = 1 << max_bits
+        self.used_rows = self.rows_needed(max_bits, rows)
+        if self.used_rows > self.n - BLINDING_ROWS:
+            raise ValueError(f"SortedColumnLayout: {self.used_rows} rows are needed, 2^{k} - {BLINDING_ROWS} is fewer "
+                             f"(min_k = {self.min_k(max_bits, rows)})")
+        cols = (("advice", self.ID),) + tuple(("advice", c) for c in self.LIMBS) + (("fixed", self.SELECTOR),)
+        self.regions = [Region(f"load range check table of {max_bits} bits", 0, self.table_rows, (("fixed", self.RANGE),))]
+        self.regions += [Region("assign id and decomposed gap", i, 1, cols) for i in range(rows - 1)]
+        self.regions += [Region("assign last id", rows - 1, 1, (("advice", self.ID),))]
+
+    @staticmethod
+    def rows_needed(max_bits: int, rows: int) -> int:
+        return max(rows, 1 << max_bits)
+
+    @classmethod
+    def min_k(cls, max_bits: int, rows: int) -> int:
+        return (cls.rows_needed(max_bits, rows) + BLINDING_ROWS - 1).bit_length()
+
+    def check_constraint_system(self, cs: ConstraintSystem) -> None:
+        if (cs.num_advice, cs.num_fixed, cs.num_instance) != (self.N_ADVICE, self.N_FIXED, 1) or \
+                list(cs.equality) != [("advice", c) for c in self.LIMBS] or len(cs.lookups) != self.acc_cols or \
+                cs.parameters != dict(max_bits=self.max_bits, acc_cols=self.acc_cols, sorted=True):
+            raise ValueError(f"SortedColumnLayout: the constraint system is not circuits.sorted_column({self.max_bits}, {self.acc_cols})")
+
+    def selector_rows(self) -> Dict[int, List[int]]:
+        return {self.SELECTOR: list(range(self.rows - 1))}
+
+    def fixed_columns(self) -> List[List[int]]:
+        cols = [[0] * self.n for _ in range(self.N_FIXED)]
+        cols[self.RANGE][:self.table_rows] = range(self.table_rows)
+        cols[self.SELECTOR][:self.rows - 1] = [1] * (self.rows - 1)
+        return cols
+
+    def copies(self) -> List[Tuple[Cell, Cell]]:
+        return []
+
+    def instance(self) -> List[List[int]]:
+        return [[]]
+
+    def gaps(self, ids: Sequence[int]) -> List[int]:
+        """(id[i+1] - id[i] - 1) mod r for i = 0 .. rows - 2"""
+        if len(ids) != self.rows:
+            raise ValueError(f"SortedColumnLayout: {self.rows} ids expected")
+        v = [int(x) % R for x in ids]
+        return [(v[i + 1] - v[i] - 1) % R for i in range(self.rows - 1)]
+
+    def assign_ints(self, ids: Sequence[int]) -> List[List[int]]:
+        """The 1 + acc_cols advice columns.  Nothing is judged: the limbs are the low max_bits * acc_cols bits of the gap mod r, so ids
+        that are not ascending, equal, or further apart than 2^(max_bits * acc_cols) give a witness that fails the gate.  The limbs of
+        row rows - 1 and of every row behind it are zero."""
+        gaps = self.gaps(ids)
+        adv = [[0] * self.n for _ in range(self.N_ADVICE)]
+        mask = (1 << self.max_bits) - 1
+        for row, v in enumerate(ids):
+            adv[self.ID][row] = int(v) % R
+        for row, g in enumerate(gaps):
+            for i, c in enumerate(self.LIMBS):
+                adv[c][row] = (g >> (self.max_bits * (self.acc_cols - 1 - i))) & mask
+        return adv
+
+    def over(self, ids: Sequence[int]) -> int:
+        """what the GPU witness counts: the rows i <= rows - 2 whose gap has a bit at or above max_bits * acc_cols -- unsorted,
+        duplicate and too distant ids alike"""
+        return sum(g >> self.width != 0 for g in self.gaps(ids))
+
+
 class SafeAccumulatorLayout:
     """``SafeAccumulatorCircuit::synthesize`` for ``circuits.safe_accumulator(max_bits, acc_cols)`` with ``rows`` added values, as
     ONE running table (DESIGN.md section 26) -- the table the reference's README draws and its gate at ``Rotation::prev`` is written
@@ -715,7 +808,7 @@ class SafeAccumulatorLayout:
 
 
 # ---- keygen's permutation columns -----------------------------------------------------------------------------------------------
-AnyLayout = Union[MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, RangeCheckLayout, SafeAccumulatorLayout]      # anything with ``n`` and ``copies()``
+AnyLayout = Union[MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, RangeCheckLayout, SortedColumnLayout, SafeAccumulatorLayout]      # anything with ``n`` and ``copies()``
 
 
 def permutation_cells(cs: ConstraintSystem, layout: "AnyLayout") -> List[List[Tuple[int, int]]]:
@@ -991,6 +1084,59 @@ def range_witness_host(values: np.ndarray, k: int, max_bits: int = 4, acc_cols: 
     adv = np.zeros((m, 1 + acc_cols, 1 << k, 4), dtype=np.uint64)
     over = np.zeros(m, dtype=np.uint32)
     _lib.check(_lib.load().hm_range_witness_bn256_fr(max_bits, acc_cols, k, m, rows, _ptr(vs), _ptr(adv), over.ctypes.data_as(_u32p)))
+    return adv, over
+
+
+def sorted_c_layout(k: int, max_bits: int = 4, acc_cols: int = 4, rows: int = 1) -> Dict[str, int]:
+    """``hm_sorted_witness_layout``: the numbers the sorted-column kernel uses (no device needed), beside ``SortedColumnLayout``'s;
+    ValueError when the two differ."""
+    n_adv, table_rows = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    _lib.check(_lib.load().hm_sorted_witness_layout(max_bits, acc_cols, k, rows, ctypes.byref(n_adv), ctypes.byref(table_rows)))
+    lay = SortedColumnLayout(k, max_bits, acc_cols, rows)
+    out = {"n_advice": n_adv.value, "table_rows": table_rows.value}
+    if out != {"n_advice": lay.N_ADVICE, "table_rows": lay.table_rows}:
+        raise ValueError(f"sorted_c_layout: the C layout {out} is not SortedColumnLayout's")
+    return out
+
+
+def sorted_witness(ids, k: int, max_bits: int = 4, acc_cols: int = 4, out=None):
+    """The sorted-column witnesses of m circuits: ``ids`` (m, rows, 4) -- or (rows, 4), one circuit -- GPU tensor of canonical
+    Montgomery words -> (advice (m, 1 + acc_cols, 2^k, 4), over (m,) int32: per circuit the rows i <= rows - 2 whose gap
+    id[i+1] - id[i] - 1 mod r is at or above 2^(max_bits * acc_cols) -- ids out of order, equal or too far apart -- whose limbs are
+    the gap's low bits only); every word written, the limbs of rows >= ``rows`` - 1 zero; asynchronous on the current stream.
+    ``out``: an advice tensor to fill instead of a new one (it may be uninitialised)."""
+    import torch
+
+    if not (_is_cuda_words(ids) and ids.dim() in (2, 3) and ids.shape[-1] == 4):
+        raise ValueError("sorted_witness: ids must be a contiguous (m, rows, 4) or (rows, 4) 64-bit GPU tensor")
+    m, rows = (1, ids.shape[0]) if ids.dim() == 2 else (ids.shape[0], ids.shape[1])
+    if m == 0 or rows == 0:
+        raise ValueError("sorted_witness: no ids")
+    if out is not None and out.is_cuda and out.device != ids.device:
+        raise ValueError(f"sorted_witness: out is on {out.device}, ids on {ids.device}")
+    for name, t in (("ids", ids), ("out", out)):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"sorted_witness: {name} must be 16-byte aligned")
+    out = _witness_out("sorted_witness", out, m, 1 + acc_cols, 1 << k, ids.device)
+    over = torch.empty(m, dtype=torch.int32, device=ids.device)
+    with torch.cuda.device(ids.device):
+        _lib.check(_lib.load().hm_sorted_witness_bn256_fr_dev(max_bits, acc_cols, k, m, rows, ctypes.c_void_p(ids.data_ptr()),
+                                                             ctypes.c_void_p(out.data_ptr()), _dev_ptr(over, _u32p),
+                                                             ctypes.c_void_p(_stream_ptr(ids))))
+    return out, over
+
+
+def sorted_witness_host(ids: np.ndarray, k: int, max_bits: int = 4, acc_cols: int = 4):
+    """``sorted_witness`` on a numpy (m, rows, 4) array through the host-pointer form (columns below 256 MiB)."""
+    vs = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64))
+    if vs.ndim == 2:
+        vs = vs.reshape(1, -1, 4)
+    if vs.ndim != 3 or vs.shape[2] != 4 or vs.shape[0] == 0 or vs.shape[1] == 0:
+        raise ValueError("sorted_witness_host: ids must be a non-empty (m, rows, 4) array")
+    m, rows = vs.shape[0], vs.shape[1]
+    adv = np.zeros((m, 1 + acc_cols, 1 << k, 4), dtype=np.uint64)
+    over = np.zeros(m, dtype=np.uint32)
+    _lib.check(_lib.load().hm_sorted_witness_bn256_fr(max_bits, acc_cols, k, m, rows, _ptr(vs), _ptr(adv), over.ctypes.data_as(_u32p)))
     return adv, over
 
 

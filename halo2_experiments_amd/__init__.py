@@ -23,7 +23,7 @@ from .batch_verifier import BatchVerifier, verify_each, verify_proofs  # noqa: F
 from .domain import EvaluationDomain  # noqa: F401
 from .keygen import (ProvingKey, VerifyingKey, copy_pairs, keygen_pk, keygen_vk, permutation_cells_dev,  # noqa: F401
                      permutation_columns_dev)
-from .ledger import (LedgerProof, LedgerStatement, ledger_eta, ledger_gamma, ledger_openings, ledger_statement,  # noqa: F401
+from .ledger import (LedgerProof, LedgerStatement, ledger_eta, ledger_gamma, ledger_openings, ledger_order, ledger_statement,  # noqa: F401
                      prove_ledger, verify_ledger, verify_ledger_user, verify_ledger_users)
 from .mock_prover import MockProver, MockResult, NotSatisfied  # noqa: F401
 from .openings import OpeningTable, open_all, open_all_ints, open_at, verify_opening, verify_openings  # noqa: F401
@@ -32,9 +32,10 @@ from .poseidon import MerkleSumTree, MerkleTree, Spec, poseidon_hash, poseidon_h
 from .prover import create_proof, create_proof_multi, create_proofs  # noqa: F401
 from .shplonk import construct_intermediate_sets, create_openings, set_quotient, set_quotient_batch, set_quotient_ints  # noqa: F401
 from .solvency import BalanceProof, prove_balances, user_openings, verify_balances, verify_user, verify_users  # noqa: F401
-from .synthesis import (MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, RangeCheckLayout, merkle_sum_witness,  # noqa: F401
+from .synthesis import (MerkleSumTreeLayout, MerkleTreeV3Layout, PoseidonCircuitLayout, RangeCheckLayout, SortedColumnLayout, merkle_sum_witness,  # noqa: F401
                         merkle_sum_witness_host, merkle_witness, merkle_witness_host, permutation_columns, poseidon_circuit_witness,
-                        poseidon_circuit_witness_host, range_c_layout, range_witness, range_witness_host)
+                        poseidon_circuit_witness_host, range_c_layout, range_witness, range_witness_host, sorted_c_layout, sorted_witness,
+                        sorted_witness_host)
 from .transcript import Blake2bRead, Blake2bWrite, KeccakRead, KeccakWrite, keccak256  # noqa: F401
 from .verifier import verify_proof, verify_proof_multi  # noqa: F401
 
@@ -52,4 +53,5 @@ __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_mult
            "OpeningTable", "open_all", "open_all_ints", "open_at", "verify_opening", "verify_openings",
            "RangeCheckLayout", "range_witness", "range_witness_host", "range_c_layout", "BalanceProof", "prove_balances", "verify_balances",
            "user_openings", "verify_user", "verify_users",
-           "LedgerProof", "LedgerStatement", "ledger_statement", "prove_ledger", "verify_ledger", "ledger_gamma", "ledger_eta", "ledger_openings", "verify_ledger_user", "verify_ledger_users"]
+           "LedgerProof", "LedgerStatement", "ledger_statement", "prove_ledger", "verify_ledger", "ledger_gamma", "ledger_eta", "ledger_openings", "verify_ledger_user", "verify_ledger_users",
+           "SortedColumnLayout", "sorted_witness", "sorted_witness_host", "sorted_c_layout", "ledger_order"]

@@ -721,6 +721,32 @@ int hm_range_witness_bn256_fr_dev(uint32_t max_bits, uint32_t acc_cols, uint32_t
 int hm_range_witness_bn256_fr(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint64_t* values,
                               uint64_t* advice, uint32_t* over_or_null);
 
+/* The witness of the sorted-column circuit (this project's own: "the ids of this committed column are pairwise distinct"): advice
+ * column 0 holds the ids, columns 1 .. acc_cols on rows 0 .. rows - 2 the limbs of the gap id[i+1] - id[i] - 1 mod r, max_bits bits
+ * each, most significant first, so that the gap equals sum limb_j * 2^(max_bits * (acc_cols - 1 - j)) whenever it is below
+ * 2^(max_bits * acc_cols); the limbs of row rows - 1 and of every row behind it are zero.
+ * layout: needs no device; *out_n_advice = 1 + acc_cols, *out_table_rows = 2^max_bits, the rows of the fixed range column.
+ * witness: m circuits of `rows` ids each; d_ids m x rows canonical elements; d_advice m x (1 + acc_cols) x 2^log_n elements (column c
+ * of circuit u is contiguous), every word of which is written.  The limbs are the low max_bits * acc_cols bits of the gap; nothing is
+ * judged: ids that are not ascending, equal or too far apart give a witness that fails the gate, and d_over_or_null, unless NULL,
+ * receives per circuit the number of such rows (m u32, set by every call).  Asynchronous on `stream`; no stream-ordered memory of the
+ * library's is used.
+ * HM_ERR_BAD_ARG, before anything is written or launched: what hm_range_witness_* refuse, and max_bits * acc_cols + log_n > 253 (with
+ * it no two ids of a column whose gaps are all in range agree mod r). */
+int hm_sorted_witness_layout(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, uint32_t rows, uint32_t* out_n_advice,
+                             uint32_t* out_table_rows);
+int hm_sorted_witness_bn256_fr_dev(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const void* d_ids,
+                                   void* d_advice, uint32_t* d_over_or_null, void* stream);
+int hm_sorted_witness_bn256_fr(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, size_t m, uint32_t rows, const uint64_t* ids,
+                               uint64_t* advice, uint32_t* over_or_null);
+/* The order that brings a column into the sorted-column circuit's: d_perm[0 .. n) receives the rows of the n canonical Montgomery
+ * elements of d_values, as 64-bit integers, sorted by the elements' canonical integers, equal elements by ascending row -- a
+ * function of the input alone.  A bitonic network over (key, row) records of 9 words, the same launches whatever the values;
+ * asynchronous on `stream`, with stream-ordered scratch of the library's (36 bytes for each of the next power of two of n).
+ * HM_ERR_BAD_ARG, before anything is launched: NULL, n = 0 or above 2^26, d_values not 16-byte or d_perm not 8-byte aligned, the two
+ * overlapping. */
+int hm_fr_argsort_bn256_dev(const void* d_values, size_t n, uint64_t* d_perm, void* stream);
+
 /* The witness of the accumulator circuit (the reference's SafeAccumulator): a running total of acc_cols limbs of max_bits bits, most
  * significant first, W = max_bits * acc_cols <= 64 bits in all.  Advice column 0 holds the added values, column 1 the inverse of the
  * top limb (0 when that limb is 0), columns 2 .. 1 + acc_cols the binary carries, columns 2 + acc_cols .. 1 + 2 acc_cols the limbs.
