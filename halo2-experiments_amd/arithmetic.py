@@ -441,6 +441,69 @@ def permute_expression_pairs(input_columns, table_columns, usable_rows: int, bli
     return outs
 
 
+LOGUP_COUNT_BITS = 20              # csrc/logup.inc LU_COUNT_BITS: table keys below 2^this are counted in value bins, nothing is sorted
+
+
+def logup_multiplicities(table_columns, input_columns, usable_rows: int, outs=None):
+    """The multiplicity columns of logUp arguments (``hm_logup_multiplicities_bn256_fr_dev``), all in one call:
+    ``table_columns[a]`` the compressed table of argument a, ``input_columns[a]`` the list of its compressed inputs, all (n, 4) GPU
+    tensors of which rows [0, usable_rows) are read.  -> one (n, 4) tensor per argument: on row i < usable_rows the number of
+    (input, row) pairs holding the table's value of row i if i is the first row holding it, else 0; rows from ``usable_rows`` on are
+    zero (the caller's blinding).  An input value its table lacks raises ``Halo2Mi355xError`` (NOT_FOUND) carrying the arguments'
+    indices in ``.missing``."""
+    import torch
+
+    lib = _lib.load()
+    tabs, ins = list(table_columns), [list(c) for c in input_columns]
+    if len(tabs) != len(ins):
+        raise ValueError("logup_multiplicities: one list of inputs per table")
+    if not tabs:
+        return []
+    n = _tensor_rows(tabs[0], 4, "table_columns")
+    for c in tabs + [c for row in ins for c in row]:
+        if not _is_tensor(c) or _tensor_rows(c, 4, "columns") != n:
+            raise ValueError("logup_multiplicities: columns must be GPU tensors of one length")
+    if not 1 <= usable_rows <= n:
+        raise ValueError("logup_multiplicities: usable_rows out of range")
+    if any(not row for row in ins):
+        raise ValueError("logup_multiplicities: an argument without inputs")
+    if outs is None:
+        outs = list(torch.zeros((len(tabs), n, 4), dtype=torch.int64, device=tabs[0].device))
+    elif len(outs) != len(tabs) or any(not _is_tensor(o) or _tensor_rows(o, 4, "outs") != n for o in outs):
+        raise ValueError("logup_multiplicities: one output of the columns' length per argument")
+    counts = (ctypes.c_uint32 * len(tabs))(*[len(row) for row in ins])
+    missing = (ctypes.c_int * len(tabs))()
+    rc = lib.hm_logup_multiplicities_bn256_fr_dev(_ptr_array(tabs), _ptr_array([c for row in ins for c in row]), counts, len(tabs), usable_rows,
+                                                  _ptr_array(list(outs)), missing, ctypes.c_void_p(_stream_ptr(tabs[0])))
+    if rc != _lib.HM_OK:
+        err = _lib.Halo2Mi355xError(rc, lib.hm_last_error().decode())
+        err.missing = [i for i in range(len(tabs)) if missing[i]]
+        raise err
+    return list(outs)
+
+
+def grand_sum_batch(terms, outs=None):
+    """The running sums of logUp arguments (``hm_fr_grand_sum_batch_dev``): for every (n, 4) GPU tensor of ``terms``
+    out[i] = sum_{j < i} terms[j] mod r -- exclusive, out[0] = 0 -- in one launch chain.  ``outs[j]`` may be ``terms[j]`` itself.
+    Returns the list of outputs."""
+    import torch
+
+    terms = list(terms)
+    if not terms:
+        return []
+    if not all(_is_tensor(t) for t in terms):
+        raise TypeError("grand_sum_batch: terms must be GPU tensors")
+    n = _tensor_rows(terms[0], 4, "terms[0]")
+    if any(_tensor_rows(t, 4, "terms") != n for t in terms):
+        raise ValueError("grand_sum_batch: columns differ in length")
+    if outs is None:
+        outs = [torch.empty((n, 4), dtype=torch.int64, device=terms[0].device) for _ in terms]
+    elif len(outs) != len(terms) or any(_tensor_rows(o, 4, "outs") != n for o in outs):
+        raise ValueError("grand_sum_batch: outs and terms differ in shape")
+    _lib.check(_lib.load().hm_fr_grand_sum_batch_dev(_ptr_array(terms), n, _ptr_array(list(outs)), len(terms), ctypes.c_void_p(_stream_ptr(terms[0]))))
+    return list(outs)
+
+
 def g1_fixed_base_mul(scalars, base_xy: np.ndarray):
     """out[i] = [scalars[i]] * base, affine (ParamsKZG::setup's per-row G1 work).  GPU tensors only."""
     import torch

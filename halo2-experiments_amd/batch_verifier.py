@@ -78,7 +78,7 @@ from .proof_layout import (EVM_POINT, EVM_SKIP, EVM_TAIL, GWC_RECORD, MAX_CIRCUI
                            MultiTermsPlan, ProofLayout, R, TermsPlan, _instance_columns, _layout_instances, derive_randomizer, proof_sums_ints, proof_terms_ints,
                            read_proof_ints, shared_points, terms_from_challenges, transcript_challenges)
 from .shplonk import g1_words_to_int
-from .transcript import check_encoding, check_multiopen
+from .transcript import check_encoding, check_lookup, check_multiopen
 from .verifier import _vk_digest
 
 VERDICT_CHUNK = 1 << 16                                                # proofs per pairing call of ``verdicts``: the largest measured size
@@ -118,9 +118,12 @@ class BatchVerifier:
     multi-circuit proofs in this encoding are the one combination left out (``circuits`` > 1 with "evm": ValueError)."""
 
     def __init__(self, params, vk: VerifyingKey, seed=None, pairing: str = "host", transcript: str = "host", encoding: str = "halo2",
-                 circuits: int = 1, multiopen: str = "shplonk"):
+                 circuits: int = 1, multiopen: str = "shplonk", lookup: str = "halo2"):
         check_encoding(encoding, "BatchVerifier")
         check_multiopen(multiopen, "BatchVerifier")
+        if check_lookup(lookup, "BatchVerifier") != "halo2":       # also the answer of verify_proofs and verify_each, which build one
+            raise ValueError("BatchVerifier: lookup=\"logup\" proofs are not batch-verified (verify_proof reads them; the terms plans and "
+                             "kernels walk the permutation-based lookup argument only)")
         if multiopen == "gwc" and circuits != 1:
             raise ValueError("BatchVerifier: multi-circuit batches with the \"gwc\" multiopen are not supported (circuits > 1)")
         if pairing not in device_pairing.MODES:
@@ -513,24 +516,24 @@ def _batch_of(who: str, params, vk: VerifyingKey, instances, proofs, seed, **mod
 
 
 def verify_proofs(params, vk: VerifyingKey, instances, proofs, seed=None, trapdoor: int = None, pairing: str = "host",
-                  transcript: str = "host", encoding: str = "halo2", circuits: int = 1, multiopen: str = "shplonk") -> bool:
+                  transcript: str = "host", encoding: str = "halo2", circuits: int = 1, multiopen: str = "shplonk", lookup: str = "halo2") -> bool:
     """True when every ``proofs[i]`` is a valid single-circuit proof of ``vk`` for ``instances[i]``: one ``BatchVerifier``, one check
     (``pairing`` / ``transcript``: where that check's pairing and the proofs' transcripts run, ``encoding``: the proofs' wire format,
     ``circuits=m``: every proof is a ``create_proof_multi`` proof and ``instances[i]`` its m instances, ``multiopen``: the scheme
-    the proofs end in, as on ``BatchVerifier``)"""
+    the proofs end in, as on ``BatchVerifier``; ``lookup="logup"`` raises ValueError there: such proofs are not batch-verified)"""
     return _batch_of("verify_proofs", params, vk, instances, proofs, seed, pairing=pairing, transcript=transcript, encoding=encoding,
-                     circuits=circuits, multiopen=multiopen).finalize(trapdoor)
+                     circuits=circuits, multiopen=multiopen, lookup=lookup).finalize(trapdoor)
 
 
 def verify_each(params, vk: VerifyingKey, instances, proofs, seed=None, trapdoor: int = None, pairing: str = "host",
-                transcript: str = "host", encoding: str = "halo2", circuits: int = 1, multiopen: str = "shplonk") -> List[bool]:
+                transcript: str = "host", encoding: str = "halo2", circuits: int = 1, multiopen: str = "shplonk", lookup: str = "halo2") -> List[bool]:
     """[is ``proofs[i]`` a valid single-circuit proof of ``vk`` for ``instances[i]``]: one ``BatchVerifier``, its ``verdicts`` -- the
     per-proof sums in one launch and, with ``pairing="device"``, one pairing call for all proofs (keywords as on ``verify_proofs``;
-    ``multiopen="gwc"`` raises ValueError: no verdict per proof under GWC)"""
+    ``multiopen="gwc"`` raises ValueError: no verdict per proof under GWC; ``lookup="logup"`` raises it too, as on ``BatchVerifier``)"""
     check_multiopen(multiopen, "verify_each")
     if multiopen == "gwc":
         raise ValueError("verify_each: per-proof verdicts are not available with the \"gwc\" multiopen")
     return _batch_of("verify_each", params, vk, instances, proofs, seed, pairing=pairing, transcript=transcript, encoding=encoding,
-                     circuits=circuits).verdicts(trapdoor)
+                     circuits=circuits, lookup=lookup).verdicts(trapdoor)
 
 

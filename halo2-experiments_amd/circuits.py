@@ -27,7 +27,7 @@ from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Sequence, Tuple
 
 from .evaluation import (Advice, Challenge, Constant, Expression, Fixed, GraphEvaluator, Instance, Negated, Product, Scaled, Sum,
-                         lookup_expressions, permutation_expressions)
+                         logup_expressions, lookup_expressions, permutation_expressions)
 from .domain import FR_MODULUS
 
 R = FR_MODULUS
@@ -132,6 +132,27 @@ class ConstraintSystem:
             if (index, 0) not in found[kind]:
                 found[kind].append((index, 0))
         return found["advice"], found["fixed"], found["instance"]
+
+    def logup_arguments(self) -> List[Tuple[List[Expression], List[List[Expression]]]]:
+        """The arguments of ``lookup="logup"`` as (table expressions, [input expression lists]): a pure function
+        of the lookups.  With D = ``degree()`` the lookups are walked in order; a lookup joins the open argument whose table expression
+        list is structurally equal to its own if afterwards 2 + deg(table) + sum_j deg(input_j) <= D (the degree of a list is the
+        maximum over its members), otherwise it opens a new argument for that table, which becomes the open one for that table.  A
+        lookup alone always fits, by the definition of D, so asking never raises the degree: ``extended_k`` and the keys stay."""
+        D = self.degree()
+        deg = lambda exprs: max(degree(e) for e in exprs)
+        out: List[Tuple[List[Expression], List[List[Expression]]]] = []
+        open_for: List[int] = []                           # per distinct table, in order of first use: its open argument
+        for ins, tabs in self.lookups:
+            at = next((g for g in open_for if out[g][0] == list(tabs)), None)
+            if at is not None and 2 + deg(tabs) + sum(deg(i) for i in out[at][1]) + deg(ins) <= D:
+                out[at][1].append(list(ins))
+                continue
+            if at is not None:
+                open_for.remove(at)
+            open_for.append(len(out))
+            out.append((list(tabs), [list(ins)]))
+        return out
 
     def permutation_chunk_len(self) -> int:
         return self.degree() - 2
@@ -458,7 +479,7 @@ class EvaluateHLayout:
 
 
 def evaluate_h_program(cs: ConstraintSystem, k: int, extended_k: int, delta: int, with_arguments: bool = True, per_coset: bool = False,
-                       divide: bool = True):
+                       divide: bool = True, lookup: str = "halo2"):
     """GraphEvaluator for evaluate_h of `cs`: the custom gates, then (with_arguments) the permutation argument over the
     equality columns, every lookup argument, and divide_by_vanishing_poly as the last multiplication.
     per_coset: the program for ONE coset of the n-th roots inside the extended domain (EvaluationDomain.coeff_to_coset;
@@ -466,12 +487,17 @@ def evaluate_h_program(cs: ConstraintSystem, k: int, extended_k: int, delta: int
     (compile with num_challenges = 1; the t_inv entry of the column table stays, unread).
     divide=False: the numerator only -- the division rides on the recombination (EvaluationDomain.combine_cosets(...,
     divide_by_vanishing=True)), so one launch can take several cosets as segments (CompiledGraph.evaluate(segments=...)).
+    lookup="logup": every argument of ``cs.logup_arguments()`` in the place of the lookups, its table entries (phi, m) from
+    ``lookup0`` on -- two per argument where a lookup has three.
     -> (GraphEvaluator, EvaluateHLayout)."""
+    if lookup not in ("halo2", "logup"):
+        raise ValueError(f"evaluate_h_program: lookup must be \"halo2\" or \"logup\", got {lookup!r}")
     nf = cs.num_fixed
     P, nsets, L = len(cs.equality), cs.permutation_sets(), len(cs.lookups)
+    groups = cs.logup_arguments() if lookup == "logup" else []
     lay = EvaluateHLayout(num_fixed_entries=nf, sigma0=nf, z0=nf + P, l0=nf + P + nsets, l_last=nf + P + nsets + 1,
                           l_active=nf + P + nsets + 2, x_coset=nf + P + nsets + 3, lookup0=nf + P + nsets + 4,
-                          t_inv=nf + P + nsets + 4 + 3 * L)
+                          t_inv=nf + P + nsets + 4 + (2 * len(groups) if lookup == "logup" else 3 * L))
     lay.num_fixed_entries = lay.t_inv + 1
     lay.short_columns = {lay.t_inv: extended_k - k}
     polys = list(cs.polynomials())
@@ -482,7 +508,11 @@ def evaluate_h_program(cs: ConstraintSystem, k: int, extended_k: int, delta: int
                                          [lambda r, i=i: Fixed(lay.z0 + i, r) for i in range(nsets)], Fixed(lay.l0), Fixed(lay.l_last),
                                          Fixed(lay.l_active), Fixed(lay.x_coset), cs.permutation_chunk_len(), delta,
                                          -(cs.blinding_factors + 1))
-        for j, (ins, tabs) in enumerate(cs.lookups):
+        for g, (tabs, ins_list) in enumerate(groups):
+            b = lay.lookup0 + 2 * g
+            polys += logup_expressions(ins_list, tabs, lambda r, b=b: Fixed(b, r), lambda r, b=b: Fixed(b + 1, r), Fixed(lay.l0),
+                                       Fixed(lay.l_last), Fixed(lay.l_active))
+        for j, (ins, tabs) in enumerate(cs.lookups if lookup == "halo2" else []):
             b = lay.lookup0 + 3 * j
             polys += lookup_expressions(ins, tabs, lambda r, b=b: Fixed(b, r), lambda r, b=b: Fixed(b + 1, r),
                                         lambda r, b=b: Fixed(b + 2, r), Fixed(lay.l0), Fixed(lay.l_last), Fixed(lay.l_active))

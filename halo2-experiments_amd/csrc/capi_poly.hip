@@ -472,6 +472,56 @@ int hm_lookup_permute_batch_bn256_fr_dev(const void* const* d_inputs, const void
   return lookup_permute_run(*ctx, d_inputs, d_tables, count, rows, d_permuted_inputs, d_permuted_tables, missing, (hipStream_t)stream);
 } HM_API_CATCH("hm_lookup_permute_batch_bn256_fr_dev")
 
+int hm_logup_multiplicities_bn256_fr_dev(const void* const* d_tables, const void* const* d_inputs, const uint32_t* input_counts, size_t count,
+                                         size_t rows, void* const* d_m, int* missing, void* stream) try {
+  const std::string who = "hm_logup_multiplicities_bn256_fr_dev: ";
+  if (count == 0) return HM_OK;
+  if (!d_tables || !d_inputs || !input_counts || !d_m) return hm_fail(HM_ERR_BAD_ARG, who + "null argument");
+  if (rows == 0 || rows >= ((size_t)1 << 31)) return hm_fail(HM_ERR_BAD_ARG, who + "need 1 <= rows < 2^31");
+  const size_t bytes = rows * 32;
+  size_t total = 0;
+  for (size_t a = 0; a < count; ++a) {
+    if (input_counts[a] == 0) return hm_fail(HM_ERR_BAD_ARG, who + "an argument without an input column");
+    if ((uint64_t)input_counts[a] * rows >= ((uint64_t)1 << 32)) return hm_fail(HM_ERR_BAD_ARG, who + "need c * rows < 2^32 (the counters are 32-bit)");
+    total += input_counts[a];
+  }
+  auto usable = [](const void* p) { return p && ((uintptr_t)p & 15) == 0; };
+  for (size_t a = 0; a < count; ++a)
+    if (!usable(d_tables[a]) || !usable(d_m[a])) return hm_fail(HM_ERR_BAD_ARG, who + "a null or misaligned column");
+  for (size_t j = 0; j < total; ++j)
+    if (!usable(d_inputs[j])) return hm_fail(HM_ERR_BAD_ARG, who + "a null or misaligned input column");
+  for (size_t a = 0; a < count; ++a) {
+    for (size_t b = 0; b < count; ++b)
+      if (ranges_overlap(d_m[a], bytes, d_tables[b], bytes) || (a != b && ranges_overlap(d_m[a], bytes, d_m[b], bytes)))
+        return hm_fail(HM_ERR_BAD_ARG, who + "an output overlaps another column of the call");
+    for (size_t j = 0; j < total; ++j)
+      if (ranges_overlap(d_m[a], bytes, d_inputs[j], bytes)) return hm_fail(HM_ERR_BAD_ARG, who + "an output overlaps an input column");
+  }
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return logup_multiplicities_run(d_tables, d_inputs, input_counts, count, rows, d_m, missing, (hipStream_t)stream);
+} HM_API_CATCH("hm_logup_multiplicities_bn256_fr_dev")
+
+int hm_fr_grand_sum_batch_dev(const void* const* d_terms, size_t n, void* const* d_out, size_t count, void* stream) try {
+  const std::string who = "hm_fr_grand_sum_batch_dev: ";
+  if (count == 0) return HM_OK;
+  if (!d_terms || !d_out) return hm_fail(HM_ERR_BAD_ARG, who + "null argument");
+  if (n == 0 || n >= ((size_t)1 << 32)) return hm_fail(HM_ERR_BAD_ARG, who + "need 1 <= n < 2^32");
+  if (count > 65535) return hm_fail(HM_ERR_BAD_ARG, who + "at most 65535 columns per call");
+  for (size_t j = 0; j < count; ++j)
+    if (!d_terms[j] || !d_out[j] || (((uintptr_t)d_terms[j] | (uintptr_t)d_out[j]) & 15)) return hm_fail(HM_ERR_BAD_ARG, who + "a null or misaligned column");
+  for (size_t j = 0; j < count; ++j) {
+    for (size_t i = 0; i < count; ++i)
+      if (i != j && (ranges_overlap(d_out[j], n * 32, d_terms[i], n * 32) || ranges_overlap(d_out[j], n * 32, d_out[i], n * 32)))
+        return hm_fail(HM_ERR_BAD_ARG, who + "an output overlaps another column of the call");
+    if (d_out[j] != d_terms[j] && ranges_overlap(d_out[j], n * 32, d_terms[j], n * 32))
+      return hm_fail(HM_ERR_BAD_ARG, who + "an output partially overlaps its terms");
+  }
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  return fr_grand_sum_batch_run(d_terms, n, d_out, count, (hipStream_t)stream);
+} HM_API_CATCH("hm_fr_grand_sum_batch_dev")
+
 int hm_fr_mul_periodic_dev(void* d_a, size_t n, const uint64_t* pattern, uint32_t period, void* stream) try {
   if ((n && !d_a) || !pattern) return hm_fail(HM_ERR_BAD_ARG, "hm_fr_mul_periodic_dev: null argument");
   DeviceCtx* ctx = ctx_for_current_device();

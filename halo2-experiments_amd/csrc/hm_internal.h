@@ -500,6 +500,17 @@ int sorted_witness_run(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n, siz
 // d_perm[0 .. n): the rows of the n canonical Montgomery elements of d_values in the order of their canonical integers, equal
 // elements by ascending row.  Asynchronous on `stream`, stream-ordered scratch of its own; 1 <= n <= 2^26 checked by the caller.
 int fr_argsort_run(const uint32_t* d_values, size_t n, uint64_t* d_perm, hipStream_t stream);
+// its launch chain on the caller's scratch: d_keys (n_pow2 x 8 words) and d_rows (n_pow2 words) leave as the sorted records, n_pow2
+// the next power of two of n; d_perm (n rows widened to 64 bits) may be null
+int fr_sort_records_run(const uint32_t* d_values, uint64_t n, uint64_t n_pow2, uint32_t* d_keys, uint32_t* d_rows, uint64_t* d_perm,
+                        hipStream_t stream);
+
+// logup.hip: the logUp lookup argument's multiplicity columns and running sums; the arguments were checked by
+// the caller (capi_poly.hip).  logup_multiplicities_run synchronises `stream` (it reads the key bits and the missing flags back);
+// fr_grand_sum_batch_run is asynchronous on it.
+int logup_multiplicities_run(const void* const* d_tables, const void* const* d_inputs, const uint32_t* input_counts, size_t count, uint64_t rows,
+                             void* const* d_m, int* missing, hipStream_t stream);
+int fr_grand_sum_batch_run(const void* const* d_terms, uint64_t n, void* const* d_out, size_t count, hipStream_t stream);
 
 // accumulator.hip: the SafeAccumulator circuit's witness: m running totals of acc_cols limbs of max_bits bits (max_bits * acc_cols <= 64),
 // row 0 the initial limbs, row r the value r, the top limb's inverse, the carries and the limbs after adding it; every row of every

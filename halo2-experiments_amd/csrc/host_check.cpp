@@ -32,6 +32,7 @@ namespace hm {
 #include "range.inc"      // the range-check witness's lane function (range.hip)
 #include "sorted.inc"     // the sorted-column witness's lane function and the argsort's record order (sorted.hip)
 #include "accumulator.inc" // the accumulator witness's row function (accumulator.hip)
+#include "logup.inc"      // the logUp argument's key, count and addition functions (logup.hip)
 #include "keygen.inc"     // the permutation assembly's key packing and link rule (keygen.hip)
 #include "shplonk.inc"    // the SHPLONK set quotient's plan, coefficients and row formula (polyops.hip)
 #include "pairing.inc"    // the pairing's tower, Miller lane and final exponentiation (pairing.hip)
@@ -1140,6 +1141,58 @@ int hc_accumulator_witness(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n,
   }
   return 0;
 }
+
+// The multiplicity column of ONE logUp argument with the rows one after the other (logup.inc: lu_key, lu_find, lu_count_ext): the table's
+// keys in (key, row) order by std::sort in the place of the device's network or its value bins, every input key searched in them, the
+// counter of the first row holding it raised.  inputs: c x rows x 8 words.  -> 1 when an input key is not in the table, -1 refused.
+int hc_logup_multiplicities(const uint32_t* table, const uint32_t* inputs, uint32_t c, uint64_t rows, uint32_t* m) {
+  if (rows == 0 || c == 0 || (uint64_t)c * rows >= ((uint64_t)1 << 32)) return -1;
+  std::vector<uint32_t> plain(rows * 8), keys(rows * 8), counters(rows, 0u);
+  std::vector<uint64_t> order(rows);
+  for (uint64_t i = 0; i < rows; ++i) {
+    uint32_t key[8];
+    (void)lu_key(table + i * 8, 1u, key);
+    std::memcpy(&plain[i * 8], key, 32);
+    order[i] = i;
+  }
+  std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+    const int cmp = mock_key_cmp(&plain[a * 8], &plain[b * 8]);
+    return cmp != 0 ? cmp < 0 : a < b;
+  });
+  for (uint64_t i = 0; i < rows; ++i) std::memcpy(&keys[i * 8], &plain[order[i] * 8], 32);
+  int missing = 0;
+  for (uint64_t j = 0; j < (uint64_t)c * rows; ++j) {
+    uint32_t key[8];
+    (void)lu_key(inputs + j * 8, 1u, key);
+    const uint64_t at = lu_find(keys.data(), rows, key);
+    if (at < rows) counters[order[at]] += 1;
+    else missing = 1;
+  }
+  LuFr to_mont;
+  const host::Fr4 r2 = {{0x1bb8e645ae216da7ULL, 0x53fe3ab1e35c59e3ULL, 0x8c49833d53bb8085ULL, 0x0216d0b17f4e44a5ULL}};   // 2^512 mod r as words = the element 2^256
+  host::fr_to_internal9(r2, to_mont.l);
+  for (uint64_t i = 0; i < rows; ++i) {
+    uint32_t w[8];
+    lu_count_ext(counters[i], to_mont, w);
+    ps_put_words(m + i * 8, w);
+  }
+  return missing;
+}
+
+// out[i] = the sum of terms[0 .. i) mod r, carried from row to row with the addition logup.hip's scan adds with
+int hc_grand_sum(const uint32_t* terms, uint64_t n, uint32_t* out) {
+  uint32_t run[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (uint64_t i = 0; i < n; ++i) {
+    uint32_t w[8];
+    ps_get_words(terms + i * 8, w);
+    ps_put_words(out + i * 8, run);
+    lu_add_mod(run, w);
+  }
+  return 0;
+}
+
+// logup.inc's LU_COUNT_BITS: table keys below 2^this are counted in value bins
+uint32_t hc_logup_count_bits() { return LU_COUNT_BITS; }
 
 // The plan of a tree update (poseidon.inc: merkle_update_key / _owned / _count, the arithmetic its kernels run) on m host indices,
 // with std::sort in the place of the device's sorting network.  counts: depth + 1 words.

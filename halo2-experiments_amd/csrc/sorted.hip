@@ -151,8 +151,9 @@ __global__ __launch_bounds__(SRT_THREADS) void srt_rows_kernel(const uint32_t* _
   if (i < n) perm[i] = rows[i];
 }
 
-static int fr_argsort_launch(const uint32_t* d_values, uint64_t n, uint64_t n_pow2, uint32_t* d_keys, uint32_t* d_rows, uint64_t* d_perm,
-                             hipStream_t stream) {
+// d_perm may be null: the caller reads the sorted records themselves (logup.hip: the general-key multiplicities)
+int fr_sort_records_run(const uint32_t* d_values, uint64_t n, uint64_t n_pow2, uint32_t* d_keys, uint32_t* d_rows, uint64_t* d_perm,
+                        hipStream_t stream) {
   const auto blocks = [](uint64_t lanes) { return dim3((unsigned)((lanes + SRT_THREADS - 1) / SRT_THREADS)); };
   hipLaunchKernelGGL(srt_records_kernel, blocks(n_pow2), dim3(SRT_THREADS), 0, stream, d_values, n, n_pow2, d_keys, d_rows);
   if (n_pow2 >= 2) {
@@ -165,7 +166,7 @@ static int fr_argsort_launch(const uint32_t* d_values, uint64_t n, uint64_t n_po
       hipLaunchKernelGGL(srt_tile_kernel, tiles, dim3(SRT_THREADS), 0, stream, d_keys, d_rows, n_pow2, k, k);
     }
   }
-  hipLaunchKernelGGL(srt_rows_kernel, blocks(n), dim3(SRT_THREADS), 0, stream, (const uint32_t*)d_rows, n, d_perm);
+  if (d_perm) hipLaunchKernelGGL(srt_rows_kernel, blocks(n), dim3(SRT_THREADS), 0, stream, (const uint32_t*)d_rows, n, d_perm);
   HM_HIP_CHECK(hipGetLastError());
   return HM_OK;
 }
@@ -178,7 +179,7 @@ int fr_argsort_run(const uint32_t* d_values, size_t n, uint64_t* d_perm, hipStre
   void* ws = nullptr;
   HM_HIP_CHECK(hipMallocAsync(&ws, (size_t)n_pow2 * 36, stream));
   uint32_t* keys = (uint32_t*)ws;
-  int rc = fr_argsort_launch(d_values, n, n_pow2, keys, keys + n_pow2 * 8, d_perm, stream);
+  int rc = fr_sort_records_run(d_values, n, n_pow2, keys, keys + n_pow2 * 8, d_perm, stream);
   const hipError_t fe = hipFreeAsync(ws, stream);
   if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("fr_argsort: hipFreeAsync: ") + hipGetErrorString(fe));
   return rc;

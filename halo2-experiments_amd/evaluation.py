@@ -600,6 +600,41 @@ def lookup_expressions(inputs: Sequence[Expression], tables: Sequence[Expression
             a_minus_s * (a - permuted_input(-1)) * l_active]
 
 
+def logup_expressions(inputs_list: Sequence[Sequence[Expression]], tables: Sequence[Expression], phi, m, l0: Expression, l_last: Expression,
+                      l_active: Expression) -> List[Expression]:
+    """One logUp argument (the logarithmic-derivative lookup): ``inputs_list`` holds the input expression lists
+    of the lookups that share it, ``tables`` their common table expressions (every list compressed by Horner in theta, as in
+    ``lookup_expressions``), phi(rot) its running sum and m(rot) its multiplicity column.  With t the compressed table and f_1 .. f_c
+    the compressed inputs:
+
+        l0 * phi,   l_last * phi,
+        l_active * [ (phi(wX) - phi(X)) (t + beta) prod_j (f_j + beta)  -  ( (t + beta) sum_j prod_{i != j} (f_i + beta)  -  m prod_j (f_j + beta) ) ]
+
+    of degree 2 + deg t + sum_j deg f_j."""
+    def compress(exprs):
+        acc = Constant(0)
+        for e in exprs:
+            acc = acc * THETA + e
+        return acc
+
+    t = compress(tables) + BETA
+    f = [compress(ins) + BETA for ins in inputs_list]
+    prod = f[0]
+    for fj in f[1:]:
+        prod = prod * fj
+    others = None                                        # sum_j prod_{i != j} f_i
+    for j in range(len(f)):
+        term = None
+        for i, fi in enumerate(f):
+            if i != j:
+                term = fi if term is None else term * fi
+        term = Constant(1) if term is None else term
+        others = term if others is None else others + term
+    return [phi(0) * l0,
+            phi(0) * l_last,
+            ((phi(1) - phi(0)) * t * prod - (t * others - m(0) * prod)) * l_active]
+
+
 def quotient_combine(domain, partials: Sequence, cosets: Sequence[int], pieces: int = None):
     """``hm_quotient_combine_bn256_fr_dev``: the partials of ALL the cosets used (one (n, 4) tensor per coset, in the order of
     ``cosets``, on this device) -> (pieces * n, 4) coefficients of h; the vanishing division rides on the matrix."""

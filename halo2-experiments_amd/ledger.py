@@ -56,7 +56,7 @@ from .pairing import g1_add, g1_mul, g1_on_curve
 from .prover import create_proofs
 from .solvency import _range_parameters
 from .synthesis import BLINDING_ROWS, range_witness, sorted_witness
-from .transcript import TranscriptError, check_encoding, check_multiopen, g1_decompress_int, g1_uncompressed_int
+from .transcript import TranscriptError, check_encoding, check_lookup, check_multiopen, g1_decompress_int, g1_uncompressed_int
 from .verifier import verify_proof
 
 R = FR_MODULUS
@@ -205,11 +205,11 @@ def ledger_order(ids):
 
 
 def prove_ledger(params, pk: ProvingKey, ids, balances, seed: int, check: bool = True, encoding: str = "halo2",
-                 multiopen: str = "shplonk", id_pk: ProvingKey = None) -> LedgerProof:
+                 multiopen: str = "shplonk", id_pk: ProvingKey = None, lookup: str = "halo2") -> LedgerProof:
     """``balances``: a (rows, 4) GPU tensor of canonical Montgomery words, one asset, or a (P, rows, 4) stack, exactly as
     ``solvency.prove_balances`` takes them; ``ids``: a (rows, 4) GPU tensor, one id per row.  The range witness and the range proofs
     go through ``range_witness`` and ``create_proofs`` (asset p with seed + p); ``check``, ``encoding`` and
-    ``multiopen`` as there.  An id whose words are not below r raises ValueError; nothing else is checked about ids unless
+    ``multiopen``, ``lookup`` as there (the id proof takes the same three).  An id whose words are not below r raises ValueError; nothing else is checked about ids unless
     ``id_pk`` is given: a proving key of ``circuits.sorted_column`` made with ``SortedColumnLayout(k, max_bits, acc_cols, rows)`` for
     these very ``rows``.  Then the ids, as passed, go through ``sorted_witness`` and ``create_proofs`` (seed + P), the proof's bytes and
     ``rows`` are stored, and ``check`` raises ValueError when a gap does not fit -- the ids are not in ascending order, not distinct,
@@ -219,6 +219,7 @@ def prove_ledger(params, pk: ProvingKey, ids, balances, seed: int, check: bool =
     who = "prove_ledger"
     check_encoding(encoding, who)
     check_multiopen(multiopen, who)
+    check_lookup(lookup, who)
     cs = pk.vk.cs
     max_bits, acc_cols = _range_parameters(cs, who)
     if cs.parameters.get("sorted"):
@@ -248,9 +249,9 @@ def prove_ledger(params, pk: ProvingKey, ids, balances, seed: int, check: bool =
         if bad:
             raise ValueError(f"{who}: {bad} gap(s) between neighbouring ids do not fit {id_bits * id_cols} bits: the ids are not in "
                              "ascending order, not distinct, or too far apart (ledger_order gives the permutation that sorts them)")
-    proofs = create_proofs(params, pk, advice, [empty] * P, seed, encoding=encoding, multiopen=multiopen)
+    proofs = create_proofs(params, pk, advice, [empty] * P, seed, encoding=encoding, multiopen=multiopen, lookup=lookup)
     if id_pk is not None:
-        id_proof = bytes(create_proofs(params, id_pk, id_advice, [empty], seed + P, encoding=encoding, multiopen=multiopen)[0])
+        id_proof = bytes(create_proofs(params, id_pk, id_advice, [empty], seed + P, encoding=encoding, multiopen=multiopen, lookup=lookup)[0])
     columns = torch.zeros((P + 1, n, 4), dtype=torch.int64, device=values.device)
     columns[0, :rows] = ids
     columns[1:] = advice[:, 0]                               # rows >= `rows` are zero
@@ -310,17 +311,18 @@ def verify_ledger_totals(params, public, id_total: int, totals, zero_opening, pa
 
 
 def verify_ledger(params, vk: VerifyingKey, proof: LedgerProof, pairing: str = "host", tail=None, encoding: str = "halo2",
-                  multiopen: str = "shplonk", id_vk: VerifyingKey = None) -> bool:
+                  multiopen: str = "shplonk", id_vk: VerifyingKey = None, lookup: str = "halo2") -> bool:
     """Per asset: the range proof verifies and its first commitment is ``proof.commitments[p]``; then the one opening of C_eta at 0
     yields (id_total + sum_p eta^(p+1) totals[p]) / n, eta = ``ledger_eta`` of the commitments and these very sums.  ``tail``: six (8,) openings -- rows n - 6 .. n - 1 of ``ledger_openings``
     -- checked with the id and every balance zero (see the module docstring).  ``pairing``: where the opening checks run;
-    ``encoding`` / ``multiopen``: the range proofs' wire format and multiopen scheme.  ``id_vk``: a verifying key of
+    ``encoding`` / ``multiopen`` / ``lookup``: the range proofs' (and the id proof's) wire format, multiopen scheme and lookup argument.  ``id_vk``: a verifying key of
     ``circuits.sorted_column`` (its parameters carry ``sorted=True``; anything else raises ValueError) made for the ledger's live rows;
     then False unless ``proof.id_proof`` verifies under it and its first commitment, decoded as the balance commitments are, is
     ``proof.id_commitment`` -- the ids of rows 0 .. rows - 1 are pairwise distinct (module docstring)."""
     who = "verify_ledger"
     check_encoding(encoding, who)
     check_multiopen(multiopen, who)
+    check_lookup(lookup, who)
     _range_parameters(vk.cs, who)
     if vk.cs.parameters.get("sorted"):
         raise ValueError(f"{who}: vk is a key of circuits.sorted_column; it belongs in id_vk")
@@ -335,7 +337,7 @@ def verify_ledger(params, vk: VerifyingKey, proof: LedgerProof, pairing: str = "
     n = 1 << k
     for p in range(P):
         rp = proof.range_proofs[p]
-        if not verify_proof(params, vk, [[]], rp, encoding=encoding, multiopen=multiopen):
+        if not verify_proof(params, vk, [[]], rp, encoding=encoding, multiopen=multiopen, lookup=lookup):
             return False
         try:
             first = g1_uncompressed_int(bytes(rp[:64])) if encoding == "evm" else g1_decompress_int(bytes(rp[:32]))
@@ -345,7 +347,7 @@ def verify_ledger(params, vk: VerifyingKey, proof: LedgerProof, pairing: str = "
             return False
     if id_vk is not None:
         ip = proof.id_proof
-        if not isinstance(ip, (bytes, bytearray)) or not verify_proof(params, id_vk, [[]], bytes(ip), encoding=encoding, multiopen=multiopen):
+        if not isinstance(ip, (bytes, bytearray)) or not verify_proof(params, id_vk, [[]], bytes(ip), encoding=encoding, multiopen=multiopen, lookup=lookup):
             return False
         try:
             first = g1_uncompressed_int(bytes(ip[:64])) if encoding == "evm" else g1_decompress_int(bytes(ip[:32]))

@@ -29,7 +29,7 @@ from .bn256 import FR_MODULUS
 from .keygen import FR_DELTA, VerifyingKey
 from .pairing import G1_GEN, g1_msm, g1_mul
 from .shplonk import g1_words_to_int
-from .transcript import (PERSONAL, PREFIX_CHALLENGE, PREFIX_POINT, PREFIX_SCALAR, TranscriptError, check_encoding, check_multiopen,
+from .transcript import (PERSONAL, PREFIX_CHALLENGE, PREFIX_POINT, PREFIX_SCALAR, TranscriptError, check_encoding, check_lookup, check_multiopen,
                          g1_decompress_int, g1_uncompressed_int, keccak256)
 from .verifier import _instance_columns, _vk_digest, evaluate_expression, proof_length
 
@@ -76,11 +76,20 @@ class ProofLayout:
     tail point and no slot has a tail bit.  ``groups`` = [(rotation, [member keys])] stands in place of ``sets``: the distinct
     rotations in order of first appearance in ``queries``, every group's members in list order -- what
     ``gwc.construct_point_groups`` finds on the real points, by the argument above.  The transcript has seven challenges
-    (``GWC_RECORD``): the schedule ends ... | evaluations | v | q points | u."""
+    (``GWC_RECORD``): the schedule ends ... | evaluations | v | q points | u.
 
-    def __init__(self, cs, k: int, encoding: str = "halo2", circuits: int = 1, multiopen: str = "shplonk"):
+    ``lookup="logup"``: the lookups stand as the G arguments of ``cs.logup_arguments()``.  Per circuit the
+    points ("logup_m", g) take the place of the lookup a' / s' pairs and ("logup_phi", g) that of the lookup z; the evaluations per
+    circuit and argument are phi at 0 and 1 and m at 0, the queries phi(0), m(0), phi(1); ``exprs`` holds
+    ``evaluation.logup_expressions`` over the table entries (phi, m) from ``lookup0`` on.  ``L`` is then 0 and ``G`` the number of
+    arguments; ``step5_points`` / ``step8_points`` are the per-circuit point counts between theta and beta and between gamma and the
+    random polynomial under either argument.  The integer twins below read such a layout; the terms plans and the batch verifier
+    do not (ValueError)."""
+
+    def __init__(self, cs, k: int, encoding: str = "halo2", circuits: int = 1, multiopen: str = "shplonk", lookup: str = "halo2"):
         self.encoding = check_encoding(encoding, "ProofLayout")
         self.multiopen = check_multiopen(multiopen, "ProofLayout")
+        self.lookup = check_lookup(lookup, "ProofLayout")
         m = int(circuits)
         if not 1 <= m <= MAX_CIRCUITS:
             raise ValueError(f"ProofLayout: need 1 <= circuits <= {MAX_CIRCUITS}, got {circuits!r}")
@@ -89,12 +98,14 @@ class ProofLayout:
         if m > 1 and multiopen == "gwc":
             raise ValueError("ProofLayout: multi-circuit proofs with the \"gwc\" multiopen are not laid out (circuits > 1)")
         self.circuits = m
-        self.lane = self if m == 1 else ProofLayout(cs, k, encoding)       # what ONE circuit of the proof looks like
+        self.lane = self if m == 1 else ProofLayout(cs, k, encoding, lookup=lookup)       # what ONE circuit of the proof looks like
         self.cs, self.k, self.n = cs, k, 1 << k
         n = self.n
         adv_q, fix_q, _ = cs.queries()
-        self.P, self.nsets, self.L = len(cs.equality), cs.permutation_sets(), len(cs.lookups)
-        P_, nsets, L = self.P, self.nsets, self.L
+        arguments = cs.logup_arguments() if lookup == "logup" else []
+        self.P, self.nsets, self.L, self.G = len(cs.equality), cs.permutation_sets(), 0 if lookup == "logup" else len(cs.lookups), len(arguments)
+        P_, nsets, L, G = self.P, self.nsets, self.L, self.G
+        self.step5_points, self.step8_points = 2 * L + G, nsets + L + G
         self.pieces = cs.degree() - 1
         self.last = -(cs.blinding_factors + 1)
         last = self.last
@@ -104,7 +115,9 @@ class ProofLayout:
         for c in M:
             for j in range(L):
                 pts += [per(("lookup_a", j), c), per(("lookup_s", j), c)]
-        pts += [per(("perm_z", i), c) for c in M for i in range(nsets)] + [per(("lookup_z", j), c) for c in M for j in range(L)] + [("random",)]
+            pts += [per(("logup_m", g), c) for g in range(G)]
+        pts += [per(("perm_z", i), c) for c in M for i in range(nsets)]
+        pts += [per((kd, j), c) for c in M for kd, count in (("lookup_z", L), ("logup_phi", G)) for j in range(count)] + [("random",)]
         pts += [("h_piece", i) for i in range(self.pieces)]
         self.points_before_evals = len(pts)
         evs = [(per(("advice", i), c), r % n) for c in M for i, r in adv_q] + [(("fixed", i), r % n) for i, r in fix_q] + [(("random",), 0)]
@@ -115,6 +128,8 @@ class ProofLayout:
         for c in M:
             for j in range(L):
                 evs += [(per((kd, j), c), r % n) for kd, r in (("lookup_z", 0), ("lookup_z", 1), ("lookup_a", 0), ("lookup_a", -1), ("lookup_s", 0))]
+            for g in range(G):
+                evs += [(per((kd, g), c), r) for kd, r in (("logup_phi", 0), ("logup_phi", 1), ("logup_m", 0))]
         # the queries in the order verifier._verify lists them; ("h",) stands for sum_i x^(n i) [h_i]
         q = []
         for c in M:
@@ -124,6 +139,8 @@ class ProofLayout:
             for j in range(L):
                 q += [(per(("lookup_z", j), c), 0), (per(("lookup_a", j), c), 0), (per(("lookup_s", j), c), 0),
                       (per(("lookup_a", j), c), (-1) % n), (per(("lookup_z", j), c), 1)]
+            for g in range(G):
+                q += [(per(("logup_phi", g), c), 0), (per(("logup_m", g), c), 0), (per(("logup_phi", g), c), 1 % n)]
         q += [(("fixed", i), r % n) for i, r in fix_q] + [(("sigma", j), 0) for j in range(P_)]
         q += [(("h",), 0), (("random",), 0)]
         self.queries = q
@@ -147,7 +164,7 @@ class ProofLayout:
             self.eval_index.setdefault(key, at)
         self.n_points, self.own_points, self.n_scalars = len(self.point_keys), len(self.point_keys) - (0 if gwc else 1), len(evs)
         self.slots = (2 if encoding == "evm" else 1) * self.n_points + self.n_scalars
-        if 32 * self.slots != proof_length(cs, m, encoding, multiopen, k):
+        if 32 * self.slots != proof_length(cs, m, encoding, multiopen, k, lookup):
             raise AssertionError("ProofLayout: the slots do not add up to proof_length")
         behind = range(self.points_before_evals, self.n_points)          # the multiopen's points, behind the evaluations
         if encoding == "evm":
@@ -198,7 +215,11 @@ class ProofLayout:
         exprs += ev.permutation_expressions([kind[kd](i) for kd, i in cs.equality], [F(self.sigma0 + j) for j in range(P_)],
                                             [lambda r, i=i: F(z0 + i, r) for i in range(nsets)], F(self.i_l0), F(self.i_last),
                                             F(self.i_active), F(self.i_x), cs.permutation_chunk_len(), FR_DELTA, last)
-        for j, (ins, tabs) in enumerate(cs.lookups):
+        for g, (tabs, ins_list) in enumerate(arguments):
+            b = self.lookup0 + 2 * g
+            exprs += ev.logup_expressions(ins_list, tabs, lambda r, b=b: F(b, r), lambda r, b=b: F(b + 1, r), F(self.i_l0), F(self.i_last),
+                                          F(self.i_active))
+        for j, (ins, tabs) in enumerate(cs.lookups if lookup == "halo2" else []):
             b = self.lookup0 + 3 * j
             exprs += ev.lookup_expressions(ins, tabs, lambda r, b=b: F(b, r), lambda r, b=b: F(b + 1, r), lambda r, b=b: F(b + 2, r),
                                            F(self.i_l0), F(self.i_last), F(self.i_active))
@@ -215,7 +236,7 @@ class ProofLayout:
         "evm" layout a point counts twice, and with ``circuits = m`` the per-circuit counts (advice, 2L, sets + L) are taken m times.
         A "gwc" layout ends ... | evaluations | v | the q witness points | u: seven challenges, nothing absorbed behind the last."""
         w, m = 2 if self.encoding == "evm" else 1, self.circuits
-        pairs = [(w * m * self.cs.num_advice, 1), (w * m * 2 * self.L, 2), (w * (m * (self.nsets + self.L) + 1), 1), (w * self.pieces, 1)]
+        pairs = [(w * m * self.cs.num_advice, 1), (w * m * self.step5_points, 2), (w * (m * self.step8_points + 1), 1), (w * self.pieces, 1)]
         pairs += [(self.n_scalars, 1), (w * len(self.groups), 1)] if self.multiopen == "gwc" else [(self.n_scalars, 2), (w, 1), (w, 0)]
         if sum(a for a, _ in pairs) != self.slots or sum(s for _, s in pairs) != len(self.record):
             raise AssertionError("ProofLayout: the transcript's schedule does not cover the proof's slots and its challenges")
@@ -335,10 +356,10 @@ def transcript_challenges(layout: ProofLayout, vk_digest: int, inst_cols, proof:
     ch = {}
     points(m * cs.num_advice)
     ch["theta"] = squeeze()
-    points(m * 2 * layout.L)
+    points(m * layout.step5_points)
     ch["beta"] = squeeze()
     ch["gamma"] = squeeze()
-    points(m * (layout.nsets + layout.L) + 1)
+    points(m * layout.step8_points + 1)
     ch["y"] = squeeze()
     points(layout.pieces)
     ch["x"] = squeeze()
@@ -402,6 +423,9 @@ def terms_from_challenges(layout: ProofLayout, omega: int, inst_cols, evals: Seq
                 return ev_at(("sigma", column - layout.sigma0), r)
             if column < layout.i_l0:
                 return ev_at(per(("perm_z", column - layout.z0), c), r)
+            if layout.lookup == "logup":
+                g, part = divmod(column - layout.lookup0, 2)
+                return ev_at(per((("logup_phi", "logup_m")[part], g), c), r)
             j, part = divmod(column - layout.lookup0, 3)
             return ev_at(per((("lookup_z", "lookup_a", "lookup_s")[part], j), c), r)
         return leaf
@@ -525,6 +549,8 @@ class TermsPlan:
     ``inst_rows[c]``: the rows given of instance column c (at most 64).  Needs no device."""
 
     def __init__(self, layout: ProofLayout, omega: int, inst_rows: Sequence[int]):
+        if layout.lookup != "halo2":
+            raise ValueError(f"{type(self).__name__}: the terms plans walk lookup=\"halo2\" layouts only (a logUp proof is verified by verify_proof)")
         cs, n = layout.cs, layout.n
         inst_rows = [int(r) for r in inst_rows]
         if len(inst_rows) != cs.num_instance:
@@ -694,6 +720,8 @@ class MultiTermsPlan:
     kernel runs.  ``inst_rows[c]``: the rows given of instance column c, the same for every circuit.  Needs no device."""
 
     def __init__(self, layout: ProofLayout, omega: int, inst_rows: Sequence[int]):
+        if layout.lookup != "halo2":
+            raise ValueError(f"{type(self).__name__}: the terms plans walk lookup=\"halo2\" layouts only (a logUp proof is verified by verify_proof)")
         m, one, cs = layout.circuits, layout.lane, layout.cs
         self.lane = TermsPlan(one, omega, inst_rows)
         per = layout.circuit_key

@@ -46,7 +46,17 @@ byte ``create_proof(params, pk, advice[b], instances[b], seeds[b])``, with its o
 The bytes of all three entries are pinned to recordings (tests/test_prover_bytes_gpu.py, tests/golden/prover_digests.json).
 
 ``multiopen="gwc"`` on the three entries ends the proof in the GWC multiopen instead (step 14: ``gwc.create_opening`` /
-``gwc.create_openings``, one witness point per distinct query point); everything before step 14 is the same code and the same bytes."""
+``gwc.create_openings``, one witness point per distinct query point); everything before step 14 is the same code and the same bytes.
+
+``lookup="logup"`` on the three entries proves the lookups with the logarithmic-derivative argument instead (the
+proof format of this mode is this project's own, after Haboeck's logUp paper, not the bytes of any fork).  The lookups are grouped
+into the arguments of ``cs.logup_arguments()``; the order above stands with two substitutions: at step 5, per circuit and per
+argument, the commitment of the multiplicity column m takes the place of the permuted pair (``logup_multiplicities``, nothing is
+sorted for small tables), and at step 8 the commitment of the running sum phi takes the place of the lookup z (the denominators
+f_j + beta and t + beta of all arguments and units from ONE helper program and ONE ``batch_invert``, the terms from one program per
+number of inputs, ``grand_sum_batch``).  gamma is still drawn.  The evaluations per circuit and argument are phi(x), phi(wx), m(x),
+the queries phi(x), m(x), phi(wx).  The blinding of m (rows from u on) comes from stream + 0x40 + 2 g, that of phi (rows from u + 1
+on) from + 0xC0 + g.  The keys are the same: the grouping never raises the degree.  Without lookups the bytes are those of the default argument."""
 from __future__ import annotations
 
 import hashlib
@@ -57,14 +67,14 @@ import numpy as np
 from . import circuits, evaluation as ev
 from ._marshal import _is_tensor
 from . import _lib
-from .arithmetic import (batch_invert, best_multiexp_batch, eval_polynomial, grand_product_batch, linear_combination_batch,
-                         permute_expression_pairs, random_fr)
+from .arithmetic import (batch_invert, best_multiexp_batch, eval_polynomial, grand_product_batch, grand_sum_batch, linear_combination_batch,
+                         logup_multiplicities, permute_expression_pairs, random_fr)
 from .domain import FR_MODULUS, FR_ZETA, fr_words
 from .keygen import FR_DELTA, ProvingKey, VerifyingKey
 from .poseidon import ints_to_words, words_to_ints
 from . import gwc, shplonk
 from .shplonk import g1_words_to_int
-from .transcript import WRITERS, check_encoding, check_multiopen
+from .transcript import WRITERS, check_encoding, check_lookup, check_multiopen
 
 R = FR_MODULUS
 
@@ -157,16 +167,18 @@ H_COLUMN_BUDGET = 2 << 30           # bytes of per-circuit extended columns in f
 
 
 def create_proof(params, pk: ProvingKey, advice, instance, seed: int, _trace: dict = None, encoding: str = "halo2",
-                 multiopen: str = "shplonk") -> bytes:
+                 multiopen: str = "shplonk", lookup: str = "halo2") -> bytes:
     """The proof bytes for the witness ``advice`` -- the (num_advice, n, 4) device tensor a witness writer returns for one circuit --
     and its ``instance`` values.  One circuit per proof: a list of several witnesses, or a 4-dimensional tensor holding more than
     one, raises ValueError (``create_proof_multi`` takes several).  ``_trace``: a dict that receives the committed polynomials and
     their commitments (tests).  ``encoding``: "halo2" -- Blake2b transcript, compressed points, little-endian scalars -- or "evm" --
     Keccak transcript, uncompressed big-endian points and scalars (``transcript`` states both); the protocol is the same.
     ``multiopen``: "shplonk", or "gwc" -- the proof then ends in one witness point per distinct query point (``gwc``) where SHPLONK
-    writes two points; everything before the multiopen is byte for byte the same."""
+    writes two points; everything before the multiopen is byte for byte the same.  ``lookup``: "halo2", the permutation-based lookup
+    argument, or "logup", the logarithmic-derivative one (the module docstring's last paragraph); the same keys prove under either."""
     check_encoding(encoding, "create_proof")
     check_multiopen(multiopen, "create_proof")
+    check_lookup(lookup, "create_proof")
     if isinstance(advice, (list, tuple)):
         if len(advice) != 1:
             raise ValueError("create_proof: one circuit per proof (create_proof_multi proves several)")
@@ -176,24 +188,26 @@ def create_proof(params, pk: ProvingKey, advice, instance, seed: int, _trace: di
             raise ValueError("create_proof: one circuit per proof (create_proof_multi proves several)")
         advice = advice[0]
     trace = None if _trace is None else {}
-    proof = _prove("create_proof", params, pk, [advice], [instance], [seed], 1, encoding, multiopen, trace)[0]
+    proof = _prove("create_proof", params, pk, [advice], [instance], [seed], 1, encoding, multiopen, trace, lookup)[0]
     if _trace is not None:                                 # one circuit: its keys without the circuit's number
         strip = lambda key: key[:2] if len(key) == 3 else key
         lag = trace["lagrange"]
         _trace.update(polys={strip(key): p for key, p in trace["polys"].items()}, commits={strip(key): p for key, p in trace["commits"].items()},
-                      lagrange={"advice": lag["advice"][0], "perm_z": lag["perm_z"][0], "lookup_z": lag["lookup_z"][0], "permuted": lag["permuted"][0]},
+                      lagrange={key: cols[0] for key, cols in lag.items()},
                       pieces=trace["pieces"], challenges=trace["challenges"])
     return proof
 
 
-def create_proof_multi(params, pk: ProvingKey, advice, instances, seed: int, _trace: dict = None, multiopen: str = "shplonk") -> bytes:
+def create_proof_multi(params, pk: ProvingKey, advice, instances, seed: int, _trace: dict = None, multiopen: str = "shplonk",
+                       lookup: str = "halo2") -> bytes:
     """ONE proof for m circuits of ``pk``'s constraint system (upstream ``create_proof(params, pk, &[circuit; m], &[instances; m])``):
     ``advice`` is the (m, num_advice, n, 4) GPU tensor a witness writer returns, or a list of m (num_advice, n, 4) tensors;
     ``instances`` holds m entries, each in the form ``create_proof`` takes.  1 <= m <= 64.  All circuits share theta, beta, gamma, y
     and x; with m = 1 the bytes are ``create_proof``'s.  ``_trace``: as in ``create_proof``, the keys of what belongs to one circuit
     carrying its number as a third element (("advice", column, circuit) ...) and ``lagrange`` holding one entry per circuit.
-    ``multiopen``: as in ``create_proof``."""
+    ``multiopen``, ``lookup``: as in ``create_proof``."""
     check_multiopen(multiopen, "create_proof_multi")
+    check_lookup(lookup, "create_proof_multi")
     if _is_tensor(advice):
         if advice.dim() != 4:
             raise ValueError("create_proof_multi: advice must be a (m, num_advice, n, 4) GPU tensor or a list of m (num_advice, n, 4) tensors")
@@ -205,18 +219,21 @@ def create_proof_multi(params, pk: ProvingKey, advice, instances, seed: int, _tr
         raise ValueError(f"create_proof_multi: between 1 and {MAX_CIRCUITS} circuits per proof")
     if _is_tensor(instances) or isinstance(instances, np.ndarray) or len(instances) != len(advice):
         raise ValueError(f"create_proof_multi: {len(advice)} circuit(s) need {len(advice)} instance entries")
-    return _prove("create_proof_multi", params, pk, advice, list(instances), [seed], len(advice), "halo2", multiopen, _trace)[0]
+    return _prove("create_proof_multi", params, pk, advice, list(instances), [seed], len(advice), "halo2", multiopen, _trace, lookup)[0]
 
 
-def create_proofs(params, pk: ProvingKey, advice, instances, seeds, encoding: str = "halo2", multiopen: str = "shplonk") -> list:
+def create_proofs(params, pk: ProvingKey, advice, instances, seeds, encoding: str = "halo2", multiopen: str = "shplonk",
+                  lookup: str = "halo2") -> list:
     """m independent proofs of ``pk``'s constraint system in one batched pass: ``create_proofs(...)[b] == create_proof(params, pk,
     advice[b], instances[b], seeds[b])``, byte for byte.  ``advice``: the (m, num_advice, n, 4) GPU tensor a witness writer returns, or
     a list of m (num_advice, n, 4) tensors; ``instances``: m entries, each in the form ``create_proof`` takes; ``seeds``: m integers,
     pairwise distinct mod 2^48 (two proofs with one seed would share their blinding: ValueError), or ONE integer s standing for
-    s, s + 1, ...  m >= 1, no upper limit.  ``encoding``, ``multiopen``: as in ``create_proof``."""
+    s, s + 1, ...  m >= 1, no upper limit.  ``encoding``, ``multiopen``, ``lookup``: as in ``create_proof`` (the keyword arguments of
+    both calls being the same)."""
     who = "create_proofs"
     check_encoding(encoding, who)
     check_multiopen(multiopen, who)
+    check_lookup(lookup, who)
     if _is_tensor(advice):
         if advice.dim() != 4:
             raise ValueError(f"{who}: advice must be a (m, num_advice, n, 4) GPU tensor or a list of m (num_advice, n, 4) tensors")
@@ -236,10 +253,10 @@ def create_proofs(params, pk: ProvingKey, advice, instances, seeds, encoding: st
         raise ValueError(f"{who}: {m} proof(s) need {m} seeds")
     if len({s & 0xFFFFFFFFFFFF for s in seeds}) != m:
         raise ValueError(f"{who}: the seeds must be pairwise distinct mod 2^48 (two proofs would share their blinding)")
-    return _prove(who, params, pk, advice, list(instances), seeds, 1, encoding, multiopen)
+    return _prove(who, params, pk, advice, list(instances), seeds, 1, encoding, multiopen, lookup=lookup)
 
 
-def _prove(who, params, pk, advice, instances, seeds, m, encoding, multiopen, _trace: dict = None) -> list:
+def _prove(who, params, pk, advice, instances, seeds, m, encoding, multiopen, _trace: dict = None, lookup: str = "halo2") -> list:
     """The protocol (module docstring, steps 1 - 14) for T = len(seeds) transcripts of m circuits each -> the T proofs.  ``advice`` and
     ``instances`` hold one entry per unit u = t m + c, circuit c of transcript t; what belongs to a circuit is indexed by its unit, what
     belongs to a transcript (challenges, random polynomial, h) by t.  ``_trace`` is filled for T = 1 only."""
@@ -261,6 +278,13 @@ def _prove(who, params, pk, advice, instances, seeds, m, encoding, multiopen, _t
     usable = n - blinding - 1
     omega, delta = dom.omega, FR_DELTA
     P, chunk, nsets, L = len(cs.equality), cs.permutation_chunk_len(), cs.permutation_sets(), len(cs.lookups)
+    logup = lookup == "logup"
+    groups = cs.logup_arguments() if logup else []        # "logup": the lookups are proved as these arguments, none on its own
+    G = len(groups)
+    if logup:
+        L = 0
+        if max([len(ins_list) for _, ins_list in groups] or [0]) * usable >= 1 << 32:
+            raise ValueError(f"{who}: a logUp argument needs inputs x usable rows below 2^32")
     counts = (cs.num_fixed, A, I)
     units, every = range(U), range(T)
     at = [(u // m, u % m) for u in units]                                    # unit -> (transcript, circuit inside it)
@@ -315,8 +339,9 @@ def _prove(who, params, pk, advice, instances, seeds, m, encoding, multiopen, _t
     try:
         # ---- the lookups: permuted columns (step 5; lookup j of unit u at index u L + j) -------------------------------------------------------
         thetas = [dict(theta=theta[t]) for t, _ in at]
-        lk_in = [progs.run_proofs(("in", j), [_compress(ins)], counts, table, n, thetas) for j, (ins, _) in enumerate(cs.lookups)]
-        lk_tab = [progs.run_proofs(("tab", j), [_compress(tabs)], counts, table, n, thetas) for j, (_, tabs) in enumerate(cs.lookups)]
+        lookups = [] if logup else cs.lookups
+        lk_in = [progs.run_proofs(("in", j), [_compress(ins)], counts, table, n, thetas) for j, (ins, _) in enumerate(lookups)]
+        lk_tab = [progs.run_proofs(("tab", j), [_compress(tabs)], counts, table, n, thetas) for j, (_, tabs) in enumerate(lookups)]
         order = [(u, j) for u in units for j in range(L)]
         try:
             permuted = permute_expression_pairs([lk_in[j][u] for u, j in order], [lk_tab[j][u] for u, j in order], usable,
@@ -330,6 +355,23 @@ def _prove(who, params, pk, advice, instances, seeds, m, encoding, multiopen, _t
             raise err from None
         commit_lagrange([item for (u, j), (a, s) in zip(order, permuted)
                          for item in ((at[u][0], ("lookup_a", j, at[u][1]), a), (at[u][0], ("lookup_s", j, at[u][1]), s))])
+        # ---- "logup": the multiplicity columns in their place (argument g of unit u at index u G + g) -----------------------------------
+        lu_tab = [progs.run_proofs(("lu_tab", g), [_compress(tabs)], counts, table, n, thetas) for g, (tabs, _) in enumerate(groups)]
+        lu_in = [[progs.run_proofs(("lu_in", g, j), [_compress(ins)], counts, table, n, thetas) for j, ins in enumerate(ins_list)]
+                 for g, (_, ins_list) in enumerate(groups)]
+        lu_order = [(u, g) for u in units for g in range(G)]
+        try:
+            lu_m = logup_multiplicities([lu_tab[g][u] for u, g in lu_order], [[f[u] for f in lu_in[g]] for u, g in lu_order], usable) if G else []
+        except _lib.Halo2Mi355xError as e:
+            if T == 1:
+                raise
+            where = [lu_order[i] for i in getattr(e, "missing", [])]          # several proofs: the same error, naming the proof (u = t)
+            err = _lib.Halo2Mi355xError(e.code, f"{e} -- " + ", ".join(f"proof {b} (argument {g})" for b, g in where))
+            err.missing, err.proofs = [g for _, g in where], sorted({b for b, _ in where})
+            raise err from None
+        for (u, g), col in zip(lu_order, lu_m):
+            col[usable:] = random_fr(n - usable, bases[u] + 0x40 + 2 * g, device)
+        commit_lagrange([(at[u][0], ("logup_m", g, at[u][1]), col) for (u, g), col in zip(lu_order, lu_m)])
         beta, gamma = squeeze(), squeeze()                                    # step 6
         bg = [dict(beta=beta[t], gamma=gamma[t]) for t, _ in at]
 
@@ -380,28 +422,57 @@ def _prove(who, params, pk, advice, instances, seeds, m, encoding, multiopen, _t
                 z[usable + 1:] = random_fr(n - usable - 1, bases[u] + 0xC0 + j, device)
                 lk_z[u].append(z)
         commit_lagrange([(t, ("lookup_z", j, c), z) for u, (t, c) in enumerate(at) for j, z in enumerate(lk_z[u])])
+        # ---- "logup": the running sums in their place.  The denominators t + beta, f_j + beta of all arguments and units are the units
+        # of ONE launch and ONE batch_invert; the terms sum_j 1 / (f_j + beta) - m / (t + beta) one launch per number of inputs --------------
+        lu_phi = [[] for _ in units]
+        if G:
+            dens, bg_d, slot = [], [], {}
+            for u, g in lu_order:
+                for key, col in [(("t", u, g), lu_tab[g][u])] + [(("f", u, g, j), f[u]) for j, f in enumerate(lu_in[g])]:
+                    slot[key] = len(dens)
+                    dens.append(col)
+                    bg_d.append(bg[u])
+            inv = progs.run_proofs("lu_den", [ev.Advice(0) + ev.BETA], (0, 1, 0), [torch.stack(dens)], n, bg_d)
+            batch_invert(inv.reshape(len(dens) * n, 4))
+            terms = {}
+            for c in sorted({len(f) for f in lu_in}):
+                mine = [(u, g) for u, g in lu_order if len(lu_in[g]) == c]
+                e = ev.Advice(0)
+                for j in range(1, c):
+                    e = e + ev.Advice(j)
+                cols = [torch.stack([inv[slot[("f", u, g, j)]] for u, g in mine]) for j in range(c)]
+                cols += [torch.stack([lu_m[u * G + g] for u, g in mine]), torch.stack([inv[slot[("t", u, g)]] for u, g in mine])]
+                out = progs.run_proofs(("lu_term", c), [e - ev.Advice(c) * ev.Advice(c + 1)], (0, c + 2, 0), cols, n, [{} for _ in mine])
+                terms.update({ug: out[i] for i, ug in enumerate(mine)})
+            for (u, g), phi in zip(lu_order, grand_sum_batch([terms[ug] for ug in lu_order])):
+                phi[usable + 1:] = random_fr(n - usable - 1, bases[u] + 0xC0 + g, device)
+                lu_phi[u].append(phi)
+        commit_lagrange([(t, ("logup_phi", g, c), phi) for u, (t, c) in enumerate(at) for g, phi in enumerate(lu_phi[u])])
     finally:
         progs.destroy()
     perm_of = [[permuted[u * L + j] for j in range(L)] for u in units]
+    lu_m_of = [[lu_m[u * G + g] for g in range(G)] for u in units]
+    NL = 2 * G if logup else 3 * L                                           # the lookup columns of its own that a circuit brings to h
 
     # ---- the vanishing argument's random polynomial (step 9: one per transcript), y (step 10), then h ------------------------------------------
     random_polys = [random_fr(n, bases[t * m] + 0x100, device) for t in every]
     commit_coeff([(t, ("random",), random_polys[t]) for t in every])
     y = squeeze()
 
-    g, tab = circuits.evaluate_h_program(cs, k, dom.extended_k, delta, divide=False)
-    V = nsets + 3 * L + A + I                                               # the columns of its own that a circuit brings to h
+    g, tab = circuits.evaluate_h_program(cs, k, dom.extended_k, delta, divide=False, lookup=lookup)
+    V = nsets + NL + A + I                                               # the columns of its own that a circuit brings to h
     lagrange = [col for u in units
-                for col in zs[u] + [t for j in range(L) for t in (lk_z[u][j], perm_of[u][j][0], perm_of[u][j][1])] + [adv[i, u] for i in range(A)]
+                for col in zs[u] + [t for j in range(L) for t in (lk_z[u][j], perm_of[u][j][0], perm_of[u][j][1])]
+                + [t for g_ in range(G) for t in (lu_phi[u][g_], lu_m_of[u][g_])] + [adv[i, u] for i in range(A)]
                 + [inst[i, u] for i in range(I)]]
     var_coeffs = dom.lagrange_to_coeff(torch.stack(lagrange)).reshape(U, V, n, 4)
-    z_polys, lk_polys = var_coeffs[:, :nsets], var_coeffs[:, nsets:nsets + 3 * L]
-    adv_polys = var_coeffs[:, nsets + 3 * L:nsets + 3 * L + A]
+    z_polys, lk_polys = var_coeffs[:, :nsets], var_coeffs[:, nsets:nsets + NL]
+    adv_polys = var_coeffs[:, nsets + NL:nsets + NL + A]
     sel = dom.lagrange_to_coeff(torch.stack([pk.l0, pk.l_last, pk.l_active]))
     x_poly = d([0, 1] + [0] * (n - 2)).reshape(1, n, 4)
     shared = dom.coeff_to_extended(torch.cat([pk.fixed_polys, pk.permutation_polys, sel, x_poly]))
     n_shared = shared.shape[0]
-    assert n_shared + nsets + 3 * L == tab.t_inv
+    assert n_shared + nsets + NL == tab.t_inv
     rot_scale = 1 << (dom.extended_k - k)
     en = dom.extended_len()
     unread = torch.zeros((max(rot_scale, 2), 4), dtype=torch.int64, device=device)[:rot_scale]     # the table's t_inv entry: divide=False never reads it
@@ -421,7 +492,7 @@ def _prove(who, params, pk, advice, instances, seeds, m, encoding, multiopen, _t
             share = lambda i: (shared[i], 0)
             # the program's table: fixed, sigma | z | l0, l_last, l_active, x | lookups | t_inv || advice | instance
             cols = ([share(i) for i in range(n_fs)] + [own(i) for i in range(nsets)] + [share(i) for i in range(n_fs, n_shared)]
-                    + [own(nsets + i) for i in range(3 * L)] + [(unread, 0)] + [own(nsets + 3 * L + i) for i in range(A + I)])
+                    + [own(nsets + i) for i in range(NL)] + [(unread, 0)] + [own(nsets + NL + i) for i in range(A + I)])
             if m == 1:
                 prog.evaluate_proofs(cols, h_ext[u0:u0 + nu], [dict(beta=beta[t], gamma=gamma[t], theta=theta[t], y=y[t]) for t in range(u0, u0 + nu)])
             else:
@@ -451,6 +522,8 @@ def _prove(who, params, pk, advice, instances, seeds, m, encoding, multiopen, _t
     for c in circuits_:
         for j in range(L):
             wanted += [(("lookup_z", j, c), 0), (("lookup_z", j, c), 1), (("lookup_a", j, c), 0), (("lookup_a", j, c), -1), (("lookup_s", j, c), 0)]
+        for g_ in range(G):
+            wanted += [(("logup_phi", g_, c), 0), (("logup_phi", g_, c), 1), (("logup_m", g_, c), 0)]
     wanted.append((("h",), 0))                                                # h(x): evaluated with the rest and not written
     queries = []                                                              # the multiopen's (step 14), upstream's order
     for c in circuits_:
@@ -459,6 +532,8 @@ def _prove(who, params, pk, advice, instances, seeds, m, encoding, multiopen, _t
         queries += [(("perm_z", i, c), last) for i in reversed(range(nsets - 1))]
         for j in range(L):
             queries += [(("lookup_z", j, c), 0), (("lookup_a", j, c), 0), (("lookup_s", j, c), 0), (("lookup_a", j, c), -1), (("lookup_z", j, c), 1)]
+        for g_ in range(G):
+            queries += [(("logup_phi", g_, c), 0), (("logup_m", g_, c), 0), (("logup_phi", g_, c), 1)]
     queries += [(("fixed", i), r) for i, r in fix_q] + [(("sigma", j), 0) for j in range(P)]
     queries += [(("h",), 0), (("random",), 0)]
     omega_to = {r: pow(omega, r, R) for r in {r for _, r in wanted}}
@@ -481,6 +556,8 @@ def _prove(who, params, pk, advice, instances, seeds, m, encoding, multiopen, _t
         for c in circuits_:
             for j in range(L):
                 polys[("lookup_z", j, c)], polys[("lookup_a", j, c)], polys[("lookup_s", j, c)] = lk_polys[t * m + c, 3 * j:3 * j + 3]
+            for g_ in range(G):
+                polys[("logup_phi", g_, c)], polys[("logup_m", g_, c)] = lk_polys[t * m + c, 2 * g_:2 * g_ + 2]
         polys[("h",)] = h_polys[t]
         polys_of.append(polys)
         for key, poly in polys.items():                                       # a slot per polynomial, the shared ones once
@@ -507,6 +584,7 @@ def _prove(who, params, pk, advice, instances, seeds, m, encoding, multiopen, _t
         scheme.create_openings(params, transcripts, queries_of, polys_of)
     if _trace is not None:
         _trace.update(polys=polys_of[0], commits=commits,
-                      lagrange={"advice": [adv[:, u] for u in units], "perm_z": zs, "lookup_z": lk_z, "permuted": perm_of},
+                      lagrange={"advice": [adv[:, u] for u in units], "perm_z": zs, "lookup_z": lk_z, "permuted": perm_of, "logup_m": lu_m_of,
+                                "logup_phi": lu_phi},
                       pieces=pieces[0], challenges=dict(theta=theta[0], beta=beta[0], gamma=gamma[0], y=y[0], x=x[0]))
     return [tr.finalize() for tr in transcripts]

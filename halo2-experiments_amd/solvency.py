@@ -30,7 +30,7 @@ from .openings import _point, _scalar_int, domain_omega, open_all, open_at, veri
 from .pairing import G1_GEN, g1_add, g1_mul, g1_neg, g1_on_curve
 from .prover import create_proofs
 from .synthesis import BLINDING_ROWS, range_witness
-from .transcript import TranscriptError, check_encoding, check_multiopen, g1_decompress_int, g1_uncompressed_int
+from .transcript import TranscriptError, check_encoding, check_lookup, check_multiopen, g1_decompress_int, g1_uncompressed_int
 from .verifier import verify_proof
 
 R = FR_MODULUS
@@ -62,16 +62,18 @@ def _range_parameters(cs, who: str) -> Tuple[int, int]:
 
 
 def prove_balances(params, pk: ProvingKey, balances, seed: int, check: bool = True, encoding: str = "halo2",
-                   multiopen: str = "shplonk") -> BalanceProof:
+                   multiopen: str = "shplonk", lookup: str = "halo2") -> BalanceProof:
     """``balances``: a (rows, 4) GPU tensor of canonical Montgomery words, one asset, or a (P, rows, 4) stack with one column per asset;
     rows <= 2^k - 6.  The witness of every asset from ``range_witness``, the range proofs from ``create_proofs``
     (asset p with seed + p), the totals n f(0) with their openings at 0 from ``open_at``.
     ``check``: a balance at or above 2^(max_bits * acc_cols) raises ValueError naming the asset and the count; without it the proof
-    is made all the same, and does not verify.  ``encoding`` / ``multiopen``: the wire format and the multiopen scheme of the range
+    is made all the same, and does not verify.  ``lookup``: the lookup argument of the range proofs, "halo2" or "logup" (``prover``); the advice commitments come first under
+    either, so C_p stands where it stood.  ``encoding`` / ``multiopen``: the wire format and the multiopen scheme of the range
     proofs, as ``create_proof`` names them."""
     who = "prove_balances"
     check_encoding(encoding, who)
     check_multiopen(multiopen, who)
+    check_lookup(lookup, who)
     cs = pk.vk.cs
     max_bits, acc_cols = _range_parameters(cs, who)
     if not (_is_tensor(balances) and balances.is_cuda and balances.dim() in (2, 3) and balances.shape[-1] == 4):
@@ -88,7 +90,7 @@ def prove_balances(params, pk: ProvingKey, balances, seed: int, check: bool = Tr
             if count:
                 raise ValueError(f"{who}: asset {p}: {count} balance(s) at or above 2^{max_bits * acc_cols}")
     empty = [[]]                                             # the instance column holds nothing
-    proofs = create_proofs(params, pk, advice, [empty] * P, seed, encoding=encoding, multiopen=multiopen)
+    proofs = create_proofs(params, pk, advice, [empty] * P, seed, encoding=encoding, multiopen=multiopen, lookup=lookup)
     columns = advice[:, 0].contiguous()                      # (P, n, 4): rows >= `rows` are zero
     coeffs = EvaluationDomain(2, k).lagrange_to_coeff(columns.clone())
     omega = domain_omega(k)
@@ -103,14 +105,16 @@ def prove_balances(params, pk: ProvingKey, balances, seed: int, check: bool = Tr
 
 
 def verify_balances(params, vk: VerifyingKey, proof: BalanceProof, pairing: str = "host", tail: bool = False,
-                    encoding: str = "halo2", multiopen: str = "shplonk") -> bool:
+                    encoding: str = "halo2", multiopen: str = "shplonk", lookup: str = "halo2") -> bool:
     """Per asset: the range proof verifies; its first 32-byte slot -- the commitment to advice column 0 -- decompresses to
     ``proof.commitments[p]``; the opening at 0 yields ``totals[p]`` / n.  ``tail``: also the 6 openings of ``tail_openings[p]``, as
     zeros on the rows 2^k - 6 .. 2^k - 1 (see the module docstring).  ``pairing``: where the opening checks run
     (``openings.verify_opening``).  ``encoding``: the range proofs' wire format; with "evm" the commitment is the first 64 bytes,
-    read as they stand: nothing is decompressed.  ``multiopen``: the range proofs' multiopen scheme."""
+    read as they stand: nothing is decompressed.  ``multiopen``: the range proofs' multiopen scheme; ``lookup``: their lookup
+    argument, as ``prove_balances`` was called."""
     check_encoding(encoding, "verify_balances")
     check_multiopen(multiopen, "verify_balances")
+    check_lookup(lookup, "verify_balances")
     _range_parameters(vk.cs, "verify_balances")
     P = len(proof.commitments)
     if P < 1 or not (len(proof.range_proofs) == len(proof.totals) == len(proof.total_openings) == P):
@@ -119,7 +123,7 @@ def verify_balances(params, vk: VerifyingKey, proof: BalanceProof, pairing: str 
     n, n_inv, omega = 1 << k, pow(1 << k, -1, R), domain_omega(k)
     for p in range(P):
         rp = proof.range_proofs[p]
-        if not verify_proof(params, vk, [[]], rp, encoding=encoding, multiopen=multiopen):
+        if not verify_proof(params, vk, [[]], rp, encoding=encoding, multiopen=multiopen, lookup=lookup):
             return False
         try:
             first = g1_uncompressed_int(bytes(rp[:64])) if encoding == "evm" else g1_decompress_int(bytes(rp[:32]))

@@ -61,6 +61,17 @@ def check_multiopen(multiopen, who: str) -> str:
     return multiopen
 
 
+LOOKUPS = ("halo2", "logup")
+
+
+def check_lookup(lookup, who: str) -> str:
+    """``lookup`` when it names one of ``LOOKUPS`` -- "halo2", the permutation-based lookup argument, or "logup", the
+    logarithmic-derivative one; ValueError otherwise, before any other work of ``who``"""
+    if lookup not in LOOKUPS:
+        raise ValueError(f"{who}: lookup must be one of {LOOKUPS}, got {lookup!r}")
+    return lookup
+
+
 class TranscriptError(ValueError):
     """A short read, bytes that are no curve point, or a scalar that is not below r."""
 

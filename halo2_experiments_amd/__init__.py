@@ -15,9 +15,9 @@ __path__.append(_os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath
 from . import _lib  # noqa: F401
 from .arithmetic import (bases_info, batch_invert, best_fft, best_multiexp, best_multiexp_batch, best_multiexp_submit,  # noqa: F401
                          best_multiexp_wait, eval_polynomial, g1_check, g1_check_host, g1_compress, g1_compress_host,
-                         g1_decompress, g1_decompress_host, g1_fft, g1_fft_host, g1_fixed_base_mul, g_to_lagrange, grand_product, grand_product_batch, kate_division,
+                         g1_decompress, g1_decompress_host, g1_fft, g1_fft_host, g1_fixed_base_mul, g_to_lagrange, grand_product, grand_product_batch, grand_sum_batch, kate_division,
                          kate_division_batch,
-                         linear_combination, linear_combination_batch, msm_stats, permute_expression_pair, permute_expression_pairs, random_fr, register_bases,
+                         linear_combination, linear_combination_batch, logup_multiplicities, msm_stats, permute_expression_pair, permute_expression_pairs, random_fr, register_bases,
                          release_bases)
 from .batch_verifier import BatchVerifier, verify_each, verify_proofs  # noqa: F401
 from .domain import EvaluationDomain  # noqa: F401
@@ -42,7 +42,7 @@ from .verifier import verify_proof, verify_proof_multi  # noqa: F401
 __all__ = ["eval_polynomial", "best_multiexp", "best_multiexp_batch", "best_multiexp_submit", "best_multiexp_wait", "best_fft",
            "register_bases", "release_bases", "bases_info", "g1_fixed_base_mul", "g1_fft", "g1_fft_host", "g1_compress", "g1_compress_host",
            "g1_decompress", "g1_decompress_host", "g1_check", "g1_check_host", "g_to_lagrange", "msm_stats", "kate_division", "kate_division_batch", "grand_product",
-           "grand_product_batch", "batch_invert",
+           "grand_product_batch", "grand_sum_batch", "logup_multiplicities", "batch_invert",
            "linear_combination", "random_fr", "permute_expression_pair", "permute_expression_pairs", "EvaluationDomain",
            "Spec", "poseidon_hash", "poseidon_hash_host", "update_plan", "MerkleSumTree", "MerkleTree", "MerkleSumTreeLayout", "merkle_sum_witness",
            "merkle_sum_witness_host", "permutation_columns", "MerkleTreeV3Layout", "PoseidonCircuitLayout", "merkle_witness",

@@ -405,6 +405,29 @@ int hm_lookup_permute_bn256_fr_dev(const void* d_input, const void* d_table, siz
 int hm_lookup_permute_batch_bn256_fr_dev(const void* const* d_inputs, const void* const* d_tables, size_t count, size_t rows,
                                          void* const* d_permuted_inputs, void* const* d_permuted_tables, int* missing, void* stream);
 
+/* The multiplicity columns of `count` logUp lookup arguments (the logarithmic-derivative lookup; this project's own proof format,
+ * DESIGN.md section 33) in one call.  Argument a has the table column d_tables[a] and input_counts[a] >= 1 input columns, its
+ * entries of d_inputs (a flat host array of sum(input_counts) device pointers, argument a's behind those of the arguments before
+ * it); of every column the first `rows` (= usable rows) entries are read, canonical Montgomery words, 16-byte aligned.
+ *     d_m[a][i] = the number of (input column, row) pairs of argument a whose value is d_tables[a][i], when i is the first row of
+ *                 the table holding that value, and 0 on the later rows that repeat it            for i < rows, Montgomery words.
+ * Nothing is sorted when every table value of the call is an integer below 2^20 (value bins); otherwise each table goes through
+ * the record sort of hm_fr_argsort_bn256_dev (then rows <= 2^26) and the inputs are searched in it.  The blinding rows beyond
+ * `rows` are the caller's.  missing (optional, count ints) is set to 1 for every argument one of whose inputs holds a value its
+ * table lacks, and the call then returns HM_ERR_NOT_FOUND (upstream: Error::ConstraintSystemFailure); the d_m of the other
+ * arguments are complete.  HM_ERR_BAD_ARG with nothing launched: a null or misaligned pointer, rows = 0 or >= 2^31, an
+ * input_counts[a] of 0 or with input_counts[a] * rows >= 2^32 (the counters are 32-bit), a d_m that overlaps any other column
+ * of the call.  Synchronises `stream`. */
+int hm_logup_multiplicities_bn256_fr_dev(const void* const* d_tables, const void* const* d_inputs, const uint32_t* input_counts, size_t count,
+                                         size_t rows, void* const* d_m, int* missing, void* stream);
+
+/* The running sums of the logUp arguments: d_out[c][i] = sum_{j < i} d_terms[c][j] mod r for i < n (exclusive: d_out[c][0] = 0),
+ * for `count` columns of n canonical Montgomery elements in one launch chain of three launches.  d_terms / d_out: host arrays of
+ * `count` device pointers, 16-byte aligned; d_out[c] may be d_terms[c] itself and must not overlap any other column of the call.
+ * HM_ERR_BAD_ARG with nothing launched: a null or misaligned pointer, n = 0 or >= 2^32, count > 65535, an overlap.  Scratch (the
+ * block totals) is allocated and freed in stream order.  Asynchronous on `stream`. */
+int hm_fr_grand_sum_batch_dev(const void* const* d_terms, size_t n, void* const* d_out, size_t count, void* stream);
+
 /* d_a[i] *= pattern[i mod period] for i < n, in place: EvaluationDomain::divide_by_vanishing_poly (upstream poly/domain.rs:
  * on the extended coset 1 / (X^n - 1) takes only 2^(extended_k - k) values, t_evaluations).  pattern: host, period x 4 u64;
  * period a power of two <= 64.  Asynchronous on `stream`. */

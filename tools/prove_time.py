@@ -21,6 +21,13 @@
     ``multiopen=`` each scheme, the routes alternating inside every repeat of one session, and in a second pass the multiopen alone
     (``create_opening`` / ``create_openings`` of ``shplonk`` and of ``gwc``, commitments included); and the polynomial side at the
     k = 18 shape: the q one-point quotients of GWC beside SHPLONK's set quotients, commitments left out of both.
+(f) ``--lookup halo2|logup|both`` (with ``--proofs m[,m...]``, default 1,16,64): instead, the two lookup arguments side by side
+     at depth 5 / k = 9 and depth 20 / k = 10: create_proof (m = 1) or create_proofs (m > 1) wall-clock with
+    ``lookup=`` each argument on the same witnesses and seeds, the arguments alternating inside every repeat of one session; the
+    commitments, evaluations and bytes of a proof under each, counted from the constraint system; and the two new kernels alone
+    (events around the call) at the k = 10 and k = 17 shapes -- eight byte columns into a 256-entry table --, the multiplicities of
+    the three arguments beside ``hm_lookup_permute_batch_bn256_fr_dev`` on the same eight columns, the running sums beside
+    ``grand_product_batch`` on as many columns: these are what they replace.
 Five repeats each: median and min .. max.  Prints one JSON object."""
 import argparse
 import json
@@ -398,6 +405,77 @@ def multiopen_k18_schemes(multiopens):
             "groups": [{"polynomials": len(members)} for _, members in groups], **{mo: spread(times[mo]) for mo in multiopens}}
 
 
+def lookup_counts(cs, k):
+    """commitments and evaluations of one proof under each lookup argument, and its bytes: counted, not measured"""
+    from halo2_experiments_amd.verifier import proof_length
+    adv_q, fix_q, _ = cs.queries()
+    nsets, L, G, P = cs.permutation_sets(), len(cs.lookups), len(cs.logup_arguments()), len(cs.equality)
+    base_c, base_e = cs.num_advice + nsets + 1 + (cs.degree() - 1), len(adv_q) + len(fix_q) + 1 + P + (3 * nsets - 1 if nsets else 0)
+    return {"lookups": L, "logup_arguments": [len(ins) for _, ins in cs.logup_arguments()], "sorts_removed": 2 * L,
+            "halo2": {"commitments": base_c + 3 * L, "evaluations": base_e + 5 * L, "proof_bytes": proof_length(cs, k=k)},
+            "logup": {"commitments": base_c + 2 * G, "evaluations": base_e + 3 * G, "proof_bytes": proof_length(cs, k=k, lookup="logup")}}
+
+
+def arguments(name, m, lookups):
+    """(f): m proofs of one shape under every lookup argument of ``lookups``, the arguments alternating inside every repeat"""
+    cs, lay, advice, instances = pmc.build_multi(name, m)
+    params = ParamsKZG.setup(lay.k, pc.SRS_S)
+    vk = h.keygen_vk(params, cs, lay)
+    pk = h.keygen_pk(params, vk, cs, lay, cosets=False)
+
+    def run(lk, rep):
+        if m == 1:
+            return [h.create_proof(params, pk, advice[0], instances[0], 1000 * rep, lookup=lk)]
+        return h.create_proofs(params, pk, advice, instances, [1000 * rep + b for b in range(m)], lookup=lk)
+    try:
+        sizes = {}
+        for lk in lookups:                                        # warm-up, and the first and last proof verify
+            made = run(lk, 1)
+            assert all(h.verify_proof(params, vk, instances[b], made[b], lookup=lk) for b in {0, m - 1})
+            sizes[lk] = len(made[0])
+        totals = {lk: [] for lk in lookups}
+        for rep in range(REPEATS):
+            for lk in lookups:
+                totals[lk].append(wall(lambda: run(lk, 2 + rep))[1])
+    finally:
+        params.release()
+    return {"k": lay.k, "proofs": m, "entry": "create_proof" if m == 1 else "create_proofs", "counts": lookup_counts(cs, lay.k),
+            **{lk: {"proof_bytes": sizes[lk], "total": spread(totals[lk]), "per_proof_ms": round(statistics.median(totals[lk]) / m, 3)}
+               for lk in lookups}}
+
+
+def events(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def logup_kernels(k):
+    """the two new kernels alone beside what they replace, on the sum tree's lookup shape: eight byte columns, one 256-entry table"""
+    n = 1 << k
+    u = n - 6
+    rng = np.random.default_rng(k)
+    col = lambda values: torch.from_numpy(ps.ints_to_words([int(v) for v in values]).view(np.int64)).cuda()
+    table = col(np.arange(n) % 256)
+    inputs = [col(rng.integers(0, 256, n)) for _ in range(8)]
+    groups = [inputs[0:3], inputs[3:6], inputs[6:8]]
+    factors = [h.random_fr(n, 70 + i) for i in range(8)]
+    routes = {"logup_multiplicities_3_arguments": lambda: h.logup_multiplicities([table] * 3, groups, u),
+              "lookup_permute_8_pairs": lambda: h.permute_expression_pairs(inputs, [table] * 8, u),
+              "grand_sum_3_columns": lambda: h.grand_sum_batch(factors[:3]),
+              "grand_product_8_columns": lambda: h.grand_product_batch(factors, fr_words(1))}
+    times = {name: [] for name in routes}
+    for fn in routes.values():
+        fn()
+    for _ in range(REPEATS):
+        for name, fn in routes.items():
+            times[name].append(events(fn))
+    return {"rows": u, **{name: spread(ms) for name, ms in times.items()}}
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--circuits", type=int, default=0, help="m: time create_proof_multi and the h step for m circuits (1 .. 64) instead")
@@ -405,8 +483,18 @@ if __name__ == "__main__":
                     "multiopen split out, for every listed m instead")
     ap.add_argument("--multiopen", choices=("shplonk", "gwc", "both"), default="",
                     help="time the multiopen schemes side by side (create_proof / create_proofs for every m of --proofs, default 1,16,64) instead")
+    ap.add_argument("--lookup", choices=("halo2", "logup", "both"), default="",
+                    help="time the lookup arguments side by side (create_proof / create_proofs for every m of --proofs, default 1,16,64) instead")
     args = ap.parse_args()
     torch.cuda.init()
+    if args.lookup:
+        lookups = ("halo2", "logup") if args.lookup == "both" else (args.lookup,)
+        out = {"tool": "tools/prove_time.py --lookup", "repeats": REPEATS, "lookups_measured": list(lookups)}
+        for name in ("merkle_sum_d5_k9", "merkle_sum_d20_k10"):
+            out[name] = {f"proofs_{m}": arguments(name, int(m), lookups) for m in (args.proofs or "1,16,64").split(",")}
+        out["kernels_alone"] = {f"k{k}": logup_kernels(k) for k in (10, 17)}
+        print(json.dumps(out))
+        sys.exit(0)
     if args.multiopen:
         multiopens = ("shplonk", "gwc") if args.multiopen == "both" else (args.multiopen,)
         out = {"tool": "tools/prove_time.py --multiopen", "repeats": REPEATS, "multiopens_measured": list(multiopens)}
