@@ -30,245 +30,194 @@ static void count_ntt_spans(DeviceCtx& ctx, const HostSpans& t) {
   ctx.calls.ntt_d2h_us += t.d2h_us;
 }
 
-int hm_ntt_bn256_fr_dev(void* d_a, const uint64_t omega[4], uint32_t log_n, void* stream) try {
-  if (!d_a || !omega) return hm_fail(HM_ERR_BAD_ARG, "hm_ntt_bn256_fr_dev: null argument");
+// ---- the NTT entries: each states its call (ntt_plan.inc: NttCall) and its pointers; ntt_entry does the rest ----
+static NttCall ntt_call(uint32_t log_n, uint64_t batch, uint32_t fused) {
+  NttCall c{};
+  c.log_n = log_n, c.batch = batch, c.fused = fused;
+  return c;
+}
+static NttPointers ntt_pointers(void* d_a, const uint64_t* omega, const uint64_t* scale = nullptr, const uint64_t* coset = nullptr,
+                                const uint64_t* post3 = nullptr) {
+  NttPointers p;
+  p.d_a = (uint32_t*)d_a, p.omega = omega, p.scale = scale, p.coset = coset, p.post3 = post3;
+  return p;
+}
+// what needs neither a device nor the context: null arguments, then ntt_check_call's refusals under the entry's name
+static int ntt_refuse(const char* who, bool null_argument, const NttCall& bound) {
+  if (null_argument) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (const char* why = ntt_check_call(bound)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": " + why);
+  return HM_OK;
+}
+// every device-pointer NTT entry: the refusals, the context and its lock, ntt_run, the call counter
+static int ntt_entry(const char* who, bool null_argument, const NttCall& call, const NttPointers& p, void* stream) {
+  if (const int refused = ntt_refuse(who, null_argument, ntt_bind(call, p))) return refused;
+  if (ntt_call_arrays(call) == 0) return HM_OK;
   DeviceCtx* ctx = ctx_for_current_device();
   if (!ctx) return HM_ERR_NO_DEVICE;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const int rc = ntt_run(*ctx, (uint32_t*)d_a, omega, log_n, 1, NttFused{}, (hipStream_t)stream);
-  if (rc == HM_OK) count_ntt(*ctx, log_n, 1);
+  const int rc = ntt_run(*ctx, call, p, (hipStream_t)stream);
+  if (rc == HM_OK) count_ntt(*ctx, call.log_n, (size_t)ntt_call_arrays(call));
   return rc;
+}
+// every host-pointer NTT entry, one array: the refusals, the context and its lock, the round trip through ctx.io with `launch` on
+// the staging buffer between the copies, the counters.  The caller's arrays are written by the download alone.
+static int ntt_host_entry(const char* who, bool null_argument, const NttCall& call, size_t staging_bytes, const HostIn& in, const HostOut& out,
+                          const std::function<int(DeviceCtx&, uint8_t*)>& launch) {
+  NttCall staged = call;                     // the arrays will lie in the staging buffer: aligned, the extending form's two apart
+  staged.in_place = call.log_z == 0;
+  if (const int refused = ntt_refuse(who, null_argument, staged)) return refused;
+  DeviceCtx* ctx = ctx_for_current_device();
+  if (!ctx) return HM_ERR_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HostSpans t;
+  const int rc = host_round_trip(who, *ctx, nullptr, staging_bytes, &in, 1, &out, 1, [&](uint8_t* d) { return launch(*ctx, d); }, &t);
+  if (rc != HM_OK) return rc;
+  count_ntt(*ctx, call.log_n, 1);
+  count_ntt_spans(*ctx, t);
+  return HM_OK;
+}
+
+int hm_ntt_bn256_fr_dev(void* d_a, const uint64_t omega[4], uint32_t log_n, void* stream) try {
+  return ntt_entry("hm_ntt_bn256_fr_dev", !d_a || !omega, ntt_call(log_n, 1, 0), ntt_pointers(d_a, omega), stream);
 } HM_API_CATCH("hm_ntt_bn256_fr_dev")
 
 int hm_ntt_batch_bn256_fr_dev(void* d_a, size_t batch, const uint64_t omega[4], uint32_t log_n, const uint64_t* scale,
                               const uint64_t* coset, void* stream) try {
-  if ((batch && !d_a) || !omega) return hm_fail(HM_ERR_BAD_ARG, "hm_ntt_batch_bn256_fr_dev: null argument");
-  if (batch > 65535) return hm_fail(HM_ERR_BAD_ARG, "hm_ntt_batch_bn256_fr_dev: batch > 65535");
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  NttFused f;
-  f.scale = scale;
-  f.coset = coset;
-  const int rc = ntt_run(*ctx, (uint32_t*)d_a, omega, log_n, (uint32_t)batch, f, (hipStream_t)stream);
-  if (rc == HM_OK) count_ntt(*ctx, log_n, batch);
-  return rc;
+  return ntt_entry("hm_ntt_batch_bn256_fr_dev", (batch && !d_a) || !omega,
+                   ntt_call(log_n, batch, (scale ? NTT_F_SCALE : 0u) | (coset ? NTT_F_COSET3 : 0u)), ntt_pointers(d_a, omega, scale, coset), stream);
 } HM_API_CATCH("hm_ntt_batch_bn256_fr_dev")
 
-// ctx->mu is held by the caller.  The zero part of the padded array is neither written nor read when the plan allows it.
-static int coeff_to_extended_locked(DeviceCtx* ctx, const void* d_coeffs, void* d_ext, size_t batch, const uint64_t extended_omega[4],
-                                    uint32_t log_n, uint32_t log_ext, const uint64_t* coset, void* stream) {
-  NttFused f;
-  f.coset = coset;
-  const uint32_t log_z = log_ext - log_n;
-  int passes = 0;
-  const int first_digit = ntt_plan_first_digit(log_ext, &passes);
-  int rc;
-  if (log_z > 0 && passes >= 2 && (int)log_z <= first_digit) {   // the zero part is never written or read
-    rc = ntt_run(*ctx, (uint32_t*)d_ext, extended_omega, log_ext, (uint32_t)batch, f, (hipStream_t)stream,
-                 (const uint32_t*)d_coeffs, log_z);
-  } else {
-    // small or un-extended domains: materialise the padded arrays, then the ordinary in-place transform
-    const size_t row_in = (size_t)32 << log_n, row_out = (size_t)32 << log_ext;
-    if (log_z) HM_HIP_CHECK(hipMemsetAsync(d_ext, 0, row_out * batch, (hipStream_t)stream));
-    HM_HIP_CHECK(hipMemcpy2DAsync(d_ext, row_out, d_coeffs, row_in, row_in, batch, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    rc = ntt_run(*ctx, (uint32_t*)d_ext, extended_omega, log_ext, (uint32_t)batch, f, (hipStream_t)stream);
+int hm_ifft_bn256_fr_dev(void* d_a, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4], void* stream) try {
+  return ntt_entry("hm_ifft_bn256_fr_dev", !d_a || !omega_inv || !divisor, ntt_call(log_n, 1, NTT_F_SCALE), ntt_pointers(d_a, omega_inv, divisor),
+                   stream);
+} HM_API_CATCH("hm_ifft_bn256_fr_dev")
+
+int hm_coset_ntt_bn256_fr_dev(void* d_a, const uint64_t omega[4], uint32_t log_n, const uint64_t coset[12], void* stream) try {
+  return ntt_entry("hm_coset_ntt_bn256_fr_dev", !d_a || !omega || !coset, ntt_call(log_n, 1, NTT_F_COSET3), ntt_pointers(d_a, omega, nullptr, coset),
+                   stream);
+} HM_API_CATCH("hm_coset_ntt_bn256_fr_dev")
+
+int hm_extended_to_coeff_bn256_fr_dev(void* d_a, size_t batch, const uint64_t extended_omega_inv[4], uint32_t log_ext,
+                                      const uint64_t divisor[4], const uint64_t coset_inv[12], void* stream) try {
+  return ntt_entry("hm_extended_to_coeff_bn256_fr_dev", (batch && !d_a) || !extended_omega_inv || !divisor || !coset_inv,
+                   ntt_call(log_ext, batch, NTT_F_SCALE | NTT_F_POST3), ntt_pointers(d_a, extended_omega_inv, divisor, nullptr, coset_inv), stream);
+} HM_API_CATCH("hm_extended_to_coeff_bn256_fr_dev")
+
+// EvaluationDomain::coeff_to_extended as a call: the extending form where the plan has it (the zero part of the padded arrays is then
+// neither written nor read), else -- small or un-extended domains -- the ordinary in-place transform of the materialised arrays.
+static NttCall extended_call(uint64_t batch, uint32_t log_n, uint32_t log_ext, bool coset) {
+  NttCall c = ntt_call(log_ext, batch, coset ? NTT_F_COSET3 : 0u);
+  c.log_z = log_ext - log_n;                                   // log_n > log_ext wraps: refused as longer than the transform
+  if (c.log_z <= log_ext && !ntt_extending_applies(log_ext, c.log_z)) c.log_z = 0;
+  return c;
+}
+// ctx.mu is held by the caller, who has checked `call` (extended_call's) against these pointers.
+static int coeff_to_extended_locked(DeviceCtx& ctx, const NttCall& call, const void* d_coeffs, void* d_ext, uint32_t log_n,
+                                    const uint64_t extended_omega[4], const uint64_t* coset, hipStream_t stream) {
+  NttPointers p = ntt_pointers(d_ext, extended_omega, nullptr, coset);
+  if (call.log_z) {
+    p.d_in = (const uint32_t*)d_coeffs;
+  } else if (d_coeffs != d_ext || log_n != call.log_n) {
+    const size_t row_in = (size_t)32 << log_n, row_out = (size_t)32 << call.log_n;
+    if (log_n != call.log_n) HM_HIP_CHECK(hipMemsetAsync(d_ext, 0, row_out * call.batch, stream));
+    HM_HIP_CHECK(hipMemcpy2DAsync(d_ext, row_out, d_coeffs, row_in, row_in, call.batch, hipMemcpyDeviceToDevice, stream));
   }
-  if (rc == HM_OK) count_ntt(*ctx, log_ext, batch);
-  return rc;
+  return ntt_run(ctx, call, p, stream);
 }
 
 int hm_coeff_to_extended_bn256_fr_dev(const void* d_coeffs, void* d_ext, size_t batch, const uint64_t extended_omega[4],
                                       uint32_t log_n, uint32_t log_ext, const uint64_t* coset, void* stream) try {
-  if ((batch && (!d_coeffs || !d_ext)) || !extended_omega)
-    return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_extended_bn256_fr_dev: null argument");
-  if (log_ext < log_n || log_ext > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_extended_bn256_fr_dev: need log_n <= log_ext <= 28");
-  if (batch > 65535) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_extended_bn256_fr_dev: batch > 65535");
+  const NttCall call = extended_call(batch, log_n, log_ext, coset != nullptr);
+  const char* who = "hm_coeff_to_extended_bn256_fr_dev";
+  NttPointers at = ntt_pointers(d_ext, extended_omega);
+  if (call.log_z) at.d_in = (const uint32_t*)d_coeffs;
+  if (const int refused = ntt_refuse(who, (batch && (!d_coeffs || !d_ext)) || !extended_omega, ntt_bind(call, at))) return refused;
   if (batch == 0) return HM_OK;
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  return coeff_to_extended_locked(ctx, d_coeffs, d_ext, batch, extended_omega, log_n, log_ext, coset, stream);
-} HM_API_CATCH("hm_coeff_to_extended_bn256_fr_dev")
-
-// Host-pointer forms of the two EvaluationDomain steps that cross PCIe in a drop-in prover: only what upstream's arrays really
-// hold travels -- the 2^log_n coefficients up (never the zero padding), the first `keep` coefficients down (never the part
-// extended_to_coeff truncates).
-int hm_coeff_to_extended_bn256_fr(const uint64_t* coeffs, uint64_t* ext, const uint64_t extended_omega[4], uint32_t log_n,
-                                  uint32_t log_ext, const uint64_t* coset) try {
-  if (!coeffs || !ext || !extended_omega) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_extended_bn256_fr: null argument");
-  if (log_ext < log_n || log_ext > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_extended_bn256_fr: need log_n <= log_ext <= 28");
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const size_t bytes_in = (size_t)32 << log_n, bytes_out = (size_t)32 << log_ext;
-  // `ext` is written by the download alone (it may be the very allocation `coeffs` lives in: the input has been uploaded whole).  It is
-  // normally a FRESH allocation (the new Vec of the result): its first-touch page faults are taken by xfer_prefault's threads, under
-  // the transform, or by the lanes' copying threads.
-  const HostIn in{coeffs, bytes_in, bytes_out};
-  const HostOut out{ext, bytes_out, 0, false};
-  HostSpans t;
-  const int rc = host_round_trip("hm_coeff_to_extended_bn256_fr", *ctx, nullptr, bytes_out + bytes_in, &in, 1, &out, 1, [&](uint8_t* d) {
-    const int lrc = coeff_to_extended_locked(ctx, d + bytes_out, d, 1, extended_omega, log_n, log_ext, coset, nullptr);
-    if (lrc == HM_OK && xfer_mode(ext, bytes_out) == 0) xfer_prefault(ext, bytes_out);   // direct copies only
-    return lrc;
-  }, &t);
-  if (rc == HM_OK) count_ntt_spans(*ctx, t);
-  return rc;
-} HM_API_CATCH("hm_coeff_to_extended_bn256_fr")
-
-int hm_extended_to_coeff_bn256_fr(uint64_t* a, size_t keep, const uint64_t extended_omega_inv[4], uint32_t log_ext,
-                                  const uint64_t divisor[4], const uint64_t coset_inv[12]) try {
-  if (!a || !extended_omega_inv || !divisor || !coset_inv) return hm_fail(HM_ERR_BAD_ARG, "hm_extended_to_coeff_bn256_fr: null argument");
-  if (log_ext > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_extended_to_coeff_bn256_fr: log_ext > 28");
-  if (keep > ((size_t)1 << log_ext)) return hm_fail(HM_ERR_BAD_ARG, "hm_extended_to_coeff_bn256_fr: keep exceeds 2^log_ext");
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const size_t bytes = (size_t)32 << log_ext;
-  NttFused f;
-  f.scale = divisor;
-  f.post3 = coset_inv;
-  const HostIn in{a, bytes, 0};
-  const HostOut out{a, keep * 32, 0, false};           // the part upstream truncates away is never downloaded
-  HostSpans t;
-  const int rc = host_round_trip("hm_extended_to_coeff_bn256_fr", *ctx, nullptr, bytes, &in, 1, &out, 1,
-                                 [&](uint8_t* d) { return ntt_run(*ctx, (uint32_t*)d, extended_omega_inv, log_ext, 1, f, nullptr); }, &t);
-  if (rc != HM_OK) return rc;
-  count_ntt(*ctx, log_ext, 1);
-  count_ntt_spans(*ctx, t);
-  return HM_OK;
-} HM_API_CATCH("hm_extended_to_coeff_bn256_fr")
-
-int hm_extended_to_coeff_bn256_fr_dev(void* d_a, size_t batch, const uint64_t extended_omega_inv[4], uint32_t log_ext,
-                                      const uint64_t divisor[4], const uint64_t coset_inv[12], void* stream) try {
-  if ((batch && !d_a) || !extended_omega_inv || !divisor || !coset_inv)
-    return hm_fail(HM_ERR_BAD_ARG, "hm_extended_to_coeff_bn256_fr_dev: null argument");
-  if (batch > 65535) return hm_fail(HM_ERR_BAD_ARG, "hm_extended_to_coeff_bn256_fr_dev: batch > 65535");
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  NttFused f;
-  f.scale = divisor;
-  f.post3 = coset_inv;
-  const int rc = ntt_run(*ctx, (uint32_t*)d_a, extended_omega_inv, log_ext, (uint32_t)batch, f, (hipStream_t)stream);
-  if (rc == HM_OK) count_ntt(*ctx, log_ext, batch);
-  return rc;
-} HM_API_CATCH("hm_extended_to_coeff_bn256_fr_dev")
-
-int hm_coeff_to_coset_bn256_fr_dev(const void* d_coeffs, void* d_out, size_t batch, const uint64_t omega[4], uint32_t log_n,
-                                   const uint64_t shift[4], int columns_internal, void* stream) try {
-  if ((batch && (!d_coeffs || !d_out)) || !omega || !shift) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_coset_bn256_fr_dev: null argument");
-  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_coset_bn256_fr_dev: log_n > 28");
-  if (batch > 65535) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_coset_bn256_fr_dev: batch > 65535");
-  if (batch == 0) return HM_OK;
-  if (d_coeffs != d_out) {
-    const size_t bytes = ((size_t)32 << log_n) * batch;
-    const char *a = (const char*)d_coeffs, *b = (const char*)d_out;
-    if (a < b + bytes && b < a + bytes)
-      return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_coset_bn256_fr_dev: output partially overlaps the coefficients");
+  // Without the extending form the padded arrays are materialised at d_ext first (the transform itself is in place there): d_coeffs is
+  // held to the same alignment, and an overlapping d_coeffs would not survive the padding (d_ext == d_coeffs with nothing to pad is
+  // the in-place transform).
+  if (!call.log_z && (d_coeffs != d_ext || log_n != log_ext)) {
+    if ((uintptr_t)d_coeffs & 15) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a data pointer is not 16-byte aligned");
+    if (ranges_overlap(d_coeffs, ((size_t)32 << log_n) * batch, d_ext, ((size_t)32 << log_ext) * batch))
+      return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": output partially overlaps the coefficients");
   }
   DeviceCtx* ctx = ctx_for_current_device();
   if (!ctx) return HM_ERR_NO_DEVICE;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const int rc = ntt_coset_run(*ctx, (const uint32_t*)d_coeffs, (uint32_t*)d_out, (uint32_t)batch, omega, log_n, shift, columns_internal != 0,
-                               (hipStream_t)stream);
-  if (rc == HM_OK) count_ntt(*ctx, log_n, batch);
+  const int rc = coeff_to_extended_locked(*ctx, call, d_coeffs, d_ext, log_n, extended_omega, coset, (hipStream_t)stream);
+  if (rc == HM_OK) count_ntt(*ctx, log_ext, batch);
   return rc;
+} HM_API_CATCH("hm_coeff_to_extended_bn256_fr_dev")
+
+int hm_coeff_to_coset_bn256_fr_dev(const void* d_coeffs, void* d_out, size_t batch, const uint64_t omega[4], uint32_t log_n,
+                                   const uint64_t shift[4], int columns_internal, void* stream) try {
+  NttPointers p = ntt_pointers(d_out, omega);
+  if (d_coeffs != d_out) p.d_in = (const uint32_t*)d_coeffs;
+  p.shifts = shift, p.internal = columns_internal != 0;
+  return ntt_entry("hm_coeff_to_coset_bn256_fr_dev", (batch && (!d_coeffs || !d_out)) || !omega || !shift, ntt_call(log_n, batch, NTT_F_IN_TABLE), p,
+                   stream);
 } HM_API_CATCH("hm_coeff_to_coset_bn256_fr_dev")
 
 int hm_coeff_to_cosets_bn256_fr_dev(const void* d_coeffs, void* d_out, size_t batch, const uint64_t omega[4], uint32_t log_n,
                                     const uint64_t* shifts, size_t count, int columns_internal, void* stream) try {
-  if ((batch && count && (!d_coeffs || !d_out)) || !omega || (count && !shifts))
-    return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_cosets_bn256_fr_dev: null argument");
-  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_cosets_bn256_fr_dev: log_n > 28");
-  if (count > 16) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_cosets_bn256_fr_dev: at most 16 cosets per call");
-  if (batch * (count ? count : 1) > 65535) return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_cosets_bn256_fr_dev: batch * count > 65535");
-  if (batch == 0 || count == 0) return HM_OK;
-  {
-    const size_t in_bytes = ((size_t)32 << log_n) * batch, out_bytes = in_bytes * count;
-    const char *a = (const char*)d_coeffs, *b = (const char*)d_out;
-    if (a < b + out_bytes && b < a + in_bytes)
-      return hm_fail(HM_ERR_BAD_ARG, "hm_coeff_to_cosets_bn256_fr_dev: the output overlaps the coefficients");
-  }
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const int rc = ntt_cosets_run(*ctx, (const uint32_t*)d_coeffs, (uint32_t*)d_out, (uint32_t)batch, omega, log_n, shifts, (uint32_t)count,
-                                columns_internal != 0, (hipStream_t)stream);
-  if (rc == HM_OK) count_ntt(*ctx, log_n, batch * count);
-  return rc;
+  NttCall call = ntt_call(log_n, batch, NTT_F_IN_TABLES);
+  call.fwd_cosets = count > NTT_COSETS_MAX ? NTT_COSETS_MAX + 1 : (uint32_t)count;
+  NttPointers p = ntt_pointers(d_out, omega);
+  p.d_in = (const uint32_t*)d_coeffs, p.shifts = shifts, p.internal = columns_internal != 0;
+  return ntt_entry("hm_coeff_to_cosets_bn256_fr_dev", (batch && count && (!d_coeffs || !d_out)) || !omega || (count && !shifts), call, p, stream);
 } HM_API_CATCH("hm_coeff_to_cosets_bn256_fr_dev")
-
-int hm_cosets_to_coeff_bn256_fr_dev(void* d_a, size_t count, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4],
-                                    const uint64_t* shift_invs, void* stream) try {
-  if ((count && (!d_a || !shift_invs)) || !omega_inv || !divisor) return hm_fail(HM_ERR_BAD_ARG, "hm_cosets_to_coeff_bn256_fr_dev: null argument");
-  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_cosets_to_coeff_bn256_fr_dev: log_n > 28");
-  if (count > 16) return hm_fail(HM_ERR_BAD_ARG, "hm_cosets_to_coeff_bn256_fr_dev: at most 16 cosets per call");
-  if (count == 0) return HM_OK;
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const int rc = ntt_cosets_inverse_run(*ctx, (uint32_t*)d_a, (uint32_t)count, omega_inv, log_n, divisor, shift_invs, (hipStream_t)stream);
-  if (rc == HM_OK) count_ntt(*ctx, log_n, count);
-  return rc;
-} HM_API_CATCH("hm_cosets_to_coeff_bn256_fr_dev")
 
 int hm_coset_to_coeff_bn256_fr_dev(void* d_a, size_t batch, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4],
                                    const uint64_t shift_inv[4], void* stream) try {
-  if ((batch && !d_a) || !omega_inv || !divisor || !shift_inv) return hm_fail(HM_ERR_BAD_ARG, "hm_coset_to_coeff_bn256_fr_dev: null argument");
-  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_coset_to_coeff_bn256_fr_dev: log_n > 28");
-  if (batch > 65535) return hm_fail(HM_ERR_BAD_ARG, "hm_coset_to_coeff_bn256_fr_dev: batch > 65535");
-  if (batch == 0) return HM_OK;
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const int rc = ntt_coset_inverse_run(*ctx, (uint32_t*)d_a, (uint32_t)batch, omega_inv, log_n, divisor, shift_inv, (hipStream_t)stream);
-  if (rc == HM_OK) count_ntt(*ctx, log_n, batch);
-  return rc;
+  NttPointers p = ntt_pointers(d_a, omega_inv, divisor);
+  p.shifts = shift_inv;
+  return ntt_entry("hm_coset_to_coeff_bn256_fr_dev", (batch && !d_a) || !omega_inv || !divisor || !shift_inv,
+                   ntt_call(log_n, batch, NTT_F_SCALE | NTT_F_OUT_TABLE), p, stream);
 } HM_API_CATCH("hm_coset_to_coeff_bn256_fr_dev")
 
+int hm_cosets_to_coeff_bn256_fr_dev(void* d_a, size_t count, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4],
+                                    const uint64_t* shift_invs, void* stream) try {
+  NttCall call = ntt_call(log_n, 1, NTT_F_SCALE | NTT_F_OUT_TABLES);
+  call.inv_cosets = count > NTT_COSETS_MAX ? NTT_COSETS_MAX + 1 : (uint32_t)count;
+  NttPointers p = ntt_pointers(d_a, omega_inv, divisor);
+  p.shifts = shift_invs;
+  return ntt_entry("hm_cosets_to_coeff_bn256_fr_dev", (count && (!d_a || !shift_invs)) || !omega_inv || !divisor, call, p, stream);
+} HM_API_CATCH("hm_cosets_to_coeff_bn256_fr_dev")
+
+// Host-pointer forms: only what upstream's arrays really hold crosses PCIe -- the 2^log_n coefficients up (never the zero padding),
+// the first `keep` coefficients down (never the part extended_to_coeff truncates).
 int hm_ntt_bn256_fr(uint64_t* a, const uint64_t omega[4], uint32_t log_n) try {
-  if (!a || !omega) return hm_fail(HM_ERR_BAD_ARG, "hm_ntt_bn256_fr: null argument");
-  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "hm_ntt_bn256_fr: log_n > 28");
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const size_t bytes = ((size_t)32) << log_n;
-  const HostIn in{a, bytes, 0};
-  const HostOut out{a, bytes, 0, false};
-  HostSpans t;
-  const int rc = host_round_trip("hm_ntt_bn256_fr", *ctx, nullptr, bytes, &in, 1, &out, 1,
-                                 [&](uint8_t* d) { return ntt_run(*ctx, (uint32_t*)d, omega, log_n, 1, NttFused{}, nullptr); }, &t);
-  if (rc != HM_OK) return rc;
-  count_ntt(*ctx, log_n, 1);
-  count_ntt_spans(*ctx, t);
-  return HM_OK;
+  const NttCall call = ntt_call(log_n, 1, 0);
+  const size_t bytes = (size_t)32 << (log_n & 31);
+  return ntt_host_entry("hm_ntt_bn256_fr", !a || !omega, call, bytes, HostIn{a, bytes, 0}, HostOut{a, bytes, 0, false},
+                        [&](DeviceCtx& ctx, uint8_t* d) { return ntt_run(ctx, call, ntt_pointers(d, omega), nullptr); });
 } HM_API_CATCH("hm_ntt_bn256_fr")
 
-int hm_ifft_bn256_fr_dev(void* d_a, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4], void* stream) try {
-  if (!d_a || !omega_inv || !divisor) return hm_fail(HM_ERR_BAD_ARG, "hm_ifft_bn256_fr_dev: null argument");
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  NttFused f;
-  f.scale = divisor;
-  const int rc = ntt_run(*ctx, (uint32_t*)d_a, omega_inv, log_n, 1, f, (hipStream_t)stream);
-  if (rc == HM_OK) count_ntt(*ctx, log_n, 1);
-  return rc;
-} HM_API_CATCH("hm_ifft_bn256_fr_dev")
+int hm_coeff_to_extended_bn256_fr(const uint64_t* coeffs, uint64_t* ext, const uint64_t extended_omega[4], uint32_t log_n,
+                                  uint32_t log_ext, const uint64_t* coset) try {
+  const NttCall call = extended_call(1, log_n, log_ext, coset != nullptr);
+  const size_t bytes_in = (size_t)32 << (log_n & 31), bytes_out = (size_t)32 << (log_ext & 31);
+  // staging: [the extended array][the coefficients].  `ext` is written by the download alone (it may be the very allocation `coeffs`
+  // lives in: the input has been uploaded whole).  It is normally a FRESH allocation (the new Vec of the result): its first-touch page
+  // faults are taken by xfer_prefault's threads, under the transform, or by the lanes' copying threads.
+  return ntt_host_entry("hm_coeff_to_extended_bn256_fr", !coeffs || !ext || !extended_omega, call, bytes_out + bytes_in,
+                        HostIn{coeffs, bytes_in, bytes_out}, HostOut{ext, bytes_out, 0, false}, [&](DeviceCtx& ctx, uint8_t* d) {
+                          const int rc = coeff_to_extended_locked(ctx, call, d + bytes_out, d, log_n, extended_omega, coset, nullptr);
+                          if (rc == HM_OK && xfer_mode(ext, bytes_out) == 0) xfer_prefault(ext, bytes_out);   // direct copies only
+                          return rc;
+                        });
+} HM_API_CATCH("hm_coeff_to_extended_bn256_fr")
 
-int hm_coset_ntt_bn256_fr_dev(void* d_a, const uint64_t omega[4], uint32_t log_n, const uint64_t coset[12], void* stream) try {
-  if (!d_a || !omega || !coset) return hm_fail(HM_ERR_BAD_ARG, "hm_coset_ntt_bn256_fr_dev: null argument");
-  DeviceCtx* ctx = ctx_for_current_device();
-  if (!ctx) return HM_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  NttFused f;
-  f.coset = coset;
-  const int rc = ntt_run(*ctx, (uint32_t*)d_a, omega, log_n, 1, f, (hipStream_t)stream);
-  if (rc == HM_OK) count_ntt(*ctx, log_n, 1);
-  return rc;
-} HM_API_CATCH("hm_coset_ntt_bn256_fr_dev")
+int hm_extended_to_coeff_bn256_fr(uint64_t* a, size_t keep, const uint64_t extended_omega_inv[4], uint32_t log_ext,
+                                  const uint64_t divisor[4], const uint64_t coset_inv[12]) try {
+  const char* who = "hm_extended_to_coeff_bn256_fr";
+  if (!a || !extended_omega_inv || !divisor || !coset_inv) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": null argument");
+  if (log_ext <= NTT_LOG_N_MAX && keep > ((size_t)1 << log_ext)) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": keep exceeds 2^log_ext");
+  const NttCall call = ntt_call(log_ext, 1, NTT_F_SCALE | NTT_F_POST3);
+  const size_t bytes = (size_t)32 << (log_ext & 31);
+  return ntt_host_entry(who, false, call, bytes, HostIn{a, bytes, 0}, HostOut{a, keep * 32, 0, false},      // the truncated part is never downloaded
+                        [&](DeviceCtx& ctx, uint8_t* d) { return ntt_run(ctx, call, ntt_pointers(d, extended_omega_inv, divisor, nullptr, coset_inv), nullptr); });
+} HM_API_CATCH("hm_extended_to_coeff_bn256_fr")
 
 int hm_eval_polynomial_bn256_fr_dev(const void* d_polys, size_t n, const uint32_t* poly_index, const uint64_t* points, size_t count,
                                     uint64_t* out, void* stream) try {
@@ -674,35 +623,43 @@ static int quotient_partials(const char* who, DeviceCtx& ctx, uint64_t program, 
     if (gp->handle == program) g = gp.get();
   if (!g) return hm_fail(HM_ERR_NOT_FOUND, std::string(who) + ": unknown program handle");
   if (n_columns != g->n_columns) return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": the program was built for another number of columns");
-  AuxSlot* slot = aux_acquire(ctx, st);
-  if (!slot) return HM_ERR_HIP;
-  // work: [the columns to transform, side by side: T x n] [those columns on the cosets: T x count x n]
   const size_t row = (size_t)n * 32;
   const size_t T = todo.size();
-  uint8_t* work = (uint8_t*)slot->work.ensure(row * (T + T * count) + 32);
-  if (!work) return hm_fail(HM_ERR_HIP, std::string(who) + ": workspace allocation failed");
-  uint8_t* contig = work;
-  uint8_t* on_cosets = contig + row * T;
-  int rc = HM_OK;
-  if (T) {
-    for (size_t j = 0; j < T; ++j)
-      HM_HIP_CHECK(hipMemcpyAsync(contig + row * j, d_coeff_columns[todo[j]], row, hipMemcpyDeviceToDevice, st));
-    rc = ntt_cosets_run(ctx, (const uint32_t*)contig, (uint32_t*)on_cosets, (uint32_t)T, omega, log_n, shifts, (uint32_t)count, true, st);
-    if (rc != HM_OK) return rc;
-    count_ntt(ctx, log_n, T * count);
-  }
   std::vector<const void*> cols(n_columns);
-  for (size_t i = 0; i < n_columns; ++i) cols[i] = d_on_cosets ? d_on_cosets[i] : nullptr;
-  for (size_t j = 0; j < T; ++j) cols[todo[j]] = on_cosets + row * count * j;
-  HM_HIP_CHECK(hipMemsetAsync(d_partials, 0, row * count, st));                // PreviousValue: upstream starts h at zero
-  rc = graph_run(ctx, *g, {GRAPH_SINGLE, n_columns, 1, n_dynamic, log_n, (uint32_t)count, HM_GRAPH_COLUMNS_INTERNAL, d_partials, 0, cols.data(), nullptr,
-                           dynamic_constants}, st);
-  if (rc != HM_OK) return rc;
-  count_vector(ctx, HM_STAT_GRAPH_EVALUATE, 1, (uint64_t)count << log_n);
-  rc = ntt_cosets_inverse_run(ctx, (uint32_t*)d_partials, (uint32_t)count, om_inv.l, log_n, n_inv.l, shift_inv[0].l, st);
-  if (rc != HM_OK) return rc;
-  count_ntt(ctx, log_n, count);
-  return aux_release(ctx, slot, st);
+  // The transforms and the numerator below take the stream's slot again (aux_scope nests on one stream) and use its other buffers.
+  return aux_scope(ctx, st, [&](AuxSlot& slot) -> int {
+    // work: [the columns to transform, side by side: T x n] [those columns on the cosets: T x count x n]
+    uint8_t* work = (uint8_t*)slot.work.ensure(row * (T + T * count) + 32);
+    if (!work) return hm_fail(HM_ERR_HIP, std::string(who) + ": workspace allocation failed");
+    uint8_t* contig = work;
+    uint8_t* on_cosets = contig + row * T;
+    int rc = HM_OK;
+    if (T) {
+      for (size_t j = 0; j < T; ++j)
+        HM_HIP_CHECK(hipMemcpyAsync(contig + row * j, d_coeff_columns[todo[j]], row, hipMemcpyDeviceToDevice, st));
+      NttCall onto = ntt_call(log_n, T, NTT_F_IN_TABLES);
+      onto.fwd_cosets = (uint32_t)count;
+      NttPointers p = ntt_pointers(on_cosets, omega);
+      p.d_in = (const uint32_t*)contig, p.shifts = shifts, p.internal = true;
+      rc = ntt_run(ctx, onto, p, st);
+      if (rc != HM_OK) return rc;
+      count_ntt(ctx, log_n, T * count);
+    }
+    for (size_t i = 0; i < n_columns; ++i) cols[i] = d_on_cosets ? d_on_cosets[i] : nullptr;
+    for (size_t j = 0; j < T; ++j) cols[todo[j]] = on_cosets + row * count * j;
+    HM_HIP_CHECK(hipMemsetAsync(d_partials, 0, row * count, st));                // PreviousValue: upstream starts h at zero
+    rc = graph_run(ctx, *g, {GRAPH_SINGLE, n_columns, 1, n_dynamic, log_n, (uint32_t)count, HM_GRAPH_COLUMNS_INTERNAL, d_partials, 0, cols.data(), nullptr,
+                             dynamic_constants}, st);
+    if (rc != HM_OK) return rc;
+    count_vector(ctx, HM_STAT_GRAPH_EVALUATE, 1, (uint64_t)count << log_n);
+    NttCall back = ntt_call(log_n, 1, NTT_F_SCALE | NTT_F_OUT_TABLES);
+    back.inv_cosets = (uint32_t)count;
+    NttPointers q = ntt_pointers(d_partials, om_inv.l, n_inv.l);
+    q.shifts = shift_inv[0].l;
+    rc = ntt_run(ctx, back, q, st);
+    if (rc == HM_OK) count_ntt(ctx, log_n, count);
+    return rc;
+  });
 }
 
 static int quotient_check_args(const char* who, const void* out, const uint64_t* omega, const uint64_t* shifts, size_t n_columns,
@@ -772,24 +729,24 @@ int hm_quotient_by_cosets_bn256_fr_dev(uint64_t program, const void* const* d_co
   hipStream_t st = (hipStream_t)stream;
   const uint64_t n = 1ull << log_n;
   const size_t row = (size_t)n * 32;
+  std::vector<const void*> parts(count);
   // the partials live in the stream's NTT scratch slot? no: that is the transforms' ping-pong buffer.  They get the tail of a
   // buffer of their own (AuxSlot::table is the scans' scratch: free between calls on this stream)
-  AuxSlot* slot = aux_acquire(*ctx, st);
-  if (!slot) return HM_ERR_HIP;
-  const size_t keep = (size_t)64 * 15 * 28 * 4;             // never shrink below the fixed-base table (see poly.hip)
-  uint8_t* parts_buf = (uint8_t*)slot->table.ensure(row * count > keep ? row * count : keep);
-  if (!parts_buf) return hm_fail(HM_ERR_HIP, std::string(who) + ": workspace allocation failed");
-  int rc = quotient_partials(who, *ctx, program, d_coeff_columns, d_on_cosets, n_columns, dynamic_constants, n_dynamic, log_n, omega, shifts, count,
-                             parts_buf, st);
-  if (rc != HM_OK) return rc;
-  std::vector<const void*> parts(count);
-  for (size_t c = 0; c < count; ++c) parts[c] = parts_buf + row * c;
-  for (size_t t = 0; t < pieces; ++t) {
-    rc = fr_linear_combination_run(parts.data(), rows[t].data(), count, n, (uint32_t*)((uint8_t*)d_h + row * t), st);
+  return aux_scope(*ctx, st, [&](AuxSlot& slot) -> int {
+    const size_t keep = (size_t)64 * 15 * 28 * 4;             // never shrink below the fixed-base table (see poly.hip)
+    uint8_t* parts_buf = (uint8_t*)slot.table.ensure(row * count > keep ? row * count : keep);
+    if (!parts_buf) return hm_fail(HM_ERR_HIP, std::string(who) + ": workspace allocation failed");
+    int rc = quotient_partials(who, *ctx, program, d_coeff_columns, d_on_cosets, n_columns, dynamic_constants, n_dynamic, log_n, omega, shifts, count,
+                               parts_buf, st);
     if (rc != HM_OK) return rc;
-  }
-  count_vector(*ctx, HM_STAT_LINEAR_COMBINATION, pieces, (uint64_t)pieces * count * n);
-  return aux_release(*ctx, slot, st);
+    for (size_t c = 0; c < count; ++c) parts[c] = parts_buf + row * c;
+    for (size_t t = 0; t < pieces; ++t) {
+      rc = fr_linear_combination_run(parts.data(), rows[t].data(), count, n, (uint32_t*)((uint8_t*)d_h + row * t), st);
+      if (rc != HM_OK) return rc;
+    }
+    count_vector(*ctx, HM_STAT_LINEAR_COMBINATION, pieces, (uint64_t)pieces * count * n);
+    return HM_OK;
+  });
 } HM_API_CATCH("hm_quotient_by_cosets_bn256_fr_dev")
 
 int hm_graph_destroy(uint64_t handle) try {

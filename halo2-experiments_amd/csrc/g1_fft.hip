@@ -416,7 +416,13 @@ int kzg_open_all_run(DeviceCtx& ctx, const uint32_t* d_table_xy, const uint32_t*
     hipLaunchKernelGGL(kzg_open_arrange_coeffs_kernel, all_m256, dim3(256), 0, stream, d_coeffs + p * n * 8, y, log_n);
     if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: arrangement kernel launch failed");
     mark(1, last);
-    if (rc == HM_OK) rc = ntt_run(ctx, y, omega2.l, log_m, 1, NttFused{}, stream);
+    if (rc == HM_OK) {
+      NttCall call{};
+      call.log_n = log_m, call.batch = 1;
+      NttPointers ptrs;
+      ptrs.d_a = y, ptrs.omega = omega2.l;
+      rc = ntt_run(ctx, call, ptrs, stream);
+    }
     mark(2, last);
     if (rc == HM_OK) {
       hipLaunchKernelGGL(kzg_open_load_mul_kernel, all_m64, dim3(ACC_THREADS), 0, stream, d_table_xy, (const uint32_t*)y, work2, log_m, k32s);

@@ -85,20 +85,38 @@ inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t 
   return pa < pb + b_bytes && pb < pa + a_bytes;
 }
 
-struct NttTables {
-  uint32_t log_n = 0;
-  uint64_t omega[4] = {0, 0, 0, 0};
-  uint32_t log_lb = 0;
-  // The table kernels run on the stream of the call that first needed them.  `ready` is recorded behind
-  // them; until it has completed (`published`), a caller on another stream waits for it on the device.
+#include "ntt_plan.inc"   // what an NTT call asks for, its check and its launch plan (ntt.hip)
+
+// How a cached device table built on one stream reaches the callers on the others (ctx.mu held).  The build kernels run on the stream
+// of the call that first needed the table; record() puts `ready` behind them.  Until that event has been seen complete (`published`),
+// wait_or_publish() makes a caller on another stream wait for it on the device.
+struct Publication {
   hipStream_t build_stream = nullptr;
   hipEvent_t ready = nullptr;
   bool published = false;
-  uint32_t* d_lo = nullptr;
-  uint32_t* d_hi = nullptr;
-  uint32_t* d_mid = nullptr;   // direct twiddles of the middle pass of a 3-pass plan
-  uint32_t* d_stage[16] = {};
-  size_t bytes = 0;            // device memory of all of the above
+  hipError_t wait_or_publish(hipStream_t stream) {      // the hit path
+    if (published) return hipSuccess;
+    if (hipEventQuery(ready) == hipSuccess) published = true;
+    else if (stream != build_stream) return hipStreamWaitEvent(stream, ready, 0);
+    return hipSuccess;
+  }
+  bool record(hipStream_t stream) {                     // the build path; false: the caller drops the table (the failure path)
+    if (hipEventCreateWithFlags(&ready, hipEventDisableTiming) != hipSuccess) return false;
+    build_stream = stream;
+    return hipEventRecord(ready, stream) == hipSuccess;
+  }
+  void release() {
+    if (ready) (void)hipEventDestroy(ready);
+    ready = nullptr;
+  }
+};
+
+struct NttTables {
+  uint32_t log_n = 0;
+  uint64_t omega[4] = {0, 0, 0, 0};
+  Publication pub;
+  uint32_t* d[NTT_TABLES_MAX] = {};   // the tables of ntt_table_set(log_n), in its order
+  size_t bytes = 0;            // device memory of all of the above: the set's byte total
   uint64_t last_use = 0;       // ctx.ntt_table_clock at the last ntt_get_tables hit (LRU)
 };
 
@@ -110,9 +128,7 @@ struct CosetTable {
   uint32_t log_n = 0;
   uint32_t internal = 0;
   uint32_t* d = nullptr;
-  hipStream_t build_stream = nullptr;
-  hipEvent_t ready = nullptr;
-  bool published = false;
+  Publication pub;
   uint64_t last_use = 0;
 };
 
@@ -308,7 +324,8 @@ AuxSlot* aux_acquire(DeviceCtx& ctx, hipStream_t stream);
 int aux_release(DeviceCtx& ctx, AuxSlot* slot, hipStream_t stream);
 // A call's use of its slot with ONE way out: body(slot) enqueues on `stream`, and the slot's event is recorded behind whatever it
 // enqueued, whatever it returns or throws -- a slot left `used` without a recorded event would hand aux_acquire's hipEventQuery /
-// hipStreamWaitEvent a null or stale event.  Refuse arguments before this, not inside.
+// hipStreamWaitEvent a null or stale event.  Refuse arguments before this, not inside.  Nesting on ONE stream is intended: a body's
+// own calls on `stream` (the quotient's transforms and numerator) are handed the same slot and use other buffers of it.
 template <class Body>
 int aux_scope(DeviceCtx& ctx, hipStream_t stream, Body&& body) {
   AuxSlot* slot = aux_acquire(ctx, stream);
@@ -378,40 +395,33 @@ int multi_msm_batch(uint64_t handle, size_t offset, const void* const* scalars, 
 int multi_local_part(uint64_t handle, int device, uint64_t* local_handle);   // replicated sets: the copy on `device`
 
 // ntt.hip
-// scale / coset: optional external (4 x u64 Montgomery) constants on the HOST; they travel to the kernels
-// by value, so no call shares a constants buffer with another.  post3: optional {1, c, c^2}-style pattern
-// multiplied into element i of every output array by i % 3 (EvaluationDomain::extended_to_coeff).
-struct NttFused {
-  const uint64_t* scale = nullptr;   // 4 words: multiply every output (ifft divisor)
-  const uint64_t* coset = nullptr;   // 12 words: input element i *= coset[i % 3] (coeff_to_extended)
-  const uint64_t* post3 = nullptr;   // 12 words: output element i *= post3[i % 3] (extended_to_coeff)
-  const uint32_t* d_in_scale = nullptr;   // DEVICE table, n x 8 words: input element i *= table[i] / 32 (the transform on a coset)
-  // several cosets of the SAME inputs in one launch chain: n_in_scales tables; output array (b, c) = number b * n_in_scales + c
-  const uint32_t* d_in_scales[16] = {};
-  uint32_t n_in_scales = 0;
+// What the driver reads beside the NttCall (ntt_plan.inc).  d_a: the arrays of the call, transformed in place, or written from d_in
+// when that is set.  The constants are external (4 x u64 Montgomery) words on the HOST, each present iff its NTT_F_* bit is set; they
+// travel to the kernels by value, so no call shares a constants buffer with another.  shifts: 4 words per coset table of the call (one,
+// fwd_cosets or inv_cosets); the tables themselves are the driver's (a bounded cache); internal: the forward tables hold 1024 * shift^i,
+// so that the outputs are in the evaluator's internal column form (HM_GRAPH_COLUMNS_INTERNAL).
+struct NttPointers {
+  uint32_t* d_a = nullptr;
+  const uint32_t* d_in = nullptr;
+  const uint64_t* omega = nullptr;    // 4 words
+  const uint64_t* scale = nullptr;    // 4 words
+  const uint64_t* coset = nullptr;    // 12 words
+  const uint64_t* post3 = nullptr;    // 12 words
+  const uint64_t* shifts = nullptr;
+  bool internal = false;
 };
-constexpr uint32_t HM_NTT_COSETS_MAX = 16;
-int ntt_run(DeviceCtx& ctx, uint32_t* d_a, const uint64_t omega_ext[4], uint32_t log_n, uint32_t batch,
-            const NttFused& fused, hipStream_t stream, const uint32_t* d_in = nullptr, uint32_t log_z = 0);
-int ntt_plan_first_digit(uint32_t log_n, int* passes);
+inline NttCall ntt_bind(NttCall c, const NttPointers& p) {       // the call's addresses are the pointers': never stated twice
+  c.out = (uintptr_t)p.d_a, c.in = (uintptr_t)p.d_in, c.in_place = p.d_in == nullptr;
+  return c;
+}
+// The one driver: the check (HM_ERR_BAD_ARG with the reason), the plan, the twiddle and coset tables, the fused constants, then the
+// launches -- inside aux_scope when the plan has scratch.
+int ntt_run(DeviceCtx& ctx, const NttCall& call, const NttPointers& p, hipStream_t stream);
 int fr_scale_run(uint32_t* d_a, const uint64_t c_ext[4], uint64_t n, hipStream_t stream);
 int fr_mul_pattern3_run(uint32_t* d_a, const uint64_t c3_ext[12], uint64_t n, hipStream_t stream);
 void ntt_tables_release(NttTables& t);
 void coset_tables_release(DeviceCtx& ctx);
 size_t ntt_caches_give_back(DeviceCtx& ctx);   // every cached twiddle / coset table freed (after a device synchronise); bytes given back
-// out_b[t] = sum_i in_b[i] (shift omega^t)^i for `batch` back-to-back n-element arrays, out of place (d_out may be d_in);
-// internal: outputs multiplied by 32 (HM_GRAPH_COLUMNS_INTERNAL)
-int ntt_coset_run(DeviceCtx& ctx, const uint32_t* d_in, uint32_t* d_out, uint32_t batch, const uint64_t omega_ext[4], uint32_t log_n,
-                  const uint64_t shift_ext[4], bool internal, hipStream_t stream);
-// the same for `count` cosets at once: d_out holds batch * count arrays, array b * count + c = input b on coset shifts[c]
-int ntt_cosets_run(DeviceCtx& ctx, const uint32_t* d_in, uint32_t* d_out, uint32_t batch, const uint64_t omega_ext[4], uint32_t log_n,
-                   const uint64_t* shifts_ext, uint32_t count, bool internal, hipStream_t stream);
-// in place, `count` arrays: a_c <- divisor * inverse transform of a_c, then a_c[i] *= shift_invs[c]^i
-int ntt_cosets_inverse_run(DeviceCtx& ctx, uint32_t* d_a, uint32_t count, const uint64_t omega_inv_ext[4], uint32_t log_n,
-                           const uint64_t divisor_ext[4], const uint64_t* shift_invs_ext, hipStream_t stream);
-// in place: a_b <- divisor * inverse transform of a_b, then a_b[i] *= shift_inv^i
-int ntt_coset_inverse_run(DeviceCtx& ctx, uint32_t* d_a, uint32_t batch, const uint64_t omega_inv_ext[4], uint32_t log_n,
-                          const uint64_t divisor_ext[4], const uint64_t shift_inv_ext[4], hipStream_t stream);
 
 // graph.hip
 int graph_create(DeviceCtx& ctx, const uint32_t* calcs5, size_t n_calc, const uint64_t* constants_ext, size_t n_const_static,

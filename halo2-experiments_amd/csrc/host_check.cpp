@@ -39,6 +39,7 @@ namespace hm {
 #include "transcript.inc" // Blake2b-512, its streaming absorber and the transcript lane of a proof (verify.hip)
 #include "keccak.inc"     // Keccak-256, the EVM encoding's read and the transcript lane of such a proof (verify.hip)
 #include "msm_plan.inc"   // the MSM's window choice, launch plans and workspace layouts (msm.hip, msm_small.hip)
+#include "ntt_plan.inc"   // the NTT's call check, launch plan and twiddle table set (ntt.hip)
 }
 
 using namespace hm;
@@ -1006,6 +1007,34 @@ void hc_graph_launch_plan(uint32_t kind, uint64_t size, uint64_t units, uint32_t
   const GraphPlan p = graph_launch_plan((GraphCallKind)kind, size, units, n_slots, (size_t)n_dyn, max_blocks);
   out[0] = p.size, out[1] = p.lanes, out[2] = p.blocks, out[3] = p.T, out[4] = p.log_c, out[5] = p.rows_per, out[6] = p.scratch_bytes, out[7] = p.args_bytes;
 }
+// The NTT's call check and launch plan (ntt_plan.inc), as ntt_run asks them.  call = { log_n, batch, fwd_cosets, inv_cosets, log_z,
+// fused, in_place, in, out } (addresses as integers).  hc_ntt_check_call -> the reason, or null for an admitted call.  hc_ntt_plan, for
+// an admitted call: head = { passes, digits[3], arrays, lds_bytes, scratch_bytes, tail, tail_grid[2], table bytes, tables };
+// passes = 3 rows of { the 13 words of NttPassHead, variant, grid[3], src, dst, stage, tw_lo, tw_hi (table indices, -1: none) };
+// tables = NTT_TABLES_MAX rows of { role, count, shift }.
+static NttCall hc_ntt_call(const uint64_t* call) {
+  return NttCall{(uint32_t)call[0], call[1], (uint32_t)call[2], (uint32_t)call[3], (uint32_t)call[4], (uint32_t)call[5], call[6] != 0,
+                 (uintptr_t)call[7], (uintptr_t)call[8]};
+}
+const char* hc_ntt_check_call(const uint64_t* call) { return ntt_check_call(hc_ntt_call(call)); }
+void hc_ntt_plan(const uint64_t* call, uint64_t* head, int64_t* passes, uint64_t* tables) {
+  const NttPlan p = ntt_plan(hc_ntt_call(call));
+  const uint64_t h[12] = {p.passes, p.digits[0], p.digits[1], p.digits[2], p.arrays, p.lds_bytes, p.scratch_bytes, p.tail, p.tail_grid[0], p.tail_grid[1],
+                          p.tables.bytes, p.tables.n_tables};
+  std::memcpy(head, h, sizeof h);
+  for (int i = 0; i < 3; ++i) {
+    const NttPassPlan& q = p.pass[i];
+    const NttPassHead& s = q.head;
+    const int64_t row[22] = {s.log_n, s.s, s.log_stride, s.log_c, s.last, s.log_r0, s.log_rows, s.log_lb, s.fin_mode, s.has_coset, s.direct_tw, s.log_z,
+                             s.has_table, q.variant, q.grid[0], q.grid[1], q.grid[2], q.src, q.dst, q.stage, q.tw_lo, q.tw_hi};
+    std::memcpy(passes + 22 * i, row, sizeof row);
+  }
+  for (int i = 0; i < NTT_TABLES_MAX; ++i) {
+    const uint64_t row[3] = {p.tables.table[i].role, p.tables.table[i].count, p.tables.table[i].shift};
+    std::memcpy(tables + 3 * i, row, sizeof row);
+  }
+}
+int hc_ntt_extending_applies(uint32_t log_n, uint32_t log_z) { return ntt_extending_applies(log_n, log_z) ? 1 : 0; }
 int hc_shplonk_row_bounds(const uint64_t* a_ext, double* report) {
   typedef Fe<FrParams> F;
   uint32_t wa[8];

@@ -23,11 +23,6 @@
 
 namespace hm {
 
-#ifndef HM_NTT_THREADS
-#define HM_NTT_THREADS 512
-#endif
-constexpr int NTT_THREADS = HM_NTT_THREADS;
-
 // ---------------------------------------------------------------------------------------------
 // twiddle tables
 // ---------------------------------------------------------------------------------------------
@@ -97,28 +92,13 @@ struct NttCosetTables {          // pointer table by value (indexed by blockIdx.
   uint32_t count;
 };
 
-struct NttPassParams {
-  uint32_t log_n;        // transform size
-  uint32_t s;            // log2 of this pass's digit R
-  uint32_t log_stride;   // log2 of the element stride between consecutive digit values (non-last passes)
-  uint32_t log_c;        // log2 of the columns (non-last) / rows (last) per tile
-  uint32_t last;         // 1: stride-1 pass with the digit-reversing, canonicalising store
-  uint32_t log_r0;       // last pass of a 3-pass plan: log2 R0 (else 0)
-  uint32_t log_rows;     // last pass: log2 of the number of rows = log_n - s
-  uint32_t log_lb;       // split point of the two-level inter-pass twiddle table
-  uint32_t fin_mode;     // last pass: 0 = canonicalise only, 1 = multiply by fin[0], 2 = output i *= fin[i % 3]
-  uint32_t has_coset;    // first pass: multiply a[i] by coset[i % 3] on load
-  uint32_t direct_tw;    // non-last pass: tw_lo holds omega_m^e for every e < m (no forming product)
-  uint32_t log_z;        // first pass of an extending transform: the input holds only the first n >> log_z
-                         // coefficients (the rest are zero by definition); 0 = ordinary transform
-  uint32_t has_table;    // first pass: multiply a[i] by in_scale[i] on load (the transform on a coset shift * <omega>: in_scale
-                         // holds 32 * shift^i as external words, so that the product of two external words is the external
-                         // word of a[i] * shift^i -- the radix is 2^261)
+struct NttPassParams : NttPassHead {      // the plan's scalar head (ntt_plan.inc: log_n ... has_table), then the
   // fused constants, 9-limb internal form, BY VALUE (a call never shares a constants buffer with another
   // call on another stream): coset[3] for the first pass, fin[3] for the last
   uint32_t coset[27];
   uint32_t fin[27];
 };
+static_assert(sizeof(NttPassHead) == 13 * 4 && sizeof(NttPassParams) == (13 + 54) * 4, "the kernels' parameter block: 13 scalars, 54 constant words");
 
 // everything a register round needs
 struct NttTileCtx {
@@ -486,140 +466,61 @@ __global__ void fr_mul_pattern3_kernel(uint32_t* a, FrWords3 c3_ext, uint64_t n)
 }
 
 // ---------------------------------------------------------------------------------------------
-// host side: plan + launch
+// host side: the tables a plan (ntt_plan.inc) names, the stream slots, and the one driver
 // ---------------------------------------------------------------------------------------------
-#ifndef HM_NTT_LOG_TILE
-#define HM_NTT_LOG_TILE 11
-#endif
-constexpr int LOG_TILE = HM_NTT_LOG_TILE;
-// Sub-problems up to 2^NTT_DIRECT_LOG get a DIRECT inter-pass twiddle table (omega_m^e for every e < m, 36 B per entry: 75 MB at
-// 2^21) instead of two sqrt-sized tables and a forming product per element.  Round 5 (tools/ntt_plans.py, profiles/r05_ntt_plans.txt):
-// 16 -> 21 together with the smaller digit first takes 6.7 % of the VALU instructions out of a 2^21 transform (3 328 -> 3 105 lane
-// instructions per element) and 4-6 % off every prover-sized shape (48 x 2^21: 11.5 -> 10.9 ms); the table is read as 36-byte
-// gathers and the transform stays VALU-bound.  Beyond 2^21 the plan has three passes and only its middle pass can be direct.
-#ifndef HM_NTT_DIRECT_LOG
-#define HM_NTT_DIRECT_LOG 21
-#endif
-constexpr uint32_t NTT_DIRECT_LOG = HM_NTT_DIRECT_LOG;
-// (a direct first-pass table is used by two-pass plans only: in a three-pass plan the first pass's m is n but the middle pass's is not)
-
-static int plan_digits(uint32_t log_n, uint32_t digits[3]) {
-  if (log_n <= (uint32_t)LOG_TILE) {
-    digits[0] = log_n;
-    return 1;
-  }
-  // two passes while both digits fit a tile (measured: 2-8 % faster than three up to 2^21, slower at 2^22
-  // where the 11-bit digit leaves single-column, 32-byte accesses)
-#ifndef HM_NTT_2PASS_MAX
-#define HM_NTT_2PASS_MAX 21
-#endif
-  const int passes = log_n <= HM_NTT_2PASS_MAX ? 2 : 3;
-  uint32_t rem = log_n;
-  for (int p = 0; p < passes; ++p) {
-    digits[p] = (rem + (passes - p) - 1) / (passes - p);
-    rem -= digits[p];
-  }
-#ifndef HM_NTT_LARGE_FIRST      // two passes: the smaller digit first (2^21 = 2^10 x 2^11): the first pass then has two columns per tile
-  if (passes == 2 && digits[0] > digits[1]) { const uint32_t t = digits[0]; digits[0] = digits[1]; digits[1] = t; }
-#endif
-  return passes;
-}
-
-int ntt_plan_first_digit(uint32_t log_n, int* passes) {
-  uint32_t digits[3] = {0, 0, 0};
-  *passes = plan_digits(log_n, digits);
-  return (int)digits[0];
-}
-
 constexpr size_t kNttTablesMax = 64;
 constexpr size_t kNttTableBytesMax = (size_t)1 << 30;        // 1 GiB: a prover keeps four (omega, omega^-1 at k and extended_k): < 200 MB
 
 void ntt_tables_release(NttTables& t) {
-  if (t.d_lo) (void)hipFree(t.d_lo);
-  if (t.d_hi) (void)hipFree(t.d_hi);
-  if (t.d_mid) (void)hipFree(t.d_mid);
-  for (auto& s : t.d_stage)
-    if (s) (void)hipFree(s);
-  if (t.ready) (void)hipEventDestroy(t.ready);
+  for (auto& d : t.d)
+    if (d) (void)hipFree(d);
+  t.pub.release();
   t = NttTables{};
 }
 
-// Tables for (omega, log_n): built once on the first caller's stream.  Later callers on OTHER streams
-// wait on the device for the `ready` event until it has been seen complete (stream-safe publication).
-NttTables* ntt_get_tables(DeviceCtx& ctx, const uint64_t omega_ext[4], uint32_t log_n, hipStream_t stream) {
+// Tables for (omega, log_n), exactly the plan's set: built once on the first caller's stream, published to the others (Publication).
+static NttTables* ntt_get_tables(DeviceCtx& ctx, const uint64_t omega_ext[4], uint32_t log_n, const NttTableSet& set, hipStream_t stream) {
   for (auto& t : ctx.ntt_tables) {
     if (t->log_n == log_n && std::memcmp(t->omega, omega_ext, 32) == 0) {
-      if (!t->published) {
-        if (hipEventQuery(t->ready) == hipSuccess) {
-          t->published = true;
-        } else if (stream != t->build_stream) {
-          HM_HIP_CHECK_PTR(hipStreamWaitEvent(stream, t->ready, 0));
-        }
-      }
+      HM_HIP_CHECK_PTR(t->pub.wait_or_publish(stream));
       t->last_use = ++ctx.ntt_table_clock;
       return t.get();
     }
   }
   // bounded (LRU): with direct tables up to 75 MB a caller that walks through many roots of unity must not keep them all.  A kernel
   // in flight on another stream may still read the set that goes: the device is synchronised first (rare: a prover uses four sets).
-  {
-    const size_t guess = log_n > (uint32_t)LOG_TILE && log_n <= NTT_DIRECT_LOG ? ((size_t)36 << log_n) : ((size_t)36 << ((log_n + 1) / 2 + 1));
-    bool synced = false;
-    while (!ctx.ntt_tables.empty() && (ctx.ntt_tables.size() >= kNttTablesMax || ctx.ntt_table_bytes + guess > kNttTableBytesMax)) {
-      if (!synced) {
-        (void)hipDeviceSynchronize();
-        synced = true;
-      }
-      size_t oldest = 0;
-      for (size_t i = 1; i < ctx.ntt_tables.size(); ++i)
-        if (ctx.ntt_tables[i]->last_use < ctx.ntt_tables[oldest]->last_use) oldest = i;
-      ctx.ntt_table_bytes -= ctx.ntt_tables[oldest]->bytes;
-      ntt_tables_release(*ctx.ntt_tables[oldest]);
-      ctx.ntt_tables.erase(ctx.ntt_tables.begin() + oldest);
+  bool synced = false;
+  while (!ctx.ntt_tables.empty() && (ctx.ntt_tables.size() >= kNttTablesMax || ctx.ntt_table_bytes + set.bytes > kNttTableBytesMax)) {
+    if (!synced) {
+      (void)hipDeviceSynchronize();
+      synced = true;
     }
+    size_t oldest = 0;
+    for (size_t i = 1; i < ctx.ntt_tables.size(); ++i)
+      if (ctx.ntt_tables[i]->last_use < ctx.ntt_tables[oldest]->last_use) oldest = i;
+    ctx.ntt_table_bytes -= ctx.ntt_tables[oldest]->bytes;
+    ntt_tables_release(*ctx.ntt_tables[oldest]);
+    ctx.ntt_tables.erase(ctx.ntt_tables.begin() + oldest);
   }
   auto t = std::make_unique<NttTables>();
   t->log_n = log_n;
   std::memcpy(t->omega, omega_ext, 32);
-  uint32_t digits[3] = {0, 0, 0};
-  const int passes = plan_digits(log_n, digits);
-  t->log_lb = (log_n + 1) / 2;
   FrWords om;
   std::memcpy(om.w, omega_ext, 32);
   bool ok = true;
-  auto make = [&](uint32_t count, uint32_t shift, uint32_t** dst) {
-    if (!ok) return;
-    if (hipMalloc(dst, (size_t)count * 36) != hipSuccess) { *dst = nullptr; ok = false; return; }
-    t->bytes += (size_t)count * 36;
-    hipLaunchKernelGGL(ntt_pow_table_kernel, dim3((count + 127) / 128), dim3(128), 0, stream, om, *dst, count, shift);
+  for (uint32_t i = 0; i < set.n_tables && ok; ++i) {
+    const NttTableSpec& spec = set.table[i];
+    if (hipMalloc(&t->d[i], (size_t)spec.count * NTT_TABLE_ENTRY_BYTES) != hipSuccess) { t->d[i] = nullptr; ok = false; break; }
+    t->bytes += (size_t)spec.count * NTT_TABLE_ENTRY_BYTES;
+    hipLaunchKernelGGL(ntt_pow_table_kernel, dim3((spec.count + 127) / 128), dim3(128), 0, stream, om, t->d[i], spec.count, spec.shift);
     if (hipGetLastError() != hipSuccess) ok = false;
-  };
-  if (passes > 1) {
-    if (log_n <= NTT_DIRECT_LOG && passes == 2) {
-      make(1u << log_n, 0, &t->d_lo);                                              // omega_n^e for every e < n
-    } else {
-      make(1u << t->log_lb, 0, &t->d_lo);
-      make(1u << (log_n - t->log_lb), t->log_lb, &t->d_hi);
-      const uint32_t log_m1 = log_n - digits[0];                                   // size of the middle pass's sub-problem
-      if (passes == 3 && log_m1 <= NTT_DIRECT_LOG) make(1u << log_m1, digits[0], &t->d_mid);   // omega_m1^e = omega_n^(e << s0)
-    }
   }
-  for (int p = 0; p < passes; ++p) {
-    const uint32_t s = digits[p];
-    if (t->d_stage[s] == nullptr) {
-      const uint32_t count = s == 0 ? 1 : (1u << (s - 1));
-      make(count == 0 ? 1 : count, log_n - s, &t->d_stage[s]);
-    }
-  }
-  if (ok && hipEventCreateWithFlags(&t->ready, hipEventDisableTiming) != hipSuccess) ok = false;
-  if (ok && hipEventRecord(t->ready, stream) != hipSuccess) ok = false;
-  if (!ok) {
+  if (!ok || !t->pub.record(stream)) {
     (void)hipStreamSynchronize(stream);      // kernels already enqueued may still write the tables being freed
     ntt_tables_release(*t);
     hm_fail(HM_ERR_HIP, "ntt: twiddle table allocation failed");
     return nullptr;
   }
-  t->build_stream = stream;
   t->last_use = ++ctx.ntt_table_clock;
   ctx.ntt_table_bytes += t->bytes;
   ctx.ntt_tables.push_back(std::move(t));
@@ -662,135 +563,21 @@ int aux_release(DeviceCtx& ctx, AuxSlot* slot, hipStream_t stream) {
   return HM_OK;
 }
 
-static void fill_internal9(const uint64_t ext[4], uint32_t out[9]) { host::fr_to_internal9(host::fr_load(ext), out); }
-
-// d_a: `batch` back-to-back arrays of n x 32 B on the device, each transformed in place.  `fused`: optional
-// constants (host pointers, external words) multiplied in by the first / last pass.
-// d_in != nullptr: an extending transform (EvaluationDomain::coeff_to_extended): `batch` compact arrays of
-// n >> log_z coefficients at d_in, zero-padded to n by definition, transformed into d_a (out of place;
-// the zero part is never materialised and the first log_z stages of the first pass cost nothing).
-int ntt_run(DeviceCtx& ctx, uint32_t* d_a, const uint64_t omega_ext[4], uint32_t log_n, uint32_t batch, const NttFused& fused,
-            hipStream_t stream, const uint32_t* d_in, uint32_t log_z) {
-  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "ntt: log_n > 28 (Fr has 2-adicity 28)");
-  if (batch == 0) return HM_OK;
-  // several cosets of the same inputs (fused.n_in_scales): the first pass reads `batch` inputs and writes batch * cosets arrays,
-  // every later pass is an ordinary batched pass over those
-  const uint32_t cosets = fused.n_in_scales, in_batch = batch;
-  if (cosets > HM_NTT_COSETS_MAX) return hm_fail(HM_ERR_BAD_ARG, "ntt: more than 16 cosets per call");
-  if (cosets) {
-    if ((uint64_t)batch * cosets > 65535) return hm_fail(HM_ERR_BAD_ARG, "ntt: batch * cosets > 65535");
-    if (!d_in || log_z != 0) return hm_fail(HM_ERR_INTERNAL, "ntt: the multi-coset form is out of place and not extending");
-    batch *= cosets;
-  }
-  if (batch > 65535) return hm_fail(HM_ERR_BAD_ARG, "ntt: batch > 65535");
-  NttTables* tab = ntt_get_tables(ctx, omega_ext, log_n, stream);
-  if (!tab) return HM_ERR_HIP;
-  uint32_t digits[3] = {0, 0, 0};
-  const int passes = plan_digits(log_n, digits);
-  const uint64_t n = 1ull << log_n;
-  uint32_t* scratch = nullptr;
-  AuxSlot* slot = nullptr;
-  if (passes > 1) {
-    slot = aux_acquire(ctx, stream);
-    if (!slot) return HM_ERR_HIP;
-    scratch = (uint32_t*)slot->scratch.ensure(n * 32 * batch);
-    if (!scratch) return hm_fail(HM_ERR_HIP, "ntt: scratch allocation failed");
-  }
-  const size_t lds_bytes = (size_t)9 * sizeof(uint32_t) << LOG_TILE;
-  if (!ctx.ntt_attr_set) {   // per device: a process may drive several GPUs
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ntt_pass_kernel<LOG_TILE, false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ntt_pass_kernel<LOG_TILE, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ntt_pass_kernel<LOG_TILE, true, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    ctx.ntt_attr_set = true;
-  }
-  if (d_in && log_z != 0 && (passes < 2 || log_z > digits[0]))
-    return hm_fail(HM_ERR_INTERNAL, "ntt: extending form needs a multi-pass plan and log_z <= first digit");
-  // fused constants -> internal 9-limb form on the host (a handful of 4 x u64 products)
-  uint32_t coset9[27] = {}, fin9[27] = {};
-  uint32_t fin_mode = 0;
-  if (fused.coset)
-    for (int j = 0; j < 3; ++j) fill_internal9(fused.coset + 4 * j, coset9 + 9 * j);
-  if (fused.post3) {
-    fin_mode = 2;
-    for (int j = 0; j < 3; ++j) {
-      host::Fr4 c = host::fr_load(fused.post3 + 4 * j);
-      if (fused.scale) c = host::fr_mul(c, host::fr_load(fused.scale));
-      host::fr_to_internal9(c, fin9 + 9 * j);
-    }
-  } else if (fused.scale) {
-    fin_mode = 1;
-    fill_internal9(fused.scale, fin9);
-  }
-  uint32_t log_stride = log_n;
-  for (int p = 0; p < passes; ++p) {
-    NttPassParams pp{};
-    pp.log_n = log_n;
-    pp.s = digits[p];
-    log_stride -= digits[p];
-    pp.log_stride = log_stride;
-    pp.last = (p == passes - 1) ? 1u : 0u;
-    pp.log_lb = tab->log_lb;
-    pp.log_rows = log_n - pp.s;
-    pp.log_r0 = (pp.last && passes == 3) ? digits[0] : 0u;
-    pp.fin_mode = pp.last ? fin_mode : 0u;
-    pp.has_coset = (p == 0 && fused.coset) ? 1u : 0u;
-    if (pp.has_coset) std::memcpy(pp.coset, coset9, sizeof coset9);
-    if (pp.fin_mode) std::memcpy(pp.fin, fin9, sizeof fin9);
-    pp.log_z = (p == 0 && d_in) ? log_z : 0u;
-    pp.has_table = (p == 0 && (fused.d_in_scale || cosets)) ? 1u : 0u;
-    uint32_t log_c = (uint32_t)LOG_TILE > pp.s ? (uint32_t)LOG_TILE - pp.s : 0u;
-    const uint32_t avail = pp.last ? pp.log_rows : pp.log_stride;  // columns / rows that exist
-    if (log_c > avail) log_c = avail;
-    pp.log_c = log_c;
-    const uint64_t tiles = n >> (pp.s + log_c);
-    const uint32_t* src = (p == 0) ? (d_in ? d_in : d_a) : scratch;
-    uint32_t* dst = (p == passes - 1) ? d_a : scratch;
-    const uint32_t* lo_tab = tab->d_lo;
-    if (!pp.last) {
-      if (log_n <= NTT_DIRECT_LOG && passes == 2) {
-        pp.direct_tw = 1;            // d_lo = omega_n^e; omega_m^e = omega_n^(e << (log_n - log_m)) only for p == 0 (m = n)
-      } else if (p == 1 && tab->d_mid) {
-        pp.direct_tw = 1;
-        lo_tab = tab->d_mid;
-      }
-    }
-    NttCosetTables zc{};
-    if (pp.has_table) {
-      if (cosets) {
-        zc.count = cosets;
-        for (uint32_t c = 0; c < cosets; ++c) zc.table[c] = fused.d_in_scales[c];
-      }
-      hipLaunchKernelGGL((ntt_pass_kernel<LOG_TILE, true, true>), dim3((uint32_t)tiles, in_batch, cosets ? cosets : 1), dim3(NTT_THREADS), lds_bytes,
-                         stream, src, dst, pp, (const uint32_t*)tab->d_stage[pp.s], lo_tab, (const uint32_t*)tab->d_hi, fused.d_in_scale, zc);
-    } else if (pp.has_coset | pp.fin_mode) {
-      hipLaunchKernelGGL((ntt_pass_kernel<LOG_TILE, true>), dim3((uint32_t)tiles, batch), dim3(NTT_THREADS), lds_bytes, stream, src, dst,
-                         pp, (const uint32_t*)tab->d_stage[pp.s], lo_tab, (const uint32_t*)tab->d_hi, (const uint32_t*)nullptr, zc);
-    } else {
-      hipLaunchKernelGGL((ntt_pass_kernel<LOG_TILE, false>), dim3((uint32_t)tiles, batch), dim3(NTT_THREADS), lds_bytes, stream, src, dst,
-                         pp, (const uint32_t*)tab->d_stage[pp.s], lo_tab, (const uint32_t*)tab->d_hi, (const uint32_t*)nullptr, zc);
-    }
-    HM_HIP_CHECK(hipGetLastError());
-  }
-  if (slot) return aux_release(ctx, slot, stream);
-  return HM_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
-// transforms on a coset shift * <omega> (the extended domain of evaluate_h taken one coset of the n-th roots at a time:
-// 2^(extended_k - k) independent n-point problems instead of one 2^extended_k-point problem -- what lets the cosets go to
+// the powers tables of the transforms on a coset shift * <omega> (the extended domain of evaluate_h taken one coset of the n-th roots
+// at a time: 2^(extended_k - k) independent n-point problems instead of one 2^extended_k-point problem -- what lets the cosets go to
 // different GPUs)
 // ---------------------------------------------------------------------------------------------
 constexpr size_t kCosetTablesMax = 48;
 constexpr size_t kCosetTableBytesMax = (size_t)2 << 30;      // 2 GiB of HBM held between calls at most (48 tables of 2^24 would be 24 GiB)
 
+static void coset_table_free(CosetTable& t) {
+  if (t.d) (void)hipFree(t.d);
+  t.pub.release();
+}
+
 void coset_tables_release(DeviceCtx& ctx) {
-  for (auto& t : ctx.coset_tables) {
-    if (t->d) (void)hipFree(t->d);
-    if (t->ready) (void)hipEventDestroy(t->ready);
-  }
+  for (auto& t : ctx.coset_tables) coset_table_free(*t);
   ctx.coset_tables.clear();
   ctx.coset_table_bytes = 0;
 }
@@ -822,26 +609,18 @@ static bool coset_table_evict_one(DeviceCtx& ctx, uint64_t keep_from, bool* sync
     (void)hipDeviceSynchronize();
     *synced = true;
   }
-  CosetTable& t = *ctx.coset_tables[oldest];
-  if (t.d) (void)hipFree(t.d);
-  if (t.ready) (void)hipEventDestroy(t.ready);
-  ctx.coset_table_bytes -= (size_t)32 << t.log_n;
+  coset_table_free(*ctx.coset_tables[oldest]);
+  ctx.coset_table_bytes -= (size_t)32 << ctx.coset_tables[oldest]->log_n;
   ctx.coset_tables.erase(ctx.coset_tables.begin() + oldest);
   return true;
 }
 
-// keep_from: the coset clock when the calling entry point started (tables it has already been handed are not evicted under it)
+// keep_from: the coset clock when the calling driver started (tables it has already been handed are not evicted under it)
 static const uint32_t* coset_table_get(DeviceCtx& ctx, const uint64_t shift_ext[4], uint32_t log_n, bool internal, hipStream_t stream,
                                        uint64_t keep_from) {
   for (auto& t : ctx.coset_tables) {
     if (t->log_n == log_n && t->internal == (internal ? 1u : 0u) && std::memcmp(t->shift, shift_ext, 32) == 0) {
-      if (!t->published) {
-        if (hipEventQuery(t->ready) == hipSuccess) {
-          t->published = true;
-        } else if (stream != t->build_stream) {
-          HM_HIP_CHECK_PTR(hipStreamWaitEvent(stream, t->ready, 0));
-        }
-      }
+      HM_HIP_CHECK_PTR(t->pub.wait_or_publish(stream));
       t->last_use = ++ctx.coset_clock;
       return t->d;
     }
@@ -867,84 +646,93 @@ static const uint32_t* coset_table_get(DeviceCtx& ctx, const uint64_t shift_ext[
   if (!ok) t->d = nullptr;
   const host::Fr4 c = internal ? host::fr_mul(host::FR_32, host::FR_32) : host::FR_32;       // 1024 resp. 32, Montgomery words
   if (ok) ok = fr_powers_run(t->d, n, shift_ext, stream) == HM_OK && fr_scale_run(t->d, c.l, n, stream) == HM_OK;
-  if (ok && hipEventCreateWithFlags(&t->ready, hipEventDisableTiming) != hipSuccess) ok = false;
-  if (ok && hipEventRecord(t->ready, stream) != hipSuccess) ok = false;
-  if (!ok) {
+  if (!ok || !t->pub.record(stream)) {
     (void)hipStreamSynchronize(stream);
-    if (t->d) (void)hipFree(t->d);
-    if (t->ready) (void)hipEventDestroy(t->ready);
+    coset_table_free(*t);
     hm_fail(HM_ERR_HIP, "ntt: coset table allocation failed");
     return nullptr;
   }
-  t->build_stream = stream;
   t->last_use = ++ctx.coset_clock;
   ctx.coset_table_bytes += bytes;
   ctx.coset_tables.push_back(std::move(t));
   return ctx.coset_tables.back()->d;
 }
 
-int ntt_coset_run(DeviceCtx& ctx, const uint32_t* d_in, uint32_t* d_out, uint32_t batch, const uint64_t omega_ext[4], uint32_t log_n,
-                  const uint64_t shift_ext[4], bool internal, hipStream_t stream) {
-  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "ntt: log_n > 28 (Fr has 2-adicity 28)");
-  if (batch == 0) return HM_OK;
-  const uint32_t* table = coset_table_get(ctx, shift_ext, log_n, internal, stream, ctx.coset_clock + 1);
-  if (!table) return HM_ERR_HIP;
-  NttFused f;
-  f.d_in_scale = table;
-  return ntt_run(ctx, d_out, omega_ext, log_n, batch, f, stream, d_in == d_out ? nullptr : d_in, 0);
-}
+// ---------------------------------------------------------------------------------------------
+// the one driver
+// ---------------------------------------------------------------------------------------------
+using NttPassKernel = void (*)(const uint32_t*, uint32_t*, NttPassParams, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*,
+                               NttCosetTables);
+static NttPassKernel const kNttPass[3] = {ntt_pass_kernel<NTT_LOG_TILE, false>, ntt_pass_kernel<NTT_LOG_TILE, true>,      // by NttVariant
+                                          ntt_pass_kernel<NTT_LOG_TILE, true, true>};
 
-int ntt_cosets_run(DeviceCtx& ctx, const uint32_t* d_in, uint32_t* d_out, uint32_t batch, const uint64_t omega_ext[4], uint32_t log_n,
-                   const uint64_t* shifts_ext, uint32_t count, bool internal, hipStream_t stream) {
-  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "ntt: log_n > 28 (Fr has 2-adicity 28)");
-  if (batch == 0 || count == 0) return HM_OK;
-  if (count > HM_NTT_COSETS_MAX) return hm_fail(HM_ERR_BAD_ARG, "ntt: more than 16 cosets per call");
-  NttFused f;
-  f.n_in_scales = count;
-  const uint64_t mine = ctx.coset_clock + 1;               // the tables handed out from here on belong to this call
-  for (uint32_t c = 0; c < count; ++c) {
-    f.d_in_scales[c] = coset_table_get(ctx, shifts_ext + 4 * c, log_n, internal, stream, mine);
-    if (!f.d_in_scales[c]) return HM_ERR_HIP;
-  }
-  return ntt_run(ctx, d_out, omega_ext, log_n, batch, f, stream, d_in, 0);
-}
-
-int ntt_cosets_inverse_run(DeviceCtx& ctx, uint32_t* d_a, uint32_t count, const uint64_t omega_inv_ext[4], uint32_t log_n,
-                           const uint64_t divisor_ext[4], const uint64_t* shift_invs_ext, hipStream_t stream) {
-  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "ntt: log_n > 28 (Fr has 2-adicity 28)");
-  if (count == 0) return HM_OK;
-  if (count > HM_NTT_COSETS_MAX) return hm_fail(HM_ERR_BAD_ARG, "ntt: more than 16 cosets per call");
+// In order: the check and the plan (ntt_plan.inc), the coset and the twiddle tables, the fused constants on the host -- every refusal
+// lies before the slot is taken -- then, inside aux_scope when the plan has scratch, the scratch buffer, the pass launches and the
+// inverse coset forms' table product.  An extending call (log_z > 0) never materialises the zero part of its padded input, and the
+// first log_z stages of its first pass cost nothing; several cosets of the same inputs: the first pass reads `batch` inputs and writes
+// batch * cosets arrays, every later pass is an ordinary batched pass over those.
+int ntt_run(DeviceCtx& ctx, const NttCall& call, const NttPointers& p, hipStream_t stream) {
+  const NttCall c = ntt_bind(call, p);
+  if (const char* why = ntt_check_call(c)) return hm_fail(HM_ERR_BAD_ARG, std::string("ntt: ") + why);
+  const NttPlan plan = ntt_plan(c);
+  if (plan.passes == 0) return HM_OK;
   NttCosetTables tabs{};
-  tabs.count = count;
-  const uint64_t mine = ctx.coset_clock + 1;
-  for (uint32_t c = 0; c < count; ++c) {
-    tabs.table[c] = coset_table_get(ctx, shift_invs_ext + 4 * c, log_n, false, stream, mine);
-    if (!tabs.table[c]) return HM_ERR_HIP;
+  tabs.count = (c.fused & NTT_F_IN_TABLES) ? c.fwd_cosets : (c.fused & NTT_F_OUT_TABLES) ? c.inv_cosets
+               : (c.fused & (NTT_F_IN_TABLE | NTT_F_OUT_TABLE)) ? 1u : 0u;
+  const uint64_t mine = ctx.coset_clock + 1;               // the tables handed out from here on belong to this call
+  for (uint32_t i = 0; i < tabs.count; ++i) {
+    tabs.table[i] = coset_table_get(ctx, p.shifts + 4 * i, c.log_n, p.internal, stream, mine);
+    if (!tabs.table[i]) return HM_ERR_HIP;
   }
-  NttFused f;
-  f.scale = divisor_ext;
-  const int rc = ntt_run(ctx, d_a, omega_inv_ext, log_n, count, f, stream);
-  if (rc != HM_OK) return rc;
-  const uint64_t n = 1ull << log_n;
-  hipLaunchKernelGGL(fr_mul_tables_kernel, dim3((uint32_t)((n + 255) / 256), count), dim3(256), 0, stream, d_a, tabs, n);
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
-}
-
-int ntt_coset_inverse_run(DeviceCtx& ctx, uint32_t* d_a, uint32_t batch, const uint64_t omega_inv_ext[4], uint32_t log_n,
-                          const uint64_t divisor_ext[4], const uint64_t shift_inv_ext[4], hipStream_t stream) {
-  if (log_n > 28) return hm_fail(HM_ERR_BAD_ARG, "ntt: log_n > 28 (Fr has 2-adicity 28)");
-  if (batch == 0) return HM_OK;
-  const uint32_t* table = coset_table_get(ctx, shift_inv_ext, log_n, false, stream, ctx.coset_clock + 1);
-  if (!table) return HM_ERR_HIP;
-  NttFused f;
-  f.scale = divisor_ext;
-  const int rc = ntt_run(ctx, d_a, omega_inv_ext, log_n, batch, f, stream);
-  if (rc != HM_OK) return rc;
-  const uint64_t n = 1ull << log_n;
-  hipLaunchKernelGGL(fr_mul_table_kernel, dim3((uint32_t)((n + 255) / 256), batch), dim3(256), 0, stream, d_a, table, n);
-  HM_HIP_CHECK(hipGetLastError());
-  return HM_OK;
+  NttTables* tab = ntt_get_tables(ctx, p.omega, c.log_n, plan.tables, stream);
+  if (!tab) return HM_ERR_HIP;
+  if (!ctx.ntt_attr_set) {   // per device: a process may drive several GPUs
+    for (NttPassKernel k : kNttPass)
+      HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
+    ctx.ntt_attr_set = true;
+  }
+  // fused constants -> internal 9-limb form on the host (a handful of 4 x u64 products)
+  uint32_t coset9[27] = {}, fin9[27] = {};
+  if (c.fused & NTT_F_COSET3)
+    for (int j = 0; j < 3; ++j) host::fr_to_internal9(host::fr_load(p.coset + 4 * j), coset9 + 9 * j);
+  if (c.fused & NTT_F_POST3) {
+    for (int j = 0; j < 3; ++j) {
+      host::Fr4 f = host::fr_load(p.post3 + 4 * j);
+      if (c.fused & NTT_F_SCALE) f = host::fr_mul(f, host::fr_load(p.scale));
+      host::fr_to_internal9(f, fin9 + 9 * j);
+    }
+  } else if (c.fused & NTT_F_SCALE) {
+    host::fr_to_internal9(host::fr_load(p.scale), fin9);
+  }
+  auto launches = [&](uint32_t* scratch) -> int {
+    auto buffer = [&](uint32_t b) { return b == NTT_BUF_INPUT ? const_cast<uint32_t*>(p.d_in) : b == NTT_BUF_ARRAY ? p.d_a : scratch; };
+    auto table = [&](int8_t i) -> const uint32_t* { return i < 0 ? nullptr : tab->d[i]; };
+    for (uint32_t i = 0; i < plan.passes; ++i) {
+      const NttPassPlan& pass = plan.pass[i];
+      NttPassParams pp{};
+      static_cast<NttPassHead&>(pp) = pass.head;
+      if (pp.has_coset) std::memcpy(pp.coset, coset9, sizeof coset9);
+      if (pp.fin_mode) std::memcpy(pp.fin, fin9, sizeof fin9);
+      const bool tabled = pass.variant == NTT_TABLE;
+      hipLaunchKernelGGL(kNttPass[pass.variant], dim3(pass.grid[0], pass.grid[1], pass.grid[2]), dim3(NTT_THREADS), plan.lds_bytes, stream,
+                         (const uint32_t*)buffer(pass.src), buffer(pass.dst), pp, table(pass.stage), table(pass.tw_lo), table(pass.tw_hi),
+                         tabled && (c.fused & NTT_F_IN_TABLE) ? tabs.table[0] : (const uint32_t*)nullptr,
+                         tabled && (c.fused & NTT_F_IN_TABLES) ? tabs : NttCosetTables{});
+      HM_HIP_CHECK(hipGetLastError());
+    }
+    const dim3 tail_grid(plan.tail_grid[0], plan.tail_grid[1]);
+    const uint64_t n = 1ull << c.log_n;
+    if (plan.tail == NTT_TAIL_TABLE) hipLaunchKernelGGL(fr_mul_table_kernel, tail_grid, dim3(256), 0, stream, p.d_a, tabs.table[0], n);
+    if (plan.tail == NTT_TAIL_TABLES) hipLaunchKernelGGL(fr_mul_tables_kernel, tail_grid, dim3(256), 0, stream, p.d_a, tabs, n);
+    if (plan.tail != NTT_TAIL_NONE) HM_HIP_CHECK(hipGetLastError());
+    return HM_OK;
+  };
+  if (plan.scratch_bytes == 0) return launches(nullptr);
+  return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
+    uint32_t* scratch = (uint32_t*)slot.scratch.ensure(plan.scratch_bytes);
+    if (!scratch) return hm_fail(HM_ERR_HIP, "ntt: scratch allocation failed");
+    return launches(scratch);
+  });
 }
 
 int fr_scale_run(uint32_t* d_a, const uint64_t c_ext[4], uint64_t n, hipStream_t stream) {

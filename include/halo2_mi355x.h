@@ -224,7 +224,11 @@ int hm_ntt_bn256_fr(uint64_t* a, const uint64_t omega[4], uint32_t log_n);
  * concurrently on different streams (and from different threads): the ping-pong buffer of a multi-pass
  * transform belongs to the stream in use (a small pool, handed over behind an event), fused constants
  * travel to the kernels by value, and twiddle tables built on one stream are published to the others
- * behind an event. */
+ * behind an event.
+ * Every *_dev NTT entry point below (hm_ntt*, hm_ifft, hm_coset_ntt, hm_coeff_to_extended, hm_extended_to_coeff, hm_coeff_to_coset(s),
+ * hm_coset(s)_to_coeff) refuses with HM_ERR_BAD_ARG, before anything is launched and without needing a device: a null argument,
+ * log_n (log_ext) > 28, log_n > log_ext, more than 16 cosets, batch or batch * cosets > 65535, an output overlapping its input where
+ * the form is out of place, and a DATA POINTER THAT IS NOT 16-BYTE ALIGNED (the passes move an element as two 16-byte halves). */
 int hm_ntt_bn256_fr_dev(void* d_a, const uint64_t omega[4], uint32_t log_n, void* stream);
 
 /* `batch` back-to-back arrays of 2^log_n elements transformed by ONE set of launches (the ~48

@@ -91,6 +91,10 @@ def test_device_pointer_entry_points_without_a_device():
     assert lib.hm_quotient_by_cosets_bn256_fr_dev(ctypes.c_uint64(1), one_col, None, 1, zp, 1, 3, zp, zp, 1, 1, ctypes.c_void_p(0x9000), None) == -1   # a zero shift
     assert lib.hm_coeff_to_coset_bn256_fr_dev(ctypes.c_void_p(0x1000), ctypes.c_void_p(0x100000), 1, zp, 29, zp, 0, None) == -1      # log_n > 28
     assert lib.hm_coeff_to_coset_bn256_fr_dev(ctypes.c_void_p(0x1000), ctypes.c_void_p(0x1020), 1, zp, 3, zp, 0, None) == -1        # partial overlap
+    assert lib.hm_coeff_to_extended_bn256_fr_dev(ctypes.c_void_p(0x1000), ctypes.c_void_p(0x1020), 2, zp, 3, 5, None, None) == -1   # padded over its input
+    assert lib.hm_coeff_to_extended_bn256_fr_dev(ctypes.c_void_p(0x1008), ctypes.c_void_p(0x100000), 2, zp, 14, 17, None, None) == -1   # 8 bytes off
+    assert b"16-byte aligned" in lib.hm_last_error()
+    assert lib.hm_ntt_bn256_fr_dev(ctypes.c_void_p(0x1008), zp, 3, None) == -1 and lib.hm_ntt_batch_bn256_fr_dev(ctypes.c_void_p(0x1000), 65536, zp, 3, None, None, None) == -1
     assert lib.hm_device_malloc(64, None) == -1 and lib.hm_copy_to_device(None, None, 8) == -1 and lib.hm_copy_to_host(None, None, 8) == -1
     assert lib.hm_copy_to_device(None, None, 0) in (0, -2) and lib.hm_set_host_copies(7) == -1 and lib.hm_set_host_copies(0) == 0
     assert lib.hm_fr_batch_invert_dev(None, 8, None) == -1
@@ -112,6 +116,15 @@ def test_device_pointer_entry_points_without_a_device():
     assert lib.hm_coset_to_coeff_bn256_fr_dev(fake, 1, zp, 3, zp, zp, None) == -2
     assert lib.hm_coeff_to_cosets_bn256_fr_dev(fake, ctypes.c_void_p(0x100000), 1, zp, 3, zp, 1, 0, None) == -2
     assert lib.hm_cosets_to_coeff_bn256_fr_dev(fake, 1, zp, 3, zp, zp, None) == -2
+    # every form of the NTT's call check admits what its entry makes: the extending form (device and host), its copy-and-pad fallback
+    big = np.zeros((1 << 17, 4), dtype=np.uint64).ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    c3 = np.zeros(12, dtype=np.uint64).ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    for log_n, log_ext in ((14, 17), (3, 5), (5, 5)):
+        assert lib.hm_coeff_to_extended_bn256_fr(big, big, zp, log_n, log_ext, c3) == -2
+        assert lib.hm_coeff_to_extended_bn256_fr_dev(fake, ctypes.c_void_p(0x10000000), 2, zp, log_n, log_ext, None, None) == -2
+    assert lib.hm_coeff_to_extended_bn256_fr_dev(fake, fake, 2, zp, 5, 5, None, None) == -2        # nothing to pad: in place
+    assert lib.hm_ntt_bn256_fr(big, zp, 17) == -2 and lib.hm_extended_to_coeff_bn256_fr(big, 5, zp, 17, zp, c3) == -2
+    assert lib.hm_extended_to_coeff_bn256_fr_dev(fake, 3, zp, 17, zp, c3, None) == -2 and lib.hm_ifft_bn256_fr_dev(fake, zp, 17, zp, None) == -2
     two = np.array([2, 0, 0, 0], dtype=np.uint64)
     twop = two.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
     one_col = (ctypes.c_void_p * 1)(0x1000)

@@ -931,3 +931,138 @@ def test_host_forms_count_the_bytes_they_move(cref, pyref):
     _lib.check(lib.hm_extended_to_coeff_bn256_fr(u64(got), 5, u64(fr_words(w4_inv)), 4, u64(fr_words(div)), u64(coset_inv)))
     assert (_pcie_bytes() - b0).tolist() == [16 * 32, 5 * 32]
     assert np.array_equal(got[:5], exp[:5]) and (got[5:] == sentinel).all()
+
+
+# ---- the coset forms on every plan shape, against entries that have oracle tests of their own ------------------------
+def _elementwise_product(a, b):
+    """a[i] * b[i] through the graph evaluator (tests/test_evaluation.py holds it to the oracle): PreviousValue = 0, one gate"""
+    import torch
+    from halo2_experiments_amd import evaluation as ev
+    g = ev.GraphEvaluator()
+    g.add_custom_gates([ev.Advice(0) * ev.Advice(1)])
+    prog = g.compile(0, 2, 0)
+    try:
+        out = torch.zeros_like(a)
+        prog.evaluate([a, b], out, y=1)
+        torch.cuda.synchronize()
+        return out
+    finally:
+        prog.destroy()
+
+
+def _powers(x, n):
+    import torch
+    from halo2_experiments_amd.arithmetic import _ptr, _stream_ptr
+    out = torch.empty((n, 4), dtype=torch.int64, device="cuda")
+    _lib.check(_lib.load().hm_fr_powers_dev(ctypes.c_void_p(out.data_ptr()), n, _ptr(fr_words(x)), ctypes.c_void_p(_stream_ptr(out))))
+    return out
+
+
+@pytest.mark.parametrize("k", [11, 12, 13, 22])
+def test_coset_forms_equal_the_powers_product_and_the_plain_transform(k):
+    """hm_coeff_to_coset, hm_coeff_to_cosets with two shifts and hm_cosets_to_coeff at one pass (2^11), the first two-pass size
+    (2^12), the first odd split (2^13) and the smallest three-pass size (2^22: the middle pass's direct table, two-level first-pass
+    twiddles), batch 1, against the composition a[i] * shift^i (hm_fr_powers_dev, the evaluator's product) and best_fft / ifft."""
+    import torch
+    from halo2_experiments_amd.arithmetic import _ptr, _stream_ptr
+    from halo2_experiments_amd.domain import FR_MODULUS as R, FR_ROOT_OF_UNITY
+    lib = _lib.load()
+    n = 1 << k
+    omega = pow(FR_ROOT_OF_UNITY, 1 << (28 - k), R)
+    shifts = [0x1234567890ABCDEF1234567890ABCDEF % R, 7]
+    a = rand_fr_gpu(n, 9300 + k)
+    vp, st = (lambda t: ctypes.c_void_p(t.data_ptr())), (lambda t: ctypes.c_void_p(_stream_ptr(t)))
+    want = []
+    for s in shifts:
+        w = _elementwise_product(a, _powers(s, n))
+        h.best_fft(w, fr_words(omega), k)
+        want.append(w)
+    one = torch.empty_like(a)
+    _lib.check(lib.hm_coeff_to_coset_bn256_fr_dev(vp(a), vp(one), 1, _ptr(fr_words(omega)), k, _ptr(fr_words(shifts[0])), 0, st(one)))
+    assert torch.equal(one, want[0])
+    both = torch.empty((2, n, 4), dtype=torch.int64, device="cuda")
+    _lib.check(lib.hm_coeff_to_cosets_bn256_fr_dev(vp(a), vp(both), 1, _ptr(fr_words(omega)), k, _ptr(np.stack([fr_words(s) for s in shifts])), 2, 0,
+                                                   st(both)))
+    assert torch.equal(both[0], want[0]) and torch.equal(both[1], want[1])
+    # back: divisor * inverse transform, then element i *= shift^-i -- the coefficients again
+    v = rand_fr_gpu(2 * n, 9400 + k).reshape(2, n, 4)
+    omega_inv, n_inv, shift_invs = pow(omega, -1, R), pow(n, -1, R), [pow(s, -1, R) for s in shifts]
+    want_back = []
+    for c in range(2):
+        t = v[c].clone()
+        _lib.check(lib.hm_ifft_bn256_fr_dev(vp(t), _ptr(fr_words(omega_inv)), k, _ptr(fr_words(n_inv)), st(t)))
+        want_back.append(_elementwise_product(t, _powers(shift_invs[c], n)))
+    got = v.clone()
+    _lib.check(lib.hm_cosets_to_coeff_bn256_fr_dev(vp(got), 2, _ptr(fr_words(omega_inv)), k, _ptr(fr_words(n_inv)),
+                                                   _ptr(np.stack([fr_words(s) for s in shift_invs])), st(got)))
+    assert torch.equal(got[0], want_back[0]) and torch.equal(got[1], want_back[1])
+    back = both.clone()
+    _lib.check(lib.hm_cosets_to_coeff_bn256_fr_dev(vp(back), 2, _ptr(fr_words(omega_inv)), k, _ptr(fr_words(n_inv)),
+                                                   _ptr(np.stack([fr_words(s) for s in shift_invs])), st(back)))
+    assert torch.equal(back[0], a) and torch.equal(back[1], a)
+
+
+def test_refused_device_calls_touch_nothing_and_leave_the_slots_healthy():
+    """Every refusal of the device entries that needs no device: HM_ERR_BAD_ARG, the arrays untouched, nothing counted and no table
+    built (nothing was launched); a good multi-pass call on a second stream afterwards equals the one made before any refusal."""
+    import torch
+    from halo2_experiments_amd.arithmetic import _ptr
+    from halo2_experiments_amd.domain import FR_MODULUS as R, FR_ROOT_OF_UNITY
+    lib = _lib.load()
+    k = 14                                                                  # two passes: the good calls take a stream slot
+    n = 1 << k
+    omega, shift = fr_words(pow(FR_ROOT_OF_UNITY, 1 << (28 - k), R)), fr_words(0xABCDEF0123456789 % R)
+    fresh = fr_words(pow(FR_ROOT_OF_UNITY, 3 << (28 - k), R))                # a root no other call uses: its tables would be new
+    a = rand_fr_gpu(2 * n + 1, 9500)                                        # room for an array that starts 8 bytes in
+    vp = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + off)
+    out = torch.zeros((2, n, 4), dtype=torch.int64, device="cuda")
+
+    def good(stream):
+        with torch.cuda.stream(stream):
+            y, z = a[:n].clone(), torch.empty((n, 4), dtype=torch.int64, device="cuda")
+            s = ctypes.c_void_p(stream.cuda_stream)
+            _lib.check(lib.hm_ntt_bn256_fr_dev(vp(y), _ptr(omega), k, s))
+            _lib.check(lib.hm_coeff_to_coset_bn256_fr_dev(vp(a), vp(z), 1, _ptr(omega), k, _ptr(shift), 0, s))
+            _lib.check(lib.hm_coset_to_coeff_bn256_fr_dev(vp(z), 1, _ptr(omega), k, _ptr(shift), _ptr(shift), s))
+        stream.synchronize()
+        return y, z
+
+    def state():
+        st = _lib.Stats()
+        _lib.check(lib.hm_get_stats(ctypes.byref(st)))
+        return st.ntt_calls, st.ntt_tables, st.coset_tables
+
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    before = good(s1)
+    a0, out0, st0 = a.clone(), out.clone(), state()
+    two = np.stack([shift, fr_words(5)])
+    seventeen = np.stack([fr_words(100 + i) for i in range(17)])
+    refusals = [
+        lib.hm_ntt_bn256_fr_dev(vp(a, 8), _ptr(fresh), k, None),                                             # a pointer 8 bytes off
+        lib.hm_ntt_batch_bn256_fr_dev(vp(a, 8), 2, _ptr(fresh), k, None, None, None),
+        lib.hm_ifft_bn256_fr_dev(vp(a, 8), _ptr(fresh), k, _ptr(shift), None),
+        lib.hm_extended_to_coeff_bn256_fr_dev(vp(a, 8), 1, _ptr(fresh), k, _ptr(shift), _ptr(np.stack([shift] * 3)), None),
+        lib.hm_coeff_to_coset_bn256_fr_dev(vp(a, 8), vp(out), 1, _ptr(fresh), k, _ptr(shift), 0, None),
+        lib.hm_coeff_to_coset_bn256_fr_dev(vp(a), vp(out, 8), 1, _ptr(fresh), k, _ptr(shift), 0, None),
+        lib.hm_coeff_to_cosets_bn256_fr_dev(vp(a, 8), vp(out), 1, _ptr(fresh), k, _ptr(two), 2, 0, None),
+        lib.hm_coset_to_coeff_bn256_fr_dev(vp(a, 8), 1, _ptr(fresh), k, _ptr(shift), _ptr(shift), None),
+        lib.hm_cosets_to_coeff_bn256_fr_dev(vp(a, 8), 2, _ptr(fresh), k, _ptr(shift), _ptr(two), None),
+        lib.hm_coeff_to_extended_bn256_fr_dev(vp(a, 8), vp(out), 1, _ptr(fresh), k - 1, k, None, None),
+        lib.hm_coeff_to_extended_bn256_fr_dev(vp(a, 8), vp(out), 1, _ptr(fresh), 3, 5, None, None),          # ... and where the padded array is copied
+        lib.hm_ntt_bn256_fr_dev(vp(a), _ptr(fresh), 29, None),                                               # log_n = 29
+        lib.hm_coset_to_coeff_bn256_fr_dev(vp(a), 1, _ptr(fresh), 29, _ptr(shift), _ptr(shift), None),
+        lib.hm_ntt_batch_bn256_fr_dev(vp(a), 65536, _ptr(fresh), 0, None, None, None),                       # batch 65536
+        lib.hm_coeff_to_coset_bn256_fr_dev(vp(a), vp(out), 65536, _ptr(fresh), 0, _ptr(shift), 0, None),
+        lib.hm_coeff_to_cosets_bn256_fr_dev(vp(a), vp(out), 1, _ptr(fresh), 3, _ptr(seventeen), 17, 0, None),     # 17 cosets
+        lib.hm_cosets_to_coeff_bn256_fr_dev(vp(a), 17, _ptr(fresh), 3, _ptr(shift), _ptr(seventeen), None),
+        lib.hm_coeff_to_coset_bn256_fr_dev(vp(a), vp(a, 32), 1, _ptr(fresh), k, _ptr(shift), 0, None),       # the output overlaps the input
+        lib.hm_coeff_to_cosets_bn256_fr_dev(vp(a), vp(a), 1, _ptr(fresh), k - 1, _ptr(two), 2, 0, None),
+        lib.hm_coeff_to_cosets_bn256_fr_dev(vp(a), vp(a, 32 * (n // 2 - 1)), 1, _ptr(fresh), k - 1, _ptr(two), 2, 0, None),
+        lib.hm_coeff_to_extended_bn256_fr_dev(vp(a), vp(out), 1, _ptr(fresh), k + 1, k, None, None),         # log_z beyond log_ext
+    ]
+    torch.cuda.synchronize()
+    assert refusals == [-1] * len(refusals), refusals
+    assert torch.equal(a, a0) and torch.equal(out, out0) and state() == st0
+    after = good(s2)
+    assert torch.equal(after[0], before[0]) and torch.equal(after[1], before[1])

@@ -4,6 +4,7 @@ differ in ntt.hip's plan knobs (tools/ab_ntt.sh), each in its own process (HALO2
 default build's, times by HIP events.
 
     python tools/ntt_plans.py                       # every gpurun_ab/libhalo2_mi355x_*.so against the tree's library
+    python tools/ntt_plans.py --shapes ntt:10:1,ntt:21:48   # other shapes than the default list: kind:k:batch
     python tools/ntt_plans.py --child               # (internal) one build: prints a JSON line
     python tools/ntt_plans.py --pmc-child K BATCH   # (internal) the workload of one `rocprofv3 --pmc SQ_INSTS_VALU` pass
 """
@@ -17,6 +18,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 SHAPES = [("ntt", 21, 1), ("ntt", 21, 48), ("c2e", 18, 48), ("c2e", 17, 10), ("ntt", 20, 10), ("ntt", 24, 1), ("ntt", 18, 48)]
+if "--shapes" in sys.argv:
+    SHAPES = [(kind, int(k), int(batch)) for kind, k, batch in (s.split(":") for s in sys.argv[sys.argv.index("--shapes") + 1].split(","))]
 
 
 def child():
@@ -90,7 +93,8 @@ def main():
         env = dict(os.environ)
         if path:
             env["HALO2_MI355X_LIB"] = path
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True, text=True, timeout=900)
+        shapes = sys.argv[sys.argv.index("--shapes"):][:2] if "--shapes" in sys.argv else []
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + shapes, env=env, capture_output=True, text=True, timeout=900)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if r.returncode != 0 or not line:
             print(f"{tag}: FAILED rc={r.returncode} {r.stderr[-400:]}")
