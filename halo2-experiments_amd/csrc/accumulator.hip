@@ -132,58 +132,56 @@ int accumulator_witness_run(uint32_t max_bits, uint32_t acc_cols, uint32_t log_n
   const uint32_t per_thread = (n_blocks + ACC_THREADS - 1) / ACC_THREADS;
   const size_t inv_bytes = pad64((((size_t)1 << max_bits) - 1) * 32), tot_bytes = pad64(m * n_blocks * sizeof(uint64_t));
   const size_t cnt_bytes = d_over ? m * (n_blocks + 1) * sizeof(uint32_t) : 0;
-  uint8_t* ws = nullptr;
-  HM_HIP_CHECK(hipMallocAsync((void**)&ws, inv_bytes + tot_bytes + cnt_bytes, stream));
-  int rc = HM_OK;
-  hipEvent_t ev[5] = {};                                     // part_ms: events around the four launches (the call then waits for them)
-  if (part_ms)
-    for (hipEvent_t& e : ev)
-      if (rc == HM_OK && hipEventCreate(&e) != hipSuccess) rc = hm_fail(HM_ERR_HIP, "accumulator_witness: hipEventCreate failed");
-  auto mark = [&](int i) {
-    if (part_ms && rc == HM_OK && hipEventRecord(ev[i], stream) != hipSuccess) rc = hm_fail(HM_ERR_HIP, "accumulator_witness: hipEventRecord failed");
-  };
-  // a pageable source: the runtime has taken its copy when this returns
-  if (hipMemcpyAsync(ws, inverses_ext, (((size_t)1 << max_bits) - 1) * 32, hipMemcpyHostToDevice, stream) != hipSuccess)
-    rc = hm_fail(HM_ERR_HIP, "accumulator_witness: upload failed");
-  mark(0);
-  if (rc == HM_OK) {
-    AccArgs a;
-    a.values = d_values;
-    a.initial = d_initial;
-    a.inverses = (const uint32_t*)ws;
-    a.advice = d_advice;
-    a.finals = d_finals;
-    a.max_bits = max_bits;
-    a.acc_cols = acc_cols;
-    a.log_n = log_n;
-    a.rows = rows;
-    uint64_t* totals = (uint64_t*)(ws + inv_bytes);
-    uint32_t* counts = d_over ? (uint32_t*)(ws + inv_bytes + tot_bytes) : nullptr;
-    hipLaunchKernelGGL(accumulator_reduce_kernel, dim3(n_blocks, (uint32_t)m), dim3(ACC_THREADS), 0, stream, a, totals, n_blocks);
-    mark(1);
-    hipLaunchKernelGGL(accumulator_scan_kernel, dim3((uint32_t)m), dim3(ACC_THREADS), 0, stream, a, totals, n_blocks, per_thread, counts);
-    mark(2);
-    hipLaunchKernelGGL(accumulator_rows_kernel, dim3(all_blocks, (uint32_t)m), dim3(ACC_THREADS), 0, stream, a, (const uint64_t*)totals, n_blocks,
-                       counts);
-    mark(3);
-    if (counts)
-      hipLaunchKernelGGL(accumulator_count_kernel, dim3((uint32_t)m), dim3(ACC_THREADS), 0, stream, (const uint32_t*)counts, n_blocks + 1, d_over);
-    mark(4);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("accumulator_witness: ") + hipGetErrorString(e));
-  }
-  if (part_ms) {
-    if (rc == HM_OK && hipEventSynchronize(ev[4]) != hipSuccess) rc = hm_fail(HM_ERR_HIP, "accumulator_witness: hipEventSynchronize failed");
-    for (int i = 0; i < 4; ++i) {
-      float ms = 0;
-      if (rc == HM_OK && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) != hipSuccess) rc = hm_fail(HM_ERR_HIP, "accumulator_witness: hipEventElapsedTime failed");
-      part_ms[i] = ms;
+  return stream_scratch("accumulator_witness", inv_bytes + tot_bytes + cnt_bytes, stream, [&](uint8_t* ws) -> int {
+    int rc = HM_OK;
+    hipEvent_t ev[5] = {};                                     // part_ms: events around the four launches (the call then waits for them)
+    if (part_ms)
+      for (hipEvent_t& e : ev)
+        if (rc == HM_OK && hipEventCreate(&e) != hipSuccess) rc = hm_fail(HM_ERR_HIP, "accumulator_witness: hipEventCreate failed");
+    auto mark = [&](int i) {
+      if (part_ms && rc == HM_OK && hipEventRecord(ev[i], stream) != hipSuccess) rc = hm_fail(HM_ERR_HIP, "accumulator_witness: hipEventRecord failed");
+    };
+    // a pageable source: the runtime has taken its copy when this returns
+    if (hipMemcpyAsync(ws, inverses_ext, (((size_t)1 << max_bits) - 1) * 32, hipMemcpyHostToDevice, stream) != hipSuccess)
+      rc = hm_fail(HM_ERR_HIP, "accumulator_witness: upload failed");
+    mark(0);
+    if (rc == HM_OK) {
+      AccArgs a;
+      a.values = d_values;
+      a.initial = d_initial;
+      a.inverses = (const uint32_t*)ws;
+      a.advice = d_advice;
+      a.finals = d_finals;
+      a.max_bits = max_bits;
+      a.acc_cols = acc_cols;
+      a.log_n = log_n;
+      a.rows = rows;
+      uint64_t* totals = (uint64_t*)(ws + inv_bytes);
+      uint32_t* counts = d_over ? (uint32_t*)(ws + inv_bytes + tot_bytes) : nullptr;
+      hipLaunchKernelGGL(accumulator_reduce_kernel, dim3(n_blocks, (uint32_t)m), dim3(ACC_THREADS), 0, stream, a, totals, n_blocks);
+      mark(1);
+      hipLaunchKernelGGL(accumulator_scan_kernel, dim3((uint32_t)m), dim3(ACC_THREADS), 0, stream, a, totals, n_blocks, per_thread, counts);
+      mark(2);
+      hipLaunchKernelGGL(accumulator_rows_kernel, dim3(all_blocks, (uint32_t)m), dim3(ACC_THREADS), 0, stream, a, (const uint64_t*)totals, n_blocks,
+                         counts);
+      mark(3);
+      if (counts)
+        hipLaunchKernelGGL(accumulator_count_kernel, dim3((uint32_t)m), dim3(ACC_THREADS), 0, stream, (const uint32_t*)counts, n_blocks + 1, d_over);
+      mark(4);
+      if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("accumulator_witness: ") + hipGetErrorString(e));
     }
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  const hipError_t fe = hipFreeAsync(ws, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("accumulator_witness: hipFreeAsync: ") + hipGetErrorString(fe));
-  return rc;
+    if (part_ms) {
+      if (rc == HM_OK && hipEventSynchronize(ev[4]) != hipSuccess) rc = hm_fail(HM_ERR_HIP, "accumulator_witness: hipEventSynchronize failed");
+      for (int i = 0; i < 4; ++i) {
+        float ms = 0;
+        if (rc == HM_OK && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) != hipSuccess) rc = hm_fail(HM_ERR_HIP, "accumulator_witness: hipEventElapsedTime failed");
+        part_ms[i] = ms;
+      }
+      for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    }
+    return rc;
+  });
 }
 
 }  // namespace hm

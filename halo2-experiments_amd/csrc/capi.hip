@@ -1,6 +1,7 @@
 // capi.hip -- the core of the extern "C" boundary declared in include/halo2_mi355x.h: the error state and the exception barrier's
 // handler, the fault points of the test build, the device contexts, memory, copies, settings and the call counters.  The entry points
-// of each subsystem live in capi_msm.hip, capi_poly.hip, capi_g1.hip and capi_hash.hip.
+// of each subsystem live in capi_msm.hip, capi_poly.hip, capi_g1.hip and capi_hash.hip.  Per-call device scratch (aux_scope's slots,
+// stream_scratch's memory) is here too: this unit owns DeviceCtx, resets the slots in hm_shutdown, and is built with the fault points.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -58,6 +59,68 @@ void hm_fault_point(const char* point) {
   if (g_fault_after-- == 0) throw std::runtime_error(std::string("injected fault at ") + point);
 }
 #endif
+
+// ---- per-call device scratch: the stream slots behind aux_scope, the stream-ordered memory behind stream_scratch (hm_internal.h) ----
+AuxSlot* aux_acquire(DeviceCtx& ctx, hipStream_t stream) {
+  AuxSlot* pick = nullptr;
+  for (auto& s : ctx.aux)
+    if (s.used && s.stream == stream) pick = &s;        // stream order already protects its buffers
+  if (!pick)
+    for (auto& s : ctx.aux)
+      if (!s.used) { pick = &s; break; }
+  if (!pick) {
+    for (auto& s : ctx.aux)                              // a slot whose last user has finished
+      if (hipEventQuery(s.done) == hipSuccess && (!pick || s.last_use < pick->last_use)) pick = &s;
+  }
+  if (!pick) {                                           // all busy on other streams: queue behind the oldest
+    pick = &ctx.aux[0];
+    for (auto& s : ctx.aux)
+      if (s.last_use < pick->last_use) pick = &s;
+    if (hipStreamWaitEvent(stream, pick->done, 0) != hipSuccess) {
+      hm_fail(HM_ERR_HIP, "aux slot: hipStreamWaitEvent failed");
+      return nullptr;
+    }
+  }
+  if (!pick->done && hipEventCreateWithFlags(&pick->done, hipEventDisableTiming) != hipSuccess) {
+    hm_fail(HM_ERR_HIP, "aux slot: event creation failed");
+    return nullptr;
+  }
+  pick->used = true;
+  pick->stream = stream;
+  pick->last_use = ++ctx.aux_clock;
+  return pick;
+}
+
+int aux_release(DeviceCtx& ctx, AuxSlot* slot, hipStream_t stream) {
+  (void)ctx;
+  HM_HIP_CHECK(hipEventRecord(slot->done, stream));
+  return HM_OK;
+}
+
+// Every request passes this first, whatever the buffers already hold.  Test build: an armed "scratch_alloc" makes the request fail like
+// an exhausted device (as "device_malloc_oom" below).
+static bool scratch_alloc_refused() {
+  try { hm_fault_point("scratch_alloc"); } catch (const std::exception&) { return true; }      // product build: the empty inline
+  return false;
+}
+void* aux_buffer(AuxSlot& slot, AuxBuf which, size_t bytes, const char* who) {
+  DevBuf* const bufs[] = {&slot.scratch, &slot.table, &slot.args, &slot.work};
+  if (which == AuxBuf::table && bytes < HM_AUX_TABLE_MIN) bytes = HM_AUX_TABLE_MIN;
+  void* p = scratch_alloc_refused() ? nullptr : bufs[(int)which]->ensure(bytes);
+  if (!p) hm_fail(HM_ERR_HIP, std::string(who) + ": scratch allocation failed");
+  return p;
+}
+bool stream_scratch_alloc(const char* who, size_t bytes, hipStream_t stream, uint8_t** ws) {
+  *ws = nullptr;                                         // stays null for 0 bytes: nothing to free
+  const hipError_t e = scratch_alloc_refused() ? hipErrorOutOfMemory : bytes ? hipMallocAsync((void**)ws, bytes, stream) : hipSuccess;
+  if (e != hipSuccess) hm_fail(HM_ERR_HIP, std::string(who) + ": scratch allocation failed");
+  return e == hipSuccess;
+}
+int stream_scratch_free(const char* who, uint8_t* ws, hipStream_t stream, int rc) {
+  const hipError_t fe = ws ? hipFreeAsync(ws, stream) : hipSuccess;
+  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": hipFreeAsync: " + hipGetErrorString(fe));
+  return rc;
+}
 
 DeviceCtx* ctx_for_current_device() {
   int count = 0;

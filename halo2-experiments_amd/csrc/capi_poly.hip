@@ -629,8 +629,8 @@ static int quotient_partials(const char* who, DeviceCtx& ctx, uint64_t program, 
   // The transforms and the numerator below take the stream's slot again (aux_scope nests on one stream) and use its other buffers.
   return aux_scope(ctx, st, [&](AuxSlot& slot) -> int {
     // work: [the columns to transform, side by side: T x n] [those columns on the cosets: T x count x n]
-    uint8_t* work = (uint8_t*)slot.work.ensure(row * (T + T * count) + 32);
-    if (!work) return hm_fail(HM_ERR_HIP, std::string(who) + ": workspace allocation failed");
+    uint8_t* work = (uint8_t*)aux_buffer(slot, AuxBuf::work, row * (T + T * count) + 32, who);
+    if (!work) return HM_ERR_HIP;
     uint8_t* contig = work;
     uint8_t* on_cosets = contig + row * T;
     int rc = HM_OK;
@@ -733,9 +733,8 @@ int hm_quotient_by_cosets_bn256_fr_dev(uint64_t program, const void* const* d_co
   // the partials live in the stream's NTT scratch slot? no: that is the transforms' ping-pong buffer.  They get the tail of a
   // buffer of their own (AuxSlot::table is the scans' scratch: free between calls on this stream)
   return aux_scope(*ctx, st, [&](AuxSlot& slot) -> int {
-    const size_t keep = (size_t)64 * 15 * 28 * 4;             // never shrink below the fixed-base table (see poly.hip)
-    uint8_t* parts_buf = (uint8_t*)slot.table.ensure(row * count > keep ? row * count : keep);
-    if (!parts_buf) return hm_fail(HM_ERR_HIP, std::string(who) + ": workspace allocation failed");
+    uint8_t* parts_buf = (uint8_t*)aux_buffer(slot, AuxBuf::table, row * count, who);
+    if (!parts_buf) return HM_ERR_HIP;
     int rc = quotient_partials(who, *ctx, program, d_coeff_columns, d_on_cosets, n_columns, dynamic_constants, n_dynamic, log_n, omega, shifts, count,
                                parts_buf, st);
     if (rc != HM_OK) return rc;

@@ -69,23 +69,22 @@ template <class Launch>
 static int g1_codec_validating_run(const char* who, size_t n, uint64_t* first_invalid, hipStream_t stream, Launch launch) {
   *first_invalid = n;
   if (n == 0) return HM_OK;
-  void* mem = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&mem, sizeof(unsigned long long), stream));
-  unsigned long long* flag = (unsigned long long*)mem;
   unsigned long long bad = ~0ull;
-  int rc = HM_OK;
-  const hipError_t me = hipMemsetAsync(flag, 0xff, sizeof(bad), stream);
-  if (me != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": hipMemsetAsync: " + hipGetErrorString(me));
-  if (rc == HM_OK) {
-    launch(dim3((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS)), flag);
-    if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": kernel launch failed");
-  }
-  if (rc == HM_OK) {
-    const hipError_t ce = hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, stream);
-    if (ce != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": reading the flag: " + hipGetErrorString(ce));
-  }
-  const hipError_t fe = hipFreeAsync(mem, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": hipFreeAsync: " + hipGetErrorString(fe));
+  int rc = stream_scratch(who, sizeof(bad), stream, [&](uint8_t* mem) -> int {
+    unsigned long long* flag = (unsigned long long*)mem;
+    int rc = HM_OK;
+    const hipError_t me = hipMemsetAsync(flag, 0xff, sizeof(bad), stream);
+    if (me != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": hipMemsetAsync: " + hipGetErrorString(me));
+    if (rc == HM_OK) {
+      launch(dim3((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS)), flag);
+      if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": kernel launch failed");
+    }
+    if (rc == HM_OK) {
+      const hipError_t ce = hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, stream);
+      if (ce != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": reading the flag: " + hipGetErrorString(ce));
+    }
+    return rc;
+  });
   const hipError_t se = hipStreamSynchronize(stream);
   if (rc == HM_OK && se != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": " + hipGetErrorString(se));
   if (rc == HM_OK && bad < n) {

@@ -187,37 +187,34 @@ int g1_fft_run(DeviceCtx& ctx, uint32_t* d_points, uint32_t words, const uint64_
     scale.on = 1;
   }
   const size_t work_bytes = n * PT_WORDS * 4, tw_bytes = half * 32;
-  void* mem = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&mem, work_bytes + tw_bytes, stream));
-  uint32_t* work = (uint32_t*)mem;
-  uint32_t* tw = work + n * PT_WORDS;
-  const dim3 all((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS)), pairs((uint32_t)((half + ACC_THREADS - 1) / ACC_THREADS));
-  int rc = HM_OK;
-  if (half) {
-    rc = fr_powers_run(tw, half, omega_ext, stream);
-    if (rc == HM_OK) {
-      hipLaunchKernelGGL(g1_fft_twiddle_kernel, dim3((uint32_t)((half + 255) / 256)), dim3(256), 0, stream, tw, half);
-      if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: twiddle kernel launch failed");
+  return stream_scratch("g1_fft", work_bytes + tw_bytes, stream, [&](uint8_t* mem) -> int {
+    uint32_t *work = (uint32_t*)mem, *tw = work + n * PT_WORDS;
+    const dim3 all((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS)), pairs((uint32_t)((half + ACC_THREADS - 1) / ACC_THREADS));
+    int rc = HM_OK;
+    if (half) {
+      rc = fr_powers_run(tw, half, omega_ext, stream);
+      if (rc == HM_OK) {
+        hipLaunchKernelGGL(g1_fft_twiddle_kernel, dim3((uint32_t)((half + 255) / 256)), dim3(256), 0, stream, tw, half);
+        if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: twiddle kernel launch failed");
+      }
     }
-  }
-  if (rc == HM_OK) {
-    if (words == 16) hipLaunchKernelGGL(g1_fft_load_kernel<16>, all, dim3(ACC_THREADS), 0, stream, d_points, work, log_n);
-    else hipLaunchKernelGGL(g1_fft_load_kernel<24>, all, dim3(ACC_THREADS), 0, stream, d_points, work, log_n);
-    if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: load kernel launch failed");
-  }
-  for (uint32_t s = 0; rc == HM_OK && s < log_n; ++s) {
-    if (log_n - 1 - s >= 6) hipLaunchKernelGGL(g1_fft_stage_kernel<true>, pairs, dim3(ACC_THREADS), 0, stream, work, tw, log_n, s);
-    else hipLaunchKernelGGL(g1_fft_stage_kernel<false>, pairs, dim3(ACC_THREADS), 0, stream, work, tw, log_n, s);
-    if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: stage kernel launch failed");
-  }
-  if (rc == HM_OK) {
-    if (words == 16) hipLaunchKernelGGL(g1_fft_store_kernel<16>, all, dim3(ACC_THREADS), 0, stream, work, d_points, log_n, scale);
-    else hipLaunchKernelGGL(g1_fft_store_kernel<24>, all, dim3(ACC_THREADS), 0, stream, work, d_points, log_n, scale);
-    if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: store kernel launch failed");
-  }
-  const hipError_t fe = hipFreeAsync(mem, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("g1_fft: hipFreeAsync: ") + hipGetErrorString(fe));
-  return rc;
+    if (rc == HM_OK) {
+      if (words == 16) hipLaunchKernelGGL(g1_fft_load_kernel<16>, all, dim3(ACC_THREADS), 0, stream, d_points, work, log_n);
+      else hipLaunchKernelGGL(g1_fft_load_kernel<24>, all, dim3(ACC_THREADS), 0, stream, d_points, work, log_n);
+      if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: load kernel launch failed");
+    }
+    for (uint32_t s = 0; rc == HM_OK && s < log_n; ++s) {
+      if (log_n - 1 - s >= 6) hipLaunchKernelGGL(g1_fft_stage_kernel<true>, pairs, dim3(ACC_THREADS), 0, stream, work, tw, log_n, s);
+      else hipLaunchKernelGGL(g1_fft_stage_kernel<false>, pairs, dim3(ACC_THREADS), 0, stream, work, tw, log_n, s);
+      if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: stage kernel launch failed");
+    }
+    if (rc == HM_OK) {
+      if (words == 16) hipLaunchKernelGGL(g1_fft_store_kernel<16>, all, dim3(ACC_THREADS), 0, stream, work, d_points, log_n, scale);
+      else hipLaunchKernelGGL(g1_fft_store_kernel<24>, all, dim3(ACC_THREADS), 0, stream, work, d_points, log_n, scale);
+      if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "g1_fft: store kernel launch failed");
+    }
+    return rc;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -389,64 +386,60 @@ int kzg_open_all_run(DeviceCtx& ctx, const uint32_t* d_table_xy, const uint32_t*
     std::memcpy(k32s.w, v.l, 32);
   }
   const size_t work2_words = m * PT_WORDS, work1_words = n * PT_WORDS, y_words = m * 8, tw2_words = n * 8, tw1_words = (n / 2) * 8;
-  void* mem = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&mem, (work2_words + work1_words + y_words + tw2_words + tw1_words) * 4, stream));
-  uint32_t* work2 = (uint32_t*)mem;
-  uint32_t* work1 = work2 + work2_words;
-  uint32_t* y = work1 + work1_words;
-  uint32_t* tw2 = y + y_words;
-  uint32_t* tw1 = tw2 + tw2_words;
   hipEvent_t ev[8] = {};
-  int rc = HM_OK;
-  if (times) {
-    for (int i = 0; i < 8 && rc == HM_OK; ++i)
-      if (hipEventCreate(&ev[i]) != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: hipEventCreate failed");
-  }
-  // with `times` the spans of the LAST polynomial are measured: one event between the steps
-  auto mark = [&](int i, bool last) {
-    if (times && last && rc == HM_OK && hipEventRecord(ev[i], stream) != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: hipEventRecord failed");
-  };
-  if (rc == HM_OK) rc = kzg_open_twiddles(tw2, n, omega2_inv, stream);
-  if (rc == HM_OK) rc = kzg_open_twiddles(tw1, n / 2, omega1, stream);
-  const dim3 all_m64((uint32_t)((m + ACC_THREADS - 1) / ACC_THREADS)), all_n64((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS));
-  const dim3 all_m256((uint32_t)((m + 255) / 256)), all_n256((uint32_t)((n + 255) / 256));
-  for (size_t p = 0; rc == HM_OK && p < count; ++p) {
-    const bool last = p + 1 == count;
-    mark(0, last);
-    hipLaunchKernelGGL(kzg_open_arrange_coeffs_kernel, all_m256, dim3(256), 0, stream, d_coeffs + p * n * 8, y, log_n);
-    if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: arrangement kernel launch failed");
-    mark(1, last);
-    if (rc == HM_OK) {
-      NttCall call{};
-      call.log_n = log_m, call.batch = 1;
-      NttPointers ptrs;
-      ptrs.d_a = y, ptrs.omega = omega2.l;
-      rc = ntt_run(ctx, call, ptrs, stream);
+  int rc = stream_scratch("kzg_open_all", (work2_words + work1_words + y_words + tw2_words + tw1_words) * 4, stream, [&](uint8_t* mem) -> int {
+    uint32_t *work2 = (uint32_t*)mem, *work1 = work2 + work2_words, *y = work1 + work1_words;
+    uint32_t *tw2 = y + y_words, *tw1 = tw2 + tw2_words;
+    int rc = HM_OK;
+    if (times) {
+      for (int i = 0; i < 8 && rc == HM_OK; ++i)
+        if (hipEventCreate(&ev[i]) != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: hipEventCreate failed");
     }
-    mark(2, last);
-    if (rc == HM_OK) {
-      hipLaunchKernelGGL(kzg_open_load_mul_kernel, all_m64, dim3(ACC_THREADS), 0, stream, d_table_xy, (const uint32_t*)y, work2, log_m, k32s);
-      if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: load kernel launch failed");
+    // with `times` the spans of the LAST polynomial are measured: one event between the steps
+    auto mark = [&](int i, bool last) {
+      if (times && last && rc == HM_OK && hipEventRecord(ev[i], stream) != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: hipEventRecord failed");
+    };
+    if (rc == HM_OK) rc = kzg_open_twiddles(tw2, n, omega2_inv, stream);
+    if (rc == HM_OK) rc = kzg_open_twiddles(tw1, n / 2, omega1, stream);
+    const dim3 all_m64((uint32_t)((m + ACC_THREADS - 1) / ACC_THREADS)), all_n64((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS));
+    const dim3 all_m256((uint32_t)((m + 255) / 256)), all_n256((uint32_t)((n + 255) / 256));
+    for (size_t p = 0; rc == HM_OK && p < count; ++p) {
+      const bool last = p + 1 == count;
+      mark(0, last);
+      hipLaunchKernelGGL(kzg_open_arrange_coeffs_kernel, all_m256, dim3(256), 0, stream, d_coeffs + p * n * 8, y, log_n);
+      if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: arrangement kernel launch failed");
+      mark(1, last);
+      if (rc == HM_OK) {
+        NttCall call{};
+        call.log_n = log_m, call.batch = 1;
+        NttPointers ptrs;
+        ptrs.d_a = y, ptrs.omega = omega2.l;
+        rc = ntt_run(ctx, call, ptrs, stream);
+      }
+      mark(2, last);
+      if (rc == HM_OK) {
+        hipLaunchKernelGGL(kzg_open_load_mul_kernel, all_m64, dim3(ACC_THREADS), 0, stream, d_table_xy, (const uint32_t*)y, work2, log_m, k32s);
+        if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: load kernel launch failed");
+      }
+      mark(3, last);
+      if (rc == HM_OK) rc = kzg_open_stages(work2, tw2, log_m, stream);
+      mark(4, last);
+      if (rc == HM_OK) {
+        hipLaunchKernelGGL(kzg_open_truncate_kernel, all_n256, dim3(256), 0, stream, (const uint32_t*)work2, work1, log_n);
+        if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: truncate kernel launch failed");
+      }
+      mark(5, last);
+      if (rc == HM_OK) rc = kzg_open_stages(work1, tw1, log_n, stream);
+      mark(6, last);
+      if (rc == HM_OK) {
+        hipLaunchKernelGGL(g1_fft_store_kernel<16>, all_n64, dim3(ACC_THREADS), 0, stream, (const uint32_t*)work1, d_proofs_xy + p * n * 16,
+                           log_n, G1FftScale{});
+        if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: store kernel launch failed");
+      }
+      mark(7, last);
     }
-    mark(3, last);
-    if (rc == HM_OK) rc = kzg_open_stages(work2, tw2, log_m, stream);
-    mark(4, last);
-    if (rc == HM_OK) {
-      hipLaunchKernelGGL(kzg_open_truncate_kernel, all_n256, dim3(256), 0, stream, (const uint32_t*)work2, work1, log_n);
-      if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: truncate kernel launch failed");
-    }
-    mark(5, last);
-    if (rc == HM_OK) rc = kzg_open_stages(work1, tw1, log_n, stream);
-    mark(6, last);
-    if (rc == HM_OK) {
-      hipLaunchKernelGGL(g1_fft_store_kernel<16>, all_n64, dim3(ACC_THREADS), 0, stream, (const uint32_t*)work1, d_proofs_xy + p * n * 16,
-                         log_n, G1FftScale{});
-      if (hipGetLastError() != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: store kernel launch failed");
-    }
-    mark(7, last);
-  }
-  const hipError_t fe = hipFreeAsync(mem, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("kzg_open_all: hipFreeAsync: ") + hipGetErrorString(fe));
+    return rc;
+  });
   if (times) {
     if (rc == HM_OK && hipEventSynchronize(ev[7]) != hipSuccess) rc = hm_fail(HM_ERR_HIP, "kzg_open_all: hipEventSynchronize failed");
     for (int i = 0; i < 7 && rc == HM_OK; ++i) {

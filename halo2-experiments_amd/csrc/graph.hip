@@ -331,10 +331,9 @@ int graph_run(DeviceCtx& ctx, GraphProgram& g, const GraphCall& c, hipStream_t s
   }
   for (size_t i = 0; i < (c.kind == GRAPH_PROOFS ? c.units : 1) * c.n_dyn; ++i) host::fr_to_internal9(host::fr_load(c.dyn_ext + 4 * i), dyn + 9 * i);
   return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
-    uint32_t* buf = (uint32_t*)slot.scratch.ensure(p.scratch_bytes);
-    if (!buf) return hm_fail(HM_ERR_HIP, "graph: scratch allocation failed");
-    uint8_t* d_block = (uint8_t*)slot.args.ensure(p.args_bytes);
-    if (!d_block) return hm_fail(HM_ERR_HIP, "graph: argument buffer allocation failed");
+    uint32_t* buf = (uint32_t*)aux_buffer(slot, AuxBuf::scratch, p.scratch_bytes, "graph");
+    uint8_t* d_block = buf ? (uint8_t*)aux_buffer(slot, AuxBuf::args, p.args_bytes, "graph") : nullptr;
+    if (!d_block) return HM_ERR_HIP;
     // pageable source: the runtime has taken its copy of `block` when this returns; the copy itself is ordered on `stream`
     // ahead of the launch and behind the previous launch that read the buffer
     HM_HIP_CHECK(hipMemcpyAsync(d_block, block.data(), p.args_bytes, hipMemcpyHostToDevice, stream));

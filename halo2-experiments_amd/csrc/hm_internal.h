@@ -239,6 +239,9 @@ struct AuxSlot {
   uint64_t last_use = 0;
 };
 constexpr int HM_AUX_SLOTS = 4;
+// never shrink `table` below the fixed-base table (64 windows x 15 multiples x PT_WORDS u32): the floor of every request for it
+constexpr size_t HM_AUX_TABLE_MIN = (size_t)64 * 15 * 28 * 4;
+enum class AuxBuf { scratch, table, args, work };
 
 struct GraphVariant {       // the program lowered for one column format (graph.hip: graph_lower)
   void* d_calcs = nullptr;
@@ -334,6 +337,20 @@ int aux_scope(DeviceCtx& ctx, hipStream_t stream, Body&& body) {
   try { rc = body(*slot); } catch (...) { (void)aux_release(ctx, slot, stream); throw; }
   const int released = aux_release(ctx, slot, stream);
   return rc != HM_OK ? rc : released;
+}
+// The slot's buffer of at least `bytes` (`table`: HM_AUX_TABLE_MIN); null, and "<who>: scratch allocation failed", when it cannot be had.
+void* aux_buffer(AuxSlot& slot, AuxBuf which, size_t bytes, const char* who);
+// The other way to per-call scratch (there are these two): stream-ordered memory of `bytes` (0: none) for body(uint8_t* ws), freed behind
+// what the body enqueued, whatever it returns or throws.  The body's code, or the free's failure when the body succeeded.
+bool stream_scratch_alloc(const char* who, size_t bytes, hipStream_t stream, uint8_t** ws);      // false: the message is set
+int stream_scratch_free(const char* who, uint8_t* ws, hipStream_t stream, int rc);
+template <class Body>
+int stream_scratch(const char* who, size_t bytes, hipStream_t stream, Body&& body) {
+  uint8_t* ws = nullptr;
+  if (!stream_scratch_alloc(who, bytes, stream, &ws)) return HM_ERR_HIP;
+  int rc;
+  try { rc = body(ws); } catch (...) { (void)stream_scratch_free(who, ws, stream, HM_ERR_INTERNAL); throw; }
+  return stream_scratch_free(who, ws, stream, rc);
 }
 
 DeviceCtx* ctx_for_current_device();     // capi.hip; null (and the message set) without a gfx950 device

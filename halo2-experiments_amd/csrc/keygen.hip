@@ -102,12 +102,9 @@ int perm_assemble_run(const uint32_t* d_copies, size_t m, uint32_t columns, uint
   if (m == 0) return HM_OK;
   uint64_t n_pow2 = 2;
   while (n_pow2 < 2 * (uint64_t)m) n_pow2 <<= 1;
-  void* keys = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&keys, (size_t)n_pow2 * 8, stream));
-  int rc = perm_assemble_launch(d_copies, m, cells, d_sigma_cells, d_dropped, (uint64_t*)keys, n_pow2, stream);
-  const hipError_t fe = hipFreeAsync(keys, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("permutation_assemble: hipFreeAsync: ") + hipGetErrorString(fe));
-  return rc;
+  return stream_scratch("permutation_assemble", (size_t)n_pow2 * 8, stream, [&](uint8_t* keys) -> int {
+    return perm_assemble_launch(d_copies, m, cells, d_sigma_cells, d_dropped, (uint64_t*)keys, n_pow2, stream);
+  });
 }
 
 }  // namespace hm

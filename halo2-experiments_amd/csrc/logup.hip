@@ -167,7 +167,7 @@ __global__ __launch_bounds__(LU_THREADS) void lu_write_general_kernel(const LuAr
 // 1 <= rows < 2^31, every c >= 1 and c * rows < 2^32, no null pointer: checked by the caller
 int logup_multiplicities_run(const void* const* d_tables, const void* const* d_inputs, const uint32_t* input_counts, size_t count, uint64_t rows,
                              void* const* d_m, int* missing, hipStream_t stream) {
-  const char* who = "logup multiplicities: ";
+  const char* who = "logup multiplicities";
   std::vector<LuArg> h_args(count);
   size_t total_inputs = 0;
   for (size_t a = 0; a < count; ++a) {
@@ -181,31 +181,28 @@ int logup_multiplicities_run(const void* const* d_tables, const void* const* d_i
   }
   const size_t args_bytes = pad64(count * sizeof(LuArg)), in_bytes = pad64(total_inputs * sizeof(void*)), flag_bytes = pad64(count * 4);
   const size_t kb_bytes = pad64((size_t)LU_KB_SLOTS * LU_KB_STRIDE * 4);
-  uint8_t* head = nullptr;
-  HM_HIP_CHECK(hipMallocAsync((void**)&head, args_bytes + in_bytes + flag_bytes + kb_bytes, stream));
-  LuArg* args = (LuArg*)head;
-  const uint32_t* const* inputs = (const uint32_t* const*)(head + args_bytes);
-  uint32_t *flags = (uint32_t*)(head + args_bytes + in_bytes), *kbits = (uint32_t*)(head + args_bytes + in_bytes + flag_bytes);
-  uint8_t* work = nullptr;
-  int rc = HM_OK;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && rc == HM_OK) rc = hm_fail(HM_ERR_HIP, std::string(who) + what + ": " + hipGetErrorString(e));
-    return e != hipSuccess;
-  };
   const uint32_t rb = (uint32_t)((rows + LU_THREADS - 1) / LU_THREADS);
   std::vector<uint32_t> h_flags(count, 0u);
-  do {
+  int rc = HM_OK;                                                    // the first failure, with its message
+  auto fail = [&](hipError_t e, const char* what) {
+    if (e != hipSuccess && rc == HM_OK) rc = hm_fail(HM_ERR_HIP, std::string(who) + ": " + what + ": " + hipGetErrorString(e));
+    return e != hipSuccess;
+  };
+  const int scope_rc = stream_scratch(who, args_bytes + in_bytes + flag_bytes + kb_bytes, stream, [&](uint8_t* head) -> int {
+    LuArg* args = (LuArg*)head;
+    const uint32_t* const* inputs = (const uint32_t* const*)(head + args_bytes);
+    uint32_t *flags = (uint32_t*)(head + args_bytes + in_bytes), *kbits = (uint32_t*)(head + args_bytes + in_bytes + flag_bytes);
     // pageable sources: the runtime has taken its copies when these return
-    if (fail(hipMemcpyAsync(args, h_args.data(), count * sizeof(LuArg), hipMemcpyHostToDevice, stream), "upload")) break;
-    if (fail(hipMemcpyAsync((void*)inputs, d_inputs, total_inputs * sizeof(void*), hipMemcpyHostToDevice, stream), "upload")) break;
-    if (fail(hipMemsetAsync(flags, 0, flag_bytes + kb_bytes, stream), "memset")) break;
+    if (fail(hipMemcpyAsync(args, h_args.data(), count * sizeof(LuArg), hipMemcpyHostToDevice, stream), "upload")) return rc;
+    if (fail(hipMemcpyAsync((void*)inputs, d_inputs, total_inputs * sizeof(void*), hipMemcpyHostToDevice, stream), "upload")) return rc;
+    if (fail(hipMemsetAsync(flags, 0, flag_bytes + kb_bytes, stream), "memset")) return rc;
     for (size_t a0 = 0; a0 < count; a0 += 32768) {
       const uint32_t cnt = (uint32_t)(count - a0 < 32768 ? count - a0 : 32768);
       hipLaunchKernelGGL(lu_bits_kernel, dim3(rb, cnt), dim3(LU_THREADS), 0, stream, (const LuArg*)(args + a0), rows, kbits);
     }
     uint32_t h_bits[LU_KB_SLOTS * LU_KB_STRIDE];
-    if (fail(hipMemcpyAsync(h_bits, kbits, sizeof h_bits, hipMemcpyDeviceToHost, stream), "key bits")) break;
-    if (fail(hipStreamSynchronize(stream), "key bits")) break;
+    if (fail(hipMemcpyAsync(h_bits, kbits, sizeof h_bits, hipMemcpyDeviceToHost, stream), "key bits")) return rc;
+    if (fail(hipStreamSynchronize(stream), "key bits")) return rc;
     uint32_t lo_or = 0, hi_or = 0;
     for (uint32_t s = 0; s < LU_KB_SLOTS; ++s) {
       lo_or |= h_bits[s * LU_KB_STRIDE];
@@ -213,61 +210,60 @@ int logup_multiplicities_run(const void* const* d_tables, const void* const* d_i
     }
     uint32_t need = 1;
     while (need < 32 && (lo_or >> need) != 0) ++need;
+    int work_rc;
     if (hi_or == 0 && need <= LU_COUNT_BITS) {
       const uint32_t nbins = 1u << need;
       const size_t per_arg = (size_t)2 * nbins * 4;
       size_t chunk = LU_BIN_BUDGET / per_arg;                  // >= 32 at 2^20 bins
       if (chunk > 32768) chunk = 32768;
       if (chunk > count) chunk = count;
-      if (fail(hipMallocAsync((void**)&work, chunk * per_arg, stream), "bins")) break;
-      uint32_t* bins = (uint32_t*)work;
-      bool stop = false;
-      for (size_t a0 = 0; a0 < count && !stop; a0 += chunk) {
-        const uint32_t cnt = (uint32_t)(count - a0 < chunk ? count - a0 : chunk);
-        for (uint32_t a = 0; a < cnt && !stop; ++a) {             // the counts to 0, the first rows to LU_NO_ROW
-          stop = fail(hipMemsetAsync(bins + (size_t)2 * a * nbins, 0, (size_t)nbins * 4, stream), "memset") ||
-                 fail(hipMemsetAsync(bins + ((size_t)2 * a + 1) * nbins, 0xFF, (size_t)nbins * 4, stream), "memset");
+      work_rc = stream_scratch(who, chunk * per_arg, stream, [&](uint8_t* work) -> int {
+        uint32_t* bins = (uint32_t*)work;
+        for (size_t a0 = 0; a0 < count; a0 += chunk) {
+          const uint32_t cnt = (uint32_t)(count - a0 < chunk ? count - a0 : chunk);
+          for (uint32_t a = 0; a < cnt; ++a)                        // the counts to 0, the first rows to LU_NO_ROW
+            if (fail(hipMemsetAsync(bins + (size_t)2 * a * nbins, 0, (size_t)nbins * 4, stream), "memset") ||
+                fail(hipMemsetAsync(bins + ((size_t)2 * a + 1) * nbins, 0xFF, (size_t)nbins * 4, stream), "memset"))
+              return rc;
+          const LuArg* part = args + a0;
+          hipLaunchKernelGGL(lu_first_kernel, dim3(rb, cnt), dim3(LU_THREADS), 0, stream, part, rows, nbins, bins);
+          hipLaunchKernelGGL(lu_count_kernel, dim3(rb, cnt), dim3(LU_THREADS), 0, stream, part, inputs, rows, nbins, bins, flags + a0);
+          hipLaunchKernelGGL(lu_write_small_kernel, dim3(rb, cnt), dim3(LU_THREADS), 0, stream, part, rows, nbins, (const uint32_t*)bins, to_mont);
         }
-        if (stop) break;
-        const LuArg* part = args + a0;
-        hipLaunchKernelGGL(lu_first_kernel, dim3(rb, cnt), dim3(LU_THREADS), 0, stream, part, rows, nbins, bins);
-        hipLaunchKernelGGL(lu_count_kernel, dim3(rb, cnt), dim3(LU_THREADS), 0, stream, part, inputs, rows, nbins, bins, flags + a0);
-        hipLaunchKernelGGL(lu_write_small_kernel, dim3(rb, cnt), dim3(LU_THREADS), 0, stream, part, rows, nbins, (const uint32_t*)bins, to_mont);
-      }
-      if (stop) break;
+        return HM_OK;
+      });
     } else {
-      if (rows > ((uint64_t)1 << 26)) {
-        rc = hm_fail(HM_ERR_BAD_ARG, std::string(who) + "a table with keys of 2^" + std::to_string(LU_COUNT_BITS) + " and above takes at most 2^26 rows");
-        break;
-      }
+      if (rows > ((uint64_t)1 << 26))
+        return hm_fail(HM_ERR_BAD_ARG, std::string(who) + ": a table with keys of 2^" + std::to_string(LU_COUNT_BITS) + " and above takes at most 2^26 rows");
       uint64_t n2 = 1;
       while (n2 < rows) n2 <<= 1;
       const size_t key_bytes = pad64((size_t)n2 * 32), row_bytes = pad64((size_t)n2 * 4), cnt_bytes = pad64((size_t)rows * 4);
-      if (fail(hipMallocAsync((void**)&work, key_bytes + row_bytes + cnt_bytes, stream), "records")) break;
-      uint32_t *keys = (uint32_t*)work, *srows = (uint32_t*)(work + key_bytes), *counters = (uint32_t*)(work + key_bytes + row_bytes);
-      for (size_t a = 0; a < count && rc == HM_OK; ++a) {
-        rc = fr_sort_records_run(h_args[a].table, rows, n2, keys, srows, nullptr, stream);
-        if (rc != HM_OK || fail(hipMemsetAsync(counters, 0, (size_t)rows * 4, stream), "memset")) break;
-        hipLaunchKernelGGL(lu_search_kernel, dim3(rb), dim3(LU_THREADS), 0, stream, (const LuArg*)(args + a), inputs, rows, (const uint32_t*)keys,
-                           (const uint32_t*)srows, counters, flags + a);
-        hipLaunchKernelGGL(lu_write_general_kernel, dim3(rb), dim3(LU_THREADS), 0, stream, (const LuArg*)(args + a), rows,
-                           (const uint32_t*)counters, to_mont);
-      }
-      if (rc != HM_OK) break;
+      work_rc = stream_scratch(who, key_bytes + row_bytes + cnt_bytes, stream, [&](uint8_t* work) -> int {
+        uint32_t *keys = (uint32_t*)work, *srows = (uint32_t*)(work + key_bytes), *counters = (uint32_t*)(work + key_bytes + row_bytes);
+        for (size_t a = 0; a < count; ++a) {
+          if (const int src = fr_sort_records_run(h_args[a].table, rows, n2, keys, srows, nullptr, stream)) return src;
+          if (fail(hipMemsetAsync(counters, 0, (size_t)rows * 4, stream), "memset")) return rc;
+          hipLaunchKernelGGL(lu_search_kernel, dim3(rb), dim3(LU_THREADS), 0, stream, (const LuArg*)(args + a), inputs, rows, (const uint32_t*)keys,
+                             (const uint32_t*)srows, counters, flags + a);
+          hipLaunchKernelGGL(lu_write_general_kernel, dim3(rb), dim3(LU_THREADS), 0, stream, (const LuArg*)(args + a), rows,
+                             (const uint32_t*)counters, to_mont);
+        }
+        return HM_OK;
+      });
     }
-    if (fail(hipGetLastError(), "launch")) break;
-    if (fail(hipMemcpyAsync(h_flags.data(), flags, count * 4, hipMemcpyDeviceToHost, stream), "flags")) break;
-    if (fail(hipStreamSynchronize(stream), "flags")) break;
-  } while (false);
-  if (work) (void)fail(hipFreeAsync(work, stream), "hipFreeAsync");
-  (void)fail(hipFreeAsync(head, stream), "hipFreeAsync");
-  if (rc != HM_OK) return rc;
+    if (work_rc != HM_OK) return work_rc;
+    if (fail(hipGetLastError(), "launch")) return rc;
+    if (fail(hipMemcpyAsync(h_flags.data(), flags, count * 4, hipMemcpyDeviceToHost, stream), "flags")) return rc;
+    (void)fail(hipStreamSynchronize(stream), "flags");
+    return rc;
+  });
+  if (scope_rc != HM_OK) return scope_rc;
   bool any = false;
   for (size_t a = 0; a < count; ++a) {
     if (missing) missing[a] = h_flags[a] ? 1 : 0;
     any = any || h_flags[a] != 0;
   }
-  if (any) return hm_fail(HM_ERR_NOT_FOUND, std::string(who) + "an input value is missing from the table (ConstraintSystemFailure)");
+  if (any) return hm_fail(HM_ERR_NOT_FOUND, std::string(who) + ": an input value is missing from the table (ConstraintSystemFailure)");
   return HM_OK;
 }
 
@@ -357,25 +353,23 @@ int fr_grand_sum_batch_run(const void* const* d_terms, uint64_t n, void* const* 
   const uint32_t n_blocks = (uint32_t)((n + LU_THREADS - 1) / LU_THREADS);
   const uint32_t per_thread = (n_blocks + LU_THREADS - 1) / LU_THREADS;
   const size_t ptr_bytes = pad64(count * sizeof(void*)), tot_bytes = pad64(count * (size_t)n_blocks * 32);
-  uint8_t* ws = nullptr;
-  HM_HIP_CHECK(hipMallocAsync((void**)&ws, 2 * ptr_bytes + tot_bytes, stream));
-  const uint32_t* const* terms = (const uint32_t* const*)ws;
-  uint32_t* const* out = (uint32_t* const*)(ws + ptr_bytes);
-  uint32_t* totals = (uint32_t*)(ws + 2 * ptr_bytes);
-  int rc = HM_OK;
-  // pageable sources: the runtime has taken its copies when these return
-  if (hipMemcpyAsync((void*)terms, d_terms, count * sizeof(void*), hipMemcpyHostToDevice, stream) != hipSuccess ||
-      hipMemcpyAsync((void*)out, d_out, count * sizeof(void*), hipMemcpyHostToDevice, stream) != hipSuccess)
-    rc = hm_fail(HM_ERR_HIP, "grand sum: upload failed");
-  if (rc == HM_OK) {
-    hipLaunchKernelGGL(gs_reduce_kernel, dim3(n_blocks, (uint32_t)count), dim3(LU_THREADS), 0, stream, terms, n, totals, n_blocks);
-    hipLaunchKernelGGL(gs_scan_kernel, dim3((uint32_t)count), dim3(LU_THREADS), 0, stream, totals, n_blocks, per_thread);
-    hipLaunchKernelGGL(gs_rows_kernel, dim3(n_blocks, (uint32_t)count), dim3(LU_THREADS), 0, stream, terms, n, (const uint32_t*)totals, n_blocks, out);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("grand sum: ") + hipGetErrorString(e));
-  }
-  const hipError_t fe = hipFreeAsync(ws, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("grand sum: hipFreeAsync: ") + hipGetErrorString(fe));
-  return rc;
+  return stream_scratch("grand sum", 2 * ptr_bytes + tot_bytes, stream, [&](uint8_t* ws) -> int {
+    const uint32_t* const* terms = (const uint32_t* const*)ws;
+    uint32_t* const* out = (uint32_t* const*)(ws + ptr_bytes);
+    uint32_t* totals = (uint32_t*)(ws + 2 * ptr_bytes);
+    int rc = HM_OK;
+    // pageable sources: the runtime has taken its copies when these return
+    if (hipMemcpyAsync((void*)terms, d_terms, count * sizeof(void*), hipMemcpyHostToDevice, stream) != hipSuccess ||
+        hipMemcpyAsync((void*)out, d_out, count * sizeof(void*), hipMemcpyHostToDevice, stream) != hipSuccess)
+      rc = hm_fail(HM_ERR_HIP, "grand sum: upload failed");
+    if (rc == HM_OK) {
+      hipLaunchKernelGGL(gs_reduce_kernel, dim3(n_blocks, (uint32_t)count), dim3(LU_THREADS), 0, stream, terms, n, totals, n_blocks);
+      hipLaunchKernelGGL(gs_scan_kernel, dim3((uint32_t)count), dim3(LU_THREADS), 0, stream, totals, n_blocks, per_thread);
+      hipLaunchKernelGGL(gs_rows_kernel, dim3(n_blocks, (uint32_t)count), dim3(LU_THREADS), 0, stream, terms, n, (const uint32_t*)totals, n_blocks, out);
+      if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("grand sum: ") + hipGetErrorString(e));
+    }
+    return rc;
+  });
 }
 
 }  // namespace hm

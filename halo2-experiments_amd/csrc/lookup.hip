@@ -447,6 +447,14 @@ static int lk_compact(const uint32_t* d_flags, uint64_t n, uint64_t stride, uint
   return HM_OK;
 }
 
+static int lk_attr_once(DeviceCtx& ctx) {
+  if (ctx.lookup_attr_set) return HM_OK;
+  HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(lk_sort_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)(8 * LK_TILE * 4)));
+  ctx.lookup_attr_set = true;                                      // lk_sort_tile_kernel's dynamic LDS is allowed once per context
+  return HM_OK;
+}
+
 // the keys of ONE column, converted and sorted with the kernels above, for the witness checker's binary search (mock.hip)
 size_t lookup_sorted_keys_bytes(uint64_t live) {
   uint64_t n2 = 1;
@@ -457,11 +465,7 @@ int lookup_sorted_keys_run(DeviceCtx& ctx, const uint32_t* d_values, uint64_t li
   if (live == 0 || live >= ((uint64_t)1 << 31)) return hm_fail(HM_ERR_BAD_ARG, "lookup keys: need 1 <= rows < 2^31");
   uint64_t n2 = 1;
   while (n2 < live) n2 <<= 1;
-  if (!ctx.lookup_attr_set) {
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(lk_sort_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(8 * LK_TILE * 4)));
-    ctx.lookup_attr_set = true;
-  }
+  if (const int rc = lk_attr_once(ctx)) return rc;
   uint32_t* keys = (uint32_t*)d_ws;
   uint32_t* kbits = (uint32_t*)(d_ws + (((size_t)n2 * 32 + 255) & ~(size_t)255));      // written by the conversion, not read here
   LkFr to_canon;
@@ -489,13 +493,7 @@ int lookup_permute_run(DeviceCtx& ctx, const void* const* d_inputs, const void* 
   if (rows >= ((uint64_t)1 << 31)) return hm_fail(HM_ERR_BAD_ARG, "lookup permute: too many rows");
   uint64_t n2 = 1;
   while (n2 < rows) n2 <<= 1;
-  if (!ctx.lookup_attr_set) {
-    HM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(lk_sort_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(8 * LK_TILE * 4)));
-    ctx.lookup_attr_set = true;
-  }
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
+  if (const int rc = lk_attr_once(ctx)) return rc;
   const uint32_t blocks = (uint32_t)((rows + SC_BLOCK - 1) / SC_BLOCK);
   const uint32_t P = (uint32_t)(pairs < (size_t)LK_MAX_PAIRS ? pairs : (size_t)LK_MAX_PAIRS);      // pairs per chain
   auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -510,79 +508,81 @@ int lookup_permute_run(DeviceCtx& ctx, const void* const* d_inputs, const void* 
   static const bool count_sort_on = [] { const char* v = std::getenv("HALO2_MI355X_LOOKUP_COUNT_SORT"); return !(v && *v == '0'); }();   // A/B
   const bool may_count = count_sort_on && n2 > 4 * (uint64_t)LK_TILE;
   const size_t o_counters = carve(may_count ? (size_t)2 * P * ((size_t)4 << LK_COUNT_BITS) : 4);
-  uint8_t* ws = (uint8_t*)slot->scratch.ensure(off);
-  if (!ws) return hm_fail(HM_ERR_HIP, "lookup permute: scratch allocation failed");
-  uint32_t *keys = (uint32_t*)(ws + o_keys), *rep = (uint32_t*)(ws + o_rep), *used = (uint32_t*)(ws + o_used);
-  uint32_t *rank = (uint32_t*)(ws + o_rank), *left = (uint32_t*)(ws + o_left), *reppos = (uint32_t*)(ws + o_reppos);
-  uint32_t *sums = (uint32_t*)(ws + o_sums), *small = (uint32_t*)(ws + o_small), *kbits = (uint32_t*)(ws + o_kbits);
-  uint32_t* counters = (uint32_t*)(ws + o_counters);
-  // the raw words are the internal form of v / 32; times the internal form of 32 * 2^-256 (the integer 32 ... see
-  // msm_s_digits_kernel) they become the canonical integer v (as Fr::to_repr); and back with 2^256
-  LkFr to_canon, to_mont;
-  {
-    const host::Fr4 one_int = {{1, 0, 0, 0}};                       // the integer 1 read as Montgomery words = 2^-256
-    host::fr_to_internal9(one_int, to_canon.l);
-    const host::Fr4 r2 = {{0x1bb8e645ae216da7ULL, 0x53fe3ab1e35c59e3ULL, 0x8c49833d53bb8085ULL, 0x0216d0b17f4e44a5ULL}};   // 2^512 mod r as words = the element 2^256
-    host::fr_to_internal9(r2, to_mont.l);
-  }
-  int result = HM_OK;
-  for (size_t p0 = 0; p0 < pairs; p0 += P) {
-    const uint32_t cnt = (uint32_t)(pairs - p0 < (size_t)P ? pairs - p0 : (size_t)P);
-    LkPtrs ptr;
-    std::memset(&ptr, 0, sizeof ptr);
-    for (uint32_t p = 0; p < cnt; ++p) {
-      ptr.in[2 * p] = (const uint32_t*)d_inputs[p0 + p];
-      ptr.in[2 * p + 1] = (const uint32_t*)d_tables[p0 + p];
-      ptr.out[2 * p] = (uint32_t*)d_out_inputs[p0 + p];
-      ptr.out[2 * p + 1] = (uint32_t*)d_out_tables[p0 + p];
+  const int verdict = aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
+    uint8_t* ws = (uint8_t*)aux_buffer(slot, AuxBuf::scratch, off, "lookup permute");
+    if (!ws) return HM_ERR_HIP;
+    uint32_t *keys = (uint32_t*)(ws + o_keys), *rep = (uint32_t*)(ws + o_rep), *used = (uint32_t*)(ws + o_used);
+    uint32_t *rank = (uint32_t*)(ws + o_rank), *left = (uint32_t*)(ws + o_left), *reppos = (uint32_t*)(ws + o_reppos);
+    uint32_t *sums = (uint32_t*)(ws + o_sums), *small = (uint32_t*)(ws + o_small), *kbits = (uint32_t*)(ws + o_kbits);
+    uint32_t* counters = (uint32_t*)(ws + o_counters);
+    // the raw words are the internal form of v / 32; times the internal form of 32 * 2^-256 (the integer 32 ... see
+    // msm_s_digits_kernel) they become the canonical integer v (as Fr::to_repr); and back with 2^256
+    LkFr to_canon, to_mont;
+    {
+      const host::Fr4 one_int = {{1, 0, 0, 0}};                       // the integer 1 read as Montgomery words = 2^-256
+      host::fr_to_internal9(one_int, to_canon.l);
+      const host::Fr4 r2 = {{0x1bb8e645ae216da7ULL, 0x53fe3ab1e35c59e3ULL, 0x8c49833d53bb8085ULL, 0x0216d0b17f4e44a5ULL}};   // 2^512 mod r as words = the element 2^256
+      host::fr_to_internal9(r2, to_mont.l);
     }
-    HM_HIP_CHECK(hipMemsetAsync(used, 0, (size_t)cnt * stride * 4, stream));
-    HM_HIP_CHECK(hipMemsetAsync(small, 0, (size_t)LK_MAX_PAIRS * 16, stream));
-    const uint32_t cb = (uint32_t)((n2 + LK_THREADS - 1) / LK_THREADS), rb = (uint32_t)((rows + LK_THREADS - 1) / LK_THREADS);
-    HM_HIP_CHECK(hipMemsetAsync(kbits, 0, LK_KB_WORDS * 4, stream));
-    hipLaunchKernelGGL(lk_convert_kernel, dim3(cb, 2 * cnt), dim3(LK_THREADS), 0, stream, ptr, keys, pitch, rows, n2, to_canon, kbits);
-    uint32_t small_bits = 0;                                       // != 0: every live key of the chain is below 2^small_bits
-    if (may_count) {                                               // (one small copy and a wait: the call synchronises at its end anyway)
-      static thread_local std::vector<uint32_t> h_bits_v(LK_KB_WORDS);
-      uint32_t* h_bits = h_bits_v.data();
-      HM_HIP_CHECK(hipMemcpyAsync(h_bits, kbits, LK_KB_WORDS * 4, hipMemcpyDeviceToHost, stream));
+    int result = HM_OK;
+    for (size_t p0 = 0; p0 < pairs; p0 += P) {
+      const uint32_t cnt = (uint32_t)(pairs - p0 < (size_t)P ? pairs - p0 : (size_t)P);
+      LkPtrs ptr;
+      std::memset(&ptr, 0, sizeof ptr);
+      for (uint32_t p = 0; p < cnt; ++p) {
+        ptr.in[2 * p] = (const uint32_t*)d_inputs[p0 + p];
+        ptr.in[2 * p + 1] = (const uint32_t*)d_tables[p0 + p];
+        ptr.out[2 * p] = (uint32_t*)d_out_inputs[p0 + p];
+        ptr.out[2 * p + 1] = (uint32_t*)d_out_tables[p0 + p];
+      }
+      HM_HIP_CHECK(hipMemsetAsync(used, 0, (size_t)cnt * stride * 4, stream));
+      HM_HIP_CHECK(hipMemsetAsync(small, 0, (size_t)LK_MAX_PAIRS * 16, stream));
+      const uint32_t cb = (uint32_t)((n2 + LK_THREADS - 1) / LK_THREADS), rb = (uint32_t)((rows + LK_THREADS - 1) / LK_THREADS);
+      HM_HIP_CHECK(hipMemsetAsync(kbits, 0, LK_KB_WORDS * 4, stream));
+      hipLaunchKernelGGL(lk_convert_kernel, dim3(cb, 2 * cnt), dim3(LK_THREADS), 0, stream, ptr, keys, pitch, rows, n2, to_canon, kbits);
+      uint32_t small_bits = 0;                                       // != 0: every live key of the chain is below 2^small_bits
+      if (may_count) {                                               // (one small copy and a wait: the call synchronises at its end anyway)
+        static thread_local std::vector<uint32_t> h_bits_v(LK_KB_WORDS);
+        uint32_t* h_bits = h_bits_v.data();
+        HM_HIP_CHECK(hipMemcpyAsync(h_bits, kbits, LK_KB_WORDS * 4, hipMemcpyDeviceToHost, stream));
+        HM_HIP_CHECK(hipStreamSynchronize(stream));
+        uint32_t lo_or = 0, hi_or = 0;
+        for (uint32_t a = 0; a < 2 * cnt; ++a)
+          for (uint32_t sl = 0; sl < LK_KB_SLOTS; ++sl) {
+            lo_or |= h_bits[((size_t)a * LK_KB_SLOTS + sl) * LK_KB_STRIDE];
+            hi_or |= h_bits[((size_t)a * LK_KB_SLOTS + sl) * LK_KB_STRIDE + 1];
+          }
+        uint32_t need = 1;
+        while (need < 32 && (lo_or >> need) != 0) ++need;
+        if (hi_or == 0 && need <= LK_COUNT_BITS) small_bits = need;
+      }
+      int rc = small_bits ? lk_sort_small(keys, rows, n2, 2 * cnt, pitch, small_bits, counters, stream)
+                          : lk_sort(keys, n2, 2 * cnt, pitch, stream);            // every column of the chain side by side
+      if (rc != HM_OK) return rc;
+      hipLaunchKernelGGL(lk_mark_kernel, dim3(rb, cnt), dim3(LK_THREADS), 0, stream, (const uint32_t*)keys, pitch, rows, stride, rep, used, small);
+      rc = lk_compact(rep, rows, stride, cnt, 0, sums, small, 0, rank, reppos, stream);
+      if (rc == HM_OK) rc = lk_compact(used, rows, stride, cnt, 1, sums + (size_t)P * blocks, small, 1, nullptr, left, stream);
+      if (rc != HM_OK) return rc;
+      hipLaunchKernelGGL(lk_fill_kernel, dim3(rb, cnt), dim3(LK_THREADS), 0, stream, (const uint32_t*)keys, pitch, rows, stride, (const uint32_t*)rep,
+                         (const uint32_t*)rank, (const uint32_t*)left, small, to_mont, ptr);
+      HM_HIP_CHECK(hipGetLastError());
+      uint32_t h_small[4 * LK_MAX_PAIRS];
+      HM_HIP_CHECK(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, stream));
       HM_HIP_CHECK(hipStreamSynchronize(stream));
-      uint32_t lo_or = 0, hi_or = 0;
-      for (uint32_t a = 0; a < 2 * cnt; ++a)
-        for (uint32_t sl = 0; sl < LK_KB_SLOTS; ++sl) {
-          lo_or |= h_bits[((size_t)a * LK_KB_SLOTS + sl) * LK_KB_STRIDE];
-          hi_or |= h_bits[((size_t)a * LK_KB_SLOTS + sl) * LK_KB_STRIDE + 1];
+      for (uint32_t p = 0; p < cnt; ++p) {
+        if (h_small[4 * p + 2]) {
+          if (missing) missing[p0 + p] = 1;
+          if (result == HM_OK) result = HM_ERR_NOT_FOUND;
+        } else if (h_small[4 * p + 3] && result == HM_OK) {
+          result = HM_ERR_INTERNAL;
         }
-      uint32_t need = 1;
-      while (need < 32 && (lo_or >> need) != 0) ++need;
-      if (hi_or == 0 && need <= LK_COUNT_BITS) small_bits = need;
-    }
-    int rc = small_bits ? lk_sort_small(keys, rows, n2, 2 * cnt, pitch, small_bits, counters, stream)
-                        : lk_sort(keys, n2, 2 * cnt, pitch, stream);            // every column of the chain side by side
-    if (rc != HM_OK) return rc;
-    hipLaunchKernelGGL(lk_mark_kernel, dim3(rb, cnt), dim3(LK_THREADS), 0, stream, (const uint32_t*)keys, pitch, rows, stride, rep, used, small);
-    rc = lk_compact(rep, rows, stride, cnt, 0, sums, small, 0, rank, reppos, stream);
-    if (rc == HM_OK) rc = lk_compact(used, rows, stride, cnt, 1, sums + (size_t)P * blocks, small, 1, nullptr, left, stream);
-    if (rc != HM_OK) return rc;
-    hipLaunchKernelGGL(lk_fill_kernel, dim3(rb, cnt), dim3(LK_THREADS), 0, stream, (const uint32_t*)keys, pitch, rows, stride, (const uint32_t*)rep,
-                       (const uint32_t*)rank, (const uint32_t*)left, small, to_mont, ptr);
-    HM_HIP_CHECK(hipGetLastError());
-    uint32_t h_small[4 * LK_MAX_PAIRS];
-    HM_HIP_CHECK(hipMemcpyAsync(h_small, small, sizeof h_small, hipMemcpyDeviceToHost, stream));
-    HM_HIP_CHECK(hipStreamSynchronize(stream));
-    for (uint32_t p = 0; p < cnt; ++p) {
-      if (h_small[4 * p + 2]) {
-        if (missing) missing[p0 + p] = 1;
-        if (result == HM_OK) result = HM_ERR_NOT_FOUND;
-      } else if (h_small[4 * p + 3] && result == HM_OK) {
-        result = HM_ERR_INTERNAL;
       }
     }
-  }
-  const int rrc = aux_release(ctx, slot, stream);
-  if (result == HM_ERR_NOT_FOUND) return hm_fail(HM_ERR_NOT_FOUND, "lookup permute: an input value is missing from the table (ConstraintSystemFailure)");
-  if (result == HM_ERR_INTERNAL) return hm_fail(HM_ERR_INTERNAL, "lookup permute: leftover / repeated counts differ");
-  return rrc;
+    return result;                                                 // NOT_FOUND / INTERNAL come from here alone: they win over the release
+  });
+  if (verdict == HM_ERR_NOT_FOUND) return hm_fail(HM_ERR_NOT_FOUND, "lookup permute: an input value is missing from the table (ConstraintSystemFailure)");
+  if (verdict == HM_ERR_INTERNAL) return hm_fail(HM_ERR_INTERNAL, "lookup permute: leftover / repeated counts differ");
+  return verdict;
 }
 
 }  // namespace hm

@@ -190,8 +190,8 @@ static int mock_table_upload(AuxSlot& slot, const MockTable& t, const GraphProgr
   for (size_t j = 0; j < n_perm; ++j) cols.perm[j] = perm[j];
   cols.n_static = g ? g->n_static : 0;
   for (size_t i = 0; i < n_dyn; ++i) host::fr_to_internal9(host::fr_load(dyn_ext + 4 * i), &cols.dyn[9 * i]);
-  CheckColumns* d_cols = (CheckColumns*)slot.args.ensure(sizeof(CheckColumns));
-  if (!d_cols) return hm_fail(HM_ERR_HIP, "mock: argument buffer allocation failed");
+  CheckColumns* d_cols = (CheckColumns*)aux_buffer(slot, AuxBuf::args, sizeof(CheckColumns), "mock");
+  if (!d_cols) return HM_ERR_HIP;
   // pageable source: the runtime has taken its copy of `cols` when this returns (as graph_run's block)
   HM_HIP_CHECK(hipMemcpyAsync(d_cols, &cols, sizeof cols, hipMemcpyHostToDevice, stream));
   *out = d_cols;
@@ -212,8 +212,8 @@ int mock_program_run(DeviceCtx& ctx, GraphProgram& g, const MockTable& t, const 
   const size_t b_keys = d_table_values ? lookup_sorted_keys_bytes(usable) : 0;
   const CheckSink sink{out.d_records, out.cap, (unsigned long long*)out.d_counter, out.d_user_flags};
   return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
-    uint8_t* buf = (uint8_t*)slot.scratch.ensure(b_scratch + b_keys);
-    if (!buf) return hm_fail(HM_ERR_HIP, "mock: scratch allocation failed");
+    uint8_t* buf = (uint8_t*)aux_buffer(slot, AuxBuf::scratch, b_scratch + b_keys, "mock");
+    if (!buf) return HM_ERR_HIP;
     if (d_table_values)
       if (const int rc = lookup_sorted_keys_run(ctx, d_table_values, usable, buf + b_scratch, stream)) return rc;
     CheckColumns* d_cols = nullptr;

@@ -2170,18 +2170,18 @@ int msm_run(DeviceCtx& ctx, const uint32_t* d_scalars_ext, const uint32_t* d_xy,
 int g1_fixed_base_mul_run(DeviceCtx& ctx, const uint32_t* d_scalars_ext, size_t n, const uint64_t base_affine_ext[8],
                           uint32_t* d_out_affine_ext, hipStream_t stream) {
   if (n == 0) return HM_OK;
-  AuxSlot* slot = aux_acquire(ctx, stream);          // the multiples table is per stream in use
-  if (!slot) return HM_ERR_HIP;
-  uint32_t* d_table = (uint32_t*)slot->table.ensure((size_t)64 * 15 * PT_WORDS * 4);
-  if (!d_table) return hm_fail(HM_ERR_HIP, "fixed-base: table allocation failed");
-  G1AffineWords base;
-  std::memcpy(base.w, base_affine_ext, 64);
-  hipLaunchKernelGGL(g1_fixed_table_kernel, dim3(1), dim3(64), 0, stream, base, d_table);
-  HM_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(g1_fixed_base_mul_kernel, dim3((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS)), dim3(ACC_THREADS), 0,
-                     stream, d_scalars_ext, (const uint32_t*)d_table, d_out_affine_ext, n);
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
+  return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {      // the multiples table is per stream in use
+    uint32_t* d_table = (uint32_t*)aux_buffer(slot, AuxBuf::table, HM_AUX_TABLE_MIN, "fixed-base");
+    if (!d_table) return HM_ERR_HIP;
+    G1AffineWords base;
+    std::memcpy(base.w, base_affine_ext, 64);
+    hipLaunchKernelGGL(g1_fixed_table_kernel, dim3(1), dim3(64), 0, stream, base, d_table);
+    HM_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(g1_fixed_base_mul_kernel, dim3((uint32_t)((n + ACC_THREADS - 1) / ACC_THREADS)), dim3(ACC_THREADS), 0,
+                       stream, d_scalars_ext, (const uint32_t*)d_table, d_out_affine_ext, n);
+    HM_HIP_CHECK(hipGetLastError());
+    return HM_OK;
+  });
 }
 
 }  // namespace hm

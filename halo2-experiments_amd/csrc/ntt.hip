@@ -527,42 +527,6 @@ static NttTables* ntt_get_tables(DeviceCtx& ctx, const uint64_t omega_ext[4], ui
   return ctx.ntt_tables.back().get();
 }
 
-AuxSlot* aux_acquire(DeviceCtx& ctx, hipStream_t stream) {
-  AuxSlot* pick = nullptr;
-  for (auto& s : ctx.aux)
-    if (s.used && s.stream == stream) pick = &s;        // stream order already protects its buffers
-  if (!pick)
-    for (auto& s : ctx.aux)
-      if (!s.used) { pick = &s; break; }
-  if (!pick) {
-    for (auto& s : ctx.aux)                              // a slot whose last user has finished
-      if (hipEventQuery(s.done) == hipSuccess && (!pick || s.last_use < pick->last_use)) pick = &s;
-  }
-  if (!pick) {                                           // all busy on other streams: queue behind the oldest
-    pick = &ctx.aux[0];
-    for (auto& s : ctx.aux)
-      if (s.last_use < pick->last_use) pick = &s;
-    if (hipStreamWaitEvent(stream, pick->done, 0) != hipSuccess) {
-      hm_fail(HM_ERR_HIP, "aux slot: hipStreamWaitEvent failed");
-      return nullptr;
-    }
-  }
-  if (!pick->done && hipEventCreateWithFlags(&pick->done, hipEventDisableTiming) != hipSuccess) {
-    hm_fail(HM_ERR_HIP, "aux slot: event creation failed");
-    return nullptr;
-  }
-  pick->used = true;
-  pick->stream = stream;
-  pick->last_use = ++ctx.aux_clock;
-  return pick;
-}
-
-int aux_release(DeviceCtx& ctx, AuxSlot* slot, hipStream_t stream) {
-  (void)ctx;
-  HM_HIP_CHECK(hipEventRecord(slot->done, stream));
-  return HM_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
 // the powers tables of the transforms on a coset shift * <omega> (the extended domain of evaluate_h taken one coset of the n-th roots
 // at a time: 2^(extended_k - k) independent n-point problems instead of one 2^extended_k-point problem -- what lets the cosets go to
@@ -729,9 +693,8 @@ int ntt_run(DeviceCtx& ctx, const NttCall& call, const NttPointers& p, hipStream
   };
   if (plan.scratch_bytes == 0) return launches(nullptr);
   return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
-    uint32_t* scratch = (uint32_t*)slot.scratch.ensure(plan.scratch_bytes);
-    if (!scratch) return hm_fail(HM_ERR_HIP, "ntt: scratch allocation failed");
-    return launches(scratch);
+    uint32_t* scratch = (uint32_t*)aux_buffer(slot, AuxBuf::scratch, plan.scratch_bytes, "ntt");
+    return scratch ? launches(scratch) : HM_ERR_HIP;
   });
 }
 

@@ -306,21 +306,19 @@ int fr_dot_run(DeviceCtx& ctx, const uint32_t* d_a, const uint32_t* d_b, uint64_
   uint32_t per = (uint32_t)((n + (uint64_t)EV_THREADS * 4096 - 1) / ((uint64_t)EV_THREADS * 4096));   // <= 4096 blocks
   if (per < 8) per = 8;
   const uint32_t B = (uint32_t)((n + (uint64_t)EV_THREADS * per - 1) / ((uint64_t)EV_THREADS * per));
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  const size_t need = (size_t)B * 36 + 32;
-  uint8_t* buf = (uint8_t*)slot->table.ensure(need > ((size_t)64 * 15 * 28 * 4) ? need : ((size_t)64 * 15 * 28 * 4));
-  if (!buf) return hm_fail(HM_ERR_HIP, "fr_dot: scratch allocation failed");
-  uint32_t* d_partial = (uint32_t*)buf;
-  uint32_t* d_out = (uint32_t*)(buf + (size_t)B * 36);
-  FrInt9 k32;
-  host::fr_to_internal9(host::FR_32, k32.l);
-  hipLaunchKernelGGL(fr_dot_partial_kernel, dim3(B), dim3(EV_THREADS), 0, stream, d_a, d_b, n, per, d_partial);
-  hipLaunchKernelGGL(fr_dot_final_kernel, dim3(1), dim3(EV_THREADS), 0, stream, (const uint32_t*)d_partial, B, k32, d_out);
-  HM_HIP_CHECK(hipGetLastError());
-  HM_HIP_CHECK(hipMemcpyAsync(out_ext, d_out, 32, hipMemcpyDeviceToHost, stream));
-  HM_HIP_CHECK(hipStreamSynchronize(stream));
-  return aux_release(ctx, slot, stream);
+  return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
+    uint8_t* buf = (uint8_t*)aux_buffer(slot, AuxBuf::table, (size_t)B * 36 + 32, "fr_dot");
+    if (!buf) return HM_ERR_HIP;
+    uint32_t *d_partial = (uint32_t*)buf, *d_out = (uint32_t*)(buf + (size_t)B * 36);
+    FrInt9 k32;
+    host::fr_to_internal9(host::FR_32, k32.l);
+    hipLaunchKernelGGL(fr_dot_partial_kernel, dim3(B), dim3(EV_THREADS), 0, stream, d_a, d_b, n, per, d_partial);
+    hipLaunchKernelGGL(fr_dot_final_kernel, dim3(1), dim3(EV_THREADS), 0, stream, (const uint32_t*)d_partial, B, k32, d_out);
+    HM_HIP_CHECK(hipGetLastError());
+    HM_HIP_CHECK(hipMemcpyAsync(out_ext, d_out, 32, hipMemcpyDeviceToHost, stream));
+    HM_HIP_CHECK(hipStreamSynchronize(stream));
+    return HM_OK;
+  });
 }
 
 int fr_affine_sequence_run(uint32_t* d_out, uint64_t n, const uint64_t a_ext[4], const uint64_t b_ext[4], hipStream_t stream) {
@@ -360,38 +358,36 @@ int fr_eval_polynomial_run(DeviceCtx& ctx, const uint32_t* d_polys, uint64_t n, 
   if (CH == 0) CH = 1;
   const uint32_t B = (uint32_t)((n + (uint64_t)EV_THREADS * CH - 1) / ((uint64_t)EV_THREADS * CH));
   if (B > EV_THREADS) return hm_fail(HM_ERR_INTERNAL, "eval_polynomial: block plan exceeds one final workgroup");
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  const size_t per_launch = (size_t)EV_MAX_Q * B * 36 + (size_t)EV_MAX_Q * 32;
-  uint8_t* buf = (uint8_t*)slot->table.ensure(per_launch > ((size_t)64 * 15 * 28 * 4) ? per_launch : ((size_t)64 * 15 * 28 * 4));
-  if (!buf) return hm_fail(HM_ERR_HIP, "eval_polynomial: scratch allocation failed");
-  uint32_t* d_partial = (uint32_t*)buf;
-  uint32_t* d_out = (uint32_t*)(buf + (size_t)EV_MAX_Q * B * 36);
-  for (size_t q0 = 0; q0 < q; q0 += EV_MAX_Q) {
-    const uint32_t cnt = (uint32_t)(q - q0 < (size_t)EV_MAX_Q ? q - q0 : (size_t)EV_MAX_Q);
-    EvalQueries qs;
-    std::memset(&qs, 0, sizeof qs);
-    for (uint32_t i = 0; i < cnt; ++i) {
-      qs.q[i].poly = poly_index ? poly_index[q0 + i] : (uint32_t)(q0 + i);
-      host::fr_to_internal9(host::fr_load(points_ext + (q0 + i) * 4), qs.q[i].x.l);
+  return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
+    uint8_t* buf = (uint8_t*)aux_buffer(slot, AuxBuf::table, (size_t)EV_MAX_Q * B * 36 + (size_t)EV_MAX_Q * 32, "eval_polynomial");
+    if (!buf) return HM_ERR_HIP;
+    uint32_t *d_partial = (uint32_t*)buf, *d_out = (uint32_t*)(buf + (size_t)EV_MAX_Q * B * 36);
+    for (size_t q0 = 0; q0 < q; q0 += EV_MAX_Q) {
+      const uint32_t cnt = (uint32_t)(q - q0 < (size_t)EV_MAX_Q ? q - q0 : (size_t)EV_MAX_Q);
+      EvalQueries qs;
+      std::memset(&qs, 0, sizeof qs);
+      for (uint32_t i = 0; i < cnt; ++i) {
+        qs.q[i].poly = poly_index ? poly_index[q0 + i] : (uint32_t)(q0 + i);
+        host::fr_to_internal9(host::fr_load(points_ext + (q0 + i) * 4), qs.q[i].x.l);
+      }
+      // Coefficients per lane of THIS launch.  A lane pays ~25 products whatever its share (x^256, x^t, the block sum), so with
+      // many queries in the launch -- the 94 openings of a k = 18 proof go 48 at a time -- longer shares are cheaper as long as
+      // the launch still has ~1 000 workgroups: 16 per lane costs 2.5 products per coefficient, 64 per lane 1.4.
+      uint32_t CHq = CH;
+      {
+        const uint32_t want_blocks = 1024 / cnt ? 1024 / cnt : 1;                        // workgroups per query
+        const uint64_t ch = (n + (uint64_t)EV_THREADS * want_blocks - 1) / ((uint64_t)EV_THREADS * want_blocks);
+        if (ch > CHq) CHq = (uint32_t)(ch > 256 ? 256 : ch);
+      }
+      const uint32_t Bq = (uint32_t)((n + (uint64_t)EV_THREADS * CHq - 1) / ((uint64_t)EV_THREADS * CHq));     // <= B
+      hipLaunchKernelGGL(fr_eval_partial_kernel, dim3(Bq, cnt), dim3(EV_THREADS), 0, stream, d_polys, n, qs, CHq, d_partial);
+      hipLaunchKernelGGL(fr_eval_final_kernel, dim3(cnt), dim3(EV_THREADS), 0, stream, (const uint32_t*)d_partial, qs, Bq, 8u, CHq, d_out);
+      HM_HIP_CHECK(hipGetLastError());
+      HM_HIP_CHECK(hipMemcpyAsync(out_ext + q0 * 4, d_out, (size_t)cnt * 32, hipMemcpyDeviceToHost, stream));
+      HM_HIP_CHECK(hipStreamSynchronize(stream));      // the results go to the caller's (pageable) memory
     }
-    // Coefficients per lane of THIS launch.  A lane pays ~25 products whatever its share (x^256, x^t, the block sum), so with
-    // many queries in the launch -- the 94 openings of a k = 18 proof go 48 at a time -- longer shares are cheaper as long as
-    // the launch still has ~1 000 workgroups: 16 per lane costs 2.5 products per coefficient, 64 per lane 1.4.
-    uint32_t CHq = CH;
-    {
-      const uint32_t want_blocks = 1024 / cnt ? 1024 / cnt : 1;                        // workgroups per query
-      const uint64_t ch = (n + (uint64_t)EV_THREADS * want_blocks - 1) / ((uint64_t)EV_THREADS * want_blocks);
-      if (ch > CHq) CHq = (uint32_t)(ch > 256 ? 256 : ch);
-    }
-    const uint32_t Bq = (uint32_t)((n + (uint64_t)EV_THREADS * CHq - 1) / ((uint64_t)EV_THREADS * CHq));     // <= B
-    hipLaunchKernelGGL(fr_eval_partial_kernel, dim3(Bq, cnt), dim3(EV_THREADS), 0, stream, d_polys, n, qs, CHq, d_partial);
-    hipLaunchKernelGGL(fr_eval_final_kernel, dim3(cnt), dim3(EV_THREADS), 0, stream, (const uint32_t*)d_partial, qs, Bq, 8u, CHq, d_out);
-    HM_HIP_CHECK(hipGetLastError());
-    HM_HIP_CHECK(hipMemcpyAsync(out_ext + q0 * 4, d_out, (size_t)cnt * 32, hipMemcpyDeviceToHost, stream));
-    HM_HIP_CHECK(hipStreamSynchronize(stream));      // the results go to the caller's (pageable) memory
-  }
-  return aux_release(ctx, slot, stream);
+    return HM_OK;
+  });
 }
 
 }  // namespace hm

@@ -644,11 +644,9 @@ static PoPlan po_plan(uint64_t n) {
 struct PoScratch {
   uint32_t *incl, *wg_total, *carry, *colprod;
 };
-static bool po_scratch(AuxSlot* slot, const PoPlan& p, size_t cols, PoScratch* out) {
+static bool po_scratch(AuxSlot& slot, const PoPlan& p, size_t cols, const char* who, PoScratch* out) {
   const size_t lanes = (size_t)p.G * PO_THREADS + 1;
-  const size_t need = cols * (lanes + 2 * (size_t)p.G + 1) * 36;
-  const size_t keep = (size_t)64 * 15 * 28 * 4;             // never shrink below the fixed-base table (see poly.hip)
-  uint8_t* buf = (uint8_t*)slot->table.ensure(need > keep ? need : keep);
+  uint8_t* buf = (uint8_t*)aux_buffer(slot, AuxBuf::table, cols * (lanes + 2 * (size_t)p.G + 1) * 36, who);
   if (!buf) return false;
   out->incl = (uint32_t*)buf;
   out->wg_total = out->incl + cols * lanes * 9;
@@ -663,29 +661,29 @@ int fr_kate_division_batch_run(DeviceCtx& ctx, const void* const* d_a, uint64_t 
   if (n < 2 || count == 0) return HM_OK;                     // a constant has the empty quotient
   const PoPlan p = po_plan(n);
   if (p.G > PO_THREADS) return hm_fail(HM_ERR_INTERNAL, "kate_division: plan exceeds one joining workgroup");
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  PoScratch sc;
   const size_t per = count < (size_t)PO_COLS_MAX ? count : (size_t)PO_COLS_MAX;
-  if (!po_scratch(slot, p, per, &sc)) return hm_fail(HM_ERR_HIP, "kate_division: scratch allocation failed");
-  for (size_t first = 0; first < count; first += per) {
-    const uint32_t c = (uint32_t)(count - first < per ? count - first : per);
-    PoCols cols;
-    PoPoints pts;
-    std::memset(&cols, 0, sizeof cols);
-    std::memset(&pts, 0, sizeof pts);
-    for (uint32_t j = 0; j < c; ++j) {
-      cols.in[j] = (const uint32_t*)d_a[first + j];
-      cols.out[j] = (uint32_t*)d_q[first + j];
-      po_internal(z_ext + (first + j) * 4, pts.z[j]);
+  return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
+    PoScratch sc;
+    if (!po_scratch(slot, p, per, "kate_division", &sc)) return HM_ERR_HIP;
+    for (size_t first = 0; first < count; first += per) {
+      const uint32_t c = (uint32_t)(count - first < per ? count - first : per);
+      PoCols cols;
+      PoPoints pts;
+      std::memset(&cols, 0, sizeof cols);
+      std::memset(&pts, 0, sizeof pts);
+      for (uint32_t j = 0; j < c; ++j) {
+        cols.in[j] = (const uint32_t*)d_a[first + j];
+        cols.out[j] = (uint32_t*)d_q[first + j];
+        po_internal(z_ext + (first + j) * 4, pts.z[j]);
+      }
+      hipLaunchKernelGGL(fr_kate_chunks_kernel, dim3(p.G, c), dim3(PO_THREADS), 0, stream, cols, n, pts, p.B, sc.incl, sc.wg_total);
+      hipLaunchKernelGGL(fr_kate_join_kernel, dim3(c), dim3(PO_THREADS), 0, stream, (const uint32_t*)sc.wg_total, p.G, pts, p.B, sc.carry);
+      hipLaunchKernelGGL(fr_kate_replay_kernel, dim3(p.G, c), dim3(PO_THREADS), 0, stream, cols, n, pts, p.B, (const uint32_t*)sc.incl,
+                         (const uint32_t*)sc.carry);
     }
-    hipLaunchKernelGGL(fr_kate_chunks_kernel, dim3(p.G, c), dim3(PO_THREADS), 0, stream, cols, n, pts, p.B, sc.incl, sc.wg_total);
-    hipLaunchKernelGGL(fr_kate_join_kernel, dim3(c), dim3(PO_THREADS), 0, stream, (const uint32_t*)sc.wg_total, p.G, pts, p.B, sc.carry);
-    hipLaunchKernelGGL(fr_kate_replay_kernel, dim3(p.G, c), dim3(PO_THREADS), 0, stream, cols, n, pts, p.B, (const uint32_t*)sc.incl,
-                       (const uint32_t*)sc.carry);
-  }
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
+    HM_HIP_CHECK(hipGetLastError());
+    return HM_OK;
+  });
 }
 
 int fr_kate_division_run(DeviceCtx& ctx, const uint32_t* d_a, uint64_t n, const uint64_t z_ext[4], uint32_t* d_q, hipStream_t stream) {
@@ -726,26 +724,24 @@ int fr_shplonk_set_quotient_run(const void* const* d_polys, const uint64_t* weig
     pts.z[l] = args.z[l];
   }
   const size_t n_bytes = (size_t)n * 32, per_point = (size_t)shq_scan_words(p);
-  void* ws = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&ws, n_bytes + (size_t)t * per_point * sizeof(uint32_t), stream));
-  uint32_t* d_n = (uint32_t*)ws;
-  uint32_t* incl = (uint32_t*)((uint8_t*)ws + n_bytes);
-  uint32_t* wg_total = incl + (size_t)t * ((size_t)p.G * PO_THREADS + 1) * 9;
-  uint32_t* carry = wg_total + (size_t)t * p.G * 9;
-  int rc = fr_linear_combination_run(d_polys, weights_ext, m, n, d_n, stream);
-  if (rc == HM_OK) {
-    const int acc = accumulate ? 1 : 0;
-    switch (t) {
-      case 1: shq_launch<1>(p, d_n, n, args, pts, incl, wg_total, carry, d_out, acc, stream); break;
-      case 2: shq_launch<2>(p, d_n, n, args, pts, incl, wg_total, carry, d_out, acc, stream); break;
-      case 3: shq_launch<3>(p, d_n, n, args, pts, incl, wg_total, carry, d_out, acc, stream); break;
-      default: shq_launch<4>(p, d_n, n, args, pts, incl, wg_total, carry, d_out, acc, stream); break;
+  return stream_scratch("shplonk_set_quotient", n_bytes + (size_t)t * per_point * sizeof(uint32_t), stream, [&](uint8_t* ws) -> int {
+    uint32_t* d_n = (uint32_t*)ws;
+    uint32_t* incl = (uint32_t*)(ws + n_bytes);
+    uint32_t* wg_total = incl + (size_t)t * ((size_t)p.G * PO_THREADS + 1) * 9;
+    uint32_t* carry = wg_total + (size_t)t * p.G * 9;
+    int rc = fr_linear_combination_run(d_polys, weights_ext, m, n, d_n, stream);
+    if (rc == HM_OK) {
+      const int acc = accumulate ? 1 : 0;
+      switch (t) {
+        case 1: shq_launch<1>(p, d_n, n, args, pts, incl, wg_total, carry, d_out, acc, stream); break;
+        case 2: shq_launch<2>(p, d_n, n, args, pts, incl, wg_total, carry, d_out, acc, stream); break;
+        case 3: shq_launch<3>(p, d_n, n, args, pts, incl, wg_total, carry, d_out, acc, stream); break;
+        default: shq_launch<4>(p, d_n, n, args, pts, incl, wg_total, carry, d_out, acc, stream); break;
+      }
+      if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("shplonk_set_quotient: ") + hipGetErrorString(e));
     }
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("shplonk_set_quotient: ") + hipGetErrorString(e));
-  }
-  const hipError_t fe = hipFreeAsync(ws, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("shplonk_set_quotient: hipFreeAsync: ") + hipGetErrorString(fe));
-  return rc;
+    return rc;
+  });
 }
 
 // `count` running products over n rows; chain_row >= n: every column starts from `start`; chain_row < n: column j + 1 starts
@@ -756,37 +752,37 @@ int fr_grand_product_batch_run(DeviceCtx& ctx, const void* const* d_m, uint64_t 
   if (n == 0 || count == 0) return HM_OK;
   const PoPlan p = po_plan(n);
   if (p.G > PO_THREADS) return hm_fail(HM_ERR_INTERNAL, "grand_product: plan exceeds one joining workgroup");
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  PoScratch sc;
   const size_t per = count < (size_t)PO_COLS_MAX ? count : (size_t)PO_COLS_MAX;
-  if (!po_scratch(slot, p, per, &sc)) return hm_fail(HM_ERR_HIP, "grand_product: scratch allocation failed");
-  PoFr k32;
-  host::fr_to_internal9(host::FR_32, k32.l);
-  const bool chained = chain_row < n;
-  PoStart st;
-  std::memset(&st, 0, sizeof st);
-  po_raw(start_ext, st.start_raw);
-  st.chain_row = chained ? chain_row : n;
-  for (size_t first = 0; first < count; first += per) {
-    const uint32_t c = (uint32_t)(count - first < per ? count - first : per);
-    PoCols cols;
-    std::memset(&cols, 0, sizeof cols);
-    for (uint32_t j = 0; j < c; ++j) {
-      cols.in[j] = (const uint32_t*)d_m[first + j];
-      cols.out[j] = (uint32_t*)d_out[first + j];
+  return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
+    PoScratch sc;
+    if (!po_scratch(slot, p, per, "grand_product", &sc)) return HM_ERR_HIP;
+    PoFr k32;
+    host::fr_to_internal9(host::FR_32, k32.l);
+    const bool chained = chain_row < n;
+    PoStart st;
+    std::memset(&st, 0, sizeof st);
+    po_raw(start_ext, st.start_raw);
+    st.chain_row = chained ? chain_row : n;
+    for (size_t first = 0; first < count; first += per) {
+      const uint32_t c = (uint32_t)(count - first < per ? count - first : per);
+      PoCols cols;
+      std::memset(&cols, 0, sizeof cols);
+      for (uint32_t j = 0; j < c; ++j) {
+        cols.in[j] = (const uint32_t*)d_m[first + j];
+        cols.out[j] = (uint32_t*)d_out[first + j];
+      }
+      st.d_start = chained && first ? (const uint32_t*)d_out[first - 1] + chain_row * 8 : nullptr;
+      hipLaunchKernelGGL(fr_product_chunks_kernel, dim3(p.G, c), dim3(PO_THREADS), 0, stream, cols, n, k32, p.B, sc.incl, sc.wg_total);
+      hipLaunchKernelGGL(fr_product_join_kernel, dim3(c), dim3(PO_THREADS), 0, stream, cols, n, k32, p.B, p.G, (const uint32_t*)sc.incl,
+                         (const uint32_t*)sc.wg_total, st, sc.carry, sc.colprod);
+      if (chained)
+        hipLaunchKernelGGL(fr_product_chain_kernel, dim3(c), dim3(PO_THREADS), 0, stream, p.G, st, (const uint32_t*)sc.colprod, sc.carry);
+      hipLaunchKernelGGL(fr_product_replay_kernel, dim3(p.G, c), dim3(PO_THREADS), 0, stream, cols, n, k32, p.B, (const uint32_t*)sc.incl,
+                         (const uint32_t*)sc.carry);
     }
-    st.d_start = chained && first ? (const uint32_t*)d_out[first - 1] + chain_row * 8 : nullptr;
-    hipLaunchKernelGGL(fr_product_chunks_kernel, dim3(p.G, c), dim3(PO_THREADS), 0, stream, cols, n, k32, p.B, sc.incl, sc.wg_total);
-    hipLaunchKernelGGL(fr_product_join_kernel, dim3(c), dim3(PO_THREADS), 0, stream, cols, n, k32, p.B, p.G, (const uint32_t*)sc.incl,
-                       (const uint32_t*)sc.wg_total, st, sc.carry, sc.colprod);
-    if (chained)
-      hipLaunchKernelGGL(fr_product_chain_kernel, dim3(c), dim3(PO_THREADS), 0, stream, p.G, st, (const uint32_t*)sc.colprod, sc.carry);
-    hipLaunchKernelGGL(fr_product_replay_kernel, dim3(p.G, c), dim3(PO_THREADS), 0, stream, cols, n, k32, p.B, (const uint32_t*)sc.incl,
-                       (const uint32_t*)sc.carry);
-  }
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
+    HM_HIP_CHECK(hipGetLastError());
+    return HM_OK;
+  });
 }
 
 int fr_grand_product_run(DeviceCtx& ctx, const uint32_t* d_m, uint64_t n, const uint64_t start_ext[4], uint32_t* d_out, hipStream_t stream) {
@@ -903,35 +899,33 @@ int fr_linear_combination_batch_run(const void* const* d_polys, const uint64_t* 
     ptrs[terms + b] = (uint64_t)(uintptr_t)d_outs[b];
   }
   const size_t b_ptrs = ptrs.size() * 8, b_c9 = c9.size() * 4;
-  void* tab = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&tab, b_ptrs + b_c9, stream));
-  int rc = HM_OK;
-  // pageable sources: the runtime has taken its copies when these return
-  if (hipMemcpyAsync(tab, ptrs.data(), b_ptrs, hipMemcpyHostToDevice, stream) != hipSuccess ||
-      hipMemcpyAsync((uint8_t*)tab + b_ptrs, c9.data(), b_c9, hipMemcpyHostToDevice, stream) != hipSuccess)
-    rc = hm_fail(HM_ERR_HIP, "linear_combination_batch: upload failed");
-  if (rc == HM_OK) {
-    const uint32_t* const* d_p = (const uint32_t* const*)tab;
-    uint32_t* const* d_o = (uint32_t* const*)((uint64_t*)tab + terms);
-    const uint32_t* d_c = (const uint32_t*)((uint8_t*)tab + b_ptrs);
-    PoFr one;
-    host::fr_to_internal9(host::FR_ONE, one.l);
-    const dim3 grid((uint32_t)((n + PO_THREADS - 1) / PO_THREADS), (uint32_t)proofs);
-    size_t done = 0;
-    bool first = true;
-    do {                                                     // count == 0: one launch that writes zeroes
-      const uint32_t room = (uint32_t)LC_MAX - (first ? 0 : 1);
-      const uint32_t k = (uint32_t)std::min<size_t>(room, count - done);
-      hipLaunchKernelGGL(fr_lincomb_batch_kernel, grid, dim3(PO_THREADS), 0, stream, d_p, d_c, d_o, (uint32_t)count, (uint32_t)done, k,
-                         first ? 0 : 1, one, n);
-      done += k;
-      first = false;
-    } while (done < count);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("linear_combination_batch: ") + hipGetErrorString(e));
-  }
-  const hipError_t fe = hipFreeAsync(tab, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("linear_combination_batch: hipFreeAsync: ") + hipGetErrorString(fe));
-  return rc;
+  return stream_scratch("linear_combination_batch", b_ptrs + b_c9, stream, [&](uint8_t* tab) -> int {
+    int rc = HM_OK;
+    // pageable sources: the runtime has taken its copies when these return
+    if (hipMemcpyAsync(tab, ptrs.data(), b_ptrs, hipMemcpyHostToDevice, stream) != hipSuccess ||
+        hipMemcpyAsync(tab + b_ptrs, c9.data(), b_c9, hipMemcpyHostToDevice, stream) != hipSuccess)
+      rc = hm_fail(HM_ERR_HIP, "linear_combination_batch: upload failed");
+    if (rc == HM_OK) {
+      const uint32_t* const* d_p = (const uint32_t* const*)tab;
+      uint32_t* const* d_o = (uint32_t* const*)((uint64_t*)tab + terms);
+      const uint32_t* d_c = (const uint32_t*)(tab + b_ptrs);
+      PoFr one;
+      host::fr_to_internal9(host::FR_ONE, one.l);
+      const dim3 grid((uint32_t)((n + PO_THREADS - 1) / PO_THREADS), (uint32_t)proofs);
+      size_t done = 0;
+      bool first = true;
+      do {                                                     // count == 0: one launch that writes zeroes
+        const uint32_t room = (uint32_t)LC_MAX - (first ? 0 : 1);
+        const uint32_t k = (uint32_t)std::min<size_t>(room, count - done);
+        hipLaunchKernelGGL(fr_lincomb_batch_kernel, grid, dim3(PO_THREADS), 0, stream, d_p, d_c, d_o, (uint32_t)count, (uint32_t)done, k,
+                           first ? 0 : 1, one, n);
+        done += k;
+        first = false;
+      } while (done < count);
+      if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("linear_combination_batch: ") + hipGetErrorString(e));
+    }
+    return rc;
+  });
 }
 
 template <int T>
@@ -969,33 +963,30 @@ int fr_shplonk_set_quotient_batch_run(const void* const* d_polys, const uint64_t
   const size_t n_bytes = (size_t)n * 32, scan_stride = (size_t)t * (size_t)shq_scan_words(p);
   // one workspace: every proof's N, the output pointers, the (points, coefficients) table, every proof's scans
   const size_t o_outs = proofs * n_bytes, o_table = o_outs + proofs * sizeof(void*), o_scan = o_table + proofs * sizeof(ShqArgs);
-  void* ws = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&ws, o_scan + proofs * scan_stride * sizeof(uint32_t), stream));
-  uint8_t* base = (uint8_t*)ws;
-  std::vector<void*> d_ns(proofs);
-  for (size_t b = 0; b < proofs; ++b) d_ns[b] = base + b * n_bytes;
-  int rc = HM_OK;
-  if (hipMemcpyAsync(base + o_table, table.data(), proofs * sizeof(ShqArgs), hipMemcpyHostToDevice, stream) != hipSuccess ||
-      hipMemcpyAsync(base + o_outs, d_outs, proofs * sizeof(void*), hipMemcpyHostToDevice, stream) != hipSuccess)
-    rc = hm_fail(HM_ERR_HIP, "shplonk_set_quotient_batch: upload failed");
-  if (rc == HM_OK) rc = fr_linear_combination_batch_run(d_polys, weights_ext, m, n, d_ns.data(), proofs, stream);
-  if (rc == HM_OK) {
-    const int acc = accumulate ? 1 : 0;
-    const uint32_t* d_n = (const uint32_t*)base;
-    const ShqArgs* d_table = (const ShqArgs*)(base + o_table);
-    uint32_t* scan = (uint32_t*)(base + o_scan);
-    uint32_t* const* outs = (uint32_t* const*)(base + o_outs);
-    switch (t) {
-      case 1: shq_launch_batch<1>(p, d_n, n, d_table, scan, scan_stride, outs, acc, (uint32_t)proofs, stream); break;
-      case 2: shq_launch_batch<2>(p, d_n, n, d_table, scan, scan_stride, outs, acc, (uint32_t)proofs, stream); break;
-      case 3: shq_launch_batch<3>(p, d_n, n, d_table, scan, scan_stride, outs, acc, (uint32_t)proofs, stream); break;
-      default: shq_launch_batch<4>(p, d_n, n, d_table, scan, scan_stride, outs, acc, (uint32_t)proofs, stream); break;
+  return stream_scratch("shplonk_set_quotient_batch", o_scan + proofs * scan_stride * sizeof(uint32_t), stream, [&](uint8_t* base) -> int {
+    std::vector<void*> d_ns(proofs);
+    for (size_t b = 0; b < proofs; ++b) d_ns[b] = base + b * n_bytes;
+    int rc = HM_OK;
+    if (hipMemcpyAsync(base + o_table, table.data(), proofs * sizeof(ShqArgs), hipMemcpyHostToDevice, stream) != hipSuccess ||
+        hipMemcpyAsync(base + o_outs, d_outs, proofs * sizeof(void*), hipMemcpyHostToDevice, stream) != hipSuccess)
+      rc = hm_fail(HM_ERR_HIP, "shplonk_set_quotient_batch: upload failed");
+    if (rc == HM_OK) rc = fr_linear_combination_batch_run(d_polys, weights_ext, m, n, d_ns.data(), proofs, stream);
+    if (rc == HM_OK) {
+      const int acc = accumulate ? 1 : 0;
+      const uint32_t* d_n = (const uint32_t*)base;
+      const ShqArgs* d_table = (const ShqArgs*)(base + o_table);
+      uint32_t* scan = (uint32_t*)(base + o_scan);
+      uint32_t* const* outs = (uint32_t* const*)(base + o_outs);
+      switch (t) {
+        case 1: shq_launch_batch<1>(p, d_n, n, d_table, scan, scan_stride, outs, acc, (uint32_t)proofs, stream); break;
+        case 2: shq_launch_batch<2>(p, d_n, n, d_table, scan, scan_stride, outs, acc, (uint32_t)proofs, stream); break;
+        case 3: shq_launch_batch<3>(p, d_n, n, d_table, scan, scan_stride, outs, acc, (uint32_t)proofs, stream); break;
+        default: shq_launch_batch<4>(p, d_n, n, d_table, scan, scan_stride, outs, acc, (uint32_t)proofs, stream); break;
+      }
+      if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("shplonk_set_quotient_batch: ") + hipGetErrorString(e));
     }
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("shplonk_set_quotient_batch: ") + hipGetErrorString(e));
-  }
-  const hipError_t fe = hipFreeAsync(ws, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("shplonk_set_quotient_batch: hipFreeAsync: ") + hipGetErrorString(fe));
-  return rc;
+    return rc;
+  });
 }
 
 int fr_mul_periodic_run(uint32_t* d_a, uint64_t n, const uint64_t* pattern_ext, uint32_t period, hipStream_t stream) {
@@ -1033,21 +1024,19 @@ __global__ __launch_bounds__(PO_THREADS) void perm_columns_kernel(const uint32_t
 int perm_columns_run(const uint32_t* d_sigma_cells, uint32_t columns, uint32_t k, const uint64_t omega_ext[4], const uint64_t delta_ext[4],
                      uint32_t* d_out, hipStream_t stream) {
   const uint64_t n = (uint64_t)1 << k, cells = (uint64_t)columns << k;
-  void* tables = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&tables, (size_t)(n + columns) * 32, stream));
-  uint32_t *d_omega = (uint32_t*)tables, *d_delta = d_omega + n * 8;
-  int rc = fr_powers_run(d_omega, n, omega_ext, stream);
-  if (rc == HM_OK) rc = fr_powers_run(d_delta, columns, delta_ext, stream);
-  if (rc == HM_OK) {
-    PoFr k32;
-    host::fr_to_internal9(host::FR_32, k32.l);
-    hipLaunchKernelGGL(perm_columns_kernel, dim3((unsigned)((cells + PO_THREADS - 1) / PO_THREADS)), dim3(PO_THREADS), 0, stream, d_sigma_cells,
-                       cells, k, (const uint32_t*)d_omega, (const uint32_t*)d_delta, k32, d_out);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("permutation_columns: ") + hipGetErrorString(e));
-  }
-  const hipError_t fe = hipFreeAsync(tables, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("permutation_columns: hipFreeAsync: ") + hipGetErrorString(fe));
-  return rc;
+  return stream_scratch("permutation_columns", (size_t)(n + columns) * 32, stream, [&](uint8_t* tables) -> int {
+    uint32_t *d_omega = (uint32_t*)tables, *d_delta = d_omega + n * 8;
+    int rc = fr_powers_run(d_omega, n, omega_ext, stream);
+    if (rc == HM_OK) rc = fr_powers_run(d_delta, columns, delta_ext, stream);
+    if (rc == HM_OK) {
+      PoFr k32;
+      host::fr_to_internal9(host::FR_32, k32.l);
+      hipLaunchKernelGGL(perm_columns_kernel, dim3((unsigned)((cells + PO_THREADS - 1) / PO_THREADS)), dim3(PO_THREADS), 0, stream, d_sigma_cells,
+                         cells, k, (const uint32_t*)d_omega, (const uint32_t*)d_delta, k32, d_out);
+      if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("permutation_columns: ") + hipGetErrorString(e));
+    }
+    return rc;
+  });
 }
 
 }  // namespace hm

@@ -380,12 +380,9 @@ int merkle_update_run(const PoseidonSpec& s, uint32_t* d_nodes, uint32_t depth, 
   uint64_t n_pow2 = 1;
   while (n_pow2 < m) n_pow2 <<= 1;
   const size_t o_order = (size_t)n_pow2 * 8, o_small = o_order + ((size_t)m * 4 + 15) / 16 * 16;
-  void* ws = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&ws, o_small + 3 * MU_BINS * sizeof(uint32_t), stream));
-  int rc = merkle_update_launch(s, d_nodes, depth, d_indices, d_new_leaves, m, d_counts, (uint8_t*)ws, n_pow2, o_order, o_small, stream);
-  const hipError_t fe = hipFreeAsync(ws, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("merkle_update: hipFreeAsync: ") + hipGetErrorString(fe));
-  return rc;
+  return stream_scratch("merkle_update", o_small + 3 * MU_BINS * sizeof(uint32_t), stream, [&](uint8_t* ws) -> int {
+    return merkle_update_launch(s, d_nodes, depth, d_indices, d_new_leaves, m, d_counts, ws, n_pow2, o_order, o_small, stream);
+  });
 }
 
 // out = rows_used, n_advice, perm_rows, level_rows, lt_row, const_row
@@ -408,31 +405,28 @@ int merkle_witness_run(uint32_t E, const PoseidonSpec& s, uint32_t depth, uint32
                        const uint32_t* d_siblings, const uint64_t* d_indices, const uint64_t* assets_ext, const uint32_t* d_nodes,
                        uint32_t* d_advice, uint32_t* d_instance, hipStream_t stream) {
   if (m == 0) return HM_OK;
-  const std::string who = E == 2 ? "merkle_sum_witness: " : "merkle_witness: ";
+  const std::string who = E == 2 ? "merkle_sum_witness" : "merkle_witness";
   WitnessArgs a = witness_args(s, depth, log_n, m, d_leaves, d_advice, d_instance);
   a.siblings = d_siblings, a.indices = d_indices, a.nodes = d_nodes;
   if (E == 2) std::memcpy(a.assets, assets_ext, 32);
   HM_HIP_CHECK(hipMemsetAsync(d_advice, 0, (size_t)m * witness_advice(E) * ((size_t)32 << log_n), stream));
-  void* run = nullptr;
-  int rc = HM_OK;
-  if (!d_nodes && depth > 1) {
-    HM_HIP_CHECK(hipMallocAsync(&run, (size_t)m * (depth - 1) * E * 32, stream));
-    a.run = (const uint32_t*)run;
-    hipLaunchKernelGGL(E == 2 ? merkle_chain_kernel<2> : merkle_chain_kernel<1>, dim3((unsigned)((m + PS_THREADS - 1) / PS_THREADS)),
-                       dim3(PS_THREADS), 0, stream, a, (uint32_t*)run);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, who + hipGetErrorString(e));
-  }
-  if (rc == HM_OK) {
-    const uint64_t lanes = (uint64_t)m * depth;
-    hipLaunchKernelGGL(E == 2 ? merkle_witness_kernel<2> : merkle_witness_kernel<1>, dim3((unsigned)((lanes + PS_THREADS - 1) / PS_THREADS)),
-                       dim3(PS_THREADS), 0, stream, a);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, who + hipGetErrorString(e));
-  }
-  if (run) {
-    const hipError_t fe = hipFreeAsync(run, stream);
-    if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, who + "hipFreeAsync: " + hipGetErrorString(fe));
-  }
-  return rc;
+  const size_t run_bytes = !d_nodes && depth > 1 ? (size_t)m * (depth - 1) * E * 32 : 0;      // with a tree: 0 bytes, no buffer
+  return stream_scratch(who.c_str(), run_bytes, stream, [&](uint8_t* run) -> int {
+    int rc = HM_OK;
+    if (run) {
+      a.run = (const uint32_t*)run;
+      hipLaunchKernelGGL(E == 2 ? merkle_chain_kernel<2> : merkle_chain_kernel<1>, dim3((unsigned)((m + PS_THREADS - 1) / PS_THREADS)),
+                         dim3(PS_THREADS), 0, stream, a, (uint32_t*)run);
+      if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, who + ": " + hipGetErrorString(e));
+    }
+    if (rc == HM_OK) {
+      const uint64_t lanes = (uint64_t)m * depth;
+      hipLaunchKernelGGL(E == 2 ? merkle_witness_kernel<2> : merkle_witness_kernel<1>, dim3((unsigned)((lanes + PS_THREADS - 1) / PS_THREADS)),
+                         dim3(PS_THREADS), 0, stream, a);
+      if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = hm_fail(HM_ERR_HIP, who + ": " + hipGetErrorString(e));
+    }
+    return rc;
+  });
 }
 
 int poseidon_witness_run(const PoseidonSpec& s, uint32_t log_n, size_t m, const uint32_t* d_msgs, uint32_t* d_advice, uint32_t* d_instance,

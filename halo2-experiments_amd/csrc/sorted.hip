@@ -176,13 +176,10 @@ int fr_sort_records_run(const uint32_t* d_values, uint64_t n, uint64_t n_pow2, u
 int fr_argsort_run(const uint32_t* d_values, size_t n, uint64_t* d_perm, hipStream_t stream) {
   uint64_t n_pow2 = 1;
   while (n_pow2 < (uint64_t)n) n_pow2 <<= 1;
-  void* ws = nullptr;
-  HM_HIP_CHECK(hipMallocAsync(&ws, (size_t)n_pow2 * 36, stream));
-  uint32_t* keys = (uint32_t*)ws;
-  int rc = fr_sort_records_run(d_values, n, n_pow2, keys, keys + n_pow2 * 8, d_perm, stream);
-  const hipError_t fe = hipFreeAsync(ws, stream);
-  if (rc == HM_OK && fe != hipSuccess) rc = hm_fail(HM_ERR_HIP, std::string("fr_argsort: hipFreeAsync: ") + hipGetErrorString(fe));
-  return rc;
+  return stream_scratch("fr_argsort", (size_t)n_pow2 * 36, stream, [&](uint8_t* ws) -> int {
+    uint32_t* keys = (uint32_t*)ws;
+    return fr_sort_records_run(d_values, n, n_pow2, keys, keys + n_pow2 * 8, d_perm, stream);
+  });
 }
 
 }  // namespace hm

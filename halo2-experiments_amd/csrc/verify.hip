@@ -285,27 +285,26 @@ static int verify_terms_launch(const char* what, const char* why, DeviceCtx& ctx
                                const uint32_t* lane_plan, size_t n_columns, size_t n_dynamic, size_t n_proofs, size_t lanes,
                                VerifyTermsKernel kernel, const uint32_t* d_records, const uint32_t* d_evals, const uint32_t* d_inst,
                                uint32_t* d_bad, uint32_t* d_own, uint32_t* d_shared, uint32_t* d_h2r, uint32_t* d_h2l, hipStream_t stream) {
-  const std::string who = what;
   GraphVariant& v = g.variant[0];
-  if (!v.ready) return hm_fail(HM_ERR_INTERNAL, who + ": the program has no lowered form");
-  if (n_columns != g.n_columns) return hm_fail(HM_ERR_BAD_ARG, who + ": the program was built for another number of columns");
+  if (!v.ready) return hm_fail(HM_ERR_INTERNAL, std::string(what) + ": the program has no lowered form");
+  if (n_columns != g.n_columns) return hm_fail(HM_ERR_BAD_ARG, std::string(what) + ": the program was built for another number of columns");
   if (n_dynamic != g.n_dynamic || n_dynamic != 4)
-    return hm_fail(HM_ERR_BAD_ARG, who + ": the program must take beta, gamma, theta, y as its per-call constants");
+    return hm_fail(HM_ERR_BAD_ARG, std::string(what) + ": the program must take beta, gamma, theta, y as its per-call constants");
   if (why) return hm_fail(HM_ERR_BAD_ARG, why);
   const uint32_t blocks = (uint32_t)((lanes + GE_THREADS - 1) / GE_THREADS), T = blocks * GE_THREADS;
   const size_t slots = (size_t)vt_ws_program(lane_plan) + v.n_slots;
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  uint32_t* ws = (uint32_t*)slot->scratch.ensure(slots * 9 * T * 4);
-  uint32_t* d_plan = (uint32_t*)slot->args.ensure(n_words * 4);
-  if (!ws || !d_plan) return hm_fail(HM_ERR_HIP, who + ": workspace allocation failed");
-  // pageable source: the runtime has taken its copy of the plan when this returns (as the witness checker's table)
-  HM_HIP_CHECK(hipMemcpyAsync(d_plan, plan, n_words * 4, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(GE_THREADS), 0, stream, (const uint32_t*)d_plan, (const uint32_t*)g.d_consts,
-                     (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src, v.result_prev, g.n_static, ws, (uint32_t)n_proofs, d_records, d_evals,
-                     d_inst, d_bad, d_own, d_shared, d_h2r, d_h2l);
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
+  return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
+    uint32_t* ws = (uint32_t*)aux_buffer(slot, AuxBuf::scratch, slots * 9 * T * 4, what);
+    uint32_t* d_plan = ws ? (uint32_t*)aux_buffer(slot, AuxBuf::args, n_words * 4, what) : nullptr;
+    if (!d_plan) return HM_ERR_HIP;
+    // pageable source: the runtime has taken its copy of the plan when this returns (as the witness checker's table)
+    HM_HIP_CHECK(hipMemcpyAsync(d_plan, plan, n_words * 4, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(GE_THREADS), 0, stream, (const uint32_t*)d_plan, (const uint32_t*)g.d_consts,
+                       (const GraphCalc*)v.d_calcs, v.n_calc, v.result_src, v.result_prev, g.n_static, ws, (uint32_t)n_proofs, d_records, d_evals,
+                       d_inst, d_bad, d_own, d_shared, d_h2r, d_h2l);
+    HM_HIP_CHECK(hipGetLastError());
+    return HM_OK;
+  });
 }
 
 // one lane per proof
@@ -413,17 +412,17 @@ int verify_transcript_run(DeviceCtx& ctx, const uint32_t* d_proofs, size_t n_pro
                           const uint32_t* schedule, size_t n_pairs, uint32_t* d_bad, uint32_t* d_records, uint32_t record_elems,
                           hipStream_t stream) {
   if (const char* why = tr_schedule_problem(schedule, n_pairs, slots, record_elems)) return hm_fail(HM_ERR_BAD_ARG, why);
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  uint32_t* d_sched = (uint32_t*)slot->args.ensure(n_pairs * 8);
-  if (!d_sched) return hm_fail(HM_ERR_HIP, "verify transcript: schedule allocation failed");
-  // pageable source: the runtime has taken its copy of the schedule when this returns (as the terms plan)
-  HM_HIP_CHECK(hipMemcpyAsync(d_sched, schedule, n_pairs * 8, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(verify_transcript_kernel, dim3((uint32_t)((n_proofs + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, stream, d_proofs,
-                     (uint32_t)n_proofs, d_slot_table, slots, n_points, d_ybytes, d_preamble, d_counts, stride, (const uint32_t*)d_sched,
-                     (uint32_t)n_pairs, d_bad, d_records, record_elems);
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
+  return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
+    uint32_t* d_sched = (uint32_t*)aux_buffer(slot, AuxBuf::args, n_pairs * 8, "verify transcript");
+    if (!d_sched) return HM_ERR_HIP;
+    // pageable source: the runtime has taken its copy of the schedule when this returns (as the terms plan)
+    HM_HIP_CHECK(hipMemcpyAsync(d_sched, schedule, n_pairs * 8, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(verify_transcript_kernel, dim3((uint32_t)((n_proofs + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, stream, d_proofs,
+                       (uint32_t)n_proofs, d_slot_table, slots, n_points, d_ybytes, d_preamble, d_counts, stride, (const uint32_t*)d_sched,
+                       (uint32_t)n_pairs, d_bad, d_records, record_elems);
+    HM_HIP_CHECK(hipGetLastError());
+    return HM_OK;
+  });
 }
 
 // ---- the EVM encoding: Keccak-256, the uncompressed read, the transcripts ---------------------
@@ -489,17 +488,17 @@ int verify_transcript_evm_run(DeviceCtx& ctx, const uint32_t* d_proofs, size_t n
                               const uint32_t* d_counts, uint32_t stride, const uint32_t* schedule, size_t n_pairs, uint32_t* d_bad,
                               uint32_t* d_records, uint32_t record_elems, hipStream_t stream) {
   if (const char* why = tr_schedule_problem(schedule, n_pairs, slots, record_elems)) return hm_fail(HM_ERR_BAD_ARG, why);
-  AuxSlot* slot = aux_acquire(ctx, stream);
-  if (!slot) return HM_ERR_HIP;
-  uint32_t* d_sched = (uint32_t*)slot->args.ensure(n_pairs * 8);
-  if (!d_sched) return hm_fail(HM_ERR_HIP, "verify transcript: schedule allocation failed");
-  // pageable source: the runtime has taken its copy of the schedule when this returns (as the terms plan)
-  HM_HIP_CHECK(hipMemcpyAsync(d_sched, schedule, n_pairs * 8, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(verify_transcript_evm_kernel, dim3((uint32_t)((n_proofs + KC_THREADS - 1) / KC_THREADS)), dim3(KC_THREADS), 0, stream,
-                     d_proofs, (uint32_t)n_proofs, slots, d_preamble, d_counts, stride, (const uint32_t*)d_sched, (uint32_t)n_pairs, d_bad,
-                     d_records, record_elems);
-  HM_HIP_CHECK(hipGetLastError());
-  return aux_release(ctx, slot, stream);
+  return aux_scope(ctx, stream, [&](AuxSlot& slot) -> int {
+    uint32_t* d_sched = (uint32_t*)aux_buffer(slot, AuxBuf::args, n_pairs * 8, "verify transcript");
+    if (!d_sched) return HM_ERR_HIP;
+    // pageable source: the runtime has taken its copy of the schedule when this returns (as the terms plan)
+    HM_HIP_CHECK(hipMemcpyAsync(d_sched, schedule, n_pairs * 8, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(verify_transcript_evm_kernel, dim3((uint32_t)((n_proofs + KC_THREADS - 1) / KC_THREADS)), dim3(KC_THREADS), 0, stream,
+                       d_proofs, (uint32_t)n_proofs, slots, d_preamble, d_counts, stride, (const uint32_t*)d_sched, (uint32_t)n_pairs, d_bad,
+                       d_records, record_elems);
+    HM_HIP_CHECK(hipGetLastError());
+    return HM_OK;
+  });
 }
 
 }  // namespace hm

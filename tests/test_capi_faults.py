@@ -283,3 +283,326 @@ def test_an_exhausted_device_gets_the_librarys_caches_back(fi):
     again = a.copy()
     assert fi.hm_ntt_bn256_fr(_u64(again), _u64(fr_words(d.omega)), d.k) == 0 and np.array_equal(again, want)      # rebuilt on demand
     assert fi.hm_get_stats(ctypes.byref(st)) == 0 and st.ntt_tables == 1
+
+
+# ---- per-call device scratch: every request can fail, and the call after it is right -----------------------------------------------------
+# The drivers get their scratch in two ways only (csrc/hm_internal.h): a buffer of the stream's slot inside aux_scope, or stream-ordered
+# memory inside stream_scratch.  Both pass the fault point "scratch_alloc" on EVERY request, so arming it at after = 0, 1, ... until the
+# call succeeds enumerates the requests of a call.  Each entry below states that number as a literal, and `clean`: for how many of the
+# leading values of `after` the pattern-filled outputs must come back untouched.  It equals `requests` but for the permutation assembly,
+# which writes the identity permutation before it asks for its keys (clean = 0): no other driver launches a kernel that writes an output
+# before its last request (the set quotient's and logUp's second requests follow launches that write scratch only).
+HM_ERR_HIP = -3
+HM_AUX_SLOTS = 4                                          # csrc/hm_internal.h
+PO_COLS_MAX, EV_MAX_Q = 16, 48                            # csrc/polyops.hip, csrc/poly.hip
+PATTERN = 0x5A5A5A5A5A5A5A5A
+u32p = ctypes.POINTER(ctypes.c_uint32)
+
+
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _ptrs(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _sp(stream):
+    return ctypes.c_void_p(stream.cuda_stream if stream is not None else None)
+
+
+def _dev(words):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(words).view(np.int64)).cuda()
+
+
+def _fr(values):
+    from halo2_experiments_amd.bn256 import fr_array
+    return fr_array(values)
+
+
+class _Entry:
+    """One call of the test build: ``call(stream)`` -> return code; ``outs``: the device tensors and host arrays it writes, filled with
+    ``fill`` (a tensor or array each; None: the pattern) before every call."""
+
+    def __init__(self, name, requests, call, outs, fill=None, clean=None):
+        self.name, self.requests, self.clean, self.call, self.outs = name, requests, requests if clean is None else clean, call, outs
+        self.fill = fill or [None] * len(outs)
+
+    def reset(self):
+        for o, f in zip(self.outs, self.fill):
+            if isinstance(o, np.ndarray):
+                o[...] = PATTERN if f is None else f
+            elif f is None:
+                o.fill_(PATTERN if o.element_size() == 8 else 0x5A5A5A5A)
+            else:
+                o.copy_(f)
+
+    def read(self):
+        return [o.copy() if isinstance(o, np.ndarray) else o.cpu().numpy().copy() for o in self.outs]
+
+
+def _same(a, b):
+    return len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def _run(fi, e, stream=None, arm=None):
+    import torch
+    e.reset()
+    torch.cuda.synchronize()
+    if arm is not None:
+        fi.hm_test_arm_fault(b"scratch_alloc", arm)
+    try:
+        rc = e.call(stream)
+    finally:
+        fi.hm_test_arm_fault(None, 0)
+    msg = fi.hm_last_error()
+    torch.cuda.synchronize()
+    return rc, msg, e.read()
+
+
+def _sweep(fi, e, second):
+    import torch
+    e.reset()
+    torch.cuda.synchronize()
+    blank = e.read()
+    rc, msg, want = _run(fi, e)
+    assert rc == 0, (e.name, msg)
+    assert not _same(want, blank) or not e.outs, e.name          # the call does write what the pattern check looks at
+    k = 0
+    while True:
+        rc, msg, got = _run(fi, e, arm=k)
+        if rc == 0:                                                # the armed passage was not reached: k requests in all
+            assert _same(got, want), (e.name, k)
+            break
+        assert rc == HM_ERR_HIP and b"scratch allocation failed" in msg, (e.name, k, rc, msg)
+        if k < e.clean:
+            assert _same(got, blank), (e.name, k)
+        for stream in (None, second):
+            rc, msg, got = _run(fi, e, stream)
+            assert rc == 0 and _same(got, want), (e.name, k, stream, msg)
+        k += 1
+        assert k <= 8, e.name
+    assert k == e.requests, (e.name, k)
+
+
+def _code(fn, *args):
+    """a wrapper of the Python layer as a return code"""
+    try:
+        fn(*args)
+    except _lib.Halo2Mi355xError as err:
+        return err.code
+    return 0
+
+
+def _poly_entries(fi):
+    import torch
+    new = lambda *shape: torch.empty(shape, dtype=torch.int64, device="cuda")
+    out = []
+    for count in (1, PO_COLS_MAX + 1):                        # one column; a second group of the loop
+        polys, z, qs = [_rand_fr(5, 9400 + i) for i in range(count)], _fr(list(range(3, 3 + count))), [new(5, 4) for _ in range(count)]
+        out.append(_Entry(f"kate x{count}", 1, lambda s, a=(polys, z, qs, count): fi.hm_kate_division_batch_bn256_fr_dev(
+            _ptrs(a[0]), 5, _u64(a[1]), _ptrs(a[2]), a[3], _sp(s)), qs))
+    count = PO_COLS_MAX + 1
+    fs, start, zs = [_rand_fr(5, 9420 + i) for i in range(count)], _fr(7), [new(5, 4) for _ in range(count)]
+    out.append(_Entry("grand product, chained", 1, lambda s: fi.hm_fr_grand_product_batch_dev(_ptrs(fs), 5, _u64(start), 3, _ptrs(zs), count,
+                                                                                             _sp(s)), zs))
+    a, b, dot = _rand_fr(3, 9440), _rand_fr(3, 9441), np.zeros(4, dtype=np.uint64)
+    out.append(_Entry("dot", 1, lambda s: fi.hm_fr_dot_bn256_dev(_vp(a), _vp(b), 3, _u64(dot), _sp(s)), [dot]))
+    q = EV_MAX_Q + 1                                           # a second launch of the loop
+    poly, idx, pts, evals = _rand_fr(17, 9442), np.zeros(q, dtype=np.uint32), _fr(list(range(2, 2 + q))), np.zeros((q, 4), dtype=np.uint64)
+    out.append(_Entry("eval_polynomial", 1, lambda s: fi.hm_eval_polynomial_bn256_fr_dev(_vp(poly), 17, idx.ctypes.data_as(u32p), _u64(pts), q,
+                                                                                        _u64(evals), _sp(s)), [evals]))
+    # SHPLONK set quotient, t = 2 points, n = 8, two polynomials per proof: the single form, and the batch form with 2 proofs (its own
+    # workspace, then the batched linear combination's table)
+    ps_, w, x, sc = [_rand_fr(8, 9450 + i) for i in range(4)], _fr([1, 2, 3, 4]), _fr([5, 7, 11, 13]), _fr([3, 9])
+    h1, h2 = new(8, 4), [new(8, 4), new(8, 4)]
+    out.append(_Entry("set quotient", 1, lambda s: fi.hm_shplonk_set_quotient_bn256_fr_dev(_ptrs(ps_[:2]), _u64(w), 2, 8, _u64(x), 2, _u64(sc),
+                                                                                          _vp(h1), 0, _sp(s)), [h1]))
+    out.append(_Entry("set quotient batch", 2, lambda s: fi.hm_shplonk_set_quotient_batch_bn256_fr_dev(_ptrs(ps_), _u64(w), 2, 8, _u64(x), 2,
+                                                                                                      _u64(sc), _ptrs(h2), 0, 2, _sp(s)), h2))
+    terms, c6, lc = [_rand_fr(8, 9460 + i) for i in range(6)], _fr(list(range(21, 27))), [new(8, 4), new(8, 4)]
+    out.append(_Entry("linear combination batch", 1, lambda s: fi.hm_fr_linear_combination_batch_dev(_ptrs(terms), _u64(c6), 3, 8, _ptrs(lc), 2,
+                                                                                                    _sp(s)), lc))
+    cells = torch.tensor([5, 0, 15, 2, 9, 1, 7, 3, 8, 4, 10, 6, 12, 14, 13, 11], dtype=torch.int32, device="cuda")
+    om, de, sigma = _fr(_omega(3)), _fr(7), new(16, 4)
+    out.append(_Entry("permutation columns", 1, lambda s: fi.hm_permutation_columns_bn256_fr_dev(ctypes.cast(_vp(cells), u32p), 2, 3, _u64(om),
+                                                                                                _u64(de), _vp(sigma), _sp(s)), [sigma]))
+    return out
+
+
+def _omega(k):
+    from oracle import bn256_ref
+    return bn256_ref.fr_omega(k)
+
+
+def _lookup_entries(fi):
+    import torch
+    new = lambda *shape: torch.empty(shape, dtype=torch.int64, device="cuda")
+    out = []
+    table = _rand_fr(5, 9500)
+    inp = table[torch.tensor([0, 0, 2, 4, 4], device="cuda")].contiguous()
+    pi, pt, miss = new(5, 4), new(5, 4), (ctypes.c_int * 1)()
+    out.append(_Entry("lookup permute", 1, lambda s: fi.hm_lookup_permute_batch_bn256_fr_dev(_ptrs([inp]), _ptrs([table]), 1, 5, _ptrs([pi]),
+                                                                                            _ptrs([pt]), miss, _sp(s)), [pi, pt]))
+    pick = torch.tensor([7, 7, 0, 3, 3, 3, 1, 6], device="cuda")
+    for name, tab in (("small keys", _dev(_fr(list(range(10, 18))))), ("general keys", _rand_fr(8, 9510))):   # value bins / sorted records
+        col, m, miss2, counts = tab[pick].contiguous(), new(8, 4), (ctypes.c_int * 1)(), (ctypes.c_uint32 * 1)(1)
+        out.append(_Entry(f"logup multiplicities, {name}", 2, lambda s, a=(tab, col, m, miss2, counts): fi.hm_logup_multiplicities_bn256_fr_dev(
+            _ptrs([a[0]]), _ptrs([a[1]]), a[4], 1, 8, _ptrs([a[2]]), a[3], _sp(s)), [m]))
+    terms, sums = _rand_fr(8, 9520), new(8, 4)
+    out.append(_Entry("grand sum", 1, lambda s: fi.hm_fr_grand_sum_batch_dev(_ptrs([terms]), 8, _ptrs([sums]), 1, _sp(s)), [sums]))
+    return out
+
+
+def _g1_entries(fi):
+    import torch
+    from halo2_experiments_amd.bn256 import g1_words
+    new = lambda *shape: torch.empty(shape, dtype=torch.int64, device="cuda")
+    out = []
+    gen, t3, p3 = g1_words((1, 2)), _rand_fr(3, 9600), new(3, 8)
+    mul = lambda s, t=t3, p=p3, n=3: fi.hm_g1_fixed_base_mul_dev(_vp(t), n, _u64(gen), _vp(p), _sp(s))
+    out.append(_Entry("fixed-base mul", 1, mul, [p3]))
+    t4, p4 = _rand_fr(4, 9601), new(4, 8)
+    assert mul(None, t4, p4, 4) == 0 and mul(None) == 0
+    torch.cuda.synchronize()
+    points, pts3, om = p4.clone(), p3.clone(), _fr(_omega(2))
+    out.append(_Entry("g1 fft", 1, lambda s: fi.hm_g1_fft_bn256_dev(_vp(p4), _u64(om), 2, None, _sp(s)), [p4], [points]))      # in place
+    table, coeffs, proofs = new(8, 8), _rand_fr(4, 9602), new(4, 8)
+    assert fi.hm_kzg_open_table_bn256_dev(_vp(points), 2, _vp(table), None) == 0
+    out.append(_Entry("open_all", 1, lambda s: fi.hm_kzg_open_all_bn256_dev(_vp(table), _vp(coeffs), 2, 1, _vp(proofs), _sp(s)), [proofs]))
+    packed, back, first = new(3, 4), new(3, 8), np.zeros(1, dtype=np.uint64)
+    assert fi.hm_g1_compress_bn256_dev(_vp(pts3), 3, _vp(packed), None) == 0
+    torch.cuda.synchronize()
+    # (*out_first_invalid is set to n before anything else, so it is no pattern-checked output: a success must leave n there)
+    def verdict(rc):
+        assert rc != 0 or first[0] == 3
+        return rc
+    out.append(_Entry("decompress", 1, lambda s: verdict(fi.hm_g1_decompress_bn256_dev(_vp(packed), 3, _vp(back), _u64(first), _sp(s))), [back]))
+    out.append(_Entry("check", 1, lambda s: verdict(fi.hm_g1_check_bn256_dev(_vp(pts3), 3, _u64(first), _sp(s))), []))
+    return out
+
+
+def _hash_entries(fi, spec_handle):
+    import torch
+    from halo2_experiments_amd._marshal import _dev_ptr
+    new = lambda *shape, dtype=torch.int64: torch.empty(shape, dtype=dtype, device="cuda")
+    out = []
+    values, perm = _rand_fr(5, 9700), new(5)
+    out.append(_Entry("argsort", 1, lambda s: fi.hm_fr_argsort_bn256_dev(_vp(values), 5, _dev_ptr(perm), _sp(s)), [perm]))
+    copies = torch.tensor([[0, 9], [9, 3], [4, 12], [15, 1]], dtype=torch.int32, device="cuda")      # cells of 2 columns of 2^3 rows
+    cells = new(16, dtype=torch.int32)
+    out.append(_Entry("permutation assembly", 1, lambda s: fi.hm_permutation_assemble_dev(_dev_ptr(copies, u32p), 4, 2, 3, _dev_ptr(cells, u32p),
+                                                                                         None, _sp(s)), [cells], clean=0))
+    # SafeAccumulator: one user, 4 rows, 4 limbs of 4 bits at k = 5 (the shape of smoke())
+    vals, init = _dev(_fr([1, 3, 2, 5])), torch.tensor([[0, 0, 14, 13]], dtype=torch.int64, device="cuda")
+    adv, fin, over = new(10, 32, 4), new(1, 4), new(1, dtype=torch.int32)
+    out.append(_Entry("accumulator witness", 1, lambda s: fi.hm_accumulator_witness_bn256_fr_dev(
+        4, 4, 5, 1, 4, _vp(vals), _dev_ptr(init), _vp(adv), _dev_ptr(fin), _dev_ptr(over, u32p), _sp(s)), [adv, fin, over]))
+    # a Merkle sum tree of depth 2: 4 leaves of (hash, balance), 7 nodes
+    leaves, nodes = _rand_fr(8, 9710), new(7, 2, 4)
+    assert fi.hm_merkle_sum_tree_build_dev(spec_handle, _vp(leaves), 2, _vp(nodes), None) == 0
+    torch.cuda.synchronize()
+    built, idx, leaf = nodes.clone(), torch.tensor([1], dtype=torch.int64, device="cuda"), _rand_fr(2, 9711)
+    out.append(_Entry("merkle update", 1, lambda s: fi.hm_merkle_sum_tree_update_dev(spec_handle, 2, _vp(nodes), _dev_ptr(idx), _vp(leaf), 1, None,
+                                                                                    _sp(s)), [nodes], [built]))           # in place
+    sibs, roots = new(2, 2, 4), new(1, 2, 4)
+    assert fi.hm_merkle_paths_dev(_vp(built), 2, 2, _dev_ptr(idx), 1, _vp(sibs), None) == 0
+    torch.cuda.synchronize()
+    out.append(_Entry("merkle roots", 0, lambda s: fi.hm_merkle_roots_bn256_dev(spec_handle, 2, 1, _vp(leaves[2:4]), _vp(sibs), _dev_ptr(idx),
+                                                                               _vp(roots), _sp(s)), [roots]))           # no scratch of its own
+    return out
+
+
+def _verifier_entries(fi, keep):
+    """The Blake2b and the Keccak transcript and one terms call, on the recorded SHPLONK proofs of the Poseidon system (tests/golden/
+    gwc_proofs_poseidon.npz, the smallest recorded).  The caller has routed the Python layer to the test build."""
+    import torch
+    import halo2_experiments_amd as h
+    from halo2_experiments_amd import device_transcript
+    import gwc_cases as gc
+    rec = gc.recorded("poseidon")
+    out = []
+    for enc in gc.ENCODINGS:
+        bv = h.BatchVerifier(None, rec["vk"], seed=5, transcript="device", encoding=enc)
+        keep.append(bv)
+        bv.add_proof(rec["instance"], rec["proofs"][("shplonk", enc)])
+        st = bv._prepare()
+        assert st["bad"] == [False]
+        n_ch = st["d_records"].shape[1] - 1
+        fresh = st["d_records"].clone()
+        fresh[:, :n_ch] = PATTERN                               # the challenges; r_b behind them stays
+        records, flags = fresh.clone(), torch.zeros(1, dtype=torch.int32, device="cuda")
+
+        def transcript(s, bv=bv, st=st, records=records, flags=flags):
+            with torch.cuda.stream(s):
+                return _code(device_transcript.challenges, bv.layout, bv._digest, bv._preamble_instances(), st["d_proofs"], st["d_ybytes"], flags,
+                             records, st["preamble"], st["d_table"])
+        out.append(_Entry(f"transcript, {enc}", 1, transcript, [records, flags], [fresh, torch.zeros_like(flags)]))
+        if enc == "halo2":
+            outs = [torch.empty_like(st[key]) for key in ("d_own", "d_shared", "d_h2_r", "d_h2_l")]
+            flags2 = torch.zeros(1, dtype=torch.int32, device="cuda")
+            terms = lambda s, bv=bv, st=st: _code(bv._queue_terms, st["plan"], 1, st["d_records"], st["d_scalars"], st["d_inst"], flags2, *outs,
+                                                  _sp(s))
+            out.append(_Entry("terms", 2, terms, outs))
+    return out
+
+
+@pytest.fixture()
+def fi_spec(fi):
+    """a width-5 Poseidon spec of the test build (its own contexts and handles)"""
+    from halo2_experiments_amd import poseidon as P
+    import poseidon_checker as chk
+    rc, mds, _ = P.default_spec(5).constants()
+    rcw, mdsw = chk.to_words([v for r in rc for v in r]), chk.to_words([v for r in mds for v in r])
+    handle = ctypes.c_uint64(0)
+    assert fi.hm_poseidon_create(5, 4, 8, 56, _u64(rcw), _u64(mdsw), ctypes.byref(handle)) == 0
+    yield handle
+    assert fi.hm_poseidon_destroy(handle) == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("group", ["poly", "lookup", "g1", "hash", "verifier"])
+def test_every_scratch_request_can_fail_and_the_next_call_is_right(fi, fi_spec, group, monkeypatch):
+    import torch
+    second = torch.cuda.Stream()
+    keep = []
+    if group == "verifier":
+        monkeypatch.setattr(_lib, "_lib", fi)                  # BatchVerifier and the transcripts' wrapper call the test build
+    try:
+        entries = {"poly": _poly_entries, "lookup": _lookup_entries, "g1": _g1_entries}[group](fi) if group in ("poly", "lookup", "g1") \
+            else _hash_entries(fi, fi_spec) if group == "hash" else _verifier_entries(fi, keep)
+        torch.cuda.synchronize()
+        for e in entries:
+            _sweep(fi, e, second)
+    finally:
+        for bv in keep:
+            bv.close()
+
+
+@pytest.mark.gpu
+def test_slot_pressure_after_a_failure(fi):
+    """A failed call leaves its slot with a recorded event: more streams than slots, back to back, each get buffers nobody is writing.
+    n = 1025 gives two workgroups per column, so the join reads what another workgroup left in the slot's buffer."""
+    import torch
+    n = 1025
+    factors, start = _rand_fr(n, 9800), _fr(1)
+    product = lambda s, out: fi.hm_fr_grand_product_dev(_vp(factors), n, _u64(start), _vp(out), _sp(s))
+    new = lambda: torch.zeros((n, 4), dtype=torch.int64, device="cuda")
+    want = new()
+    assert product(None, want) == 0
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream() for _ in range(HM_AUX_SLOTS + 1)]
+    torch.cuda.synchronize()
+    fi.hm_test_arm_fault(b"scratch_alloc", 0)
+    try:
+        assert product(streams[0], new()) == HM_ERR_HIP and b"scratch allocation failed" in fi.hm_last_error()
+    finally:
+        fi.hm_test_arm_fault(None, 0)
+    outs = [new() for _ in streams]
+    torch.cuda.synchronize()
+    for s, out in zip(streams, outs):                          # no wait between them
+        assert product(s, out) == 0
+    torch.cuda.synchronize()
+    for out in outs:
+        assert torch.equal(out, want)
